@@ -13,10 +13,15 @@ one pass of up to 32*G clips (the autoregressive chain is latency-bound below ~6
 streams each stage's weights once instead of 8 times), on S HIP streams so that the conv stacks of one pass overlap the
 chain of another.  A clip's result does not depend on how
 its batch was grouped (bit-identical; tests/test_gpu_parity.py::test_golden_clips_inside_baseline_batches).  Every
-step's batch is completely processed inside the timed region.  The strict one-batch-at-a-time figure and the round-1
-mode (4 independent batches on 4 streams, no coalescing) are measured beside it (`modes`).
+step's batch is completely processed inside the timed region.  A plain run does only what the headline needs: set up,
+warm up, time the --steps steps once, write the last step's outputs (--dump-outputs DIR), print the line.  With --full the
+line also carries everything measured or checked beside it: the selfcheck re-run, the strict one-batch-at-a-time figure, the
+round-1 mode (4 independent batches on 4 streams, no coalescing) and the other modes (`modes`), rooflines, the face /
+front-end / whole-body legs, the CPU baseline, and the median of --repeats (default 3) timed regions.
 
-    python bench.py                          # N=1, configs[1]
+    python bench.py                          # N=1, configs[1], headline only
+    python bench.py --full                   # ... and every leg beside it
+    python bench.py --dump-outputs DIR       # ... and DIR/<name>.npy of what the last timed step computed
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
     ... bench.py --config whole_body         # BASELINE configs[4]: 128 clips per rank, body_pixel + face -> 265-d rows
@@ -662,6 +667,9 @@ def main_whole_body(a, world, rank, local, dist):
         "per_gpu_frames_per_s": frames / dt / world, "gathered_shape": list(allrows.shape),
     }
     if rank == 0:
+        if a.dump_outputs:
+            # this rank's (n_local, 300, 265) rows of the last step; past 48 MB only its first clips (128 per rank: 40.7 MB)
+            dump_outputs(a.dump_outputs, {"rows": rows[:max(1, (48 << 20) // (rows[0].numel() * 4))]})
         print(json.dumps(out), flush=True)
 
 
@@ -727,8 +735,18 @@ class BodyJob:
                 "parallelism": f"clip-sharded x{self.world}; per GPU the queued batches run as passes of up to {G} batches "
                                f"({B * G} clips), {S} passes in flight (one HIP stream each)"}
 
-    def selfcheck(self):
-        """Outside the timed region: the LAST timed pass's outputs against the same clips run alone, one 32-clip batch on one
+    def last_step_outputs(self, steps):
+        """What the timed path computed in its last step (step `steps` - 1, the last batch of the last pass), as its caller
+        receives it: generated poses (32, 300, 129), generated codes and the VQ-encode codes of the GT poses (32, 75, 2) each."""
+        ks, si = self.eng.last_group
+        j = ks.index(steps - 1)
+        codes, poses = self.eng.last
+        sl = slice(j * self.B, (j + 1) * self.B)
+        return {"poses": poses[sl], "codes": codes[sl], "vq_encode_codes": self.eng.gt_codes[si][sl]}
+
+    def selfcheck(self, rerun=True):
+        """Outside the timed region: no hipGraph may have been captured inside a timed region (every run).  With `rerun`
+        (--full): the LAST timed pass's outputs against the same clips run alone, one 32-clip batch on one
         stream (the strict mode) — generated codes, poses and the VQ-encode codes must be bit-equal (a clip's result does not
         depend on how its batch was grouped), so a skipped or mis-ordered launch inside the timed region cannot pass as a
         better number.  Raises on a mismatch: a wrong result must not leave a bench line behind."""
@@ -736,6 +754,8 @@ class BodyJob:
         caps = getattr(self, "captures_in_regions", [])
         if any(caps):
             raise RuntimeError(f"bench: hipGraphs were captured INSIDE the timed regions ({caps}): warm() did not cover a pass shape")
+        if not rerun:
+            return {"graph_captures_in_timed_regions": caps}
         ks, si = eng.last_group
         codes, poses = eng.last
         gtc = eng.gt_codes[si][:B * len(ks)]
@@ -892,14 +912,15 @@ def run_contract(job, dist, world, rank, steps, warmup, clock=time.perf_counter,
     return runs[mid][0], runs[mid][1], runs[mid][2]
 
 
-def finish(job, dist, world, rank, steps, warmup, dt, info, emit=print, collectives=None):
+def finish(job, dist, world, rank, steps, warmup, dt, info, emit=print, collectives=None, full=True):
     """After the timed region: every rank checks what it timed (local work), the ranks leave the process group TOGETHER, and only
     then does rank 0 run its extra legs and print the one JSON line.  Ranks != 0 run nothing else.  A rank whose check fails does
-    not leave the others waiting in a barrier: the failure is all-reduced first, every rank leaves the group, every rank raises."""
+    not leave the others waiting in a barrier: the failure is all-reduced first, every rank leaves the group, every rank raises.
+    `full=False` (a plain run): the check skips its re-run of the last pass and rank 0 runs no extra legs."""
     coll = world > 1 if collectives is None else collectives
     failure = None
     try:
-        check = job.selfcheck()
+        check = job.selfcheck() if full else job.selfcheck(rerun=False)
     except Exception as e:                      # noqa: BLE001 — re-raised below, after the group has been left together
         failure, check = e, None
     if coll:
@@ -941,9 +962,24 @@ def finish(job, dist, world, rank, steps, warmup, dt, info, emit=print, collecti
     # whole path against the fp32 MFMA roof: algorithmic work of configs[1] (64.25 MFLOP per generated frame)
     ach = ALG_FLOP_PER_FRAME * frames / dt / world / 1e12
     out["whole_path"] = {"algorithmic_TFLOPs_per_gpu": ach, "frac_of_fp32_mfma_peak": ach / PEAK_FP32_MFMA_TFLOPS}
-    job.extras(out)
+    if full:
+        job.extras(out)
     emit(json.dumps(out))
     return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array of the last timed step, float32 as computed (the integer code grids as
+    float64, exact), so that two builds run with the same arguments (same seeded inputs) can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        x = x.astype(np.float64) if x.dtype.kind in "iub" else x.astype(np.float32 if x.dtype != np.float64 else np.float64)
+        total += x.nbytes
+        if total > 64 << 20:
+            raise RuntimeError(f"--dump-outputs: {total} bytes exceed the 64 MB bound")
+        np.save(os.path.join(d, name + ".npy"), x)
 
 
 def free_port():
@@ -1012,9 +1048,17 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-face", action="store_true")
     ap.add_argument("--no-modes", action="store_true")
-    ap.add_argument("--repeats", type=int, default=int(os.environ.get("TS_BENCH_REPEATS", "3")),
-                    help="timed regions of exactly --steps steps each, back to back in the same warm state; the line reports their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each, back to back in the same warm state; the line reports their median "
+                         "(default: TS_BENCH_REPEATS, else 3 with --full and 1 without)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: selfcheck re-run, modes, rooflines, face / front-end / whole-body legs, "
+                         "CPU baseline (each can still be left out with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = int(os.environ.get("TS_BENCH_REPEATS", "3" if a.full else "1"))
 
     if needs_spawn(os.environ, a.gpus):
         sys.exit(spawn_ranks(a.gpus, os.path.abspath(__file__), sys.argv[1:]))
@@ -1044,7 +1088,11 @@ def main():
     job = BodyJob(a, world, rank, local)
     job.host_affinity = affinity
     dt, _, info = run_contract(job, dist, world, rank, a.steps, a.warmup, collectives=coll, repeats=a.repeats)
-    finish(job, dist, world, rank, a.steps, a.warmup, dt, info, emit=lambda line: print(line, flush=True), collectives=coll)
+    if a.dump_outputs and rank == 0:
+        job.sync()
+        dump_outputs(a.dump_outputs, job.last_step_outputs(a.steps))
+    finish(job, dist, world, rank, a.steps, a.warmup, dt, info, emit=lambda line: print(line, flush=True), collectives=coll,
+           full=a.full)
 
 
 if __name__ == "__main__":

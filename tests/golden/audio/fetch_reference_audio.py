@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Copies the reference's own demo recordings — format fixtures it ships under demo_audio/ — into tests/golden/audio/ (git-ignored:
-they are the reference's files, not this repository's; `__graft_entry__.build()` runs this where /root/reference exists and the
-copies travel to the GPU box with the snapshot, like oracle/_ref) so that the GPU box, which has no /root/reference, can run the
-wav-in path on real speech: style.wav (22 kHz stereo int16, exactly 10.0 s),
+"""Copies the reference's own demo recordings — format fixtures it ships under demo_audio/ — into tests/golden/audio/, where they
+are committed as test fixtures, and writes next to them the 16 kHz samples the face path reads (`*.wav16.npy`, git-ignored side
+files; the tests regenerate them with the host twin when they are absent): style.wav (22 kHz stereo int16, exactly 10.0 s),
 1st-page.wav (16 kHz mono, 12.816 s), french.wav (24 kHz mono, 9.6125 s).  Writes audio_manifest.json with their sha256, sample
 rate, shape and the frame counts SURVEY.md §8(c) documents for them (demo/*/*.npy hold 300 / 384 / 288 rows of 265 values).
+A maintainer's tool: neither the build nor the tests run it.
 
-    python tests/golden/audio/fetch_reference_audio.py [/root/reference]
+    python tests/golden/audio/fetch_reference_audio.py REFERENCE_TREE
 """
 import hashlib
 import json

@@ -59,8 +59,8 @@ class StubJob:
     def describe(self):
         return {"workload": "stub"}
 
-    def selfcheck(self):
-        self._say("selfcheck")
+    def selfcheck(self, rerun=True):
+        self._say("selfcheck" if rerun else "selfcheck without re-run")
         if self.rank == self.fail_rank:
             raise RuntimeError(f"selfcheck: rank {self.rank} found a difference")
         return {"selfcheck": "ok"}
@@ -238,3 +238,32 @@ def test_bench_spawns_its_own_ranks_without_a_launcher(tmp_path):
     bad = tmp_path / "bad.py"
     bad.write_text("import sys; sys.exit(3)\n")
     assert bench.spawn_ranks(2, str(bad), [], env=env, timeout=240) != 0
+
+
+def test_plain_run_finishes_without_extra_legs(tmp_path):
+    """A plain bench run (no --full): `finish(full=False)` checks without re-running, runs no extra leg, and the line still carries
+    the headline fields with `ms_per_step` = the timed region / steps."""
+    import bench
+    job = StubJob(1, 0, str(tmp_path / "log.jsonl"))
+    dt, _, info = bench.run_contract(job, dist, 1, 0, 4, 1)
+    lines = []
+    bench.finish(job, dist, 1, 0, 4, 1, dt, info, emit=lines.append, full=False)
+    what = [json.loads(l)["what"] for l in open(tmp_path / "log.jsonl")]
+    assert what == ["warm 4", "run_steps 1", "run_steps 4", "selfcheck without re-run"], what
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert "roofline" not in line and line["steps"] == 4
+    assert abs(line["ms_per_step"] - dt / 4 * 1e3) < 1e-9
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one <name>.npy per array, float32 kept as is, integer code grids as exact float64."""
+    import numpy as np
+    import bench
+    poses = torch.randn(2, 3, 4)
+    codes = torch.tensor([[0, 2047], [5, 3]], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "out"), {"poses": poses, "codes": codes})
+    p, c = np.load(tmp_path / "out" / "poses.npy"), np.load(tmp_path / "out" / "codes.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, poses.numpy())
+    assert c.dtype == np.float64 and np.array_equal(c, codes.numpy().astype(np.float64))

@@ -36,17 +36,14 @@ def test_linear_interpolation_endpoints():
 
 def test_face_generator_on_a_recording(golden):
     """Real speech (tests/golden/real_audio_face.npz: the reference wrapper on its own demo recordings): french.wav, 9.6 s at
-    16 kHz as the host kaiser_best twin produces it (tests/golden/audio/french.wav.wav16.npy, a build-time file; skipped without it)."""
+    16 kHz as the host kaiser_best twin produces it from the committed recording (tests/golden/audio/french.wav); the samples
+    must hash to the golden's input."""
     import hashlib
     import os
-    import pytest
+    from talkshow_amd import frontend as fe
     g = golden("real_audio_face")
-    side = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "audio", "french.wav.wav16.npy")
-    if not os.path.exists(side):
-        pytest.skip("tests/golden/audio/french.wav.wav16.npy is absent (__graft_entry__.build() writes it where /root/reference exists)")
-    wav = np.load(side)
-    if hashlib.sha256(wav.tobytes()).hexdigest() != str(g["french_wav16_sha256"]):
-        pytest.skip("the side file is not the golden's input")
+    wav = fe.get_wav16(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "audio", "french.wav"), host=True)[:, 0]
+    assert hashlib.sha256(wav.tobytes()).hexdigest() == str(g["french_wav16_sha256"]), "the host twin's samples are not the golden's input"
     N, frame, spk = (int(v) for v in g["french_n"])
     sd = synth.face_state_dict(seed=7)
     hs = FO.wav2vec2_forward(wav[None], sd, frame)

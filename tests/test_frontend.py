@@ -14,7 +14,7 @@ import pytest
 
 from talkshow_amd import frontend as fe
 
-REF_AUDIO = "/root/reference/demo_audio"
+REF_AUDIO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "audio")   # the reference's demo recordings
 
 
 def _mfcc_f64(wave, sr, n_fft=2048, hop=734, n_mels=256, n_mfcc=64):
@@ -68,7 +68,6 @@ def test_length_rule_matches_survey():
         assert fe.mfcc(np.zeros(n, np.float32) + 1e-3, 22000).shape[1] == n // 734 + 1
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_AUDIO, "style.wav")), reason="reference demo audio not present")
 def test_reference_demo_wavs_give_the_documented_frame_counts():
     # style.wav is 22 kHz stereo, exactly 10.0 s -> 300 frames (+1); 1st-page.wav 16 kHz, 12.816 s -> 385
     f = fe.get_mfcc_ta(os.path.join(REF_AUDIO, "style.wav"), sr=22000, fps=30)

@@ -45,9 +45,7 @@ def _tag(name):
 
 def _need_recording(name):
     p = os.path.join(AUDIO, name)
-    if not os.path.exists(p):
-        pytest.skip("tests/golden/audio/ holds no recordings (python tests/golden/audio/fetch_reference_audio.py where /root/reference "
-                    "exists; __graft_entry__.build() does it)")
+    assert os.path.exists(p), f"{p}: the committed recording is missing"
     return p
 
 
@@ -182,8 +180,9 @@ def test_stochastic_decode_on_a_recording_vs_oracle(golden):
 
 
 def _wav16(name, g):
-    """The face golden's input: the 16 kHz samples whose sha256 the golden stores.  The side file written at build time, else
-    regenerated here by the host twin; anything that does not hash to the golden's input is not used."""
+    """The face golden's input: the 16 kHz samples whose sha256 the golden stores.  A side file written by
+    tests/golden/audio/fetch_reference_audio.py where present, else regenerated here by the host twin from the committed recording;
+    anything that does not hash to the golden's input is not used."""
     t = _tag(name)
     want = str(g[t + "_wav16_sha256"])
     side = os.path.join(AUDIO, name + ".wav16.npy")
@@ -195,7 +194,7 @@ def _wav16(name, g):
     wav = fe.get_wav16(_need_recording(name), host=True)[:, 0]
     if hashlib.sha256(wav.tobytes()).hexdigest() != want:
         pytest.skip(f"{name}: the host resampler on this machine does not reproduce the golden's input bit for bit and "
-                    f"{side} is absent (build() writes it)")
+                    f"{side} is absent")
     return wav
 
 

@@ -4,7 +4,7 @@ cp talkshow_amd/lib/libtalkshow_hip.so /tmp/lib_keep.so
 for round in 1 2; do
 for v in "$@"; do
   cp tools/lib_$v.so talkshow_amd/lib/libtalkshow_hip.so
-  line=$(TS_BENCH_WATCHDOG=150 timeout 200 python bench.py --steps 24 --warmup 8 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
+  line=$(TS_BENCH_WATCHDOG=150 timeout 200 python bench.py --full --steps 24 --warmup 8 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
   python - "$v" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

@@ -5,6 +5,6 @@ BS=${1:-"32 64 128 256"}; SS=${2:-"1 2 4"}
 for B in $BS; do
   for S in $SS; do
     steps=$(( 24 * 32 / B )); [ $steps -lt 4 ] && steps=4
-    timeout 300 python bench.py --batch $B --streams $S --steps $steps --warmup $S --no-cpu-baseline --no-face 2>/dev/null | tail -1
+    timeout 300 python bench.py --full --batch $B --streams $S --steps $steps --warmup $S --no-cpu-baseline --no-face 2>/dev/null | tail -1
   done
 done

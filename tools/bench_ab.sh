@@ -2,7 +2,7 @@
 # same-box A/B of environment settings on the driver's bench command (no CPU baseline / face / modes): bench_ab.sh "ENV=.. ENV=.." "ENV=.." ...
 for round in 1 2; do
 for e in "$@"; do
-  line=$(env $e TS_BENCH_WATCHDOG=150 timeout 200 python bench.py --steps 24 --warmup 8 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
+  line=$(env $e TS_BENCH_WATCHDOG=150 timeout 200 python bench.py --full --steps 24 --warmup 8 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
   python - "$e" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

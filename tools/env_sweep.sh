@@ -1,6 +1,6 @@
 #!/bin/bash
 # Which HIP runtime knobs move the multi-stream throughput?  (informational)
-run() { out=$(env "$@" timeout 300 python bench.py --steps 24 --warmup 4 --no-cpu-baseline --no-face --no-roofline --streams ${S:-4} 2>&1 | tail -1); python - "$out" "$*" <<'PY'
+run() { out=$(env "$@" timeout 300 python bench.py --full --steps 24 --warmup 4 --no-cpu-baseline --no-face --no-roofline --streams ${S:-4} 2>&1 | tail -1); python - "$out" "$*" <<'PY'
 import json, sys
 try:
     d = json.loads(sys.argv[1]); print(f"{sys.argv[2]:55s} streams={d['streams']} {d['value']:9.0f} frames/s  {d['ms_per_step']:.2f} ms/step  latency {d['batch_latency_ms']:.2f} ms")

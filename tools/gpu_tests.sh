@@ -5,7 +5,7 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -q -s > $O/tests_full.log 2>&1
 grep -E "equal to the reference|chi-square|first difference|passed|failed|FAILED|^E  " $O/tests_full.log | tail -40
 if [ "$2" != "nobench" ]; then
-  timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
   python - $O/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # bench lines (no CPU baseline / face / modes) under kernel knobs, one per argument ("A=1 B=2"); prints the key numbers
 mkdir -p gpurun_out; : > gpurun_out/knobs.log
 for env in "$@"; do
-  line=$(env $env TS_BENCH_WATCHDOG=150 timeout 200 python bench.py --steps 24 --warmup 8 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
+  line=$(env $env TS_BENCH_WATCHDOG=150 timeout 200 python bench.py --full --steps 24 --warmup 8 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
   python - "$env" "$line" >> gpurun_out/knobs.log <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@
 for round in 1 2; do
 for gs in "$@"; do
   set -- $gs
-  line=$(TS_BENCH_WATCHDOG=200 timeout 300 python bench.py --steps 20 --warmup 5 --coalesce $1 --streams $2 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
+  line=$(TS_BENCH_WATCHDOG=200 timeout 300 python bench.py --full --steps 20 --warmup 5 --coalesce $1 --streams $2 --no-cpu-baseline --no-face --no-modes 2>/dev/null | tail -1)
   python - "$gs" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

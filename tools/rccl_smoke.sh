@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/${1:-rccl_smoke}; mkdir -p $O
 cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0 TS_BENCH_FORCE_COLLECTIVES=1
 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 8 --warmup 2 \
-  --no-cpu-baseline --no-face --no-modes --no-roofline > $O/body.json 2> $O/body.err
+  --full --no-cpu-baseline --no-face --no-modes --no-roofline > $O/body.json 2> $O/body.err
 python - $O/body.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
