@@ -45,7 +45,9 @@ int ts_debug_tile_weights(const float *W, int N, int K, long ldw, int epi, int g
  * 2 = 64x64, 3 = 128x64, 4 = 64x128, 5 = 64x64 with 64-deep K chunks, 6 = 160x128, 7 = 96x128; 31 / 39 / 33 = the LDS-DMA ring engine's
  * 128x128 tile with 4 / 8 waves and its 96x128 tile (conv_gemm_ring.hip), 35 / 36 = 39 / 33 with the tiles dealt to the XCDs in blocks that
  * share operands, 37 = bands (128 x 128 + 64 x 128 tiles) + dealt tiles, 38 = whole tiles + a stream-K band (deterministic; not bit-identical
- * with the others).  *ms_out = mean launch duration in milliseconds. */
+ * with the others); 22 / 23 = the split-bf16 kernel (conv_gemm_split.hip) with 2 / 3 planes (3 / 6 bf16 products per fp32 product; the ids
+ * run_conv maps), 24 = 22 on plane images of the weights made by launch_split_weight_planes (w_planes = 1: the face's x3 plan); the
+ * split kernel takes 128 x 128 tiles from 200 of them on, 64 x 64 below.  *ms_out = mean launch duration in milliseconds. */
 int ts_op_conv1d_timed(ts_ctx *ctx, const float *x_dev, int B, int Lin, int Cin, const float *w_packed_dev,
                        const float *bias_dev, int Cout, int K, int tile, int iters, float *out_dev, float *ms_out,
                        void *stream);
@@ -73,18 +75,40 @@ int ts_debug_conv_ring_pick(int M, int N, int groups);
  * stages per tile, the plan the layer gets by cost: 8 = this one, 9 / 3 / 7 = a whole-tile plan}; 0 = no stream-K plan for this shape
  * (whole units, under one unit, runs under 4 stages); -1 = bad argument.  No reference counterpart. */
 int ts_debug_conv_sk_plan(int M, int N, int K, int groups, int *out6);
+/* 1 if the current device passed the stream-K band's hardware check (workgroup ids of equal residue mod 8 share an XCD: probed once by
+ * ts_ctx_create), 0 if not or if no context was created yet: then no layer gets a stream-K plan. */
+int ts_debug_conv_sk_supported(void);
 /* Host-only: the run of band workgroup q (0 <= q < band_workgroups, a multiple of 8) over a stream-K band of `band_tiles` tiles x `stages`
  * stages, in band-iteration units (tile * stages + stage): out4 = {first iteration, one past the last, the XCD (= q % 8) whose tiles
  * [xcd * band_tiles / 8, (xcd + 1) * band_tiles / 8) the run lies in, the run index the kernel's owner search finds for the first iteration
  * (= q / 8)}.  0 on success, -1 on a bad argument.  No reference counterpart. */
-/* 1 if the current device passed the stream-K band's hardware check (workgroup ids of equal residue mod 8 share an XCD: probed once by
- * ts_ctx_create), 0 if not or if no context was created yet: then no layer gets a stream-K plan. */
-int ts_debug_conv_sk_supported(void);
 int ts_debug_conv_sk_run(int band_tiles, int stages, int band_workgroups, int q, int *out4);
 
 /* Test aid: out[i] = the chain kernels' gate activation tanh(v[i]) * sigmoid(p[i]) as they compute it (v_exp_f32 / v_rcp_f32 form,
  * csrc/kernels.h::gate_act; reference: GatedActivation, gated_pixelcnn_v2.py:16-22) on n device floats. */
 int ts_debug_gate_act(const float *v_dev, const float *p_dev, float *out_dev, long n, void *stream);
+/* Test aid: out[i] = the face generator's GELU epilogue v / 2 (1 + erf(v / sqrt 2)) as the kernels compute it (csrc/kernels.h::gelu_fast,
+ * branch-free erf_fast) on n device floats. */
+int ts_debug_gelu(const float *v_dev, float *out_dev, long n, void *stream);
+
+/* Test aids: the face generator's non-GEMM kernels (csrc/face.hip), one launch each on `stream` (device pointers throughout, fp32).
+ * ts_debug_attention: qkv (B, T, 3 HID) rows [q | k | v] with heads of 64 channels (HID = 64 heads) -> out (B, T, HID) = per (clip, head)
+ * softmax(q k^T * scale) v (attention_kernel: fused QK^T, online soft-max over key tiles of 64, PV). */
+int ts_debug_attention(const float *qkv, int B, int T, int HID, int heads, float scale, float *out, void *stream);
+/* Row-wise LayerNorm (eps 1e-5) over C = 64 / 256 / 512 / 768 channels of M rows of pitch ldx: out = LN(x) gamma + beta (+ post_res rows of
+ * pitch ldr when given), then ReLU if relu != 0; out rows of pitch ldo. */
+int ts_debug_layernorm_rows(const float *x, int ldx, long M, int C, const float *gamma, const float *beta, const float *post_res, int ldr,
+                            int relu, float *out, int ldo, void *stream);
+/* Linear interpolation over time (align_corners = False) of x (B, Lin, 512) to (B, T, 512), fused with LayerNorm(512). */
+int ts_debug_lerp_ln(const float *x, int B, int Lin, int T, const float *gamma, const float *beta, float *out, void *stream);
+/* wav2vec2 feature-extractor layer 0: wav (B, N) -> out (B, L0, 512), L0 = (N - 10) / 5 + 1, = GELU(GroupNorm(512, 512)(Conv1d(1, 512, 10,
+ * stride 5, no bias))); w [512][10], gamma / beta [512].  form: 1 = statistics from the waveform's second moments, 0 = from a pass that
+ * computes the convolution, -1 = what production picks (TS_W2V_MOMENTS).  Allocates its own scratch and synchronizes `stream`. */
+int ts_debug_w2v_conv0(const float *wav, int B, int N, const float *w, const float *gamma, const float *beta, int form, float *out,
+                       void *stream);
+/* x[b][t][col0 + j] = bias[j] + sum_c w[j][c] id[b][c] for j < nj, c < nc, every t < T of clip b < B; x rows of pitch ld. */
+int ts_debug_fill_id(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0, int B, int T,
+                     void *stream);
 
 /* Test aid: how many captured hipGraphs the PixelCNN keeps for `stream` right now (whole-call graphs of repeated shapes + the chunk
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */

@@ -86,6 +86,12 @@ SIGNATURES = {
     "ts_pixelcnn_prepare": (_i, [_vp, _i, _i, _i, _vp]),
     "ts_debug_conv_ring_pick": (_i, [_i, _i, _i]),
     "ts_debug_gate_act": (_i, [_vp, _vp, _vp, C.c_long, _vp]),
+    "ts_debug_gelu": (_i, [_vp, _vp, C.c_long, _vp]),
+    "ts_debug_attention": (_i, [_vp, _i, _i, _i, _i, C.c_float, _vp, _vp]),
+    "ts_debug_layernorm_rows": (_i, [_vp, _i, C.c_long, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "ts_debug_lerp_ln": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ts_debug_w2v_conv0": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ts_debug_fill_id": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "ts_op_vq_argmin": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "ts_op_linear": (_i, [_vp, _vp, _i, _i, _fp, _fp, _i, _i, _vp, _vp]),
     "ts_op_sample": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

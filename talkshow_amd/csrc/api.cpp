@@ -199,14 +199,19 @@ int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const flo
     return 0;
 }
 
+// tile ids 22 / 23 = the split-bf16 kernel with 2 / 3 planes (as run_conv maps them), every other id = launch_conv_gemm's
+static hipError_t launch_timed_tile(const ts::ConvParams &p, int tile, hipStream_t s) {
+    return tile == 22 || tile == 23 ? ts::launch_conv_gemm_split(p, tile - 20, s) : ts::launch_conv_gemm(p, tile, s);
+}
+
 // one warm-up launch, then `iters` launches of the layer between two HIP events on `s`: *ms_out = mean launch duration (ms)
 static int time_conv_launches(const ts::ConvParams &p, int tile, int iters, float *ms_out, hipStream_t s) {
     hipEvent_t a, b;
     TS_HIP(hipEventCreate(&a));
     TS_HIP(hipEventCreate(&b));
-    TS_HIP(ts::launch_conv_gemm(p, tile, s));
+    TS_HIP(launch_timed_tile(p, tile, s));
     TS_HIP(hipEventRecord(a, s));
-    for (int i = 0; i < iters; ++i) TS_HIP(ts::launch_conv_gemm(p, tile, s));
+    for (int i = 0; i < iters; ++i) TS_HIP(launch_timed_tile(p, tile, s));
     TS_HIP(hipEventRecord(b, s));
     TS_HIP(hipEventSynchronize(b));
     float ms = 0.f;
@@ -243,6 +248,17 @@ int ts_op_conv1d_timed(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, con
     p.g[0].out = out;
     p.g[0].nseg = K;
     for (int k = 0; k < K; ++k) p.g[0].seg[k] = ConvSeg{K == 1 ? 0 : k - 1, 0, Cin};
+    if (tile == 24) {   // 2 planes from plane images of the packed weights (launch_split_weight_planes), as the face's x3 plan runs them
+        DevBuf planes;
+        const long rows = (Cout + 127) / 128 * 128;
+        TS_TRY(planes.ensure((size_t)rows * p.Ktot * sizeof(float)));
+        TS_HIP(launch_split_weight_planes(w_packed_dev, planes.f(), rows, p.Ktot, s));
+        p.g[0].w = planes.f();
+        p.w_planes = 1;
+        const int rc = time_conv_launches(p, 22, iters, ms_out, s);
+        TS_HIP(hipStreamSynchronize(s));   // the plane images die with this frame
+        return rc;
+    }
     return time_conv_launches(p, tile, iters, ms_out, s);
 }
 
@@ -357,6 +373,52 @@ int ts_debug_conv_sk_run(int band_tiles, int stages, int band_workgroups, int q,
 int ts_debug_gate_act(const float *v_dev, const float *p_dev, float *out_dev, long n, void *stream) {
     if (!v_dev || !p_dev || !out_dev || n < 0) return fail("ts_debug_gate_act: bad argument");
     TS_HIP(ts::launch_gate_act(v_dev, p_dev, out_dev, n, (hipStream_t)stream));
+    return 0;
+}
+
+int ts_debug_gelu(const float *v_dev, float *out_dev, long n, void *stream) {
+    if (!v_dev || !out_dev || n < 0) return fail("ts_debug_gelu: bad argument");
+    TS_HIP(ts::launch_gelu(v_dev, out_dev, n, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- the face generator's non-GEMM kernels (face.hip), one launch each on `stream` ----
+int ts_debug_attention(const float *qkv, int B, int T, int HID, int heads, float scale, float *out, void *stream) {
+    if (!qkv || !out || B < 1 || T < 1 || heads < 1 || HID != heads * 64) return fail("ts_debug_attention: bad argument");
+    TS_HIP(ts::launch_attention(qkv, B, T, HID, heads, scale, out, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_layernorm_rows(const float *x, int ldx, long M, int C, const float *gamma, const float *beta, const float *post_res,
+                            int ldr, int relu, float *out, int ldo, void *stream) {
+    if (!x || !gamma || !beta || !out || M < 1 || ldx < C || ldo < C || (post_res && ldr < C)) return fail("ts_debug_layernorm_rows: bad argument");
+    if (C != 64 && C != 256 && C != 512 && C != 768) return fail("ts_debug_layernorm_rows: C must be 64, 256, 512 or 768");
+    TS_HIP(ts::launch_layernorm_rows(x, ldx, M, C, gamma, beta, post_res, ldr, relu, out, ldo, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_lerp_ln(const float *x, int B, int Lin, int T, const float *gamma, const float *beta, float *out, void *stream) {
+    if (!x || !gamma || !beta || !out || B < 1 || Lin < 1 || T < 1) return fail("ts_debug_lerp_ln: bad argument");
+    TS_HIP(ts::launch_lerp_ln(x, B, Lin, T, gamma, beta, out, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_w2v_conv0(const float *wav, int B, int N, const float *w, const float *gamma, const float *beta, int form, float *out,
+                       void *stream) {
+    if (!wav || !w || !gamma || !beta || !out || B < 1 || N < 10 || form < -1 || form > 1) return fail("ts_debug_w2v_conv0: bad argument");
+    constexpr int C = 512;
+    const int L0 = (N - 10) / 5 + 1, ntb = (L0 + 127) / 128;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf part, stats;
+    TS_TRY(part.ensure((size_t)B * ntb * C * sizeof(double2)));
+    TS_TRY(stats.ensure((size_t)B * C * sizeof(float2)));
+    const bool moments = form < 0 ? ts::knobs().w2v_moments : form == 1;
+    TS_HIP(ts::launch_w2v_conv0(wav, B, N, L0, w, gamma, beta, static_cast<double2 *>(part.p), static_cast<float2 *>(stats.p), out, C,
+                                moments, s));
+    TS_HIP(hipStreamSynchronize(s));   // the scratch dies with this frame
+    return 0;
+}
+int ts_debug_fill_id(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0, int B, int T,
+                     void *stream) {
+    if (!id || !w || !bias || !x || nc < 1 || nj < 1 || col0 < 0 || ld < col0 + nj || B < 1 || T < 1) return fail("ts_debug_fill_id: bad argument");
+    TS_HIP(ts::launch_fill_id(id, nc, w, bias, nj, x, ld, col0, B, T, (hipStream_t)stream));
     return 0;
 }
 

@@ -337,7 +337,7 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     {
         MiscScope ms(ctx, s);
         TS_HIP(launch_w2v_conv0(wav, B, N, L[0], f->c0_w.f(), f->c0_g.f(), f->c0_b.f(), static_cast<double2 *>(w.part.p),
-                                static_cast<float2 *>(w.stats.p), w.A.f(), C0, s));
+                                static_cast<float2 *>(w.stats.p), w.A.f(), C0, ts::knobs().w2v_moments, s));
     }
     float *cur = w.A.f(), *nxt = w.Bf.f();
     for (int i = 0; i < 6; ++i) {

@@ -176,9 +176,9 @@ __global__ void w2v_gn_from_moments_kernel(const double *__restrict__ mom, const
 }
 
 hipError_t launch_w2v_conv0(const float *wav, int B, int N, int L0, const float *w, const float *gamma, const float *beta,
-                            double2 *part, float2 *stats, float *out, int C, hipStream_t s) {
+                            double2 *part, float2 *stats, float *out, int C, bool moments, hipStream_t s) {
     const int ntb = (L0 + C0_TB - 1) / C0_TB;
-    if (knobs().w2v_moments) {   // `part` holds B x ntb x C double2: room for B x nblk x 65 + B x 65 doubles many times over
+    if (moments) {   // `part` holds B x ntb x C double2: room for B x nblk x 65 + B x 65 doubles many times over
         const int nblk = (L0 + C0_MB - 1) / C0_MB;
         double *pm = reinterpret_cast<double *>(part), *mom = pm + (size_t)B * nblk * C0_NQ;
         hipLaunchKernelGGL(w2v_conv0_moments_kernel, dim3(nblk, B), dim3(256), 0, s, wav, N, L0, pm);
@@ -246,6 +246,13 @@ hipError_t launch_layernorm_rows(const float *x, int ldx, long M, int C, const f
 }
 
 // ---- time interpolation (align_corners=False) + LayerNorm(512) --------------------------------------------------
+// Source index of frame j: scale * (j + 0.5) - 0.5 as ONE fused multiply-add, the rounding of ATen's vectorized (AVX2 / AVX512) CPU
+// kernels that made the reference's goldens (tests/test_face_oracle_golden.py::test_lerp_source_index_matches_aten); ATen's scalar
+// kernel and the numpy oracle round the product first, which moves the lerp weight of a few frames by up to an ulp of the index.
+__device__ inline float lerp_src_index(float scale, int j) {
+    const float src = __builtin_fmaf(scale, (float)j + 0.5f, -0.5f);
+    return src < 0.f ? 0.f : src;
+}
 __global__ __launch_bounds__(256) void lerp_ln_kernel(const float *__restrict__ x, int Lin, int T, long M,
                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
                                                       float *__restrict__ out) {
@@ -255,8 +262,7 @@ __global__ __launch_bounds__(256) void lerp_ln_kernel(const float *__restrict__ 
     const int lane = threadIdx.x & 63;
     const int b = (int)(m / T), j = (int)(m - (long)b * T);
     const float scale = (float)Lin / (float)T;
-    float src = scale * ((float)j + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
+    const float src = lerp_src_index(scale, j);
     const int i0 = (int)floorf(src);
     const int i1 = min(i0 + 1, Lin - 1);
     const float l1 = src - (float)i0, l0 = 1.0f - l1;

@@ -235,6 +235,8 @@ hipError_t launch_assemble_full(const float *body, const float *face, const floa
 hipError_t launch_i64_to_i32(const int64_t *src, int *dst, long n, hipStream_t stream);
 // test aid: out[i] = gate_act(v[i], p[i])
 hipError_t launch_gate_act(const float *v, const float *p, float *out, long n, hipStream_t stream);
+// test aid: out[i] = gelu_fast(v[i])
+hipError_t launch_gelu(const float *v, float *out, long n, hipStream_t stream);
 // dst[0..2] = a, b, c, carried by the launch's own arguments (no host buffer has to outlive the call)
 hipError_t launch_set_words3(uint64_t *dst, uint64_t a, uint64_t b, uint64_t c, hipStream_t stream);
 // measurement aid: n records of (wall ticks since start, wall ticks of the window, shader cycles of the window), 100 MHz wall clock
@@ -356,8 +358,10 @@ hipError_t launch_sample(const SampleParams &p, hipStream_t stream);
 // ------------------------------------------------------------------------------------------------
 // face generator kernels (face.hip)
 // ------------------------------------------------------------------------------------------------
+// moments: the GroupNorm statistics from the waveform's second moments (true; production: knobs().w2v_moments) or from a pass that
+// computes the convolution (false).  part: B x ceil(L0 / 128) x C double2 of scratch, stats: B x C float2
 hipError_t launch_w2v_conv0(const float *wav, int B, int N, int L0, const float *w, const float *gamma, const float *beta,
-                            double2 *part, float2 *stats, float *out, int C, hipStream_t s);
+                            double2 *part, float2 *stats, float *out, int C, bool moments, hipStream_t s);
 hipError_t launch_layernorm_rows(const float *x, int ldx, long M, int C, const float *gamma, const float *beta,
                                  const float *post_res, int ldr, int relu, float *out, int ldo, hipStream_t s);
 hipError_t launch_lerp_ln(const float *x, int B, int Lin, int T, const float *gamma, const float *beta, float *out,

@@ -346,6 +346,15 @@ hipError_t launch_gate_act(const float *v, const float *p, float *out, long n, h
     hipLaunchKernelGGL(gate_act_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, p, out, n);
     return hipGetLastError();
 }
+// test aid: out[i] = gelu_fast(v[i]) — the face generator's GELU epilogue on given operands (tests measure it against float64 erf)
+__global__ void gelu_kernel(const float *v, float *out, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = gelu_fast(v[i]);
+}
+hipError_t launch_gelu(const float *v, float *out, long n, hipStream_t stream) {
+    hipLaunchKernelGGL(gelu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, out, n);
+    return hipGetLastError();
+}
 
 // measurement aid: one wave that sleeps and, every `window_ticks` of the 100 MHz wall clock, records (wall ticks, shader cycles)
 // since the previous record — the shader clock the chip actually runs at while other streams load it

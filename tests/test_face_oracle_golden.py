@@ -52,3 +52,33 @@ def test_face_generator_on_a_recording(golden):
     np.testing.assert_allclose(FO.face_generator(wav[None], ids, sd, frame)[0], g["french_out_zero_id"], atol=1e-4, rtol=0)
     ids[0, spk] = 1.0
     np.testing.assert_allclose(FO.face_generator(wav[None], ids, sd, frame)[0], g["french_out_one_hot"], atol=1e-4, rtol=0)
+
+
+def test_lerp_source_index_matches_aten():
+    """FO.source_index against this host's own F.interpolate(mode='linear', align_corners=False), read back from an input whose frame i
+    holds i: ATen's AVX2 / AVX512 kernels round scale * (j + 0.5) - 0.5 once (fused=True: what made the reference's goldens, and what the
+    HIP kernel computes), its scalar kernel rounds the product first (fused=False: the oracle's linear_interpolation).  At the frames where
+    the two forms differ (they do for every length below), torch must sit on its form's side."""
+    import torch
+    import torch.nn.functional as F
+    cap = torch.backends.cpu.get_cpu_capability()
+    want = {"AVX2": True, "AVX512": True, "DEFAULT": False}.get(cap)
+    for L, T in ((499, 300), (49, 30), (2999, 1800), (1499, 900)):
+        got = F.interpolate(torch.arange(L, dtype=torch.float32).view(1, 1, L), size=T, mode="linear", align_corners=False)[0, 0]
+        got = got.double().numpy()
+        form = {}
+        for fused in (False, True):
+            i0, i1, l0, l1 = FO.source_index(L, T, fused)
+            form[fused] = i0 * l0.astype(np.float64) + i1 * l1.astype(np.float64)
+        diff = np.abs(form[True] - form[False])
+        d = diff > 0
+        assert d.any(), f"{L} -> {T}: the two index forms agree everywhere"
+        near = {f: bool((np.abs(got[d] - form[f][d]) < diff[d] / 4).all()) for f in (False, True)}
+        assert near[True] or near[False], f"{L} -> {T}: torch ({cap}) matches neither index form"
+        if want is not None:
+            assert near[want], f"{L} -> {T}: torch ({cap}) does not round the source index {'once' if want else 'twice'}"
+        np.testing.assert_allclose(got[~d], form[True][~d], atol=1e-3, rtol=0)
+    # the oracle's interpolation is the two-rounding form
+    x = np.random.default_rng(0).standard_normal((1, 1499, 4)).astype(np.float32)
+    i0, i1, l0, l1 = FO.source_index(1499, 900)
+    assert np.array_equal(FO.linear_interpolation(x, 900), (x[:, i0] * l0[None, :, None] + x[:, i1] * l1[None, :, None]).astype(np.float32))
