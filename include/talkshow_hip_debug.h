@@ -41,13 +41,13 @@ int ts_debug_tile_weights(const float *W, int N, int K, long ldw, int epi, int g
 
 /* Tuning / roofline entry (not part of the drop-in surface): a stride-1 conv layer (K = 1 or 3, Cin % 32 == 0)
  * whose weights are ALREADY packed on the device as [round128(Cout)][K*Cin] (tap-major, k contiguous), launched
- * `iters` times between two HIP events recorded on `stream`; tile: 0 = production heuristic, 1 = 128x128,
- * 2 = 64x64, 3 = 128x64, 4 = 64x128, 5 = 64x64 with 64-deep K chunks, 6 = 160x128, 7 = 96x128; 31 / 39 / 33 = the LDS-DMA ring engine's
- * 128x128 tile with 4 / 8 waves and its 96x128 tile (conv_gemm_ring.hip), 35 / 36 = 39 / 33 with the tiles dealt to the XCDs in blocks that
- * share operands, 37 = bands (128 x 128 + 64 x 128 tiles) + dealt tiles, 38 = whole tiles + a stream-K band (deterministic; not bit-identical
- * with the others); 22 / 23 = the split-bf16 kernel (conv_gemm_split.hip) with 2 / 3 planes (3 / 6 bf16 products per fp32 product; the ids
- * run_conv maps), 24 = 22 on plane images of the weights made by launch_split_weight_planes (w_planes = 1: the face's x3 plan); the
- * split kernel takes 128 x 128 tiles from 200 of them on, 64 x 64 below.  *ms_out = mean launch duration in milliseconds. */
+ * `iters` times between two HIP events recorded on `stream`.  tile: 0 = the production plan; otherwise one plan (engine names of
+ * ts_debug_conv_plan): 1 .. 7 = Reg with 128x128, 64x64, 128x64, 64x128, 64x64 with 64-deep K chunks, 160x128, 96x128 tiles; 31 / 39 / 33 =
+ * Ring with the 128x128 tile on 4 / 8 waves and its 96x128 tile, 35 / 36 = RingDealt with 39's / 33's tiles, 37 = RingBanded (128 x 128 +
+ * 64 x 128 tiles), 38 = RingSK (deterministic; not bit-identical with the others) — 37 / 38 fall back to 35 where the layer has no such plan;
+ * 22 / 23 = Split with 2 / 3 planes (3 / 6 bf16 products per fp32 product), 24 = 22 on plane images of the weights made by
+ * launch_split_weight_planes (w_planes = 1: the face's x3 plan); the split kernel takes 128 x 128 tiles from 200 of them on, 64 x 64 below;
+ * 48 = Taps48 (batched 48-channel taps only).  *ms_out = mean launch duration in milliseconds. */
 int ts_op_conv1d_timed(ts_ctx *ctx, const float *x_dev, int B, int Lin, int Cin, const float *w_packed_dev,
                        const float *bias_dev, int Cout, int K, int tile, int iters, float *out_dev, float *ms_out,
                        void *stream);
@@ -64,11 +64,20 @@ int ts_op_conv1d_strided_timed(ts_ctx *ctx, const float *x_dev, int B, int Lin, 
 int ts_op_conv_taps48_timed(ts_ctx *ctx, const float *x_dev, int B, int T, int G, int ntap, const float *w_dev, const float *bias_dev,
                             const float *res_dev, int iters, float *out_dev, float *ms_out, void *stream);
 
-/* Host-only helper (no GPU needed): the tile plan conv_gemm_f32's LDS-DMA ring engine gives a layer of `groups` problems of M rows x N columns —
- * 128 (128 x 128 tiles), 96 (96 x 128 tiles) or 64 (bands: 128 x 128 tiles for the whole rounds of 512 resident workgroups, 64 x 128 tiles for
- * the rows that are left) — by tile count: a last round at most half full costs half a round (csrc/conv_gemm_ring.hip::conv_gemm_ring_pick).
- * -1 on a bad argument.  No reference counterpart. */
-int ts_debug_conv_ring_pick(int M, int N, int groups);
+/* Host-only helper (no GPU needed, no HIP call): the plan launch_conv_gemm gives a layer (csrc/conv_gemm.hip::plan_conv) — `groups` problems of
+ * M rows x N columns x Ktot, each with nseg (<= 4) segments of seg_len[i] channels (one tap each); groups > 4: that many batched problems of one
+ * segment whose Ktot / seg_len[0] taps make up K (the positional convolution's layout).  sk_ok: the caller accepts the stream-K band (the face
+ * generator sets it); the device is taken to pass the band's hardware check.  tile: 0 = the production choice, else a tile id of
+ * ts_op_conv1d_timed.  knob_list: "NAME=VALUE,..." of the TS_* levers in place of the environment, null = the defaults.
+ * Returns the engine — 0 Reg (conv_gemm.hip, register-staged), 1 RegBanded, 2 Ring (LDS-DMA ring engine, plain grid), 3 RingDealt (tiles dealt
+ * to the XCDs), 4 RingBanded, 5 RingSK (stream-K band), 6 Taps48, 7 Split — with out4 = {tile rows, tile columns, waves, K chunk} (Reg / Ring /
+ * RingDealt; the big tile of a banded or stream-K plan), or -1 on a bad argument or an unknown tile id.  No reference counterpart. */
+int ts_debug_conv_plan(int M, int N, int Ktot, int groups, int sk_ok, const int *seg_len, int nseg, int tile, const char *knob_list, int *out4);
+/* Host-only helper (no GPU needed, no HIP call): the plan launch_skinny_batch gives n (<= 6) chain problems of mnk[3 i .. 3 i + 2] = (M, N, K)
+ * rows x columns x depth, laid out as the PixelCNN lays out its operands; a negative K is an epilogue-only block of zero rows of that depth.
+ * knob_list as for ts_debug_conv_plan.  Returns the kernel — 0 wide (skinny_wide.hip), 1 fast (the descriptor kernel), 2 generic 16-column,
+ * 3 generic 32-column — with out4 = {waves, row blocks of 16, column blocks of 16 (fast), workgroups}, or -1 on a bad argument. */
+int ts_debug_skinny_plan(const int *mnk, int n, const char *knob_list, int *out4);
 /* Host-only helper (no GPU needed): the stream-K plan of the ring engine for `groups` problems of M rows x N columns x K (csrc/conv_gemm_ring.hip:
  * whole 128 x 128 tiles for the row tiles that fill whole units of 256 tiles, the rows after them as one list of (tile, 32-k stage) iterations
  * cut into equal runs).  1 = out6 = {row tiles kept whole, row tiles in the band, dealt ids of the whole-tile region, band workgroups,

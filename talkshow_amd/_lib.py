@@ -84,7 +84,8 @@ SIGNATURES = {
     "ts_debug_conv_sk_supported": (_i, []),
     "ts_pixelcnn_graph_captures": (C.c_long, [_vp, _vp]),
     "ts_pixelcnn_prepare": (_i, [_vp, _i, _i, _i, _vp]),
-    "ts_debug_conv_ring_pick": (_i, [_i, _i, _i]),
+    "ts_debug_conv_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, C.c_char_p, C.POINTER(_i)]),
+    "ts_debug_skinny_plan": (_i, [C.POINTER(_i), _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_gate_act": (_i, [_vp, _vp, _vp, C.c_long, _vp]),
     "ts_debug_gelu": (_i, [_vp, _vp, C.c_long, _vp]),
     "ts_debug_attention": (_i, [_vp, _i, _i, _i, _i, C.c_float, _vp, _vp]),

@@ -20,33 +20,45 @@ BodyWork &body_work(hipStream_t s) {
 }  // namespace
 
 namespace ts {
+// the TS_* levers as `get` (NAME -> value text or null) reports them
+template <class Get>
+static Knobs read_knobs(Get get) {
+    Knobs v;
+    auto num = [&](const char *name, int dflt) { const char *e = get(name); return e && e[0] ? std::atoi(e) : dflt; };
+    v.conv_bands = num("TS_CONV_BANDS", 1) != 0;
+    v.conv_ring = num("TS_CONV_RING", 9);
+    v.conv_deal = num("TS_CONV_DEAL", 1) != 0;
+    v.conv_ring_paired = num("TS_CONV_RING_PAIRED", 1) != 0;
+    v.conv_taps48 = num("TS_CONV_TAPS48", 1) != 0;
+    v.conv_sk = num("TS_CONV_SK", 1);
+    v.w2v_moments = num("TS_W2V_MOMENTS", 1) != 0;
+    v.vq_lds = num("TS_VQ_LDS", 1) != 0;
+    v.split_xcd = num("TS_SPLIT_XCD", 8);
+    v.prof_log = num("TS_PROF_LOG", 0) != 0;
+    if (const char *e = get("TS_NO_GRAPH")) v.no_graph = e[0] && e[0] != '0';
+    v.pix_defer_p = num("TS_PIX_DEFER_P", -1);
+    v.skinny_v = num("TS_SKINNY_V", 1);
+    v.skinny_nt = num("TS_SKINNY_NT", 16);
+    v.skinny_tiled = num("TS_SKINNY_TILED", 1) != 0;
+    v.wide_min = num("TS_SKINNY_WIDE_MIN", 160);
+    v.skinny_shape = num("TS_SKINNY_SHAPE", 0);
+    v.skinny_trace = num("TS_SKINNY_TRACE", 0);
+    v.wide_ablate = num("TS_SKINNY_WIDE_ABLATE", 0);
+    v.wide_pair = num("TS_SKINNY_WIDE_PAIR", 1) != 0;
+    return v;
+}
 const Knobs &knobs() {
-    static const Knobs k = [] {
-        Knobs v;
-        auto num = [](const char *name, int dflt) { const char *e = std::getenv(name); return e && e[0] ? std::atoi(e) : dflt; };
-        v.conv_bands = num("TS_CONV_BANDS", 1) != 0;
-        v.conv_ring = num("TS_CONV_RING", 9);
-        v.conv_deal = num("TS_CONV_DEAL", 1) != 0;
-        v.conv_ring_paired = num("TS_CONV_RING_PAIRED", 1) != 0;
-        v.conv_taps48 = num("TS_CONV_TAPS48", 1) != 0;
-        v.conv_sk = num("TS_CONV_SK", 1);
-        v.w2v_moments = num("TS_W2V_MOMENTS", 1) != 0;
-        v.vq_lds = num("TS_VQ_LDS", 1) != 0;
-        v.split_xcd = num("TS_SPLIT_XCD", 8);
-        v.prof_log = num("TS_PROF_LOG", 0) != 0;
-        if (const char *e = std::getenv("TS_NO_GRAPH")) v.no_graph = e[0] && e[0] != '0';
-        v.pix_defer_p = num("TS_PIX_DEFER_P", -1);
-        v.skinny_v = num("TS_SKINNY_V", 1);
-        v.skinny_nt = num("TS_SKINNY_NT", 16);
-        v.skinny_tiled = num("TS_SKINNY_TILED", 1) != 0;
-        v.wide_min = num("TS_SKINNY_WIDE_MIN", 160);
-        v.skinny_shape = num("TS_SKINNY_SHAPE", 0);
-        v.skinny_trace = num("TS_SKINNY_TRACE", 0);
-        v.wide_ablate = num("TS_SKINNY_WIDE_ABLATE", 0);
-        v.wide_pair = num("TS_SKINNY_WIDE_PAIR", 1) != 0;
-        return v;
-    }();
+    static const Knobs k = read_knobs([](const char *name) { return std::getenv(name); });
     return k;
+}
+// the plan debug entries: the levers of a "NAME=VALUE,NAME=VALUE" list (null: the defaults), read by the same table as the environment
+static Knobs knobs_from_list(const char *list) {
+    return read_knobs([list](const char *name) -> const char * {
+        const size_t n = std::strlen(name);
+        for (const char *q = list; q && (q = std::strstr(q, name)); q += n)
+            if ((q == list || q[-1] == ',' || q[-1] == ' ') && q[n] == '=') return q + n + 1;
+        return nullptr;
+    });
 }
 }  // namespace ts
 
@@ -109,10 +121,10 @@ int ts_debug_conv_bands(int M, int N, int groups, int *out4) {
     p.M = M;
     p.N = N;
     p.ngroups = groups;
-    ts::ConvBands bd{};
-    const bool banded = ts::conv_gemm_band_plan(p, bd);
+    const ts::ConvPlan pl = ts::plan_conv(p, 0, ts::knobs_from_list("TS_CONV_RING=0"), false);
+    const ts::ConvBands &bd = pl.bands;
     out4[0] = bd.mt_big; out4[1] = bd.mt_small; out4[2] = bd.first_small; out4[3] = bd.total;
-    return banded ? 1 : 0;
+    return pl.engine == ts::ConvEngine::RegBanded ? 1 : 0;
 }
 // Host-only (no GPU): tile (out2 = {row tile, column tile}) that workgroup `bid` of conv_gemm_split's 1-D grid works on for an MT x NT
 // tile grid and column groups of `gw` tiles; returns 1, 0 if that workgroup has no tile, -1 on a bad argument
@@ -199,19 +211,14 @@ int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const flo
     return 0;
 }
 
-// tile ids 22 / 23 = the split-bf16 kernel with 2 / 3 planes (as run_conv maps them), every other id = launch_conv_gemm's
-static hipError_t launch_timed_tile(const ts::ConvParams &p, int tile, hipStream_t s) {
-    return tile == 22 || tile == 23 ? ts::launch_conv_gemm_split(p, tile - 20, s) : ts::launch_conv_gemm(p, tile, s);
-}
-
 // one warm-up launch, then `iters` launches of the layer between two HIP events on `s`: *ms_out = mean launch duration (ms)
 static int time_conv_launches(const ts::ConvParams &p, int tile, int iters, float *ms_out, hipStream_t s) {
     hipEvent_t a, b;
     TS_HIP(hipEventCreate(&a));
     TS_HIP(hipEventCreate(&b));
-    TS_HIP(launch_timed_tile(p, tile, s));
+    TS_HIP(ts::launch_conv_gemm(p, tile, s));
     TS_HIP(hipEventRecord(a, s));
-    for (int i = 0; i < iters; ++i) TS_HIP(launch_timed_tile(p, tile, s));
+    for (int i = 0; i < iters; ++i) TS_HIP(ts::launch_conv_gemm(p, tile, s));
     TS_HIP(hipEventRecord(b, s));
     TS_HIP(hipEventSynchronize(b));
     float ms = 0.f;
@@ -322,17 +329,67 @@ int ts_op_conv_taps48_timed(ts_ctx *ctx, const float *x, int B, int T, int G, in
     return time_conv_launches(p, 48, iters, ms_out, s);
 }
 
-int ts_debug_conv_ring_pick(int M, int N, int groups) {
-    if (M < 1 || N < 1 || groups < 1 || groups > 4) return -1;
+int ts_debug_conv_plan(int M, int N, int Ktot, int groups, int sk_ok, const int *seg_len, int nseg, int tile, const char *knob_list, int *out4) {
+    if (M < 1 || N < 1 || Ktot < 1 || groups < 1 || groups > 64 || nseg < 1 || nseg > 4 || !seg_len || !out4) return -1;
+    if (groups > 4 && (nseg != 1 || seg_len[0] < 1 || Ktot % seg_len[0])) return -1;
     ts::ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.M = M;
+    p.Lout = p.Lin = M;
+    p.stride = 1;
     p.N = N;
+    p.Ktot = Ktot;
     p.ngroups = groups;
-    ts::ConvBands bd{};
-    const bool have = ts::conv_gemm_plan_bands(p, bd);
-    const int pick = ts::conv_gemm_ring_pick(p, have ? &bd : nullptr, nullptr);
-    return pick == 3 ? 96 : (pick == 7 ? 64 : 128);
+    p.zdiv = groups > 4 ? groups : 0;   // batched problems sharing g[0]'s geometry; the segment's taps make up Ktot
+    p.sk_ok = sk_ok != 0;
+    for (int z = 0; z < (groups > 4 ? 1 : groups); ++z) {
+        p.g[z].nseg = nseg;
+        for (int i = 0; i < nseg; ++i) p.g[z].seg[i] = ts::ConvSeg{0, 0, seg_len[i], groups > 4 ? Ktot / seg_len[0] : 1};
+    }
+    const ts::ConvPlan pl = ts::plan_conv(p, tile, ts::knobs_from_list(knob_list), true);
+    if (pl.engine == ts::ConvEngine::Invalid) return -1;
+    out4[0] = pl.bm;
+    out4[1] = pl.bn;
+    out4[2] = pl.wm > 0 ? (pl.bm / pl.wm) * (pl.bn / pl.wn) : 0;
+    out4[3] = pl.bk;
+    return (int)pl.engine;
+}
+
+int ts_debug_skinny_plan(const int *mnk, int n, const char *knob_list, int *out4) {
+    if (!mnk || n < 1 || n > ts::SKINNY_MAX_PROBLEMS || !out4) return -1;
+    const ts::Knobs k = ts::knobs_from_list(knob_list);
+    const bool tiled = k.skinny_v != 0 && k.skinny_nt != 32 && k.skinny_tiled;   // the operands the PixelCNN lays out (skinny_descriptor_kernel_enabled)
+    const float *fake = reinterpret_cast<const float *>(uintptr_t(4096));        // 16-byte aligned, never read: the plan looks at shapes only
+    ts::SkinnyParams p[ts::SKINNY_MAX_PROBLEMS];
+    const ts::SkinnyParams *ps[ts::SKINNY_MAX_PROBLEMS];
+    for (int i = 0; i < n; ++i) {
+        const int M = mnk[3 * i], N = mnk[3 * i + 1], K = mnk[3 * i + 2] < 0 ? -mnk[3 * i + 2] : mnk[3 * i + 2];
+        if (M < 1 || N < 1 || K < 1) return -1;
+        const bool zero_rows = mnk[3 * i + 2] < 0;
+        std::memset(&p[i], 0, sizeof(p[i]));
+        p[i].M = M;
+        p[i].N = N;
+        p[i].Ktot = K;
+        p[i].nseg = 1;
+        p[i].seg[0].base = zero_rows ? nullptr : fake;
+        p[i].seg[0].row_stride = K;
+        p[i].seg[0].len = K;
+        p[i].seg[0].tiled_w = tiled && !zero_rows ? K : 0;
+        p[i].W = fake;
+        p[i].ldw = K;
+        p[i].w_tiled = tiled && !zero_rows ? K / 16 : 0;
+        p[i].out = const_cast<float *>(fake);
+        p[i].out_stride = N;
+        ps[i] = &p[i];
+    }
+    const ts::SkinnyPlan pl = ts::plan_skinny(ps, n, k);
+    if (pl.kernel == ts::SkinnyKernel::Invalid) return -1;
+    const bool grid1d = pl.kernel == ts::SkinnyKernel::Wide || pl.kernel == ts::SkinnyKernel::Fast;
+    out4[0] = pl.W;
+    out4[1] = pl.RB;
+    out4[2] = pl.CB;
+    out4[3] = grid1d ? pl.total : pl.gx * pl.gy * n;
+    return (int)pl.kernel;
 }
 
 int ts_debug_conv_sk_plan(int M, int N, int K, int groups, int *out6) {
@@ -351,8 +408,10 @@ int ts_debug_conv_sk_plan(int M, int N, int K, int groups, int *out6) {
     if (!ts::conv_gemm_plan_sk_shape(p, sk)) return 0;
     ts::ConvBands bd{};
     const bool have = ts::conv_gemm_plan_bands(p, bd) && bd.mt_big >= 1;
-    const int pick = ts::conv_gemm_ring_pick(p, have ? &bd : nullptr, &sk);
-    const int o[6] = {sk.mt_dp, sk.mt_sk, sk.dp8, sk.wsk, sk.stages, pick};
+    const ts::ConvPlan pick = ts::conv_gemm_ring_pick(p, have ? &bd : nullptr, &sk);
+    // the plan by cost in this entry's documented numbers (tools/sk_layers.py reads them): 8 = the band, 9 / 3 / 7 = RingDealt 128 / 96, RingBanded
+    const int code = pick.engine == ts::ConvEngine::RingSK ? 8 : pick.engine == ts::ConvEngine::RingBanded ? 7 : pick.bm == 96 ? 3 : 9;
+    const int o[6] = {sk.mt_dp, sk.mt_sk, sk.dp8, sk.wsk, sk.stages, code};
     std::memcpy(out6, o, sizeof(o));
     return 1;
 }

@@ -340,76 +340,121 @@ bool conv_gemm_plan_bands(const ConvParams &p, ConvBands &bd) {
     return true;
 }
 
-// host-only view of the launch plan (tests): would `launch_conv_gemm(p, 0, ...)` band this layer, and how
-bool conv_gemm_band_plan(const ConvParams &p, ConvBands &bd) { return pick_tile(p) == 1 && conv_gemm_plan_bands(p, bd); }
+// The tile ids of ts_op_conv1d_timed / run_conv (include/talkshow_hip_debug.h) as plans.  37 and 38 fall back to RingDealt 128 x 128 when the
+// layer has no band / stream-K plan.
+struct TileId {
+    int id;
+    ConvEngine engine;
+    int bm, bn, wm, wn, bk, planes;
+};
+static const TileId tile_ids[] = {
+    {1, ConvEngine::Reg, 128, 128, 64, 64, 32, 0},       {2, ConvEngine::Reg, 64, 64, 32, 32, 32, 0},
+    {3, ConvEngine::Reg, 128, 64, 64, 32, 32, 0},        {4, ConvEngine::Reg, 64, 128, 32, 64, 32, 0},
+    {5, ConvEngine::Reg, 64, 64, 32, 32, 64, 0},         // 64-deep chunks: all segment lengths must be multiples of 64
+    // tall tiles, waves side by side along N (each 32 columns x the whole tile height): 160x128 turns the three big layer shapes of the VQ
+    // stacks at batch 32 (M*N = 2 x 2400x1024 = 2 x 4800x512 = 2 x 9600x256) into exactly 240 tiles, one per CU in a single wave
+    {6, ConvEngine::Reg, 160, 128, 160, 32, 32, 0},      {7, ConvEngine::Reg, 96, 128, 96, 32, 32, 0},
+    {22, ConvEngine::Split, 0, 0, 0, 0, 32, 2},          {23, ConvEngine::Split, 0, 0, 0, 0, 32, 3},
+    {31, ConvEngine::Ring, 128, 128, 64, 64, 32, 0},     {39, ConvEngine::Ring, 128, 128, 32, 64, 32, 0},
+    {33, ConvEngine::Ring, 96, 128, 96, 32, 32, 0},      {35, ConvEngine::RingDealt, 128, 128, 32, 64, 32, 0},
+    {36, ConvEngine::RingDealt, 96, 128, 96, 32, 32, 0}, {37, ConvEngine::RingBanded, 128, 128, 32, 64, 32, 0},
+    {38, ConvEngine::RingSK, 128, 128, 32, 64, 32, 0},   {48, ConvEngine::Taps48, 0, 0, 0, 0, 32, 0},
+};
+static ConvPlan plan_of_tile(int id) {
+    ConvPlan pl;
+    for (const TileId &t : tile_ids)
+        if (t.id == id) {
+            pl.engine = t.engine;
+            pl.bm = t.bm, pl.bn = t.bn, pl.wm = t.wm, pl.wn = t.wn, pl.bk = t.bk, pl.planes = t.planes;
+        }
+    return pl;
+}
 
-hipError_t launch_conv_gemm(const ConvParams &p_in, int tile, hipStream_t stream) {
+ConvPlan plan_conv(const ConvParams &p, int tile, const Knobs &k, bool sk_hw) {
+    if (tile == 37 || tile == 38) {   // bands / stream-K band + dealt tiles where the layer has such a plan, else the dealt plain grid
+        ConvPlan pl = plan_of_tile(tile);
+        if (tile == 37 ? conv_gemm_plan_bands(p, pl.bands) : sk_hw && conv_gemm_plan_sk_shape(p, pl.sk)) return pl;
+        return plan_of_tile(35);
+    }
+    if (tile != 0) return plan_of_tile(tile);
+    if (k.conv_taps48 && conv_taps48_takes(p)) return plan_of_tile(48);   // grouped 48-channel taps, unpadded
+    const ConvPlan reg = plan_of_tile(pick_tile(p));
+    // layers that take 128 x 128 tiles run on the ring engine (same-box A/B: profiles/r05_notes/): the face generator's GEMMs, and the paired
+    // body + hand layers unless TS_CONV_RING_PAIRED=0 (then: the banded launch below)
+    if (k.conv_ring > 0 && (p.ngroups == 1 || k.conv_ring_paired) && p.zdiv == 0 && reg.bm == 128 && reg.bn == 128 && conv_gemm_ring_takes(p)) {
+        // TS_CONV_RING: 9 = the plan by tile count (default; tiles dealt to the XCDs unless TS_CONV_DEAL=0), 1 / 3 / 5 / 6 / 8 = the ring tile
+        // of that tile id; anything else is not a variant and means the plan by tile count on a plain grid, not a launch error on every layer
+        static const int ring_ids[][2] = {{1, 31}, {3, 33}, {5, 35}, {6, 36}, {8, 39}};
+        for (const auto &r : ring_ids)
+            if (k.conv_ring == r[0]) return plan_of_tile(r[1]);
+        if (k.conv_ring != 9 || !k.conv_deal) {
+            ConvPlan pl = conv_gemm_ring_pick(p, nullptr, nullptr);
+            pl.engine = ConvEngine::Ring;
+            return pl;
+        }
+        // a band plan without a single 128-row block in its big band (more than 512 column tiles: a very wide N x groups) is no plan:
+        // the banded launch refuses it, so it must not be offered to the pick
+        ConvBands bd;
+        const bool have = k.conv_bands && conv_gemm_plan_bands(p, bd) && bd.mt_big >= 1;
+        ConvSK sk;
+        const bool have_sk = k.conv_sk && p.sk_ok && sk_hw && conv_gemm_plan_sk_shape(p, sk);
+        ConvPlan pl = conv_gemm_ring_pick(p, have ? &bd : nullptr, have_sk ? &sk : nullptr);
+        if (have_sk && k.conv_sk == 2) {   // TS_CONV_SK=2: the band wherever the layer has a plan for one
+            pl = plan_of_tile(38);
+            pl.sk = sk;
+        }
+        return pl;
+    }
+    ConvPlan pl = reg;
+    if (reg.bm == 128 && reg.bn == 128 && k.conv_bands && conv_gemm_plan_bands(p, pl.bands)) pl.engine = ConvEngine::RegBanded;   // TS_CONV_BANDS=0: plain grid
+    return pl;
+}
+
+template <int BM, int BN, int WM, int WN, int BK>
+static void launch_reg(const ConvParams &p, hipStream_t s) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BK>), dim3((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, p.ngroups), dim3(256), 0, s, p);
+}
+struct RegInstance {
+    int bm, bn, wm, wn, bk;
+    void (*launch)(const ConvParams &, hipStream_t);
+};
+static const RegInstance reg_instances[] = {
+    {128, 128, 64, 64, 32, launch_reg<128, 128, 64, 64, 32>}, {64, 64, 32, 32, 32, launch_reg<64, 64, 32, 32, 32>},
+    {128, 64, 64, 32, 32, launch_reg<128, 64, 64, 32, 32>},   {64, 128, 32, 64, 32, launch_reg<64, 128, 32, 64, 32>},
+    {64, 64, 32, 32, 64, launch_reg<64, 64, 32, 32, 64>},     {160, 128, 160, 32, 32, launch_reg<160, 128, 160, 32, 32>},
+    {96, 128, 96, 32, 32, launch_reg<96, 128, 96, 32, 32>},
+};
+
+hipError_t launch_conv_plan(const ConvParams &p_in, const ConvPlan &pl, hipStream_t stream) {
     ConvParams p = p_in;
-    if (!p.zero) {
+    if (!p.zero) {   // zero buffer (ts::skinny_init, called by ts_ctx_create): 64 Ki floats; parked pointers walk at most Ktot floats of it
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
     }
-    dim3 block(256);
-    auto grid = [&](int bm, int bn) { return dim3((p.M + bm - 1) / bm, (p.N + bn - 1) / bn, p.ngroups); };
-    // zero buffer (ts::skinny_init, called by ts_ctx_create): 64 Ki floats; parked pointers walk at most Ktot floats of it
     if (!p.zero || p.g[0].nseg > 4 || p.Ktot > 60000) return hipErrorInvalidValue;
-    if (tile == 31 || tile == 33 || tile == 39 || tile == 35 || tile == 36) return launch_conv_gemm_ring(p, tile - 30, stream);   // LDS-DMA ring engine (conv_gemm_ring.hip)
-    if (tile == 37) {   // ring engine, banded + dealt (falls back to the dealt plain grid when the layer has no band plan)
-        ConvBands bd;
-        if (!conv_gemm_plan_bands(p, bd)) return launch_conv_gemm_ring(p, 5, stream);
-        return launch_conv_gemm_ring_banded(p, bd, stream);
-    }
-    if (tile == 38) {   // ring engine, whole tiles for the whole units of 256 + a stream-K band for the rest (falls back to the dealt plain grid)
-        ConvSK sk;
-        if (!conv_gemm_plan_sk(p, sk)) return launch_conv_gemm_ring(p, 5, stream);
-        return launch_conv_gemm_ring_sk(p, sk, stream);
-    }
-    if (tile == 48 || (tile == 0 && knobs().conv_taps48 && conv_taps48_takes(p))) return launch_conv_taps48(p, stream);   // grouped 48-channel taps, unpadded (conv_taps48.hip)
-    // layers that take 128 x 128 tiles run on the ring engine (same-box A/B: profiles/r05_notes/): the face generator's GEMMs, and the paired
-    // body + hand layers unless TS_CONV_RING_PAIRED=0 (then: the banded launch below)
-    if (tile == 0 && knobs().conv_ring > 0 && (p.ngroups == 1 || knobs().conv_ring_paired) && p.zdiv == 0 && pick_tile(p) == 1 && conv_gemm_ring_takes(p)) {
-        const int v = knobs().conv_ring;   // 9: the tile plan by tile count (conv_gemm_ring_pick); tiles dealt to the XCDs unless TS_CONV_DEAL=0
-        if (v == 9 && knobs().conv_deal) {
-            ConvBands bd;
-            // a band plan without a single 128-row block in its big band (more than 512 column tiles: a very wide N x groups) is no plan:
-            // the banded launch refuses it, so it must not be offered to the pick
-            const bool have = knobs().conv_bands && conv_gemm_plan_bands(p, bd) && bd.mt_big >= 1;
-            ConvSK sk;
-            const bool have_sk = knobs().conv_sk && p.sk_ok && conv_gemm_plan_sk(p, sk);
-            const int pick = conv_gemm_ring_pick(p, have ? &bd : nullptr, have_sk ? &sk : nullptr);
-            if (pick == 8 || (have_sk && knobs().conv_sk == 2)) return launch_conv_gemm_ring_sk(p, sk, stream);
-            return pick == 7 ? launch_conv_gemm_ring_banded(p, bd, stream) : launch_conv_gemm_ring(p, pick == 3 ? 6 : 5, stream);
-        }
-        // TS_CONV_RING: 9 = the plan by tile count (default), 8 = the 8-wave 128 x 128 tile, 1 / 3 / 5 / 6 = that variant; anything else is
-        // not a variant and means the default plan, not a launch error on every layer
-        const int variant = v == 9 ? 0 : (v == 8 ? 9 : ((v == 1 || v == 3 || v == 5 || v == 6) ? v : 0));
-        return launch_conv_gemm_ring(p, variant, stream);
-    }
-    if (tile == 0 && pick_tile(p) == 1) {
-        const bool banded = knobs().conv_bands;   // TS_CONV_BANDS=0: plain grid (A/B, tests)
-        ConvBands bd;
-        if (banded && conv_gemm_plan_bands(p, bd)) {
-            hipLaunchKernelGGL((conv_gemm_banded_kernel<64, 128, 32, 64>), dim3(bd.total), block, 0, stream, p, bd);
+    switch (pl.engine) {
+        case ConvEngine::Reg:
+            for (const RegInstance &r : reg_instances)
+                if (r.bm == pl.bm && r.bn == pl.bn && r.wm == pl.wm && r.wn == pl.wn && r.bk == pl.bk) {
+                    r.launch(p, stream);
+                    return hipGetLastError();
+                }
+            return hipErrorInvalidValue;
+        case ConvEngine::RegBanded:
+            hipLaunchKernelGGL((conv_gemm_banded_kernel<64, 128, 32, 64>), dim3(pl.bands.total), dim3(256), 0, stream, p, pl.bands);
             return hipGetLastError();
-        }
-    }
-    if (tile == 0) tile = pick_tile(p);
-    switch (tile) {
-        case 1: hipLaunchKernelGGL((conv_gemm_kernel<128, 128, 64, 64>), grid(128, 128), block, 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((conv_gemm_kernel<64, 64, 32, 32>), grid(64, 64), block, 0, stream, p); break;
-        case 3: hipLaunchKernelGGL((conv_gemm_kernel<128, 64, 64, 32>), grid(128, 64), block, 0, stream, p); break;
-        case 4: hipLaunchKernelGGL((conv_gemm_kernel<64, 128, 32, 64>), grid(64, 128), block, 0, stream, p); break;
-        case 5:   // 64x64 with 64-deep chunks (all segment lengths must be multiples of 64)
-            hipLaunchKernelGGL((conv_gemm_kernel<64, 64, 32, 32, 64>), grid(64, 64), block, 0, stream, p);
-            break;
-        // tall tiles, waves side by side along N (each 32 columns x the whole tile height): 160x128 turns the three big
-        // layer shapes of the VQ stacks at batch 32 (M*N = 2 x 2400x1024 = 2 x 4800x512 = 2 x 9600x256) into exactly 240
-        // tiles, one per CU in a single wave, with the L2->LDS traffic per MAC of the 128x128 tile
-        case 6: hipLaunchKernelGGL((conv_gemm_kernel<160, 128, 160, 32>), grid(160, 128), block, 0, stream, p); break;
-        case 7: hipLaunchKernelGGL((conv_gemm_kernel<96, 128, 96, 32>), grid(96, 128), block, 0, stream, p); break;
+        case ConvEngine::Ring:
+        case ConvEngine::RingDealt: return launch_conv_gemm_ring(p, pl, stream);
+        case ConvEngine::RingBanded: return launch_conv_gemm_ring_banded(p, pl.bands, stream);
+        case ConvEngine::RingSK: return launch_conv_gemm_ring_sk(p, pl.sk, stream);
+        case ConvEngine::Taps48: return launch_conv_taps48(p, stream);
+        case ConvEngine::Split: return launch_conv_gemm_split(p, pl.planes, stream);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
+}
+
+hipError_t launch_conv_gemm(const ConvParams &p, int tile, hipStream_t stream) {
+    return launch_conv_plan(p, plan_conv(p, tile, knobs(), conv_sk_supported()), stream);
 }
 
 }  // namespace ts

@@ -446,8 +446,6 @@ bool conv_sk_supported() {
     return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16 && g_sk_map_ok[dev] == 1;
 }
 
-bool conv_gemm_plan_sk(const ConvParams &p, ConvSK &sk) { return conv_sk_supported() && conv_gemm_plan_sk_shape(p, sk); }
-
 // the plan as a function of the layer's shape alone (host-side tests call this one: no device needed)
 bool conv_gemm_plan_sk_shape(const ConvParams &p, ConvSK &sk) {
     if (p.zdiv > 0 || !conv_gemm_ring_takes(p) || p.ngroups < 1 || 256 % p.ngroups) return false;
@@ -464,7 +462,7 @@ bool conv_gemm_plan_sk_shape(const ConvParams &p, ConvSK &sk) {
         if (sk.mt_dp < 1 || sk.mt_sk < 1) return false;
         const long I = (long)sk.mt_sk * nt * sk.stages;
         if (I * (sk.wsk + 1) >= (1l << 31)) return false;        // the kernel cuts the runs in int arithmetic
-        if (I / sk.wsk >= 4 && sk.mt_sk * nt >= 32) return true;   // (and at least 4 tiles per XCD: the band is dealt to the XCDs in whole tiles)
+        if (I / sk.wsk >= 4 && sk.mt_sk * nt >= 32) return conv_sk_valid(p, sk);   // (and at least 4 tiles per XCD: the band is dealt to the XCDs in whole tiles)
         // a few tiles over whole units (3 600 = 14 x 256 + 16): runs of under 4 stages would be all prologue — the band takes one more
         // unit of tiles instead (runs of a little over one tile each)
         if (full < 2 * unit) return false;
@@ -472,14 +470,24 @@ bool conv_gemm_plan_sk_shape(const ConvParams &p, ConvSK &sk) {
     }
 }
 
+// A plan the kernel can run: its row tiles are the layer's, one band workgroup per slot of a unit of 256 (a multiple of 8: workgroup
+// q works on XCD q % 8), and every run holds at least one iteration — with an empty run `rl - rf` over-counts a tile's pieces and it is never
+// finalized.
+bool conv_sk_valid(const ConvParams &p, const ConvSK &sk) {
+    if (p.zdiv > 0 || p.ngroups < 1 || 256 % p.ngroups || !conv_gemm_ring_takes(p)) return false;
+    const int nt = (p.N + 127) / 128;
+    if (sk.mt_dp < 1 || sk.mt_sk < 1 || sk.mt_dp + sk.mt_sk != (p.M + 127) / 128 || sk.wsk != 256 / p.ngroups || (sk.wsk & 7) ||
+        sk.stages != p.Ktot / 32 || sk.dp8 != 8 * ((sk.mt_dp * nt + 7) / 8))
+        return false;
+    const SkRuns R{sk.mt_sk * nt, sk.stages, sk.wsk >> 3};
+    for (int c = 0; c < 8; ++c)
+        if ((long)(R.tlo(c + 1) - R.tlo(c)) * sk.stages < R.w8) return false;   // runs cut an XCD's iterations evenly: none empty
+    return true;
+}
+
 hipError_t launch_conv_gemm_ring_sk(const ConvParams &p_in, const ConvSK &sk, hipStream_t stream) {
     ConvParams p = p_in;
-    if (!p.zero) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
-    }
-    if (!p.zero || !conv_gemm_ring_takes(p) || p.zdiv > 0 || sk.mt_dp < 1 || sk.mt_sk < 1 || sk.wsk < 8 || (sk.wsk & 7) || sk.stages != p.Ktot / 32)
-        return hipErrorInvalidValue;
+    if (!p.zero || !conv_sk_valid(p, sk)) return hipErrorInvalidValue;
     const int nt = (p.N + 127) / 128;
     if (conv_sk_workspace(stream, (size_t)sk.wsk * p.ngroups * 2 * 128 * 128, (size_t)sk.mt_sk * nt * p.ngroups, &p.sk_ws, &p.sk_flags) != 0)
         return hipErrorOutOfMemory;
@@ -487,12 +495,7 @@ hipError_t launch_conv_gemm_ring_sk(const ConvParams &p_in, const ConvSK &sk, hi
     return hipGetLastError();
 }
 
-hipError_t launch_conv_gemm_ring_banded(const ConvParams &p_in, const ConvBands &bd, hipStream_t stream) {
-    ConvParams p = p_in;
-    if (!p.zero) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
-    }
+hipError_t launch_conv_gemm_ring_banded(const ConvParams &p, const ConvBands &bd, hipStream_t stream) {
     if (!p.zero || !conv_gemm_ring_takes(p) || p.zdiv > 0 || bd.mt_big < 1 || bd.mt_small < 1) return hipErrorInvalidValue;
     const int nt = (p.N + 127) / 128;
     const int big8 = 8 * ((bd.mt_big * nt + 7) / 8), small8 = 8 * ((bd.mt_small * nt + 7) / 8);
@@ -508,16 +511,16 @@ bool conv_gemm_ring_takes(const ConvParams &p) {
     return true;
 }
 
-// Which tile plan for a layer?  A launch is rounds of 512 resident workgroups (two per CU); a workgroup alone on its CU runs at the full
+// Which tile plan for a layer (ConvEngine::RingDealt / RingBanded / RingSK)?  A launch is rounds of 512 resident workgroups (two per CU); a workgroup alone on its CU runs at the full
 // pipe rate (tools/ring_probe.py: 256 tiles on 256 CUs take what 512 take), so a last round that is at most half full costs half a
 // round, a fuller one a whole round.  Three plans, cost = rounds x tile height / efficiency:
-//   9: 128 x 128 tiles on 8 waves, the fastest per tile;
-//   3: 96 x 128 tiles (4 waves of 96 x 32, ~5 % slower per flop) change the tile COUNT: the N = 768 layers of the wav2vec2 blocks (900 tiles
+//   128 x 128 tiles on 8 waves, the fastest per tile;
+//   96 x 128 tiles (4 waves of 96 x 32, ~5 % slower per flop) change the tile COUNT: the N = 768 layers of the wav2vec2 blocks (900 tiles
 //      of 128 rows = 1.76 rounds -> 2; 1 200 of 96 rows = 2.34 -> 2.5 x 0.75 = 1.875): out-proj 207 -> 200 us, FFN2 750 -> 718 us in a face batch;
-//   7: bands (conv_gemm.hip's plan, `bd`): 128 x 128 tiles for the whole rounds, 64 x 128 tiles (~7 % slower per flop) for the rows that
+//   bands (conv_gemm.hip's plan, `bd`): 128 x 128 tiles for the whole rounds, 64 x 128 tiles (~7 % slower per flop) for the rows that
 //      are left: FFN1 (3 600 tiles = 7.03 rounds -> 6.98 + half a round of short tiles: 715 -> 693 us) and the paired body + hand layers
 //      (2 400 tiles = 4.69 rounds -> 4 + 1.5 short ones: conv stacks of a 256-clip pass 25.7 -> 25.2 ms); ties go to the plain plans.
-//   8: whole tiles + stream-K band (`sk`, round 6): cost = the tile list's exact share of the chip + the band's hand-over.
+//   whole tiles + stream-K band (`sk`, round 6): cost = the tile list's exact share of the chip + the band's hand-over.
 // Measured: profiles/r05_notes/ring_tall_tiles.txt, face_layers_ab.txt, ring_banded_probe.txt; round 6: profiles/r06_notes/stream_k_*.txt.
 // In the face pass (profiles/r06_notes/stream_k_in_situ.txt; band forced vs off, per layer): FFN2 (K = 3 072: 96 stages) -5.8 %, the feature
 // convolutions of K = 1 536 -0.6 ... -1.6 %, K = 1 024 +1.4 %, QKV (K = 768, 2 700 tiles) -1.1 %, out-proj (K = 768, 900 tiles) +1.7 %, FFN1 +-0:
@@ -525,7 +528,7 @@ bool conv_gemm_ring_takes(const ConvParams &p) {
 // share falls with K.
 constexpr double SK_OVERHEAD_STAGES = 4.0;    // ... in rounds of 512 tiles: 4 stages' worth, i.e. 4 / (stages per tile)
 constexpr double SK_MARGIN = 0.97;            // the band must promise 3 % over the best whole-tile plan
-int conv_gemm_ring_pick(const ConvParams &p, const ConvBands *bd, const ConvSK *sk) {
+ConvPlan conv_gemm_ring_pick(const ConvParams &p, const ConvBands *bd, const ConvSK *sk) {
     const long nt = (long)((p.N + 127) / 128) * p.ngroups;
     auto rounds = [](long tiles) {
         const long full = tiles / 512, rest = tiles - full * 512;
@@ -534,45 +537,61 @@ int conv_gemm_ring_pick(const ConvParams &p, const ConvBands *bd, const ConvSK *
     const double c128 = rounds((long)((p.M + 127) / 128) * nt) * 128.0;
     const double c96 = rounds((long)((p.M + 95) / 96) * nt) * 96.0 / 0.95;   // layers without a tail: 122.7 vs 130.8, 114 vs 123 TFLOP/s
     double best = c128;
-    int pick = 9;
+    ConvPlan pl;
+    pl.engine = ConvEngine::RingDealt;
+    pl.bm = 128, pl.bn = 128, pl.wm = 32, pl.wn = 64;
     if (c96 < best) {
         best = c96;
-        pick = 3;
+        pl.bm = 96, pl.wm = 96, pl.wn = 32;
     }
     if (bd) {   // the big band is whole rounds but for a few tiles, whose slots the short tiles take
         const double cb = bd->first_small / 512.0 * 128.0 + rounds((long)bd->mt_small * nt) * 64.0 / 0.93;
         if (cb < 0.98 * best) {   // within 2 % the plain plans measure as fast or faster (feature convolutions 5 / 6: 537 vs 532, 277 vs 271 us)
             best = cb;
-            pick = 7;
+            pl.engine = ConvEngine::RingBanded;
+            pl.bm = 128, pl.wm = 32, pl.wn = 64;
+            pl.bands = *bd;
         }
     }
-    if (sk) {   // 8: whole tiles for the whole units of 256 + a stream-K band: the chip's share of the tile list, plus what the band's hand-over costs
+    if (sk) {   // whole tiles for the whole units of 256 + a stream-K band: the chip's share of the tile list, plus what the band's hand-over costs
         const double cs = ((double)((p.M + 127) / 128) * nt / 512.0 + SK_OVERHEAD_STAGES / sk->stages) * 128.0;
-        if (cs < SK_MARGIN * best) pick = 8;
+        if (cs < SK_MARGIN * best) {
+            pl.engine = ConvEngine::RingSK;
+            pl.bm = 128, pl.wm = 32, pl.wn = 64;
+            pl.sk = *sk;
+        }
     }
-    return pick;
+    return pl;
 }
 
-hipError_t launch_conv_gemm_ring(const ConvParams &p_in, int variant, hipStream_t stream) {
-    ConvParams p = p_in;
-    if (!p.zero) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
-    }
-    if (!p.zero || !conv_gemm_ring_takes(p)) return hipErrorInvalidValue;
-    if (variant == 0) variant = conv_gemm_ring_pick(p, nullptr, nullptr);
-    if (variant == 10) variant = conv_gemm_ring_pick(p, nullptr, nullptr) == 3 ? 6 : 5;   // the pick (without bands), tiles dealt to the XCDs
-    const dim3 grid((p.M + 127) / 128, (p.N + 127) / 128, p.ngroups);
-    auto dealt = [&](int bm) { return dim3(8 * (unsigned)(((long)((p.M + bm - 1) / bm) * grid.y + 7) / 8), 1, grid.z); };
-    switch (variant) {
-        case 1: hipLaunchKernelGGL((conv_ring_kernel<128, 128, 64, 64, false>), grid, dim3(256), 0, stream, p); break;   // 4 waves of 64 x 64
-        case 9: hipLaunchKernelGGL((conv_ring_kernel<128, 128, 32, 64, false>), grid, dim3(512), 0, stream, p); break;   // 8 waves of 32 x 64
-        case 3: hipLaunchKernelGGL((conv_ring_kernel<96, 128, 96, 32, false>), dim3((p.M + 95) / 96, grid.y, grid.z), dim3(256), 0, stream, p); break;   // 96 x 128: 4 waves of 96 x 32
-        case 5: hipLaunchKernelGGL((conv_ring_kernel<128, 128, 32, 64, true>), dealt(128), dim3(512), 0, stream, p); break;   // 9 with the tiles dealt to the XCDs
-        case 6: hipLaunchKernelGGL((conv_ring_kernel<96, 128, 96, 32, true>), dealt(96), dim3(256), 0, stream, p); break;     // 3 likewise
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+// XCD = false: grid (row tiles, column tiles, problems); XCD = true: 8 ceil(tiles / 8) dealt ids per problem
+template <int BM, int BN, int WM, int WN, bool XCD>
+static void launch_ring(const ConvParams &p, hipStream_t s) {
+    const unsigned mt = (p.M + BM - 1) / BM, nt = (p.N + BN - 1) / BN;
+    const dim3 grid = XCD ? dim3(8 * (unsigned)(((long)mt * nt + 7) / 8), 1, p.ngroups) : dim3(mt, nt, p.ngroups);
+    hipLaunchKernelGGL((conv_ring_kernel<BM, BN, WM, WN, XCD>), grid, dim3(64 * (BM / WM) * (BN / WN)), 0, s, p);
+}
+struct RingInstance {
+    bool dealt;
+    int bm, wm, wn;
+    void (*launch)(const ConvParams &, hipStream_t);
+};
+static const RingInstance ring_instances[] = {
+    {false, 128, 64, 64, launch_ring<128, 128, 64, 64, false>},   // 4 waves of 64 x 64
+    {false, 128, 32, 64, launch_ring<128, 128, 32, 64, false>},   // 8 waves of 32 x 64
+    {false, 96, 96, 32, launch_ring<96, 128, 96, 32, false>},     // 96 x 128: 4 waves of 96 x 32
+    {true, 128, 32, 64, launch_ring<128, 128, 32, 64, true>},
+    {true, 96, 96, 32, launch_ring<96, 128, 96, 32, true>},
+};
+
+hipError_t launch_conv_gemm_ring(const ConvParams &p, const ConvPlan &pl, hipStream_t stream) {
+    if (!p.zero || !conv_gemm_ring_takes(p) || pl.bn != 128) return hipErrorInvalidValue;
+    for (const RingInstance &r : ring_instances)
+        if (r.dealt == (pl.engine == ConvEngine::RingDealt) && r.bm == pl.bm && r.wm == pl.wm && r.wn == pl.wn) {
+            r.launch(p, stream);
+            return hipGetLastError();
+        }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace ts

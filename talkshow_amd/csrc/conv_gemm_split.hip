@@ -402,10 +402,6 @@ __global__ __launch_bounds__(256) void conv_gemm_split_kernel(const ConvParams p
 // planes: 2 (three products) or 3 (six products).  Same tile ids as launch_conv_gemm (1: 128 x 128, 2: 64 x 64); 0 = by size.
 hipError_t launch_conv_gemm_split(const ConvParams &p_in, int planes, hipStream_t stream) {
     ConvParams p = p_in;
-    if (!p.zero) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
-    }
     if (!p.zero || p.g[0].nseg > 4 || p.Ktot > 60000 || p.Ktot % 32 != 0 || (planes != 2 && planes != 3)) return hipErrorInvalidValue;
     dim3 block(256);
     const bool xcd = knobs().split_xcd > 0 && p.ngroups == 1 && p.zdiv == 0;

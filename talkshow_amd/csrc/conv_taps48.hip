@@ -220,12 +220,7 @@ bool conv_taps48_takes(const ConvParams &p) {
            al4(p.r_zs0);
 }
 
-hipError_t launch_conv_taps48(const ConvParams &p_in, hipStream_t stream) {
-    ConvParams p = p_in;
-    if (!p.zero) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
-    }
+hipError_t launch_conv_taps48(const ConvParams &p, hipStream_t stream) {
     if (!p.zero || !conv_taps48_takes(p)) return hipErrorInvalidValue;
     const long total = (long)((p.M + T48_BM - 1) / T48_BM) * p.ngroups;
     hipLaunchKernelGGL(conv_taps48_kernel, dim3(8 * (unsigned)((total + 7) / 8)), dim3(512), 0, stream, p);

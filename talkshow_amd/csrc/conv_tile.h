@@ -98,15 +98,16 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvParams &p, const Co
     }
 }
 
-// the LDS-DMA ring engine (conv_gemm_ring.hip); variant 1 = 128 x 128 on 4 waves of 64 x 64, 9 = 128 x 128 on 8 waves of 32 x 64, 3 = 96 x 128 on 4 waves
-// of 96 x 32 (tile ids 31 / 39 / 33), 0 = 9 or 3 by the layer's tile count (conv_gemm_ring_pick)
-hipError_t launch_conv_gemm_ring(const ConvParams &p, int variant, hipStream_t stream);
-hipError_t launch_conv_gemm_ring_banded(const ConvParams &p, const ConvBands &bd, hipStream_t stream);   // tile id 37: bands (plan_bands) + dealt tiles
+// the engines behind launch_conv_plan (conv_gemm.hip), which resolves p.zero and then hands each plan to its launcher
+hipError_t launch_conv_gemm_ring(const ConvParams &p, const ConvPlan &plan, hipStream_t stream);   // Ring / RingDealt (conv_gemm_ring.hip)
+hipError_t launch_conv_gemm_ring_banded(const ConvParams &p, const ConvBands &bd, hipStream_t stream);
+hipError_t launch_conv_gemm_ring_sk(const ConvParams &p, const ConvSK &sk, hipStream_t stream);
 bool conv_gemm_ring_takes(const ConvParams &p);   // host: every segment a multiple of the 32-deep stage
-int conv_gemm_ring_pick(const ConvParams &p, const ConvBands *bd, const ConvSK *sk);   // host: the plan by tile count: 9 (128 x 128), 3 (96 x 128), 7 (bands, if `bd` is given) or 8 (stream-K band, if `sk` is given)
-
-// grouped many-tap convolution with 48 channels per group (conv_taps48.hip: the wav2vec2 positional convolution); tile id 48
-hipError_t launch_conv_taps48(const ConvParams &p, hipStream_t stream);
-bool conv_taps48_takes(const ConvParams &p);
+// host: the ring engine's plan by tile count: RingDealt with 128 x 128 or 96 x 128 tiles, RingBanded (if `bd` is given) or RingSK (if `sk` is given)
+ConvPlan conv_gemm_ring_pick(const ConvParams &p, const ConvBands *bd, const ConvSK *sk);
+hipError_t launch_conv_taps48(const ConvParams &p, hipStream_t stream);   // conv_taps48.hip: the wav2vec2 positional convolution
+// the same convolution on the bf16 matrix cores with fp32 operands split into `planes` bf16 terms (2: three products, ~2^-16;
+// 3: six products, fp32 grade) — conv_gemm_split.hip; an opt-in plan for tolerance-only GEMMs (the face generator)
+hipError_t launch_conv_gemm_split(const ConvParams &p, int planes, hipStream_t stream);
 
 }  // namespace ts

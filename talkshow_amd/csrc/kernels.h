@@ -6,6 +6,8 @@
 
 namespace ts {
 
+struct Knobs;   // the TS_* test levers (below)
+
 // ------------------------------------------------------------------------------------------------
 // conv_gemm_f32: 1-D convolution / transposed convolution / pointwise linear as an implicit GEMM on the
 // fp32 MFMA (v_mfma_f32_32x32x2_f32).  Activations are NLC ([b][t][c], row stride ld floats, c padded to
@@ -95,22 +97,38 @@ struct SkRuns {
 
 hipError_t conv_sk_probe_xcd_map(int device);                   // host, once per device (ts_ctx_create): do workgroup ids of equal residue mod 8 share an XCD?
 bool conv_sk_supported();                                       // ... the answer for the current device (false before the probe ran)
-bool conv_gemm_plan_sk_shape(const ConvParams &p, ConvSK &sk); // host only: the plan by shape (no device needed)
-bool conv_gemm_plan_sk(const ConvParams &p, ConvSK &sk);       // host only: ... where the device supports it: false = the layer has no partly filled last unit worth splitting
-hipError_t launch_conv_gemm_ring_sk(const ConvParams &p, const ConvSK &sk, hipStream_t stream);   // tile id 38
+bool conv_gemm_plan_sk_shape(const ConvParams &p, ConvSK &sk); // host only, by shape: false = the layer has no partly filled last unit worth splitting
+bool conv_sk_valid(const ConvParams &p, const ConvSK &sk);     // host only: sk covers p's row tiles, has one band workgroup per unit slot and no empty run
 // host (models.cpp): per-stream scratch of the stream-K band — ws_floats floats + nflags zeroed ints, grown on demand, dropped with the stream
 int conv_sk_workspace(hipStream_t s, size_t ws_floats, size_t nflags, float **ws, int **flags);
 
-bool conv_gemm_band_plan(const ConvParams &p, ConvBands &bd);   // host only: the plan launch_conv_gemm(p, 0, ...) would use
 bool conv_gemm_plan_bands(const ConvParams &p, ConvBands &bd);  // host only: the bands of a layer given to 128 x 128 tiles (false: none — under one round, or whole rounds)
-// tile: 0 = auto, 1 = 128x128, 2 = 64x64, 3 = 128x64, 4 = 64x128, 5 = 64x64 (BK 64), 6 = 160x128, 7 = 96x128 (for tuning / tests);
-// 31 / 39 / 33 = the LDS-DMA ring engine's 128x128 tile with 4 / 8 waves, its 96x128 tile (conv_gemm_ring.hip); 35 / 36 = 39 / 33 with the
-// tiles dealt to the XCDs in operand-sharing blocks, 37 = bands + dealt tiles; 48 = conv_taps48.hip (batched problems of 48-channel taps only)
-hipError_t launch_conv_gemm(const ConvParams &p, int tile, hipStream_t stream);
-bool conv_taps48_takes(const ConvParams &p);   // host: would tile 48 (conv_taps48.hip) take this layer as laid out?
-// the same convolution on the bf16 matrix cores with fp32 operands split into `planes` bf16 terms (2: three products, ~2^-16;
-// 3: six products, fp32 grade) — conv_gemm_split.hip; an opt-in plan for tolerance-only GEMMs (the face generator)
-hipError_t launch_conv_gemm_split(const ConvParams &p, int planes, hipStream_t stream);
+bool conv_taps48_takes(const ConvParams &p);   // host: would conv_taps48.hip take this layer as laid out?
+
+// Which kernel runs a conv layer (conv_gemm.hip::plan_conv):
+//   Reg         conv_gemm.hip, global -> VGPR -> LDS staging: one plain grid of bm x bn tiles (wm x wn per wave, bk-deep chunks)
+//   RegBanded   conv_gemm.hip: 128 x 128 tiles for the whole rounds of 512 workgroups, 64 x 128 tiles for the rows left (`bands`)
+//   Ring        conv_gemm_ring.hip, LDS-DMA ring: a plain (row tiles, column tiles, problems) grid of bm x bn tiles
+//   RingDealt   the same tiles dealt to the XCDs in operand-sharing blocks (1-D grid)
+//   RingBanded  ring engine: bands (`bands`) + dealt tiles
+//   RingSK      ring engine: whole tiles for the whole units of 256 + a stream-K band (`sk`; not bit-identical with the others)
+//   Taps48      conv_taps48.hip: batched problems of 48-channel taps
+//   Split       conv_gemm_split.hip: the bf16 matrix cores with fp32 operands split into `planes` terms
+//   Invalid     no kernel: an unknown tile id
+enum class ConvEngine { Reg, RegBanded, Ring, RingDealt, RingBanded, RingSK, Taps48, Split, Invalid };
+struct ConvPlan {
+    ConvEngine engine = ConvEngine::Invalid;
+    int bm = 0, bn = 0, wm = 0, wn = 0, bk = 32;   // Reg / Ring / RingDealt: the tile and one wave's share of it
+    int planes = 0;                                // Split
+    ConvBands bands{};                             // RegBanded, RingBanded
+    ConvSK sk{};                                   // RingSK
+};
+// Host only, no HIP call: the plan for a layer.  tile: 0 = the production choice under `k`; otherwise a tile id of ts_op_conv1d_timed
+// (include/talkshow_hip_debug.h).  sk_hw: the device passed the stream-K band's hardware check (conv_sk_supported).
+ConvPlan plan_conv(const ConvParams &p, int tile, const Knobs &k, bool sk_hw);
+hipError_t launch_conv_plan(const ConvParams &p, const ConvPlan &plan, hipStream_t stream);
+hipError_t launch_conv_gemm(const ConvParams &p, int tile, hipStream_t stream);   // = launch_conv_plan(p, plan_conv(p, tile, knobs(), ...))
+
 // conv_gemm_split's XCD-aware tile order (one definition for the kernel and for the host-side test): workgroup `bid` of a 1-D grid of
 // 8 ceil(MT NT / 8) -> tile (tx, ty) of an MT x NT tile grid, false if the workgroup has no tile.  Workgroup ids go round-robin over the 8
 // XCDs; XCD x takes the x-th contiguous eighth of a tile list that runs through column groups of GW tiles, rows inside a group, columns fastest.
@@ -206,6 +224,21 @@ void skinny_tile_weights(const float *W, int N, int K, long ldw, int epi, int ga
 // false if an environment knob forces the generic kernels (which do not read tiled operands)
 bool skinny_descriptor_kernel_enabled();
 hipError_t launch_skinny_gemm(const SkinnyParams &p, hipStream_t stream);
+// Which kernel runs a batch of chain problems (skinny_gemm.hip::plan_skinny): Wide = skinny_wide.hip's 64 x 64 full-K tiles, Fast = the
+// descriptor kernel skinny16_fast_kernel<W, RB, CB> (tiles of RB x CB blocks of 16 x 16, K split over W waves), Generic16 / Generic32 = the
+// row-major kernels with 16- / 32-column workgroups (W waves); Invalid = the problems fit no kernel.
+enum class SkinnyKernel { Wide, Fast, Generic16, Generic32, Invalid };
+struct SkinnyPlan {
+    SkinnyKernel kernel = SkinnyKernel::Invalid;
+    int W = 0, RB = 0, CB = 0;
+    int total = 0;                        // Wide / Fast: workgroups of the 1-D grid
+    int gx = 0, gy = 0;                   // Generic: the (gx, gy, problems) grid
+    int items[SKINNY_MAX_PROBLEMS] = {};  // Wide: tiles per workgroup of each problem
+    int start[SKINNY_MAX_PROBLEMS] = {};  // Wide / Fast: first workgroup of each problem
+};
+// Host only, no HIP call: the plan for n problems under `k`.  Wide and Fast need the descriptors to pack and the zero buffer; where either
+// is missing, launch_skinny_batch runs Generic16 with the plan's W.
+SkinnyPlan plan_skinny(const SkinnyParams *const *ps, int n, const Knobs &k);
 hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream);
 // allocates the per-device zero buffer the fast skinny kernel substitutes for absent operands (call once per device,
 // outside stream capture; without it the generic kernels are used)

@@ -753,170 +753,183 @@ static int skinny_grid(SkinnyParams &p, int ncol) {
     return 0;
 }
 
-bool skinny_descriptor_kernel_enabled();
-
-hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream) {
-    if (n < 1 || n > SKINNY_MAX_PROBLEMS) return hipErrorInvalidValue;
-    SkinnyBatch b;
-    int gx = 0, gy = 0, Q = 0;
-    // column-tile width: 16 (more, leaner workgroups per stage) unless a shape needs the 8-granular 32-column kernel
-    const int ncol_pref = knobs().skinny_nt;
-    int ncol = ncol_pref == 32 ? 32 : 16;
-    if (ncol == 16)
-        for (int i = 0; i < n; ++i) {
-            SkinnyParams t = *ps[i];
-            if (skinny_grid(t, 16)) ncol = 32;
-        }
+// The wide kernel (skinny_wide.hip): a coalesced pass whose launch fills the chip with 64 x 64 full-K tiles.  One tile per workgroup while
+// the launch fits one workgroup per CU.  Beyond that, workgroups of equal work (problems with a fraction of the launch's biggest K get several
+// tiles; an epilogue-only tile counts as 4 q-steps), and as many such units per workgroup as it takes to stay within one round: a workgroup's
+// next tile is prefetched under the epilogue of the current one, a second ROUND of workgroups pays the start-up again.
+static bool plan_wide(const SkinnyParams *b, int n, const Knobs &k, SkinnyPlan &pl) {
+    int wM = 0, Qmax = 0, Qp[SKINNY_MAX_PROBLEMS];
     for (int i = 0; i < n; ++i) {
-        b.p[i] = *ps[i];
-        if (b.p[i].nseg > SKINNY_MAX_SEG || skinny_grid(b.p[i], ncol)) return hipErrorInvalidValue;
-        gx = gx > b.p[i].grid_x ? gx : b.p[i].grid_x;
-        gy = gy > b.p[i].grid_y ? gy : b.p[i].grid_y;
-        Q = Q > b.p[i].Ktot / 8 ? Q : b.p[i].Ktot / 8;
+        if (!skinny_wide_ok(b[i], pl.W, &Qp[i])) return false;
+        wM = wM > b[i].M ? wM : b[i].M;
+        Qmax = Qmax > Qp[i] ? Qmax : Qp[i];
     }
-    dim3 grid(gx, gy, n);
-    // K is split over the waves of the workgroup; more waves = more loads in flight (lower latency for ONE chain) but a
-    // fatter workgroup
-    if (ncol == 16) {   // Q counts 8-k steps: K = 8 Q; the 16-column kernel keeps 8 accumulators -> at most 8 waves
-        const int W16 = Q >= 32 ? 8 : 4;
-        const int variant = knobs().skinny_v;
-        int dev = 0;
-        if (variant != 0 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16 && g_zero[dev]) {
-            SkinnyDescBatch db;
-            bool fast = true;
-            // ---- wide path (skinny_wide.hip): a coalesced pass whose launch fills the chip with 64 x 64 full-K tiles ----
-            const int wide_min = knobs().wide_min;
-            {
-                int wM = 0, Qmax = 0, Qp[SKINNY_MAX_PROBLEMS];
-                bool wide = wide_min > 0;
-                for (int i = 0; i < n && wide; ++i) {
-                    wM = wM > b.p[i].M ? wM : b.p[i].M;
-                    wide = skinny_wide_ok(b.p[i], W16, &Qp[i]);
-                    Qmax = Qmax > Qp[i] ? Qmax : Qp[i];
-                }
-                if (wide && wM >= 64) {
-                    int total = 0, items[SKINNY_MAX_PROBLEMS];
-                    for (int i = 0; i < 8; ++i) db.start[i] = 0x7fffffff;
-                    // one tile per workgroup while the launch fits one workgroup per CU.  Beyond that, workgroups of equal work
-                    // (problems with a fraction of the launch's biggest K get several tiles; an epilogue-only tile counts as 4
-                    // q-steps), and as many such units per workgroup as it takes to stay within one round: a workgroup's next
-                    // tile is prefetched under the epilogue of the current one, a second ROUND of workgroups pays the start-up again
-                    auto count_wgs = [&](int mult) {
-                        int t = 0;
-                        for (int i = 0; i < n; ++i) {
-                            const int cost = Qp[i] > 4 ? Qp[i] : 4;
-                            const int eq = Qmax / cost < 1 ? 1 : (Qmax / cost > 4 ? 4 : Qmax / cost);
-                            items[i] = mult == 0 ? 1 : eq * mult;
-                            const int tiles = (b.p[i].N / 64) * ((b.p[i].M + 63) / 64);
-                            db.start[i] = t;
-                            t += (tiles + items[i] - 1) / items[i];
-                        }
-                        return t;
-                    };
-                    total = count_wgs(0);
-                    for (int mult = 1; total > 256 && mult <= 8; ++mult) total = count_wgs(mult);
-                    if (total >= wide_min) {
-                        for (int i = 0; i < n && wide; ++i) {
-                            wide = skinny_pack_desc(b.p[i], W16, g_zero[dev], db.d[i]);
-                            if (Qp[i] == 0) db.d[i].w[SD_WTQ] = 0, db.d[i].w[SD_NSEG] = 0;   // zero rows: epilogue only
-                            db.d[i].w[SD_ITEMS] = items[i];
-                        }
-                        for (int i = n; i < SKINNY_MAX_PROBLEMS; ++i) std::memset(&db.d[i], 0, sizeof(SkinnyDesc));
-                        if (wide) {
-                            db.start[6] = db.start[7] = 0;
-                            const int wide_abl = knobs().wide_ablate;
-                            db.start[0] = (g_trace_host ? wide_abl : 0) | (knobs().wide_pair ? 8 : 0);   // trace builds only: 2 = no loads, 4 = no MFMAs (problem 0 always starts at workgroup 0)
-                            if (g_trace_host) {
-                                const uint64_t rec = (uint64_t)(uintptr_t)(g_trace_host + (size_t)(g_trace_seq++ % TRACE_LAUNCHES) * TRACE_WGS * TRACE_REC);
-                                db.start[6] = (int)(uint32_t)rec;
-                                db.start[7] = (int)(uint32_t)(rec >> 32);
-                            }
-                            return launch_skinny_wide(db, total, stream, g_trace_host != nullptr);
-                        }
-                    }
-                }
-            }
-            // Tile shape (rows x columns in blocks of 16).  One batch (M <= 32): 16-row tiles when the launch then still
-            // fits one workgroup per CU (less to fetch per CU), else 32 x 16.  Coalesced batches (M >= 64): the biggest of
-            // 64 x 32 / 32 x 32 / 32 x 16 that still spreads the launch over about all CUs (fewer operand bytes per output).
-            constexpr int half_max = 256, fat_min = 200;
-            const int force_shape = knobs().skinny_shape;   // 11, 21, 22, 42 (tests)
-            int maxM = 0, maxcnt = 0;
-            bool even = true;
-            for (int i = 0; i < n; ++i) {
-                maxM = maxM > b.p[i].M ? maxM : b.p[i].M;
-                const int c = b.p[i].Ktot / (16 * W16);
-                maxcnt = maxcnt > c ? maxcnt : c;
-                if (b.p[i].grid_x % 2) even = false;
-            }
-            auto count = [&](int rows, int cb) {
-                int t = 0;
-                for (int i = 0; i < n; ++i) t += (b.p[i].grid_x / cb) * ((b.p[i].M + rows - 1) / rows);
-                return t;
-            };
-            int RB = 2, CB = 1;
-            if (force_shape) {
-                RB = force_shape / 10;
-                CB = force_shape % 10;
-                if (CB > 2) CB = 2;
-                if (RB > 4) RB = 4;
-                if (CB == 2 && (!even || maxcnt > 4)) CB = 1;
-                if (CB == 1 && RB > 2) RB = 2;
-            } else if (maxM <= 32) {
-                if (count(16, 1) <= half_max) RB = 1;
-            } else if (even && maxcnt <= 4) {
-                if (count(64, 2) >= fat_min) { RB = 4; CB = 2; }
-                else if (count(32, 2) >= fat_min) { RB = 2; CB = 2; }
-            }
-            const int rows = RB * 16;
-            int total = 0;
-            for (int i = 0; i < 8; ++i) db.start[i] = 0x7fffffff;
-            for (int i = 0; i < n && fast; ++i) {
-                fast = skinny_pack_desc(b.p[i], W16, g_zero[dev], db.d[i]);
-                db.start[i] = total;
-                total += (b.p[i].grid_x / CB) * ((b.p[i].M + rows - 1) / rows);
-            }
-            for (int i = n; i < SKINNY_MAX_PROBLEMS; ++i) std::memset(&db.d[i], 0, sizeof(SkinnyDesc));
-            if (fast) {
-                const dim3 grid(total);
-                const int trace = knobs().skinny_trace;
-                if (trace) db.start[7] = (int)(g_trace_seq++);
-                const int shape = RB * 10 + CB;
-#define TS_SK_LAUNCH(Wv, R, C)                                                                                         \
-    do {                                                                                                               \
-        if (trace) hipLaunchKernelGGL((skinny16_fast_kernel<Wv, R, C, true>), grid, dim3(Wv * 64), 0, stream, db); \
-        else hipLaunchKernelGGL((skinny16_fast_kernel<Wv, R, C, false>), grid, dim3(Wv * 64), 0, stream, db);     \
-    } while (0)
-                if (W16 == 8) {
-                    if (shape == 11) TS_SK_LAUNCH(8, 1, 1);
-                    else if (shape == 21) TS_SK_LAUNCH(8, 2, 1);
-                    else if (shape == 22) TS_SK_LAUNCH(8, 2, 2);
-                    else TS_SK_LAUNCH(8, 4, 2);
-                } else {
-                    if (shape == 11) TS_SK_LAUNCH(4, 1, 1);
-                    else if (shape == 21) TS_SK_LAUNCH(4, 2, 1);
-                    else if (shape == 22) TS_SK_LAUNCH(4, 2, 2);
-                    else TS_SK_LAUNCH(4, 4, 2);
-                }
-#undef TS_SK_LAUNCH
-                return hipGetLastError();
-            }
+    if (k.wide_min <= 0 || wM < 64) return false;
+    auto count_wgs = [&](int mult) {
+        int t = 0;
+        for (int i = 0; i < n; ++i) {
+            const int cost = Qp[i] > 4 ? Qp[i] : 4;
+            const int eq = Qmax / cost < 1 ? 1 : (Qmax / cost > 4 ? 4 : Qmax / cost);
+            pl.items[i] = mult == 0 ? 1 : eq * mult;
+            const int tiles = (b[i].N / 64) * ((b[i].M + 63) / 64);
+            pl.start[i] = t;
+            t += (tiles + pl.items[i] - 1) / pl.items[i];
         }
-        for (int i = 0; i < n; ++i) {   // the generic kernels read row-major operands only
-            const SkinnyParams &q = b.p[i];
-            bool tiled = q.w_tiled || q.out_tiled_w || q.pre_tiled_w || q.add1_tiled_w;
-            for (int sgi = 0; sgi < q.nseg; ++sgi) tiled = tiled || q.seg[sgi].tiled_w;
-            if (tiled) return hipErrorInvalidValue;
-        }
-        if (W16 == 8) hipLaunchKernelGGL(skinny16_kernel<8>, grid, dim3(512), 0, stream, b);
-        else hipLaunchKernelGGL(skinny16_kernel<4>, grid, dim3(256), 0, stream, b);
+        return t;
+    };
+    pl.total = count_wgs(0);
+    for (int mult = 1; pl.total > 256 && mult <= 8; ++mult) pl.total = count_wgs(mult);
+    if (pl.total >= k.wide_min) return pl.kernel = SkinnyKernel::Wide, true;
+    for (int i = 0; i < n; ++i) pl.items[i] = 0;
+    return false;
+}
+
+// Fast kernel tile shape (rows x columns in blocks of 16).  One batch (M <= 32): 16-row tiles when the launch then still fits one workgroup
+// per CU (less to fetch per CU), else 32 x 16.  Coalesced batches (M >= 64): the biggest of 64 x 32 / 32 x 32 / 32 x 16 that still spreads
+// the launch over about all CUs (fewer operand bytes per output).
+static void plan_fast(const SkinnyParams *b, int n, const Knobs &k, SkinnyPlan &pl) {
+    constexpr int half_max = 256, fat_min = 200;
+    const int force_shape = k.skinny_shape;   // 11, 21, 22, 42 (tests)
+    int maxM = 0, maxcnt = 0;
+    bool even = true;
+    for (int i = 0; i < n; ++i) {
+        maxM = maxM > b[i].M ? maxM : b[i].M;
+        const int c = b[i].Ktot / (16 * pl.W);
+        maxcnt = maxcnt > c ? maxcnt : c;
+        if (b[i].grid_x % 2) even = false;
+    }
+    auto count = [&](int rows, int cb) {
+        int t = 0;
+        for (int i = 0; i < n; ++i) t += (b[i].grid_x / cb) * ((b[i].M + rows - 1) / rows);
+        return t;
+    };
+    int RB = 2, CB = 1;
+    if (force_shape) {
+        RB = force_shape / 10;
+        CB = force_shape % 10;
+        if (CB > 2) CB = 2;
+        if (RB > 4) RB = 4;
+        if (CB == 2 && (!even || maxcnt > 4)) CB = 1;
+        if (CB == 1 && RB > 2) RB = 2;
+    } else if (maxM <= 32) {
+        if (count(16, 1) <= half_max) RB = 1;
+    } else if (even && maxcnt <= 4) {
+        if (count(64, 2) >= fat_min) { RB = 4; CB = 2; }
+        else if (count(32, 2) >= fat_min) { RB = 2; CB = 2; }
+    }
+    pl.kernel = SkinnyKernel::Fast;
+    pl.RB = RB;
+    pl.CB = CB;
+    pl.total = 0;
+    for (int i = 0; i < n; ++i) {
+        pl.start[i] = pl.total;
+        pl.total += (b[i].grid_x / CB) * ((b[i].M + RB * 16 - 1) / (RB * 16));
+    }
+}
+
+SkinnyPlan plan_skinny(const SkinnyParams *const *ps, int n, const Knobs &k) {
+    SkinnyPlan pl;
+    if (n < 1 || n > SKINNY_MAX_PROBLEMS) return pl;
+    // column-tile width: 16 (more, leaner workgroups per stage) unless a shape needs the 8-granular 32-column kernel
+    SkinnyParams b[SKINNY_MAX_PROBLEMS];
+    int ncol = k.skinny_nt == 32 ? 32 : 16, Q = 0;
+    for (int i = 0; i < n; ++i) {
+        b[i] = *ps[i];
+        if (ncol == 16 && skinny_grid(b[i], 16)) ncol = 32;
+    }
+    for (int i = 0; i < n; ++i) {
+        b[i] = *ps[i];
+        if (b[i].nseg > SKINNY_MAX_SEG || skinny_grid(b[i], ncol)) return pl;
+        pl.gx = pl.gx > b[i].grid_x ? pl.gx : b[i].grid_x;
+        pl.gy = pl.gy > b[i].grid_y ? pl.gy : b[i].grid_y;
+        Q = Q > b[i].Ktot / 8 ? Q : b[i].Ktot / 8;
+    }
+    // K is split over the waves of the workgroup; more waves = more loads in flight (lower latency for ONE chain) but a fatter workgroup.
+    // Q counts 8-k steps: K = 8 Q; the 16-column kernels keep 8 accumulators -> at most 8 waves
+    if (ncol == 32) {
+        pl.kernel = SkinnyKernel::Generic32;
+        pl.W = Q >= 64 ? 16 : (Q >= 32 ? 8 : 4);
+        return pl;
+    }
+    pl.kernel = SkinnyKernel::Generic16;
+    pl.W = Q >= 32 ? 8 : 4;
+    if (k.skinny_v != 0 && !plan_wide(b, n, k, pl)) plan_fast(b, n, k, pl);
+    return pl;
+}
+
+// the fast kernel's instances by (W, tile shape, trace): shapes 11, 21, 22 and (any other) 42
+template <int W, int RB, int CB, bool TRACE>
+static void launch_fast(const SkinnyDescBatch &db, int total, hipStream_t s) {
+    hipLaunchKernelGGL((skinny16_fast_kernel<W, RB, CB, TRACE>), dim3(total), dim3(W * 64), 0, s, db);
+}
+using FastLaunch = void (*)(const SkinnyDescBatch &, int, hipStream_t);
+#define TS_FAST_SHAPES(W, T) {launch_fast<W, 1, 1, T>, launch_fast<W, 2, 1, T>, launch_fast<W, 2, 2, T>, launch_fast<W, 4, 2, T>}
+static const FastLaunch fast_instances[2][2][4] = {{TS_FAST_SHAPES(4, false), TS_FAST_SHAPES(4, true)},
+                                                   {TS_FAST_SHAPES(8, false), TS_FAST_SHAPES(8, true)}};
+#undef TS_FAST_SHAPES
+
+// the generic kernels: where the plan is generic, or the zero buffer is missing or a descriptor does not pack
+static hipError_t launch_skinny_generic(const SkinnyBatch &b, int n, const SkinnyPlan &pl, hipStream_t stream) {
+    const dim3 grid(pl.gx, pl.gy, n);
+    if (pl.kernel == SkinnyKernel::Generic32) {
+        if (pl.W >= 16) hipLaunchKernelGGL(skinny_gemm_kernel<16>, grid, dim3(1024), 0, stream, b);
+        else if (pl.W >= 8) hipLaunchKernelGGL(skinny_gemm_kernel<8>, grid, dim3(512), 0, stream, b);
+        else hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, stream, b);
         return hipGetLastError();
     }
-    const int W = Q >= 64 ? 16 : (Q >= 32 ? 8 : 4);
-    if (W >= 16) hipLaunchKernelGGL(skinny_gemm_kernel<16>, grid, dim3(1024), 0, stream, b);
-    else if (W >= 8) hipLaunchKernelGGL(skinny_gemm_kernel<8>, grid, dim3(512), 0, stream, b);
-    else hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, stream, b);
+    for (int i = 0; i < n; ++i) {   // the generic kernels read row-major operands only
+        const SkinnyParams &q = b.p[i];
+        bool tiled = q.w_tiled || q.out_tiled_w || q.pre_tiled_w || q.add1_tiled_w;
+        for (int sgi = 0; sgi < q.nseg; ++sgi) tiled = tiled || q.seg[sgi].tiled_w;
+        if (tiled) return hipErrorInvalidValue;
+    }
+    if (pl.W == 8) hipLaunchKernelGGL(skinny16_kernel<8>, grid, dim3(512), 0, stream, b);
+    else hipLaunchKernelGGL(skinny16_kernel<4>, grid, dim3(256), 0, stream, b);
     return hipGetLastError();
+}
+
+hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream) {
+    const SkinnyPlan pl = plan_skinny(ps, n, knobs());
+    if (pl.kernel == SkinnyKernel::Invalid) return hipErrorInvalidValue;
+    SkinnyBatch b;
+    for (int i = 0; i < n; ++i) {
+        b.p[i] = *ps[i];
+        skinny_grid(b.p[i], pl.kernel == SkinnyKernel::Generic32 ? 32 : 16);
+    }
+    int dev = 0;
+    const bool descriptors = pl.kernel == SkinnyKernel::Wide || pl.kernel == SkinnyKernel::Fast;
+    const float *zero = descriptors && hipGetDevice(&dev) == hipSuccess ? skinny_zero_buffer(dev) : nullptr;
+    SkinnyDescBatch db;
+    bool packed = zero != nullptr;
+    for (int i = 0; i < n && packed; ++i) {
+        packed = skinny_pack_desc(b.p[i], pl.W, zero, db.d[i]);
+        if (pl.kernel == SkinnyKernel::Wide) {
+            int q;
+            if (skinny_wide_ok(b.p[i], pl.W, &q) && q == 0) db.d[i].w[SD_WTQ] = 0, db.d[i].w[SD_NSEG] = 0;   // zero rows: epilogue only
+            db.d[i].w[SD_ITEMS] = pl.items[i];
+        }
+    }
+    if (packed) {
+        for (int i = n; i < SKINNY_MAX_PROBLEMS; ++i) std::memset(&db.d[i], 0, sizeof(SkinnyDesc));
+        for (int i = 0; i < 8; ++i) db.start[i] = i < n ? pl.start[i] : 0x7fffffff;
+        if (pl.kernel == SkinnyKernel::Wide) {
+            db.start[6] = db.start[7] = 0;
+            // trace builds only: 2 = no loads, 4 = no MFMAs (problem 0 always starts at workgroup 0)
+            db.start[0] = (g_trace_host ? knobs().wide_ablate : 0) | (knobs().wide_pair ? 8 : 0);
+            if (g_trace_host) {
+                const uint64_t rec = (uint64_t)(uintptr_t)(g_trace_host + (size_t)(g_trace_seq++ % TRACE_LAUNCHES) * TRACE_WGS * TRACE_REC);
+                db.start[6] = (int)(uint32_t)rec;
+                db.start[7] = (int)(uint32_t)(rec >> 32);
+            }
+            return launch_skinny_wide(db, pl.total, stream, g_trace_host != nullptr);
+        }
+        const int trace = knobs().skinny_trace;
+        if (trace) db.start[7] = (int)(g_trace_seq++);
+        const int shape = pl.RB * 10 + pl.CB;
+        fast_instances[pl.W == 8][trace != 0][shape == 11 ? 0 : shape == 21 ? 1 : shape == 22 ? 2 : 3](db, pl.total, stream);
+        return hipGetLastError();
+    }
+    return launch_skinny_generic(b, n, pl, stream);
 }
 
 // copies the TRACE records to the host and resets the counter; returns the number of records

@@ -319,25 +319,196 @@ def test_pixelcnn_audio_map_columns_must_be_copies():
         GatedPixelCNN._audio_rows(other)
 
 
-def test_conv_ring_tile_choice_by_tile_count():
+ENGINES = ["Reg", "RegBanded", "Ring", "RingDealt", "RingBanded", "RingSK", "Taps48", "Split"]
+CHAIN_KERNELS = ["wide", "fast", "generic16", "generic32"]
+
+
+def conv_plan(lib, M, N, K, groups, sk_ok, lens, tile=0, knobs=None):
+    """ts_debug_conv_plan -> (engine name, tile rows, tile columns, waves), or None for a bad argument."""
+    import ctypes as C
+    out, seg = (C.c_int * 4)(), (C.c_int * len(lens))(*lens)
+    r = lib.ts_debug_conv_plan(M, N, K, groups, sk_ok, seg, len(lens), tile, knobs.encode() if knobs else None, out)
+    return None if r < 0 else (ENGINES[r], out[0], out[1], out[2])
+
+
+def chain_plan(lib, problems, knobs=None):
+    """ts_debug_skinny_plan -> (kernel name, waves, row blocks, column blocks, workgroups); RB / CB are 0 off the fast kernel."""
+    import ctypes as C
+    mnk, out = (C.c_int * (3 * len(problems)))(*[v for p in problems for v in p]), (C.c_int * 4)()
+    r = lib.ts_debug_skinny_plan(mnk, len(problems), knobs.encode() if knobs else None, out)
+    assert r >= 0, problems
+    fast = CHAIN_KERNELS[r] == "fast"
+    return (CHAIN_KERNELS[r], out[0], out[1] if fast else 0, out[2] if fast else 0, out[3])
+
+
+def test_conv_plan_tile_choice_by_tile_count():
     """The ring engine's tile plan for a layer (host-only): rounds of 512 resident workgroups, a last round at most half full costs half a
     round; 128-row tiles, 96-row tiles (5 % more per flop) or bands (128-row tiles for the whole rounds + 64-row tiles, 7 % more per flop, for
-    the rest; reported as 64).  The wav2vec2 blocks at batch 64 x 300 frames: out-proj / FFN2 (N = 768: 900 tiles of 128 rows = 1.76 rounds
+    the rest).  The wav2vec2 blocks at batch 64 x 300 frames: out-proj / FFN2 (N = 768: 900 tiles of 128 rows = 1.76 rounds
     -> 2; 1 200 of 96 rows -> 2.5 x 0.75) take 96-row tiles; FFN1 (7.03 rounds -> 6.98 + half a short one) and the paired body + hand layers of
     a 256-clip pass (2 400 tiles = 4.69 rounds -> 4 + 1.5 short ones) take bands; QKV (5.27 -> 5.5), exact multiples of a round and the long
-    feature convolutions (bands within 2 %) keep 128."""
+    feature convolutions (bands within 2 %) keep 128.  (Whole-tile plans: sk_ok = 0.)"""
     from talkshow_amd import _lib
     lib = _lib.load()
-    assert lib.ts_debug_conv_ring_pick(19200, 768, 1) == 96
-    assert lib.ts_debug_conv_ring_pick(19200, 3072, 1) == 64
-    assert lib.ts_debug_conv_ring_pick(255936, 512, 1) == 128 and lib.ts_debug_conv_ring_pick(511936, 512, 1) == 128
-    assert lib.ts_debug_conv_ring_pick(1023936, 512, 1) == 128 and lib.ts_debug_conv_ring_pick(63936, 512, 1) == 128
-    assert lib.ts_debug_conv_ring_pick(19200, 2304, 1) == 128
-    assert lib.ts_debug_conv_ring_pick(16384, 1024, 1) == 128          # 1 024 tiles: two whole rounds
-    assert lib.ts_debug_conv_ring_pick(8192, 1024, 1) == 128
+    p = lambda M, N, G=1: conv_plan(lib, M, N, 768, G, 0, [768])
+    rows96, rows128, bands = ("RingDealt", 96, 128, 4), ("RingDealt", 128, 128, 8), ("RingBanded", 128, 128, 8)
+    assert p(19200, 768) == rows96
+    assert p(19200, 3072) == bands
+    assert p(255936, 512) == rows128 and p(511936, 512) == rows128
+    assert p(1023936, 512) == rows128 and p(63936, 512) == rows128
+    assert p(19200, 2304) == rows128
+    assert p(16384, 1024) == rows128          # 1 024 tiles: two whole rounds
+    assert p(8192, 1024) == rows128
     for M, N, G in ((19200, 1024, 2), (38400, 512, 2), (76800, 256, 2), (19200, 512, 4)):   # the paired layers of the VQ stacks at 256 clips
-        assert lib.ts_debug_conv_ring_pick(M, N, G) == 64
-    assert lib.ts_debug_conv_ring_pick(0, 64, 1) == -1
+        assert p(M, N, G) == bands
+    assert p(0, 64) is None
+
+
+# Every conv launch of a pass, as the code at the parent of the plan/launch split launched it (recorded per launch on an MI355X):
+# (launches, M, N, K, problems, segment lengths, plan).  A change of the cost model that moves a layer to another kernel changes its bits
+# (the stream-K band) or its speed: it shows here first.
+BODY32_CONV = [   # configs[1], one 32-clip batch: audio encoder + VQ-VAE encode and decode (body + hand layers paired where their shapes agree)
+    (1, 2400, 1024, 2048, 2, [512, 512, 512, 512], ("Reg", 64, 64, 4)), (2, 2400, 1024, 256, 1, [256], ("Reg", 64, 64, 4)),
+    (6, 2400, 1024, 3072, 2, [1024, 1024, 1024], ("Reg", 64, 64, 4)), (3, 2400, 256, 256, 1, [256], ("Reg", 64, 64, 4)),
+    (1, 2400, 256, 512, 1, [128, 128, 128, 128], ("Reg", 64, 64, 4)), (3, 2400, 256, 768, 1, [256, 256, 256], ("Reg", 64, 64, 4)),
+    (1, 2400, 512, 2048, 4, [1024, 1024], ("Reg", 64, 64, 4)), (1, 2400, 512, 256, 1, [256], ("Reg", 128, 64, 4)),
+    (1, 2400, 64, 1024, 2, [1024], ("Reg", 64, 64, 4)), (1, 4800, 128, 256, 1, [64, 64, 64, 64], ("Reg", 64, 64, 4)),
+    (3, 4800, 128, 384, 1, [128, 128, 128], ("Reg", 64, 64, 4)), (1, 4800, 256, 1024, 4, [512, 512], ("Reg", 64, 64, 4)),
+    (1, 4800, 512, 1024, 2, [256, 256, 256, 256], ("Reg", 64, 64, 4)), (6, 4800, 512, 1536, 2, [512, 512, 512], ("Reg", 64, 64, 4)),
+    (1, 9600, 256, 192, 1, [64, 64, 64], ("Reg", 64, 64, 4)), (1, 9600, 256, 288, 1, [96, 96, 96], ("Reg", 64, 64, 4)),
+    (6, 9600, 256, 768, 2, [256, 256, 256], ("Reg", 64, 64, 4)), (1, 9600, 39, 256, 1, [256], ("Reg", 64, 64, 4)),
+    (4, 9600, 64, 192, 1, [64, 64, 64], ("Reg", 64, 64, 4)), (1, 9600, 90, 256, 1, [256], ("Reg", 128, 64, 4)),
+]
+BODY256_CONV = [  # configs[1], one 256-clip pass (8 batches of 32)
+    (1, 19200, 1024, 2048, 2, [512, 512, 512, 512], ("RingBanded", 128, 128, 8)), (2, 19200, 1024, 256, 1, [256], ("RingDealt", 128, 128, 8)),
+    (6, 19200, 1024, 3072, 2, [1024, 1024, 1024], ("RingBanded", 128, 128, 8)), (3, 19200, 256, 256, 1, [256], ("Reg", 64, 64, 4)),
+    (1, 19200, 256, 512, 1, [128, 128, 128, 128], ("Reg", 64, 64, 4)), (3, 19200, 256, 768, 1, [256, 256, 256], ("Reg", 64, 64, 4)),
+    (1, 19200, 512, 2048, 4, [1024, 1024], ("RingBanded", 128, 128, 8)), (1, 19200, 512, 256, 1, [256], ("Reg", 128, 64, 4)),
+    (1, 19200, 64, 1024, 2, [1024], ("Reg", 64, 64, 4)), (1, 38400, 128, 256, 1, [64, 64, 64, 64], ("Reg", 64, 64, 4)),
+    (3, 38400, 128, 384, 1, [128, 128, 128], ("Reg", 64, 64, 4)), (1, 38400, 256, 1024, 4, [512, 512], ("RingBanded", 128, 128, 8)),
+    (1, 38400, 512, 1024, 2, [256, 256, 256, 256], ("RingBanded", 128, 128, 8)), (6, 38400, 512, 1536, 2, [512, 512, 512], ("RingBanded", 128, 128, 8)),
+    (1, 76800, 256, 192, 1, [64, 64, 64], ("RingDealt", 128, 128, 8)), (1, 76800, 256, 288, 1, [96, 96, 96], ("RingDealt", 128, 128, 8)),
+    (6, 76800, 256, 768, 2, [256, 256, 256], ("RingBanded", 128, 128, 8)), (1, 76800, 39, 256, 1, [256], ("Reg", 64, 64, 4)),
+    (4, 76800, 64, 192, 1, [64, 64, 64], ("Reg", 64, 64, 4)), (1, 76800, 90, 256, 1, [256], ("Reg", 128, 64, 4)),
+]
+FACE64_CONV = [   # configs[2], the face generator at batch 64 x 10 s (every GEMM sets sk_ok)
+    (1, 1023936, 512, 1536, 1, [512, 512, 512], ("RingDealt", 128, 128, 8)),   # feature convolutions 1-6
+    (1, 511936, 512, 1536, 1, [512, 512, 512], ("RingDealt", 128, 128, 8)), (1, 255936, 512, 1536, 1, [512, 512, 512], ("RingDealt", 128, 128, 8)),
+    (1, 127936, 512, 1536, 1, [512, 512, 512], ("RingDealt", 128, 128, 8)), (1, 63936, 512, 1024, 1, [512, 512], ("RingDealt", 128, 128, 8)),
+    (1, 31936, 512, 1024, 1, [512, 512], ("RingDealt", 128, 128, 8)),
+    (1, 19200, 768, 512, 1, [512], ("RingDealt", 96, 128, 4)),                # feature projection
+    (1, 19200, 48, 6144, 16, [48], ("Taps48", 0, 0, 0)),                       # positional convolution: 16 groups of 48 channels x 128 taps
+    (12, 19200, 2304, 768, 1, [768], ("RingDealt", 128, 128, 8)),             # QKV
+    (12, 19200, 768, 768, 1, [768], ("RingDealt", 96, 128, 4)),               # out-proj
+    (12, 19200, 3072, 768, 1, [768], ("RingBanded", 128, 128, 8)),            # FFN1
+    (12, 19200, 768, 3072, 1, [3072], ("RingSK", 128, 128, 8)),               # FFN2: the only stream-K band
+    (1, 19200, 100, 256, 1, [256], ("Reg", 64, 64, 4)), (1, 19200, 256, 768, 1, [768], ("Reg", 64, 64, 4)),   # heads
+    (5, 19200, 256, 768, 1, [256, 256, 256], ("Reg", 64, 64, 4)), (2, 19200, 256, 960, 1, [320, 320, 320], ("Reg", 64, 64, 4)),
+    (1, 19200, 3, 64, 1, [64], ("Reg", 128, 64, 4)), (2, 19200, 64, 192, 1, [64, 64, 64], ("Reg", 128, 64, 4)),
+    (1, 19200, 64, 768, 1, [256, 256, 256], ("Reg", 128, 64, 4)),
+]
+
+
+def test_production_conv_layer_plans_are_pinned():
+    """which kernel every production conv layer gets under the default cost model — the configs[1] body layers of a 32-clip
+    batch and of a 256-clip pass, the face generator's 69 launches at batch 64 — and, since the stream-K band makes a row's bits depend on M,
+    exactly which face layers take it (FFN2 of the 12 encoder blocks)."""
+    from talkshow_amd import _lib
+    lib = _lib.load()
+    for table, sk_ok in ((BODY32_CONV, 0), (BODY256_CONV, 0), (FACE64_CONV, 1)):
+        for n, M, N, K, G, lens, want in table:
+            assert conv_plan(lib, M, N, K, G, sk_ok, lens) == want, (M, N, K, G, lens)
+    assert sum(r[0] for r in FACE64_CONV) == 69
+    assert [(r[1], r[2], r[3]) for r in FACE64_CONV if r[6][0] == "RingSK"] == [(19200, 768, 3072)]
+    # without sk_ok (the body path) the same shape never gets the band
+    assert conv_plan(lib, 19200, 768, 3072, 1, 0, [3072]) == ("RingDealt", 96, 128, 4)
+
+
+# Every chain launch of one code-row sweep (the stages of the vertical and horizontal stacks, the next-row projections, the heads) as the code
+# at the parent of the plan/launch split launched it: (launches per pass, problems as (M, N, K); negative K = an epilogue-only block of zero
+# rows, plan = (kernel, waves, row blocks, column blocks, workgroups)).
+CHAIN32 = [
+    (1, [(32, 1024, -128)], ("fast", 4, 1, 1, 128)), (38, [(32, 2048, 512)], ("fast", 8, 1, 1, 256)),
+    (19, [(32, 512, 512)], ("fast", 8, 1, 1, 64)), (19, [(32, 1024, 512), (32, 512, 256)], ("fast", 8, 1, 1, 192)),
+    (19, [(32, 512, 256), (32, 512, 512)], ("fast", 8, 1, 1, 128)), (19, [(32, 512, 512), (32, 256, 256)], ("fast", 8, 1, 1, 96)),
+    (19, [(64, 512, 512), (32, 1024, 512)], ("fast", 8, 2, 1, 128)),
+    (19, [(32, 1024, 512), (32, 512, 256), (32, 256, 256)], ("fast", 8, 1, 1, 224)),
+    (228, [(32, 1024, 512), (32, 512, 512), (32, 256, 256)], ("fast", 8, 1, 1, 224)),
+    (18, [(32, 1024, 512), (32, 1024, 512), (32, 1024, 512)], ("fast", 8, 2, 1, 192)),
+    (19, [(32, 1024, 512), (64, 512, 512), (32, 512, -128)], ("fast", 8, 2, 1, 160)),
+    (19, [(32, 512, 256), (32, 512, 512), (32, 256, 256)], ("fast", 8, 1, 1, 160)),
+    (19, [(32, 1024, 512), (64, 512, 512), (32, 512, 256), (32, 256, 256)], ("fast", 8, 2, 1, 176)),
+    (19, [(64, 512, 512), (32, 512, 256), (32, 512, 512), (32, 256, 256)], ("fast", 8, 2, 1, 144)),
+    (209, [(32, 1024, 512), (64, 512, 512), (32, 512, 256), (32, 512, 512), (32, 256, 256)], ("fast", 8, 2, 1, 208)),
+]
+CHAIN256 = [
+    (1, [(256, 1024, -128)], ("fast", 4, 2, 2, 256)), (38, [(256, 2048, 512)], ("fast", 8, 4, 2, 256)),
+    (19, [(256, 512, 256)], ("fast", 8, 2, 1, 256)), (19, [(256, 512, 512)], ("fast", 8, 2, 1, 256)),
+    (19, [(256, 512, 256), (256, 512, 512)], ("fast", 8, 2, 2, 256)), (19, [(256, 512, 256), (256, 256, 256)], ("fast", 8, 2, 1, 384)),
+    (247, [(256, 512, 512), (256, 256, 256)], ("fast", 8, 2, 1, 384)),
+    (18, [(256, 1024, 512), (256, 1024, 512), (256, 1024, 512)], ("wide", 8, 0, 0, 192)),
+    (19, [(256, 512, 256), (256, 512, 512), (256, 256, 256)], ("fast", 8, 2, 2, 320)),
+    (19, [(512, 512, 512), (256, 1024, 512), (256, 1024, 512)], ("wide", 8, 0, 0, 192)),
+    (19, [(256, 1024, 512), (256, 1024, 512), (512, 512, 512), (256, 512, -128)], ("wide", 8, 0, 0, 224)),
+    (19, [(512, 512, 512), (256, 512, 256), (256, 512, 512), (256, 256, 256)], ("fast", 8, 4, 2, 288)),
+    (19, [(256, 1024, 512), (256, 1024, 512), (512, 512, 512), (256, 512, 256), (256, 256, 256)], ("wide", 8, 0, 0, 240)),
+    (209, [(256, 1024, 512), (256, 1024, 512), (512, 512, 512), (256, 512, 256), (256, 512, 512), (256, 256, 256)], ("wide", 8, 0, 0, 248)),
+]
+
+
+def test_production_chain_plans_are_pinned():
+    """The PixelCNN chain's kernel for every launch kind of a code row at 32 clips and in a 256-clip pass (a 256-clip pass
+    uses the wide kernel, fast<8,2,1>, fast<8,4,2> and fast<8,2,2>)."""
+    from talkshow_amd import _lib
+    lib = _lib.load()
+    for table in (CHAIN32, CHAIN256):
+        for n, problems, want in table:
+            assert chain_plan(lib, problems) == want, problems
+    used = {(w[0], w[2], w[3]) for n, p, w in CHAIN256 if w[1] == 8}
+    assert used == {("wide", 0, 0), ("fast", 2, 1), ("fast", 4, 2), ("fast", 2, 2)}
+
+
+def test_knob_settings_force_their_paths():
+    """The settings of tests/test_gpu_parity.py::test_alternate_kernel_paths, evaluated through the plans with an explicit knob list (no child
+    process): each forces the path its id names on the production shapes, and the settings that are not plan levers (graph replay, where the
+    next-row projections run) leave every plan as it is."""
+    from talkshow_amd import _lib
+    lib = _lib.load()
+    convs = [(r, 0) for r in BODY32_CONV + BODY256_CONV] + [(r, 1) for r in FACE64_CONV]
+    chains = CHAIN32 + CHAIN256
+    cplan = lambda knobs: [conv_plan(lib, M, N, K, G, sk, lens, knobs=knobs) for (n, M, N, K, G, lens, w), sk in convs]
+    kplan = lambda knobs: [chain_plan(lib, p, knobs) for n, p, w in chains]
+    assert cplan(None) == [r[6] for r, sk in convs] and kplan(None) == [w for n, p, w in chains]
+    for knobs in ("TS_NO_GRAPH=1", "TS_PIX_DEFER_P=0", "TS_PIX_DEFER_P=1", "TS_VQ_LDS=0", "TS_W2V_MOMENTS=0"):
+        assert cplan(knobs) == cplan(None) and kplan(knobs) == kplan(None), knobs
+    # chain kernels
+    assert {p[0] for p in kplan("TS_SKINNY_V=0")} == {"generic16"}                                          # generic_skinny_kernel
+    assert {p[0] for p in kplan("TS_SKINNY_NT=32")} == {"generic32"}                                        # skinny_32col_kernel
+    for knobs, rb_cb in (("TS_SKINNY_SHAPE=22", (2, 2)), ("TS_SKINNY_SHAPE=42", (4, 2))):                # tile_32x32, tile_64x32
+        plans = kplan(knobs)
+        assert {p[0] for p in plans} <= {"fast", "wide"} and (("fast",) + rb_cb) in {(p[0], p[2], p[3]) for p in plans}, knobs
+        assert {(p[2], p[3]) for p in plans if p[0] == "fast"} <= {rb_cb, (2, 1)}   # 2 x 1 where the columns are odd or K too deep
+    assert "wide" not in {p[0] for p in kplan("TS_SKINNY_TILED=0")}                                         # row_major_operands
+    assert "wide" not in {p[0] for p in kplan("TS_SKINNY_WIDE_MIN=0")}                                      # split_k_kernels_only
+    everywhere = kplan("TS_SKINNY_WIDE_MIN=1,TS_SKINNY_WIDE_PAIR=0")                                       # wide_kernel_everywhere_column_major
+    assert [p[0] == "wide" for p in everywhere] == [max(m for m, _, _ in pr) >= 64 for n, pr, w in chains]
+    # conv engines
+    assert {p[0] for p in cplan("TS_VQ_LDS=0,TS_CONV_RING=0")} <= {"Reg", "RegBanded", "Taps48"}            # register_staged_conv
+    plain = cplan("TS_CONV_DEAL=0,TS_CONV_TAPS48=0,TS_W2V_MOMENTS=0")                                      # ring_conv_on_a_plain_grid_and_padded_positional_conv
+    assert {p[0] for p in plain} == {"Reg", "Ring"}
+    assert [p[0] == "Ring" for p in plain] == [r[6][0].startswith("Ring") for r, sk in convs]
+    paired = cplan("TS_CONV_RING_PAIRED=0")                                                                  # paired_layers_on_the_register_staged_banded_launch
+    for (r, sk), p in zip(convs, paired):
+        assert p == (("RegBanded", 128, 128, 4) if r[4] > 1 and r[6][0].startswith("Ring") else r[6]), r
+    assert "RingSK" not in {p[0] for p in cplan("TS_CONV_SK=0")}                                             # face_gemms_without_the_stream_k_band
+    forced = cplan("TS_CONV_SK=2")                                                                           # face_gemms_with_the_stream_k_band_wherever_a_plan_exists
+    import ctypes as C
+    o6 = (C.c_int * 6)()
+    for (r, sk), p in zip(convs, forced):
+        ring = r[6][0] in ("RingDealt", "RingBanded", "RingSK")
+        has = ring and sk == 1 and r[4] == 1 and lib.ts_debug_conv_sk_plan(r[1], r[2], r[3], 1, o6) == 1
+        assert (p[0] == "RingSK") == has and (has or p == r[6]), r
+    assert sum(p[0] == "RingSK" for p in forced) > 1
 
 
 def test_stream_k_band_plan_and_runs():
