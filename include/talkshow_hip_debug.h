@@ -78,6 +78,43 @@ int ts_debug_conv_plan(int M, int N, int Ktot, int groups, int sk_ok, const int 
  * knob_list as for ts_debug_conv_plan.  Returns the kernel — 0 wide (skinny_wide.hip), 1 fast (the descriptor kernel), 2 generic 16-column,
  * 3 generic 32-column — with out4 = {waves, row blocks of 16, column blocks of 16 (fast), workgroups}, or -1 on a bad argument. */
 int ts_debug_skinny_plan(const int *mnk, int n, const char *knob_list, int *out4);
+/* Test aid: one launch of up to 6 INDEPENDENT PixelCNN chain problems (csrc/kernels.h, SkinnySeg / SkinnyParams: the fields below mirror
+ * them one for one; Ktot is the sum of the segment lengths; every pointer is a device pointer the caller owns) through the production
+ * plan, descriptor packing and launch code (launch_skinny_batch) under knob_list ("NAME=VALUE,..." as for ts_debug_skinny_plan, null =
+ * the defaults; TS_SKINNY_TRACE is refused).  Allocates and uploads nothing; does not synchronize `stream`.  Returns the kernel that
+ * ran (0 wide, 1 fast, 2 generic 16-column, 3 generic 32-column: a wide or fast plan whose descriptors do not pack runs generic
+ * 16-column) with out5 = {kernel, waves, row blocks of 16, column blocks of 16 (fast), workgroups (generic: the grid's, problems
+ * included)}, or -1 with ts_last_error() set: a bad argument, problems that fit no kernel, tiled operands on a generic kernel. */
+typedef struct ts_debug_skinny_seg {
+    const float *base;   /* dense: row m at base + (m >> row_shift) * row_stride; null (without gidx) = zero rows */
+    const int *gidx;     /* gather: row = base + gidx[m * gidx_stride] * row_stride; a negative index = a zero row */
+    long row_stride, gidx_stride;
+    int row_shift, len, tiled_w;
+} ts_debug_skinny_seg;
+typedef struct ts_debug_skinny_problem {
+    int M, N, nseg;
+    ts_debug_skinny_seg seg[3];
+    const float *W;
+    long ldw;
+    const float *bias;
+    const float *add1;
+    long add1_stride;
+    int add1_shift;
+    const float *add2;
+    long add2_stride;
+    int add2_shift;
+    const float *add3;
+    long add3_stride;
+    const float *clsrow;
+    int cls_ld;
+    int epi, relu, gateD;   /* epi 0 linear, 1 gate */
+    float *out;
+    long out_stride;
+    float *pre;
+    long pre_stride;
+    int w_tiled, out_tiled_w, pre_tiled_w, add1_tiled_w;
+} ts_debug_skinny_problem;
+int ts_debug_skinny_run(ts_ctx *ctx, const ts_debug_skinny_problem *problems, int n, const char *knob_list, int *out5, void *stream);
 /* Host-only helper (no GPU needed): the stream-K plan of the ring engine for `groups` problems of M rows x N columns x K (csrc/conv_gemm_ring.hip:
  * whole 128 x 128 tiles for the row tiles that fill whole units of 256 tiles, the rows after them as one list of (tile, 32-k stage) iterations
  * cut into equal runs).  1 = out6 = {row tiles kept whole, row tiles in the band, dealt ids of the whole-tile region, band workgroups,

@@ -24,6 +24,22 @@ class TsTensor(C.Structure):
 
 _vp, _i, _i64, _u64, _fp = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.POINTER(C.c_float)
 
+
+class SkinnySeg(C.Structure):
+    """ts_debug_skinny_seg (include/talkshow_hip_debug.h)."""
+    _fields_ = [("base", _vp), ("gidx", _vp), ("row_stride", C.c_long), ("gidx_stride", C.c_long), ("row_shift", _i), ("len", _i),
+                ("tiled_w", _i)]
+
+
+class SkinnyProblem(C.Structure):
+    """ts_debug_skinny_problem (include/talkshow_hip_debug.h): one chain problem, the fields of csrc/kernels.h::SkinnyParams."""
+    _fields_ = [("M", _i), ("N", _i), ("nseg", _i), ("seg", SkinnySeg * 3), ("W", _vp), ("ldw", C.c_long), ("bias", _vp),
+                ("add1", _vp), ("add1_stride", C.c_long), ("add1_shift", _i), ("add2", _vp), ("add2_stride", C.c_long), ("add2_shift", _i),
+                ("add3", _vp), ("add3_stride", C.c_long), ("clsrow", _vp), ("cls_ld", _i), ("epi", _i), ("relu", _i), ("gateD", _i),
+                ("out", _vp), ("out_stride", C.c_long), ("pre", _vp), ("pre_stride", C.c_long), ("w_tiled", _i), ("out_tiled_w", _i),
+                ("pre_tiled_w", _i), ("add1_tiled_w", _i)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "ts_ctx_create": (_i, [_i, C.POINTER(_vp)]),
@@ -86,6 +102,7 @@ SIGNATURES = {
     "ts_pixelcnn_prepare": (_i, [_vp, _i, _i, _i, _vp]),
     "ts_debug_conv_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_plan": (_i, [C.POINTER(_i), _i, C.c_char_p, C.POINTER(_i)]),
+    "ts_debug_skinny_run": (_i, [_vp, C.POINTER(SkinnyProblem), _i, C.c_char_p, C.POINTER(_i), _vp]),
     "ts_debug_gate_act": (_i, [_vp, _vp, _vp, C.c_long, _vp]),
     "ts_debug_gelu": (_i, [_vp, _vp, C.c_long, _vp]),
     "ts_debug_attention": (_i, [_vp, _i, _i, _i, _i, C.c_float, _vp, _vp]),

@@ -392,6 +392,65 @@ int ts_debug_skinny_plan(const int *mnk, int n, const char *knob_list, int *out4
     return (int)pl.kernel;
 }
 
+int ts_debug_skinny_run(ts_ctx *ctx, const ts_debug_skinny_problem *pr, int n, const char *knob_list, int *out5, void *stream) {
+    if (!ctx || !pr || !out5 || n < 1 || n > ts::SKINNY_MAX_PROBLEMS) return fail("ts_debug_skinny_run: bad argument") ? -1 : -1;
+    if (knob_list && std::strstr(knob_list, "TS_SKINNY_TRACE"))   // the record buffer only exists when the environment asked for it
+        return fail("ts_debug_skinny_run: TS_SKINNY_TRACE is not a knob of this entry") ? -1 : -1;
+    ts::SkinnyParams q[ts::SKINNY_MAX_PROBLEMS];
+    const ts::SkinnyParams *ps[ts::SKINNY_MAX_PROBLEMS];
+    for (int i = 0; i < n; ++i) {
+        const ts_debug_skinny_problem &d = pr[i];
+        if (d.M < 1 || d.N < 1 || d.nseg < 1 || d.nseg > ts::SKINNY_MAX_SEG || !d.W || !d.out) return fail("ts_debug_skinny_run: bad problem") ? -1 : -1;
+        ts::SkinnyParams &p = q[i];
+        std::memset(&p, 0, sizeof(p));
+        p.M = d.M;
+        p.N = d.N;
+        p.nseg = d.nseg;
+        for (int k = 0; k < d.nseg; ++k) {
+            const ts_debug_skinny_seg &g = d.seg[k];
+            if (g.len < 1) return fail("ts_debug_skinny_run: empty segment") ? -1 : -1;
+            p.seg[k] = ts::SkinnySeg{g.base, g.gidx, g.row_stride, g.gidx_stride, g.row_shift, g.len, g.tiled_w};
+            p.Ktot += g.len;
+        }
+        p.W = d.W;
+        p.ldw = d.ldw;
+        p.bias = d.bias;
+        p.add1 = d.add1;
+        p.add1_stride = d.add1_stride;
+        p.add1_shift = d.add1_shift;
+        p.add2 = d.add2;
+        p.add2_stride = d.add2_stride;
+        p.add2_shift = d.add2_shift;
+        p.add3 = d.add3;
+        p.add3_stride = d.add3_stride;
+        p.clsrow = d.clsrow;
+        p.cls_ld = d.cls_ld;
+        p.epi = d.epi;
+        p.relu = d.relu;
+        p.gateD = d.gateD;
+        p.out = d.out;
+        p.out_stride = d.out_stride;
+        p.pre = d.pre;
+        p.pre_stride = d.pre_stride;
+        p.w_tiled = d.w_tiled;
+        p.out_tiled_w = d.out_tiled_w;
+        p.pre_tiled_w = d.pre_tiled_w;
+        p.add1_tiled_w = d.add1_tiled_w;
+        ps[i] = &p;
+    }
+    ts::SkinnyPlan ran;
+    const hipError_t e = ts::launch_skinny_batch(ps, n, (hipStream_t)stream, ts::knobs_from_list(knob_list), &ran);
+    if (ran.kernel == ts::SkinnyKernel::Invalid) return fail("ts_debug_skinny_run: the problems fit no kernel") ? -1 : -1;
+    if (e != hipSuccess) return fail(std::string("ts_debug_skinny_run: ") + hipGetErrorString(e)) ? -1 : -1;
+    const bool grid1d = ran.kernel == ts::SkinnyKernel::Wide || ran.kernel == ts::SkinnyKernel::Fast;
+    out5[0] = (int)ran.kernel;
+    out5[1] = ran.W;
+    out5[2] = ran.RB;
+    out5[3] = ran.CB;
+    out5[4] = grid1d ? ran.total : ran.gx * ran.gy * n;
+    return (int)ran.kernel;
+}
+
 int ts_debug_conv_sk_plan(int M, int N, int K, int groups, int *out6) {
     if (M < 1 || N < 1 || K < 32 || K % 32 || groups < 1 || groups > 4 || !out6) return -1;
     ts::ConvParams p;

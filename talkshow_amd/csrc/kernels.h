@@ -239,7 +239,10 @@ struct SkinnyPlan {
 // Host only, no HIP call: the plan for n problems under `k`.  Wide and Fast need the descriptors to pack and the zero buffer; where either
 // is missing, launch_skinny_batch runs Generic16 with the plan's W.
 SkinnyPlan plan_skinny(const SkinnyParams *const *ps, int n, const Knobs &k);
-hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream);
+hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream);   // = the form below under knobs()
+// the same launch under the levers `k` (a trace instance only where skinny_init made the record buffer); ran (optional) = the plan that
+// actually launched: a Wide or Fast plan whose descriptors did not pack, or without the zero buffer, reports Generic16 with the plan's W
+hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream, const Knobs &k, SkinnyPlan *ran);
 // allocates the per-device zero buffer the fast skinny kernel substitutes for absent operands (call once per device,
 // outside stream capture; without it the generic kernels are used)
 hipError_t skinny_init(int device);

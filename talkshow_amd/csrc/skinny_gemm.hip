@@ -10,11 +10,15 @@
 // terms (v->h contribution / residual / audio term), the class conditioning and the tanh*sigmoid gate: a tile's
 // columns are "tanh" channels followed by their "sigmoid" partners, so the gate is one cross-lane exchange.
 //
-// Three kernels, one contract (bit-identical results):
+// Three kernels here and the wide kernel (skinny_wide.hip):
 //   skinny16_fast_kernel  production path: 64-dword problem descriptors, branch-free loads, exact 1-D grid, 16- or
 //                         32-row tiles (see the comment above it; tools/skinny_trace.py is its in-kernel profiler)
 //   skinny16_kernel       generic 16-column kernel: any K multiple of 16, any segment layout (small / odd models)
 //   skinny_gemm_kernel    generic 32-column kernel on the 32x32x2 MFMA: K multiple of 8
+// The contract: at the same wave count W (plan_skinny: 8 from K >= 256, else 4), skinny16_kernel<W>, skinny16_fast_kernel<W, RB, CB>
+// at every tile shape and the wide kernel give bit-identical results (same K split, same MFMA, same summation order).
+// skinny_gemm_kernel does not: its 8-k steps group the products differently, so its results are only within fp32 rounding of
+// theirs, at every W (tests/test_gpu_chain_ops.py::test_kernels_bit_identical pins both).
 #include <cstdlib>
 #include <cstring>
 #include <cstdint>
@@ -888,8 +892,9 @@ static hipError_t launch_skinny_generic(const SkinnyBatch &b, int n, const Skinn
     return hipGetLastError();
 }
 
-hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream) {
-    const SkinnyPlan pl = plan_skinny(ps, n, knobs());
+hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream, const Knobs &k, SkinnyPlan *ran) {
+    const SkinnyPlan pl = plan_skinny(ps, n, k);
+    if (ran) *ran = pl;
     if (pl.kernel == SkinnyKernel::Invalid) return hipErrorInvalidValue;
     SkinnyBatch b;
     for (int i = 0; i < n; ++i) {
@@ -915,7 +920,7 @@ hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t
         if (pl.kernel == SkinnyKernel::Wide) {
             db.start[6] = db.start[7] = 0;
             // trace builds only: 2 = no loads, 4 = no MFMAs (problem 0 always starts at workgroup 0)
-            db.start[0] = (g_trace_host ? knobs().wide_ablate : 0) | (knobs().wide_pair ? 8 : 0);
+            db.start[0] = (g_trace_host ? k.wide_ablate : 0) | (k.wide_pair ? 8 : 0);
             if (g_trace_host) {
                 const uint64_t rec = (uint64_t)(uintptr_t)(g_trace_host + (size_t)(g_trace_seq++ % TRACE_LAUNCHES) * TRACE_WGS * TRACE_REC);
                 db.start[6] = (int)(uint32_t)rec;
@@ -923,13 +928,25 @@ hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t
             }
             return launch_skinny_wide(db, pl.total, stream, g_trace_host != nullptr);
         }
-        const int trace = knobs().skinny_trace;
+        const int trace = g_trace_host ? k.skinny_trace : 0;   // the trace instances need the record buffer skinny_init made
         if (trace) db.start[7] = (int)(g_trace_seq++);
         const int shape = pl.RB * 10 + pl.CB;
         fast_instances[pl.W == 8][trace != 0][shape == 11 ? 0 : shape == 21 ? 1 : shape == 22 ? 2 : 3](db, pl.total, stream);
         return hipGetLastError();
     }
+    if (ran && pl.kernel != SkinnyKernel::Generic32) {   // a Wide or Fast plan whose descriptors did not pack runs Generic16 at its W
+        const int W = pl.W;
+        *ran = SkinnyPlan{};
+        ran->kernel = SkinnyKernel::Generic16;
+        ran->W = W;
+        ran->gx = pl.gx;
+        ran->gy = pl.gy;
+    }
     return launch_skinny_generic(b, n, pl, stream);
+}
+
+hipError_t launch_skinny_batch(const SkinnyParams *const *ps, int n, hipStream_t stream) {
+    return launch_skinny_batch(ps, n, stream, knobs(), nullptr);
 }
 
 // copies the TRACE records to the host and resets the counter; returns the number of records
