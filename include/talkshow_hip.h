@@ -140,7 +140,9 @@ int ts_pixelcnn_generate(ts_pixelcnn *pix, const int64_t *label_dev, const float
  * most 24 unpinned graphs per stream are kept (8 whole-call + 16 chunk / streaming-step graphs), least recently used of its class out
  * first, destroyed behind an event (no host-side wait).  A serving host
  * that knows its pass shapes calls ts_pixelcnn_prepare once per (stream, shape): the whole-call graph is captured there (nothing
- * runs), pinned (never evicted; at most 12 per stream) and the first real call is already one replay. */
+ * runs), pinned (never evicted; at most 12 per stream) and the first real call is already one replay.
+ * Mixed passes (ts_body_pixel_infer_mixed) run on chunk graphs only, keyed by (active clips, rows, phase, mode, clips of the pass): at most
+ * 12 distinct active clip counts per pass, more are rounded UP to multiples of 2, 4, 8, ... — the rule is stated at that entry. */
 int ts_pixelcnn_prepare(ts_pixelcnn *pix, int B, int H, int mode, void *stream);
 /* hipGraphs captured + instantiated on `stream` since the handle was created, or -1 (a serving loop checks that this stands still
  * once it is warm; bench.py asserts it over its timed regions). */
@@ -209,6 +211,45 @@ int ts_body_pixel_infer(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_bod
                         const float *mfcc_dev, const int64_t *ids_dev, int B, int T, int mode,
                         const float *uniforms_dev, uint64_t seed, int64_t clip_index0, int64_t *codes_dev,
                         float *poses_dev, void *stream);
+/* ---- mixed passes: clips of DIFFERENT lengths in one pass (no counterpart in the reference, whose loops run one clip at a time) ------
+ * B clips, clip b with lens[b] MFCC rows, padded to T_max rows each; H_b = lens[b] / 4 code rows and 4 H_b pose frames, the arithmetic of
+ * ts_body_pixel_infer.  A clip's codes and poses are BIT-IDENTICAL to what ts_body_pixel_infer gives for the clip alone (or in any other
+ * pass): the conv stacks store zeros for every row beyond a clip's own length — the operand a clip run alone reads past its ends — and the
+ * chain computes row r for the clips that have it.
+ *   lens_host / lens_dev (B,) int32: the same table in host memory (planning never synchronises; not read after the call returns) and in
+ *     device memory.  4 <= lens[b] <= T_max, NON-INCREASING (the active clips of a row are then a prefix of every buffer); anything else is
+ *     an error.  The caller sorts (nets/smplx_body_pixel.py: generate_batches / generate_clips sort and un-sort).
+ *   mfcc_dev (B,T_max,64): rows at or beyond lens[b] are never read (they may hold anything, NaNs included).
+ *   uniforms_dev (B,H_max,2), H_max = T_max / 4, for TS_SAMPLE_UNIFORMS; rows at or beyond H_b are not read.
+ *   clip_index_dev (B,) int64 or NULL: the Philox subsequence of every clip, in place of `clip_index0 + b` (sorting by length breaks
+ *     that rule; with the table a clip's draws depend on its GLOBAL index only).  NULL: clip b draws from subsequence b.  Copied into
+ *     the library's own buffer on the stream: graphs stay replayable and any number of calls may be queued.
+ *   codes_dev (B,H_max,2): rows r < H_b = the clip's codes; rows r >= H_b are written as -1.
+ *   poses_dev (B,4 H_max,body_dim+hand_dim): rows t < 4 H_b = the clip's poses; rows t >= 4 H_b are written as 0.
+ *   Every element of both outputs is written, nothing else is touched.
+ * Graph policy of a mixed pass: chunk graphs only (8 code rows each, as for first-time shapes of ts_pixelcnn_generate), keyed by (active
+ * clips, rows, buffer phase, mode, clips of the pass).  A pass may use at most 12 DISTINCT active clip counts; one with more has every
+ * count rounded UP to a multiple of 2, 4, 8, ... (the smallest power of two that fits; finished clips are carried along, which is always
+ * correct), so that its graphs — one per count, one for the first chunk, one or two for a short last chunk — fit the 16 chunk graphs kept
+ * per stream and a repeated pass captures nothing from its second run on (ts_pixelcnn_graph_captures stands still).  No whole-call graphs.
+ * TS_TEACHER_FORCED and logits are not offered. */
+int ts_body_pixel_infer_mixed(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                              const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                              const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                              float *poses_dev, void *stream);
+/* The three stages of a mixed pass on their own (same table, same rules; lens are MFCC frame counts in all of them):
+ * ts_audioenc_forward with length-masked layers: feat_dev (B,T_max/4,num_hiddens), rows at or beyond lens[b] / 4 written as 0; */
+int ts_audioenc_forward_masked(ts_convnet *net, const float *mfcc_dev, const int32_t *lens_dev, int B, int T_max, float *feat_dev,
+                               void *stream);
+/* ts_pixelcnn_generate over a shrinking prefix of the clips: aud_dev (B,H_max,aud_dim), codes_dev (B,H_max,2) with -1 beyond lens[b] / 4; */
+int ts_pixelcnn_generate_mixed(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                               const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                               const int64_t *clip_index_dev, int64_t *codes_dev, void *stream);
+/* ts_vqvae_decode_pair with length-masked layers: latents (B,H) each, rows at or beyond lens[b] / 4 are not read (gathered as zero rows;
+ * an index outside the codebook INSIDE a clip still gives NaNs); out_dev (B,4H,body_dim+hand_dim), rows at or beyond 4 (lens[b] / 4) = 0. */
+int ts_vqvae_decode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *lat_body_dev, const int64_t *lat_hand_dev,
+                                const int32_t *lens_dev, int B, int H, float *out_dev, void *stream);
+
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.
  * Either output may be NULL: recon_dev == NULL is the encode-only form (VQVAE.encode of both parts, the latents

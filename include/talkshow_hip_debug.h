@@ -160,6 +160,13 @@ int ts_debug_fill_id(const float *id, int nc, const float *w, const float *bias,
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */
 int ts_debug_pixelcnn_graphs(ts_pixelcnn *pix, void *stream);
 
+/* Host-only (no GPU): the chunk plan of a mixed pass (talkshow_hip.h, "mixed passes").  hrows (B,) = code rows per clip, >= 1 and
+ * non-increasing; max_counts = distinct active clip counts a pass may use (<= 0: the library's bound, 12).  active_out (ceil(hrows[0] / 8),)
+ * or NULL: the clips chunk k = rows [8 k, 8 k + 8) runs with = #{b : hrows[b] > 8 k} rounded up to a multiple of the returned grid (capped
+ * at B).  Returns the grid (1: nothing rounded; 2, 4, 8, ...: the smallest power of two that brings the distinct counts within the bound),
+ * -1 on a bad table.  No reference counterpart. */
+int ts_debug_mixed_plan(const int32_t *hrows, int B, int max_counts, int32_t *active_out);
+
 /* Tuning entry (not part of the drop-in surface): `iters` DEPENDENT skinny_gemm launches replayed from one hipGraph;
  * *us_out = microseconds per launch.  gate != 0: N = 2K with the tanh*sigmoid epilogue; debug: unused. */
 int ts_debug_skinny_chain(ts_ctx *ctx, int M, int K, int gate, int iters, int debug, float *us_out);

@@ -18,6 +18,17 @@ def _fresh_seed():
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+def mixed_pass_order(lens):
+    """Order of a mixed pass: the clips by NON-INCREASING length, ties in submission order (a stable sort, so the order — and with it the
+    memory a clip's rows live in — is a function of the lengths alone).  Returns (order, inverse): sorted slot k holds submitted clip
+    order[k]; submitted clip b sits in slot inverse[b].  Pure host code (tests/test_mixed_pass_host.py)."""
+    order = sorted(range(len(lens)), key=lambda b: (-int(lens[b]), b))
+    inverse = [0] * len(order)
+    for k, b in enumerate(order):
+        inverse[b] = k
+    return order, inverse
+
+
 class TrainWrapper(TrainWrapperBaseClass):
     '''
     a wrapper receiving audio features and generating motion (reference: a wrapper receving a batch from data_utils
@@ -123,9 +134,15 @@ class TrainWrapper(TrainWrapperBaseClass):
         to running each batch alone (tests/test_gpu_parity.py::test_golden_clips_inside_baseline_batches); global clip
         indices (the Philox subsequences) run on from `clip_index0` in list order.
 
-        mfccs: list of (B_i,T,64) device tensors, ids_list: list of (B_i,) -> list of (codes_i, poses_i) views."""
+        Batches whose T differ ride in ONE mixed pass (`generate_clips`: length-masked conv stacks, the chain over a shrinking prefix
+        of the clips); each batch gets its results trimmed to its own H and 4 H, with the same bits and the same Philox subsequences.
+        Batches of one T take the uniform path below, unchanged.
+
+        mfccs: list of (B_i,T_i,64) device tensors, ids_list: list of (B_i,) -> list of (codes_i, poses_i) views."""
         dev = self.generator._dev()
         sizes = [int(m.shape[0]) for m in mfccs]
+        if len({int(m.shape[1]) for m in mfccs}) > 1:     # batches of different lengths: one mixed pass (equal lengths: the path below, unchanged)
+            return self._generate_batches_mixed(mfccs, ids_list, sizes, mode, seed, clip_index0)
         # nn.Embedding's IndexError per submitted batch, BEFORE stacking: host ids are checked on the host, a caller-owned device
         # tensor once per tensor version (modules._check_index_range) — the stacked tensor built below is new on every call, and
         # checking it would cost the serving path one blocking device -> host read per pass (ADVICE r3)
@@ -138,6 +155,99 @@ class TrainWrapper(TrainWrapperBaseClass):
                          for i, b in zip(ids_list, sizes)], 0)
         codes, poses = self.generate_batch(mf, ids, mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True)
         return list(zip(codes.split(sizes, 0), poses.split(sizes, 0)))
+
+    def _generate_batches_mixed(self, mfccs, ids_list, sizes, mode, seed, clip_index0):
+        from talkshow_amd.modules import _check_index_range
+        dev = self.generator._dev()
+        clips, ids = [], []
+        for m, i, b in zip(mfccs, ids_list, sizes):
+            _check_index_range(i, self.num_classes, 'speaker id')
+            m = torch.as_tensor(m, dtype=torch.float32, device=dev)
+            i = torch.as_tensor(i, dtype=torch.int64, device=dev).reshape(-1)
+            if i.numel() == 1 and b > 1:
+                i = i.expand(b)
+            if i.numel() != b:
+                raise ValueError(f"ids must hold 1 or B={b} speaker indices, got {i.numel()}")
+            clips += list(m.unbind(0))
+            ids.append(i)
+        codes, poses = self.generate_clips(clips, torch.cat(ids, 0), mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True,
+                                           _stacked=True)
+        out, k = [], 0
+        for m, b in zip(mfccs, sizes):          # per submitted batch, trimmed to that batch's own H and 4 H
+            H = int(m.shape[1]) // 4
+            out.append((codes[k:k + b, :H], poses[k:k + b, :4 * H]))
+            k += b
+        return out
+
+    def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
+                       _ids_checked=False, _stacked=False):
+        """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
+        one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
+
+        Every clip's result is bit-identical to `generate_batch` on the clip alone.  The library wants the clips ordered by length; they
+        are sorted here (stable, longest first), padded to the longest, and the results are put back in submission order.  Clip b draws from
+        Philox subsequence `clip_index0 + b` with b its position in the SUBMITTED list, whatever the sort does: the draws are what they
+        would be had all clips had one length; `clip_indices` (B ints) names every clip's global index outright instead (a host that
+        regroups clips between passes keeps each clip's random stream).  uniforms: list of (H_b,2) per clip for TS_SAMPLE_UNIFORMS."""
+        dev = self.generator._dev()
+        B = len(mfcc_list)
+        if B < 1:
+            raise ValueError("generate_clips: no clips")
+        clips = [torch.as_tensor(m, dtype=torch.float32, device=dev) for m in mfcc_list]
+        lens = [int(m.shape[0]) for m in clips]
+        for b, (m, t) in enumerate(zip(clips, lens)):
+            if m.dim() != 2 or m.shape[1] != 64:
+                raise ValueError(f"generate_clips: clip {b} must have shape (T, 64), got {tuple(m.shape)}")
+            if t < 4:
+                raise ValueError(f"generate_clips: clip {b} has {t} MFCC rows; one code row needs 4")
+        if _ids_checked:
+            ids = torch.as_tensor(ids, dtype=torch.int64, device=dev).reshape(-1)
+        else:
+            ids = _index_tensor(ids, self.num_classes, 'speaker id', dev)
+        if ids.numel() == 1 and B > 1:
+            ids = ids.repeat(B)
+        if ids.numel() != B:
+            raise ValueError(f"ids must hold 1 or B={B} speaker indices, got {ids.numel()}")
+        order, inverse = mixed_pass_order(lens)
+        T_max = lens[order[0]]
+        H_max = T_max // 4
+        sorted_lens = [lens[i] for i in order]
+        mf = torch.zeros((B, T_max, 64), dtype=torch.float32, device=dev)
+        for k, i in enumerate(order):
+            mf[k, :lens[i]] = clips[i]
+        lens_host = np.asarray(sorted_lens, dtype=np.int32)
+        lens_dev = torch.from_numpy(lens_host).to(dev)
+        order_dev = torch.as_tensor(order, dtype=torch.int64, device=dev)
+        ids_sorted = ids.index_select(0, order_dev).contiguous()
+        if clip_indices is None:
+            clip_index = (order_dev + int(clip_index0)).contiguous()      # global index of the clip in each sorted slot
+        else:
+            if len(clip_indices) != B:
+                raise ValueError(f"generate_clips: clip_indices must name {B} clips, got {len(clip_indices)}")
+            clip_index = torch.as_tensor([int(clip_indices[i]) for i in order], dtype=torch.int64, device=dev)
+        u = None
+        if mode == _lib.TS_SAMPLE_UNIFORMS:
+            if uniforms is None or len(uniforms) != B:
+                raise ValueError("generate_clips: TS_SAMPLE_UNIFORMS needs one (H_b, 2) array of uniforms per clip")
+            u = torch.zeros((B, H_max, 2), dtype=torch.float32, device=dev)
+            for k, i in enumerate(order):
+                ui = torch.as_tensor(uniforms[i], dtype=torch.float32, device=dev)
+                if tuple(ui.shape) != (lens[i] // 4, 2):
+                    raise ValueError(f"generate_clips: uniforms of clip {i} must have shape ({lens[i] // 4}, 2), got {tuple(ui.shape)}")
+                u[k, :lens[i] // 4] = ui
+        if seed is None:
+            seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
+        codes = torch.empty((B, H_max, 2), dtype=torch.int64, device=dev)
+        poses = torch.empty((B, 4 * H_max, self.each_dim[1] + self.each_dim[2]), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().ts_body_pixel_infer_mixed(
+            self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
+            _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
+            mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses), _lib.stream_ptr()))
+        inv_dev = torch.as_tensor(inverse, dtype=torch.int64, device=dev)
+        codes, poses = codes.index_select(0, inv_dev), poses.index_select(0, inv_dev)     # back to submission order
+        if _stacked:
+            return codes, poses
+        return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,
                        continuity=False, id=None, fps=15, sr=22000, B=1, am=None, am_sr=None, frame=0, **kwargs):

@@ -89,6 +89,11 @@ SIGNATURES = {
     "ts_resample_kaiser": (_i, [_vp, _vp, _i, C.c_long, _i, _i, _vp, _vp]),
     "ts_pixelcnn_graph_stats": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "ts_body_pixel_infer": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp]),
+    "ts_body_pixel_infer_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "ts_audioenc_forward_masked": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ts_pixelcnn_generate_mixed": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp]),
+    "ts_vqvae_decode_pair_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ts_debug_mixed_plan": (_i, [C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32)]),
     "ts_body_vq_infer": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ts_op_conv1d": (_i, [_vp, _vp, _i, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ts_op_conv1d_timed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(C.c_float), _vp]),

@@ -171,6 +171,37 @@ int ts_body_pixel_infer(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae
     return ts_vqvae_decode_pair(vb, vh, static_cast<int64_t *>(w.lat[0].p), static_cast<int64_t *>(w.lat[1].p), B, H, poses, s);
 }
 
+// The same path for clips of different lengths in ONE pass (talkshow_hip.h: "mixed passes"): length-masked conv stacks, the chain over
+// a shrinking prefix of the clips, documented padding in both outputs.
+int ts_body_pixel_infer_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                              const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                              uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, void *stream) {
+    if (!ae || !pix || !vb || !vh || !mfcc || !ids || !lens_host || !lens_dev || !codes || !poses)
+        return fail("ts_body_pixel_infer_mixed: null argument");
+    if (B < 1) return fail("ts_body_pixel_infer_mixed: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = (T_max / 2) / 2;
+    if (H < 1) return fail("ts_body_pixel_infer_mixed: T_max too short");
+    for (int b = 0; b < B; ++b) {
+        if (lens_host[b] > T_max) return fail("ts_body_pixel_infer_mixed: clip " + std::to_string(b) + " is longer than T_max");
+        if (lens_host[b] < 4) return fail("ts_body_pixel_infer_mixed: clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
+        if (b > 0 && lens_host[b] > lens_host[b - 1])
+            return fail("ts_body_pixel_infer_mixed: lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
+    }
+    const int aud_dim = convnet_hidden(ae);
+    BodyWork &w = body_work(s);
+    TS_TRY(w.feat.ensure((size_t)B * H * aud_dim * sizeof(float)));
+    TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
+    TS_TRY(ts_pixelcnn_generate_mixed(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, s));
+    for (int k = 0; k < 2; ++k) {
+        TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
+        TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),
+                                (size_t)B * H, hipMemcpyDeviceToDevice, s));
+    }
+    return ts_vqvae_decode_pair_masked(vb, vh, static_cast<int64_t *>(w.lat[0].p), static_cast<int64_t *>(w.lat[1].p), lens_dev, B, H,
+                                       poses, s);
+}
+
 int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const float *w, const float *bias, int Cout,
                  int K, int stride, int pad, int transposed, int act, float *out, void *stream) {
     if (!ctx || !x || !w || !out) return fail("ts_op_conv1d: null argument");

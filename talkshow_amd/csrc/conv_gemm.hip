@@ -26,7 +26,7 @@
 namespace ts {
 
 // one BM x BN output tile at (m0, n0) of problem / group `zidx`; smem: 2 * (BM + BN) * (BK + 4) floats of LDS
-template <int BM, int BN, int WM, int WN, int BK = 32>
+template <int BM, int BN, int WM, int WN, int BK = 32, bool MASK = false>
 __device__ __forceinline__ void conv_tile(const ConvParams &p, const int zidx, const int m0, const int n0, float *smem) {
     constexpr int LDS_LD = BK + 4;   // 36 (68) floats: conflict-free row pitch for ds_read_b128
     constexpr int KC = BK / 32;      // 32-float column blocks per chunk
@@ -275,7 +275,7 @@ __device__ __forceinline__ void conv_tile(const ConvParams &p, const int zidx, c
         buf ^= 1;
     }
 
-    conv_tile_epilogue<TM, TN>(p, g, tp, acc, m0 + wm * WM, n0 + wn * WN, li, lh);   // conv_tile.h
+    conv_tile_epilogue<TM, TN, MASK>(p, g, tp, acc, m0 + wm * WM, n0 + wn * WN, li, lh);   // conv_tile.h
 }
 
 template <int BM, int BN, int WM, int WN, int BK = 32>
@@ -283,21 +283,37 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvParams p) {
     __shared__ __attribute__((aligned(16))) float smem[2 * (BM + BN) * (BK + 4)];
     conv_tile<BM, BN, WM, WN, BK>(p, blockIdx.z, blockIdx.x * BM, blockIdx.y * BN, smem);
 }
+// the same tile with the length-masked epilogue (ConvParams::lens; conv_tile.h): kernels of their own, taken only by mixed passes —
+// the ones above keep their names and their code
+template <int BM, int BN, int WM, int WN, int BK = 32>
+__global__ __launch_bounds__(256) void conv_gemm_masked_kernel(const ConvParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + BN) * (BK + 4)];
+    conv_tile<BM, BN, WM, WN, BK, true>(p, blockIdx.z, blockIdx.x * BM, blockIdx.y * BN, smem);
+}
 
 // Banded launch: the rows of the output are cut into two bands — 128 x 128 tiles where whole rounds of 512 resident workgroups
 // fit, the small shape S for what is left, so that the last, partly filled round of a layer is made of short tiles (2 400 tiles
 // of 128 x 128 are 4.69 rounds).  Workgroup ids run band by band; inside a band M tiles fastest, then N, then group.
-template <int SBM, int SBN, int SWM, int SWN>
-__global__ __launch_bounds__(256) void conv_gemm_banded_kernel(const ConvParams p, const ConvBands bands) {
-    __shared__ __attribute__((aligned(16))) float smem[2 * (128 + 128) * 36];
+template <int SBM, int SBN, int SWM, int SWN, bool MASK>
+__device__ __forceinline__ void conv_banded_body(const ConvParams &p, const ConvBands &bands, float *smem) {
     const int big = (int)blockIdx.x < bands.first_small;
     const int local = big ? blockIdx.x : blockIdx.x - bands.first_small;
     const int mt = big ? bands.mt_big : bands.mt_small;
     const int nt = big ? (p.N + 127) / 128 : (p.N + SBN - 1) / SBN;
     const int rest = local / mt, m = local - rest * mt;
     const int z = rest / nt, n = rest - z * nt;
-    if (big) conv_tile<128, 128, 64, 64>(p, z, m * 128, n * 128, smem);
-    else conv_tile<SBM, SBN, SWM, SWN>(p, z, bands.mt_big * 128 + m * SBM, n * SBN, smem);
+    if (big) conv_tile<128, 128, 64, 64, 32, MASK>(p, z, m * 128, n * 128, smem);
+    else conv_tile<SBM, SBN, SWM, SWN, 32, MASK>(p, z, bands.mt_big * 128 + m * SBM, n * SBN, smem);
+}
+template <int SBM, int SBN, int SWM, int SWN>
+__global__ __launch_bounds__(256) void conv_gemm_banded_kernel(const ConvParams p, const ConvBands bands) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * (128 + 128) * 36];
+    conv_banded_body<SBM, SBN, SWM, SWN, false>(p, bands, smem);
+}
+template <int SBM, int SBN, int SWM, int SWN>
+__global__ __launch_bounds__(256) void conv_gemm_banded_masked_kernel(const ConvParams p, const ConvBands bands) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * (128 + 128) * 36];
+    conv_banded_body<SBM, SBN, SWM, SWN, true>(p, bands, smem);
 }
 
 double conv_gemm_flops(const ConvParams &p) { return 2.0 * p.M * (double)p.N * p.Ktot * p.ngroups; }
@@ -414,15 +430,24 @@ template <int BM, int BN, int WM, int WN, int BK>
 static void launch_reg(const ConvParams &p, hipStream_t s) {
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BK>), dim3((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, p.ngroups), dim3(256), 0, s, p);
 }
+template <int BM, int BN, int WM, int WN, int BK>
+static void launch_reg_masked(const ConvParams &p, hipStream_t s) {
+    hipLaunchKernelGGL((conv_gemm_masked_kernel<BM, BN, WM, WN, BK>), dim3((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, p.ngroups), dim3(256), 0, s, p);
+}
 struct RegInstance {
     int bm, bn, wm, wn, bk;
     void (*launch)(const ConvParams &, hipStream_t);
+    void (*launch_masked)(const ConvParams &, hipStream_t);   // ConvParams::lens given; null: the tile has no masked variant (a launch error)
 };
+// the four tiles pick_tile chooses from have a length-masked twin (the body path's mixed passes); the tuning-only tiles do not
 static const RegInstance reg_instances[] = {
-    {128, 128, 64, 64, 32, launch_reg<128, 128, 64, 64, 32>}, {64, 64, 32, 32, 32, launch_reg<64, 64, 32, 32, 32>},
-    {128, 64, 64, 32, 32, launch_reg<128, 64, 64, 32, 32>},   {64, 128, 32, 64, 32, launch_reg<64, 128, 32, 64, 32>},
-    {64, 64, 32, 32, 64, launch_reg<64, 64, 32, 32, 64>},     {160, 128, 160, 32, 32, launch_reg<160, 128, 160, 32, 32>},
-    {96, 128, 96, 32, 32, launch_reg<96, 128, 96, 32, 32>},
+    {128, 128, 64, 64, 32, launch_reg<128, 128, 64, 64, 32>, launch_reg_masked<128, 128, 64, 64, 32>},
+    {64, 64, 32, 32, 32, launch_reg<64, 64, 32, 32, 32>, launch_reg_masked<64, 64, 32, 32, 32>},
+    {128, 64, 64, 32, 32, launch_reg<128, 64, 64, 32, 32>, launch_reg_masked<128, 64, 64, 32, 32>},
+    {64, 128, 32, 64, 32, launch_reg<64, 128, 32, 64, 32>, launch_reg_masked<64, 128, 32, 64, 32>},
+    {64, 64, 32, 32, 64, launch_reg<64, 64, 32, 32, 64>, nullptr},
+    {160, 128, 160, 32, 32, launch_reg<160, 128, 160, 32, 32>, nullptr},
+    {96, 128, 96, 32, 32, launch_reg<96, 128, 96, 32, 32>, nullptr},
 };
 
 hipError_t launch_conv_plan(const ConvParams &p_in, const ConvPlan &pl, hipStream_t stream) {
@@ -432,16 +457,22 @@ hipError_t launch_conv_plan(const ConvParams &p_in, const ConvPlan &pl, hipStrea
         if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
     }
     if (!p.zero || p.g[0].nseg > 4 || p.Ktot > 60000) return hipErrorInvalidValue;
+    // length-masked rows: whole-tile plans of the two engines only, on per-clip geometry (no batched problems)
+    if (p.lens && (p.zdiv > 0 || p.len_shr < 0 || p.len_shl < 0 || pl.engine == ConvEngine::RingSK || pl.engine == ConvEngine::Taps48 ||
+                   pl.engine == ConvEngine::Split))
+        return hipErrorInvalidValue;
     switch (pl.engine) {
         case ConvEngine::Reg:
             for (const RegInstance &r : reg_instances)
                 if (r.bm == pl.bm && r.bn == pl.bn && r.wm == pl.wm && r.wn == pl.wn && r.bk == pl.bk) {
-                    r.launch(p, stream);
+                    if (p.lens && !r.launch_masked) return hipErrorInvalidValue;
+                    (p.lens ? r.launch_masked : r.launch)(p, stream);
                     return hipGetLastError();
                 }
             return hipErrorInvalidValue;
         case ConvEngine::RegBanded:
-            hipLaunchKernelGGL((conv_gemm_banded_kernel<64, 128, 32, 64>), dim3(pl.bands.total), dim3(256), 0, stream, p, pl.bands);
+            if (p.lens) hipLaunchKernelGGL((conv_gemm_banded_masked_kernel<64, 128, 32, 64>), dim3(pl.bands.total), dim3(256), 0, stream, p, pl.bands);
+            else hipLaunchKernelGGL((conv_gemm_banded_kernel<64, 128, 32, 64>), dim3(pl.bands.total), dim3(256), 0, stream, p, pl.bands);
             return hipGetLastError();
         case ConvEngine::Ring:
         case ConvEngine::RingDealt: return launch_conv_gemm_ring(p, pl, stream);

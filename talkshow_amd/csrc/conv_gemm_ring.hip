@@ -262,12 +262,13 @@ __device__ __forceinline__ void ring_tile_range(const ConvParams &p, const int z
 }
 
 // one whole BM x BN output tile: the full K walk, then the epilogue (conv_tile.h)
-template <int BM, int BN, int WM, int WN>
+// MASK: the length-masked epilogue (ConvParams::lens; conv_tile.h) — instantiations of their own, taken only by mixed passes
+template <int BM, int BN, int WM, int WN, bool MASK = false>
 __device__ __forceinline__ void ring_tile(const ConvParams &p, const int zidx, const int m0, const int n0, float *smem) {
     constexpr int TM = WM / 32, TN = WN / 32;
     ring_tile_range<BM, BN, WM, WN>(p, zidx, m0, n0, smem, 0, p.Ktot / 32,
                                     [&](f32x16 (&acc)[TM][TN], const ConvGroup &g, const ConvTilePtrs &tp, int mw, int nw, int li, int lh) {
-                                        conv_tile_epilogue<TM, TN>(p, g, tp, acc, mw, nw, li, lh);
+                                        conv_tile_epilogue<TM, TN, MASK>(p, g, tp, acc, mw, nw, li, lh);
                                     });
 }
 
@@ -284,26 +285,46 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM / WM) * (BN / WN) /
     }
     ring_tile<BM, BN, WM, WN>(p, blockIdx.z, tx * BM, ty * BN, smem);
 }
+// the same tiles with the length-masked epilogue (mixed passes): kernels of their own, the ones above keep their names and their code
+template <int BM, int BN, int WM, int WN, bool XCD>
+__global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM / WM) * (BN / WN) / 2) void conv_ring_masked_kernel(const ConvParams p) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (BM + BN) * 32];
+    int tx = blockIdx.x, ty = blockIdx.y;
+    if constexpr (XCD) {
+        const int nt = (p.N + BN - 1) / BN;
+        if (!split_tile_of((int)blockIdx.x, (p.M + BM - 1) / BM, nt, nt < 8 ? nt : 8, tx, ty)) return;
+    }
+    ring_tile<BM, BN, WM, WN, true>(p, blockIdx.z, tx * BM, ty * BN, smem);
+}
 
 // Banded + dealt: rows [0, mt_big * 128) in 128 x 128 tiles for the whole rounds of 512 resident workgroups, the rows after them in
 // 64 x 128 tiles (conv_gemm.hip's plan_bands: the last, partly filled round of a layer is made of short tiles); per problem each band's
 // tiles are dealt to the XCDs (split_tile_of), every region padded to a multiple of 8 ids so that id mod 8 stays the XCD.
 // ids: [problem][big band, big8 ids] ..., then [problem][small band, small8 ids] ...
-__global__ __launch_bounds__(512, 4) void conv_ring_banded_kernel(const ConvParams p, const ConvBands bd, const int big8, const int small8) {
-    __shared__ __attribute__((aligned(1024))) float smem[2 * (128 + 128) * 32];
+template <bool MASK>
+__device__ __forceinline__ void ring_banded_body(const ConvParams &p, const ConvBands &bd, const int big8, const int small8, float *smem) {
     const int nt = (p.N + 127) / 128, gw = nt < 8 ? nt : 8;
     int id = blockIdx.x, tx, ty;
     const int nbig = big8 * p.ngroups;
     if (id < nbig) {
         const int z = id / big8;
         if (!split_tile_of(id - z * big8, bd.mt_big, nt, gw, tx, ty)) return;
-        ring_tile<128, 128, 32, 64>(p, z, tx * 128, ty * 128, smem);
+        ring_tile<128, 128, 32, 64, MASK>(p, z, tx * 128, ty * 128, smem);
     } else {
         id -= nbig;
         const int z = id / small8;
         if (!split_tile_of(id - z * small8, bd.mt_small, nt, gw, tx, ty)) return;
-        ring_tile<64, 128, 32, 32>(p, z, bd.mt_big * 128 + tx * 64, ty * 128, smem);
+        ring_tile<64, 128, 32, 32, MASK>(p, z, bd.mt_big * 128 + tx * 64, ty * 128, smem);
     }
+}
+__global__ __launch_bounds__(512, 4) void conv_ring_banded_kernel(const ConvParams p, const ConvBands bd, const int big8, const int small8) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (128 + 128) * 32];
+    ring_banded_body<false>(p, bd, big8, small8, smem);
+}
+// the same bands with the length-masked epilogue (mixed passes)
+__global__ __launch_bounds__(512, 4) void conv_ring_banded_masked_kernel(const ConvParams p, const ConvBands bd, const int big8, const int small8) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (128 + 128) * 32];
+    ring_banded_body<true>(p, bd, big8, small8, smem);
 }
 
 // ---- stream-K band (the partly filled last round) -------------------------------------------------------------
@@ -487,7 +508,7 @@ bool conv_sk_valid(const ConvParams &p, const ConvSK &sk) {
 
 hipError_t launch_conv_gemm_ring_sk(const ConvParams &p_in, const ConvSK &sk, hipStream_t stream) {
     ConvParams p = p_in;
-    if (!p.zero || !conv_sk_valid(p, sk)) return hipErrorInvalidValue;
+    if (!p.zero || p.lens || !conv_sk_valid(p, sk)) return hipErrorInvalidValue;   // (a split tile has no length-masked epilogue: the body path never gets this plan)
     const int nt = (p.N + 127) / 128;
     if (conv_sk_workspace(stream, (size_t)sk.wsk * p.ngroups * 2 * 128 * 128, (size_t)sk.mt_sk * nt * p.ngroups, &p.sk_ws, &p.sk_flags) != 0)
         return hipErrorOutOfMemory;
@@ -499,7 +520,8 @@ hipError_t launch_conv_gemm_ring_banded(const ConvParams &p, const ConvBands &bd
     if (!p.zero || !conv_gemm_ring_takes(p) || p.zdiv > 0 || bd.mt_big < 1 || bd.mt_small < 1) return hipErrorInvalidValue;
     const int nt = (p.N + 127) / 128;
     const int big8 = 8 * ((bd.mt_big * nt + 7) / 8), small8 = 8 * ((bd.mt_small * nt + 7) / 8);
-    hipLaunchKernelGGL(conv_ring_banded_kernel, dim3((unsigned)((big8 + small8) * p.ngroups)), dim3(512), 0, stream, p, bd, big8, small8);
+    if (p.lens) hipLaunchKernelGGL(conv_ring_banded_masked_kernel, dim3((unsigned)((big8 + small8) * p.ngroups)), dim3(512), 0, stream, p, bd, big8, small8);
+    else hipLaunchKernelGGL(conv_ring_banded_kernel, dim3((unsigned)((big8 + small8) * p.ngroups)), dim3(512), 0, stream, p, bd, big8, small8);
     return hipGetLastError();
 }
 
@@ -569,7 +591,8 @@ template <int BM, int BN, int WM, int WN, bool XCD>
 static void launch_ring(const ConvParams &p, hipStream_t s) {
     const unsigned mt = (p.M + BM - 1) / BM, nt = (p.N + BN - 1) / BN;
     const dim3 grid = XCD ? dim3(8 * (unsigned)(((long)mt * nt + 7) / 8), 1, p.ngroups) : dim3(mt, nt, p.ngroups);
-    hipLaunchKernelGGL((conv_ring_kernel<BM, BN, WM, WN, XCD>), grid, dim3(64 * (BM / WM) * (BN / WN)), 0, s, p);
+    if (p.lens) hipLaunchKernelGGL((conv_ring_masked_kernel<BM, BN, WM, WN, XCD>), grid, dim3(64 * (BM / WM) * (BN / WN)), 0, s, p);
+    else hipLaunchKernelGGL((conv_ring_kernel<BM, BN, WM, WN, XCD>), grid, dim3(64 * (BM / WM) * (BN / WN)), 0, s, p);
 }
 struct RingInstance {
     bool dealt;

@@ -35,7 +35,9 @@ __device__ __forceinline__ ConvTilePtrs conv_tile_ptrs(const ConvParams &p, cons
 // instead of 16; the residual values of a block are fetched together, ahead of their use).  Rows / buffers that are not
 // 16-byte aligned (the 39- / 90- / 129-wide pose rows) and channel tails take the scalar form.
 // (mw, nw): first row / column of this wave's TM x TN blocks of 32 x 32.
-template <int TM, int TN>
+// MASK (ConvParams::lens given): rows at or beyond their clip's valid length are stored as zeros.  A variant of its own: the
+// unmasked instantiations keep the code they had (no register, no branch added to an epilogue that shows in the profile).
+template <int TM, int TN, bool MASK = false>
 __device__ __forceinline__ void conv_tile_epilogue(const ConvParams &p, const ConvGroup &g, const ConvTilePtrs &t,
                                                    f32x16 (&acc)[TM][TN], const int mw, const int nw, const int li, const int lh) {
     const float *gbias = t.bias, *gres = t.res;
@@ -55,6 +57,13 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvParams &p, const Co
     for (int i = 0; i < TM; ++i) {
         const int m = mw + i * 32 + li;
         const bool mok = m < p.M;
+        bool live = true;   // MASK: row m lies inside its clip (one division per 32-row block and lane, not per stored element)
+        if constexpr (MASK) {
+            if (mok) {
+                const int b = m / p.Lout, t = m - b * p.Lout;
+                live = t < ((p.lens[b] >> p.len_shr) << p.len_shl);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int nb0 = nw + j * 32 + 4 * lh;
@@ -86,6 +95,9 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvParams &p, const Co
                     f32x4 v;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = activate(acc[i][j][4 * q + r] + bv[q][r], rv[q][r]);
+                    if constexpr (MASK) {
+                        if (!live) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
                     float *op = gout + (long)m * p.ldo + g.out_col0 + nb;
                     if (vec_out && nb + 3 < p.N) *reinterpret_cast<f32x4 *>(op) = v;
                     else

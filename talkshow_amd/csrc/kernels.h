@@ -56,6 +56,12 @@ struct ConvParams {
     int *sk_flags;       // and one arrival counter per band tile (zero between launches); set by launch_conv_gemm_ring_sk
     int w_planes;        // conv_gemm_split, 2 planes only: the weights are plane images already (split_weight_planes): no split of B in the kernel
     int xcd_tiles;       // set by launch_conv_gemm_split (0 or the column-group width): 1-D grid, tiles dealt to the XCDs in blocks that share operands
+    // length-masked rows (mixed passes: clips of different lengths padded into one batch; null = off, the kernels that run then are
+    // the unmasked instantiations).  lens[b] = the clip's base length; GEMM row m = b * Lout + t is valid for t < (lens[b] >> len_shr) << len_shl.
+    // The masked epilogue stores ZERO for every other row — the operand the gather parks for rows outside [0, Lin) of a clip run alone,
+    // so the next layer's taps read the same values in both cases and a valid row's bits do not depend on the padding.
+    const int *lens;
+    int len_shr, len_shl;
 };
 
 // banded conv_gemm launch (conv_gemm.hip): rows [0, mt_big * 128) in 128 x 128 tiles = workgroups [0, first_small), the rows
@@ -262,6 +268,17 @@ hipError_t launch_row_sqnorm(const float *e, int n, int dim, float *out, hipStre
 // out[m][0..width) = table[idx[m*idx_stride]][0..width); an index outside [0, nrows) gives a row of NaNs
 hipError_t launch_gather_rows(const float *table, int ld_table, int nrows, const int64_t *idx, long idx_stride, int M,
                               int width, float *out, int ldo, hipStream_t stream);
+// the same for a padded batch of clips (mixed passes): row m = b * L + t with t >= lens[b] >> len_shr is written as a ZERO row whatever
+// idx holds there (the index is not read); rows inside the clip keep the NaN answer to a bad index
+hipError_t launch_gather_rows_masked(const float *table, int ld_table, int nrows, const int64_t *idx, long idx_stride, int M,
+                                     int width, float *out, int ldo, int L, const int *lens, int len_shr, hipStream_t stream);
+// dst[b][t][0..cpad) = src[b][t][0..c) then zeros for t < lens[b], a zero row for t >= lens[b]  (B clips of L rows)
+hipError_t launch_pad_rows_masked(const float *src, int lds, int c, float *dst, int ldd, int cpad, int B, int L, const int *lens,
+                                  hipStream_t stream);
+// codes[b][r][0..1] = -1 for r >= lens[b] >> 2  (B clips of H rows of 2 codes: the documented padding of a mixed pass)
+hipError_t launch_mask_codes(int64_t *codes, int B, int H, const int *lens, hipStream_t stream);
+// dst[b] = first + b (the per-clip Philox subsequences of a mixed pass that was given no table)
+hipError_t launch_iota_i64(int64_t *dst, int n, int64_t first, hipStream_t stream);
 // dst[m][0..cpad) = src[m][0..c) then zeros
 hipError_t launch_pad_rows(const float *src, int lds, int c, float *dst, int ldd, int cpad, long M, hipStream_t stream);
 // (B,Tb,129) body/hand poses + (B,Tf,103) jaw/expression -> (B,Tf,265) full SMPL-X parameter rows (demo.py:207-229, part2full)
@@ -388,6 +405,7 @@ struct SampleParams {
     long code_stride;
     float *logits_copy;    // optional: logits_copy[b * copy_stride + v] = logits[b][v]
     long copy_stride;
+    const int64_t *clip_table;   // optional: clip b draws from Philox subsequence clip_table[b] instead of clip_index0 + b (mixed passes)
 };
 hipError_t launch_sample(const SampleParams &p, hipStream_t stream);
 

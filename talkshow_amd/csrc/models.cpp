@@ -395,17 +395,28 @@ int pack_trunk(ts_ctx *ctx, const StateDict &sd, const std::string &p, int in_di
     return 0;
 }
 
+// Length table of a mixed pass as one conv layer sees it: clip b has (lens[b] >> shr) << shl valid GEMM rows.  The encoder halves the
+// base length twice (shr 0, 1, 2), the decoders start from lens >> 2 code rows and double twice (shl 0, 1, 2); a transposed layer's GEMM
+// rows are its INPUT rows (each writes two output rows), so it is masked at its input's length.
+struct LenMask {
+    const int *lens;
+    int shr, shl;
+};
+
 // Runs the same layer of n (1 or 2) structurally identical networks.  Body and hand VQ-VAEs differ only in their weights
 // (and in the width of their first / last layer), so wherever the two layers have the same geometry they go out as ONE
 // grouped conv_gemm launch (blockIdx.z selects the network): twice the tiles per launch, which is what the 256 CUs need
 // at these sizes (608 tiles of 64x64 per network leave a 21 % tail; 1216 leave 5 %).
+// mk (mixed passes): the layer's GEMM rows at or beyond (lens[b] >> shr) << shl of clip b are stored as zeros (ConvParams::lens)
 int run_layer_n(ts_ctx *ctx, int n, const ConvLayer *const *L, const float *const *x, int ldx, int B, int Lin,
                 const float *const *res, int ldr, float *const *out, int ldo, const int *col0, const int *nstore,
-                hipStream_t s, int *Lout) {
+                hipStream_t s, int *Lout, const LenMask *mk = nullptr) {
     ConvParams p[2];
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         *Lout = conv_layer_params(*L[i], x[i], ldx, B, Lin, res ? res[i] : nullptr, ldr, out[i], ldo, col0 ? col0[i] : 0,
                                   nstore[i], &p[i]);
+        if (mk) p[i].lens = mk->lens, p[i].len_shr = mk->shr, p[i].len_shl = mk->shl;
+    }
     bool same = n == 2 && L[0]->kind == L[1]->kind && L[0]->cin_pad == L[1]->cin_pad && L[0]->ktot == L[1]->ktot &&
                 L[0]->act == L[1]->act && L[0]->ngroups == L[1]->ngroups && nstore[0] == nstore[1] &&
                 2 * L[0]->ngroups <= 4;
@@ -420,16 +431,16 @@ int run_layer_n(ts_ctx *ctx, int n, const ConvLayer *const *L, const float *cons
 }
 
 int run_layer(ts_ctx *ctx, const ConvLayer &L, const float *x, int ldx, int B, int Lin, const float *res, int ldr,
-              float *out, int ldo, int col0, int nstore, hipStream_t s, int *Lout) {
+              float *out, int ldo, int col0, int nstore, hipStream_t s, int *Lout, const LenMask *mk = nullptr) {
     const ConvLayer *Lp[1] = {&L};
     const float *xp[1] = {x}, *rp[1] = {res};
     float *op[1] = {out};
-    return run_layer_n(ctx, 1, Lp, xp, ldx, B, Lin, rp, ldr, op, ldo, &col0, &nstore, s, Lout);
+    return run_layer_n(ctx, 1, Lp, xp, ldx, B, Lin, rp, ldr, op, ldo, &col0, &nstore, s, Lout, mk);
 }
 
 // Res_CNR_Stack on pool buffer `cur` of each network; returns the index of the output buffer (same for all)
 int run_stack_n(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool, int cur, int c, int B, int L, hipStream_t s,
-                int *out_idx) {
+                int *out_idx, const LenMask *mk = nullptr) {
     int h = cur, tmp = 0;
     const int ns[2] = {c, c};
     const ConvLayer *Lp[2];
@@ -438,21 +449,25 @@ int run_stack_n(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool, i
     for (size_t k = 0; k < st[0]->layers.size(); ++k) {
         const int o = pool[0]->pick(cur, h);
         for (int i = 0; i < n; ++i) { Lp[i] = st[i]->layers[k].get(); xp[i] = pool[i]->buf(h); op[i] = pool[i]->buf(o); }
-        TS_TRY(run_layer_n(ctx, n, Lp, xp, c, B, L, nullptr, 0, op, c, nullptr, ns, s, &tmp));
+        TS_TRY(run_layer_n(ctx, n, Lp, xp, c, B, L, nullptr, 0, op, c, nullptr, ns, s, &tmp, mk));
         h = o;
     }
     const int o = pool[0]->pick(cur, h);
     for (int i = 0; i < n; ++i) { Lp[i] = &st[i]->tail; xp[i] = pool[i]->buf(h); rp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); }
-    TS_TRY(run_layer_n(ctx, n, Lp, xp, c, B, L, rp, c, op, c, nullptr, ns, s, &tmp));
+    TS_TRY(run_layer_n(ctx, n, Lp, xp, c, B, L, rp, c, op, c, nullptr, ns, s, &tmp, mk));
     *out_idx = o;
     return 0;
 }
 
 // encoder trunks of n networks: x[i] (B,T,in_dim_i) with row stride x_ld (0 = in_dim) -> pool buffer holding
 // (B,T/4,hid); returns buffer index (same for all) and H
+// lens (mixed passes): device table of the clips' own frame counts (<= T); every layer is length-masked and the input rows beyond a
+// clip's end are replaced by zeros (never read), so a clip's rows come out as they do when it runs alone
 int run_trunk_n(int n, ts_convnet *const *net, const float *const *x, int x_ld, int B, int T, hipStream_t s, int *out_idx,
-                int *H) {
+                int *H, const int *lens = nullptr) {
     if (T < 4) return fail("sequence too short: need T >= 4 frames");
+    LenMask m0{lens, 0, 0}, m1{lens, 1, 0}, m2{lens, 2, 0};
+    const LenMask *k0 = lens ? &m0 : nullptr, *k1 = lens ? &m1 : nullptr, *k2 = lens ? &m2 : nullptr;
     ts_ctx *ctx = net[0]->ctx;
     const int hid = net[0]->hid;
     Pool *pool[2];
@@ -465,11 +480,13 @@ int run_trunk_n(int n, ts_convnet *const *net, const float *const *x, int x_ld, 
         TS_TRY(pool[i]->ensure((size_t)B * T * (hid / 4)));
         xin[i] = x[i];
         ldx[i] = net[i]->in_dim;
-        if (net[i]->in_dim % 32 != 0) {
+        if (net[i]->in_dim % 32 != 0 || lens) {
             const int cp = net[i]->project.cin_pad;
             TS_TRY(wk.xin.ensure((size_t)B * T * cp * sizeof(float)));
             MiscScope ms(ctx, s);
-            TS_HIP(launch_pad_rows(x[i], x_ld > 0 ? x_ld : net[i]->in_dim, net[i]->in_dim, wk.xin.f(), cp, cp, (long)B * T, s));
+            const int xl = x_ld > 0 ? x_ld : net[i]->in_dim;
+            if (lens) TS_HIP(launch_pad_rows_masked(x[i], xl, net[i]->in_dim, wk.xin.f(), cp, cp, B, T, lens, s));
+            else TS_HIP(launch_pad_rows(x[i], xl, net[i]->in_dim, wk.xin.f(), cp, cp, (long)B * T, s));
             xin[i] = wk.xin.f();
             ldx[i] = cp;
         } else if (x_ld > 0) {
@@ -484,32 +501,32 @@ int run_trunk_n(int n, ts_convnet *const *net, const float *const *x, int x_ld, 
     int ns[2];
     // first layer: input widths differ between body and hand (39 / 90 channels) -> separate launches
     for (int i = 0; i < n; ++i)
-        TS_TRY(run_layer(ctx, net[i]->project, xin[i], ldx[i], B, L, nullptr, 0, pool[i]->buf(0), hid / 4, 0, hid / 4, s, &tmp));
+        TS_TRY(run_layer(ctx, net[i]->project, xin[i], ldx[i], B, L, nullptr, 0, pool[i]->buf(0), hid / 4, 0, hid / 4, s, &tmp, k0));
     for (int i = 0; i < n; ++i) Sp[i] = &net[i]->s1;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 4, B, L, s, &o));
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 4, B, L, s, &o, k0));
     cur = o;
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &net[i]->down1; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 2; }
-    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 4, B, L, nullptr, 0, op, hid / 2, nullptr, ns, s, &L));
+    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 4, B, L, nullptr, 0, op, hid / 2, nullptr, ns, s, &L, k1));
     cur = o;
     for (int i = 0; i < n; ++i) Sp[i] = &net[i]->s2;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 2, B, L, s, &o));
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 2, B, L, s, &o, k1));
     cur = o;
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &net[i]->down2; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid; }
-    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 2, B, L, nullptr, 0, op, hid, nullptr, ns, s, &L));
+    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 2, B, L, nullptr, 0, op, hid, nullptr, ns, s, &L, k2));
     cur = o;
     for (int i = 0; i < n; ++i) Sp[i] = &net[i]->s3;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o));
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o, k2));
     *out_idx = o;
     *H = L;
     return 0;
 }
 
-int run_trunk(ts_convnet *n, const float *x, int x_ld, int B, int T, hipStream_t s, int *out_idx, int *H) {
+int run_trunk(ts_convnet *n, const float *x, int x_ld, int B, int T, hipStream_t s, int *out_idx, int *H, const int *lens = nullptr) {
     ts_convnet *np[1] = {n};
     const float *xp[1] = {x};
-    return run_trunk_n(1, np, xp, x_ld, B, T, s, out_idx, H);
+    return run_trunk_n(1, np, xp, x_ld, B, T, s, out_idx, H, lens);
 }
 
 }  // namespace
@@ -579,9 +596,15 @@ int vq_encode_impl(ts_vqvae *vq, const float *poses, int poses_ld, int B, int T,
 
 // n = 1 or 2 decoders in lockstep: first layer (aft_vq table gather for codes, or aft_vq_conv on continuous latents z)
 // -> stacks / up-convs -> project into out[.., col0_i .. col0_i+in_dim_i)
+// lens (mixed passes, codes only): device table of the clips' MFCC frame counts; clip b has lens[b] >> 2 code rows of the H given.  Rows
+// beyond them are gathered as zero rows (whatever `lat` holds there) and every layer is length-masked: pose rows at or beyond
+// 4 (lens[b] >> 2) are written as zeros.
 int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const float *const *z, int B, int H, float *out,
-                int out_ld, const int *col0, hipStream_t s) {
+                int out_ld, const int *col0, hipStream_t s, const int *lens = nullptr) {
     ts_ctx *ctx = vq[0]->ctx;
+    LenMask m0{lens, 2, 0}, m1{lens, 2, 1}, m2{lens, 2, 2};
+    const LenMask *k0 = lens ? &m0 : nullptr, *k1 = lens ? &m1 : nullptr, *k2 = lens ? &m2 : nullptr;
+    if (lens && z) return fail("length-masked decode takes code indices");
     const int hid = vq[0]->hid;
     Pool *pool[2];
     for (int i = 0; i < n; ++i) {
@@ -594,7 +617,8 @@ int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const flo
         } else {
             if (vq[i]->ncode == 0) return fail("this network has no codebook (auto-encoder): decode continuous latents");
             MiscScope ms(ctx, s);
-            TS_HIP(launch_gather_rows(vq[i]->aft_table.f(), hid, vq[i]->ncode, lat[i], 1, B * H, hid, pool[i]->buf(0), hid, s));
+            if (lens) TS_HIP(launch_gather_rows_masked(vq[i]->aft_table.f(), hid, vq[i]->ncode, lat[i], 1, B * H, hid, pool[i]->buf(0), hid, H, lens, 2, s));
+            else TS_HIP(launch_gather_rows(vq[i]->aft_table.f(), hid, vq[i]->ncode, lat[i], 1, B * H, hid, pool[i]->buf(0), hid, s));
         }
     }
     int cur = 0, o = 0, L = H;
@@ -604,25 +628,25 @@ int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const flo
     float *op[2];
     int ns[2];
     for (int i = 0; i < n; ++i) Sp[i] = &vq[i]->d1;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o));
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o, k0));
     cur = o;
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &vq[i]->up2; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 2; }
-    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid, B, L, nullptr, 0, op, hid / 2, nullptr, ns, s, &L));
+    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid, B, L, nullptr, 0, op, hid / 2, nullptr, ns, s, &L, k0));   // (up-conv: masked at its input's length)
     cur = o;
     for (int i = 0; i < n; ++i) Sp[i] = &vq[i]->d2;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 2, B, L, s, &o));
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 2, B, L, s, &o, k1));
     cur = o;
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &vq[i]->up3; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 4; }
-    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 2, B, L, nullptr, 0, op, hid / 4, nullptr, ns, s, &L));
+    TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 2, B, L, nullptr, 0, op, hid / 4, nullptr, ns, s, &L, k1));
     cur = o;
     for (int i = 0; i < n; ++i) Sp[i] = &vq[i]->d3;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 4, B, L, s, &o));
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 4, B, L, s, &o, k2));
     int tmp = 0;
     // last layer: output widths differ (39 / 90) -> separate launches into the two column ranges of `out`
     for (int i = 0; i < n; ++i)
-        TS_TRY(run_layer(ctx, vq[i]->project, pool[i]->buf(o), hid / 4, B, L, nullptr, 0, out, out_ld, col0[i], vq[i]->in_dim, s, &tmp));
+        TS_TRY(run_layer(ctx, vq[i]->project, pool[i]->buf(o), hid / 4, B, L, nullptr, 0, out, out_ld, col0[i], vq[i]->in_dim, s, &tmp, k2));
     return 0;
 }
 
@@ -704,6 +728,16 @@ int ts_audioenc_forward(ts_convnet *net, const float *mfcc, int B, int T, float 
     hipStream_t s = (hipStream_t)stream;
     int idx = 0, H = 0;
     TS_TRY(run_trunk(net, mfcc, 0, B, T, s, &idx, &H));
+    TS_HIP(hipMemcpyAsync(feat, net->work(s).pool.buf(idx), (size_t)B * H * net->hid * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+int ts_audioenc_forward_masked(ts_convnet *net, const float *mfcc, const int32_t *lens, int B, int T, float *feat, void *stream) {
+    if (!net || !mfcc || !lens || !feat) return fail("ts_audioenc_forward_masked: null argument");
+    if (B < 1) return fail("ts_audioenc_forward_masked: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    int idx = 0, H = 0;
+    TS_TRY(run_trunk(net, mfcc, 0, B, T, s, &idx, &H, lens));
     TS_HIP(hipMemcpyAsync(feat, net->work(s).pool.buf(idx), (size_t)B * H * net->hid * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
@@ -828,6 +862,16 @@ int ts_vqvae_decode_pair(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_body, co
     const int64_t *lc[2] = {lat_body, lat_hand};
     const int col0[2] = {0, vb->in_dim};
     return vq_decode_n(2, vqs, lc, nullptr, B, H, out, vb->in_dim + vh->in_dim, col0, (hipStream_t)stream);
+}
+
+int ts_vqvae_decode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_body, const int64_t *lat_hand, const int32_t *lens,
+                                int B, int H, float *out, void *stream) {
+    if (!vb || !vh || !lat_body || !lat_hand || !lens || !out) return fail("ts_vqvae_decode_pair_masked: null argument");
+    if (B < 1 || H < 1) return fail("ts_vqvae_decode_pair_masked: bad shape");
+    ts_vqvae *vqs[2] = {vb, vh};
+    const int64_t *lc[2] = {lat_body, lat_hand};
+    const int col0[2] = {0, vb->in_dim};
+    return vq_decode_n(2, vqs, lc, nullptr, B, H, out, vb->in_dim + vh->in_dim, col0, (hipStream_t)stream, lens);
 }
 
 }  // extern "C"

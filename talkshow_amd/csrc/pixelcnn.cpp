@@ -85,11 +85,14 @@ struct ts_pixelcnn {
         // is valid for any caller pointers; key = (B, H, H0, mode)
         DevBuf codes_int, unif_int, dyn;   // dyn: {seed, clip0, position base} of the call being replayed, written by a kernel ahead of it
         DevBuf cAEH, cAEH1, cAV1C, cAV1P;  // the audio terms of ONE chunk of rows, compact (chunked one-shot calls: see run_chunked)
+        DevBuf clip_tab;                   // mixed passes: the Philox subsequence of every clip (int64), read by the captured samplers
         hipStream_t cap_stream = nullptr;
-        // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode) = a whole one-shot call;
-        // (B, Hc, -(1 + phase), mode) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode) = a streaming step.
+        // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
+        // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
+        // (Br, Hc, -(1 + phase), mode, Bs) = Hc rows of a MIXED pass of Bs clips for its first Br clips: the per-clip slabs of the work
+        // buffers are Bs clips apart whatever Br is, so the stride is part of what a captured graph is valid for (0: the slabs are B apart).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
-        typedef std::tuple<int, int, int, int> Key;
+        typedef std::tuple<int, int, int, int, int> Key;
         struct Entry {
             hipGraphExec_t exec;
             uint64_t used;
@@ -233,6 +236,7 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->codes_int.ensure((size_t)cb * ch * 2 * sizeof(int64_t)));
     TS_TRY(w->unif_int.ensure((size_t)cb * ch * 2 * sizeof(float)));
     TS_TRY(w->dyn.ensure(3 * sizeof(uint64_t)));
+    TS_TRY(w->clip_tab.ensure((size_t)cb * sizeof(int64_t)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -264,6 +268,12 @@ struct RunCfg {
     const float *aeh = nullptr, *aeh1 = nullptr, *av1c = nullptr, *av1p = nullptr;
     // the caller's codes / uniforms arrays hold out_H rows per clip, of which this run fills rows out_row0 .. out_row0 + H - 1
     int out_H = 0, out_row0 = 0;
+    // mixed passes (run_mixed): B is the ACTIVE prefix of a pass of Bs clips.  Every per-clip slab of the work buffers is addressed with
+    // Bs, so "the first B clips" is the same memory in every chunk of the pass (0: a uniform call, the slabs are B apart)
+    int Bs = 0;
+    const int64_t *clip_table = nullptr;   // device (Bs,) Philox subsequence per clip, in place of clip0 + b
+    int io_H = 0, io_row0 = 0;             // set by run_rows: row count / first row of the arrays the samplers address (staging or the caller's)
+    int slabB() const { return Bs > 0 ? Bs : B; }
     void audio_from(ts_pixelcnn::Work *wk) { aeh = wk->AEH.f(), aeh1 = wk->AEH1.f(), av1c = wk->AV1C.f(), av1p = wk->AV1P.f(); }
 };
 inline RunCfg one_shot_cfg(int B, int H, int H0, int mode, const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes,
@@ -352,15 +362,16 @@ int launch_slot(ts_pixelcnn *p, ts_pixelcnn::Work *w, const Slot &a, const Slot 
 // `deferred` (optional): the P_l problems (only read by row r+1) are handed back instead of riding in slot V_l
 void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &out, std::vector<SkinnyParams> *deferred = nullptr) {
     const int B = c.B, D = p->D, NL = p->NL, R = c.R;
+    const size_t Bs = c.slabB();         // clips between the per-layer / per-row slabs of a buffer (>= B: see RunCfg::Bs)
     ts_pixelcnn::Work *w = c.w;
     const int *tok = w->tok32.i();
-    const size_t Bp = round_up(B, 16);   // slices of the tiled buffers are whole 16-row blocks apart
+    const size_t Bp = round_up((int)Bs, 16);   // slices of the tiled buffers are whole 16-row blocks apart
     auto XV = [&](int l, int par) { return w->XV.f() + ((size_t)(l * 2 + par) * Bp) * 2 * D; };
     auto HV = [&](int l) { return w->HV.f() + (size_t)l * Bp * 4 * D; };
-    auto V2H = [&](int l) { return w->V2H.f() + (size_t)l * B * 4 * D; };
-    auto P = [&](int l, int par) { return w->P.f() + ((size_t)(l * 2 + par) * B) * 4 * D; };
-    auto Q = [&](DevBuf &q, int row) { return q.f() + (size_t)(row & 3) * B * 4 * D; };
-    auto CR = [&](int l) { return w->CR.f() + (size_t)l * B * 2 * D; };
+    auto V2H = [&](int l) { return w->V2H.f() + (size_t)l * Bs * 4 * D; };
+    auto P = [&](int l, int par) { return w->P.f() + ((size_t)(l * 2 + par) * Bs) * 4 * D; };
+    auto Q = [&](DevBuf &q, int row) { return q.f() + (size_t)(row & 3) * Bs * 4 * D; };
+    auto CR = [&](int l) { return w->CR.f() + (size_t)l * Bs * 2 * D; };
 
     auto gate_common = [&](SkinnyParams &q, int l) {
         q.ldw = 2 * D;
@@ -473,14 +484,15 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
 // horizontal chain + head of position (r, j): NL + 2 launch slots (the sampler launch follows separately)
 void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector<Slot> &out) {
     const int B = c.B, D = p->D, NL = p->NL, R = c.R;
+    const size_t Bs = c.slabB();
     ts_pixelcnn::Work *w = c.w;
     const int *tok = w->tok32.i();
-    auto V2H = [&](int l) { return w->V2H.f() + (size_t)l * B * 4 * D + (size_t)j * 2 * D; };
-    const size_t Bp = round_up(B, 16);
+    auto V2H = [&](int l) { return w->V2H.f() + (size_t)l * Bs * 4 * D + (size_t)j * 2 * D; };
+    const size_t Bp = round_up((int)Bs, 16);
     auto XH = [&](int l, int col) { return w->XH.f() + ((size_t)(l * 2 + col) * Bp) * D; };
-    auto CR = [&](int l) { return w->CR.f() + (size_t)l * B * 2 * D; };
+    auto CR = [&](int l) { return w->CR.f() + (size_t)l * Bs * 2 * D; };
     auto G = [&](int l) { return w->G.f() + (size_t)(l & 1) * Bp * D; };
-    auto T0 = [&](int l) { return w->T0.f() + (size_t)l * B * 2 * D; };
+    auto T0 = [&](int l) { return w->T0.f() + (size_t)l * Bs * 2 * D; };
     auto make_t0 = [&](int l) {   // column 0 only: Wh0_l . XH_l[0], consumed by column 1's S_l
         SkinnyParams t = base_params(B, 2 * D, EPI_LINEAR);
         add_dense(t, XH(l, 0), D, 0, D);
@@ -586,24 +598,26 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
     ts_pixelcnn::Work *w = c.w;
     SampleParams sp;
     std::memset(&sp, 0, sizeof(sp));
-    const int ro = r - c.out_r0;   // row in the caller's (B,H,2) arrays
+    const int ro = r - c.out_r0 + c.io_row0;     // row in the (B,sH,2) arrays the samplers address
+    const int sH = c.io_H > 0 ? c.io_H : c.H;
     sp.logits = w->LG.f();
     sp.B = c.B;
     sp.V = p->V;
     sp.mode = c.mode;
     sp.uniforms = c.uniforms ? c.uniforms + (size_t)ro * 2 + j : nullptr;
-    sp.u_stride = (long)c.H * 2;
+    sp.u_stride = (long)sH * 2;
     sp.seed = c.seed;
     sp.clip_index0 = c.clip0;
+    sp.clip_table = c.clip_table;
     sp.dyn = c.dyn;
     sp.position = (uint32_t)((r - c.pos_r0) * 2 + j + (c.dyn ? 0 : c.pos_base));
     sp.tok32 = w->tok32.i() + (size_t)(r % c.R) * 2 + j;
     sp.tok_stride = (long)c.R * 2;
     sp.codes = c.codes + (size_t)ro * 2 + j;
-    sp.code_stride = (long)c.H * 2;
+    sp.code_stride = (long)sH * 2;
     if (c.logits) {
         sp.logits_copy = c.logits + ((size_t)ro * 2 + j) * p->V;
-        sp.copy_stride = (long)c.H * 2 * p->V;
+        sp.copy_stride = (long)sH * 2 * p->V;
     }
     MiscScope ms(p->ctx, s);
     TS_HIP(launch_sample(sp, s));
@@ -917,7 +931,7 @@ int ts_pixelcnn_graph_stats(ts_pixelcnn *p, void *stream, int B, int H, int mode
     if (!p) return fail("ts_pixelcnn_graph_stats: null argument");
     ts_pixelcnn::Work *w = p->works.find((hipStream_t)stream);
     if (!w) return fail("ts_pixelcnn_graph_stats: nothing was run on this stream");
-    auto jt = w->graph_stats.find(std::make_tuple(B, H, 0, mode));
+    auto jt = w->graph_stats.find(std::make_tuple(B, H, 0, mode, 0));
     if (jt == w->graph_stats.end()) return fail("ts_pixelcnn_graph_stats: no captured graph for this shape");
     if (launches) *launches = jt->second.first;
     if (flops) *flops = jt->second.second;
@@ -976,10 +990,12 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
         }
         return 0;
     };
-    if (!graph) {
-        if (out_H != c.H) return fail("pixelcnn: eager rows write the caller's arrays whole");
+    if (!graph) {   // the samplers address the caller's arrays directly: rows out_row0 .. of out_H per clip
+        if (out_H != c.H && c.logits) return fail("pixelcnn: eager rows with logits write the caller's arrays whole");
         c.codes = codes;
         c.uniforms = uniforms;
+        c.io_H = out_H;
+        c.io_row0 = c.out_row0;
         return row_loop(s);
     }
     c.codes = static_cast<int64_t *>(w->codes_int.p);
@@ -1048,7 +1064,67 @@ int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, co
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H * m.width * f,
                                         (size_t)Hc * m.width * f, B, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode), uniforms, codes, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode, 0), uniforms, codes, s));
+    }
+    return 0;
+}
+
+// ---- mixed passes: clips of different lengths in one pass (talkshow_hip.h has the contract) ------------------------------------------
+// The network is causal in the row direction and no clip reads another, so code row r only has to be computed for the clips that have
+// more than r rows.  With the clips ordered by non-increasing length those are a PREFIX of every per-clip buffer: chunk [r0, r0 + 8) runs
+// with B = #{b : H_b > r0} on the chunk graphs of run_chunked.  A clip that ends inside a chunk is carried to the chunk's end; its surplus
+// rows are computed and discarded (harmless by causality, like the look-ahead sums past the end of a uniform call).
+//
+// Pure host arithmetic (ts_debug_mixed_plan, tests/test_mixed_pass_host.py): active[k] = clips of chunk k.  A pass may use at most
+// `max_counts` DISTINCT active counts; beyond that every count is rounded UP to a multiple of grid = 2, 4, 8, ... (capped at B) — finished
+// clips are carried along, which is always correct — until the distinct counts fit.  Returns the grid.
+int mixed_plan(const int *hrows, int B, int max_counts, std::vector<int> &active) {
+    const int nchunks = (hrows[0] + CHUNK_ROWS - 1) / CHUNK_ROWS;
+    std::vector<int> raw(nchunks);
+    for (int k = 0; k < nchunks; ++k) {
+        int n = 0;
+        while (n < B && hrows[n] > k * CHUNK_ROWS) ++n;   // non-increasing lengths: the active clips are the first n
+        raw[k] = n;
+    }
+    for (int grid = 1;; grid *= 2) {
+        active.resize(nchunks);
+        std::set<int> distinct;
+        for (int k = 0; k < nchunks; ++k) {
+            active[k] = std::min(B, round_up(raw[k], grid));
+            distinct.insert(active[k]);
+        }
+        if ((int)distinct.size() <= max_counts) return grid;
+    }
+}
+
+// graph keys of one mixed pass: one for the first chunk (buffer phase 0), one per distinct active count for the chunks behind it, one or
+// two for a short last chunk — MIXED_MAX_COUNTS + 3 <= the 16 chunk-class slots of Work::make_room, so that a repeated pass finds every
+// graph it needs and captures nothing from its second run on
+constexpr int MIXED_MAX_COUNTS = 12;
+
+int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
+              uint64_t seed, int64_t *codes, bool graph, hipStream_t s) {
+    const size_t D = p->D, f = sizeof(float);
+    constexpr int RING = 4;
+    std::vector<int> active;
+    (void)mixed_plan(hrows.data(), B, MIXED_MAX_COUNTS, active);
+    for (int k = 0; k < (int)active.size(); ++k) {
+        const int r0 = k * CHUNK_ROWS, Hc = std::min(CHUNK_ROWS, hrows[0] - r0), Ba = active[k];
+        RunCfg c{Ba, Hc, 0, r0 + Hc, mode, nullptr, seed, 0, nullptr, nullptr, nullptr, w,
+                 RING, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
+        c.aeh = w->cAEH.f(), c.aeh1 = w->cAEH1.f(), c.av1c = w->cAV1C.f(), c.av1p = w->cAV1P.f();
+        c.out_H = H_max;
+        c.out_row0 = r0;
+        c.Bs = B;
+        c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
+        struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
+            {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
+        for (auto &m : rows)
+            if (p->NL > 1 || m.src == &w->AEH)
+                TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
+                                        (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
+        const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B), uniforms, codes, s));
     }
     return 0;
 }
@@ -1056,6 +1132,52 @@ int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, co
 }  // namespace
 
 extern "C" {
+
+// Host only (no GPU): the chunk plan of a mixed pass.  hrows (B,) code rows per clip, non-increasing, >= 1; max_counts <= 0 = the
+// library's bound.  active_out (ceil(hrows[0] / 8),) clips of every 8-row chunk (may be NULL); returns the rounding grid (1 = no rounding), -1 on a bad table.
+int ts_debug_mixed_plan(const int32_t *hrows, int B, int max_counts, int32_t *active_out) {
+    if (!hrows || B < 1) return fail("ts_debug_mixed_plan: bad argument") ? -1 : -1;
+    for (int b = 0; b < B; ++b)
+        if (hrows[b] < 1 || (b > 0 && hrows[b] > hrows[b - 1])) return fail("ts_debug_mixed_plan: lengths must be >= 1 and non-increasing") ? -1 : -1;
+    std::vector<int> active;
+    const int grid = mixed_plan(hrows, B, max_counts > 0 ? max_counts : MIXED_MAX_COUNTS, active);
+    if (active_out)
+        for (size_t k = 0; k < active.size(); ++k) active_out[k] = active[k];
+    return grid;
+}
+
+int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                               int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                               int64_t *codes, void *stream) {
+    if (!p || !label || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
+    if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
+    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail("ts_pixelcnn_generate_mixed: bad mode");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_pixelcnn_generate_mixed: uniforms required");
+    std::vector<int> hrows(B);
+    for (int b = 0; b < B; ++b) {
+        if (lens_host[b] < 4) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
+        if (b > 0 && lens_host[b] > lens_host[b - 1])
+            return fail("ts_pixelcnn_generate_mixed: lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
+        hrows[b] = lens_host[b] >> 2;
+        if (hrows[b] > H_max) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " has more code rows than H_max");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ts_ctx *ctx = p->ctx;
+    ts_pixelcnn::Work *w = &p->work(s);
+    TS_TRY(ensure_work(p, w, B, H_max));
+    TS_TRY(audio_terms(p, w, aud, B, H_max, s));
+    TS_TRY(class_rows(p, w, label, B, s));
+    {   // the clips' Philox subsequences, in a Work buffer (what the captured samplers read): the caller's table, or 0 .. B-1
+        MiscScope ms(ctx, s);
+        if (clip_index) TS_HIP(hipMemcpyAsync(w->clip_tab.p, clip_index, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        else TS_HIP(launch_iota_i64(static_cast<int64_t *>(w->clip_tab.p), B, 0, s));
+    }
+    const bool graph = p->use_graph && !ctx->prof.on;
+    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, s));
+    MiscScope ms(ctx, s);
+    TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
+    return 0;
+}
 
 int ts_pixelcnn_generate(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
                          const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
@@ -1099,7 +1221,7 @@ int ts_pixelcnn_generate(ts_pixelcnn *p, const int64_t *label, const float *aud,
                                     (size_t)H * 2 * e, B, hipMemcpyDeviceToDevice, s));
         TS_HIP(launch_i64_to_i32(tf, w->tok32.i(), (long)B * Htot * 2, s));
     }
-    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode);
+    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0);
     // A shape without a whole-call graph runs as chunk graphs (two or three small captures that serve every clip length) until it is
     // hot (Work::hot: pinned by ts_pixelcnn_prepare, or its third sighting among the last 16 one-shot calls of this stream); then it gets
     // its own whole-call graph (one replay per call: the serving loops, bench.py).  The cache is bounded either way.
@@ -1120,7 +1242,7 @@ int ts_pixelcnn_prepare(ts_pixelcnn *p, int B, int H, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H));
-    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, 0, mode);
+    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, 0, mode, 0);
     if (!w->pinned.count(key) && w->pinned.size() >= ts_pixelcnn::Work::PIN_CAP) return fail("ts_pixelcnn_prepare: too many pinned shapes on this stream");
     RunCfg c = one_shot_cfg(B, H, 0, mode, nullptr, 0, 0, nullptr, nullptr, w);
     TS_TRY(run_rows(p, c, 0, H, true, key, nullptr, nullptr, s, /*capture_only=*/true));
@@ -1174,7 +1296,7 @@ int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, in
     // in the 4-row rings) and the same set of existing rows above (rows 0..2 have fewer): key on that, not on r0
     const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode), uniforms, codes, s));
+    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0), uniforms, codes, s));
     st->rows += Hc;
     return 0;
 }

@@ -248,6 +248,75 @@ hipError_t launch_gather_rows(const float *table, int ld_table, int nrows, const
     return hipGetLastError();
 }
 
+// gather_rows_kernel for a padded batch of clips of different lengths (mixed passes): rows beyond a clip's own length become zero rows —
+// what the conv gather substitutes past the end of a clip run alone — and their index is never read
+__global__ __launch_bounds__(256) void gather_rows_masked_kernel(const float *__restrict__ table, int ld_table,
+                                                                 const int64_t *__restrict__ idx, long idx_stride, int M, int width,
+                                                                 float *__restrict__ out, int ldo, int nrows, int L,
+                                                                 const int *__restrict__ lens, int len_shr) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const int lane = threadIdx.x & 63;
+    const int b = m / L, t = m - b * L;
+    float4 *dst = reinterpret_cast<float4 *>(out + (long)m * ldo);
+    if (t >= (lens[b] >> len_shr)) {
+        for (int c = lane; c < width / 4; c += 64) dst[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int64_t r = idx[(long)m * idx_stride];
+    if (r < 0 || r >= nrows) {   // a bad index INSIDE the clip stays loud
+        const float q = __builtin_nanf("");
+        for (int c = lane; c < width / 4; c += 64) dst[c] = make_float4(q, q, q, q);
+        return;
+    }
+    const float4 *src = reinterpret_cast<const float4 *>(table + r * ld_table);
+    for (int c = lane; c < width / 4; c += 64) dst[c] = src[c];
+}
+hipError_t launch_gather_rows_masked(const float *table, int ld_table, int nrows, const int64_t *idx, long idx_stride, int M,
+                                     int width, float *out, int ldo, int L, const int *lens, int len_shr, hipStream_t stream) {
+    if (width % 4 || ld_table % 4 || ldo % 4 || L < 1 || M % L || !lens || len_shr < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows_masked_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, table, ld_table, idx, idx_stride, M, width,
+                       out, ldo, nrows, L, lens, len_shr);
+    return hipGetLastError();
+}
+
+__global__ void pad_rows_masked_kernel(const float *__restrict__ src, int lds_, int c, float *__restrict__ dst, int ldd, int cpad,
+                                       long M, int L, const int *__restrict__ lens) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M * cpad) return;
+    const long m = i / cpad;
+    const int k = (int)(i - m * cpad);
+    const int b = (int)(m / L), t = (int)(m - (long)b * L);
+    dst[m * ldd + k] = (k < c && t < lens[b]) ? src[m * lds_ + k] : 0.f;   // the padding is not read: NaNs there never enter a product
+}
+hipError_t launch_pad_rows_masked(const float *src, int lds_, int c, float *dst, int ldd, int cpad, int B, int L, const int *lens,
+                                  hipStream_t stream) {
+    const long M = (long)B * L, n = M * cpad;
+    if (!lens || L < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pad_rows_masked_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, lds_, c, dst, ldd, cpad, M, L, lens);
+    return hipGetLastError();
+}
+
+__global__ void mask_codes_kernel(int64_t *codes, int B, int H, const int *__restrict__ lens) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * H) return;
+    const int b = i / H, r = i - b * H;
+    if (r >= (lens[b] >> 2)) codes[2l * i] = codes[2l * i + 1] = -1;
+}
+hipError_t launch_mask_codes(int64_t *codes, int B, int H, const int *lens, hipStream_t stream) {
+    hipLaunchKernelGGL(mask_codes_kernel, dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, stream, codes, B, H, lens);
+    return hipGetLastError();
+}
+
+__global__ void iota_i64_kernel(int64_t *dst, int n, int64_t first) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = first + i;
+}
+hipError_t launch_iota_i64(int64_t *dst, int n, int64_t first, hipStream_t stream) {
+    hipLaunchKernelGGL(iota_i64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dst, n, first);
+    return hipGetLastError();
+}
+
 __global__ void pad_rows_kernel(const float *__restrict__ src, int lds_, int c, float *__restrict__ dst, int ldd,
                                 int cpad, long M) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -471,7 +540,9 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleParams p) {
             u = p.uniforms[(long)b * p.u_stride];
         } else {
             const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-            const uint64_t clip = (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+            // a mixed pass orders its clips by length: the subsequence then comes from a per-clip table, so that a clip's draws keep
+            // depending on its GLOBAL index only
+            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
             uint32_t r;
             philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
                           (uint32_t)(seed >> 32), r);
