@@ -185,6 +185,26 @@ void ts_face_destroy(ts_face *face);
  * hidden_dev optional (B,frames,768): the wav2vec2 last_hidden_state (parity tests). */
 int ts_face_generate(ts_face *face, const float *wav_dev, int B, int N, int frames, const float *id_dev, float *out_dev,
                      float *hidden_dev, void *stream);
+/* ---- mixed face passes: clips of DIFFERENT lengths in one pass (no counterpart in the reference, which runs one recording at a time) ------
+ * B clips, clip b with ns[b] 16 kHz samples and frames[b] output frames, stored padded to N_max samples and written padded to T_max frames;
+ * the arithmetic of ts_face_generate on every clip.  Rows t < frames[b] of clip b are BIT-IDENTICAL whatever else is in the pass — the clip
+ * alone in a mixed pass of one included — and bit-identical to ts_face_generate on the clip alone (B = 1, N = ns[b], frames = frames[b]) in a
+ * process that runs without the stream-K band (TS_CONV_SK=0): no GEMM of a mixed pass takes the band, every kernel that looks across rows
+ * (GroupNorm statistics, interpolation, positional and k = 3 convolutions, attention) stops at the clip's own length, and the rows beyond it
+ * hold the zeros a clip run alone reads past its end.  This is the batch-invariant face entry: ts_face_generate's bits depend, by default,
+ * on the batch a clip rides in (to rounding only).  Clips need no particular order.
+ *   ns_host / ns_dev, frames_host / frames_dev (B,) int32: the same tables in host memory (checked and planned from without synchronising;
+ *     not read after the call returns) and in device memory.  400 <= ns[b] <= N_max, 1 <= frames[b] <= T_max <= 65536 (frames[b] =
+ *     ns[b] * 30 / 16000 normally); anything else, or a NULL table, is an error and nothing is written.
+ *   wav_dev (B,N_max): samples at or beyond ns[b] are never read (they may hold anything, NaNs included).
+ *   id_dev (B,num_classes) as for ts_face_generate.
+ *   out_dev (B,T_max,103 | 106): rows t < frames[b] = the clip's output, rows t >= frames[b] are written as 0.
+ *   hidden_dev optional (B,T_max,768): the same rule.  Every element of both outputs is written, nothing else is touched.
+ * The opt-in split-bf16 plans (ts_face_set_arith 3 / 6) are not offered: an error.  The call allocates nothing beyond the growth of the stream's
+ * work buffers and never synchronises; the attention work list travels to the device in kernel arguments, in stream order. */
+int ts_face_generate_mixed(ts_face *face, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
+                           const int32_t *frames_dev, int B, int N_max, int T_max, const float *id_dev, float *out_dev, float *hidden_dev,
+                           void *stream);
 /* OPT-IN arithmetic plan of the generator's GEMMs (no counterpart in the reference, which runs fp32 throughout): 0 = fp32 MFMA,
  * the default and the path every parity claim is made on; 3 / 6 = split-bf16: each fp32 operand becomes 2 / 3 bf16 terms and a
  * product 3 / 6 exact bf16 products accumulated in fp32 (csrc/conv_gemm_split.hip; measured error vs the reference golden in

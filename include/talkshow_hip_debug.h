@@ -155,6 +155,30 @@ int ts_debug_w2v_conv0(const float *wav, int B, int N, const float *w, const flo
 /* x[b][t][col0 + j] = bias[j] + sum_c w[j][c] id[b][c] for j < nj, c < nc, every t < T of clip b < B; x rows of pitch ld. */
 int ts_debug_fill_id(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0, int B, int T,
                      void *stream);
+/* Their length variants (mixed face passes, talkshow_hip.h: B clips padded to N samples / T frames; ns / frames / lens are DEVICE int32 tables
+ * of the clips' own counts unless named _host).  Valid rows are the arithmetic of the entries above on the clip alone, bit for bit; rows at or
+ * beyond a clip's length are written as zeros, samples / rows beyond it are not read.
+ * ts_debug_attention_mixed: qkv (B, T_max, 3 HID), out (B, T_max, HID); keys and queries of clip b stop at frames[b]; out rows beyond are NOT
+ * written.  Builds the work list from frames_host (ts_debug_face_mixed_grid) and synchronizes `stream`. */
+int ts_debug_attention_mixed(const float *qkv, const int32_t *frames_host, const int32_t *frames_dev, int B, int T_max, int HID, int heads,
+                             float scale, float *out, void *stream);
+/* M = B T rows (b, t); rows t >= lens[b] are written as zeros, their input is not read. */
+int ts_debug_layernorm_rows_lens(const float *x, int ldx, int B, int T, const int32_t *lens, int C, const float *gamma, const float *beta,
+                                 const float *post_res, int ldr, int relu, float *out, int ldo, void *stream);
+/* x (B, Lin, 512) -> out (B, T, 512): clip b interpolates its own feature rows (of ns[b] samples) to its own frames[b] frames. */
+int ts_debug_lerp_ln_lens(const float *x, int B, int Lin, int T, const int32_t *ns, const int32_t *frames, const float *gamma,
+                          const float *beta, float *out, void *stream);
+/* wav (B, N) -> out (B, L0, 512), L0 = (N - 10) / 5 + 1; GroupNorm statistics over the clip's own (ns[b] - 10) / 5 + 1 rows.  form as above.
+ * Allocates its own scratch and synchronizes `stream`. */
+int ts_debug_w2v_conv0_lens(const float *wav, int B, int N, const int32_t *ns, const float *w, const float *gamma, const float *beta,
+                            int form, float *out, void *stream);
+int ts_debug_fill_id_lens(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0, int B, int T,
+                          const int32_t *lens, void *stream);
+/* Host-only (no GPU): the work list of a mixed pass's attention launch for the frame table frames_host (B,), 1 <= frames <= 65536.  Returns the
+ * number n of workgroups (-1: bad table, or cap < n); out3 (n, 3) or NULL: workgroup i runs (clip, head, query tile of 64) or (-1, -1, -1).
+ * Every tile with 64 tile < frames[clip] appears once; the tiles of one (clip, head) carry ids of equal residue mod 8 (one XCD); ids without a
+ * tile pad the eight queues to equal length.  No reference counterpart. */
+int ts_debug_face_mixed_grid(const int32_t *frames_host, int B, int heads, int32_t *out3, int cap);
 
 /* Test aid: how many captured hipGraphs the PixelCNN keeps for `stream` right now (whole-call graphs of repeated shapes + the chunk
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */

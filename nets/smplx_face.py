@@ -84,6 +84,47 @@ class TrainWrapper(TrainWrapperBaseClass):
             out = denormalize(out, norm_stats[0], norm_stats[1])
         return out
 
+    def generate_clips(self, clips, ids=None, frames=None, norm_stats=None):
+        '''
+        Recordings of DIFFERENT lengths in one pass (`FaceGenerator.run_clips`; nothing like it in the reference, which runs one recording
+        per call): clips = list of 1-D arrays of 16 kHz samples or .wav / .npy paths (through `get_wav16`, as `infer_on_audio`);
+        ids = None (the all-zero identity row for every clip) or one class index per clip; frames = one count per clip (default
+        samples * 30 // 16000) -> list of float32 numpy (frames[b], 103), denormalised under the same rule as `infer_on_audio`.
+        '''
+        if self.config.Data.pose.normalization and norm_stats is None:
+            raise AssertionError("config.Data.pose.normalization is set: norm_stats=(mean, std) is required")
+        if isinstance(clips, (str, bytes, np.ndarray, torch.Tensor)) or not hasattr(clips, "__len__") or len(clips) < 1:
+            raise ValueError("generate_clips: clips must be a non-empty list of sample arrays or audio paths")
+        B = len(clips)
+        if ids is None:
+            id_rows = np.zeros((B, self.num_classes), dtype=np.float32)
+        else:
+            idx = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids)
+            if idx.ndim != 1 or idx.shape[0] != B or not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError(f"generate_clips: ids must be {B} class indices, one per clip")
+            if ((idx < 0) | (idx >= self.num_classes)).any():
+                raise ValueError(f"generate_clips: class indices must lie in [0, {self.num_classes})")
+            id_rows = np.eye(self.num_classes, dtype=np.float32)[idx]
+        if frames is not None and (np.ndim(frames) != 1 or len(frames) != B):
+            raise ValueError(f"generate_clips: frames must be {B} integers, one per clip")
+        wavs = []
+        for b, c in enumerate(clips):
+            if isinstance(c, (str, bytes)) or hasattr(c, "__fspath__"):
+                c = get_wav16(c)[:, 0]
+            elif torch.is_tensor(c):
+                c = c.detach().cpu().numpy()
+            c = np.asarray(c)
+            if c.ndim != 1:
+                raise ValueError(f"generate_clips: clip {b} has shape {tuple(c.shape)}; 1-D samples or a path is expected")
+            wavs.append(c)
+        self.generator.eval()
+        with torch.no_grad():
+            outs = self.generator.run_clips(wavs, id_rows, frames)
+        outs = [o.cpu().numpy() for o in outs]
+        if self.config.Data.pose.normalization:
+            outs = [denormalize(o, norm_stats[0], norm_stats[1]) for o in outs]
+        return outs
+
     def generate(self, wv2_feat, frame):
         '''wv2_feat (B,1,N) samples -> tensor (B,frame,103) with the all-zero identity vector    [smplx_face.py:221-238]'''
         return self._run(wv2_feat, self._identity(None).repeat(wv2_feat.shape[0], 1), frame)

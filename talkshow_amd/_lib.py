@@ -78,6 +78,7 @@ SIGNATURES = {
     "ts_face_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, C.POINTER(_vp)]),
     "ts_face_destroy": (None, [_vp]),
     "ts_face_generate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ts_face_generate_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ts_face_set_arith": (_i, [_vp, _i]),
     "ts_mfcc_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "ts_mfcc_destroy": (None, [_vp]),
@@ -115,6 +116,12 @@ SIGNATURES = {
     "ts_debug_lerp_ln": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ts_debug_w2v_conv0": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "ts_debug_fill_id": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "ts_debug_attention_mixed": (_i, [_vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, C.c_float, _vp, _vp]),
+    "ts_debug_layernorm_rows_lens": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "ts_debug_lerp_ln_lens": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ts_debug_w2v_conv0_lens": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ts_debug_fill_id_lens": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ts_debug_face_mixed_grid": (_i, [C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), _i]),
     "ts_op_vq_argmin": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "ts_op_linear": (_i, [_vp, _vp, _i, _i, _fp, _fp, _i, _i, _vp, _vp]),
     "ts_op_sample": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

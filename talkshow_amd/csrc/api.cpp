@@ -571,6 +571,77 @@ int ts_debug_fill_id(const float *id, int nc, const float *w, const float *bias,
     return 0;
 }
 
+// ---- their length variants (mixed face passes), one launch each; the tables are device int32 unless named _host ----
+int ts_debug_face_mixed_grid(const int32_t *frames_host, int B, int heads, int32_t *out3, int cap) {
+    std::vector<int> work;
+    const int n = ts::face_mixed_grid(frames_host, B, heads, work);
+    if (n < 0) return -1;
+    if (out3) {
+        if (cap < n) return -1;
+        for (int i = 0; i < n; ++i) {
+            const int e = work[i], z = e >> 10;
+            out3[3 * i] = e < 0 ? -1 : z / heads;
+            out3[3 * i + 1] = e < 0 ? -1 : z % heads;
+            out3[3 * i + 2] = e < 0 ? -1 : e & 1023;
+        }
+    }
+    return n;
+}
+int ts_debug_attention_mixed(const float *qkv, const int32_t *frames_host, const int32_t *frames_dev, int B, int T_max, int HID, int heads,
+                             float scale, float *out, void *stream) {
+    if (!qkv || !out || !frames_host || !frames_dev || B < 1 || T_max < 1 || T_max > 65536 || heads < 1 || HID != heads * 64)
+        return fail("ts_debug_attention_mixed: bad argument");
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] < 1 || frames_host[b] > T_max) return fail("ts_debug_attention_mixed: bad frame table");
+    std::vector<int> work;
+    const int n = ts::face_mixed_grid(frames_host, B, heads, work);
+    if (n < 1) return fail("ts_debug_attention_mixed: bad frame table");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf wk;
+    TS_TRY(wk.ensure((size_t)n * sizeof(int)));
+    TS_HIP(ts::launch_put_words(wk.i(), work.data(), n, s));
+    TS_HIP(ts::launch_attention_mixed(qkv, T_max, HID, heads, wk.i(), n, frames_dev, scale, out, s));
+    TS_HIP(hipStreamSynchronize(s));   // the work list dies with this frame
+    return 0;
+}
+int ts_debug_layernorm_rows_lens(const float *x, int ldx, int B, int T, const int32_t *lens, int C, const float *gamma, const float *beta,
+                                 const float *post_res, int ldr, int relu, float *out, int ldo, void *stream) {
+    if (!x || !gamma || !beta || !out || !lens || B < 1 || T < 1 || ldx < C || ldo < C || (post_res && ldr < C))
+        return fail("ts_debug_layernorm_rows_lens: bad argument");
+    if (C != 64 && C != 256 && C != 512 && C != 768) return fail("ts_debug_layernorm_rows_lens: C must be 64, 256, 512 or 768");
+    TS_HIP(ts::launch_layernorm_rows_lens(x, ldx, B, T, lens, C, gamma, beta, post_res, ldr, relu, out, ldo, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_lerp_ln_lens(const float *x, int B, int Lin, int T, const int32_t *ns, const int32_t *frames, const float *gamma,
+                          const float *beta, float *out, void *stream) {
+    if (!x || !ns || !frames || !gamma || !beta || !out || B < 1 || Lin < 1 || T < 1) return fail("ts_debug_lerp_ln_lens: bad argument");
+    TS_HIP(ts::launch_lerp_ln_lens(x, B, Lin, T, ns, frames, gamma, beta, out, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_w2v_conv0_lens(const float *wav, int B, int N, const int32_t *ns, const float *w, const float *gamma, const float *beta,
+                            int form, float *out, void *stream) {
+    if (!wav || !ns || !w || !gamma || !beta || !out || B < 1 || N < 10 || form < -1 || form > 1)
+        return fail("ts_debug_w2v_conv0_lens: bad argument");
+    constexpr int C = 512;
+    const int L0 = (N - 10) / 5 + 1, ntb = (L0 + 127) / 128;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf part, stats;
+    TS_TRY(part.ensure((size_t)B * ntb * C * sizeof(double2)));
+    TS_TRY(stats.ensure((size_t)B * C * sizeof(float2)));
+    const bool moments = form < 0 ? ts::knobs().w2v_moments : form == 1;
+    TS_HIP(ts::launch_w2v_conv0_lens(wav, B, N, ns, w, gamma, beta, static_cast<double2 *>(part.p), static_cast<float2 *>(stats.p), out, C,
+                                     moments, s));
+    TS_HIP(hipStreamSynchronize(s));   // the scratch dies with this frame
+    return 0;
+}
+int ts_debug_fill_id_lens(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0, int B, int T,
+                          const int32_t *lens, void *stream) {
+    if (!id || !w || !bias || !x || !lens || nc < 1 || nj < 1 || col0 < 0 || ld < col0 + nj || B < 1 || T < 1)
+        return fail("ts_debug_fill_id_lens: bad argument");
+    TS_HIP(ts::launch_fill_id_lens(id, nc, w, bias, nj, x, ld, col0, B, T, lens, (hipStream_t)stream));
+    return 0;
+}
+
 int ts_op_vq_argmin(ts_ctx *ctx, const float *x, int M, const float *cb, int ncode, int dim, int64_t *idx, void *stream) {
     if (!ctx || !x || !cb || !idx) return fail("ts_op_vq_argmin: null argument");
     hipStream_t s = (hipStream_t)stream;

@@ -102,6 +102,7 @@ struct ts_face {
 
     struct Work {
         DevBuf A, Bf, part, stats, X512, H, H2, TMP, QKV, ATT, FF, X320, Y1, Y2, R, D1, D2;
+        DevBuf att_work;   // mixed passes: the attention work list (face_mixed_grid), written on the stream by every call
     };
     StreamWorks<Work> works;
     Work &work(hipStream_t s) { return works.get(s); }
@@ -109,7 +110,49 @@ struct ts_face {
 
 namespace ts {
 int face_hidden(const ts_face *f) { return f->HID; }
+
+// Work list of the mixed attention launch (face.hip::attention_mixed_kernel), host arithmetic only: one entry per workgroup id,
+// (clip * heads + head) << 10 | query tile for every tile with 64 tile < frames[clip], -1 for an id without a tile.  Workgroup ids go to the
+// XCDs round-robin, so lane x = id % 8 of the list is XCD x's queue: every (clip, head) is dealt WHOLE to one lane — its tiles run on one XCD
+// back to back and find K / V in that L2, as in the uniform kernel — longest first (stable: clip-major, head-minor among equals), each to the
+// lane that is shortest so far (ties: the lowest lane), and the lanes are padded to the longest with -1.  Equal frame counts give the uniform
+// kernel's order.
+int face_mixed_grid(const int32_t *frames, int B, int heads, std::vector<int> &work) {
+    work.clear();
+    if (!frames || B < 1 || heads < 1 || (long)B * heads >= (1l << 21)) return -1;
+    std::vector<int> clips(B);
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1 || frames[b] > 65536) return -1;
+        clips[b] = b;
+    }
+    std::stable_sort(clips.begin(), clips.end(), [&](int a, int b) { return (frames[a] + 63) / 64 > (frames[b] + 63) / 64; });
+    std::vector<int> lane[8];
+    for (int b : clips) {
+        const int nq = (frames[b] + 63) / 64;
+        for (int h = 0; h < heads; ++h) {
+            int x = 0;
+            for (int c = 1; c < 8; ++c)
+                if (lane[c].size() < lane[x].size()) x = c;
+            for (int q = 0; q < nq; ++q) lane[x].push_back(((b * heads + h) << 10) | q);
+        }
+    }
+    size_t slots = 0;
+    for (auto &l : lane) slots = std::max(slots, l.size());
+    work.assign(slots * 8, -1);
+    for (int x = 0; x < 8; ++x)
+        for (size_t i = 0; i < lane[x].size(); ++i) work[i * 8 + x] = lane[x][i];
+    return (int)work.size();
 }
+}  // namespace ts
+
+namespace {
+// a mixed pass (ts_face_generate_mixed): the clips' own sample and frame counts; the uniform entry passes none
+struct FaceLens {
+    const int32_t *ns_dev, *frames_host, *frames_dev;
+};
+int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float *id, float *out, float *hidden_out, hipStream_t s,
+             const FaceLens *mx);
+}  // namespace
 
 extern "C" {
 
@@ -287,7 +330,35 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
                      void *stream) {
     if (!f || !wav || !out || (!id && f->NCLS > 0)) return fail("ts_face_generate: null argument");
     if (B < 1 || frames < 1) return fail("ts_face_generate: bad shape");
-    hipStream_t s = (hipStream_t)stream;
+    return face_run(f, wav, B, N, frames, id, out, hidden_out, (hipStream_t)stream, nullptr);
+}
+
+// Clips of different lengths in one pass (talkshow_hip.h): the launch plan of ts_face_generate on the padded batch, with the length variants
+// of the kernels wherever a clip's end matters, and no stream-K band.
+int ts_face_generate_mixed(ts_face *f, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
+                           const int32_t *frames_dev, int B, int N_max, int T_max, const float *id, float *out, float *hidden_out,
+                           void *stream) {
+    if (!f || !wav || !out || (!id && f->NCLS > 0)) return fail("ts_face_generate_mixed: null argument");
+    if (!ns_host || !ns_dev || !frames_host || !frames_dev) return fail("ts_face_generate_mixed: null length table");
+    if (B < 1 || N_max < 1 || T_max < 1 || T_max > 65536) return fail("ts_face_generate_mixed: bad shape");
+    if (f->split_planes) return fail("ts_face_generate_mixed: the split-bf16 plans (ts_face_set_arith 3 / 6) are not offered in a mixed pass");
+    for (int b = 0; b < B; ++b) {
+        const std::string clip = "ts_face_generate_mixed: clip " + std::to_string(b);
+        if (ns_host[b] < 400) return fail(clip + " is shorter than 400 samples");
+        if (ns_host[b] > N_max) return fail(clip + " is longer than N_max");
+        if (frames_host[b] < 1) return fail(clip + " has no frames");
+        if (frames_host[b] > T_max) return fail(clip + " has more frames than T_max");
+    }
+    const FaceLens mx{ns_dev, frames_host, frames_dev};
+    return face_run(f, wav, B, N_max, T_max, id, out, hidden_out, (hipStream_t)stream, &mx);
+}
+
+}  // extern "C"
+
+namespace {
+// mx == nullptr: B clips of N samples and `frames` frames each.  mx: B clips padded to N samples and `frames` frames (the tables are checked)
+int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float *id, float *out, float *hidden_out, hipStream_t s,
+             const FaceLens *mx) {
     ts_ctx *ctx = f->ctx;
     const int C0 = f->C0, HID = f->HID, FFN = f->FFN, HEADS = f->HEADS, T = frames;
     int L[7];
@@ -319,26 +390,53 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     TS_TRY(w.R.ensure(M * 256 * F));
     TS_TRY(w.D1.ensure(M * 64 * F));
     TS_TRY(w.D2.ensure(M * 64 * F));
+    const int32_t *lens = mx ? mx->frames_dev : nullptr;   // frames per clip: the length table of every masked layer
+    int n_work = 0;
+    if (mx) {   // the attention work list of this pass, from the host table; it reaches the stream's buffer in stream order
+        std::vector<int> work;
+        n_work = face_mixed_grid(mx->frames_host, B, HEADS, work);
+        if (n_work < 1) return fail("ts_face_generate_mixed: bad frame table");
+        TS_TRY(w.att_work.ensure((size_t)n_work * sizeof(int)));
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w.att_work.i(), work.data(), n_work, s));
+    }
 
     ConvParams p;
     auto conv = [&](const ConvLayer &Ly, const float *x, int ldx, int Bc, int Lin, int Lout, int stride, const float *res,
                     int ldr, float *o, int ldo, int col0, int nstore, int act) -> int {
         params_for(Ly, x, ldx, Bc, Lin, Lout, stride, res, ldr, o, ldo, col0, nstore, act, &p, f->split_planes == 2);
-        p.sk_ok = 1;   // tolerance-only GEMMs (<= 1e-4 vs the reference; measured 2e-6): the ring engine may split the last unit's tiles in K
+        // tolerance-only GEMMs (<= 1e-4 vs the reference; measured 2e-6): the ring engine may split the last unit's tiles in K.  Not in a mixed
+        // pass: without the band a row's bits do not depend on the rows it shares a launch with
+        p.sk_ok = mx ? 0 : 1;
         return run_conv(ctx, p, f->split_planes ? 20 + f->split_planes : 0, s);
+    };
+    // a pointwise layer over all M rows.  Mixed passes: in the (B, T) row form with the masked epilogue — rows at or beyond frames[b] are stored
+    // as zeros (same plan: it depends on M, N and K only)
+    auto linear_masked = [&](const ConvLayer &Ly, const float *x, int ldx, float *o, int ldo, int col0, int nstore) -> int {
+        if (!mx) return conv(Ly, x, ldx, 1, (int)M, (int)M, 1, nullptr, 0, o, ldo, col0, nstore, 0);
+        params_for(Ly, x, ldx, B, T, T, 1, nullptr, 0, o, ldo, col0, nstore, 0, &p);
+        p.lens = lens;
+        return run_conv(ctx, p, 0, s);
     };
     auto ln = [&](const float *x, int C, const LNp &q, const float *post, int relu, float *o) -> int {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_layernorm_rows(x, C, M, C, q.g.f(), q.b.f(), post, C, relu, o, C, s));
+        // mixed passes: zeros at or beyond frames[b] — what the k = 3 layers read past a clip's end, and the padding of `hidden`
+        if (mx) TS_HIP(launch_layernorm_rows_lens(x, C, B, T, lens, C, q.g.f(), q.b.f(), post, C, relu, o, C, s));
+        else TS_HIP(launch_layernorm_rows(x, C, M, C, q.g.f(), q.b.f(), post, C, relu, o, C, s));
         return 0;
     };
 
     // ---- wav2vec2 feature extractor ----
     {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_w2v_conv0(wav, B, N, L[0], f->c0_w.f(), f->c0_g.f(), f->c0_b.f(), static_cast<double2 *>(w.part.p),
-                                static_cast<float2 *>(w.stats.p), w.A.f(), C0, ts::knobs().w2v_moments, s));
+        if (mx)   // statistics over each clip's own rows; samples at or beyond ns[b] are not read
+            TS_HIP(launch_w2v_conv0_lens(wav, B, N, mx->ns_dev, f->c0_w.f(), f->c0_g.f(), f->c0_b.f(), static_cast<double2 *>(w.part.p),
+                                         static_cast<float2 *>(w.stats.p), w.A.f(), C0, ts::knobs().w2v_moments, s));
+        else
+            TS_HIP(launch_w2v_conv0(wav, B, N, L[0], f->c0_w.f(), f->c0_g.f(), f->c0_b.f(), static_cast<double2 *>(w.part.p),
+                                    static_cast<float2 *>(w.stats.p), w.A.f(), C0, ts::knobs().w2v_moments, s));
     }
+    // (stride 2, no padding: a valid output row reads valid input rows only — in a mixed pass the rows beyond a clip's own are dead weight)
     float *cur = w.A.f(), *nxt = w.Bf.f();
     for (int i = 0; i < 6; ++i) {
         TS_TRY(conv(f->fc[i], cur, C0, B, L[i], L[i + 1], 2, nullptr, 0, nxt, C0, 0, C0, 3));
@@ -346,12 +444,15 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     }
     {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_lerp_ln(cur, B, L[6], T, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
+        if (mx) TS_HIP(launch_lerp_ln_lens(cur, B, L[6], T, mx->ns_dev, lens, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
+        else TS_HIP(launch_lerp_ln(cur, B, L[6], T, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
     }
     // the grouped positional conv reads 64-channel windows every 48 channels: the last group's window runs 16 floats past
     // the row (zero weights there) — keep the slack after the final row finite
     TS_HIP(hipMemsetAsync(w.H.f() + M * HID, 0, 64 * F, s));
-    TS_TRY(conv(f->fp_proj, w.X512.f(), C0, 1, (int)M, (int)M, 1, nullptr, 0, w.H.f(), HID, 0, HID, 0));
+    // (masked in a mixed pass: the positional conv reads 64 rows either side of a frame and finds zeros beyond the clip's end, as it finds its own
+    // padding when the clip runs alone)
+    TS_TRY(linear_masked(f->fp_proj, w.X512.f(), C0, w.H.f(), HID, 0, HID));
     // ---- positional conv embedding (16 groups as batched problems) + residual + LayerNorm ----
     {
         std::memset(&p, 0, sizeof(p));
@@ -404,13 +505,19 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     }
     TS_TRY(ln(w.TMP.f(), HID, f->enc_ln, nullptr, 0, w.H.f()));
     // ---- transformer layers (post-LN) ----
+    double att_tt = (double)B * T * T;   // sum over the clips of frames^2
+    if (mx) {
+        att_tt = 0;
+        for (int b = 0; b < B; ++b) att_tt += (double)mx->frames_host[b] * mx->frames_host[b];
+    }
     for (auto &Lp : f->layers) {
         EncLayer &E = *Lp;
         TS_TRY(conv(E.qkv, w.H.f(), HID, 1, (int)M, (int)M, 1, nullptr, 0, w.QKV.f(), 3 * HID, 0, 3 * HID, 0));
         // softmax(Q K^T / 8) V per (clip, head), fused: the scores stay in registers (face.hip::attention_kernel)
         {
-            MiscScope ms(ctx, s, FAM_ATTN, 4.0 * B * HEADS * (double)T * T * 64);   // Q K^T and P V: 2 x (2 T^2 d) per (clip, head)
-            TS_HIP(launch_attention(w.QKV.f(), B, T, HID, HEADS, 0.125f, w.ATT.f(), s));
+            MiscScope ms(ctx, s, FAM_ATTN, 4.0 * HEADS * att_tt * 64);   // Q K^T and P V: 2 x (2 T^2 d) per (clip, head)
+            if (mx) TS_HIP(launch_attention_mixed(w.QKV.f(), T, HID, HEADS, w.att_work.i(), n_work, lens, 0.125f, w.ATT.f(), s));
+            else TS_HIP(launch_attention(w.QKV.f(), B, T, HID, HEADS, 0.125f, w.ATT.f(), s));
         }
         TS_TRY(conv(E.outp, w.ATT.f(), HID, 1, (int)M, (int)M, 1, w.H.f(), HID, w.TMP.f(), HID, 0, HID, 0));
         TS_TRY(ln(w.TMP.f(), HID, E.ln1, nullptr, 0, w.H2.f()));
@@ -420,10 +527,11 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     }
     if (hidden_out) TS_HIP(hipMemcpyAsync(hidden_out, w.H.f(), M * HID * F, hipMemcpyDeviceToDevice, s));
     // ---- audio_feature_map | id channels ----
-    TS_TRY(conv(f->afm, w.H.f(), HID, 1, (int)M, (int)M, 1, nullptr, 0, w.X320.f(), CIN, 0, 256, 0));
+    TS_TRY(linear_masked(f->afm, w.H.f(), HID, w.X320.f(), CIN, 0, 256));
     if (f->NCLS > 0) {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_fill_id(id, f->NCLS, f->id_w.f(), f->id_b.f(), 64, w.X320.f(), 320, 256, B, T, s));
+        if (mx) TS_HIP(launch_fill_id_lens(id, f->NCLS, f->id_w.f(), f->id_b.f(), 64, w.X320.f(), 320, 256, B, T, lens, s));
+        else TS_HIP(launch_fill_id(id, f->NCLS, f->id_w.f(), f->id_b.f(), 64, w.X320.f(), 320, 256, B, T, s));
     }
     // ---- SeqTranslator1D: 3 x {conv, LN, + residual, ReLU} ----
     TS_TRY(conv(f->fn[0], w.X320.f(), CIN, B, T, T, 1, nullptr, 0, w.Y1.f(), 256, 0, 256, 0));
@@ -440,7 +548,7 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     TS_TRY(ln(w.D1.f(), 64, f->dec_ln[0][1], nullptr, 1, w.D2.f()));
     TS_TRY(conv(f->dec[0][2], w.D2.f(), 64, B, T, T, 1, nullptr, 0, w.D1.f(), 64, 0, 64, 0));
     TS_TRY(ln(w.D1.f(), 64, f->dec_ln[0][2], nullptr, 1, w.D2.f()));
-    TS_TRY(conv(f->fin[0], w.D2.f(), 64, 1, (int)M, (int)M, 1, nullptr, 0, out, OUTW, 0, JAW, 0));
+    TS_TRY(linear_masked(f->fin[0], w.D2.f(), 64, out, OUTW, 0, JAW));
     // ---- expression head (256 ch) ----
     TS_TRY(conv(f->dec[1][0], w.Y2.f(), 256, B, T, T, 1, nullptr, 0, w.Y1.f(), 256, 0, 256, 0));
     TS_TRY(ln(w.Y1.f(), 256, f->dec_ln[1][0], nullptr, 1, w.R.f()));
@@ -448,8 +556,7 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     TS_TRY(ln(w.Y1.f(), 256, f->dec_ln[1][1], nullptr, 1, w.R.f()));
     TS_TRY(conv(f->dec[1][2], w.R.f(), 256, B, T, T, 1, nullptr, 0, w.Y1.f(), 256, 0, 256, 0));
     TS_TRY(ln(w.Y1.f(), 256, f->dec_ln[1][2], nullptr, 1, w.R.f()));
-    TS_TRY(conv(f->fin[1], w.R.f(), 256, 1, (int)M, (int)M, 1, nullptr, 0, out, OUTW, JAW, 100, 0));
+    TS_TRY(linear_masked(f->fin[1], w.R.f(), 256, out, OUTW, JAW, 100));
     return 0;
 }
-
-}  // extern "C"
+}  // namespace

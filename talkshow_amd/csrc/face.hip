@@ -8,6 +8,8 @@
 //   layernorm_rows   nn.LayerNorm over channels (+ post-norm residual, ReLU): encoder LNs and nets/layers.py:142-151
 //   attention        fused QK^T -> online soft-max -> PV of HF eager_attention_forward, one workgroup per 64 queries of a (clip, head)
 //   fill_id          id_mlp(one-hot id) broadcast over time and concatenated (nets/spg/s2g_face.py:127-130)
+#include <cstring>
+
 #include "kernels.h"
 
 namespace ts {
@@ -192,6 +194,168 @@ hipError_t launch_w2v_conv0(const float *wav, int B, int N, int L0, const float 
     return hipGetLastError();
 }
 
+// ---- length variants of the conv0 kernels (mixed passes: clips of different lengths padded to N samples; ns = the clips' own sample counts on the
+// device).  The statements of the kernels above on the clip's own counts: a clip's frames fall into the same time blocks as when it runs alone,
+// blocks beyond its last frame add exact zeros to the fixed-order double sums, no sample at or beyond ns[b] is read, and the apply pass stores
+// zeros for the rows between the clip's own count and the padded one.  Kernels of their own: the uniform ones keep their names and their code ----
+__host__ __device__ inline int w2v_l0(int n) { return (n - 10) / 5 + 1; }
+__global__ __launch_bounds__(256) void w2v_conv0_stats_len_kernel(const float *__restrict__ wav, int N, const int *__restrict__ ns,
+                                                              const float *__restrict__ w, double2 *__restrict__ part,
+                                                              int C) {
+    __shared__ float sw[C0_TB * 5 + 16];
+    const int b = blockIdx.y, tb = blockIdx.x, t0 = tb * C0_TB;
+    const int n = ns[b], L0 = w2v_l0(n);
+    const int nt = min(C0_TB, L0 - t0);   // <= 0 in a block beyond the clip: every loop below is empty, the block's sums are exact zeros
+    for (int i = threadIdx.x; i < nt * 5 + 5; i += 256) {
+        const int idx = t0 * 5 + i;
+        sw[i] = idx < n ? wav[(long)b * N + idx] : 0.f;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float wk[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) wk[k] = w[c * 10 + k];
+        double s = 0.0, s2 = 0.0;
+        for (int t = 0; t < nt; ++t) {
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) v = fmaf(wk[k], sw[t * 5 + k], v);
+            s += v;
+            s2 += (double)v * v;
+        }
+        part[((long)b * gridDim.x + tb) * C + c] = double2{s, s2};
+    }
+}
+__global__ void w2v_gn_finalize_len_kernel(const double2 *__restrict__ part, int ntb, int C, const int *__restrict__ ns, float2 *__restrict__ stats,
+                                       int BC) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BC) return;
+    const int b = i / C, c = i - b * C;
+    const int L0 = w2v_l0(ns[b]);
+    double s = 0.0, s2 = 0.0;
+    for (int t = 0; t < ntb; ++t) {
+        const double2 v = part[((long)b * ntb + t) * C + c];
+        s += v.x;
+        s2 += v.y;
+    }
+    const double mean = s / L0;
+    double var = s2 / L0 - mean * mean;
+    if (var < 0) var = 0;
+    stats[i] = float2{(float)mean, (float)(1.0 / sqrt(var + 1e-5))};
+}
+__global__ __launch_bounds__(256) void w2v_conv0_apply_len_kernel(const float *__restrict__ wav, int N, int L0, const int *__restrict__ ns,
+                                                              const float *__restrict__ w, const float2 *__restrict__ stats,
+                                                              const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                              float *__restrict__ out, int C) {
+    __shared__ float sw[C0_TB * 5 + 16];
+    const int b = blockIdx.y, t0 = blockIdx.x * C0_TB;
+    const int n = ns[b];
+    const int nt = min(C0_TB, w2v_l0(n) - t0);   // the clip's own rows of this block (L0 = the padded clip's: the pitch of `out`)
+    for (int i = threadIdx.x; i < nt * 5 + 5; i += 256) {
+        const int idx = t0 * 5 + i;
+        sw[i] = idx < n ? wav[(long)b * N + idx] : 0.f;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float wk[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) wk[k] = w[c * 10 + k];
+        const float2 st = stats[b * C + c];
+        const float g = gamma[c], be = beta[c];
+        for (int t = 0; t < nt; ++t) {
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) v = fmaf(wk[k], sw[t * 5 + k], v);
+            v = (v - st.x) * st.y * g + be;
+            out[((long)b * L0 + t0 + t) * C + c] = gelu_erf(v);
+        }
+        for (int t = max(nt, 0); t < min(C0_TB, L0 - t0); ++t) out[((long)b * L0 + t0 + t) * C + c] = 0.f;
+    }
+}
+__global__ __launch_bounds__(256) void w2v_conv0_moments_len_kernel(const float *__restrict__ wav, int N, const int *__restrict__ ns, double *__restrict__ part) {
+    __shared__ float sw[C0_MB * 5 + 16];
+    __shared__ double red[3][C0_NQ];
+    const int b = blockIdx.y, t0 = blockIdx.x * C0_MB;
+    const int n = ns[b];
+    const int nt = min(C0_MB, w2v_l0(n) - t0);
+    for (int i = threadIdx.x; i < nt * 5 + 5; i += 256) {
+        const int idx = t0 * 5 + i;
+        sw[i] = idx < n ? wav[(long)b * N + idx] : 0.f;
+    }
+    __syncthreads();
+    const int q = threadIdx.x % C0_NQ, slice = threadIdx.x / C0_NQ;   // 195 threads: quantity q over every third frame
+    if (slice < 3) {
+        int k = q, k2 = -1;                 // q < 10: S[q]
+        if (q >= 10) {                      // pair number q - 10 in the order (0,0) (0,1) .. (0,9) (1,1) ..
+            int r = q - 10;
+            k = 0;
+            while (r >= 10 - k) {
+                r -= 10 - k;
+                ++k;
+            }
+            k2 = k + r;
+        }
+        // eight independent partial sums: the loop is a chain of LDS round trips + one dependent double add otherwise (3 waves per SIMD)
+        const float *pa = sw + k, *pb = k2 < 0 ? nullptr : sw + k2;
+        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        int t = slice;
+        for (; t + 21 < nt; t += 24) {
+            float va[8], vb[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                va[u] = pa[(t + 3 * u) * 5];
+                vb[u] = pb ? pb[(t + 3 * u) * 5] : 1.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc[u] += (double)va[u] * (double)vb[u];
+        }
+        for (; t < nt; t += 3) acc[0] += (double)pa[t * 5] * (pb ? (double)pb[t * 5] : 1.0);
+        red[slice][q] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    }
+    __syncthreads();
+    if (threadIdx.x < C0_NQ) part[((long)b * gridDim.x + blockIdx.x) * C0_NQ + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x];
+}
+__global__ void w2v_gn_from_moments_len_kernel(const double *__restrict__ mom, const float *__restrict__ w, int C, const int *__restrict__ ns, float2 *__restrict__ stats, int BC) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BC) return;
+    const int b = i / C, c = i - b * C;
+    const int L0 = w2v_l0(ns[b]);
+    const double *m = mom + (long)b * C0_NQ;
+    double wk[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) wk[k] = (double)w[c * 10 + k];
+    double s = 0.0, s2 = 0.0;
+    int q = 10;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+        s += wk[k] * m[k];
+#pragma unroll
+        for (int k2 = k; k2 < 10; ++k2, ++q) s2 += (k2 == k ? 1.0 : 2.0) * wk[k] * wk[k2] * m[q];
+    }
+    const double mean = s / L0;
+    double var = s2 / L0 - mean * mean;
+    if (var < 0) var = 0;
+    stats[i] = float2{(float)mean, (float)(1.0 / sqrt(var + 1e-5))};
+}
+// the length variant: wav (B, N) padded rows, ns (B,) device table of the clips' own sample counts (10 <= ns[b] <= N); out (B, L0, C) with
+// L0 = the rows of N samples; rows at or beyond a clip's own (ns[b] - 10) / 5 + 1 are written as zeros.  Same scratch as launch_w2v_conv0
+hipError_t launch_w2v_conv0_lens(const float *wav, int B, int N, const int *ns, const float *w, const float *gamma, const float *beta,
+                                 double2 *part, float2 *stats, float *out, int C, bool moments, hipStream_t s) {
+    const int L0 = w2v_l0(N), ntb = (L0 + C0_TB - 1) / C0_TB;
+    if (moments) {
+        const int nblk = (L0 + C0_MB - 1) / C0_MB;
+        double *pm = reinterpret_cast<double *>(part), *mom = pm + (size_t)B * nblk * C0_NQ;
+        hipLaunchKernelGGL(w2v_conv0_moments_len_kernel, dim3(nblk, B), dim3(256), 0, s, wav, N, ns, pm);
+        hipLaunchKernelGGL(w2v_moments_reduce_kernel, dim3((B * C0_NQ + 255) / 256), dim3(256), 0, s, pm, nblk, mom, B * C0_NQ);
+        hipLaunchKernelGGL(w2v_gn_from_moments_len_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, mom, w, C, ns, stats, B * C);
+    } else {
+        hipLaunchKernelGGL(w2v_conv0_stats_len_kernel, dim3(ntb, B), dim3(256), 0, s, wav, N, ns, w, part, C);
+        hipLaunchKernelGGL(w2v_gn_finalize_len_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, part, ntb, C, ns, stats, B * C);
+    }
+    hipLaunchKernelGGL(w2v_conv0_apply_len_kernel, dim3(ntb, B), dim3(256), 0, s, wav, N, L0, ns, w, stats, gamma, beta, out, C);
+    return hipGetLastError();
+}
+
 // ---- row-wise LayerNorm: one wavefront per row, C = 64 * CPL -----------------------------------------------------
 template <int CPL>
 __device__ inline void ln_row(float (&v)[CPL], const float *gamma, const float *beta, int lane, float eps) {
@@ -245,6 +409,49 @@ hipError_t launch_layernorm_rows(const float *x, int ldx, long M, int C, const f
     return hipGetLastError();
 }
 
+// the length variant (mixed passes): rows (b, t) of B clips padded to T rows; a row at or beyond its clip's lens[b] is written as zeros and its
+// input is not read (one wavefront per row: the branch is wave-uniform).  The arithmetic of a valid row is ln_row's, as above
+template <int CPL>
+__global__ __launch_bounds__(256) void layernorm_rows_len_kernel(const float *__restrict__ x, int ldx, long M, int T, const int *__restrict__ lens,
+                                                                 const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                                 const float *__restrict__ post_res, int ldr, int relu,
+                                                                 float *__restrict__ out, int ldo) {
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(m / T), t = (int)(m - (long)b * T);
+    if (t >= lens[b]) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) out[m * ldo + lane + 64 * i] = 0.f;
+        return;
+    }
+    float v[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) v[i] = x[m * ldx + lane + 64 * i];
+    ln_row<CPL>(v, gamma, beta, lane, 1e-5f);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        float y = v[i];
+        if (post_res) y += post_res[m * ldr + lane + 64 * i];
+        if (relu) y = y > 0.f ? y : 0.f;
+        out[m * ldo + lane + 64 * i] = y;
+    }
+}
+
+hipError_t launch_layernorm_rows_lens(const float *x, int ldx, int B, int T, const int *lens, int C, const float *gamma, const float *beta,
+                                      const float *post_res, int ldr, int relu, float *out, int ldo, hipStream_t s) {
+    const long M = (long)B * T;
+    dim3 grid((unsigned)((M + 3) / 4)), block(256);
+    switch (C) {
+        case 64: hipLaunchKernelGGL(layernorm_rows_len_kernel<1>, grid, block, 0, s, x, ldx, M, T, lens, gamma, beta, post_res, ldr, relu, out, ldo); break;
+        case 256: hipLaunchKernelGGL(layernorm_rows_len_kernel<4>, grid, block, 0, s, x, ldx, M, T, lens, gamma, beta, post_res, ldr, relu, out, ldo); break;
+        case 512: hipLaunchKernelGGL(layernorm_rows_len_kernel<8>, grid, block, 0, s, x, ldx, M, T, lens, gamma, beta, post_res, ldr, relu, out, ldo); break;
+        case 768: hipLaunchKernelGGL(layernorm_rows_len_kernel<12>, grid, block, 0, s, x, ldx, M, T, lens, gamma, beta, post_res, ldr, relu, out, ldo); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // ---- time interpolation (align_corners=False) + LayerNorm(512) --------------------------------------------------
 // Source index of frame j: scale * (j + 0.5) - 0.5 as ONE fused multiply-add, the rounding of ATen's vectorized (AVX2 / AVX512) CPU
 // kernels that made the reference's goldens (tests/test_face_oracle_golden.py::test_lerp_source_index_matches_aten); ATen's scalar
@@ -278,6 +485,45 @@ hipError_t launch_lerp_ln(const float *x, int B, int Lin, int T, const float *ga
                           hipStream_t s) {
     const long M = (long)B * T;
     hipLaunchKernelGGL(lerp_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, Lin, T, M, gamma, beta, out);
+    return hipGetLastError();
+}
+
+// the length variant (mixed passes): x (B, Lin, 512) and out (B, T, 512) are padded; clip b interpolates ITS rows w2v_feature_rows(ns[b]) to ITS
+// frames[b] frames with its own scale (the same expressions as above on the clip's own counts); frames at or beyond frames[b] are written as zeros
+__global__ __launch_bounds__(256) void lerp_ln_len_kernel(const float *__restrict__ x, int Lin, int T, long M, const int *__restrict__ ns,
+                                                          const int *__restrict__ frames, const float *__restrict__ gamma,
+                                                          const float *__restrict__ beta, float *__restrict__ out) {
+    constexpr int CPL = 8, C = 512;
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(m / T), j = (int)(m - (long)b * T);
+    const int Tb = frames[b];
+    if (j >= Tb) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) out[m * C + lane + 64 * i] = 0.f;
+        return;
+    }
+    const int Lb = w2v_feature_rows(ns[b]);
+    const float scale = (float)Lb / (float)Tb;
+    const float src = lerp_src_index(scale, j);
+    const int i0 = (int)floorf(src);
+    const int i1 = min(i0 + 1, Lb - 1);
+    const float l1 = src - (float)i0, l0 = 1.0f - l1;
+    const float *r0 = x + ((long)b * Lin + i0) * C, *r1 = x + ((long)b * Lin + i1) * C;
+    float v[CPL];
+#pragma unroll
+    // r0 l0 + r1 l1 as the uniform kernel's code has it: the product r1 l1 rounded, then ONE fused multiply-add.  Stated explicitly: left to
+    // the compiler's contraction this kernel got packed math with the two products' roles swapped in every other channel (an ulp apart)
+    for (int i = 0; i < CPL; ++i) v[i] = __builtin_fmaf(r0[lane + 64 * i], l0, r1[lane + 64 * i] * l1);
+    ln_row<CPL>(v, gamma, beta, lane, 1e-5f);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) out[m * C + lane + 64 * i] = v[i];
+}
+hipError_t launch_lerp_ln_lens(const float *x, int B, int Lin, int T, const int *ns, const int *frames, const float *gamma, const float *beta,
+                               float *out, hipStream_t s) {
+    const long M = (long)B * T;
+    hipLaunchKernelGGL(lerp_ln_len_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, Lin, T, M, ns, frames, gamma, beta, out);
     return hipGetLastError();
 }
 
@@ -318,118 +564,58 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float *__restri
     const int b = z / heads, h = z - b * heads;
     const int q0 = (grp % nq) * 64 + wave * 16;
     const long ld = 3L * HID;
-    const float *base = qkv + (long)b * T * ld + h * 64;
-    // soft-max in base 2: exp(s * scale - max) = 2^(s * scale * log2 e - max'), one v_exp_f32 per probability instead of expf's
-    // range reduction (32 of them per lane and key tile: as many VALU slots as the tile's MFMAs have issue slots)
-    const float scale2 = scale * 1.44269504088896341f;
-    // Q fragments (pre-multiplied by scale * log2 e), B operand of the first product: lane (li, lg) holds Q[q0 + li][16 qs + 4 lg + e]; rows past T are clamped (computed, never stored)
-    f32x4 qf[4];
-    {
-        const int qrow = q0 + li < T ? q0 + li : T - 1;
-#pragma unroll
-        for (int qs = 0; qs < 4; ++qs) qf[qs] = *reinterpret_cast<const f32x4 *>(base + (long)qrow * ld + 16 * qs + 4 * lg) * scale2;
-    }
-    f32x4 o[4];
-#pragma unroll
-    for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;
-    const bool live = q0 < T;   // wave-uniform: this wave has at least one real query (it still stages K / V and meets the barriers)
-    for (int k0 = 0; k0 < T; k0 += 64) {
-        __syncthreads();   // every wave is done reading the previous tile
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = (tid >> 4) + 16 * i, col = (tid & 15) * 4, key = k0 + row;
-            f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (key < T) {
-                kv = *reinterpret_cast<const f32x4 *>(base + (long)key * ld + HID + col);
-                vv = *reinterpret_cast<const f32x4 *>(base + (long)key * ld + 2 * HID + col);
-            }
-            *reinterpret_cast<f32x4 *>(&Ks[row * ATT_P + col]) = kv;
-            *reinterpret_cast<f32x4 *>(&Vs[row * ATT_P + col]) = vv;
-        }
-        __syncthreads();
-        // The products of one key tile for NKB real 16-key blocks (compile-time: the MFMA stream has no branches in it).  The key block /
-        // d block is the INNER loop of both products: four independent accumulators take turns, so an MFMA never waits for its
-        // predecessor's result (16 in a row on one accumulator issue every 40 cycles, not 32).  Key blocks wholly beyond T (the last
-        // tile of a 300-frame clip has three real blocks) are not multiplied, nor are waves whose 16 queries all lie beyond T.
-        auto tile = [&](auto NKBc, auto RAGc) {
-            constexpr int NKB = decltype(NKBc)::value;
-            constexpr bool RAGGED = decltype(RAGc)::value != 0;   // the tile reaches beyond T: its padding keys are masked
-            f32x4 sacc[NKB];
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) sacc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int qs = 0; qs < 4; ++qs) {
-                f32x4 kf[NKB];
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) kf[kb] = *reinterpret_cast<const f32x4 *>(&Ks[(kb * 16 + li) * ATT_P + 16 * qs + 4 * lg]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int kb = 0; kb < NKB; ++kb) sacc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kb][e], qf[qs][e], sacc[kb], 0, 0, 0);
-            }
-            // scale, mask the padding keys, online soft-max of query li (this lane's keys: k0 + 16 kb + 4 lg + r)
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (RAGGED && (k0 + kb * 16 + 4 * lg + r) >= T) sacc[kb][r] = -INFINITY;
-                    mx = fmaxf(mx, sacc[kb][r]);
-                }
-            mx = rows_allreduce(mx, [](float a, float b) { return fmaxf(a, b); });
-            const float m_new = fmaxf(m, mx);          // finite: every tile holds at least one real key
-            const float alpha = __builtin_amdgcn_exp2f(m - m_new);       // first tile: 2^-inf = 0
-            float rs = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pv = __builtin_amdgcn_exp2f(sacc[kb][r] - m_new);
-                    sacc[kb][r] = pv;
-                    rs += pv;
-                }
-            rs = rows_allreduce(rs, [](float a, float b) { return a + b; });
-            l = l * alpha + rs;
-            m = m_new;
-#pragma unroll
-            for (int db = 0; db < 4; ++db) o[db] *= alpha;
-            // O^T += V^T P^T; the B operand is the probability registers as they are.  The A operand V^T[d = li][key = 4 lg + e] is read
-            // from V as it was staged ([key][d], 16 consecutive d per lane group: four ds_read_b32, rows 4 lg + e of a 68-float pitch
-            // land 16 banks apart for lg and lg + 1: conflict-free) — a transposed copy of V would need 16 scattered ds_write_b32 per
-            // thread and tile, 8 lanes to a bank (measured: 63 % of the LDS cycles were conflicts)
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float va[4];
-#pragma unroll
-                    for (int db = 0; db < 4; ++db) va[db] = Vs[(kb * 16 + 4 * lg + e) * ATT_P + db * 16 + li];
-#pragma unroll
-                    for (int db = 0; db < 4; ++db) o[db] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[db], sacc[kb][e], o[db], 0, 0, 0);
-                }
-        };
-        if (live) {
-            const int nkb = (T - k0 + 15) >> 4;
-            if (k0 + 64 <= T) tile(IC4<4>{}, IC4<0>{});
-            else if (nkb >= 4) tile(IC4<4>{}, IC4<1>{});
-            else if (nkb == 3) tile(IC4<3>{}, IC4<1>{});
-            else if (nkb == 2) tile(IC4<2>{}, IC4<1>{});
-            else tile(IC4<1>{}, IC4<1>{});
-        }
-    }
-    if (q0 + li < T) {
-        const float inv = 1.0f / l;
-        float *dst = out + ((long)b * T + q0 + li) * HID + h * 64 + 4 * lg;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) *reinterpret_cast<f32x4 *>(dst + db * 16) = o[db] * inv;
-    }
+    const int Tp = T;   // clip stride in rows (attention_tile.inc)
+    const float *base = qkv + (long)b * Tp * ld + h * 64;
+#include "attention_tile.inc"
+}
+// Mixed passes: clips of different lengths padded to Tp rows; clip b has frames[b] keys and queries in rows [b Tp, b Tp + frames[b]) of qkv and
+// out.  work[workgroup id] = (clip * heads + head) << 10 | query tile, or -1 for an id without a tile (face.cpp::face_mixed_grid: the tiles of
+// one (clip, head) carry ids of equal residue mod 8, as above; query tiles wholly beyond frames[b] are not in the list).  The key-tile walk, the
+// ragged last tile and the online soft-max of a clip are those of the clip alone; K / V rows at or beyond frames[b] are never read, out rows
+// there are not written.
+__global__ __launch_bounds__(256, 2) void attention_mixed_kernel(const float *__restrict__ qkv, int Tp, int HID, int heads,
+                                                                 const int *__restrict__ work, const int *__restrict__ frames, float scale,
+                                                                 float *__restrict__ out) {
+    __shared__ float Ks[64 * ATT_P];
+    __shared__ float Vs[64 * ATT_P];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int e = work[blockIdx.x];
+    if (e < 0) return;
+    const int z = e >> 10, b = z / heads, h = z - b * heads;
+    const int T = frames[b];
+    const int q0 = (e & 1023) * 64 + wave * 16;
+    const long ld = 3L * HID;
+    const float *base = qkv + (long)b * Tp * ld + h * 64;
+#include "attention_tile.inc"
 }
 // qkv (B, T, 3 HID) rows [q | k | v], heads of 64 channels -> out (B, T, HID) = concatenated heads' softmax(q k^T * scale) v
 hipError_t launch_attention(const float *qkv, int B, int T, int HID, int heads, float scale, float *out, hipStream_t s) {
     if (HID != heads * 64 || B < 1 || T < 1 || (long)B * heads * ((T + 63) / 64) > (1l << 30)) return hipErrorInvalidValue;
     const int nq = (T + 63) / 64, nz = B * heads;
     hipLaunchKernelGGL(attention_kernel, dim3((unsigned)(((nz + 7) / 8) * 8 * nq)), dim3(256), 0, s, qkv, T, HID, heads, nz, scale, out);
+    return hipGetLastError();
+}
+// the mixed form: qkv (B, Tp, 3 HID), out (B, Tp, HID); `work` = n_work device entries as attention_mixed_kernel reads them, frames (B,) device
+hipError_t launch_attention_mixed(const float *qkv, int Tp, int HID, int heads, const int *work, int n_work, const int *frames, float scale,
+                                  float *out, hipStream_t s) {
+    if (HID != heads * 64 || Tp < 1 || Tp > 65536 || n_work < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_mixed_kernel, dim3((unsigned)n_work), dim3(256), 0, s, qkv, Tp, HID, heads, work, frames, scale, out);
+    return hipGetLastError();
+}
+
+// dst[0 .. n) = the words of `w`, carried by the launch's own arguments: a host table reaches a stream's buffer in stream order, without a
+// host buffer that has to outlive the call and without a copy that waits for the stream
+__global__ void put_words_kernel(int *__restrict__ dst, const PutWords w, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = w.v[i];
+}
+hipError_t launch_put_words(int *dst, const int *host, long n, hipStream_t s) {
+    PutWords w;
+    for (long i0 = 0; i0 < n; i0 += PutWords::N) {
+        const int c = (int)(n - i0 < PutWords::N ? n - i0 : PutWords::N);
+        std::memcpy(w.v, host + i0, (size_t)c * sizeof(int));
+        hipLaunchKernelGGL(put_words_kernel, dim3((c + 255) / 256), dim3(256), 0, s, dst + i0, w, c);
+    }
     return hipGetLastError();
 }
 
@@ -450,6 +636,29 @@ hipError_t launch_fill_id(const float *id, int nc, const float *w, const float *
     const long n = (long)B * T * nj;
     hipLaunchKernelGGL(fill_id_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, id, nc, w, bias, nj, x, ld, col0,
                        (long)B * T, T);
+    return hipGetLastError();
+}
+
+// the length variant (mixed passes): B clips padded to T rows; rows at or beyond lens[b] get zeros in the id columns
+__global__ void fill_id_len_kernel(const float *__restrict__ id, int nc, const float *__restrict__ w, const float *__restrict__ bias,
+                                   int nj, float *__restrict__ x, int ld, int col0, long rows, int T, const int *__restrict__ lens) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * nj) return;
+    const long m = i / nj;
+    const int j = (int)(i - m * nj);
+    const int b = (int)(m / T);
+    float v = 0.f;
+    if ((int)(m - (long)b * T) < lens[b]) {
+        v = bias[j];
+        for (int c = 0; c < nc; ++c) v = fmaf(w[j * nc + c], id[b * nc + c], v);
+    }
+    x[m * ld + col0 + j] = v;
+}
+hipError_t launch_fill_id_lens(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0,
+                               int B, int T, const int *lens, hipStream_t s) {
+    const long n = (long)B * T * nj;
+    hipLaunchKernelGGL(fill_id_len_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, id, nc, w, bias, nj, x, ld, col0,
+                       (long)B * T, T, lens);
     return hipGetLastError();
 }
 

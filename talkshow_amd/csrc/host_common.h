@@ -229,6 +229,9 @@ int conv_layer_params(const ConvLayer &layer, const float *x, int ldx, int B, in
 
 // accessors so that api.cpp needs no knowledge of the model structs
 int convnet_hidden(const ts_convnet *n);
+// face.cpp, host arithmetic only: the work list of a mixed pass's attention launch (one word per workgroup id; see there).  Returns the number
+// of workgroups, -1 on a bad table
+int face_mixed_grid(const int32_t *frames, int B, int heads, std::vector<int> &work);
 int vqvae_in_dim(const ts_vqvae *v);
 
 }  // namespace ts

@@ -424,4 +424,33 @@ hipError_t launch_attention(const float *qkv, int B, int T, int HID, int heads, 
 hipError_t launch_fill_id(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0,
                           int B, int T, hipStream_t s);
 
+// ---- length variants of the same kernels (mixed face passes: B clips of different lengths, padded to N samples / T frames each; `ns` and
+// `frames` / `lens` are DEVICE tables of the clips' own sample and frame counts).  A clip's valid rows are the arithmetic of the kernels above
+// on the clip alone; rows at or beyond its length are written as zeros (the operand a k = 3 / k = 128 convolution of a clip run alone reads
+// past its end) and samples / rows beyond a clip's length are never read ----
+// rows of the feature extractor's output for n samples (conv0 k10 s5, then k = 3 3 3 3 2 2 at stride 2, no padding); >= 1 from 400 samples on
+__host__ __device__ inline int w2v_feature_rows(int n) {
+    int L = (n - 10) / 5 + 1;
+    L = (L - 3) / 2 + 1, L = (L - 3) / 2 + 1, L = (L - 3) / 2 + 1, L = (L - 3) / 2 + 1;
+    L = (L - 2) / 2 + 1, L = (L - 2) / 2 + 1;
+    return L;
+}
+hipError_t launch_w2v_conv0_lens(const float *wav, int B, int N, const int *ns, const float *w, const float *gamma, const float *beta,
+                                 double2 *part, float2 *stats, float *out, int C, bool moments, hipStream_t s);
+hipError_t launch_layernorm_rows_lens(const float *x, int ldx, int B, int T, const int *lens, int C, const float *gamma, const float *beta,
+                                      const float *post_res, int ldr, int relu, float *out, int ldo, hipStream_t s);
+hipError_t launch_lerp_ln_lens(const float *x, int B, int Lin, int T, const int *ns, const int *frames, const float *gamma, const float *beta,
+                               float *out, hipStream_t s);
+// work: n_work device words, (clip * heads + head) << 10 | query tile or -1 (face.cpp::face_mixed_grid); T <= 65536
+hipError_t launch_attention_mixed(const float *qkv, int T, int HID, int heads, const int *work, int n_work, const int *frames, float scale,
+                                  float *out, hipStream_t s);
+hipError_t launch_fill_id_lens(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0,
+                               int B, int T, const int *lens, hipStream_t s);
+// dst[0 .. n) (device) = host[0 .. n), carried by kernel arguments (ceil(n / 960) tiny launches): `host` is free when the call returns
+struct PutWords {
+    static constexpr int N = 960;
+    int v[N];
+};
+hipError_t launch_put_words(int *dst, const int *host, long n, hipStream_t s);
+
 }  // namespace ts

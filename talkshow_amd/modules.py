@@ -561,6 +561,65 @@ class FaceGenerator(NativeModule):
                                                 _lib.dptr(out), _lib.dptr(hid), _lib.stream_ptr()))
         return (out, hid) if want_hidden else out
 
+    def _check_clips(self, wavs, id_vec, frames):
+        """Host-side argument checking of `run_clips` (no device call): -> (list of 1-D float32 arrays, ns, frames, id rows or None)."""
+        if isinstance(wavs, (np.ndarray, torch.Tensor)) or not hasattr(wavs, "__len__") or len(wavs) < 1:
+            raise ValueError("run_clips: wavs must be a non-empty list of 1-D sample arrays")
+        clips = []
+        for b, w in enumerate(wavs):
+            a = w.detach().cpu().numpy() if torch.is_tensor(w) else np.asarray(w)
+            if a.ndim != 1:
+                raise ValueError(f"run_clips: clip {b} has shape {tuple(a.shape)}; a 1-D array of 16 kHz samples is expected")
+            if a.shape[0] < 400:
+                raise ValueError(f"run_clips: clip {b} has {a.shape[0]} samples; the feature extractor needs at least 400")
+            clips.append(np.ascontiguousarray(a, dtype=np.float32))
+        B = len(clips)
+        ns = np.array([c.shape[0] for c in clips], dtype=np.int32)
+        if frames is None:
+            fr = (ns.astype(np.int64) * 30 // 16000).astype(np.int32)        # 30 fps out of 16 kHz in
+        else:
+            fr = np.asarray(frames)
+            if fr.ndim != 1 or fr.shape[0] != B or not np.issubdtype(fr.dtype, np.integer):
+                raise ValueError(f"run_clips: frames must be {B} integers, one per clip")
+            fr = fr.astype(np.int32)
+        if (fr < 1).any():
+            raise ValueError(f"run_clips: clip {int(np.argmax(fr < 1))} would have no output frame")
+        ids = None
+        if self.identity:
+            if id_vec is None:
+                ids = np.zeros((B, self.num_classes), dtype=np.float32)
+            else:
+                ids = (id_vec.detach().cpu().numpy() if torch.is_tensor(id_vec) else np.asarray(id_vec)).astype(np.float32)
+                if ids.ndim != 2 or ids.shape[1] != self.num_classes or ids.shape[0] not in (1, B):
+                    raise ValueError(f"run_clips: id_vec must be ({B}, {self.num_classes}) or (1, {self.num_classes}), got {tuple(ids.shape)}")
+                if ids.shape[0] == 1 and B > 1:
+                    ids = np.repeat(ids, B, axis=0)
+            ids = np.ascontiguousarray(ids)
+        return clips, ns, fr, ids
+
+    def run_clips(self, wavs, id_vec, frames=None, want_hidden=False):
+        """Clips of DIFFERENT lengths in one pass (`ts_face_generate_mixed`): wavs = list of 1-D arrays / tensors of 16 kHz samples (>= 400 each),
+        id_vec (B,num_classes), (1,num_classes) or None (all-zero rows), frames = one frame count per clip (default len * 30 // 16000)
+        -> list of (frames[b], 103 | 106) device tensors [, list of hidden states (frames[b], 768)].  A clip's rows are bit-identical whatever
+        else is in the pass.  Wrong argument shapes raise ValueError before any device call."""
+        clips, ns, fr, ids = self._check_clips(wavs, id_vec, frames)
+        dev = self._dev()
+        B, N_max, T_max = len(clips), int(ns.max()), int(fr.max())
+        padded = np.zeros((B, N_max), dtype=np.float32)
+        for b, c in enumerate(clips):
+            padded[b, :c.shape[0]] = c
+        wav = torch.from_numpy(padded).to(dev)
+        ns_dev, fr_dev = torch.from_numpy(ns).to(dev), torch.from_numpy(fr).to(dev)
+        id_dev = torch.from_numpy(ids).to(dev) if ids is not None else None
+        out = torch.empty((B, T_max, self.out_dim), dtype=torch.float32, device=dev)
+        hid = torch.empty((B, T_max, 768), dtype=torch.float32, device=dev) if want_hidden else None
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(_lib.load().ts_face_generate_mixed(self.handle(), _lib.dptr(wav), ns.ctypes.data_as(i32p), _lib.dptr(ns_dev),
+                                                      fr.ctypes.data_as(i32p), _lib.dptr(fr_dev), B, N_max, T_max, _lib.dptr(id_dev),
+                                                      _lib.dptr(out), _lib.dptr(hid), _lib.stream_ptr()))
+        outs = [out[b, :int(fr[b])] for b in range(B)]
+        return (outs, [hid[b, :int(fr[b])] for b in range(B)]) if want_hidden else outs
+
     def __call__(self, in_spec, gt_poses=None, id=None, pre_state=None, time_steps=None):
         """reference call shape (`s2g_face.py:196`): in_spec (B,1,N) -> (out (B,time_steps,103), None)."""
         wav = _dev_f32(in_spec, self._dev())
