@@ -115,6 +115,43 @@ typedef struct ts_debug_skinny_problem {
     int w_tiled, out_tiled_w, pre_tiled_w, add1_tiled_w;
 } ts_debug_skinny_problem;
 int ts_debug_skinny_run(ts_ctx *ctx, const ts_debug_skinny_problem *problems, int n, const char *knob_list, int *out5, void *stream);
+/* Test aid: ONE launch of a conv_gemm_f32 problem given as plain structs (csrc/kernels.h, ConvSeg / ConvGroup / ConvParams: the fields below
+ * mirror them one for one; every pointer is a device pointer the caller owns; what the launchers set themselves — zero, sk_ws, sk_flags,
+ * xcd_tiles, w_planes — is left out) through production's planning and launch code: plan_conv(p, tile, knob_list, the device's stream-K
+ * check) and launch_conv_plan.  tile: 0 = the production plan, else a tile id of ts_op_conv1d_timed; 22 / 23 / 24 (Split) are refused here.
+ * knob_list: "NAME=VALUE,..." as for ts_debug_conv_plan, null = the defaults.  Allocates and uploads nothing beyond what the launchers do (the
+ * stream-K band's per-stream scratch); does not synchronize `stream`.
+ * dry != 0: host only, no HIP call (ctx and the pointers may be null; the device is taken to pass the stream-K check): stops after planning
+ * and the launcher's layout checks, so the same return value and out8 say what a launch WOULD run.
+ * Returns the engine that ran (numbering of ts_debug_conv_plan) with out8 = {engine, tile rows, tile columns, waves, K chunk, tiles of
+ * the second band (the 64-row tiles of a banded plan, the tiles of the stream-K band; 0 if none), workgroups in all, masked (0 / 1: the length-masked kernels)},
+ * or -1 with ts_last_error() set: a bad argument, an unknown tile id, a layout the plan's kernel does not implement (lens on a tile without a
+ * masked kernel or with batched problems, more than 4 segments, Ktot over 60 000, a segment that is no multiple of the tile's K chunk, ...).
+ * Nothing is launched then. */
+typedef struct ts_debug_conv_seg {
+    int d, c0, len, ntap;
+} ts_debug_conv_seg;
+typedef struct ts_debug_conv_group {
+    const float *x, *w, *bias, *res;
+    float *out;
+    int out_col0, nseg;
+    ts_debug_conv_seg seg[4];
+} ts_debug_conv_group;
+typedef struct ts_debug_conv_problem {
+    int M, Lout, Lin, stride;
+    int ldx, ldo, ldr;
+    int N, Ktot, act, ngroups;
+    ts_debug_conv_group g[4];
+    int res_after_act;
+    long ldw;
+    int w_rows;
+    int zdiv;
+    long x_zs0, x_zs1, w_zs0, w_zs1, o_zs0, o_zs1, b_zs1, r_zs0, r_zs1;
+    int sk_ok;
+    const int32_t *lens;
+    int len_shr, len_shl;
+} ts_debug_conv_problem;
+int ts_debug_conv_run(ts_ctx *ctx, const ts_debug_conv_problem *problem, int tile, const char *knob_list, int dry, int *out8, void *stream);
 /* Host-only helper (no GPU needed): the stream-K plan of the ring engine for `groups` problems of M rows x N columns x K (csrc/conv_gemm_ring.hip:
  * whole 128 x 128 tiles for the row tiles that fill whole units of 256 tiles, the rows after them as one list of (tile, 32-k stage) iterations
  * cut into equal runs).  1 = out6 = {row tiles kept whole, row tiles in the band, dealt ids of the whole-tile region, band workgroups,

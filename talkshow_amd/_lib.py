@@ -40,6 +40,25 @@ class SkinnyProblem(C.Structure):
                 ("pre_tiled_w", _i), ("add1_tiled_w", _i)]
 
 
+class ConvSeg(C.Structure):
+    """ts_debug_conv_seg (include/talkshow_hip_debug.h)."""
+    _fields_ = [("d", _i), ("c0", _i), ("len", _i), ("ntap", _i)]
+
+
+class ConvGroup(C.Structure):
+    """ts_debug_conv_group (include/talkshow_hip_debug.h)."""
+    _fields_ = [("x", _vp), ("w", _vp), ("bias", _vp), ("res", _vp), ("out", _vp), ("out_col0", _i), ("nseg", _i), ("seg", ConvSeg * 4)]
+
+
+class ConvProblem(C.Structure):
+    """ts_debug_conv_problem (include/talkshow_hip_debug.h): one conv_gemm_f32 launch, the fields of csrc/kernels.h::ConvParams."""
+    _fields_ = [("M", _i), ("Lout", _i), ("Lin", _i), ("stride", _i), ("ldx", _i), ("ldo", _i), ("ldr", _i), ("N", _i), ("Ktot", _i),
+                ("act", _i), ("ngroups", _i), ("g", ConvGroup * 4), ("res_after_act", _i), ("ldw", C.c_long), ("w_rows", _i), ("zdiv", _i),
+                ("x_zs0", C.c_long), ("x_zs1", C.c_long), ("w_zs0", C.c_long), ("w_zs1", C.c_long), ("o_zs0", C.c_long),
+                ("o_zs1", C.c_long), ("b_zs1", C.c_long), ("r_zs0", C.c_long), ("r_zs1", C.c_long), ("sk_ok", _i), ("lens", _vp),
+                ("len_shr", _i), ("len_shl", _i)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "ts_ctx_create": (_i, [_i, C.POINTER(_vp)]),
@@ -101,6 +120,7 @@ SIGNATURES = {
     "ts_op_conv_taps48_timed": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(C.c_float), _vp]),
     "ts_op_conv1d_strided_timed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_float), _vp]),
     "ts_debug_pixelcnn_graphs": (_i, [_vp, _vp]),
+    "ts_debug_conv_run": (_i, [_vp, C.POINTER(ConvProblem), _i, C.c_char_p, _i, C.POINTER(_i), _vp]),
     "ts_debug_conv_sk_plan": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "ts_debug_conv_sk_run": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "ts_debug_conv_sk_supported": (_i, []),

@@ -482,6 +482,67 @@ int ts_debug_skinny_run(ts_ctx *ctx, const ts_debug_skinny_problem *pr, int n, c
     return (int)ran.kernel;
 }
 
+int ts_debug_conv_run(ts_ctx *ctx, const ts_debug_conv_problem *d, int tile, const char *knob_list, int dry, int *out8, void *stream) {
+    auto bad = [](const std::string &m) { return fail("ts_debug_conv_run: " + m) ? -1 : -1; };
+    if (!d || !out8 || (!dry && !ctx)) return bad("null argument");
+    if (tile >= 22 && tile <= 24) return bad("the Split plans are not run here (tests/test_gpu_face_ops.py::test_split_bf16_gemm)");
+    if (d->M < 1 || d->N < 1 || d->Lout < 1 || d->Lin < 1 || d->stride < 1 || d->M % d->Lout || d->ldx < 1 || d->ldo < 1 || d->Ktot < 32 || d->Ktot % 32 ||
+        d->act < 0 || d->act > 3 || d->ldw < 0 || d->w_rows < 0 || d->zdiv < 0)
+        return bad("bad geometry");
+    if (d->ngroups < 1 || (d->zdiv == 0 && d->ngroups > 4) || (d->zdiv > 0 && d->ngroups % d->zdiv)) return bad("1 to 4 groups, or a multiple of zdiv batched problems");
+    ts::ConvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.M = d->M, p.Lout = d->Lout, p.Lin = d->Lin, p.stride = d->stride;
+    p.ldx = d->ldx, p.ldo = d->ldo, p.ldr = d->ldr;
+    p.N = d->N, p.Ktot = d->Ktot, p.act = d->act, p.ngroups = d->ngroups;
+    p.res_after_act = d->res_after_act, p.ldw = d->ldw, p.w_rows = d->w_rows;
+    p.zdiv = d->zdiv;
+    p.x_zs0 = d->x_zs0, p.x_zs1 = d->x_zs1, p.w_zs0 = d->w_zs0, p.w_zs1 = d->w_zs1, p.o_zs0 = d->o_zs0, p.o_zs1 = d->o_zs1;
+    p.b_zs1 = d->b_zs1, p.r_zs0 = d->r_zs0, p.r_zs1 = d->r_zs1;
+    p.sk_ok = d->sk_ok;
+    p.lens = d->lens, p.len_shr = d->len_shr, p.len_shl = d->len_shl;
+    for (int z = 0; z < (d->zdiv > 0 ? 1 : d->ngroups); ++z) {
+        const ts_debug_conv_group &s = d->g[z];
+        ts::ConvGroup &g = p.g[z];
+        if (!dry && (!s.x || !s.w || !s.out)) return bad("null operand");
+        if (s.nseg < 1 || s.out_col0 < 0 || (s.res && d->ldr < 1)) return bad("bad group");
+        g.x = s.x, g.w = s.w, g.bias = s.bias, g.res = s.res, g.out = s.out;
+        g.out_col0 = s.out_col0, g.nseg = s.nseg;
+        long k = 0;
+        for (int i = 0; i < s.nseg && i < 4; ++i) {
+            if (s.seg[i].len < 1 || s.seg[i].c0 < 0 || s.seg[i].ntap < 0) return bad("bad segment");
+            g.seg[i] = ts::ConvSeg{s.seg[i].d, s.seg[i].c0, s.seg[i].len, s.seg[i].ntap};
+            k += (long)s.seg[i].len * (s.seg[i].ntap > 1 ? s.seg[i].ntap : 1);
+        }
+        if (s.nseg <= 4 && k != d->Ktot) return bad("the segments do not add up to Ktot");
+    }
+    const ts::ConvPlan pl = ts::plan_conv(p, tile, ts::knobs_from_list(knob_list), dry ? true : ts::conv_sk_supported());
+    if (pl.engine == ts::ConvEngine::Invalid) return bad("unknown tile id");
+    if (const char *why = ts::conv_plan_refusal(p, pl)) return bad(why);
+    if (!dry) {
+        const hipError_t e = ts::launch_conv_plan(p, pl, (hipStream_t)stream);
+        if (e != hipSuccess) return bad(hipGetErrorString(e));
+    }
+    const int nt128 = (p.N + 127) / 128;
+    int second = 0, wgs = 0;
+    switch (pl.engine) {
+        case ts::ConvEngine::Reg: wgs = ((p.M + pl.bm - 1) / pl.bm) * ((p.N + pl.bn - 1) / pl.bn) * p.ngroups; break;
+        case ts::ConvEngine::RegBanded: second = pl.bands.total - pl.bands.first_small, wgs = pl.bands.total; break;
+        case ts::ConvEngine::Ring: wgs = ((p.M + pl.bm - 1) / pl.bm) * nt128 * p.ngroups; break;
+        case ts::ConvEngine::RingDealt: wgs = 8 * ((((p.M + pl.bm - 1) / pl.bm) * nt128 + 7) / 8) * p.ngroups; break;
+        case ts::ConvEngine::RingBanded:
+            second = pl.bands.mt_small * nt128 * p.ngroups;
+            wgs = (8 * ((pl.bands.mt_big * nt128 + 7) / 8) + 8 * ((pl.bands.mt_small * nt128 + 7) / 8)) * p.ngroups;
+            break;
+        case ts::ConvEngine::RingSK: second = pl.sk.mt_sk * nt128 * p.ngroups, wgs = (pl.sk.dp8 + pl.sk.wsk) * p.ngroups; break;
+        case ts::ConvEngine::Taps48: wgs = 8 * (int)((((long)(p.M + 127) / 128) * p.ngroups + 7) / 8); break;
+        default: break;
+    }
+    const int o[8] = {(int)pl.engine, pl.bm, pl.bn, pl.wm > 0 ? (pl.bm / pl.wm) * (pl.bn / pl.wn) : 0, pl.bk, second, wgs, p.lens ? 1 : 0};
+    std::memcpy(out8, o, sizeof(o));
+    return (int)pl.engine;
+}
+
 int ts_debug_conv_sk_plan(int M, int N, int K, int groups, int *out6) {
     if (M < 1 || N < 1 || K < 32 || K % 32 || groups < 1 || groups > 4 || !out6) return -1;
     ts::ConvParams p;

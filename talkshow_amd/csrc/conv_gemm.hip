@@ -450,22 +450,51 @@ static const RegInstance reg_instances[] = {
     {96, 128, 96, 32, 32, launch_reg<96, 128, 96, 32, 32>, nullptr},
 };
 
+// The layouts a plan's kernel does not implement, in one place: launch_conv_plan refuses them, and the host-side tests ask without a device.
+// (The engines' own launchers keep their checks: they are also called with plans made elsewhere.)
+const char *conv_plan_refusal(const ConvParams &p, const ConvPlan &pl) {
+    if (p.Ktot > 60000) return "Ktot over 60 000: a parked operand pointer would walk off the zero buffer";
+    const int ng = p.zdiv > 0 ? 1 : (p.ngroups < 4 ? p.ngroups : 4);
+    for (int z = 0; z < ng; ++z)
+        if (p.g[z].nseg > 4) return "more than 4 segments";
+    // length-masked rows: whole-tile plans of the two engines only, on per-clip geometry (no batched problems)
+    if (p.lens && (p.zdiv > 0 || p.len_shr < 0 || p.len_shl < 0)) return "length-masked rows with batched problems or a negative shift";
+    if (p.lens && (pl.engine == ConvEngine::RingSK || pl.engine == ConvEngine::Taps48 || pl.engine == ConvEngine::Split))
+        return "this engine has no length-masked kernel";
+    switch (pl.engine) {
+        case ConvEngine::Reg:
+            for (const RegInstance &r : reg_instances)
+                if (r.bm == pl.bm && r.bn == pl.bn && r.wm == pl.wm && r.wn == pl.wn && r.bk == pl.bk) {
+                    if (p.lens && !r.launch_masked) return "this tile has no length-masked kernel";
+                    for (int z = 0; z < ng; ++z)   // a chunk of bk floats never straddles two taps / segments
+                        for (int i = 0; i < p.g[z].nseg; ++i)
+                            if (p.g[z].seg[i].len % r.bk) return "a segment length that is no multiple of the tile's K chunk";
+                    return nullptr;
+                }
+            return "no such tile";
+        case ConvEngine::RegBanded: return nullptr;   // (plan_conv gives bands to per-group geometry only)
+        case ConvEngine::Ring:
+        case ConvEngine::RingDealt: return !conv_gemm_ring_takes(p) || pl.bn != 128 ? "the ring engine does not take this layer" : nullptr;
+        case ConvEngine::RingBanded:
+            return !conv_gemm_ring_takes(p) || p.zdiv > 0 || pl.bands.mt_big < 1 || pl.bands.mt_small < 1 ? "no ring band plan for this layer" : nullptr;
+        case ConvEngine::RingSK: return !conv_sk_valid(p, pl.sk) ? "no stream-K plan for this layer" : nullptr;
+        case ConvEngine::Taps48: return !conv_taps48_takes(p) ? "conv_taps48 does not take this layer" : nullptr;
+        case ConvEngine::Split: return nullptr;   // conv_gemm_split.hip checks its own layouts
+        default: return "unknown tile id";
+    }
+}
+
 hipError_t launch_conv_plan(const ConvParams &p_in, const ConvPlan &pl, hipStream_t stream) {
     ConvParams p = p_in;
     if (!p.zero) {   // zero buffer (ts::skinny_init, called by ts_ctx_create): 64 Ki floats; parked pointers walk at most Ktot floats of it
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess) p.zero = skinny_zero_buffer(dev);
     }
-    if (!p.zero || p.g[0].nseg > 4 || p.Ktot > 60000) return hipErrorInvalidValue;
-    // length-masked rows: whole-tile plans of the two engines only, on per-clip geometry (no batched problems)
-    if (p.lens && (p.zdiv > 0 || p.len_shr < 0 || p.len_shl < 0 || pl.engine == ConvEngine::RingSK || pl.engine == ConvEngine::Taps48 ||
-                   pl.engine == ConvEngine::Split))
-        return hipErrorInvalidValue;
+    if (!p.zero || conv_plan_refusal(p, pl)) return hipErrorInvalidValue;
     switch (pl.engine) {
         case ConvEngine::Reg:
             for (const RegInstance &r : reg_instances)
                 if (r.bm == pl.bm && r.bn == pl.bn && r.wm == pl.wm && r.wn == pl.wn && r.bk == pl.bk) {
-                    if (p.lens && !r.launch_masked) return hipErrorInvalidValue;
                     (p.lens ? r.launch_masked : r.launch)(p, stream);
                     return hipGetLastError();
                 }

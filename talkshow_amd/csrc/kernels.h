@@ -132,6 +132,8 @@ struct ConvPlan {
 // Host only, no HIP call: the plan for a layer.  tile: 0 = the production choice under `k`; otherwise a tile id of ts_op_conv1d_timed
 // (include/talkshow_hip_debug.h).  sk_hw: the device passed the stream-K band's hardware check (conv_sk_supported).
 ConvPlan plan_conv(const ConvParams &p, int tile, const Knobs &k, bool sk_hw);
+// Host only, no HIP call: why launch_conv_plan refuses (p, plan) — a layout the plan's kernel does not implement — or null if it launches
+const char *conv_plan_refusal(const ConvParams &p, const ConvPlan &plan);
 hipError_t launch_conv_plan(const ConvParams &p, const ConvPlan &plan, hipStream_t stream);
 hipError_t launch_conv_gemm(const ConvParams &p, int tile, hipStream_t stream);   // = launch_conv_plan(p, plan_conv(p, tile, knobs(), ...))
 
