@@ -310,6 +310,14 @@ int ts_op_sample_philox(ts_ctx *ctx, const float *logits_dev, int B, int V, uint
 int ts_assemble_full(ts_ctx *ctx, const float *body_dev, int Tb, const float *face_dev, int Tf, int B,
                      const float *lower_pose33_host, float *out_dev, void *stream);
 
+/* The same for clips of DIFFERENT lengths (after ts_body_pixel_infer_mixed and ts_face_generate_mixed): body_dev (B,Tb_max,129) with
+ * tb[b] frames of clip b, face_dev (B,Tf_max,103) with tf[b] -> out_dev (B,Tf_max,265).  tb_dev / tf_dev (B,) int32 DEVICE tables,
+ * 1 <= tb[b] <= Tb_max, 1 <= tf[b] <= Tf_max.  Row t < tf[b] is ts_assemble_full's row for the clip alone (Tb = tb[b], Tf = tf[b]): the body
+ * frame is min(t, tb[b] - 1) — the last frame repeated, or trimmed.  Rows t >= tf[b] are written as 0.  Pure copies: bit-exact.  Every element
+ * of out_dev is written, nothing else is touched; no synchronisation. */
+int ts_assemble_full_mixed(ts_ctx *ctx, const float *body_dev, const int32_t *tb_dev, const float *face_dev, const int32_t *tf_dev, int B,
+                           int Tb_max, int Tf_max, const float *lower_pose33_host, float *out_dev, void *stream);
+
 /* ---- instrumentation ---------------------------------------------------------------------------------------- */
 /* Per-kernel-family device time of the calls made on this context since the last reset, measured with HIP
  * events on the launch stream when enabled (adds synchronisation: benchmarking / profiling only).
@@ -332,6 +340,31 @@ int ts_mfcc_resample(ts_mfcc *m, const float *wav_dev, int B, long n_samples, fl
 long ts_resample_kaiser_len(long n_samples, int sr_in, int sr_out);
 int ts_resample_kaiser(ts_ctx *ctx, const float *wav_dev, int B, long n_samples, int sr_in, int sr_out, float *out_dev,
                        void *stream);
+
+/* ---- mixed front-end passes: recordings of DIFFERENT lengths in one call (no counterpart in the reference, which reads one file at a time) ----
+ * B recordings, recording b with ns[b] samples at the handle's input rate, stored padded to N_max samples.  The arithmetic of the uniform entries
+ * on every recording: a recording's rows / samples are BIT-IDENTICAL whatever else is in the pass, and bit-identical to the uniform entry on the
+ * recording alone (B = 1, N = ns[b]).  The kernels that look across a recording's samples or rows (polyphase and Kaiser resamplers, the STFT's
+ * reflect padding, the per-clip top_db clamp) run as length variants that take from ns[b] what the uniform kernels take from N; the mel and DCT
+ * GEMMs run over (B, T_max) rows with the length-masked epilogue and never take a stream-K band.  Recordings need no particular order.
+ *   ns_host / ns_dev (B,) int32: the same table in host memory (checked and planned from without synchronising; not read after the call
+ *     returns) and in device memory.  1 <= ns[b] <= N_max; anything else, a NULL table or B < 1 is an error and nothing is written.
+ *   wav_dev (B,N_max): samples at or beyond ns[b] are never read (they may hold anything, NaNs included).
+ * ONE HANDLE = ONE (sr_in, sr_out, fps): a host whose recordings come at several source rates groups them by rate, one handle and one
+ * call per group.  The calls allocate nothing beyond the growth of the stream's work buffers and never synchronise.
+ * ts_mfcc_forward_mixed: feat_dev (B,T_max,64), T_max = ts_mfcc_num_frames(m, N_max).  Rows t < T_b = ts_mfcc_num_frames(m, ns[b]) are the
+ *   recording's MFCC rows, rows t >= T_b are written as 0; every element of feat_dev is written, nothing else is touched.  A recording whose
+ *   resampled length is <= half an FFT window is an error (the rule of ts_mfcc_forward) and nothing is written. */
+int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max,
+                          float *feat_dev, void *stream);
+/* stage 1 alone: out_dev (B, ts_mfcc_resampled_len(m, N_max)); samples at or beyond ts_mfcc_resampled_len(m, ns[b]) are written as 0. */
+int ts_mfcc_resample_mixed(ts_mfcc *m, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max,
+                           float *out_dev, void *stream);
+/* ts_resample_kaiser on recordings of different lengths: out_dev (B, ts_resample_kaiser_len(N_max, sr_in, sr_out)); row b holds the
+ * ts_resample_kaiser_len(ns[b], ...) samples of the recording alone, zeros beyond.  A recording too short to give one output sample is an
+ * error. */
+int ts_resample_kaiser_mixed(ts_ctx *ctx, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max,
+                             int sr_in, int sr_out, float *out_dev, void *stream);
 
 /* ---- streaming generation -----------------------------------------------------------------------
  * Replaces the pre_latents / pre_audio prefix of GatedPixelCNN.generate (gated_pixelcnn_v2.py:158-165) and its caller

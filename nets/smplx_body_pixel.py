@@ -249,6 +249,59 @@ class TrainWrapper(TrainWrapperBaseClass):
             return codes, poses
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
+    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None):
+        """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
+        their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
+        and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
+        pass's host table is `mixed_tables` arithmetic (lens_dev: its device copy, (B,) int32, if the caller has uploaded one).  No synchronisation."""
+        from talkshow_amd.frontend import device_mfcc, mixed_tables
+        from talkshow_amd.modules import upload
+        dev = self.generator._dev()
+        rows = mixed_tables(ns_host, sr, 22000, fps)["mfcc_rows"]
+        if int(rows.min()) < 4:
+            raise ValueError(f"clip of {int(ns_host[int(np.argmin(rows))])} samples gives {int(rows.min())} MFCC rows; one code row needs 4")
+        lens_host = np.ascontiguousarray(rows, dtype=np.int32)
+        if lens_dev is None:
+            lens_dev = upload(lens_host, dev)
+        mf = device_mfcc(sr, 22000, fps).forward_padded(wav, ns_host, ns_dev)
+        B, T_max = mf.shape[0], mf.shape[1]
+        H_max = T_max // 4
+        codes = torch.empty((B, H_max, 2), dtype=torch.int64, device=dev)
+        poses = torch.empty((B, 4 * H_max, self.each_dim[1] + self.each_dim[2]), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().ts_body_pixel_infer_mixed(
+            self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
+            _lib.dptr(mf), _lib.dptr(ids), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
+            mode, None, int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses), _lib.stream_ptr()))
+        return codes, poses, lens_host
+
+    def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30):
+        """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
+        (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
+        device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
+        `generate_batch(MFCC(sr)(wav_b), id_b)` on the clip alone; clip b draws from Philox subsequence `clip_index0 + b`, b its position in
+        the SUBMITTED list (or `clip_indices[b]`)."""
+        from talkshow_amd.frontend import check_recordings
+        from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
+        ns = check_recordings(wavs, "generate_clips_from_wav")
+        B = len(ns)
+        n_ids = int(ids.numel()) if torch.is_tensor(ids) else int(np.asarray(ids).size)
+        if n_ids not in (1, B):
+            raise ValueError(f"ids must hold 1 or B={B} speaker indices, got {n_ids}")
+        if clip_indices is not None and len(clip_indices) != B:
+            raise ValueError(f"generate_clips_from_wav: clip_indices must name {B} clips, got {len(clip_indices)}")
+        dev = self.generator._dev()
+        order, inverse = mixed_pass_order(ns)
+        ids = ids_in_row_order(ids, self.num_classes, order, dev)
+        if clip_indices is None:
+            clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
+        else:
+            clip_index = upload(np.asarray([int(clip_indices[i]) for i in order], np.int64), dev)
+        if seed is None:
+            seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
+        wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
+        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps)
+        return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
+
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,
                        continuity=False, id=None, fps=15, sr=22000, B=1, am=None, am_sr=None, frame=0, **kwargs):
         '''

@@ -73,6 +73,7 @@ SIGNATURES = {
     "ts_debug_split_tile": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
     "ts_debug_tile_weights": (_i, [_vp, _i, _i, C.c_long, _i, _i, _vp]),
     "ts_assemble_full": (_i, [_vp, _vp, _i, _vp, _i, _i, _fp, _vp, _vp]),
+    "ts_assemble_full_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _fp, _vp, _vp]),
     "ts_stream_destroy": (_i, [_vp, _vp]),
     "ts_audioenc_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_convnet_destroy": (None, [_vp]),
@@ -107,6 +108,9 @@ SIGNATURES = {
     "ts_mfcc_resample": (_i, [_vp, _vp, _i, C.c_long, _vp, _vp]),
     "ts_resample_kaiser_len": (C.c_long, [C.c_long, _i, _i]),
     "ts_resample_kaiser": (_i, [_vp, _vp, _i, C.c_long, _i, _i, _vp, _vp]),
+    "ts_mfcc_forward_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
+    "ts_mfcc_resample_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
+    "ts_resample_kaiser_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _i, _i, _vp, _vp]),
     "ts_pixelcnn_graph_stats": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "ts_body_pixel_infer": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp]),
     "ts_body_pixel_infer_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp]),

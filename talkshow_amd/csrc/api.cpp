@@ -101,6 +101,17 @@ int ts_assemble_full(ts_ctx *ctx, const float *body, int Tb, const float *face, 
     return 0;
 }
 
+// The same for clips of different lengths (talkshow_hip.h): the tables are read on the device only
+int ts_assemble_full_mixed(ts_ctx *ctx, const float *body, const int32_t *tb_dev, const float *face, const int32_t *tf_dev, int B, int Tb_max,
+                           int Tf_max, const float *lower_pose33, float *out, void *stream) {
+    if (!ctx || !body || !face || !lower_pose33 || !out) return fail("ts_assemble_full_mixed: null argument");
+    if (!tb_dev || !tf_dev) return fail("ts_assemble_full_mixed: null length table");
+    if (B < 1 || Tb_max < 1 || Tf_max < 1) return fail("ts_assemble_full_mixed: empty input");
+    MiscScope ms(ctx, (hipStream_t)stream);
+    TS_HIP(launch_assemble_full_lens(body, tb_dev, face, tf_dev, lower_pose33, B, Tb_max, Tf_max, out, (hipStream_t)stream));
+    return 0;
+}
+
 // tuning aid (TS_SKINNY_TRACE=1): in-kernel wall-clock stamps of the PixelCNN chain kernel, 6 u64 per record
 int ts_debug_skinny_trace(unsigned long long *out, int max_records) {
     if (!out) return -1;

@@ -286,6 +286,10 @@ hipError_t launch_pad_rows(const float *src, int lds, int c, float *dst, int ldd
 // (B,Tb,129) body/hand poses + (B,Tf,103) jaw/expression -> (B,Tf,265) full SMPL-X parameter rows (demo.py:207-229, part2full)
 hipError_t launch_assemble_full(const float *body, const float *face, const float *lower_pose33, int B, int Tb, int Tf,
                                 float *out, hipStream_t stream);
+// the same for a padded batch (mixed passes): tb / tf = device tables of the clips' own body and face frame counts; rows t < tf[b] as above on
+// the clip alone (body frame min(t, tb[b] - 1)), rows t >= tf[b] written as 0
+hipError_t launch_assemble_full_lens(const float *body, const int *tb, const float *face, const int *tf, const float *lower_pose33, int B,
+                                     int Tb, int Tf, float *out, hipStream_t stream);
 // int64 -> int32 (labels, teacher-forced codes)
 hipError_t launch_i64_to_i32(const int64_t *src, int *dst, long n, hipStream_t stream);
 // test aid: out[i] = gate_act(v[i], p[i])

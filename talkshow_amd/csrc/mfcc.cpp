@@ -21,6 +21,16 @@ hipError_t launch_stft_power(const float *x, int B, int N, int T, int hop, const
 hipError_t launch_resample_kaiser(const float *x, int B, int N, const float *win, const float *delta, int nwin, int num_table,
                                   double ratio, float *out, int Nout, int ldo, hipStream_t s);
 hipError_t launch_db_topdb(float *mel, int B, long per_clip, float top_db, hipStream_t s);
+// length variants (mixed passes; mfcc.hip): ns = device table of the recordings' own sample counts at the input rate
+hipError_t launch_resample_polyphase_lens(const float *x, int B, int N, const int *ns, const float *kern, int norig, int nnew, int width,
+                                          int kw, float *out, int Nout, hipStream_t s);
+hipError_t launch_copy_samples_lens(const float *x, int B, int N, const int *ns, float *out, hipStream_t s);
+hipError_t launch_resample_kaiser_lens(const float *x, int B, int N, const int *ns, const float *win, const float *delta, int nwin,
+                                       int num_table, double ratio, float *out, int ldo, hipStream_t s);
+hipError_t launch_mfcc_frames(const int *ns, int B, int N, int norig, int nnew, int hop, int *frames, hipStream_t s);
+hipError_t launch_stft_power_lens(const float *x, int B, int N, int T, const int *ns, int norig, int nnew, int hop, const float *win,
+                                  const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
+hipError_t launch_db_topdb_lens(float *mel, int B, int T, int width, const int *frames, float top_db, hipStream_t s);
 }  // namespace ts
 
 struct ts_mfcc {
@@ -31,6 +41,7 @@ struct ts_mfcc {
     ConvLayer mel, dct;
     struct Work {
         DevBuf x22, power, melb;
+        DevBuf frames;   // mixed passes: the recordings' own frame counts (the row table of the masked GEMMs), written on the stream by every call
     };
     StreamWorks<Work> works;
     Work &work(hipStream_t s) { return works.get(s); }
@@ -260,6 +271,107 @@ int ts_mfcc_forward(ts_mfcc *m, const float *wav, int B, long N, float *feat, vo
         TS_HIP(launch_db_topdb(w.melb.f(), B, (long)T * m->nmels, 80.0f, s));
     }
     conv_layer_params(m->dct, w.melb.f(), m->nmels, 1, (int)M, nullptr, 0, feat, m->nmfcc, 0, m->nmfcc, &p);
+    TS_TRY(run_conv(ctx, p, 0, s));
+    return 0;
+}
+
+// ---- mixed passes: recordings of different lengths in one call (talkshow_hip.h) ---------------------------------------------------------
+namespace {
+// the host table of a mixed entry, checked before anything is launched: 1 <= ns[b] <= N_max
+int check_counts(const char *who, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max) {
+    if (!ns_host || !ns_dev) return fail(std::string(who) + ": null length table");
+    if (B < 1 || N_max < 1 || N_max > 0x7fffffffl) return fail(std::string(who) + ": bad shape");
+    for (int b = 0; b < B; ++b) {
+        if (ns_host[b] < 1) return fail(std::string(who) + ": clip " + std::to_string(b) + " has no samples");
+        if (ns_host[b] > N_max) return fail(std::string(who) + ": clip " + std::to_string(b) + " is longer than N_max");
+    }
+    return 0;
+}
+}  // namespace
+
+int ts_mfcc_resample_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, float *out,
+                           void *stream) {
+    if (!m || !wav || !out) return fail("ts_mfcc_resample_mixed: null argument");
+    TS_TRY(check_counts("ts_mfcc_resample_mixed", ns_host, ns_dev, B, N_max));
+    if (m->resampled_len(N_max) > 0x7fffffffl) return fail("ts_mfcc_resample_mixed: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    MiscScope ms(m->ctx, s);
+    if (m->sr_in == m->sr_out) {
+        TS_HIP(launch_copy_samples_lens(wav, B, (int)N_max, ns_dev, out, s));
+        return 0;
+    }
+    TS_HIP(launch_resample_polyphase_lens(wav, B, (int)N_max, ns_dev, m->rs_kern.f(), m->norig, m->nnew, m->width, m->kw, out,
+                                          (int)m->resampled_len(N_max), s));
+    return 0;
+}
+
+int ts_resample_kaiser_mixed(ts_ctx *ctx, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, int sr_in,
+                             int sr_out, float *out, void *stream) {
+    if (!ctx || !wav || !out) return fail("ts_resample_kaiser_mixed: null argument");
+    if (sr_in < 1 || sr_out < 1) return fail("ts_resample_kaiser_mixed: bad shape");
+    TS_TRY(check_counts("ts_resample_kaiser_mixed", ns_host, ns_dev, B, N_max));
+    const long Nfix = ts_resample_kaiser_len(N_max, sr_in, sr_out);
+    if (Nfix > 0x7fffffffl) return fail("ts_resample_kaiser_mixed: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    const double ratio = (double)sr_out / (double)sr_in;
+    if (sr_in != sr_out)
+        for (int b = 0; b < B; ++b)
+            if ((long)((double)ns_host[b] * ratio) < 1)
+                return fail("ts_resample_kaiser_mixed: clip " + std::to_string(b) + " is too short for this rate change");
+    MiscScope ms(ctx, s);
+    if (sr_in == sr_out) {
+        TS_HIP(launch_copy_samples_lens(wav, B, (int)N_max, ns_dev, out, s));
+        return 0;
+    }
+    const KaiserTable *kt = nullptr;
+    TS_TRY(kaiser_table(ctx->device, &kt));
+    TS_HIP(launch_resample_kaiser_lens(wav, B, (int)N_max, ns_dev, kt->win.f(), kt->delta.f(), kt->nwin, kt->num_table, ratio, out, (int)Nfix, s));
+    return 0;
+}
+
+// The launch plan of ts_mfcc_forward on the padded block: the length variants of the three kernels that look across a recording's samples or
+// rows, and the two GEMMs in the (B, T_max) row form with the length-masked epilogue (whole-tile plans only: sk_ok stays 0, so a row's bits do
+// not depend on the rows it shares a launch with)
+int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, float *feat,
+                          void *stream) {
+    if (!m || !wav || !feat) return fail("ts_mfcc_forward_mixed: null argument");
+    TS_TRY(check_counts("ts_mfcc_forward_mixed", ns_host, ns_dev, B, N_max));
+    hipStream_t s = (hipStream_t)stream;
+    ts_ctx *ctx = m->ctx;
+    const long N22 = m->resampled_len(N_max);
+    const long T = N22 / m->hop + 1, M = (long)B * T;
+    if (N22 > 0x7fffffffl || M > 0x7fffffffl) return fail("ts_mfcc_forward_mixed: bad shape");
+    for (int b = 0; b < B; ++b)
+        if (m->resampled_len(ns_host[b]) <= m->nfft / 2)
+            return fail("ts_mfcc_forward_mixed: clip " + std::to_string(b) + " is shorter than half an FFT window (reflect padding undefined)");
+    ts_mfcc::Work &w = m->work(s);
+    const size_t F = sizeof(float);
+    const float *x22 = wav;
+    if (m->sr_in != m->sr_out) TS_TRY(w.x22.ensure((size_t)B * N22 * F));
+    TS_TRY(w.power.ensure((size_t)M * m->nbins_pad * F));
+    TS_TRY(w.melb.ensure((size_t)M * m->nmels * F));
+    TS_TRY(w.frames.ensure((size_t)B * sizeof(int)));
+    {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_mfcc_frames(ns_dev, B, (int)N_max, m->norig, m->nnew, m->hop, w.frames.i(), s));
+        if (m->sr_in != m->sr_out) {
+            TS_HIP(launch_resample_polyphase_lens(wav, B, (int)N_max, ns_dev, m->rs_kern.f(), m->norig, m->nnew, m->width, m->kw, w.x22.f(),
+                                                  (int)N22, s));
+            x22 = w.x22.f();
+        }
+        TS_HIP(launch_stft_power_lens(x22, B, (int)N22, (int)T, ns_dev, m->norig, m->nnew, m->hop, m->window.f(), m->tw1024.f(),
+                                      m->tw2048.f(), w.power.f(), m->nbins_pad, s));
+    }
+    ConvParams p;
+    conv_layer_params(m->mel, w.power.f(), m->nbins_pad, B, (int)T, nullptr, 0, w.melb.f(), m->nmels, 0, m->nmels, &p);
+    p.lens = w.frames.i();
+    TS_TRY(run_conv(ctx, p, 0, s));
+    {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_db_topdb_lens(w.melb.f(), B, (int)T, m->nmels, w.frames.i(), 80.0f, s));
+    }
+    conv_layer_params(m->dct, w.melb.f(), m->nmels, B, (int)T, nullptr, 0, feat, m->nmfcc, 0, m->nmfcc, &p);
+    p.lens = w.frames.i();
     TS_TRY(run_conv(ctx, p, 0, s));
     return 0;
 }

@@ -211,4 +211,255 @@ hipError_t launch_db_topdb(float *mel, int B, long per_clip, float top_db, hipSt
     return hipGetLastError();
 }
 
+// ---- length variants (mixed front-end passes: B recordings of different lengths, padded to N samples each; `ns` is the DEVICE table of the
+// recordings' own sample counts at the input rate).  Kernels of their own: the ones above keep their code.  Each takes from ns[b] what the
+// uniform kernel takes from N, Nout and T — the resampled length ceil(ns[b] nnew / norig), the frame count of that length — so a valid element
+// is the arithmetic of the uniform kernel on the recording alone, term for term; everything beyond a recording's own length is written as 0,
+// and samples at or beyond ns[b] are never read. ----
+// (a count outside [0, N] is an error of the caller that the entries refuse from the host table; clamped, a device table that disagrees with
+// it still cannot take a kernel outside its buffers)
+__device__ __forceinline__ int clamp_count(int n, int N) { return n < 0 ? 0 : (n > N ? N : n); }
+__device__ __forceinline__ int resampled_len_of(int n, int norig, int nnew) { return (int)(((long)nnew * n + norig - 1) / norig); }
+
+__global__ void resample_polyphase_len_kernel(const float *__restrict__ x, int N, const int *__restrict__ ns, const float *__restrict__ kern,
+                                              int norig, int nnew, int width, int kw, float *__restrict__ out, int Nout) {
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= Nout) return;
+    const int Nb = clamp_count(ns[b], N);
+    if (j >= resampled_len_of(Nb, norig, nnew)) {
+        out[(long)b * Nout + j] = 0.f;
+        return;
+    }
+    const int wdw = j / nnew, ph = j - wdw * nnew;
+    const float *kr = kern + ph * kw;
+    const float *xb = x + (long)b * N;
+    const int base = wdw * norig - width;
+    float acc = 0.f;
+    for (int k = 0; k < kw; ++k) {
+        const int i = base + k;
+        if (i >= 0 && i < Nb) acc = fmaf(kr[k], xb[i], acc);
+    }
+    out[(long)b * Nout + j] = acc;
+}
+__global__ __launch_bounds__(256) void resample_polyphase_lds_len_kernel(const float *__restrict__ x, int N, const int *__restrict__ ns,
+                                                                         const float *__restrict__ kern, int norig, int nnew, int width,
+                                                                         int kw, float *__restrict__ out, int Nout, int nwin) {
+    extern __shared__ float sm[];
+    float *sk = sm, *sw = sm + nnew * kw;
+    const int b = blockIdx.y, j0 = blockIdx.x * 256;
+    const int Nb = clamp_count(ns[b], N), Nout_b = resampled_len_of(Nb, norig, nnew);
+    const int j = j0 + threadIdx.x;
+    if (j0 >= Nout_b) {                                       // a block wholly beyond the recording: its zeros, nothing staged
+        if (j < Nout) out[(long)b * Nout + j] = 0.f;
+        return;
+    }
+    const float *xb = x + (long)b * N;
+    const int base = (j0 / nnew) * norig - width;
+    for (int i = threadIdx.x; i < nnew * kw; i += 256) sk[i] = kern[i];
+    for (int i = threadIdx.x; i < nwin; i += 256) {
+        const int g = base + i;
+        sw[i] = (g >= 0 && g < Nb) ? xb[g] : 0.f;
+    }
+    __syncthreads();
+    if (j >= Nout) return;
+    if (j >= Nout_b) {
+        out[(long)b * Nout + j] = 0.f;
+        return;
+    }
+    const int wdw = j / nnew, ph = j - wdw * nnew;
+    const float *kr = sk + ph * kw, *xw = sw + (wdw * norig - width - base);
+    float acc = 0.f;
+    for (int k = 0; k < kw; ++k) acc = fmaf(kr[k], xw[k], acc);
+    out[(long)b * Nout + j] = acc;
+}
+// rows of N samples in, rows of Nout = ceil(N nnew / norig) samples out
+hipError_t launch_resample_polyphase_lens(const float *x, int B, int N, const int *ns, const float *kern, int norig, int nnew, int width,
+                                          int kw, float *out, int Nout, hipStream_t s) {
+    const int nwin = (255 / nnew + 1) * norig + kw;
+    const size_t lds = ((size_t)nnew * kw + nwin) * sizeof(float);
+    if (lds <= 48 * 1024) {   // the same choice as launch_resample_polyphase: by the rate ratio alone
+        hipLaunchKernelGGL(resample_polyphase_lds_len_kernel, dim3((Nout + 255) / 256, B), dim3(256), lds, s, x, N, ns, kern, norig, nnew,
+                           width, kw, out, Nout, nwin);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(resample_polyphase_len_kernel, dim3((Nout + 255) / 256, B), dim3(256), 0, s, x, N, ns, kern, norig, nnew, width,
+                       kw, out, Nout);
+    return hipGetLastError();
+}
+
+// out[b][j] = x[b][j] for j < ns[b], 0 up to the row width (a mixed pass at equal rates: the copy of the uniform entries with its padding)
+__global__ void copy_samples_len_kernel(const float *__restrict__ x, int N, const int *__restrict__ ns, float *__restrict__ out) {
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    out[(long)b * N + j] = j < clamp_count(ns[b], N) ? x[(long)b * N + j] : 0.f;
+}
+hipError_t launch_copy_samples_lens(const float *x, int B, int N, const int *ns, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(copy_samples_len_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, x, N, ns, out);
+    return hipGetLastError();
+}
+
+// rows of N samples in; row b holds ns[b]: int(ns[b] ratio) samples computed, zeros from there to the row width ldo (fix_length's one
+// sample and the padding)
+__global__ void resample_kaiser_len_kernel(const float *__restrict__ x, int N, const int *__restrict__ ns, const float *__restrict__ win,
+                                           const float *__restrict__ delta, int nwin, int num_table, double ratio,
+                                           float *__restrict__ out, int ldo) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ldo) return;
+    const int Nb = clamp_count(ns[b], N);
+    if (t >= (int)((double)Nb * ratio)) {
+        out[(long)b * ldo + t] = 0.f;
+        return;
+    }
+    const float *xb = x + (long)b * N;
+    const double scale = ratio < 1.0 ? ratio : 1.0;
+    const int index_step = (int)(scale * num_table);
+    const double time_register = (double)t / ratio;
+    const int n = (int)time_register;
+    double frac = scale * (time_register - n);
+    double index_frac = frac * num_table;
+    int offset = (int)index_frac;
+    double eta = index_frac - offset;
+    int i_max = (nwin - offset) / index_step;
+    i_max = i_max < n + 1 ? i_max : n + 1;
+    double acc = 0.0;
+    for (int i = 0; i < i_max; ++i) {
+        const int k = offset + i * index_step;
+        acc += ((double)win[k] + eta * (double)delta[k]) * (double)xb[n - i];
+    }
+    frac = scale - frac;
+    index_frac = frac * num_table;
+    offset = (int)index_frac;
+    eta = index_frac - offset;
+    int k_max = (nwin - offset) / index_step;
+    k_max = k_max < Nb - n - 1 ? k_max : Nb - n - 1;
+    for (int k2 = 0; k2 < k_max; ++k2) {
+        const int k = offset + k2 * index_step;
+        acc += ((double)win[k] + eta * (double)delta[k]) * (double)xb[n + k2 + 1];
+    }
+    out[(long)b * ldo + t] = (float)(acc * scale);
+}
+hipError_t launch_resample_kaiser_lens(const float *x, int B, int N, const int *ns, const float *win, const float *delta, int nwin,
+                                       int num_table, double ratio, float *out, int ldo, hipStream_t s) {
+    hipLaunchKernelGGL(resample_kaiser_len_kernel, dim3((ldo + 255) / 256, B), dim3(256), 0, s, x, N, ns, win, delta, nwin, num_table,
+                       ratio, out, ldo);
+    return hipGetLastError();
+}
+
+// frames[b] = resampled length of recording b / hop + 1: the row table of the masked mel and DCT GEMMs (ConvParams::lens)
+__global__ void mfcc_frames_kernel(const int *__restrict__ ns, int B, int N, int norig, int nnew, int hop, int *__restrict__ frames) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) frames[b] = resampled_len_of(clamp_count(ns[b], N), norig, nnew) / hop + 1;
+}
+hipError_t launch_mfcc_frames(const int *ns, int B, int N, int norig, int nnew, int hop, int *frames, hipStream_t s) {
+    hipLaunchKernelGGL(mfcc_frames_kernel, dim3((B + 255) / 256), dim3(256), 0, s, ns, B, N, norig, nnew, hop, frames);
+    return hipGetLastError();
+}
+
+// x: rows of N samples at the OUTPUT rate (N = the resampled length of the padded input width); recording b holds
+// ceil(ns[b] nnew / norig) of them.  Workgroup (b, t) of a (B, T) grid: the frame of stft_power_kernel with the reflect index on the
+// recording's own length, or a zero row for t at or beyond the recording's own frame count (no FFT)
+__global__ __launch_bounds__(256) void stft_power_len_kernel(const float *__restrict__ x, int N, int T, const int *__restrict__ ns, int norig,
+                                                             int nnew, int hop, const float *__restrict__ win,
+                                                             const f32x2 *__restrict__ tw1024, const f32x2 *__restrict__ tw2048,
+                                                             float *__restrict__ pw, int ldp) {
+    __shared__ f32x2 bufA[1024], bufB[1024];
+    const long row = blockIdx.x;   // b * T + t
+    const int b = (int)(row / T), t = (int)(row - (long)b * T);
+    const int Nb = clamp_count(resampled_len_of(ns[b], norig, nnew), N);
+    const int j = threadIdx.x;
+    float *out = pw + row * ldp;
+    if (t >= Nb / hop + 1) {
+        for (int k = j; k < ldp; k += 256) out[k] = 0.f;
+        return;
+    }
+    const float *xb = x + (long)b * N;
+    auto sample = [&](int n) {
+        int i = t * hop + n - 1024;
+        if (i < 0) i = -i;
+        if (i >= Nb) i = 2 * (Nb - 1) - i;
+        i = i < 0 ? 0 : (i >= Nb ? Nb - 1 : i);
+        return xb[i] * win[n];
+    };
+    auto butterfly = [](f32x2 &v0, f32x2 &v1, f32x2 &v2, f32x2 &v3) {
+        const f32x2 a = v0 + v2, bb = v0 - v2, c = v1 + v3, d0 = v1 - v3;
+        const f32x2 d = {d0[1], -d0[0]};
+        v0 = a + c; v2 = a - c; v1 = bb + d; v3 = bb - d;
+    };
+    f32x2 v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n = j + 256 * r;
+        v[r] = f32x2{sample(2 * n), sample(2 * n + 1)};
+    }
+    butterfly(v[0], v[1], v[2], v[3]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bufA[j * 4 + r] = v[r];
+    __syncthreads();
+    f32x2 *src = bufA, *dst = bufB;
+#pragma unroll
+    for (int p = 1; p < 5; ++p) {
+        const int Ns = 1 << (2 * p), k = j & (Ns - 1), step = 256 >> (2 * p);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            v[r] = src[j + 256 * r];
+            if (r) v[r] = cmul(v[r], tw1024[r * k * step]);
+        }
+        butterfly(v[0], v[1], v[2], v[3]);
+        const int base = ((j - k) << 2) + k;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[base + r * Ns] = v[r];
+        __syncthreads();
+        f32x2 *tmp = src; src = dst; dst = tmp;
+    }
+    for (int k = j; k < ldp; k += 256) {
+        float val = 0.f;
+        if (k <= 1024) {
+            const f32x2 zk = src[k & 1023], zn0 = src[(1024 - k) & 1023];
+            const f32x2 zn = {zn0[0], -zn0[1]};
+            const f32x2 e = (zk + zn) * 0.5f, o = (zk - zn) * 0.5f;
+            const f32x2 tt = cmul(tw2048[k], o);
+            const float xr = e[0] + tt[1], xi = e[1] - tt[0];
+            val = xr * xr + xi * xi;
+        }
+        out[k] = val;
+    }
+}
+hipError_t launch_stft_power_lens(const float *x, int B, int N, int T, const int *ns, int norig, int nnew, int hop, const float *win,
+                                  const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s) {
+    hipLaunchKernelGGL(stft_power_len_kernel, dim3((unsigned)((long)B * T)), dim3(256), 0, s, x, N, T, ns, norig, nnew, hop, win,
+                       reinterpret_cast<const f32x2 *>(tw1024), reinterpret_cast<const f32x2 *>(tw2048), pw, ldp);
+    return hipGetLastError();
+}
+
+// one workgroup per recording, rows of `width` values, T rows per recording of which frames[b] are its own: decibels, the maximum and the
+// clamp over those rows only; the rows beyond are written as 0 (a second time in ts_mfcc_forward_mixed, whose masked mel GEMM has stored
+// zeros there already: the kernel states its own contract and does not lean on its caller's)
+__global__ __launch_bounds__(256) void db_topdb_len_kernel(float *__restrict__ mel, int T, int width, const int *__restrict__ frames,
+                                                           float top_db) {
+    __shared__ float sm[4];
+    float *p = mel + (long)blockIdx.x * T * width;
+    const long per_clip = (long)clamp_count(frames[blockIdx.x], T) * width, padded = (long)T * width;
+    float mx = -INFINITY;
+    for (long i = threadIdx.x; i < per_clip; i += 256) {
+        const float v = 10.0f * log10f(fmaxf(p[i], 1e-10f));
+        p[i] = v;
+        mx = fmaxf(mx, v);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    const float lo = mx - top_db;
+    for (long i = threadIdx.x; i < per_clip; i += 256) p[i] = fmaxf(p[i], lo);
+    for (long i = per_clip + threadIdx.x; i < padded; i += 256) p[i] = 0.f;
+}
+hipError_t launch_db_topdb_lens(float *mel, int B, int T, int width, const int *frames, float top_db, hipStream_t s) {
+    hipLaunchKernelGGL(db_topdb_len_kernel, dim3(B), dim3(256), 0, s, mel, T, width, frames, top_db);
+    return hipGetLastError();
+}
+
 }  // namespace ts

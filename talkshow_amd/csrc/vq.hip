@@ -384,6 +384,63 @@ hipError_t launch_assemble_full(const float *body, const float *face, const floa
     return hipGetLastError();
 }
 
+// The same assembly for a padded batch (mixed passes): clip b has tb[b] body frames of Tb and tf[b] face frames of Tf.  Row t < tf[b] is the
+// row of assemble_full_kernel on the clip alone (body frame min(t, tb[b] - 1)); rows at or beyond tf[b] are written as 0.  A kernel of its
+// own: the one above keeps its code.
+struct AssembleMixedParams {
+    const float *body;   // (B, Tb, 129)
+    const float *face;   // (B, Tf, 103)
+    const int *tb, *tf;  // (B,) device tables
+    float *out;          // (B, Tf, 265)
+    int B, Tb, Tf;
+    float lp[33];
+};
+__global__ void assemble_full_len_kernel(const AssembleMixedParams p) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long n = (long)p.B * p.Tf * 265;
+    if (i >= n) return;
+    const int c = (int)(i % 265);
+    const long bt = i / 265;
+    const int t = (int)(bt % p.Tf), b = (int)(bt / p.Tf);
+    if (t >= p.tf[b]) {
+        p.out[i] = 0.f;
+        return;
+    }
+    int src;
+    if (c < 3) src = c;
+    else if (c < 18) src = -(c - 3 + 1);
+    else if (c < 21) src = c - 15;
+    else if (c < 27) src = -(15 + c - 21 + 1);
+    else if (c < 30) src = c - 21;
+    else if (c < 36) src = -(21 + c - 30 + 1);
+    else if (c < 39) src = c - 27;
+    else if (c < 45) src = -(27 + c - 39 + 1);
+    else src = c - 33;
+    float v;
+    if (src < 0) {
+        v = p.lp[-src - 1];
+    } else if (src < 3) {
+        v = p.face[((long)b * p.Tf + t) * 103 + src];
+    } else if (src < 132) {
+        int last = p.tb[b] - 1;                       // (clamped into the buffer: the tables exist on the device only)
+        last = last < 0 ? 0 : (last >= p.Tb ? p.Tb - 1 : last);
+        const int tb = t < last ? t : last;
+        v = p.body[((long)b * p.Tb + tb) * 129 + (src - 3)];
+    } else {
+        v = p.face[((long)b * p.Tf + t) * 103 + 3 + (src - 132)];
+    }
+    p.out[i] = v;
+}
+hipError_t launch_assemble_full_lens(const float *body, const int *tb, const float *face, const int *tf, const float *lower_pose33, int B,
+                                     int Tb, int Tf, float *out, hipStream_t stream) {
+    AssembleMixedParams p;
+    p.body = body; p.face = face; p.tb = tb; p.tf = tf; p.out = out; p.B = B; p.Tb = Tb; p.Tf = Tf;
+    for (int k = 0; k < 33; ++k) p.lp[k] = lower_pose33[k];
+    const long n = (long)B * Tf * 265;
+    hipLaunchKernelGGL(assemble_full_len_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 __global__ void i64_to_i32_kernel(const int64_t *src, int *dst, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = (int)src[i];

@@ -338,7 +338,56 @@ def _load_mono_resampled(aud_fn, sr):
     return audio[0]
 
 
+def mixed_tables(ns, sr_in, sr_out=22000, fps=30):
+    """What every recording of a mixed pass gives, from its sample count alone.  Pure host arithmetic (no torch device, no library): the
+    closed forms of the device entries, so a host plans a whole pass — the body pass's length table included — without reading anything
+    back from the device.  ns = sample counts at `sr_in` -> dict of int64 arrays, one entry per recording:
+      n_resampled  samples at sr_out: ceil(N sr_out / sr_in)                      (`ts_mfcc_resampled_len`)
+      mfcc_rows    MFCC rows T = n_resampled // hop + 1, hop 734 | 1467           (`ts_mfcc_num_frames`)
+      code_rows    T // 4                                                         (two k4 / s2 convolutions)
+      pose_frames  4 (T // 4)
+      n16          samples at 16 kHz: ceil(N 16000 / sr_in)                       (`ts_resample_kaiser_len`)
+      face_frames  n16 * 30 // 16000                                              (smplx_face.py:203)"""
+    hop = _hop(fps)
+    ns = np.asarray(ns, dtype=np.int64).reshape(-1)
+    if (ns < 0).any():
+        raise ValueError("mixed_tables: negative sample count")
+    g = math.gcd(int(sr_in), int(sr_out))
+    orig, new = int(sr_in) // g, int(sr_out) // g
+    n_res = (ns * new + orig - 1) // orig
+    rows = n_res // hop + 1
+    # the library's own expression, in the same double arithmetic: ceil(N * 16000.0 / sr_in)
+    n16 = np.asarray([int(math.ceil(float(n) * 16000.0 / float(sr_in))) for n in ns], dtype=np.int64)
+    return {"n_resampled": n_res, "mfcc_rows": rows, "code_rows": rows // 4, "pose_frames": 4 * (rows // 4), "n16": n16,
+            "face_frames": n16 * 30 // 16000}
+
+
+def check_recordings(wavs, who):
+    """Argument check shared by the entries that take a LIST of recordings (no device call): a non-empty list of 1-D sample arrays or
+    tensors -> their sample counts (int64).  Anything else is a ValueError."""
+    if isinstance(wavs, (np.ndarray, torch.Tensor, str, bytes)) or not hasattr(wavs, "__len__") or len(wavs) < 1:
+        raise ValueError(f"{who}: wavs must be a non-empty list of 1-D sample arrays")
+    ns = []
+    for b, w in enumerate(wavs):
+        shape = tuple(w.shape) if hasattr(w, "shape") else np.asarray(w).shape
+        if len(shape) != 1:
+            raise ValueError(f"{who}: clip {b} has shape {shape}; a 1-D array of samples is expected")
+        if shape[0] < 1:
+            raise ValueError(f"{who}: clip {b} is empty")
+        ns.append(int(shape[0]))
+    return np.asarray(ns, dtype=np.int64)
+
+
 _device_mfcc = {}
+
+
+def device_mfcc(sr_in, sr=22000, fps=30):
+    """The front-end handle (`modules.MFCC`) of (sr_in, sr, fps) on the current device, made once."""
+    from .modules import MFCC
+    key = (int(sr_in), int(sr), int(fps), torch.cuda.current_device())
+    if key not in _device_mfcc:
+        _device_mfcc[key] = MFCC(sr_in, sr, fps)
+    return _device_mfcc[key]
 
 
 def _mfcc_on_device(wave_mono, sr_in, sr, fps):

@@ -666,6 +666,114 @@ class MFCC:
         return out
 
 
+    # --- recordings of different lengths in one call (`ts_mfcc_*_mixed`) ---
+    def _tables(self, ns):
+        from .frontend import mixed_tables
+        return mixed_tables(ns, self.sr_in, self.sr_out, self.fps)
+
+    def forward_padded(self, wav, ns_host, ns_dev):
+        """wav (B,N_max) device block, ns_host (B,) int32 numpy and ns_dev its device copy -> (B,T_max,64), rows beyond a recording's own
+        T_b = 0.  No host work beyond the check of ns_host, no synchronisation."""
+        B, N_max = wav.shape
+        T_max = int(self._tables([N_max])["mfcc_rows"][0])
+        out = torch.empty((B, T_max, 64), dtype=torch.float32, device=self._dev)
+        _lib.check(_lib.load().ts_mfcc_forward_mixed(self._h, _lib.dptr(wav), ns_host.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     _lib.dptr(ns_dev), B, N_max, _lib.dptr(out), _lib.stream_ptr()))
+        return out
+
+    def run_clips(self, wavs):
+        """Recordings of DIFFERENT lengths in one call (`ts_mfcc_forward_mixed`): wavs = list of (N_b,) arrays / tensors at sr_in -> list of
+        (T_b, 64) device views of one padded result.  A recording's rows are bit-identical whatever else is in the list, and equal
+        `MFCC(...)(wav_b)`."""
+        from .frontend import check_recordings
+        ns = check_recordings(wavs, "MFCC.run_clips")
+        wav, ns_host, ns_dev = pad_recordings(wavs, ns, range(len(ns)), self._dev)
+        out = self.forward_padded(wav, ns_host, ns_dev)
+        rows = self._tables(ns)["mfcc_rows"]
+        return [out[b, :int(rows[b])] for b in range(len(ns))]
+
+    def resample_clips(self, wavs):
+        """Stage 1 alone on recordings of different lengths (`ts_mfcc_resample_mixed`) -> list of (N'_b,) device views at sr_out."""
+        from .frontend import check_recordings
+        ns = check_recordings(wavs, "MFCC.resample_clips")
+        wav, ns_host, ns_dev = pad_recordings(wavs, ns, range(len(ns)), self._dev)
+        B, N_max = wav.shape
+        n_res = self._tables(ns)["n_resampled"]
+        out = torch.empty((B, int(self._tables([N_max])["n_resampled"][0])), dtype=torch.float32, device=self._dev)
+        _lib.check(_lib.load().ts_mfcc_resample_mixed(self._h, _lib.dptr(wav), ns_host.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      _lib.dptr(ns_dev), B, N_max, _lib.dptr(out), _lib.stream_ptr()))
+        return [out[b, :int(n_res[b])] for b in range(B)]
+
+
+def upload(a, dev):
+    """numpy array -> device tensor through pinned memory, without blocking the host (a pageable copy waits for the stream)."""
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
+def ids_in_row_order(ids, n_classes, order, dev, what='speaker id'):
+    """Class indices of a pass whose rows are recordings order[0], order[1], ...: ids (B values or one for all; anything `_index_tensor`
+    takes) -> (B,) int64 device tensor in row order, range-checked like nn.Embedding.  Host ids are checked, broadcast and reordered on the
+    host and travel through pinned memory: nothing waits for the stream.  Ids that already live on the device are reordered there."""
+    B = len(order)
+    if torch.is_tensor(ids) and ids.is_cuda:
+        ids = _index_tensor(ids, n_classes, what, dev)
+        if ids.numel() == 1 and B > 1:
+            ids = ids.repeat(B)
+        if ids.numel() != B:
+            raise ValueError(f"ids must hold 1 or B={B} indices, got {ids.numel()}")
+        return ids.index_select(0, upload(np.asarray(order, np.int64), dev)).contiguous()
+    _check_index_range(ids, n_classes, what)
+    a = (ids.detach().numpy() if torch.is_tensor(ids) else np.asarray(ids)).astype(np.int64).reshape(-1)
+    if a.size == 1 and B > 1:
+        a = np.repeat(a, B)
+    if a.size != B:
+        raise ValueError(f"ids must hold 1 or B={B} indices, got {a.size}")
+    return upload(a[np.asarray(order, np.int64)], dev)
+
+
+def pad_recordings(wavs, ns, order, dev):
+    """The padded block of a pass: recording order[k] in row k of a (B, N_max) float32 device tensor, zeros beyond it, + the sample counts
+    of the rows as int32 on the host and on the device.  Host recordings are padded on the host and travel in ONE copy; recordings that
+    already live on the device are copied there.  Nothing here waits for the device."""
+    order = list(order)
+    ns_host = np.ascontiguousarray([int(ns[i]) for i in order], dtype=np.int32)
+    N_max = int(ns_host.max())
+    if all(torch.is_tensor(w) and w.is_cuda for w in wavs):
+        wav = torch.zeros((len(order), N_max), dtype=torch.float32, device=dev)
+        for k, i in enumerate(order):
+            wav[k, :int(ns[i])] = wavs[i]
+    else:
+        padded = np.zeros((len(order), N_max), dtype=np.float32)
+        for k, i in enumerate(order):
+            w = wavs[i]
+            padded[k, :int(ns[i])] = w.detach().cpu().numpy() if torch.is_tensor(w) else np.asarray(w)
+        wav = upload(padded, dev)
+    return wav, ns_host, upload(ns_host, dev)
+
+
+def resample_kaiser_padded(wav, ns_host, ns_dev, sr_in, sr_out):
+    """`ts_resample_kaiser_mixed` on a padded device block (B,N_max) -> (B, ceil(N_max sr_out / sr_in)), zeros beyond a recording's own samples."""
+    B, N_max = wav.shape
+    lib = _lib.load()
+    out = torch.empty((B, lib.ts_resample_kaiser_len(N_max, int(sr_in), int(sr_out))), dtype=torch.float32, device=wav.device)
+    _lib.check(lib.ts_resample_kaiser_mixed(_lib.context(wav.device.index), _lib.dptr(wav), ns_host.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            _lib.dptr(ns_dev), B, N_max, int(sr_in), int(sr_out), _lib.dptr(out), _lib.stream_ptr()))
+    return out
+
+
+def resample_kaiser_clips(wavs, sr_in, sr_out, device=None):
+    """`resample_kaiser_device` on recordings of DIFFERENT lengths in one call (`ts_resample_kaiser_mixed`): list of (N_b,) -> list of
+    (ceil(N_b sr_out / sr_in),) device views, each equal to the recording resampled alone."""
+    from .frontend import check_recordings
+    ns = check_recordings(wavs, "resample_kaiser_clips")
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    dev = torch.device("cuda", idx if idx is not None else torch.cuda.current_device())
+    wav, ns_host, ns_dev = pad_recordings(wavs, ns, range(len(ns)), dev)
+    out = resample_kaiser_padded(wav, ns_host, ns_dev, sr_in, sr_out)
+    lib = _lib.load()
+    return [out[b, :lib.ts_resample_kaiser_len(int(n), int(sr_in), int(sr_out))] for b, n in enumerate(ns)]
+
+
 def resample_kaiser_device(wav, sr_in, sr_out, device=None):
     """`librosa.resample(..., res_type='kaiser_best')` on the GPU (`ts_resample_kaiser`): wav (B,N) -> (B, ceil(N*sr_out/sr_in))."""
     idx = torch.cuda.current_device() if device is None else torch.device(device).index

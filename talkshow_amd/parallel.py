@@ -139,6 +139,90 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
     return assemble_full(torch.cat(poses, 0), torch.cat(faces, 0), stand=stand)
 
 
+def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True):
+    """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
+    rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
+    (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
+    `frontend.mixed_tables(ns, sr)["face_frames"]`.
+
+    The recordings are sorted once by sample count (longest first, stable: the order the body pass asks for; the face pass does not care)
+    into one padded block.  Body branch: mixed MFCC front-end -> `ts_body_pixel_infer_mixed`; face branch: the same samples at 16 kHz,
+    otherwise through `ts_resample_kaiser_mixed`, -> `ts_face_generate_mixed`; the branches run on the side-stream arrangement of
+    `whole_body_local`, then `ts_assemble_full_mixed`.  Every table is host arithmetic and every host array travels through pinned memory
+    (`modules.upload`): nothing between taking the list and returning it synchronises or leaves the device (speaker ids handed over as a
+    DEVICE tensor are range-checked once per tensor version, which reads them back; host ids are checked on the host).  A recording's rows are bit-identical to the route of uniform entries on the recording alone
+    (`MFCC` -> `generate_batch`, `FaceGenerator.run_clips`, `assemble_full`), its Philox subsequence is `clip_index0` + its position in
+    the submitted list."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    from nets.smplx_body_pixel import mixed_pass_order
+
+    from .frontend import check_recordings, mixed_tables
+    from .modules import ids_in_row_order, pad_recordings, resample_kaiser_padded, upload
+    from .pose_index import lower_pose_block
+    ns = check_recordings(wavs, "whole_body_clips")
+    B = len(ns)
+    n_ids = int(ids.numel()) if torch.is_tensor(ids) else int(np.asarray(ids).size)
+    if n_ids not in (1, B):
+        raise ValueError(f"whole_body_clips: ids must hold 1 or B={B} speaker indices, got {n_ids}")
+    gen = face.generator
+    if gen.out_dim != 103:
+        raise ValueError("whole_body_clips: the 265-d assembly takes the 103-wide face output (jaw 3 + expression 100)")
+    fid = None
+    if gen.identity:
+        fid = np.zeros((B, gen.num_classes), np.float32) if face_ids is None else \
+            (face_ids.detach().cpu().numpy() if torch.is_tensor(face_ids) else np.asarray(face_ids)).astype(np.float32)
+        if fid.ndim != 2 or fid.shape[1] != gen.num_classes or fid.shape[0] not in (1, B):
+            raise ValueError(f"whole_body_clips: face_ids must be ({B}, {gen.num_classes}) or (1, {gen.num_classes}), got {tuple(fid.shape)}")
+        if fid.shape[0] == 1 and B > 1:
+            fid = np.repeat(fid, B, axis=0)
+    order, inverse = mixed_pass_order(ns)
+    tab = mixed_tables([ns[i] for i in order], sr)
+    if int(tab["mfcc_rows"].min()) < 4 or int(tab["n16"].min()) < 400 or int(tab["face_frames"].min()) < 1:
+        raise ValueError("whole_body_clips: a recording is too short (4 MFCC rows, 400 samples at 16 kHz and one face frame are needed)")
+    mode = _lib.TS_SAMPLE_PHILOX if mode is None else mode
+    dev = body.generator._dev()
+    # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
+    wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
+    small = np.ascontiguousarray(np.stack([tab["n16"], tab["face_frames"], tab["pose_frames"], tab["mfcc_rows"]]), dtype=np.int32)
+    small_dev = upload(small, dev)
+    n16_dev, tf_dev, tb_dev, rows_dev = small_dev[0], small_dev[1], small_dev[2], small_dev[3]
+    ids_sorted = ids_in_row_order(ids, body.num_classes, order, dev)
+    clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
+    fid_dev = upload(fid[order], dev) if fid is not None else None
+    Tf_max = int(small[1].max())
+    cur = torch.cuda.current_stream()
+    side = _side_stream(cur.device) if overlap else cur
+    if overlap:
+        side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev)
+    i32p = C.POINTER(C.c_int32)
+    if int(sr) == 16000:
+        wav16 = wav
+    else:
+        wav16 = resample_kaiser_padded(wav, ns_host, ns_dev, sr, 16000)
+    T16_max = int(wav16.shape[1])                                    # the block's own width; every n16[b] must fit it
+    if int(small[0].max()) > T16_max:
+        raise RuntimeError(f"whole_body_clips: a recording has {int(small[0].max())} samples at 16 kHz, the resampled block is {T16_max} wide")
+    fout = torch.empty((B, Tf_max, gen.out_dim), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().ts_face_generate_mixed(gen.handle(), _lib.dptr(wav16), small[0].ctypes.data_as(i32p), _lib.dptr(n16_dev),
+                                                  small[1].ctypes.data_as(i32p), _lib.dptr(tf_dev), B, T16_max, Tf_max, _lib.dptr(fid_dev),
+                                                  _lib.dptr(fout), None, _lib.stream_ptr()))
+    if overlap:
+        cur.wait_stream(side)
+        poses.record_stream(cur)
+    out = torch.empty((B, Tf_max, 265), dtype=torch.float32, device=dev)
+    lp = lower_pose_block(stand)
+    _lib.check(_lib.load().ts_assemble_full_mixed(_lib.context(dev.index), _lib.dptr(poses), _lib.dptr(tb_dev), _lib.dptr(fout),
+                                                  _lib.dptr(tf_dev), B, poses.shape[1], Tf_max, _lib.fptr(lp), _lib.dptr(out),
+                                                  _lib.stream_ptr()))
+    return [out[inverse[b], :int(small[1][inverse[b]])] for b in range(B)]
+
+
 def whole_body_sharded(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, batch_body=32, batch_face=64, stand=False):
     """BASELINE configs[4]: whole-body generation of N clips sharded over the ranks, one all-gather at the end.
 
