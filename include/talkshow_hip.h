@@ -201,10 +201,18 @@ int ts_face_generate(ts_face *face, const float *wav_dev, int B, int N, int fram
  *   out_dev (B,T_max,103 | 106): rows t < frames[b] = the clip's output, rows t >= frames[b] are written as 0.
  *   hidden_dev optional (B,T_max,768): the same rule.  Every element of both outputs is written, nothing else is touched.
  * The opt-in split-bf16 plans (ts_face_set_arith 3 / 6) are not offered: an error.  The call allocates nothing beyond the growth of the stream's
- * work buffers and never synchronises; the attention work list travels to the device in kernel arguments, in stream order. */
+ * work buffers and never synchronises; the attention work list and the row tables travel to the device in kernel arguments, in stream order.
+ * Cost: every stage runs on B x longest rows, so clips of similar length make the cheaper pass.  TS_FACE_PACK=1 selects the packed plan, with
+ * the same bits: the feature convolutions and the transformer layers (over nine tenths of the work) then run on the clips' OWN rows, packed back
+ * to back — ts_face_mixed_rows gives both counts; the feature projection, the positional convolution and the heads stay on B x T_max rows. */
 int ts_face_generate_mixed(ts_face *face, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
                            const int32_t *frames_dev, int B, int N_max, int T_max, const float *id_dev, float *out_dev, float *hidden_dev,
                            void *stream);
+/* Host only (no device, no handle): the rows a mixed pass of these clips computes, so that a host sizes its passes by real cost.  Same tables and
+ * checks as ts_face_generate_mixed.  out4 = {feature rows padded = B ((N_max - 10) / 5 + 1), feature rows packed = sum over the clips of
+ * (ns[b] - 10) / 5 + 1 rounded up to a multiple of 64, frames padded = B T_max, frames packed = sum of frames[b]}: the feature convolutions cost
+ * in proportion to the second figure, the transformer layers to the fourth (attention: to the sum of frames[b]^2), the rest to the third. */
+int ts_face_mixed_rows(const int32_t *ns_host, const int32_t *frames_host, int B, int N_max, int T_max, int64_t *out4);
 /* OPT-IN arithmetic plan of the generator's GEMMs (no counterpart in the reference, which runs fp32 throughout): 0 = fp32 MFMA,
  * the default and the path every parity claim is made on; 3 / 6 = split-bf16: each fp32 operand becomes 2 / 3 bf16 terms and a
  * product 3 / 6 exact bf16 products accumulated in fp32 (csrc/conv_gemm_split.hip; measured error vs the reference golden in

@@ -217,6 +217,34 @@ int ts_debug_fill_id_lens(const float *id, int nc, const float *w, const float *
  * tile pad the eight queues to equal length.  No reference counterpart. */
 int ts_debug_face_mixed_grid(const int32_t *frames_host, int B, int heads, int32_t *out3, int cap);
 
+/* ---- packed mixed face passes (csrc/face.cpp::face_packed_layout): the clips' own rows back to back ----
+ * Host-only (no GPU): the row layout of a packed pass for ns_host / frames_host (B,).  feat_off (B + 1,): clip b's first row on the one time
+ * axis of the feature convolutions at the conv0 rate (a multiple of 64; [B] = the total); row0 (B + 1,): its first transformer row ([B] = the
+ * sum of frames); levels7: rows of level 0 .. 6 of the feature chain run as ONE problem (levels7[i] / levels7[i + 1] = Lin / Lout of
+ * convolution i, k = 3 3 3 3 2 2, stride 2).  Any output may be NULL.  0, or -1: a bad table (ns < 400, frames < 1 or > 65536) or more rows
+ * than the engines' int row indices hold. */
+int ts_debug_face_packed_layout(const int32_t *ns_host, const int32_t *frames_host, int B, int64_t *feat_off, int64_t *row0, int64_t *levels7);
+/* ts_face_generate_mixed with the row layout named: 0 = padded to the longest clip throughout, 1 = packed.  Same arguments, checks and outputs. */
+int ts_debug_face_generate_mixed(ts_face *face, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev,
+                                 const int32_t *frames_host, const int32_t *frames_dev, int B, int N_max, int T_max, const float *id_dev,
+                                 float *out_dev, float *hidden_dev, void *stream, int layout);
+/* The packed pass's kernels (csrc/face.hip), one launch each; each builds its tables from the host tables and synchronizes `stream`.
+ * ts_debug_attention_packed: qkv (sum frames, 3 HID), out (sum frames, HID), clip b in rows row0[b] .. row0[b] + frames[b]: the values of
+ * ts_debug_attention_mixed on those rows. */
+int ts_debug_attention_packed(const float *qkv, const int32_t *frames_host, const int32_t *frames_dev, int B, int HID, int heads, float scale,
+                              float *out, void *stream);
+/* dst (sum frames, C) row row0[b] + t = src (B, T_max, C) row (b, t), t < frames[b]; C % 4 == 0. */
+int ts_debug_pack_rows(const float *src, const int32_t *frames_host, int B, int T_max, int C, float *dst, void *stream);
+/* dst (B, T_max, C) row (b, t) = src row row0[b] + t for t < frames[b], +0.0 at and beyond: every element of dst is written. */
+int ts_debug_unpack_rows(const float *src, const int32_t *frames_host, const int32_t *frames_dev, int B, int T_max, int C, float *dst,
+                         void *stream);
+/* ts_debug_w2v_conv0_lens writing out (feat_off[B], 512): clip b's rows from feat_off[b], zeros from its own count to feat_off[b + 1]. */
+int ts_debug_w2v_conv0_packed(const float *wav, int B, int N, const int32_t *ns_host, const int32_t *ns_dev, const float *w,
+                              const float *gamma, const float *beta, int form, float *out, void *stream);
+/* ts_debug_lerp_ln_lens reading x (>= feat_off[B] / 64 rows, 512) with clip b's feature rows from feat_off[b] / 64; out (B, T, 512) padded. */
+int ts_debug_lerp_ln_packed(const float *x, int B, int T, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_dev,
+                            const float *gamma, const float *beta, float *out, void *stream);
+
 /* Test aid: how many captured hipGraphs the PixelCNN keeps for `stream` right now (whole-call graphs of repeated shapes + the chunk
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */
 int ts_debug_pixelcnn_graphs(ts_pixelcnn *pix, void *stream);

@@ -99,6 +99,7 @@ SIGNATURES = {
     "ts_face_destroy": (None, [_vp]),
     "ts_face_generate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ts_face_generate_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ts_face_mixed_rows": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(_i64)]),
     "ts_face_set_arith": (_i, [_vp, _i]),
     "ts_mfcc_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "ts_mfcc_destroy": (None, [_vp]),
@@ -146,6 +147,13 @@ SIGNATURES = {
     "ts_debug_w2v_conv0_lens": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "ts_debug_fill_id_lens": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ts_debug_face_mixed_grid": (_i, [C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), _i]),
+    "ts_debug_face_packed_layout": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "ts_debug_face_generate_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "ts_debug_attention_packed": (_i, [_vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, C.c_float, _vp, _vp]),
+    "ts_debug_pack_rows": (_i, [_vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp]),
+    "ts_debug_unpack_rows": (_i, [_vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _vp]),
+    "ts_debug_w2v_conv0_packed": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ts_debug_lerp_ln_packed": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "ts_op_vq_argmin": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "ts_op_linear": (_i, [_vp, _vp, _i, _i, _fp, _fp, _i, _i, _vp, _vp]),
     "ts_op_sample": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -206,6 +214,20 @@ def dptr(t):
 
 def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def face_generate_mixed(handle, wav, ns, ns_dev, frames, frames_dev, B, N_max, T_max, id_dev, out, hidden, layout=None):
+    """`ts_face_generate_mixed` on the current stream; ns / frames = int32 numpy tables, the rest device tensors.  layout None = the
+    library's plan (padded unless TS_FACE_PACK=1); 0 / 1 = padded / packed named through the debug entry (tests, A/B in one process)."""
+    i32p = C.POINTER(C.c_int32)
+    args = [handle, dptr(wav), ns.ctypes.data_as(i32p), dptr(ns_dev), frames.ctypes.data_as(i32p), dptr(frames_dev), int(B), int(N_max),
+            int(T_max), dptr(id_dev), dptr(out), dptr(hidden), stream_ptr()]
+    if layout is None:
+        check(load().ts_face_generate_mixed(*args))
+    else:
+        if layout not in (0, 1):
+            raise ValueError("layout is None (the library's plan), 0 (padded) or 1 (packed)")
+        check(load().ts_debug_face_generate_mixed(*args, int(layout)))
 
 
 def pack_state_dict(sd):

@@ -30,6 +30,7 @@ static Knobs read_knobs(Get get) {
     v.conv_deal = num("TS_CONV_DEAL", 1) != 0;
     v.conv_ring_paired = num("TS_CONV_RING_PAIRED", 1) != 0;
     v.conv_taps48 = num("TS_CONV_TAPS48", 1) != 0;
+    v.face_pack = num("TS_FACE_PACK", 0) != 0;
     v.conv_sk = num("TS_CONV_SK", 1);
     v.w2v_moments = num("TS_W2V_MOMENTS", 1) != 0;
     v.vq_lds = num("TS_VQ_LDS", 1) != 0;
@@ -711,6 +712,108 @@ int ts_debug_fill_id_lens(const float *id, int nc, const float *w, const float *
     if (!id || !w || !bias || !x || !lens || nc < 1 || nj < 1 || col0 < 0 || ld < col0 + nj || B < 1 || T < 1)
         return fail("ts_debug_fill_id_lens: bad argument");
     TS_HIP(ts::launch_fill_id_lens(id, nc, w, bias, nj, x, ld, col0, B, T, lens, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- the packed mixed pass's layout and kernels (face.cpp::face_packed_layout, face.hip); tables built here from the host tables ----
+namespace {
+// feat_off[0 .. B] and row0[0 .. B] of `lay` on the device, in stream order
+int put_layout(const ts::FacePacked &lay, DevBuf &tab, hipStream_t s) {
+    std::vector<int> t(lay.feat_off);
+    t.insert(t.end(), lay.row0.begin(), lay.row0.end());
+    TS_TRY(tab.ensure(t.size() * sizeof(int)));
+    TS_HIP(ts::launch_put_words(tab.i(), t.data(), (long)t.size(), s));
+    return 0;
+}
+}  // namespace
+int ts_debug_face_packed_layout(const int32_t *ns_host, const int32_t *frames_host, int B, int64_t *feat_off, int64_t *row0, int64_t *levels7) {
+    ts::FacePacked lay;
+    if (ts::face_packed_layout(ns_host, frames_host, B, &lay)) return -1;
+    for (int b = 0; b <= B; ++b) {
+        if (feat_off) feat_off[b] = lay.feat_off[b];
+        if (row0) row0[b] = lay.row0[b];
+    }
+    for (int i = 0; i < 7 && levels7; ++i) levels7[i] = lay.len[i];
+    return 0;
+}
+int ts_debug_attention_packed(const float *qkv, const int32_t *frames_host, const int32_t *frames_dev, int B, int HID, int heads, float scale,
+                              float *out, void *stream) {
+    if (!qkv || !out || !frames_host || !frames_dev || B < 1 || heads < 1 || HID != heads * 64) return fail("ts_debug_attention_packed: bad argument");
+    std::vector<int> work, ns(B, 400);
+    const int n = ts::face_mixed_grid(frames_host, B, heads, work);
+    ts::FacePacked lay;
+    if (n < 1 || ts::face_packed_layout(ns.data(), frames_host, B, &lay)) return fail("ts_debug_attention_packed: bad frame table");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf wk, tab;
+    TS_TRY(wk.ensure((size_t)n * sizeof(int)));
+    TS_HIP(ts::launch_put_words(wk.i(), work.data(), n, s));
+    TS_TRY(put_layout(lay, tab, s));
+    TS_HIP(ts::launch_attention_packed(qkv, HID, heads, wk.i(), n, frames_dev, tab.i() + B + 1, scale, out, s));
+    TS_HIP(hipStreamSynchronize(s));   // the tables die with this frame
+    return 0;
+}
+int ts_debug_pack_rows(const float *src, const int32_t *frames_host, int B, int T_max, int C, float *dst, void *stream) {
+    if (!src || !dst || !frames_host || B < 1 || T_max < 1 || C < 4 || C % 4) return fail("ts_debug_pack_rows: bad argument");
+    std::vector<int> ns(B, 400);
+    ts::FacePacked lay;
+    if (ts::face_packed_layout(ns.data(), frames_host, B, &lay)) return fail("ts_debug_pack_rows: bad frame table");
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] > T_max) return fail("ts_debug_pack_rows: bad frame table");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tab;
+    TS_TRY(put_layout(lay, tab, s));
+    TS_HIP(ts::launch_pack_rows(src, B, T_max, C, tab.i() + B + 1, (int)lay.rows, dst, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+int ts_debug_unpack_rows(const float *src, const int32_t *frames_host, const int32_t *frames_dev, int B, int T_max, int C, float *dst,
+                         void *stream) {
+    if (!src || !dst || !frames_host || !frames_dev || B < 1 || T_max < 1 || C < 4 || C % 4) return fail("ts_debug_unpack_rows: bad argument");
+    std::vector<int> ns(B, 400);
+    ts::FacePacked lay;
+    if (ts::face_packed_layout(ns.data(), frames_host, B, &lay)) return fail("ts_debug_unpack_rows: bad frame table");
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] > T_max) return fail("ts_debug_unpack_rows: bad frame table");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tab;
+    TS_TRY(put_layout(lay, tab, s));
+    TS_HIP(ts::launch_unpack_rows(src, tab.i() + B + 1, frames_dev, B, T_max, C, dst, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+int ts_debug_w2v_conv0_packed(const float *wav, int B, int N, const int32_t *ns_host, const int32_t *ns_dev, const float *w,
+                              const float *gamma, const float *beta, int form, float *out, void *stream) {
+    if (!wav || !ns_host || !ns_dev || !w || !gamma || !beta || !out || B < 1 || N < 400 || form < -1 || form > 1)
+        return fail("ts_debug_w2v_conv0_packed: bad argument");
+    std::vector<int> fr(B, 1);
+    ts::FacePacked lay;
+    if (ts::face_packed_layout(ns_host, fr.data(), B, &lay)) return fail("ts_debug_w2v_conv0_packed: bad sample table");
+    for (int b = 0; b < B; ++b)
+        if (ns_host[b] > N) return fail("ts_debug_w2v_conv0_packed: bad sample table");
+    constexpr int C = 512;
+    const int L0 = (N - 10) / 5 + 1, ntb = (L0 + 127) / 128;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf part, stats, tab;
+    TS_TRY(part.ensure((size_t)B * ntb * C * sizeof(double2)));
+    TS_TRY(stats.ensure((size_t)B * C * sizeof(float2)));
+    TS_TRY(put_layout(lay, tab, s));
+    const bool moments = form < 0 ? ts::knobs().w2v_moments : form == 1;
+    TS_HIP(ts::launch_w2v_conv0_packed(wav, B, N, ns_dev, tab.i(), lay.len[0], w, gamma, beta, static_cast<double2 *>(part.p),
+                                       static_cast<float2 *>(stats.p), out, C, moments, s));
+    TS_HIP(hipStreamSynchronize(s));   // the scratch dies with this frame
+    return 0;
+}
+int ts_debug_lerp_ln_packed(const float *x, int B, int T, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_dev,
+                            const float *gamma, const float *beta, float *out, void *stream) {
+    if (!x || !ns_host || !ns_dev || !frames_dev || !gamma || !beta || !out || B < 1 || T < 1) return fail("ts_debug_lerp_ln_packed: bad argument");
+    std::vector<int> fr(B, 1);
+    ts::FacePacked lay;
+    if (ts::face_packed_layout(ns_host, fr.data(), B, &lay)) return fail("ts_debug_lerp_ln_packed: bad sample table");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tab;
+    TS_TRY(put_layout(lay, tab, s));
+    TS_HIP(ts::launch_lerp_ln_packed(x, B, T, ns_dev, frames_dev, tab.i(), gamma, beta, out, s));
+    TS_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

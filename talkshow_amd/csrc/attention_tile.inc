@@ -1,7 +1,7 @@
-// The body of face.hip's attention kernels from the Q fragments to the store, included once per kernel (the uniform kernel and the mixed-pass
-// variant: one text, two compilations — the uniform kernel's code does not depend on the variant's existence).  Expects in scope:
+// The body of face.hip's attention kernels from the Q fragments to the store, included once per kernel (the uniform kernel, the mixed-pass
+// variant and the packed-row variant: one text, three compilations — no kernel's code depends on another's existence).  Expects in scope:
 //   base   qkv + the clip's first row + the head's 64 channels          ld     row pitch of qkv (3 HID)
-//   T      keys and queries of this clip                                 Tp     clip stride of `out` in rows
+//   T      keys and queries of this clip                                 Tp     clip stride of `out` in rows: clip b starts at row b Tp (0 where `out` already points at the clip's first row)
 //   q0     this wave's first query                                       b, h, HID, scale, out, Ks, Vs, tid, wave, li, lg
     // soft-max in base 2: exp(s * scale - max) = 2^(s * scale * log2 e - max'), one v_exp_f32 per probability instead of expf's
     // range reduction (32 of them per lane and key tile: as many VALU slots as the tile's MFMAs have issue slots)

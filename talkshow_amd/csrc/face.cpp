@@ -85,7 +85,6 @@ struct ts_face {
     int JAW = 3, CIN = 320;   // identity=False (num_classes 0, the reference's convert_to_6d form): no id channels (CIN 256), 6 jaw values
     DevBuf c0_w, c0_g, c0_b;
     ConvLayer fc[6];
-    int fc_k[6] = {3, 3, 3, 3, 2, 2};
     LNp fp_ln;
     ConvLayer fp_proj;
     DevBuf pos_w, pos_b, pos_wp;
@@ -103,6 +102,7 @@ struct ts_face {
     struct Work {
         DevBuf A, Bf, part, stats, X512, H, H2, TMP, QKV, ATT, FF, X320, Y1, Y2, R, D1, D2;
         DevBuf att_work;   // mixed passes: the attention work list (face_mixed_grid), written on the stream by every call
+        DevBuf pack_tab;   // packed mixed passes: feat_off[0 .. B], row0[0 .. B] (face_packed_layout), written on the stream by every call
     };
     StreamWorks<Work> works;
     Work &work(hipStream_t s) { return works.get(s); }
@@ -143,15 +143,55 @@ int face_mixed_grid(const int32_t *frames, int B, int heads, std::vector<int> &w
         for (size_t i = 0; i < lane[x].size(); ++i) work[i * 8 + x] = lane[x][i];
     return (int)work.size();
 }
+
+// Row layout of a packed mixed pass, host arithmetic only (no HIP call, no order among the clips needed).
+//   Feature rows: the six stride-2 convolutions read no padding, so the clips lie back to back on ONE time axis and run as a single problem
+//   (B = 1): clip b owns S_b = roundup64(L0(ns[b])) rows at the conv0 rate from feat_off[b] = sum of the segments before it.  Both are
+//   multiples of 64 = 2^6, so at level i (0 .. 6) the clip starts at feat_off[b] >> i exactly, and output row (feat_off[b] >> (i + 1)) + t of
+//   level i + 1 reads input rows (feat_off[b] >> i) + 2 t + d: for t below the clip's own count these are the clip's own valid rows.  Rows near
+//   a seam are computed from a neighbour's data and read by nothing valid.  len[i] = rows of level i of that one problem (len[0] = feat_rows,
+//   len[i + 1] = (len[i] - k_i) / 2 + 1: Lin / Lout of convolution i).
+//   Transformer rows: clip b owns rows [row0[b], row0[b] + frames[b]), no rounding.
+// Refused (-1): a null or bad table (ns < 400, frames < 1 or > 65536), or a row count beyond what the engines index with — rows are `int` in
+// conv_tile.h and the ring engine, and a tile forms row indices up to one tile past the last row before it clamps them (element offsets are
+// `long`: rows x pitch cannot leave them).  The packed totals exceed the padded pass's by at most 63 rows per clip.
+int face_packed_layout(const int32_t *ns, const int32_t *frames, int B, FacePacked *o) {
+    if (!ns || !frames || !o || B < 1) return -1;
+    constexpr long ROW_MAX = 2147483647l - 4096;
+    o->feat_off.assign(B + 1, 0);
+    o->row0.assign(B + 1, 0);
+    long foff = 0, roff = 0;
+    for (int b = 0; b < B; ++b) {
+        if (ns[b] < 400 || frames[b] < 1 || frames[b] > 65536) return -1;
+        o->feat_off[b] = (int)foff;
+        o->row0[b] = (int)roff;
+        foff += ((long)((ns[b] - 10) / 5 + 1) + 63) / 64 * 64;
+        roff += frames[b];
+        if (foff > ROW_MAX || roff > ROW_MAX) return -1;
+    }
+    o->feat_off[B] = (int)foff;
+    o->row0[B] = (int)roff;
+    o->feat_rows = foff;
+    o->rows = roff;
+    o->len[0] = (int)foff;
+    for (int i = 0; i < 6; ++i) o->len[i + 1] = (o->len[i] - FACE_FC_K[i]) / 2 + 1;
+    return 0;
+}
 }  // namespace ts
 
 namespace {
 // a mixed pass (ts_face_generate_mixed): the clips' own sample and frame counts; the uniform entry passes none
 struct FaceLens {
-    const int32_t *ns_dev, *frames_host, *frames_dev;
+    const int32_t *ns_host, *ns_dev, *frames_host, *frames_dev;
+    const char *who;   // the entry's name, for messages
+    bool pack;   // the packed plan (face_packed_layout) for the feature convolutions and the transformer; false: padded throughout
 };
+int face_generate_mixed(ts_face *f, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
+                        const int32_t *frames_dev, int B, int N_max, int T_max, const float *id, float *out, float *hidden_out, void *stream,
+                        bool pack, const char *who);
 int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float *id, float *out, float *hidden_out, hipStream_t s,
              const FaceLens *mx);
+int check_mixed_tables(const int32_t *ns_host, const int32_t *frames_host, int B, int N_max, int T_max, const char *who);
 }  // namespace
 
 extern "C" {
@@ -180,7 +220,7 @@ int ts_face_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int n_layers, int n
     TS_TRY(up(f->c0_g, g0, C0));
     TS_TRY(up(f->c0_b, b0, C0));
     for (int i = 0; i < 6; ++i) {
-        const int K = f->fc_k[i];
+        const int K = FACE_FC_K[i];
         const float *w = sd.get(p + "feature_extractor.conv_layers." + std::to_string(i + 1) + ".conv.weight", {C0, C0, K});
         if (!w) return 1;
         const int taps[3] = {0, 1, 2};   // stride 2, no padding: out[t] = sum_k W_k x[2t + k]
@@ -333,29 +373,64 @@ int ts_face_generate(ts_face *f, const float *wav, int B, int N, int frames, con
     return face_run(f, wav, B, N, frames, id, out, hidden_out, (hipStream_t)stream, nullptr);
 }
 
-// Clips of different lengths in one pass (talkshow_hip.h): the launch plan of ts_face_generate on the padded batch, with the length variants
-// of the kernels wherever a clip's end matters, and no stream-K band.
+// Clips of different lengths in one pass (talkshow_hip.h): the launch plan of ts_face_generate with the length variants of the kernels wherever
+// a clip's end matters and no stream-K band, padded to the longest clip throughout; with TS_FACE_PACK=1 the feature convolutions and the
+// transformer run on the clips' own rows, packed back to back (face_packed_layout), with the same bits.
 int ts_face_generate_mixed(ts_face *f, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
                            const int32_t *frames_dev, int B, int N_max, int T_max, const float *id, float *out, float *hidden_out,
                            void *stream) {
-    if (!f || !wav || !out || (!id && f->NCLS > 0)) return fail("ts_face_generate_mixed: null argument");
-    if (!ns_host || !ns_dev || !frames_host || !frames_dev) return fail("ts_face_generate_mixed: null length table");
-    if (B < 1 || N_max < 1 || T_max < 1 || T_max > 65536) return fail("ts_face_generate_mixed: bad shape");
-    if (f->split_planes) return fail("ts_face_generate_mixed: the split-bf16 plans (ts_face_set_arith 3 / 6) are not offered in a mixed pass");
-    for (int b = 0; b < B; ++b) {
-        const std::string clip = "ts_face_generate_mixed: clip " + std::to_string(b);
-        if (ns_host[b] < 400) return fail(clip + " is shorter than 400 samples");
-        if (ns_host[b] > N_max) return fail(clip + " is longer than N_max");
-        if (frames_host[b] < 1) return fail(clip + " has no frames");
-        if (frames_host[b] > T_max) return fail(clip + " has more frames than T_max");
-    }
-    const FaceLens mx{ns_dev, frames_host, frames_dev};
-    return face_run(f, wav, B, N_max, T_max, id, out, hidden_out, (hipStream_t)stream, &mx);
+    return face_generate_mixed(f, wav, ns_host, ns_dev, frames_host, frames_dev, B, N_max, T_max, id, out, hidden_out, stream,
+                               ts::knobs().face_pack, "ts_face_generate_mixed");
+}
+// the same with the row layout named: 0 = padded, 1 = packed (both in one process: tests, A/B)
+int ts_debug_face_generate_mixed(ts_face *f, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
+                                 const int32_t *frames_dev, int B, int N_max, int T_max, const float *id, float *out, float *hidden_out,
+                                 void *stream, int layout) {
+    if (layout != 0 && layout != 1) return fail("ts_debug_face_generate_mixed: layout is 0 (padded) or 1 (packed)");
+    return face_generate_mixed(f, wav, ns_host, ns_dev, frames_host, frames_dev, B, N_max, T_max, id, out, hidden_out, stream, layout == 1,
+                               "ts_debug_face_generate_mixed");
+}
+
+// Host only: what a mixed pass of these clips costs in rows — out4 = {feature rows (conv0 rate) padded = B L0(N_max), packed = sum of the clips'
+// own rounded up to 64 each, frames padded = B T_max, packed = sum of frames[b]}.  The tables are checked as ts_face_generate_mixed checks them.
+int ts_face_mixed_rows(const int32_t *ns_host, const int32_t *frames_host, int B, int N_max, int T_max, int64_t *out4) {
+    if (!ns_host || !frames_host || !out4) return fail("ts_face_mixed_rows: null argument");
+    TS_TRY(check_mixed_tables(ns_host, frames_host, B, N_max, T_max, "ts_face_mixed_rows"));
+    FacePacked lay;
+    if (face_packed_layout(ns_host, frames_host, B, &lay)) return fail("ts_face_mixed_rows: the pass has more rows than the kernels index");
+    out4[0] = (int64_t)B * ((N_max - 10) / 5 + 1);
+    out4[1] = lay.feat_rows;
+    out4[2] = (int64_t)B * T_max;
+    out4[3] = lay.rows;
+    return 0;
 }
 
 }  // extern "C"
 
 namespace {
+int check_mixed_tables(const int32_t *ns_host, const int32_t *frames_host, int B, int N_max, int T_max, const char *who_) {
+    const std::string who = who_;
+    if (B < 1 || N_max < 1 || T_max < 1 || T_max > 65536) return fail(who + ": bad shape");
+    for (int b = 0; b < B; ++b) {
+        const std::string clip = who + ": clip " + std::to_string(b);
+        if (ns_host[b] < 400) return fail(clip + " is shorter than 400 samples");
+        if (ns_host[b] > N_max) return fail(clip + " is longer than N_max");
+        if (frames_host[b] < 1) return fail(clip + " has no frames");
+        if (frames_host[b] > T_max) return fail(clip + " has more frames than T_max");
+    }
+    return 0;
+}
+int face_generate_mixed(ts_face *f, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_host,
+                        const int32_t *frames_dev, int B, int N_max, int T_max, const float *id, float *out, float *hidden_out, void *stream,
+                        bool pack, const char *who_) {
+    const std::string who = who_;
+    if (!f || !wav || !out || (!id && f->NCLS > 0)) return fail(who + ": null argument");
+    if (!ns_host || !ns_dev || !frames_host || !frames_dev) return fail(who + ": null length table");
+    if (f->split_planes) return fail(who + ": the split-bf16 plans (ts_face_set_arith 3 / 6) are not offered in a mixed pass");
+    TS_TRY(check_mixed_tables(ns_host, frames_host, B, N_max, T_max, who_));
+    const FaceLens mx{ns_host, ns_dev, frames_host, frames_dev, who_, pack};
+    return face_run(f, wav, B, N_max, T_max, id, out, hidden_out, (hipStream_t)stream, &mx);
+}
 // mx == nullptr: B clips of N samples and `frames` frames each.  mx: B clips padded to N samples and `frames` frames (the tables are checked)
 int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float *id, float *out, float *hidden_out, hipStream_t s,
              const FaceLens *mx) {
@@ -365,24 +440,30 @@ int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float
     L[0] = (N - 10) / 5 + 1;
     if (N < 10 || L[0] < 1) return fail("ts_face_generate: audio too short");
     for (int i = 0; i < 6; ++i) {
-        L[i + 1] = (L[i] - f->fc_k[i]) / 2 + 1;
-        if (L[i] < f->fc_k[i]) return fail("ts_face_generate: audio too short (needs >= 400 samples)");
+        L[i + 1] = (L[i] - FACE_FC_K[i]) / 2 + 1;
+        if (L[i] < FACE_FC_K[i]) return fail("ts_face_generate: audio too short (needs >= 400 samples)");
     }
     const long M = (long)B * T;
+    // packed mixed pass: the feature convolutions as ONE problem over the clips' segments, the transformer over the clips' own frames
+    const bool pk = mx && mx->pack;
+    FacePacked lay;
+    if (pk && face_packed_layout(mx->ns_host, mx->frames_host, B, &lay))
+        return fail(std::string(mx->who) + ": the pass has more rows than the kernels index");
+    const long R = pk ? lay.rows : M;   // rows of the transformer block
     ts_face::Work &w = f->work(s);
     const size_t F = sizeof(float);
     const int ntb = (L[0] + 127) / 128;
-    TS_TRY(w.A.ensure((size_t)B * L[0] * C0 * F));
-    TS_TRY(w.Bf.ensure((size_t)B * L[1] * C0 * F));
+    TS_TRY(w.A.ensure((size_t)(pk ? lay.len[0] : (long)B * L[0]) * C0 * F));
+    TS_TRY(w.Bf.ensure((size_t)(pk ? lay.len[1] : (long)B * L[1]) * C0 * F));
     TS_TRY(w.part.ensure((size_t)B * ntb * C0 * sizeof(double2)));
     TS_TRY(w.stats.ensure((size_t)B * C0 * sizeof(float2)));
     TS_TRY(w.X512.ensure(M * C0 * F));
     TS_TRY(w.H.ensure((M * HID + 64) * F));
-    TS_TRY(w.H2.ensure(M * HID * F));
+    TS_TRY(w.H2.ensure(R * HID * F));
     TS_TRY(w.TMP.ensure(M * HID * F));
-    TS_TRY(w.QKV.ensure(M * 3 * HID * F));
-    TS_TRY(w.ATT.ensure(M * HID * F));
-    TS_TRY(w.FF.ensure(M * FFN * F));
+    TS_TRY(w.QKV.ensure(R * 3 * HID * F));
+    TS_TRY(w.ATT.ensure(R * HID * F));
+    TS_TRY(w.FF.ensure(R * FFN * F));
     TS_TRY(w.X320.ensure(M * 320 * F));
     const int CIN = f->CIN, JAW = f->JAW, OUTW = f->JAW + 100;
     TS_TRY(w.Y1.ensure(M * 256 * F));
@@ -399,6 +480,16 @@ int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float
         TS_TRY(w.att_work.ensure((size_t)n_work * sizeof(int)));
         MiscScope ms(ctx, s);
         TS_HIP(launch_put_words(w.att_work.i(), work.data(), n_work, s));
+    }
+    const int *feat_off = nullptr, *row0 = nullptr;   // device tables of the packed layout, B + 1 words each
+    if (pk) {
+        std::vector<int> tab(lay.feat_off);
+        tab.insert(tab.end(), lay.row0.begin(), lay.row0.end());
+        TS_TRY(w.pack_tab.ensure(tab.size() * sizeof(int)));
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w.pack_tab.i(), tab.data(), (long)tab.size(), s));
+        feat_off = w.pack_tab.i();
+        row0 = feat_off + B + 1;
     }
 
     ConvParams p;
@@ -429,22 +520,29 @@ int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float
     // ---- wav2vec2 feature extractor ----
     {
         MiscScope ms(ctx, s);
-        if (mx)   // statistics over each clip's own rows; samples at or beyond ns[b] are not read
+        if (pk)   // the same statistics; the apply pass writes each clip's segment of the one time axis
+            TS_HIP(launch_w2v_conv0_packed(wav, B, N, mx->ns_dev, feat_off, lay.len[0], f->c0_w.f(), f->c0_g.f(), f->c0_b.f(),
+                                           static_cast<double2 *>(w.part.p), static_cast<float2 *>(w.stats.p), w.A.f(), C0,
+                                           ts::knobs().w2v_moments, s));
+        else if (mx)   // statistics over each clip's own rows; samples at or beyond ns[b] are not read
             TS_HIP(launch_w2v_conv0_lens(wav, B, N, mx->ns_dev, f->c0_w.f(), f->c0_g.f(), f->c0_b.f(), static_cast<double2 *>(w.part.p),
                                          static_cast<float2 *>(w.stats.p), w.A.f(), C0, ts::knobs().w2v_moments, s));
         else
             TS_HIP(launch_w2v_conv0(wav, B, N, L[0], f->c0_w.f(), f->c0_g.f(), f->c0_b.f(), static_cast<double2 *>(w.part.p),
                                     static_cast<float2 *>(w.stats.p), w.A.f(), C0, ts::knobs().w2v_moments, s));
     }
-    // (stride 2, no padding: a valid output row reads valid input rows only — in a mixed pass the rows beyond a clip's own are dead weight)
+    // (stride 2, no padding: a valid output row reads valid input rows only — in a padded mixed pass the rows beyond a clip's own are dead
+    // weight; a packed pass runs the clips' segments as one clip, face_packed_layout)
     float *cur = w.A.f(), *nxt = w.Bf.f();
     for (int i = 0; i < 6; ++i) {
-        TS_TRY(conv(f->fc[i], cur, C0, B, L[i], L[i + 1], 2, nullptr, 0, nxt, C0, 0, C0, 3));
+        if (pk) TS_TRY(conv(f->fc[i], cur, C0, 1, lay.len[i], lay.len[i + 1], 2, nullptr, 0, nxt, C0, 0, C0, 3));
+        else TS_TRY(conv(f->fc[i], cur, C0, B, L[i], L[i + 1], 2, nullptr, 0, nxt, C0, 0, C0, 3));
         std::swap(cur, nxt);
     }
     {
         MiscScope ms(ctx, s);
-        if (mx) TS_HIP(launch_lerp_ln_lens(cur, B, L[6], T, mx->ns_dev, lens, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
+        if (pk) TS_HIP(launch_lerp_ln_packed(cur, B, T, mx->ns_dev, lens, feat_off, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
+        else if (mx) TS_HIP(launch_lerp_ln_lens(cur, B, L[6], T, mx->ns_dev, lens, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
         else TS_HIP(launch_lerp_ln(cur, B, L[6], T, f->fp_ln.g.f(), f->fp_ln.b.f(), w.X512.f(), s));
     }
     // the grouped positional conv reads 64-channel windows every 48 channels: the last group's window runs 16 floats past
@@ -510,20 +608,39 @@ int face_run(ts_face *f, const float *wav, int B, int N, int frames, const float
         att_tt = 0;
         for (int b = 0; b < B; ++b) att_tt += (double)mx->frames_host[b] * mx->frames_host[b];
     }
+    // packed: the clips' own rows of the padded block back to back (every row real: uniform LayerNorms, no masks), the padded block again after
+    // the last layer with zeros at and beyond frames[b]
+    float *h = w.H.f(), *tmp = w.TMP.f();
+    if (pk) {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_pack_rows(w.H.f(), B, T, HID, row0, (int)R, w.TMP.f(), s));
+        std::swap(h, tmp);
+    }
+    auto ln_t = [&](const float *x, const LNp &q, float *o) -> int {
+        if (!pk) return ln(x, HID, q, nullptr, 0, o);
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_layernorm_rows(x, HID, R, HID, q.g.f(), q.b.f(), nullptr, HID, 0, o, HID, s));
+        return 0;
+    };
     for (auto &Lp : f->layers) {
         EncLayer &E = *Lp;
-        TS_TRY(conv(E.qkv, w.H.f(), HID, 1, (int)M, (int)M, 1, nullptr, 0, w.QKV.f(), 3 * HID, 0, 3 * HID, 0));
+        TS_TRY(conv(E.qkv, h, HID, 1, (int)R, (int)R, 1, nullptr, 0, w.QKV.f(), 3 * HID, 0, 3 * HID, 0));
         // softmax(Q K^T / 8) V per (clip, head), fused: the scores stay in registers (face.hip::attention_kernel)
         {
             MiscScope ms(ctx, s, FAM_ATTN, 4.0 * HEADS * att_tt * 64);   // Q K^T and P V: 2 x (2 T^2 d) per (clip, head)
-            if (mx) TS_HIP(launch_attention_mixed(w.QKV.f(), T, HID, HEADS, w.att_work.i(), n_work, lens, 0.125f, w.ATT.f(), s));
+            if (pk) TS_HIP(launch_attention_packed(w.QKV.f(), HID, HEADS, w.att_work.i(), n_work, lens, row0, 0.125f, w.ATT.f(), s));
+            else if (mx) TS_HIP(launch_attention_mixed(w.QKV.f(), T, HID, HEADS, w.att_work.i(), n_work, lens, 0.125f, w.ATT.f(), s));
             else TS_HIP(launch_attention(w.QKV.f(), B, T, HID, HEADS, 0.125f, w.ATT.f(), s));
         }
-        TS_TRY(conv(E.outp, w.ATT.f(), HID, 1, (int)M, (int)M, 1, w.H.f(), HID, w.TMP.f(), HID, 0, HID, 0));
-        TS_TRY(ln(w.TMP.f(), HID, E.ln1, nullptr, 0, w.H2.f()));
-        TS_TRY(conv(E.ff1, w.H2.f(), HID, 1, (int)M, (int)M, 1, nullptr, 0, w.FF.f(), FFN, 0, FFN, 3));
-        TS_TRY(conv(E.ff2, w.FF.f(), FFN, 1, (int)M, (int)M, 1, w.H2.f(), HID, w.TMP.f(), HID, 0, HID, 0));
-        TS_TRY(ln(w.TMP.f(), HID, E.ln2, nullptr, 0, w.H.f()));
+        TS_TRY(conv(E.outp, w.ATT.f(), HID, 1, (int)R, (int)R, 1, h, HID, tmp, HID, 0, HID, 0));
+        TS_TRY(ln_t(tmp, E.ln1, w.H2.f()));
+        TS_TRY(conv(E.ff1, w.H2.f(), HID, 1, (int)R, (int)R, 1, nullptr, 0, w.FF.f(), FFN, 0, FFN, 3));
+        TS_TRY(conv(E.ff2, w.FF.f(), FFN, 1, (int)R, (int)R, 1, w.H2.f(), HID, tmp, HID, 0, HID, 0));
+        TS_TRY(ln_t(tmp, E.ln2, h));
+    }
+    if (pk) {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_unpack_rows(h, row0, lens, B, T, HID, w.H.f(), s));
     }
     if (hidden_out) TS_HIP(hipMemcpyAsync(hidden_out, w.H.f(), M * HID * F, hipMemcpyDeviceToDevice, s));
     // ---- audio_feature_map | id channels ----

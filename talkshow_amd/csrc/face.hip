@@ -662,4 +662,170 @@ hipError_t launch_fill_id_lens(const float *id, int nc, const float *w, const fl
     return hipGetLastError();
 }
 
+// ---- packed mixed passes (kernels.h, "packed mixed passes"; face.cpp::face_packed_layout): the clips' own rows back to back.  Kernels of their
+// own: the uniform kernels and the length variants keep their names and their code ----
+// the clip that owns row g of a packed axis: the last b with off[b] <= g (off ascending, off[0] = 0, every clip owns at least one row)
+__device__ __forceinline__ int packed_clip(const int *__restrict__ off, int B, int g) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+constexpr int C0_PB = 64;   // rows per block of the packed apply kernel: a clip's segment is a whole number of them
+// w2v_conv0_apply_len_kernel's statements on one block of 64 rows of the packed axis: rows [off[b], off[b] + L0(ns[b])) are clip b's, the rest of
+// its segment is zeros (what a neighbour's seam rows read; no valid row reads them)
+__global__ __launch_bounds__(256) void w2v_conv0_apply_packed_kernel(const float *__restrict__ wav, int N, int B, const int *__restrict__ ns,
+                                                                 const int *__restrict__ off, const float *__restrict__ w,
+                                                                 const float2 *__restrict__ stats, const float *__restrict__ gamma,
+                                                                 const float *__restrict__ beta, float *__restrict__ out, int C) {
+    __shared__ float sw[C0_PB * 5 + 16];
+    const int g0 = blockIdx.x * C0_PB;
+    const int b = packed_clip(off, B, g0), t0 = g0 - off[b];
+    const int n = ns[b];
+    const int nt = min(C0_PB, w2v_l0(n) - t0);   // >= 1: the segment ends within 64 rows of the clip's last
+    for (int i = threadIdx.x; i < nt * 5 + 5; i += 256) {
+        const int idx = t0 * 5 + i;
+        sw[i] = idx < n ? wav[(long)b * N + idx] : 0.f;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float wk[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) wk[k] = w[c * 10 + k];
+        const float2 st = stats[b * C + c];
+        const float g = gamma[c], be = beta[c];
+        for (int t = 0; t < nt; ++t) {
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) v = fmaf(wk[k], sw[t * 5 + k], v);
+            v = (v - st.x) * st.y * g + be;
+            out[((long)g0 + t) * C + c] = gelu_erf(v);
+        }
+        for (int t = nt; t < C0_PB; ++t) out[((long)g0 + t) * C + c] = 0.f;
+    }
+}
+hipError_t launch_w2v_conv0_packed(const float *wav, int B, int N, const int *ns, const int *off, int feat_rows, const float *w,
+                                   const float *gamma, const float *beta, double2 *part, float2 *stats, float *out, int C, bool moments,
+                                   hipStream_t s) {
+    if (feat_rows < C0_PB || feat_rows % C0_PB) return hipErrorInvalidValue;
+    const int L0 = w2v_l0(N), ntb = (L0 + C0_TB - 1) / C0_TB;
+    if (moments) {
+        const int nblk = (L0 + C0_MB - 1) / C0_MB;
+        double *pm = reinterpret_cast<double *>(part), *mom = pm + (size_t)B * nblk * C0_NQ;
+        hipLaunchKernelGGL(w2v_conv0_moments_len_kernel, dim3(nblk, B), dim3(256), 0, s, wav, N, ns, pm);
+        hipLaunchKernelGGL(w2v_moments_reduce_kernel, dim3((B * C0_NQ + 255) / 256), dim3(256), 0, s, pm, nblk, mom, B * C0_NQ);
+        hipLaunchKernelGGL(w2v_gn_from_moments_len_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, mom, w, C, ns, stats, B * C);
+    } else {
+        hipLaunchKernelGGL(w2v_conv0_stats_len_kernel, dim3(ntb, B), dim3(256), 0, s, wav, N, ns, w, part, C);
+        hipLaunchKernelGGL(w2v_gn_finalize_len_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, part, ntb, C, ns, stats, B * C);
+    }
+    hipLaunchKernelGGL(w2v_conv0_apply_packed_kernel, dim3(feat_rows / C0_PB), dim3(256), 0, s, wav, N, B, ns, off, w, stats, gamma, beta, out, C);
+    return hipGetLastError();
+}
+
+// lerp_ln_len_kernel reading clip b's level-6 rows at off[b] >> 6 of the packed axis; out (B, T, 512) padded, the same values and zeros
+__global__ __launch_bounds__(256) void lerp_ln_packed_kernel(const float *__restrict__ x, int T, long M, const int *__restrict__ ns,
+                                                             const int *__restrict__ frames, const int *__restrict__ off,
+                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                             float *__restrict__ out) {
+    constexpr int CPL = 8, C = 512;
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(m / T), j = (int)(m - (long)b * T);
+    const int Tb = frames[b];
+    if (j >= Tb) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) out[m * C + lane + 64 * i] = 0.f;
+        return;
+    }
+    const int Lb = w2v_feature_rows(ns[b]);
+    const float scale = (float)Lb / (float)Tb;
+    const float src = lerp_src_index(scale, j);
+    const int i0 = (int)floorf(src);
+    const int i1 = min(i0 + 1, Lb - 1);
+    const float l1 = src - (float)i0, l0 = 1.0f - l1;
+    const long first = off[b] >> 6;
+    const float *r0 = x + (first + i0) * C, *r1 = x + (first + i1) * C;
+    float v[CPL];
+#pragma unroll
+    // the product r1 l1 rounded, then ONE fused multiply-add: the order lerp_ln_kernel's code has and lerp_ln_len_kernel states
+    for (int i = 0; i < CPL; ++i) v[i] = __builtin_fmaf(r0[lane + 64 * i], l0, r1[lane + 64 * i] * l1);
+    ln_row<CPL>(v, gamma, beta, lane, 1e-5f);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) out[m * C + lane + 64 * i] = v[i];
+}
+hipError_t launch_lerp_ln_packed(const float *x, int B, int T, const int *ns, const int *frames, const int *off, const float *gamma,
+                                 const float *beta, float *out, hipStream_t s) {
+    const long M = (long)B * T;
+    hipLaunchKernelGGL(lerp_ln_packed_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, T, M, ns, frames, off, gamma, beta, out);
+    return hipGetLastError();
+}
+
+// one wavefront per row, float4 per lane
+__global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict__ src, int T, int C4, const int *__restrict__ row0, int B,
+                                                        int rows, float *__restrict__ dst) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int b = packed_clip(row0, B, m), t = m - row0[b];
+    const float4 *sp = reinterpret_cast<const float4 *>(src) + ((long)b * T + t) * C4;
+    float4 *dp = reinterpret_cast<float4 *>(dst) + (long)m * C4;
+    for (int i = lane; i < C4; i += 64) dp[i] = sp[i];
+}
+__global__ __launch_bounds__(256) void unpack_rows_kernel(const float *__restrict__ src, const int *__restrict__ row0,
+                                                          const int *__restrict__ frames, int T, int C4, long M, float *__restrict__ dst) {
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(m / T), t = (int)(m - (long)b * T);
+    float4 *dp = reinterpret_cast<float4 *>(dst) + m * C4;
+    if (t >= frames[b]) {
+        for (int i = lane; i < C4; i += 64) dp[i] = float4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const float4 *sp = reinterpret_cast<const float4 *>(src) + ((long)row0[b] + t) * C4;
+    for (int i = lane; i < C4; i += 64) dp[i] = sp[i];
+}
+hipError_t launch_pack_rows(const float *src, int B, int T, int C, const int *row0, int rows, float *dst, hipStream_t s) {
+    if (B < 1 || T < 1 || rows < 1 || C < 4 || C % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, src, T, C / 4, row0, B, rows, dst);
+    return hipGetLastError();
+}
+hipError_t launch_unpack_rows(const float *src, const int *row0, const int *frames, int B, int T, int C, float *dst, hipStream_t s) {
+    if (B < 1 || T < 1 || C < 4 || C % 4) return hipErrorInvalidValue;
+    const long M = (long)B * T;
+    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, src, row0, frames, T, C / 4, M, dst);
+    return hipGetLastError();
+}
+
+// attention_mixed_kernel on packed rows: clip b's keys and queries are rows [row0[b], row0[b] + frames[b]) of qkv and out.  Same work list, same
+// tile body (attention_tile.inc, a third compilation: its clip stride is 0 here, the clip's first row is folded into both pointers)
+__global__ __launch_bounds__(256, 2) void attention_packed_kernel(const float *__restrict__ qkv, int HID, int heads,
+                                                                  const int *__restrict__ work, const int *__restrict__ frames,
+                                                                  const int *__restrict__ row0, float scale, float *__restrict__ out_rows) {
+    __shared__ float Ks[64 * ATT_P];
+    __shared__ float Vs[64 * ATT_P];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int e = work[blockIdx.x];
+    if (e < 0) return;
+    const int z = e >> 10, b = z / heads, h = z - b * heads;
+    const int T = frames[b];
+    const int q0 = (e & 1023) * 64 + wave * 16;
+    const long ld = 3L * HID, first = row0[b];
+    constexpr int Tp = 0;
+    const float *base = qkv + first * ld + h * 64;
+    float *__restrict__ out = out_rows + first * HID;
+#include "attention_tile.inc"
+}
+hipError_t launch_attention_packed(const float *qkv, int HID, int heads, const int *work, int n_work, const int *frames, const int *row0,
+                                   float scale, float *out, hipStream_t s) {
+    if (HID != heads * 64 || n_work < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attention_packed_kernel, dim3((unsigned)n_work), dim3(256), 0, s, qkv, HID, heads, work, frames, row0, scale, out);
+    return hipGetLastError();
+}
+
 }  // namespace ts

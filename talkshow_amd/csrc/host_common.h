@@ -232,6 +232,15 @@ int convnet_hidden(const ts_convnet *n);
 // face.cpp, host arithmetic only: the work list of a mixed pass's attention launch (one word per workgroup id; see there).  Returns the number
 // of workgroups, -1 on a bad table
 int face_mixed_grid(const int32_t *frames, int B, int heads, std::vector<int> &work);
+// face.cpp, host arithmetic only: the row layout of a packed mixed pass (see there).  feat_off / row0 hold B + 1 entries (the last = the total);
+// len[i] = rows of level i of the feature chain run as one problem.  0, or -1 on a bad table or a row count the engines cannot index
+struct FacePacked {
+    std::vector<int> feat_off, row0;
+    long feat_rows = 0, rows = 0;
+    int len[7] = {};
+};
+constexpr int FACE_FC_K[6] = {3, 3, 3, 3, 2, 2};   // kernel sizes of the six stride-2 feature convolutions (wav2vec2 base)
+int face_packed_layout(const int32_t *ns, const int32_t *frames, int B, FacePacked *out);
 int vqvae_in_dim(const ts_vqvae *v);
 
 }  // namespace ts

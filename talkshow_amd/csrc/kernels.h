@@ -312,6 +312,7 @@ struct Knobs {
     int conv_ring = 9;          // TS_CONV_RING=0|1|3|8|9: single-problem layers that take 128 x 128 tiles on conv_gemm.hip (0) / forced onto the ring engine's 128 x 128 tile with 4 (1) or 8 (8) waves or its 96 x 128 tile (3) / (9, default) 128 x 128 on 8 waves or 96 x 128 by tile count
     bool w2v_moments = true;    // TS_W2V_MOMENTS=0: conv0's GroupNorm statistics from a pass that computes the convolution (512 channels) instead of from the input's second moments (A/B, tests)
     int conv_sk = 1;            // TS_CONV_SK=0: no stream-K band in the ring engine's plans (whole tiles only: the round-5 plans); 2: the band wherever a layer has a plan for one (A/B, tests)
+    bool face_pack = false;     // TS_FACE_PACK=1: mixed face passes on the packed plan — feature convolutions and transformer rows over the clips' own rows back to back instead of B x longest; same bits; off until padded and packed have been timed side by side
     bool conv_taps48 = true;    // TS_CONV_TAPS48=0: the face generator's grouped positional conv as 64-channel windows on conv_gemm_f32's tiles instead of conv_taps48.hip (A/B, tests)
     bool conv_ring_paired = true;    // TS_CONV_RING_PAIRED=0: paired layers (two problems per launch: body + hands) on conv_gemm.hip's banded launch instead of the ring engine (A/B, tests)
     bool conv_deal = true;      // TS_CONV_DEAL=0: the ring engine's tiles as a plain (row tiles, column tiles) grid instead of dealt to the XCDs in operand-sharing blocks (A/B, tests)
@@ -452,6 +453,25 @@ hipError_t launch_attention_mixed(const float *qkv, int T, int HID, int heads, c
                                   float *out, hipStream_t s);
 hipError_t launch_fill_id_lens(const float *id, int nc, const float *w, const float *bias, int nj, float *x, int ld, int col0,
                                int B, int T, const int *lens, hipStream_t s);
+// ---- packed mixed passes (face.cpp::face_packed_layout): the clips' own rows back to back instead of padded to the longest.  Feature rows:
+// clip b owns rows [off[b], off[b + 1]) of ONE time axis at the conv0 rate, off a multiple of 64 (so off[b] >> i is the clip's first row at
+// level i of the stride-2 chain); transformer rows: clip b owns rows [row0[b], row0[b] + frames[b]).  off / row0: DEVICE tables of B + 1 words,
+// ascending from 0 to the total.  A clip's valid rows are the bits of the length variants above ----
+// conv0 with the statistics kernels of launch_w2v_conv0_lens (per clip, same scratch) and the apply pass into out (feat_rows, C): rows
+// [off[b], off[b] + L0(ns[b])) = the clip's, zeros up to off[b + 1]; one block per 64 rows of the axis, none for rows no clip has
+hipError_t launch_w2v_conv0_packed(const float *wav, int B, int N, const int *ns, const int *off, int feat_rows, const float *w,
+                                   const float *gamma, const float *beta, double2 *part, float2 *stats, float *out, int C, bool moments,
+                                   hipStream_t s);
+// x = level 6 of the packed chain (clip b's rows from off[b] >> 6) -> out (B, T, 512) padded, exactly as launch_lerp_ln_lens writes it
+hipError_t launch_lerp_ln_packed(const float *x, int B, int T, const int *ns, const int *frames, const int *off, const float *gamma,
+                                 const float *beta, float *out, hipStream_t s);
+// dst (rows, C) row row0[b] + t = src (B, T, C) row (b, t) for t < frames[b] = row0[b + 1] - row0[b]; C % 4 == 0
+hipError_t launch_pack_rows(const float *src, int B, int T, int C, const int *row0, int rows, float *dst, hipStream_t s);
+// dst (B, T, C) row (b, t) = src row row0[b] + t for t < frames[b], +0.0 at and beyond; every element of dst is written
+hipError_t launch_unpack_rows(const float *src, const int *row0, const int *frames, int B, int T, int C, float *dst, hipStream_t s);
+// launch_attention_mixed on packed rows: qkv (rows, 3 HID), out (rows, HID), clip b's keys and queries in rows row0[b] .. + frames[b]
+hipError_t launch_attention_packed(const float *qkv, int HID, int heads, const int *work, int n_work, const int *frames, const int *row0,
+                                   float scale, float *out, hipStream_t s);
 // dst[0 .. n) (device) = host[0 .. n), carried by kernel arguments (ceil(n / 960) tiny launches): `host` is free when the call returns
 struct PutWords {
     static constexpr int N = 960;

@@ -597,11 +597,34 @@ class FaceGenerator(NativeModule):
             ids = np.ascontiguousarray(ids)
         return clips, ns, fr, ids
 
-    def run_clips(self, wavs, id_vec, frames=None, want_hidden=False):
+    @staticmethod
+    def mixed_rows(wavs_or_counts, frames=None):
+        """What a mixed pass of these clips computes, in rows (`ts_face_mixed_rows`; host arithmetic, no device): wavs_or_counts = the list
+        `run_clips` takes, or the clips' sample counts; frames as for `run_clips` -> dict(feature_rows_padded, feature_rows_packed,
+        frames_padded, frames_packed).  The feature convolutions cost in proportion to feature_rows_packed, the transformer layers to
+        frames_packed, the feature projection, positional convolution and heads to frames_padded."""
+        ns = np.asarray([int(w) if np.ndim(w) == 0 else int(w.shape[0]) for w in wavs_or_counts], dtype=np.int64)
+        if ns.size < 1 or (ns < 400).any() or (ns >= 2 ** 31).any():
+            raise ValueError("mixed_rows: a non-empty list of clips of at least 400 samples each is expected")
+        ns = ns.astype(np.int32)
+        fr = (ns.astype(np.int64) * 30 // 16000).astype(np.int32) if frames is None else np.asarray(frames)
+        if fr.ndim != 1 or fr.shape[0] != ns.shape[0] or not np.issubdtype(fr.dtype, np.integer) or (fr < 1).any():
+            raise ValueError(f"mixed_rows: frames must be {ns.shape[0]} positive integers, one per clip")
+        fr = np.ascontiguousarray(fr, dtype=np.int32)
+        out = (C.c_int64 * 4)()
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(_lib.load().ts_face_mixed_rows(ns.ctypes.data_as(i32p), fr.ctypes.data_as(i32p), len(ns), int(ns.max()), int(fr.max()), out))
+        return dict(zip(("feature_rows_padded", "feature_rows_packed", "frames_padded", "frames_packed"), (int(v) for v in out)))
+
+    def run_clips(self, wavs, id_vec, frames=None, want_hidden=False, layout=None):
         """Clips of DIFFERENT lengths in one pass (`ts_face_generate_mixed`): wavs = list of 1-D arrays / tensors of 16 kHz samples (>= 400 each),
         id_vec (B,num_classes), (1,num_classes) or None (all-zero rows), frames = one frame count per clip (default len * 30 // 16000)
         -> list of (frames[b], 103 | 106) device tensors [, list of hidden states (frames[b], 768)].  A clip's rows are bit-identical whatever
-        else is in the pass.  Wrong argument shapes raise ValueError before any device call."""
+        else is in the pass.  layout: None = the library's plan (padded to the longest clip unless TS_FACE_PACK=1); 0 / 1 name the padded plan / the
+        packed plan (the clips' own rows back to back in the feature convolutions and the transformer; same bits).  Wrong argument shapes raise ValueError before any
+        device call."""
+        if layout not in (None, 0, 1):
+            raise ValueError("run_clips: layout is None, 0 (padded) or 1 (packed)")
         clips, ns, fr, ids = self._check_clips(wavs, id_vec, frames)
         dev = self._dev()
         B, N_max, T_max = len(clips), int(ns.max()), int(fr.max())
@@ -613,10 +636,7 @@ class FaceGenerator(NativeModule):
         id_dev = torch.from_numpy(ids).to(dev) if ids is not None else None
         out = torch.empty((B, T_max, self.out_dim), dtype=torch.float32, device=dev)
         hid = torch.empty((B, T_max, 768), dtype=torch.float32, device=dev) if want_hidden else None
-        i32p = C.POINTER(C.c_int32)
-        _lib.check(_lib.load().ts_face_generate_mixed(self.handle(), _lib.dptr(wav), ns.ctypes.data_as(i32p), _lib.dptr(ns_dev),
-                                                      fr.ctypes.data_as(i32p), _lib.dptr(fr_dev), B, N_max, T_max, _lib.dptr(id_dev),
-                                                      _lib.dptr(out), _lib.dptr(hid), _lib.stream_ptr()))
+        _lib.face_generate_mixed(self.handle(), wav, ns, ns_dev, fr, fr_dev, B, N_max, T_max, id_dev, out, hid, layout)
         outs = [out[b, :int(fr[b])] for b in range(B)]
         return (outs, [hid[b, :int(fr[b])] for b in range(B)]) if want_hidden else outs
 

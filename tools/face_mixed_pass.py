@@ -8,9 +8,11 @@ Four rows, full-size network (12 layers), inputs staged on the device before any
                adds masked epilogues, against the uniform entry in the default process (band on)
 (A) `FaceGenerator.run` once per distinct length, (B) ONE `ts_face_generate_mixed` over all clips.  Timed regions alternate A B A B after
 a warm-up of both; events on the stream; the figure is the median of the regions.  Padding waste of B = sum(T_max - frames[b]) / (B T_max).
+`--layout` names B's row layout: `default` = the public entry (padded unless TS_FACE_PACK=1), `padded` / `packed` = that plan through
+`ts_debug_face_generate_mixed`, `both` = padded AND packed in the same loop (A B0 B1 A B0 B1): the two plans in one process, one session.
 One JSON line per row; `--out FILE` writes them (with the commit id) as one JSON document.
 
-    python tools/face_mixed_pass.py --regions 5 --out profiles/face_mixed_pass.json
+    python tools/face_mixed_pass.py --regions 5 --layout both --out profiles/face_packed_pass.json
 """
 import argparse
 import ctypes as C
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rows", default="recordings,lengths8,lengths64,equal64")
+    ap.add_argument("--layout", default="default", choices=["default", "padded", "packed", "both"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None, help="commit id to record (default: git rev-parse HEAD of this tree)")
     a = ap.parse_args()
@@ -76,27 +79,44 @@ def main():
         def per_length():
             return [m.run(w, i, f) for w, i, f in staged]
 
-        def mixed():
-            _lib.check(lib.ts_face_generate_mixed(m.handle(), _lib.dptr(wav_d), ns.ctypes.data_as(I32P), _lib.dptr(ns_d), fr.ctypes.data_as(I32P),
-                                                  _lib.dptr(fr_d), B, N_max, T_max, _lib.dptr(ids_d), _lib.dptr(out), None, _lib.stream_ptr()))
+        def mixed(layout):
+            args = [m.handle(), _lib.dptr(wav_d), ns.ctypes.data_as(I32P), _lib.dptr(ns_d), fr.ctypes.data_as(I32P), _lib.dptr(fr_d), B, N_max,
+                    T_max, _lib.dptr(ids_d), _lib.dptr(out), None, _lib.stream_ptr()]
+            if layout == "default":
+                _lib.check(lib.ts_face_generate_mixed(*args))
+            else:
+                _lib.check(lib.ts_debug_face_generate_mixed(*args, 1 if layout == "packed" else 0))
 
+        layouts = ["padded", "packed"] if a.layout == "both" else [a.layout]
+        fns = [("per_length", per_length)] + [(lay, lambda lay=lay: mixed(lay)) for lay in layouts]
         for _ in range(a.warmup):
-            per_length(), mixed()
+            for _, fn in fns:
+                fn()
         torch.cuda.synchronize()
-        ta, tb = [], []
+        t = {k: [] for k, _ in fns}
         for _ in range(a.regions):
-            for fn, acc in ((per_length, ta), (mixed, tb)):
+            for k, fn in fns:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 fn()
                 e1.record()
                 e1.synchronize()
-                acc.append(e0.elapsed_time(e1))
-        rec = dict(row=name, clips=B, distinct_lengths=len(groups), frames_min_max=[int(fr.min()), int(fr.max())],
+                t[k].append(e0.elapsed_time(e1))
+        ta, tb = t["per_length"], t[layouts[-1]]                           # mixed_ms: the named layout (both: packed)
+        rows4 = (C.c_int64 * 4)()
+        _lib.check(lib.ts_face_mixed_rows(ns.ctypes.data_as(I32P), fr.ctypes.data_as(I32P), B, N_max, T_max, rows4))
+        rec = dict(row=name, clips=B, distinct_lengths=len(groups), frames_min_max=[int(fr.min()), int(fr.max())], layout=a.layout,
                    per_length_ms=[round(x, 3) for x in ta], mixed_ms=[round(x, 3) for x in tb],
                    per_length_ms_median=round(statistics.median(ta), 3), mixed_ms_median=round(statistics.median(tb), 3),
                    a_over_b=round(statistics.median(ta) / statistics.median(tb), 3),
-                   padding_waste=round(float((T_max - fr).sum()) / (B * T_max), 4), frames_total=int(fr.sum()))
+                   padding_waste=round(float((T_max - fr).sum()) / (B * T_max), 4), frames_total=int(fr.sum()),
+                   rows=dict(zip(("feature_padded", "feature_packed", "frames_padded", "frames_packed"), (int(v) for v in rows4))))
+        if a.layout == "both":
+            tp = t["padded"]
+            rec.update(padded_ms=[round(x, 3) for x in tp], padded_ms_median=round(statistics.median(tp), 3),
+                       padded_ms_spread=round(max(tp) - min(tp), 3), packed_ms_spread=round(max(tb) - min(tb), 3),
+                       a_over_padded=round(statistics.median(ta) / statistics.median(tp), 3),
+                       padded_over_packed=round(statistics.median(tp) / statistics.median(tb), 3))
         print(json.dumps(rec))
         results.append(rec)
     if a.out:
