@@ -245,6 +245,29 @@ int ts_debug_w2v_conv0_packed(const float *wav, int B, int N, const int32_t *ns_
 int ts_debug_lerp_ln_packed(const float *x, int B, int T, const int32_t *ns_host, const int32_t *ns_dev, const int32_t *frames_dev,
                             const float *gamma, const float *beta, float *out, void *stream);
 
+/* Test aids: the stages of ts_mfcc_forward / ts_mfcc_forward_mixed after the resampler (csrc/mfcc.cpp, csrc/mfcc.hip), one production launch each
+ * on `stream` with the handle's OWN tables (window, FFT twiddles, mel filterbank, DCT matrix; hop and rates as created).  Device pointers the
+ * caller owns throughout; nothing is allocated or synchronized.  The resamplers have public entries (ts_mfcc_resample, ts_resample_kaiser and
+ * their _mixed forms).  frames_dev: null = the uniform kernel; else the DEVICE table (B,) of the clips' own frame counts (the length variant:
+ * rows at or beyond frames[b] are written as +0.0, the masked GEMMs may read but never use them, the dB kernel does not read them).  The table is
+ * NOT checked: the caller keeps 1 <= frames[b] <= T (the kernels clamp a count to [0, T], so a bad table cannot take them outside the
+ * buffers, but a clip of 0 rows has no maximum to clamp at).
+ * ts_debug_mfcc_stft: x (B, N) at the OUTPUT rate -> power (B T, 1056), T = N / hop + 1: bins 0 .. 1024 of |STFT|^2 (center, reflect, periodic
+ * Hann, n_fft 2048), then zeros.  N <= 1024 is refused like ts_mfcc_forward refuses it (reflect padding undefined). */
+int ts_debug_mfcc_stft(ts_mfcc *m, const float *x, int B, long N, float *power, void *stream);
+/* The length variant as production passes it: rows of N samples at the output rate, ns = the clips' sample counts at the INPUT rate (host and
+ * device copies); clip b holds ts_mfcc_resampled_len of ns[b] samples (<= N, > 1024: checked on the host table) and that / hop + 1 frames. */
+int ts_debug_mfcc_stft_lens(ts_mfcc *m, const float *x, const int32_t *ns_host, const int32_t *ns_dev, int B, long N, float *power,
+                            void *stream);
+/* frames_dev[b] = ts_mfcc_num_frames of ns_dev[b] (counts clamped to [0, N_max]): the row table of a mixed pass, made on the device. */
+int ts_debug_mfcc_frames(ts_mfcc *m, const int32_t *ns_dev, int B, long N_max, int32_t *frames_dev, void *stream);
+/* power (B T, 1056) -> mel (B T, 256): the HTK filterbank on conv_gemm_f32 (columns 1025 .. 1055 meet zero weights). */
+int ts_debug_mfcc_mel(ts_mfcc *m, const float *power, const int32_t *frames_dev, int B, int T, float *mel, void *stream);
+/* mel (B, T 256) in place: 10 log10(max(x, 1e-10)), clamped at the clip's own maximum - 80. */
+int ts_debug_mfcc_db(ts_mfcc *m, float *mel, const int32_t *frames_dev, int B, int T, void *stream);
+/* mel (B T, 256) -> feat (B T, 64): the orthonormal DCT-II on conv_gemm_f32. */
+int ts_debug_mfcc_dct(ts_mfcc *m, const float *mel, const int32_t *frames_dev, int B, int T, float *feat, void *stream);
+
 /* Test aid: how many captured hipGraphs the PixelCNN keeps for `stream` right now (whole-call graphs of repeated shapes + the chunk
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */
 int ts_debug_pixelcnn_graphs(ts_pixelcnn *pix, void *stream);

@@ -112,6 +112,12 @@ SIGNATURES = {
     "ts_mfcc_forward_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
     "ts_mfcc_resample_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
     "ts_resample_kaiser_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _i, _i, _vp, _vp]),
+    "ts_debug_mfcc_stft": (_i, [_vp, _vp, _i, C.c_long, _vp, _vp]),
+    "ts_debug_mfcc_stft_lens": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
+    "ts_debug_mfcc_frames": (_i, [_vp, _vp, _i, C.c_long, _vp, _vp]),
+    "ts_debug_mfcc_mel": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ts_debug_mfcc_db": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "ts_debug_mfcc_dct": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "ts_pixelcnn_graph_stats": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "ts_body_pixel_infer": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp]),
     "ts_body_pixel_infer_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp]),

@@ -239,13 +239,55 @@ int ts_resample_kaiser(ts_ctx *ctx, const float *wav, int B, long N, int sr_in, 
 // number of MFCC frames for N input samples: T = floor(N_resampled / hop) + 1 (center=True)
 int ts_mfcc_num_frames(const ts_mfcc *m, long N) { return m ? (int)(m->resampled_len(N) / m->hop) + 1 : -1; }
 
+}  // extern "C"
+
+// ---- the stages of ts_mfcc_forward / ts_mfcc_forward_mixed after the resampler, one launch each on the handle's own tables: shared by the two
+// entries and by the test aids at the end of this file (talkshow_hip_debug.h); the caller opens the MiscScope.  ns = the DEVICE table of sample counts at the input rate and
+// frames = the DEVICE frame table of a mixed pass; null = the uniform kernels. ----
+namespace {
+const char *const SHORT_CLIP = "clip shorter than half an FFT window (reflect padding undefined)";
+
+// x (B, N) at the output rate -> power (B T, nbins_pad): framing + window + 2048-point real FFT + |X|^2 in one kernel (mfcc.hip)
+int stft_stage(ts_mfcc *m, const float *x, const int *ns, int B, int N, int T, float *power, hipStream_t s) {
+    if (ns)
+        TS_HIP(launch_stft_power_lens(x, B, N, T, ns, m->norig, m->nnew, m->hop, m->window.f(), m->tw1024.f(), m->tw2048.f(), power,
+                                      m->nbins_pad, s));
+    else
+        TS_HIP(launch_stft_power(x, B, N, T, m->hop, m->window.f(), m->tw1024.f(), m->tw2048.f(), power, m->nbins_pad, s));
+    return 0;
+}
+// the mel projection (layer = m->mel) and the DCT (m->dct) on conv_gemm_f32: x (B T, ldx) -> out (B T, n); uniform passes run the rows as one
+// clip of B T rows, mixed passes in the (B, T) row form with the length-masked epilogue (rows at or beyond frames[b]: +0.0)
+int gemm_stage(ts_mfcc *m, const ConvLayer &layer, const float *x, int ldx, const int *frames, int B, int T, float *out, int n,
+               hipStream_t s) {
+    ConvParams p;
+    if (frames) {
+        conv_layer_params(layer, x, ldx, B, T, nullptr, 0, out, n, 0, n, &p);
+        p.lens = frames;
+    } else {
+        conv_layer_params(layer, x, ldx, 1, B * T, nullptr, 0, out, n, 0, n, &p);
+    }
+    return run_conv(m->ctx, p, 0, s);
+}
+// mel (B, T nmels) in place: decibels and the per-clip clamp at (max - 80)
+int db_stage(ts_mfcc *m, float *mel, const int *frames, int B, int T, hipStream_t s) {
+    if (frames)
+        TS_HIP(launch_db_topdb_lens(mel, B, T, m->nmels, frames, 80.0f, s));
+    else
+        TS_HIP(launch_db_topdb(mel, B, (long)T * m->nmels, 80.0f, s));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
 // wav_dev (B,N) mono fp32 at sr_in -> feat_dev (B,T,64), T = ts_mfcc_num_frames(m, N)
 int ts_mfcc_forward(ts_mfcc *m, const float *wav, int B, long N, float *feat, void *stream) {
     if (!m || !wav || !feat) return fail("ts_mfcc_forward: null argument");
     hipStream_t s = (hipStream_t)stream;
     ts_ctx *ctx = m->ctx;
     const long N22 = m->resampled_len(N);
-    if (N22 <= m->nfft / 2) return fail("ts_mfcc_forward: clip shorter than half an FFT window (reflect padding undefined)");
+    if (N22 <= m->nfft / 2) return fail(std::string("ts_mfcc_forward: ") + SHORT_CLIP);
     const int T = (int)(N22 / m->hop) + 1;
     const long M = (long)B * T;
     ts_mfcc::Work &w = m->work(s);
@@ -258,20 +300,16 @@ int ts_mfcc_forward(ts_mfcc *m, const float *wav, int B, long N, float *feat, vo
             TS_HIP(launch_resample_polyphase(wav, B, (int)N, m->rs_kern.f(), m->norig, m->nnew, m->width, m->kw, w.x22.f(), (int)N22, s));
             x22 = w.x22.f();
         }
-        // framing + window + 2048-point real FFT + |X|^2 in one kernel (mfcc.hip::stft_power_kernel)
         TS_TRY(w.power.ensure((size_t)M * m->nbins_pad * F));
-        TS_HIP(launch_stft_power(x22, B, (int)N22, T, m->hop, m->window.f(), m->tw1024.f(), m->tw2048.f(), w.power.f(), m->nbins_pad, s));
+        TS_TRY(stft_stage(m, x22, nullptr, B, (int)N22, T, w.power.f(), s));
     }
     TS_TRY(w.melb.ensure((size_t)M * m->nmels * F));
-    ConvParams p;
-    conv_layer_params(m->mel, w.power.f(), m->nbins_pad, 1, (int)M, nullptr, 0, w.melb.f(), m->nmels, 0, m->nmels, &p);
-    TS_TRY(run_conv(ctx, p, 0, s));
+    TS_TRY(gemm_stage(m, m->mel, w.power.f(), m->nbins_pad, nullptr, B, T, w.melb.f(), m->nmels, s));
     {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_db_topdb(w.melb.f(), B, (long)T * m->nmels, 80.0f, s));
+        TS_TRY(db_stage(m, w.melb.f(), nullptr, B, T, s));
     }
-    conv_layer_params(m->dct, w.melb.f(), m->nmels, 1, (int)M, nullptr, 0, feat, m->nmfcc, 0, m->nmfcc, &p);
-    TS_TRY(run_conv(ctx, p, 0, s));
+    TS_TRY(gemm_stage(m, m->dct, w.melb.f(), m->nmels, nullptr, B, T, feat, m->nmfcc, s));
     return 0;
 }
 
@@ -359,21 +397,58 @@ int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, 
                                                   (int)N22, s));
             x22 = w.x22.f();
         }
-        TS_HIP(launch_stft_power_lens(x22, B, (int)N22, (int)T, ns_dev, m->norig, m->nnew, m->hop, m->window.f(), m->tw1024.f(),
-                                      m->tw2048.f(), w.power.f(), m->nbins_pad, s));
+        TS_TRY(stft_stage(m, x22, ns_dev, B, (int)N22, (int)T, w.power.f(), s));
     }
-    ConvParams p;
-    conv_layer_params(m->mel, w.power.f(), m->nbins_pad, B, (int)T, nullptr, 0, w.melb.f(), m->nmels, 0, m->nmels, &p);
-    p.lens = w.frames.i();
-    TS_TRY(run_conv(ctx, p, 0, s));
+    TS_TRY(gemm_stage(m, m->mel, w.power.f(), m->nbins_pad, w.frames.i(), B, (int)T, w.melb.f(), m->nmels, s));
     {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_db_topdb_lens(w.melb.f(), B, (int)T, m->nmels, w.frames.i(), 80.0f, s));
+        TS_TRY(db_stage(m, w.melb.f(), w.frames.i(), B, (int)T, s));
     }
-    conv_layer_params(m->dct, w.melb.f(), m->nmels, B, (int)T, nullptr, 0, feat, m->nmfcc, 0, m->nmfcc, &p);
-    p.lens = w.frames.i();
-    TS_TRY(run_conv(ctx, p, 0, s));
+    TS_TRY(gemm_stage(m, m->dct, w.melb.f(), m->nmels, w.frames.i(), B, (int)T, feat, m->nmfcc, s));
     return 0;
+}
+
+// ---- test aids (talkshow_hip_debug.h): the stages above on caller-owned device buffers; nothing is allocated, `stream` is not synchronized ----
+int ts_debug_mfcc_stft(ts_mfcc *m, const float *x, int B, long N, float *power, void *stream) {
+    if (!m || !x || !power || B < 1 || N < 1 || N > 0x7fffffffl) return fail("ts_debug_mfcc_stft: bad argument");
+    if (N <= m->nfft / 2) return fail(std::string("ts_debug_mfcc_stft: ") + SHORT_CLIP);
+    const long T = N / m->hop + 1;
+    if ((long)B * T > 0x7fffffffl) return fail("ts_debug_mfcc_stft: bad shape");
+    MiscScope ms(m->ctx, (hipStream_t)stream);
+    return stft_stage(m, x, nullptr, B, (int)N, (int)T, power, (hipStream_t)stream);
+}
+int ts_debug_mfcc_stft_lens(ts_mfcc *m, const float *x, const int32_t *ns_host, const int32_t *ns_dev, int B, long N, float *power,
+                            void *stream) {
+    if (!m || !x || !power || !ns_host || !ns_dev || B < 1 || N < 1 || N > 0x7fffffffl) return fail("ts_debug_mfcc_stft_lens: bad argument");
+    for (int b = 0; b < B; ++b) {
+        const long nb = ns_host[b] < 1 ? 0 : m->resampled_len(ns_host[b]);
+        if (nb > N) return fail("ts_debug_mfcc_stft_lens: clip " + std::to_string(b) + " is longer than the rows");
+        if (nb <= m->nfft / 2) return fail("ts_debug_mfcc_stft_lens: clip " + std::to_string(b) + ": " + SHORT_CLIP);
+    }
+    const long T = N / m->hop + 1;
+    if ((long)B * T > 0x7fffffffl) return fail("ts_debug_mfcc_stft_lens: bad shape");
+    MiscScope ms(m->ctx, (hipStream_t)stream);
+    return stft_stage(m, x, ns_dev, B, (int)N, (int)T, power, (hipStream_t)stream);
+}
+int ts_debug_mfcc_frames(ts_mfcc *m, const int32_t *ns_dev, int B, long N_max, int32_t *frames_dev, void *stream) {
+    if (!m || !ns_dev || !frames_dev || B < 1 || N_max < 1 || N_max > 0x7fffffffl) return fail("ts_debug_mfcc_frames: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    MiscScope ms(m->ctx, s);
+    TS_HIP(launch_mfcc_frames(ns_dev, B, (int)N_max, m->norig, m->nnew, m->hop, frames_dev, s));
+    return 0;
+}
+int ts_debug_mfcc_mel(ts_mfcc *m, const float *power, const int32_t *frames_dev, int B, int T, float *mel, void *stream) {
+    if (!m || !power || !mel || B < 1 || T < 1 || (long)B * T > 0x7fffffffl) return fail("ts_debug_mfcc_mel: bad argument");
+    return gemm_stage(m, m->mel, power, m->nbins_pad, frames_dev, B, T, mel, m->nmels, (hipStream_t)stream);
+}
+int ts_debug_mfcc_db(ts_mfcc *m, float *mel, const int32_t *frames_dev, int B, int T, void *stream) {
+    if (!m || !mel || B < 1 || T < 1) return fail("ts_debug_mfcc_db: bad argument");
+    MiscScope ms(m->ctx, (hipStream_t)stream);
+    return db_stage(m, mel, frames_dev, B, T, (hipStream_t)stream);
+}
+int ts_debug_mfcc_dct(ts_mfcc *m, const float *mel, const int32_t *frames_dev, int B, int T, float *feat, void *stream) {
+    if (!m || !mel || !feat || B < 1 || T < 1 || (long)B * T > 0x7fffffffl) return fail("ts_debug_mfcc_dct: bad argument");
+    return gemm_stage(m, m->dct, mel, m->nmels, frames_dev, B, T, feat, m->nmfcc, (hipStream_t)stream);
 }
 
 }  // extern "C"
