@@ -148,6 +148,59 @@ int ts_pixelcnn_prepare(ts_pixelcnn *pix, int B, int H, int mode, void *stream);
  * once it is warm; bench.py asserts it over its timed regions). */
 long ts_pixelcnn_graph_captures(ts_pixelcnn *pix, void *stream);
 
+/* ---- per-clip sampling controls: temperature, top-k, top-p (nucleus) ------------------------------------------------------------------
+ * No counterpart in the reference, which draws from the raw distribution (softmax + multinomial(1), gated_pixelcnn_v2.py:173-176).  One
+ * record per clip; a draw is a pure, bit-reproducible function of the clip's logits row, the clip's record and the clip's uniform. */
+typedef struct ts_sampling {
+    float temperature;   /* finite, > 0, and 1.0f / temperature finite                                */
+    float top_p;         /* 0 < top_p <= 1; 1 = off                                                    */
+    int32_t top_k;       /* >= 0; 0 or any value >= V = off                                            */
+    int32_t reserved;    /* 0                                                                          */
+} ts_sampling;
+/* neutral: {1.0f, 1.0f, 0, 0}.
+ *
+ * THE RULE, for a row l[0..V) with record (T, k, p) and uniform u (talkshow_amd/sampling.py restates it in numpy, operation for operation):
+ *  1. Weights.  m = max l;  d_v = (l_v - m) * inv_T as TWO fp32 operations (subtract, then multiply; never fused), inv_T = 1.0f / T computed
+ *     once on the host in fp32;  w_v = det_expf(d_v), the sampler's exponential (fp32 multiplies and adds only; 0 below -86).  At T = 1 the
+ *     multiplication is exact and w_v has the bits of the sampler without controls.
+ *  2. Rank.  Tokens are ranked by l_v descending (-0 equal to +0), ties by index ascending.  Exact; independent of T.
+ *  3. Top-k.  If 1 <= k < V: keep ranks < k.
+ *  4. Top-p, after top-k, on the mass top-k kept.  MASSES ARE INTEGERS: q_v = floor(w_v * 2^31) (exact product, truncating cast), summed as
+ *     64-bit integers — an order-free accumulation, so no result depends on thread timing (no floating-point atomics exist in the library).
+ *     Q = sum of q over the ranks top-k kept (all ranks when top-k is off);  M(i) = sum of q over ranks < i.  If p < 1: keep rank i iff
+ *     i == 0 or M(i) < ceil(fl64((double)p * (double)Q)): both factors are exact in fp64, their product is ONE IEEE fp64 multiplication,
+ *     rounded to nearest (p has 24 significant bits, Q up to 44: the exact product need not fit 53), then ceil; integers from there on.
+ *     V <= 8191 keeps every sum below 2^44, the width the device gives a mass: a larger vocabulary is refused by every entry.
+ *     Error of the quantisation against the real masses: < 2^-31 per token, < V * 2^-31 (9.6e-7 at V = 2048) of the largest weight (= 1).
+ *  5. Draw.  The inverse CDF of the sampler without controls, in INDEX order with its summation structure, over w'_v = kept ? w_v : 0 in
+ *     fp32: 256 contiguous chunks of ceil(V / 256) tokens summed left to right, the chunk sums prefix-summed left to right (pre[0] = 0),
+ *     thr = u * total; the owning chunk t has pre[t] <= thr and (thr < pre[t+1] or t == 255); the draw is the first token of chunk t at
+ *     which the running sum pre[t] + w'.. exceeds thr (a dropped token adds nothing and is never returned).  If no running sum of the
+ *     chunk exceeds thr: the chunk's highest-index kept token when thr < pre[t+1]; otherwise (thr >= total: u = 1 - 2^-24) the row's
+ *     highest-index kept token.  For a neutral record these are V - 1 and the chunk's last token: exactly what the sampler without
+ *     controls returns.  u comes from uniforms_dev, or from Philox with the same key and counter as without controls: a clip's
+ *     uniform does not depend on its record.
+ * Consequences (tests/test_gpu_sampling_ops.py, test_gpu_sampling_pass.py): a neutral record draws bit for bit what the sampler without
+ * controls draws; top_k = 1 is the argmax with lowest-index ties for every u; a clip's codes depend on its own record only.
+ *
+ * Graphs: the key of a captured graph has one "controls" field.  Passes without a table find and replay exactly the graphs they always did; a
+ * pass with a table captures its own chunk (or whole-call) graphs once, and a repeated pass — with the same or another table: the table
+ * travels to the stream's work buffers as kernel arguments ahead of the replay, no host memory is read after the call returns, nothing
+ * synchronises, any number of calls may be queued — captures nothing.  BUDGET: a host that alternates passes with and without a table on
+ * one stream shares the 16 chunk graphs (and the 8 whole-call graphs) kept per stream between the two kinds.
+ * Out of scope: ts_pixelcnn_stream_* (and BodyStream), ts_pixelcnn_v_*, the face generator, repetition penalties or any control that
+ * reads earlier codes. */
+/* Host only: the validation every _ctl entry applies before anything is launched.  n records for vocabulary V, 1 <= V <= 8191 (a larger V
+ * is an error: see step 4); 0, or an error whose message names the clip: temperature not finite / <= 0 / with an infinite fp32 reciprocal, top_p outside (0, 1], top_k < 0, reserved != 0.
+ * (The entries also refuse a table with TS_SAMPLE_GREEDY or TS_TEACHER_FORCED: per-clip greedy is top_k = 1.) */
+int ts_sampling_check(const ts_sampling *ctl_host, int n, int V);
+/* ts_pixelcnn_generate with a table: its arguments plus ctl_host (n_ctl records: 1 = one for all clips, or B); prefix and logits_dev as
+ * there.  ctl_host == NULL: exactly ts_pixelcnn_generate. */
+int ts_pixelcnn_generate_ctl(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, int B, int H, int mode,
+                             const float *uniforms_dev, uint64_t seed, int64_t clip_index0, int64_t *codes_dev, float *logits_dev,
+                             const int64_t *pre_codes_dev, const float *pre_aud_dev, int H0, const ts_sampling *ctl_host, int n_ctl,
+                             void *stream);
+
 /* GatedPixelCNN(input_dim, dim, n_layers, n_classes, audio, bh_model=False) — the single-stack form (gated_pixelcnn_v2.py:37-42,
  * 80-85,147-150): vertical kernels one column wide, out_v = horiz_resid(gate(vert_stack(x_v) + class)) [+ x_v], logits from x_v; the
  * grid's W columns never mix, so the W codes of a row are drawn together.  Same state_dict keys as the reference module (the
@@ -273,6 +326,18 @@ int ts_audioenc_forward_masked(ts_convnet *net, const float *mfcc_dev, const int
 int ts_pixelcnn_generate_mixed(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
                                const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
                                const int64_t *clip_index_dev, int64_t *codes_dev, void *stream);
+/* ts_body_pixel_infer_mixed / ts_pixelcnn_generate_mixed with per-clip sampling controls (ts_sampling above): their arguments plus ctl_host
+ * (n_ctl records: 1 = one for all clips, or B, in the order of the submitted, SORTED clips — record b belongs to row b of every table of the
+ * pass).  The records ride in the stream's work buffers, indexed by the clip's slot in the pass (the active clips are a prefix, so the slot
+ * is the same in every chunk).  A clip's codes and poses are bit-identical to the clip run alone with its record.  ctl_host == NULL: exactly
+ * the entry without the suffix.  A table needs TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX. */
+int ts_body_pixel_infer_mixed_ctl(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                  const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                  const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                  float *poses_dev, const ts_sampling *ctl_host, int n_ctl, void *stream);
+int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                   const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                   const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl, void *stream);
 /* ts_vqvae_decode_pair with length-masked layers: latents (B,H) each, rows at or beyond lens[b] / 4 are not read (gathered as zero rows;
  * an index outside the codebook INSIDE a clip still gives NaNs); out_dev (B,4H,body_dim+hand_dim), rows at or beyond 4 (lens[b] / 4) = 0. */
 int ts_vqvae_decode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *lat_body_dev, const int64_t *lat_hand_dev,
@@ -310,6 +375,13 @@ int ts_op_sample(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, c
  * exactly what ts_pixelcnn_generate uses for clip clip_index0 + b at grid position row * 2 + column. */
 int ts_op_sample_philox(ts_ctx *ctx, const float *logits_dev, int B, int V, uint64_t seed, int64_t clip_index0,
                         uint32_t position, int64_t *idx_dev, void *stream);
+
+/* ts_op_sample / ts_op_sample_philox with sampling controls (ts_sampling, steps 1-5): logits_dev (B,V), 1 <= V <= 8191; mode TS_SAMPLE_UNIFORMS
+ * (uniforms_dev (B)) or TS_SAMPLE_PHILOX (seed, clip_index0, position as in ts_op_sample_philox); ctl_host: n_ctl = 1 (one record for all
+ * rows) or B records -> idx_dev (B) int64 and, if not NULL, kept_dev (B,V) uint8: 1 for the tokens the filters kept. */
+int ts_op_sample_ctl(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                     int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, uint8_t *kept_dev,
+                     void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

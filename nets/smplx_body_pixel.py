@@ -96,12 +96,22 @@ class TrainWrapper(TrainWrapperBaseClass):
         self.g_hand.decode_nlc(latents[..., 1].contiguous(), out=out, col0=self.each_dim[1])
         return out
 
-    def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False):
+    def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
         driver use it directly.
+
+        sampling: one sampling record (`_lib.sampling_record`: temperature, top_p, top_k) for all clips, or one per clip.  WITH a record the
+        batch goes through the mixed entry (`generate_clips`, `ts_body_pixel_infer_mixed_ctl`) with equal lengths — a clip's codes there
+        equal this entry's, bit for bit, so a neutral record changes nothing but the route.  Without one: the uniform entry below, unchanged.
         """
+        if sampling is not None:
+            dev = self.generator._dev()
+            mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
+            u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
+            return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
+                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -127,7 +137,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             _lib.dptr(codes), _lib.dptr(poses), _lib.stream_ptr()))
         return codes, poses
 
-    def generate_batches(self, mfccs, ids_list, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0):
+    def generate_batches(self, mfccs, ids_list, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, sampling=None):
         """Coalesced execution of several independent batches (the serving path): the batches' clips are stacked and
         the autoregressive chain runs ONCE over all of them, so a stage's weights are streamed once for all batches
         in flight instead of once per batch (a chain stage is latency-bound below ~64 clips).  Results are bit-identical
@@ -136,13 +146,15 @@ class TrainWrapper(TrainWrapperBaseClass):
 
         Batches whose T differ ride in ONE mixed pass (`generate_clips`: length-masked conv stacks, the chain over a shrinking prefix
         of the clips); each batch gets its results trimmed to its own H and 4 H, with the same bits and the same Philox subsequences.
-        Batches of one T take the uniform path below, unchanged.
+        Batches of one T take the uniform path below, unchanged.  sampling: one sampling record for all clips or one per clip of the
+        stacked batches, in list order; WITH a record the batches go through the mixed pass whatever their lengths (equal ones included):
+        a clip's codes there equal the uniform entry's.
 
         mfccs: list of (B_i,T_i,64) device tensors, ids_list: list of (B_i,) -> list of (codes_i, poses_i) views."""
         dev = self.generator._dev()
         sizes = [int(m.shape[0]) for m in mfccs]
-        if len({int(m.shape[1]) for m in mfccs}) > 1:     # batches of different lengths: one mixed pass (equal lengths: the path below, unchanged)
-            return self._generate_batches_mixed(mfccs, ids_list, sizes, mode, seed, clip_index0)
+        if len({int(m.shape[1]) for m in mfccs}) > 1 or sampling is not None:     # different lengths, or controls: one mixed pass
+            return self._generate_batches_mixed(mfccs, ids_list, sizes, mode, seed, clip_index0, sampling)
         # nn.Embedding's IndexError per submitted batch, BEFORE stacking: host ids are checked on the host, a caller-owned device
         # tensor once per tensor version (modules._check_index_range) — the stacked tensor built below is new on every call, and
         # checking it would cost the serving path one blocking device -> host read per pass (ADVICE r3)
@@ -156,7 +168,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         codes, poses = self.generate_batch(mf, ids, mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True)
         return list(zip(codes.split(sizes, 0), poses.split(sizes, 0)))
 
-    def _generate_batches_mixed(self, mfccs, ids_list, sizes, mode, seed, clip_index0):
+    def _generate_batches_mixed(self, mfccs, ids_list, sizes, mode, seed, clip_index0, sampling=None):
         from talkshow_amd.modules import _check_index_range
         dev = self.generator._dev()
         clips, ids = [], []
@@ -171,7 +183,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             clips += list(m.unbind(0))
             ids.append(i)
         codes, poses = self.generate_clips(clips, torch.cat(ids, 0), mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True,
-                                           _stacked=True)
+                                           _stacked=True, sampling=sampling)
         out, k = [], 0
         for m, b in zip(mfccs, sizes):          # per submitted batch, trimmed to that batch's own H and 4 H
             H = int(m.shape[1]) // 4
@@ -180,7 +192,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
-                       _ids_checked=False, _stacked=False):
+                       _ids_checked=False, _stacked=False, sampling=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -188,7 +200,10 @@ class TrainWrapper(TrainWrapperBaseClass):
         are sorted here (stable, longest first), padded to the longest, and the results are put back in submission order.  Clip b draws from
         Philox subsequence `clip_index0 + b` with b its position in the SUBMITTED list, whatever the sort does: the draws are what they
         would be had all clips had one length; `clip_indices` (B ints) names every clip's global index outright instead (a host that
-        regroups clips between passes keeps each clip's random stream).  uniforms: list of (H_b,2) per clip for TS_SAMPLE_UNIFORMS."""
+        regroups clips between passes keeps each clip's random stream).  uniforms: list of (H_b,2) per clip for TS_SAMPLE_UNIFORMS.
+        sampling: one sampling record (`_lib.sampling_record`: temperature, top_p, top_k) for all clips, or a list of one per clip in
+        SUBMISSION order; the records are carried through the length sort exactly as `clip_indices` are, and a clip's codes depend on its
+        own record only (`ts_body_pixel_infer_mixed_ctl`).  A bad record raises ValueError naming the clip, before anything is launched."""
         dev = self.generator._dev()
         B = len(mfcc_list)
         if B < 1:
@@ -209,6 +224,10 @@ class TrainWrapper(TrainWrapperBaseClass):
         if ids.numel() != B:
             raise ValueError(f"ids must hold 1 or B={B} speaker indices, got {ids.numel()}")
         order, inverse = mixed_pass_order(lens)
+        ctl, n_ctl = None, 0
+        if sampling is not None:   # sorted slot k holds the record of submitted clip order[k]
+            recs = _lib.sampling_records(sampling, B)
+            ctl, n_ctl = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -239,21 +258,25 @@ class TrainWrapper(TrainWrapperBaseClass):
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         codes = torch.empty((B, H_max, 2), dtype=torch.int64, device=dev)
         poses = torch.empty((B, 4 * H_max, self.each_dim[1] + self.each_dim[2]), dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().ts_body_pixel_infer_mixed(
-            self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
-            _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
-            mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses), _lib.stream_ptr()))
+        args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
+                _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
+                mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
+        if ctl is None:
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_ctl(*args, ctl, n_ctl, _lib.stream_ptr()))
         inv_dev = torch.as_tensor(inverse, dtype=torch.int64, device=dev)
         codes, poses = codes.index_select(0, inv_dev), poses.index_select(0, inv_dev)     # back to submission order
         if _stacked:
             return codes, poses
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
-    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None):
+    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
-        pass's host table is `mixed_tables` arithmetic (lens_dev: its device copy, (B,) int32, if the caller has uploaded one).  No synchronisation."""
+        pass's host table is `mixed_tables` arithmetic (lens_dev: its device copy, (B,) int32, if the caller has uploaded one).  No synchronisation.
+        sampling_table: `_lib.sampling_table(...)` in ROW order (the caller sorted it with the rows), or None."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -268,18 +291,23 @@ class TrainWrapper(TrainWrapperBaseClass):
         H_max = T_max // 4
         codes = torch.empty((B, H_max, 2), dtype=torch.int64, device=dev)
         poses = torch.empty((B, 4 * H_max, self.each_dim[1] + self.each_dim[2]), dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().ts_body_pixel_infer_mixed(
-            self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
-            _lib.dptr(mf), _lib.dptr(ids), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
-            mode, None, int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses), _lib.stream_ptr()))
+        args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
+                _lib.dptr(mf), _lib.dptr(ids), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
+                mode, None, int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
+        if sampling_table is None:
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_ctl(*args, sampling_table[0], sampling_table[1], _lib.stream_ptr()))
         return codes, poses, lens_host
 
-    def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30):
+    def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
+                                sampling=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
         `generate_batch(MFCC(sr)(wav_b), id_b)` on the clip alone; clip b draws from Philox subsequence `clip_index0 + b`, b its position in
-        the SUBMITTED list (or `clip_indices[b]`)."""
+        the SUBMITTED list (or `clip_indices[b]`).  sampling: one sampling record for all recordings or one per recording in submission
+        order; the records follow the recordings through the sort by sample count."""
         from talkshow_amd.frontend import check_recordings
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -291,6 +319,10 @@ class TrainWrapper(TrainWrapperBaseClass):
             raise ValueError(f"generate_clips_from_wav: clip_indices must name {B} clips, got {len(clip_indices)}")
         dev = self.generator._dev()
         order, inverse = mixed_pass_order(ns)
+        table = None
+        if sampling is not None:
+            recs = _lib.sampling_records(sampling, B)
+            table = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -299,7 +331,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         if seed is None:
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
-        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps)
+        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,
@@ -308,9 +340,20 @@ class TrainWrapper(TrainWrapperBaseClass):
         (aud_fn, txgfile) -> generated motion (B, T, C)      [smplx_body_pixel.py:232-289]
 
         Extra keyword arguments understood here (ignored by the reference through **kwargs):
-        `greedy=True` (argmax decode), `seed=int`, `uniforms=(B,H,2)`.
+        `greedy=True` (argmax decode), `seed=int`, `uniforms=(B,H,2)`, and the sampling controls `temperature=`, `top_k=`, `top_p=`
+        (one record for all B samples; `generate_batch(..., sampling=)`).  The streaming session behind `continuity=True` takes no
+        controls yet: together they raise ValueError.
         '''
         assert self.args.infer, "train mode"
+        sampling = None
+        if any(kwargs.get(k) is not None for k in ('temperature', 'top_k', 'top_p')):
+            if continuity:
+                raise ValueError("infer_on_audio: the streaming session behind continuity=True takes no sampling controls yet "
+                                 "(temperature / top_k / top_p)")
+            if kwargs.get('greedy', False):
+                raise ValueError("infer_on_audio: sampling controls with greedy=True (greedy through the controls is top_k=1)")
+            sampling = {k: kwargs[k] for k in ('temperature', 'top_k', 'top_p') if kwargs.get(k) is not None}
+            _lib.sampling_table(sampling, 1, self.generator.input_dim)      # a bad record raises before the audio is read
         self.generator.eval()
         self.g_body.eval()
         self.g_hand.eval()
@@ -359,7 +402,7 @@ class TrainWrapper(TrainWrapperBaseClass):
                 pred_poses = torch.cat([part0, part1], dim=1).cpu().numpy()
             else:
                 self.audioencoder.eval()
-                _, poses = self.generate_batch(aud_feat, id, mode=mode, uniforms=uniforms, seed=seed)
+                _, poses = self.generate_batch(aud_feat, id, mode=mode, uniforms=uniforms, seed=seed, sampling=sampling)
                 pred_poses = poses.cpu().numpy()
 
         output = pred_poses

@@ -25,6 +25,14 @@ class TsTensor(C.Structure):
 _vp, _i, _i64, _u64, _fp = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.POINTER(C.c_float)
 
 
+class TsSampling(C.Structure):
+    """ts_sampling (include/talkshow_hip.h): the sampling record of one clip; neutral = (1.0, 1.0, 0, 0)."""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32)]
+
+
+_sp = C.POINTER(TsSampling)
+
+
 class SkinnySeg(C.Structure):
     """ts_debug_skinny_seg (include/talkshow_hip_debug.h)."""
     _fields_ = [("base", _vp), ("gidx", _vp), ("row_stride", C.c_long), ("gidx_stride", C.c_long), ("row_shift", _i), ("len", _i),
@@ -88,6 +96,12 @@ SIGNATURES = {
     "ts_pixelcnn_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_destroy": (None, [_vp]),
     "ts_pixelcnn_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ts_sampling_check": (_i, [_sp, _i, _i]),
+    "ts_pixelcnn_generate_ctl": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _sp, _i, _vp]),
+    "ts_op_sample_ctl": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, _vp]),
+    "ts_body_pixel_infer_mixed_ctl": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                           _vp]),
+    "ts_pixelcnn_generate_mixed_ctl": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -234,6 +248,58 @@ def face_generate_mixed(handle, wav, ns, ns_dev, frames, frames_dev, B, N_max, T
         if layout not in (0, 1):
             raise ValueError("layout is None (the library's plan), 0 (padded) or 1 (packed)")
         check(load().ts_debug_face_generate_mixed(*args, int(layout)))
+
+
+NEUTRAL_SAMPLING = (1.0, 1.0, 0)
+
+
+def sampling_record(rec):
+    """One sampling record as (temperature, top_p, top_k) floats / int: None (neutral), a dict with any of the keys `temperature`, `top_p`,
+    `top_k`, or a TUPLE (temperature, top_p, top_k).  A list is never one record: lists hold one record per clip (`sampling_records`).
+    Pure host code."""
+    if rec is None:
+        return NEUTRAL_SAMPLING
+    if isinstance(rec, dict):
+        unknown = set(rec) - {"temperature", "top_p", "top_k"}
+        if unknown:
+            raise ValueError(f"sampling record: unknown keys {sorted(unknown)} (temperature, top_p, top_k)")
+        t, p, k = rec.get("temperature"), rec.get("top_p"), rec.get("top_k")
+        return (1.0 if t is None else float(t), 1.0 if p is None else float(p), 0 if k is None else int(k))
+    if isinstance(rec, tuple) and len(rec) == 3:
+        return (float(rec[0]), float(rec[1]), int(rec[2]))
+    raise ValueError(f"a sampling record is None, a dict or a tuple (temperature, top_p, top_k), got {rec!r}")
+
+
+def sampling_records(sampling, n):
+    """`sampling` as a list of n records: None / a dict / a 3-tuple is ONE record for all clips, a LIST of n entries (each None, a dict or a
+    3-tuple) is one per clip.  A single record written as a list, `[0.9, 0.95, 64]`, is refused with a message that says so."""
+    if sampling is None or isinstance(sampling, (dict, tuple)):
+        return [sampling_record(sampling)] * n
+    if not isinstance(sampling, list):
+        raise ValueError(f"sampling must be None, a dict, a tuple (temperature, top_p, top_k) or a list of one record per clip, got {sampling!r}")
+    recs = sampling
+    if recs and all(isinstance(r, (int, float)) for r in recs):
+        raise ValueError(f"sampling={recs!r}: a list holds one record per clip; write one record for all clips as a tuple (temperature, top_p, top_k)")
+    if len(recs) != n:
+        raise ValueError(f"sampling must hold one record or one per clip ({n}), got {len(recs)}")
+    return [sampling_record(r) for r in recs]
+
+
+def sampling_table(sampling, n, V=2048, mode=None):
+    """A validated `ts_sampling` table of n records (ts_sampling_check: a bad record raises ValueError naming the clip) -> (array, n).  With
+    `mode`, a table for a mode that draws nothing (greedy, teacher forced) is refused here as the C entries refuse it."""
+    if mode is not None and mode not in (TS_SAMPLE_UNIFORMS, TS_SAMPLE_PHILOX):
+        raise ValueError("sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)")
+    recs = sampling_records(sampling, n)
+    arr = (TsSampling * n)()
+    for b, (t, p, k) in enumerate(recs):
+        if not -2 ** 31 <= k < 2 ** 31:
+            raise ValueError(f"sampling record of clip {b}: top_k out of range")
+        arr[b].temperature, arr[b].top_p, arr[b].top_k, arr[b].reserved = t, p, k, 0
+    lib = load()
+    if lib.ts_sampling_check(arr, n, int(V)) != 0:
+        raise ValueError("libtalkshow_hip: " + lib.ts_last_error().decode())
+    return arr, n
 
 
 def pack_state_dict(sd):

@@ -416,6 +416,22 @@ struct SampleParams {
 };
 hipError_t launch_sample(const SampleParams &p, hipStream_t stream);
 
+// Per-clip sampling controls (talkshow_hip.h: ts_sampling and the rule of steps 1-5).  The device record of a clip: 1 / temperature as the
+// HOST computed it in fp32, top_p, top_k (0 or >= V: off).  A sibling of SampleParams: the sampler without controls keeps its arguments.
+struct SampleCtl {
+    float inv_t, top_p;
+    int32_t top_k, pad;
+};
+struct SampleCtlParams {
+    SampleParams s;            // mode TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX
+    const SampleCtl *ctl;      // record of clip b at ctl[b]
+    unsigned char *kept;       // optional (B,V): 1 for the tokens the filters kept
+};
+// a histogram bin of the kernel holds count << 44 | mass with mass <= V * 2^31: V * 2^31 < 2^44 bounds the vocabulary (the tie counters' 16 bits
+// and the count field hold more); launch_sample_ctl and the host checks refuse anything above
+constexpr int SAMPLE_CTL_MAX_V = 8191;
+hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------------
 // face generator kernels (face.hip)
 // ------------------------------------------------------------------------------------------------

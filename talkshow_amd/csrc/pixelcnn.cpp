@@ -86,13 +86,16 @@ struct ts_pixelcnn {
         DevBuf codes_int, unif_int, dyn;   // dyn: {seed, clip0, position base} of the call being replayed, written by a kernel ahead of it
         DevBuf cAEH, cAEH1, cAV1C, cAV1P;  // the audio terms of ONE chunk of rows, compact (chunked one-shot calls: see run_chunked)
         DevBuf clip_tab;                   // mixed passes: the Philox subsequence of every clip (int64), read by the captured samplers
+        DevBuf ctl_tab;                    // passes with sampling controls: one SampleCtl per clip SLOT of the pass, written in stream order ahead of it
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
         // (Br, Hc, -(1 + phase), mode, Bs) = Hc rows of a MIXED pass of Bs clips for its first Br clips: the per-clip slabs of the work
         // buffers are Bs clips apart whatever Br is, so the stride is part of what a captured graph is valid for (0: the slabs are B apart).
+        // The sixth field is 1 for a run whose samplers read ctl_tab (sample_ctl_kernel) and 0 otherwise: runs without controls find exactly
+        // the graphs they found before the field existed; the table's CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
-        typedef std::tuple<int, int, int, int, int> Key;
+        typedef std::tuple<int, int, int, int, int, int> Key;
         struct Entry {
             hipGraphExec_t exec;
             uint64_t used;
@@ -237,6 +240,7 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->unif_int.ensure((size_t)cb * ch * 2 * sizeof(float)));
     TS_TRY(w->dyn.ensure(3 * sizeof(uint64_t)));
     TS_TRY(w->clip_tab.ensure((size_t)cb * sizeof(int64_t)));
+    TS_TRY(w->ctl_tab.ensure((size_t)cb * sizeof(SampleCtl)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -272,6 +276,7 @@ struct RunCfg {
     // Bs, so "the first B clips" is the same memory in every chunk of the pass (0: a uniform call, the slabs are B apart)
     int Bs = 0;
     const int64_t *clip_table = nullptr;   // device (Bs,) Philox subsequence per clip, in place of clip0 + b
+    const SampleCtl *ctl = nullptr;        // device (slabB(),) sampling controls per clip slot (the Work's ctl_tab), or null: the sampler without controls
     int io_H = 0, io_row0 = 0;             // set by run_rows: row count / first row of the arrays the samplers address (staging or the caller's)
     int slabB() const { return Bs > 0 ? Bs : B; }
     void audio_from(ts_pixelcnn::Work *wk) { aeh = wk->AEH.f(), aeh1 = wk->AEH1.f(), av1c = wk->AV1C.f(), av1p = wk->AV1P.f(); }
@@ -620,7 +625,15 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         sp.copy_stride = (long)sH * 2 * p->V;
     }
     MiscScope ms(p->ctx, s);
-    TS_HIP(launch_sample(sp, s));
+    if (c.ctl) {
+        SampleCtlParams cp;
+        cp.s = sp;
+        cp.ctl = c.ctl;
+        cp.kept = nullptr;
+        TS_HIP(launch_sample_ctl(cp, s));
+    } else {
+        TS_HIP(launch_sample(sp, s));
+    }
     return 0;
 }
 
@@ -931,7 +944,7 @@ int ts_pixelcnn_graph_stats(ts_pixelcnn *p, void *stream, int B, int H, int mode
     if (!p) return fail("ts_pixelcnn_graph_stats: null argument");
     ts_pixelcnn::Work *w = p->works.find((hipStream_t)stream);
     if (!w) return fail("ts_pixelcnn_graph_stats: nothing was run on this stream");
-    auto jt = w->graph_stats.find(std::make_tuple(B, H, 0, mode, 0));
+    auto jt = w->graph_stats.find(std::make_tuple(B, H, 0, mode, 0, 0));
     if (jt == w->graph_stats.end()) return fail("ts_pixelcnn_graph_stats: no captured graph for this shape");
     if (launches) *launches = jt->second.first;
     if (flops) *flops = jt->second.second;
@@ -941,6 +954,46 @@ int ts_pixelcnn_graph_stats(ts_pixelcnn *p, void *stream, int B, int H, int mode
 }  // extern "C"
 
 namespace {
+
+// ---- sampling controls (talkshow_hip.h: ts_sampling) ------------------------------------------------------------------------------------
+// the rules of ts_sampling_check on one record; 0 or the message's tail
+const char *ctl_fault(const ts_sampling &r) {
+    if (!(r.temperature > 0.0f) || !std::isfinite(r.temperature)) return "temperature must be finite and > 0";
+    if (!std::isfinite(1.0f / r.temperature)) return "1 / temperature overflows fp32";
+    if (!(r.top_p > 0.0f) || !(r.top_p <= 1.0f)) return "top_p must be in (0, 1]";
+    if (r.top_k < 0) return "top_k must be >= 0 (0 or >= V: off)";
+    if (r.reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+int ctl_check(const ts_sampling *ctl, int n, int V, const char *who) {
+    if (!ctl || n < 1 || V < 1) return fail(std::string(who) + ": bad argument");
+    if (V > SAMPLE_CTL_MAX_V)
+        return fail(std::string(who) + ": sampling controls support vocabularies of at most " + std::to_string(SAMPLE_CTL_MAX_V) + " classes, got V = " + std::to_string(V));
+    for (int b = 0; b < n; ++b)
+        if (const char *m = ctl_fault(ctl[b])) return fail(std::string(who) + ": sampling record of clip " + std::to_string(b) + ": " + m);
+    return 0;
+}
+// validated host table -> the B device records of a pass (n_ctl = 1: one record for all clips); 1 / temperature is computed HERE, once, in fp32
+int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const char *who, std::vector<SampleCtl> &tab) {
+    if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
+        return fail(std::string(who) + ": sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
+    if (n_ctl != 1 && n_ctl != B) return fail(std::string(who) + ": n_ctl must be 1 or B");
+    TS_TRY(ctl_check(ctl, n_ctl, V, who));
+    tab.resize(B);
+    for (int b = 0; b < B; ++b) {
+        const ts_sampling &r = ctl[n_ctl == 1 ? 0 : b];
+        tab[b] = SampleCtl{1.0f / r.temperature, r.top_p, r.top_k, 0};
+    }
+    return 0;
+}
+// The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
+// synchronises, and any number of calls — each with its own table — may be queued behind each other.
+int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
+    static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
+    MiscScope ms(ctx, s);
+    TS_HIP(launch_put_words(w->ctl_tab.i(), reinterpret_cast<const int *>(tab.data()), (long)tab.size() * 4, s));
+    return 0;
+}
 
 // audio conditioning of `rows` code rows per clip: AE = embedding_aud(aud); AEV / AEH = fusion_{v,h}[:, D:] . AE + bias;
 // AEH1 = layer 1's horiz_stack applied to AEH (gated_pixelcnn_v2.py:137-144) — four conv_gemm launches for all rows at once
@@ -1047,7 +1100,7 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
 // compact chunk buffers its graph reads.  Bit-identical to the whole-call graph (same launches, same order, same rings: only the
 // look-ahead partial sums of rows past the end are computed and never read).
 int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
-                int64_t *codes, hipStream_t s) {
+                int64_t *codes, const SampleCtl *ctl, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     for (int r0 = 0; r0 < H; r0 += CHUNK_ROWS) {
@@ -1057,6 +1110,7 @@ int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, co
         c.aeh = w->cAEH.f(), c.aeh1 = w->cAEH1.f(), c.av1c = w->cAV1C.f(), c.av1p = w->cAV1P.f();
         c.out_H = H;
         c.out_row0 = r0;
+        c.ctl = ctl;
         struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
             {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
         for (auto &m : rows)
@@ -1064,7 +1118,7 @@ int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, co
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H * m.width * f,
                                         (size_t)Hc * m.width * f, B, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode, 0), uniforms, codes, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode, 0, ctl ? 1 : 0), uniforms, codes, s));
     }
     return 0;
 }
@@ -1103,7 +1157,7 @@ int mixed_plan(const int *hrows, int B, int max_counts, std::vector<int> &active
 constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
-              uint64_t seed, int64_t *codes, bool graph, hipStream_t s) {
+              uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1117,6 +1171,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
         c.out_row0 = r0;
         c.Bs = B;
         c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
+        c.ctl = ctl;   // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
         struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
             {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
         for (auto &m : rows)
@@ -1124,7 +1179,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B), uniforms, codes, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, ctl ? 1 : 0), uniforms, codes, s));
     }
     return 0;
 }
@@ -1146,9 +1201,47 @@ int ts_debug_mixed_plan(const int32_t *hrows, int B, int max_counts, int32_t *ac
     return grid;
 }
 
-int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
-                               int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
-                               int64_t *codes, void *stream) {
+int ts_sampling_check(const ts_sampling *ctl_host, int n, int V) { return ctl_check(ctl_host, n, V, "ts_sampling_check"); }
+
+// the sampler with controls on given logits (ts_op_sample / ts_op_sample_philox with a table; kernel-level tests call it)
+int ts_op_sample_ctl(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                     uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, uint8_t *kept, void *stream) {
+    if (!ctx || !logits || !idx) return fail("ts_op_sample_ctl: null argument");
+    if (B < 1 || V < 1) return fail("ts_op_sample_ctl: bad shape");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_op_sample_ctl: uniforms required");
+    std::vector<SampleCtl> tab;
+    if (!ctl_host) return fail("ts_op_sample_ctl: a table is required (ts_op_sample / ts_op_sample_philox are the entries without one)");
+    TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, "ts_op_sample_ctl", tab));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tok, dtab;
+    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
+    TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
+    TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
+    SampleCtlParams cp;
+    std::memset(&cp, 0, sizeof(cp));
+    cp.s.logits = logits;
+    cp.s.B = B;
+    cp.s.V = V;
+    cp.s.mode = mode;
+    cp.s.uniforms = uniforms;
+    cp.s.u_stride = 1;
+    cp.s.seed = seed;
+    cp.s.clip_index0 = clip_index0;
+    cp.s.position = position;
+    cp.s.tok32 = tok.i();
+    cp.s.tok_stride = 1;
+    cp.s.codes = idx;
+    cp.s.code_stride = 1;
+    cp.ctl = static_cast<const SampleCtl *>(dtab.p);
+    cp.kept = kept;
+    TS_HIP(launch_sample_ctl(cp, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                   int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                   int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
     if (!p || !label || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail("ts_pixelcnn_generate_mixed: bad mode");
@@ -1161,10 +1254,13 @@ int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float
         hrows[b] = lens_host[b] >> 2;
         if (hrows[b] > H_max) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " has more code rows than H_max");
     }
+    std::vector<SampleCtl> tab;
+    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
     hipStream_t s = (hipStream_t)stream;
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));
+    if (ctl_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
     TS_TRY(audio_terms(p, w, aud, B, H_max, s));
     TS_TRY(class_rows(p, w, label, B, s));
     {   // the clips' Philox subsequences, in a Work buffer (what the captured samplers read): the caller's table, or 0 .. B-1
@@ -1173,29 +1269,40 @@ int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float
         else TS_HIP(launch_iota_i64(static_cast<int64_t *>(w->clip_tab.p), B, 0, s));
     }
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, s));
+    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     return 0;
 }
 
-int ts_pixelcnn_generate(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
-                         const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
-                         const int64_t *pre_codes, const float *pre_aud, int H0, void *stream) {
+int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                               int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                               int64_t *codes, void *stream) {
+    return ts_pixelcnn_generate_mixed_ctl(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, nullptr, 0, stream);
+}
+
+int ts_pixelcnn_generate_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
+                             const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
+                             const int64_t *pre_codes, const float *pre_aud, int H0, const ts_sampling *ctl_host, int n_ctl, void *stream) {
     if (!p || !label || !aud || !codes) return fail("ts_pixelcnn_generate: null argument");
     if (B < 1 || H < 1 || H0 < 0) return fail("ts_pixelcnn_generate: bad shape");
     if (mode < 0 || mode > TS_TEACHER_FORCED) return fail("ts_pixelcnn_generate: bad mode");
     if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_pixelcnn_generate: uniforms required");
     if (H0 > 0 && (!pre_codes || !pre_aud)) return fail("ts_pixelcnn_generate: prefix pointers required");
+    std::vector<SampleCtl> tab;
+    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_ctl", tab));   // before anything is launched
     hipStream_t s = (hipStream_t)stream;
     ts_ctx *ctx = p->ctx;
     const int Htot = H0 + H, AD = p->AD;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, Htot));
+    if (ctl_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
+    const SampleCtl *ctl = ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr;
 
     // eager launches remain for the instrumented / logits-returning / teacher-forced paths
     const bool graph = p->use_graph && !ctx->prof.on && !logits && mode != TS_TEACHER_FORCED;
     RunCfg c = one_shot_cfg(B, H, H0, mode, uniforms, seed, clip0, codes, logits, w);
+    c.ctl = ctl;
 
     const float *aud_all = aud;
     if (H0 > 0) {
@@ -1221,13 +1328,19 @@ int ts_pixelcnn_generate(ts_pixelcnn *p, const int64_t *label, const float *aud,
                                     (size_t)H * 2 * e, B, hipMemcpyDeviceToDevice, s));
         TS_HIP(launch_i64_to_i32(tf, w->tok32.i(), (long)B * Htot * 2, s));
     }
-    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0);
+    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0, ctl ? 1 : 0);
     // A shape without a whole-call graph runs as chunk graphs (two or three small captures that serve every clip length) until it is
     // hot (Work::hot: pinned by ts_pixelcnn_prepare, or its third sighting among the last 16 one-shot calls of this stream); then it gets
     // its own whole-call graph (one replay per call: the serving loops, bench.py).  The cache is bounded either way.
     if (graph && H0 == 0 && H > CHUNK_ROWS && !w->graphs.count(key) && !w->hot(key))
-        return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, s);
+        return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, ctl, s);
     return run_rows(p, c, 0, Htot, graph, key, uniforms, codes, s);
+}
+
+int ts_pixelcnn_generate(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
+                         const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
+                         const int64_t *pre_codes, const float *pre_aud, int H0, void *stream) {
+    return ts_pixelcnn_generate_ctl(p, label, aud, B, H, mode, uniforms, seed, clip0, codes, logits, pre_codes, pre_aud, H0, nullptr, 0, stream);
 }
 
 // Captures (without running anything) the whole-call graph of a one-shot shape on `stream` and pins it: the first real call of that
@@ -1242,7 +1355,7 @@ int ts_pixelcnn_prepare(ts_pixelcnn *p, int B, int H, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H));
-    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, 0, mode, 0);
+    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, 0, mode, 0, 0);
     if (!w->pinned.count(key) && w->pinned.size() >= ts_pixelcnn::Work::PIN_CAP) return fail("ts_pixelcnn_prepare: too many pinned shapes on this stream");
     RunCfg c = one_shot_cfg(B, H, 0, mode, nullptr, 0, 0, nullptr, nullptr, w);
     TS_TRY(run_rows(p, c, 0, H, true, key, nullptr, nullptr, s, /*capture_only=*/true));
@@ -1296,7 +1409,7 @@ int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, in
     // in the 4-row rings) and the same set of existing rows above (rows 0..2 have fewer): key on that, not on r0
     const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0), uniforms, codes, s));
+    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0, 0), uniforms, codes, s));
     st->rows += Hc;
     return 0;
 }

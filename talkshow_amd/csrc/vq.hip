@@ -658,4 +658,326 @@ hipError_t launch_sample(const SampleParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// sampler with per-clip controls (temperature, top-k, top-p): the rule is stated in talkshow_hip.h (ts_sampling, steps 1-5) and restated
+// in talkshow_amd/sampling.py.  A kernel of its own: sample_kernel above keeps its code, and a pass without controls its launches.
+//
+// Same launch shape (one workgroup of 256 threads per clip, thread t owns the contiguous chunk [t*ceil(V/256), ...)); at V = 2048 the 8
+// logits of a thread, their order keys and their quantised weights stay in registers.  The kept set is a PREFIX of the ranking (logit
+// descending, ties by index ascending), so it is found by radix select instead of a sort:
+//   key(l)   the logit's bits mapped to an unsigned integer of the same order (-0 counts as +0);
+//   q(w)     floor(w * 2^31), the weight as an integer: integer sums do not depend on the order they are taken in, so the LDS atomics
+//            below are deterministic (no floating-point atomics anywhere);
+//   a level  256-bin histogram of the next 8 key bits over the tokens that match the bits chosen so far; a bin holds count and mass in
+//            ONE 64-bit word (count << 44 | mass: V * 2^31 < 2^44 for every V <= SAMPLE_CTL_MAX_V = 8191, which the launcher enforces), i.e. one LDS atomic per token and level.  After the barrier every
+//            WAVE scans all 256 bins by itself (lane l: bins 4l .. 4l+3, one wave suffix scan) — the chosen bin is then workgroup-uniform
+//            without a second barrier or an LDS round trip.
+// top-k descends by count to the key K* of rank k-1, top-p by mass to the lowest key whose mass-above is below the threshold; four levels
+// each, level 0 shared.  Ties at the two boundary keys are resolved in index order with one packed prefix count over the threads.
+// A neutral record (1, 1, 0) skips all of it (workgroup-uniform) and computes sample_kernel's bits.
+// ---------------------------------------------------------------------------------------------------------------
+typedef unsigned long long ctl_u64;
+constexpr int CTL_CNT_SHIFT = 44;   // a bin = count << 44 | mass; mass = sums of floor(w * 2^31)
+static_assert(((ctl_u64)SAMPLE_CTL_MAX_V << 31) < (1ull << CTL_CNT_SHIFT), "the mass of a full row must stay below the count field");
+static_assert(SAMPLE_CTL_MAX_V < 65536, "the packed tie counters hold 16 bits each");
+constexpr ctl_u64 CTL_MASS_MASK = (1ull << CTL_CNT_SHIFT) - 1;
+
+__device__ inline uint32_t ctl_key(float l) {
+    uint32_t b = __float_as_uint(l);
+    if (b == 0x80000000u) b = 0u;   // -0 ranks with +0
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ inline float ctl_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
+// step 1: subtract, multiply (two fp32 operations: a difference times a factor cannot contract), det_expf
+__device__ inline float ctl_weight(float l, float m, float inv_t) {
+#pragma clang fp contract(off)
+    const float d = l - m;
+    return det_expf(d * inv_t);
+}
+__device__ inline uint32_t ctl_quant(float w) { return (uint32_t)(w * 2147483648.0f); }   // w in [0, 1]: the product is exact, the cast truncates
+
+// packed sum of all 256 bins (every lane gets it)
+__device__ inline ctl_u64 ctl_hist_total(const ctl_u64 *h, int lane) {
+    ctl_u64 s = h[4 * lane] + h[4 * lane + 1] + h[4 * lane + 2] + h[4 * lane + 3];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+// One level of a descent, computed by every wave for itself.  acc = packed (count, mass) of the tokens ABOVE the bins of this level.
+//   by count: the bin b with  count above b < target <= count above b + count(b)
+//   by mass : the lowest non-empty bin b with  mass above b < target
+// Returns b (-1 if none: malformed rows only) and adds the bins above b to acc.
+__device__ inline int ctl_pick_bin(const ctl_u64 *h, int lane, bool by_mass, ctl_u64 target, ctl_u64 &acc) {
+    ctl_u64 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = h[4 * lane + j];
+    const ctl_u64 own = v[0] + v[1] + v[2] + v[3];
+    ctl_u64 suf = own;   // inclusive suffix sum over the lanes
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const ctl_u64 o = __shfl_down(suf, off);
+        if (lane + off < 64) suf += o;
+    }
+    ctl_u64 above = suf - own + acc;
+    int pick = -1;
+    ctl_u64 pick_above = 0;
+#pragma unroll
+    for (int j = 3; j >= 0; --j) {
+        const ctl_u64 cnt = v[j] >> CTL_CNT_SHIFT;
+        const bool ok = by_mass ? (cnt > 0 && (above & CTL_MASS_MASK) < target)
+                                : ((above >> CTL_CNT_SHIFT) < target && target <= (above >> CTL_CNT_SHIFT) + cnt);
+        if (ok) { pick = 4 * lane + j; pick_above = above; }   // walking down: the lowest qualifying bin of the lane stays
+        above += v[j];
+    }
+    const ctl_u64 vote = __ballot(pick >= 0);
+    const int src = vote ? __ffsll(vote) - 1 : 0;             // lowest lane = lowest bin
+    acc = __shfl(pick_above, src);
+    return __shfl(pick, src);
+}
+
+// what a token needs to decide whether the filters keep it (workgroup-uniform except the two tie counters' start values)
+struct CtlSel {
+    bool need_k, need_p, p_top;   // p_top: no token ranks above key Kp (its first tie is rank 0, always kept)
+    uint32_t Kk, Kp;              // boundary keys of top-k / top-p
+    int ntie_k;                   // ties at Kk that top-k keeps (lowest indices first)
+    ctl_u64 mgt_p, q_p, Tq;       // mass above Kp, quantised weight of a token at Kp, threshold ceil(p * mass kept by top-k)
+};
+// tokens are visited in index order; jk / jp count the ties met so far at the two boundary keys (start: the ties owned by lower threads)
+__device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) {
+    bool ok = true;
+    if (S.need_k) {
+        if (ky < S.Kk) ok = false;
+        else if (ky == S.Kk) ok = jk++ < S.ntie_k;
+    }
+    if (S.need_p) {
+        if (ky < S.Kp) ok = false;
+        else if (ky == S.Kp) {
+            const int j = jp++;
+            ok = ok && ((S.p_top && j == 0) || S.mgt_p + (ctl_u64)j * S.q_p < S.Tq);
+        }
+    }
+    return ok;
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams cp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];   // levels 0-3 of the top-k descent (level 0 shared), 1-3 of the top-p descent
+    const SampleParams &p = cp.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+
+    const int chunk = (p.V + 255) / 256;
+    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
+    const int n = FAST ? 8 : max(v1 - v0, 0);   // FAST: V = 2048, every thread owns 8 logits, held in registers from two 16-byte loads
+    float x[8];
+    if constexpr (FAST) {
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
+    }
+    auto logit = [&](int k) -> float {
+        if constexpr (FAST) return x[k];
+        else return lg[v0 + k];
+    };
+    if (p.logits_copy) {
+        float *dst = p.logits_copy + (long)b * p.copy_stride;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) dst[v0 + k] = logit(k);
+    }
+
+    const SampleCtl rec = cp.ctl[b];
+    CtlSel S;
+    S.need_k = rec.top_k >= 1 && rec.top_k < p.V;
+    S.need_p = rec.top_p < 1.0f;
+    const bool sel = S.need_k || S.need_p;   // workgroup-uniform: a neutral record (and a temperature alone) goes straight to the draw
+    if (sel) {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) hist[i][tid] = 0;
+    }
+
+    // ---- max / argmax as in sample_kernel; ties -> lowest index ----
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll 8
+    for (int k = 0; k < n; ++k) {
+        const float t = logit(k);
+        if (t > best) { best = t; bi = v0 + k; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
+    __syncthreads();
+    best = sf[0]; bi = si[0];
+    for (int w = 1; w < 4; ++w)
+        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
+    __syncthreads();
+
+    // the uniform: the same source as sample_kernel, so it does not depend on the record
+    float u;
+    if (p.mode == TS_SAMPLE_UNIFORMS) {
+        u = p.uniforms[(long)b * p.u_stride];
+    } else {
+        const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
+        const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+        uint32_t r;
+        philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
+                      (uint32_t)(seed >> 32), r);
+        u = (float)(r >> 8) * (1.0f / 16777216.0f);
+    }
+
+    const float inv_t = rec.inv_t;
+    auto weight = [&](int k) -> float { return ctl_weight(logit(k), best, inv_t); };
+
+    // ---- steps 2-4: the kept set ----
+    uint32_t key[8], q[8];
+    auto key_of = [&](int k) -> uint32_t {
+        if constexpr (FAST) return key[k];
+        else return ctl_key(lg[v0 + k]);
+    };
+    auto q_of = [&](int k) -> uint32_t {
+        if constexpr (FAST) return q[k];
+        else return ctl_quant(weight(k));
+    };
+    int jk0 = 0, jp0 = 0;
+    if (sel) {
+        if constexpr (FAST) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { key[k] = ctl_key(x[k]); q[k] = ctl_quant(weight(k)); }
+        }
+        // level lv of a descent: the tokens whose upper 8 lv key bits equal `prefix`, binned by the next 8
+        auto fill = [&](ctl_u64 *h, int lv, uint32_t prefix) {
+#pragma unroll 8
+            for (int k = 0; k < n; ++k) {
+                const uint32_t ky = key_of(k);
+                if (lv == 0 || (ky >> (32 - 8 * lv)) == prefix)
+                    atomicAdd(&h[(ky >> (24 - 8 * lv)) & 255u], (1ull << CTL_CNT_SHIFT) | (ctl_u64)q_of(k));
+            }
+            __syncthreads();
+        };
+        fill(hist[0], 0, 0u);
+        ctl_u64 Qk;   // quantised mass of the tokens top-k keeps
+        if (S.need_k) {
+            uint32_t prefix = 0;
+            ctl_u64 acc = 0;
+            for (int lv = 0; lv < 4; ++lv) {
+                if (lv > 0) fill(hist[lv], lv, prefix);
+                prefix = (prefix << 8) | (uint32_t)(ctl_pick_bin(hist[lv], lane, false, (ctl_u64)rec.top_k, acc) & 255);
+            }
+            S.Kk = prefix;
+            S.ntie_k = rec.top_k - (int)(acc >> CTL_CNT_SHIFT);
+            Qk = (acc & CTL_MASS_MASK) + (ctl_u64)S.ntie_k * ctl_quant(ctl_weight(ctl_unkey(prefix), best, inv_t));   // equal logits, equal weights
+        } else {
+            S.Kk = 0;
+            S.ntie_k = 0;
+            Qk = ctl_hist_total(hist[0], lane) & CTL_MASS_MASK;
+        }
+        S.Kp = 0; S.p_top = false; S.mgt_p = S.q_p = S.Tq = 0;
+        if (S.need_p) {
+            S.Tq = (ctl_u64)ceil((double)rec.top_p * (double)Qk);   // M < p * Qk  <=>  M < ceil(p * Qk) for an integer M; one fp64 product
+            uint32_t prefix = 0;
+            ctl_u64 acc = 0;
+            for (int lv = 0; lv < 4; ++lv) {
+                ctl_u64 *h = lv == 0 ? hist[0] : hist[3 + lv];
+                if (lv > 0) fill(h, lv, prefix);
+                prefix = (prefix << 8) | (uint32_t)(ctl_pick_bin(h, lane, true, S.Tq, acc) & 255);
+            }
+            S.Kp = prefix;
+            S.mgt_p = acc & CTL_MASS_MASK;
+            S.p_top = (acc >> CTL_CNT_SHIFT) == 0;
+            S.q_p = ctl_quant(ctl_weight(ctl_unkey(prefix), best, inv_t));
+        }
+        // ties at the boundary keys owned by lower threads (= lower indices): one packed exclusive prefix count (both counts < 2^16)
+        uint32_t c = 0;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) {
+            const uint32_t ky = key_of(k);
+            c += (S.need_k && ky == S.Kk ? 1u : 0u) + (S.need_p && ky == S.Kp ? 65536u : 0u);
+        }
+        uint32_t inc = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(inc, off);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) s_tie[wave] = inc;
+        __syncthreads();
+        uint32_t ex = inc - c;
+        for (int w = 0; w < wave; ++w) ex += s_tie[w];
+        jk0 = (int)(ex & 0xffffu);
+        jp0 = (int)(ex >> 16);
+    }
+
+    // ---- step 5: sample_kernel's inverse CDF over w' = kept ? w : 0 (adding a zero changes no bit, so dropped tokens are skipped) ----
+    float s = 0.f;
+    int hi = -1;   // highest kept index of the chunk
+    {
+        int jk = jk0, jp = jp0;
+        unsigned char *kd = cp.kept ? cp.kept + (long)b * p.V : nullptr;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) {
+            const bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
+            if (kp) { s += weight(k); hi = v0 + k; }
+            if (kd) kd[v0 + k] = kp ? 1 : 0;
+        }
+    }
+    sf[tid + 1] = s;
+    si[tid] = hi;
+    __syncthreads();
+    if (tid == 0) {
+        float c = 0.f;
+        int last = 0;
+        sf[0] = 0.f;
+        for (int t = 1; t <= 256; ++t) {
+            c += sf[t]; sf[t] = c;
+            if (si[t - 1] >= 0) last = si[t - 1];
+        }
+        s_thr = u * c;
+        s_last = last;   // highest kept index of the row (rank 0 is always kept)
+    }
+    __syncthreads();
+    const float thr = s_thr;
+    const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
+    const int last = s_last;
+    __syncthreads();   // si[0] becomes the result below: every thread has read what it needs
+    if (mine) {
+        int res = -1;
+        float c = sf[tid];
+        int jk = jk0, jp = jp0;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) {
+            if (!sel || ctl_keep(S, key_of(k), jk, jp)) {
+                c += weight(k);
+                if (res < 0 && c > thr) res = v0 + k;   // the first crossing is latched
+            }
+        }
+        // no crossing: inside an owning chunk its highest kept token; with no running sum above u * total (u = 1 - 2^-24) the row's
+        if (res < 0) res = (thr < sf[tid + 1] && hi >= 0) ? hi : last;
+        si[0] = res;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int choice = si[0];
+        p.tok32[(long)b * p.tok_stride] = choice;
+        p.codes[(long)b * p.code_stride] = choice;
+    }
+}
+
+hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
+    if (!p.ctl || p.s.V < 1 || p.s.V > SAMPLE_CTL_MAX_V || (p.s.mode != TS_SAMPLE_UNIFORMS && p.s.mode != TS_SAMPLE_PHILOX)) return hipErrorInvalidValue;
+    const long ls = p.s.logit_stride ? p.s.logit_stride : (long)p.s.V;
+    const bool fast = p.s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s.logits) & 15) == 0;
+    if (fast) hipLaunchKernelGGL(sample_ctl_kernel<true>, dim3(p.s.B), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(sample_ctl_kernel<false>, dim3(p.s.B), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 }  // namespace ts

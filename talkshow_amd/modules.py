@@ -341,9 +341,13 @@ class GatedPixelCNN(NativeModule):
         (_lib.load().ts_pixelcnn_destroy if self.bh_model else _lib.load().ts_pixelcnn_v_destroy)(h)
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
-            want_logits=False, pre_codes=None, pre_aud=None, shape=None):
+            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
-        (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise."""
+        (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
+        (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
+        are the network's, before any control.  bh_model=False takes none."""
+        if sampling is not None and not self.bh_model:
+            raise NotImplementedError("sampling controls exist for the bh_model=True chain (ts_pixelcnn_generate_ctl), not for the single-stack form")
         dev = self._dev()
         W = 2
         if aud_rows is not None:
@@ -358,6 +362,8 @@ class GatedPixelCNN(NativeModule):
             W = int(shape[2]) if len(shape) == 3 else 2
         if self.bh_model and W != 2:
             raise NotImplementedError("bh_model grids have exactly 2 columns (body, hand)")
+        if sampling is not None:   # validated (ValueError names the clip) before any device work
+            ctl, n_ctl = _lib.sampling_table(sampling, B, self.input_dim, mode)
         if self.bh_model and aud_rows is None:
             aud_rows = torch.zeros((B, H, self.aud_dim), dtype=torch.float32, device=dev)
         label = _index_tensor(label, self.n_classes, "class label", dev)
@@ -385,10 +391,12 @@ class GatedPixelCNN(NativeModule):
                 self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, W, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0, _lib.stream_ptr()))
             return codes, logits
-        _lib.check(_lib.load().ts_pixelcnn_generate(
-            self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
-            int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0,
-            _lib.stream_ptr()))
+        args = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
+                int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0)
+        if sampling is None:
+            _lib.check(_lib.load().ts_pixelcnn_generate(*args, _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.load().ts_pixelcnn_generate_ctl(*args, ctl, n_ctl, _lib.stream_ptr()))
         return codes, logits
 
     def prepare(self, batch_size, rows, mode=_lib.TS_SAMPLE_GREEDY):
@@ -431,11 +439,11 @@ class GatedPixelCNN(NativeModule):
 
     # --- reference call shapes ---
     def generate(self, label, shape=(8, 8), batch_size=64, aud_feat=None, pre_latents=None, pre_audio=None,
-                 mode=None, seed=None, uniforms=None):
+                 mode=None, seed=None, uniforms=None, sampling=None):
         """`GatedPixelCNN.generate` (`gated_pixelcnn_v2.py:152-177`): aud_feat (B,aud_dim,H,2) -> codes (B,H,2).
 
         Default is stochastic like the reference (softmax + one multinomial draw per position), with Philox uniforms
-        seeded from torch's default generator; `mode=TS_SAMPLE_GREEDY` gives the argmax harness.
+        seeded from torch's default generator; `mode=TS_SAMPLE_GREEDY` gives the argmax harness.  `sampling`: as for `run`.
         """
         rows = self._audio_rows(aud_feat)
         pre_rows = self._audio_rows(pre_audio)
@@ -444,7 +452,7 @@ class GatedPixelCNN(NativeModule):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if mode == _lib.TS_SAMPLE_PHILOX else 0
         codes, _ = self.run(label, rows, mode=mode, uniforms=uniforms, seed=seed, pre_codes=pre_latents, pre_aud=pre_rows,
-                            shape=(batch_size, shape[0], shape[1]))
+                            shape=(batch_size, shape[0], shape[1]), sampling=sampling)
         return codes
 
     def __call__(self, x, label, aud=None):

@@ -139,7 +139,7 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
     return assemble_full(torch.cat(poses, 0), torch.cat(faces, 0), stand=stand)
 
 
-def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True):
+def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -152,7 +152,8 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     (`modules.upload`): nothing between taking the list and returning it synchronises or leaves the device (speaker ids handed over as a
     DEVICE tensor are range-checked once per tensor version, which reads them back; host ids are checked on the host).  A recording's rows are bit-identical to the route of uniform entries on the recording alone
     (`MFCC` -> `generate_batch`, `FaceGenerator.run_clips`, `assemble_full`), its Philox subsequence is `clip_index0` + its position in
-    the submitted list."""
+    the submitted list.  sampling: one sampling record (`_lib.sampling_record`) for all recordings or one per recording in submission order —
+    they follow the recordings through the sort (the body branch then runs `ts_body_pixel_infer_mixed_ctl`; the face generator takes none)."""
     import ctypes as C
 
     import numpy as np
@@ -184,6 +185,9 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if int(tab["mfcc_rows"].min()) < 4 or int(tab["n16"].min()) < 400 or int(tab["face_frames"].min()) < 1:
         raise ValueError("whole_body_clips: a recording is too short (4 MFCC rows, 400 samples at 16 kHz and one face frame are needed)")
     mode = _lib.TS_SAMPLE_PHILOX if mode is None else mode
+    if sampling is not None:   # validated before the first launch; sorted slot k holds the record of submitted recording order[k]
+        recs = _lib.sampling_records(sampling, B)
+        sampling = _lib.sampling_table([recs[i] for i in order], B, body.generator.input_dim, mode)
     dev = body.generator._dev()
     # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
     wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
@@ -199,7 +203,7 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if overlap:
         side.wait_stream(cur)
     with torch.cuda.stream(side):
-        _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev)
+        _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling)
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

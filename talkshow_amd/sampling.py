@@ -1,0 +1,118 @@
+"""Numpy twin of the sampler with per-clip controls (`csrc/vq.hip::sample_ctl_kernel`; the rule: `include/talkshow_hip.h`, ts_sampling,
+steps 1-5).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
+bit for bit, so tests compare indices and kept sets for equality.  A record is (temperature, top_p, top_k), `_lib.sampling_record`'s form.
+
+The kept set is written here from its DEFINITION (sort the row, cumulative integer masses in rank order); the kernel finds the same set by
+radix select.  Both use the same integers, and integer sums do not depend on the order they are taken in.
+"""
+import numpy as np
+
+F32 = np.float32
+NTHREADS = 256
+Q_SCALE = 2.0 ** 31      # q_v = floor(w_v * 2^31): the weight as an integer mass
+
+
+def det_expf(x):
+    """exp(x) for x <= 0 as the samplers compute it (`csrc/kernels.h::det_expf`): fp32 multiplies and adds only, one IEEE rounding each,
+    no fused multiply-add.  A copy of `oracle.talkshow_oracle.det_expf` (product code does not import the oracle);
+    tests/test_sampling_host.py pins the two to each other."""
+    x = np.asarray(x, F32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        xs = np.where(x < F32(-86.0), F32(0.0), x).astype(F32)            # the arguments that give 0 take no part below (-inf included)
+        n = np.rint(xs * F32(1.44269504088896341)).astype(F32)
+        r = (xs - n * F32(0.693145751953125)).astype(F32)
+        r = (r - n * F32(1.42860682030941723212e-6)).astype(F32)
+        q = np.full_like(r, F32(1.9875691500e-4))
+        for c in (1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1):
+            q = (q * r + F32(c)).astype(F32)
+        y = (q * (r * r) + r).astype(F32)
+        y = (y + F32(1.0)).astype(F32)
+        out = (y * np.ldexp(F32(1.0), np.maximum(n, -126).astype(np.int32)).astype(F32)).astype(F32)
+    return np.where(x < F32(-86.0), F32(0.0), out).astype(F32)
+
+
+def inv_temperature(temperature):
+    """1.0f / T as the host computes it once per record (fp32 division)."""
+    return F32(F32(1.0) / F32(temperature))
+
+
+def weights(row, temperature):
+    """Step 1: w_v = det_expf((l_v - max l) * inv_T), subtraction and multiplication as two fp32 operations."""
+    row = np.asarray(row, F32)
+    d = (row - row.max()).astype(F32)
+    with np.errstate(invalid="ignore"):
+        d = (d * inv_temperature(temperature)).astype(F32)
+    return det_expf(d)
+
+
+def ranking(row):
+    """Step 2: token indices by logit descending (-0 equal to +0), ties by index ascending."""
+    row = np.asarray(row, F32) + F32(0.0)
+    return np.lexsort((np.arange(row.size), -row.astype(np.float64)))     # last key first: -l ascending, then index ascending
+
+
+def keep_mask(logits, record):
+    """Steps 1-4 for ONE row: (V,) bool, True for the tokens the record keeps."""
+    temperature, top_p, top_k = record
+    row = np.asarray(logits, F32).reshape(-1)
+    V = row.size
+    order = ranking(row)
+    q = np.floor(weights(row, temperature).astype(np.float64) * Q_SCALE).astype(np.int64)[order]      # integer masses in rank order
+    n_k = int(top_k) if 1 <= int(top_k) < V else V                        # step 3
+    keep_rank = np.arange(V) < n_k
+    if F32(top_p) < F32(1.0):                                             # step 4
+        Q = int(q[:n_k].sum())
+        thr = int(np.ceil(np.float64(F32(top_p)) * np.float64(Q)))        # one fp64 product; M < p Q <=> M < ceil(p Q) for an integer M
+        M = np.concatenate([[0], np.cumsum(q)[:-1]])                      # mass of the ranks before each rank
+        keep_rank &= (np.arange(V) == 0) | (M < thr)
+    kept = np.zeros(V, bool)
+    kept[order[keep_rank]] = True
+    return kept
+
+
+def draw(row, u, temperature, kept):
+    """Step 5 for one row: the samplers' inverse CDF in index order over w' = kept ? w : 0 (256 contiguous chunks summed left to right,
+    chunk sums prefix-summed left to right, a left-to-right walk in the owning chunk), all in fp32."""
+    row = np.asarray(row, F32).reshape(-1)
+    V = row.size
+    chunk = (V + NTHREADS - 1) // NTHREADS
+    w = np.where(kept, weights(row, temperature), F32(0.0)).astype(F32)
+    pad = np.zeros(NTHREADS * chunk, F32)
+    pad[:V] = w
+    pad = pad.reshape(NTHREADS, chunk)
+    s = np.zeros(NTHREADS, F32)
+    for j in range(chunk):                                               # every chunk left to right (adding a zero changes no bit)
+        s = (s + pad[:, j]).astype(F32)
+    pre = np.concatenate([[F32(0.0)], np.add.accumulate(s, dtype=F32)]).astype(F32)
+    thr = F32(F32(u) * pre[NTHREADS])
+    owner = NTHREADS - 1
+    for t in range(NTHREADS):
+        if pre[t] <= thr and (thr < pre[t + 1] or t == NTHREADS - 1):
+            owner = t
+            break
+    v0, v1 = owner * chunk, min((owner + 1) * chunk, V)
+    kept_idx = np.flatnonzero(kept)
+    c = pre[owner]
+    for v in range(v0, v1):
+        if kept[v]:
+            c = F32(c + w[v])
+            if c > thr:
+                return int(v)
+    own = kept_idx[(kept_idx >= v0) & (kept_idx < v1)]
+    if thr < pre[owner + 1] and own.size:
+        return int(own[-1])                                              # no crossing inside the owning chunk: its highest kept token
+    return int(kept_idx[-1])                                             # no running sum above u * total: the row's highest kept token
+
+
+def sample_ctl(logits, u, records):
+    """Steps 1-5 for (B,V) rows: u (B,) uniforms, records = one record or B -> (idx (B,) int64, kept (B,V) bool)."""
+    logits = np.asarray(logits, F32)
+    B, V = logits.shape
+    if isinstance(records, tuple) and len(records) == 3 and not isinstance(records[0], (tuple, list)):
+        records = [records] * B
+    idx = np.zeros(B, np.int64)
+    kept = np.zeros((B, V), bool)
+    for b in range(B):
+        kept[b] = keep_mask(logits[b], records[b])
+        idx[b] = draw(logits[b], u[b], records[b][0], kept[b])
+    return idx, kept
