@@ -189,7 +189,9 @@ typedef struct ts_sampling {
  * synchronises, any number of calls may be queued — captures nothing.  BUDGET: a host that alternates passes with and without a table on
  * one stream shares the 16 chunk graphs (and the 8 whole-call graphs) kept per stream between the two kinds.
  * Out of scope: ts_pixelcnn_stream_* (and BodyStream), ts_pixelcnn_v_*, the face generator, repetition penalties or any control that
- * reads earlier codes. */
+ * reads earlier codes.  Log-probabilities (below) share the scope: the streaming sessions, ts_pixelcnn_v_* and the face generator return
+ * none, clips of different lengths are not SCORED in one pass, and scoring runs the rows one after the other as the decode does (given
+ * the codes, teacher-forced rows do not depend on each other and could run as large GEMMs: other work, with other bits). */
 /* Host only: the validation every _ctl entry applies before anything is launched.  n records for vocabulary V, 1 <= V <= 8191 (a larger V
  * is an error: see step 4); 0, or an error whose message names the clip: temperature not finite / <= 0 / with an infinite fp32 reciprocal, top_p outside (0, 1], top_k < 0, reserved != 0.
  * (The entries also refuse a table with TS_SAMPLE_GREEDY or TS_TEACHER_FORCED: per-clip greedy is top_k = 1.) */
@@ -200,6 +202,54 @@ int ts_pixelcnn_generate_ctl(ts_pixelcnn *pix, const int64_t *label_dev, const f
                              const float *uniforms_dev, uint64_t seed, int64_t clip_index0, int64_t *codes_dev, float *logits_dev,
                              const int64_t *pre_codes_dev, const float *pre_aud_dev, int H0, const ts_sampling *ctl_host, int n_ctl,
                              void *stream);
+
+/* ---- log-probabilities: how likely was that code? ---------------------------------------------------------------------------------------
+ * The sampler launch already holds the row maximum, the 256 chunk sums, their total and the chosen index; the _lp entries also return
+ *
+ *     logprob = (float)( (double)d_c - log((double)S) )          one fp64 log per position, one rounding to fp32
+ *
+ * for the chosen (greedy, drawn) or given (teacher forced) code c, where
+ *   m    the row maximum;
+ *   d_c  the fp32 value the sampler feeds to det_expf for c: l_c - m without controls; (l_c - m) * inv_T, two fp32 operations, with a record;
+ *   S    the fp32 total of the distribution the draw is made from, with the samplers' summation structure (256 contiguous chunks summed
+ *        left to right, then the chunk sums added left to right); with a record, the total over the kept weights w' of step 5.
+ * talkshow_amd/sampling.py::logprob restates it in numpy, operation for operation.  Consequences (tests/test_gpu_logprob_ops.py):
+ *   - it is the log-probability under the distribution the draw was made from: with temperature and filtering when there is a record, the
+ *     raw model distribution when there is no table, in greedy mode and in teacher-forced mode;
+ *   - a neutral record gives the bits of the path without a table;
+ *   - top_k = 1 gives exactly 0.0f (S = det_expf(0) = 1, d_c = 0; in a row whose maximum is attained by +0 and by -0 the zero may carry
+ *     either sign: it is the sign of l_c - m);
+ *   - a row whose other weights underflow gives 0.0f for the maximum and the finite d_c for any other code: d_c is used, never log(w_c);
+ *   - there are no clamps;
+ *   - the logit of c is picked up by the thread that owns index c; the code is never used as an address: a teacher-forced code outside
+ *     [0, V) yields NaN for that position and reads nothing out of bounds.
+ * It is a pure function of the clip's own logits row (and record): bit-identical alone or inside a mixed pass of any size, eager or replayed.
+ * Accuracy.  (a) Device against the numpy restatement: S and d_c are bit-equal; the two fp64 logs may differ in the last place, so the
+ * results are equal or adjacent fp32 values (the tests allow one fp32 spacing and no more).  (b) Restatement against an exact float64
+ * log-softmax of the fp32 logits, without a record (sampling.py::logprob_error_bound, asserted by tests/test_logprob_host.py):
+ *   |d_c| 2^-24 for the subtraction;  on S, relatively: (chunk - 1 + 255) 2^-24 for its fp32 additions (262 at V = 2048), det_expf's
+ *   relative error — at most 8.11e-8 = 1.36 * 2^-24 against float64 exp on 2^26 + 1 evenly spaced arguments of [-86, 0] (the bit-exact numpy
+ *   twin on a CPU; arguments in [-87, -86) give 0), bounded by 2^-23 in the tests — plus 86 * 2^-24 for the rounding of a weight's argument
+ *   and V e^-86 for the dropped weights;  |logprob| 2^-24 for the final rounding.  At V = 2048: 2.1e-5 + (|d_c| + |logprob|) 6e-8.
+ * Graphs: the sixth key field is a bit set, bit 0 = controls, bit 1 = log-probabilities.  Passes without either keep their keys, replay the
+ * graphs they had and issue the launches they always did; a pass with log-probabilities captures its own graphs once (the samplers write
+ * a staging buffer of the stream's work buffers, copied to logprob_dev behind the replay as the codes are) and a repeated one captures
+ * nothing.  Teacher forced WITH a log-probability output runs the horizontal stack (eager launches, as teacher forced always does);
+ * without one it stays the vertical-stack-only pass it was.
+ *
+ * ts_pixelcnn_generate_ctl's arguments plus logprob_dev (B,H,2) fp32: the prefix is allowed, the log-probabilities cover the H generated
+ * (teacher forced: given) rows only.  ctl_host may be NULL (no table); a table with TS_TEACHER_FORCED or TS_SAMPLE_GREEDY stays refused.
+ * logprob_dev == NULL: exactly ts_pixelcnn_generate_ctl. */
+int ts_pixelcnn_generate_lp(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, int B, int H, int mode,
+                            const float *uniforms_dev, uint64_t seed, int64_t clip_index0, int64_t *codes_dev, float *logits_dev,
+                            const int64_t *pre_codes_dev, const float *pre_aud_dev, int H0, const ts_sampling *ctl_host, int n_ctl,
+                            float *logprob_dev, void *stream);
+/* Per-clip fixed-order float64 sums of a pass's log-probabilities: logprob_dev (B,H,2) -> sums_dev (B,3) = {body column, hand column,
+ * body + hand}.  lens_dev: the table of the mixed pass that wrote them ((B,) int32 MFCC frames, H_b = lens[b] >> 2, capped at H), or NULL
+ * for H rows per clip; rows at or beyond H_b do not enter.  Two stages: lane t of 256 adds rows t, t + 256, ... of a column in ascending
+ * order, the 256 lane sums are added in ascending order; the third value is one addition of the first two.
+ * talkshow_amd/sampling.py::logprob_sums equals it bit for bit. */
+int ts_logprob_sums(ts_ctx *ctx, const float *logprob_dev, const int32_t *lens_dev, int B, int H, double *sums_dev, void *stream);
 
 /* GatedPixelCNN(input_dim, dim, n_layers, n_classes, audio, bh_model=False) — the single-stack form (gated_pixelcnn_v2.py:37-42,
  * 80-85,147-150): vertical kernels one column wide, out_v = horiz_resid(gate(vert_stack(x_v) + class)) [+ x_v], logits from x_v; the
@@ -338,6 +388,17 @@ int ts_body_pixel_infer_mixed_ctl(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqv
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
                                    const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
                                    const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl, void *stream);
+/* The two entries above plus logprob_dev (B,H_max,2) fp32 ("log-probabilities" above; H_max = T_max / 4): a clip's values are bit-identical
+ * to the clip run alone; rows at or beyond a clip's own H_b are written as 0.  ctl_host may be NULL.  The mixed entries stay sampling-only
+ * (no teacher forcing).  logprob_dev == NULL: exactly the _ctl entry. */
+int ts_body_pixel_infer_mixed_lp(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                 const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                 const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                 float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, void *stream);
+int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                  const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                  const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                  float *logprob_dev, void *stream);
 /* ts_vqvae_decode_pair with length-masked layers: latents (B,H) each, rows at or beyond lens[b] / 4 are not read (gathered as zero rows;
  * an index outside the codebook INSIDE a clip still gives NaNs); out_dev (B,4H,body_dim+hand_dim), rows at or beyond 4 (lens[b] / 4) = 0. */
 int ts_vqvae_decode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *lat_body_dev, const int64_t *lat_hand_dev,
@@ -382,6 +443,13 @@ int ts_op_sample_philox(ts_ctx *ctx, const float *logits_dev, int B, int V, uint
 int ts_op_sample_ctl(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
                      int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, uint8_t *kept_dev,
                      void *stream);
+/* One sampler launch with the log-probability of every row's code: ts_op_sample_ctl's arguments plus logprob_dev (B) fp32.  ctl_host may be
+ * NULL: then mode is any of the four (sample_lp_kernel), V is any size >= 1, kept_dev must be NULL, and for TS_TEACHER_FORCED idx_dev (B) is
+ * the INPUT: the given codes (left as they are; one outside [0, V) gives NaN).  logprob_dev == NULL: ts_op_sample_ctl with a table, the
+ * sampler of ts_op_sample / ts_op_sample_philox without. */
+int ts_op_sample_lp(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                    int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, uint8_t *kept_dev,
+                    float *logprob_dev, void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

@@ -96,7 +96,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         self.g_hand.decode_nlc(latents[..., 1].contiguous(), out=out, col0=self.each_dim[1])
         return out
 
-    def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None):
+    def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
+                       logprobs=False):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -105,13 +106,17 @@ class TrainWrapper(TrainWrapperBaseClass):
         sampling: one sampling record (`_lib.sampling_record`: temperature, top_p, top_k) for all clips, or one per clip.  WITH a record the
         batch goes through the mixed entry (`generate_clips`, `ts_body_pixel_infer_mixed_ctl`) with equal lengths — a clip's codes there
         equal this entry's, bit for bit, so a neutral record changes nothing but the route.  Without one: the uniform entry below, unchanged.
+        logprobs=True: a third return value, (B,H,2) float32, the log-probability of every code under the distribution it was drawn from
+        (`ts_body_pixel_infer_mixed_lp`: the route of `sampling`, with or without a record; codes and poses are those of the call without it).
         """
-        if sampling is not None:
+        if not (logprobs is None or isinstance(logprobs, bool)):
+            raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
+        if sampling is not None or logprobs:
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
-                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling)
+                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs))
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -137,7 +142,22 @@ class TrainWrapper(TrainWrapperBaseClass):
             _lib.dptr(codes), _lib.dptr(poses), _lib.stream_ptr()))
         return codes, poses
 
-    def generate_batches(self, mfccs, ids_list, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, sampling=None):
+    def score_batch(self, mfcc, ids, codes):
+        """Teacher-forced scoring of GIVEN codes: mfcc (B,T,64), ids (B,) or one for all, codes (B,T//4,2) int64 -> (logprobs (B,H,2)
+        float32, sums (B,3) float64): log p(code | earlier codes, audio, speaker) at every position under the model's raw distribution,
+        and per clip the fixed-order float64 sums {body column, hand column, both} — the negative of a clip's total is its NLL.  The
+        audio encoder and `GatedPixelCNN.score` (`ts_pixelcnn_generate_lp`, `ts_logprob_sums`): no logits are written anywhere."""
+        dev = self.generator._dev()
+        mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
+        if mfcc.dim() != 3:
+            raise ValueError(f"score_batch: mfcc must be (B, T, 64), got {tuple(mfcc.shape)}")
+        B, T, _ = mfcc.shape
+        _lib.score_codes_shape(tuple(getattr(codes, "shape", ())), B, T // 4)
+        ids = _index_tensor(ids, self.num_classes, 'speaker id', dev)
+        rows = self.audioencoder.forward_nlc(mfcc)
+        return self.generator.score(ids, rows, codes)
+
+    def generate_batches(self, mfccs, ids_list, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, sampling=None, logprobs=False):
         """Coalesced execution of several independent batches (the serving path): the batches' clips are stacked and
         the autoregressive chain runs ONCE over all of them, so a stage's weights are streamed once for all batches
         in flight instead of once per batch (a chain stage is latency-bound below ~64 clips).  Results are bit-identical
@@ -148,13 +168,14 @@ class TrainWrapper(TrainWrapperBaseClass):
         of the clips); each batch gets its results trimmed to its own H and 4 H, with the same bits and the same Philox subsequences.
         Batches of one T take the uniform path below, unchanged.  sampling: one sampling record for all clips or one per clip of the
         stacked batches, in list order; WITH a record the batches go through the mixed pass whatever their lengths (equal ones included):
-        a clip's codes there equal the uniform entry's.
+        a clip's codes there equal the uniform entry's.  logprobs=True: every batch's tuple gains its (B_i,H_i,2) log-probabilities, and
+        the batches take the mixed pass as with a record.
 
         mfccs: list of (B_i,T_i,64) device tensors, ids_list: list of (B_i,) -> list of (codes_i, poses_i) views."""
         dev = self.generator._dev()
         sizes = [int(m.shape[0]) for m in mfccs]
-        if len({int(m.shape[1]) for m in mfccs}) > 1 or sampling is not None:     # different lengths, or controls: one mixed pass
-            return self._generate_batches_mixed(mfccs, ids_list, sizes, mode, seed, clip_index0, sampling)
+        if len({int(m.shape[1]) for m in mfccs}) > 1 or sampling is not None or logprobs:     # different lengths, controls or log-probabilities: one mixed pass
+            return self._generate_batches_mixed(mfccs, ids_list, sizes, mode, seed, clip_index0, sampling, bool(logprobs))
         # nn.Embedding's IndexError per submitted batch, BEFORE stacking: host ids are checked on the host, a caller-owned device
         # tensor once per tensor version (modules._check_index_range) — the stacked tensor built below is new on every call, and
         # checking it would cost the serving path one blocking device -> host read per pass (ADVICE r3)
@@ -168,7 +189,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         codes, poses = self.generate_batch(mf, ids, mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True)
         return list(zip(codes.split(sizes, 0), poses.split(sizes, 0)))
 
-    def _generate_batches_mixed(self, mfccs, ids_list, sizes, mode, seed, clip_index0, sampling=None):
+    def _generate_batches_mixed(self, mfccs, ids_list, sizes, mode, seed, clip_index0, sampling=None, logprobs=False):
         from talkshow_amd.modules import _check_index_range
         dev = self.generator._dev()
         clips, ids = [], []
@@ -182,17 +203,18 @@ class TrainWrapper(TrainWrapperBaseClass):
                 raise ValueError(f"ids must hold 1 or B={b} speaker indices, got {i.numel()}")
             clips += list(m.unbind(0))
             ids.append(i)
-        codes, poses = self.generate_clips(clips, torch.cat(ids, 0), mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True,
-                                           _stacked=True, sampling=sampling)
+        res = self.generate_clips(clips, torch.cat(ids, 0), mode=mode, seed=seed, clip_index0=clip_index0, _ids_checked=True,
+                                  _stacked=True, sampling=sampling, logprobs=logprobs)
+        codes, poses = res[0], res[1]
         out, k = [], 0
         for m, b in zip(mfccs, sizes):          # per submitted batch, trimmed to that batch's own H and 4 H
             H = int(m.shape[1]) // 4
-            out.append((codes[k:k + b, :H], poses[k:k + b, :4 * H]))
+            out.append((codes[k:k + b, :H], poses[k:k + b, :4 * H]) + ((res[2][k:k + b, :H],) if logprobs else ()))
             k += b
         return out
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
-                       _ids_checked=False, _stacked=False, sampling=None):
+                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -203,7 +225,10 @@ class TrainWrapper(TrainWrapperBaseClass):
         regroups clips between passes keeps each clip's random stream).  uniforms: list of (H_b,2) per clip for TS_SAMPLE_UNIFORMS.
         sampling: one sampling record (`_lib.sampling_record`: temperature, top_p, top_k) for all clips, or a list of one per clip in
         SUBMISSION order; the records are carried through the length sort exactly as `clip_indices` are, and a clip's codes depend on its
-        own record only (`ts_body_pixel_infer_mixed_ctl`).  A bad record raises ValueError naming the clip, before anything is launched."""
+        own record only (`ts_body_pixel_infer_mixed_ctl`).  A bad record raises ValueError naming the clip, before anything is launched.
+        logprobs=True: every clip's tuple gains logprobs_b (H_b,2) float32 (`ts_body_pixel_infer_mixed_lp`), bit-identical to the clip alone."""
+        if not (logprobs is None or isinstance(logprobs, bool)):
+            raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
         B = len(mfcc_list)
         if B < 1:
@@ -261,12 +286,20 @@ class TrainWrapper(TrainWrapperBaseClass):
         args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
                 _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
-        if ctl is None:
+        lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
+        if lp is not None:
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_lp(*args, ctl, n_ctl, _lib.dptr(lp), _lib.stream_ptr()))
+        elif ctl is None:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
         else:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed_ctl(*args, ctl, n_ctl, _lib.stream_ptr()))
         inv_dev = torch.as_tensor(inverse, dtype=torch.int64, device=dev)
         codes, poses = codes.index_select(0, inv_dev), poses.index_select(0, inv_dev)     # back to submission order
+        if lp is not None:
+            lp = lp.index_select(0, inv_dev)
+            if _stacked:
+                return codes, poses, lp
+            return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)], lp[b, :lens[b] // 4]) for b in range(B)]
         if _stacked:
             return codes, poses
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]

@@ -102,6 +102,13 @@ SIGNATURES = {
     "ts_body_pixel_infer_mixed_ctl": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
                                            _vp]),
     "ts_pixelcnn_generate_mixed_ctl": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp]),
+    # the _ctl entries plus logprob_dev ahead of the stream
+    "ts_pixelcnn_generate_lp": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _sp, _i, _vp, _vp]),
+    "ts_op_sample_lp": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, _vp, _vp]),
+    "ts_body_pixel_infer_mixed_lp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                          _vp, _vp]),
+    "ts_pixelcnn_generate_mixed_lp": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp]),
+    "ts_logprob_sums": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -300,6 +307,34 @@ def sampling_table(sampling, n, V=2048, mode=None):
     if lib.ts_sampling_check(arr, n, int(V)) != 0:
         raise ValueError("libtalkshow_hip: " + lib.ts_last_error().decode())
     return arr, n
+
+
+def logprob_request(logprobs, shape, device=None):
+    """The `logprobs=` keyword of the decode entries: False / None -> None (no output, the entries without the suffix); True -> "new" (the
+    entry allocates a float32 tensor of `shape`, the codes' shape); a tensor -> that tensor, which must be float32, contiguous, of `shape`
+    and, where `device` is given, on it.  Anything else, or a wrong tensor, raises ValueError: pure host code, ahead of any launch."""
+    if logprobs is None or logprobs is False:
+        return None
+    if logprobs is True:
+        return "new"
+    dtype, tshape = getattr(logprobs, "dtype", None), getattr(logprobs, "shape", None)
+    if dtype is None or tshape is None or not hasattr(logprobs, "is_contiguous"):
+        raise ValueError(f"logprobs must be True, False or a float32 output tensor of shape {tuple(shape)}, got {logprobs!r}")
+    if "float32" not in str(dtype):
+        raise ValueError(f"logprobs output must be float32, got {dtype}")
+    if tuple(tshape) != tuple(shape):
+        raise ValueError(f"logprobs output must have the codes' shape {tuple(shape)}, got {tuple(tshape)}")
+    if not logprobs.is_contiguous():
+        raise ValueError("logprobs output must be contiguous")
+    if device is not None and str(logprobs.device).split(":")[0] != str(device).split(":")[0]:
+        raise ValueError(f"logprobs output must live on {device}, got {logprobs.device}")
+    return logprobs
+
+
+def score_codes_shape(codes_shape, B, H):
+    """`score` / `score_batch` take the codes of the pass they score: (B, H, 2).  ValueError otherwise; pure host code."""
+    if tuple(codes_shape) != (int(B), int(H), 2):
+        raise ValueError(f"score: codes must have shape (B, H, 2) = ({int(B)}, {int(H)}, 2), got {tuple(codes_shape)}")
 
 
 def pack_state_dict(sd):

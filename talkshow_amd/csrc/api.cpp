@@ -197,6 +197,15 @@ int ts_body_pixel_infer_mixed_ctl(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb
                                   const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
                                   uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                   void *stream) {
+    return ts_body_pixel_infer_mixed_lp(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                        ctl_host, n_ctl, nullptr, stream);
+}
+
+// the same pass with a log-probability output (B, T_max / 4, 2); logprob == NULL: exactly the entry above
+int ts_body_pixel_infer_mixed_lp(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                 const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                 uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                 float *logprob, void *stream) {
     if (!ae || !pix || !vb || !vh || !mfcc || !ids || !lens_host || !lens_dev || !codes || !poses)
         return fail("ts_body_pixel_infer_mixed: null argument");
     if (B < 1) return fail("ts_body_pixel_infer_mixed: bad shape");
@@ -219,7 +228,8 @@ int ts_body_pixel_infer_mixed_ctl(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb
         if (ts_sampling_check(ctl_host, n_ctl, 1) != 0) return 1;   // the records; the vocabulary is checked by ts_pixelcnn_generate_mixed_ctl
     }
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
-    TS_TRY(ts_pixelcnn_generate_mixed_ctl(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl, s));
+    TS_TRY(ts_pixelcnn_generate_mixed_lp(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                         logprob, s));
     for (int k = 0; k < 2; ++k) {
         TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
         TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),

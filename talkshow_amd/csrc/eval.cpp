@@ -72,4 +72,17 @@ int ts_eval_diversity(ts_ctx *ctx, const float *kps, int bs, int64_t L, double *
     return 0;
 }
 
+// Per-clip fixed-order fp64 sums of a decode's log-probabilities (vq.hip: launch_logprob_sums; talkshow_amd/sampling.py::logprob_sums is the
+// same additions in numpy): logprob (B,H,2) -> sums (B,3) = {body, hand, body + hand} over each clip's own rows.
+int ts_logprob_sums(ts_ctx *ctx, const float *logprob, const int32_t *lens_dev, int B, int H, double *sums, void *stream) {
+    if (!ctx || !logprob || !sums) return fail("ts_logprob_sums: null argument");
+    if (B < 1 || H < 1) return fail("ts_logprob_sums: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    EvalWork &w = eval_work(s);
+    TS_TRY(w.scratch.ensure((size_t)B * LOGPROB_SUM_LANES * 2 * sizeof(double)));
+    MiscScope ms(ctx, s);
+    TS_HIP(launch_logprob_sums(logprob, B, H, lens_dev, static_cast<double *>(w.scratch.p), sums, s));
+    return 0;
+}
+
 }  // extern "C"

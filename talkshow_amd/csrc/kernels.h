@@ -426,11 +426,30 @@ struct SampleCtlParams {
     SampleParams s;            // mode TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX
     const SampleCtl *ctl;      // record of clip b at ctl[b]
     unsigned char *kept;       // optional (B,V): 1 for the tokens the filters kept
+    float *logprob;            // optional: the log-probability of the drawn code (talkshow_hip.h, "log-probabilities") at logprob[b * lp_stride]
+    long lp_stride;
 };
 // a histogram bin of the kernel holds count << 44 | mass with mass <= V * 2^31: V * 2^31 < 2^44 bounds the vocabulary (the tie counters' 16 bits
 // and the count field hold more); launch_sample_ctl and the host checks refuse anything above
 constexpr int SAMPLE_CTL_MAX_V = 8191;
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream);
+
+// The sampler without controls plus the log-probability of the chosen (greedy, drawn) or given (teacher forced: s.codes is read) code:
+// logprob[b * lp_stride] = (float)((double)(l_c - max) - log((double)S)), S the sampler's own fp32 total (talkshow_hip.h).  A sibling of
+// SampleParams again: sample_kernel keeps its arguments and its code.
+struct SampleLpParams {
+    SampleParams s;            // any mode
+    float *logprob;
+    long lp_stride;
+};
+hipError_t launch_sample_lp(const SampleLpParams &p, hipStream_t stream);
+// logprob (B,H,2) rows at or beyond a clip's own H_b = lens[b] >> 2 become 0 (mixed passes; beside launch_mask_codes)
+hipError_t launch_mask_logprob(float *logprob, int B, int H, const int *lens, hipStream_t stream);
+// Per-clip fixed-order fp64 sums of logprob (B,H,2): out[b] = {body column, hand column, body + hand} over rows r < H_b (lens == nullptr:
+// H_b = H, else min(H, lens[b] >> 2)).  Two stages: part[b][t] = the sums of rows t, t + 256, ... in ascending order (t < 256), then the 256
+// partials added in ascending order.  scratch: B * 256 * 2 doubles.
+constexpr int LOGPROB_SUM_LANES = 256;
+hipError_t launch_logprob_sums(const float *logprob, int B, int H, const int *lens, double *scratch, double *out, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // face generator kernels (face.hip)

@@ -87,13 +87,15 @@ struct ts_pixelcnn {
         DevBuf cAEH, cAEH1, cAV1C, cAV1P;  // the audio terms of ONE chunk of rows, compact (chunked one-shot calls: see run_chunked)
         DevBuf clip_tab;                   // mixed passes: the Philox subsequence of every clip (int64), read by the captured samplers
         DevBuf ctl_tab;                    // passes with sampling controls: one SampleCtl per clip SLOT of the pass, written in stream order ahead of it
+        DevBuf lp_int;                     // runs with a log-probability output: what the captured samplers write, (B,rows,2) fp32 beside codes_int
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
         // (Br, Hc, -(1 + phase), mode, Bs) = Hc rows of a MIXED pass of Bs clips for its first Br clips: the per-clip slabs of the work
         // buffers are Bs clips apart whatever Br is, so the stride is part of what a captured graph is valid for (0: the slabs are B apart).
-        // The sixth field is 1 for a run whose samplers read ctl_tab (sample_ctl_kernel) and 0 otherwise: runs without controls find exactly
-        // the graphs they found before the field existed; the table's CONTENT is not part of the key (a replay reads what the call wrote).
+        // The sixth field is a bit set: bit 0 for a run whose samplers read ctl_tab (sample_ctl_kernel), bit 1 for a run whose samplers write
+        // log-probabilities into lp_int; 0 otherwise: runs with neither find exactly the graphs they found before the field existed; the
+        // table's CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
         struct Entry {
@@ -241,6 +243,7 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->dyn.ensure(3 * sizeof(uint64_t)));
     TS_TRY(w->clip_tab.ensure((size_t)cb * sizeof(int64_t)));
     TS_TRY(w->ctl_tab.ensure((size_t)cb * sizeof(SampleCtl)));
+    TS_TRY(w->lp_int.ensure((size_t)cb * ch * 2 * sizeof(float)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -277,6 +280,7 @@ struct RunCfg {
     int Bs = 0;
     const int64_t *clip_table = nullptr;   // device (Bs,) Philox subsequence per clip, in place of clip0 + b
     const SampleCtl *ctl = nullptr;        // device (slabB(),) sampling controls per clip slot (the Work's ctl_tab), or null: the sampler without controls
+    float *logprob = nullptr;              // set by run_rows: (B,io_H,2) log-probabilities beside `codes` (staging or the caller's), or null
     int io_H = 0, io_row0 = 0;             // set by run_rows: row count / first row of the arrays the samplers address (staging or the caller's)
     int slabB() const { return Bs > 0 ? Bs : B; }
     void audio_from(ts_pixelcnn::Work *wk) { aeh = wk->AEH.f(), aeh1 = wk->AEH1.f(), av1c = wk->AV1C.f(), av1p = wk->AV1P.f(); }
@@ -625,12 +629,21 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         sp.copy_stride = (long)sH * 2 * p->V;
     }
     MiscScope ms(p->ctx, s);
+    float *lp = c.logprob ? c.logprob + (size_t)ro * 2 + j : nullptr;
     if (c.ctl) {
         SampleCtlParams cp;
         cp.s = sp;
         cp.ctl = c.ctl;
         cp.kept = nullptr;
+        cp.logprob = lp;
+        cp.lp_stride = (long)sH * 2;
         TS_HIP(launch_sample_ctl(cp, s));
+    } else if (lp) {
+        SampleLpParams q;
+        q.s = sp;
+        q.logprob = lp;
+        q.lp_stride = (long)sH * 2;
+        TS_HIP(launch_sample_lp(q, s));
     } else {
         TS_HIP(launch_sample(sp, s));
     }
@@ -988,6 +1001,8 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 }
 // The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
+// the sixth field of a graph key: which sampler the run's launches are (Work::Key)
+inline int sampler_bits(const SampleCtl *ctl, const float *logprob) { return (ctl ? 1 : 0) | (logprob ? 2 : 0); }
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
     MiscScope ms(ctx, s);
@@ -1032,13 +1047,14 @@ int class_rows(ts_pixelcnn *p, ts_pixelcnn::Work *w, const int64_t *label, int B
 // staging buffer (every pointer inside a captured kernel is a Work buffer, so a graph is valid for any caller pointers);
 // the caller's arrays hold c.out_H rows per clip, of which this run covers rows c.out_row0 .. c.out_row0 + c.H - 1.
 int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const ts_pixelcnn::Work::Key &key,
-             const float *uniforms, int64_t *codes, hipStream_t s, bool capture_only = false) {
+             const float *uniforms, int64_t *codes, float *logprob, hipStream_t s, bool capture_only = false) {
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = c.w;
     const int out_H = c.out_H > 0 ? c.out_H : c.H;
     auto row_loop = [&](hipStream_t st) -> int {
         for (int r = r_begin; r < r_end; ++r) {
-            const bool need_h = r >= c.out_r0 && !(c.mode == TS_TEACHER_FORCED && !c.logits);   // prefix rows only feed the row cache
+            // prefix rows only feed the row cache; so do teacher-forced rows that return neither logits nor log-probabilities
+            const bool need_h = r >= c.out_r0 && !(c.mode == TS_TEACHER_FORCED && !c.logits && !logprob);
             TS_TRY(run_row(p, c, r, need_h, st));
         }
         return 0;
@@ -1046,12 +1062,14 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
     if (!graph) {   // the samplers address the caller's arrays directly: rows out_row0 .. of out_H per clip
         if (out_H != c.H && c.logits) return fail("pixelcnn: eager rows with logits write the caller's arrays whole");
         c.codes = codes;
+        c.logprob = logprob;
         c.uniforms = uniforms;
         c.io_H = out_H;
         c.io_row0 = c.out_row0;
         return row_loop(s);
     }
     c.codes = static_cast<int64_t *>(w->codes_int.p);
+    c.logprob = logprob ? w->lp_int.f() : nullptr;
     c.uniforms = c.mode == TS_SAMPLE_UNIFORMS ? w->unif_int.f() : nullptr;
     c.dyn = static_cast<const uint64_t *>(w->dyn.p);
     if (c.mode == TS_SAMPLE_UNIFORMS && !capture_only)
@@ -1088,6 +1106,9 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
     TS_HIP(hipGraphLaunch(it->second.exec, s));
     TS_HIP(hipMemcpy2DAsync(codes + (size_t)c.out_row0 * 2, (size_t)out_H * 2 * sizeof(int64_t), w->codes_int.p,
                             (size_t)c.H * 2 * sizeof(int64_t), (size_t)c.H * 2 * sizeof(int64_t), c.B, hipMemcpyDeviceToDevice, s));
+    if (logprob)   // the same rows of the caller's log-probability array, the way the codes travel
+        TS_HIP(hipMemcpy2DAsync(logprob + (size_t)c.out_row0 * 2, (size_t)out_H * 2 * sizeof(float), w->lp_int.p,
+                                (size_t)c.H * 2 * sizeof(float), (size_t)c.H * 2 * sizeof(float), c.B, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -1100,7 +1121,7 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
 // compact chunk buffers its graph reads.  Bit-identical to the whole-call graph (same launches, same order, same rings: only the
 // look-ahead partial sums of rows past the end are computed and never read).
 int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
-                int64_t *codes, const SampleCtl *ctl, hipStream_t s) {
+                int64_t *codes, const SampleCtl *ctl, float *logprob, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     for (int r0 = 0; r0 < H; r0 += CHUNK_ROWS) {
@@ -1118,7 +1139,7 @@ int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, co
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H * m.width * f,
                                         (size_t)Hc * m.width * f, B, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode, 0, ctl ? 1 : 0), uniforms, codes, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode, 0, sampler_bits(ctl, logprob)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1157,7 +1178,7 @@ int mixed_plan(const int *hrows, int B, int max_counts, std::vector<int> &active
 constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
-              uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, hipStream_t s) {
+              uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1179,7 +1200,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, ctl ? 1 : 0), uniforms, codes, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1206,13 +1227,48 @@ int ts_sampling_check(const ts_sampling *ctl_host, int n, int V) { return ctl_ch
 // the sampler with controls on given logits (ts_op_sample / ts_op_sample_philox with a table; kernel-level tests call it)
 int ts_op_sample_ctl(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
                      uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, uint8_t *kept, void *stream) {
-    if (!ctx || !logits || !idx) return fail("ts_op_sample_ctl: null argument");
-    if (B < 1 || V < 1) return fail("ts_op_sample_ctl: bad shape");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_op_sample_ctl: uniforms required");
-    std::vector<SampleCtl> tab;
     if (!ctl_host) return fail("ts_op_sample_ctl: a table is required (ts_op_sample / ts_op_sample_philox are the entries without one)");
-    TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, "ts_op_sample_ctl", tab));
+    return ts_op_sample_lp(ctx, logits, B, V, mode, uniforms, seed, clip_index0, position, ctl_host, n_ctl, idx, kept, nullptr, stream);
+}
+
+// one sampler launch on given logits, with the log-probability of every row's code (kernel-level tests call it).  Without a table: any of
+// the four modes through sample_lp_kernel (sample_kernel when logprob is NULL); teacher forced reads idx.  With one: ts_op_sample_ctl's launch.
+int ts_op_sample_lp(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                    uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, uint8_t *kept, float *logprob, void *stream) {
+    const char *who = logprob ? "ts_op_sample_lp" : "ts_op_sample_ctl";
+    if (!ctx || !logits || !idx) return fail(std::string(who) + ": null argument");
+    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
+    if (mode < 0 || mode > TS_TEACHER_FORCED) return fail(std::string(who) + ": bad mode");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
     hipStream_t s = (hipStream_t)stream;
+    if (!ctl_host) {
+        if (kept) return fail(std::string(who) + ": kept_dev needs a table");
+        DevBuf tok;
+        TS_TRY(tok.ensure((size_t)B * sizeof(int)));
+        SampleLpParams q;
+        std::memset(&q, 0, sizeof(q));
+        q.s.logits = logits;
+        q.s.B = B;
+        q.s.V = V;
+        q.s.mode = mode;
+        q.s.uniforms = uniforms;
+        q.s.u_stride = 1;
+        q.s.seed = seed;
+        q.s.clip_index0 = clip_index0;
+        q.s.position = position;
+        q.s.tok32 = tok.i();
+        q.s.tok_stride = 1;
+        q.s.codes = idx;
+        q.s.code_stride = 1;
+        q.logprob = logprob;
+        q.lp_stride = 1;
+        if (logprob) TS_HIP(launch_sample_lp(q, s));
+        else TS_HIP(launch_sample(q.s, s));
+        TS_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+    std::vector<SampleCtl> tab;
+    TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, who, tab));
     DevBuf tok, dtab;
     TS_TRY(tok.ensure((size_t)B * sizeof(int)));
     TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
@@ -1234,6 +1290,8 @@ int ts_op_sample_ctl(ts_ctx *ctx, const float *logits, int B, int V, int mode, c
     cp.s.code_stride = 1;
     cp.ctl = static_cast<const SampleCtl *>(dtab.p);
     cp.kept = kept;
+    cp.logprob = logprob;
+    cp.lp_stride = 1;
     TS_HIP(launch_sample_ctl(cp, s));
     TS_HIP(hipStreamSynchronize(s));
     return 0;
@@ -1242,6 +1300,14 @@ int ts_op_sample_ctl(ts_ctx *ctx, const float *logits, int B, int V, int mode, c
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
+    return ts_pixelcnn_generate_mixed_lp(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                         nullptr, stream);
+}
+
+// the mixed pass with a log-probability output (B,H_max,2): rows at or beyond a clip's own H_b are 0 (logprob == NULL: the entry above)
+int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                  int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                  int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, void *stream) {
     if (!p || !label || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail("ts_pixelcnn_generate_mixed: bad mode");
@@ -1269,9 +1335,11 @@ int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const f
         else TS_HIP(launch_iota_i64(static_cast<int64_t *>(w->clip_tab.p), B, 0, s));
     }
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr, s));
+    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
+                     logprob, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
+    if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0
     return 0;
 }
 
@@ -1284,6 +1352,15 @@ int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float
 int ts_pixelcnn_generate_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
                              const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
                              const int64_t *pre_codes, const float *pre_aud, int H0, const ts_sampling *ctl_host, int n_ctl, void *stream) {
+    return ts_pixelcnn_generate_lp(p, label, aud, B, H, mode, uniforms, seed, clip0, codes, logits, pre_codes, pre_aud, H0, ctl_host, n_ctl,
+                                   nullptr, stream);
+}
+
+// ts_pixelcnn_generate_ctl with a log-probability output (B,H,2) over the generated (teacher forced: the given) rows; NULL: that entry
+int ts_pixelcnn_generate_lp(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
+                            const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
+                            const int64_t *pre_codes, const float *pre_aud, int H0, const ts_sampling *ctl_host, int n_ctl, float *logprob,
+                            void *stream) {
     if (!p || !label || !aud || !codes) return fail("ts_pixelcnn_generate: null argument");
     if (B < 1 || H < 1 || H0 < 0) return fail("ts_pixelcnn_generate: bad shape");
     if (mode < 0 || mode > TS_TEACHER_FORCED) return fail("ts_pixelcnn_generate: bad mode");
@@ -1299,7 +1376,8 @@ int ts_pixelcnn_generate_ctl(ts_pixelcnn *p, const int64_t *label, const float *
     if (ctl_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
     const SampleCtl *ctl = ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr;
 
-    // eager launches remain for the instrumented / logits-returning / teacher-forced paths
+    // eager launches remain for the instrumented / logits-returning / teacher-forced paths (teacher forced with log-probabilities too: it
+    // runs the horizontal stack, see need_h in run_rows, as eager launches)
     const bool graph = p->use_graph && !ctx->prof.on && !logits && mode != TS_TEACHER_FORCED;
     RunCfg c = one_shot_cfg(B, H, H0, mode, uniforms, seed, clip0, codes, logits, w);
     c.ctl = ctl;
@@ -1328,13 +1406,13 @@ int ts_pixelcnn_generate_ctl(ts_pixelcnn *p, const int64_t *label, const float *
                                     (size_t)H * 2 * e, B, hipMemcpyDeviceToDevice, s));
         TS_HIP(launch_i64_to_i32(tf, w->tok32.i(), (long)B * Htot * 2, s));
     }
-    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0, ctl ? 1 : 0);
+    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0, sampler_bits(ctl, logprob));
     // A shape without a whole-call graph runs as chunk graphs (two or three small captures that serve every clip length) until it is
     // hot (Work::hot: pinned by ts_pixelcnn_prepare, or its third sighting among the last 16 one-shot calls of this stream); then it gets
     // its own whole-call graph (one replay per call: the serving loops, bench.py).  The cache is bounded either way.
     if (graph && H0 == 0 && H > CHUNK_ROWS && !w->graphs.count(key) && !w->hot(key))
-        return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, ctl, s);
-    return run_rows(p, c, 0, Htot, graph, key, uniforms, codes, s);
+        return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, ctl, logprob, s);
+    return run_rows(p, c, 0, Htot, graph, key, uniforms, codes, logprob, s);
 }
 
 int ts_pixelcnn_generate(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
@@ -1358,7 +1436,7 @@ int ts_pixelcnn_prepare(ts_pixelcnn *p, int B, int H, int mode, void *stream) {
     const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, 0, mode, 0, 0);
     if (!w->pinned.count(key) && w->pinned.size() >= ts_pixelcnn::Work::PIN_CAP) return fail("ts_pixelcnn_prepare: too many pinned shapes on this stream");
     RunCfg c = one_shot_cfg(B, H, 0, mode, nullptr, 0, 0, nullptr, nullptr, w);
-    TS_TRY(run_rows(p, c, 0, H, true, key, nullptr, nullptr, s, /*capture_only=*/true));
+    TS_TRY(run_rows(p, c, 0, H, true, key, nullptr, nullptr, nullptr, s, /*capture_only=*/true));
     w->pinned.insert(key);
     return 0;
 }
@@ -1409,7 +1487,7 @@ int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, in
     // in the 4-row rings) and the same set of existing rows above (rows 0..2 have fewer): key on that, not on r0
     const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0, 0), uniforms, codes, s));
+    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0, 0), uniforms, codes, nullptr, s));
     st->rows += Hc;
     return 0;
 }

@@ -659,6 +659,205 @@ hipError_t launch_sample(const SampleParams &p, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// sample_kernel plus the log-probability of the code (talkshow_hip.h, "log-probabilities"): a kernel of its own, so that sample_kernel
+// keeps its code and a pass without the output its launches.  Same launch shape, same loads, the same choice in every mode; greedy and
+// teacher forced compute the total S here too (the sampler's summation structure: chunk sums left to right, then the 256 chunk sums left
+// to right).  The logit of the code c is picked up by the thread that OWNS index c (a 64-bit comparison against its chunk): c is never an
+// address, and a teacher-forced code outside [0, V) finds no owner — thread 0 then writes NaN.  One fp64 log on one lane, one 4-byte store.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ inline float logprob_value(float d, float S) { return (float)((double)d - log((double)S)); }
+
+__global__ __launch_bounds__(256) void sample_lp_kernel(const SampleLpParams lp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    const SampleParams &p = lp.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+
+    const int chunk = (p.V + 255) / 256;
+    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
+    // the production vocabulary on 16-byte aligned rows: every thread's 8 logits come from two 16-byte loads up front, as in sample_kernel
+    const bool fast = p.V == 2048 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
+    float x[8];
+    if (fast) {
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
+    }
+
+    if (p.logits_copy) {
+        float *dst = p.logits_copy + (long)b * p.copy_stride;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
+        } else {
+            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
+        }
+    }
+
+    // ---- max / argmax; ties -> lowest index ----
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (fast) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (x[k] > best) { best = x[k]; bi = v0 + k; }
+    } else {
+        for (int v = v0; v < v1; ++v) {
+            const float t = lg[v];
+            if (t > best) { best = t; bi = v; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
+    __syncthreads();
+    best = sf[0]; bi = si[0];
+    for (int w = 1; w < 4; ++w)
+        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
+    __syncthreads();
+
+    // ---- the total, in every mode: sf[t] = sum of the chunks < t, sf[256] = S ----
+    float s = 0.f;
+    if (fast) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += det_expf(x[k] - best);
+    } else {
+        for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
+    }
+    sf[tid + 1] = s;
+    __syncthreads();
+    const bool draws = p.mode == TS_SAMPLE_UNIFORMS || p.mode == TS_SAMPLE_PHILOX;
+    if (tid == 0) {
+        float u = 0.f;
+        if (p.mode == TS_SAMPLE_UNIFORMS) {
+            u = p.uniforms[(long)b * p.u_stride];
+        } else if (p.mode == TS_SAMPLE_PHILOX) {
+            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
+            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+            uint32_t r;
+            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
+                          (uint32_t)(seed >> 32), r);
+            u = (float)(r >> 8) * (1.0f / 16777216.0f);
+        }
+        float c = 0.f;
+        sf[0] = 0.f;
+        for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }
+        s_thr = u * c;
+    }
+    __syncthreads();
+
+    long long code;   // 64 bits: a teacher-forced code is compared, never truncated
+    if (p.mode == TS_TEACHER_FORCED) {
+        code = p.codes[(long)b * p.code_stride];
+    } else if (!draws) {
+        code = bi;
+    } else {
+        const float thr = s_thr;
+        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
+        if (mine && v0 < p.V) {
+            float c = sf[tid];
+            int k = v1 - 1;
+            if (fast) {
+                bool found = false;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    c += det_expf(x[j] - best);
+                    if (!found && c > thr) { k = v0 + j; found = true; }
+                }
+            } else {
+                for (int v = v0; v < v1; ++v) {
+                    c += det_expf(lg[v] - best);
+                    if (c > thr) { k = v; break; }
+                }
+            }
+            si[0] = k;
+        } else if (mine) {
+            si[0] = p.V - 1;
+        }
+        __syncthreads();
+        code = si[0];
+    }
+
+    float *out = lp.logprob + (long)b * lp.lp_stride;
+    if (code >= (long long)v0 && code < (long long)v1) {   // the owner of index `code`: exactly one thread, or none when it is out of range
+        float lc = 0.f;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if ((long long)(v0 + k) == code) lc = x[k];
+        } else {
+            for (int v = v0; v < v1; ++v)
+                if ((long long)v == code) lc = lg[v];
+        }
+        *out = logprob_value(lc - best, sf[256]);
+    }
+    if (tid == 0) {
+        if (code < 0 || code >= (long long)p.V) *out = __uint_as_float(0x7fc00000u);
+        p.tok32[(long)b * p.tok_stride] = (int)code;
+        if (p.mode != TS_TEACHER_FORCED) p.codes[(long)b * p.code_stride] = code;
+    }
+}
+
+hipError_t launch_sample_lp(const SampleLpParams &p, hipStream_t stream) {
+    if (!p.logprob || p.s.V < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_lp_kernel, dim3(p.s.B), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+__global__ void mask_logprob_kernel(float *lp, int B, int H, const int *__restrict__ lens) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * H) return;
+    const int b = i / H, r = i - b * H;
+    if (r >= (lens[b] >> 2)) lp[2l * i] = lp[2l * i + 1] = 0.f;
+}
+hipError_t launch_mask_logprob(float *logprob, int B, int H, const int *lens, hipStream_t stream) {
+    hipLaunchKernelGGL(mask_logprob_kernel, dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, stream, logprob, B, H, lens);
+    return hipGetLastError();
+}
+
+// stage 1: lane t of clip b adds rows t, t + 256, ... (ascending) of the clip's own rows, each column by itself
+__global__ __launch_bounds__(LOGPROB_SUM_LANES) void logprob_sums_partial(const float *__restrict__ lp, int H, const int *__restrict__ lens,
+                                                                          double *__restrict__ part) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int Hb = lens ? min(H, max(lens[b] >> 2, 0)) : H;
+    const float *row = lp + (size_t)b * H * 2;
+    double s0 = 0.0, s1 = 0.0;
+    for (int r = t; r < Hb; r += LOGPROB_SUM_LANES) {
+        s0 += (double)row[2 * r];
+        s1 += (double)row[2 * r + 1];
+    }
+    part[((size_t)b * LOGPROB_SUM_LANES + t) * 2] = s0;
+    part[((size_t)b * LOGPROB_SUM_LANES + t) * 2 + 1] = s1;
+}
+// stage 2: the 256 partials of a clip in ascending order; out[b] = {body, hand, body + hand}
+__global__ void logprob_sums_final(const double *__restrict__ part, int B, double *__restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s0 = 0.0, s1 = 0.0;
+    for (int t = 0; t < LOGPROB_SUM_LANES; ++t) {
+        s0 += part[((size_t)b * LOGPROB_SUM_LANES + t) * 2];
+        s1 += part[((size_t)b * LOGPROB_SUM_LANES + t) * 2 + 1];
+    }
+    out[3 * b] = s0;
+    out[3 * b + 1] = s1;
+    out[3 * b + 2] = s0 + s1;
+}
+hipError_t launch_logprob_sums(const float *logprob, int B, int H, const int *lens, double *scratch, double *out, hipStream_t stream) {
+    if (!logprob || !scratch || !out || B < 1 || H < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(logprob_sums_partial, dim3(B), dim3(LOGPROB_SUM_LANES), 0, stream, logprob, H, lens, scratch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(logprob_sums_final, dim3((B + 63) / 64), dim3(64), 0, stream, scratch, B, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // sampler with per-clip controls (temperature, top-k, top-p): the rule is stated in talkshow_hip.h (ts_sampling, steps 1-5) and restated
 // in talkshow_amd/sampling.py.  A kernel of its own: sample_kernel above keeps its code, and a pass without controls its launches.
 //
@@ -689,11 +888,12 @@ __device__ inline uint32_t ctl_key(float l) {
 }
 __device__ inline float ctl_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
 // step 1: subtract, multiply (two fp32 operations: a difference times a factor cannot contract), det_expf
-__device__ inline float ctl_weight(float l, float m, float inv_t) {
+__device__ inline float ctl_arg(float l, float m, float inv_t) {
 #pragma clang fp contract(off)
     const float d = l - m;
-    return det_expf(d * inv_t);
+    return d * inv_t;
 }
+__device__ inline float ctl_weight(float l, float m, float inv_t) { return det_expf(ctl_arg(l, m, inv_t)); }
 __device__ inline uint32_t ctl_quant(float w) { return (uint32_t)(w * 2147483648.0f); }   // w in [0, 1]: the product is exact, the cast truncates
 
 // packed sum of all 256 bins (every lane gets it)
@@ -759,7 +959,10 @@ __device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) 
     return ok;
 }
 
-template <bool FAST>
+// LP: also write the log-probability of the drawn code under the distribution it was drawn from (cp.logprob; talkshow_hip.h,
+// "log-probabilities"): d_c - log S with d_c the argument of the drawn code's exponential and S the total of the kept weights, both already
+// here.  The instantiations without it are the kernels they were.
+template <bool FAST, bool LP>
 __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams cp) {
     __shared__ float sf[256 + 1];
     __shared__ int si[256];
@@ -969,14 +1172,30 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
         p.tok32[(long)b * p.tok_stride] = choice;
         p.codes[(long)b * p.code_stride] = choice;
     }
+    if constexpr (LP) {
+        const int choice = si[0];
+        if (choice >= v0 && choice < v1) {   // the owner of the drawn index (a draw is always a kept token of the row)
+            float lc = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < n; ++k)
+                if (v0 + k == choice) lc = logit(k);
+            cp.logprob[(long)b * cp.lp_stride] = logprob_value(ctl_arg(lc, best, inv_t), sf[256]);
+        }
+    }
 }
 
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
     if (!p.ctl || p.s.V < 1 || p.s.V > SAMPLE_CTL_MAX_V || (p.s.mode != TS_SAMPLE_UNIFORMS && p.s.mode != TS_SAMPLE_PHILOX)) return hipErrorInvalidValue;
     const long ls = p.s.logit_stride ? p.s.logit_stride : (long)p.s.V;
     const bool fast = p.s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s.logits) & 15) == 0;
-    if (fast) hipLaunchKernelGGL(sample_ctl_kernel<true>, dim3(p.s.B), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(sample_ctl_kernel<false>, dim3(p.s.B), dim3(256), 0, stream, p);
+    if (p.logprob) {
+        if (fast) hipLaunchKernelGGL((sample_ctl_kernel<true, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((sample_ctl_kernel<false, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+    } else if (fast) {
+        hipLaunchKernelGGL((sample_ctl_kernel<true, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL((sample_ctl_kernel<false, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+    }
     return hipGetLastError();
 }
 

@@ -341,13 +341,18 @@ class GatedPixelCNN(NativeModule):
         (_lib.load().ts_pixelcnn_destroy if self.bh_model else _lib.load().ts_pixelcnn_v_destroy)(h)
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
-            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None):
+            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
-        are the network's, before any control.  bh_model=False takes none."""
+        are the network's, before any control.  bh_model=False takes none.
+        logprobs: True, or a float32 (B,H,2) device tensor to fill -> a THIRD return value, the log-probability of every code under the
+        distribution it was drawn from (`ts_pixelcnn_generate_lp`; teacher forced: of the given codes under the model's); the decode
+        stays on its graphs.  False (the default): two return values and the launches there always were."""
         if sampling is not None and not self.bh_model:
             raise NotImplementedError("sampling controls exist for the bh_model=True chain (ts_pixelcnn_generate_ctl), not for the single-stack form")
+        if logprobs is not None and logprobs is not False and not self.bh_model:
+            raise NotImplementedError("log-probabilities exist for the bh_model=True chain (ts_pixelcnn_generate_lp), not for the single-stack form")
         dev = self._dev()
         W = 2
         if aud_rows is not None:
@@ -362,6 +367,8 @@ class GatedPixelCNN(NativeModule):
             W = int(shape[2]) if len(shape) == 3 else 2
         if self.bh_model and W != 2:
             raise NotImplementedError("bh_model grids have exactly 2 columns (body, hand)")
+        lp = _lib.logprob_request(logprobs, (B, H, 2), dev)   # a wrong output tensor: ValueError before any device work
+        ctl, n_ctl = None, 0
         if sampling is not None:   # validated (ValueError names the clip) before any device work
             ctl, n_ctl = _lib.sampling_table(sampling, B, self.input_dim, mode)
         if self.bh_model and aud_rows is None:
@@ -373,6 +380,8 @@ class GatedPixelCNN(NativeModule):
             raise ValueError(f"label must hold 1 or B={B} class indices, got {label.numel()}")
         if mode == _lib.TS_TEACHER_FORCED:
             codes = torch.as_tensor(codes, dtype=torch.int64, device=dev).contiguous()
+            if lp is not None:
+                _lib.score_codes_shape(codes.shape, B, H)
         else:
             codes = torch.zeros((B, H, W), dtype=torch.int64, device=dev)
         logits = torch.empty((B, H, W, self.input_dim), dtype=torch.float32, device=dev) if want_logits else None
@@ -393,11 +402,41 @@ class GatedPixelCNN(NativeModule):
             return codes, logits
         args = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0)
+        if lp is not None:
+            if isinstance(lp, str):
+                lp = torch.empty((B, H, 2), dtype=torch.float32, device=dev)
+            _lib.check(_lib.load().ts_pixelcnn_generate_lp(*args, ctl, n_ctl, _lib.dptr(lp), _lib.stream_ptr()))
+            return codes, logits, lp
         if sampling is None:
             _lib.check(_lib.load().ts_pixelcnn_generate(*args, _lib.stream_ptr()))
         else:
             _lib.check(_lib.load().ts_pixelcnn_generate_ctl(*args, ctl, n_ctl, _lib.stream_ptr()))
         return codes, logits
+
+    def score(self, label, aud_rows, codes, logprobs=True):
+        """Teacher-forced scoring: the log-probability of every GIVEN code under the model, label / aud_rows (B,H,aud_dim) as for `run`,
+        codes (B,H,2) int64 -> (logprobs (B,H,2) float32, sums (B,3) float64 = per clip {body column, hand column, both}:
+        `ts_logprob_sums`, fixed-order fp64).  No logits leave the sampler launch; a code outside [0, input_dim) gives NaN at its position.
+        Scoring the codes of a decode without a sampling table returns that decode's own log-probabilities, bit for bit."""
+        if not self.bh_model:
+            raise NotImplementedError("log-probabilities exist for the bh_model=True chain (ts_pixelcnn_generate_lp), not for the single-stack form")
+        B, H = int(aud_rows.shape[0]), int(aud_rows.shape[1])
+        _lib.score_codes_shape(tuple(getattr(codes, "shape", ())), B, H)
+        _, _, lp = self.run(label, aud_rows, mode=_lib.TS_TEACHER_FORCED, codes=codes, logprobs=logprobs)
+        return lp, self.logprob_sums(lp)
+
+    def logprob_sums(self, lp, rows=None):
+        """(B,H,2) log-probabilities -> (B,3) float64 per-clip sums {body, hand, both} (`ts_logprob_sums`; `sampling.logprob_sums` is its
+        numpy restatement, equal bit for bit).  rows: (B,) every clip's own row count (None: H); rows beyond do not enter."""
+        dev = self._dev()
+        lp = _dev_f32(lp, dev)
+        B, H = int(lp.shape[0]), int(lp.shape[1])
+        lens = None
+        if rows is not None:
+            lens = upload(np.asarray(rows, np.int32) * 4, dev)           # the entry takes the mixed pass's table: MFCC frames, 4 per code row
+        sums = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().ts_logprob_sums(self._ctx(), _lib.dptr(lp), _lib.dptr(lens), B, H, _lib.dptr(sums), _lib.stream_ptr()))
+        return sums
 
     def prepare(self, batch_size, rows, mode=_lib.TS_SAMPLE_GREEDY):
         """Serving aid (`ts_pixelcnn_prepare`): capture and pin the whole-call hipGraph of a (batch_size, rows, mode) decode on the current
@@ -439,11 +478,12 @@ class GatedPixelCNN(NativeModule):
 
     # --- reference call shapes ---
     def generate(self, label, shape=(8, 8), batch_size=64, aud_feat=None, pre_latents=None, pre_audio=None,
-                 mode=None, seed=None, uniforms=None, sampling=None):
+                 mode=None, seed=None, uniforms=None, sampling=None, logprobs=False):
         """`GatedPixelCNN.generate` (`gated_pixelcnn_v2.py:152-177`): aud_feat (B,aud_dim,H,2) -> codes (B,H,2).
 
         Default is stochastic like the reference (softmax + one multinomial draw per position), with Philox uniforms
         seeded from torch's default generator; `mode=TS_SAMPLE_GREEDY` gives the argmax harness.  `sampling`: as for `run`.
+        `logprobs=True` (or an output tensor): returns (codes, logprobs (B,H,2) float32) instead of codes.
         """
         rows = self._audio_rows(aud_feat)
         pre_rows = self._audio_rows(pre_audio)
@@ -451,9 +491,9 @@ class GatedPixelCNN(NativeModule):
             mode = _lib.TS_SAMPLE_PHILOX if uniforms is None else _lib.TS_SAMPLE_UNIFORMS
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if mode == _lib.TS_SAMPLE_PHILOX else 0
-        codes, _ = self.run(label, rows, mode=mode, uniforms=uniforms, seed=seed, pre_codes=pre_latents, pre_aud=pre_rows,
-                            shape=(batch_size, shape[0], shape[1]), sampling=sampling)
-        return codes
+        out = self.run(label, rows, mode=mode, uniforms=uniforms, seed=seed, pre_codes=pre_latents, pre_aud=pre_rows,
+                       shape=(batch_size, shape[0], shape[1]), sampling=sampling, logprobs=logprobs)
+        return out[0] if len(out) == 2 else (out[0], out[2])
 
     def __call__(self, x, label, aud=None):
         """`GatedPixelCNN.forward` (`gated_pixelcnn_v2.py:130-150`): x (B,H,2) codes -> logits (B,input_dim,H,2)."""

@@ -116,3 +116,88 @@ def sample_ctl(logits, u, records):
         kept[b] = keep_mask(logits[b], records[b])
         idx[b] = draw(logits[b], u[b], records[b][0], kept[b])
     return idx, kept
+
+
+# ---- log-probabilities (include/talkshow_hip.h, "log-probabilities"; csrc/vq.hip: sample_lp_kernel, sample_ctl_kernel<., true>) --------------
+
+DET_EXPF_REL_ERR = 2.0 ** -23   # bound used for det_expf against exp on [-86, 0]; the worst error found on 2^26 + 1 points is 8.11e-8
+
+
+def chunk_total(w):
+    """The fp32 total S of a row of weights with the samplers' summation structure: 256 contiguous chunks of ceil(V / 256) summed left to
+    right, then the 256 chunk sums added left to right."""
+    w = np.asarray(w, F32).reshape(-1)
+    chunk = (w.size + NTHREADS - 1) // NTHREADS
+    pad = np.zeros(NTHREADS * chunk, F32)
+    pad[:w.size] = w
+    pad = pad.reshape(NTHREADS, chunk)
+    s = np.zeros(NTHREADS, F32)
+    for j in range(chunk):
+        s = (s + pad[:, j]).astype(F32)
+    return F32(np.add.accumulate(s, dtype=F32)[-1])
+
+
+def logprob(row, code, record=None):
+    """The log-probability the device returns for `code` on the logits `row` (V,): float32((double) d_c - log((double) S)), d_c the fp32
+    argument of the code's exponential, S the fp32 total the draw is made from.  record None: the sampler without controls (greedy and
+    teacher forced too), d_c = l_c - max, S over all weights.  With a record (temperature, top_p, top_k): d_c = (l_c - max) * inv_T as two
+    fp32 operations, S over the weights the record keeps.  S and d_c equal the device's bit for bit; the fp64 log may differ from the
+    device's in its last place, so the result is the device's or an adjacent float32.  A code outside [0, V) gives NaN.  (The device
+    only ever returns values for kept tokens: a draw is one.)"""
+    row = np.asarray(row, F32).reshape(-1)
+    V = row.size
+    code = int(code)
+    if not 0 <= code < V:
+        return F32(np.nan)
+    d = (row - row.max()).astype(F32)
+    if record is None:
+        w = det_expf(d)
+    else:
+        temperature = record[0]
+        with np.errstate(invalid="ignore"):
+            d = (d * inv_temperature(temperature)).astype(F32)
+        w = np.where(keep_mask(row, record), det_expf(d), F32(0.0)).astype(F32)
+    S = chunk_total(w)
+    return F32(np.float64(d[code]) - np.log(np.float64(S)))
+
+
+LOGPROB_SUM_LANES = 256
+
+
+def logprob_sums(lp, rows=None):
+    """`ts_logprob_sums` addition for addition: lp (B,H,2) float32, rows (B,) = every clip's own row count H_b (None: H) -> (B,3) float64
+    {body column, hand column, body + hand}.  Lane t adds rows t, t + 256, ... of a column in ascending order in fp64; the 256 lane sums
+    are then added in ascending order; the third value is one fp64 addition of the first two.  Rows at or beyond H_b do not enter."""
+    lp = np.asarray(lp, F32)
+    B, H, W = lp.shape
+    if W != 2:
+        raise ValueError(f"logprob_sums: lp must be (B, H, 2), got {lp.shape}")
+    out = np.zeros((B, 3), np.float64)
+    for b in range(B):
+        Hb = H if rows is None else min(H, max(int(rows[b]), 0))
+        x = lp[b, :Hb].astype(np.float64)
+        for k in range(2):
+            lanes = np.zeros(LOGPROB_SUM_LANES, np.float64)
+            for r0 in range(0, Hb, LOGPROB_SUM_LANES):                   # round j of every lane: row r0 + t
+                seg = x[r0:r0 + LOGPROB_SUM_LANES, k]
+                lanes[:seg.size] = lanes[:seg.size] + seg
+            s = np.float64(0.0)
+            for t in range(LOGPROB_SUM_LANES):
+                s = s + lanes[t]
+            out[b, k] = s
+        out[b, 2] = out[b, 0] + out[b, 1]
+    return out
+
+
+def logprob_error_bound(V, d_c, lp):
+    """Bound on |logprob(row, c) - exact| WITHOUT a record, exact = the float64 log-softmax of the fp32 logits at c, DERIVED from the rule:
+      d_c            one fp32 subtraction: |d_c| * 2^-24
+      every weight   det_expf's relative error (DET_EXPF_REL_ERR) + the rounding of its argument, |d_v| <= 86 for a non-zero weight:
+                     exp(d (1 + e)), |e| <= 2^-24 -> relative 86 * 2^-24 (1 + small); weights below e^-86 are dropped: V * e^-86 of S >= 1
+      S              at most chunk - 1 + 255 fp32 additions, each relative 2^-24 of a partial sum <= S (all terms are >= 0)
+      log            |d log S| <= eps / (1 - eps);  the fp64 log and subtraction: 2^-50 (1 + |lp|)
+      result         one rounding to fp32: |lp| * 2^-24."""
+    u = 2.0 ** -24
+    chunk = (int(V) + NTHREADS - 1) // NTHREADS
+    eps = ((chunk - 1 + 255) * u + DET_EXPF_REL_ERR + 86 * u) * 1.001 + V * np.exp(-86.0)
+    return abs(float(d_c)) * u + eps / (1 - eps) + 2.0 ** -50 * (1 + abs(float(lp))) + abs(float(lp)) * u
