@@ -399,6 +399,56 @@ int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *pix, const int64_t *label_dev, co
                                   const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
                                   const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
                                   float *logprob_dev, void *stream);
+/* ---- given rows: continue each clip of a mixed pass from codes that already exist -------------------------------------------------------
+ * The _lp entries plus, per clip, G_b GIVEN code rows, 0 <= G_b <= H_b = lens[b] / 4 (the reference's `infer(..., pre_latents, pre_audio)`
+ * flow for a host that batches; keep a head and regenerate the tail; N tails for one head).  The audio is the clip's WHOLE audio, as in any
+ * one-shot call.  Code rows r < G_b are TAKEN from the caller; rows G_b <= r < H_b are produced exactly as the pass produces them without
+ * given rows (greedy, injected uniforms or Philox, with or without a sampling record).  codes_dev holds the given rows followed by the
+ * produced rows, poses_dev the VQ decode of all H_b rows; rows at or beyond H_b are -1 / 0 as in every mixed pass.
+ *   given_dev (B,H_max,2) int64: rows r < G_b of clip b are read, rows at or beyond G_b never are (they may hold anything);
+ *   given_rows_host (B,) int32: G_b in the order of the submitted, SORTED clips like every other table of the pass.  It travels to the
+ *     stream's work buffers as kernel arguments ahead of the first chunk: not read after the call returns, nothing synchronises, any number
+ *     of calls — each with its own table and its own codes — may be queued.  G_b < 0 or G_b > lens[b] / 4 is an error, reported before
+ *     anything is launched (ts_given_rows_check is that rule on its own);
+ *   given_rows_dev (B,) int32 or NULL: the same table in device memory, for hosts that keep one beside lens_dev; the pass is planned and
+ *     fed from the host copy and does not read it;
+ *   uniforms_dev: the uniforms of rows below G_b are never read (they may hold anything, NaNs included).
+ * THE RULE.  The sampler launch of position (r, j) — one workgroup per clip — is FORCED for clip slot b iff 2 r + j < 2 G_b, the position
+ * being the Philox counter word of the launch.  A forced workgroup reads its code, writes it where a drawn code goes and draws nothing; an
+ * unforced one runs the arithmetic of the sampler it stands in for.  Nothing else in the pass changes: a given row runs through the same
+ * launches as a produced one (it costs what a produced row costs), so the row cache behind the prefix holds what a decode that DREW those
+ * codes left there.  Consequences (tests/test_gpu_given_ops.py, test_gpu_given_pass.py):
+ *   - values are pure: a clip's codes, poses and log-probabilities depend on the clip's own audio, id, given rows, record and random
+ *     stream only — bit-identical alone or among any neighbours with other G, eager or replayed;
+ *   - resume: given the first G_b rows of an earlier decode of the clip (same seed / clip index / record), the pass returns that decode bit
+ *     for bit — a code's Philox position is its absolute (row, column), so the tail draws the numbers it drew then;
+ *   - the produced rows equal what ts_pixelcnn_generate(..., pre_codes_dev, pre_aud_dev, H0 = G_b) returns for the clip alone on the same
+ *     audio rows split at G_b.
+ * Log-probabilities of given rows ("log-probabilities" above).  A given code c gets the log-probability of c under the distribution the row
+ * would have been drawn from: (float)((double)d_c - log((double)S)) with the row's own m, d_c and S.  Without a record that is the value
+ * teacher forcing (GatedPixelCNN.score) returns, bit for bit.  With a record, S is the total over the kept weights and a code the filters
+ * REMOVED has weight w'_c = 0 in that distribution: its log-probability is log(0) = -inf (top_k = 1: 0.0f for the argmax, -inf for every
+ * other code).  Kept codes get the bits a draw of them gets.  talkshow_amd/sampling.py::given_logprob restates it in numpy.
+ * Bad codes.  A given code is compared, never used as an address.  One outside [0, V) inside a clip's prefix is copied to codes_dev as it
+ * is, gets NaN as its log-probability, and enters the rows below it as a row of zeros in place of its embedding (its pose frames are the VQ
+ * decoder's NaNs); nothing is addressed outside the buffers.  The Python layer refuses such a code on the host before anything is launched.
+ * Graphs: bit 2 of the sixth key field.  In a pass with given rows EVERY chunk runs the given variants of the samplers, so its distinct keys
+ * are what they are without given rows (at most 14 of the 16 chunk graphs); the given codes of a chunk travel into a staging block of the
+ * work buffers ahead of its replay, for chunks with rows below max G_b only.  A repeated pass captures nothing, whatever its tables.
+ * Passes without given rows find the keys, graphs and launches they found before.  given_dev == NULL: exactly the _lp entry.
+ * Out of scope: rows inside every active clip's prefix still run the horizontal stack (the eager H0 path of ts_pixelcnn_generate skips
+ * it); the streaming sessions are untouched; uniform lengths are the special case of equal lens (no uniform entry). */
+int ts_given_rows_check(const int32_t *given_rows_host, const int32_t *lens_host, int B);
+int ts_body_pixel_infer_mixed_given(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                    const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                    const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                    float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                    const int32_t *given_rows_host, const int32_t *given_rows_dev, void *stream);
+int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                     const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                     const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                     float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                     const int32_t *given_rows_dev, void *stream);
 /* ts_vqvae_decode_pair with length-masked layers: latents (B,H) each, rows at or beyond lens[b] / 4 are not read (gathered as zero rows;
  * an index outside the codebook INSIDE a clip still gives NaNs); out_dev (B,4H,body_dim+hand_dim), rows at or beyond 4 (lens[b] / 4) = 0. */
 int ts_vqvae_decode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *lat_body_dev, const int64_t *lat_hand_dev,
@@ -450,6 +500,14 @@ int ts_op_sample_ctl(ts_ctx *ctx, const float *logits_dev, int B, int V, int mod
 int ts_op_sample_lp(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
                     int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, uint8_t *kept_dev,
                     float *logprob_dev, void *stream);
+
+/* One launch of the samplers' given variants ("given rows" above) on given logits: ts_op_sample_lp's arguments without kept_dev, plus
+ * forced_host (B) int32 — row b is forced iff forced_host[b] != 0 — and given_dev (B) int64, read for forced rows only.  mode greedy,
+ * uniforms or Philox; ctl_host and logprob_dev may each be NULL.  idx_dev (B) receives the given code of a forced row and the sampler's
+ * choice of every other row. */
+int ts_op_sample_given(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                       int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
+                       const int32_t *forced_host, const int64_t *given_dev, void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

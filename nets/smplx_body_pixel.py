@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False):
+                       logprobs=False, given=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -108,15 +108,17 @@ class TrainWrapper(TrainWrapperBaseClass):
         equal this entry's, bit for bit, so a neutral record changes nothing but the route.  Without one: the uniform entry below, unchanged.
         logprobs=True: a third return value, (B,H,2) float32, the log-probability of every code under the distribution it was drawn from
         (`ts_body_pixel_infer_mixed_lp`: the route of `sampling`, with or without a record; codes and poses are those of the call without it).
+        given: one (B,G,2) integer block or a list of B entries (None or (G_b,2)): the clips' first code rows, taken instead of drawn
+        (`generate_clips`, `ts_body_pixel_infer_mixed_given`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
-        if sampling is not None or logprobs:
+        if sampling is not None or logprobs or given is not None:
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
-                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs))
+                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -214,7 +216,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
-                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False):
+                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -226,7 +228,13 @@ class TrainWrapper(TrainWrapperBaseClass):
         sampling: one sampling record (`_lib.sampling_record`: temperature, top_p, top_k) for all clips, or a list of one per clip in
         SUBMISSION order; the records are carried through the length sort exactly as `clip_indices` are, and a clip's codes depend on its
         own record only (`ts_body_pixel_infer_mixed_ctl`).  A bad record raises ValueError naming the clip, before anything is launched.
-        logprobs=True: every clip's tuple gains logprobs_b (H_b,2) float32 (`ts_body_pixel_infer_mixed_lp`), bit-identical to the clip alone."""
+        logprobs=True: every clip's tuple gains logprobs_b (H_b,2) float32 (`ts_body_pixel_infer_mixed_lp`), bit-identical to the clip alone.
+        given: a list in SUBMISSION order with None or a (G_b,2) integer array per clip (or one (B,G,2) block), 0 <= G_b <= H_b: the clip's
+        first G_b code rows are TAKEN from it, the rest produced as without it (`ts_body_pixel_infer_mixed_given`; the MFCC rows are the
+        clip's whole audio).  The entries are carried through the length sort exactly as the sampling records and `clip_indices` are.  Given
+        the first rows of an earlier decode of the clip (same seed, index and record) the pass returns that decode bit for bit; a given
+        row's log-probability is that of its code under the distribution it would have been drawn from (-inf for a code the record's
+        filters remove).  A bad shape, G_b > H_b or a code outside [0, V) raises ValueError naming the clip before anything is launched."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -253,6 +261,9 @@ class TrainWrapper(TrainWrapperBaseClass):
         if sampling is not None:   # sorted slot k holds the record of submitted clip order[k]
             recs = _lib.sampling_records(sampling, B)
             ctl, n_ctl = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
+        gblock = gtable = None
+        if given is not None:      # sorted slot k holds the given rows of submitted clip order[k]; validated before anything is launched
+            gblock, gtable = _lib.given_block(given, [t // 4 for t in lens], self.generator.input_dim, order, who="generate_clips")
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -287,7 +298,12 @@ class TrainWrapper(TrainWrapperBaseClass):
                 _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
         lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
-        if lp is not None:
+        if gblock is not None:
+            from talkshow_amd.modules import upload
+            gdev = upload(gblock, dev)
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev),
+                                                                   gtable.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), None, _lib.stream_ptr()))
+        elif lp is not None:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed_lp(*args, ctl, n_ctl, _lib.dptr(lp), _lib.stream_ptr()))
         elif ctl is None:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
@@ -304,12 +320,13 @@ class TrainWrapper(TrainWrapperBaseClass):
             return codes, poses
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
-    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None):
+    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
         pass's host table is `mixed_tables` arithmetic (lens_dev: its device copy, (B,) int32, if the caller has uploaded one).  No synchronisation.
-        sampling_table: `_lib.sampling_table(...)` in ROW order (the caller sorted it with the rows), or None."""
+        sampling_table: `_lib.sampling_table(...)` in ROW order (the caller sorted it with the rows), or None.
+        given: `_lib.given_block(...)` in ROW order — (block, table), both numpy — or None."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -327,21 +344,29 @@ class TrainWrapper(TrainWrapperBaseClass):
         args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
                 _lib.dptr(mf), _lib.dptr(ids), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, None, int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
-        if sampling_table is None:
+        if given is not None:
+            gblock, gtable = given
+            if gblock.shape != (B, H_max, 2):
+                raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {gblock.shape}")
+            ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, None, _lib.dptr(upload(gblock, dev)),
+                                                                   gtable.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), None, _lib.stream_ptr()))
+        elif sampling_table is None:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
         else:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed_ctl(*args, sampling_table[0], sampling_table[1], _lib.stream_ptr()))
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None):
+                                sampling=None, given=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
         `generate_batch(MFCC(sr)(wav_b), id_b)` on the clip alone; clip b draws from Philox subsequence `clip_index0 + b`, b its position in
         the SUBMITTED list (or `clip_indices[b]`).  sampling: one sampling record for all recordings or one per recording in submission
-        order; the records follow the recordings through the sort by sample count."""
-        from talkshow_amd.frontend import check_recordings
+        order; the records follow the recordings through the sort by sample count.  given: as for `generate_clips`, one entry per recording
+        in submission order (a recording's code rows: `frontend.mixed_tables(ns, sr)["code_rows"]`)."""
+        from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
         B = len(ns)
@@ -356,6 +381,9 @@ class TrainWrapper(TrainWrapperBaseClass):
         if sampling is not None:
             recs = _lib.sampling_records(sampling, B)
             table = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
+        if given is not None:
+            given = _lib.given_block(given, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], self.generator.input_dim, order,
+                                     who="generate_clips_from_wav")
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -364,7 +392,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         if seed is None:
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
-        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table)
+        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,

@@ -109,6 +109,13 @@ SIGNATURES = {
                                           _vp, _vp]),
     "ts_pixelcnn_generate_mixed_lp": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp]),
     "ts_logprob_sums": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    # the mixed _lp entries plus given_dev, given_rows_host, given_rows_dev ahead of the stream
+    "ts_given_rows_check": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i]),
+    "ts_body_pixel_infer_mixed_given": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                             _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
+    "ts_pixelcnn_generate_mixed_given": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
+                                              C.POINTER(C.c_int32), _vp, _vp]),
+    "ts_op_sample_given": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -329,6 +336,49 @@ def logprob_request(logprobs, shape, device=None):
     if device is not None and str(logprobs.device).split(":")[0] != str(device).split(":")[0]:
         raise ValueError(f"logprobs output must live on {device}, got {logprobs.device}")
     return logprobs
+
+
+def given_block(given, rows, V, order=None, who="given"):
+    """The `given=` keyword of the decode entries -> (block (B, max rows, 2) int64, table (B,) int32), both numpy, both in SLOT order: what
+    `ts_body_pixel_infer_mixed_given` / `ts_pixelcnn_generate_mixed_given` take as given_dev (after an upload) and given_rows_host.
+    given: a list in SUBMISSION order with None (nothing given: G = 0) or a (G_b, 2) integer array per clip, or one (B, G, 2) integer block;
+    rows: every clip's own code rows H_b in submission order; V: the vocabulary; order: sorted slot k holds submitted clip order[k] (None:
+    the submitted order).  Rows of the block at or beyond a clip's G_b are 0 (the pass never reads them).  ValueError naming the SUBMITTED
+    clip for a bad shape, a non-integer array, G_b > H_b, or a code outside [0, V).  Pure host code; a device tensor is read back."""
+    B = len(rows)
+    if hasattr(given, "detach"):
+        given = given.detach().cpu().numpy()
+    if isinstance(given, np.ndarray):
+        if given.ndim != 3 or given.shape[0] != B or given.shape[2] != 2:
+            raise ValueError(f"{who}: one block for all clips must have shape (B={B}, G, 2), got {tuple(given.shape)}")
+        given = list(given)
+    if not isinstance(given, (list, tuple)) or len(given) != B:
+        raise ValueError(f"{who}: one entry per clip ({B}) — None or a (G, 2) integer array — or one (B, G, 2) block, got "
+                         f"{type(given).__name__}" + (f" of {len(given)}" if isinstance(given, (list, tuple)) else ""))
+    order = list(range(B)) if order is None else [int(i) for i in order]
+    if sorted(order) != list(range(B)):
+        raise ValueError(f"{who}: order must be a permutation of the {B} clips")
+    block = np.zeros((B, max(int(h) for h in rows), 2), np.int64)
+    table = np.zeros(B, np.int32)
+    for k, i in enumerate(order):
+        g = given[i]
+        if g is None:
+            continue
+        if hasattr(g, "detach"):
+            g = g.detach().cpu().numpy()
+        g = np.asarray(g)
+        if g.ndim != 2 or g.shape[1] != 2:
+            raise ValueError(f"{who}: given rows of clip {i} must have shape (G, 2), got {tuple(g.shape)}")
+        if g.dtype.kind not in "iu":
+            raise ValueError(f"{who}: given rows of clip {i} must be integers, got {g.dtype}")
+        if g.shape[0] > int(rows[i]):
+            raise ValueError(f"{who}: clip {i} brings {g.shape[0]} given rows but has {int(rows[i])} code rows of its own")
+        if g.size and (int(g.min()) < 0 or int(g.max()) >= int(V)):
+            bad = g[(g < 0) | (g >= int(V))]
+            raise ValueError(f"{who}: given rows of clip {i} hold the code {int(bad.flat[0])}, outside [0, {int(V)})")
+        block[k, :g.shape[0]] = g
+        table[k] = g.shape[0]
+    return block, table
 
 
 def score_codes_shape(codes_shape, B, H):

@@ -206,6 +206,16 @@ int ts_body_pixel_infer_mixed_lp(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb,
                                  const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
                                  uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                  float *logprob, void *stream) {
+    return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                           ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
+}
+
+// the same pass in which clip b brings given_rows[b] code rows (given (B, T_max / 4, 2)); given == NULL: exactly the entry above
+int ts_body_pixel_infer_mixed_given(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                    const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
+                                    void *stream) {
     if (!ae || !pix || !vb || !vh || !mfcc || !ids || !lens_host || !lens_dev || !codes || !poses)
         return fail("ts_body_pixel_infer_mixed: null argument");
     if (B < 1) return fail("ts_body_pixel_infer_mixed: bad shape");
@@ -227,9 +237,13 @@ int ts_body_pixel_infer_mixed_lp(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb,
         if (n_ctl != 1 && n_ctl != B) return fail("ts_body_pixel_infer_mixed_ctl: n_ctl must be 1 or B");
         if (ts_sampling_check(ctl_host, n_ctl, 1) != 0) return 1;   // the records; the vocabulary is checked by ts_pixelcnn_generate_mixed_ctl
     }
+    if (given) {   // a bad row table is refused before the first launch of the pass, too
+        if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
+        if (ts_given_rows_check(given_rows_host, lens_host, B) != 0) return 1;
+    }
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
-    TS_TRY(ts_pixelcnn_generate_mixed_lp(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                         logprob, s));
+    TS_TRY(ts_pixelcnn_generate_mixed_given(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
+                                            n_ctl, logprob, given, given_rows_host, given_rows_dev, s));
     for (int k = 0; k < 2; ++k) {
         TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
         TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),

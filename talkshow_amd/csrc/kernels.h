@@ -443,6 +443,17 @@ struct SampleLpParams {
     long lp_stride;
 };
 hipError_t launch_sample_lp(const SampleLpParams &p, hipStream_t stream);
+// The three samplers with GIVEN rows (talkshow_hip.h, "given rows"; vq.hip: sample_given_kernel, sample_lp_given_kernel,
+// sample_ctl_given_kernel): clip slot b is forced — its code is read from `given`, nothing is drawn — iff the launch's absolute position
+// (c.s.position plus the dynamic base word) is below 2 * rows[b].  c: the sibling's arguments (c.s.mode greedy / uniforms / Philox; c.ctl,
+// c.kept and c.logprob optional, a table needs a drawing mode).  A sibling of the three structs above again: they keep their arguments.
+struct SampleGivenParams {
+    SampleCtlParams c;
+    const int *rows;           // (slots,) G of every clip slot of the pass
+    const int64_t *given;      // the given code of clip b at given[b * given_stride]; read by forced workgroups only
+    long given_stride;
+};
+hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream);
 // logprob (B,H,2) rows at or beyond a clip's own H_b = lens[b] >> 2 become 0 (mixed passes; beside launch_mask_codes)
 hipError_t launch_mask_logprob(float *logprob, int B, int H, const int *lens, hipStream_t stream);
 // Per-clip fixed-order fp64 sums of logprob (B,H,2): out[b] = {body column, hand column, body + hand} over rows r < H_b (lens == nullptr:

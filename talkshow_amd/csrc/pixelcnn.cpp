@@ -88,14 +88,17 @@ struct ts_pixelcnn {
         DevBuf clip_tab;                   // mixed passes: the Philox subsequence of every clip (int64), read by the captured samplers
         DevBuf ctl_tab;                    // passes with sampling controls: one SampleCtl per clip SLOT of the pass, written in stream order ahead of it
         DevBuf lp_int;                     // runs with a log-probability output: what the captured samplers write, (B,rows,2) fp32 beside codes_int
+        DevBuf given_tab, given_int;       // passes with given rows: G of every clip SLOT (int32, written in stream order ahead of the pass); the given codes of
+                                           // ONE chunk, (B,rows,2) int64 beside codes_int (what the captured samplers read)
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
         // (Br, Hc, -(1 + phase), mode, Bs) = Hc rows of a MIXED pass of Bs clips for its first Br clips: the per-clip slabs of the work
         // buffers are Bs clips apart whatever Br is, so the stride is part of what a captured graph is valid for (0: the slabs are B apart).
         // The sixth field is a bit set: bit 0 for a run whose samplers read ctl_tab (sample_ctl_kernel), bit 1 for a run whose samplers write
-        // log-probabilities into lp_int; 0 otherwise: runs with neither find exactly the graphs they found before the field existed; the
-        // table's CONTENT is not part of the key (a replay reads what the call wrote).
+        // log-probabilities into lp_int, bit 2 for a pass with given rows (EVERY chunk of such a pass runs the given variants of the samplers,
+        // which read given_tab and given_int); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
         struct Entry {
@@ -244,6 +247,8 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->clip_tab.ensure((size_t)cb * sizeof(int64_t)));
     TS_TRY(w->ctl_tab.ensure((size_t)cb * sizeof(SampleCtl)));
     TS_TRY(w->lp_int.ensure((size_t)cb * ch * 2 * sizeof(float)));
+    TS_TRY(w->given_tab.ensure((size_t)cb * sizeof(int)));
+    TS_TRY(w->given_int.ensure((size_t)cb * CHUNK_ROWS * 2 * sizeof(int64_t)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -282,6 +287,12 @@ struct RunCfg {
     const SampleCtl *ctl = nullptr;        // device (slabB(),) sampling controls per clip slot (the Work's ctl_tab), or null: the sampler without controls
     float *logprob = nullptr;              // set by run_rows: (B,io_H,2) log-probabilities beside `codes` (staging or the caller's), or null
     int io_H = 0, io_row0 = 0;             // set by run_rows: row count / first row of the arrays the samplers address (staging or the caller's)
+    // passes with given rows (run_mixed): the samplers are the given variants.  given_rows: device (slabB(),) G per clip slot (the Work's
+    // given_tab); given_src: the caller's (B,out_H,2) block; given_stage: this run has rows below max G, so its rows of the block are staged
+    // ahead of a replay; given: set by run_rows, laid out like `codes` (staging or the caller's)
+    const int *given_rows = nullptr;
+    const int64_t *given_src = nullptr, *given = nullptr;
+    bool given_stage = false;
     int slabB() const { return Bs > 0 ? Bs : B; }
     void audio_from(ts_pixelcnn::Work *wk) { aeh = wk->AEH.f(), aeh1 = wk->AEH1.f(), av1c = wk->AV1C.f(), av1p = wk->AV1P.f(); }
 };
@@ -630,7 +641,18 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
     }
     MiscScope ms(p->ctx, s);
     float *lp = c.logprob ? c.logprob + (size_t)ro * 2 + j : nullptr;
-    if (c.ctl) {
+    if (c.given_rows) {
+        SampleGivenParams gp;
+        gp.c.s = sp;
+        gp.c.ctl = c.ctl;
+        gp.c.kept = nullptr;
+        gp.c.logprob = lp;
+        gp.c.lp_stride = (long)sH * 2;
+        gp.rows = c.given_rows;
+        gp.given = c.given + (size_t)ro * 2 + j;
+        gp.given_stride = (long)sH * 2;
+        TS_HIP(launch_sample_given(gp, s));
+    } else if (c.ctl) {
         SampleCtlParams cp;
         cp.s = sp;
         cp.ctl = c.ctl;
@@ -1002,7 +1024,9 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 // The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
-inline int sampler_bits(const SampleCtl *ctl, const float *logprob) { return (ctl ? 1 : 0) | (logprob ? 2 : 0); }
+inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr) {
+    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0);
+}
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
     MiscScope ms(ctx, s);
@@ -1064,10 +1088,15 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
         c.codes = codes;
         c.logprob = logprob;
         c.uniforms = uniforms;
+        c.given = c.given_src;
         c.io_H = out_H;
         c.io_row0 = c.out_row0;
         return row_loop(s);
     }
+    c.given = static_cast<const int64_t *>(w->given_int.p);
+    if (c.given_rows && c.given_stage && !capture_only)   // the chunk's rows of the given block, the way the uniforms travel
+        TS_HIP(hipMemcpy2DAsync(w->given_int.p, (size_t)c.H * 2 * sizeof(int64_t), c.given_src + (size_t)c.out_row0 * 2,
+                                (size_t)out_H * 2 * sizeof(int64_t), (size_t)c.H * 2 * sizeof(int64_t), c.B, hipMemcpyDeviceToDevice, s));
     c.codes = static_cast<int64_t *>(w->codes_int.p);
     c.logprob = logprob ? w->lp_int.f() : nullptr;
     c.uniforms = c.mode == TS_SAMPLE_UNIFORMS ? w->unif_int.f() : nullptr;
@@ -1178,7 +1207,8 @@ int mixed_plan(const int *hrows, int B, int max_counts, std::vector<int> &active
 constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
-              uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, hipStream_t s) {
+              uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, const int64_t *given, int given_max,
+              hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1193,6 +1223,11 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
         c.Bs = B;
         c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
         c.ctl = ctl;   // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
+        if (given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
+            c.given_rows = w->given_tab.i();
+            c.given_src = given;
+            c.given_stage = r0 < given_max;
+        }
         struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
             {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
         for (auto &m : rows)
@@ -1200,7 +1235,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob)), uniforms, codes, logprob, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1297,6 +1332,56 @@ int ts_op_sample_lp(ts_ctx *ctx, const float *logits, int B, int V, int mode, co
     return 0;
 }
 
+// one launch of the samplers' given variants on given logits (kernel-level tests call it): row b is forced iff forced_host[b] != 0
+int ts_op_sample_given(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                       uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *forced_host,
+                       const int64_t *given, void *stream) {
+    const char *who = "ts_op_sample_given";
+    if (!ctx || !logits || !idx || !forced_host || !given) return fail(std::string(who) + ": null argument");
+    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
+    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
+    if (position > 0x7ffffff0u) return fail(std::string(who) + ": position too large for a row table");
+    std::vector<SampleCtl> tab;
+    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, who, tab));
+    // the kernels force a workgroup whose position is below 2 G: G = position / 2 + 1 forces row b at this position, G = 0 never does
+    std::vector<int> rows(B);
+    for (int b = 0; b < B; ++b) rows[b] = forced_host[b] ? (int)(position / 2) + 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tok, dtab, drows;
+    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
+    TS_TRY(drows.ensure((size_t)B * sizeof(int)));
+    TS_HIP(launch_put_words(drows.i(), rows.data(), B, s));
+    if (ctl_host) {
+        TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
+        TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
+    }
+    SampleGivenParams gp;
+    std::memset(&gp, 0, sizeof(gp));
+    gp.c.s.logits = logits;
+    gp.c.s.B = B;
+    gp.c.s.V = V;
+    gp.c.s.mode = mode;
+    gp.c.s.uniforms = uniforms;
+    gp.c.s.u_stride = 1;
+    gp.c.s.seed = seed;
+    gp.c.s.clip_index0 = clip_index0;
+    gp.c.s.position = position;
+    gp.c.s.tok32 = tok.i();
+    gp.c.s.tok_stride = 1;
+    gp.c.s.codes = idx;
+    gp.c.s.code_stride = 1;
+    gp.c.ctl = ctl_host ? static_cast<const SampleCtl *>(dtab.p) : nullptr;
+    gp.c.logprob = logprob;
+    gp.c.lp_stride = 1;
+    gp.rows = drows.i();
+    gp.given = given;
+    gp.given_stride = 1;
+    TS_HIP(launch_sample_given(gp, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
@@ -1308,6 +1393,27 @@ int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const f
 int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                   int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                   int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, void *stream) {
+    return ts_pixelcnn_generate_mixed_given(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                            logprob, nullptr, nullptr, nullptr, stream);
+}
+
+// Host only: the rule every _given entry applies to its row table before anything is launched
+int ts_given_rows_check(const int32_t *given_rows_host, const int32_t *lens_host, int B) {
+    if (!given_rows_host || !lens_host || B < 1) return fail("ts_given_rows_check: bad argument");
+    for (int b = 0; b < B; ++b)
+        if (given_rows_host[b] < 0 || given_rows_host[b] > (lens_host[b] >> 2))
+            return fail("given rows of clip " + std::to_string(b) + ": G = " + std::to_string(given_rows_host[b]) + " must be in [0, " +
+                        std::to_string(lens_host[b] >> 2) + "], the clip's own code rows");
+    return 0;
+}
+
+// the mixed pass in which clip b brings given_rows[b] code rows that are taken, not drawn (talkshow_hip.h, "given rows"); given == NULL: the
+// _lp entry, launch for launch
+int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                     int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, void *stream) {
+    (void)given_rows_dev;   // the table travels as kernel arguments from the host copy (see talkshow_hip.h)
     if (!p || !label || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail("ts_pixelcnn_generate_mixed: bad mode");
@@ -1322,11 +1428,21 @@ int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *p, const int64_t *label, const fl
     }
     std::vector<SampleCtl> tab;
     if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
+    int given_max = 0;
+    if (given) {
+        if (!given_rows_host) return fail("ts_pixelcnn_generate_mixed_given: given codes need their row table");
+        TS_TRY(ts_given_rows_check(given_rows_host, lens_host, B));
+        for (int b = 0; b < B; ++b) given_max = std::max(given_max, (int)given_rows_host[b]);
+    }
     hipStream_t s = (hipStream_t)stream;
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));
     if (ctl_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
+    if (given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w->given_tab.i(), given_rows_host, B, s));
+    }
     TS_TRY(audio_terms(p, w, aud, B, H_max, s));
     TS_TRY(class_rows(p, w, label, B, s));
     {   // the clips' Philox subsequences, in a Work buffer (what the captured samplers read): the caller's table, or 0 .. B-1
@@ -1336,7 +1452,7 @@ int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *p, const int64_t *label, const fl
     }
     const bool graph = p->use_graph && !ctx->prof.on;
     TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
-                     logprob, s));
+                     logprob, given, given_max, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0

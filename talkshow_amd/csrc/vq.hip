@@ -1199,4 +1199,562 @@ hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// "given" variants of the three samplers (talkshow_hip.h, "given rows"): clip b of a pass brings G_b code rows that are TAKEN, not drawn.
+// Kernels of their own: sample_kernel, sample_lp_kernel and the four sample_ctl_kernel instantiations above keep their source and their
+// code, and a pass without given rows its launches.  A workgroup (one per clip, 256 threads) is FORCED iff its absolute position
+// 2 row + column — the Philox counter word, the dynamic base word of a replayed graph included — is below 2 G[slot]: a workgroup-uniform
+// decision from kernel arguments and two uniform loads, taken before any barrier.  A forced workgroup reads its code from the staging
+// block, writes it to tok32 and codes, reads no uniform and draws nothing; with the log-probability output it computes the row's S and the
+// code's d_c exactly as its sibling does for a code it drew.  An unforced workgroup executes its sibling's arithmetic, operation for
+// operation.  A given code is compared, never used as an address; outside [0, V) it leaves -1 in tok32 (the chain's gathers read a
+// row of zeros for a negative index) and NaN as its log-probability.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ inline bool given_forced(const SampleParams &p, const SampleGivenParams &gp, int b) {
+    const uint32_t pos = p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u);
+    const int G = gp.rows[b];
+    return G > 0 && (uint64_t)pos < 2ull * (uint64_t)G;
+}
+__device__ inline int given_token(long long code, int V) { return code >= 0 && code < (long long)V ? (int)code : -1; }
+
+__global__ __launch_bounds__(256) void sample_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    const SampleParams &p = gp.c.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+
+    const int chunk = (p.V + 255) / 256;
+    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
+    const bool fast = chunk == 8 && (p.V & 7) == 0;
+    float x[8];
+    if (fast) {
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
+    }
+
+    if (p.logits_copy) {
+        float *dst = p.logits_copy + (long)b * p.copy_stride;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
+        } else {
+            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
+        }
+    }
+
+    if (given_forced(p, gp, b)) {   // workgroup-uniform, ahead of every barrier
+        if (tid == 0) {
+            const long long code = gp.given[(long)b * gp.given_stride];
+            p.tok32[(long)b * p.tok_stride] = given_token(code, p.V);
+            p.codes[(long)b * p.code_stride] = code;
+        }
+        return;
+    }
+
+    // ---- from here on: sample_kernel ----
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (fast) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (x[k] > best) { best = x[k]; bi = v0 + k; }
+    } else {
+        for (int v = v0; v < v1; ++v) {
+            const float t = lg[v];
+            if (t > best) { best = t; bi = v; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
+    __syncthreads();
+    best = sf[0]; bi = si[0];
+    for (int w = 1; w < 4; ++w)
+        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
+    __syncthreads();
+
+    int choice = bi;
+    if (p.mode != TS_SAMPLE_GREEDY) {
+        float u;
+        if (p.mode == TS_SAMPLE_UNIFORMS) {
+            u = p.uniforms[(long)b * p.u_stride];
+        } else {
+            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
+            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+            uint32_t r;
+            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
+                          (uint32_t)(seed >> 32), r);
+            u = (float)(r >> 8) * (1.0f / 16777216.0f);
+        }
+        float s = 0.f;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += det_expf(x[k] - best);
+        } else {
+            for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
+        }
+        sf[tid + 1] = s;
+        __syncthreads();
+        if (tid == 0) {
+            float c = 0.f;
+            sf[0] = 0.f;
+            for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }
+            s_thr = u * c;
+        }
+        __syncthreads();
+        const float thr = s_thr;
+        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
+        if (mine && v0 < p.V) {
+            float c = sf[tid];
+            int k = v1 - 1;
+            if (fast) {
+                bool found = false;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    c += det_expf(x[j] - best);
+                    if (!found && c > thr) { k = v0 + j; found = true; }
+                }
+            } else {
+                for (int v = v0; v < v1; ++v) {
+                    c += det_expf(lg[v] - best);
+                    if (c > thr) { k = v; break; }
+                }
+            }
+            si[0] = k;
+        } else if (mine) {
+            si[0] = p.V - 1;
+        }
+        __syncthreads();
+        choice = si[0];
+    }
+    if (tid == 0) {
+        p.tok32[(long)b * p.tok_stride] = choice;
+        p.codes[(long)b * p.code_stride] = choice;
+    }
+}
+
+// sample_lp_kernel with given rows: a forced workgroup is that kernel's teacher-forced path (the total S in the samplers' summation
+// structure, the logit picked up by the thread that owns the code) on a code read from the staging block, which it also writes out
+__global__ __launch_bounds__(256) void sample_lp_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    const SampleParams &p = gp.c.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+    const bool forced = given_forced(p, gp, b);   // workgroup-uniform, ahead of every barrier
+
+    const int chunk = (p.V + 255) / 256;
+    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
+    const bool fast = p.V == 2048 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
+    float x[8];
+    if (fast) {
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
+    }
+
+    if (p.logits_copy) {
+        float *dst = p.logits_copy + (long)b * p.copy_stride;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
+        } else {
+            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
+        }
+    }
+
+    // ---- max / argmax; ties -> lowest index ----
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (fast) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (x[k] > best) { best = x[k]; bi = v0 + k; }
+    } else {
+        for (int v = v0; v < v1; ++v) {
+            const float t = lg[v];
+            if (t > best) { best = t; bi = v; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
+    __syncthreads();
+    best = sf[0]; bi = si[0];
+    for (int w = 1; w < 4; ++w)
+        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
+    __syncthreads();
+
+    // ---- the total, in every mode: sf[t] = sum of the chunks < t, sf[256] = S ----
+    float s = 0.f;
+    if (fast) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += det_expf(x[k] - best);
+    } else {
+        for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
+    }
+    sf[tid + 1] = s;
+    __syncthreads();
+    const bool draws = !forced && (p.mode == TS_SAMPLE_UNIFORMS || p.mode == TS_SAMPLE_PHILOX);
+    if (tid == 0) {
+        float u = 0.f;
+        if (draws && p.mode == TS_SAMPLE_UNIFORMS) {   // the uniform of a forced row is never read
+            u = p.uniforms[(long)b * p.u_stride];
+        } else if (draws) {
+            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
+            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+            uint32_t r;
+            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
+                          (uint32_t)(seed >> 32), r);
+            u = (float)(r >> 8) * (1.0f / 16777216.0f);
+        }
+        float c = 0.f;
+        sf[0] = 0.f;
+        for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }
+        s_thr = u * c;
+    }
+    __syncthreads();
+
+    long long code;   // 64 bits: a given code is compared, never truncated
+    if (forced) {
+        code = gp.given[(long)b * gp.given_stride];
+    } else if (!draws) {
+        code = bi;
+    } else {
+        const float thr = s_thr;
+        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
+        if (mine && v0 < p.V) {
+            float c = sf[tid];
+            int k = v1 - 1;
+            if (fast) {
+                bool found = false;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    c += det_expf(x[j] - best);
+                    if (!found && c > thr) { k = v0 + j; found = true; }
+                }
+            } else {
+                for (int v = v0; v < v1; ++v) {
+                    c += det_expf(lg[v] - best);
+                    if (c > thr) { k = v; break; }
+                }
+            }
+            si[0] = k;
+        } else if (mine) {
+            si[0] = p.V - 1;
+        }
+        __syncthreads();
+        code = si[0];
+    }
+
+    float *out = gp.c.logprob + (long)b * gp.c.lp_stride;
+    if (code >= (long long)v0 && code < (long long)v1) {   // the owner of index `code`: exactly one thread, or none when it is out of range
+        float lc = 0.f;
+        if (fast) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if ((long long)(v0 + k) == code) lc = x[k];
+        } else {
+            for (int v = v0; v < v1; ++v)
+                if ((long long)v == code) lc = lg[v];
+        }
+        *out = logprob_value(lc - best, sf[256]);
+    }
+    if (tid == 0) {
+        if (code < 0 || code >= (long long)p.V) *out = __uint_as_float(0x7fc00000u);
+        p.tok32[(long)b * p.tok_stride] = given_token(code, p.V);
+        p.codes[(long)b * p.code_stride] = code;
+    }
+}
+
+// sample_ctl_kernel with given rows.  Without the log-probability output a forced workgroup leaves ahead of everything; with it, it runs
+// steps 1-4 and the sums of step 5 as its sibling does (the thread that owns the given code notes whether the filters kept it), then
+// writes d_c - log S for a kept code and log(0) for a code the filters removed: the code's weight in the distribution the row would have
+// been drawn from is 0.
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    const SampleCtlParams &cp = gp.c;
+    const SampleParams &p = cp.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+    const bool forced = given_forced(p, gp, b);   // workgroup-uniform, ahead of every barrier
+    const long long gcode = forced ? (long long)gp.given[(long)b * gp.given_stride] : -1;
+
+    const int chunk = (p.V + 255) / 256;
+    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
+    const int n = FAST ? 8 : max(v1 - v0, 0);
+    float x[8];
+    if constexpr (FAST) {
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
+    }
+    auto logit = [&](int k) -> float {
+        if constexpr (FAST) return x[k];
+        else return lg[v0 + k];
+    };
+    if (p.logits_copy) {
+        float *dst = p.logits_copy + (long)b * p.copy_stride;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) dst[v0 + k] = logit(k);
+    }
+    if constexpr (!LP) {
+        if (forced) {
+            if (tid == 0) {
+                p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
+                p.codes[(long)b * p.code_stride] = gcode;
+            }
+            return;
+        }
+    }
+
+    const SampleCtl rec = cp.ctl[b];
+    CtlSel S;
+    S.need_k = rec.top_k >= 1 && rec.top_k < p.V;
+    S.need_p = rec.top_p < 1.0f;
+    const bool sel = S.need_k || S.need_p;
+    if (sel) {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) hist[i][tid] = 0;
+    }
+
+    // ---- max / argmax as in sample_kernel; ties -> lowest index ----
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll 8
+    for (int k = 0; k < n; ++k) {
+        const float t = logit(k);
+        if (t > best) { best = t; bi = v0 + k; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
+    __syncthreads();
+    best = sf[0]; bi = si[0];
+    for (int w = 1; w < 4; ++w)
+        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
+    __syncthreads();
+
+    // the uniform: the same source as sample_kernel; a forced row reads none
+    float u = 0.f;
+    if (forced) {
+    } else if (p.mode == TS_SAMPLE_UNIFORMS) {
+        u = p.uniforms[(long)b * p.u_stride];
+    } else {
+        const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
+        const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+        uint32_t r;
+        philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
+                      (uint32_t)(seed >> 32), r);
+        u = (float)(r >> 8) * (1.0f / 16777216.0f);
+    }
+
+    const float inv_t = rec.inv_t;
+    auto weight = [&](int k) -> float { return ctl_weight(logit(k), best, inv_t); };
+
+    // ---- steps 2-4: the kept set ----
+    uint32_t key[8], q[8];
+    auto key_of = [&](int k) -> uint32_t {
+        if constexpr (FAST) return key[k];
+        else return ctl_key(lg[v0 + k]);
+    };
+    auto q_of = [&](int k) -> uint32_t {
+        if constexpr (FAST) return q[k];
+        else return ctl_quant(weight(k));
+    };
+    int jk0 = 0, jp0 = 0;
+    if (sel) {
+        if constexpr (FAST) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { key[k] = ctl_key(x[k]); q[k] = ctl_quant(weight(k)); }
+        }
+        auto fill = [&](ctl_u64 *h, int lv, uint32_t prefix) {
+#pragma unroll 8
+            for (int k = 0; k < n; ++k) {
+                const uint32_t ky = key_of(k);
+                if (lv == 0 || (ky >> (32 - 8 * lv)) == prefix)
+                    atomicAdd(&h[(ky >> (24 - 8 * lv)) & 255u], (1ull << CTL_CNT_SHIFT) | (ctl_u64)q_of(k));
+            }
+            __syncthreads();
+        };
+        fill(hist[0], 0, 0u);
+        ctl_u64 Qk;
+        if (S.need_k) {
+            uint32_t prefix = 0;
+            ctl_u64 acc = 0;
+            for (int lv = 0; lv < 4; ++lv) {
+                if (lv > 0) fill(hist[lv], lv, prefix);
+                prefix = (prefix << 8) | (uint32_t)(ctl_pick_bin(hist[lv], lane, false, (ctl_u64)rec.top_k, acc) & 255);
+            }
+            S.Kk = prefix;
+            S.ntie_k = rec.top_k - (int)(acc >> CTL_CNT_SHIFT);
+            Qk = (acc & CTL_MASS_MASK) + (ctl_u64)S.ntie_k * ctl_quant(ctl_weight(ctl_unkey(prefix), best, inv_t));
+        } else {
+            S.Kk = 0;
+            S.ntie_k = 0;
+            Qk = ctl_hist_total(hist[0], lane) & CTL_MASS_MASK;
+        }
+        S.Kp = 0; S.p_top = false; S.mgt_p = S.q_p = S.Tq = 0;
+        if (S.need_p) {
+            S.Tq = (ctl_u64)ceil((double)rec.top_p * (double)Qk);
+            uint32_t prefix = 0;
+            ctl_u64 acc = 0;
+            for (int lv = 0; lv < 4; ++lv) {
+                ctl_u64 *h = lv == 0 ? hist[0] : hist[3 + lv];
+                if (lv > 0) fill(h, lv, prefix);
+                prefix = (prefix << 8) | (uint32_t)(ctl_pick_bin(h, lane, true, S.Tq, acc) & 255);
+            }
+            S.Kp = prefix;
+            S.mgt_p = acc & CTL_MASS_MASK;
+            S.p_top = (acc >> CTL_CNT_SHIFT) == 0;
+            S.q_p = ctl_quant(ctl_weight(ctl_unkey(prefix), best, inv_t));
+        }
+        uint32_t c = 0;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) {
+            const uint32_t ky = key_of(k);
+            c += (S.need_k && ky == S.Kk ? 1u : 0u) + (S.need_p && ky == S.Kp ? 65536u : 0u);
+        }
+        uint32_t inc = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(inc, off);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) s_tie[wave] = inc;
+        __syncthreads();
+        uint32_t ex = inc - c;
+        for (int w = 0; w < wave; ++w) ex += s_tie[w];
+        jk0 = (int)(ex & 0xffffu);
+        jp0 = (int)(ex >> 16);
+    }
+
+    // ---- step 5: the sums over w' = kept ? w : 0; the owner of a given code notes its logit and whether it was kept ----
+    float s = 0.f;
+    int hi = -1;
+    bool gkept = false;
+    float glc = 0.f;
+    {
+        int jk = jk0, jp = jp0;
+        unsigned char *kd = cp.kept ? cp.kept + (long)b * p.V : nullptr;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) {
+            const bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
+            if (kp) { s += weight(k); hi = v0 + k; }
+            if (kd) kd[v0 + k] = kp ? 1 : 0;
+            if constexpr (LP) {
+                if ((long long)(v0 + k) == gcode) { gkept = kp; glc = logit(k); }
+            }
+        }
+    }
+    sf[tid + 1] = s;
+    si[tid] = hi;
+    __syncthreads();
+    if (tid == 0) {
+        float c = 0.f;
+        int last = 0;
+        sf[0] = 0.f;
+        for (int t = 1; t <= 256; ++t) {
+            c += sf[t]; sf[t] = c;
+            if (si[t - 1] >= 0) last = si[t - 1];
+        }
+        s_thr = u * c;
+        s_last = last;
+    }
+    __syncthreads();
+    if constexpr (LP) {
+        if (forced) {   // workgroup-uniform: S = sf[256] is there, nothing is drawn
+            float *out = cp.logprob + (long)b * cp.lp_stride;
+            if (gcode >= (long long)v0 && gcode < (long long)v1)
+                *out = gkept ? logprob_value(ctl_arg(glc, best, inv_t), sf[256]) : (float)log(0.0);
+            if (tid == 0) {
+                if (gcode < 0 || gcode >= (long long)p.V) *out = __uint_as_float(0x7fc00000u);
+                p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
+                p.codes[(long)b * p.code_stride] = gcode;
+            }
+            return;
+        }
+    }
+    const float thr = s_thr;
+    const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
+    const int last = s_last;
+    __syncthreads();
+    if (mine) {
+        int res = -1;
+        float c = sf[tid];
+        int jk = jk0, jp = jp0;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) {
+            if (!sel || ctl_keep(S, key_of(k), jk, jp)) {
+                c += weight(k);
+                if (res < 0 && c > thr) res = v0 + k;
+            }
+        }
+        if (res < 0) res = (thr < sf[tid + 1] && hi >= 0) ? hi : last;
+        si[0] = res;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int choice = si[0];
+        p.tok32[(long)b * p.tok_stride] = choice;
+        p.codes[(long)b * p.code_stride] = choice;
+    }
+    if constexpr (LP) {
+        const int choice = si[0];
+        if (choice >= v0 && choice < v1) {
+            float lc = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < n; ++k)
+                if (v0 + k == choice) lc = logit(k);
+            cp.logprob[(long)b * cp.lp_stride] = logprob_value(ctl_arg(lc, best, inv_t), sf[256]);
+        }
+    }
+}
+
+hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
+    const SampleParams &s = p.c.s;
+    if (!p.rows || !p.given || s.V < 1) return hipErrorInvalidValue;
+    if (s.mode != TS_SAMPLE_GREEDY && s.mode != TS_SAMPLE_UNIFORMS && s.mode != TS_SAMPLE_PHILOX) return hipErrorInvalidValue;
+    if (!p.c.ctl) {
+        if (p.c.kept) return hipErrorInvalidValue;
+        if (p.c.logprob) hipLaunchKernelGGL(sample_lp_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(sample_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    }
+    if (s.V > SAMPLE_CTL_MAX_V || s.mode == TS_SAMPLE_GREEDY) return hipErrorInvalidValue;
+    const long ls = s.logit_stride ? s.logit_stride : (long)s.V;
+    const bool fast = s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(s.logits) & 15) == 0;
+    if (p.c.logprob) {
+        if (fast) hipLaunchKernelGGL((sample_ctl_given_kernel<true, true>), dim3(s.B), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((sample_ctl_given_kernel<false, true>), dim3(s.B), dim3(256), 0, stream, p);
+    } else if (fast) {
+        hipLaunchKernelGGL((sample_ctl_given_kernel<true, false>), dim3(s.B), dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL((sample_ctl_given_kernel<false, false>), dim3(s.B), dim3(256), 0, stream, p);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace ts

@@ -341,14 +341,25 @@ class GatedPixelCNN(NativeModule):
         (_lib.load().ts_pixelcnn_destroy if self.bh_model else _lib.load().ts_pixelcnn_v_destroy)(h)
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
-            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False):
+            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
         are the network's, before any control.  bh_model=False takes none.
         logprobs: True, or a float32 (B,H,2) device tensor to fill -> a THIRD return value, the log-probability of every code under the
         distribution it was drawn from (`ts_pixelcnn_generate_lp`; teacher forced: of the given codes under the model's); the decode
-        stays on its graphs.  False (the default): two return values and the launches there always were."""
+        stays on its graphs.  False (the default): two return values and the launches there always were.
+        given: one (B,G,2) integer block, or a list of B entries (None or a (G_b,2) integer array): clip b's first G_b code rows are TAKEN
+        from it and the rest produced as without it (`ts_pixelcnn_generate_mixed_given`, the mixed entry with equal lengths; aud_rows is the
+        clip's whole audio).  The codes returned hold the given rows followed by the produced ones; with logprobs, a given row gets the
+        log-probability of its code under the distribution it would have been drawn from (`sampling.given_logprob`).  A code outside
+        [0, input_dim), a bad shape or G_b > H raises ValueError naming the clip before any device work.  Not with want_logits, pre_codes or
+        TS_TEACHER_FORCED.  None (the default): no return value and no launch changes."""
+        if given is not None:
+            if not self.bh_model:
+                raise NotImplementedError("given rows exist for the bh_model=True chain (ts_pixelcnn_generate_mixed_given), not for the single-stack form")
+            if want_logits or pre_codes is not None or mode == _lib.TS_TEACHER_FORCED:
+                raise ValueError("run: given rows go through the mixed entry, which takes no logits output, no pre_codes and no teacher forcing")
         if sampling is not None and not self.bh_model:
             raise NotImplementedError("sampling controls exist for the bh_model=True chain (ts_pixelcnn_generate_ctl), not for the single-stack form")
         if logprobs is not None and logprobs is not False and not self.bh_model:
@@ -371,6 +382,8 @@ class GatedPixelCNN(NativeModule):
         ctl, n_ctl = None, 0
         if sampling is not None:   # validated (ValueError names the clip) before any device work
             ctl, n_ctl = _lib.sampling_table(sampling, B, self.input_dim, mode)
+        if given is not None:
+            block, table = _lib.given_block(given, [H] * B, self.input_dim, who="run")   # ValueError before any device work
         if self.bh_model and aud_rows is None:
             aud_rows = torch.zeros((B, H, self.aud_dim), dtype=torch.float32, device=dev)
         label = _index_tensor(label, self.n_classes, "class label", dev)
@@ -400,6 +413,18 @@ class GatedPixelCNN(NativeModule):
                 self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, W, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0, _lib.stream_ptr()))
             return codes, logits
+        if given is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
+            i32p = C.POINTER(C.c_int32)
+            lens = np.full(B, 4 * H, np.int32)
+            lens_dev, block_dev = upload(lens, dev), upload(block, dev)
+            clip_index = upload(np.arange(B, dtype=np.int64) + int(clip_index0), dev)
+            if isinstance(lp, str):
+                lp = torch.empty((B, H, 2), dtype=torch.float32, device=dev)
+            _lib.check(_lib.load().ts_pixelcnn_generate_mixed_given(
+                self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
+                _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), ctl, n_ctl, _lib.dptr(lp),
+                _lib.dptr(block_dev), table.ctypes.data_as(i32p), None, _lib.stream_ptr()))
+            return (codes, None) if lp is None else (codes, None, lp)
         args = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0)
         if lp is not None:

@@ -139,7 +139,8 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
     return assemble_full(torch.cat(poses, 0), torch.cat(faces, 0), stand=stand)
 
 
-def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None):
+def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None,
+                     given=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -153,7 +154,9 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     DEVICE tensor are range-checked once per tensor version, which reads them back; host ids are checked on the host).  A recording's rows are bit-identical to the route of uniform entries on the recording alone
     (`MFCC` -> `generate_batch`, `FaceGenerator.run_clips`, `assemble_full`), its Philox subsequence is `clip_index0` + its position in
     the submitted list.  sampling: one sampling record (`_lib.sampling_record`) for all recordings or one per recording in submission order —
-    they follow the recordings through the sort (the body branch then runs `ts_body_pixel_infer_mixed_ctl`; the face generator takes none)."""
+    they follow the recordings through the sort (the body branch then runs `ts_body_pixel_infer_mixed_ctl`; the face generator takes none).
+    given: one entry per recording in submission order, None or the (G_b, 2) code rows the body decode of that recording starts from
+    (`TrainWrapper.generate_clips`; the body branch then runs `ts_body_pixel_infer_mixed_given`); they follow the recordings through the sort."""
     import ctypes as C
 
     import numpy as np
@@ -188,6 +191,11 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if sampling is not None:   # validated before the first launch; sorted slot k holds the record of submitted recording order[k]
         recs = _lib.sampling_records(sampling, B)
         sampling = _lib.sampling_table([recs[i] for i in order], B, body.generator.input_dim, mode)
+    if given is not None:      # validated before the first launch, too: rows_sub[i] = code rows of submitted recording i
+        rows_sub = [0] * B
+        for k, i in enumerate(order):
+            rows_sub[i] = int(tab["mfcc_rows"][k]) // 4
+        given = _lib.given_block(given, rows_sub, body.generator.input_dim, order, who="whole_body_clips")
     dev = body.generator._dev()
     # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
     wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
@@ -203,7 +211,8 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if overlap:
         side.wait_stream(cur)
     with torch.cuda.stream(side):
-        _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling)
+        _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling,
+                                               given=given)
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

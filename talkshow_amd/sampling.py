@@ -161,6 +161,48 @@ def logprob(row, code, record=None):
     return F32(np.float64(d[code]) - np.log(np.float64(S)))
 
 
+def given_logprob(row, code, record=None):
+    """The log-probability a GIVEN code gets on the logits `row` (include/talkshow_hip.h, "given rows"): that of `code` under the
+    distribution the row would have been drawn from.  Without a record: `logprob(row, code)`, the teacher-forced value.  With one: the
+    same expression over the kept weights when the record keeps `code` — the bits a draw of it gets — and log(0) = -inf when the filters
+    removed it (its weight in that distribution is 0); top_k = 1 therefore gives 0 for the argmax and -inf for every other code.  NaN for a
+    code outside [0, V)."""
+    row = np.asarray(row, F32).reshape(-1)
+    code = int(code)
+    if not 0 <= code < row.size:
+        return F32(np.nan)
+    if record is not None and not keep_mask(row, record)[code]:
+        with np.errstate(divide="ignore"):
+            return F32(np.log(np.float64(0.0)))
+    return logprob(row, code, record)
+
+
+def sample_given(logits, u, forced, given, records=None, greedy=False):
+    """One launch of the samplers' given variants, restated: logits (B,V), u (B,) uniforms (those of forced rows are not read), forced (B,)
+    flags, given (B,) codes (those of unforced rows are not read), records = None, one record or B -> (idx (B,) int64, logprob (B,)
+    float32).  A forced row returns its given code and `given_logprob` of it; an unforced row what the sampler it stands in for returns:
+    `sample_ctl` with records, the plain inverse CDF (a neutral record's draw) or, greedy, the first maximum."""
+    logits = np.asarray(logits, F32)
+    B, V = logits.shape
+    if records is not None and isinstance(records, tuple) and len(records) == 3 and not isinstance(records[0], (tuple, list)):
+        records = [records] * B
+    idx = np.zeros(B, np.int64)
+    lp = np.zeros(B, F32)
+    for b in range(B):
+        rec = None if records is None else records[b]
+        if forced[b]:
+            idx[b] = int(given[b])
+            lp[b] = given_logprob(logits[b], idx[b], rec)
+            continue
+        if greedy:
+            idx[b] = int(np.argmax(logits[b]))
+        else:
+            r = (1.0, 1.0, 0) if rec is None else rec
+            idx[b] = draw(logits[b], u[b], r[0], keep_mask(logits[b], r))
+        lp[b] = logprob(logits[b], idx[b], rec)
+    return idx, lp
+
+
 LOGPROB_SUM_LANES = 256
 
 
