@@ -449,6 +449,42 @@ int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *pix, const int64_t *label_dev,
                                      const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
                                      float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
                                      const int32_t *given_rows_dev, void *stream);
+/* ---- given poses: continue, resume and score from MOTION ---------------------------------------------------------------------------------
+ * The entries of "given rows" start from codes; a host usually holds pose frames (the reference's `infer(..., pre_latents, pre_audio)` gets
+ * pre_latents by encoding the poses of the previous window).  These entries encode the frames of many clips of DIFFERENT lengths in one pass
+ * and hand the codes to the chain on the device: no synchronisation, no host copy of codes.
+ *   poses_dev (B,P_max,ld) fp32, body columns [0, body_dim) and hand columns [body_dim, body_dim + hand_dim) of every row, as in
+ *     ts_body_vq_infer; frames at or beyond a clip's own P_b are never read (they may hold anything, NaNs included);
+ *   pose lens (B,) int32: P_b, the clip's own frame count, in ANY order (the encoders have no prefix structure).  The device table feeds the
+ *     kernels; where a host table is taken too, it plans the pass and is not read after the call returns.
+ * THE RULE.  Clip b has P_b / 4 code rows.  Every encoder layer is length-masked (ts_audioenc_forward_masked's scheme: whole-tile plans,
+ * sk_ok = 0, no stream-K band), pre_vq_conv is masked at P_b / 4, and ONE kernel searches both codebooks: row h of clip b is valid iff
+ * h < P_b / 4; a valid row gets exactly the index the uniform entries return for it (same arithmetic, operation for operation), an invalid
+ * row gets -1 — the padding of every mixed pass — and its latent row is never read.  A clip's codes, latents and reconstruction are
+ * bit-identical to ts_vqvae_encode / ts_body_vq_infer on the clip alone, whatever its neighbours and the padding hold.
+ * ts_given_pose_rows_check is the host rule of a pass that CONTINUES from poses: P_b == 0 (nothing given), or P_b >= 4 with
+ * P_b / 4 <= lens[b] / 4 (lens: the pass's MFCC frame counts); the clip then brings G_b = P_b / 4 given rows.  1 <= P_b <= 3 is an error (a
+ * caller who hands over frames that cannot make one code row has miscounted), reported with the clip's index before anything is launched. */
+/* VQVAE.encode of both parts, clips of different lengths: codes_dev (B,T_max/4,2) int64, -1 beyond a clip's rows; z_body_dev / z_hand_dev
+ * (B,T_max/4,embedding_dim) or NULL: the encoders' outputs, 0 beyond a clip's rows.  T_max < 4 fails as the uniform encode does. */
+int ts_vqvae_encode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *poses_dev, int poses_ld, const int32_t *lens_dev, int B,
+                                int T_max, int64_t *codes_dev, float *z_body_dev, float *z_hand_dev, void *stream);
+/* ts_body_vq_infer for clips of different lengths: poses_dev (B,T_max,body_dim+hand_dim) -> codes_dev (B,T_max/4,2) with -1 and recon_dev
+ * (B,4 (T_max/4),body_dim+hand_dim) with 0 beyond a clip's rows (the encode above, then ts_vqvae_decode_pair_masked).  Either may be NULL. */
+int ts_body_vq_infer_mixed(ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *poses_dev, const int32_t *lens_dev, int B, int T_max,
+                           int64_t *codes_dev, float *recon_dev, void *stream);
+int ts_given_pose_rows_check(const int32_t *pose_lens_host, const int32_t *lens_host, int B);
+/* ts_body_pixel_infer_mixed_given whose given block is PRODUCED here: given_poses_dev (B,P_max,body_dim+hand_dim), pose_lens_host /
+ * pose_lens_dev (B,) in the order of the submitted, sorted clips.  The encoders run in front of the pass as the audio encoder does, into a
+ * code block of the stream's work buffers; G_b = P_b / 4 is set on the host; then exactly what the _given entry runs, with the same graphs.
+ * P_max / 4 <= T_max / 4.  given_poses_dev == NULL, or every P_b == 0: exactly the _lp entry.  Passes that do not use this entry launch
+ * what they launched before it existed. */
+int ts_body_pixel_infer_mixed_poses(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                    const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                    const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                    float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                    const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                    void *stream);
 /* ts_vqvae_decode_pair with length-masked layers: latents (B,H) each, rows at or beyond lens[b] / 4 are not read (gathered as zero rows;
  * an index outside the codebook INSIDE a clip still gives NaNs); out_dev (B,4H,body_dim+hand_dim), rows at or beyond 4 (lens[b] / 4) = 0. */
 int ts_vqvae_decode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *lat_body_dev, const int64_t *lat_hand_dev,

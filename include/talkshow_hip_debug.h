@@ -279,6 +279,20 @@ int ts_debug_pixelcnn_graphs(ts_pixelcnn *pix, void *stream);
  * -1 on a bad table.  No reference counterpart. */
 int ts_debug_mixed_plan(const int32_t *hrows, int B, int max_counts, int32_t *active_out);
 
+/* Test aid: the paired, length-masked codebook search of a mixed pass on given latents (talkshow_hip.h, "given poses"; csrc/vq.hip:
+ * vq_argmin_pair_lds_kernel).  z_body_dev (B H_max, dim_body), z_hand_dev (B H_max, dim_hand), lens_dev (B,) int32 POSE frame counts in any
+ * order, codebooks (ncode, dim) in device memory -> codes_dev (B, H_max, 2) int64: column 0 / 1 = body / hand; row h of clip b holds what
+ * ts_op_vq_argmin returns for that row of z if h < lens[b] / 4, else -1 (the row of z is then not read).  Networks with dim = 64 and one
+ * ncode take the paired LDS kernel, every other pair two launches of the masked generic kernel. */
+int ts_op_vq_argmin_pair_masked(ts_ctx *ctx, const float *z_body_dev, const float *z_hand_dev, const int32_t *lens_dev, int B, int H_max,
+                                const float *codebook_body_dev, const float *codebook_hand_dev, int ncode_body, int ncode_hand, int dim_body,
+                                int dim_hand, int64_t *codes_dev, void *stream);
+/* The same with the launch form named — 0: the library's choice (TS_VQ_PAIR), 1: one paired launch, 2: one launch per network, 3: the masked
+ * generic kernel — and `iters` >= 1 launches queued back to back ahead of the one synchronisation (tools/poses_pass.py times them). */
+int ts_debug_vq_argmin_pair_masked(ts_ctx *ctx, const float *z_body_dev, const float *z_hand_dev, const int32_t *lens_dev, int B, int H_max,
+                                   const float *codebook_body_dev, const float *codebook_hand_dev, int ncode_body, int ncode_hand,
+                                   int dim_body, int dim_hand, int64_t *codes_dev, int form, int iters, void *stream);
+
 /* Tuning entry (not part of the drop-in surface): `iters` DEPENDENT skinny_gemm launches replayed from one hipGraph;
  * *us_out = microseconds per launch.  gate != 0: N = 2K with the tanh*sigmoid epilogue; debug: unused. */
 int ts_debug_skinny_chain(ts_ctx *ctx, int M, int K, int gate, int iters, int debug, float *us_out);

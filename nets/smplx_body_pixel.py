@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None):
+                       logprobs=False, given=None, given_poses=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -110,15 +110,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         (`ts_body_pixel_infer_mixed_lp`: the route of `sampling`, with or without a record; codes and poses are those of the call without it).
         given: one (B,G,2) integer block or a list of B entries (None or (G_b,2)): the clips' first code rows, taken instead of drawn
         (`generate_clips`, `ts_body_pixel_infer_mixed_given`).  None: nothing changes.
+        given_poses: one (B,P,129) block or a list of B entries (None or (P_b,129)): the clips' first pose frames, encoded on the device into
+        their first P_b // 4 code rows (`generate_clips`, `ts_body_pixel_infer_mixed_poses`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
-        if sampling is not None or logprobs or given is not None:
+        if sampling is not None or logprobs or given is not None or given_poses is not None:
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
-                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given)
+                                       _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
+                                       given_poses=given_poses)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -216,7 +219,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
-                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None):
+                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -234,7 +237,14 @@ class TrainWrapper(TrainWrapperBaseClass):
         clip's whole audio).  The entries are carried through the length sort exactly as the sampling records and `clip_indices` are.  Given
         the first rows of an earlier decode of the clip (same seed, index and record) the pass returns that decode bit for bit; a given
         row's log-probability is that of its code under the distribution it would have been drawn from (-inf for a code the record's
-        filters remove).  A bad shape, G_b > H_b or a code outside [0, V) raises ValueError naming the clip before anything is launched."""
+        filters remove).  A bad shape, G_b > H_b or a code outside [0, V) raises ValueError naming the clip before anything is launched.
+        given_poses: the same from MOTION — a list in submission order with None or a (P_b,129) float array per clip (or one (B,P,129) block),
+        P_b = 0 or 4 <= P_b with P_b // 4 <= H_b: the frames are encoded on the device (`ts_body_pixel_infer_mixed_poses`: both VQ encoders,
+        length-masked, in front of the pass; no synchronisation, no host copy of codes) and the clip continues from its first P_b // 4 code
+        rows, exactly as with `given=` set to `encode_clips`' codes of those frames.  The frames are in the wrapper's own pose layout: the
+        129 c_index columns this method RETURNS (the VQ-VAEs' side; a caller who un-normalised or re-ordered its poses for display hands
+        back the rows as they were before that).  A clip brings `given` or `given_poses`, never both (ValueError naming the clip); a pass may
+        hold both kinds.  1 <= P_b <= 3, P_b // 4 > H_b or a wrong width raises ValueError naming the clip before anything is launched."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -264,6 +274,13 @@ class TrainWrapper(TrainWrapperBaseClass):
         gblock = gtable = None
         if given is not None:      # sorted slot k holds the given rows of submitted clip order[k]; validated before anything is launched
             gblock, gtable = _lib.given_block(given, [t // 4 for t in lens], self.generator.input_dim, order, who="generate_clips")
+        pblock = ptable = None
+        if given_poses is not None:
+            _lib.given_kinds_check(given, given_poses, B, "generate_clips")
+            pblock, ptable = _lib.given_pose_block(given_poses, [t // 4 for t in lens], order, who="generate_clips",
+                                                   width=self.each_dim[1] + self.each_dim[2])
+            if int(ptable.max()) == 0:      # nothing given anywhere: the pass without the keyword
+                pblock = ptable = None
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -298,7 +315,17 @@ class TrainWrapper(TrainWrapperBaseClass):
                 _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
         lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
-        if gblock is not None:
+        i32p = _lib.C.POINTER(_lib.C.c_int32)
+        if pblock is not None and gblock is None:
+            from talkshow_amd.modules import upload
+            pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]),
+                                                                   ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)), _lib.stream_ptr()))
+        elif pblock is not None:      # both kinds in one pass: the pose clips' codes join the code clips' in one block, on the device
+            gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
+            _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), gtable.ctypes.data_as(i32p),
+                                                                   None, _lib.stream_ptr()))
+        elif gblock is not None:
             from talkshow_amd.modules import upload
             gdev = upload(gblock, dev)
             _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev),
@@ -320,13 +347,109 @@ class TrainWrapper(TrainWrapperBaseClass):
             return codes, poses
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
-    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None):
+    def _stage_given(self, gblock, gtable, pblock, ptable, dev):
+        """One given block for a pass that holds code clips AND pose clips: gblock / gtable from `_lib.given_block`, pblock / ptable from
+        `_lib.given_pose_block` (slot order; no clip is in both) -> ((B,H_max,2) int64 device block, (B,) int32 host table).  The pose
+        clips are encoded on the device (`ts_vqvae_encode_pair_masked`, the kernels `ts_body_pixel_infer_mixed_poses` runs) and their rows
+        selected into the uploaded code block there: nothing is read back."""
+        from talkshow_amd.modules import encode_pair_masked, upload
+        pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
+        gdev = upload(gblock, dev)
+        enc = encode_pair_masked(self.g_body, self.g_hand, pdev, upload(ptable, dev))          # (B, P_max // 4, 2), -1 beyond a clip's rows
+        Hp = min(int(enc.shape[1]), int(gdev.shape[1]))
+        from_poses = upload(np.ascontiguousarray(ptable > 0), dev)[:, None, None]
+        gdev[:, :Hp] = torch.where(from_poses, enc[:, :Hp], gdev[:, :Hp])
+        return gdev, np.ascontiguousarray(gtable + ptable // 4, dtype=np.int32)
+
+    def _score_pass(self, mfcc_list, ids, who, make_given):
+        """The shared body of `score_clips` / `score_motion_clips`: the masked audio encoder, `ts_pixelcnn_generate_mixed_given` with every
+        row given (G_b = H_b: nothing is drawn) and the log-probability output, `ts_logprob_sums` with the length table."""
+        from talkshow_amd.modules import upload
+        dev = self.generator._dev()
+        B = len(mfcc_list)
+        if B < 1:
+            raise ValueError(f"{who}: no clips")
+        clips = [torch.as_tensor(m, dtype=torch.float32, device=dev) for m in mfcc_list]
+        lens = [int(m.shape[0]) for m in clips]
+        for b, (m, t) in enumerate(zip(clips, lens)):
+            if m.dim() != 2 or m.shape[1] != 64:
+                raise ValueError(f"{who}: clip {b} must have shape (T, 64), got {tuple(m.shape)}")
+            if t < 4:
+                raise ValueError(f"{who}: clip {b} has {t} MFCC rows; one code row needs 4")
+        order, inverse = mixed_pass_order(lens)
+        rows = [t // 4 for t in lens]
+        given = make_given(rows, order, dev)               # validated on the host before anything is launched; (B,H_max,2) device block
+        ids = _index_tensor(ids, self.num_classes, 'speaker id', dev)
+        if ids.numel() == 1 and B > 1:
+            ids = ids.repeat(B)
+        if ids.numel() != B:
+            raise ValueError(f"ids must hold 1 or B={B} speaker indices, got {ids.numel()}")
+        T_max, H_max = lens[order[0]], lens[order[0]] // 4
+        mf = torch.zeros((B, T_max, 64), dtype=torch.float32, device=dev)
+        for k, i in enumerate(order):
+            mf[k, :lens[i]] = clips[i]
+        lens_host = np.asarray([lens[i] for i in order], dtype=np.int32)
+        table = np.asarray([rows[i] for i in order], dtype=np.int32)
+        lens_dev = upload(lens_host, dev)
+        ids_sorted = ids.index_select(0, torch.as_tensor(order, dtype=torch.int64, device=dev)).contiguous()
+        feat = torch.empty((B, H_max, self.audioencoder.num_hiddens), dtype=torch.float32, device=dev)
+        codes = torch.empty((B, H_max, 2), dtype=torch.int64, device=dev)
+        lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev)
+        sums = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        lib, i32p = _lib.load(), _lib.C.POINTER(_lib.C.c_int32)
+        _lib.check(lib.ts_audioenc_forward_masked(self.audioencoder.handle(), _lib.dptr(mf), _lib.dptr(lens_dev), B, T_max, _lib.dptr(feat),
+                                                  _lib.stream_ptr()))
+        _lib.check(lib.ts_pixelcnn_generate_mixed_given(self.generator.handle(), _lib.dptr(ids_sorted), _lib.dptr(feat), lens_host.ctypes.data_as(i32p),
+                                                        _lib.dptr(lens_dev), B, H_max, _lib.TS_SAMPLE_GREEDY, None, 0, None, _lib.dptr(codes), None, 0,
+                                                        _lib.dptr(lp), _lib.dptr(given), table.ctypes.data_as(i32p), None, _lib.stream_ptr()))
+        _lib.check(lib.ts_logprob_sums(self.generator._ctx(), _lib.dptr(lp), _lib.dptr(lens_dev), B, H_max, _lib.dptr(sums), _lib.stream_ptr()))
+        return [(lp[inverse[b], :rows[b]], sums[inverse[b]]) for b in range(B)]
+
+    def score_clips(self, mfcc_list, ids, codes_list):
+        """`score_batch` for clips of DIFFERENT lengths in ONE pass: mfcc_list = list of (T_b,64), ids (B,) or one for all, codes_list = list
+        of (T_b // 4, 2) integer arrays -> list of (logprobs_b (H_b,2) float32, sums_b (3,) float64 {body, hand, both}) in submission order,
+        each bit-identical to `score_batch` on the clip alone.  A wrong shape or a code outside [0, V) raises ValueError naming the clip."""
+        from talkshow_amd.modules import upload
+
+        def make(rows, order, dev):
+            if not isinstance(codes_list, (list, tuple)) or len(codes_list) != len(rows):
+                raise ValueError(f"score_clips: one (H_b, 2) code array per clip ({len(rows)})")
+            for b, c in enumerate(codes_list):
+                if c is None or tuple(c.shape) != (rows[b], 2):
+                    raise ValueError(f"score_clips: codes of clip {b} must have shape ({rows[b]}, 2), got {None if c is None else tuple(c.shape)}")
+            block, _ = _lib.given_block(list(codes_list), rows, self.generator.input_dim, order, who="score_clips")
+            return upload(block, dev)
+        return self._score_pass(mfcc_list, ids, "score_clips", make)
+
+    def score_motion_clips(self, mfcc_list, ids, poses_list):
+        """How likely is this recorded MOTION under the model: `score_clips` on the codes the VQ encoders give the poses, encoded on the
+        device in the same pass (`ts_vqvae_encode_pair_masked` in front of it; no host copy of codes).  poses_list = list of (P_b,129)
+        arrays in the wrapper's own pose layout (see `generate_clips`) with P_b = 4 (T_b // 4) frames: ValueError naming the clip otherwise."""
+        from talkshow_amd.modules import encode_pair_masked, upload
+
+        def make(rows, order, dev):
+            if not isinstance(poses_list, (list, tuple)) or len(poses_list) != len(rows):
+                raise ValueError(f"score_motion_clips: one (P_b, 129) pose array per clip ({len(rows)})")
+            for b, g in enumerate(poses_list):
+                P = None if g is None or len(getattr(g, "shape", ())) != 2 else int(g.shape[0])
+                if P != 4 * rows[b]:
+                    raise ValueError(f"score_motion_clips: clip {b} has {rows[b]} code rows and needs {4 * rows[b]} pose frames, got "
+                                     f"{None if g is None else tuple(getattr(g, 'shape', ()))}")
+            pblock, ptable = _lib.given_pose_block(list(poses_list), rows, order, who="score_motion_clips",
+                                                   width=self.each_dim[1] + self.each_dim[2])
+            pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
+            return encode_pair_masked(self.g_body, self.g_hand, pdev, upload(ptable, dev))     # (B, H_max, 2): P_max = 4 H_max
+        return self._score_pass(mfcc_list, ids, "score_motion_clips", make)
+
+    def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
+                         given_poses=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
         pass's host table is `mixed_tables` arithmetic (lens_dev: its device copy, (B,) int32, if the caller has uploaded one).  No synchronisation.
         sampling_table: `_lib.sampling_table(...)` in ROW order (the caller sorted it with the rows), or None.
-        given: `_lib.given_block(...)` in ROW order — (block, table), both numpy — or None."""
+        given: `_lib.given_block(...)` in ROW order — (block, table), both numpy — or None.
+        given_poses: `_lib.given_pose_block(...)` in ROW order — (block, table) — or None; with `given` too, no clip is in both."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -344,7 +467,25 @@ class TrainWrapper(TrainWrapperBaseClass):
         args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
                 _lib.dptr(mf), _lib.dptr(ids), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, None, int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
-        if given is not None:
+        i32p = _lib.C.POINTER(_lib.C.c_int32)
+        if given_poses is not None and int(given_poses[1].max()) == 0:
+            given_poses = None
+        if given_poses is not None:
+            pblock, ptable = given_poses
+            if int(pblock.shape[1]) // 4 > H_max:
+                raise ValueError(f"infer_padded_wav: the given poses hold {int(pblock.shape[1])} frames but the pass has {H_max} code rows")
+            ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
+            if given is None:
+                pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]),
+                                                                       ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)), _lib.stream_ptr()))
+            else:
+                if given[0].shape != (B, H_max, 2):
+                    raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
+                gdev, gtable = self._stage_given(given[0], given[1], pblock, ptable, dev)
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, None, _lib.dptr(gdev), gtable.ctypes.data_as(i32p), None,
+                                                                       _lib.stream_ptr()))
+        elif given is not None:
             gblock, gtable = given
             if gblock.shape != (B, H_max, 2):
                 raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {gblock.shape}")
@@ -358,14 +499,15 @@ class TrainWrapper(TrainWrapperBaseClass):
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None):
+                                sampling=None, given=None, given_poses=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
         `generate_batch(MFCC(sr)(wav_b), id_b)` on the clip alone; clip b draws from Philox subsequence `clip_index0 + b`, b its position in
         the SUBMITTED list (or `clip_indices[b]`).  sampling: one sampling record for all recordings or one per recording in submission
         order; the records follow the recordings through the sort by sample count.  given: as for `generate_clips`, one entry per recording
-        in submission order (a recording's code rows: `frontend.mixed_tables(ns, sr)["code_rows"]`)."""
+        in submission order (a recording's code rows: `frontend.mixed_tables(ns, sr)["code_rows"]`).  given_poses: as for `generate_clips`,
+        one entry per recording."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -381,9 +523,14 @@ class TrainWrapper(TrainWrapperBaseClass):
         if sampling is not None:
             recs = _lib.sampling_records(sampling, B)
             table = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
+        given_in = given
         if given is not None:
             given = _lib.given_block(given, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], self.generator.input_dim, order,
                                      who="generate_clips_from_wav")
+        if given_poses is not None:
+            _lib.given_kinds_check(given_in, given_poses, B, "generate_clips_from_wav")
+            given_poses = _lib.given_pose_block(given_poses, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], order,
+                                                who="generate_clips_from_wav", width=self.each_dim[1] + self.each_dim[2])
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -392,7 +539,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         if seed is None:
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
-        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given)
+        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given,
+                                                    given_poses=given_poses)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,

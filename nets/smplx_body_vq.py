@@ -65,6 +65,39 @@ class TrainWrapper(TrainWrapperBaseClass):
                                                 _lib.dptr(codes), _lib.dptr(recon), _lib.stream_ptr()))
         return codes, recon
 
+    def encode_clips(self, poses_list, want_z=False, lens=None):
+        """`VQVAE.encode` of body and hands for clips of DIFFERENT lengths in ONE pass (`ts_vqvae_encode_pair_masked`): poses_list = list of
+        (P_b,129) clips in c_index order, P_b >= 4 -> list of codes_b (P_b // 4, 2) int64 device views in submission order; want_z=True:
+        list of (codes_b, z_body_b, z_hand_b) with the encoders' outputs (P_b // 4, 64).  Every clip's values are bit-identical to
+        `g_body.encode_nlc` / `g_hand.encode_nlc` on the clip alone.  lens: poses_list is one padded (B,T_max,129) block instead and lens
+        its clips' own frame counts; frames beyond them are never read.  Composition models only."""
+        from talkshow_amd.modules import encode_pair_masked, pad_pose_clips, upload
+        if not self.composition:
+            raise NotImplementedError("encode_clips pairs the body and hand networks (composition=True)")
+        dev = self.g_body._dev()
+        block, lens = pad_pose_clips(poses_list, dev, "encode_clips", self.each_dim[1] + self.each_dim[2], lens)
+        res = encode_pair_masked(self.g_body, self.g_hand, block, upload(lens, dev), want_z)
+        if not want_z:
+            return [res[b, :int(t) // 4] for b, t in enumerate(lens)]
+        return [(res[0][b, :int(t) // 4], res[1][b, :int(t) // 4], res[2][b, :int(t) // 4]) for b, t in enumerate(lens)]
+
+    def reconstruct_clips(self, poses_list, lens=None):
+        """`reconstruct_batch` for clips of DIFFERENT lengths in ONE pass (`ts_body_vq_infer_mixed`): list of (P_b,129) clips -> list of
+        (codes_b (P_b // 4, 2), recon_b (4 (P_b // 4), 129)) in submission order, each bit-identical to `reconstruct_batch` on the clip
+        alone.  lens: as for `encode_clips`."""
+        from talkshow_amd.modules import pad_pose_clips, upload
+        if not self.composition:
+            raise NotImplementedError("reconstruct_clips pairs the body and hand networks (composition=True)")
+        dev = self.g_body._dev()
+        block, lens = pad_pose_clips(poses_list, dev, "reconstruct_clips", self.each_dim[1] + self.each_dim[2], lens)
+        B, T_max, ld = block.shape
+        H = T_max // 4
+        codes = torch.empty((B, H, 2), dtype=torch.int64, device=dev)
+        recon = torch.empty((B, 4 * H, ld), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().ts_body_vq_infer_mixed(self.g_body.handle(), self.g_hand.handle(), _lib.dptr(block), _lib.dptr(upload(lens, dev)),
+                                                      int(B), int(T_max), _lib.dptr(codes), _lib.dptr(recon), _lib.stream_ptr()))
+        return [(codes[b, :int(t) // 4], recon[b, :4 * (int(t) // 4)]) for b, t in enumerate(lens)]
+
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False,
                        continuity=False, id=None, fps=15, sr=22000, smooth=False, **kwargs):
         '''

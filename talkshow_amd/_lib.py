@@ -115,6 +115,14 @@ SIGNATURES = {
                                              _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
     "ts_pixelcnn_generate_mixed_given": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
                                               C.POINTER(C.c_int32), _vp, _vp]),
+    # given poses: the mixed VQ encode and the pass that continues from it
+    "ts_vqvae_encode_pair_masked": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "ts_body_vq_infer_mixed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ts_given_pose_rows_check": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i]),
+    "ts_body_pixel_infer_mixed_poses": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                             _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp]),
+    "ts_op_vq_argmin_pair_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ts_debug_vq_argmin_pair_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "ts_op_sample_given": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
@@ -379,6 +387,72 @@ def given_block(given, rows, V, order=None, who="given"):
         block[k, :g.shape[0]] = g
         table[k] = g.shape[0]
     return block, table
+
+
+def given_pose_block(given_poses, rows, order=None, who="given_poses", width=129):
+    """The `given_poses=` keyword of the decode entries -> (block (B, P_max, width) float32, table (B,) int32 numpy), both in SLOT order: what
+    `ts_body_pixel_infer_mixed_poses` takes as given_poses_dev and pose_lens_host (talkshow_hip.h, "given poses").
+    given_poses: a list in SUBMISSION order with None (nothing given) or a (P_b, width) float array per clip, or one (B, P, width) block;
+    rows: every clip's own code rows H_b in submission order; order: sorted slot k holds submitted clip order[k] (None: the submitted order).
+    The rule of `sampling.given_pose_rows`: P_b = 0, or P_b >= 4 with P_b // 4 <= H_b.  Frames of the block at or beyond a clip's P_b are 0
+    (the pass never reads them).  ValueError naming the SUBMITTED clip for a bad shape, a non-float array, 1 <= P_b <= 3 or too many frames.
+    The block is a numpy array when every entry lives on the host; with a device tensor among them it is a torch tensor on that device and no
+    entry is read back.  Pure host code: the library is not loaded."""
+    B = len(rows)
+    if hasattr(given_poses, "shape") and not isinstance(given_poses, (list, tuple)):
+        if len(given_poses.shape) != 3 or given_poses.shape[0] != B or given_poses.shape[2] != width:
+            raise ValueError(f"{who}: one block for all clips must have shape (B={B}, P, {width}), got {tuple(given_poses.shape)}")
+        given_poses = [given_poses[b] for b in range(B)]
+    if not isinstance(given_poses, (list, tuple)) or len(given_poses) != B:
+        raise ValueError(f"{who}: one entry per clip ({B}) — None or a (P, {width}) float array — or one (B, P, {width}) block, got "
+                         f"{type(given_poses).__name__}" + (f" of {len(given_poses)}" if isinstance(given_poses, (list, tuple)) else ""))
+    order = list(range(B)) if order is None else [int(i) for i in order]
+    if sorted(order) != list(range(B)):
+        raise ValueError(f"{who}: order must be a permutation of the {B} clips")
+    table = np.zeros(B, np.int32)
+    slots, device = [None] * B, None
+    for k, i in enumerate(order):
+        g = given_poses[i]
+        if g is None:
+            continue
+        if not hasattr(g, "detach"):
+            g = np.asarray(g)
+        if len(g.shape) != 2 or g.shape[1] != width:
+            raise ValueError(f"{who}: given poses of clip {i} must have shape (P, {width}), got {tuple(g.shape)}")
+        if not (g.dtype.is_floating_point if hasattr(g, "detach") else g.dtype.kind == "f"):
+            raise ValueError(f"{who}: given poses of clip {i} must be floats, got {g.dtype}")
+        P = int(g.shape[0])
+        if 1 <= P <= 3:
+            raise ValueError(f"{who}: clip {i} brings {P} given pose frames; one code row needs 4 (or none)")
+        if P // 4 > int(rows[i]):
+            raise ValueError(f"{who}: clip {i} brings {P} given pose frames = {P // 4} code rows but has {int(rows[i])} code rows of its own")
+        if hasattr(g, "detach") and g.is_cuda and device is None:
+            device = g.device
+        slots[k], table[k] = g, P
+    P_max = int(table.max()) if B else 0
+    if device is None:
+        block = np.zeros((B, P_max, width), np.float32)
+        for k, g in enumerate(slots):
+            if g is not None and table[k]:
+                block[k, :table[k]] = g.detach().numpy() if hasattr(g, "detach") else g
+        return block, table
+    block = torch.zeros((B, P_max, width), dtype=torch.float32, device=device)
+    for k, g in enumerate(slots):
+        if g is not None and table[k]:
+            block[k, :int(table[k])] = torch.as_tensor(g, dtype=torch.float32).to(device)
+    return block, table
+
+
+def given_kinds_check(given, given_poses, B, who="given"):
+    """A clip brings `given` rows or `given_poses` frames, never both: ValueError naming the first clip with both.  Entries that are not
+    per-clip lists (one block for all clips) count for every clip.  Pure host code."""
+    if given is None or given_poses is None:
+        return
+    has_g = [g is not None for g in given] if isinstance(given, (list, tuple)) else [True] * B
+    has_p = [g is not None for g in given_poses] if isinstance(given_poses, (list, tuple)) else [True] * B
+    for b, (g, p) in enumerate(zip(has_g, has_p)):
+        if g and p:
+            raise ValueError(f"{who}: clip {b} brings both given code rows and given poses; a clip brings one kind")
 
 
 def score_codes_shape(codes_shape, B, H):

@@ -11,6 +11,7 @@ namespace {
 struct BodyWork {
     DevBuf feat;
     DevBuf lat[2];
+    DevBuf given;   // ts_body_pixel_infer_mixed_poses: the code rows its encoders produce, (B, H_max, 2) int64 — the pass's given block
 };
 // scratch between the stages of ts_body_pixel_infer (audio feature map, split latents), one set per stream
 BodyWork &body_work(hipStream_t s) {
@@ -34,6 +35,7 @@ static Knobs read_knobs(Get get) {
     v.conv_sk = num("TS_CONV_SK", 1);
     v.w2v_moments = num("TS_W2V_MOMENTS", 1) != 0;
     v.vq_lds = num("TS_VQ_LDS", 1) != 0;
+    v.vq_pair = num("TS_VQ_PAIR", 1) != 0;
     v.split_xcd = num("TS_SPLIT_XCD", 8);
     v.prof_log = num("TS_PROF_LOG", 0) != 0;
     if (const char *e = get("TS_NO_GRAPH")) v.no_graph = e[0] && e[0] != '0';
@@ -210,33 +212,43 @@ int ts_body_pixel_infer_mixed_lp(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb,
                                            ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
 }
 
+// What every mixed body entry refuses before its first launch: null arguments, the shape, the length table (within T_max, at least one code
+// row, non-increasing) and the sampling records; `who` names the entry in the messages
+static int body_mixed_check(const char *who, const void *ae, const void *pix, const void *vb, const void *vh, const float *mfcc, const int64_t *ids,
+                            const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const int64_t *codes, const float *poses,
+                            const ts_sampling *ctl_host, int n_ctl) {
+    const std::string w(who);
+    if (!ae || !pix || !vb || !vh || !mfcc || !ids || !lens_host || !lens_dev || !codes || !poses) return fail(w + ": null argument");
+    if (B < 1) return fail(w + ": bad shape");
+    if ((T_max / 2) / 2 < 1) return fail(w + ": T_max too short");
+    for (int b = 0; b < B; ++b) {
+        if (lens_host[b] > T_max) return fail(w + ": clip " + std::to_string(b) + " is longer than T_max");
+        if (lens_host[b] < 4) return fail(w + ": clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
+        if (b > 0 && lens_host[b] > lens_host[b - 1])
+            return fail(w + ": lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
+    }
+    if (ctl_host) {   // a bad record or mode is refused before the first launch of the pass
+        if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
+            return fail(w + "_ctl: sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
+        if (n_ctl != 1 && n_ctl != B) return fail(w + "_ctl: n_ctl must be 1 or B");
+        if (ts_sampling_check(ctl_host, n_ctl, 1) != 0) return 1;   // the records; the vocabulary is checked by ts_pixelcnn_generate_mixed_ctl
+    }
+    return 0;
+}
+
 // the same pass in which clip b brings given_rows[b] code rows (given (B, T_max / 4, 2)); given == NULL: exactly the entry above
 int ts_body_pixel_infer_mixed_given(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
                                     const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                     float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                     void *stream) {
-    if (!ae || !pix || !vb || !vh || !mfcc || !ids || !lens_host || !lens_dev || !codes || !poses)
-        return fail("ts_body_pixel_infer_mixed: null argument");
-    if (B < 1) return fail("ts_body_pixel_infer_mixed: bad shape");
+    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
+        return 1;
     hipStream_t s = (hipStream_t)stream;
     const int H = (T_max / 2) / 2;
-    if (H < 1) return fail("ts_body_pixel_infer_mixed: T_max too short");
-    for (int b = 0; b < B; ++b) {
-        if (lens_host[b] > T_max) return fail("ts_body_pixel_infer_mixed: clip " + std::to_string(b) + " is longer than T_max");
-        if (lens_host[b] < 4) return fail("ts_body_pixel_infer_mixed: clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
-        if (b > 0 && lens_host[b] > lens_host[b - 1])
-            return fail("ts_body_pixel_infer_mixed: lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
-    }
     const int aud_dim = convnet_hidden(ae);
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * aud_dim * sizeof(float)));
-    if (ctl_host) {   // a bad record or mode is refused before the first launch of the pass
-        if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
-            return fail("ts_body_pixel_infer_mixed_ctl: sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
-        if (n_ctl != 1 && n_ctl != B) return fail("ts_body_pixel_infer_mixed_ctl: n_ctl must be 1 or B");
-        if (ts_sampling_check(ctl_host, n_ctl, 1) != 0) return 1;   // the records; the vocabulary is checked by ts_pixelcnn_generate_mixed_ctl
-    }
     if (given) {   // a bad row table is refused before the first launch of the pass, too
         if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
         if (ts_given_rows_check(given_rows_host, lens_host, B) != 0) return 1;
@@ -251,6 +263,61 @@ int ts_body_pixel_infer_mixed_given(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
     }
     return ts_vqvae_decode_pair_masked(vb, vh, static_cast<int64_t *>(w.lat[0].p), static_cast<int64_t *>(w.lat[1].p), lens_dev, B, H,
                                        poses, s);
+}
+
+// Host only: the rule every entry with given POSES applies to its frame table before anything is launched (talkshow_hip.h, "given poses")
+int ts_given_pose_rows_check(const int32_t *pose_lens_host, const int32_t *lens_host, int B) {
+    if (!pose_lens_host || !lens_host || B < 1) return fail("ts_given_pose_rows_check: bad argument");
+    for (int b = 0; b < B; ++b) {
+        const int P = pose_lens_host[b];
+        if (P == 0) continue;
+        if (P < 4)
+            return fail("given poses of clip " + std::to_string(b) + ": P = " + std::to_string(P) + " frames; one code row needs 4 (or P = 0: none)");
+        if (P / 4 > (lens_host[b] >> 2))
+            return fail("given poses of clip " + std::to_string(b) + ": P = " + std::to_string(P) + " frames are " + std::to_string(P / 4) +
+                        " code rows but the clip has " + std::to_string(lens_host[b] >> 2) + " of its own");
+    }
+    return 0;
+}
+
+// ts_body_pixel_infer_mixed_given whose given rows are ENCODED here from pose frames, on the device and in stream order (talkshow_hip.h,
+// "given poses"); given_poses == NULL: exactly the _lp entry
+int ts_body_pixel_infer_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                    const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
+                                    const int32_t *pose_lens_dev, void *stream) {
+    if (!given_poses)
+        return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
+    const char *who = "ts_body_pixel_infer_mixed_poses";
+    // everything the pass itself would refuse is refused here too, ahead of the encoders' launches
+    if (!pose_lens_host || !pose_lens_dev) return fail(std::string(who) + ": given poses need their frame tables");
+    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
+        return 1;
+    const int H = (T_max / 2) / 2;
+    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": TS_SAMPLE_UNIFORMS needs uniforms_dev");
+    if (ts_given_pose_rows_check(pose_lens_host, lens_host, B) != 0) return 1;
+    std::vector<int32_t> G(B);
+    int p_top = 0;
+    for (int b = 0; b < B; ++b) {
+        G[b] = pose_lens_host[b] / 4;
+        p_top = std::max(p_top, (int)pose_lens_host[b]);
+    }
+    if (p_top > P_max) return fail(std::string(who) + ": a clip brings more pose frames than P_max");
+    if (p_top == 0)   // nothing given anywhere: the pass without given rows
+        return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
+    if (P_max / 4 > H) return fail(std::string(who) + ": P_max / 4 exceeds the pass's code rows T_max / 4");
+    hipStream_t s = (hipStream_t)stream;
+    BodyWork &w = body_work(s);
+    TS_TRY(w.given.ensure((size_t)B * H * 2 * sizeof(int64_t)));
+    int64_t *given = static_cast<int64_t *>(w.given.p);
+    // rows h < P_b / 4 of clip b: its codes; rows up to P_max / 4: -1; rows beyond stay as they are — the pass reads rows below G_b only
+    TS_TRY(vq_encode_pair_masked(vb, vh, given_poses, vqvae_in_dim(vb) + vqvae_in_dim(vh), pose_lens_dev, B, P_max, given, H, nullptr, nullptr, 0, s));
+    return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                           ctl_host, n_ctl, logprob, given, G.data(), nullptr, stream);
 }
 
 int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const float *w, const float *bias, int Cout,
@@ -865,6 +932,38 @@ int ts_op_vq_argmin(ts_ctx *ctx, const float *x, int M, const float *cb, int nco
     TS_HIP(launch_vq_argmin(x, dim, M, cb, sq.f(), ncode, dim, idx, 1, s));
     TS_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+// the paired, length-masked codebook search on given latents (kernel-level tests): form 0 = the library's choice, 1 paired, 2 two launches,
+// 3 the generic fallback; `iters` launches back to back (tools time them), one synchronisation
+int ts_debug_vq_argmin_pair_masked(ts_ctx *ctx, const float *z_body, const float *z_hand, const int32_t *lens, int B, int H, const float *cb_body,
+                                   const float *cb_hand, int ncode_body, int ncode_hand, int dim_body, int dim_hand, int64_t *codes, int form,
+                                   int iters, void *stream) {
+    if (!ctx || !z_body || !z_hand || !lens || !cb_body || !cb_hand || !codes) return fail("ts_op_vq_argmin_pair_masked: null argument");
+    if (B < 1 || H < 1 || ncode_body < 1 || ncode_hand < 1 || dim_body < 4 || dim_hand < 4 || dim_body % 4 || dim_hand % 4 || form < 0 || form > 3 ||
+        iters < 1)
+        return fail("ts_op_vq_argmin_pair_masked: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf sq[2];
+    TS_TRY(sq[0].ensure((size_t)ncode_body * sizeof(float)));
+    TS_TRY(sq[1].ensure((size_t)ncode_hand * sizeof(float)));
+    TS_HIP(launch_row_sqnorm(cb_body, ncode_body, dim_body, sq[0].f(), s));
+    TS_HIP(launch_row_sqnorm(cb_hand, ncode_hand, dim_hand, sq[1].f(), s));
+    VqPairParams p;
+    p.z[0] = z_body; p.z[1] = z_hand;
+    p.cb[0] = cb_body; p.cb[1] = cb_hand;
+    p.csq[0] = sq[0].f(); p.csq[1] = sq[1].f();
+    p.ncode[0] = ncode_body; p.ncode[1] = ncode_hand;
+    p.dim[0] = dim_body; p.dim[1] = dim_hand;
+    p.B = B; p.H = H; p.Hout = H; p.lens = lens; p.codes = codes;
+    for (int i = 0; i < iters; ++i) TS_HIP(launch_vq_argmin_pair_masked(p, form, s));
+    TS_HIP(hipStreamSynchronize(s));   // the scratch dies with this frame
+    return 0;
+}
+int ts_op_vq_argmin_pair_masked(ts_ctx *ctx, const float *z_body, const float *z_hand, const int32_t *lens, int B, int H, const float *cb_body,
+                                const float *cb_hand, int ncode_body, int ncode_hand, int dim_body, int dim_hand, int64_t *codes, void *stream) {
+    return ts_debug_vq_argmin_pair_masked(ctx, z_body, z_hand, lens, B, H, cb_body, cb_hand, ncode_body, ncode_hand, dim_body, dim_hand, codes, 0, 1,
+                                          stream);
 }
 
 int ts_op_linear(ts_ctx *ctx, const float *x, int M, int K, const float *w, const float *bias, int N, int relu,

@@ -242,5 +242,8 @@ struct FacePacked {
 constexpr int FACE_FC_K[6] = {3, 3, 3, 3, 2, 2};   // kernel sizes of the six stride-2 feature convolutions (wav2vec2 base)
 int face_packed_layout(const int32_t *ns, const int32_t *frames, int B, FacePacked *out);
 int vqvae_in_dim(const ts_vqvae *v);
+// models.cpp: both VQ encoders over clips of different lengths, codes into a (B, codes_H, 2) block (codes_H >= T_max / 4); form: launch_vq_argmin_pair_masked
+int vq_encode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int poses_ld, const int32_t *lens_dev, int B, int T_max, int64_t *codes,
+                          int codes_H, float *z_body, float *z_hand, int form, hipStream_t s);
 
 }  // namespace ts

@@ -265,6 +265,20 @@ int skinny_trace_read(unsigned long long *out, int max_records);
 // idx[m] = argmin_j (|x_m|^2 + |e_j|^2) - 2 x_m.e_j   (ties -> lowest j); also writes int32 copy if idx32 != null
 hipError_t launch_vq_argmin(const float *x, int ldx, int M, const float *codebook, const float *code_sq, int ncode,
                             int dim, int64_t *idx, long idx_stride, hipStream_t stream);
+// The codebook search of a MIXED pass for both networks at once (talkshow_hip.h, "given poses"): row m = b * H + h of network n is valid iff
+// h < lens[b] >> 2 (lens: device table of pose frame counts, any order).  codes[(b * Hout + h) * 2 + n] = the index launch_vq_argmin returns
+// for that row if it is valid, -1 if not (the row of z is then never read).  z[n] (B * H, dim[n]) contiguous rows.
+struct VqPairParams {
+    const float *z[2], *cb[2], *csq[2];
+    int ncode[2], dim[2];
+    int B, H, Hout;      // Hout >= H: rows per clip of the code block (rows h >= H of it are left alone)
+    const int *lens;
+    int64_t *codes;
+};
+// form 0: the library's choice (one paired LDS launch where both networks have dim = 64 and one ncode; TS_VQ_PAIR=0: two launches of it);
+// 1 / 2: paired / two launches named outright (tools, tests); 3: two launches of the masked generic kernel, which is also where every
+// configuration the LDS form does not cover goes
+hipError_t launch_vq_argmin_pair_masked(const VqPairParams &p, int form, hipStream_t stream);
 // code_sq[j] = sum_c e[j][c]^2
 hipError_t launch_row_sqnorm(const float *e, int n, int dim, float *out, hipStream_t stream);
 // out[m][0..width) = table[idx[m*idx_stride]][0..width); an index outside [0, nrows) gives a row of NaNs
@@ -309,6 +323,7 @@ hipError_t launch_clock_sample(unsigned long long *out, int n, unsigned long lon
 struct Knobs {
     bool conv_bands = true;     // TS_CONV_BANDS=0: big conv layers as one plain grid of 128 x 128 tiles
     bool vq_lds = true;         // TS_VQ_LDS=0: the codebook search reads code rows from L2 per thread instead of LDS-staged tiles (tests, A/B)
+    bool vq_pair = true;        // TS_VQ_PAIR=0: the mixed pass's codebook search as two launches (one per network) instead of one paired launch; same indices (A/B, tools/poses_pass.py)
     int conv_ring = 9;          // TS_CONV_RING=0|1|3|8|9: single-problem layers that take 128 x 128 tiles on conv_gemm.hip (0) / forced onto the ring engine's 128 x 128 tile with 4 (1) or 8 (8) waves or its 96 x 128 tile (3) / (9, default) 128 x 128 on 8 waves or 96 x 128 by tile count
     bool w2v_moments = true;    // TS_W2V_MOMENTS=0: conv0's GroupNorm statistics from a pass that computes the convolution (512 channels) instead of from the input's second moments (A/B, tests)
     int conv_sk = 1;            // TS_CONV_SK=0: no stream-K band in the ring engine's plans (whole tiles only: the round-5 plans); 2: the band wherever a layer has a plan for one (A/B, tests)

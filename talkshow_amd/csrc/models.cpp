@@ -543,6 +543,7 @@ struct ts_vqvae {
     struct Work {
         Pool pool;
         DevBuf z, lat;   // encoder output (B*H, emb), internal latents (B*H) int64
+        DevBuf pair;     // mixed encode without a caller's block: the interleaved codes (B, H, 2) int64
     };
     StreamWorks<Work> works;
     Work &work(hipStream_t s) { return works.get(s); }
@@ -659,6 +660,51 @@ int vq_decode_impl(ts_vqvae *vq, const int64_t *lat, int B, int H, float *out, i
 }  // namespace
 
 namespace ts {
+// Both encoders of a MIXED pass in lockstep (talkshow_hip.h, "given poses"): length-masked trunks -> pre_vq_conv masked at lens >> 2 -> the
+// paired codebook search, which writes codes (B, codes_H, 2) with -1 beyond a clip's rows.  z_out[i] (B, T_max / 4, emb) or null.
+int vq_encode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int poses_ld, const int32_t *lens, int B, int T_max, int64_t *codes,
+                          int codes_H, float *z_body, float *z_hand, int form, hipStream_t s) {
+    ts_vqvae *vq[2] = {vb, vh};
+    if (vb->ncode == 0 || vh->ncode == 0) return fail("mixed encode: auto-encoder handle (no codebook)");
+    ts_ctx *ctx = vb->ctx;
+    const float *pp[2] = {poses, poses + vb->in_dim};
+    float *zu[2] = {z_body, z_hand};
+    ts_convnet *nets[2] = {&vb->enc, &vh->enc};
+    int idx = 0, H = 0, tmp = 0;
+    TS_TRY(run_trunk_n(2, nets, pp, poses_ld, B, T_max, s, &idx, &H, lens));
+    if (codes_H < H) return fail("mixed encode: the code block has fewer rows per clip than T_max / 4");
+    const LenMask mk{lens, 2, 0};
+    const ConvLayer *Lp[2];
+    const float *xp[2];
+    float *zp[2];
+    int ns[2];
+    for (int i = 0; i < 2; ++i) {
+        ts_vqvae::Work &wk = vq[i]->work(s);
+        TS_TRY(wk.z.ensure((size_t)B * H * vq[i]->emb * sizeof(float)));
+        zp[i] = zu[i] ? zu[i] : wk.z.f();
+        Lp[i] = &vq[i]->enc.pre_vq;
+        xp[i] = vq[i]->enc.work(s).pool.buf(idx);
+        ns[i] = vq[i]->emb;
+    }
+    if (vb->emb == vh->emb) {
+        TS_TRY(run_layer_n(ctx, 2, Lp, xp, vb->hid, B, H, nullptr, 0, zp, vb->emb, nullptr, ns, s, &tmp, &mk));
+    } else {
+        for (int i = 0; i < 2; ++i)
+            TS_TRY(run_layer(ctx, *Lp[i], xp[i], vq[i]->hid, B, H, nullptr, 0, zp[i], vq[i]->emb, 0, ns[i], s, &tmp, &mk));
+    }
+    VqPairParams q;
+    for (int i = 0; i < 2; ++i) {
+        q.z[i] = zp[i];
+        q.cb[i] = vq[i]->codebook.f();
+        q.csq[i] = vq[i]->code_sq.f();
+        q.ncode[i] = vq[i]->ncode;
+        q.dim[i] = vq[i]->emb;
+    }
+    q.B = B; q.H = H; q.Hout = codes_H; q.lens = lens; q.codes = codes;
+    MiscScope ms(ctx, s);
+    TS_HIP(launch_vq_argmin_pair_masked(q, form, s));
+    return 0;
+}
 int convnet_hidden(const ts_convnet *n) { return n->hid; }
 int vqvae_in_dim(const ts_vqvae *v) { return v->in_dim; }
 }  // namespace ts
@@ -872,6 +918,42 @@ int ts_vqvae_decode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_b
     const int64_t *lc[2] = {lat_body, lat_hand};
     const int col0[2] = {0, vb->in_dim};
     return vq_decode_n(2, vqs, lc, nullptr, B, H, out, vb->in_dim + vh->in_dim, col0, (hipStream_t)stream, lens);
+}
+
+
+// VQVAE.encode of both parts for clips of different lengths in one pass (talkshow_hip.h, "given poses")
+int ts_vqvae_encode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int poses_ld, const int32_t *lens, int B, int T_max,
+                                int64_t *codes, float *z_body, float *z_hand, void *stream) {
+    if (!vb || !vh || !poses || !lens || !codes) return fail("ts_vqvae_encode_pair_masked: null argument");
+    if (B < 1) return fail("ts_vqvae_encode_pair_masked: bad shape");
+    if (poses_ld < vb->in_dim + vh->in_dim) return fail("ts_vqvae_encode_pair_masked: poses_ld is smaller than body_dim + hand_dim");
+    return vq_encode_pair_masked(vb, vh, poses, poses_ld, lens, B, T_max, codes, T_max / 4, z_body, z_hand, 0, (hipStream_t)stream);
+}
+
+// ts_body_vq_infer for clips of different lengths: the encode above, then ts_vqvae_decode_pair_masked
+int ts_body_vq_infer_mixed(ts_vqvae *vb, ts_vqvae *vh, const float *poses, const int32_t *lens, int B, int T_max, int64_t *codes, float *recon,
+                           void *stream) {
+    if (!vb || !vh || !poses || !lens) return fail("ts_body_vq_infer_mixed: null argument");
+    if (!codes && !recon) return fail("ts_body_vq_infer_mixed: nothing to produce");
+    if (B < 1) return fail("ts_body_vq_infer_mixed: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = T_max / 4;
+    if (!codes) {
+        ts_vqvae::Work &wk = vb->work(s);
+        TS_TRY(wk.pair.ensure((size_t)B * (H + 1) * 2 * sizeof(int64_t)));
+        codes = static_cast<int64_t *>(wk.pair.p);
+    }
+    TS_TRY(vq_encode_pair_masked(vb, vh, poses, vb->in_dim + vh->in_dim, lens, B, T_max, codes, H, nullptr, nullptr, 0, s));
+    if (!recon) return 0;
+    ts_vqvae *vqs[2] = {vb, vh};
+    int64_t *lp[2];
+    for (int k = 0; k < 2; ++k) {
+        ts_vqvae::Work &wk = vqs[k]->work(s);
+        TS_TRY(wk.lat.ensure((size_t)B * (H + 1) * sizeof(int64_t)));
+        lp[k] = static_cast<int64_t *>(wk.lat.p);
+        TS_HIP(hipMemcpy2DAsync(lp[k], sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t), (size_t)B * H, hipMemcpyDeviceToDevice, s));
+    }
+    return ts_vqvae_decode_pair_masked(vb, vh, lp[0], lp[1], lens, B, H, recon, s);
 }
 
 }  // extern "C"

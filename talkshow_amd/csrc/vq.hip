@@ -211,6 +211,257 @@ hipError_t launch_vq_argmin(const float *x, int ldx, int M, const float *codeboo
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// vq_argmin for a MIXED pass, both networks in one launch (talkshow_hip.h, "given poses").  vq_argmin_lds_kernel with
+//   * blockIdx.y = network (net0 + blockIdx.y: a one-network launch names its network through net0): {z, codebook, |e|^2, output column};
+//   * a validity bit per row: row m = b * H + h is valid iff h < lens[b] >> 2.  b, h and lens[b] are functions of blockIdx and the wave
+//     index only, so the bits sit in scalar registers like the query rows themselves and every test on them is wave-uniform;
+//   * output straight into the interleaved code block codes (B, Hout, 2): the arg-min of a valid row, -1 for an invalid one.
+// A workgroup without a valid row stores its -1s and returns before it touches the codebook.  In a partly valid workgroup every wave walks
+// every tile and reaches every barrier; an invalid row skips its |x|^2, its FMAs and its reduction — its row of z is never addressed, so no
+// clamped address exists that could point outside z.  Arithmetic: that of vq_argmin_lds_kernel, statement for statement.
+// ---------------------------------------------------------------------------------------------------------------
+template <int RW>
+__global__ __launch_bounds__(256) void vq_argmin_pair_lds_kernel(const VqPairParams p, int net0) {
+    static_assert(4 * RW <= 32, "the workgroup's validity bits live in one 32-bit word");
+    __shared__ __attribute__((aligned(16))) float tile[2][VQ_TILE][VQ_PITCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = net0 + blockIdx.y;
+    const float *__restrict__ x = p.z[n], *__restrict__ cb = p.cb[n], *__restrict__ csq = p.csq[n];
+    const int ncode = p.ncode[n], M = p.B * p.H;
+    const int g0 = blockIdx.x * (4 * RW);               // the workgroup's first row
+    int64_t *__restrict__ out = p.codes + n;
+    auto slot = [&](int m) -> int64_t * {
+        const int b = m / p.H, h = m - b * p.H;
+        return out + ((long)b * p.Hout + h) * 2;
+    };
+
+    // validity of the workgroup's 4 RW rows (every wave computes all of them: the early return below is workgroup-uniform without a barrier)
+    unsigned wg = 0;
+    {
+        int b = g0 / p.H, h = g0 - b * p.H;
+        int hb = g0 < M ? (p.lens[b] >> 2) : 0;
+        for (int i = 0; i < 4 * RW && g0 + i < M; ++i) {
+            if (h < hb) wg |= 1u << i;
+            if (++h == p.H) {
+                h = 0;
+                ++b;
+                if (g0 + i + 1 < M) hb = p.lens[b] >> 2;
+            }
+        }
+    }
+    wg = __builtin_amdgcn_readfirstlane(wg);
+    if (wg == 0) {
+        if (tid < 4 * RW && g0 + tid < M) *slot(g0 + tid) = -1;
+        return;
+    }
+    const int m0 = g0 + wave * RW;                       // this wave's first query row (wave-uniform)
+    const unsigned vm = (wg >> (wave * RW)) & ((1u << RW) - 1u);
+    const int ntile = (ncode + VQ_TILE - 1) / VQ_TILE;
+
+    float xsq[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        xsq[r] = 0.f;
+        if ((vm >> r) & 1u) {
+            const float *xr = x + (long)(m0 + r) * VQ_DIM;
+            float sq = 0.f;
+            for (int c = 0; c < VQ_DIM; ++c) sq += xr[c] * xr[c];
+            xsq[r] = sq;
+        }
+    }
+    float best[RW];
+    int bidx[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) { best[r] = INFINITY; bidx[r] = 0x7fffffff; }
+
+    f32x4 st[4];
+    auto fetch = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = tid + 256 * i, row = q >> 4;
+            st[i] = t * VQ_TILE + row < ncode ? *reinterpret_cast<const f32x4 *>(cb + ((long)t * VQ_TILE + row) * VQ_DIM + (q & 15) * 4)
+                                              : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto park = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = tid + 256 * i;
+            *reinterpret_cast<f32x4 *>(&tile[buf][q >> 4][(q & 15) * 4]) = st[i];
+        }
+    };
+    fetch(0);
+    park(0);
+    __syncthreads();
+    for (int t = 0; t < ntile; ++t) {
+        const int buf = t & 1;
+        if (t + 1 < ntile) fetch(t + 1);
+        const int j = t * VQ_TILE + lane;
+        if (vm) {                                        // a wave without a valid row only stages tiles and keeps the barriers
+            f32x4 e[VQ_DIM / 4];
+#pragma unroll
+            for (int c4 = 0; c4 < VQ_DIM / 4; ++c4) e[c4] = *reinterpret_cast<const f32x4 *>(&tile[buf][lane][c4 * 4]);
+            const float ee = j < ncode ? csq[j] : 0.f;
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                if (!((vm >> r) & 1u)) continue;         // wave-uniform: skip the FMAs, never a barrier
+                const float *xr = x + (long)(m0 + r) * VQ_DIM;   // wave-uniform address: scalar loads
+                float dot = 0.f;
+#pragma unroll
+                for (int c4 = 0; c4 < VQ_DIM / 4; ++c4) {
+                    dot = fmaf(xr[c4 * 4 + 0], e[c4][0], dot);
+                    dot = fmaf(xr[c4 * 4 + 1], e[c4][1], dot);
+                    dot = fmaf(xr[c4 * 4 + 2], e[c4][2], dot);
+                    dot = fmaf(xr[c4 * 4 + 3], e[c4][3], dot);
+                }
+                const float d = (xsq[r] + ee) - 2.0f * dot;
+                if (j < ncode && d < best[r]) { best[r] = d; bidx[r] = j; }
+            }
+        }
+        if (t + 1 < ntile) park(buf ^ 1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        if (m0 + r >= M) continue;
+        if (!((vm >> r) & 1u)) {
+            if (lane == 0) *slot(m0 + r) = -1;
+            continue;
+        }
+        float d = best[r];
+        int j = bidx[r];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float od = __shfl_xor(d, off);
+            const int oj = __shfl_xor(j, off);
+            if (od < d || (od == d && oj < j)) { d = od; j = oj; }
+        }
+        if (lane == 0) *slot(m0 + r) = j;
+    }
+}
+
+// vq_argmin_kernel (any dim % 4 == 0, any ncode) for one network of a mixed pass: the fallback of the kernel above.  Invalid rows are staged
+// as zeros without being read and stored as -1; a workgroup without a valid row returns before its first barrier.
+__global__ __launch_bounds__(256) void vq_argmin_masked_kernel(const float *__restrict__ x, int B, int H, int Hout, const int *__restrict__ lens,
+                                                               const float *__restrict__ cb, const float *__restrict__ csq, int ncode, int dim,
+                                                               int64_t *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *xs = sm;                              // [VQ_ROWS][dim]
+    float *xsq = sm + VQ_ROWS * dim;             // [VQ_ROWS]
+    float *rd = xsq + VQ_ROWS;                   // [4][VQ_ROWS]
+    int *ri = reinterpret_cast<int *>(rd + 4 * VQ_ROWS);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int M = B * H, m0 = blockIdx.x * VQ_ROWS;
+    unsigned vm = 0;
+    for (int r = 0; r < VQ_ROWS && m0 + r < M; ++r) {
+        const int b = (m0 + r) / H, h = (m0 + r) - b * H;
+        if (h < (lens[b] >> 2)) vm |= 1u << r;
+    }
+    auto slot = [&](int m) -> int64_t * {
+        const int b = m / H, h = m - b * H;
+        return out + ((long)b * Hout + h) * 2;
+    };
+    if (vm == 0) {
+        if (tid < VQ_ROWS && m0 + tid < M) *slot(m0 + tid) = -1;
+        return;
+    }
+    for (int i = tid; i < VQ_ROWS * dim; i += 256) {
+        int r = i / dim, c = i - r * dim;
+        xs[i] = ((vm >> r) & 1u) ? x[(long)(m0 + r) * dim + c] : 0.f;
+    }
+    __syncthreads();
+    if (tid < VQ_ROWS) {
+        float s = 0.f;
+        for (int c = 0; c < dim; ++c) s += xs[tid * dim + c] * xs[tid * dim + c];
+        xsq[tid] = s;
+    }
+    __syncthreads();
+
+    float best[VQ_ROWS];
+    int bidx[VQ_ROWS];
+#pragma unroll
+    for (int r = 0; r < VQ_ROWS; ++r) { best[r] = INFINITY; bidx[r] = 0x7fffffff; }
+
+    for (int j = tid; j < ncode; j += 256) {
+        float dot[VQ_ROWS];
+#pragma unroll
+        for (int r = 0; r < VQ_ROWS; ++r) dot[r] = 0.f;
+        const float4 *e = reinterpret_cast<const float4 *>(cb + (long)j * dim);
+        for (int c4 = 0; c4 < dim / 4; ++c4) {
+            const float4 ev = e[c4];
+#pragma unroll
+            for (int r = 0; r < VQ_ROWS; ++r) {
+                const float4 xv = *reinterpret_cast<const float4 *>(&xs[r * dim + c4 * 4]);
+                dot[r] = fmaf(xv.x, ev.x, dot[r]);
+                dot[r] = fmaf(xv.y, ev.y, dot[r]);
+                dot[r] = fmaf(xv.z, ev.z, dot[r]);
+                dot[r] = fmaf(xv.w, ev.w, dot[r]);
+            }
+        }
+        const float ee = csq[j];
+#pragma unroll
+        for (int r = 0; r < VQ_ROWS; ++r) {
+            const float d = (xsq[r] + ee) - 2.0f * dot[r];
+            if (d < best[r]) { best[r] = d; bidx[r] = j; }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < VQ_ROWS; ++r) {
+        float d = best[r];
+        int j = bidx[r];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float od = __shfl_xor(d, off);
+            const int oj = __shfl_xor(j, off);
+            if (od < d || (od == d && oj < j)) { d = od; j = oj; }
+        }
+        if (lane == 0) { rd[wave * VQ_ROWS + r] = d; ri[wave * VQ_ROWS + r] = j; }
+    }
+    __syncthreads();
+    if (tid < VQ_ROWS && m0 + tid < M) {
+        float d = rd[tid];
+        int j = ri[tid];
+        for (int w = 1; w < 4; ++w) {
+            const float od = rd[w * VQ_ROWS + tid];
+            const int oj = ri[w * VQ_ROWS + tid];
+            if (od < d || (od == d && oj < j)) { d = od; j = oj; }
+        }
+        *slot(m0 + tid) = ((vm >> tid) & 1u) ? (int64_t)j : (int64_t)-1;
+    }
+}
+
+hipError_t launch_vq_argmin_pair_masked(const VqPairParams &p, int form, hipStream_t stream) {
+    if (!p.lens || !p.codes || p.B < 1 || p.H < 1 || p.Hout < p.H || (long)p.B * p.H > 0x7fffffffl) return hipErrorInvalidValue;
+    for (int n = 0; n < 2; ++n)
+        if (!p.z[n] || !p.cb[n] || !p.csq[n] || p.ncode[n] < 1 || p.dim[n] < 4 || p.dim[n] % 4) return hipErrorInvalidValue;
+    const int M = p.B * p.H;
+    const bool lds = p.dim[0] == VQ_DIM && p.dim[1] == VQ_DIM && p.ncode[0] == p.ncode[1] && knobs().vq_lds &&
+                     ((reinterpret_cast<uintptr_t>(p.cb[0]) | reinterpret_cast<uintptr_t>(p.cb[1])) & 15) == 0;
+    if (form == 0) form = knobs().vq_pair ? 1 : 2;
+    if (!lds || form == 3) {
+        for (int n = 0; n < 2; ++n) {
+            const int dim = p.dim[n];
+            size_t smem = (VQ_ROWS * dim + VQ_ROWS + 4 * VQ_ROWS) * sizeof(float) + 4 * VQ_ROWS * sizeof(int);
+            hipLaunchKernelGGL(vq_argmin_masked_kernel, dim3((M + VQ_ROWS - 1) / VQ_ROWS), dim3(256), smem, stream, p.z[n], p.B, p.H, p.Hout,
+                               p.lens, p.cb[n], p.csq[n], p.ncode[n], dim, p.codes + n);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    // the row-count switch of launch_vq_argmin; one launch over both networks, or one per network
+    const int nl = form == 2 ? 2 : 1, ny = form == 2 ? 1 : 2;
+    for (int l = 0; l < nl; ++l) {
+        if (M >= 32 * 512) hipLaunchKernelGGL(vq_argmin_pair_lds_kernel<8>, dim3((M + 31) / 32, ny), dim3(256), 0, stream, p, l);
+        else hipLaunchKernelGGL(vq_argmin_pair_lds_kernel<2>, dim3((M + 7) / 8, ny), dim3(256), 0, stream, p, l);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 __global__ void row_sqnorm_kernel(const float *e, int n, int dim, float *out) {
     int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;

@@ -803,6 +803,54 @@ def upload(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
 
 
+def pad_pose_clips(poses_list, dev, who, width, lens=None):
+    """Pose clips of different lengths -> (block (B, T_max, width) float32 device tensor, lens (B,) int32 numpy).  poses_list: a list of
+    (P_b, width) arrays / tensors (padded here with zeros), or — with `lens` — one (B, T_max, width) block whose frames at or beyond lens[b]
+    are never read.  ValueError naming the clip for a bad shape or a clip shorter than 4 frames (one code row).  Nothing waits for the device."""
+    if lens is not None:
+        block = _dev_f32(poses_list, dev)
+        lens = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if block.dim() != 3 or block.shape[0] != lens.size or block.shape[2] != width:
+            raise ValueError(f"{who}: a padded block must have shape (B={lens.size}, T_max, {width}), got {tuple(block.shape)}")
+        for b, t in enumerate(lens):
+            if t < 4 or t > block.shape[1]:
+                raise ValueError(f"{who}: clip {b} has {int(t)} frames; a clip holds 4 (one code row) to T_max = {int(block.shape[1])}")
+        return block, lens
+    if not isinstance(poses_list, (list, tuple)) or len(poses_list) < 1:
+        raise ValueError(f"{who}: a non-empty list of (P, {width}) pose clips, got {type(poses_list).__name__}")
+    for b, g in enumerate(poses_list):
+        shape = tuple(getattr(g, "shape", ()))
+        if len(shape) != 2 or shape[1] != width:
+            raise ValueError(f"{who}: clip {b} must have shape (P, {width}), got {shape}")
+        if shape[0] < 4:
+            raise ValueError(f"{who}: clip {b} has {shape[0]} pose frames; one code row needs 4")
+    lens = np.ascontiguousarray([int(g.shape[0]) for g in poses_list], dtype=np.int32)
+    B, T_max = len(poses_list), int(lens.max())
+    if all(torch.is_tensor(g) and g.is_cuda for g in poses_list):
+        block = torch.zeros((B, T_max, width), dtype=torch.float32, device=dev)
+        for b, g in enumerate(poses_list):
+            block[b, :int(lens[b])] = g
+    else:
+        padded = np.zeros((B, T_max, width), dtype=np.float32)
+        for b, g in enumerate(poses_list):
+            padded[b, :int(lens[b])] = g.detach().cpu().numpy() if torch.is_tensor(g) else np.asarray(g)
+        block = upload(padded, dev)
+    return block, lens
+
+
+def encode_pair_masked(g_body, g_hand, block, lens_dev, want_z=False):
+    """`ts_vqvae_encode_pair_masked`: block (B, T_max, body + hand) device tensor, lens_dev (B,) int32 device table of the clips' own frame
+    counts -> codes (B, T_max // 4, 2) int64 with -1 beyond a clip's rows [, z_body, z_hand (B, T_max // 4, embedding_dim), 0 beyond]."""
+    B, T_max, ld = block.shape
+    H = T_max // 4
+    codes = torch.empty((B, H, 2), dtype=torch.int64, device=block.device)
+    zb = torch.empty((B, H, g_body.embedding_dim), dtype=torch.float32, device=block.device) if want_z else None
+    zh = torch.empty((B, H, g_hand.embedding_dim), dtype=torch.float32, device=block.device) if want_z else None
+    _lib.check(_lib.load().ts_vqvae_encode_pair_masked(g_body.handle(), g_hand.handle(), _lib.dptr(block), int(ld), _lib.dptr(lens_dev), int(B),
+                                                       int(T_max), _lib.dptr(codes), _lib.dptr(zb), _lib.dptr(zh), _lib.stream_ptr()))
+    return (codes, zb, zh) if want_z else codes
+
+
 def ids_in_row_order(ids, n_classes, order, dev, what='speaker id'):
     """Class indices of a pass whose rows are recordings order[0], order[1], ...: ids (B values or one for all; anything `_index_tensor`
     takes) -> (B,) int64 device tensor in row order, range-checked like nn.Embedding.  Host ids are checked, broadcast and reordered on the

@@ -140,7 +140,7 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
 
 
 def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None,
-                     given=None):
+                     given=None, given_poses=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -156,7 +156,9 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     the submitted list.  sampling: one sampling record (`_lib.sampling_record`) for all recordings or one per recording in submission order —
     they follow the recordings through the sort (the body branch then runs `ts_body_pixel_infer_mixed_ctl`; the face generator takes none).
     given: one entry per recording in submission order, None or the (G_b, 2) code rows the body decode of that recording starts from
-    (`TrainWrapper.generate_clips`; the body branch then runs `ts_body_pixel_infer_mixed_given`); they follow the recordings through the sort."""
+    (`TrainWrapper.generate_clips`; the body branch then runs `ts_body_pixel_infer_mixed_given`); they follow the recordings through the sort.
+    given_poses: the same from motion — None or the (P_b, 129) pose frames of that recording's head, encoded on the device
+    (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_poses`).  A recording brings one kind."""
     import ctypes as C
 
     import numpy as np
@@ -191,11 +193,15 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if sampling is not None:   # validated before the first launch; sorted slot k holds the record of submitted recording order[k]
         recs = _lib.sampling_records(sampling, B)
         sampling = _lib.sampling_table([recs[i] for i in order], B, body.generator.input_dim, mode)
-    if given is not None:      # validated before the first launch, too: rows_sub[i] = code rows of submitted recording i
+    if given is not None or given_poses is not None:      # validated before the first launch, too: rows_sub[i] = code rows of submitted recording i
         rows_sub = [0] * B
         for k, i in enumerate(order):
             rows_sub[i] = int(tab["mfcc_rows"][k]) // 4
-        given = _lib.given_block(given, rows_sub, body.generator.input_dim, order, who="whole_body_clips")
+        _lib.given_kinds_check(given, given_poses, B, "whole_body_clips")
+        if given is not None:
+            given = _lib.given_block(given, rows_sub, body.generator.input_dim, order, who="whole_body_clips")
+        if given_poses is not None:
+            given_poses = _lib.given_pose_block(given_poses, rows_sub, order, who="whole_body_clips", width=body.each_dim[1] + body.each_dim[2])
     dev = body.generator._dev()
     # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
     wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
@@ -212,7 +218,7 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
         side.wait_stream(cur)
     with torch.cuda.stream(side):
         _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling,
-                                               given=given)
+                                               given=given, given_poses=given_poses)
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

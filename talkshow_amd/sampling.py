@@ -203,6 +203,22 @@ def sample_given(logits, u, forced, given, records=None, greedy=False):
     return idx, lp
 
 
+def given_pose_rows(P, T):
+    """`ts_given_pose_rows_check` for one clip: P given pose frames (None: none) of a clip with T MFCC rows -> the given code rows G = P // 4.
+    0 for None or P = 0.  ValueError for 1 <= P <= 3 (frames that cannot make one code row: the caller has miscounted), for P < 0, and for
+    P // 4 > T // 4 (more rows than the clip has of its own).  A remainder P % 4 is dropped, as the VQ encoder drops it."""
+    if P is None:
+        return 0
+    P, T = int(P), int(T)
+    if P == 0:
+        return 0
+    if P < 4:
+        raise ValueError(f"given poses: P = {P} frames; one code row needs 4 (or none: P = 0)")
+    if P // 4 > T // 4:
+        raise ValueError(f"given poses: P = {P} frames are {P // 4} code rows but the clip has {T // 4} of its own")
+    return P // 4
+
+
 LOGPROB_SUM_LANES = 256
 
 
