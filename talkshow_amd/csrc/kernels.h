@@ -432,7 +432,8 @@ struct SampleParams {
 hipError_t launch_sample(const SampleParams &p, hipStream_t stream);
 
 // Per-clip sampling controls (talkshow_hip.h: ts_sampling and the rule of steps 1-5).  The device record of a clip: 1 / temperature as the
-// HOST computed it in fp32, top_p, top_k (0 or >= V: off).  A sibling of SampleParams: the sampler without controls keeps its arguments.
+// HOST computed it in fp32, top_p, top_k (0 or >= V: off).  A sibling of SampleParams: the sampler without controls keeps its arguments (vq.hip: sample_ctl_body behind
+// sample_ctl_kernel<FAST, LP>; the samplers without controls share sample_plain_body).
 struct SampleCtl {
     float inv_t, top_p;
     int32_t top_k, pad;
@@ -451,7 +452,8 @@ hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream);
 
 // The sampler without controls plus the log-probability of the chosen (greedy, drawn) or given (teacher forced: s.codes is read) code:
 // logprob[b * lp_stride] = (float)((double)(l_c - max) - log((double)S)), S the sampler's own fp32 total (talkshow_hip.h).  A sibling of
-// SampleParams again: sample_kernel keeps its arguments and its code.
+// SampleParams again: sample_kernel keeps its arguments.  vq.hip: sample_lp_kernel = sample_plain_body<LP = true, GIVEN = false>,
+// sample_kernel = the same body with both flags off.
 struct SampleLpParams {
     SampleParams s;            // any mode
     float *logprob;
@@ -462,6 +464,7 @@ hipError_t launch_sample_lp(const SampleLpParams &p, hipStream_t stream);
 // sample_ctl_given_kernel): clip slot b is forced — its code is read from `given`, nothing is drawn — iff the launch's absolute position
 // (c.s.position plus the dynamic base word) is below 2 * rows[b].  c: the sibling's arguments (c.s.mode greedy / uniforms / Philox; c.ctl,
 // c.kept and c.logprob optional, a table needs a drawing mode).  A sibling of the three structs above again: they keep their arguments.
+// The given kernels are the GIVEN = true instantiations of the two bodies their siblings are made of.
 struct SampleGivenParams {
     SampleCtlParams c;
     const int *rows;           // (slots,) G of every clip slot of the pass

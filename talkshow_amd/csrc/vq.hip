@@ -759,7 +759,10 @@ hipError_t launch_clock_sample(unsigned long long *out, int n, unsigned long lon
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// sampler: one workgroup per clip over V logits.
+// samplers: one workgroup per clip over V logits.  Twelve __global__ entries, two bodies: sample_plain_body<LP, GIVEN> behind
+// sample_kernel, sample_lp_kernel, sample_given_kernel and sample_lp_given_kernel; sample_ctl_body<FAST, LP, GIVEN> behind the four
+// sample_ctl_kernel and the four sample_ctl_given_kernel instantiations.  An entry declares its LDS and calls its body; the variants
+// differ by `if constexpr` inside a body, so the rule below is stated on the device once per body and its blocks once.
 //   greedy   : argmax, ties -> lowest index (torch.argmax on CPU returns the first maximum).
 //   sampling : inverse CDF of softmax(logits).  p_v ∝ exp(l_v - max); thread t owns the contiguous chunk
 //              [t*V/256, (t+1)*V/256), sums it left to right; thread 0 prefix-sums the 256 chunk sums left to right;
@@ -780,54 +783,32 @@ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint
     o0 = c0;
 }
 
-__global__ __launch_bounds__(256) void sample_kernel(const SampleParams p) {
-    __shared__ float sf[256 + 1];
-    __shared__ int si[256];
-    __shared__ float s_thr;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+// ---- the blocks both sampler bodies (sample_plain_body, sample_ctl_body) are made of, each written once ----
 
-    // Every thread owns `chunk` consecutive logits [v0, v1).  For the production vocabulary (V = 2048: chunk = 8) they are
-    // fetched up front with two 16-byte loads — this kernel sits on the dependent chain, and a load-per-iteration loop
-    // costs one memory round trip per element.
-    const int chunk = (p.V + 255) / 256;
-    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
-    const bool fast = chunk == 8 && (p.V & 7) == 0;
-    float x[8];
-    if (fast) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
+__device__ __forceinline__ const float *sample_row(const SampleParams &p, int b) {
+    return p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+}
+// the row load of the vector path: a thread's 8 consecutive logits from two 16-byte loads, up front — the samplers sit on the dependent
+// chain, and a load-per-iteration loop costs one memory round trip per element
+__device__ __forceinline__ void sample_load8(const float *lg, int v0, float (&x)[8]) {
+    const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
-    }
-
-    if (p.logits_copy) {
-        float *dst = p.logits_copy + (long)b * p.copy_stride;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
-        } else {
-            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
-        }
-    }
-
-    if (p.mode == TS_TEACHER_FORCED) {
-        if (tid == 0) p.tok32[(long)b * p.tok_stride] = (int)p.codes[(long)b * p.code_stride];
-        return;
-    }
-
-    // ---- max / argmax (needed by both modes); ties -> lowest index ----
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
+    for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
+}
+// logits_copy: every thread stores its chunk [v0, v1) (vector path: the 8 registers)
+__device__ __forceinline__ void sample_copy_row(const SampleParams &p, int b, bool fast, const float *lg, const float (&x)[8], int v0, int v1) {
+    if (!p.logits_copy) return;
+    float *dst = p.logits_copy + (long)b * p.copy_stride;
     if (fast) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (x[k] > best) { best = x[k]; bi = v0 + k; }
+        for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
     } else {
-        for (int v = v0; v < v1; ++v) {
-            const float t = lg[v];
-            if (t > best) { best = t; bi = v; }
-        }
+        for (int v = v0; v < v1; ++v) dst[v] = lg[v];
     }
+}
+// workgroup arg-max over every thread's own (best, bi); ties -> lowest index.  Uses sf[0..3] / si[0..3] between two barriers of its own.
+__device__ __forceinline__ void sample_argmax(float &best, int &bi, float *sf, int *si) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const float ob = __shfl_xor(best, off);
@@ -840,140 +821,37 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleParams p) {
     for (int w = 1; w < 4; ++w)
         if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
     __syncthreads();
-
-    int choice = bi;
-    if (p.mode != TS_SAMPLE_GREEDY) {
-        float u;
-        if (p.mode == TS_SAMPLE_UNIFORMS) {
-            u = p.uniforms[(long)b * p.u_stride];
-        } else {
-            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-            // a mixed pass orders its clips by length: the subsequence then comes from a per-clip table, so that a clip's draws keep
-            // depending on its GLOBAL index only
-            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
-            uint32_t r;
-            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                          (uint32_t)(seed >> 32), r);
-            u = (float)(r >> 8) * (1.0f / 16777216.0f);
-        }
-        float s = 0.f;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += det_expf(x[k] - best);
-        } else {
-            for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
-        }
-        sf[tid + 1] = s;
-        __syncthreads();
-        if (tid == 0) {
-            float c = 0.f;
-            sf[0] = 0.f;
-            for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }   // sf[t] = sum of chunks < t
-            s_thr = u * c;
-        }
-        __syncthreads();
-        const float thr = s_thr;
-        // owner: the first chunk whose inclusive prefix exceeds thr (the last non-empty chunk if none does)
-        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
-        if (mine && v0 < p.V) {
-            float c = sf[tid];
-            int k = v1 - 1;
-            if (fast) {
-                bool found = false;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {   // same running sum as the loop below; the first crossing is latched
-                    c += det_expf(x[j] - best);
-                    if (!found && c > thr) { k = v0 + j; found = true; }
-                }
-            } else {
-                for (int v = v0; v < v1; ++v) {
-                    c += det_expf(lg[v] - best);
-                    if (c > thr) { k = v; break; }
-                }
-            }
-            si[0] = k;
-        } else if (mine) {
-            si[0] = p.V - 1;
-        }
-        __syncthreads();
-        choice = si[0];
-    }
-    if (tid == 0) {
-        p.tok32[(long)b * p.tok_stride] = choice;
-        p.codes[(long)b * p.code_stride] = choice;
-    }
 }
-
-hipError_t launch_sample(const SampleParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL(sample_kernel, dim3(p.B), dim3(256), 0, stream, p);
-    return hipGetLastError();
+// the source of u for clip b in a drawing mode: the injected uniform, or Philox at (position, clip)
+__device__ __forceinline__ float sample_uniform(const SampleParams &p, int b) {
+    if (p.mode == TS_SAMPLE_UNIFORMS) return p.uniforms[(long)b * p.u_stride];
+    const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
+    // a mixed pass orders its clips by length: the subsequence then comes from a per-clip table, so that a clip's draws keep
+    // depending on its GLOBAL index only
+    const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+    uint32_t r;
+    philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
+                  (uint32_t)(seed >> 32), r);
+    return (float)(r >> 8) * (1.0f / 16777216.0f);
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// sample_kernel plus the log-probability of the code (talkshow_hip.h, "log-probabilities"): a kernel of its own, so that sample_kernel
-// keeps its code and a pass without the output its launches.  Same launch shape, same loads, the same choice in every mode; greedy and
-// teacher forced compute the total S here too (the sampler's summation structure: chunk sums left to right, then the 256 chunk sums left
-// to right).  The logit of the code c is picked up by the thread that OWNS index c (a 64-bit comparison against its chunk): c is never an
-// address, and a teacher-forced code outside [0, V) finds no owner — thread 0 then writes NaN.  One fp64 log on one lane, one 4-byte store.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ inline float logprob_value(float d, float S) { return (float)((double)d - log((double)S)); }
-
-__global__ __launch_bounds__(256) void sample_lp_kernel(const SampleLpParams lp) {
-    __shared__ float sf[256 + 1];
-    __shared__ int si[256];
-    __shared__ float s_thr;
-    const SampleParams &p = lp.s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
-
-    const int chunk = (p.V + 255) / 256;
-    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
-    // the production vocabulary on 16-byte aligned rows: every thread's 8 logits come from two 16-byte loads up front, as in sample_kernel
-    const bool fast = p.V == 2048 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
-    float x[8];
-    if (fast) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
-    }
-
-    if (p.logits_copy) {
-        float *dst = p.logits_copy + (long)b * p.copy_stride;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
-        } else {
-            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
+// thread 0, after every thread t stored its chunk sum in sf[t + 1]: the 256 sums left to right, sf[t] = sum of the chunks < t; returns the
+// total (= sf[256]).  LAST: hi[t] holds chunk t's highest kept index or -1, and last receives the highest kept index of the row.
+template <bool LAST = false>
+__device__ __forceinline__ float sample_prefix_sum(float *sf, const int *hi = nullptr, int *last = nullptr) {
+    float c = 0.f;
+    int l = 0;
+    sf[0] = 0.f;
+    for (int t = 1; t <= 256; ++t) {
+        c += sf[t]; sf[t] = c;
+        if constexpr (LAST) {
+            if (hi[t - 1] >= 0) l = hi[t - 1];
         }
     }
-
-    // ---- max / argmax; ties -> lowest index ----
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    if (fast) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (x[k] > best) { best = x[k]; bi = v0 + k; }
-    } else {
-        for (int v = v0; v < v1; ++v) {
-            const float t = lg[v];
-            if (t > best) { best = t; bi = v; }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
-    __syncthreads();
-    best = sf[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w)
-        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
-    __syncthreads();
-
-    // ---- the total, in every mode: sf[t] = sum of the chunks < t, sf[256] = S ----
+    if constexpr (LAST) *last = l;
+    return c;
+}
+// a thread's chunk sum of p_v ∝ exp(l_v - max), left to right
+__device__ __forceinline__ float sample_chunk_sum(bool fast, const float *lg, const float (&x)[8], int v0, int v1, float best) {
     float s = 0.f;
     if (fast) {
 #pragma unroll
@@ -981,80 +859,199 @@ __global__ __launch_bounds__(256) void sample_lp_kernel(const SampleLpParams lp)
     } else {
         for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
     }
-    sf[tid + 1] = s;
-    __syncthreads();
-    const bool draws = p.mode == TS_SAMPLE_UNIFORMS || p.mode == TS_SAMPLE_PHILOX;
-    if (tid == 0) {
-        float u = 0.f;
-        if (p.mode == TS_SAMPLE_UNIFORMS) {
-            u = p.uniforms[(long)b * p.u_stride];
-        } else if (p.mode == TS_SAMPLE_PHILOX) {
-            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
-            uint32_t r;
-            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                          (uint32_t)(seed >> 32), r);
-            u = (float)(r >> 8) * (1.0f / 16777216.0f);
+    return s;
+}
+// the draw, after sample_prefix_sum: the owner — the first chunk whose inclusive prefix exceeds thr (the last non-empty chunk if none
+// does) — repeats its running sum and finds the first index that crosses thr.  One barrier; the index travels through si[0].
+__device__ __forceinline__ int sample_crossing(bool fast, const float *lg, const float (&x)[8], int v0, int v1, int V, float best, float thr,
+                                               const float *sf, int *si) {
+    const int tid = threadIdx.x;
+    const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
+    if (mine && v0 < V) {
+        float c = sf[tid];
+        int k = v1 - 1;
+        if (fast) {
+            bool found = false;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {   // same running sum as the loop below; the first crossing is latched
+                c += det_expf(x[j] - best);
+                if (!found && c > thr) { k = v0 + j; found = true; }
+            }
+        } else {
+            for (int v = v0; v < v1; ++v) {
+                c += det_expf(lg[v] - best);
+                if (c > thr) { k = v; break; }
+            }
         }
-        float c = 0.f;
-        sf[0] = 0.f;
-        for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }
-        s_thr = u * c;
+        si[0] = k;
+    } else if (mine) {
+        si[0] = V - 1;
     }
     __syncthreads();
+    return si[0];
+}
+// given rows (talkshow_hip.h): clip b of a pass brings G_b = rows[b] code rows that are TAKEN, not drawn.  A workgroup is FORCED iff its
+// absolute position 2 row + column — the Philox counter word, the dynamic base word of a replayed graph included — is below 2 G_b: a
+// workgroup-uniform decision from kernel arguments and two uniform loads, taken before any barrier.  A given code is compared, never used
+// as an address; outside [0, V) it leaves -1 in tok32 (the chain's gathers read a row of zeros for a negative index).
+__device__ __forceinline__ bool given_forced(const SampleParams &p, const int *rows, int b) {
+    const uint32_t pos = p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u);
+    const int G = rows[b];
+    return G > 0 && (uint64_t)pos < 2ull * (uint64_t)G;
+}
+__device__ __forceinline__ int given_token(long long code, int V) { return code >= 0 && code < (long long)V ? (int)code : -1; }
+// the log-probability (talkshow_hip.h, "log-probabilities") of the row's code, stored by the ONE thread that owns the code's index: d = the
+// fp32 argument of the code's exponential, S = the row's total.  A code outside [0, V) finds no owner: thread 0 then stores NaN.
+// kept = false: a given code the filters removed has weight 0 in the distribution the row would have been drawn from, log(0).
+__device__ __forceinline__ void sample_store_logprob(float *out, float d, float S, bool kept = true) {
+    *out = kept ? (float)((double)d - log((double)S)) : (float)log(0.0);
+}
+__device__ __forceinline__ void sample_store_unowned(float *out, long long code, int V) {
+    if (code < 0 || code >= (long long)V) *out = __uint_as_float(0x7fc00000u);
+}
 
-    long long code;   // 64 bits: a teacher-forced code is compared, never truncated
-    if (p.mode == TS_TEACHER_FORCED) {
-        code = p.codes[(long)b * p.code_stride];
-    } else if (!draws) {
-        code = bi;
-    } else {
-        const float thr = s_thr;
-        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
-        if (mine && v0 < p.V) {
-            float c = sf[tid];
-            int k = v1 - 1;
-            if (fast) {
-                bool found = false;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    c += det_expf(x[j] - best);
-                    if (!found && c > thr) { k = v0 + j; found = true; }
-                }
-            } else {
-                for (int v = v0; v < v1; ++v) {
-                    c += det_expf(lg[v] - best);
-                    if (c > thr) { k = v; break; }
-                }
+// ---------------------------------------------------------------------------------------------------------------
+// The body of the four samplers without controls.  Flags:
+//   LP     also the log-probability of the code: greedy and teacher forced compute the total S too (the sampler's summation structure).
+//          The logit of the code c is picked up by the thread that OWNS index c (a 64-bit comparison against its chunk): c is never an
+//          address.  One fp64 log on one lane, one 4-byte store.  Without LP a teacher-forced workgroup copies its code and leaves.
+//   GIVEN  a forced workgroup takes its code from `given`, writes it to tok32 and codes, reads no uniform and draws nothing: without LP
+//          it leaves right after the copy, with LP it scores the code the way LP scores a teacher-forced one.  An unforced workgroup
+//          executes the arithmetic of the kernel without GIVEN, operation for operation.
+// Each kernel keeps the predicate of its vector path: chunk == 8 and V a multiple of 8 without LP, V == 2048 on a 16-byte aligned row
+// with it.  The body is inlined into its four __global__ entries; what was compared against the six separate kernels it replaces is
+// recorded in DESIGN.md §5 ("One body per sampler family").
+// ---------------------------------------------------------------------------------------------------------------
+template <bool LP, bool GIVEN>
+__device__ __forceinline__ void sample_plain_body(const SampleParams &p, float *logprob, long lp_stride, const int *rows, const int64_t *given,
+                                                  long given_stride, float *sf, int *si, float &s_thr) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float *lg = sample_row(p, b);
+    bool forced = false;   // workgroup-uniform, ahead of every barrier
+    if constexpr (GIVEN && LP) forced = given_forced(p, rows, b);
+
+    // Every thread owns `chunk` consecutive logits [v0, v1); for the production vocabulary (V = 2048: chunk = 8) they stay in registers
+    const int chunk = (p.V + 255) / 256;
+    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
+    bool fast;
+    if constexpr (LP) fast = p.V == 2048 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
+    else fast = chunk == 8 && (p.V & 7) == 0;
+    float x[8];
+    if (fast) sample_load8(lg, v0, x);
+    sample_copy_row(p, b, fast, lg, x, v0, v1);
+
+    if constexpr (!LP && GIVEN) {
+        if (given_forced(p, rows, b)) {
+            if (tid == 0) {
+                const long long code = given[(long)b * given_stride];
+                p.tok32[(long)b * p.tok_stride] = given_token(code, p.V);
+                p.codes[(long)b * p.code_stride] = code;
             }
-            si[0] = k;
-        } else if (mine) {
-            si[0] = p.V - 1;
+            return;
+        }
+    } else if constexpr (!LP) {
+        if (p.mode == TS_TEACHER_FORCED) {
+            if (tid == 0) p.tok32[(long)b * p.tok_stride] = (int)p.codes[(long)b * p.code_stride];
+            return;
+        }
+    }
+
+    // ---- max / argmax (needed by every mode); ties -> lowest index ----
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (fast) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (x[k] > best) { best = x[k]; bi = v0 + k; }
+    } else {
+        for (int v = v0; v < v1; ++v) {
+            const float t = lg[v];
+            if (t > best) { best = t; bi = v; }
+        }
+    }
+    sample_argmax(best, bi, sf, si);
+
+    if constexpr (!LP) {
+        int choice = bi;
+        if (p.mode != TS_SAMPLE_GREEDY) {
+            const float u = sample_uniform(p, b);
+            sf[tid + 1] = sample_chunk_sum(fast, lg, x, v0, v1, best);
+            __syncthreads();
+            if (tid == 0) s_thr = u * sample_prefix_sum(sf);
+            __syncthreads();
+            choice = sample_crossing(fast, lg, x, v0, v1, p.V, best, s_thr, sf, si);
+        }
+        if (tid == 0) {
+            p.tok32[(long)b * p.tok_stride] = choice;
+            p.codes[(long)b * p.code_stride] = choice;
+        }
+    } else {
+        // ---- the total, in every mode: sf[t] = sum of the chunks < t, sf[256] = S ----
+        sf[tid + 1] = sample_chunk_sum(fast, lg, x, v0, v1, best);
+        __syncthreads();
+        const bool draws = !forced && (p.mode == TS_SAMPLE_UNIFORMS || p.mode == TS_SAMPLE_PHILOX);
+        if (tid == 0) {
+            const float u = draws ? sample_uniform(p, b) : 0.f;   // the uniform of a forced row is never read
+            s_thr = u * sample_prefix_sum(sf);
         }
         __syncthreads();
-        code = si[0];
-    }
 
-    float *out = lp.logprob + (long)b * lp.lp_stride;
-    if (code >= (long long)v0 && code < (long long)v1) {   // the owner of index `code`: exactly one thread, or none when it is out of range
-        float lc = 0.f;
-        if (fast) {
+        const bool taken = GIVEN ? forced : p.mode == TS_TEACHER_FORCED;   // the code is read, not chosen
+        long long code;   // 64 bits: a teacher-forced or given code is compared, never truncated
+        if (taken) code = GIVEN ? given[(long)b * given_stride] : p.codes[(long)b * p.code_stride];
+        else if (!draws) code = bi;
+        else code = sample_crossing(fast, lg, x, v0, v1, p.V, best, s_thr, sf, si);
+
+        float *out = logprob + (long)b * lp_stride;
+        if (code >= (long long)v0 && code < (long long)v1) {   // the owner of index `code`: exactly one thread, or none when it is out of range
+            float lc = 0.f;
+            if (fast) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if ((long long)(v0 + k) == code) lc = x[k];
-        } else {
-            for (int v = v0; v < v1; ++v)
-                if ((long long)v == code) lc = lg[v];
+                for (int k = 0; k < 8; ++k)
+                    if ((long long)(v0 + k) == code) lc = x[k];
+            } else {
+                for (int v = v0; v < v1; ++v)
+                    if ((long long)v == code) lc = lg[v];
+            }
+            sample_store_logprob(out, lc - best, sf[256]);
         }
-        *out = logprob_value(lc - best, sf[256]);
-    }
-    if (tid == 0) {
-        if (code < 0 || code >= (long long)p.V) *out = __uint_as_float(0x7fc00000u);
-        p.tok32[(long)b * p.tok_stride] = (int)code;
-        if (p.mode != TS_TEACHER_FORCED) p.codes[(long)b * p.code_stride] = code;
+        if (tid == 0) {
+            sample_store_unowned(out, code, p.V);
+            p.tok32[(long)b * p.tok_stride] = GIVEN ? given_token(code, p.V) : (int)code;
+            if (GIVEN || p.mode != TS_TEACHER_FORCED) p.codes[(long)b * p.code_stride] = code;
+        }
     }
 }
 
+__global__ __launch_bounds__(256) void sample_kernel(const SampleParams p) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    sample_plain_body<false, false>(p, nullptr, 0, nullptr, nullptr, 0, sf, si, s_thr);
+}
+__global__ __launch_bounds__(256) void sample_lp_kernel(const SampleLpParams lp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    sample_plain_body<true, false>(lp.s, lp.logprob, lp.lp_stride, nullptr, nullptr, 0, sf, si, s_thr);
+}
+__global__ __launch_bounds__(256) void sample_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    sample_plain_body<false, true>(gp.c.s, nullptr, 0, gp.rows, gp.given, gp.given_stride, sf, si, s_thr);
+}
+__global__ __launch_bounds__(256) void sample_lp_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    sample_plain_body<true, true>(gp.c.s, gp.c.logprob, gp.c.lp_stride, gp.rows, gp.given, gp.given_stride, sf, si, s_thr);
+}
+
+hipError_t launch_sample(const SampleParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL(sample_kernel, dim3(p.B), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 hipError_t launch_sample_lp(const SampleLpParams &p, hipStream_t stream) {
     if (!p.logprob || p.s.V < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sample_lp_kernel, dim3(p.s.B), dim3(256), 0, stream, p);
@@ -1110,7 +1107,9 @@ hipError_t launch_logprob_sums(const float *logprob, int B, int H, const int *le
 
 // ---------------------------------------------------------------------------------------------------------------
 // sampler with per-clip controls (temperature, top-k, top-p): the rule is stated in talkshow_hip.h (ts_sampling, steps 1-5) and restated
-// in talkshow_amd/sampling.py.  A kernel of its own: sample_kernel above keeps its code, and a pass without controls its launches.
+// in talkshow_amd/sampling.py.  A body of its own (sample_ctl_body below) behind kernels of their own: a pass without controls keeps the
+// launches of the plain body's kernels.  The two bodies share the blocks above (row load, arg-max, the source of u, the prefix sum, the
+// given-row decision, the log-probability store) and nothing else.
 //
 // Same launch shape (one workgroup of 256 threads per clip, thread t owns the contiguous chunk [t*ceil(V/256), ...)); at V = 2048 the 8
 // logits of a thread, their order keys and their quantised weights stay in registers.  The kept set is a PREFIX of the ranking (logit
@@ -1124,7 +1123,7 @@ hipError_t launch_logprob_sums(const float *logprob, int B, int H, const int *le
 //            without a second barrier or an LDS round trip.
 // top-k descends by count to the key K* of rank k-1, top-p by mass to the lowest key whose mass-above is below the threshold; four levels
 // each, level 0 shared.  Ties at the two boundary keys are resolved in index order with one packed prefix count over the threads.
-// A neutral record (1, 1, 0) skips all of it (workgroup-uniform) and computes sample_kernel's bits.
+// A neutral record (1, 1, 0) skips all of it (workgroup-uniform) and computes the plain body's bits.
 // ---------------------------------------------------------------------------------------------------------------
 typedef unsigned long long ctl_u64;
 constexpr int CTL_CNT_SHIFT = 44;   // a bin = count << 44 | mass; mass = sums of floor(w * 2^31)
@@ -1210,38 +1209,48 @@ __device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) 
     return ok;
 }
 
-// LP: also write the log-probability of the drawn code under the distribution it was drawn from (cp.logprob; talkshow_hip.h,
-// "log-probabilities"): d_c - log S with d_c the argument of the drawn code's exponential and S the total of the kept weights, both already
-// here.  The instantiations without it are the kernels they were.
-template <bool FAST, bool LP>
-__global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams cp) {
-    __shared__ float sf[256 + 1];
-    __shared__ int si[256];
-    __shared__ float s_thr;
-    __shared__ int s_last;
-    __shared__ uint32_t s_tie[4];
-    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];   // levels 0-3 of the top-k descent (level 0 shared), 1-3 of the top-p descent
+// The body of the eight samplers with controls.  Flags:
+//   FAST   V = 2048 on 16-byte aligned rows (the launchers decide): every thread owns 8 logits, held in registers from two 16-byte loads
+//   LP     also write the log-probability of the row's code under the distribution it was drawn from (cp.logprob; talkshow_hip.h,
+//          "log-probabilities"): d_c - log S with d_c the argument of the code's exponential and S the total of the kept weights, both
+//          already here
+//   GIVEN  given rows: without LP a forced workgroup copies its code and leaves ahead of everything; with it, it runs steps 1-4 and the
+//          sums of step 5 as an unforced one does (the thread that owns the given code notes whether the filters kept it), then writes
+//          d_c - log S for a kept code and log(0) for a code the filters removed.  An unforced workgroup executes the arithmetic of the
+//          kernel without GIVEN, operation for operation.
+// Inlined into its eight __global__ entries; DESIGN.md §5 ("One body per sampler family") records what was compared against the two
+// separate kernel templates it replaces.
+template <bool FAST, bool LP, bool GIVEN>
+__device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride, float *sf,
+                                                int *si, float &s_thr, int &s_last, uint32_t *s_tie, ctl_u64 (*hist)[256]) {
     const SampleParams &p = cp.s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
+    const float *lg = sample_row(p, b);
+    bool forced = false;       // workgroup-uniform, ahead of every barrier
+    long long gcode = -1;
+    if constexpr (GIVEN) {
+        forced = given_forced(p, rows, b);
+        gcode = forced ? (long long)given[(long)b * given_stride] : -1;
+    }
 
     const int chunk = (p.V + 255) / 256;
     const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
-    const int n = FAST ? 8 : max(v1 - v0, 0);   // FAST: V = 2048, every thread owns 8 logits, held in registers from two 16-byte loads
+    const int n = FAST ? 8 : max(v1 - v0, 0);
     float x[8];
-    if constexpr (FAST) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
-    }
+    if constexpr (FAST) sample_load8(lg, v0, x);
     auto logit = [&](int k) -> float {
         if constexpr (FAST) return x[k];
         else return lg[v0 + k];
     };
-    if (p.logits_copy) {
-        float *dst = p.logits_copy + (long)b * p.copy_stride;
-#pragma unroll 8
-        for (int k = 0; k < n; ++k) dst[v0 + k] = logit(k);
+    sample_copy_row(p, b, FAST, lg, x, v0, v1);
+    if constexpr (GIVEN && !LP) {
+        if (forced) {
+            if (tid == 0) {
+                p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
+                p.codes[(long)b * p.code_stride] = gcode;
+            }
+            return;
+        }
     }
 
     const SampleCtl rec = cp.ctl[b];
@@ -1254,7 +1263,7 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
         for (int i = 0; i < 7; ++i) hist[i][tid] = 0;
     }
 
-    // ---- max / argmax as in sample_kernel; ties -> lowest index ----
+    // ---- max / argmax as in the plain body; ties -> lowest index ----
     float best = -INFINITY;
     int bi = 0x7fffffff;
 #pragma unroll 8
@@ -1262,31 +1271,11 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
         const float t = logit(k);
         if (t > best) { best = t; bi = v0 + k; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
-    __syncthreads();
-    best = sf[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w)
-        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
-    __syncthreads();
+    sample_argmax(best, bi, sf, si);
 
-    // the uniform: the same source as sample_kernel, so it does not depend on the record
-    float u;
-    if (p.mode == TS_SAMPLE_UNIFORMS) {
-        u = p.uniforms[(long)b * p.u_stride];
-    } else {
-        const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-        const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
-        uint32_t r;
-        philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                      (uint32_t)(seed >> 32), r);
-        u = (float)(r >> 8) * (1.0f / 16777216.0f);
-    }
+    // the uniform: the plain body's source, so it does not depend on the record; a forced row reads none
+    float u = 0.f;
+    if (!forced) u = sample_uniform(p, b);
 
     const float inv_t = rec.inv_t;
     auto weight = [&](int k) -> float { return ctl_weight(logit(k), best, inv_t); };
@@ -1370,9 +1359,12 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
         jp0 = (int)(ex >> 16);
     }
 
-    // ---- step 5: sample_kernel's inverse CDF over w' = kept ? w : 0 (adding a zero changes no bit, so dropped tokens are skipped) ----
+    // ---- step 5: the plain body's inverse CDF over w' = kept ? w : 0 (adding a zero changes no bit, so dropped tokens are skipped);
+    //      the owner of a given code notes its logit and whether it was kept ----
     float s = 0.f;
     int hi = -1;   // highest kept index of the chunk
+    bool gkept = false;
+    float glc = 0.f;
     {
         int jk = jk0, jp = jp0;
         unsigned char *kd = cp.kept ? cp.kept + (long)b * p.V : nullptr;
@@ -1381,23 +1373,30 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
             const bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
             if (kp) { s += weight(k); hi = v0 + k; }
             if (kd) kd[v0 + k] = kp ? 1 : 0;
+            if constexpr (GIVEN && LP) {
+                if ((long long)(v0 + k) == gcode) { gkept = kp; glc = logit(k); }
+            }
         }
     }
     sf[tid + 1] = s;
     si[tid] = hi;
     __syncthreads();
     if (tid == 0) {
-        float c = 0.f;
-        int last = 0;
-        sf[0] = 0.f;
-        for (int t = 1; t <= 256; ++t) {
-            c += sf[t]; sf[t] = c;
-            if (si[t - 1] >= 0) last = si[t - 1];
-        }
-        s_thr = u * c;
-        s_last = last;   // highest kept index of the row (rank 0 is always kept)
+        s_thr = u * sample_prefix_sum<true>(sf, si, &s_last);   // s_last: the highest kept index of the row (rank 0 is always kept)
     }
     __syncthreads();
+    if constexpr (GIVEN && LP) {
+        if (forced) {   // workgroup-uniform: S = sf[256] is there, nothing is drawn
+            float *out = cp.logprob + (long)b * cp.lp_stride;
+            if (gcode >= (long long)v0 && gcode < (long long)v1) sample_store_logprob(out, ctl_arg(glc, best, inv_t), sf[256], gkept);
+            if (tid == 0) {
+                sample_store_unowned(out, gcode, p.V);
+                p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
+                p.codes[(long)b * p.code_stride] = gcode;
+            }
+            return;
+        }
+    }
     const float thr = s_thr;
     const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
     const int last = s_last;
@@ -1430,9 +1429,30 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
 #pragma unroll 8
             for (int k = 0; k < n; ++k)
                 if (v0 + k == choice) lc = logit(k);
-            cp.logprob[(long)b * cp.lp_stride] = logprob_value(ctl_arg(lc, best, inv_t), sf[256]);
+            sample_store_logprob(cp.logprob + (long)b * cp.lp_stride, ctl_arg(lc, best, inv_t), sf[256]);
         }
     }
+}
+
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams cp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];   // levels 0-3 of the top-k descent (level 0 shared), 1-3 of the top-p descent
+    sample_ctl_body<FAST, LP, false>(cp, nullptr, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist);
+}
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, true>(gp.c, gp.rows, gp.given, gp.given_stride, sf, si, s_thr, s_last, s_tie, hist);
 }
 
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
@@ -1448,540 +1468,6 @@ hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
         hipLaunchKernelGGL((sample_ctl_kernel<false, false>), dim3(p.s.B), dim3(256), 0, stream, p);
     }
     return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// "given" variants of the three samplers (talkshow_hip.h, "given rows"): clip b of a pass brings G_b code rows that are TAKEN, not drawn.
-// Kernels of their own: sample_kernel, sample_lp_kernel and the four sample_ctl_kernel instantiations above keep their source and their
-// code, and a pass without given rows its launches.  A workgroup (one per clip, 256 threads) is FORCED iff its absolute position
-// 2 row + column — the Philox counter word, the dynamic base word of a replayed graph included — is below 2 G[slot]: a workgroup-uniform
-// decision from kernel arguments and two uniform loads, taken before any barrier.  A forced workgroup reads its code from the staging
-// block, writes it to tok32 and codes, reads no uniform and draws nothing; with the log-probability output it computes the row's S and the
-// code's d_c exactly as its sibling does for a code it drew.  An unforced workgroup executes its sibling's arithmetic, operation for
-// operation.  A given code is compared, never used as an address; outside [0, V) it leaves -1 in tok32 (the chain's gathers read a
-// row of zeros for a negative index) and NaN as its log-probability.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ inline bool given_forced(const SampleParams &p, const SampleGivenParams &gp, int b) {
-    const uint32_t pos = p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u);
-    const int G = gp.rows[b];
-    return G > 0 && (uint64_t)pos < 2ull * (uint64_t)G;
-}
-__device__ inline int given_token(long long code, int V) { return code >= 0 && code < (long long)V ? (int)code : -1; }
-
-__global__ __launch_bounds__(256) void sample_given_kernel(const SampleGivenParams gp) {
-    __shared__ float sf[256 + 1];
-    __shared__ int si[256];
-    __shared__ float s_thr;
-    const SampleParams &p = gp.c.s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
-
-    const int chunk = (p.V + 255) / 256;
-    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
-    const bool fast = chunk == 8 && (p.V & 7) == 0;
-    float x[8];
-    if (fast) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
-    }
-
-    if (p.logits_copy) {
-        float *dst = p.logits_copy + (long)b * p.copy_stride;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
-        } else {
-            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
-        }
-    }
-
-    if (given_forced(p, gp, b)) {   // workgroup-uniform, ahead of every barrier
-        if (tid == 0) {
-            const long long code = gp.given[(long)b * gp.given_stride];
-            p.tok32[(long)b * p.tok_stride] = given_token(code, p.V);
-            p.codes[(long)b * p.code_stride] = code;
-        }
-        return;
-    }
-
-    // ---- from here on: sample_kernel ----
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    if (fast) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (x[k] > best) { best = x[k]; bi = v0 + k; }
-    } else {
-        for (int v = v0; v < v1; ++v) {
-            const float t = lg[v];
-            if (t > best) { best = t; bi = v; }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
-    __syncthreads();
-    best = sf[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w)
-        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
-    __syncthreads();
-
-    int choice = bi;
-    if (p.mode != TS_SAMPLE_GREEDY) {
-        float u;
-        if (p.mode == TS_SAMPLE_UNIFORMS) {
-            u = p.uniforms[(long)b * p.u_stride];
-        } else {
-            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
-            uint32_t r;
-            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                          (uint32_t)(seed >> 32), r);
-            u = (float)(r >> 8) * (1.0f / 16777216.0f);
-        }
-        float s = 0.f;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += det_expf(x[k] - best);
-        } else {
-            for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
-        }
-        sf[tid + 1] = s;
-        __syncthreads();
-        if (tid == 0) {
-            float c = 0.f;
-            sf[0] = 0.f;
-            for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }
-            s_thr = u * c;
-        }
-        __syncthreads();
-        const float thr = s_thr;
-        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
-        if (mine && v0 < p.V) {
-            float c = sf[tid];
-            int k = v1 - 1;
-            if (fast) {
-                bool found = false;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    c += det_expf(x[j] - best);
-                    if (!found && c > thr) { k = v0 + j; found = true; }
-                }
-            } else {
-                for (int v = v0; v < v1; ++v) {
-                    c += det_expf(lg[v] - best);
-                    if (c > thr) { k = v; break; }
-                }
-            }
-            si[0] = k;
-        } else if (mine) {
-            si[0] = p.V - 1;
-        }
-        __syncthreads();
-        choice = si[0];
-    }
-    if (tid == 0) {
-        p.tok32[(long)b * p.tok_stride] = choice;
-        p.codes[(long)b * p.code_stride] = choice;
-    }
-}
-
-// sample_lp_kernel with given rows: a forced workgroup is that kernel's teacher-forced path (the total S in the samplers' summation
-// structure, the logit picked up by the thread that owns the code) on a code read from the staging block, which it also writes out
-__global__ __launch_bounds__(256) void sample_lp_given_kernel(const SampleGivenParams gp) {
-    __shared__ float sf[256 + 1];
-    __shared__ int si[256];
-    __shared__ float s_thr;
-    const SampleParams &p = gp.c.s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
-    const bool forced = given_forced(p, gp, b);   // workgroup-uniform, ahead of every barrier
-
-    const int chunk = (p.V + 255) / 256;
-    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
-    const bool fast = p.V == 2048 && (reinterpret_cast<uintptr_t>(lg) & 15) == 0;
-    float x[8];
-    if (fast) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
-    }
-
-    if (p.logits_copy) {
-        float *dst = p.logits_copy + (long)b * p.copy_stride;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dst[v0 + k] = x[k];
-        } else {
-            for (int v = v0; v < v1; ++v) dst[v] = lg[v];
-        }
-    }
-
-    // ---- max / argmax; ties -> lowest index ----
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    if (fast) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (x[k] > best) { best = x[k]; bi = v0 + k; }
-    } else {
-        for (int v = v0; v < v1; ++v) {
-            const float t = lg[v];
-            if (t > best) { best = t; bi = v; }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
-    __syncthreads();
-    best = sf[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w)
-        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
-    __syncthreads();
-
-    // ---- the total, in every mode: sf[t] = sum of the chunks < t, sf[256] = S ----
-    float s = 0.f;
-    if (fast) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += det_expf(x[k] - best);
-    } else {
-        for (int v = v0; v < v1; ++v) s += det_expf(lg[v] - best);
-    }
-    sf[tid + 1] = s;
-    __syncthreads();
-    const bool draws = !forced && (p.mode == TS_SAMPLE_UNIFORMS || p.mode == TS_SAMPLE_PHILOX);
-    if (tid == 0) {
-        float u = 0.f;
-        if (draws && p.mode == TS_SAMPLE_UNIFORMS) {   // the uniform of a forced row is never read
-            u = p.uniforms[(long)b * p.u_stride];
-        } else if (draws) {
-            const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-            const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
-            uint32_t r;
-            philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                          (uint32_t)(seed >> 32), r);
-            u = (float)(r >> 8) * (1.0f / 16777216.0f);
-        }
-        float c = 0.f;
-        sf[0] = 0.f;
-        for (int t = 1; t <= 256; ++t) { c += sf[t]; sf[t] = c; }
-        s_thr = u * c;
-    }
-    __syncthreads();
-
-    long long code;   // 64 bits: a given code is compared, never truncated
-    if (forced) {
-        code = gp.given[(long)b * gp.given_stride];
-    } else if (!draws) {
-        code = bi;
-    } else {
-        const float thr = s_thr;
-        const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
-        if (mine && v0 < p.V) {
-            float c = sf[tid];
-            int k = v1 - 1;
-            if (fast) {
-                bool found = false;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    c += det_expf(x[j] - best);
-                    if (!found && c > thr) { k = v0 + j; found = true; }
-                }
-            } else {
-                for (int v = v0; v < v1; ++v) {
-                    c += det_expf(lg[v] - best);
-                    if (c > thr) { k = v; break; }
-                }
-            }
-            si[0] = k;
-        } else if (mine) {
-            si[0] = p.V - 1;
-        }
-        __syncthreads();
-        code = si[0];
-    }
-
-    float *out = gp.c.logprob + (long)b * gp.c.lp_stride;
-    if (code >= (long long)v0 && code < (long long)v1) {   // the owner of index `code`: exactly one thread, or none when it is out of range
-        float lc = 0.f;
-        if (fast) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if ((long long)(v0 + k) == code) lc = x[k];
-        } else {
-            for (int v = v0; v < v1; ++v)
-                if ((long long)v == code) lc = lg[v];
-        }
-        *out = logprob_value(lc - best, sf[256]);
-    }
-    if (tid == 0) {
-        if (code < 0 || code >= (long long)p.V) *out = __uint_as_float(0x7fc00000u);
-        p.tok32[(long)b * p.tok_stride] = given_token(code, p.V);
-        p.codes[(long)b * p.code_stride] = code;
-    }
-}
-
-// sample_ctl_kernel with given rows.  Without the log-probability output a forced workgroup leaves ahead of everything; with it, it runs
-// steps 1-4 and the sums of step 5 as its sibling does (the thread that owns the given code notes whether the filters kept it), then
-// writes d_c - log S for a kept code and log(0) for a code the filters removed: the code's weight in the distribution the row would have
-// been drawn from is 0.
-template <bool FAST, bool LP>
-__global__ __launch_bounds__(256) void sample_ctl_given_kernel(const SampleGivenParams gp) {
-    __shared__ float sf[256 + 1];
-    __shared__ int si[256];
-    __shared__ float s_thr;
-    __shared__ int s_last;
-    __shared__ uint32_t s_tie[4];
-    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
-    const SampleCtlParams &cp = gp.c;
-    const SampleParams &p = cp.s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *lg = p.logits + (long)b * (p.logit_stride ? p.logit_stride : (long)p.V);
-    const bool forced = given_forced(p, gp, b);   // workgroup-uniform, ahead of every barrier
-    const long long gcode = forced ? (long long)gp.given[(long)b * gp.given_stride] : -1;
-
-    const int chunk = (p.V + 255) / 256;
-    const int v0 = tid * chunk, v1 = min(v0 + chunk, p.V);
-    const int n = FAST ? 8 : max(v1 - v0, 0);
-    float x[8];
-    if constexpr (FAST) {
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(lg + v0), hi = *reinterpret_cast<const f32x4 *>(lg + v0 + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x[k] = lo[k]; x[4 + k] = hi[k]; }
-    }
-    auto logit = [&](int k) -> float {
-        if constexpr (FAST) return x[k];
-        else return lg[v0 + k];
-    };
-    if (p.logits_copy) {
-        float *dst = p.logits_copy + (long)b * p.copy_stride;
-#pragma unroll 8
-        for (int k = 0; k < n; ++k) dst[v0 + k] = logit(k);
-    }
-    if constexpr (!LP) {
-        if (forced) {
-            if (tid == 0) {
-                p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
-                p.codes[(long)b * p.code_stride] = gcode;
-            }
-            return;
-        }
-    }
-
-    const SampleCtl rec = cp.ctl[b];
-    CtlSel S;
-    S.need_k = rec.top_k >= 1 && rec.top_k < p.V;
-    S.need_p = rec.top_p < 1.0f;
-    const bool sel = S.need_k || S.need_p;
-    if (sel) {
-#pragma unroll
-        for (int i = 0; i < 7; ++i) hist[i][tid] = 0;
-    }
-
-    // ---- max / argmax as in sample_kernel; ties -> lowest index ----
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll 8
-    for (int k = 0; k < n; ++k) {
-        const float t = logit(k);
-        if (t > best) { best = t; bi = v0 + k; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { sf[wave] = best; si[wave] = bi; }
-    __syncthreads();
-    best = sf[0]; bi = si[0];
-    for (int w = 1; w < 4; ++w)
-        if (sf[w] > best || (sf[w] == best && si[w] < bi)) { best = sf[w]; bi = si[w]; }
-    __syncthreads();
-
-    // the uniform: the same source as sample_kernel; a forced row reads none
-    float u = 0.f;
-    if (forced) {
-    } else if (p.mode == TS_SAMPLE_UNIFORMS) {
-        u = p.uniforms[(long)b * p.u_stride];
-    } else {
-        const uint64_t seed = p.dyn ? p.dyn[0] : p.seed;
-        const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
-        uint32_t r;
-        philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                      (uint32_t)(seed >> 32), r);
-        u = (float)(r >> 8) * (1.0f / 16777216.0f);
-    }
-
-    const float inv_t = rec.inv_t;
-    auto weight = [&](int k) -> float { return ctl_weight(logit(k), best, inv_t); };
-
-    // ---- steps 2-4: the kept set ----
-    uint32_t key[8], q[8];
-    auto key_of = [&](int k) -> uint32_t {
-        if constexpr (FAST) return key[k];
-        else return ctl_key(lg[v0 + k]);
-    };
-    auto q_of = [&](int k) -> uint32_t {
-        if constexpr (FAST) return q[k];
-        else return ctl_quant(weight(k));
-    };
-    int jk0 = 0, jp0 = 0;
-    if (sel) {
-        if constexpr (FAST) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { key[k] = ctl_key(x[k]); q[k] = ctl_quant(weight(k)); }
-        }
-        auto fill = [&](ctl_u64 *h, int lv, uint32_t prefix) {
-#pragma unroll 8
-            for (int k = 0; k < n; ++k) {
-                const uint32_t ky = key_of(k);
-                if (lv == 0 || (ky >> (32 - 8 * lv)) == prefix)
-                    atomicAdd(&h[(ky >> (24 - 8 * lv)) & 255u], (1ull << CTL_CNT_SHIFT) | (ctl_u64)q_of(k));
-            }
-            __syncthreads();
-        };
-        fill(hist[0], 0, 0u);
-        ctl_u64 Qk;
-        if (S.need_k) {
-            uint32_t prefix = 0;
-            ctl_u64 acc = 0;
-            for (int lv = 0; lv < 4; ++lv) {
-                if (lv > 0) fill(hist[lv], lv, prefix);
-                prefix = (prefix << 8) | (uint32_t)(ctl_pick_bin(hist[lv], lane, false, (ctl_u64)rec.top_k, acc) & 255);
-            }
-            S.Kk = prefix;
-            S.ntie_k = rec.top_k - (int)(acc >> CTL_CNT_SHIFT);
-            Qk = (acc & CTL_MASS_MASK) + (ctl_u64)S.ntie_k * ctl_quant(ctl_weight(ctl_unkey(prefix), best, inv_t));
-        } else {
-            S.Kk = 0;
-            S.ntie_k = 0;
-            Qk = ctl_hist_total(hist[0], lane) & CTL_MASS_MASK;
-        }
-        S.Kp = 0; S.p_top = false; S.mgt_p = S.q_p = S.Tq = 0;
-        if (S.need_p) {
-            S.Tq = (ctl_u64)ceil((double)rec.top_p * (double)Qk);
-            uint32_t prefix = 0;
-            ctl_u64 acc = 0;
-            for (int lv = 0; lv < 4; ++lv) {
-                ctl_u64 *h = lv == 0 ? hist[0] : hist[3 + lv];
-                if (lv > 0) fill(h, lv, prefix);
-                prefix = (prefix << 8) | (uint32_t)(ctl_pick_bin(h, lane, true, S.Tq, acc) & 255);
-            }
-            S.Kp = prefix;
-            S.mgt_p = acc & CTL_MASS_MASK;
-            S.p_top = (acc >> CTL_CNT_SHIFT) == 0;
-            S.q_p = ctl_quant(ctl_weight(ctl_unkey(prefix), best, inv_t));
-        }
-        uint32_t c = 0;
-#pragma unroll 8
-        for (int k = 0; k < n; ++k) {
-            const uint32_t ky = key_of(k);
-            c += (S.need_k && ky == S.Kk ? 1u : 0u) + (S.need_p && ky == S.Kp ? 65536u : 0u);
-        }
-        uint32_t inc = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_tie[wave] = inc;
-        __syncthreads();
-        uint32_t ex = inc - c;
-        for (int w = 0; w < wave; ++w) ex += s_tie[w];
-        jk0 = (int)(ex & 0xffffu);
-        jp0 = (int)(ex >> 16);
-    }
-
-    // ---- step 5: the sums over w' = kept ? w : 0; the owner of a given code notes its logit and whether it was kept ----
-    float s = 0.f;
-    int hi = -1;
-    bool gkept = false;
-    float glc = 0.f;
-    {
-        int jk = jk0, jp = jp0;
-        unsigned char *kd = cp.kept ? cp.kept + (long)b * p.V : nullptr;
-#pragma unroll 8
-        for (int k = 0; k < n; ++k) {
-            const bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
-            if (kp) { s += weight(k); hi = v0 + k; }
-            if (kd) kd[v0 + k] = kp ? 1 : 0;
-            if constexpr (LP) {
-                if ((long long)(v0 + k) == gcode) { gkept = kp; glc = logit(k); }
-            }
-        }
-    }
-    sf[tid + 1] = s;
-    si[tid] = hi;
-    __syncthreads();
-    if (tid == 0) {
-        float c = 0.f;
-        int last = 0;
-        sf[0] = 0.f;
-        for (int t = 1; t <= 256; ++t) {
-            c += sf[t]; sf[t] = c;
-            if (si[t - 1] >= 0) last = si[t - 1];
-        }
-        s_thr = u * c;
-        s_last = last;
-    }
-    __syncthreads();
-    if constexpr (LP) {
-        if (forced) {   // workgroup-uniform: S = sf[256] is there, nothing is drawn
-            float *out = cp.logprob + (long)b * cp.lp_stride;
-            if (gcode >= (long long)v0 && gcode < (long long)v1)
-                *out = gkept ? logprob_value(ctl_arg(glc, best, inv_t), sf[256]) : (float)log(0.0);
-            if (tid == 0) {
-                if (gcode < 0 || gcode >= (long long)p.V) *out = __uint_as_float(0x7fc00000u);
-                p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
-                p.codes[(long)b * p.code_stride] = gcode;
-            }
-            return;
-        }
-    }
-    const float thr = s_thr;
-    const bool mine = (sf[tid] <= thr) && (thr < sf[tid + 1] || tid == 255);
-    const int last = s_last;
-    __syncthreads();
-    if (mine) {
-        int res = -1;
-        float c = sf[tid];
-        int jk = jk0, jp = jp0;
-#pragma unroll 8
-        for (int k = 0; k < n; ++k) {
-            if (!sel || ctl_keep(S, key_of(k), jk, jp)) {
-                c += weight(k);
-                if (res < 0 && c > thr) res = v0 + k;
-            }
-        }
-        if (res < 0) res = (thr < sf[tid + 1] && hi >= 0) ? hi : last;
-        si[0] = res;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int choice = si[0];
-        p.tok32[(long)b * p.tok_stride] = choice;
-        p.codes[(long)b * p.code_stride] = choice;
-    }
-    if constexpr (LP) {
-        const int choice = si[0];
-        if (choice >= v0 && choice < v1) {
-            float lc = 0.f;
-#pragma unroll 8
-            for (int k = 0; k < n; ++k)
-                if (v0 + k == choice) lc = logit(k);
-            cp.logprob[(long)b * cp.lp_stride] = logprob_value(ctl_arg(lc, best, inv_t), sf[256]);
-        }
-    }
 }
 
 hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {

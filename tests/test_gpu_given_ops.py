@@ -1,5 +1,6 @@
 """The samplers' given variants as an operator (`ts_op_sample_given`; `csrc/vq.hip`: sample_given_kernel, sample_lp_given_kernel,
-sample_ctl_given_kernel) against their siblings (`ts_op_sample_lp`) and the numpy restatement (`sampling.given_logprob`).
+sample_ctl_given_kernel — the `GIVEN` instantiations of `sample_plain_body` and `sample_ctl_body`) against their
+siblings (`ts_op_sample_lp`) and the numpy restatement (`sampling.given_logprob`).
 
 One launch of B = 5 rows, forced in the pattern [1, 0, 1, 0, 0]: an unforced row returns its sibling's index and log-probability BIT FOR
 BIT; a forced row returns its given code, the teacher-forced log-probability without a record and, with one, the restatement's value to

@@ -1,5 +1,6 @@
-"""The samplers' log-probability output as an operator (`ts_op_sample_lp`: `csrc/vq.hip::sample_lp_kernel` without a table,
-`sample_ctl_kernel<., true>` with one) and `ts_logprob_sums`, against the existing entries and the numpy restatement
+"""The samplers' log-probability output as an operator (`ts_op_sample_lp`; `csrc/vq.hip`: `sample_lp_kernel` without a table, the `LP`
+instantiation of `sample_plain_body`; `sample_ctl_kernel<., true>` with one, the `LP` instantiations of `sample_ctl_body`) and
+`ts_logprob_sums`, against the existing entries and the numpy restatement
 (`talkshow_amd/sampling.py::logprob`, `logprob_sums`).
 
 Codes equal the existing entries' codes EXACTLY.  A log-probability may differ from the restatement by one fp32 spacing and no more: S and

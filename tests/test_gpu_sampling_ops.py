@@ -1,7 +1,8 @@
-"""The sampler with per-clip controls as an operator (`ts_op_sample_ctl`, `csrc/vq.hip::sample_ctl_kernel`) against the sampler without
-controls, the numpy twin (`talkshow_amd/sampling.py`), the float64 definition of tests/test_sampling_host.py and the float64 truncated
-distribution.  Every comparison with the twin or the plain sampler is EQUALITY: a draw is a pure function of (logits row, record,
-uniform).  Operator launches carry B = 5 rows (the chi-square draws 4 096 per call, as `test_op_sample_philox_chi_square` does).
+"""The sampler with per-clip controls as an operator (`ts_op_sample_ctl`; `csrc/vq.hip`: `sample_ctl_kernel`, an entry of
+`sample_ctl_body`) against the sampler without controls (`sample_kernel`, an entry of `sample_plain_body`), the numpy twin
+(`talkshow_amd/sampling.py`), the float64 definition of tests/test_sampling_host.py and the float64 truncated distribution.
+Every comparison with the twin or the plain sampler is EQUALITY: a draw is a pure function of (logits row, record, uniform).  Operator
+launches carry B = 5 rows (the chi-square draws 4 096 per call, as `test_op_sample_philox_chi_square` does).
 Every test fails on a build without the feature: `ts_op_sample_ctl` does not exist there.
 """
 import numpy as np
