@@ -489,6 +489,52 @@ int ts_body_pixel_infer_mixed_poses(ts_convnet *audioenc, ts_pixelcnn *pix, ts_v
  * an index outside the codebook INSIDE a clip still gives NaNs); out_dev (B,4H,body_dim+hand_dim), rows at or beyond 4 (lens[b] / 4) = 0. */
 int ts_vqvae_decode_pair_masked(ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *lat_body_dev, const int64_t *lat_hand_dev,
                                 const int32_t *lens_dev, int B, int H, float *out_dev, void *stream);
+/* ---- kept positions: keep chosen positions of given codes, redraw the rest -----------------------------------------------------------------
+ * "given rows" keeps a prefix in TIME.  The code grid has a second axis: column 0 is the BODY codebook, column 1 the HAND codebook, and the
+ * chain predicts (r, 0) then (r, 1), each conditioned on the other part's past.  A pass with given rows may bring a mask `keep` beside the
+ * given block, in the block's layout: (B,H_max,2) uint8, in slot order (the order of the submitted, sorted clips).
+ * THE RULE.  The sampler launch of position (r, j) is FORCED for clip slot b iff 2 r + j < 2 G_b AND (keep == NULL or keep[b, r, j] != 0).
+ * Everything else in "given rows" stays word for word: a forced workgroup reads its code, writes it where a drawn code goes and draws
+ * nothing; an unforced one runs the arithmetic of the sampler it stands in for, operation for operation.  One rule therefore covers resume,
+ * tail redraw, per-part redraw ("keep this body motion, draw new hands"; N hand takes for one body take; keep the hands, redraw the body)
+ * and any mixture per clip, and the pass stays on its hipGraphs.  What follows from the rule:
+ *   - unkept codes are never read: a position below G_b with keep == 0 is PRODUCED, and its entry of the given block may hold anything
+ *     (values outside the vocabulary, -1);
+ *   - unkept uniforms ARE read: the uniform of an unkept position below G_b is read (without a mask no uniform below G_b is); the uniform
+ *     of a kept position still is not;
+ *   - Philox is unchanged: a code's position is its absolute (row, column); kept positions consume nothing, their numbers are skipped, not
+ *     shifted.  Handing back an earlier decode with ANY mask (same seed, clip index and record) therefore returns that decode bit for bit;
+ *   - log-probabilities are unchanged in kind: a kept position gets the log-probability of its code under the distribution it would have
+ *     been drawn from (talkshow_amd/sampling.py::given_logprob; -inf for a code the record removed), a produced position what a draw gets;
+ *   - the mask is read for rows r < G_b only; rows beyond may hold anything.  A byte is 0 or not 0.
+ * Forcing the HAND column while drawing the BODY column is a forced decode, not a posterior sample: the body draw at row r sees the hands
+ * of rows < r only, never the hand code of its own row or of later rows; the result is NOT a sample of p(body | hands).
+ * The entries: the _given / _poses entries with keep_dev appended before the stream.  keep_dev == NULL is exactly the existing entry (which
+ * calls these with NULL); keep_dev without the given block it selects from is an error.  In the _poses_keep entry the mask applies to the
+ * codes the encoders produce (rows r < P_b / 4).
+ * Graphs: bit 3 (value 8) of the sixth key field for "mask present".  A masked pass runs the masked form in every chunk, so its number of
+ * distinct keys is what a given pass has (at most 14 of the 16 chunk slots); a chunk's rows of the mask travel into a uint8 staging block of
+ * the work buffers ahead of its replay, exactly as its given codes do (chunks with rows below max G_b only; eager runs read the caller's
+ * mask).  A repeated masked pass captures nothing, whatever its mask; passes without a mask find the keys, graphs and launches they found
+ * before.  talkshow_amd/sampling.py::keep_forced restates the rule in numpy.
+ * Out of scope: the output head of a kept column still runs (a kept position costs what a produced one costs); poses remain the VQ decode
+ * of the returned codes; the streaming sessions are untouched. */
+int ts_pixelcnn_generate_mixed_keep(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                    const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                    const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                    const int32_t *given_rows_dev, const uint8_t *keep_dev, void *stream);
+int ts_body_pixel_infer_mixed_keep(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                   const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                   const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                   float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                   const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep_dev, void *stream);
+int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                         const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                         const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                         float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                         const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                         const uint8_t *keep_dev, void *stream);
 
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.
@@ -544,6 +590,14 @@ int ts_op_sample_lp(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode
 int ts_op_sample_given(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
                        int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
                        const int32_t *forced_host, const int64_t *given_dev, void *stream);
+/* The same launch with the DEVICE-side decision of "kept positions" exercised: ts_op_sample_lp's arguments without kept_dev, plus
+ * given_rows_host (B) int32 (G of every row, >= 0), keep_dev (B) uint8 or NULL, given_dev (B) int64 and the launch's `position`: row b is
+ * forced iff position < 2 given_rows_host[b] and (keep_dev == NULL or keep_dev[b] != 0).  given_dev is read for forced rows only, keep_dev
+ * for rows with position < 2 G only, uniforms_dev for unforced rows only.  (ts_op_sample_given takes a host `forced` flag, turns it into a
+ * row table and passes no mask: it does not reach the mask load.) */
+int ts_op_sample_keep(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                      int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
+                      const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

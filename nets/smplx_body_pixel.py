@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None, given_poses=None):
+                       logprobs=False, given=None, given_poses=None, given_keep=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -112,16 +112,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         (`generate_clips`, `ts_body_pixel_infer_mixed_given`).  None: nothing changes.
         given_poses: one (B,P,129) block or a list of B entries (None or (P_b,129)): the clips' first pose frames, encoded on the device into
         their first P_b // 4 code rows (`generate_clips`, `ts_body_pixel_infer_mixed_poses`).  None: nothing changes.
+        given_keep: which positions of the given rows are taken — None (all), "body", "hand", a (G_b,2) mask, a list of these or one (B,G,2)
+        block (`generate_clips`, `ts_body_pixel_infer_mixed_keep`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
-        if sampling is not None or logprobs or given is not None or given_poses is not None:
+        if sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None:
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
                                        _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
-                                       given_poses=given_poses)
+                                       given_poses=given_poses, given_keep=given_keep)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -219,7 +221,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
-                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None):
+                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -244,7 +246,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         rows, exactly as with `given=` set to `encode_clips`' codes of those frames.  The frames are in the wrapper's own pose layout: the
         129 c_index columns this method RETURNS (the VQ-VAEs' side; a caller who un-normalised or re-ordered its poses for display hands
         back the rows as they were before that).  A clip brings `given` or `given_poses`, never both (ValueError naming the clip); a pass may
-        hold both kinds.  1 <= P_b <= 3, P_b // 4 > H_b or a wrong width raises ValueError naming the clip before anything is launched."""
+        hold both kinds.  1 <= P_b <= 3, P_b // 4 > H_b or a wrong width raises ValueError naming the clip before anything is launched.
+        given_keep: WHICH positions of a clip's given rows are taken (talkshow_hip.h, "kept positions"; `_lib.given_keep_block`) — a list in
+        submission order with, per clip, None (all of them: the behaviour without the keyword), "body" (column 0, the body codebook, is
+        kept and the hands are drawn), "hand" (column 1 kept, the body drawn) or a (G_b,2) bool / 0-1 array ((P_b // 4, 2) for a clip that
+        brings poses: the mask applies to the codes the encoders produce); or one string or one (B,G,2) block for all clips.  Position
+        (r, j) is taken iff r < G_b and its mask entry is 1; every other position is produced as if nothing were given there: its given code
+        is never read (it may hold anything, so the vocabulary check covers kept positions only), it draws the Philox number of its absolute
+        (row, column) — "keep this body take, draw N hand takes" is N entries with N clip indices — and its log-probability is a draw's.
+        Handing back an earlier decode (same seed, index, record) with ANY mask returns that decode bit for bit.  Keeping the hands while
+        drawing the body is a forced decode, not a posterior sample: the body draw at row r sees the hands of rows < r only.  Poses are the
+        VQ decode of the returned codes.  A mask of the wrong shape, a non-0/1 array, an unknown string or an entry on a clip that brings
+        nothing raises ValueError naming the clip before anything is launched (`ts_body_pixel_infer_mixed_keep` / `_poses_keep`)."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -271,9 +284,11 @@ class TrainWrapper(TrainWrapperBaseClass):
         if sampling is not None:   # sorted slot k holds the record of submitted clip order[k]
             recs = _lib.sampling_records(sampling, B)
             ctl, n_ctl = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
-        gblock = gtable = None
+        gblock = gtable = kblock = None
+        if given_keep is not None:   # the mask of kept positions, in slot order like the blocks it selects from
+            kblock = _lib.given_keep_block(given_keep, _lib.given_counts(given, given_poses, B), [t // 4 for t in lens], order, who="generate_clips")
         if given is not None:      # sorted slot k holds the given rows of submitted clip order[k]; validated before anything is launched
-            gblock, gtable = _lib.given_block(given, [t // 4 for t in lens], self.generator.input_dim, order, who="generate_clips")
+            gblock, gtable = _lib.given_block(given, [t // 4 for t in lens], self.generator.input_dim, order, who="generate_clips", keep=kblock)
         pblock = ptable = None
         if given_poses is not None:
             _lib.given_kinds_check(given, given_poses, B, "generate_clips")
@@ -281,6 +296,8 @@ class TrainWrapper(TrainWrapperBaseClass):
                                                    width=self.each_dim[1] + self.each_dim[2])
             if int(ptable.max()) == 0:      # nothing given anywhere: the pass without the keyword
                 pblock = ptable = None
+        if gblock is None and pblock is None:
+            kblock = None
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -316,20 +333,29 @@ class TrainWrapper(TrainWrapperBaseClass):
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
         lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
         i32p = _lib.C.POINTER(_lib.C.c_int32)
+        kdev = None
+        if kblock is not None:
+            from talkshow_amd.modules import upload
+            kdev = upload(kblock, dev)
         if pblock is not None and gblock is None:
             from talkshow_amd.modules import upload
             pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]),
-                                                                   ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)), _lib.stream_ptr()))
-        elif pblock is not None:      # both kinds in one pass: the pose clips' codes join the code clips' in one block, on the device
-            gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), gtable.ctypes.data_as(i32p),
-                                                                   None, _lib.stream_ptr()))
+            pargs = (*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)))
+            if kdev is None:
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*pargs, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_keep(*pargs, _lib.dptr(kdev), _lib.stream_ptr()))
         elif gblock is not None:
-            from talkshow_amd.modules import upload
-            gdev = upload(gblock, dev)
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev),
-                                                                   gtable.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), None, _lib.stream_ptr()))
+            if pblock is not None:    # both kinds in one pass: the pose clips' codes join the code clips' in one block, on the device
+                gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
+            else:
+                from talkshow_amd.modules import upload
+                gdev = upload(gblock, dev)
+            gargs = (*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), gtable.ctypes.data_as(i32p), None)
+            if kdev is None:
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*gargs, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_keep(*gargs, _lib.dptr(kdev), _lib.stream_ptr()))
         elif lp is not None:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed_lp(*args, ctl, n_ctl, _lib.dptr(lp), _lib.stream_ptr()))
         elif ctl is None:
@@ -442,14 +468,15 @@ class TrainWrapper(TrainWrapperBaseClass):
         return self._score_pass(mfcc_list, ids, "score_motion_clips", make)
 
     def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
-                         given_poses=None):
+                         given_poses=None, given_keep=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
         pass's host table is `mixed_tables` arithmetic (lens_dev: its device copy, (B,) int32, if the caller has uploaded one).  No synchronisation.
         sampling_table: `_lib.sampling_table(...)` in ROW order (the caller sorted it with the rows), or None.
         given: `_lib.given_block(...)` in ROW order — (block, table), both numpy — or None.
-        given_poses: `_lib.given_pose_block(...)` in ROW order — (block, table) — or None; with `given` too, no clip is in both."""
+        given_poses: `_lib.given_pose_block(...)` in ROW order — (block, table) — or None; with `given` too, no clip is in both.
+        given_keep: `_lib.given_keep_block(...)` in ROW order — the (B, H_max, 2) uint8 mask of kept positions — or None."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -470,6 +497,11 @@ class TrainWrapper(TrainWrapperBaseClass):
         i32p = _lib.C.POINTER(_lib.C.c_int32)
         if given_poses is not None and int(given_poses[1].max()) == 0:
             given_poses = None
+        kdev = None
+        if given_keep is not None and (given is not None or given_poses is not None):
+            if given_keep.shape != (B, H_max, 2):
+                raise ValueError(f"infer_padded_wav: the mask of kept positions must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given_keep.shape}")
+            kdev = upload(given_keep, dev)
         if given_poses is not None:
             pblock, ptable = given_poses
             if int(pblock.shape[1]) // 4 > H_max:
@@ -477,21 +509,27 @@ class TrainWrapper(TrainWrapperBaseClass):
             ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
             if given is None:
                 pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]),
-                                                                       ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)), _lib.stream_ptr()))
+                pargs = (*args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)))
+                if kdev is None:
+                    _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*pargs, _lib.stream_ptr()))
+                else:
+                    _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_keep(*pargs, _lib.dptr(kdev), _lib.stream_ptr()))
             else:
                 if given[0].shape != (B, H_max, 2):
                     raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
                 gdev, gtable = self._stage_given(given[0], given[1], pblock, ptable, dev)
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, None, _lib.dptr(gdev), gtable.ctypes.data_as(i32p), None,
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_keep(*args, ctl, n_ctl, None, _lib.dptr(gdev), gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
                                                                        _lib.stream_ptr()))
         elif given is not None:
             gblock, gtable = given
             if gblock.shape != (B, H_max, 2):
                 raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {gblock.shape}")
             ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*args, ctl, n_ctl, None, _lib.dptr(upload(gblock, dev)),
-                                                                   gtable.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), None, _lib.stream_ptr()))
+            gargs = (*args, ctl, n_ctl, None, _lib.dptr(upload(gblock, dev)), gtable.ctypes.data_as(i32p), None)
+            if kdev is None:
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*gargs, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_keep(*gargs, _lib.dptr(kdev), _lib.stream_ptr()))
         elif sampling_table is None:
             _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
         else:
@@ -499,7 +537,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None, given_poses=None):
+                                sampling=None, given=None, given_poses=None, given_keep=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
@@ -507,7 +545,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         the SUBMITTED list (or `clip_indices[b]`).  sampling: one sampling record for all recordings or one per recording in submission
         order; the records follow the recordings through the sort by sample count.  given: as for `generate_clips`, one entry per recording
         in submission order (a recording's code rows: `frontend.mixed_tables(ns, sr)["code_rows"]`).  given_poses: as for `generate_clips`,
-        one entry per recording."""
+        one entry per recording.  given_keep: as for `generate_clips` — which positions of a recording's given rows are taken (None, "body",
+        "hand", a mask; one entry per recording, or one for all)."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -524,9 +563,12 @@ class TrainWrapper(TrainWrapperBaseClass):
             recs = _lib.sampling_records(sampling, B)
             table = _lib.sampling_table([recs[i] for i in order], B, self.generator.input_dim, mode)
         given_in = given
+        if given_keep is not None:
+            given_keep = _lib.given_keep_block(given_keep, _lib.given_counts(given, given_poses, B),
+                                               [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], order, who="generate_clips_from_wav")
         if given is not None:
             given = _lib.given_block(given, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], self.generator.input_dim, order,
-                                     who="generate_clips_from_wav")
+                                     who="generate_clips_from_wav", keep=given_keep)
         if given_poses is not None:
             _lib.given_kinds_check(given_in, given_poses, B, "generate_clips_from_wav")
             given_poses = _lib.given_pose_block(given_poses, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], order,
@@ -540,7 +582,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
         codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given,
-                                                    given_poses=given_poses)
+                                                    given_poses=given_poses, given_keep=given_keep)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,

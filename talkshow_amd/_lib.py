@@ -124,6 +124,14 @@ SIGNATURES = {
     "ts_op_vq_argmin_pair_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ts_debug_vq_argmin_pair_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "ts_op_sample_given": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
+    # kept positions: the _given / _poses entries with keep_dev ahead of the stream; the one-launch form with the device-side decision
+    "ts_pixelcnn_generate_mixed_keep": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
+                                             C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "ts_body_pixel_infer_mixed_keep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                            _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "ts_body_pixel_infer_mixed_poses_keep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
+                                                  _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "ts_op_sample_keep": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -346,13 +354,16 @@ def logprob_request(logprobs, shape, device=None):
     return logprobs
 
 
-def given_block(given, rows, V, order=None, who="given"):
+def given_block(given, rows, V, order=None, who="given", keep=None):
     """The `given=` keyword of the decode entries -> (block (B, max rows, 2) int64, table (B,) int32), both numpy, both in SLOT order: what
     `ts_body_pixel_infer_mixed_given` / `ts_pixelcnn_generate_mixed_given` take as given_dev (after an upload) and given_rows_host.
     given: a list in SUBMISSION order with None (nothing given: G = 0) or a (G_b, 2) integer array per clip, or one (B, G, 2) integer block;
     rows: every clip's own code rows H_b in submission order; V: the vocabulary; order: sorted slot k holds submitted clip order[k] (None:
     the submitted order).  Rows of the block at or beyond a clip's G_b are 0 (the pass never reads them).  ValueError naming the SUBMITTED
-    clip for a bad shape, a non-integer array, G_b > H_b, or a code outside [0, V).  Pure host code; a device tensor is read back."""
+    clip for a bad shape, a non-integer array, G_b > H_b, or a code outside [0, V).  Pure host code; a device tensor is read back.
+    keep: the pass's mask of kept positions (`given_keep_block`: (B, max rows, 2) uint8, slot order) or None.  With a mask the vocabulary
+    rule applies to KEPT positions only — an unkept code is never read by the pass and may hold anything — and unkept entries of the block
+    are 0."""
     B = len(rows)
     if hasattr(given, "detach"):
         given = given.detach().cpu().numpy()
@@ -381,12 +392,100 @@ def given_block(given, rows, V, order=None, who="given"):
             raise ValueError(f"{who}: given rows of clip {i} must be integers, got {g.dtype}")
         if g.shape[0] > int(rows[i]):
             raise ValueError(f"{who}: clip {i} brings {g.shape[0]} given rows but has {int(rows[i])} code rows of its own")
+        if keep is not None:       # what the pass reads of this clip: its kept positions
+            g = np.where(np.asarray(keep[k, :g.shape[0]]) != 0, g, np.zeros_like(g))
         if g.size and (int(g.min()) < 0 or int(g.max()) >= int(V)):
             bad = g[(g < 0) | (g >= int(V))]
             raise ValueError(f"{who}: given rows of clip {i} hold the code {int(bad.flat[0])}, outside [0, {int(V)})")
         block[k, :g.shape[0]] = g
         table[k] = g.shape[0]
     return block, table
+
+
+KEEP_PARTS = {"body": 0, "hand": 1}   # the code grid's columns: column 0 is the body codebook, column 1 the hand codebook
+
+
+def given_counts(given, given_poses, B):
+    """How many given code rows every SUBMITTED clip brings, for `given_keep_block`: G_b for an entry of `given=`, P_b // 4 for an entry of
+    `given_poses=`, None for a clip that brings nothing.  Lenient — a malformed entry counts as None; `given_block` / `given_pose_block`
+    are what refuse it."""
+    def per_clip(x, div):
+        if x is None:
+            return [None] * B
+        if not isinstance(x, (list, tuple)):
+            sh = tuple(getattr(x, "shape", ()))
+            return [int(sh[1]) // div if len(sh) == 3 else None] * B
+        out = [None] * B
+        for b, g in enumerate(x[:B]):
+            if g is None:
+                continue
+            sh = tuple(g.shape) if hasattr(g, "shape") else np.shape(g)
+            out[b] = int(sh[0]) // div if len(sh) >= 1 else None
+        return out
+    gc, pc = per_clip(given, 1), per_clip(given_poses, 4)
+    return [g if g is not None else p for g, p in zip(gc, pc)]
+
+
+def given_keep_block(given_keep, counts, rows, order=None, who="given_keep"):
+    """The `given_keep=` keyword of the decode entries -> the mask (B, max rows, 2) uint8 in SLOT order that the `_keep` entries take as
+    keep_dev (talkshow_hip.h, "kept positions": position (r, j) of a clip is TAKEN from its given rows iff r < G_b and the mask byte is 1,
+    and produced otherwise), or None for `given_keep=None` (every given position kept).
+    given_keep: one entry per clip in SUBMISSION order — None (keep all of the clip's given rows), "body" (column 0 kept, the hands
+    redrawn), "hand" (column 1 kept, the body redrawn) or a (G_b, 2) bool / 0-1 integer array — or one string or one (B, G, 2) block for
+    all clips (one string applies to the clips that bring rows).  counts: `given_counts(...)`, every clip's given rows in submission order
+    (None: the clip brings nothing); rows: every clip's own code rows H_b; order: sorted slot k holds submitted clip order[k].  Bytes at or
+    beyond a clip's G_b are 0 (the pass never reads them).  ValueError naming the SUBMITTED clip for a shape that does not match the clip's
+    given rows, an array that is neither bool nor 0 / 1 integers, an unknown string, or an entry on a clip that brings nothing.  Pure host
+    code; a device tensor is read back."""
+    if given_keep is None:
+        return None
+    B = len(rows)
+    if len(counts) != B:
+        raise ValueError(f"{who}: one given-row count per clip ({B}), got {len(counts)}")
+    for_all = isinstance(given_keep, str)
+    if for_all:
+        if given_keep not in KEEP_PARTS:
+            raise ValueError(f"{who}: given_keep is None, 'body', 'hand' or a (G, 2) mask, got {given_keep!r}")
+        if all(c is None for c in counts):
+            raise ValueError(f"{who}: given_keep={given_keep!r} selects from given rows, but clip 0 — like every clip — brings none")
+        given_keep = [given_keep if counts[b] is not None else None for b in range(B)]
+    if hasattr(given_keep, "detach"):
+        given_keep = given_keep.detach().cpu().numpy()
+    if isinstance(given_keep, np.ndarray):
+        if given_keep.ndim != 3 or given_keep.shape[0] != B or given_keep.shape[2] != 2:
+            raise ValueError(f"{who}: one mask for all clips must have shape (B={B}, G, 2), got {tuple(given_keep.shape)}")
+        given_keep = list(given_keep)
+    if not isinstance(given_keep, (list, tuple)) or len(given_keep) != B:
+        raise ValueError(f"{who}: given_keep takes one entry per clip ({B}) — None, 'body', 'hand' or a (G, 2) mask — one string, or one "
+                         f"(B, G, 2) block, got {type(given_keep).__name__}" + (f" of {len(given_keep)}" if isinstance(given_keep, (list, tuple)) else ""))
+    order = list(range(B)) if order is None else [int(i) for i in order]
+    if sorted(order) != list(range(B)):
+        raise ValueError(f"{who}: order must be a permutation of the {B} clips")
+    mask = np.zeros((B, max(int(h) for h in rows), 2), np.uint8)
+    for k, i in enumerate(order):
+        m, G = given_keep[i], counts[i]
+        if m is not None and G is None:
+            raise ValueError(f"{who}: given_keep of clip {i} selects from given rows, but the clip brings none (no given= / given_poses= entry)")
+        if G is None:
+            continue
+        G = min(int(G), mask.shape[1])      # more rows than the clip has: the given helper's error, not this one's
+        if m is None:
+            mask[k, :G] = 1
+        elif isinstance(m, str):
+            if m not in KEEP_PARTS:
+                raise ValueError(f"{who}: given_keep of clip {i} is None, 'body', 'hand' or a (G, 2) mask, got {m!r}")
+            mask[k, :G, KEEP_PARTS[m]] = 1
+        else:
+            if hasattr(m, "detach"):
+                m = m.detach().cpu().numpy()
+            m = np.asarray(m)
+            if m.shape != (int(counts[i]), 2):
+                raise ValueError(f"{who}: given_keep of clip {i} must have shape ({int(counts[i])}, 2), the clip's given rows, got {tuple(m.shape)}")
+            if m.dtype.kind not in "biu" or (m.dtype.kind != "b" and m.size and (int(m.min()) < 0 or int(m.max()) > 1)):
+                raise ValueError(f"{who}: given_keep of clip {i} must be bool or 0 / 1 integers, got {m.dtype}"
+                                 + ("" if m.dtype.kind not in "iu" else f" with the value {int(m[(m < 0) | (m > 1)].flat[0])}"))
+            mask[k, :G] = m[:G] != 0
+    return mask
 
 
 def given_pose_block(given_poses, rows, order=None, who="given_poses", width=129):

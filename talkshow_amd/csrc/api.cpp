@@ -242,20 +242,32 @@ int ts_body_pixel_infer_mixed_given(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                     float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                     void *stream) {
+    return ts_body_pixel_infer_mixed_keep(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                          ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, nullptr, stream);
+}
+
+// the given pass with a mask of kept positions (talkshow_hip.h, "kept positions"; keep (B, T_max / 4, 2) uint8); keep == NULL: exactly the
+// entry above
+int ts_body_pixel_infer_mixed_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                   const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                   uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                   float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
+                                   const uint8_t *keep, void *stream) {
     if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
         return 1;
+    if (keep && !given) return fail("ts_body_pixel_infer_mixed_keep: a mask of kept positions needs the given codes it selects from");
+    if (given) {   // a bad row table is refused before the first launch of the pass, too
+        if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
+        if (ts_given_rows_check(given_rows_host, lens_host, B) != 0) return 1;
+    }
     hipStream_t s = (hipStream_t)stream;
     const int H = (T_max / 2) / 2;
     const int aud_dim = convnet_hidden(ae);
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * aud_dim * sizeof(float)));
-    if (given) {   // a bad row table is refused before the first launch of the pass, too
-        if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
-        if (ts_given_rows_check(given_rows_host, lens_host, B) != 0) return 1;
-    }
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
-    TS_TRY(ts_pixelcnn_generate_mixed_given(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
-                                            n_ctl, logprob, given, given_rows_host, given_rows_dev, s));
+    TS_TRY(ts_pixelcnn_generate_mixed_keep(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
+                                           n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, s));
     for (int k = 0; k < 2; ++k) {
         TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
         TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),
@@ -287,6 +299,19 @@ int ts_body_pixel_infer_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                     float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                     const int32_t *pose_lens_dev, void *stream) {
+    return ts_body_pixel_infer_mixed_poses_keep(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                                poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, nullptr, stream);
+}
+
+// the same with a mask of kept positions over the codes the encoders produce (keep (B, T_max / 4, 2) uint8, rows r < P_b / 4 read); keep ==
+// NULL: exactly the entry above
+int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                         const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                         uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
+                                         int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
+                                         const int32_t *pose_lens_dev, const uint8_t *keep, void *stream) {
+    if (keep && !given_poses)
+        return fail("ts_body_pixel_infer_mixed_poses_keep: a mask of kept positions needs the given poses whose codes it selects from");
     if (!given_poses)
         return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
                                                poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
@@ -316,8 +341,8 @@ int ts_body_pixel_infer_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
     int64_t *given = static_cast<int64_t *>(w.given.p);
     // rows h < P_b / 4 of clip b: its codes; rows up to P_max / 4: -1; rows beyond stay as they are — the pass reads rows below G_b only
     TS_TRY(vq_encode_pair_masked(vb, vh, given_poses, vqvae_in_dim(vb) + vqvae_in_dim(vh), pose_lens_dev, B, P_max, given, H, nullptr, nullptr, 0, s));
-    return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                           ctl_host, n_ctl, logprob, given, G.data(), nullptr, stream);
+    return ts_body_pixel_infer_mixed_keep(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                          ctl_host, n_ctl, logprob, given, G.data(), nullptr, keep, stream);
 }
 
 int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const float *w, const float *bias, int Cout,

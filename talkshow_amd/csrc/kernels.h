@@ -470,6 +470,10 @@ struct SampleGivenParams {
     const int *rows;           // (slots,) G of every clip slot of the pass
     const int64_t *given;      // the given code of clip b at given[b * given_stride]; read by forced workgroups only
     long given_stride;
+    // "kept positions": the mask byte of clip b at keep[b * keep_stride], read by workgroups below 2 * rows[b] only; a byte of 0 makes the
+    // workgroup unforced.  nullptr: every given position is kept, and the kernels execute what they executed before the mask existed
+    const unsigned char *keep;
+    long keep_stride;
 };
 hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream);
 // logprob (B,H,2) rows at or beyond a clip's own H_b = lens[b] >> 2 become 0 (mixed passes; beside launch_mask_codes)

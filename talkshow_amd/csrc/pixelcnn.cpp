@@ -90,6 +90,7 @@ struct ts_pixelcnn {
         DevBuf lp_int;                     // runs with a log-probability output: what the captured samplers write, (B,rows,2) fp32 beside codes_int
         DevBuf given_tab, given_int;       // passes with given rows: G of every clip SLOT (int32, written in stream order ahead of the pass); the given codes of
                                            // ONE chunk, (B,rows,2) int64 beside codes_int (what the captured samplers read)
+        DevBuf keep_int;                   // passes with a mask of kept positions: the mask bytes of ONE chunk, (B,rows,2) uint8 beside given_int
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
@@ -97,7 +98,8 @@ struct ts_pixelcnn {
         // buffers are Bs clips apart whatever Br is, so the stride is part of what a captured graph is valid for (0: the slabs are B apart).
         // The sixth field is a bit set: bit 0 for a run whose samplers read ctl_tab (sample_ctl_kernel), bit 1 for a run whose samplers write
         // log-probabilities into lp_int, bit 2 for a pass with given rows (EVERY chunk of such a pass runs the given variants of the samplers,
-        // which read given_tab and given_int); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // which read given_tab and given_int), bit 3 for a given pass that brings a mask of kept positions (every chunk's samplers then also
+        // read keep_int; without the bit their mask pointer is null); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -249,6 +251,7 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->lp_int.ensure((size_t)cb * ch * 2 * sizeof(float)));
     TS_TRY(w->given_tab.ensure((size_t)cb * sizeof(int)));
     TS_TRY(w->given_int.ensure((size_t)cb * CHUNK_ROWS * 2 * sizeof(int64_t)));
+    TS_TRY(w->keep_int.ensure((size_t)cb * CHUNK_ROWS * 2));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -293,6 +296,9 @@ struct RunCfg {
     const int *given_rows = nullptr;
     const int64_t *given_src = nullptr, *given = nullptr;
     bool given_stage = false;
+    // "kept positions": keep_src the caller's (B,out_H,2) uint8 mask beside given_src or null (every given position kept); staged with the
+    // given codes; keep: set by run_rows, laid out like `given`
+    const unsigned char *keep_src = nullptr, *keep = nullptr;
     int slabB() const { return Bs > 0 ? Bs : B; }
     void audio_from(ts_pixelcnn::Work *wk) { aeh = wk->AEH.f(), aeh1 = wk->AEH1.f(), av1c = wk->AV1C.f(), av1p = wk->AV1P.f(); }
 };
@@ -651,6 +657,8 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         gp.rows = c.given_rows;
         gp.given = c.given + (size_t)ro * 2 + j;
         gp.given_stride = (long)sH * 2;
+        gp.keep = c.keep ? c.keep + (size_t)ro * 2 + j : nullptr;
+        gp.keep_stride = (long)sH * 2;
         TS_HIP(launch_sample_given(gp, s));
     } else if (c.ctl) {
         SampleCtlParams cp;
@@ -1024,8 +1032,8 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 // The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
-inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr) {
-    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0);
+inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr, const unsigned char *keep = nullptr) {
+    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0);
 }
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
@@ -1089,6 +1097,7 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
         c.logprob = logprob;
         c.uniforms = uniforms;
         c.given = c.given_src;
+        c.keep = c.keep_src;
         c.io_H = out_H;
         c.io_row0 = c.out_row0;
         return row_loop(s);
@@ -1097,6 +1106,10 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
     if (c.given_rows && c.given_stage && !capture_only)   // the chunk's rows of the given block, the way the uniforms travel
         TS_HIP(hipMemcpy2DAsync(w->given_int.p, (size_t)c.H * 2 * sizeof(int64_t), c.given_src + (size_t)c.out_row0 * 2,
                                 (size_t)out_H * 2 * sizeof(int64_t), (size_t)c.H * 2 * sizeof(int64_t), c.B, hipMemcpyDeviceToDevice, s));
+    c.keep = c.keep_src ? static_cast<const unsigned char *>(w->keep_int.p) : nullptr;
+    if (c.given_rows && c.keep_src && c.given_stage && !capture_only)   // and the same rows of the mask
+        TS_HIP(hipMemcpy2DAsync(w->keep_int.p, (size_t)c.H * 2, c.keep_src + (size_t)c.out_row0 * 2, (size_t)out_H * 2, (size_t)c.H * 2, c.B,
+                                hipMemcpyDeviceToDevice, s));
     c.codes = static_cast<int64_t *>(w->codes_int.p);
     c.logprob = logprob ? w->lp_int.f() : nullptr;
     c.uniforms = c.mode == TS_SAMPLE_UNIFORMS ? w->unif_int.f() : nullptr;
@@ -1208,7 +1221,7 @@ constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
               uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, const int64_t *given, int given_max,
-              hipStream_t s) {
+              const unsigned char *keep, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1226,6 +1239,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
         if (given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
             c.given_rows = w->given_tab.i();
             c.given_src = given;
+            c.keep_src = keep;   // a masked pass runs the masked form in every chunk, too
             c.given_stage = r0 < given_max;
         }
         struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
@@ -1235,7 +1249,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows)), uniforms, codes, logprob, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1382,6 +1396,66 @@ int ts_op_sample_given(ts_ctx *ctx, const float *logits, int B, int V, int mode,
     return 0;
 }
 
+// Host only: what ts_op_sample_keep refuses before it touches the device
+static int op_sample_keep_check(const void *ctx, const void *logits, int B, int V, int mode, const void *uniforms, uint32_t position, const void *idx,
+                            const int32_t *given_rows_host, const void *given) {
+    const char *who = "ts_op_sample_keep";
+    if (!ctx || !logits || !idx || !given_rows_host || !given) return fail(std::string(who) + ": null argument");
+    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
+    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
+    if (position > 0x7ffffff0u) return fail(std::string(who) + ": position too large for a row table");
+    for (int b = 0; b < B; ++b)
+        if (given_rows_host[b] < 0) return fail(std::string(who) + ": given rows of row " + std::to_string(b) + " are negative");
+    return 0;
+}
+
+// one launch of the samplers' given variants on given logits with the DEVICE-side decision exercised (kernel-level tests call it): row b is
+// forced iff position < 2 given_rows_host[b] and (keep == NULL or keep[b] != 0)
+int ts_op_sample_keep(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                      uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
+                      const uint8_t *keep, const int64_t *given, void *stream) {
+    const char *who = "ts_op_sample_keep";
+    TS_TRY(op_sample_keep_check(ctx, logits, B, V, mode, uniforms, position, idx, given_rows_host, given));
+    std::vector<SampleCtl> tab;
+    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, who, tab));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tok, dtab, drows;
+    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
+    TS_TRY(drows.ensure((size_t)B * sizeof(int)));
+    TS_HIP(launch_put_words(drows.i(), given_rows_host, B, s));
+    if (ctl_host) {
+        TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
+        TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
+    }
+    SampleGivenParams gp;
+    std::memset(&gp, 0, sizeof(gp));
+    gp.c.s.logits = logits;
+    gp.c.s.B = B;
+    gp.c.s.V = V;
+    gp.c.s.mode = mode;
+    gp.c.s.uniforms = uniforms;
+    gp.c.s.u_stride = 1;
+    gp.c.s.seed = seed;
+    gp.c.s.clip_index0 = clip_index0;
+    gp.c.s.position = position;
+    gp.c.s.tok32 = tok.i();
+    gp.c.s.tok_stride = 1;
+    gp.c.s.codes = idx;
+    gp.c.s.code_stride = 1;
+    gp.c.ctl = ctl_host ? static_cast<const SampleCtl *>(dtab.p) : nullptr;
+    gp.c.logprob = logprob;
+    gp.c.lp_stride = 1;
+    gp.rows = drows.i();
+    gp.given = given;
+    gp.given_stride = 1;
+    gp.keep = keep;
+    gp.keep_stride = 1;
+    TS_HIP(launch_sample_given(gp, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
@@ -1413,6 +1487,16 @@ int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const
                                      int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                      int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                      const int32_t *given_rows_host, const int32_t *given_rows_dev, void *stream) {
+    return ts_pixelcnn_generate_mixed_keep(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                           logprob, given, given_rows_host, given_rows_dev, nullptr, stream);
+}
+
+// the given pass with a mask of kept positions beside the given block (talkshow_hip.h, "kept positions"): position (r, j) of clip b is taken
+// iff r < G_b and keep[b, r, j] != 0, every other position is produced.  keep == NULL: the _given entry, launch for launch
+int ts_pixelcnn_generate_mixed_keep(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                    const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, void *stream) {
     (void)given_rows_dev;   // the table travels as kernel arguments from the host copy (see talkshow_hip.h)
     if (!p || !label || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
@@ -1429,6 +1513,7 @@ int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const
     std::vector<SampleCtl> tab;
     if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
     int given_max = 0;
+    if (keep && !given) return fail("ts_pixelcnn_generate_mixed_keep: a mask of kept positions needs the given codes it selects from");
     if (given) {
         if (!given_rows_host) return fail("ts_pixelcnn_generate_mixed_given: given codes need their row table");
         TS_TRY(ts_given_rows_check(given_rows_host, lens_host, B));
@@ -1452,7 +1537,7 @@ int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const
     }
     const bool graph = p->use_graph && !ctx->prof.on;
     TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
-                     logprob, given, given_max, s));
+                     logprob, given, given_max, keep, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0

@@ -891,13 +891,18 @@ __device__ __forceinline__ int sample_crossing(bool fast, const float *lg, const
     return si[0];
 }
 // given rows (talkshow_hip.h): clip b of a pass brings G_b = rows[b] code rows that are TAKEN, not drawn.  A workgroup is FORCED iff its
-// absolute position 2 row + column — the Philox counter word, the dynamic base word of a replayed graph included — is below 2 G_b: a
-// workgroup-uniform decision from kernel arguments and two uniform loads, taken before any barrier.  A given code is compared, never used
-// as an address; outside [0, V) it leaves -1 in tok32 (the chain's gathers read a row of zeros for a negative index).
-__device__ __forceinline__ bool given_forced(const SampleParams &p, const int *rows, int b) {
+// absolute position 2 row + column — the Philox counter word, the dynamic base word of a replayed graph included — is below 2 G_b and
+// ("kept positions") the pass brings no mask or the mask's byte of this (clip, row, column) is not 0: a workgroup-uniform decision from
+// kernel arguments, two uniform loads and, with a mask, one byte every lane loads from the same address (made scalar by readfirstlane, so
+// the branches on it stay scalar branches), taken before any barrier.  The byte is read below 2 G_b only; keep == nullptr executes the
+// loads and compares there were before the mask existed.  A given code is compared, never used as an address; outside [0, V) it leaves
+// -1 in tok32 (the chain's gathers read a row of zeros for a negative index).
+__device__ __forceinline__ bool given_forced(const SampleParams &p, const int *rows, const unsigned char *keep, long keep_stride, int b) {
     const uint32_t pos = p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u);
     const int G = rows[b];
-    return G > 0 && (uint64_t)pos < 2ull * (uint64_t)G;
+    if (!(G > 0 && (uint64_t)pos < 2ull * (uint64_t)G)) return false;
+    if (!keep) return true;
+    return __builtin_amdgcn_readfirstlane((int)keep[(long)b * keep_stride]) != 0;
 }
 __device__ __forceinline__ int given_token(long long code, int V) { return code >= 0 && code < (long long)V ? (int)code : -1; }
 // the log-probability (talkshow_hip.h, "log-probabilities") of the row's code, stored by the ONE thread that owns the code's index: d = the
@@ -924,11 +929,12 @@ __device__ __forceinline__ void sample_store_unowned(float *out, long long code,
 // ---------------------------------------------------------------------------------------------------------------
 template <bool LP, bool GIVEN>
 __device__ __forceinline__ void sample_plain_body(const SampleParams &p, float *logprob, long lp_stride, const int *rows, const int64_t *given,
-                                                  long given_stride, float *sf, int *si, float &s_thr) {
+                                                  long given_stride, const unsigned char *keep, long keep_stride, float *sf, int *si,
+                                                  float &s_thr) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const float *lg = sample_row(p, b);
     bool forced = false;   // workgroup-uniform, ahead of every barrier
-    if constexpr (GIVEN && LP) forced = given_forced(p, rows, b);
+    if constexpr (GIVEN && LP) forced = given_forced(p, rows, keep, keep_stride, b);
 
     // Every thread owns `chunk` consecutive logits [v0, v1); for the production vocabulary (V = 2048: chunk = 8) they stay in registers
     const int chunk = (p.V + 255) / 256;
@@ -941,7 +947,7 @@ __device__ __forceinline__ void sample_plain_body(const SampleParams &p, float *
     sample_copy_row(p, b, fast, lg, x, v0, v1);
 
     if constexpr (!LP && GIVEN) {
-        if (given_forced(p, rows, b)) {
+        if (given_forced(p, rows, keep, keep_stride, b)) {
             if (tid == 0) {
                 const long long code = given[(long)b * given_stride];
                 p.tok32[(long)b * p.tok_stride] = given_token(code, p.V);
@@ -1027,25 +1033,26 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleParams p) {
     __shared__ float sf[256 + 1];
     __shared__ int si[256];
     __shared__ float s_thr;
-    sample_plain_body<false, false>(p, nullptr, 0, nullptr, nullptr, 0, sf, si, s_thr);
+    sample_plain_body<false, false>(p, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr);
 }
 __global__ __launch_bounds__(256) void sample_lp_kernel(const SampleLpParams lp) {
     __shared__ float sf[256 + 1];
     __shared__ int si[256];
     __shared__ float s_thr;
-    sample_plain_body<true, false>(lp.s, lp.logprob, lp.lp_stride, nullptr, nullptr, 0, sf, si, s_thr);
+    sample_plain_body<true, false>(lp.s, lp.logprob, lp.lp_stride, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr);
 }
 __global__ __launch_bounds__(256) void sample_given_kernel(const SampleGivenParams gp) {
     __shared__ float sf[256 + 1];
     __shared__ int si[256];
     __shared__ float s_thr;
-    sample_plain_body<false, true>(gp.c.s, nullptr, 0, gp.rows, gp.given, gp.given_stride, sf, si, s_thr);
+    sample_plain_body<false, true>(gp.c.s, nullptr, 0, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr);
 }
 __global__ __launch_bounds__(256) void sample_lp_given_kernel(const SampleGivenParams gp) {
     __shared__ float sf[256 + 1];
     __shared__ int si[256];
     __shared__ float s_thr;
-    sample_plain_body<true, true>(gp.c.s, gp.c.logprob, gp.c.lp_stride, gp.rows, gp.given, gp.given_stride, sf, si, s_thr);
+    sample_plain_body<true, true>(gp.c.s, gp.c.logprob, gp.c.lp_stride, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si,
+                                  s_thr);
 }
 
 hipError_t launch_sample(const SampleParams &p, hipStream_t stream) {
@@ -1221,15 +1228,16 @@ __device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) 
 // Inlined into its eight __global__ entries; DESIGN.md §5 ("One body per sampler family") records what was compared against the two
 // separate kernel templates it replaces.
 template <bool FAST, bool LP, bool GIVEN>
-__device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride, float *sf,
-                                                int *si, float &s_thr, int &s_last, uint32_t *s_tie, ctl_u64 (*hist)[256]) {
+__device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride,
+                                                const unsigned char *keep, long keep_stride, float *sf, int *si, float &s_thr, int &s_last,
+                                                uint32_t *s_tie, ctl_u64 (*hist)[256]) {
     const SampleParams &p = cp.s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *lg = sample_row(p, b);
     bool forced = false;       // workgroup-uniform, ahead of every barrier
     long long gcode = -1;
     if constexpr (GIVEN) {
-        forced = given_forced(p, rows, b);
+        forced = given_forced(p, rows, keep, keep_stride, b);
         gcode = forced ? (long long)given[(long)b * given_stride] : -1;
     }
 
@@ -1442,7 +1450,7 @@ __global__ __launch_bounds__(256) void sample_ctl_kernel(const SampleCtlParams c
     __shared__ int s_last;
     __shared__ uint32_t s_tie[4];
     __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];   // levels 0-3 of the top-k descent (level 0 shared), 1-3 of the top-p descent
-    sample_ctl_body<FAST, LP, false>(cp, nullptr, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist);
+    sample_ctl_body<FAST, LP, false>(cp, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist);
 }
 template <bool FAST, bool LP>
 __global__ __launch_bounds__(256) void sample_ctl_given_kernel(const SampleGivenParams gp) {
@@ -1452,7 +1460,7 @@ __global__ __launch_bounds__(256) void sample_ctl_given_kernel(const SampleGiven
     __shared__ int s_last;
     __shared__ uint32_t s_tie[4];
     __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
-    sample_ctl_body<FAST, LP, true>(gp.c, gp.rows, gp.given, gp.given_stride, sf, si, s_thr, s_last, s_tie, hist);
+    sample_ctl_body<FAST, LP, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie, hist);
 }
 
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {

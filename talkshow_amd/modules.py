@@ -341,7 +341,7 @@ class GatedPixelCNN(NativeModule):
         (_lib.load().ts_pixelcnn_destroy if self.bh_model else _lib.load().ts_pixelcnn_v_destroy)(h)
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
-            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None):
+            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None, given_keep=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
@@ -354,7 +354,16 @@ class GatedPixelCNN(NativeModule):
         clip's whole audio).  The codes returned hold the given rows followed by the produced ones; with logprobs, a given row gets the
         log-probability of its code under the distribution it would have been drawn from (`sampling.given_logprob`).  A code outside
         [0, input_dim), a bad shape or G_b > H raises ValueError naming the clip before any device work.  Not with want_logits, pre_codes or
-        TS_TEACHER_FORCED.  None (the default): no return value and no launch changes."""
+        TS_TEACHER_FORCED.  None (the default): no return value and no launch changes.
+        given_keep: with `given`, WHICH of the given positions are taken (`_lib.given_keep_block`; talkshow_hip.h, "kept positions"): None
+        (all: the behaviour without the keyword), "body" (column 0 kept, the hand column drawn), "hand" (column 1 kept, the body column
+        drawn), a (G_b,2) bool / 0-1 array, one of these per clip in a list, or one (B,G,2) block.  An unkept position is produced as if
+        nothing were given there — its given code is not read and may hold anything — and draws the number of its absolute (row, column), so
+        handing back an earlier decode with any mask returns that decode.  Keeping hands while drawing the body is a forced decode, not a
+        posterior sample (the body draw at row r sees hands of rows < r only).  ValueError naming the clip for a bad mask or a mask on a
+        clip that brings nothing; `ts_pixelcnn_generate_mixed_keep`."""
+        if given_keep is not None and not self.bh_model:
+            raise NotImplementedError("kept positions exist for the bh_model=True chain (ts_pixelcnn_generate_mixed_keep), not for the single-stack form")
         if given is not None:
             if not self.bh_model:
                 raise NotImplementedError("given rows exist for the bh_model=True chain (ts_pixelcnn_generate_mixed_given), not for the single-stack form")
@@ -382,8 +391,11 @@ class GatedPixelCNN(NativeModule):
         ctl, n_ctl = None, 0
         if sampling is not None:   # validated (ValueError names the clip) before any device work
             ctl, n_ctl = _lib.sampling_table(sampling, B, self.input_dim, mode)
+        kblock = None
+        if given_keep is not None:   # ValueError before any device work, too (without given rows there is nothing to select from)
+            kblock = _lib.given_keep_block(given_keep, _lib.given_counts(given, None, B), [H] * B, who="run")
         if given is not None:
-            block, table = _lib.given_block(given, [H] * B, self.input_dim, who="run")   # ValueError before any device work
+            block, table = _lib.given_block(given, [H] * B, self.input_dim, who="run", keep=kblock)   # ValueError before any device work
         if self.bh_model and aud_rows is None:
             aud_rows = torch.zeros((B, H, self.aud_dim), dtype=torch.float32, device=dev)
         label = _index_tensor(label, self.n_classes, "class label", dev)
@@ -420,10 +432,14 @@ class GatedPixelCNN(NativeModule):
             clip_index = upload(np.arange(B, dtype=np.int64) + int(clip_index0), dev)
             if isinstance(lp, str):
                 lp = torch.empty((B, H, 2), dtype=torch.float32, device=dev)
-            _lib.check(_lib.load().ts_pixelcnn_generate_mixed_given(
-                self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
-                _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), ctl, n_ctl, _lib.dptr(lp),
-                _lib.dptr(block_dev), table.ctypes.data_as(i32p), None, _lib.stream_ptr()))
+            gargs = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
+                     _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), ctl, n_ctl, _lib.dptr(lp),
+                     _lib.dptr(block_dev), table.ctypes.data_as(i32p), None)
+            if kblock is None:
+                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_given(*gargs, _lib.stream_ptr()))
+            else:
+                keep_dev = upload(kblock, dev)
+                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_keep(*gargs, _lib.dptr(keep_dev), _lib.stream_ptr()))
             return (codes, None) if lp is None else (codes, None, lp)
         args = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0)

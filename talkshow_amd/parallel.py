@@ -140,7 +140,7 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
 
 
 def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None,
-                     given=None, given_poses=None):
+                     given=None, given_poses=None, given_keep=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -158,7 +158,9 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     given: one entry per recording in submission order, None or the (G_b, 2) code rows the body decode of that recording starts from
     (`TrainWrapper.generate_clips`; the body branch then runs `ts_body_pixel_infer_mixed_given`); they follow the recordings through the sort.
     given_poses: the same from motion — None or the (P_b, 129) pose frames of that recording's head, encoded on the device
-    (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_poses`).  A recording brings one kind."""
+    (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_poses`).  A recording brings one kind.
+    given_keep: which positions of a recording's given rows are taken — None (all), "body" (keep the body column, draw new hands), "hand",
+    or a (G_b, 2) mask, per recording or one for all (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_keep`)."""
     import ctypes as C
 
     import numpy as np
@@ -193,13 +195,15 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if sampling is not None:   # validated before the first launch; sorted slot k holds the record of submitted recording order[k]
         recs = _lib.sampling_records(sampling, B)
         sampling = _lib.sampling_table([recs[i] for i in order], B, body.generator.input_dim, mode)
-    if given is not None or given_poses is not None:      # validated before the first launch, too: rows_sub[i] = code rows of submitted recording i
+    if given_keep is not None or given is not None or given_poses is not None:      # validated before the first launch, too: rows_sub[i] = code rows of submitted recording i
         rows_sub = [0] * B
         for k, i in enumerate(order):
             rows_sub[i] = int(tab["mfcc_rows"][k]) // 4
         _lib.given_kinds_check(given, given_poses, B, "whole_body_clips")
+        if given_keep is not None:
+            given_keep = _lib.given_keep_block(given_keep, _lib.given_counts(given, given_poses, B), rows_sub, order, who="whole_body_clips")
         if given is not None:
-            given = _lib.given_block(given, rows_sub, body.generator.input_dim, order, who="whole_body_clips")
+            given = _lib.given_block(given, rows_sub, body.generator.input_dim, order, who="whole_body_clips", keep=given_keep)
         if given_poses is not None:
             given_poses = _lib.given_pose_block(given_poses, rows_sub, order, who="whole_body_clips", width=body.each_dim[1] + body.each_dim[2])
     dev = body.generator._dev()
@@ -218,7 +222,7 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
         side.wait_stream(cur)
     with torch.cuda.stream(side):
         _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling,
-                                               given=given, given_poses=given_poses)
+                                               given=given, given_poses=given_poses, given_keep=given_keep)
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

@@ -177,6 +177,19 @@ def given_logprob(row, code, record=None):
     return logprob(row, code, record)
 
 
+def keep_forced(G, keep, r, j):
+    """The rule of "kept positions" (include/talkshow_hip.h) for one sampler launch: G (B,) given rows per clip slot, keep (B,H,2) mask of
+    kept positions or None, (r, j) the launch's row and column -> (B,) bool: clip b is FORCED at (r, j) iff 2 r + j < 2 G_b and (keep is None
+    or keep[b, r, j] != 0).  The mask is read below G_b only.  `sample_given` takes the result as its per-row `forced`."""
+    G = np.asarray(G, np.int64).reshape(-1)
+    pos = 2 * int(r) + int(j)
+    out = np.zeros(G.size, bool)
+    for b in range(G.size):
+        if pos < 2 * int(G[b]):
+            out[b] = True if keep is None else bool(keep[b][int(r)][int(j)] != 0)
+    return out
+
+
 def sample_given(logits, u, forced, given, records=None, greedy=False):
     """One launch of the samplers' given variants, restated: logits (B,V), u (B,) uniforms (those of forced rows are not read), forced (B,)
     flags, given (B,) codes (those of unforced rows are not read), records = None, one record or B -> (idx (B,) int64, logprob (B,)
