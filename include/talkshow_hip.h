@@ -535,6 +535,68 @@ int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *audioenc, ts_pixelcnn *pix,
                                          float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
                                          const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
                                          const uint8_t *keep_dev, void *stream);
+/* ---- speaker style: blended and time-varying speakers per clip ------------------------------------------------------------------------------
+ * The speaker reaches the model in exactly one way: a vector h_l of 2D floats per layer, added pointwise to the pre-gate sums of every
+ * position (gated_pixelcnn_v2.py:65, `h[:, :, None, None]`); with integer ids it is row label[b] of class_cond_embedding_l.  A pass may
+ * bring float WEIGHTS in place of the ids.  A clip's style is a row of NC = n_classes float32 weights: one row for the whole clip, or one
+ * row per CODE row (a code row is 4 pose frames).
+ * THE RULE.  The class-conditioning vector of layer l at code row r of clip b, element k, with E_l the layer's (NC, 2D) table:
+ *     acc = nothing
+ *     for c = 0 .. NC-1 ascending:
+ *         if w[b,r,c] != 0:  t = w[b,r,c] * E_l[c,k]            (rounded to fp32)
+ *                            acc = t if acc is nothing else acc + t   (rounded to fp32)
+ *     h_l[b,r,k] = acc, or +0.0 if every weight is 0
+ * Product and sum are rounded separately (__fmul_rn / __fadd_rn: no FMA contraction).  A zero weight (+0.0 or -0.0) contributes nothing
+ * and its table row is not read.  Weights are any FINITE floats: there is no non-negativity rule and no sum-to-one rule, because
+ * extrapolation (1.5 and -0.5) is a use.  What follows from the rule:
+ *   - a one-hot row gives E_l[c] bit for bit, a -0.0 entry included: a pass whose clips all bring one-hot rows returns what the integer
+ *     ids return;
+ *   - numpy.float32 arithmetic reproduces the rule exactly (talkshow_amd/sampling.py::style_rows);
+ *   - a blend is an INTERPOLATION OF THE CONDITIONING VECTORS.  It is not a mixture of the speakers' distributions: 0.5 / 0.5 is a virtual
+ *     fifth speaker whose vector lies between two trained ones, not a coin flip between two speakers.
+ * The entries: the most general sibling of each family plus `const float *style_dev, int style_rows` ahead of the stream.  style_dev is
+ * (B, style_rows, NC) float32 in slot order (the order of the submitted, sorted clips); style_rows is 1 (one row per clip) or H_max (one
+ * row per code row; rows at or beyond a clip's own H_b are not used — a clip carried to a chunk's end runs under its last own row).  With
+ * style_dev set, label_dev / ids_dev is not read and may be NULL.  style_dev == NULL: the sibling entry, launch for launch.  The weights
+ * are NOT validated on the device (a NaN weight gives NaN logits); ts_style_check is the host-side rule.
+ * style_rows == 1: the work buffer that held the gathered rows is filled by style_rows_kernel instead of the gather; keys, graphs and
+ * chain launches are the same (the buffer's content is in no key), and a warm host captures nothing.
+ * style_rows == H_max: the conditioning rows of ONE chunk (8 code rows) live in a staging buffer [NL][8][B][2D] fp32 of the work set
+ * (allocated by the first such pass; 4 NL 8 B 2D bytes), filled by style_rows_kernel ahead of every chunk's replay — launched eagerly on
+ * the stream like the staging of a chunk's uniforms and given codes; it is the only launch that reads the caller's block, so no caller
+ * pointer enters a captured graph — and every gate launch of code row r reads row r's slab.  Graphs: bit 4 (value 16) of the sixth key
+ * field.  Such a pass runs the staged form in every chunk, so its number of distinct keys is what the pass without tracks has (at most
+ * 14 of the 16 chunk slots); a repeated tracked pass captures nothing, whatever its weights; passes without tracks find the keys, graphs
+ * and launches they found before.
+ * The style is orthogonal to sampling records, log-probabilities, given rows / poses, kept positions, clip indices and the draw modes.
+ * Forced rows run under the style too (it shapes the row cache): handing back the head of an earlier decode WITH THE SAME STYLE returns
+ * that decode bit for bit.
+ * Out of scope: the streaming sessions, ts_body_pixel_infer, the face path, the single-stack form, weights per layer. */
+int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                     const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                     const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                     float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                     const int32_t *given_rows_dev, const uint8_t *keep_dev, const float *style_dev, int style_rows,
+                                     void *stream);
+int ts_body_pixel_infer_mixed_style(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                    const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                    const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                    float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                    const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep_dev,
+                                    const float *style_dev, int style_rows, void *stream);
+int ts_body_pixel_infer_mixed_poses_style(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                          const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                          const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                          float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                          const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                          const uint8_t *keep_dev, const float *style_dev, int style_rows, void *stream);
+/* Host only: every one of the n weights of a style block (rows of NC) is finite; the error names the first bad index.  Python calls it
+ * before anything is launched. */
+int ts_style_check(const float *w_host, long n, int NC);
+/* style_rows_kernel on its own (kernel-level tests): tables_dev (NL,NC,W) float32, weights_dev (M,NC) -> out_dev (NL,M,W), row m under
+ * weight row m, by THE RULE above.  W is a positive multiple of 4; the three blocks are 16-byte aligned.  Synchronises. */
+int ts_op_style_rows(ts_ctx *ctx, const float *tables_dev, int NL, int NC, int W, const float *weights_dev, int M, float *out_dev,
+                     void *stream);
 
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.

@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None, given_poses=None, given_keep=None):
+                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -114,16 +114,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         their first P_b // 4 code rows (`generate_clips`, `ts_body_pixel_infer_mixed_poses`).  None: nothing changes.
         given_keep: which positions of the given rows are taken — None (all), "body", "hand", a (G_b,2) mask, a list of these or one (B,G,2)
         block (`generate_clips`, `ts_body_pixel_infer_mixed_keep`).  None: nothing changes.
+        style: float speaker weights in place of the integer ids — per clip None, an (NC,) row or an (H,NC) track, or one (NC,) / (B,NC)
+        array for all clips (`generate_clips`, `ts_body_pixel_infer_mixed_style`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
-        if sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None:
+        if sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None or style is not None:
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
                                        _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
-                                       given_poses=given_poses, given_keep=given_keep)
+                                       given_poses=given_poses, given_keep=given_keep, style=style)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -221,7 +223,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
-                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None):
+                       _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None,
+                       style=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -257,7 +260,19 @@ class TrainWrapper(TrainWrapperBaseClass):
         Handing back an earlier decode (same seed, index, record) with ANY mask returns that decode bit for bit.  Keeping the hands while
         drawing the body is a forced decode, not a posterior sample: the body draw at row r sees the hands of rows < r only.  Poses are the
         VQ decode of the returned codes.  A mask of the wrong shape, a non-0/1 array, an unknown string or an entry on a clip that brings
-        nothing raises ValueError naming the clip before anything is launched (`ts_body_pixel_infer_mixed_keep` / `_poses_keep`)."""
+        nothing raises ValueError naming the clip before anything is launched (`ts_body_pixel_infer_mixed_keep` / `_poses_keep`).
+        style: float SPEAKER WEIGHTS in place of the integer ids (talkshow_hip.h, "speaker style"; `_lib.style_block`) — a list in submission
+        order with, per clip, None (the clip's id, that is, its one-hot row), an (NC,) row of weights for the whole clip (0.7 of speaker 0
+        and 0.3 of speaker 2; 1.5 and -0.5 to exaggerate) or an (H_b,NC) track with one row per code row (4 pose frames: start as A, hand
+        over to B across two seconds); or one (NC,) or (B,NC) array for all clips.  The class-conditioning vector of a code row is the
+        weighted sum of the speakers' vectors (ascending, product and sum rounded to fp32 separately, zero weights skipped;
+        `sampling.style_rows`): a blend is an INTERPOLATION OF THE CONDITIONING VECTORS — a virtual speaker between the trained ones — NOT
+        a mixture of the speakers' distributions.  A one-hot row is the integer id bit for bit; weights are any finite floats.  Entries
+        follow the clips through the length sort like the sampling records.  If no clip brings a track the pass is the pass of the ids with
+        other conditioning rows (same graphs); otherwise per-clip rows are repeated into tracks and the pass stages every chunk's rows
+        (graph keys of its own).  Orthogonal to every other keyword; given rows run under the style too, so handing back the head of an
+        earlier decode WITH THE SAME STYLE returns that decode.  A wrong shape, a wrong NC or a non-finite weight raises ValueError naming
+        the clip before anything is launched (`ts_body_pixel_infer_mixed_style` / `_poses_style`).  None: nothing changes."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -298,6 +313,7 @@ class TrainWrapper(TrainWrapperBaseClass):
                 pblock = ptable = None
         if gblock is None and pblock is None:
             kblock = None
+        sblock = _lib.style_block(style, [t // 4 for t in lens], self.num_classes, order, who="generate_clips", ids=ids)   # slot order, like the records
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -337,7 +353,24 @@ class TrainWrapper(TrainWrapperBaseClass):
         if kblock is not None:
             from talkshow_amd.modules import upload
             kdev = upload(kblock, dev)
-        if pblock is not None and gblock is None:
+        if sblock is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
+            from talkshow_amd.modules import upload
+            sdev = upload(sblock, dev)
+            if pblock is not None and gblock is None:
+                pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_style(
+                    *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)),
+                    _lib.dptr(kdev), _lib.dptr(sdev), int(sblock.shape[1]), _lib.stream_ptr()))
+            else:
+                gdev = None
+                if gblock is not None and pblock is not None:
+                    gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
+                elif gblock is not None:
+                    gdev = upload(gblock, dev)
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_style(
+                    *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), None if gdev is None else gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
+                    _lib.dptr(sdev), int(sblock.shape[1]), _lib.stream_ptr()))
+        elif pblock is not None and gblock is None:
             from talkshow_amd.modules import upload
             pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
             pargs = (*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)))
@@ -387,7 +420,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         gdev[:, :Hp] = torch.where(from_poses, enc[:, :Hp], gdev[:, :Hp])
         return gdev, np.ascontiguousarray(gtable + ptable // 4, dtype=np.int32)
 
-    def _score_pass(self, mfcc_list, ids, who, make_given):
+    def _score_pass(self, mfcc_list, ids, who, make_given, style=None):
         """The shared body of `score_clips` / `score_motion_clips`: the masked audio encoder, `ts_pixelcnn_generate_mixed_given` with every
         row given (G_b = H_b: nothing is drawn) and the log-probability output, `ts_logprob_sums` with the length table."""
         from talkshow_amd.modules import upload
@@ -410,6 +443,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             ids = ids.repeat(B)
         if ids.numel() != B:
             raise ValueError(f"ids must hold 1 or B={B} speaker indices, got {ids.numel()}")
+        sblock = _lib.style_block(style, rows, self.num_classes, order, who=who, ids=ids)   # before anything is launched, too
         T_max, H_max = lens[order[0]], lens[order[0]] // 4
         mf = torch.zeros((B, T_max, 64), dtype=torch.float32, device=dev)
         for k, i in enumerate(order):
@@ -425,16 +459,22 @@ class TrainWrapper(TrainWrapperBaseClass):
         lib, i32p = _lib.load(), _lib.C.POINTER(_lib.C.c_int32)
         _lib.check(lib.ts_audioenc_forward_masked(self.audioencoder.handle(), _lib.dptr(mf), _lib.dptr(lens_dev), B, T_max, _lib.dptr(feat),
                                                   _lib.stream_ptr()))
-        _lib.check(lib.ts_pixelcnn_generate_mixed_given(self.generator.handle(), _lib.dptr(ids_sorted), _lib.dptr(feat), lens_host.ctypes.data_as(i32p),
-                                                        _lib.dptr(lens_dev), B, H_max, _lib.TS_SAMPLE_GREEDY, None, 0, None, _lib.dptr(codes), None, 0,
-                                                        _lib.dptr(lp), _lib.dptr(given), table.ctypes.data_as(i32p), None, _lib.stream_ptr()))
+        gargs = (self.generator.handle(), _lib.dptr(ids_sorted), _lib.dptr(feat), lens_host.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H_max,
+                 _lib.TS_SAMPLE_GREEDY, None, 0, None, _lib.dptr(codes), None, 0, _lib.dptr(lp), _lib.dptr(given), table.ctypes.data_as(i32p), None)
+        if sblock is None:
+            _lib.check(lib.ts_pixelcnn_generate_mixed_given(*gargs, _lib.stream_ptr()))
+        else:
+            sdev = upload(sblock, dev)
+            _lib.check(lib.ts_pixelcnn_generate_mixed_style(*gargs, None, _lib.dptr(sdev), int(sblock.shape[1]), _lib.stream_ptr()))
         _lib.check(lib.ts_logprob_sums(self.generator._ctx(), _lib.dptr(lp), _lib.dptr(lens_dev), B, H_max, _lib.dptr(sums), _lib.stream_ptr()))
         return [(lp[inverse[b], :rows[b]], sums[inverse[b]]) for b in range(B)]
 
-    def score_clips(self, mfcc_list, ids, codes_list):
+    def score_clips(self, mfcc_list, ids, codes_list, style=None):
         """`score_batch` for clips of DIFFERENT lengths in ONE pass: mfcc_list = list of (T_b,64), ids (B,) or one for all, codes_list = list
         of (T_b // 4, 2) integer arrays -> list of (logprobs_b (H_b,2) float32, sums_b (3,) float64 {body, hand, both}) in submission order,
-        each bit-identical to `score_batch` on the clip alone.  A wrong shape or a code outside [0, V) raises ValueError naming the clip."""
+        each bit-identical to `score_batch` on the clip alone.  A wrong shape or a code outside [0, V) raises ValueError naming the clip.
+        style: the clips' speaker weights as for `generate_clips` (None, an (NC,) row or an (H_b,NC) track per clip, or one array for all):
+        the codes are scored under that style — the log-probabilities a decode with the same style returned."""
         from talkshow_amd.modules import upload
 
         def make(rows, order, dev):
@@ -445,12 +485,13 @@ class TrainWrapper(TrainWrapperBaseClass):
                     raise ValueError(f"score_clips: codes of clip {b} must have shape ({rows[b]}, 2), got {None if c is None else tuple(c.shape)}")
             block, _ = _lib.given_block(list(codes_list), rows, self.generator.input_dim, order, who="score_clips")
             return upload(block, dev)
-        return self._score_pass(mfcc_list, ids, "score_clips", make)
+        return self._score_pass(mfcc_list, ids, "score_clips", make, style=style)
 
-    def score_motion_clips(self, mfcc_list, ids, poses_list):
+    def score_motion_clips(self, mfcc_list, ids, poses_list, style=None):
         """How likely is this recorded MOTION under the model: `score_clips` on the codes the VQ encoders give the poses, encoded on the
         device in the same pass (`ts_vqvae_encode_pair_masked` in front of it; no host copy of codes).  poses_list = list of (P_b,129)
-        arrays in the wrapper's own pose layout (see `generate_clips`) with P_b = 4 (T_b // 4) frames: ValueError naming the clip otherwise."""
+        arrays in the wrapper's own pose layout (see `generate_clips`) with P_b = 4 (T_b // 4) frames: ValueError naming the clip otherwise.
+        style: as for `score_clips`; the encoders never see a speaker, the style shapes the scoring pass only."""
         from talkshow_amd.modules import encode_pair_masked, upload
 
         def make(rows, order, dev):
@@ -465,10 +506,10 @@ class TrainWrapper(TrainWrapperBaseClass):
                                                    width=self.each_dim[1] + self.each_dim[2])
             pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
             return encode_pair_masked(self.g_body, self.g_hand, pdev, upload(ptable, dev))     # (B, H_max, 2): P_max = 4 H_max
-        return self._score_pass(mfcc_list, ids, "score_motion_clips", make)
+        return self._score_pass(mfcc_list, ids, "score_motion_clips", make, style=style)
 
     def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
-                         given_poses=None, given_keep=None):
+                         given_poses=None, given_keep=None, style=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
@@ -476,7 +517,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         sampling_table: `_lib.sampling_table(...)` in ROW order (the caller sorted it with the rows), or None.
         given: `_lib.given_block(...)` in ROW order — (block, table), both numpy — or None.
         given_poses: `_lib.given_pose_block(...)` in ROW order — (block, table) — or None; with `given` too, no clip is in both.
-        given_keep: `_lib.given_keep_block(...)` in ROW order — the (B, H_max, 2) uint8 mask of kept positions — or None."""
+        given_keep: `_lib.given_keep_block(...)` in ROW order — the (B, H_max, 2) uint8 mask of kept positions — or None.
+        style: `_lib.style_block(...)` in ROW order — the (B, 1 or H_max, NC) float32 speaker weights that take the place of `ids` — or None."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -502,6 +544,31 @@ class TrainWrapper(TrainWrapperBaseClass):
             if given_keep.shape != (B, H_max, 2):
                 raise ValueError(f"infer_padded_wav: the mask of kept positions must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given_keep.shape}")
             kdev = upload(given_keep, dev)
+        if style is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
+            if style.ndim != 3 or style.shape[0] != B or style.shape[1] not in (1, H_max):
+                raise ValueError(f"infer_padded_wav: the style block must be (B, 1 or H_max, NC) = ({B}, 1 or {H_max}, NC), got {style.shape}")
+            sdev = upload(np.ascontiguousarray(style, dtype=np.float32), dev)
+            ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
+            if given is not None and given[0].shape != (B, H_max, 2):
+                raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
+            if given_poses is not None and int(given_poses[0].shape[1]) // 4 > H_max:
+                raise ValueError(f"infer_padded_wav: the given poses hold {int(given_poses[0].shape[1])} frames but the pass has {H_max} code rows")
+            if given_poses is not None and given is None:
+                pblock, ptable = given_poses
+                pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_style(
+                    *args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)),
+                    _lib.dptr(kdev), _lib.dptr(sdev), int(style.shape[1]), _lib.stream_ptr()))
+            else:
+                gdev = gtable = None
+                if given is not None and given_poses is not None:
+                    gdev, gtable = self._stage_given(given[0], given[1], given_poses[0], given_poses[1], dev)
+                elif given is not None:
+                    gdev, gtable = upload(given[0], dev), given[1]
+                _lib.check(_lib.load().ts_body_pixel_infer_mixed_style(
+                    *args, ctl, n_ctl, None, _lib.dptr(gdev), None if gdev is None else gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
+                    _lib.dptr(sdev), int(style.shape[1]), _lib.stream_ptr()))
+            return codes, poses, lens_host
         if given_poses is not None:
             pblock, ptable = given_poses
             if int(pblock.shape[1]) // 4 > H_max:
@@ -537,7 +604,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None, given_poses=None, given_keep=None):
+                                sampling=None, given=None, given_poses=None, given_keep=None, style=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
@@ -546,7 +613,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         order; the records follow the recordings through the sort by sample count.  given: as for `generate_clips`, one entry per recording
         in submission order (a recording's code rows: `frontend.mixed_tables(ns, sr)["code_rows"]`).  given_poses: as for `generate_clips`,
         one entry per recording.  given_keep: as for `generate_clips` — which positions of a recording's given rows are taken (None, "body",
-        "hand", a mask; one entry per recording, or one for all)."""
+        "hand", a mask; one entry per recording, or one for all).  style: as for `generate_clips` — float speaker weights in place of the
+        ids, per recording None, an (NC,) row or an (H_b,NC) track (H_b the recording's code rows), or one array for all."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -573,6 +641,9 @@ class TrainWrapper(TrainWrapperBaseClass):
             _lib.given_kinds_check(given_in, given_poses, B, "generate_clips_from_wav")
             given_poses = _lib.given_pose_block(given_poses, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], order,
                                                 who="generate_clips_from_wav", width=self.each_dim[1] + self.each_dim[2])
+        if style is not None:
+            style = _lib.style_block(style, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], self.num_classes, order,
+                                     who="generate_clips_from_wav", ids=ids)
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -582,7 +653,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
         codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given,
-                                                    given_poses=given_poses, given_keep=given_keep)
+                                                    given_poses=given_poses, given_keep=given_keep, style=style)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,

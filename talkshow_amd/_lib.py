@@ -132,6 +132,15 @@ SIGNATURES = {
     "ts_body_pixel_infer_mixed_poses_keep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
                                                   _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
     "ts_op_sample_keep": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    # speaker style: the most general sibling of each family with style_dev, style_rows ahead of the stream; the host rule; the kernel alone
+    "ts_pixelcnn_generate_mixed_style": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
+                                              C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
+    "ts_body_pixel_infer_mixed_style": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                             _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
+    "ts_body_pixel_infer_mixed_poses_style": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
+                                                   _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
+    "ts_style_check": (_i, [C.POINTER(C.c_float), C.c_long, _i]),
+    "ts_op_style_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -486,6 +495,77 @@ def given_keep_block(given_keep, counts, rows, order=None, who="given_keep"):
                                  + ("" if m.dtype.kind not in "iu" else f" with the value {int(m[(m < 0) | (m > 1)].flat[0])}"))
             mask[k, :G] = m[:G] != 0
     return mask
+
+
+def style_block(style, rows, NC, order=None, who="style", ids=None):
+    """The `style=` keyword of the decode and scoring entries -> the weight block (B, S, NC) float32 numpy in SLOT order that the `_style`
+    entries take as style_dev (after an upload) with style_rows = S, or None for `style=None` (talkshow_hip.h, "speaker style": the
+    class-conditioning vector of a code row is the ascending sum of weight * table row over the non-zero weights — an interpolation of
+    the speakers' conditioning vectors, NOT a mixture of their distributions).
+    style: a list in SUBMISSION order with, per clip, None (the clip's integer id, that is, its one-hot row: `ids` must be given), an
+    (NC,) row of weights for the whole clip, or an (H_b, NC) track with one row per code row; or one (NC,) or one (B, NC) array for all
+    clips.  rows: every clip's own code rows H_b in submission order; NC: the model's n_classes; order: sorted slot k holds submitted clip
+    order[k]; ids: the clips' integer speaker ids in submission order (one for all, or B).  S = 1 if no clip brings a track; otherwise
+    S = max rows, per-clip rows are repeated into tracks and a track's rows beyond H_b repeat its last row (the pass does not use them).
+    Weights are any finite floats (no sign rule, no sum rule).  ValueError naming the SUBMITTED clip, before anything is launched, for a
+    wrong shape, a wrong NC or a non-finite weight (`ts_style_check`).  Pure host code; a device tensor is read back."""
+    if style is None:
+        return None
+    B, NC = len(rows), int(NC)
+
+    def host(x):
+        return x.detach().cpu().numpy() if hasattr(x, "detach") else x
+    style = host(style)
+    if isinstance(style, (list, tuple)) and not any(e is None or np.ndim(host(e)) >= 1 for e in style):
+        style = np.asarray(style)      # a plain list of numbers: one row for all clips
+    if isinstance(style, np.ndarray):
+        if style.ndim == 1:
+            style = [style] * B
+        elif style.ndim == 2 and style.shape[0] == B:
+            style = list(style)
+        else:
+            raise ValueError(f"{who}: one style array for all clips must have shape (NC={NC},) or (B={B}, NC={NC}), got {tuple(style.shape)} "
+                             f"(a track is one entry of a list)")
+    if not isinstance(style, (list, tuple)) or len(style) != B:
+        raise ValueError(f"{who}: style takes one entry per clip ({B}) — None, an (NC,) row or an (H_b, NC) track — or one (NC,) or (B, NC) "
+                         f"array, got {type(style).__name__}" + (f" of {len(style)}" if isinstance(style, (list, tuple)) else ""))
+    order = list(range(B)) if order is None else [int(i) for i in order]
+    if sorted(order) != list(range(B)):
+        raise ValueError(f"{who}: order must be a permutation of the {B} clips")
+    if ids is not None and any(e is None for e in style):      # read back only where an entry asks for the clip's id
+        ids = np.asarray(host(ids), np.int64).reshape(-1)
+        if ids.size == 1 and B > 1:
+            ids = np.repeat(ids, B)
+    entries = [None] * B
+    for i, e in enumerate(style):
+        if e is None:
+            if ids is None or ids.size != B or not 0 <= int(ids[i]) < NC:
+                raise ValueError(f"{who}: style of clip {i} is None — the clip's integer id — but the clip has no id in [0, {NC})")
+            e = np.zeros(NC, np.float32)
+            e[int(ids[i])] = 1.0
+        else:
+            e = np.asarray(host(e))
+            if e.dtype.kind not in "fiub":
+                raise ValueError(f"{who}: style of clip {i} must be numbers, got {e.dtype}")
+            if e.ndim not in (1, 2) or (e.ndim == 2 and e.shape[0] != int(rows[i])):
+                raise ValueError(f"{who}: style of clip {i} must have shape ({NC},) or ({int(rows[i])}, {NC}), the clip's code rows, got "
+                                 f"{tuple(e.shape)}")
+            if e.shape[-1] != NC:
+                raise ValueError(f"{who}: style of clip {i} has {e.shape[-1]} weights per row, the model has NC = {NC} speakers")
+            e = np.ascontiguousarray(e, dtype=np.float32)
+            if load().ts_style_check(e.ctypes.data_as(C.POINTER(C.c_float)), int(e.size), NC) != 0:
+                raise ValueError(f"{who}: style of clip {i}: " + load().ts_last_error().decode())
+        entries[i] = e
+    S = max(int(h) for h in rows) if any(e.ndim == 2 for e in entries) else 1
+    block = np.zeros((B, S, NC), np.float32)
+    for k, i in enumerate(order):
+        e = entries[i]
+        if e.ndim == 1:
+            block[k, :] = e
+        else:
+            block[k, :e.shape[0]] = e
+            block[k, e.shape[0]:] = e[-1]
+    return block
 
 
 def given_pose_block(given_poses, rows, order=None, who="given_poses", width=129):

@@ -213,8 +213,9 @@ int ts_body_pixel_infer_mixed_lp(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb,
 }
 
 // What every mixed body entry refuses before its first launch: null arguments, the shape, the length table (within T_max, at least one code
-// row, non-increasing) and the sampling records; `who` names the entry in the messages
-static int body_mixed_check(const char *who, const void *ae, const void *pix, const void *vb, const void *vh, const float *mfcc, const int64_t *ids,
+// row, non-increasing) and the sampling records; `who` names the entry in the messages.  `ids`: the speaker ids, or — a pass under a "speaker
+// style" does not read them — the style block that takes their place
+static int body_mixed_check(const char *who, const void *ae, const void *pix, const void *vb, const void *vh, const float *mfcc, const void *ids,
                             const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const int64_t *codes, const float *poses,
                             const ts_sampling *ctl_host, int n_ctl) {
     const std::string w(who);
@@ -253,8 +254,22 @@ int ts_body_pixel_infer_mixed_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *v
                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                    const uint8_t *keep, void *stream) {
-    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
+    return ts_body_pixel_infer_mixed_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                           ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, nullptr, 0, stream);
+}
+
+// the same pass under a "speaker style" (talkshow_hip.h): style (B, style_rows, NC) float weights in slot order in place of the ids, which
+// are then not read and may be NULL; style_rows is 1 or T_max / 4.  style == NULL: exactly the entry above
+int ts_body_pixel_infer_mixed_style(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                    const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
+                                    const uint8_t *keep, const float *style, int style_rows, void *stream) {
+    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, style ? static_cast<const void *>(style) : ids, lens_host, lens_dev, B,
+                         T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
         return 1;
+    if (style && style_rows != 1 && style_rows != (T_max / 2) / 2)
+        return fail("ts_body_pixel_infer_mixed_style: style_rows is 1 or T_max / 4 = " + std::to_string((T_max / 2) / 2) + ", got " + std::to_string(style_rows));
     if (keep && !given) return fail("ts_body_pixel_infer_mixed_keep: a mask of kept positions needs the given codes it selects from");
     if (given) {   // a bad row table is refused before the first launch of the pass, too
         if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
@@ -266,8 +281,8 @@ int ts_body_pixel_infer_mixed_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *v
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * aud_dim * sizeof(float)));
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
-    TS_TRY(ts_pixelcnn_generate_mixed_keep(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
-                                           n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, s));
+    TS_TRY(ts_pixelcnn_generate_mixed_style(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
+                                            n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, s));
     for (int k = 0; k < 2; ++k) {
         TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
         TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),
@@ -310,17 +325,32 @@ int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
                                          uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
                                          int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                          const int32_t *pose_lens_dev, const uint8_t *keep, void *stream) {
+    return ts_body_pixel_infer_mixed_poses_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                                 poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, keep, nullptr, 0,
+                                                 stream);
+}
+
+// the same under a "speaker style" (style (B, style_rows, NC) in place of the ids; style == NULL: exactly the entry above).  The encoders
+// never see a speaker: the style shapes the pass behind them only
+int ts_body_pixel_infer_mixed_poses_style(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                          const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                          uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
+                                          int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
+                                          const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows, void *stream) {
     if (keep && !given_poses)
         return fail("ts_body_pixel_infer_mixed_poses_keep: a mask of kept positions needs the given poses whose codes it selects from");
     if (!given_poses)
-        return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
+        return ts_body_pixel_infer_mixed_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, nullptr, style, style_rows, stream);
     const char *who = "ts_body_pixel_infer_mixed_poses";
     // everything the pass itself would refuse is refused here too, ahead of the encoders' launches
     if (!pose_lens_host || !pose_lens_dev) return fail(std::string(who) + ": given poses need their frame tables");
-    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
+    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, style ? static_cast<const void *>(style) : ids, lens_host, lens_dev, B,
+                         T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
         return 1;
     const int H = (T_max / 2) / 2;
+    if (style && style_rows != 1 && style_rows != H)
+        return fail("ts_body_pixel_infer_mixed_style: style_rows is 1 or T_max / 4 = " + std::to_string(H) + ", got " + std::to_string(style_rows));
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
     if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": TS_SAMPLE_UNIFORMS needs uniforms_dev");
     if (ts_given_pose_rows_check(pose_lens_host, lens_host, B) != 0) return 1;
@@ -332,8 +362,8 @@ int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
     }
     if (p_top > P_max) return fail(std::string(who) + ": a clip brings more pose frames than P_max");
     if (p_top == 0)   // nothing given anywhere: the pass without given rows
-        return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
+        return ts_body_pixel_infer_mixed_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, nullptr, style, style_rows, stream);
     if (P_max / 4 > H) return fail(std::string(who) + ": P_max / 4 exceeds the pass's code rows T_max / 4");
     hipStream_t s = (hipStream_t)stream;
     BodyWork &w = body_work(s);
@@ -341,8 +371,8 @@ int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
     int64_t *given = static_cast<int64_t *>(w.given.p);
     // rows h < P_b / 4 of clip b: its codes; rows up to P_max / 4: -1; rows beyond stay as they are — the pass reads rows below G_b only
     TS_TRY(vq_encode_pair_masked(vb, vh, given_poses, vqvae_in_dim(vb) + vqvae_in_dim(vh), pose_lens_dev, B, P_max, given, H, nullptr, nullptr, 0, s));
-    return ts_body_pixel_infer_mixed_keep(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                          ctl_host, n_ctl, logprob, given, G.data(), nullptr, keep, stream);
+    return ts_body_pixel_infer_mixed_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                           ctl_host, n_ctl, logprob, given, G.data(), nullptr, keep, style, style_rows, stream);
 }
 
 int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const float *w, const float *bias, int Cout,

@@ -288,6 +288,22 @@ hipError_t launch_gather_rows(const float *table, int ld_table, int nrows, const
 // idx holds there (the index is not read); rows inside the clip keep the NaN answer to a bad index
 hipError_t launch_gather_rows_masked(const float *table, int ld_table, int nrows, const int64_t *idx, long idx_stride, int M,
                                      int width, float *out, int ldo, int L, const int *lens, int len_shr, hipStream_t stream);
+// speaker style (talkshow_hip.h): out[l][rr][slot][0..W) for the rows [r0, r0 + n) of `slots` clip slots and NL layers, from float weights
+// (slots, S, NC) with rows w_ld floats apart (S == 1: one row per slot for every code row) and the NL class tables [NL][NC][W]:
+// the ascending sum of w[c] * E_l[c] over the non-zero weights, product and sum rounded separately, +0.0 if there is none.
+// lens (optional, (slots,)): rows at or beyond lens[slot] >> len_shr take the weights of the slot's last own row.
+struct StyleRowsParams {
+    const float *tables;
+    const float *weights;
+    long w_ld;
+    int S, NC, W, NL;
+    int r0, n, slots;
+    const int *lens;
+    int len_shr;
+    float *out;
+    long out_l_stride, out_r_stride;   // floats between the layers / the rows of `out`; slots are W apart
+};
+hipError_t launch_style_rows(const StyleRowsParams &p, hipStream_t stream);
 // dst[b][t][0..cpad) = src[b][t][0..c) then zeros for t < lens[b], a zero row for t >= lens[b]  (B clips of L rows)
 hipError_t launch_pad_rows_masked(const float *src, int lds, int c, float *dst, int ldd, int cpad, int B, int L, const int *lens,
                                   hipStream_t stream);

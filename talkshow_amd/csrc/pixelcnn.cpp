@@ -39,6 +39,7 @@
 // Rows are absolute indices: a one-shot call runs rows 0..H-1 (after an optional known prefix), a streaming session
 // (ts_pixelcnn_stream_*) continues at the row where its previous step stopped, on a row cache that persists in its Work.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <deque>
 #include <set>
@@ -66,6 +67,7 @@ struct ts_pixelcnn {
     std::vector<std::unique_ptr<DevBuf>> wB, bm;             // B: [2D][D or 2D], bm_l [2D]
     DevBuf w1m, b1m;                                         // head1': [HID][D or 2D], [HID]
     ConvLayer aud_h1;                                        // Wh1_1 applied to AEH for every row (l = 1 has AEH in place of XH_0)
+    DevBuf cls_all;                                          // the NL class tables again, contiguous [NL][NC][2D]: what style_rows_kernel reads
     bool use_graph = true;
     int defer_p = -1;     // the next-row projections P_l of the vertical stack ride with column 1's launches: -1 auto, 0 never, 1 always
     // tiled operand layouts (kernels.h, SkinnyParams::w_tiled): every weight matrix of the chain gets a tiled twin, and
@@ -91,6 +93,8 @@ struct ts_pixelcnn {
         DevBuf given_tab, given_int;       // passes with given rows: G of every clip SLOT (int32, written in stream order ahead of the pass); the given codes of
                                            // ONE chunk, (B,rows,2) int64 beside codes_int (what the captured samplers read)
         DevBuf keep_int;                   // passes with a mask of kept positions: the mask bytes of ONE chunk, (B,rows,2) uint8 beside given_int
+        DevBuf style_int;                  // passes with per-row speaker style: the class-conditioning rows of ONE chunk, [NL][CHUNK_ROWS][Bs][2D] fp32 (slabs Bs
+                                           // clips apart, like CR); allocated by the first such pass, filled ahead of every chunk by style_rows_kernel
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
@@ -99,7 +103,8 @@ struct ts_pixelcnn {
         // The sixth field is a bit set: bit 0 for a run whose samplers read ctl_tab (sample_ctl_kernel), bit 1 for a run whose samplers write
         // log-probabilities into lp_int, bit 2 for a pass with given rows (EVERY chunk of such a pass runs the given variants of the samplers,
         // which read given_tab and given_int), bit 3 for a given pass that brings a mask of kept positions (every chunk's samplers then also
-        // read keep_int; without the bit their mask pointer is null); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // read keep_int; without the bit their mask pointer is null), bit 4 for a pass with per-row speaker style (the gate launches of every chunk
+        // read their conditioning rows from style_int in place of CR); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -299,6 +304,15 @@ struct RunCfg {
     // "kept positions": keep_src the caller's (B,out_H,2) uint8 mask beside given_src or null (every given position kept); staged with the
     // given codes; keep: set by run_rows, laid out like `given`
     const unsigned char *keep_src = nullptr, *keep = nullptr;
+    // "speaker style" with per-row tracks: the Work's style_int, which holds the conditioning rows of code rows [style_r0, style_r0 +
+    // CHUNK_ROWS) as [NL][CHUNK_ROWS][slabB()][2D]; null: one conditioning row per clip for the whole call (the Work's CR)
+    const float *style = nullptr;
+    int style_r0 = 0;
+    // the class-conditioning rows of layer l for the gate launches of code row r (every such launch belongs to one row)
+    const float *cls_rows(int l, int r, size_t D2) const {
+        if (!style) return w->CR.f() + (size_t)l * slabB() * D2;
+        return style + ((size_t)l * CHUNK_ROWS + (size_t)(r - style_r0)) * slabB() * D2;
+    }
     int slabB() const { return Bs > 0 ? Bs : B; }
     void audio_from(ts_pixelcnn::Work *wk) { aeh = wk->AEH.f(), aeh1 = wk->AEH1.f(), av1c = wk->AV1C.f(), av1p = wk->AV1P.f(); }
 };
@@ -397,7 +411,7 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
     auto V2H = [&](int l) { return w->V2H.f() + (size_t)l * Bs * 4 * D; };
     auto P = [&](int l, int par) { return w->P.f() + ((size_t)(l * 2 + par) * Bs) * 4 * D; };
     auto Q = [&](DevBuf &q, int row) { return q.f() + (size_t)(row & 3) * Bs * 4 * D; };
-    auto CR = [&](int l) { return w->CR.f() + (size_t)l * Bs * 2 * D; };
+    auto CR = [&](int l) { return c.cls_rows(l, r, 2 * (size_t)D); };
 
     auto gate_common = [&](SkinnyParams &q, int l) {
         q.ldw = 2 * D;
@@ -516,7 +530,7 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
     auto V2H = [&](int l) { return w->V2H.f() + (size_t)l * Bs * 4 * D + (size_t)j * 2 * D; };
     const size_t Bp = round_up((int)Bs, 16);
     auto XH = [&](int l, int col) { return w->XH.f() + ((size_t)(l * 2 + col) * Bp) * D; };
-    auto CR = [&](int l) { return w->CR.f() + (size_t)l * Bs * 2 * D; };
+    auto CR = [&](int l) { return c.cls_rows(l, r, 2 * (size_t)D); };
     auto G = [&](int l) { return w->G.f() + (size_t)(l & 1) * Bp * D; };
     auto T0 = [&](int l) { return w->T0.f() + (size_t)l * Bs * 2 * D; };
     auto make_t0 = [&](int l) {   // column 0 only: Wh0_l . XH_l[0], consumed by column 1's S_l
@@ -739,6 +753,7 @@ int ts_pixelcnn_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int V, int D, i
     TS_TRY(p->emb.upload(emb, (size_t)V * D * sizeof(float)));
 
     p->wvt.resize(NL);
+    std::vector<float> cls_all;
     for (int l = 0; l < NL; ++l) {
         const std::string q = "layers." + std::to_string(l);
         const int kh = l == 0 ? 4 : 2;       // kernel // 2 + 1 rows, kernel = 7 / 3 (gated_pixelcnn_v2.py:34,112-113)
@@ -780,9 +795,11 @@ int ts_pixelcnn_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int V, int D, i
         TS_TRY(upload_vec(p->wh, ph));
         TS_TRY(upload_vec(p->bh, std::vector<float>(bh, bh + D2)));
         TS_TRY(upload_vec(p->cls, std::vector<float>(cl, cl + (size_t)NC * D2)));
+        cls_all.insert(cls_all.end(), cl, cl + (size_t)NC * D2);
         TS_TRY(upload_vec(p->wr, std::vector<float>(wr, wr + (size_t)D * D)));
         TS_TRY(upload_vec(p->br, std::vector<float>(br, br + D)));
     }
+    TS_TRY(p->cls_all.upload(cls_all.data(), cls_all.size() * sizeof(float)));
     // audio conditioning
     const float *wa = sd.get("embedding_aud.weight", {D, AD, 1, 1}), *ba = sd.get("embedding_aud.bias", {D});
     const float *wfv = sd.get("fusion_v.weight", {D, D2, 1, 1}), *bfv = sd.get("fusion_v.bias", {D});
@@ -1032,8 +1049,9 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 // The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
-inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr, const unsigned char *keep = nullptr) {
-    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0);
+inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr, const unsigned char *keep = nullptr,
+                        const float *style = nullptr) {
+    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0) | (style ? 16 : 0);
 }
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
@@ -1071,6 +1089,24 @@ int class_rows(ts_pixelcnn *p, ts_pixelcnn::Work *w, const int64_t *label, int B
     MiscScope ms(p->ctx, s);
     for (int l = 0; l < p->NL; ++l)
         TS_HIP(launch_gather_rows(p->cls[l]->f(), 2 * D, p->NC, label, 1, B, 2 * D, w->CR.f() + (size_t)l * B * 2 * D, 2 * D, s));
+    return 0;
+}
+
+// "speaker style" (talkshow_hip.h): the same rows from float weights, one row of NC weights per clip slot (style (B,NC)), through
+// style_rows_kernel in place of the gather.  CR's content is in no graph key: the pass behind it is the pass behind the labels
+int class_rows_style(ts_pixelcnn *p, ts_pixelcnn::Work *w, const float *style, int B, hipStream_t s) {
+    MiscScope ms(p->ctx, s);
+    StyleRowsParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.tables = p->cls_all.f();
+    q.weights = style;
+    q.w_ld = p->NC;
+    q.S = 1, q.NC = p->NC, q.W = 2 * p->D, q.NL = p->NL;
+    q.r0 = 0, q.n = 1, q.slots = B;
+    q.out = w->CR.f();
+    q.out_l_stride = (long)B * 2 * p->D;
+    q.out_r_stride = 0;
+    TS_HIP(launch_style_rows(q, s));
     return 0;
 }
 
@@ -1221,7 +1257,7 @@ constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
               uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, const int64_t *given, int given_max,
-              const unsigned char *keep, hipStream_t s) {
+              const unsigned char *keep, const float *style_track, const int *lens_dev, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1242,6 +1278,24 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
             c.keep_src = keep;   // a masked pass runs the masked form in every chunk, too
             c.given_stage = r0 < given_max;
         }
+        if (style_track) {   // the chunk's conditioning rows, staged eagerly ahead of the replay like its uniforms and given codes: the only
+                             // launch that reads the caller's weight block, so no caller pointer enters a captured graph
+            MiscScope ms(p->ctx, s);
+            StyleRowsParams q;
+            std::memset(&q, 0, sizeof(q));
+            q.tables = p->cls_all.f();
+            q.weights = style_track;
+            q.w_ld = p->NC;
+            q.S = H_max, q.NC = p->NC, q.W = (int)(2 * D), q.NL = p->NL;
+            q.r0 = r0, q.n = Hc, q.slots = Ba;
+            q.lens = lens_dev, q.len_shr = 2;
+            q.out = w->style_int.f();
+            q.out_l_stride = (long)CHUNK_ROWS * B * 2 * D;
+            q.out_r_stride = (long)B * 2 * D;
+            TS_HIP(launch_style_rows(q, s));
+            c.style = w->style_int.f();
+            c.style_r0 = r0;
+        }
         struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
             {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
         for (auto &m : rows)
@@ -1249,7 +1303,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src)), uniforms, codes, logprob, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src, c.style)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1456,6 +1510,37 @@ int ts_op_sample_keep(ts_ctx *ctx, const float *logits, int B, int V, int mode, 
     return 0;
 }
 
+// Host only ("speaker style"): every weight of a style block is finite; the first bad index is named
+int ts_style_check(const float *w_host, long n, int NC) {
+    if (!w_host || n < 0 || NC < 1) return fail("ts_style_check: bad argument");
+    for (long i = 0; i < n; ++i)
+        if (!std::isfinite(w_host[i]))
+            return fail("ts_style_check: weight " + std::to_string(i) + " (row " + std::to_string(i / NC) + ", speaker " + std::to_string(i % NC) +
+                        ") is not finite");
+    return 0;
+}
+
+// style_rows_kernel on its own (kernel-level tests call it): tables (NL,NC,W), weights (M,NC) -> out (NL,M,W), row m from weight row m.
+// Run as ONE clip slot with a track of M rows, so the kernel's row indexing is what is exercised
+int ts_op_style_rows(ts_ctx *ctx, const float *tables, int NL, int NC, int W, const float *weights, int M, float *out, void *stream) {
+    if (!ctx || !tables || !weights || !out) return fail("ts_op_style_rows: null argument");
+    if (NL < 1 || NC < 1 || M < 1 || W < 4 || W % 4) return fail("ts_op_style_rows: bad shape (W is a positive multiple of 4)");
+    hipStream_t s = (hipStream_t)stream;
+    StyleRowsParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.tables = tables;
+    q.weights = weights;
+    q.w_ld = NC;
+    q.S = M, q.NC = NC, q.W = W, q.NL = NL;
+    q.r0 = 0, q.n = M, q.slots = 1;
+    q.out = out;
+    q.out_l_stride = (long)M * W;
+    q.out_r_stride = W;
+    TS_HIP(launch_style_rows(q, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
@@ -1491,15 +1576,30 @@ int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const
                                            logprob, given, given_rows_host, given_rows_dev, nullptr, stream);
 }
 
-// the given pass with a mask of kept positions beside the given block (talkshow_hip.h, "kept positions"): position (r, j) of clip b is taken
-// iff r < G_b and keep[b, r, j] != 0, every other position is produced.  keep == NULL: the _given entry, launch for launch
 int ts_pixelcnn_generate_mixed_keep(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                     int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, void *stream) {
+    return ts_pixelcnn_generate_mixed_style(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                            logprob, given, given_rows_host, given_rows_dev, keep, nullptr, 0, stream);
+}
+
+// the given pass with a mask of kept positions beside the given block (talkshow_hip.h, "kept positions"): position (r, j) of clip b is taken
+// iff r < G_b and keep[b, r, j] != 0, every other position is produced.  keep == NULL: the _given entry, launch for launch.
+// With "speaker style" (talkshow_hip.h): style (B, style_rows, NC) float weights in slot order take the place of the labels — style_rows == 1
+// fills CR through style_rows_kernel and changes nothing else; style_rows == H_max stages every chunk's conditioning rows into style_int and
+// runs on graph keys of its own (bit 4).  style == NULL: the _keep entry, launch for launch
+int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                     int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
+                                     int style_rows, void *stream) {
     (void)given_rows_dev;   // the table travels as kernel arguments from the host copy (see talkshow_hip.h)
-    if (!p || !label || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
+    if (!p || (!label && !style) || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
+    if (style && style_rows != 1 && style_rows != H_max)
+        return fail("ts_pixelcnn_generate_mixed_style: style_rows is 1 or H_max = " + std::to_string(H_max) + ", got " + std::to_string(style_rows));
+    const bool tracked = style && style_rows > 1;   // H_max == 1: one row per clip either way
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail("ts_pixelcnn_generate_mixed: bad mode");
     if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_pixelcnn_generate_mixed: uniforms required");
     std::vector<int> hrows(B);
@@ -1529,7 +1629,14 @@ int ts_pixelcnn_generate_mixed_keep(ts_pixelcnn *p, const int64_t *label, const 
         TS_HIP(launch_put_words(w->given_tab.i(), given_rows_host, B, s));
     }
     TS_TRY(audio_terms(p, w, aud, B, H_max, s));
-    TS_TRY(class_rows(p, w, label, B, s));
+    if (tracked) {   // sized with the Work's clip capacity, so it moves only when ensure_work has dropped the graphs that read it
+                     // (its size follows capB alone, and no graph reads it before its first allocation)
+        TS_TRY(w->style_int.ensure((size_t)p->NL * CHUNK_ROWS * w->capB * 2 * p->D * sizeof(float)));
+    } else if (style) {
+        TS_TRY(class_rows_style(p, w, style, B, s));
+    } else {
+        TS_TRY(class_rows(p, w, label, B, s));
+    }
     {   // the clips' Philox subsequences, in a Work buffer (what the captured samplers read): the caller's table, or 0 .. B-1
         MiscScope ms(ctx, s);
         if (clip_index) TS_HIP(hipMemcpyAsync(w->clip_tab.p, clip_index, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
@@ -1537,7 +1644,7 @@ int ts_pixelcnn_generate_mixed_keep(ts_pixelcnn *p, const int64_t *label, const 
     }
     const bool graph = p->use_graph && !ctx->prof.on;
     TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
-                     logprob, given, given_max, keep, s));
+                     logprob, given, given_max, keep, tracked ? style : nullptr, lens_dev, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0

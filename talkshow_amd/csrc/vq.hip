@@ -499,6 +499,44 @@ hipError_t launch_gather_rows(const float *table, int ld_table, int nrows, const
     return hipGetLastError();
 }
 
+// speaker style (talkshow_hip.h): the class-conditioning rows of a window of code rows from float WEIGHTS in place of integer labels.
+// One wave per (row of the window, clip slot, layer): out[l][rr][slot][0..W) = sum over c ascending of w[slot][r][c] * E_l[c][0..W), every
+// product and every sum rounded to fp32 on its own (__fmul_rn / __fadd_rn: no FMA contraction), a weight of exactly 0 skipped — its table
+// row is not loaded — and +0.0 where every weight is 0.  The weight row's address depends on blockIdx only, so its loads are scalar and
+// the zero-skip is a uniform branch.  S == 1: one weight row per slot serves every row.  With a length table, a row at or beyond the
+// slot's own H_b = lens[slot] >> len_shr takes the weights of row H_b - 1 (rows carried to a chunk's end read finite data).
+__global__ __launch_bounds__(64) void style_rows_kernel(const StyleRowsParams p) {
+    const int rr = blockIdx.x / p.slots, slot = blockIdx.x - rr * p.slots, l = blockIdx.y;
+    int r = p.r0 + rr;
+    if (p.lens) r = min(r, (p.lens[slot] >> p.len_shr) - 1);
+    r = max(min(r, p.S - 1), 0);
+    const float *__restrict__ wrow = p.weights + ((long)slot * p.S + r) * p.w_ld;
+    const float *__restrict__ tab = p.tables + (long)l * p.NC * p.W;
+    float4 *__restrict__ dst = reinterpret_cast<float4 *>(p.out + (long)l * p.out_l_stride + (long)rr * p.out_r_stride + (long)slot * p.W);
+    for (int q = threadIdx.x; q < p.W / 4; q += 64) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        bool any = false;
+        for (int c = 0; c < p.NC; ++c) {
+            const float wc = wrow[c];
+            if (wc == 0.f) continue;
+            const float4 e = reinterpret_cast<const float4 *>(tab + (long)c * p.W)[q];
+            const float4 t = make_float4(__fmul_rn(wc, e.x), __fmul_rn(wc, e.y), __fmul_rn(wc, e.z), __fmul_rn(wc, e.w));
+            acc = any ? make_float4(__fadd_rn(acc.x, t.x), __fadd_rn(acc.y, t.y), __fadd_rn(acc.z, t.z), __fadd_rn(acc.w, t.w)) : t;
+            any = true;
+        }
+        dst[q] = acc;
+    }
+}
+hipError_t launch_style_rows(const StyleRowsParams &p, hipStream_t stream) {
+    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (!p.tables || !p.weights || !p.out || p.NL < 1 || p.NC < 1 || p.W < 4 || p.W % 4 || p.S < 1 || p.n < 1 || p.slots < 1 || p.r0 < 0 ||
+        p.w_ld < p.NC || p.out_l_stride % 4 || p.out_r_stride % 4 || !al16(p.tables) || !al16(p.out) || (p.S > 1 && p.r0 + p.n > p.S) ||
+        (long)p.n * p.slots > 0x7fffffffl || p.NL > 65535 || (p.lens && p.len_shr < 0))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(style_rows_kernel, dim3((unsigned)(p.n * p.slots), (unsigned)p.NL), dim3(64), 0, stream, p);
+    return hipGetLastError();
+}
+
 // gather_rows_kernel for a padded batch of clips of different lengths (mixed passes): rows beyond a clip's own length become zero rows —
 // what the conv gather substitutes past the end of a clip run alone — and their index is never read
 __global__ __launch_bounds__(256) void gather_rows_masked_kernel(const float *__restrict__ table, int ld_table,

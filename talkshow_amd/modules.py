@@ -341,7 +341,8 @@ class GatedPixelCNN(NativeModule):
         (_lib.load().ts_pixelcnn_destroy if self.bh_model else _lib.load().ts_pixelcnn_v_destroy)(h)
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
-            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None, given_keep=None):
+            want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None, given_keep=None,
+            style=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
@@ -361,7 +362,20 @@ class GatedPixelCNN(NativeModule):
         nothing were given there — its given code is not read and may hold anything — and draws the number of its absolute (row, column), so
         handing back an earlier decode with any mask returns that decode.  Keeping hands while drawing the body is a forced decode, not a
         posterior sample (the body draw at row r sees hands of rows < r only).  ValueError naming the clip for a bad mask or a mask on a
-        clip that brings nothing; `ts_pixelcnn_generate_mixed_keep`."""
+        clip that brings nothing; `ts_pixelcnn_generate_mixed_keep`.
+        style: float SPEAKER WEIGHTS in place of `label` (`_lib.style_block`; talkshow_hip.h, "speaker style"): a list with, per clip,
+        None (the clip's label, that is, its one-hot row), an (n_classes,) row for the whole clip or an (H,n_classes) track with one row
+        per code row; or one (n_classes,) or (B,n_classes) array for all clips.  The class-conditioning vector of a code row is the
+        weighted sum of the classes' vectors (`sampling.style_rows`): a blend is an interpolation of the conditioning vectors, NOT a
+        mixture of the classes' distributions; a one-hot row is the label bit for bit; weights are any finite floats.  Goes through the
+        mixed entry with equal lengths (`ts_pixelcnn_generate_mixed_style`): not with want_logits, pre_codes or TS_TEACHER_FORCED.
+        ValueError naming the clip for a wrong shape, a wrong n_classes or a non-finite weight, before any device work.  None (the
+        default): no return value and no launch changes."""
+        if style is not None:
+            if not self.bh_model:
+                raise NotImplementedError("speaker style exists for the bh_model=True chain (ts_pixelcnn_generate_mixed_style), not for the single-stack form")
+            if want_logits or pre_codes is not None or mode == _lib.TS_TEACHER_FORCED:
+                raise ValueError("run: a speaker style goes through the mixed entry, which takes no logits output, no pre_codes and no teacher forcing")
         if given_keep is not None and not self.bh_model:
             raise NotImplementedError("kept positions exist for the bh_model=True chain (ts_pixelcnn_generate_mixed_keep), not for the single-stack form")
         if given is not None:
@@ -403,6 +417,7 @@ class GatedPixelCNN(NativeModule):
             label = label.repeat(B)
         if label.numel() != B:
             raise ValueError(f"label must hold 1 or B={B} class indices, got {label.numel()}")
+        sblock = _lib.style_block(style, [H] * B, self.n_classes, who="run", ids=label)   # ValueError before any device work
         if mode == _lib.TS_TEACHER_FORCED:
             codes = torch.as_tensor(codes, dtype=torch.int64, device=dev).contiguous()
             if lp is not None:
@@ -425,17 +440,23 @@ class GatedPixelCNN(NativeModule):
                 self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, W, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0, _lib.stream_ptr()))
             return codes, logits
-        if given is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
+        if given is not None or sblock is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
             i32p = C.POINTER(C.c_int32)
             lens = np.full(B, 4 * H, np.int32)
-            lens_dev, block_dev = upload(lens, dev), upload(block, dev)
+            lens_dev = upload(lens, dev)
+            block_dev = upload(block, dev) if given is not None else None
             clip_index = upload(np.arange(B, dtype=np.int64) + int(clip_index0), dev)
             if isinstance(lp, str):
                 lp = torch.empty((B, H, 2), dtype=torch.float32, device=dev)
             gargs = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
                      _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), ctl, n_ctl, _lib.dptr(lp),
-                     _lib.dptr(block_dev), table.ctypes.data_as(i32p), None)
-            if kblock is None:
+                     _lib.dptr(block_dev), table.ctypes.data_as(i32p) if given is not None else None, None)
+            if sblock is not None:
+                keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
+                style_dev = upload(sblock, dev)
+                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_style(*gargs, _lib.dptr(keep_dev), _lib.dptr(style_dev), int(sblock.shape[1]),
+                                                                        _lib.stream_ptr()))
+            elif kblock is None:
                 _lib.check(_lib.load().ts_pixelcnn_generate_mixed_given(*gargs, _lib.stream_ptr()))
             else:
                 keep_dev = upload(kblock, dev)

@@ -140,7 +140,7 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
 
 
 def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None,
-                     given=None, given_poses=None, given_keep=None):
+                     given=None, given_poses=None, given_keep=None, style=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -160,7 +160,10 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     given_poses: the same from motion — None or the (P_b, 129) pose frames of that recording's head, encoded on the device
     (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_poses`).  A recording brings one kind.
     given_keep: which positions of a recording's given rows are taken — None (all), "body" (keep the body column, draw new hands), "hand",
-    or a (G_b, 2) mask, per recording or one for all (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_keep`)."""
+    or a (G_b, 2) mask, per recording or one for all (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_keep`).
+    style: float speaker weights for the BODY half in place of `ids` — per recording None (its id), an (NC,) row or an (H_b, NC) track with
+    one row per code row, or one (NC,) / (B, NC) array for all (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_style`; a blend
+    interpolates the conditioning vectors, it is not a mixture of the speakers' distributions).  The face half keeps `face_ids`."""
     import ctypes as C
 
     import numpy as np
@@ -206,6 +209,11 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
             given = _lib.given_block(given, rows_sub, body.generator.input_dim, order, who="whole_body_clips", keep=given_keep)
         if given_poses is not None:
             given_poses = _lib.given_pose_block(given_poses, rows_sub, order, who="whole_body_clips", width=body.each_dim[1] + body.each_dim[2])
+    if style is not None:      # validated before the first launch, too; the body half only
+        rows_sub = [0] * B
+        for k, i in enumerate(order):
+            rows_sub[i] = int(tab["mfcc_rows"][k]) // 4
+        style = _lib.style_block(style, rows_sub, body.num_classes, order, who="whole_body_clips", ids=ids)
     dev = body.generator._dev()
     # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
     wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
@@ -222,7 +230,7 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
         side.wait_stream(cur)
     with torch.cuda.stream(side):
         _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling,
-                                               given=given, given_poses=given_poses, given_keep=given_keep)
+                                               given=given, given_poses=given_poses, given_keep=given_keep, style=style)
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

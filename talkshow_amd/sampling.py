@@ -177,6 +177,30 @@ def given_logprob(row, code, record=None):
     return logprob(row, code, record)
 
 
+def style_rows(weights, table):
+    """The rule of "speaker style" (include/talkshow_hip.h), restated: weights (..., NC) float, table (NC, W) float32 — one layer's
+    class_cond_embedding — -> (..., W) float32, the class-conditioning vector of every weight row: over c ascending, every weight that is
+    not 0 contributes t = w[c] * table[c], product and sum each rounded to float32 (numpy.float32 arithmetic: no fused multiply-add); the
+    first contribution starts the sum; a zero weight contributes nothing and its table row is not read (it may hold NaN); +0.0 where every
+    weight is 0.  A one-hot row therefore returns its table row bit for bit (-0.0 included).  style_rows_kernel computes exactly this."""
+    w = np.asarray(weights, np.float32)
+    table = np.asarray(table, np.float32)
+    if w.ndim < 1 or table.ndim != 2 or w.shape[-1] != table.shape[0]:
+        raise ValueError(f"style_rows: weights (..., NC) and table (NC, W) disagree: {w.shape} and {table.shape}")
+    flat = w.reshape(-1, w.shape[-1])
+    out = np.zeros((flat.shape[0], table.shape[1]), np.float32)
+    with np.errstate(all="ignore"):
+        for m in range(flat.shape[0]):
+            acc = None
+            for c in range(flat.shape[1]):
+                if flat[m, c] != 0:
+                    t = (flat[m, c] * table[c]).astype(np.float32)      # float32 * float32, rounded once
+                    acc = t if acc is None else (acc + t).astype(np.float32)
+            if acc is not None:
+                out[m] = acc
+    return out.reshape(w.shape[:-1] + (table.shape[1],))
+
+
 def keep_forced(G, keep, r, j):
     """The rule of "kept positions" (include/talkshow_hip.h) for one sampler launch: G (B,) given rows per clip slot, keep (B,H,2) mask of
     kept positions or None, (r, j) the launch's row and column -> (B,) bool: clip b is FORCED at (r, j) iff 2 r + j < 2 G_b and (keep is None
