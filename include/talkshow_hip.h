@@ -189,7 +189,7 @@ typedef struct ts_sampling {
  * synchronises, any number of calls may be queued — captures nothing.  BUDGET: a host that alternates passes with and without a table on
  * one stream shares the 16 chunk graphs (and the 8 whole-call graphs) kept per stream between the two kinds.
  * Out of scope: ts_pixelcnn_stream_* (and BodyStream), ts_pixelcnn_v_*, the face generator, repetition penalties or any control that
- * reads earlier codes.  Log-probabilities (below) share the scope: the streaming sessions, ts_pixelcnn_v_* and the face generator return
+ * reads earlier codes.  (A STATIC per-clip bias on the codes, allow-lists and bans included, is in scope: "code bias" below.)  Log-probabilities (below) share the scope: the streaming sessions, ts_pixelcnn_v_* and the face generator return
  * none, clips of different lengths are not SCORED in one pass, and scoring runs the rows one after the other as the decode does (given
  * the codes, teacher-forced rows do not depend on each other and could run as large GEMMs: other work, with other bits). */
 /* Host only: the validation every _ctl entry applies before anything is launched.  n records for vocabulary V, 1 <= V <= 8191 (a larger V
@@ -598,6 +598,70 @@ int ts_style_check(const float *w_host, long n, int NC);
 int ts_op_style_rows(ts_ctx *ctx, const float *tables_dev, int NL, int NC, int W, const float *weights_dev, int M, float *out_dev,
                      void *stream);
 
+/* ---- code bias: per-clip bias and allow-lists on the codes ----------------------------------------------------------------------------------
+ * No counterpart in the reference, which draws from the raw softmax.  A clip of a mixed pass may bring a TABLE b[2][V] of float32: row 0 is
+ * added to the logits of the body column, row 1 to those of the hand column; the table is constant over the clip's code rows.  Every entry
+ * is either -inf (the code is BANNED) or finite with |b_v| <= 1e30; NaN and +inf are refused; each of the two rows holds at least one entry
+ * above -inf (ts_code_bias_check; V <= 8191 as for the controls).  An allow-list is a table of 0 and -inf.
+ * THE RULE is a step 0 in front of steps 1-5 of ts_sampling, and one sentence added to the kept set:
+ *  0. l'_v = l_v + b_v, ONE IEEE fp32 addition.  Steps 1-5 and the log-probability rule then run on l' unchanged, operation for operation:
+ *     the maximum, d_v, det_expf, the ranking, top-k, the integer masses, top-p, the inverse CDF and d_c - log S.  The logits OUTPUT (the
+ *     operator's row copy) stays the network's l.
+ *  Kept set.  A token with l'_v = -inf is never kept, whatever top_k and top_p say and also under a neutral record.  (The sentence is
+ *     needed: w_v = det_expf(-inf) = 0 already, key(-inf) ranks lowest and floor(0 * 2^31) = 0, so sums and masses do not move — but with
+ *     such a token "kept" the two fallbacks of step 5, the chunk's and the row's highest kept token, can return it at u = 1 - 2^-24.  With
+ *     banned tokens out of the kept set the draw never returns one.)
+ *  Log-probabilities.  A drawn code gets d_c - log S under the biased, filtered distribution.
+ *  Given codes.  A given or kept code that the bias bans is still TAKEN, as a code the filters remove is; its log-probability is -inf
+ *     (d_c = -inf, and the code is not kept).
+ *  Bit identity.  A clip without a table (index -1) executes the arithmetic of the sampler with controls as it was: nothing is added, its
+ *     bits do not move.  An all-zero table gives the same CODES; its log-probabilities may differ in the sign of a zero only
+ *     (-0 + 0 = +0: a logit -0 becomes +0, so a d_c or a result that was -0 may come out as +0).
+ *  Scope.  The bias is a sampling control and shares the table's scope: TS_SAMPLE_UNIFORMS and TS_SAMPLE_PHILOX are accepted;
+ *     TS_SAMPLE_GREEDY and TS_TEACHER_FORCED are refused with the table's message (per-clip greedy is top_k = 1).  A pass that brings a
+ *     bias and no sampling table runs on neutral records, which compute the plain sampler's bits.  A uniform and a Philox number are
+ *     consumed exactly as without a bias: a clip's random stream does not depend on its table.
+ * talkshow_amd/sampling.py restates it (biased, keep_mask_bias, sample_bias).
+ * The entries: the _style sibling of each family plus `const float *bias_dev, int n_bias, const int32_t *bias_index_host` ahead of the
+ * stream.  bias_dev is (n_bias, 2, V) float32 on the device, 1 <= n_bias <= B (clips that share a table share one copy);
+ * bias_index_host (B,) in slot order holds every clip's table, or -1 for a clip without one.  bias_dev == NULL: the _style entry, launch
+ * for launch.  The tables' content is NOT validated on the device; ts_code_bias_check is the host-side rule.
+ * Staging and graphs.  Tables and index are copied into the stream's work buffers in stream order ahead of the pass (one device-to-device
+ * copy; the index travels as kernel arguments): captured samplers read work memory only, no host memory is read after the call returns,
+ * nothing synchronises.  The samplers are kernels of their own (sample_ctl_bias_kernel / sample_ctl_bias_given_kernel) on graph keys of
+ * their own: bit 5 (value 32) of the sixth key field.  Neither the tables' content nor n_bias is in the key: a repeated pass with other
+ * tables captures nothing.  The table buffer is sized for one table per clip of the work set's clip CAPACITY (8 V bytes per clip), so it
+ * NEVER MOVES between the passes of one capacity; the capacity grows only where every work buffer grows, and that drops all graphs of
+ * the stream.  Passes without a bias launch the kernels and find the graphs they always did.
+ * Out of scope: per-row bias tracks; repetition penalties or anything that reads earlier codes; the streaming sessions
+ * (ts_pixelcnn_stream_*, BodyStream); ts_pixelcnn_v_*; the face generator; the scoring entries (score_clips / score_motion_clips take no
+ * sampling table either). */
+int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                    const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                    const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                    const int32_t *given_rows_dev, const uint8_t *keep_dev, const float *style_dev, int style_rows,
+                                    const float *bias_dev, int n_bias, const int32_t *bias_index_host, void *stream);
+int ts_body_pixel_infer_mixed_bias(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                   const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                   const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                   float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                   const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep_dev,
+                                   const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                   const int32_t *bias_index_host, void *stream);
+int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                         const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                         const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                         float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                         const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                         const uint8_t *keep_dev, const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                         const int32_t *bias_index_host, void *stream);
+/* Host only: the rule above on n_tables tables (n_tables, 2, V), 1 <= V <= 8191; 0, or an error that names the table, the column and the
+ * code.  Python calls it before anything is launched. */
+int ts_code_bias_check(const float *tables_host, int n_tables, int V);
+/* Host only: 1 <= n_bias <= B and every index is -1 or in [0, n_bias); every entry that takes tables applies it before its first launch. */
+int ts_code_bias_index_check(const int32_t *bias_index_host, int B, int n_bias);
+
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.
  * Either output may be NULL: recon_dev == NULL is the encode-only form (VQVAE.encode of both parts, the latents
@@ -660,6 +724,16 @@ int ts_op_sample_given(ts_ctx *ctx, const float *logits_dev, int B, int V, int m
 int ts_op_sample_keep(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
                       int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
                       const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, void *stream);
+/* One launch of the samplers under a "code bias": ts_op_sample_keep's arguments, then kept_dev (B,V) uint8 or NULL (1 for the tokens of
+ * the kept set, banned tokens out) and logits_copy_dev (B,V) or NULL (the launch's row copy: the network's l, not l'), then bias_dev
+ * (n_bias,2,V), n_bias, bias_index_host (B) (-1: the row has no table and computes ts_op_sample_ctl's bits) and column (0 body, 1 hand).
+ * mode uniforms or Philox; ctl_host == NULL: neutral records.  given_rows_host == NULL (then keep_dev and given_dev are NULL too): the
+ * launch without given rows, sample_ctl_bias_kernel; otherwise sample_ctl_bias_given_kernel.  The vector path is taken for V = 2048 on
+ * 16-byte aligned logits and tables. */
+int ts_op_sample_bias(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                      int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
+                      const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, uint8_t *kept_dev,
+                      float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column, void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

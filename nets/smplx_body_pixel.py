@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None):
+                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -116,16 +116,19 @@ class TrainWrapper(TrainWrapperBaseClass):
         block (`generate_clips`, `ts_body_pixel_infer_mixed_keep`).  None: nothing changes.
         style: float speaker weights in place of the integer ids — per clip None, an (NC,) row or an (H,NC) track, or one (NC,) / (B,NC)
         array for all clips (`generate_clips`, `ts_body_pixel_infer_mixed_style`).  None: nothing changes.
+        code_bias: a per-clip bias / allow-list on the codes — one (2, V) table for all clips, or per clip None, a (2, V) table or a
+        {"body", "hand"} dict (`generate_clips`, `ts_body_pixel_infer_mixed_bias`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
-        if sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None or style is not None:
+        if (sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None or style is not None
+                or code_bias is not None):
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
                                        _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
-                                       given_poses=given_poses, given_keep=given_keep, style=style)
+                                       given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -224,7 +227,7 @@ class TrainWrapper(TrainWrapperBaseClass):
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
                        _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None,
-                       style=None):
+                       style=None, code_bias=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -272,7 +275,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         other conditioning rows (same graphs); otherwise per-clip rows are repeated into tracks and the pass stages every chunk's rows
         (graph keys of its own).  Orthogonal to every other keyword; given rows run under the style too, so handing back the head of an
         earlier decode WITH THE SAME STYLE returns that decode.  A wrong shape, a wrong NC or a non-finite weight raises ValueError naming
-        the clip before anything is launched (`ts_body_pixel_infer_mixed_style` / `_poses_style`).  None: nothing changes."""
+        the clip before anything is launched (`ts_body_pixel_infer_mixed_style` / `_poses_style`).  None: nothing changes.
+        code_bias: WHICH CODES A CLIP MAY USE, and how likely (talkshow_hip.h, "code bias"; `_lib.code_bias_block`) — one (2, V) float
+        table for all clips, or a list in submission order with, per clip, None (the clip's bits do not move), a (2, V) table or a dict
+        {"body": (V,), "hand": (V,)} (a missing key: zeros).  Row 0 is added to the logits of the body column and row 1 to those of the
+        hand column, ahead of temperature / top-k / top-p (one fp32 addition; `sampling.biased`); -inf BANS a code: it is never drawn.
+        `sampling.allow_bias(codes, V)` makes the allow-list of the codes in an (n, 2) array — `code_bias_from_motion(poses)` that of
+        example motion ("stay inside the vocabulary of this seated speaker") —, `sampling.ban_bias` its complement.  Entries that are the
+        same object travel once.  Log-probabilities are those of the biased, filtered distribution.  Given rows are taken whatever the
+        table says (a banned given code gets -inf).  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only (per-clip greedy is top_k = 1); a clip's
+        random numbers do not depend on its table.  Orthogonal to every other keyword.  A wrong shape, a NaN, a +inf, a value beyond
+        1e30 or a column without an allowed code raises ValueError naming the clip before anything is launched
+        (`ts_body_pixel_infer_mixed_bias` / `_poses_bias`).  None: nothing changes."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -314,6 +328,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         if gblock is None and pblock is None:
             kblock = None
         sblock = _lib.style_block(style, [t // 4 for t in lens], self.num_classes, order, who="generate_clips", ids=ids)   # slot order, like the records
+        btab, bidx = _lib.code_bias_block(code_bias, B, self.generator.input_dim, order, who="generate_clips", mode=mode)   # slot order, too
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -353,23 +368,29 @@ class TrainWrapper(TrainWrapperBaseClass):
         if kblock is not None:
             from talkshow_amd.modules import upload
             kdev = upload(kblock, dev)
-        if sblock is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
+        if sblock is not None or btab is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
             from talkshow_amd.modules import upload
-            sdev = upload(sblock, dev)
+            sdev = upload(sblock, dev) if sblock is not None else None
+            tail = (_lib.dptr(sdev), int(sblock.shape[1]) if sblock is not None else 0)
+            poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_style, _lib.load().ts_body_pixel_infer_mixed_style
+            if btab is not None:
+                bdev = upload(btab, dev)
+                tail += (_lib.dptr(bdev), int(btab.shape[0]), bidx.ctypes.data_as(i32p))
+                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_bias, _lib.load().ts_body_pixel_infer_mixed_bias
             if pblock is not None and gblock is None:
                 pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_style(
+                _lib.check(poses_entry(
                     *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)),
-                    _lib.dptr(kdev), _lib.dptr(sdev), int(sblock.shape[1]), _lib.stream_ptr()))
+                    _lib.dptr(kdev), *tail, _lib.stream_ptr()))
             else:
                 gdev = None
                 if gblock is not None and pblock is not None:
                     gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
                 elif gblock is not None:
                     gdev = upload(gblock, dev)
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_style(
+                _lib.check(codes_entry(
                     *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), None if gdev is None else gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
-                    _lib.dptr(sdev), int(sblock.shape[1]), _lib.stream_ptr()))
+                    *tail, _lib.stream_ptr()))
         elif pblock is not None and gblock is None:
             from talkshow_amd.modules import upload
             pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
@@ -508,8 +529,20 @@ class TrainWrapper(TrainWrapperBaseClass):
             return encode_pair_masked(self.g_body, self.g_hand, pdev, upload(ptable, dev))     # (B, H_max, 2): P_max = 4 H_max
         return self._score_pass(mfcc_list, ids, "score_motion_clips", make, style=style)
 
+    def code_bias_from_motion(self, poses_list):
+        """The ALLOW-LIST of example motion: poses_list = list of (P_b, 129) pose clips in the wrapper's own pose layout (see
+        `generate_clips`; P_b >= 4) -> a (2, V) float32 table, 0 for every body / hand code the clips encode to and -inf for every other:
+        `code_bias=` of the decode entries ("stay inside the vocabulary of this reference motion").  One `ts_vqvae_encode_pair_masked` pass
+        on the device — the route `given_poses` takes — then `sampling.allow_bias` on the host (this call reads the codes back)."""
+        from talkshow_amd import sampling as S
+        from talkshow_amd.modules import encode_pair_masked, pad_pose_clips, upload
+        dev = self.generator._dev()
+        block, lens = pad_pose_clips(list(poses_list), dev, "code_bias_from_motion", self.each_dim[1] + self.each_dim[2])
+        codes = encode_pair_masked(self.g_body, self.g_hand, block, upload(lens, dev)).cpu().numpy()      # -1 beyond a clip's own rows
+        return S.allow_bias(codes.reshape(-1, 2), self.generator.input_dim)
+
     def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
-                         given_poses=None, given_keep=None, style=None):
+                         given_poses=None, given_keep=None, style=None, code_bias=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
@@ -518,7 +551,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         given: `_lib.given_block(...)` in ROW order — (block, table), both numpy — or None.
         given_poses: `_lib.given_pose_block(...)` in ROW order — (block, table) — or None; with `given` too, no clip is in both.
         given_keep: `_lib.given_keep_block(...)` in ROW order — the (B, H_max, 2) uint8 mask of kept positions — or None.
-        style: `_lib.style_block(...)` in ROW order — the (B, 1 or H_max, NC) float32 speaker weights that take the place of `ids` — or None."""
+        style: `_lib.style_block(...)` in ROW order — the (B, 1 or H_max, NC) float32 speaker weights that take the place of `ids` — or None.
+        code_bias: `_lib.code_bias_block(...)` in ROW order — (tables (NB, 2, V) float32, index (B,) int32), both numpy — or None."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -544,10 +578,26 @@ class TrainWrapper(TrainWrapperBaseClass):
             if given_keep.shape != (B, H_max, 2):
                 raise ValueError(f"infer_padded_wav: the mask of kept positions must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given_keep.shape}")
             kdev = upload(given_keep, dev)
-        if style is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
-            if style.ndim != 3 or style.shape[0] != B or style.shape[1] not in (1, H_max):
-                raise ValueError(f"infer_padded_wav: the style block must be (B, 1 or H_max, NC) = ({B}, 1 or {H_max}, NC), got {style.shape}")
-            sdev = upload(np.ascontiguousarray(style, dtype=np.float32), dev)
+        if code_bias is not None and code_bias[0] is None:
+            code_bias = None
+        if style is not None or code_bias is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
+            sdev = None
+            if style is not None:
+                if style.ndim != 3 or style.shape[0] != B or style.shape[1] not in (1, H_max):
+                    raise ValueError(f"infer_padded_wav: the style block must be (B, 1 or H_max, NC) = ({B}, 1 or {H_max}, NC), got {style.shape}")
+                sdev = upload(np.ascontiguousarray(style, dtype=np.float32), dev)
+            tail = (_lib.dptr(sdev), int(style.shape[1]) if style is not None else 0)
+            poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_style, _lib.load().ts_body_pixel_infer_mixed_style
+            if code_bias is not None:
+                btab, bidx = code_bias
+                V = self.generator.input_dim
+                if btab.ndim != 3 or btab.shape[1:] != (2, V) or btab.dtype != np.float32 or bidx.shape != (B,) or bidx.dtype != np.int32:
+                    raise ValueError(f"infer_padded_wav: the code bias is (tables (NB, 2, {V}) float32, index ({B},) int32), got "
+                                     f"{btab.dtype} {btab.shape} and {bidx.dtype} {bidx.shape}")
+                bdev = upload(np.ascontiguousarray(btab), dev)
+                bidx = np.ascontiguousarray(bidx)
+                tail += (_lib.dptr(bdev), int(btab.shape[0]), bidx.ctypes.data_as(i32p))
+                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_bias, _lib.load().ts_body_pixel_infer_mixed_bias
             ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
             if given is not None and given[0].shape != (B, H_max, 2):
                 raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
@@ -556,18 +606,18 @@ class TrainWrapper(TrainWrapperBaseClass):
             if given_poses is not None and given is None:
                 pblock, ptable = given_poses
                 pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_style(
+                _lib.check(poses_entry(
                     *args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)),
-                    _lib.dptr(kdev), _lib.dptr(sdev), int(style.shape[1]), _lib.stream_ptr()))
+                    _lib.dptr(kdev), *tail, _lib.stream_ptr()))
             else:
                 gdev = gtable = None
                 if given is not None and given_poses is not None:
                     gdev, gtable = self._stage_given(given[0], given[1], given_poses[0], given_poses[1], dev)
                 elif given is not None:
                     gdev, gtable = upload(given[0], dev), given[1]
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_style(
+                _lib.check(codes_entry(
                     *args, ctl, n_ctl, None, _lib.dptr(gdev), None if gdev is None else gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
-                    _lib.dptr(sdev), int(style.shape[1]), _lib.stream_ptr()))
+                    *tail, _lib.stream_ptr()))
             return codes, poses, lens_host
         if given_poses is not None:
             pblock, ptable = given_poses
@@ -604,7 +654,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None, given_poses=None, given_keep=None, style=None):
+                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
@@ -614,7 +664,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         in submission order (a recording's code rows: `frontend.mixed_tables(ns, sr)["code_rows"]`).  given_poses: as for `generate_clips`,
         one entry per recording.  given_keep: as for `generate_clips` — which positions of a recording's given rows are taken (None, "body",
         "hand", a mask; one entry per recording, or one for all).  style: as for `generate_clips` — float speaker weights in place of the
-        ids, per recording None, an (NC,) row or an (H_b,NC) track (H_b the recording's code rows), or one array for all."""
+        ids, per recording None, an (NC,) row or an (H_b,NC) track (H_b the recording's code rows), or one array for all.  code_bias: as for
+        `generate_clips` — which codes a recording may use: one (2, V) table for all, or per recording None, a table or a dict."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -644,6 +695,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         if style is not None:
             style = _lib.style_block(style, [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]], self.num_classes, order,
                                      who="generate_clips_from_wav", ids=ids)
+        if code_bias is not None:
+            code_bias = _lib.code_bias_block(code_bias, B, self.generator.input_dim, order, who="generate_clips_from_wav", mode=mode)
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -653,7 +706,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
         codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given,
-                                                    given_poses=given_poses, given_keep=given_keep, style=style)
+                                                    given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,
@@ -663,10 +716,19 @@ class TrainWrapper(TrainWrapperBaseClass):
 
         Extra keyword arguments understood here (ignored by the reference through **kwargs):
         `greedy=True` (argmax decode), `seed=int`, `uniforms=(B,H,2)`, and the sampling controls `temperature=`, `top_k=`, `top_p=`
-        (one record for all B samples; `generate_batch(..., sampling=)`).  The streaming session behind `continuity=True` takes no
+        (one record for all B samples; `generate_batch(..., sampling=)`), and `code_bias=` — ONE (2, V) table (or {"body", "hand"} dict) for
+        all B samples: which codes the decode may use (`generate_clips`).  The streaming session behind `continuity=True` takes no
         controls yet: together they raise ValueError.
         '''
         assert self.args.infer, "train mode"
+        code_bias = kwargs.get('code_bias', None)
+        if code_bias is not None:
+            if continuity:
+                raise ValueError("infer_on_audio: the streaming session behind continuity=True takes no code bias")
+            if isinstance(code_bias, (list, tuple)):
+                raise ValueError("infer_on_audio: code_bias is ONE (2, V) table or dict for all B samples (generate_clips takes one per clip)")
+            mode_ = _lib.TS_SAMPLE_GREEDY if kwargs.get('greedy', False) else _lib.TS_SAMPLE_PHILOX
+            _lib.code_bias_block(code_bias, 1, self.generator.input_dim, who="infer_on_audio", mode=mode_)   # raises before the audio is read
         sampling = None
         if any(kwargs.get(k) is not None for k in ('temperature', 'top_k', 'top_p')):
             if continuity:
@@ -724,7 +786,7 @@ class TrainWrapper(TrainWrapperBaseClass):
                 pred_poses = torch.cat([part0, part1], dim=1).cpu().numpy()
             else:
                 self.audioencoder.eval()
-                _, poses = self.generate_batch(aud_feat, id, mode=mode, uniforms=uniforms, seed=seed, sampling=sampling)
+                _, poses = self.generate_batch(aud_feat, id, mode=mode, uniforms=uniforms, seed=seed, sampling=sampling, code_bias=code_bias)
                 pred_poses = poses.cpu().numpy()
 
         output = pred_poses

@@ -141,6 +141,17 @@ SIGNATURES = {
                                                    _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
     "ts_style_check": (_i, [C.POINTER(C.c_float), C.c_long, _i]),
     "ts_op_style_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    # code bias: the _style sibling of each family with bias_dev, n_bias, bias_index_host ahead of the stream; the host rules; one launch
+    "ts_pixelcnn_generate_mixed_bias": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
+                                             C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _vp]),
+    "ts_body_pixel_infer_mixed_bias": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                            _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _vp]),
+    "ts_body_pixel_infer_mixed_poses_bias": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
+                                                  _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _vp]),
+    "ts_code_bias_check": (_i, [C.POINTER(C.c_float), _i, _i]),
+    "ts_code_bias_index_check": (_i, [C.POINTER(C.c_int32), _i, _i]),
+    "ts_op_sample_bias": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
+                               _i, C.POINTER(C.c_int32), _i, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -566,6 +577,70 @@ def style_block(style, rows, NC, order=None, who="style", ids=None):
             block[k, :e.shape[0]] = e
             block[k, e.shape[0]:] = e[-1]
     return block
+
+
+def code_bias_block(code_bias, B, V, order=None, who="code_bias", mode=None):
+    """The `code_bias=` keyword of the decode entries -> (tables (NB, 2, V) float32, index (B,) int32), both numpy: what the `_bias` entries
+    take as bias_dev (after an upload), n_bias = NB and bias_index_host, the index in SLOT order; (None, None) for `code_bias=None`
+    (talkshow_hip.h, "code bias": l' = l + b ahead of the sampling rule, row 0 for the body column and row 1 for the hand column; -inf bans
+    a code).
+    code_bias: one (2, V) array for all clips; or a list in SUBMISSION order with, per clip, None (no table: the clip's bits do not move),
+    a (2, V) array, or a dict {"body": (V,), "hand": (V,)} in which a missing key means zeros.  Entries that are the SAME OBJECT share one
+    table (NB counts distinct objects).  order: sorted slot k holds submitted clip order[k].  A list of None only gives (None, None).
+    mode: the call's draw mode, if the caller wants the scope checked here too (greedy and teacher forced are refused as for a sampling table).
+    ValueError naming the SUBMITTED clip, before anything is launched, for a wrong shape, a NaN, a +inf, a finite value beyond 1e30 or a
+    column without an allowed code (`ts_code_bias_check`).  Pure host code; a device tensor is read back."""
+    if code_bias is None:
+        return None, None
+    if mode is not None and mode not in (TS_SAMPLE_UNIFORMS, TS_SAMPLE_PHILOX):      # the bias shares the sampling table's scope
+        raise ValueError(f"{who}: a code bias is a sampling control: sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip "
+                         f"greedy is top_k = 1)")
+    B, V = int(B), int(V)
+
+    def host(x):
+        return x.detach().cpu().numpy() if hasattr(x, "detach") else x
+    code_bias = host(code_bias)
+    if isinstance(code_bias, (np.ndarray, dict)):
+        code_bias = [code_bias] * B
+    if not isinstance(code_bias, (list, tuple)) or len(code_bias) != B:
+        raise ValueError(f"{who}: code_bias takes one entry per clip ({B}) — None, a (2, V) array or a dict with 'body' / 'hand' rows — or one "
+                         f"(2, V) array for all, got {type(code_bias).__name__}" + (f" of {len(code_bias)}" if isinstance(code_bias, (list, tuple)) else ""))
+    order = list(range(B)) if order is None else [int(i) for i in order]
+    if sorted(order) != list(range(B)):
+        raise ValueError(f"{who}: order must be a permutation of the {B} clips")
+    tables, seen, index_sub = [], {}, [-1] * B
+    for i, e in enumerate(code_bias):
+        if e is None:
+            continue
+        if id(e) in seen:
+            index_sub[i] = seen[id(e)]
+            continue
+        if isinstance(e, dict):
+            if not e or any(k not in ("body", "hand") for k in e):
+                raise ValueError(f"{who}: code_bias of clip {i}: a dict holds 'body' and / or 'hand' rows, got keys {sorted(map(str, e))}")
+            t = np.zeros((2, V), np.float32)
+            for j, k in enumerate(("body", "hand")):
+                if e.get(k) is not None:
+                    r = np.asarray(host(e[k]))
+                    if r.dtype.kind not in "fiub" or r.shape != (V,):
+                        raise ValueError(f"{who}: code_bias of clip {i}: the '{k}' row must be ({V},) numbers, got {r.dtype} {tuple(r.shape)}")
+                    t[j] = r
+        else:
+            t = np.asarray(host(e))
+            if t.dtype.kind not in "fiub" or t.shape != (2, V):
+                raise ValueError(f"{who}: code_bias of clip {i} must be a (2, {V}) array of numbers (row 0 body, row 1 hand), got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+            with np.errstate(over="ignore"):
+                t = np.ascontiguousarray(t, dtype=np.float32)
+        if load().ts_code_bias_check(t.ctypes.data_as(C.POINTER(C.c_float)), 1, V) != 0:
+            msg = load().ts_last_error().decode().replace("ts_code_bias_check: table 0, ", "")
+            raise ValueError(f"{who}: code_bias of clip {i}: {msg}")
+        seen[id(e)] = index_sub[i] = len(tables)
+        tables.append(t)
+    if not tables:
+        return None, None
+    index = np.asarray([index_sub[i] for i in order], np.int32)
+    return np.ascontiguousarray(np.stack(tables), dtype=np.float32), index
 
 
 def given_pose_block(given_poses, rows, order=None, who="given_poses", width=129):

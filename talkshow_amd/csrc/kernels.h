@@ -460,6 +460,12 @@ struct SampleCtlParams {
     unsigned char *kept;       // optional (B,V): 1 for the tokens the filters kept
     float *logprob;            // optional: the log-probability of the drawn code (talkshow_hip.h, "log-probabilities") at logprob[b * lp_stride]
     long lp_stride;
+    // "code bias" (talkshow_hip.h): bias (NB,2,V) fp32 tables, bias_index[b] the table of clip slot b or -1 (the clip has none and executes
+    // the arithmetic of a launch without tables), bias_col 0 (body) / 1 (hand): the row added to the logits ahead of step 1.  Read by the
+    // sample_ctl_bias kernels only; null for every other launch
+    const float *bias;
+    const int32_t *bias_index;
+    int bias_col;
 };
 // a histogram bin of the kernel holds count << 44 | mass with mass <= V * 2^31: V * 2^31 < 2^44 bounds the vocabulary (the tie counters' 16 bits
 // and the count field hold more); launch_sample_ctl and the host checks refuse anything above

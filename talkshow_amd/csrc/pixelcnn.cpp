@@ -95,6 +95,9 @@ struct ts_pixelcnn {
         DevBuf keep_int;                   // passes with a mask of kept positions: the mask bytes of ONE chunk, (B,rows,2) uint8 beside given_int
         DevBuf style_int;                  // passes with per-row speaker style: the class-conditioning rows of ONE chunk, [NL][CHUNK_ROWS][Bs][2D] fp32 (slabs Bs
                                            // clips apart, like CR); allocated by the first such pass, filled ahead of every chunk by style_rows_kernel
+        DevBuf bias_tab, bias_idx;         // passes with a code bias: the tables (NB,2,V) fp32 and the table index of every clip SLOT (int32, -1: none), both
+                                           // written in stream order ahead of the pass (what the captured samplers read).  bias_tab holds capB tables — a pass
+                                           // brings at most one per clip — so it moves only when ensure_work has dropped the graphs that read it
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
@@ -104,7 +107,8 @@ struct ts_pixelcnn {
         // log-probabilities into lp_int, bit 2 for a pass with given rows (EVERY chunk of such a pass runs the given variants of the samplers,
         // which read given_tab and given_int), bit 3 for a given pass that brings a mask of kept positions (every chunk's samplers then also
         // read keep_int; without the bit their mask pointer is null), bit 4 for a pass with per-row speaker style (the gate launches of every chunk
-        // read their conditioning rows from style_int in place of CR); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // read their conditioning rows from style_int in place of CR), bit 5 for a pass with a code bias (its samplers are the sample_ctl_bias
+        // kernels, which read bias_tab and bias_idx; neither the tables' content nor their number is part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -257,6 +261,7 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->given_tab.ensure((size_t)cb * sizeof(int)));
     TS_TRY(w->given_int.ensure((size_t)cb * CHUNK_ROWS * 2 * sizeof(int64_t)));
     TS_TRY(w->keep_int.ensure((size_t)cb * CHUNK_ROWS * 2));
+    TS_TRY(w->bias_idx.ensure((size_t)cb * sizeof(int32_t)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -308,6 +313,10 @@ struct RunCfg {
     // CHUNK_ROWS) as [NL][CHUNK_ROWS][slabB()][2D]; null: one conditioning row per clip for the whole call (the Work's CR)
     const float *style = nullptr;
     int style_r0 = 0;
+    // "code bias": the Work's bias_tab (NB,2,V) and bias_idx (slabB(),), or null: the samplers without tables.  With tables c.ctl is set too
+    // (neutral records when the call brought none)
+    const float *bias = nullptr;
+    const int32_t *bias_index = nullptr;
     // the class-conditioning rows of layer l for the gate launches of code row r (every such launch belongs to one row)
     const float *cls_rows(int l, int r, size_t D2) const {
         if (!style) return w->CR.f() + (size_t)l * slabB() * D2;
@@ -668,6 +677,9 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         gp.c.kept = nullptr;
         gp.c.logprob = lp;
         gp.c.lp_stride = (long)sH * 2;
+        gp.c.bias = c.bias;
+        gp.c.bias_index = c.bias_index;
+        gp.c.bias_col = j;
         gp.rows = c.given_rows;
         gp.given = c.given + (size_t)ro * 2 + j;
         gp.given_stride = (long)sH * 2;
@@ -681,6 +693,9 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         cp.kept = nullptr;
         cp.logprob = lp;
         cp.lp_stride = (long)sH * 2;
+        cp.bias = c.bias;
+        cp.bias_index = c.bias_index;
+        cp.bias_col = j;
         TS_HIP(launch_sample_ctl(cp, s));
     } else if (lp) {
         SampleLpParams q;
@@ -1050,8 +1065,8 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
 inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr, const unsigned char *keep = nullptr,
-                        const float *style = nullptr) {
-    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0) | (style ? 16 : 0);
+                        const float *style = nullptr, const float *bias = nullptr) {
+    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0) | (style ? 16 : 0) | (bias ? 32 : 0);
 }
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
@@ -1257,7 +1272,7 @@ constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
               uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, const int64_t *given, int given_max,
-              const unsigned char *keep, const float *style_track, const int *lens_dev, hipStream_t s) {
+              const unsigned char *keep, const float *style_track, const int *lens_dev, bool biased, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1272,6 +1287,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
         c.Bs = B;
         c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
         c.ctl = ctl;   // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
+        if (biased) c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);   // by slot, too
         if (given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
             c.given_rows = w->given_tab.i();
             c.given_src = given;
@@ -1303,7 +1319,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src, c.style)), uniforms, codes, logprob, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src, c.style, c.bias)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1510,6 +1526,105 @@ int ts_op_sample_keep(ts_ctx *ctx, const float *logits, int B, int V, int mode, 
     return 0;
 }
 
+// Host only ("code bias"): tables (n_tables,2,V) — every entry -inf or finite with |b| <= 1e30 (no NaN, no +inf), every row with at least
+// one entry above -inf, V within the controls' limit; the message names the table, the column and the code
+int ts_code_bias_check(const float *tables_host, int n_tables, int V) {
+    if (!tables_host || n_tables < 1 || V < 1) return fail("ts_code_bias_check: bad argument");
+    if (V > SAMPLE_CTL_MAX_V)
+        return fail("ts_code_bias_check: a code bias supports vocabularies of at most " + std::to_string(SAMPLE_CTL_MAX_V) + " classes, got V = " +
+                    std::to_string(V));
+    static const char *const col[2] = {"body", "hand"};
+    for (int t = 0; t < n_tables; ++t)
+        for (int j = 0; j < 2; ++j) {
+            const float *row = tables_host + ((size_t)t * 2 + j) * V;
+            const std::string where = "ts_code_bias_check: table " + std::to_string(t) + ", " + col[j] + " column";
+            bool any = false;
+            for (int v = 0; v < V; ++v) {
+                const float x = row[v];
+                if (std::isnan(x)) return fail(where + ": the bias of code " + std::to_string(v) + " is NaN");
+                if (std::isinf(x)) {
+                    if (x > 0) return fail(where + ": the bias of code " + std::to_string(v) + " is +inf (only -inf, a ban, is allowed)");
+                    continue;
+                }
+                if (std::fabs(x) > 1e30f) return fail(where + ": the bias of code " + std::to_string(v) + " exceeds 1e30 in magnitude");
+                any = true;
+            }
+            if (!any) return fail(where + ": every code is banned (-inf); a column needs at least one code it may use");
+        }
+    return 0;
+}
+
+// ts_op_sample_keep's launch under a "code bias" (kernel-level tests call it): bias (n_bias,2,V) device tables, bias_index_host (B,) the
+// table of every row or -1, column 0 / 1.  Without a sampling table the rows run on neutral records.  given_rows_host == NULL: no given
+// rows (sample_ctl_bias_kernel; given, keep unused); otherwise the given variant.  kept (optional, (B,V)): the kept bytes
+int ts_op_sample_bias(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                      uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
+                      const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
+                      const int32_t *bias_index_host, int column, void *stream) {
+    const char *who = "ts_op_sample_bias";
+    if (!ctx || !logits || !idx || !bias || !bias_index_host) return fail(std::string(who) + ": null argument");
+    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
+    if (column != 0 && column != 1) return fail(std::string(who) + ": column is 0 (body) or 1 (hand)");
+    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
+    if (given_rows_host) {
+        if (!given) return fail(std::string(who) + ": given rows need their codes");
+        if (position > 0x7ffffff0u) return fail(std::string(who) + ": position too large for a row table");
+        for (int b = 0; b < B; ++b)
+            if (given_rows_host[b] < 0) return fail(std::string(who) + ": given rows of row " + std::to_string(b) + " are negative");
+    } else if (keep || given) {
+        return fail(std::string(who) + ": given codes and their mask need the row table");
+    }
+    std::vector<SampleCtl> tab;
+    const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
+    TS_TRY(ctl_table(ctl_host ? ctl_host : &neutral, ctl_host ? n_ctl : 1, B, V, mode, who, tab));   // refuses greedy and teacher forced
+    TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf tok, dtab, drows, dbi;
+    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
+    TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
+    TS_TRY(dbi.ensure((size_t)B * sizeof(int32_t)));
+    TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
+    TS_HIP(launch_put_words(dbi.i(), bias_index_host, B, s));
+    SampleGivenParams gp;
+    std::memset(&gp, 0, sizeof(gp));
+    gp.c.s.logits = logits;
+    gp.c.s.B = B;
+    gp.c.s.V = V;
+    gp.c.s.mode = mode;
+    gp.c.s.uniforms = uniforms;
+    gp.c.s.u_stride = 1;
+    gp.c.s.seed = seed;
+    gp.c.s.clip_index0 = clip_index0;
+    gp.c.s.position = position;
+    gp.c.s.tok32 = tok.i();
+    gp.c.s.tok_stride = 1;
+    gp.c.s.codes = idx;
+    gp.c.s.code_stride = 1;
+    gp.c.s.logits_copy = logits_copy;
+    gp.c.s.copy_stride = V;
+    gp.c.ctl = static_cast<const SampleCtl *>(dtab.p);
+    gp.c.kept = kept;
+    gp.c.logprob = logprob;
+    gp.c.lp_stride = 1;
+    gp.c.bias = bias;
+    gp.c.bias_index = static_cast<const int32_t *>(dbi.p);
+    gp.c.bias_col = column;
+    if (given_rows_host) {
+        TS_TRY(drows.ensure((size_t)B * sizeof(int)));
+        TS_HIP(launch_put_words(drows.i(), given_rows_host, B, s));
+        gp.rows = drows.i();
+        gp.given = given;
+        gp.given_stride = 1;
+        gp.keep = keep;
+        gp.keep_stride = 1;
+        TS_HIP(launch_sample_given(gp, s));
+    } else {
+        TS_HIP(launch_sample_ctl(gp.c, s));
+    }
+    TS_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 // Host only ("speaker style"): every weight of a style block is finite; the first bad index is named
 int ts_style_check(const float *w_host, long n, int NC) {
     if (!w_host || n < 0 || NC < 1) return fail("ts_style_check: bad argument");
@@ -1594,6 +1709,32 @@ int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const
                                      int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                      const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
                                      int style_rows, void *stream) {
+    return ts_pixelcnn_generate_mixed_bias(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                           logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, nullptr, 0, nullptr, stream);
+}
+
+// Host only ("code bias"): what every entry that takes tables checks of their number and of the index table before anything is launched
+int ts_code_bias_index_check(const int32_t *bias_index_host, int B, int n_bias) {
+    if (!bias_index_host || B < 1) return fail("ts_code_bias_index_check: bad argument");
+    if (n_bias < 1 || n_bias > B)
+        return fail("code bias: a pass of " + std::to_string(B) + " clips brings 1 to " + std::to_string(B) + " tables (shared tables travel once), got " +
+                    std::to_string(n_bias));
+    for (int b = 0; b < B; ++b)
+        if (bias_index_host[b] < -1 || bias_index_host[b] >= n_bias)
+            return fail("code bias: the table index of clip " + std::to_string(b) + " is " + std::to_string(bias_index_host[b]) + ", not -1 (none) or in [0, " +
+                        std::to_string(n_bias) + ")");
+    return 0;
+}
+
+// the same pass under a "code bias" (talkshow_hip.h): bias_dev (n_bias,2,V) fp32 tables on the device, bias_index_host (B,) the table of every
+// clip in slot order or -1.  Tables and index are copied into the Work in stream order ahead of the pass; the samplers are the
+// sample_ctl_bias kernels on graph keys of their own (bit 5); a call without a sampling table runs on neutral records.  bias_dev == NULL:
+// the _style entry, launch for launch
+int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                    const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
+                                    int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host, void *stream) {
     (void)given_rows_dev;   // the table travels as kernel arguments from the host copy (see talkshow_hip.h)
     if (!p || (!label && !style) || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
@@ -1612,6 +1753,14 @@ int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const
     }
     std::vector<SampleCtl> tab;
     if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
+    if (bias_dev) {   // a sampling control with the table's scope; without a table the pass runs on neutral records (the plain sampler's bits)
+        if (!ctl_host) {
+            const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
+            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, "ts_pixelcnn_generate_mixed_bias", tab));
+        }
+        TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
+    }
+    const bool with_ctl = ctl_host || bias_dev;
     int given_max = 0;
     if (keep && !given) return fail("ts_pixelcnn_generate_mixed_keep: a mask of kept positions needs the given codes it selects from");
     if (given) {
@@ -1623,7 +1772,13 @@ int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));
-    if (ctl_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
+    if (with_ctl) TS_TRY(put_ctl_table(ctx, w, tab, s));
+    if (bias_dev) {   // n_bias <= B <= capB tables: the buffer follows capB alone (see Work::bias_tab); the index travels as kernel arguments
+        TS_TRY(w->bias_tab.ensure((size_t)w->capB * 2 * p->V * sizeof(float)));
+        MiscScope ms(ctx, s);
+        TS_HIP(hipMemcpyAsync(w->bias_tab.p, bias_dev, (size_t)n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
+        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), bias_index_host, B, s));
+    }
     if (given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
         MiscScope ms(ctx, s);
         TS_HIP(launch_put_words(w->given_tab.i(), given_rows_host, B, s));
@@ -1643,8 +1798,8 @@ int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const
         else TS_HIP(launch_iota_i64(static_cast<int64_t *>(w->clip_tab.p), B, 0, s));
     }
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
-                     logprob, given, given_max, keep, tracked ? style : nullptr, lens_dev, s));
+    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, with_ctl ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
+                     logprob, given, given_max, keep, tracked ? style : nullptr, lens_dev, bias_dev != nullptr, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0

@@ -1263,9 +1263,13 @@ __device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) 
 //          sums of step 5 as an unforced one does (the thread that owns the given code notes whether the filters kept it), then writes
 //          d_c - log S for a kept code and log(0) for a code the filters removed.  An unforced workgroup executes the arithmetic of the
 //          kernel without GIVEN, operation for operation.
-// Inlined into its eight __global__ entries; DESIGN.md §5 ("One body per sampler family") records what was compared against the two
-// separate kernel templates it replaces.
-template <bool FAST, bool LP, bool GIVEN>
+//   BIAS   "code bias" (talkshow_hip.h, step 0): a clip slot whose bias_index is not negative adds its table's row of this column to the
+//          logits, one fp32 addition per token, and runs every step on the sums l'; a token with l' = -inf is never kept.  The row copy
+//          stays the network's l.  The index is workgroup-uniform: a slot with -1 reads no table and executes the arithmetic of the
+//          kernel without BIAS, operation for operation.  BIAS = false compiles to what the body was before the flag existed.
+// Inlined into its __global__ entries (eight without BIAS, eight with); DESIGN.md §5 ("One body per sampler family") records what was
+// compared against the two separate kernel templates it replaces.
+template <bool FAST, bool LP, bool GIVEN, bool BIAS = false>
 __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride,
                                                 const unsigned char *keep, long keep_stride, float *sf, int *si, float &s_thr, int &s_last,
                                                 uint32_t *s_tie, ctl_u64 (*hist)[256]) {
@@ -1284,11 +1288,33 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     const int n = FAST ? 8 : max(v1 - v0, 0);
     float x[8];
     if constexpr (FAST) sample_load8(lg, v0, x);
+    // BIAS: the clip's row of this column, or null (workgroup-uniform: the index is one uniform load)
+    const float *bias = nullptr;
+    if constexpr (BIAS) {
+        const int t = cp.bias_index[b];
+        if (t >= 0) bias = cp.bias + ((long)t * 2 + cp.bias_col) * p.V;
+    }
+    [[maybe_unused]] float xb[8];
+    if constexpr (BIAS && FAST) {
+        if (bias) sample_load8(bias, v0, xb);   // beside the logits: both pairs of loads are in flight ahead of the row copy
+    }
     auto logit = [&](int k) -> float {
         if constexpr (FAST) return x[k];
+        else if constexpr (BIAS) return bias ? lg[v0 + k] + bias[v0 + k] : lg[v0 + k];
         else return lg[v0 + k];
     };
-    sample_copy_row(p, b, FAST, lg, x, v0, v1);
+    // BIAS: l' = -inf is out of the kept set whatever the record says (a neutral record included)
+    auto banned = [&](int k) -> bool {
+        if constexpr (BIAS) return bias && logit(k) == -INFINITY;
+        else return false;
+    };
+    sample_copy_row(p, b, FAST, lg, x, v0, v1);   // the network's l: step 0 comes behind the copy
+    if constexpr (BIAS && FAST) {
+        if (bias) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = x[k] + xb[k];
+        }
+    }
     if constexpr (GIVEN && !LP) {
         if (forced) {
             if (tid == 0) {
@@ -1330,7 +1356,7 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     uint32_t key[8], q[8];
     auto key_of = [&](int k) -> uint32_t {
         if constexpr (FAST) return key[k];
-        else return ctl_key(lg[v0 + k]);
+        else return ctl_key(logit(k));
     };
     auto q_of = [&](int k) -> uint32_t {
         if constexpr (FAST) return q[k];
@@ -1416,7 +1442,8 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         unsigned char *kd = cp.kept ? cp.kept + (long)b * p.V : nullptr;
 #pragma unroll 8
         for (int k = 0; k < n; ++k) {
-            const bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
+            bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
+            if constexpr (BIAS) kp = kp && !banned(k);
             if (kp) { s += weight(k); hi = v0 + k; }
             if (kd) kd[v0 + k] = kp ? 1 : 0;
             if constexpr (GIVEN && LP) {
@@ -1453,7 +1480,9 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         int jk = jk0, jp = jp0;
 #pragma unroll 8
         for (int k = 0; k < n; ++k) {
-            if (!sel || ctl_keep(S, key_of(k), jk, jp)) {
+            bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
+            if constexpr (BIAS) kp = kp && !banned(k);
+            if (kp) {
                 c += weight(k);
                 if (res < 0 && c > thr) res = v0 + k;   // the first crossing is latched
             }
@@ -1501,10 +1530,49 @@ __global__ __launch_bounds__(256) void sample_ctl_given_kernel(const SampleGiven
     sample_ctl_body<FAST, LP, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie, hist);
 }
 
+// "code bias": the same two entry families with BIAS = true, launched only for a run that brings tables (p.bias != null)
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_bias_kernel(const SampleCtlParams cp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, false, true>(cp, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist);
+}
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_bias_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, true, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie, hist);
+}
+// what a launch with tables needs beyond its sibling's checks; the vector path also needs 16-byte aligned table rows (V = 2048: every row
+// of an aligned block is)
+static bool sample_bias_ok(const SampleCtlParams &p) { return p.ctl && p.bias_index && (p.bias_col == 0 || p.bias_col == 1); }
+static bool sample_bias_fast(const SampleCtlParams &p) { return (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0; }
+
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
     if (!p.ctl || p.s.V < 1 || p.s.V > SAMPLE_CTL_MAX_V || (p.s.mode != TS_SAMPLE_UNIFORMS && p.s.mode != TS_SAMPLE_PHILOX)) return hipErrorInvalidValue;
     const long ls = p.s.logit_stride ? p.s.logit_stride : (long)p.s.V;
     const bool fast = p.s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s.logits) & 15) == 0;
+    if (p.bias) {
+        if (!sample_bias_ok(p)) return hipErrorInvalidValue;
+        const bool bfast = fast && sample_bias_fast(p);
+        if (p.logprob) {
+            if (bfast) hipLaunchKernelGGL((sample_ctl_bias_kernel<true, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((sample_ctl_bias_kernel<false, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+        } else if (bfast) {
+            hipLaunchKernelGGL((sample_ctl_bias_kernel<true, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((sample_ctl_bias_kernel<false, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.logprob) {
         if (fast) hipLaunchKernelGGL((sample_ctl_kernel<true, true>), dim3(p.s.B), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((sample_ctl_kernel<false, true>), dim3(p.s.B), dim3(256), 0, stream, p);
@@ -1521,7 +1589,7 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
     if (!p.rows || !p.given || s.V < 1) return hipErrorInvalidValue;
     if (s.mode != TS_SAMPLE_GREEDY && s.mode != TS_SAMPLE_UNIFORMS && s.mode != TS_SAMPLE_PHILOX) return hipErrorInvalidValue;
     if (!p.c.ctl) {
-        if (p.c.kept) return hipErrorInvalidValue;
+        if (p.c.kept || p.c.bias) return hipErrorInvalidValue;
         if (p.c.logprob) hipLaunchKernelGGL(sample_lp_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(sample_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
         return hipGetLastError();
@@ -1529,6 +1597,19 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
     if (s.V > SAMPLE_CTL_MAX_V || s.mode == TS_SAMPLE_GREEDY) return hipErrorInvalidValue;
     const long ls = s.logit_stride ? s.logit_stride : (long)s.V;
     const bool fast = s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(s.logits) & 15) == 0;
+    if (p.c.bias) {
+        if (!sample_bias_ok(p.c)) return hipErrorInvalidValue;
+        const bool bfast = fast && sample_bias_fast(p.c);
+        if (p.c.logprob) {
+            if (bfast) hipLaunchKernelGGL((sample_ctl_bias_given_kernel<true, true>), dim3(s.B), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((sample_ctl_bias_given_kernel<false, true>), dim3(s.B), dim3(256), 0, stream, p);
+        } else if (bfast) {
+            hipLaunchKernelGGL((sample_ctl_bias_given_kernel<true, false>), dim3(s.B), dim3(256), 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((sample_ctl_bias_given_kernel<false, false>), dim3(s.B), dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.c.logprob) {
         if (fast) hipLaunchKernelGGL((sample_ctl_given_kernel<true, true>), dim3(s.B), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((sample_ctl_given_kernel<false, true>), dim3(s.B), dim3(256), 0, stream, p);

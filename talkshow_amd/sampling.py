@@ -1,5 +1,5 @@
 """Numpy twin of the sampler with per-clip controls (`csrc/vq.hip::sample_ctl_kernel`; the rule: `include/talkshow_hip.h`, ts_sampling,
-steps 1-5).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
+steps 1-5, and "code bias": step 0 and the kept-set sentence, `biased` / `keep_mask_bias` / `sample_bias` below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
 bit for bit, so tests compare indices and kept sets for equality.  A record is (temperature, top_p, top_k), `_lib.sampling_record`'s form.
 
 The kept set is written here from its DEFINITION (sort the row, cumulative integer masses in rank order); the kernel finds the same set by
@@ -199,6 +199,104 @@ def style_rows(weights, table):
             if acc is not None:
                 out[m] = acc
     return out.reshape(w.shape[:-1] + (table.shape[1],))
+
+
+# ---- code bias (include/talkshow_hip.h, "code bias"; csrc/vq.hip: sample_ctl_body<., ., ., BIAS = true>) -------------------------------------
+
+def biased(row, bias=None):
+    """Step 0: l' = l + b, one fp32 addition per token; bias None: the row itself (nothing is added, so a -0 stays -0)."""
+    row = np.asarray(row, F32).reshape(-1)
+    if bias is None:
+        return row
+    return (row + np.asarray(bias, F32).reshape(-1)).astype(F32)
+
+
+def keep_mask_bias(logits, record, bias=None):
+    """Steps 0-4 for ONE row: `keep_mask` of l' under the record, and — the kept-set sentence — never a token with l' = -inf.  bias None:
+    `keep_mask(logits, record)`, nothing else."""
+    if bias is None:
+        return keep_mask(logits, record)
+    lb = biased(logits, bias)
+    return keep_mask(lb, record) & (lb != F32(-np.inf))
+
+
+def sample_bias(logits, u, records, bias, index, column):
+    """One launch of the samplers under a code bias, restated: logits (B,V), u (B,), records = None (neutral), one record or B, bias
+    (NB,2,V) tables, index (B,) the table of every row or -1, column 0 (body) / 1 (hand) -> (idx (B,) int64, kept (B,V) bool, logprob (B,)
+    float32).  A row with index -1 is `sample_ctl`'s row."""
+    logits = np.asarray(logits, F32)
+    B, V = logits.shape
+    if records is None:
+        records = (1.0, 1.0, 0)
+    if isinstance(records, tuple) and len(records) == 3 and not isinstance(records[0], (tuple, list)):
+        records = [records] * B
+    idx = np.zeros(B, np.int64)
+    kept = np.zeros((B, V), bool)
+    lp = np.zeros(B, F32)
+    for b in range(B):
+        t = int(index[b])
+        row_bias = None if t < 0 else np.asarray(bias, F32)[t, int(column)]
+        lb = biased(logits[b], row_bias)
+        kept[b] = keep_mask_bias(logits[b], records[b], row_bias)
+        idx[b] = draw(lb, u[b], records[b][0], kept[b])
+        lp[b] = logprob(lb, idx[b], records[b])
+    return idx, kept, lp
+
+
+def given_logprob_bias(row, code, record=None, bias=None):
+    """`given_logprob` under a code bias: the given code is taken whatever the table says; its log-probability is that of the code under
+    the biased, filtered distribution — -inf for a code the bias bans or the filters remove.  record None: a neutral record."""
+    if bias is None:
+        return given_logprob(row, code, record)
+    record = (1.0, 1.0, 0) if record is None else record
+    lb = biased(row, bias)
+    code = int(code)
+    if not 0 <= code < lb.size:
+        return F32(np.nan)
+    if not keep_mask_bias(row, record, bias)[code]:
+        with np.errstate(divide="ignore"):
+            return F32(np.log(np.float64(0.0)))
+    return logprob(lb, code, record)
+
+
+def _code_columns(codes, V):
+    if isinstance(codes, (tuple, list)) and len(codes) == 2 and not (np.ndim(codes[0]) == 0 and np.ndim(codes[1]) == 0):
+        cols = [np.asarray(codes[0], np.int64).reshape(-1), np.asarray(codes[1], np.int64).reshape(-1)]
+    else:
+        c = np.asarray(codes.detach().cpu().numpy() if hasattr(codes, "detach") else codes)
+        if c.ndim != 2 or c.shape[1] != 2 or c.dtype.kind not in "iu":
+            raise ValueError(f"codes must be an (n, 2) integer array or a pair of index lists (body, hand), got {c.dtype} {tuple(c.shape)}")
+        cols = [c[:, 0].astype(np.int64), c[:, 1].astype(np.int64)]
+    for j, c in enumerate(cols):
+        c = c[c >= 0]                                                     # -1 marks rows beyond a clip's own (decode outputs): not a code
+        if c.size and c.max() >= V:
+            raise ValueError(f"column {j} holds code {int(c.max())}, outside [0, {V})")
+        cols[j] = c
+    return cols
+
+
+def allow_bias(codes, V):
+    """ALLOW-LIST: codes (n, 2) integers (column 0 body, column 1 hand; -1 entries are skipped) or a pair (body indices, hand indices) ->
+    (2, V) float32 table, 0 for the codes that occur in a column and -inf for every other.  ValueError for a column without a code."""
+    V = int(V)
+    t = np.full((2, V), -np.inf, F32)
+    for j, c in enumerate(_code_columns(codes, V)):
+        if c.size == 0:
+            raise ValueError(f"allow_bias: column {j} allows no code")
+        t[j, c] = F32(0.0)
+    return t
+
+
+def ban_bias(codes, V):
+    """BAN-LIST, `allow_bias`'s complement: -inf for the codes that occur in a column, 0 for every other.  ValueError if a column bans
+    every code."""
+    V = int(V)
+    t = np.zeros((2, V), F32)
+    for j, c in enumerate(_code_columns(codes, V)):
+        t[j, c] = F32(-np.inf)
+        if not np.isfinite(t[j]).any():
+            raise ValueError(f"ban_bias: column {j} bans every code")
+    return t
 
 
 def keep_forced(G, keep, r, j):
