@@ -834,7 +834,9 @@ void ts_smplx_destroy(ts_smplx *m);
 /* J + n_extra + n_lmk (127 for the reference's model) */
 int ts_smplx_num_joints(const ts_smplx *m);
 /* rows_dev (N,row_ld): pose rows, expression coefficients at columns [expr_off, expr_off + n_expr); betas_dev (n_betas) shared
- * by all rows, or (N,n_betas) when betas_per_row != 0 -> joints_dev (N, num_joints, 3) and, if not NULL, verts_dev (N,V,3). */
+ * by all rows, or (N,n_betas) when betas_per_row != 0 -> joints_dev (N, num_joints, 3) and, if not NULL, verts_dev (N,V,3).
+ * A row must hold every column the model reads: row_ld >= max(pose_src_offset) + 3, expr_off >= 0 and, for n_expr > 0,
+ * expr_off + n_expr <= row_ld; anything else is an error and nothing is launched (ts_smplx_create refuses a negative pose_src_offset). */
 int ts_smplx_forward(ts_smplx *m, const float *betas_dev, int betas_per_row, const float *rows_dev, int row_ld, int expr_off,
                      int64_t N, float *joints_dev, float *verts_dev, void *stream);
 

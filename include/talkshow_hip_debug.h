@@ -268,6 +268,31 @@ int ts_debug_mfcc_db(ts_mfcc *m, float *mel, const int32_t *frames_dev, int B, i
 /* mel (B T, 256) -> feat (B T, 64): the orthonormal DCT-II on conv_gemm_f32. */
 int ts_debug_mfcc_dct(ts_mfcc *m, const float *mel, const int32_t *frames_dev, int B, int T, float *feat, void *stream);
 
+/* Test aids: the stages of the SMPL-X forward pass of talkshow_hip.h (csrc/smplx.cpp, csrc/smplx.hip), one production launch each on `stream` with the handle's OWN
+ * tables (pose offsets and mean, the three packed GEMM operands, parents, sparse skinning weights, selector and landmark maps).  Device pointers
+ * the caller owns throughout; nothing is allocated or synchronized.  N <= 2^31 - 1 frames.
+ * ts_debug_smplx_dims (host only): out5 = {Kpad = the GEMM depth (n_betas + n_expr + 9 (J - 1) rounded up to 32), U = needed vertices, KW = bones
+ * kept per vertex, NJ = ts_smplx_num_joints, frames of one full-mesh chunk as ts_smplx_forward cuts them (for a call of more frames than that)}. */
+int ts_debug_smplx_dims(const ts_smplx *m, int32_t *out5);
+/* Host only: the U needed vertex ids in slot order (extra joints first, then landmark corners, each vertex once; {0} if the model has neither). */
+int ts_debug_smplx_need(const ts_smplx *m, int32_t *verts_out);
+/* rows (N, row_ld), betas (n_betas) or (N, n_betas) -> rot (N, J, 9) row-major rotation matrices, X (N, Kpad) = [betas | expression |
+ * R_j - I for j >= 1 | +0.0].  row_ld and expr_off are checked as ts_smplx_forward checks them (talkshow_hip.h). */
+int ts_debug_smplx_pose_prepare(ts_smplx *m, const float *betas, int betas_per_row, const float *rows, int row_ld, int expr_off, int64_t N,
+                                float *rot_out, float *X_out, void *stream);
+/* X (N, Kpad) -> which 0: the rest joints (N, 3 J) (the folded regressor); 1: the posed needed vertices (N, 3 U); 2: the posed mesh (N, 3 V)
+ * (with_vertices models only).  The GEMM on conv_gemm_f32 as ts_smplx_forward issues it. */
+int ts_debug_smplx_blend(ts_smplx *m, int which, const float *X, int64_t N, float *out, void *stream);
+/* rot (N, J, 9), jrest (N, 3 J) -> G (N, J, 12) world transforms [R | t] by rows, A (N, J, 12) = [G.R | G.t - G.R J_j], joints (N, NJ, 3):
+ * entries 0 .. J - 1 of every frame are written, the rest left alone. */
+int ts_debug_smplx_rigid_chain(ts_smplx *m, const float *rot, const float *jrest, int64_t N, float *G_out, float *A_out, float *joints_out,
+                               void *stream);
+/* Linear blend skinning: vposed (N, 3 n), A (N, J, 12) -> out (N, 3 n); n = U with the needed vertices' weights (full == 0), V with the mesh's. */
+int ts_debug_smplx_skin(ts_smplx *m, int full, const float *vposed, const float *A, int64_t N, float *out, void *stream);
+/* vs (N, U, 3) skinned needed vertices -> entries J .. NJ - 1 of joints (N, NJ, 3): extra joints (copies), then landmarks (barycentric).
+ * Launches nothing for a model without either. */
+int ts_debug_smplx_joints_tail(ts_smplx *m, const float *vs, int64_t N, float *joints, void *stream);
+
 /* Test aid: how many captured hipGraphs the PixelCNN keeps for `stream` right now (whole-call graphs of repeated shapes + the chunk
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */
 int ts_debug_pixelcnn_graphs(ts_pixelcnn *pix, void *stream);

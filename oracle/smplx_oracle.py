@@ -21,10 +21,12 @@ SMPLX_PARENTS = np.asarray(
      21, 40, 41, 21, 43, 44, 21, 46, 47, 21, 49, 50, 21, 52, 53], dtype=np.int64)
 
 
-def synthetic_model(seed=0, V=512, n_betas=300, n_expr=100, n_extra=21, n_lmk=51, max_bones=4):
+def synthetic_model(seed=0, V=512, n_betas=300, n_expr=100, n_extra=21, n_lmk=51, max_bones=4, all_bones_vertex=None, shared=0):
     """Random model parameters with the real SMPL-X's structure and value ranges (metres): a point cloud around a stick
     figure, small shape / pose blend shapes, a sparse non-negative joint regressor with rows summing to 1, skinning weights
-    with <= `max_bones` bones per vertex summing to 1, a hand-pose mean, extra-joint vertex ids and landmark triangles."""
+    with <= `max_bones` bones per vertex summing to 1, a hand-pose mean, extra-joint vertex ids and landmark triangles.
+    all_bones_vertex: that vertex is weighted on every bone.  shared: landmark triangle i < shared takes extra joint i's vertex as its
+    first corner and, for i >= 1, triangle i - 1's last corner as its second: vertices that several joint-list entries use."""
     rng = np.random.default_rng([seed, V])
     J = SMPLX_PARENTS.shape[0]
     # rest joints: children offset from their parents
@@ -49,9 +51,19 @@ def synthetic_model(seed=0, V=512, n_betas=300, n_expr=100, n_extra=21, n_lmk=51
     pose_mean = np.zeros(J * 3)
     pose_mean[25 * 3:] = rng.normal(0, 0.15, 30 * 3)                      # left / right hand means (flat_hand_mean=False)
     extra_idx = rng.choice(V, n_extra, replace=False)
-    lmk_faces = np.stack([rng.choice(V, 3, replace=False) for _ in range(n_lmk)])   # faces_tensor[lmk_faces_idx]
+    if n_lmk:
+        lmk_faces = np.stack([rng.choice(V, 3, replace=False) for _ in range(n_lmk)])   # faces_tensor[lmk_faces_idx]
+    else:
+        lmk_faces = np.zeros((0, 3), np.int64)
     bary = rng.random((n_lmk, 3))
     bary /= bary.sum(1, keepdims=True)
+    if all_bones_vertex is not None:
+        w = np.random.default_rng([seed, V, 1]).random(J) + 0.1
+        lbs_weights[all_bones_vertex] = w / w.sum()
+    for i in range(shared):
+        lmk_faces[i, 0] = extra_idx[i]
+        if i >= 1:
+            lmk_faces[i, 1] = lmk_faces[i - 1, 2]
     return dict(v_template=v_template, shapedirs=shapedirs, posedirs=posedirs, J_regressor=J_regressor,
                 parents=SMPLX_PARENTS.copy(), lbs_weights=lbs_weights, pose_mean=pose_mean, extra_idx=extra_idx,
                 lmk_faces=lmk_faces, lmk_bary=bary, n_betas=n_betas, n_expr=n_expr)
@@ -77,23 +89,45 @@ def full_pose_from_rows(rows):
     return full, rows[:, 165:265]
 
 
-def smplx_forward(model, betas, rows):
-    """SMPLX.forward(...)['joints'] and ['vertices'] for TalkSHOW rows: betas (n_betas,) or (N,n_betas), rows (N,265) ->
-    joints (N, 55 + n_extra + n_lmk, 3), vertices (N,V,3), float64."""
+def pose_and_shape_from_rows(model, betas, rows, expr_off=165):
+    """TalkSHOW rows (N, >= 165 [+ expression]) and betas (n_betas,) or (N, n_betas) -> full pose with the hand mean added (N, 165),
+    shape coefficients [betas | expression] (N, S)."""
     rows = np.asarray(rows, np.float64)
     N = rows.shape[0]
-    full_pose, expr = full_pose_from_rows(rows)
+    full_pose, _ = full_pose_from_rows(rows)
     full_pose = full_pose + model["pose_mean"][None]
-    betas = np.broadcast_to(np.asarray(betas, np.float64).reshape(-1, model["n_betas"]), (N, model["n_betas"]))
-    shape = np.concatenate([betas, expr[:, :model["n_expr"]]], axis=1)                       # (N,S)
-    v_shaped = model["v_template"][None] + np.einsum("bl,mkl->bmk", shape, model["shapedirs"])
-    J = np.einsum("bik,ji->bjk", v_shaped, model["J_regressor"])                            # (N,55,3)
-    nj = J.shape[1]
+    betas = np.zeros((N, 0)) if model["n_betas"] == 0 else \
+        np.broadcast_to(np.asarray(betas, np.float64).reshape(-1, model["n_betas"]), (N, model["n_betas"]))
+    expr = rows[:, expr_off:expr_off + model["n_expr"]]
+    return full_pose, np.concatenate([betas, expr], axis=1)
+
+
+def rodrigues_pose_feature(full_pose):
+    """full pose (N, 3 J) -> R (N, J, 3, 3), pose feature (N, 9 (J - 1)) = R_j - I for j >= 1."""
+    N, nj = full_pose.shape[0], full_pose.shape[1] // 3
     R = batch_rodrigues(full_pose.reshape(-1, 3)).reshape(N, nj, 3, 3)
-    pose_feature = (R[:, 1:] - np.eye(3)).reshape(N, -1)
-    v_posed = v_shaped + (pose_feature @ model["posedirs"]).reshape(N, -1, 3)
-    # batch_rigid_transform
-    parents = model["parents"]
+    return R, (R[:, 1:] - np.eye(3)).reshape(N, -1)
+
+
+def shaped_vertices(model, shape):
+    """blend_shapes: shape (N, S) -> v_shaped (N, V, 3)."""
+    return model["v_template"][None] + np.einsum("bl,mkl->bmk", shape, model["shapedirs"])
+
+
+def posed_vertices(model, v_shaped, pose_feature):
+    """v_shaped plus the pose blend shapes -> v_posed (N, V, 3)."""
+    return v_shaped + (pose_feature @ model["posedirs"]).reshape(v_shaped.shape[0], -1, 3)
+
+
+def rest_joints(model, v_shaped):
+    """vertices2joints: (N, V, 3) -> (N, J, 3)."""
+    return np.einsum("bik,ji->bjk", v_shaped, model["J_regressor"])
+
+
+def rigid_chain(R, J, parents):
+    """batch_rigid_transform: R (N, J, 3, 3), rest joints J (N, J, 3) -> G (N, J, 4, 4) world transforms, A (N, J, 4, 4) transforms
+    relative to the rest pose, posed joints (N, J, 3)."""
+    N, nj = J.shape[:2]
     rel = J.copy()
     rel[:, 1:] -= J[:, parents[1:]]
     T = np.zeros((N, nj, 4, 4))
@@ -108,10 +142,32 @@ def smplx_forward(model, betas, rows):
     Jh = np.concatenate([J, np.zeros((N, nj, 1))], -1)[..., None]                             # F.pad(joints, [0,0,0,1])
     A = G.copy()
     A[:, :, :, 3:] -= G @ Jh                                                                  # rel_transforms
-    Tv = np.einsum("vj,bjrc->bvrc", model["lbs_weights"], A)
-    vh = np.concatenate([v_posed, np.ones((N, v_posed.shape[1], 1))], -1)
-    verts = np.einsum("bvrc,bvc->bvr", Tv, vh)[..., :3]
-    extra = verts[:, model["extra_idx"]]                                                      # vertex_joint_selector
+    return G, A, posed_joints
+
+
+def skin(lbs_weights, A, v_posed):
+    """Linear blend skinning: lbs_weights (V, J), A (N, J, 4, 4), v_posed (N, V, 3) -> (N, V, 3)."""
+    Tv = np.einsum("vj,bjrc->bvrc", lbs_weights, A)
+    vh = np.concatenate([v_posed, np.ones((v_posed.shape[0], v_posed.shape[1], 1))], -1)
+    return np.einsum("bvrc,bvc->bvr", Tv, vh)[..., :3]
+
+
+def selector_and_landmarks(model, verts):
+    """vertex_joint_selector (picked vertices) and vertices2landmarks (barycentric) -> (N, n_extra, 3), (N, n_lmk, 3)."""
+    extra = verts[:, model["extra_idx"]]
     tri = verts[:, model["lmk_faces"]]                                                        # (N,L,3,3)
-    lmk = np.einsum("blfi,lf->bli", tri, model["lmk_bary"])                                   # vertices2landmarks
+    return extra, np.einsum("blfi,lf->bli", tri, model["lmk_bary"])
+
+
+def smplx_forward(model, betas, rows):
+    """SMPLX.forward(...)['joints'] and ['vertices'] for TalkSHOW rows: betas (n_betas,) or (N,n_betas), rows (N,265) ->
+    joints (N, 55 + n_extra + n_lmk, 3), vertices (N,V,3), float64."""
+    full_pose, shape = pose_and_shape_from_rows(model, betas, rows)
+    v_shaped = shaped_vertices(model, shape)
+    J = rest_joints(model, v_shaped)
+    R, pose_feature = rodrigues_pose_feature(full_pose)
+    v_posed = posed_vertices(model, v_shaped, pose_feature)
+    _, A, posed_joints = rigid_chain(R, J, model["parents"])
+    verts = skin(model["lbs_weights"], A, v_posed)
+    extra, lmk = selector_and_landmarks(model, verts)
     return np.concatenate([posed_joints, extra, lmk], axis=1), verts

@@ -234,6 +234,13 @@ SIGNATURES = {
     "ts_smplx_destroy": (None, [_vp]),
     "ts_smplx_num_joints": (_i, [_vp]),
     "ts_smplx_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp]),
+    "ts_debug_smplx_dims": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "ts_debug_smplx_need": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "ts_debug_smplx_pose_prepare": (_i, [_vp, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp]),
+    "ts_debug_smplx_blend": (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
+    "ts_debug_smplx_rigid_chain": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ts_debug_smplx_skin": (_i, [_vp, _i, _vp, _vp, _i64, _vp, _vp]),
+    "ts_debug_smplx_joints_tail": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "ts_eval_feat_stats": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "ts_eval_l1_total": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "ts_eval_body_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

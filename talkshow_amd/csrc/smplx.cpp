@@ -31,7 +31,9 @@ hipError_t launch_smplx_joints_tail(const float *vs, long vs_frame_stride, const
 struct ts_smplx {
     ts_ctx *ctx = nullptr;
     int V = 0, J = 0, NB = 0, NE = 0, S = 0, P = 0, Kpad = 0, U = 0, KW = 0, n_extra = 0, n_lmk = 0, NJ = 0;
+    int max_src_off = 0;                         // the largest pose_src_offset: a row is read up to column max_src_off + 2
     bool with_vertices = false;
+    std::vector<int> need;                       // host copy of the needed vertex ids in slot order (ts_debug_smplx_need)
     ConvLayer blend_sub, blend_full, jdirs;      // [3U | 3V | 3J] x Kpad, bias = template
     DevBuf src_off, pose_mean, parents, bone_sub, wgt_sub, bone_full, wgt_full, extra_map, lmk_map, bary;
     struct Work {
@@ -78,6 +80,23 @@ int pack_blend(const float *v_template, const float *shapedirs, const float *pos
     return pack_linear_layer(w.data(), Kpad, bias.data(), (int)rows, Kpad, L);
 }
 
+// frames of one full-mesh chunk: the posed-vertex scratch of one chunk stays around 256 MB
+long full_mesh_chunk(int V, long N) {
+    return std::max<long>(1, std::min<long>(N, (long)(256u << 20) / ((long)V * 3 * (long)sizeof(float))));
+}
+
+// the columns a pose row must hold: every joint's three axis-angle columns and, where the model has them, the expression coefficients
+int check_row_layout(const ts_smplx *m, const char *who, int row_ld, int expr_off) {
+    if (row_ld < m->max_src_off + 3)
+        return fail(std::string(who) + ": rows of " + std::to_string(row_ld) + " columns, the model's pose offsets read " +
+                    std::to_string(m->max_src_off + 3));
+    if (expr_off < 0) return fail(std::string(who) + ": negative expression offset");
+    if (m->NE > 0 && (long)expr_off + m->NE > row_ld)
+        return fail(std::string(who) + ": rows of " + std::to_string(row_ld) + " columns, the " + std::to_string(m->NE) +
+                    " expression coefficients at column " + std::to_string(expr_off) + " need " + std::to_string((long)expr_off + m->NE));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -107,6 +126,10 @@ int ts_smplx_create(ts_ctx *ctx, int V, int J, int n_betas, int n_expr, const fl
     m->with_vertices = with_vertices != 0;
     for (int j = 0; j < J; ++j)
         if (parents[j] >= j || (j > 0 && parents[j] < 0)) return fail("ts_smplx_create: parents must precede their children");
+    for (int j = 0; j < J; ++j) {
+        if (pose_src_offset[j] < 0) return fail("ts_smplx_create: negative pose_src_offset");
+        m->max_src_off = std::max(m->max_src_off, (int)pose_src_offset[j]);
+    }
     // needed vertices, de-duplicated, and the maps from joint-list entries into that subset
     std::vector<int> need, extra_map(n_extra), lmk_map((size_t)n_lmk * 3);
     std::map<int, int> slot;
@@ -128,6 +151,7 @@ int ts_smplx_create(ts_ctx *ctx, int V, int J, int n_betas, int n_expr, const fl
     }
     if (need.empty()) need.push_back(0);
     m->U = (int)need.size();
+    m->need = need;
     int kw = 1;
     for (int v = 0; v < V; ++v) {
         int k = 0;
@@ -182,6 +206,7 @@ int ts_smplx_forward(ts_smplx *m, const float *betas, int betas_per_row, const f
     if (!m || !betas || !rows || !joints) return fail("ts_smplx_forward: null argument");
     if (N < 1 || row_ld < 1) return fail("ts_smplx_forward: bad shape");
     if (N > 0x7fffffff) return fail("ts_smplx_forward: more than 2^31 - 1 frames in one call");
+    TS_TRY(check_row_layout(m, "ts_smplx_forward", row_ld, expr_off));
     if (verts && !m->with_vertices) return fail("ts_smplx_forward: model was created without the full-mesh matrices (with_vertices = 0)");
     hipStream_t s = (hipStream_t)stream;
     ts_ctx *ctx = m->ctx;
@@ -217,9 +242,9 @@ int ts_smplx_forward(ts_smplx *m, const float *betas, int betas_per_row, const f
         TS_HIP(launch_smplx_joints_tail(w.vs.f(), (long)U * 3, m->extra_map.i(), m->n_extra, m->lmk_map.i(), m->bary.f(),
                                         m->n_lmk, J, joints, m->NJ, N, s));
     }
-    if (verts) {   // the full mesh, in chunks of frames (the posed-vertex scratch of one chunk stays around 256 MB)
+    if (verts) {   // the full mesh, in chunks of frames
         const int V = m->V;
-        const long chunk = std::max<long>(1, std::min<long>(N, (long)(256u << 20) / ((long)V * 3 * F)));
+        const long chunk = full_mesh_chunk(V, N);
         TS_TRY(w.vposed.ensure((size_t)chunk * V * 3 * F));
         for (long n0 = 0; n0 < N; n0 += chunk) {
             const long nn = std::min(chunk, N - n0);
@@ -230,6 +255,81 @@ int ts_smplx_forward(ts_smplx *m, const float *betas, int betas_per_row, const f
                                      m->KW, V, nn, verts + (size_t)n0 * V * 3, (long)V * 3, s));
         }
     }
+    return 0;
+}
+
+// ---- test aids (include/talkshow_hip_debug.h): one production launch each on the handle's own tables ----
+int ts_debug_smplx_dims(const ts_smplx *m, int32_t *out5) {
+    if (!m || !out5) return fail("ts_debug_smplx_dims: null argument");
+    out5[0] = m->Kpad;
+    out5[1] = m->U;
+    out5[2] = m->KW;
+    out5[3] = m->NJ;
+    out5[4] = (int32_t)full_mesh_chunk(m->V, 0x7fffffffl);
+    return 0;
+}
+
+int ts_debug_smplx_need(const ts_smplx *m, int32_t *verts_out) {
+    if (!m || !verts_out) return fail("ts_debug_smplx_need: null argument");
+    std::copy(m->need.begin(), m->need.end(), verts_out);
+    return 0;
+}
+
+int ts_debug_smplx_pose_prepare(ts_smplx *m, const float *betas, int betas_per_row, const float *rows, int row_ld, int expr_off,
+                                int64_t N, float *rot_out, float *X_out, void *stream) {
+    if (!m || !betas || !rows || !rot_out || !X_out) return fail("ts_debug_smplx_pose_prepare: null argument");
+    if (N < 1 || N > 0x7fffffff || row_ld < 1) return fail("ts_debug_smplx_pose_prepare: bad shape");
+    TS_TRY(check_row_layout(m, "ts_debug_smplx_pose_prepare", row_ld, expr_off));
+    hipStream_t s = (hipStream_t)stream;
+    MiscScope ms(m->ctx, s);
+    TS_HIP(launch_smplx_pose_prepare(rows, row_ld, betas, betas_per_row, m->NB, m->NE, expr_off, m->src_off.i(), m->pose_mean.f(),
+                                     m->J, rot_out, X_out, m->Kpad, N, s));
+    return 0;
+}
+
+int ts_debug_smplx_blend(ts_smplx *m, int which, const float *X, int64_t N, float *out, void *stream) {
+    if (!m || !X || !out) return fail("ts_debug_smplx_blend: null argument");
+    if (N < 1 || N > 0x7fffffff || which < 0 || which > 2) return fail("ts_debug_smplx_blend: bad argument");
+    if (which == 2 && !m->with_vertices)
+        return fail("ts_debug_smplx_blend: model was created without the full-mesh matrices (with_vertices = 0)");
+    const ConvLayer &L = which == 0 ? m->jdirs : which == 1 ? m->blend_sub : m->blend_full;
+    const int n = 3 * (which == 0 ? m->J : which == 1 ? m->U : m->V);
+    ConvParams p;
+    conv_layer_params(L, X, m->Kpad, 1, (int)N, nullptr, 0, out, n, 0, n, &p);
+    return run_conv(m->ctx, p, 0, (hipStream_t)stream);
+}
+
+int ts_debug_smplx_rigid_chain(ts_smplx *m, const float *rot, const float *jrest, int64_t N, float *G_out, float *A_out,
+                               float *joints_out, void *stream) {
+    if (!m || !rot || !jrest || !G_out || !A_out || !joints_out) return fail("ts_debug_smplx_rigid_chain: null argument");
+    if (N < 1 || N > 0x7fffffff) return fail("ts_debug_smplx_rigid_chain: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    MiscScope ms(m->ctx, s);
+    TS_HIP(launch_smplx_rigid_chain(rot, jrest, m->J * 3, m->parents.i(), m->J, N, G_out, A_out, joints_out, m->NJ, s));
+    return 0;
+}
+
+int ts_debug_smplx_skin(ts_smplx *m, int full, const float *vposed, const float *A, int64_t N, float *out, void *stream) {
+    if (!m || !vposed || !A || !out) return fail("ts_debug_smplx_skin: null argument");
+    if (N < 1 || N > 0x7fffffff) return fail("ts_debug_smplx_skin: bad shape");
+    if (full && !m->with_vertices)
+        return fail("ts_debug_smplx_skin: model was created without the full-mesh matrices (with_vertices = 0)");
+    hipStream_t s = (hipStream_t)stream;
+    const int n = full ? m->V : m->U;
+    MiscScope ms(m->ctx, s);
+    TS_HIP(launch_smplx_skin(vposed, n * 3, A, m->J, full ? m->bone_full.i() : m->bone_sub.i(), full ? m->wgt_full.f() : m->wgt_sub.f(),
+                             m->KW, n, N, out, (long)n * 3, s));
+    return 0;
+}
+
+int ts_debug_smplx_joints_tail(ts_smplx *m, const float *vs, int64_t N, float *joints, void *stream) {
+    if (!m || !vs || !joints) return fail("ts_debug_smplx_joints_tail: null argument");
+    if (N < 1 || N > 0x7fffffff) return fail("ts_debug_smplx_joints_tail: bad shape");
+    if (m->n_extra + m->n_lmk == 0) return 0;   // ts_smplx_forward launches nothing either
+    hipStream_t s = (hipStream_t)stream;
+    MiscScope ms(m->ctx, s);
+    TS_HIP(launch_smplx_joints_tail(vs, (long)m->U * 3, m->extra_map.i(), m->n_extra, m->lmk_map.i(), m->bary.f(), m->n_lmk, m->J,
+                                    joints, m->NJ, N, s));
     return 0;
 }
 

@@ -50,6 +50,7 @@ class SMPLXLayer:
         self.V, self.J = int(model["v_template"].shape[0]), int(np.asarray(model["parents"]).shape[0])
         self.n_betas, self.n_expr = int(model["n_betas"]), int(model["n_expr"])
         self.expr_offset = int(expr_offset)
+        self.pose_width = int(np.asarray(pose_offsets).max()) + 3          # columns the pose offsets read
         S = self.n_betas + self.n_expr
         sd = np.asarray(model["shapedirs"]).reshape(self.V, 3, -1)
         if sd.shape[2] != S:
@@ -81,7 +82,12 @@ class SMPLXLayer:
     def _run(self, betas, rows, want_verts):
         rows = torch.as_tensor(rows, dtype=torch.float32, device=self.device)
         lead = rows.shape[:-1]
-        flat = rows.reshape(-1, rows.shape[-1]).contiguous()
+        width = int(rows.shape[-1])
+        need = max(self.pose_width, self.expr_offset + self.n_expr if self.n_expr else 0)
+        if width < need or self.expr_offset < 0:
+            raise ValueError(f"rows of {width} columns: the model reads {self.pose_width} pose columns and {self.n_expr} expression "
+                             f"coefficients from column {self.expr_offset}, {need} columns in all")
+        flat = rows.reshape(-1, width).contiguous()
         N = flat.shape[0]
         betas = torch.as_tensor(betas, dtype=torch.float32, device=self.device).reshape(-1, self.n_betas).contiguous()
         if betas.shape[0] not in (1, N):
