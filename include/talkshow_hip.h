@@ -188,8 +188,9 @@ typedef struct ts_sampling {
  * travels to the stream's work buffers as kernel arguments ahead of the replay, no host memory is read after the call returns, nothing
  * synchronises, any number of calls may be queued — captures nothing.  BUDGET: a host that alternates passes with and without a table on
  * one stream shares the 16 chunk graphs (and the 8 whole-call graphs) kept per stream between the two kinds.
- * Out of scope: ts_pixelcnn_stream_* (and BodyStream), ts_pixelcnn_v_*, the face generator, repetition penalties or any control that
- * reads earlier codes.  (A STATIC per-clip bias on the codes, allow-lists and bans included, is in scope: "code bias" below.)  Log-probabilities (below) share the scope: the streaming sessions, ts_pixelcnn_v_* and the face generator return
+ * Out of scope: ts_pixelcnn_stream_* (and BodyStream), ts_pixelcnn_v_*, the face generator.  (A STATIC per-clip bias on the codes,
+ * allow-lists and bans included, is in scope: "code bias" below; so is a windowed penalty on the codes a clip has already produced:
+ * "repetition penalty" below.)  Log-probabilities (below) share the scope: the streaming sessions, ts_pixelcnn_v_* and the face generator return
  * none, clips of different lengths are not SCORED in one pass, and scoring runs the rows one after the other as the decode does (given
  * the codes, teacher-forced rows do not depend on each other and could run as large GEMMs: other work, with other bits). */
 /* Host only: the validation every _ctl entry applies before anything is launched.  n records for vocabulary V, 1 <= V <= 8191 (a larger V
@@ -633,7 +634,7 @@ int ts_op_style_rows(ts_ctx *ctx, const float *tables_dev, int NL, int NC, int W
  * tables captures nothing.  The table buffer is sized for one table per clip of the work set's clip CAPACITY (8 V bytes per clip), so it
  * NEVER MOVES between the passes of one capacity; the capacity grows only where every work buffer grows, and that drops all graphs of
  * the stream.  Passes without a bias launch the kernels and find the graphs they always did.
- * Out of scope: per-row bias tracks; repetition penalties or anything that reads earlier codes; the streaming sessions
+ * Out of scope: per-row bias tracks; the streaming sessions
  * (ts_pixelcnn_stream_*, BodyStream); ts_pixelcnn_v_*; the face generator; the scoring entries (score_clips / score_motion_clips take no
  * sampling table either). */
 int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
@@ -661,6 +662,79 @@ int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *audioenc, ts_pixelcnn *pix,
 int ts_code_bias_check(const float *tables_host, int n_tables, int V);
 /* Host only: 1 <= n_bias <= B and every index is -1 or in [0, n_bias); every entry that takes tables applies it before its first launch. */
 int ts_code_bias_index_check(const int32_t *bias_index_host, int B, int n_bias);
+
+/* ---- repetition penalty: a per-clip penalty over a window of earlier codes ------------------------------------------------------------------
+ * No counterpart in the reference.  The one sampling control that reads what the clip has already produced: "not this code again within
+ * the next W rows", or, with the opposite sign, "hold the pose".  One record per clip: */
+#define TS_REPEAT_MAX_WINDOW 64
+typedef struct ts_repeat {
+    int32_t window;    /* W in [0, TS_REPEAT_MAX_WINDOW]; 0: off */
+    float presence;    /* finite, |x| <= 1e30, any sign: subtracted once from a code the window has met */
+    float frequency;   /* finite, |x| <= 1e30, any sign: subtracted once per time the window has met it */
+    int32_t reserved;  /* 0 */
+} ts_repeat;
+/* A violation is refused, naming the clip, before anything is launched (ts_repeat_check).
+ * THE RULE, for the sampler launch of absolute position (r, j) — code row r, column j — of a clip with W > 0:
+ *  History.  c_v = the number of rows r' in [max(0, r - W), r) whose code in column j of THIS clip equals v.  Counted are the codes as the
+ *     pass returns them: drawn, given and kept ones alike.  The two columns have separate histories (body and hand codebooks are different
+ *     vocabularies), and no clip reads another's.
+ *  0b. Behind step 0 (code bias) and ahead of step 1 (temperature): for c_v > 0, f = frequency * (float)c_v, g = presence + f,
+ *     l''_v = l'_v - g — THREE IEEE fp32 operations, each rounded, never contracted into a fused multiply-add; for c_v == 0, l''_v is
+ *     l'_v bit for bit.  Steps 1-5, the kept-set sentence of the code bias and the log-probability rule then run on l'' unchanged.  The
+ *     logits OUTPUT (the row copy) stays the network's l.
+ *  Finite by design.  |g| <= 1e30 + 64e30 < FLT_MAX, so a finite l' stays finite and -inf stays -inf: the penalty never empties a column
+ *     and bans nothing, so no check depends on a draw.  presence = 1e30 is the practical "no repeat within W": such a code has weight
+ *     det_expf(-1e30) = 0 and no crossing of step 5 lands on it.  It stays in the kept set, though (the penalty is no ban): where every
+ *     code the filters keep has been met, it is what is drawn, and at u = 1 - 2^-24 the two fallbacks of step 5 may return it, as they
+ *     may return any kept token of weight 0.  A host that needs a hard ban for the whole clip writes -inf into a code bias.
+ *  Given and kept positions.  A forced position takes its code as before, and the code ENTERS THE HISTORY (a code outside [0, V) matches
+ *     no token).  Its log-probability, when asked for, is that under the penalised, biased, filtered distribution; an unkept position is
+ *     drawn under the penalty.
+ *  Random numbers.  A uniform and a Philox number are consumed exactly as without the record.
+ *  Bit identity.  A clip with window = 0 executes the arithmetic of the launch without the feature, operation for operation.  A clip with
+ *     W > 0 and both penalties +0 returns the same codes AND the same log-probability bits: x - (+0) = x for every x, -0 included.
+ *  Scope.  A sampling control with the table's scope: TS_SAMPLE_UNIFORMS and TS_SAMPLE_PHILOX; TS_SAMPLE_GREEDY and TS_TEACHER_FORCED are
+ *     refused with the table's message (per-clip greedy is top_k = 1).  A pass without a sampling table runs on neutral records.
+ * talkshow_amd/sampling.py restates it (repeat_counts, penalised, sample_repeat, decode_repeat).
+ * Device state.  Every stream's work set holds history rings [clip slot][2][64] of int32: the code of row r, column j at index r & 63,
+ * written by the thread that stores the code.  They are sized by the work set's clip CAPACITY like the bias tables, so they never move
+ * between the passes of one capacity, and they need no clearing: a launch reads min(r, W) entries, all written earlier in the same pass by
+ * the same slot (the active clips of a mixed pass are a prefix, so a clip's slot is the same in every chunk; clips carried past their end
+ * write only their own ring).  r comes from the launch's absolute position — the kernel argument plus the dynamic base word under graph
+ * replay, as for the given rows — so the eager route and the chunk graphs share one addressing.  A clip with window = 0 touches no ring.
+ * Staging and graphs.  The records are copied into the stream's work buffers in stream order ahead of the pass (kernel arguments, like the
+ * sampling table).  The samplers are kernels of their own (sample_ctl_rep_kernel / sample_ctl_rep_given_kernel: the code-bias kernels with
+ * the penalty compiled in; a pass without tables runs them on a table index of -1) on graph keys of their own: bit 6 (value 64) of the
+ * sixth key field.  Neither the records nor their number is in the key: a repeated pass with other records captures nothing.  Passes
+ * without records launch the kernels and find the graphs they always did.
+ * The entries: the _bias sibling of each family plus `const ts_repeat *rep_host, int n_rep` ahead of the stream: n_rep = 1 (one record
+ * for all clips) or B records in slot order.  rep_host == NULL: the _bias entry, launch for launch.
+ * Out of scope: the streaming sessions (ts_pixelcnn_stream_*, BodyStream); ts_pixelcnn_v_*; the single-stack form; the scoring entries;
+ * the face generator; windows beyond 64 rows; penalties that read the other column or other clips. */
+int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                      const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                      const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                      float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                      const int32_t *given_rows_dev, const uint8_t *keep_dev, const float *style_dev, int style_rows,
+                                      const float *bias_dev, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
+                                      void *stream);
+int ts_body_pixel_infer_mixed_repeat(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                     const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                     const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                     float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep_dev,
+                                     const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                     const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, void *stream);
+int ts_body_pixel_infer_mixed_poses_repeat(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                           const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                           const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                           float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                           const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                           const uint8_t *keep_dev, const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                           const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, void *stream);
+/* Host only: the rule above on n records for vocabulary V, 1 <= V <= 8191; 0, or an error that names the clip.  The validation every
+ * entry applies before its first launch. */
+int ts_repeat_check(const ts_repeat *rep_host, int n, int V);
 
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.
@@ -734,6 +808,17 @@ int ts_op_sample_bias(ts_ctx *ctx, const float *logits_dev, int B, int V, int mo
                       int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
                       const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, uint8_t *kept_dev,
                       float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column, void *stream);
+/* One launch of the samplers under a "repetition penalty": ts_op_sample_bias's arguments (bias_dev may be NULL here: no tables), then
+ * rep_host, n_rep (1 or B records), then history_dev (B, R) int32, R = min(position >> 1, 64): the codes of rows (position >> 1) - R ...
+ * (position >> 1) - 1 of the launch's column, oldest first (NULL for R = 0), then ring_out_dev (B, 64) int32 or NULL.  The entry fills
+ * rings of -1, places the history in the ring slots where a pass would have left it, launches once (sample_ctl_rep_kernel, or
+ * sample_ctl_rep_given_kernel with given rows) and copies each row's ring of that column to ring_out_dev.  rep_host == NULL:
+ * ts_op_sample_bias. */
+int ts_op_sample_repeat(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                        int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
+                        const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, uint8_t *kept_dev,
+                        float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column,
+                        const ts_repeat *rep_host, int n_rep, const int32_t *history_dev, int32_t *ring_out_dev, void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None):
+                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -118,17 +118,19 @@ class TrainWrapper(TrainWrapperBaseClass):
         array for all clips (`generate_clips`, `ts_body_pixel_infer_mixed_style`).  None: nothing changes.
         code_bias: a per-clip bias / allow-list on the codes — one (2, V) table for all clips, or per clip None, a (2, V) table or a
         {"body", "hand"} dict (`generate_clips`, `ts_body_pixel_infer_mixed_bias`).  None: nothing changes.
+        repeat: a per-clip repetition penalty over a window of earlier codes — one (window, presence, frequency) record or dict for all
+        clips, or a list with one per clip (`generate_clips`, `ts_body_pixel_infer_mixed_repeat`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
         if (sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None or style is not None
-                or code_bias is not None):
+                or code_bias is not None or repeat is not None):
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
                                        _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
-                                       given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias)
+                                       given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -227,7 +229,7 @@ class TrainWrapper(TrainWrapperBaseClass):
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
                        _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None,
-                       style=None, code_bias=None):
+                       style=None, code_bias=None, repeat=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -286,7 +288,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         table says (a banned given code gets -inf).  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only (per-clip greedy is top_k = 1); a clip's
         random numbers do not depend on its table.  Orthogonal to every other keyword.  A wrong shape, a NaN, a +inf, a value beyond
         1e30 or a column without an allowed code raises ValueError naming the clip before anything is launched
-        (`ts_body_pixel_infer_mixed_bias` / `_poses_bias`).  None: nothing changes."""
+        (`ts_body_pixel_infer_mixed_bias` / `_poses_bias`).  None: nothing changes.
+        repeat: NOT THIS CODE AGAIN SO SOON (talkshow_hip.h, "repetition penalty"; `_lib.repeat_table`) — one record (window, presence,
+        frequency), a dict with those keys or None for all clips, or a list in submission order with one such entry per clip (a single
+        record is never written as a list).  At code row r a code the clip produced c > 0 times in the last `window` <= 64 rows of the
+        SAME column loses presence + frequency * c ahead of temperature / top-k / top-p (`sampling.penalised`); drawn, given and kept codes
+        count alike; body and hand columns have separate histories.  presence = 1e30 is "no repeat within the window"; negative values
+        favour what was just produced ("hold the pose").  window 0: the clip's bits do not move.  Log-probabilities are those of the
+        penalised, biased, filtered distribution; given rows are taken as before and enter the history, so handing back the head of a
+        decode WITH THE SAME RECORD returns that decode.  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only; a clip's random numbers do not depend
+        on its record.  Orthogonal to every other keyword.  A window outside [0, 64], a NaN, an infinity or a value beyond 1e30 raises
+        ValueError naming the clip before anything is launched (`ts_body_pixel_infer_mixed_repeat` / `_poses_repeat`).  None: nothing
+        changes."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -329,6 +342,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             kblock = None
         sblock = _lib.style_block(style, [t // 4 for t in lens], self.num_classes, order, who="generate_clips", ids=ids)   # slot order, like the records
         btab, bidx = _lib.code_bias_block(code_bias, B, self.generator.input_dim, order, who="generate_clips", mode=mode)   # slot order, too
+        rtab, n_rep = _lib.repeat_table(repeat, B, self.generator.input_dim, order, who="generate_clips", mode=mode)                # and the records
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -368,15 +382,18 @@ class TrainWrapper(TrainWrapperBaseClass):
         if kblock is not None:
             from talkshow_amd.modules import upload
             kdev = upload(kblock, dev)
-        if sblock is not None or btab is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
+        if sblock is not None or btab is not None or rtab is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
             from talkshow_amd.modules import upload
             sdev = upload(sblock, dev) if sblock is not None else None
             tail = (_lib.dptr(sdev), int(sblock.shape[1]) if sblock is not None else 0)
             poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_style, _lib.load().ts_body_pixel_infer_mixed_style
-            if btab is not None:
-                bdev = upload(btab, dev)
-                tail += (_lib.dptr(bdev), int(btab.shape[0]), bidx.ctypes.data_as(i32p))
+            if btab is not None or rtab is not None:
+                bdev = upload(btab, dev) if btab is not None else None
+                tail += (_lib.dptr(bdev), int(btab.shape[0]) if btab is not None else 0, bidx.ctypes.data_as(i32p) if btab is not None else None)
                 poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_bias, _lib.load().ts_body_pixel_infer_mixed_bias
+            if rtab is not None:
+                tail += (rtab, n_rep)
+                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_repeat, _lib.load().ts_body_pixel_infer_mixed_repeat
             if pblock is not None and gblock is None:
                 pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
                 _lib.check(poses_entry(
@@ -542,7 +559,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return S.allow_bias(codes.reshape(-1, 2), self.generator.input_dim)
 
     def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
-                         given_poses=None, given_keep=None, style=None, code_bias=None):
+                         given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
@@ -552,7 +569,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         given_poses: `_lib.given_pose_block(...)` in ROW order — (block, table) — or None; with `given` too, no clip is in both.
         given_keep: `_lib.given_keep_block(...)` in ROW order — the (B, H_max, 2) uint8 mask of kept positions — or None.
         style: `_lib.style_block(...)` in ROW order — the (B, 1 or H_max, NC) float32 speaker weights that take the place of `ids` — or None.
-        code_bias: `_lib.code_bias_block(...)` in ROW order — (tables (NB, 2, V) float32, index (B,) int32), both numpy — or None."""
+        code_bias: `_lib.code_bias_block(...)` in ROW order — (tables (NB, 2, V) float32, index (B,) int32), both numpy — or None.
+        repeat: `_lib.repeat_table(...)` in ROW order — (records, B) — or None."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -580,7 +598,11 @@ class TrainWrapper(TrainWrapperBaseClass):
             kdev = upload(given_keep, dev)
         if code_bias is not None and code_bias[0] is None:
             code_bias = None
-        if style is not None or code_bias is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
+        if repeat is not None and repeat[0] is None:
+            repeat = None
+        if repeat is not None and repeat[1] != B:
+            raise ValueError(f"infer_padded_wav: the repetition records are one per row ({B}), got {repeat[1]}")
+        if style is not None or code_bias is not None or repeat is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
             sdev = None
             if style is not None:
                 if style.ndim != 3 or style.shape[0] != B or style.shape[1] not in (1, H_max):
@@ -598,6 +620,11 @@ class TrainWrapper(TrainWrapperBaseClass):
                 bidx = np.ascontiguousarray(bidx)
                 tail += (_lib.dptr(bdev), int(btab.shape[0]), bidx.ctypes.data_as(i32p))
                 poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_bias, _lib.load().ts_body_pixel_infer_mixed_bias
+            if repeat is not None:
+                if code_bias is None:
+                    tail += (None, 0, None)
+                tail += (repeat[0], int(repeat[1]))
+                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_repeat, _lib.load().ts_body_pixel_infer_mixed_repeat
             ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
             if given is not None and given[0].shape != (B, H_max, 2):
                 raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
@@ -654,7 +681,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None):
+                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
@@ -665,7 +692,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         one entry per recording.  given_keep: as for `generate_clips` — which positions of a recording's given rows are taken (None, "body",
         "hand", a mask; one entry per recording, or one for all).  style: as for `generate_clips` — float speaker weights in place of the
         ids, per recording None, an (NC,) row or an (H_b,NC) track (H_b the recording's code rows), or one array for all.  code_bias: as for
-        `generate_clips` — which codes a recording may use: one (2, V) table for all, or per recording None, a table or a dict."""
+        `generate_clips` — which codes a recording may use: one (2, V) table for all, or per recording None, a table or a dict.  repeat:
+        as for `generate_clips` — a repetition penalty over a window of earlier codes: one record for all, or a list with one per recording."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -697,6 +725,8 @@ class TrainWrapper(TrainWrapperBaseClass):
                                      who="generate_clips_from_wav", ids=ids)
         if code_bias is not None:
             code_bias = _lib.code_bias_block(code_bias, B, self.generator.input_dim, order, who="generate_clips_from_wav", mode=mode)
+        if repeat is not None:
+            repeat = _lib.repeat_table(repeat, B, self.generator.input_dim, order, who="generate_clips_from_wav", mode=mode)
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -706,7 +736,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
         codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given,
-                                                    given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias)
+                                                    given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,
@@ -717,7 +747,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         Extra keyword arguments understood here (ignored by the reference through **kwargs):
         `greedy=True` (argmax decode), `seed=int`, `uniforms=(B,H,2)`, and the sampling controls `temperature=`, `top_k=`, `top_p=`
         (one record for all B samples; `generate_batch(..., sampling=)`), and `code_bias=` — ONE (2, V) table (or {"body", "hand"} dict) for
-        all B samples: which codes the decode may use (`generate_clips`).  The streaming session behind `continuity=True` takes no
+        all B samples: which codes the decode may use (`generate_clips`), and `repeat=` — ONE (window, presence, frequency) record or
+        dict for all B samples: a repetition penalty over a window of earlier codes (`generate_clips`).  The streaming session behind `continuity=True` takes no
         controls yet: together they raise ValueError.
         '''
         assert self.args.infer, "train mode"
@@ -729,6 +760,14 @@ class TrainWrapper(TrainWrapperBaseClass):
                 raise ValueError("infer_on_audio: code_bias is ONE (2, V) table or dict for all B samples (generate_clips takes one per clip)")
             mode_ = _lib.TS_SAMPLE_GREEDY if kwargs.get('greedy', False) else _lib.TS_SAMPLE_PHILOX
             _lib.code_bias_block(code_bias, 1, self.generator.input_dim, who="infer_on_audio", mode=mode_)   # raises before the audio is read
+        repeat = kwargs.get('repeat', None)
+        if repeat is not None:
+            if continuity:
+                raise ValueError("infer_on_audio: the streaming session behind continuity=True takes no repetition penalty")
+            if isinstance(repeat, list):
+                raise ValueError("infer_on_audio: repeat is ONE (window, presence, frequency) record or dict for all B samples (generate_clips takes one per clip)")
+            mode_ = _lib.TS_SAMPLE_GREEDY if kwargs.get('greedy', False) else _lib.TS_SAMPLE_PHILOX
+            _lib.repeat_table(repeat, 1, self.generator.input_dim, who="infer_on_audio", mode=mode_)   # raises before the audio is read
         sampling = None
         if any(kwargs.get(k) is not None for k in ('temperature', 'top_k', 'top_p')):
             if continuity:
@@ -786,7 +825,7 @@ class TrainWrapper(TrainWrapperBaseClass):
                 pred_poses = torch.cat([part0, part1], dim=1).cpu().numpy()
             else:
                 self.audioencoder.eval()
-                _, poses = self.generate_batch(aud_feat, id, mode=mode, uniforms=uniforms, seed=seed, sampling=sampling, code_bias=code_bias)
+                _, poses = self.generate_batch(aud_feat, id, mode=mode, uniforms=uniforms, seed=seed, sampling=sampling, code_bias=code_bias, repeat=repeat)
                 pred_poses = poses.cpu().numpy()
 
         output = pred_poses

@@ -33,6 +33,15 @@ class TsSampling(C.Structure):
 _sp = C.POINTER(TsSampling)
 
 
+class TsRepeat(C.Structure):
+    """ts_repeat (include/talkshow_hip.h, "repetition penalty"): the record of one clip; window 0 = off."""
+    _fields_ = [("window", C.c_int32), ("presence", C.c_float), ("frequency", C.c_float), ("reserved", C.c_int32)]
+
+
+_rp = C.POINTER(TsRepeat)
+TS_REPEAT_MAX_WINDOW = 64
+
+
 class SkinnySeg(C.Structure):
     """ts_debug_skinny_seg (include/talkshow_hip_debug.h)."""
     _fields_ = [("base", _vp), ("gidx", _vp), ("row_stride", C.c_long), ("gidx_stride", C.c_long), ("row_shift", _i), ("len", _i),
@@ -152,6 +161,17 @@ SIGNATURES = {
     "ts_code_bias_index_check": (_i, [C.POINTER(C.c_int32), _i, _i]),
     "ts_op_sample_bias": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
                                _i, C.POINTER(C.c_int32), _i, _vp]),
+    # repetition penalty: the _bias sibling of each family with rep_host, n_rep ahead of the stream; the host rule; one launch
+    "ts_pixelcnn_generate_mixed_repeat": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
+                                               C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _rp, _i, _vp]),
+    "ts_body_pixel_infer_mixed_repeat": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
+                                              _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _rp, _i, _vp]),
+    "ts_body_pixel_infer_mixed_poses_repeat": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
+                                                    _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _rp, _i,
+                                                    _vp]),
+    "ts_repeat_check": (_i, [_rp, _i, _i]),
+    "ts_op_sample_repeat": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
+                                 _i, C.POINTER(C.c_int32), _i, _rp, _i, _vp, _vp, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -648,6 +668,83 @@ def code_bias_block(code_bias, B, V, order=None, who="code_bias", mode=None):
         return None, None
     index = np.asarray([index_sub[i] for i in order], np.int32)
     return np.ascontiguousarray(np.stack(tables), dtype=np.float32), index
+
+
+def repeat_record(rec):
+    """One repetition record as (window, presence, frequency): None (off: (0, 0.0, 0.0)), a dict with any of the keys `window`,
+    `presence`, `frequency`, or a TUPLE (window, presence, frequency).  A list is never one record: lists hold one record per clip.
+    Pure host code."""
+    if rec is None:
+        return (0, 0.0, 0.0)
+    if isinstance(rec, dict):
+        unknown = set(rec) - {"window", "presence", "frequency"}
+        if unknown:
+            raise ValueError(f"repetition record: unknown keys {sorted(map(str, unknown))} (window, presence, frequency)")
+        rec = (rec.get("window", 0), rec.get("presence", 0.0), rec.get("frequency", 0.0))
+    if isinstance(rec, tuple) and len(rec) == 3:
+        w, p, f = rec
+        try:      # inf, NaN, a string, None: refused like a fraction, as a ValueError the caller can name the clip in
+            whole = not isinstance(w, bool) and int(w) == w
+        except (TypeError, ValueError, OverflowError):
+            whole = False
+        if not whole:
+            raise ValueError(f"a repetition record's window is a whole number of code rows, got {w!r}")
+        try:
+            return (int(w), float(p), float(f))
+        except (TypeError, ValueError):
+            raise ValueError(f"a repetition record's presence and frequency are numbers, got {p!r} and {f!r}") from None
+    raise ValueError(f"a repetition record is None, a dict or a tuple (window, presence, frequency), got {rec!r}")
+
+
+def repeat_table(repeat, B, V, order=None, who="repeat", mode=None):
+    """The `repeat=` keyword of the decode entries -> (array of B `ts_repeat` records in SLOT order, B): what the `_repeat` entries take as
+    rep_host and n_rep; (None, 0) for `repeat=None` (talkshow_hip.h, "repetition penalty": a code the clip produced in the last `window`
+    rows of a column loses presence + frequency * count ahead of the sampling rule).
+    repeat: None, a dict or a tuple (window, presence, frequency) — ONE record for all clips — or a LIST in SUBMISSION order with one such
+    entry per clip.  A single record written as a list is refused with a message that says so.  order: sorted slot k holds submitted clip
+    order[k].  mode: the call's draw mode, if the caller wants the scope checked here too (greedy and teacher forced are refused as for a
+    sampling table).  ValueError naming the SUBMITTED clip, before anything is launched, for a window outside [0, 64], a NaN, an
+    infinity or a value beyond 1e30 (`ts_repeat_check`).  Pure host code."""
+    if repeat is None:
+        return None, 0
+    if mode is not None and mode not in (TS_SAMPLE_UNIFORMS, TS_SAMPLE_PHILOX):      # the penalty shares the sampling table's scope
+        raise ValueError(f"{who}: a repetition penalty is a sampling control: sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX "
+                         f"(per-clip greedy is top_k = 1)")
+    B = int(B)
+    if isinstance(repeat, (dict, tuple)):
+        recs = [repeat] * B
+    elif isinstance(repeat, list):
+        if repeat and all(isinstance(r, (int, float)) for r in repeat):
+            raise ValueError(f"{who}: repeat={repeat!r}: a list holds one record per clip; write one record for all clips as a tuple "
+                             f"(window, presence, frequency)")
+        if len(repeat) != B:
+            raise ValueError(f"{who}: repeat must hold one record or one per clip ({B}), got {len(repeat)}")
+        recs = repeat
+    else:
+        raise ValueError(f"{who}: repeat must be None, a dict, a tuple (window, presence, frequency) or a list of one record per clip, got {repeat!r}")
+    order = list(range(B)) if order is None else [int(i) for i in order]
+    if sorted(order) != list(range(B)):
+        raise ValueError(f"{who}: order must be a permutation of the {B} clips")
+    one = (TsRepeat * 1)()
+    arr = (TsRepeat * B)()
+    checked = {}
+    for i, r in enumerate(recs):
+        try:
+            w, p, f = repeat_record(r)
+        except ValueError as e:
+            raise ValueError(f"{who}: repeat of clip {i}: {e}") from None
+        if (w, p, f) not in checked:
+            if not -2 ** 31 <= w < 2 ** 31:
+                raise ValueError(f"{who}: repeat of clip {i}: window out of range")
+            one[0].window, one[0].presence, one[0].frequency, one[0].reserved = w, p, f, 0
+            if load().ts_repeat_check(one, 1, int(V)) != 0:
+                msg = load().ts_last_error().decode().replace("ts_repeat_check: clip 0: ", "")
+                raise ValueError(f"{who}: repeat of clip {i}: {msg}")
+            checked[(w, p, f)] = True
+    for k, i in enumerate(order):
+        w, p, f = repeat_record(recs[i])
+        arr[k].window, arr[k].presence, arr[k].frequency, arr[k].reserved = w, p, f, 0
+    return arr, B
 
 
 def given_pose_block(given_poses, rows, order=None, who="given_poses", width=129):

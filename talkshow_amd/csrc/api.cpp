@@ -287,12 +287,38 @@ int ts_body_pixel_infer_mixed_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *v
                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                    const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
                                    const int32_t *bias_index_host, void *stream) {
+    return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                            ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias, n_bias,
+                                            bias_index_host, nullptr, 0, stream);
+}
+
+// What the body entries refuse of a "repetition penalty" before their first launch: the mode (a sampling control, like the bias), the
+// number of records and the records themselves
+static int body_repeat_check(const char *who, int mode, int B, int V, const ts_repeat *rep_host, int n_rep) {   // V = 1: the vocabulary is
+                                                                                                                // checked by the pass itself
+    if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
+        return fail(std::string(who) + ": sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
+    if (n_rep != 1 && n_rep != B)
+        return fail(std::string(who) + ": a pass of " + std::to_string(B) + " clips brings 1 or " + std::to_string(B) + " repetition records, got " +
+                    std::to_string(n_rep));
+    return ts_repeat_check(rep_host, n_rep, V);
+}
+
+// the same pass under a "repetition penalty" (talkshow_hip.h): rep_host n_rep (1 or B) records in slot order.  rep_host == NULL: exactly
+// the entry above
+int ts_body_pixel_infer_mixed_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                     const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                     float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
+                                     const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
+                                     const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, void *stream) {
     if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, style ? static_cast<const void *>(style) : ids, lens_host, lens_dev, B,
                          T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
         return 1;
     if (style && style_rows != 1 && style_rows != (T_max / 2) / 2)
         return fail("ts_body_pixel_infer_mixed_style: style_rows is 1 or T_max / 4 = " + std::to_string((T_max / 2) / 2) + ", got " + std::to_string(style_rows));
     if (bias && body_bias_check("ts_body_pixel_infer_mixed_bias", mode, B, n_bias, bias_index_host) != 0) return 1;
+    if (rep_host && body_repeat_check("ts_body_pixel_infer_mixed_repeat", mode, B, 1, rep_host, n_rep) != 0) return 1;
     if (keep && !given) return fail("ts_body_pixel_infer_mixed_keep: a mask of kept positions needs the given codes it selects from");
     if (given) {   // a bad row table is refused before the first launch of the pass, too
         if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
@@ -304,9 +330,9 @@ int ts_body_pixel_infer_mixed_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *v
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * aud_dim * sizeof(float)));
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
-    TS_TRY(ts_pixelcnn_generate_mixed_bias(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
-                                           n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias, n_bias,
-                                           bias_index_host, s));
+    TS_TRY(ts_pixelcnn_generate_mixed_repeat(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
+                                             n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias, n_bias,
+                                             bias_index_host, rep_host, n_rep, s));
     for (int k = 0; k < 2; ++k) {
         TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
         TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),
@@ -374,12 +400,26 @@ int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
                                          int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                          const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows, const float *bias,
                                          int n_bias, const int32_t *bias_index_host, void *stream) {
+    return ts_body_pixel_infer_mixed_poses_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+                                                  poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, keep, style,
+                                                  style_rows, bias, n_bias, bias_index_host, nullptr, 0, stream);
+}
+
+// the same under a "repetition penalty" (rep_host n_rep (1 or B) records in slot order; rep_host == NULL: exactly the entry above).  The
+// encoders never see the records: the codes they find enter the histories as given codes do
+int ts_body_pixel_infer_mixed_poses_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                           const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                           uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
+                                           int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
+                                           const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows,
+                                           const float *bias, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
+                                           void *stream) {
     if (keep && !given_poses)
         return fail("ts_body_pixel_infer_mixed_poses_keep: a mask of kept positions needs the given poses whose codes it selects from");
     if (!given_poses)
-        return ts_body_pixel_infer_mixed_bias(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+        return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, nullptr, style, style_rows, bias, n_bias,
-                                              bias_index_host, stream);
+                                              bias_index_host, rep_host, n_rep, stream);
     const char *who = "ts_body_pixel_infer_mixed_poses";
     // everything the pass itself would refuse is refused here too, ahead of the encoders' launches
     if (!pose_lens_host || !pose_lens_dev) return fail(std::string(who) + ": given poses need their frame tables");
@@ -392,6 +432,7 @@ int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
     if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": TS_SAMPLE_UNIFORMS needs uniforms_dev");
     if (bias && body_bias_check("ts_body_pixel_infer_mixed_poses_bias", mode, B, n_bias, bias_index_host) != 0) return 1;
+    if (rep_host && body_repeat_check("ts_body_pixel_infer_mixed_poses_repeat", mode, B, 1, rep_host, n_rep) != 0) return 1;
     if (ts_given_pose_rows_check(pose_lens_host, lens_host, B) != 0) return 1;
     std::vector<int32_t> G(B);
     int p_top = 0;
@@ -401,9 +442,9 @@ int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
     }
     if (p_top > P_max) return fail(std::string(who) + ": a clip brings more pose frames than P_max");
     if (p_top == 0)   // nothing given anywhere: the pass without given rows
-        return ts_body_pixel_infer_mixed_bias(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
+        return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
                                               poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, nullptr, style, style_rows, bias, n_bias,
-                                              bias_index_host, stream);
+                                              bias_index_host, rep_host, n_rep, stream);
     if (P_max / 4 > H) return fail(std::string(who) + ": P_max / 4 exceeds the pass's code rows T_max / 4");
     hipStream_t s = (hipStream_t)stream;
     BodyWork &w = body_work(s);
@@ -411,9 +452,8 @@ int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
     int64_t *given = static_cast<int64_t *>(w.given.p);
     // rows h < P_b / 4 of clip b: its codes; rows up to P_max / 4: -1; rows beyond stay as they are — the pass reads rows below G_b only
     TS_TRY(vq_encode_pair_masked(vb, vh, given_poses, vqvae_in_dim(vb) + vqvae_in_dim(vh), pose_lens_dev, B, P_max, given, H, nullptr, nullptr, 0, s));
-    return ts_body_pixel_infer_mixed_bias(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                          ctl_host, n_ctl, logprob, given, G.data(), nullptr, keep, style, style_rows, bias, n_bias, bias_index_host,
-                                          stream);
+    return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
+                                          ctl_host, n_ctl, logprob, given, G.data(), nullptr, keep, style, style_rows, bias, n_bias, bias_index_host, rep_host, n_rep, stream);
 }
 
 int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const float *w, const float *bias, int Cout,

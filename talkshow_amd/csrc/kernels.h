@@ -454,6 +454,13 @@ struct SampleCtl {
     float inv_t, top_p;
     int32_t top_k, pad;
 };
+// The device record of a clip's repetition penalty: ts_repeat's four words (window in [0, SAMPLE_REP_RING], 0 = off)
+struct SampleRep {
+    int32_t window;
+    float presence, frequency;
+    int32_t pad;
+};
+constexpr int SAMPLE_REP_RING = 64;
 struct SampleCtlParams {
     SampleParams s;            // mode TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX
     const SampleCtl *ctl;      // record of clip b at ctl[b]
@@ -466,6 +473,12 @@ struct SampleCtlParams {
     const float *bias;
     const int32_t *bias_index;
     int bias_col;
+    // "repetition penalty" (talkshow_hip.h): rep[b] the record of clip slot b, rep_ring[b][bias_col][64] the codes the slot produced in this
+    // column, row r at index r & 63 (r = the launch's absolute position >> 1).  A slot with window 0 reads and writes no ring and executes
+    // the arithmetic of the sample_ctl_bias kernels.  Read by the sample_ctl_rep kernels only, which also need bias_index (all -1 and
+    // bias null: a pass without tables); null for every other launch
+    const SampleRep *rep;
+    int32_t *rep_ring;
 };
 // a histogram bin of the kernel holds count << 44 | mass with mass <= V * 2^31: V * 2^31 < 2^44 bounds the vocabulary (the tie counters' 16 bits
 // and the count field hold more); launch_sample_ctl and the host checks refuse anything above

@@ -98,6 +98,10 @@ struct ts_pixelcnn {
         DevBuf bias_tab, bias_idx;         // passes with a code bias: the tables (NB,2,V) fp32 and the table index of every clip SLOT (int32, -1: none), both
                                            // written in stream order ahead of the pass (what the captured samplers read).  bias_tab holds capB tables — a pass
                                            // brings at most one per clip — so it moves only when ensure_work has dropped the graphs that read it
+        DevBuf rep_tab, rep_ring;          // passes with a repetition penalty: one SampleRep per clip SLOT, written in stream order ahead of the pass, and the
+                                           // history rings [slot][2][64] int32 (the code of row r, column j at index r & 63) the sample_ctl_rep kernels read and
+                                           // write.  Both are sized by capB in ensure_work, so they never move under a graph; the rings need no clearing: a launch
+                                           // reads min(r, W) entries, all written earlier in the same pass by the same slot
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
@@ -108,7 +112,8 @@ struct ts_pixelcnn {
         // which read given_tab and given_int), bit 3 for a given pass that brings a mask of kept positions (every chunk's samplers then also
         // read keep_int; without the bit their mask pointer is null), bit 4 for a pass with per-row speaker style (the gate launches of every chunk
         // read their conditioning rows from style_int in place of CR), bit 5 for a pass with a code bias (its samplers are the sample_ctl_bias
-        // kernels, which read bias_tab and bias_idx; neither the tables' content nor their number is part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // kernels, which read bias_tab and bias_idx; neither the tables' content nor their number is part of the key), bit 6 for a pass with a repetition penalty (its samplers are the
+        // sample_ctl_rep kernels, which read rep_tab and bias_idx and read and write rep_ring; the records are not part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -262,6 +267,8 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->given_int.ensure((size_t)cb * CHUNK_ROWS * 2 * sizeof(int64_t)));
     TS_TRY(w->keep_int.ensure((size_t)cb * CHUNK_ROWS * 2));
     TS_TRY(w->bias_idx.ensure((size_t)cb * sizeof(int32_t)));
+    TS_TRY(w->rep_tab.ensure((size_t)cb * sizeof(SampleRep)));
+    TS_TRY(w->rep_ring.ensure((size_t)cb * 2 * SAMPLE_REP_RING * sizeof(int32_t)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -317,6 +324,10 @@ struct RunCfg {
     // (neutral records when the call brought none)
     const float *bias = nullptr;
     const int32_t *bias_index = nullptr;
+    // "repetition penalty": the Work's rep_tab (slabB(),) and rep_ring [slabB()][2][64], or null: the samplers without records.  With
+    // records c.ctl and c.bias_index are set too (neutral records / an index of -1 when the call brought none)
+    const SampleRep *rep = nullptr;
+    int32_t *rep_ring = nullptr;
     // the class-conditioning rows of layer l for the gate launches of code row r (every such launch belongs to one row)
     const float *cls_rows(int l, int r, size_t D2) const {
         if (!style) return w->CR.f() + (size_t)l * slabB() * D2;
@@ -680,6 +691,8 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         gp.c.bias = c.bias;
         gp.c.bias_index = c.bias_index;
         gp.c.bias_col = j;
+        gp.c.rep = c.rep;
+        gp.c.rep_ring = c.rep_ring;
         gp.rows = c.given_rows;
         gp.given = c.given + (size_t)ro * 2 + j;
         gp.given_stride = (long)sH * 2;
@@ -696,6 +709,8 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         cp.bias = c.bias;
         cp.bias_index = c.bias_index;
         cp.bias_col = j;
+        cp.rep = c.rep;
+        cp.rep_ring = c.rep_ring;
         TS_HIP(launch_sample_ctl(cp, s));
     } else if (lp) {
         SampleLpParams q;
@@ -1065,8 +1080,8 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
 inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr, const unsigned char *keep = nullptr,
-                        const float *style = nullptr, const float *bias = nullptr) {
-    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0) | (style ? 16 : 0) | (bias ? 32 : 0);
+                        const float *style = nullptr, const float *bias = nullptr, const SampleRep *rep = nullptr) {
+    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0) | (style ? 16 : 0) | (bias ? 32 : 0) | (rep ? 64 : 0);
 }
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
@@ -1272,7 +1287,7 @@ constexpr int MIXED_MAX_COUNTS = 12;
 
 int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
               uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, const int64_t *given, int given_max,
-              const unsigned char *keep, const float *style_track, const int *lens_dev, bool biased, hipStream_t s) {
+              const unsigned char *keep, const float *style_track, const int *lens_dev, bool biased, bool repeat, hipStream_t s) {
     const size_t D = p->D, f = sizeof(float);
     constexpr int RING = 4;
     std::vector<int> active;
@@ -1288,6 +1303,11 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
         c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
         c.ctl = ctl;   // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
         if (biased) c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);   // by slot, too
+        if (repeat) {   // records and rings by slot; without tables the index the caller staged is -1 everywhere and c.bias stays null
+            c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
+            c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
+            c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+        }
         if (given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
             c.given_rows = w->given_tab.i();
             c.given_src = given;
@@ -1319,7 +1339,7 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
                 TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
                                         (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
         const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src, c.style, c.bias)), uniforms, codes, logprob, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src, c.style, c.bias, c.rep)), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1554,6 +1574,22 @@ int ts_code_bias_check(const float *tables_host, int n_tables, int V) {
     return 0;
 }
 
+namespace {
+// n_rep (1 or B) checked records -> one device record per clip slot
+int rep_table(const ts_repeat *rep_host, int n_rep, int B, int V, const char *who, std::vector<SampleRep> &tab) {
+    if (n_rep != 1 && n_rep != B)
+        return fail(std::string(who) + ": a pass of " + std::to_string(B) + " clips brings 1 or " + std::to_string(B) + " repetition records, got " +
+                    std::to_string(n_rep));
+    TS_TRY(ts_repeat_check(rep_host, n_rep, V));
+    tab.resize(B);
+    for (int b = 0; b < B; ++b) {
+        const ts_repeat &r = rep_host[n_rep == 1 ? 0 : b];
+        tab[b] = SampleRep{r.window, r.presence, r.frequency, 0};
+    }
+    return 0;
+}
+}  // namespace
+
 // ts_op_sample_keep's launch under a "code bias" (kernel-level tests call it): bias (n_bias,2,V) device tables, bias_index_host (B,) the
 // table of every row or -1, column 0 / 1.  Without a sampling table the rows run on neutral records.  given_rows_host == NULL: no given
 // rows (sample_ctl_bias_kernel; given, keep unused); otherwise the given variant.  kept (optional, (B,V)): the kept bytes
@@ -1561,8 +1597,25 @@ int ts_op_sample_bias(ts_ctx *ctx, const float *logits, int B, int V, int mode, 
                       uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
                       const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
                       const int32_t *bias_index_host, int column, void *stream) {
-    const char *who = "ts_op_sample_bias";
-    if (!ctx || !logits || !idx || !bias || !bias_index_host) return fail(std::string(who) + ": null argument");
+    if (!bias || !bias_index_host) return fail("ts_op_sample_bias: null argument");
+    return ts_op_sample_repeat(ctx, logits, B, V, mode, uniforms, seed, clip_index0, position, ctl_host, n_ctl, idx, logprob, given_rows_host, keep,
+                               given, kept, logits_copy, bias, n_bias, bias_index_host, column, nullptr, 0, nullptr, nullptr, stream);
+}
+
+// The same launch under a "repetition penalty" (kernel-level tests call it): rep_host n_rep (1 or B) records; history (B,R) int32 on the
+// device, R = min(position >> 1, 64), the codes of rows (position >> 1) - R .. (position >> 1) - 1 of this column, oldest first; ring_out
+// (B,64) int32 or NULL.  The entry fills rings of -1, places the history where a pass would have left it (row r at r & 63), launches once
+// and copies every row's ring of this column out.  bias == NULL: no tables (an index of -1 everywhere).  rep_host == NULL: ts_op_sample_bias
+int ts_op_sample_repeat(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                        uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
+                        const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
+                        const int32_t *bias_index_host, int column, const ts_repeat *rep_host, int n_rep, const int32_t *history,
+                        int32_t *ring_out, void *stream) {
+    const char *who = rep_host ? "ts_op_sample_repeat" : "ts_op_sample_bias";
+    if (!ctx || !logits || !idx || (bias && !bias_index_host) || (!bias && !rep_host)) return fail(std::string(who) + ": null argument");
+    const int hist_rows = (int)std::min<uint32_t>(position >> 1, (uint32_t)SAMPLE_REP_RING);
+    if (rep_host && hist_rows > 0 && !history) return fail(std::string(who) + ": rows behind row 0 need their history");
+    if (!rep_host && (history || ring_out)) return fail(std::string(who) + ": a history and a ring output need records");
     if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
     if (column != 0 && column != 1) return fail(std::string(who) + ": column is 0 (body) or 1 (hand)");
     if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
@@ -1577,14 +1630,33 @@ int ts_op_sample_bias(ts_ctx *ctx, const float *logits, int B, int V, int mode, 
     std::vector<SampleCtl> tab;
     const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
     TS_TRY(ctl_table(ctl_host ? ctl_host : &neutral, ctl_host ? n_ctl : 1, B, V, mode, who, tab));   // refuses greedy and teacher forced
-    TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
+    if (bias) TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
+    std::vector<SampleRep> rtab;
+    if (rep_host) TS_TRY(rep_table(rep_host, n_rep, B, V, who, rtab));
     hipStream_t s = (hipStream_t)stream;
-    DevBuf tok, dtab, drows, dbi;
+    DevBuf tok, dtab, drows, dbi, drep, dring;
     TS_TRY(tok.ensure((size_t)B * sizeof(int)));
     TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
     TS_TRY(dbi.ensure((size_t)B * sizeof(int32_t)));
     TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
-    TS_HIP(launch_put_words(dbi.i(), bias_index_host, B, s));
+    const std::vector<int32_t> none(B, -1);
+    TS_HIP(launch_put_words(dbi.i(), bias ? bias_index_host : none.data(), B, s));
+    const size_t ring_pitch = (size_t)2 * SAMPLE_REP_RING * sizeof(int32_t);   // one clip's two rings
+    if (rep_host) {
+        TS_TRY(drep.ensure((size_t)B * sizeof(SampleRep)));
+        TS_TRY(dring.ensure((size_t)B * ring_pitch));
+        TS_HIP(launch_put_words(drep.i(), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
+        TS_HIP(hipMemsetAsync(dring.p, 0xff, (size_t)B * ring_pitch, s));
+        // rows r - R .. r - 1 are consecutive ring slots modulo 64: one or two strided copies
+        const uint32_t first = (position >> 1) - (uint32_t)hist_rows;
+        for (int done = 0; done < hist_rows;) {
+            const int slot = (int)((first + (uint32_t)done) & (uint32_t)(SAMPLE_REP_RING - 1));
+            const int n = std::min(hist_rows - done, SAMPLE_REP_RING - slot);
+            TS_HIP(hipMemcpy2DAsync(dring.i() + (size_t)column * SAMPLE_REP_RING + slot, ring_pitch, history + done,
+                                    (size_t)hist_rows * sizeof(int32_t), (size_t)n * sizeof(int32_t), B, hipMemcpyDeviceToDevice, s));
+            done += n;
+        }
+    }
     SampleGivenParams gp;
     std::memset(&gp, 0, sizeof(gp));
     gp.c.s.logits = logits;
@@ -1609,6 +1681,10 @@ int ts_op_sample_bias(ts_ctx *ctx, const float *logits, int B, int V, int mode, 
     gp.c.bias = bias;
     gp.c.bias_index = static_cast<const int32_t *>(dbi.p);
     gp.c.bias_col = column;
+    if (rep_host) {
+        gp.c.rep = static_cast<const SampleRep *>(drep.p);
+        gp.c.rep_ring = dring.i();
+    }
     if (given_rows_host) {
         TS_TRY(drows.ensure((size_t)B * sizeof(int)));
         TS_HIP(launch_put_words(drows.i(), given_rows_host, B, s));
@@ -1621,6 +1697,9 @@ int ts_op_sample_bias(ts_ctx *ctx, const float *logits, int B, int V, int mode, 
     } else {
         TS_HIP(launch_sample_ctl(gp.c, s));
     }
+    if (rep_host && ring_out)
+        TS_HIP(hipMemcpy2DAsync(ring_out, (size_t)SAMPLE_REP_RING * sizeof(int32_t), dring.i() + (size_t)column * SAMPLE_REP_RING, ring_pitch,
+                                (size_t)SAMPLE_REP_RING * sizeof(int32_t), B, hipMemcpyDeviceToDevice, s));
     TS_HIP(hipStreamSynchronize(s));
     return 0;
 }
@@ -1735,6 +1814,45 @@ int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const 
                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
                                     int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host, void *stream) {
+    return ts_pixelcnn_generate_mixed_repeat(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
+                                             logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias_dev, n_bias,
+                                             bias_index_host, nullptr, 0, stream);
+}
+
+// Host only ("repetition penalty"): n records — window in [0, 64], presence and frequency finite with |x| <= 1e30, reserved 0 — for a
+// vocabulary within the controls' limit; the message names the clip
+int ts_repeat_check(const ts_repeat *rep_host, int n, int V) {
+    if (!rep_host || n < 1 || V < 1) return fail("ts_repeat_check: bad argument");
+    if (V > SAMPLE_CTL_MAX_V)
+        return fail("ts_repeat_check: a repetition penalty supports vocabularies of at most " + std::to_string(SAMPLE_CTL_MAX_V) +
+                    " classes, got V = " + std::to_string(V));
+    for (int b = 0; b < n; ++b) {
+        const ts_repeat &r = rep_host[b];
+        const std::string where = "ts_repeat_check: clip " + std::to_string(b);
+        if (r.window < 0 || r.window > TS_REPEAT_MAX_WINDOW)
+            return fail(where + ": window " + std::to_string(r.window) + " is outside [0, " + std::to_string(TS_REPEAT_MAX_WINDOW) + "]");
+        const float v[2] = {r.presence, r.frequency};
+        static const char *const name[2] = {"presence", "frequency"};
+        for (int k = 0; k < 2; ++k) {
+            if (std::isnan(v[k])) return fail(where + ": " + name[k] + " is NaN");
+            if (std::isinf(v[k])) return fail(where + ": " + name[k] + " is infinite");
+            if (std::fabs(v[k]) > 1e30f) return fail(where + ": " + name[k] + " exceeds 1e30 in magnitude");
+        }
+        if (r.reserved != 0) return fail(where + ": the reserved word is " + std::to_string(r.reserved) + ", not 0");
+    }
+    return 0;
+}
+
+// the same pass under a "repetition penalty" (talkshow_hip.h): rep_host n_rep (1 or B) records in slot order.  The records are copied into the
+// Work in stream order ahead of the pass (kernel arguments, like the sampling table); the samplers are the sample_ctl_rep kernels on graph
+// keys of their own (bit 6), which keep every slot's history in Work::rep_ring; a call without a sampling table runs on neutral records, a
+// call without tables on an index of -1.  rep_host == NULL: the _bias entry, launch for launch
+int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                      int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                      int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                      const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
+                                      int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                      const ts_repeat *rep_host, int n_rep, void *stream) {
     (void)given_rows_dev;   // the table travels as kernel arguments from the host copy (see talkshow_hip.h)
     if (!p || (!label && !style) || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
@@ -1753,14 +1871,16 @@ int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const 
     }
     std::vector<SampleCtl> tab;
     if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
-    if (bias_dev) {   // a sampling control with the table's scope; without a table the pass runs on neutral records (the plain sampler's bits)
+    if (bias_dev || rep_host) {   // sampling controls with the table's scope; without a table the pass runs on neutral records (the plain sampler's bits)
         if (!ctl_host) {
             const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
-            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, "ts_pixelcnn_generate_mixed_bias", tab));
+            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, rep_host ? "ts_pixelcnn_generate_mixed_repeat" : "ts_pixelcnn_generate_mixed_bias", tab));
         }
-        TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
+        if (bias_dev) TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
     }
-    const bool with_ctl = ctl_host || bias_dev;
+    std::vector<SampleRep> rtab;
+    if (rep_host) TS_TRY(rep_table(rep_host, n_rep, B, p->V, "ts_pixelcnn_generate_mixed_repeat", rtab));
+    const bool with_ctl = ctl_host || bias_dev || rep_host;
     int given_max = 0;
     if (keep && !given) return fail("ts_pixelcnn_generate_mixed_keep: a mask of kept positions needs the given codes it selects from");
     if (given) {
@@ -1778,6 +1898,15 @@ int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const 
         MiscScope ms(ctx, s);
         TS_HIP(hipMemcpyAsync(w->bias_tab.p, bias_dev, (size_t)n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
         TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), bias_index_host, B, s));
+    }
+    if (rep_host) {   // the records as kernel arguments, like the sampling table; a pass without tables brings the index the BIAS path wants
+        static_assert(sizeof(SampleRep) == 4 * sizeof(int), "SampleRep is four words");
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
+        if (!bias_dev) {
+            const std::vector<int32_t> none(B, -1);
+            TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), none.data(), B, s));
+        }
     }
     if (given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
         MiscScope ms(ctx, s);
@@ -1799,7 +1928,7 @@ int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const 
     }
     const bool graph = p->use_graph && !ctx->prof.on;
     TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, with_ctl ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
-                     logprob, given, given_max, keep, tracked ? style : nullptr, lens_dev, bias_dev != nullptr, s));
+                     logprob, given, given_max, keep, tracked ? style : nullptr, lens_dev, bias_dev != nullptr, rep_host != nullptr, s));
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0

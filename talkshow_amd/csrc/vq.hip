@@ -1254,6 +1254,15 @@ __device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) 
     return ok;
 }
 
+// step 0b of the "repetition penalty" (talkshow_hip.h) for one token: c = how often the window met it
+__device__ __forceinline__ float rep_penalise(float l, int c, float presence, float frequency) {
+#pragma clang fp contract(off)
+    if (c <= 0) return l;                      // a token the window has not met keeps its bits
+    const float f = frequency * (float)c;      // three fp32 operations, each rounded on its own
+    const float g = presence + f;
+    return l - g;
+}
+
 // The body of the eight samplers with controls.  Flags:
 //   FAST   V = 2048 on 16-byte aligned rows (the launchers decide): every thread owns 8 logits, held in registers from two 16-byte loads
 //   LP     also write the log-probability of the row's code under the distribution it was drawn from (cp.logprob; talkshow_hip.h,
@@ -1267,12 +1276,22 @@ __device__ inline bool ctl_keep(const CtlSel &S, uint32_t ky, int &jk, int &jp) 
 //          logits, one fp32 addition per token, and runs every step on the sums l'; a token with l' = -inf is never kept.  The row copy
 //          stays the network's l.  The index is workgroup-uniform: a slot with -1 reads no table and executes the arithmetic of the
 //          kernel without BIAS, operation for operation.  BIAS = false compiles to what the body was before the flag existed.
-// Inlined into its __global__ entries (eight without BIAS, eight with); DESIGN.md §5 ("One body per sampler family") records what was
-// compared against the two separate kernel templates it replaces.
-template <bool FAST, bool LP, bool GIVEN, bool BIAS = false>
+//   REP    "repetition penalty" (talkshow_hip.h, step 0b): a clip slot whose record has window W > 0 counts, per token, the codes its
+//          last min(r, W) rows left in this column's ring (wave 0 copies them into s_rep ahead of the first barrier; every thread then
+//          counts matches against its own tokens: in the vector path by comparisons unrolled over the 8 registers, never by indexing
+//          them) and subtracts presence + frequency * count from the tokens it met, behind step 0 and ahead of step 1.  The thread that
+//          stores tok32 and the code stores the code into ring slot r & 63 too, a forced workgroup included.  The record is
+//          workgroup-uniform: a slot with W = 0 touches no ring and executes the arithmetic of the kernel without REP, operation for
+//          operation.  REP = false compiles to what the body was before the flag existed.
+//          W = 64: slot r & 63 holds row r - 64, the OLDEST entry read, and is the entry written.  The reads are wave 0's, ahead of the
+//          barrier behind them; the store comes behind every barrier of the body, and a ring belongs to one workgroup of one launch.
+//          (A forced workgroup without LP returns ahead of the barriers: it reads no entry at all.)
+// Inlined into its __global__ entries (eight without BIAS, eight with, eight with BIAS and REP); DESIGN.md §5 ("One body per sampler
+// family") records what was compared against the two separate kernel templates it replaces.
+template <bool FAST, bool LP, bool GIVEN, bool BIAS = false, bool REP = false>
 __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride,
                                                 const unsigned char *keep, long keep_stride, float *sf, int *si, float &s_thr, int &s_last,
-                                                uint32_t *s_tie, ctl_u64 (*hist)[256]) {
+                                                uint32_t *s_tie, ctl_u64 (*hist)[256], int *s_rep = nullptr) {
     const SampleParams &p = cp.s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *lg = sample_row(p, b);
@@ -1298,8 +1317,40 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     if constexpr (BIAS && FAST) {
         if (bias) sample_load8(bias, v0, xb);   // beside the logits: both pairs of loads are in flight ahead of the row copy
     }
+    // REP: the clip's record (workgroup-uniform: one uniform load), its ring of this column, the launch's row r and the min(r, W) entries
+    // to count.  The window is clamped to the ring: s_rep holds SAMPLE_REP_RING entries whatever a record says
+    [[maybe_unused]] int rep_n = 0, rep_slot = 0;
+    [[maybe_unused]] float rep_pres = 0.f, rep_freq = 0.f;
+    [[maybe_unused]] int32_t *ring = nullptr;
+    [[maybe_unused]] bool rep_any = false;     // generic path: one of this thread's tokens is in the window
+    if constexpr (REP) {
+        const SampleRep rr = cp.rep[b];
+        if (rr.window > 0) {
+            const uint32_t r = (p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u)) >> 1;
+            ring = cp.rep_ring + ((long)b * 2 + cp.bias_col) * SAMPLE_REP_RING;
+            rep_slot = (int)(r & (uint32_t)(SAMPLE_REP_RING - 1));
+            rep_pres = rr.presence;
+            rep_freq = rr.frequency;
+            if (!(GIVEN && !LP && forced)) {   // rows r - 1, r - 2, ...: wave 0 alone (rep_n <= 64), ahead of the first barrier
+                rep_n = (int)min(r, (uint32_t)min(rr.window, SAMPLE_REP_RING));
+                if (tid < rep_n) s_rep[tid] = ring[(r - 1u - (uint32_t)tid) & (uint32_t)(SAMPLE_REP_RING - 1)];
+            }
+        }
+    }
+    auto rep_count = [&](int v) -> int {
+        int c = 0;
+        if constexpr (REP) {
+            for (int i = 0; i < rep_n; ++i) c += s_rep[i] == v ? 1 : 0;
+        }
+        return c;
+    };
     auto logit = [&](int k) -> float {
         if constexpr (FAST) return x[k];
+        else if constexpr (REP) {
+            float l = lg[v0 + k];
+            if (bias) l = l + bias[v0 + k];
+            return rep_any ? rep_penalise(l, rep_count(v0 + k), rep_pres, rep_freq) : l;
+        }
         else if constexpr (BIAS) return bias ? lg[v0 + k] + bias[v0 + k] : lg[v0 + k];
         else return lg[v0 + k];
     };
@@ -1320,8 +1371,33 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
             if (tid == 0) {
                 p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
                 p.codes[(long)b * p.code_stride] = gcode;
+                if constexpr (REP) {
+                    if (ring) ring[rep_slot] = given_token(gcode, p.V);   // a taken code enters the history
+                }
             }
             return;
+        }
+    }
+    // REP, step 0b: l'' = l' - (presence + frequency * c) for the tokens the window met
+    if constexpr (REP) {
+        if (rep_n > 0) {   // workgroup-uniform
+            __syncthreads();
+            if constexpr (FAST) {
+                int cnt[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) cnt[k] = 0;
+                for (int i = 0; i < rep_n; ++i) {
+                    const int d = s_rep[i] - v0;
+                    if ((unsigned)d < 8u) {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) cnt[k] += d == k ? 1 : 0;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) x[k] = rep_penalise(x[k], cnt[k], rep_pres, rep_freq);
+            } else {
+                for (int i = 0; i < rep_n; ++i) rep_any = rep_any || (s_rep[i] >= v0 && s_rep[i] < v1);
+            }
         }
     }
 
@@ -1466,6 +1542,9 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
                 sample_store_unowned(out, gcode, p.V);
                 p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
                 p.codes[(long)b * p.code_stride] = gcode;
+                if constexpr (REP) {
+                    if (ring) ring[rep_slot] = given_token(gcode, p.V);
+                }
             }
             return;
         }
@@ -1496,6 +1575,9 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         const int choice = si[0];
         p.tok32[(long)b * p.tok_stride] = choice;
         p.codes[(long)b * p.code_stride] = choice;
+        if constexpr (REP) {
+            if (ring) ring[rep_slot] = choice;
+        }
     }
     if constexpr (LP) {
         const int choice = si[0];
@@ -1551,15 +1633,55 @@ __global__ __launch_bounds__(256) void sample_ctl_bias_given_kernel(const Sample
     __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
     sample_ctl_body<FAST, LP, true, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie, hist);
 }
+// "repetition penalty": the two families once more with BIAS = true and REP = true, launched only for a run that brings records
+// (p.rep != null).  A run without tables brings an index of -1 everywhere, which the BIAS path treats as "no table, same arithmetic"
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_rep_kernel(const SampleCtlParams cp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ int s_rep[SAMPLE_REP_RING];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, false, true, true>(cp, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist, s_rep);
+}
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_rep_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ int s_rep[SAMPLE_REP_RING];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, true, true, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie, hist,
+                                                s_rep);
+}
 // what a launch with tables needs beyond its sibling's checks; the vector path also needs 16-byte aligned table rows (V = 2048: every row
 // of an aligned block is)
 static bool sample_bias_ok(const SampleCtlParams &p) { return p.ctl && p.bias_index && (p.bias_col == 0 || p.bias_col == 1); }
 static bool sample_bias_fast(const SampleCtlParams &p) { return (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0; }
+// and a launch with records: its ring, and the index table the BIAS path reads (tables themselves are optional)
+static bool sample_rep_ok(const SampleCtlParams &p) { return p.ctl && p.rep_ring && p.bias_index && (p.bias_col == 0 || p.bias_col == 1); }
 
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
     if (!p.ctl || p.s.V < 1 || p.s.V > SAMPLE_CTL_MAX_V || (p.s.mode != TS_SAMPLE_UNIFORMS && p.s.mode != TS_SAMPLE_PHILOX)) return hipErrorInvalidValue;
     const long ls = p.s.logit_stride ? p.s.logit_stride : (long)p.s.V;
     const bool fast = p.s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s.logits) & 15) == 0;
+    if (p.rep) {
+        if (!sample_rep_ok(p)) return hipErrorInvalidValue;
+        const bool bfast = fast && sample_bias_fast(p);
+        if (p.logprob) {
+            if (bfast) hipLaunchKernelGGL((sample_ctl_rep_kernel<true, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((sample_ctl_rep_kernel<false, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+        } else if (bfast) {
+            hipLaunchKernelGGL((sample_ctl_rep_kernel<true, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((sample_ctl_rep_kernel<false, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.bias) {
         if (!sample_bias_ok(p)) return hipErrorInvalidValue;
         const bool bfast = fast && sample_bias_fast(p);
@@ -1589,7 +1711,7 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
     if (!p.rows || !p.given || s.V < 1) return hipErrorInvalidValue;
     if (s.mode != TS_SAMPLE_GREEDY && s.mode != TS_SAMPLE_UNIFORMS && s.mode != TS_SAMPLE_PHILOX) return hipErrorInvalidValue;
     if (!p.c.ctl) {
-        if (p.c.kept || p.c.bias) return hipErrorInvalidValue;
+        if (p.c.kept || p.c.bias || p.c.rep) return hipErrorInvalidValue;
         if (p.c.logprob) hipLaunchKernelGGL(sample_lp_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(sample_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
         return hipGetLastError();
@@ -1597,6 +1719,19 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
     if (s.V > SAMPLE_CTL_MAX_V || s.mode == TS_SAMPLE_GREEDY) return hipErrorInvalidValue;
     const long ls = s.logit_stride ? s.logit_stride : (long)s.V;
     const bool fast = s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(s.logits) & 15) == 0;
+    if (p.c.rep) {
+        if (!sample_rep_ok(p.c)) return hipErrorInvalidValue;
+        const bool bfast = fast && sample_bias_fast(p.c);
+        if (p.c.logprob) {
+            if (bfast) hipLaunchKernelGGL((sample_ctl_rep_given_kernel<true, true>), dim3(s.B), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((sample_ctl_rep_given_kernel<false, true>), dim3(s.B), dim3(256), 0, stream, p);
+        } else if (bfast) {
+            hipLaunchKernelGGL((sample_ctl_rep_given_kernel<true, false>), dim3(s.B), dim3(256), 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((sample_ctl_rep_given_kernel<false, false>), dim3(s.B), dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.c.bias) {
         if (!sample_bias_ok(p.c)) return hipErrorInvalidValue;
         const bool bfast = fast && sample_bias_fast(p.c);

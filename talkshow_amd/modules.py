@@ -342,7 +342,7 @@ class GatedPixelCNN(NativeModule):
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
             want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None, given_keep=None,
-            style=None, code_bias=None):
+            style=None, code_bias=None, repeat=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
@@ -375,7 +375,18 @@ class GatedPixelCNN(NativeModule):
         clips, or a list with, per clip, None, a table or a {"body", "hand"} dict.  Row 0 is added to the logits of column 0 and row 1 to
         those of column 1 ahead of the sampling rule (`sampling.biased`); -inf bans a code.  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only.
         Goes through the mixed entry with equal lengths (`ts_pixelcnn_generate_mixed_bias`): not with want_logits or pre_codes.
-        ValueError naming the clip for a bad table, before any device work.  None (the default): no return value and no launch changes."""
+        ValueError naming the clip for a bad table, before any device work.  None (the default): no return value and no launch changes.
+        repeat: a REPETITION PENALTY over a window of earlier codes (`_lib.repeat_table`; talkshow_hip.h, "repetition penalty"): one record
+        (window, presence, frequency) or dict for all clips, or a list with one per clip.  A code the clip produced c > 0 times in the last
+        `window` rows of the same column loses presence + frequency * c ahead of the sampling rule (`sampling.penalised`).
+        TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only.  Goes through the mixed entry with equal lengths (`ts_pixelcnn_generate_mixed_repeat`):
+        not with want_logits or pre_codes.  ValueError naming the clip for a bad record, before any device work.  None (the default): no
+        return value and no launch changes."""
+        if repeat is not None:
+            if not self.bh_model:
+                raise NotImplementedError("a repetition penalty exists for the bh_model=True chain (ts_pixelcnn_generate_mixed_repeat), not for the single-stack form")
+            if want_logits or pre_codes is not None:
+                raise ValueError("run: a repetition penalty goes through the mixed entry, which takes no logits output and no pre_codes")
         if code_bias is not None:
             if not self.bh_model:
                 raise NotImplementedError("a code bias exists for the bh_model=True chain (ts_pixelcnn_generate_mixed_bias), not for the single-stack form")
@@ -416,6 +427,7 @@ class GatedPixelCNN(NativeModule):
         if sampling is not None:   # validated (ValueError names the clip) before any device work
             ctl, n_ctl = _lib.sampling_table(sampling, B, self.input_dim, mode)
         btab, bidx = _lib.code_bias_block(code_bias, B, self.input_dim, who="run", mode=mode)   # ValueError before any device work
+        rtab, n_rep = _lib.repeat_table(repeat, B, self.input_dim, who="run", mode=mode)       # too
         kblock = None
         if given_keep is not None:   # ValueError before any device work, too (without given rows there is nothing to select from)
             kblock = _lib.given_keep_block(given_keep, _lib.given_counts(given, None, B), [H] * B, who="run")
@@ -451,7 +463,7 @@ class GatedPixelCNN(NativeModule):
                 self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, W, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0, _lib.stream_ptr()))
             return codes, logits
-        if given is not None or sblock is not None or btab is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
+        if given is not None or sblock is not None or btab is not None or rtab is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
             i32p = C.POINTER(C.c_int32)
             lens = np.full(B, 4 * H, np.int32)
             lens_dev = upload(lens, dev)
@@ -462,7 +474,16 @@ class GatedPixelCNN(NativeModule):
             gargs = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
                      _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), ctl, n_ctl, _lib.dptr(lp),
                      _lib.dptr(block_dev), table.ctypes.data_as(i32p) if given is not None else None, None)
-            if btab is not None:
+            if rtab is not None:
+                keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
+                style_dev = upload(sblock, dev) if sblock is not None else None
+                bias_dev = upload(btab, dev) if btab is not None else None
+                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_repeat(*gargs, _lib.dptr(keep_dev), _lib.dptr(style_dev),
+                                                                         int(sblock.shape[1]) if sblock is not None else 0, _lib.dptr(bias_dev),
+                                                                         int(btab.shape[0]) if btab is not None else 0,
+                                                                         bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep,
+                                                                         _lib.stream_ptr()))
+            elif btab is not None:
                 keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
                 style_dev = upload(sblock, dev) if sblock is not None else None
                 bias_dev = upload(btab, dev)

@@ -140,7 +140,7 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
 
 
 def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None,
-                     given=None, given_poses=None, given_keep=None, style=None, code_bias=None):
+                     given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -165,7 +165,9 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     one row per code row, or one (NC,) / (B, NC) array for all (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_style`; a blend
     interpolates the conditioning vectors, it is not a mixture of the speakers' distributions).  The face half keeps `face_ids`.
     code_bias: which codes the BODY half of a recording may use — one (2, V) table for all, or per recording None, a (2, V) table or a
-    {"body", "hand"} dict; -inf bans a code (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_bias`).  The face half has no codes."""
+    {"body", "hand"} dict; -inf bans a code (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_bias`).  The face half has no codes.
+    repeat: a repetition penalty over a window of earlier codes for the BODY half — one (window, presence, frequency) record or dict for
+    all, or a list with one per recording (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_repeat`)."""
     import ctypes as C
 
     import numpy as np
@@ -218,6 +220,8 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
         style = _lib.style_block(style, rows_sub, body.num_classes, order, who="whole_body_clips", ids=ids)
     if code_bias is not None:      # validated before the first launch, too; the body half only
         code_bias = _lib.code_bias_block(code_bias, B, body.generator.input_dim, order, who="whole_body_clips", mode=mode)
+    if repeat is not None:         # and the records
+        repeat = _lib.repeat_table(repeat, B, body.generator.input_dim, order, who="whole_body_clips", mode=mode)
     dev = body.generator._dev()
     # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
     wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
@@ -234,7 +238,7 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
         side.wait_stream(cur)
     with torch.cuda.stream(side):
         _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling,
-                                               given=given, given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias)
+                                               given=given, given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

@@ -1,5 +1,6 @@
 """Numpy twin of the sampler with per-clip controls (`csrc/vq.hip::sample_ctl_kernel`; the rule: `include/talkshow_hip.h`, ts_sampling,
-steps 1-5, and "code bias": step 0 and the kept-set sentence, `biased` / `keep_mask_bias` / `sample_bias` below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
+steps 1-5, "code bias": step 0 and the kept-set sentence, `biased` / `keep_mask_bias` / `sample_bias` below, and "repetition penalty":
+step 0b, `repeat_counts` / `penalised` / `sample_repeat` / `decode_repeat` below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
 bit for bit, so tests compare indices and kept sets for equality.  A record is (temperature, top_p, top_k), `_lib.sampling_record`'s form.
 
 The kept set is written here from its DEFINITION (sort the row, cumulative integer masses in rank order); the kernel finds the same set by
@@ -297,6 +298,114 @@ def ban_bias(codes, V):
         if not np.isfinite(t[j]).any():
             raise ValueError(f"ban_bias: column {j} bans every code")
     return t
+
+
+# ---- repetition penalty (include/talkshow_hip.h, "repetition penalty"; csrc/vq.hip: sample_ctl_body<., ., ., true, REP = true>) ---------------
+# A record is (window, presence, frequency), `_lib.repeat_record`'s form.
+
+REPEAT_MAX_WINDOW = 64      # the ring: the code of row r of a column lives at index r & 63
+
+
+def repeat_counts(history, V, window):
+    """History: c_v for every token.  history = the codes of rows 0 .. r - 1 of ONE clip and ONE column, oldest first (or any tail of them
+    that holds the last min(r, window) rows) -> (V,) int32, how often each code occurs in the last `window` entries.  Codes outside [0, V)
+    (a given code may be one) match no token.  window 0: zeros."""
+    h = np.asarray(history, np.int64).reshape(-1)
+    W = int(window)
+    if not 0 <= W <= REPEAT_MAX_WINDOW:
+        raise ValueError(f"repeat_counts: window {W} is outside [0, {REPEAT_MAX_WINDOW}]")
+    h = h[h.size - min(h.size, W):]
+    h = h[(h >= 0) & (h < int(V))]
+    return np.bincount(h, minlength=int(V)).astype(np.int32)
+
+
+def penalised(row, counts, record):
+    """Step 0b: for c_v > 0, f = frequency * float(c_v), g = presence + f, l''_v = l'_v - g — three float32 operations, each rounded
+    (numpy.float32 arithmetic: no fused multiply-add); for c_v == 0 the token's bits (a -0 stays -0)."""
+    row = np.asarray(row, F32).reshape(-1)
+    c = np.asarray(counts).reshape(-1)
+    _, presence, frequency = record
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = (F32(frequency) * c.astype(F32)).astype(F32)
+        g = (F32(presence) + f).astype(F32)
+        out = (row - g).astype(F32)
+    return np.where(c > 0, out, row).astype(F32)
+
+
+def _per_row(x, B, width):
+    if isinstance(x, tuple) and len(x) == width and not isinstance(x[0], (tuple, list)):
+        return [x] * B
+    return list(x)
+
+
+def sample_repeat(logits, u, records, repeat, history, position, bias=None, index=None, column=0, given=None, forced=None):
+    """One launch of the samplers under a repetition penalty, restated, ring update included (`ts_op_sample_repeat`): logits (B,V), u
+    (B,), records = None (neutral), one sampling record or B, repeat = one (window, presence, frequency) record or B, history (B,R) the
+    codes of rows r - R .. r - 1 of this column, oldest first, R = min(r, 64), r = position >> 1; bias (NB,2,V) / index (B,) / column as
+    for `sample_bias` (bias None: no tables); given (B,) codes and forced (B,) bool: the rows that TAKE their given code ->
+    (idx (B,) int64, kept (B,V) bool, logprob (B,) float32, ring (B,64) int32).  The ring starts as -1 everywhere, holds the history where
+    a pass would have left it (row r' at r' & 63) and, for a row with window > 0, the row's code at r & 63 (a given code outside [0, V):
+    -1); a row with window 0 touches no ring and is `sample_bias`'s row."""
+    logits = np.asarray(logits, F32)
+    B, V = logits.shape
+    r = int(position) >> 1
+    R = min(r, REPEAT_MAX_WINDOW)
+    history = np.zeros((B, 0), np.int64) if R == 0 else np.asarray(history, np.int64).reshape(B, R)
+    records = _per_row((1.0, 1.0, 0) if records is None else records, B, 3)
+    repeat = _per_row(repeat, B, 3)
+    idx = np.zeros(B, np.int64)
+    kept = np.zeros((B, V), bool)
+    lp = np.zeros(B, F32)
+    ring = np.full((B, REPEAT_MAX_WINDOW), -1, np.int32)
+    for i in range(R):
+        ring[:, (r - R + i) & (REPEAT_MAX_WINDOW - 1)] = history[:, i]
+    for b in range(B):
+        t = -1 if bias is None else int(index[b])
+        row_bias = None if t < 0 else np.asarray(bias, F32)[t, int(column)]
+        lb = biased(logits[b], row_bias)
+        W = int(repeat[b][0])
+        lpen = penalised(lb, repeat_counts(history[b], V, W), repeat[b]) if W > 0 else lb
+        kept[b] = keep_mask(lpen, records[b])
+        if row_bias is not None:
+            kept[b] &= lpen != F32(-np.inf)
+        if forced is not None and forced[b]:
+            code = int(given[b])
+            idx[b] = code
+            if not 0 <= code < V:
+                lp[b] = F32(np.nan)
+            elif not kept[b, code]:
+                with np.errstate(divide="ignore"):
+                    lp[b] = F32(np.log(np.float64(0.0)))
+            else:
+                lp[b] = logprob(lpen, code, records[b])
+            tok = code if 0 <= code < V else -1
+        else:
+            idx[b] = tok = draw(lpen, u[b], records[b][0], kept[b])
+            lp[b] = logprob(lpen, idx[b], records[b])
+        if W > 0:
+            ring[b, r & (REPEAT_MAX_WINDOW - 1)] = tok
+    return idx, kept, lp, ring
+
+
+def decode_repeat(logits, u, record, repeat, bias=None, given=None, forced=None):
+    """The row loop of ONE clip over logits a decode returned: logits (H,2,V) (the network's l of every position: the penalty does not
+    change them as long as the codes agree), u (H,2) uniforms, record = a sampling record or None, repeat = the clip's (window, presence,
+    frequency), bias = the clip's (2,V) table or None, given (H,2) codes and forced (H,2) bool or None -> (codes (H,2) int64, logprob
+    (H,2) float32): position (r, j) is `sample_repeat` on the codes this loop produced in column j so far."""
+    logits = np.asarray(logits, F32)
+    H = logits.shape[0]
+    codes = np.zeros((H, 2), np.int64)
+    lps = np.zeros((H, 2), F32)
+    tables = None if bias is None else np.asarray(bias, F32)[None]
+    for r in range(H):
+        R = min(r, REPEAT_MAX_WINDOW)
+        for j in range(2):
+            hist = np.where((codes[r - R:r, j] >= 0) & (codes[r - R:r, j] < logits.shape[2]), codes[r - R:r, j], -1)[None]
+            f = None if forced is None else [bool(forced[r, j])]
+            g = None if given is None else [int(given[r, j])]
+            i, _, l, _ = sample_repeat(logits[r, j][None], [u[r, j]], record, repeat, hist, 2 * r + j, tables, [0], j, g, f)
+            codes[r, j], lps[r, j] = i[0], l[0]
+    return codes, lps
 
 
 def keep_forced(G, keep, r, j):
