@@ -297,6 +297,22 @@ int ts_debug_smplx_joints_tail(ts_smplx *m, const float *vs, int64_t N, float *j
  * graphs that serve first-time shapes of any length; bounded, least recently used out first), or -1. */
 int ts_debug_pixelcnn_graphs(ts_pixelcnn *pix, void *stream);
 
+/* ---- code tables of the PixelCNN chain (csrc/code_tables.hip) ----
+ * ts_debug_code_tables_plan (host only): the tables of a network of V codes and dim D under knob_list ("NAME=VALUE,...", null = defaults) and
+ * the launches of code row r, column j of a pass of B clips that are lookups.  out12 = {tables fit (cap, kernels), the pass takes them, K-split
+ * waves of slot V0, row sets per V0 table, bytes of the three V0 tables, waves of hg_0, bytes of the hg_0 table, slot V0 of row r is a lookup,
+ * it writes the Q1 rider (row r+1 < last_row), it writes the Q0 rider (row r+2 < last_row), hg_0 of column j is a lookup, the cap in bytes}. */
+int ts_debug_code_tables_plan(int V, int D, int B, int r, int j, int last_row, const char *knob_list, int64_t *out12);
+/* TS_PIX_TABLES (-1 / 0 / 1) for one model object; builds the tables where wanted, drops the object's captured graphs.  mode -2 changes nothing.
+ * Returns 1: tables exist, 0: not, -1: error. */
+int ts_debug_pixelcnn_tables(ts_pixelcnn *pix, int mode);
+/* A whole work buffer of `stream` (which = 0 HV, 1 OV0, 2 Q1, 3 Q0, 4 G) copied to buf_dev (put = 0) or filled from it (put = 1); returns floats. */
+int64_t ts_debug_pixelcnn_work(ts_pixelcnn *pix, void *stream, int which, float *buf_dev, int64_t cap_floats, int put);
+/* One lookup launch on row-major caller buffers: which = 0 slot V0 (tok (B,2) int32; add1, add2 (B,4D) or null; cls (B,2D); pre (B,4D); out
+ * (B,2D); q1, q0 (B,4D) or null), 1 hg_0 of column 1 (tok (B,2), column 0 read; add1 (B,2D) or null; cls (B,2D); out (B,D)). */
+int ts_debug_code_table_stage(ts_pixelcnn *pix, int which, const int32_t *tok_dev, int B, const float *add1, const float *add2, const float *cls,
+                              float *pre, float *out, float *q1, float *q0, void *stream);
+
 /* Host-only (no GPU): the chunk plan of a mixed pass (talkshow_hip.h, "mixed passes").  hrows (B,) = code rows per clip, >= 1 and
  * non-increasing; max_counts = distinct active clip counts a pass may use (<= 0: the library's bound, 12).  active_out (ceil(hrows[0] / 8),)
  * or NULL: the clips chunk k = rows [8 k, 8 k + 8) runs with = #{b : hrows[b] > 8 k} rounded up to a multiple of the returned grid (capped

@@ -215,6 +215,10 @@ SIGNATURES = {
     "ts_op_conv_taps48_timed": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(C.c_float), _vp]),
     "ts_op_conv1d_strided_timed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_float), _vp]),
     "ts_debug_pixelcnn_graphs": (_i, [_vp, _vp]),
+    "ts_debug_code_tables_plan": (_i, [_i, _i, _i, _i, _i, _i, C.c_char_p, C.POINTER(_i64)]),
+    "ts_debug_pixelcnn_tables": (_i, [_vp, _i]),
+    "ts_debug_pixelcnn_work": (_i64, [_vp, _vp, _i, _vp, _i64, _i]),
+    "ts_debug_code_table_stage": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ts_debug_conv_run": (_i, [_vp, C.POINTER(ConvProblem), _i, C.c_char_p, _i, C.POINTER(_i), _vp]),
     "ts_debug_conv_sk_plan": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "ts_debug_conv_sk_run": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),

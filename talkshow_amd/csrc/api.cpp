@@ -40,6 +40,7 @@ static Knobs read_knobs(Get get) {
     v.prof_log = num("TS_PROF_LOG", 0) != 0;
     if (const char *e = get("TS_NO_GRAPH")) v.no_graph = e[0] && e[0] != '0';
     v.pix_defer_p = num("TS_PIX_DEFER_P", -1);
+    v.pix_tables = num("TS_PIX_TABLES", -1);
     v.skinny_v = num("TS_SKINNY_V", 1);
     v.skinny_nt = num("TS_SKINNY_NT", 16);
     v.skinny_tiled = num("TS_SKINNY_TILED", 1) != 0;
@@ -112,6 +113,23 @@ int ts_assemble_full_mixed(ts_ctx *ctx, const float *body, const int32_t *tb_dev
     if (B < 1 || Tb_max < 1 || Tf_max < 1) return fail("ts_assemble_full_mixed: empty input");
     MiscScope ms(ctx, (hipStream_t)stream);
     TS_HIP(launch_assemble_full_lens(body, tb_dev, face, tf_dev, lower_pose33, B, Tb_max, Tf_max, out, (hipStream_t)stream));
+    return 0;
+}
+
+// Host-only (no GPU): the code tables of a PixelCNN of V codes and dim D under knob_list, and which launches of code row r, column j of a
+// pass of B clips are lookups.  out12 = {the tables fit, the pass takes them, K-split waves of V0, row sets per V0 table, bytes of the three
+// V0 tables, waves of hg_0, bytes of the hg_0 table, slot V0 of row r is a lookup, it writes the Q1 rider, it writes the Q0 rider, hg_0 of
+// column j is a lookup, the cap in bytes}
+int ts_debug_code_tables_plan(int V, int D, int B, int r, int j, int last_row, const char *knob_list, int64_t *out12) {
+    if (!out12 || B < 1 || r < 0 || j < 0 || j > 1) return fail("ts_debug_code_tables_plan: bad argument");
+    const Knobs k = knob_list ? ts::knobs_from_list(knob_list) : Knobs();
+    const ts::CodeTablePlan t = ts::code_table_plan(V, D, k);
+    const bool takes = ts::code_table_pass(t.fits && k.pix_tables != 0, k.pix_tables, B);
+    const bool v0 = takes && ts::code_table_v0_row(r);
+    const int64_t o[12] = {t.fits, takes, t.waves_v0, t.sets_v0, (int64_t)t.bytes_v0, t.waves_hg, (int64_t)t.bytes_hg, v0,
+                           v0 && ts::code_table_rider(r, 1, last_row), v0 && ts::code_table_rider(r, 0, last_row),
+                           takes && ts::code_table_hg_col(j), (int64_t)ts::CODE_TABLE_CAP_BYTES};
+    for (int i = 0; i < 12; ++i) out12[i] = o[i];
     return 0;
 }
 

@@ -259,6 +259,43 @@ const float *skinny_zero_buffer(int device);
 // TS_SKINNY_TRACE=1 instrumentation: records of 6 u64 {t_entry, t_desc, t_mfma_done, t_reduced, t_end, cnt<<32|workgroups}
 int skinny_trace_read(unsigned long long *out, int max_records);
 
+// ---- code tables of the chain (code_tables.hip): slot V0 and column 1's hg_0 as lookups of slice sums ----
+// The K split of a chain GEMM: W waves (plan_skinny's rule for the 16-column kernels), wave w owning q-steps [Q w / W, Q (w + 1) / W) of 16 k
+inline int code_table_waves(int K) { return K / 8 >= 32 ? 8 : 4; }
+constexpr int CODE_TABLE_MAX_SETS = 5;   // row sets of a table: one prefix (the first code's slices) + one per slice of a second code (W / 2 <= 4)
+// one row set: out[code][0..N) = sum in index order of slices [s0, s1) of W[n][k] . emb[code][k - kcol], K = the GEMM's whole K
+struct CodeTableBuild {
+    const float *W;     // [N][ldw] row-major
+    long ldw;
+    int N, K, waves, s0, s1;
+    const float *emb;   // [V][D]
+    int D, V, kcol;
+    float *out;         // [V][N]
+};
+hipError_t launch_code_table_build(const CodeTableBuild &p, hipStream_t stream);
+// the gate problem of a slot (+ up to two linear riders that share its codes) from tables; see code_tables.hip for the arithmetic
+struct CodeTableStage {
+    const float *tab[3];       // gate, rider 0, rider 1: [nsets][V][N]
+    long set_stride;           // V * N
+    int nsets;                 // 1: only tok0 (prefix rows); 1 + s: tok1's s slice rows are added one by one behind it
+    int M, N, gateD;           // clips; channels (weight rows) = groups of gateD tanh + gateD sigmoid
+    const int *tok0, *tok1;    // code of clip m at tok[m * tok_stride]; negative: the zero row
+    long tok_stride;
+    const float *bias, *add1, *add2;   // [N] / (M, stride) rows; null: +0.0
+    long add1_stride, add2_stride;
+    const float *cls;          // (M, cls_ld) class-conditioning rows, column n % cls_ld
+    int cls_ld;
+    float *pre;                // pre-gate values (M, pre_stride) or null; pre_tw: log2 of its tiled view width, 0 row-major
+    long pre_stride;
+    int pre_tw;
+    float *out;                // gated values (M, out_stride), N / 2 per clip
+    long out_stride;
+    int out_tw;
+    float *rider[2];           // (M, rider_stride) rows of N, or null
+    long rider_stride;
+};
+hipError_t launch_code_table_stage(const CodeTableStage &p, hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------------
 // VQ / sampling / glue kernels
 // ------------------------------------------------------------------------------------------------
@@ -351,6 +388,7 @@ struct Knobs {
     bool prof_log = false;      // TS_PROF_LOG=1: one stderr line per conv launch while ts_prof is enabled
     bool no_graph = false;      // TS_NO_GRAPH=1: PixelCNN launches go out eagerly
     int pix_defer_p = -1;       // TS_PIX_DEFER_P: -1 auto (<= 128 clips), 0 / 1 forced
+    int pix_tables = -1;        // TS_PIX_TABLES: slot V0 and column 1's hg_0 from code tables (code_tables.hip): -1 auto (passes of >= 64 clips), 0 never (the GEMM launches; no tables are built), 1 every pass
     int skinny_v = 1;           // TS_SKINNY_V=0: generic chain kernels
     int skinny_nt = 16;         // TS_SKINNY_NT=32: 32-column generic kernel
     bool skinny_tiled = true;   // TS_SKINNY_TILED=0: row-major chain operands
@@ -361,6 +399,37 @@ struct Knobs {
     int wide_ablate = 0;        // TS_SKINNY_WIDE_ABLATE=2|4 (trace builds): no loads / no MFMAs in the wide kernel
 };
 const Knobs &knobs();
+
+// ---- code tables: host arithmetic (ts_debug_code_tables_plan, tests/test_code_tables_host.py) ----
+// Tables are skipped, and the GEMM launches kept, where V x 4D x 4 B x 15 (the three V0 tables at five row sets) exceeds this: the
+// shipped network (V = 2048, D = 256) takes 120 MiB + 4 MiB, an odd configuration still loads
+constexpr size_t CODE_TABLE_CAP_BYTES = (size_t)192 << 20;
+// TS_PIX_TABLES = -1: passes (chunks of a mixed pass: their active clips) of at least this many clips take the tables.  Bits are equal
+// either way, so the rule is free; the measurement behind it is in DESIGN.md §4
+constexpr int CODE_TABLE_MIN_CLIPS = 64;
+struct CodeTablePlan {
+    bool fits = false;                   // under the cap, and on kernels whose K split the tables reproduce (not TS_SKINNY_NT=32)
+    int waves_v0 = 0, sets_v0 = 0, waves_hg = 0;
+    size_t bytes_v0 = 0, bytes_hg = 0;   // all three V0 tables; the hg_0 table
+};
+inline CodeTablePlan code_table_plan(int V, int D, const Knobs &k) {
+    CodeTablePlan t;
+    if (V < 1 || D < 32 || D % 32) return t;
+    t.waves_v0 = code_table_waves(2 * D);
+    t.sets_v0 = 1 + t.waves_v0 / 2;
+    t.waves_hg = code_table_waves(D);
+    t.bytes_v0 = (size_t)3 * t.sets_v0 * V * 4 * D * sizeof(float);
+    t.bytes_hg = (size_t)V * 2 * D * sizeof(float);
+    t.fits = k.skinny_nt != 32 && (size_t)V * 4 * D * sizeof(float) * 15 <= CODE_TABLE_CAP_BYTES;
+    return t;
+}
+inline bool code_table_pass(bool built, int mode, int B) { return built && (mode > 0 || (mode < 0 && B >= CODE_TABLE_MIN_CLIPS)); }
+// which launches of code row r become lookups: slot V0 from row 1 on (row 0 has no code above it), hg_0 of column 1 only (column 0 has
+// none to its left); a rider is written iff the row it serves is generated (the GEMM riders' rule)
+inline bool code_table_v0_row(int r) { return r >= 1; }
+inline bool code_table_hg_col(int j) { return j == 1; }
+inline bool code_table_rider(int r, int t, int last_row) { return r >= 1 && r + (2 - t) < last_row; }   // t = 1: Q1 of row r+1, t = 0: Q0 of row r+2
+
 
 // GELU(x) = x / 2 (1 + erf(x / sqrt 2)) for the conv epilogues of the face generator (reference: torch's exact-erf GELU behind the HF wav2vec2
 // layers of nets/spg/wav2vec.py).  libm's erff is two branches (|x| < 1: an odd polynomial; else 1 - exp(-poly)) with expf's own range

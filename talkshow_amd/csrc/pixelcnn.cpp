@@ -15,6 +15,8 @@
 // Launch plan of row r (every entry is ONE skinny_gemm launch over all clips of the pass; "|" separates independent
 // problems that share a launch):
 //   V0        v0.gate | v0.Q1 | v0.Q0                     gate: OV0 = gate(W2.E[r-1] + Q1[r] + Q0[r] + b + c0)
+//                                                         (rows r >= 1 of a pass that takes the code tables: ONE lookup launch, no GEMM;
+//                                                         so is hg_0 of column 1 — see ts_pixelcnn::CodeTables)
 //   V1        v1.gate | v1.P | v2h_0                      layer 1 reads OV0 directly: fusion_v[:, :D] (gated_pixelcnn_v2.py:137-144)
 //                                                         is composed into its two tap matrices on the host, the audio half
 //                                                         of the fusion becomes two per-row additive terms precomputed for
@@ -68,6 +70,19 @@ struct ts_pixelcnn {
     DevBuf w1m, b1m;                                         // head1': [HID][D or 2D], [HID]
     ConvLayer aud_h1;                                        // Wh1_1 applied to AEH for every row (l = 1 has AEH in place of XH_0)
     DevBuf cls_all;                                          // the NL class tables again, contiguous [NL][NC][2D]: what style_rows_kernel reads
+    // Code tables (code_tables.hip).  Two launches of a code row multiply nothing but embeddings of codes that are already known: slot
+    // V0 (W2 . E[r-1] and its riders W1 . E[r-1], W0 . E[r-1]) and hg_0 of column 1 (wh[0] . emb[code(r, 0)]).  The tables hold, per code,
+    // the slice sums the chain kernels would form (same MFMA, same k order, same K split), so a lookup launch that adds them in the
+    // kernels' order gives the kernels' bits without MFMAs, weight streams or whole-CU workgroups.  Built once per model from the weights
+    // alone, shared by every stream.  V0: per matrix 1 + W / 2 row sets of [V][4D] (the prefix of column 0's slices; column 1's slices one
+    // by one); hg_0: one row set of [V][2D].
+    struct CodeTables {
+        DevBuf v0[3];      // wvt[0][2] (the gate), wvt[0][1] (rider Q1), wvt[0][0] (rider Q0)
+        DevBuf hg;
+        int sets = 0;      // row sets of a V0 table
+        bool built = false;
+    } tables;
+    int tables_mode = -1;  // TS_PIX_TABLES: -1 auto (see use_tables), 0 the GEMM launches, 1 every pass
     bool use_graph = true;
     int defer_p = -1;     // the next-row projections P_l of the vertical stack ride with column 1's launches: -1 auto, 0 never, 1 always
     // tiled operand layouts (kernels.h, SkinnyParams::w_tiled): every weight matrix of the chain gets a tiled twin, and
@@ -379,7 +394,53 @@ struct Slot {   // one launch: up to SKINNY_MAX_PROBLEMS independent problems
     SkinnyParams p[SKINNY_MAX_PROBLEMS];
     int n = 0;
     void add(const SkinnyParams &q) { p[n++] = q; }
+    bool table = false;   // the slot is a code-table lookup (ts_pixelcnn::CodeTables): `ts` is launched, there are no problems
+    CodeTableStage ts;
 };
+
+// ---- code tables (the host arithmetic is in kernels.h: code_table_plan and the rules beside it) ----
+bool use_tables(const ts_pixelcnn *p, int B) { return code_table_pass(p->tables.built, p->tables_mode, B); }
+
+int build_code_tables(ts_pixelcnn *p) {
+    if (p->tables.built) return 0;
+    const CodeTablePlan t = code_table_plan(p->V, p->D, ts::knobs());
+    if (!t.fits) return 0;
+    const int V = p->V, D = p->D;
+    const size_t set = (size_t)V * 4 * D;
+    for (int m = 0; m < 3; ++m) {
+        TS_TRY(p->tables.v0[m].ensure(t.sets_v0 * set * sizeof(float)));
+        for (int st = 0; st < t.sets_v0; ++st) {   // set 0: column 0's slices summed; set 1 + i: slice W / 2 + i of column 1 alone
+            CodeTableBuild b;
+            b.W = p->wvt[0][2 - m]->f();
+            b.ldw = 2 * D;
+            b.N = 4 * D, b.K = 2 * D, b.waves = t.waves_v0;
+            b.s0 = st == 0 ? 0 : t.waves_v0 / 2 + st - 1;
+            b.s1 = st == 0 ? t.waves_v0 / 2 : b.s0 + 1;
+            b.emb = p->emb.f();
+            b.D = D, b.V = V, b.kcol = st == 0 ? 0 : D;
+            b.out = p->tables.v0[m].f() + st * set;
+            TS_HIP(launch_code_table_build(b, nullptr));
+        }
+    }
+    TS_TRY(p->tables.hg.ensure(t.bytes_hg));
+    CodeTableBuild b;
+    b.W = p->wh[0]->f();      // tap 0 block: the first D columns of [2D][2D]
+    b.ldw = 2 * D;
+    b.N = 2 * D, b.K = D, b.waves = t.waves_hg, b.s0 = 0, b.s1 = t.waves_hg;
+    b.emb = p->emb.f();
+    b.D = D, b.V = V, b.kcol = 0;
+    b.out = p->tables.hg.f();
+    TS_HIP(launch_code_table_build(b, nullptr));
+    TS_HIP(hipStreamSynchronize(nullptr));   // the chain's streams do not wait for the null stream
+    p->tables.sets = t.sets_v0;
+    p->tables.built = true;
+    return 0;
+}
+inline int tiled_log2(int w) {
+    int l = 0;
+    while ((1 << l) < w) ++l;
+    return w > 0 ? l : 0;
+}
 
 // the tiled view width of the work buffer that holds `ptr`, or 0 (row-major buffers / foreign pointers)
 int tiled_width_of(const ts_pixelcnn *p, const ts_pixelcnn::Work *w, const void *ptr) {
@@ -397,6 +458,11 @@ int launch_slot(ts_pixelcnn *p, ts_pixelcnn::Work *w, const Slot &a, const Slot 
     SkinnyParams q[SKINNY_MAX_PROBLEMS];
     const SkinnyParams *ps[SKINNY_MAX_PROBLEMS];
     int n = 0;
+    if (a.table) {   // a lookup launch: no GEMM, so not a skinny launch of the statistics; a rider (none today) would follow as its own launch
+        MiscScope ms(p->ctx, s);
+        TS_HIP(launch_code_table_stage(a.ts, s));
+        if (!b || b->n == 0) return 0;
+    }
     if (b)
         for (int i = 0; i < b->n; ++i) q[n++] = b->p[i];
     for (int i = a.n - 1; i >= 0; --i) q[n++] = a.p[i];
@@ -475,8 +541,30 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
             g.add2_stride = 4 * D;
         }
         gate_common(g, 0);
-        s.add(g);
-        for (int t = 1; t >= 0 && r >= 1; --t) {   // row r-1's codes as seen from row r+1 (kernel row 1) and r+2 (kernel row 0)
+        if (code_table_v0_row(r) && use_tables(p, B)) {   // the same sums from the code tables: one lookup launch for the gate and both riders
+            CodeTableStage &ts = s.ts;
+            std::memset(&ts, 0, sizeof(ts));
+            for (int m = 0; m < 3; ++m) ts.tab[m] = p->tables.v0[m].f();
+            ts.set_stride = (long)p->V * 4 * D;
+            ts.nsets = p->tables.sets;
+            ts.M = B, ts.N = 4 * D, ts.gateD = D;
+            ts.tok0 = tok + (size_t)((r - 1) % R) * 2;   // exactly where emb_row's gather reads the two codes of row r-1
+            ts.tok1 = ts.tok0 + 1;
+            ts.tok_stride = (long)R * 2;
+            ts.bias = g.bias;
+            ts.add1 = g.add1, ts.add1_stride = g.add1_stride;
+            ts.add2 = g.add2, ts.add2_stride = g.add2_stride;
+            ts.cls = g.clsrow, ts.cls_ld = g.cls_ld;
+            ts.pre = g.pre, ts.pre_stride = g.pre_stride, ts.pre_tw = tiled_log2(tiled_width_of(p, w, g.pre));
+            ts.out = g.out, ts.out_stride = g.out_stride, ts.out_tw = tiled_log2(tiled_width_of(p, w, g.out));
+            for (int t = 1; t >= 0; --t)
+                if (code_table_rider(r, t, c.last_row)) ts.rider[1 - t] = Q(t == 1 ? w->Q1 : w->Q0, r + (2 - t));
+            ts.rider_stride = 4 * D;
+            s.table = true;
+        } else {
+            s.add(g);
+        }
+        for (int t = 1; t >= 0 && r >= 1 && !s.table; --t) {   // row r-1's codes as seen from row r+1 (kernel row 1) and r+2 (kernel row 0)
             const int target = r + (2 - t);
             if (target >= c.last_row) continue;
             SkinnyParams q = base_params(B, 4 * D, EPI_LINEAR);
@@ -579,7 +667,23 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
         q.gateD = D;
         q.out = G(0);
         q.out_stride = D;
-        s.add(q);
+        if (code_table_hg_col(j) && use_tables(p, B)) {   // the code just sampled: its row of the hg_0 table in place of the GEMM
+            CodeTableStage &ts = s.ts;
+            std::memset(&ts, 0, sizeof(ts));
+            ts.tab[0] = p->tables.hg.f();
+            ts.set_stride = (long)p->V * 2 * D;
+            ts.nsets = 1;
+            ts.M = B, ts.N = 2 * D, ts.gateD = D;
+            ts.tok0 = tok + (size_t)(r % R) * 2 + 0;
+            ts.tok_stride = (long)R * 2;
+            ts.bias = q.bias;
+            ts.add1 = q.add1, ts.add1_stride = q.add1_stride;
+            ts.cls = q.clsrow, ts.cls_ld = q.cls_ld;
+            ts.out = q.out, ts.out_stride = q.out_stride, ts.out_tw = tiled_log2(tiled_width_of(p, w, q.out));
+            s.table = true;
+        } else {
+            s.add(q);
+        }
         out.push_back(s);
     }
     for (int l = 1; l < NL; ++l) {   // S_l
@@ -726,6 +830,10 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
 
 int run_row(ts_pixelcnn *p, const RunCfg &c, int r, bool need_h, hipStream_t s) {
     std::vector<Slot> V, H;
+    // Slot V0 from row 1 on and hg_0 of column 1 are lookups in the code tables (ts_pixelcnn::CodeTables) where the pass takes them:
+    // TS_PIX_TABLES = 1 every pass, 0 none, -1 (default) passes of at least CODE_TABLE_MIN_CLIPS = 64 clips — the passes whose V0 is a wide
+    // launch (one 128 KB workgroup per CU, which chains on other streams cannot share).  Below that V0 and hg_0 are `fast` launches of
+    // about the cost of the lookup launch, and hg_0 carries a deferred P_l besides.  Bits are equal either way.
     // Up to 128 clips the column-0 launches (vertical slot riding with the horizontal one) come to 272 workgroups at every
     // tile shape — 16 more than CUs, and the 16 doubled-up CUs set the launch time (5.9 vs 3.6 us at 32 clips).  The P_l
     // projections are only read by the next row: there they ride with column 1's launches (96 -> 160 workgroups).
@@ -752,7 +860,7 @@ int run_row(ts_pixelcnn *p, const RunCfg &c, int r, bool need_h, hipStream_t s) 
     for (size_t k = 0; k < H.size(); ++k) {
         Slot ride;
         // the last horizontal slots take what is left, so that every P_l has run before the row ends
-        while (pi < Pd.size() && H[k].n + ride.n < SKINNY_MAX_PROBLEMS && (ride.n == 0 || Pd.size() - pi > H.size() - 1 - k)) ride.add(Pd[pi++]);
+        while (!H[k].table && pi < Pd.size() && H[k].n + ride.n < SKINNY_MAX_PROBLEMS && (ride.n == 0 || Pd.size() - pi > H.size() - 1 - k)) ride.add(Pd[pi++]);
         TS_TRY(launch_slot(p, c.w, H[k], ride.n ? &ride : nullptr, s));
     }
     if (pi < Pd.size()) return fail("pixelcnn: deferred projections left over");
@@ -1013,6 +1121,8 @@ int ts_pixelcnn_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int V, int D, i
     }
     if (ts::knobs().no_graph) p->use_graph = false;
     if (ts::knobs().pix_defer_p >= 0) p->defer_p = ts::knobs().pix_defer_p;
+    p->tables_mode = ts::knobs().pix_tables;
+    if (p->tables_mode != 0) TS_TRY(build_code_tables(p.get()));   // where they do not fit (code_table_plan) the GEMM launches stay
     *out = p.release();
     return 0;
 }
@@ -1038,6 +1148,78 @@ int ts_pixelcnn_graph_stats(ts_pixelcnn *p, void *stream, int B, int H, int mode
     if (jt == w->graph_stats.end()) return fail("ts_pixelcnn_graph_stats: no captured graph for this shape");
     if (launches) *launches = jt->second.first;
     if (flops) *flops = jt->second.second;
+    return 0;
+}
+
+// ---- code tables: test entries (talkshow_hip_debug.h) ----
+// TS_PIX_TABLES for one model object: mode -1 / 0 / 1 as the variable (-2: change nothing, only answer); builds the tables if they are
+// wanted and fit.  Every captured graph of the object's per-stream Works is dropped (their launches belong to the old setting); streaming
+// sessions opened earlier keep theirs.
+// Returns 1 if the tables exist, 0 if not (mode 0 before any build, or they do not fit), -1 on error
+int ts_debug_pixelcnn_tables(ts_pixelcnn *p, int mode) {
+    if (!p || mode < -2 || mode > 1) return fail("ts_debug_pixelcnn_tables: bad argument") ? -1 : -1;
+    if (mode == -2) return p->tables.built ? 1 : 0;   // a question only
+    if (hipSetDevice(p->ctx->device) != hipSuccess) return fail("ts_debug_pixelcnn_tables: hipSetDevice") ? -1 : -1;
+    if (mode != 0 && build_code_tables(p) != 0) return -1;
+    p->tables_mode = mode;
+    {
+        std::lock_guard<std::mutex> g(p->works.mu);
+        for (auto &kv : p->works.m) kv.second->drop_graphs();
+    }
+    return p->tables.built ? 1 : 0;
+}
+
+// A work buffer of `stream`'s Work, whole: which = 0 HV, 1 OV0, 2 Q1, 3 Q0, 4 G.  put = 0: copied to buf_dev, put = 1: filled from buf_dev
+// (tests poison the buffers ahead of a run).  Copies min(buffer, cap_floats) floats behind the stream's work and waits; returns the count, -1 on error
+int64_t ts_debug_pixelcnn_work(ts_pixelcnn *p, void *stream, int which, float *buf_dev, int64_t cap_floats, int put) {
+    if (!p || !buf_dev || cap_floats < 0 || which < 0 || which > 4) return fail("ts_debug_pixelcnn_work: bad argument") ? -1 : -1;
+    ts_pixelcnn::Work *w = p->works.find((hipStream_t)stream);
+    if (!w) return fail("ts_debug_pixelcnn_work: nothing was run on this stream") ? -1 : -1;
+    DevBuf *bufs[5] = {&w->HV, &w->OV0, &w->Q1, &w->Q0, &w->G};
+    const size_t n = std::min((size_t)cap_floats, bufs[which]->bytes / sizeof(float));
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(put ? bufs[which]->p : (void *)buf_dev, put ? (const void *)buf_dev : bufs[which]->p, n * sizeof(float), hipMemcpyDeviceToDevice, s) !=
+            hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail("ts_debug_pixelcnn_work: copy failed") ? -1 : -1;
+    return (int64_t)n;
+}
+
+// One lookup launch on the caller's row-major buffers (the red-zone tests): which = 0 slot V0 — tok (B,2) int32 codes of the row above,
+// add1 / add2 (B,4D) or null, cls (B,2D), pre (B,4D), out (B,2D), q1 / q0 (B,4D) rider outputs or null; which = 1 hg_0 of column 1 — tok
+// (B,2) of which column 0 is read, add1 (B,2D) or null, cls (B,2D), out (B,D); the rest null.  Needs the tables (ts_debug_pixelcnn_tables)
+int ts_debug_code_table_stage(ts_pixelcnn *p, int which, const int32_t *tok, int B, const float *add1, const float *add2, const float *cls,
+                              float *pre, float *out, float *q1, float *q0, void *stream) {
+    if (!p || !tok || !cls || !out || B < 1 || which < 0 || which > 1) return fail("ts_debug_code_table_stage: bad argument");
+    if (!p->tables.built) return fail("ts_debug_code_table_stage: this model has no code tables");
+    const int D = p->D;
+    CodeTableStage ts;
+    std::memset(&ts, 0, sizeof(ts));
+    ts.M = B, ts.gateD = D;
+    ts.tok0 = tok, ts.tok1 = tok + 1, ts.tok_stride = 2;
+    ts.cls = cls, ts.cls_ld = 2 * D;
+    ts.out = out;
+    if (which == 0) {
+        for (int m = 0; m < 3; ++m) ts.tab[m] = p->tables.v0[m].f();
+        ts.set_stride = (long)p->V * 4 * D;
+        ts.nsets = p->tables.sets;
+        ts.N = 4 * D;
+        ts.bias = p->bv[0]->f();
+        ts.add1 = add1, ts.add2 = add2, ts.add1_stride = ts.add2_stride = 4 * D;
+        ts.pre = pre, ts.pre_stride = 4 * D;
+        ts.out_stride = 2 * D;
+        ts.rider[0] = q1, ts.rider[1] = q0, ts.rider_stride = 4 * D;
+    } else {
+        ts.tab[0] = p->tables.hg.f();
+        ts.set_stride = (long)p->V * 2 * D;
+        ts.nsets = 1;
+        ts.N = 2 * D;
+        ts.bias = p->bh[0]->f();
+        ts.add1 = add1, ts.add1_stride = 2 * D;
+        ts.out_stride = D;
+    }
+    MiscScope ms(p->ctx, (hipStream_t)stream);
+    TS_HIP(launch_code_table_stage(ts, (hipStream_t)stream));
     return 0;
 }
 
