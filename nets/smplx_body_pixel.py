@@ -377,62 +377,8 @@ class TrainWrapper(TrainWrapperBaseClass):
                 _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
         lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
-        i32p = _lib.C.POINTER(_lib.C.c_int32)
-        kdev = None
-        if kblock is not None:
-            from talkshow_amd.modules import upload
-            kdev = upload(kblock, dev)
-        if sblock is not None or btab is not None or rtab is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
-            from talkshow_amd.modules import upload
-            sdev = upload(sblock, dev) if sblock is not None else None
-            tail = (_lib.dptr(sdev), int(sblock.shape[1]) if sblock is not None else 0)
-            poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_style, _lib.load().ts_body_pixel_infer_mixed_style
-            if btab is not None or rtab is not None:
-                bdev = upload(btab, dev) if btab is not None else None
-                tail += (_lib.dptr(bdev), int(btab.shape[0]) if btab is not None else 0, bidx.ctypes.data_as(i32p) if btab is not None else None)
-                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_bias, _lib.load().ts_body_pixel_infer_mixed_bias
-            if rtab is not None:
-                tail += (rtab, n_rep)
-                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_repeat, _lib.load().ts_body_pixel_infer_mixed_repeat
-            if pblock is not None and gblock is None:
-                pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-                _lib.check(poses_entry(
-                    *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)),
-                    _lib.dptr(kdev), *tail, _lib.stream_ptr()))
-            else:
-                gdev = None
-                if gblock is not None and pblock is not None:
-                    gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
-                elif gblock is not None:
-                    gdev = upload(gblock, dev)
-                _lib.check(codes_entry(
-                    *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), None if gdev is None else gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
-                    *tail, _lib.stream_ptr()))
-        elif pblock is not None and gblock is None:
-            from talkshow_amd.modules import upload
-            pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-            pargs = (*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)))
-            if kdev is None:
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*pargs, _lib.stream_ptr()))
-            else:
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_keep(*pargs, _lib.dptr(kdev), _lib.stream_ptr()))
-        elif gblock is not None:
-            if pblock is not None:    # both kinds in one pass: the pose clips' codes join the code clips' in one block, on the device
-                gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
-            else:
-                from talkshow_amd.modules import upload
-                gdev = upload(gblock, dev)
-            gargs = (*args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(gdev), gtable.ctypes.data_as(i32p), None)
-            if kdev is None:
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*gargs, _lib.stream_ptr()))
-            else:
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_keep(*gargs, _lib.dptr(kdev), _lib.stream_ptr()))
-        elif lp is not None:
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_lp(*args, ctl, n_ctl, _lib.dptr(lp), _lib.stream_ptr()))
-        elif ctl is None:
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
-        else:
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_ctl(*args, ctl, n_ctl, _lib.stream_ptr()))
+        self._mixed_call(args, dev, ctl=(ctl, n_ctl), lp=lp, given=(gblock, gtable), poses=(pblock, ptable), keep=kblock, style=sblock,
+                         bias=(btab, bidx), repeat=(rtab, n_rep))      # the most general entry of the family; absent keywords travel as NULL
         inv_dev = torch.as_tensor(inverse, dtype=torch.int64, device=dev)
         codes, poses = codes.index_select(0, inv_dev), poses.index_select(0, inv_dev)     # back to submission order
         if lp is not None:
@@ -443,6 +389,28 @@ class TrainWrapper(TrainWrapperBaseClass):
         if _stacked:
             return codes, poses
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
+
+    def _mixed_call(self, args, dev, ctl=(None, 0), lp=None, given=(None, None), poses=(None, None), keep=None, style=None, bias=(None, None),
+                    repeat=(None, 0)):
+        """Uploads the host blocks of a mixed pass, each once, and makes its one call (`_lib.body_mixed_call`): args the fixed arguments,
+        the rest validated blocks (pairs: block and table) in slot order or None.  Given poses beside given codes are staged into one block."""
+        from talkshow_amd.modules import upload
+        i32p = _lib.C.POINTER(_lib.C.c_int32)
+        (gblock, gtable), (pblock, ptable), (btab, bidx) = given, poses, bias
+        gdev = pose_piece = None
+        if gblock is not None and pblock is not None:    # both kinds in one pass: the pose clips' codes join the code clips' in one block, on the device
+            gdev, gtable = self._stage_given(gblock, gtable, pblock, ptable, dev)
+        elif gblock is not None:
+            gdev = upload(gblock, dev)
+        elif pblock is not None:
+            pdev, tdev = (pblock if torch.is_tensor(pblock) else upload(pblock, dev)), upload(ptable, dev)   # both alive until the call is queued
+            pose_piece = (_lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(tdev))
+        kdev, sdev, bdev = (None if block is None else upload(block, dev) for block in (keep, style, btab))
+        _lib.body_mixed_call(
+            args, ctl=ctl[0], n_ctl=ctl[1], logprob=_lib.dptr(lp), given=_lib.dptr(gdev), given_rows=None if gdev is None else gtable.ctypes.data_as(i32p),
+            poses=pose_piece, keep=_lib.dptr(kdev), style=_lib.dptr(sdev), style_rows=0 if style is None else int(style.shape[1]),
+            bias=_lib.dptr(bdev), n_bias=0 if btab is None else int(btab.shape[0]), bias_index=None if btab is None else bidx.ctypes.data_as(i32p),
+            rep=repeat[0], n_rep=repeat[1])
 
     def _stage_given(self, gblock, gtable, pblock, ptable, dev):
         """One given block for a pass that holds code clips AND pose clips: gblock / gtable from `_lib.given_block`, pblock / ptable from
@@ -497,13 +465,11 @@ class TrainWrapper(TrainWrapperBaseClass):
         lib, i32p = _lib.load(), _lib.C.POINTER(_lib.C.c_int32)
         _lib.check(lib.ts_audioenc_forward_masked(self.audioencoder.handle(), _lib.dptr(mf), _lib.dptr(lens_dev), B, T_max, _lib.dptr(feat),
                                                   _lib.stream_ptr()))
-        gargs = (self.generator.handle(), _lib.dptr(ids_sorted), _lib.dptr(feat), lens_host.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H_max,
-                 _lib.TS_SAMPLE_GREEDY, None, 0, None, _lib.dptr(codes), None, 0, _lib.dptr(lp), _lib.dptr(given), table.ctypes.data_as(i32p), None)
-        if sblock is None:
-            _lib.check(lib.ts_pixelcnn_generate_mixed_given(*gargs, _lib.stream_ptr()))
-        else:
-            sdev = upload(sblock, dev)
-            _lib.check(lib.ts_pixelcnn_generate_mixed_style(*gargs, None, _lib.dptr(sdev), int(sblock.shape[1]), _lib.stream_ptr()))
+        fixed = (self.generator.handle(), _lib.dptr(ids_sorted), _lib.dptr(feat), lens_host.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H_max,
+                 _lib.TS_SAMPLE_GREEDY, None, 0, None, _lib.dptr(codes))
+        sdev = upload(sblock, dev) if sblock is not None else None
+        _lib.pixelcnn_mixed_call(fixed, logprob=_lib.dptr(lp), given=_lib.dptr(given), given_rows=table.ctypes.data_as(i32p),
+                                 style=_lib.dptr(sdev), style_rows=0 if sblock is None else int(sblock.shape[1]))
         _lib.check(lib.ts_logprob_sums(self.generator._ctx(), _lib.dptr(lp), _lib.dptr(lens_dev), B, H_max, _lib.dptr(sums), _lib.stream_ptr()))
         return [(lp[inverse[b], :rows[b]], sums[inverse[b]]) for b in range(B)]
 
@@ -588,96 +554,34 @@ class TrainWrapper(TrainWrapperBaseClass):
         args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
                 _lib.dptr(mf), _lib.dptr(ids), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
                 mode, None, int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
-        i32p = _lib.C.POINTER(_lib.C.c_int32)
         if given_poses is not None and int(given_poses[1].max()) == 0:
             given_poses = None
-        kdev = None
-        if given_keep is not None and (given is not None or given_poses is not None):
-            if given_keep.shape != (B, H_max, 2):
-                raise ValueError(f"infer_padded_wav: the mask of kept positions must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given_keep.shape}")
-            kdev = upload(given_keep, dev)
-        if code_bias is not None and code_bias[0] is None:
-            code_bias = None
-        if repeat is not None and repeat[0] is None:
-            repeat = None
-        if repeat is not None and repeat[1] != B:
-            raise ValueError(f"infer_padded_wav: the repetition records are one per row ({B}), got {repeat[1]}")
-        if style is not None or code_bias is not None or repeat is not None:      # the most general entry of each family; the keywords that are absent travel as NULL
-            sdev = None
-            if style is not None:
-                if style.ndim != 3 or style.shape[0] != B or style.shape[1] not in (1, H_max):
-                    raise ValueError(f"infer_padded_wav: the style block must be (B, 1 or H_max, NC) = ({B}, 1 or {H_max}, NC), got {style.shape}")
-                sdev = upload(np.ascontiguousarray(style, dtype=np.float32), dev)
-            tail = (_lib.dptr(sdev), int(style.shape[1]) if style is not None else 0)
-            poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_style, _lib.load().ts_body_pixel_infer_mixed_style
-            if code_bias is not None:
-                btab, bidx = code_bias
-                V = self.generator.input_dim
-                if btab.ndim != 3 or btab.shape[1:] != (2, V) or btab.dtype != np.float32 or bidx.shape != (B,) or bidx.dtype != np.int32:
-                    raise ValueError(f"infer_padded_wav: the code bias is (tables (NB, 2, {V}) float32, index ({B},) int32), got "
-                                     f"{btab.dtype} {btab.shape} and {bidx.dtype} {bidx.shape}")
-                bdev = upload(np.ascontiguousarray(btab), dev)
-                bidx = np.ascontiguousarray(bidx)
-                tail += (_lib.dptr(bdev), int(btab.shape[0]), bidx.ctypes.data_as(i32p))
-                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_bias, _lib.load().ts_body_pixel_infer_mixed_bias
-            if repeat is not None:
-                if code_bias is None:
-                    tail += (None, 0, None)
-                tail += (repeat[0], int(repeat[1]))
-                poses_entry, codes_entry = _lib.load().ts_body_pixel_infer_mixed_poses_repeat, _lib.load().ts_body_pixel_infer_mixed_repeat
-            ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
-            if given is not None and given[0].shape != (B, H_max, 2):
-                raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
-            if given_poses is not None and int(given_poses[0].shape[1]) // 4 > H_max:
-                raise ValueError(f"infer_padded_wav: the given poses hold {int(given_poses[0].shape[1])} frames but the pass has {H_max} code rows")
-            if given_poses is not None and given is None:
-                pblock, ptable = given_poses
-                pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-                _lib.check(poses_entry(
-                    *args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)),
-                    _lib.dptr(kdev), *tail, _lib.stream_ptr()))
-            else:
-                gdev = gtable = None
-                if given is not None and given_poses is not None:
-                    gdev, gtable = self._stage_given(given[0], given[1], given_poses[0], given_poses[1], dev)
-                elif given is not None:
-                    gdev, gtable = upload(given[0], dev), given[1]
-                _lib.check(codes_entry(
-                    *args, ctl, n_ctl, None, _lib.dptr(gdev), None if gdev is None else gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
-                    *tail, _lib.stream_ptr()))
-            return codes, poses, lens_host
-        if given_poses is not None:
-            pblock, ptable = given_poses
-            if int(pblock.shape[1]) // 4 > H_max:
-                raise ValueError(f"infer_padded_wav: the given poses hold {int(pblock.shape[1])} frames but the pass has {H_max} code rows")
-            ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
-            if given is None:
-                pdev = pblock if torch.is_tensor(pblock) else upload(pblock, dev)
-                pargs = (*args, ctl, n_ctl, None, _lib.dptr(pdev), int(pdev.shape[1]), ptable.ctypes.data_as(i32p), _lib.dptr(upload(ptable, dev)))
-                if kdev is None:
-                    _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses(*pargs, _lib.stream_ptr()))
-                else:
-                    _lib.check(_lib.load().ts_body_pixel_infer_mixed_poses_keep(*pargs, _lib.dptr(kdev), _lib.stream_ptr()))
-            else:
-                if given[0].shape != (B, H_max, 2):
-                    raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given[0].shape}")
-                gdev, gtable = self._stage_given(given[0], given[1], pblock, ptable, dev)
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_keep(*args, ctl, n_ctl, None, _lib.dptr(gdev), gtable.ctypes.data_as(i32p), None, _lib.dptr(kdev),
-                                                                       _lib.stream_ptr()))
-        elif given is not None:
-            gblock, gtable = given
-            if gblock.shape != (B, H_max, 2):
-                raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {gblock.shape}")
-            ctl, n_ctl = sampling_table if sampling_table is not None else (None, 0)
-            gargs = (*args, ctl, n_ctl, None, _lib.dptr(upload(gblock, dev)), gtable.ctypes.data_as(i32p), None)
-            if kdev is None:
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_given(*gargs, _lib.stream_ptr()))
-            else:
-                _lib.check(_lib.load().ts_body_pixel_infer_mixed_keep(*gargs, _lib.dptr(kdev), _lib.stream_ptr()))
-        elif sampling_table is None:
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed(*args, _lib.stream_ptr()))
-        else:
-            _lib.check(_lib.load().ts_body_pixel_infer_mixed_ctl(*args, sampling_table[0], sampling_table[1], _lib.stream_ptr()))
+        if given is None and given_poses is None:
+            given_keep = None
+        if given_keep is not None and given_keep.shape != (B, H_max, 2):
+            raise ValueError(f"infer_padded_wav: the mask of kept positions must be (B, H_max, 2) = ({B}, {H_max}, 2), got {given_keep.shape}")
+        if style is not None:
+            if style.ndim != 3 or style.shape[0] != B or style.shape[1] not in (1, H_max):
+                raise ValueError(f"infer_padded_wav: the style block must be (B, 1 or H_max, NC) = ({B}, 1 or {H_max}, NC), got {style.shape}")
+            style = np.ascontiguousarray(style, dtype=np.float32)
+        btab, bidx = code_bias if code_bias is not None else (None, None)
+        if btab is not None:
+            V = self.generator.input_dim
+            if btab.ndim != 3 or btab.shape[1:] != (2, V) or btab.dtype != np.float32 or bidx.shape != (B,) or bidx.dtype != np.int32:
+                raise ValueError(f"infer_padded_wav: the code bias is (tables (NB, 2, {V}) float32, index ({B},) int32), got "
+                                 f"{btab.dtype} {btab.shape} and {bidx.dtype} {bidx.shape}")
+            bidx = np.ascontiguousarray(bidx)
+        rtab, n_rep = repeat if repeat is not None and repeat[0] is not None else (None, 0)
+        if rtab is not None and n_rep != B:
+            raise ValueError(f"infer_padded_wav: the repetition records are one per row ({B}), got {n_rep}")
+        gblock, gtable = given if given is not None else (None, None)
+        if gblock is not None and gblock.shape != (B, H_max, 2):
+            raise ValueError(f"infer_padded_wav: the given block must be (B, H_max, 2) = ({B}, {H_max}, 2), got {gblock.shape}")
+        pblock, ptable = given_poses if given_poses is not None else (None, None)
+        if pblock is not None and int(pblock.shape[1]) // 4 > H_max:
+            raise ValueError(f"infer_padded_wav: the given poses hold {int(pblock.shape[1])} frames but the pass has {H_max} code rows")
+        self._mixed_call(args, dev, ctl=sampling_table or (None, 0), given=(gblock, gtable), poses=(pblock, ptable), keep=given_keep, style=style,
+                         bias=(btab, bidx), repeat=(rtab, int(n_rep)))
         return codes, poses, lens_host
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,

@@ -108,67 +108,29 @@ SIGNATURES = {
     "ts_sampling_check": (_i, [_sp, _i, _i]),
     "ts_pixelcnn_generate_ctl": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _sp, _i, _vp]),
     "ts_op_sample_ctl": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, _vp]),
-    "ts_body_pixel_infer_mixed_ctl": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                           _vp]),
-    "ts_pixelcnn_generate_mixed_ctl": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp]),
     # the _ctl entries plus logprob_dev ahead of the stream
     "ts_pixelcnn_generate_lp": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _sp, _i, _vp, _vp]),
     "ts_op_sample_lp": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, _vp, _vp]),
-    "ts_body_pixel_infer_mixed_lp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                          _vp, _vp]),
-    "ts_pixelcnn_generate_mixed_lp": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp]),
     "ts_logprob_sums": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
-    # the mixed _lp entries plus given_dev, given_rows_host, given_rows_dev ahead of the stream
     "ts_given_rows_check": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i]),
-    "ts_body_pixel_infer_mixed_given": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                             _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
-    "ts_pixelcnn_generate_mixed_given": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
-                                              C.POINTER(C.c_int32), _vp, _vp]),
-    # given poses: the mixed VQ encode and the pass that continues from it
+    # given poses: the mixed VQ encode
     "ts_vqvae_encode_pair_masked": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ts_body_vq_infer_mixed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ts_given_pose_rows_check": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i]),
-    "ts_body_pixel_infer_mixed_poses": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                             _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp]),
     "ts_op_vq_argmin_pair_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ts_debug_vq_argmin_pair_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "ts_op_sample_given": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp]),
-    # kept positions: the _given / _poses entries with keep_dev ahead of the stream; the one-launch form with the device-side decision
-    "ts_pixelcnn_generate_mixed_keep": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
-                                             C.POINTER(C.c_int32), _vp, _vp, _vp]),
-    "ts_body_pixel_infer_mixed_keep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                            _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp]),
-    "ts_body_pixel_infer_mixed_poses_keep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
-                                                  _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    # kept positions: the one-launch form with the device-side decision
     "ts_op_sample_keep": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp]),
-    # speaker style: the most general sibling of each family with style_dev, style_rows ahead of the stream; the host rule; the kernel alone
-    "ts_pixelcnn_generate_mixed_style": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
-                                              C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
-    "ts_body_pixel_infer_mixed_style": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                             _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
-    "ts_body_pixel_infer_mixed_poses_style": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
-                                                   _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
+    # speaker style: the host rule; the kernel alone
     "ts_style_check": (_i, [C.POINTER(C.c_float), C.c_long, _i]),
     "ts_op_style_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    # code bias: the _style sibling of each family with bias_dev, n_bias, bias_index_host ahead of the stream; the host rules; one launch
-    "ts_pixelcnn_generate_mixed_bias": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
-                                             C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _vp]),
-    "ts_body_pixel_infer_mixed_bias": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                            _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _vp]),
-    "ts_body_pixel_infer_mixed_poses_bias": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
-                                                  _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _vp]),
+    # code bias: the host rules; one launch
     "ts_code_bias_check": (_i, [C.POINTER(C.c_float), _i, _i]),
     "ts_code_bias_index_check": (_i, [C.POINTER(C.c_int32), _i, _i]),
     "ts_op_sample_bias": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
                                _i, C.POINTER(C.c_int32), _i, _vp]),
-    # repetition penalty: the _bias sibling of each family with rep_host, n_rep ahead of the stream; the host rule; one launch
-    "ts_pixelcnn_generate_mixed_repeat": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _sp, _i, _vp, _vp,
-                                               C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _rp, _i, _vp]),
-    "ts_body_pixel_infer_mixed_repeat": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp, _i,
-                                              _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _rp, _i, _vp]),
-    "ts_body_pixel_infer_mixed_poses_repeat": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sp,
-                                                    _i, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _rp, _i,
-                                                    _vp]),
+    # repetition penalty: the host rule; one launch
     "ts_repeat_check": (_i, [_rp, _i, _i]),
     "ts_op_sample_repeat": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
                                  _i, C.POINTER(C.c_int32), _i, _rp, _i, _vp, _vp, _vp]),
@@ -274,6 +236,37 @@ SIGNATURES = {
     "ts_prof_read_n": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), _i]),
 }
 
+# The suffixed mixed entries: each sibling is its parent plus one piece of arguments ahead of the stream
+_i32p = C.POINTER(C.c_int32)
+MIXED_CORE = {
+    "ts_body_pixel_infer_mixed": [_vp, _vp, _vp, _vp, _vp, _vp, _i32p, _vp, _i, _i, _i, _vp, _u64, _vp, _vp, _vp],
+    "ts_pixelcnn_generate_mixed": [_vp, _vp, _vp, _i32p, _vp, _i, _i, _i, _vp, _u64, _vp, _vp],
+}
+MIXED_PIECES = {
+    "ctl": [_sp, _i],                 # ctl_host, n_ctl
+    "lp": [_vp],                      # logprob_dev
+    "given": [_vp, _i32p, _vp],       # given_dev, given_rows_host, given_rows_dev
+    "poses": [_vp, _i, _i32p, _vp],   # given_poses_dev, P_max, pose_lens_host, pose_lens_dev
+    "keep": [_vp],                    # keep_dev
+    "style": [_vp, _i],               # style_dev, style_rows
+    "bias": [_vp, _i, _i32p],         # bias_dev, n_bias, bias_index_host
+    "repeat": [_rp, _i],              # rep_host, n_rep
+}
+
+
+def _declare_ladder(stem, below, suffixes):
+    """SIGNATURES[stem + "_" + suffix] for every suffix in turn: the pieces `below` it, its own (named by the suffix's last word) and
+    those of the suffixes ahead of it, between the stem's core arguments and the stream."""
+    args = MIXED_CORE[stem] + [a for piece in below for a in MIXED_PIECES[piece]]
+    for suffix in suffixes:
+        args = args + MIXED_PIECES[suffix.rsplit("_", 1)[-1]]
+        SIGNATURES[f"{stem}_{suffix}"] = (_i, args + [_vp])
+
+
+_declare_ladder("ts_body_pixel_infer_mixed", (), ("ctl", "lp", "given", "keep", "style", "bias", "repeat"))
+_declare_ladder("ts_pixelcnn_generate_mixed", (), ("ctl", "lp", "given", "keep", "style", "bias", "repeat"))
+_declare_ladder("ts_body_pixel_infer_mixed", ("ctl", "lp"), ("poses", "poses_keep", "poses_style", "poses_bias", "poses_repeat"))
+
 _lib = None
 
 
@@ -329,6 +322,43 @@ def face_generate_mixed(handle, wav, ns, ns_dev, frames, frames_dev, B, N_max, T
         if layout not in (0, 1):
             raise ValueError("layout is None (the library's plan), 0 (padded) or 1 (packed)")
         check(load().ts_debug_face_generate_mixed(*args, int(layout)))
+
+
+def _mixed_tail(middle, ctl=None, n_ctl=0, logprob=None, keep=None, style=None, style_rows=0, bias=None, n_bias=0, bias_index=None,
+                rep=None, n_rep=0, stream=None):
+    """What follows the fixed arguments of a most general mixed entry (`..._repeat`), `middle` being its given or poses piece: every
+    keyword is an already-converted value (pointer, int, ctypes array), an absent one travels as None / 0."""
+    return (ctl, int(n_ctl) if ctl is not None else 0, logprob, *middle, keep, style, int(style_rows) if style is not None else 0,
+            bias, int(n_bias) if bias is not None else 0, bias_index if bias is not None else None,
+            rep, int(n_rep) if rep is not None else 0, stream)
+
+
+def body_mixed_args(fixed, given=None, given_rows=None, poses=None, **pieces):
+    """(entry name, argument tuple) of a mixed body pass: `fixed` the 16 arguments of `ts_body_pixel_infer_mixed` ahead of its stream,
+    given / given_rows the device block and its host table, poses (given_poses_dev, P_max, pose_lens_host, pose_lens_dev), the rest as
+    `_mixed_tail` takes it.  A pass that brings poses and no given codes is `ts_body_pixel_infer_mixed_poses_repeat`, every other one
+    `ts_body_pixel_infer_mixed_repeat`: NULL is "the entry without that keyword, launch for launch" (talkshow_hip.h)."""
+    if poses is not None and given is not None:
+        raise ValueError("body_mixed_args: a pass brings given codes or given poses (stage the poses' codes into the given block)")
+    if poses is not None:
+        return "ts_body_pixel_infer_mixed_poses_repeat", (*fixed, *_mixed_tail(tuple(poses), **pieces))
+    return "ts_body_pixel_infer_mixed_repeat", (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
+
+
+def body_mixed_call(fixed, **pieces):
+    """`body_mixed_args` on the current stream: load, call, check."""
+    name, args = body_mixed_args(fixed, stream=stream_ptr(), **pieces)
+    check(getattr(load(), name)(*args))
+
+
+def pixelcnn_mixed_args(fixed, given=None, given_rows=None, **pieces):
+    """`body_mixed_args` for the PixelCNN alone (`fixed`: its 12 arguments ahead of the stream): always `ts_pixelcnn_generate_mixed_repeat`."""
+    return "ts_pixelcnn_generate_mixed_repeat", (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
+
+
+def pixelcnn_mixed_call(fixed, **pieces):
+    name, args = pixelcnn_mixed_args(fixed, stream=stream_ptr(), **pieces)
+    check(getattr(load(), name)(*args))
 
 
 NEUTRAL_SAMPLING = (1.0, 1.0, 0)

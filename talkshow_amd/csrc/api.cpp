@@ -203,13 +203,86 @@ int ts_body_pixel_infer(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae
     return ts_vqvae_decode_pair(vb, vh, static_cast<int64_t *>(w.lat[0].p), static_cast<int64_t *>(w.lat[1].p), B, H, poses, s);
 }
 
+// the scope every sampling control shares (sampling records, code bias, repetition penalty); `who` names the entry in the message
+static int ctl_mode_check(const std::string &who, int mode) {
+    if (mode == TS_SAMPLE_UNIFORMS || mode == TS_SAMPLE_PHILOX) return 0;
+    return fail(who + ": sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
+}
+
+// What every mixed body entry refuses before its first launch: null arguments, the shape, the length table (within T_max, at least one code
+// row, non-increasing) and the sampling records; `who` names the entry in the messages.  A pass under a "speaker style" does not read the
+// speaker ids: the style block takes their place
+static int body_mixed_check(const char *who, const void *ae, const void *pix, const void *vb, const void *vh, const float *mfcc, const MixedPass &a,
+                            const float *poses, const MixedOpts &o) {
+    const std::string w(who);
+    const int B = a.B, T_max = a.rows;
+    if (!ae || !pix || !vb || !vh || !mfcc || !(o.style ? static_cast<const void *>(o.style) : a.ids) || !a.lens_host || !a.lens_dev || !a.codes || !poses)
+        return fail(w + ": null argument");
+    if (B < 1) return fail(w + ": bad shape");
+    if ((T_max / 2) / 2 < 1) return fail(w + ": T_max too short");
+    for (int b = 0; b < B; ++b) {
+        if (a.lens_host[b] > T_max) return fail(w + ": clip " + std::to_string(b) + " is longer than T_max");
+        if (a.lens_host[b] < 4) return fail(w + ": clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
+        if (b > 0 && a.lens_host[b] > a.lens_host[b - 1])
+            return fail(w + ": lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
+    }
+    if (o.ctl_host) {   // a bad record or mode is refused before the first launch of the pass
+        TS_TRY(ctl_mode_check(w + "_ctl", a.mode));
+        if (o.n_ctl != 1 && o.n_ctl != B) return fail(w + "_ctl: n_ctl must be 1 or B");
+        if (ts_sampling_check(o.ctl_host, o.n_ctl, 1) != 0) return 1;   // the records; the vocabulary is checked by the PixelCNN's pass
+    }
+    return 0;
+}
+
+// What the body entries refuse of a "code bias" before their first launch: the mode (the bias shares the sampling table's scope) and the
+// index table
+static int body_bias_check(const char *who, int mode, int B, int n_bias, const int32_t *bias_index_host) {
+    TS_TRY(ctl_mode_check(who, mode));
+    if (!bias_index_host) return fail(std::string(who) + ": the tables need their index table");
+    return ts_code_bias_index_check(bias_index_host, B, n_bias);
+}
+
+// What the body entries refuse of a "repetition penalty" before their first launch: the mode (a sampling control, like the bias), the
+// number of records and the records themselves
+static int body_repeat_check(const char *who, int mode, int B, int V, const ts_repeat *rep_host, int n_rep) {   // V = 1: the vocabulary is
+                                                                                                                // checked by the pass itself
+    TS_TRY(ctl_mode_check(who, mode));
+    if (n_rep != 1 && n_rep != B)
+        return fail(std::string(who) + ": a pass of " + std::to_string(B) + " clips brings 1 or " + std::to_string(B) + " repetition records, got " +
+                    std::to_string(n_rep));
+    return ts_repeat_check(rep_host, n_rep, V);
+}
+
+// The body of every ts_body_pixel_infer_mixed* entry without given poses (a.rows = T_max): each entry fills `o` with its own arguments
+static int body_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const MixedPass &a, float *poses,
+                      const MixedOpts &o, hipStream_t s) {
+    TS_TRY(body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, a, poses, o));
+    const int B = a.B, H = (a.rows / 2) / 2;
+    TS_TRY(mixed_style_rows_check("ts_body_pixel_infer_mixed", "T_max / 4", o, H));
+    if (o.bias && body_bias_check("ts_body_pixel_infer_mixed_bias", a.mode, B, o.n_bias, o.bias_index_host) != 0) return 1;
+    if (o.rep_host && body_repeat_check("ts_body_pixel_infer_mixed_repeat", a.mode, B, 1, o.rep_host, o.n_rep) != 0) return 1;
+    TS_TRY(mixed_given_check("ts_body_pixel_infer_mixed", o, a.lens_host, B));   // a bad row table is refused before the first launch of the pass, too
+    BodyWork &w = body_work(s);
+    TS_TRY(w.feat.ensure((size_t)B * H * convnet_hidden(ae) * sizeof(float)));
+    TS_TRY(ts_audioenc_forward_masked(ae, mfcc, a.lens_dev, B, a.rows, w.feat.f(), s));
+    MixedPass rows = a;
+    rows.rows = H;
+    TS_TRY(pixelcnn_generate_mixed(pix, w.feat.f(), rows, o, s));
+    for (int k = 0; k < 2; ++k) {
+        TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
+        TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), a.codes + k, 2 * sizeof(int64_t), sizeof(int64_t),
+                                (size_t)B * H, hipMemcpyDeviceToDevice, s));
+    }
+    return ts_vqvae_decode_pair_masked(vb, vh, static_cast<int64_t *>(w.lat[0].p), static_cast<int64_t *>(w.lat[1].p), a.lens_dev, B, H,
+                                       poses, s);
+}
+
 // The same path for clips of different lengths in ONE pass (talkshow_hip.h: "mixed passes"): length-masked conv stacks, the chain over
 // a shrinking prefix of the clips, documented padding in both outputs.
 int ts_body_pixel_infer_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
                               const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
                               uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, void *stream) {
-    return ts_body_pixel_infer_mixed_ctl(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                         nullptr, 0, stream);
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, MixedOpts(), (hipStream_t)stream);
 }
 
 // the same pass with per-clip sampling controls (ctl_host == NULL: exactly the entry above)
@@ -217,8 +290,9 @@ int ts_body_pixel_infer_mixed_ctl(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb
                                   const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
                                   uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                   void *stream) {
-    return ts_body_pixel_infer_mixed_lp(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                        ctl_host, n_ctl, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same pass with a log-probability output (B, T_max / 4, 2); logprob == NULL: exactly the entry above
@@ -226,33 +300,9 @@ int ts_body_pixel_infer_mixed_lp(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb,
                                  const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
                                  uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                  float *logprob, void *stream) {
-    return ts_body_pixel_infer_mixed_given(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                           ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, stream);
-}
-
-// What every mixed body entry refuses before its first launch: null arguments, the shape, the length table (within T_max, at least one code
-// row, non-increasing) and the sampling records; `who` names the entry in the messages.  `ids`: the speaker ids, or — a pass under a "speaker
-// style" does not read them — the style block that takes their place
-static int body_mixed_check(const char *who, const void *ae, const void *pix, const void *vb, const void *vh, const float *mfcc, const void *ids,
-                            const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const int64_t *codes, const float *poses,
-                            const ts_sampling *ctl_host, int n_ctl) {
-    const std::string w(who);
-    if (!ae || !pix || !vb || !vh || !mfcc || !ids || !lens_host || !lens_dev || !codes || !poses) return fail(w + ": null argument");
-    if (B < 1) return fail(w + ": bad shape");
-    if ((T_max / 2) / 2 < 1) return fail(w + ": T_max too short");
-    for (int b = 0; b < B; ++b) {
-        if (lens_host[b] > T_max) return fail(w + ": clip " + std::to_string(b) + " is longer than T_max");
-        if (lens_host[b] < 4) return fail(w + ": clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
-        if (b > 0 && lens_host[b] > lens_host[b - 1])
-            return fail(w + ": lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
-    }
-    if (ctl_host) {   // a bad record or mode is refused before the first launch of the pass
-        if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
-            return fail(w + "_ctl: sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
-        if (n_ctl != 1 && n_ctl != B) return fail(w + "_ctl: n_ctl must be 1 or B");
-        if (ts_sampling_check(ctl_host, n_ctl, 1) != 0) return 1;   // the records; the vocabulary is checked by ts_pixelcnn_generate_mixed_ctl
-    }
-    return 0;
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same pass in which clip b brings given_rows[b] code rows (given (B, T_max / 4, 2)); given == NULL: exactly the entry above
@@ -261,8 +311,10 @@ int ts_body_pixel_infer_mixed_given(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                     float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                     void *stream) {
-    return ts_body_pixel_infer_mixed_keep(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                          ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the given pass with a mask of kept positions (talkshow_hip.h, "kept positions"; keep (B, T_max / 4, 2) uint8); keep == NULL: exactly the
@@ -272,8 +324,10 @@ int ts_body_pixel_infer_mixed_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *v
                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                    const uint8_t *keep, void *stream) {
-    return ts_body_pixel_infer_mixed_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                           ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, nullptr, 0, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same pass under a "speaker style" (talkshow_hip.h): style (B, style_rows, NC) float weights in slot order in place of the ids, which
@@ -283,18 +337,11 @@ int ts_body_pixel_infer_mixed_style(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                     float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                     const uint8_t *keep, const float *style, int style_rows, void *stream) {
-    return ts_body_pixel_infer_mixed_bias(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                          ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, nullptr, 0, nullptr,
-                                          stream);
-}
-
-// What the body entries refuse of a "code bias" before their first launch: the mode (the bias shares the sampling table's scope) and the
-// index table
-static int body_bias_check(const char *who, int mode, int B, int n_bias, const int32_t *bias_index_host) {
-    if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
-        return fail(std::string(who) + ": sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
-    if (!bias_index_host) return fail(std::string(who) + ": the tables need their index table");
-    return ts_code_bias_index_check(bias_index_host, B, n_bias);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same pass under a "code bias" (talkshow_hip.h): bias (n_bias, 2, V) device tables, bias_index_host (B,) the table of every clip in
@@ -305,21 +352,11 @@ int ts_body_pixel_infer_mixed_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *v
                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                    const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
                                    const int32_t *bias_index_host, void *stream) {
-    return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                            ctl_host, n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias, n_bias,
-                                            bias_index_host, nullptr, 0, stream);
-}
-
-// What the body entries refuse of a "repetition penalty" before their first launch: the mode (a sampling control, like the bias), the
-// number of records and the records themselves
-static int body_repeat_check(const char *who, int mode, int B, int V, const ts_repeat *rep_host, int n_rep) {   // V = 1: the vocabulary is
-                                                                                                                // checked by the pass itself
-    if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
-        return fail(std::string(who) + ": sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
-    if (n_rep != 1 && n_rep != B)
-        return fail(std::string(who) + ": a pass of " + std::to_string(B) + " clips brings 1 or " + std::to_string(B) + " repetition records, got " +
-                    std::to_string(n_rep));
-    return ts_repeat_check(rep_host, n_rep, V);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same pass under a "repetition penalty" (talkshow_hip.h): rep_host n_rep (1 or B) records in slot order.  rep_host == NULL: exactly
@@ -330,34 +367,12 @@ int ts_body_pixel_infer_mixed_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae 
                                      float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
                                      const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
                                      const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, void *stream) {
-    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, style ? static_cast<const void *>(style) : ids, lens_host, lens_dev, B,
-                         T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
-        return 1;
-    if (style && style_rows != 1 && style_rows != (T_max / 2) / 2)
-        return fail("ts_body_pixel_infer_mixed_style: style_rows is 1 or T_max / 4 = " + std::to_string((T_max / 2) / 2) + ", got " + std::to_string(style_rows));
-    if (bias && body_bias_check("ts_body_pixel_infer_mixed_bias", mode, B, n_bias, bias_index_host) != 0) return 1;
-    if (rep_host && body_repeat_check("ts_body_pixel_infer_mixed_repeat", mode, B, 1, rep_host, n_rep) != 0) return 1;
-    if (keep && !given) return fail("ts_body_pixel_infer_mixed_keep: a mask of kept positions needs the given codes it selects from");
-    if (given) {   // a bad row table is refused before the first launch of the pass, too
-        if (!given_rows_host) return fail("ts_body_pixel_infer_mixed_given: given codes need their row table");
-        if (ts_given_rows_check(given_rows_host, lens_host, B) != 0) return 1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int H = (T_max / 2) / 2;
-    const int aud_dim = convnet_hidden(ae);
-    BodyWork &w = body_work(s);
-    TS_TRY(w.feat.ensure((size_t)B * H * aud_dim * sizeof(float)));
-    TS_TRY(ts_audioenc_forward_masked(ae, mfcc, lens_dev, B, T_max, w.feat.f(), s));
-    TS_TRY(ts_pixelcnn_generate_mixed_repeat(pix, ids, w.feat.f(), lens_host, lens_dev, B, H, mode, uniforms, seed, clip_index, codes, ctl_host,
-                                             n_ctl, logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias, n_bias,
-                                             bias_index_host, rep_host, n_rep, s));
-    for (int k = 0; k < 2; ++k) {
-        TS_TRY(w.lat[k].ensure((size_t)B * H * sizeof(int64_t)));
-        TS_HIP(hipMemcpy2DAsync(w.lat[k].p, sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t),
-                                (size_t)B * H, hipMemcpyDeviceToDevice, s));
-    }
-    return ts_vqvae_decode_pair_masked(vb, vh, static_cast<int64_t *>(w.lat[0].p), static_cast<int64_t *>(w.lat[1].p), lens_dev, B, H,
-                                       poses, s);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // Host only: the rule every entry with given POSES applies to its frame table before anything is launched (talkshow_hip.h, "given poses")
@@ -375,6 +390,47 @@ int ts_given_pose_rows_check(const int32_t *pose_lens_host, const int32_t *lens_
     return 0;
 }
 
+// The body of every ts_body_pixel_infer_mixed_poses* entry: the given rows of body_mixed are ENCODED here from o.given_poses, on the device
+// and in stream order, and the pass behind them is body_mixed's
+static int body_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const MixedPass &a, float *poses,
+                            MixedOpts o, hipStream_t s) {
+    if (o.keep && !o.given_poses)
+        return fail("ts_body_pixel_infer_mixed_poses_keep: a mask of kept positions needs the given poses whose codes it selects from");
+    std::vector<int32_t> G;   // the code rows the frames of every clip make: outlives the pass's host checks
+    if (o.given_poses) {
+        const char *who = "ts_body_pixel_infer_mixed_poses";
+        const int B = a.B, H = (a.rows / 2) / 2;
+        // everything the pass itself would refuse is refused here too, ahead of the encoders' launches
+        if (!o.pose_lens_host || !o.pose_lens_dev) return fail(std::string(who) + ": given poses need their frame tables");
+        TS_TRY(body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, a, poses, o));
+        TS_TRY(mixed_style_rows_check("ts_body_pixel_infer_mixed", "T_max / 4", o, H));
+        if (a.mode != TS_SAMPLE_GREEDY && a.mode != TS_SAMPLE_UNIFORMS && a.mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
+        if (a.mode == TS_SAMPLE_UNIFORMS && !a.uniforms) return fail(std::string(who) + ": TS_SAMPLE_UNIFORMS needs uniforms_dev");
+        if (o.bias && body_bias_check("ts_body_pixel_infer_mixed_poses_bias", a.mode, B, o.n_bias, o.bias_index_host) != 0) return 1;
+        if (o.rep_host && body_repeat_check("ts_body_pixel_infer_mixed_poses_repeat", a.mode, B, 1, o.rep_host, o.n_rep) != 0) return 1;
+        if (ts_given_pose_rows_check(o.pose_lens_host, a.lens_host, B) != 0) return 1;
+        int p_top = 0;
+        G.resize(B);
+        for (int b = 0; b < B; ++b) {
+            G[b] = o.pose_lens_host[b] / 4;
+            p_top = std::max(p_top, (int)o.pose_lens_host[b]);
+        }
+        if (p_top > o.P_max) return fail(std::string(who) + ": a clip brings more pose frames than P_max");
+        if (p_top == 0) {   // nothing given anywhere: the pass without given rows
+            o.keep = nullptr;
+        } else {
+            if (o.P_max / 4 > H) return fail(std::string(who) + ": P_max / 4 exceeds the pass's code rows T_max / 4");
+            BodyWork &w = body_work(s);
+            TS_TRY(w.given.ensure((size_t)B * H * 2 * sizeof(int64_t)));
+            int64_t *given = static_cast<int64_t *>(w.given.p);
+            // rows h < P_b / 4 of clip b: its codes; rows up to P_max / 4: -1; rows beyond stay as they are — the pass reads rows below G_b only
+            TS_TRY(vq_encode_pair_masked(vb, vh, o.given_poses, vqvae_in_dim(vb) + vqvae_in_dim(vh), o.pose_lens_dev, B, o.P_max, given, H, nullptr, nullptr, 0, s));
+            o.given = given, o.given_rows_host = G.data();
+        }
+    }
+    return body_mixed(ae, pix, vb, vh, mfcc, a, poses, o, s);
+}
+
 // ts_body_pixel_infer_mixed_given whose given rows are ENCODED here from pose frames, on the device and in stream order (talkshow_hip.h,
 // "given poses"); given_poses == NULL: exactly the _lp entry
 int ts_body_pixel_infer_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
@@ -382,8 +438,10 @@ int ts_body_pixel_infer_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *
                                     uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
                                     float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                     const int32_t *pose_lens_dev, void *stream) {
-    return ts_body_pixel_infer_mixed_poses_keep(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                                poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same with a mask of kept positions over the codes the encoders produce (keep (B, T_max / 4, 2) uint8, rows r < P_b / 4 read); keep ==
@@ -393,9 +451,10 @@ int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
                                          uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
                                          int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                          const int32_t *pose_lens_dev, const uint8_t *keep, void *stream) {
-    return ts_body_pixel_infer_mixed_poses_style(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                                 poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, keep, nullptr, 0,
-                                                 stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same under a "speaker style" (style (B, style_rows, NC) in place of the ids; style == NULL: exactly the entry above).  The encoders
@@ -405,9 +464,11 @@ int ts_body_pixel_infer_mixed_poses_style(ts_convnet *ae, ts_pixelcnn *pix, ts_v
                                           uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
                                           int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                           const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows, void *stream) {
-    return ts_body_pixel_infer_mixed_poses_bias(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                                poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, keep, style,
-                                                style_rows, nullptr, 0, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
+    o.style = style, o.style_rows = style_rows;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same under a "code bias" (bias (n_bias, 2, V), bias_index_host (B,) in slot order; bias == NULL: exactly the entry above).  The
@@ -418,9 +479,11 @@ int ts_body_pixel_infer_mixed_poses_bias(ts_convnet *ae, ts_pixelcnn *pix, ts_vq
                                          int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
                                          const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows, const float *bias,
                                          int n_bias, const int32_t *bias_index_host, void *stream) {
-    return ts_body_pixel_infer_mixed_poses_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                                  poses, ctl_host, n_ctl, logprob, given_poses, P_max, pose_lens_host, pose_lens_dev, keep, style,
-                                                  style_rows, bias, n_bias, bias_index_host, nullptr, 0, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 // the same under a "repetition penalty" (rep_host n_rep (1 or B) records in slot order; rep_host == NULL: exactly the entry above).  The
@@ -432,46 +495,12 @@ int ts_body_pixel_infer_mixed_poses_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_
                                            const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows,
                                            const float *bias, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
                                            void *stream) {
-    if (keep && !given_poses)
-        return fail("ts_body_pixel_infer_mixed_poses_keep: a mask of kept positions needs the given poses whose codes it selects from");
-    if (!given_poses)
-        return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                              poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, nullptr, style, style_rows, bias, n_bias,
-                                              bias_index_host, rep_host, n_rep, stream);
-    const char *who = "ts_body_pixel_infer_mixed_poses";
-    // everything the pass itself would refuse is refused here too, ahead of the encoders' launches
-    if (!pose_lens_host || !pose_lens_dev) return fail(std::string(who) + ": given poses need their frame tables");
-    if (body_mixed_check("ts_body_pixel_infer_mixed", ae, pix, vb, vh, mfcc, style ? static_cast<const void *>(style) : ids, lens_host, lens_dev, B,
-                         T_max, mode, codes, poses, ctl_host, n_ctl) != 0)
-        return 1;
-    const int H = (T_max / 2) / 2;
-    if (style && style_rows != 1 && style_rows != H)
-        return fail("ts_body_pixel_infer_mixed_style: style_rows is 1 or T_max / 4 = " + std::to_string(H) + ", got " + std::to_string(style_rows));
-    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": TS_SAMPLE_UNIFORMS needs uniforms_dev");
-    if (bias && body_bias_check("ts_body_pixel_infer_mixed_poses_bias", mode, B, n_bias, bias_index_host) != 0) return 1;
-    if (rep_host && body_repeat_check("ts_body_pixel_infer_mixed_poses_repeat", mode, B, 1, rep_host, n_rep) != 0) return 1;
-    if (ts_given_pose_rows_check(pose_lens_host, lens_host, B) != 0) return 1;
-    std::vector<int32_t> G(B);
-    int p_top = 0;
-    for (int b = 0; b < B; ++b) {
-        G[b] = pose_lens_host[b] / 4;
-        p_top = std::max(p_top, (int)pose_lens_host[b]);
-    }
-    if (p_top > P_max) return fail(std::string(who) + ": a clip brings more pose frames than P_max");
-    if (p_top == 0)   // nothing given anywhere: the pass without given rows
-        return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes,
-                                              poses, ctl_host, n_ctl, logprob, nullptr, nullptr, nullptr, nullptr, style, style_rows, bias, n_bias,
-                                              bias_index_host, rep_host, n_rep, stream);
-    if (P_max / 4 > H) return fail(std::string(who) + ": P_max / 4 exceeds the pass's code rows T_max / 4");
-    hipStream_t s = (hipStream_t)stream;
-    BodyWork &w = body_work(s);
-    TS_TRY(w.given.ensure((size_t)B * H * 2 * sizeof(int64_t)));
-    int64_t *given = static_cast<int64_t *>(w.given.p);
-    // rows h < P_b / 4 of clip b: its codes; rows up to P_max / 4: -1; rows beyond stay as they are — the pass reads rows below G_b only
-    TS_TRY(vq_encode_pair_masked(vb, vh, given_poses, vqvae_in_dim(vb) + vqvae_in_dim(vh), pose_lens_dev, B, P_max, given, H, nullptr, nullptr, 0, s));
-    return ts_body_pixel_infer_mixed_repeat(ae, pix, vb, vh, mfcc, ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes, poses,
-                                          ctl_host, n_ctl, logprob, given, G.data(), nullptr, keep, style, style_rows, bias, n_bias, bias_index_host, rep_host, n_rep, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
 int ts_op_conv1d(ts_ctx *ctx, const float *x, int B, int Lin, int Cin, const float *w, const float *bias, int Cout,

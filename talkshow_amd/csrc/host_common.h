@@ -246,4 +246,49 @@ int vqvae_in_dim(const ts_vqvae *v);
 int vq_encode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int poses_ld, const int32_t *lens_dev, int B, int T_max, int64_t *codes,
                           int codes_H, float *z_body, float *z_hand, int form, hipStream_t s);
 
+// ---- mixed passes: the arguments behind the exported ts_*_mixed* ladders (talkshow_hip.h has every contract) -----------------
+// What every mixed entry takes, in the entries' own order: `rows` is H_max for the PixelCNN, T_max for the body wrapper
+struct MixedPass {
+    const int64_t *ids;
+    const int32_t *lens_host, *lens_dev;
+    int B, rows, mode;
+    const float *uniforms;
+    uint64_t seed;
+    const int64_t *clip_index;
+    int64_t *codes;
+};
+// What a mixed entry MAY take: a suffixed entry sets the fields its parameters name; null / 0 is the entry without that keyword
+struct MixedOpts {
+    const ts_sampling *ctl_host = nullptr;   // sampling controls
+    int n_ctl = 0;
+    float *logprob = nullptr;                // log-probabilities
+    const int64_t *given = nullptr;          // given rows
+    const int32_t *given_rows_host = nullptr;
+    const uint8_t *keep = nullptr;           // kept positions
+    const float *style = nullptr;            // speaker style
+    int style_rows = 0;
+    const float *bias = nullptr;             // code bias
+    int n_bias = 0;
+    const int32_t *bias_index_host = nullptr;
+    const ts_repeat *rep_host = nullptr;     // repetition penalty
+    int n_rep = 0;
+    // the body wrapper only: given poses
+    const float *given_poses = nullptr;
+    int P_max = 0;
+    const int32_t *pose_lens_host = nullptr, *pose_lens_dev = nullptr;
+};
+// pixelcnn.cpp: the one body behind ts_pixelcnn_generate_mixed and its suffixed siblings (a.ids the labels, a.rows = H_max)
+int pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPass &a, const MixedOpts &o, hipStream_t s);
+// the checks both levels make with one text: `who` the entry family the messages name, `rows_name` what it calls its H code rows
+inline int mixed_style_rows_check(const char *who, const char *rows_name, const MixedOpts &o, int H) {
+    if (!o.style || o.style_rows == 1 || o.style_rows == H) return 0;
+    return fail(std::string(who) + "_style: style_rows is 1 or " + rows_name + " = " + std::to_string(H) + ", got " + std::to_string(o.style_rows));
+}
+inline int mixed_given_check(const char *who, const MixedOpts &o, const int32_t *lens_host, int B) {
+    if (o.keep && !o.given) return fail(std::string(who) + "_keep: a mask of kept positions needs the given codes it selects from");
+    if (!o.given) return 0;
+    if (!o.given_rows_host) return fail(std::string(who) + "_given: given codes need their row table");
+    return ts_given_rows_check(o.given_rows_host, lens_host, B);
+}
+
 }  // namespace ts

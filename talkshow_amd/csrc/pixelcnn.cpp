@@ -785,18 +785,14 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
     }
     MiscScope ms(p->ctx, s);
     float *lp = c.logprob ? c.logprob + (size_t)ro * 2 + j : nullptr;
+    SampleCtlParams cp;   // read by the given and the controlled samplers only
+    cp.s = sp, cp.ctl = c.ctl, cp.kept = nullptr;
+    cp.logprob = lp, cp.lp_stride = (long)sH * 2;
+    cp.bias = c.bias, cp.bias_index = c.bias_index, cp.bias_col = j;
+    cp.rep = c.rep, cp.rep_ring = c.rep_ring;
     if (c.given_rows) {
         SampleGivenParams gp;
-        gp.c.s = sp;
-        gp.c.ctl = c.ctl;
-        gp.c.kept = nullptr;
-        gp.c.logprob = lp;
-        gp.c.lp_stride = (long)sH * 2;
-        gp.c.bias = c.bias;
-        gp.c.bias_index = c.bias_index;
-        gp.c.bias_col = j;
-        gp.c.rep = c.rep;
-        gp.c.rep_ring = c.rep_ring;
+        gp.c = cp;
         gp.rows = c.given_rows;
         gp.given = c.given + (size_t)ro * 2 + j;
         gp.given_stride = (long)sH * 2;
@@ -804,17 +800,6 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
         gp.keep_stride = (long)sH * 2;
         TS_HIP(launch_sample_given(gp, s));
     } else if (c.ctl) {
-        SampleCtlParams cp;
-        cp.s = sp;
-        cp.ctl = c.ctl;
-        cp.kept = nullptr;
-        cp.logprob = lp;
-        cp.lp_stride = (long)sH * 2;
-        cp.bias = c.bias;
-        cp.bias_index = c.bias_index;
-        cp.bias_col = j;
-        cp.rep = c.rep;
-        cp.rep_ring = c.rep_ring;
         TS_HIP(launch_sample_ctl(cp, s));
     } else if (lp) {
         SampleLpParams q;
@@ -1261,9 +1246,9 @@ int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const c
 // The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own table — may be queued behind each other.
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
-inline int sampler_bits(const SampleCtl *ctl, const float *logprob, const int *given_rows = nullptr, const unsigned char *keep = nullptr,
-                        const float *style = nullptr, const float *bias = nullptr, const SampleRep *rep = nullptr) {
-    return (ctl ? 1 : 0) | (logprob ? 2 : 0) | (given_rows ? 4 : 0) | (given_rows && keep ? 8 : 0) | (style ? 16 : 0) | (bias ? 32 : 0) | (rep ? 64 : 0);
+inline int sampler_bits(const RunCfg &c, const float *logprob) {
+    const bool given = c.given_rows;
+    return (c.ctl ? 1 : 0) | (logprob ? 2 : 0) | (given ? 4 : 0) | (given && c.keep_src ? 8 : 0) | (c.style ? 16 : 0) | (c.bias ? 32 : 0) | (c.rep ? 64 : 0);
 }
 int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
     static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
@@ -1410,26 +1395,40 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
 // short last chunk serve every clip length.  The audio terms were computed for the whole call; a chunk's rows are copied into the
 // compact chunk buffers its graph reads.  Bit-identical to the whole-call graph (same launches, same order, same rings: only the
 // look-ahead partial sums of rows past the end are computed and never read).
+// rows [r0, r0 + Hc) of a call of out_H rows as one chunk: a 4-row token ring, the Work's compact chunk buffers for the audio terms
+RunCfg chunk_cfg(ts_pixelcnn::Work *w, int B, int r0, int Hc, int out_H, int mode, uint64_t seed, int64_t clip0) {
+    RunCfg c{B, Hc, 0, r0 + Hc, mode, nullptr, seed, clip0, nullptr, nullptr, nullptr, w,
+             /* ring */ 4, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
+    c.aeh = w->cAEH.f(), c.aeh1 = w->cAEH1.f(), c.av1c = w->cAV1C.f(), c.av1p = w->cAV1P.f();
+    c.out_H = out_H;
+    c.out_row0 = r0;
+    return c;
+}
+// the graph key of chunk `c` in a pass of Bs clip slots (0: a uniform call): its rows, the buffer phase of its first row, its samplers
+ts_pixelcnn::Work::Key chunk_key(const RunCfg &c, int Bs, const float *logprob) {
+    const int r0 = c.out_row0, phase = r0 < 3 ? r0 : 3 + (r0 % 4);
+    return std::make_tuple(c.B, c.H, -(1 + phase), c.mode, Bs, sampler_bits(c, logprob));
+}
+// the chunk's rows of the whole call's audio terms (H rows per clip), for the first B clips, into the chunk buffers
+int stage_chunk_audio(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int r0, int Hc, int H, hipStream_t s) {
+    const size_t D = p->D, f = sizeof(float);
+    struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
+        {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
+    for (auto &m : rows)
+        if (p->NL > 1 || m.src == &w->AEH)
+            TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H * m.width * f,
+                                    (size_t)Hc * m.width * f, B, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 int run_chunked(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
                 int64_t *codes, const SampleCtl *ctl, float *logprob, hipStream_t s) {
-    const size_t D = p->D, f = sizeof(float);
-    constexpr int RING = 4;
     for (int r0 = 0; r0 < H; r0 += CHUNK_ROWS) {
         const int Hc = std::min(CHUNK_ROWS, H - r0);
-        RunCfg c{B, Hc, 0, r0 + Hc, mode, nullptr, seed, clip0, nullptr, nullptr, nullptr, w,
-                 RING, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
-        c.aeh = w->cAEH.f(), c.aeh1 = w->cAEH1.f(), c.av1c = w->cAV1C.f(), c.av1p = w->cAV1P.f();
-        c.out_H = H;
-        c.out_row0 = r0;
+        RunCfg c = chunk_cfg(w, B, r0, Hc, H, mode, seed, clip0);
         c.ctl = ctl;
-        struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
-            {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
-        for (auto &m : rows)
-            if (p->NL > 1 || m.src == &w->AEH)
-                TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H * m.width * f,
-                                        (size_t)Hc * m.width * f, B, hipMemcpyDeviceToDevice, s));
-        const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, std::make_tuple(B, Hc, -(1 + phase), mode, 0, sampler_bits(ctl, logprob)), uniforms, codes, logprob, s));
+        TS_TRY(stage_chunk_audio(p, w, B, r0, Hc, H, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, true, chunk_key(c, 0, logprob), uniforms, codes, logprob, s));
     }
     return 0;
 }
@@ -1467,46 +1466,46 @@ int mixed_plan(const int *hrows, int B, int max_counts, std::vector<int> &active
 // graph it needs and captures nothing from its second run on
 constexpr int MIXED_MAX_COUNTS = 12;
 
-int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std::vector<int> &hrows, int mode, const float *uniforms,
-              uint64_t seed, int64_t *codes, bool graph, const SampleCtl *ctl, float *logprob, const int64_t *given, int given_max,
-              const unsigned char *keep, const float *style_track, const int *lens_dev, bool biased, bool repeat, hipStream_t s) {
-    const size_t D = p->D, f = sizeof(float);
-    constexpr int RING = 4;
+// the chunks of one validated pass whose tables are staged in the Work: a.rows = H_max, hrows the clips' own code rows
+int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, const MixedPass &a, const MixedOpts &o, const std::vector<int> &hrows, bool graph, hipStream_t s) {
+    const int B = a.B, H_max = a.rows;
+    const size_t D = p->D;
+    const bool tracked = o.style && o.style_rows > 1;
+    int given_max = 0;
+    if (o.given)
+        for (int b = 0; b < B; ++b) given_max = std::max(given_max, (int)o.given_rows_host[b]);
     std::vector<int> active;
     (void)mixed_plan(hrows.data(), B, MIXED_MAX_COUNTS, active);
     for (int k = 0; k < (int)active.size(); ++k) {
         const int r0 = k * CHUNK_ROWS, Hc = std::min(CHUNK_ROWS, hrows[0] - r0), Ba = active[k];
-        RunCfg c{Ba, Hc, 0, r0 + Hc, mode, nullptr, seed, 0, nullptr, nullptr, nullptr, w,
-                 RING, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
-        c.aeh = w->cAEH.f(), c.aeh1 = w->cAEH1.f(), c.av1c = w->cAV1C.f(), c.av1p = w->cAV1P.f();
-        c.out_H = H_max;
-        c.out_row0 = r0;
+        RunCfg c = chunk_cfg(w, Ba, r0, Hc, H_max, a.mode, a.seed, 0);
         c.Bs = B;
         c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
-        c.ctl = ctl;   // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
-        if (biased) c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);   // by slot, too
-        if (repeat) {   // records and rings by slot; without tables the index the caller staged is -1 everywhere and c.bias stays null
+        // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
+        if (o.ctl_host || o.bias || o.rep_host) c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
+        if (o.bias) c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);   // by slot, too
+        if (o.rep_host) {   // records and rings by slot; without tables the index the caller staged is -1 everywhere and c.bias stays null
             c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
             c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
             c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
         }
-        if (given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
+        if (o.given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
             c.given_rows = w->given_tab.i();
-            c.given_src = given;
-            c.keep_src = keep;   // a masked pass runs the masked form in every chunk, too
+            c.given_src = o.given;
+            c.keep_src = o.keep;   // a masked pass runs the masked form in every chunk, too
             c.given_stage = r0 < given_max;
         }
-        if (style_track) {   // the chunk's conditioning rows, staged eagerly ahead of the replay like its uniforms and given codes: the only
-                             // launch that reads the caller's weight block, so no caller pointer enters a captured graph
+        if (tracked) {   // the chunk's conditioning rows, staged eagerly ahead of the replay like its uniforms and given codes: the only
+                         // launch that reads the caller's weight block, so no caller pointer enters a captured graph
             MiscScope ms(p->ctx, s);
             StyleRowsParams q;
             std::memset(&q, 0, sizeof(q));
             q.tables = p->cls_all.f();
-            q.weights = style_track;
+            q.weights = o.style;
             q.w_ld = p->NC;
             q.S = H_max, q.NC = p->NC, q.W = (int)(2 * D), q.NL = p->NL;
             q.r0 = r0, q.n = Hc, q.slots = Ba;
-            q.lens = lens_dev, q.len_shr = 2;
+            q.lens = a.lens_dev, q.len_shr = 2;
             q.out = w->style_int.f();
             q.out_l_stride = (long)CHUNK_ROWS * B * 2 * D;
             q.out_r_stride = (long)B * 2 * D;
@@ -1514,14 +1513,8 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int H_max, const std:
             c.style = w->style_int.f();
             c.style_r0 = r0;
         }
-        struct { const DevBuf *src; DevBuf *dst; size_t width; } rows[4] = {
-            {&w->AEH, &w->cAEH, D}, {&w->AEH1, &w->cAEH1, 2 * D}, {&w->AV1C, &w->cAV1C, 4 * D}, {&w->AV1P, &w->cAV1P, 4 * D}};
-        for (auto &m : rows)
-            if (p->NL > 1 || m.src == &w->AEH)
-                TS_HIP(hipMemcpy2DAsync(m.dst->p, (size_t)Hc * m.width * f, m.src->f() + (size_t)r0 * m.width, (size_t)H_max * m.width * f,
-                                        (size_t)Hc * m.width * f, Ba, hipMemcpyDeviceToDevice, s));
-        const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(Ba, Hc, -(1 + phase), mode, B, sampler_bits(ctl, logprob, c.given_rows, c.keep_src, c.style, c.bias, c.rep)), uniforms, codes, logprob, s));
+        TS_TRY(stage_chunk_audio(p, w, Ba, r0, Hc, H_max, s));
+        TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, chunk_key(c, B, o.logprob), a.uniforms, a.codes, o.logprob, s));
     }
     return 0;
 }
@@ -1920,16 +1913,18 @@ int ts_op_style_rows(ts_ctx *ctx, const float *tables, int NL, int NC, int W, co
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
-    return ts_pixelcnn_generate_mixed_lp(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                         nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
 // the mixed pass with a log-probability output (B,H_max,2): rows at or beyond a clip's own H_b are 0 (logprob == NULL: the entry above)
 int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                   int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                   int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, void *stream) {
-    return ts_pixelcnn_generate_mixed_given(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                            logprob, nullptr, nullptr, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
 // Host only: the rule every _given entry applies to its row table before anything is launched
@@ -1948,16 +1943,20 @@ int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const
                                      int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                      int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                      const int32_t *given_rows_host, const int32_t *given_rows_dev, void *stream) {
-    return ts_pixelcnn_generate_mixed_keep(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                           logprob, given, given_rows_host, given_rows_dev, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
 int ts_pixelcnn_generate_mixed_keep(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                     int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, void *stream) {
-    return ts_pixelcnn_generate_mixed_style(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                            logprob, given, given_rows_host, given_rows_dev, keep, nullptr, 0, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
 // the given pass with a mask of kept positions beside the given block (talkshow_hip.h, "kept positions"): position (r, j) of clip b is taken
@@ -1970,8 +1969,11 @@ int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const
                                      int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                      const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
                                      int style_rows, void *stream) {
-    return ts_pixelcnn_generate_mixed_bias(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                           logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, nullptr, 0, nullptr, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
 // Host only ("code bias"): what every entry that takes tables checks of their number and of the index table before anything is launched
@@ -1996,9 +1998,11 @@ int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const 
                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
                                     int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host, void *stream) {
-    return ts_pixelcnn_generate_mixed_repeat(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, ctl_host, n_ctl,
-                                             logprob, given, given_rows_host, given_rows_dev, keep, style, style_rows, bias_dev, n_bias,
-                                             bias_index_host, nullptr, 0, stream);
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
 // Host only ("repetition penalty"): n records — window in [0, 64], presence and frequency finite with |x| <= 1e30, reserved 0 — for a
@@ -2035,92 +2039,96 @@ int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *p, const int64_t *label, cons
                                       const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
                                       int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host,
                                       const ts_repeat *rep_host, int n_rep, void *stream) {
-    (void)given_rows_dev;   // the table travels as kernel arguments from the host copy (see talkshow_hip.h)
-    if (!p || (!label && !style) || !aud || !lens_host || !lens_dev || !codes) return fail("ts_pixelcnn_generate_mixed: null argument");
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// The body of every ts_pixelcnn_generate_mixed* entry: each fills `o` with its own arguments, so an absent keyword is null here and costs no
+// launch, no buffer and no bit of a graph key.  (given_rows_dev is not passed on: the table travels as kernel arguments from the host copy.)
+int ts::pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPass &a, const MixedOpts &o, hipStream_t s) {
+    const int B = a.B, H_max = a.rows, mode = a.mode;
+    if (!p || (!a.ids && !o.style) || !aud || !a.lens_host || !a.lens_dev || !a.codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
-    if (style && style_rows != 1 && style_rows != H_max)
-        return fail("ts_pixelcnn_generate_mixed_style: style_rows is 1 or H_max = " + std::to_string(H_max) + ", got " + std::to_string(style_rows));
-    const bool tracked = style && style_rows > 1;   // H_max == 1: one row per clip either way
+    TS_TRY(mixed_style_rows_check("ts_pixelcnn_generate_mixed", "H_max", o, H_max));
+    const bool tracked = o.style && o.style_rows > 1;   // H_max == 1: one row per clip either way
     if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail("ts_pixelcnn_generate_mixed: bad mode");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_pixelcnn_generate_mixed: uniforms required");
+    if (mode == TS_SAMPLE_UNIFORMS && !a.uniforms) return fail("ts_pixelcnn_generate_mixed: uniforms required");
     std::vector<int> hrows(B);
     for (int b = 0; b < B; ++b) {
-        if (lens_host[b] < 4) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
-        if (b > 0 && lens_host[b] > lens_host[b - 1])
+        if (a.lens_host[b] < 4) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " is shorter than 4 frames (one code row)");
+        if (b > 0 && a.lens_host[b] > a.lens_host[b - 1])
             return fail("ts_pixelcnn_generate_mixed: lengths must be non-increasing (clip " + std::to_string(b) + " is longer than the one before it)");
-        hrows[b] = lens_host[b] >> 2;
+        hrows[b] = a.lens_host[b] >> 2;
         if (hrows[b] > H_max) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " has more code rows than H_max");
     }
     std::vector<SampleCtl> tab;
-    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
-    if (bias_dev || rep_host) {   // sampling controls with the table's scope; without a table the pass runs on neutral records (the plain sampler's bits)
-        if (!ctl_host) {
+    if (o.ctl_host) TS_TRY(ctl_table(o.ctl_host, o.n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
+    if (o.bias || o.rep_host) {   // sampling controls with the table's scope; without a table the pass runs on neutral records (the plain sampler's bits)
+        if (!o.ctl_host) {
             const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
-            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, rep_host ? "ts_pixelcnn_generate_mixed_repeat" : "ts_pixelcnn_generate_mixed_bias", tab));
+            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, o.rep_host ? "ts_pixelcnn_generate_mixed_repeat" : "ts_pixelcnn_generate_mixed_bias", tab));
         }
-        if (bias_dev) TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
+        if (o.bias) TS_TRY(ts_code_bias_index_check(o.bias_index_host, B, o.n_bias));
     }
     std::vector<SampleRep> rtab;
-    if (rep_host) TS_TRY(rep_table(rep_host, n_rep, B, p->V, "ts_pixelcnn_generate_mixed_repeat", rtab));
-    const bool with_ctl = ctl_host || bias_dev || rep_host;
-    int given_max = 0;
-    if (keep && !given) return fail("ts_pixelcnn_generate_mixed_keep: a mask of kept positions needs the given codes it selects from");
-    if (given) {
-        if (!given_rows_host) return fail("ts_pixelcnn_generate_mixed_given: given codes need their row table");
-        TS_TRY(ts_given_rows_check(given_rows_host, lens_host, B));
-        for (int b = 0; b < B; ++b) given_max = std::max(given_max, (int)given_rows_host[b]);
-    }
-    hipStream_t s = (hipStream_t)stream;
+    if (o.rep_host) TS_TRY(rep_table(o.rep_host, o.n_rep, B, p->V, "ts_pixelcnn_generate_mixed_repeat", rtab));
+    TS_TRY(mixed_given_check("ts_pixelcnn_generate_mixed", o, a.lens_host, B));
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));
-    if (with_ctl) TS_TRY(put_ctl_table(ctx, w, tab, s));
-    if (bias_dev) {   // n_bias <= B <= capB tables: the buffer follows capB alone (see Work::bias_tab); the index travels as kernel arguments
+    if (o.ctl_host || o.bias || o.rep_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
+    if (o.bias) {   // n_bias <= B <= capB tables: the buffer follows capB alone (see Work::bias_tab); the index travels as kernel arguments
         TS_TRY(w->bias_tab.ensure((size_t)w->capB * 2 * p->V * sizeof(float)));
         MiscScope ms(ctx, s);
-        TS_HIP(hipMemcpyAsync(w->bias_tab.p, bias_dev, (size_t)n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
-        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), bias_index_host, B, s));
+        TS_HIP(hipMemcpyAsync(w->bias_tab.p, o.bias, (size_t)o.n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
+        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), o.bias_index_host, B, s));
     }
-    if (rep_host) {   // the records as kernel arguments, like the sampling table; a pass without tables brings the index the BIAS path wants
+    if (o.rep_host) {   // the records as kernel arguments, like the sampling table; a pass without tables brings the index the BIAS path wants
         static_assert(sizeof(SampleRep) == 4 * sizeof(int), "SampleRep is four words");
         MiscScope ms(ctx, s);
         TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
-        if (!bias_dev) {
+        if (!o.bias) {
             const std::vector<int32_t> none(B, -1);
             TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), none.data(), B, s));
         }
     }
-    if (given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
+    if (o.given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
         MiscScope ms(ctx, s);
-        TS_HIP(launch_put_words(w->given_tab.i(), given_rows_host, B, s));
+        TS_HIP(launch_put_words(w->given_tab.i(), o.given_rows_host, B, s));
     }
     TS_TRY(audio_terms(p, w, aud, B, H_max, s));
     if (tracked) {   // sized with the Work's clip capacity, so it moves only when ensure_work has dropped the graphs that read it
                      // (its size follows capB alone, and no graph reads it before its first allocation)
         TS_TRY(w->style_int.ensure((size_t)p->NL * CHUNK_ROWS * w->capB * 2 * p->D * sizeof(float)));
-    } else if (style) {
-        TS_TRY(class_rows_style(p, w, style, B, s));
+    } else if (o.style) {
+        TS_TRY(class_rows_style(p, w, o.style, B, s));
     } else {
-        TS_TRY(class_rows(p, w, label, B, s));
+        TS_TRY(class_rows(p, w, a.ids, B, s));
     }
     {   // the clips' Philox subsequences, in a Work buffer (what the captured samplers read): the caller's table, or 0 .. B-1
         MiscScope ms(ctx, s);
-        if (clip_index) TS_HIP(hipMemcpyAsync(w->clip_tab.p, clip_index, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        if (a.clip_index) TS_HIP(hipMemcpyAsync(w->clip_tab.p, a.clip_index, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
         else TS_HIP(launch_iota_i64(static_cast<int64_t *>(w->clip_tab.p), B, 0, s));
     }
-    const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_mixed(p, w, B, H_max, hrows, mode, uniforms, seed, codes, graph, with_ctl ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr,
-                     logprob, given, given_max, keep, tracked ? style : nullptr, lens_dev, bias_dev != nullptr, rep_host != nullptr, s));
+    TS_TRY(run_mixed(p, w, a, o, hrows, p->use_graph && !ctx->prof.on, s));
     MiscScope ms(ctx, s);
-    TS_HIP(launch_mask_codes(codes, B, H_max, lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
-    if (logprob) TS_HIP(launch_mask_logprob(logprob, B, H_max, lens_dev, s));   // and their log-probabilities: 0
+    TS_HIP(launch_mask_codes(a.codes, B, H_max, a.lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
+    if (o.logprob) TS_HIP(launch_mask_logprob(o.logprob, B, H_max, a.lens_dev, s));   // and their log-probabilities: 0
     return 0;
 }
+
+extern "C" {
 
 int ts_pixelcnn_generate_mixed(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                int64_t *codes, void *stream) {
-    return ts_pixelcnn_generate_mixed_ctl(p, label, aud, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes, nullptr, 0, stream);
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, MixedOpts(), (hipStream_t)stream);
 }
 
 int ts_pixelcnn_generate_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, int B, int H, int mode,
@@ -2180,7 +2188,7 @@ int ts_pixelcnn_generate_lp(ts_pixelcnn *p, const int64_t *label, const float *a
                                     (size_t)H * 2 * e, B, hipMemcpyDeviceToDevice, s));
         TS_HIP(launch_i64_to_i32(tf, w->tok32.i(), (long)B * Htot * 2, s));
     }
-    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0, sampler_bits(ctl, logprob));
+    const ts_pixelcnn::Work::Key key = std::make_tuple(B, H, H0, mode, 0, sampler_bits(c, logprob));
     // A shape without a whole-call graph runs as chunk graphs (two or three small captures that serve every clip length) until it is
     // hot (Work::hot: pinned by ts_pixelcnn_prepare, or its third sighting among the last 16 one-shot calls of this stream); then it gets
     // its own whole-call graph (one replay per call: the serving loops, bench.py).  The cache is bounded either way.

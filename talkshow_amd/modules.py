@@ -467,39 +467,20 @@ class GatedPixelCNN(NativeModule):
             i32p = C.POINTER(C.c_int32)
             lens = np.full(B, 4 * H, np.int32)
             lens_dev = upload(lens, dev)
-            block_dev = upload(block, dev) if given is not None else None
             clip_index = upload(np.arange(B, dtype=np.int64) + int(clip_index0), dev)
             if isinstance(lp, str):
                 lp = torch.empty((B, H, 2), dtype=torch.float32, device=dev)
-            gargs = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
-                     _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), ctl, n_ctl, _lib.dptr(lp),
-                     _lib.dptr(block_dev), table.ctypes.data_as(i32p) if given is not None else None, None)
-            if rtab is not None:
-                keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
-                style_dev = upload(sblock, dev) if sblock is not None else None
-                bias_dev = upload(btab, dev) if btab is not None else None
-                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_repeat(*gargs, _lib.dptr(keep_dev), _lib.dptr(style_dev),
-                                                                         int(sblock.shape[1]) if sblock is not None else 0, _lib.dptr(bias_dev),
-                                                                         int(btab.shape[0]) if btab is not None else 0,
-                                                                         bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep,
-                                                                         _lib.stream_ptr()))
-            elif btab is not None:
-                keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
-                style_dev = upload(sblock, dev) if sblock is not None else None
-                bias_dev = upload(btab, dev)
-                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_bias(*gargs, _lib.dptr(keep_dev), _lib.dptr(style_dev),
-                                                                       int(sblock.shape[1]) if sblock is not None else 0, _lib.dptr(bias_dev),
-                                                                       int(btab.shape[0]), bidx.ctypes.data_as(i32p), _lib.stream_ptr()))
-            elif sblock is not None:
-                keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
-                style_dev = upload(sblock, dev)
-                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_style(*gargs, _lib.dptr(keep_dev), _lib.dptr(style_dev), int(sblock.shape[1]),
-                                                                        _lib.stream_ptr()))
-            elif kblock is None:
-                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_given(*gargs, _lib.stream_ptr()))
-            else:
-                keep_dev = upload(kblock, dev)
-                _lib.check(_lib.load().ts_pixelcnn_generate_mixed_keep(*gargs, _lib.dptr(keep_dev), _lib.stream_ptr()))
+            fixed = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
+                     _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes))
+            block_dev = upload(block, dev) if given is not None else None
+            keep_dev = upload(kblock, dev) if kblock is not None and given is not None else None
+            style_dev = upload(sblock, dev) if sblock is not None else None
+            bias_dev = upload(btab, dev) if btab is not None else None
+            _lib.pixelcnn_mixed_call(
+                fixed, ctl=ctl, n_ctl=n_ctl, logprob=_lib.dptr(lp), given=_lib.dptr(block_dev), given_rows=table.ctypes.data_as(i32p) if given is not None else None,
+                keep=_lib.dptr(keep_dev), style=_lib.dptr(style_dev), style_rows=int(sblock.shape[1]) if sblock is not None else 0,
+                bias=_lib.dptr(bias_dev), n_bias=int(btab.shape[0]) if btab is not None else 0, bias_index=bidx.ctypes.data_as(i32p) if btab is not None else None,
+                rep=rtab, n_rep=n_rep)
             return (codes, None) if lp is None else (codes, None, lp)
         args = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0)
