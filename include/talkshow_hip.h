@@ -188,10 +188,11 @@ typedef struct ts_sampling {
  * travels to the stream's work buffers as kernel arguments ahead of the replay, no host memory is read after the call returns, nothing
  * synchronises, any number of calls may be queued — captures nothing.  BUDGET: a host that alternates passes with and without a table on
  * one stream shares the 16 chunk graphs (and the 8 whole-call graphs) kept per stream between the two kinds.
- * Out of scope: ts_pixelcnn_stream_* (and BodyStream), ts_pixelcnn_v_*, the face generator.  (A STATIC per-clip bias on the codes,
+ * The streaming sessions take a table per step (ts_pixelcnn_stream_step_ctl, "streaming sessions" below: the records hold for that step
+ * only).  Out of scope: ts_pixelcnn_v_*, the face generator.  (A STATIC per-clip bias on the codes,
  * allow-lists and bans included, is in scope: "code bias" below; so is a windowed penalty on the codes a clip has already produced:
- * "repetition penalty" below.)  Log-probabilities (below) share the scope: the streaming sessions, ts_pixelcnn_v_* and the face generator return
- * none, clips of different lengths are not SCORED in one pass, and scoring runs the rows one after the other as the decode does (given
+ * "repetition penalty" below.)  Log-probabilities (below) share the scope: a session's step returns those of its own rows, ts_pixelcnn_v_* and the face
+ * generator return none, a session does not SCORE given codes (its given rows apart), clips of different lengths are not SCORED in one pass, and scoring runs the rows one after the other as the decode does (given
  * the codes, teacher-forced rows do not depend on each other and could run as large GEMMs: other work, with other bits). */
 /* Host only: the validation every _ctl entry applies before anything is launched.  n records for vocabulary V, 1 <= V <= 8191 (a larger V
  * is an error: see step 4); 0, or an error whose message names the clip: temperature not finite / <= 0 / with an infinite fp32 reciprocal, top_p outside (0, 1], top_k < 0, reserved != 0.
@@ -438,7 +439,8 @@ int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *pix, const int64_t *label_dev, co
  * work buffers ahead of its replay, for chunks with rows below max G_b only.  A repeated pass captures nothing, whatever its tables.
  * Passes without given rows find the keys, graphs and launches they found before.  given_dev == NULL: exactly the _lp entry.
  * Out of scope: rows inside every active clip's prefix still run the horizontal stack (the eager H0 path of ts_pixelcnn_generate skips
- * it); the streaming sessions are untouched; uniform lengths are the special case of equal lens (no uniform entry). */
+ * it); a streaming session takes given rows per step ("streaming sessions" below: the first g_b rows OF THE STEP); uniform lengths are the
+ * special case of equal lens (no uniform entry). */
 int ts_given_rows_check(const int32_t *given_rows_host, const int32_t *lens_host, int B);
 int ts_body_pixel_infer_mixed_given(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
                                     const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
@@ -572,7 +574,9 @@ int ts_body_pixel_infer_mixed_poses_keep(ts_convnet *audioenc, ts_pixelcnn *pix,
  * The style is orthogonal to sampling records, log-probabilities, given rows / poses, kept positions, clip indices and the draw modes.
  * Forced rows run under the style too (it shapes the row cache): handing back the head of an earlier decode WITH THE SAME STYLE returns
  * that decode bit for bit.
- * Out of scope: the streaming sessions, ts_body_pixel_infer, the face path, the single-stack form, weights per layer. */
+ * The streaming sessions take one weight row per clip per step, which holds until a later step brings another ("streaming sessions"
+ * below).  Out of scope: per-row tracks inside a session's step, ts_body_pixel_infer, the face path, the single-stack form, weights per
+ * layer. */
 int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
                                      const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
                                      const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
@@ -634,8 +638,8 @@ int ts_op_style_rows(ts_ctx *ctx, const float *tables_dev, int NL, int NC, int W
  * tables captures nothing.  The table buffer is sized for one table per clip of the work set's clip CAPACITY (8 V bytes per clip), so it
  * NEVER MOVES between the passes of one capacity; the capacity grows only where every work buffer grows, and that drops all graphs of
  * the stream.  Passes without a bias launch the kernels and find the graphs they always did.
- * Out of scope: per-row bias tracks; the streaming sessions
- * (ts_pixelcnn_stream_*, BodyStream); ts_pixelcnn_v_*; the face generator; the scoring entries (score_clips / score_motion_clips take no
+ * The streaming sessions take tables per step ("streaming sessions" below).
+ * Out of scope: per-row bias tracks; ts_pixelcnn_v_*; the face generator; the scoring entries (score_clips / score_motion_clips take no
  * sampling table either). */
 int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
                                     const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
@@ -709,7 +713,14 @@ typedef struct ts_repeat {
  * without records launch the kernels and find the graphs they always did.
  * The entries: the _bias sibling of each family plus `const ts_repeat *rep_host, int n_rep` ahead of the stream: n_rep = 1 (one record
  * for all clips) or B records in slot order.  rep_host == NULL: the _bias entry, launch for launch.
- * Out of scope: the streaming sessions (ts_pixelcnn_stream_*, BodyStream); ts_pixelcnn_v_*; the single-stack form; the scoring entries;
+ * Sessions.  The device record's fourth word is from_row, the first absolute row of the clip's current unbroken run of rows written under
+ * window > 0: a launch at row r counts min(r - from_row, W) entries.  Every entry above leaves it 0 (a pass's history starts at row 0), so
+ * their bits are those of min(r, W).  A streaming session (ts_pixelcnn_stream_step_ctl) keeps its rings between steps — a window reaches
+ * back across step seams — and one from_row per clip on the host: set to the step's first row when the clip's window becomes positive
+ * after being absent or 0, dropped when a step brings the clip no record or window = 0.  A penalty switched on mid-session therefore
+ * starts from an EMPTY history at that row and never reads ring entries left by rows 64, 128, ... earlier.  ts_repeat and
+ * ts_op_sample_repeat are unchanged: the word is not part of the public record.
+ * Out of scope: ts_pixelcnn_v_*; the single-stack form; the scoring entries;
  * the face generator; windows beyond 64 rows; penalties that read the other column or other clips. */
 int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
                                       const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
@@ -899,6 +910,35 @@ int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud_dev, int Hc
                             uint64_t seed, int64_t clip_index0, int64_t *codes_dev, void *stream);
 /* code rows generated so far */
 int64_t ts_pixelcnn_stream_rows(const ts_pixelcnn_stream *st);
+/* Streaming sessions with per-clip sampling controls.  ts_pixelcnn_stream_step plus the optional pieces of a mixed pass, each under the
+ * rule of the mixed entry of the same name and FOR THIS STEP ONLY; all NULL / 0: ts_pixelcnn_stream_step launch for launch, on its graph
+ * keys (sixth field 0), with its bits.  Everything is checked on the host, the failing clip named, before anything is launched and before
+ * the session's row counter moves.  Rows are absolute: Philox positions, given-row tests and the history ring of a step that starts at
+ * row r0 are those of rows r0 .. r0 + Hc - 1 of a one-shot call, so a clip stepped under some pieces equals ts_pixelcnn_generate_mixed_*
+ * under the same pieces bit for bit, codes and log-probabilities.
+ *   ctl_host, n_ctl      "sampling controls": 1 record for all clips or B in slot order; UNIFORMS / PHILOX only.  A step without a table
+ *                        runs the plain sampler.
+ *   logprob_dev          (B,Hc,2) fp32, "log-probabilities" of this step's codes, written in the sampler launch; every mode.
+ *   given_dev,           (B,Hc,2) int64 and (B,) with 0 <= g_b <= Hc: clip b's first g_b rows OF THIS STEP are taken, the rest produced
+ *   given_rows_host      ("given rows"; the samplers' table holds r0 + g_b).  A taken code draws no number; with logprob_dev it scores under
+ *                        the distribution it would have been drawn from; it enters the row cache and the history ring.
+ *   style_dev            (B,NC) "speaker style" weights, one row per clip: the conditioning rows are rewritten ahead of this step and STAY
+ *                        until a later step brings others (NULL: as they are; at row 0 the labels given at open).  A one-hot row is the
+ *                        label bit for bit.
+ *   bias_dev, n_bias,    "code bias": (n_bias,2,V) tables and (B,) table index or -1.  Without ctl_host the step runs on neutral records.
+ *   bias_index_host      The session's table buffer is allocated at its first biased step, sized by its fixed clip count: it never moves.
+ *   rep_host, n_rep      "repetition penalty" over the session's own rings (see "Sessions" there): 1 record or B.
+ * Graphs: the sixth key field is the samplers' bit set as in a mixed pass; records, tables, given codes and style are in no key, so a
+ * second step of the same (Hc, buffer phase) under other values captures nothing, and plain steps keep their graphs.
+ * Not taken by a session: a mask of kept positions, given poses, style tracks inside a step, the scoring entries. */
+int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud_dev, int Hc, int mode, const float *uniforms_dev,
+                                uint64_t seed, int64_t clip_index0, int64_t *codes_dev,
+                                const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                const int64_t *given_dev, const int32_t *given_rows_host,
+                                const float *style_dev,
+                                const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                const ts_repeat *rep_host, int n_rep, void *stream);
+int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st);   /* hipGraphs this session has captured so far */
 void ts_pixelcnn_stream_close(ts_pixelcnn_stream *st);
 
 /* ---- batched SMPL-X joints / vertices ----------------------------------------------------------------

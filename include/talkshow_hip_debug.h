@@ -320,6 +320,11 @@ int ts_debug_code_table_stage(ts_pixelcnn *pix, int which, const int32_t *tok_de
  * -1 on a bad table.  No reference counterpart. */
 int ts_debug_mixed_plan(const int32_t *hrows, int B, int max_counts, int32_t *active_out);
 
+/* Host-only (no GPU): the device records the library makes of n_rep (1 or B) public repetition records (talkshow_hip.h, "repetition
+ * penalty"), four 32-bit words per clip slot into words_out (4 B,): window, presence, frequency (their bits) and from_row, which every
+ * one-shot pass leaves 0 (only a streaming session sets it).  The rules of ts_repeat_check.  No reference counterpart. */
+int ts_debug_rep_table(const ts_repeat *rep_host, int n_rep, int B, int V, int32_t *words_out);
+
 /* Test aid: the paired, length-masked codebook search of a mixed pass on given latents (talkshow_hip.h, "given poses"; csrc/vq.hip:
  * vq_argmin_pair_lds_kernel).  z_body_dev (B H_max, dim_body), z_hand_dev (B H_max, dim_hand), lens_dev (B,) int32 POSE frame counts in any
  * order, codebooks (ncode, dim) in device memory -> codes_dev (B, H_max, 2) int64: column 0 / 1 = body / hand; row h of clip b holds what

@@ -652,8 +652,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         `greedy=True` (argmax decode), `seed=int`, `uniforms=(B,H,2)`, and the sampling controls `temperature=`, `top_k=`, `top_p=`
         (one record for all B samples; `generate_batch(..., sampling=)`), and `code_bias=` — ONE (2, V) table (or {"body", "hand"} dict) for
         all B samples: which codes the decode may use (`generate_clips`), and `repeat=` — ONE (window, presence, frequency) record or
-        dict for all B samples: a repetition penalty over a window of earlier codes (`generate_clips`).  The streaming session behind `continuity=True` takes no
-        controls yet: together they raise ValueError.
+        dict for all B samples: a repetition penalty over a window of earlier codes (`generate_clips`).  With `continuity=True` they raise ValueError: a host that wants
+        controls on a streaming session opens one itself (`open_stream(..., sampling=, style=, code_bias=, repeat=)`, `BodyStream.push`).
         '''
         assert self.args.infer, "train mode"
         code_bias = kwargs.get('code_bias', None)
@@ -735,13 +735,14 @@ class TrainWrapper(TrainWrapperBaseClass):
         output = pred_poses
         return output
 
-    def open_stream(self, id, B, max_frames):
+    def open_stream(self, id, B, max_frames, *, sampling=None, style=None, code_bias=None, repeat=None):
         """Long-audio / continuity generation: a session that is fed MFCC chunks and returns the poses of
         each chunk, every chunk continuing the PixelCNN row cache of the ones before it (`ts_pixelcnn_stream_*`) — the
         reference's `infer(..., pre_latents, pre_audio)` chain (`:291-304`) for any number of chunks, at a cost per chunk
         that does not grow with the history.  As in the reference, each chunk goes through the audio encoder and the VQ
-        decoders on its own (their receptive fields are not carried across chunks)."""
-        return BodyStream(self, id, B, max_frames)
+        decoders on its own (their receptive fields are not carried across chunks).  sampling / style / code_bias / repeat: session
+        defaults for the keywords of `BodyStream.push` (`GatedPixelCNN.open_stream`)."""
+        return BodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
 
     def infer(self, aud_feat, frame, id, B, pre_latents=None, pre_audio=None, pre_pose=None, mode=None, seed=None):
         """smplx_body_pixel.py:291-304 (continuity helper, reference call shape): returns latents, audio (B,256,H,2),
@@ -769,21 +770,28 @@ class TrainWrapper(TrainWrapperBaseClass):
 class BodyStream:
     """See `TrainWrapper.open_stream`.  `push(mfcc_chunk (B,T,64)) -> poses (B, 4*(T//4), 129)` device tensor."""
 
-    def __init__(self, wrapper, id, B, max_frames):
+    def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None):
         self.w, self.B = wrapper, int(B)
         if id is None:
             id = torch.tensor([0])
-        self.pix = wrapper.generator.open_stream(id, self.B, max(1, int(max_frames) // 4))
+        self.pix = wrapper.generator.open_stream(id, self.B, max(1, int(max_frames) // 4), sampling=sampling, style=style,
+                                                 code_bias=code_bias, repeat=repeat)
         self.seed = _fresh_seed()          # one stream of random numbers per session unless push() is given a seed
 
     @property
     def frames(self):
         return 4 * self.pix.rows
 
-    def push(self, mfcc, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, uniforms=None):
+    def push(self, mfcc, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, uniforms=None, *, sampling=None, logprobs=False, given=None,
+             style=None, code_bias=None, repeat=None):
+        """The keywords are `PixelCNNStream.step`'s, for this chunk's code rows; with `logprobs` the return value is (poses, logprobs
+        (B, T//4, 2))."""
         rows = self.w.audioencoder.forward_nlc(mfcc)                      # (B, T//4, 256), this chunk alone
-        codes = self.pix.step(rows, mode=mode, uniforms=uniforms, seed=self.seed if seed is None else seed, clip_index0=clip_index0)
-        return self.w._decode_pair(codes)
+        out = self.pix.step(rows, mode=mode, uniforms=uniforms, seed=self.seed if seed is None else seed, clip_index0=clip_index0,
+                            sampling=sampling, logprobs=logprobs, given=given, style=style, code_bias=code_bias, repeat=repeat)
+        if isinstance(out, tuple):
+            return self.w._decode_pair(out[0]), out[1]
+        return self.w._decode_pair(out)
 
     def close(self):
         self.pix.close()

@@ -139,6 +139,11 @@ SIGNATURES = {
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
     "ts_pixelcnn_stream_open": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_stream_step": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _vp]),
+    # the step plus ctl / n_ctl, logprob, given / given_rows, style, bias / n_bias / bias_index, rep / n_rep ahead of the stream
+    "ts_pixelcnn_stream_step_ctl": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                         C.POINTER(C.c_int32), _rp, _i, _vp]),
+    "ts_pixelcnn_stream_captures": (_i64, [_vp]),
+    "ts_debug_rep_table": (_i, [_rp, _i, _i, _i, C.POINTER(C.c_int32)]),
     "ts_pixelcnn_stream_rows": (_i64, [_vp]),
     "ts_pixelcnn_stream_close": (None, [_vp]),
     "ts_face_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, C.POINTER(_vp)]),

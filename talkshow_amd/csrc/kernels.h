@@ -523,11 +523,14 @@ struct SampleCtl {
     float inv_t, top_p;
     int32_t top_k, pad;
 };
-// The device record of a clip's repetition penalty: ts_repeat's four words (window in [0, SAMPLE_REP_RING], 0 = off)
+// The device record of a clip's repetition penalty: ts_repeat's first three words (window in [0, SAMPLE_REP_RING], 0 = off) and from_row, the
+// first absolute row of the clip's current unbroken run of rows written under window > 0: a launch at row r counts min(r - from_row, window)
+// ring entries.  0 for every one-shot pass (rep_table): its history starts at row 0.  A streaming session sets it to the row at which a
+// clip's penalty was switched on, so that ring entries of rows from before that row are never read
 struct SampleRep {
     int32_t window;
     float presence, frequency;
-    int32_t pad;
+    int32_t from_row;
 };
 constexpr int SAMPLE_REP_RING = 64;
 struct SampleCtlParams {

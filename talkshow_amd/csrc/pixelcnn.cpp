@@ -106,7 +106,7 @@ struct ts_pixelcnn {
         DevBuf ctl_tab;                    // passes with sampling controls: one SampleCtl per clip SLOT of the pass, written in stream order ahead of it
         DevBuf lp_int;                     // runs with a log-probability output: what the captured samplers write, (B,rows,2) fp32 beside codes_int
         DevBuf given_tab, given_int;       // passes with given rows: G of every clip SLOT (int32, written in stream order ahead of the pass); the given codes of
-                                           // ONE chunk, (B,rows,2) int64 beside codes_int (what the captured samplers read)
+                                           // ONE chunk, (B,rows,2) int64 beside codes_int (what the captured samplers read); a session's holds max_chunk_rows rows
         DevBuf keep_int;                   // passes with a mask of kept positions: the mask bytes of ONE chunk, (B,rows,2) uint8 beside given_int
         DevBuf style_int;                  // passes with per-row speaker style: the class-conditioning rows of ONE chunk, [NL][CHUNK_ROWS][Bs][2D] fp32 (slabs Bs
                                            // clips apart, like CR); allocated by the first such pass, filled ahead of every chunk by style_rows_kernel
@@ -119,7 +119,7 @@ struct ts_pixelcnn {
                                            // reads min(r, W) entries, all written earlier in the same pass by the same slot
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
-        // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step;
+        // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step (in a session's own Work);
         // (Br, Hc, -(1 + phase), mode, Bs) = Hc rows of a MIXED pass of Bs clips for its first Br clips: the per-clip slabs of the work
         // buffers are Bs clips apart whatever Br is, so the stride is part of what a captured graph is valid for (0: the slabs are B apart).
         // The sixth field is a bit set: bit 0 for a run whose samplers read ctl_tab (sample_ctl_kernel), bit 1 for a run whose samplers write
@@ -231,6 +231,9 @@ struct ts_pixelcnn_stream {
     int max_rows = 0;           // largest chunk a step may bring (buffers are sized once, at open)
     ts_pixelcnn::Work w;
     DevBuf label;
+    // "repetition penalty" on a session: per clip, the first row of its current unbroken run of rows written under window > 0 (what
+    // SampleRep::from_row carries to the samplers), -1 while the clip has no such run
+    std::vector<int32_t> rep_from;
 };
 
 namespace {
@@ -2235,6 +2238,9 @@ int ts_pixelcnn_stream_open(ts_pixelcnn *p, const int64_t *label, int B, int max
     st->max_rows = max_chunk_rows;
     // everything is allocated here, once: growing a buffer later would drop the row cache it holds
     TS_TRY(ensure_work(p, &st->w, B, std::max(max_chunk_rows, 4)));
+    // a step's given block is staged whole ((B,Hc,2) with Hc up to max_chunk_rows), where a one-shot pass stages CHUNK_ROWS rows at a time
+    TS_TRY(st->w.given_int.ensure((size_t)B * std::max(max_chunk_rows, CHUNK_ROWS) * 2 * sizeof(int64_t)));
+    st->rep_from.assign(B, -1);
     TS_TRY(st->label.ensure((size_t)B * sizeof(int64_t)));
     TS_HIP(hipMemcpy(st->label.p, label, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice));
     *out = st.release();
@@ -2245,8 +2251,14 @@ void ts_pixelcnn_stream_close(ts_pixelcnn_stream *st) { delete st; }
 
 int64_t ts_pixelcnn_stream_rows(const ts_pixelcnn_stream *st) { return st ? st->rows : -1; }
 
-int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed,
-                            int64_t clip0, int64_t *codes, void *stream) {
+}  // extern "C"
+
+namespace {
+// The body of both step entries: `o` holds what ts_pixelcnn_stream_step_ctl brought (the fields of a mixed pass that a session takes: no
+// mask of kept positions, no style track, no poses), so an absent piece is null here and costs no launch, no buffer and no bit of the
+// graph key.  Everything is checked before anything is launched and before st->rows moves.
+int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
+                int64_t *codes, const MixedOpts &o, hipStream_t s) {
     if (!st || !aud || !codes) return fail("ts_pixelcnn_stream_step: null argument");
     if (Hc < 1) return fail("ts_pixelcnn_stream_step: empty chunk");
     if (Hc > st->max_rows) return fail("ts_pixelcnn_stream_step: chunk longer than max_chunk_rows given to ts_pixelcnn_stream_open");
@@ -2256,21 +2268,110 @@ int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, in
     if (st->rows + Hc > (1l << 30)) return fail("ts_pixelcnn_stream_step: row counter overflow");
     ts_pixelcnn *p = st->p;
     ts_ctx *ctx = p->ctx;
-    hipStream_t s = (hipStream_t)stream;
     ts_pixelcnn::Work *w = &st->w;
     const int B = st->B, r0 = (int)st->rows;
+    const char *who = "ts_pixelcnn_stream_step_ctl";
+    std::vector<SampleCtl> tab;
+    if (o.ctl_host) TS_TRY(ctl_table(o.ctl_host, o.n_ctl, B, p->V, mode, who, tab));
+    if (o.bias || o.rep_host) {   // the rules of the mixed entry: the table's scope, neutral records where the step brought none
+        if (!o.ctl_host) {
+            const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
+            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, who, tab));
+        }
+        if (o.bias) TS_TRY(ts_code_bias_index_check(o.bias_index_host, B, o.n_bias));
+    }
+    std::vector<SampleRep> rtab;
+    std::vector<int32_t> rep_from(B, -1);   // the session's table behind this step, kept only if the step is queued
+    if (o.rep_host) {
+        TS_TRY(rep_table(o.rep_host, o.n_rep, B, p->V, who, rtab));
+        for (int b = 0; b < B; ++b)
+            if (rtab[b].window > 0) rtab[b].from_row = rep_from[b] = st->rep_from[b] >= 0 ? st->rep_from[b] : r0;
+    }
+    std::vector<int32_t> gtab;
+    if (o.given) {   // the table the samplers read holds absolute bounds: clip b is forced at positions below 2 (r0 + g_b)
+        if (!o.given_rows_host) return fail(std::string(who) + ": given codes need their row table");
+        const std::vector<int32_t> lens(B, 4 * Hc);
+        TS_TRY(ts_given_rows_check(o.given_rows_host, lens.data(), B));
+        gtab.resize(B);
+        for (int b = 0; b < B; ++b) gtab[b] = r0 + o.given_rows_host[b];
+    }
     constexpr int RING = 4;   // token rows kept: layer 0 looks three code rows up; 4 also is the period of the Q ring
-    if (r0 == 0) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
-    TS_TRY(audio_terms(p, w, aud, B, Hc, s));
+    if (r0 == 0 && !o.style) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
+    if (o.style) TS_TRY(class_rows_style(p, w, o.style, B, s));   // CR stays as written until a later step brings other rows
     RunCfg c{B, Hc, 0, r0 + Hc, mode, nullptr, seed, clip0, nullptr, nullptr, nullptr, w,
              RING, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
     c.audio_from(w);
+    if (o.ctl_host || o.bias || o.rep_host) {
+        TS_TRY(put_ctl_table(ctx, w, tab, s));
+        c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
+    }
+    if (o.bias) {   // sized by the session's fixed clip capacity at the first biased step: it never moves, and no graph read it before
+        TS_TRY(w->bias_tab.ensure((size_t)w->capB * 2 * p->V * sizeof(float)));
+        MiscScope ms(ctx, s);
+        TS_HIP(hipMemcpyAsync(w->bias_tab.p, o.bias, (size_t)o.n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
+        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), o.bias_index_host, B, s));
+        c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+    }
+    if (o.rep_host) {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
+        if (!o.bias) {
+            const std::vector<int32_t> none(B, -1);
+            TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), none.data(), B, s));
+        }
+        c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
+        c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
+        c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+    }
+    if (o.given) {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w->given_tab.i(), gtab.data(), B, s));
+        c.given_rows = w->given_tab.i();
+        c.given_src = o.given;
+        c.given_stage = true;
+    }
+    TS_TRY(audio_terms(p, w, aud, B, Hc, s));
     // a captured chunk is valid for every start row with the same buffer phases (parity of the per-layer row cache, slot
     // in the 4-row rings) and the same set of existing rows above (rows 0..2 have fewer): key on that, not on r0
     const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0, 0), uniforms, codes, nullptr, s));
+    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0, sampler_bits(c, o.logprob)), uniforms, codes,
+                    o.logprob, s));
+    st->rep_from.swap(rep_from);
     st->rows += Hc;
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int ts_pixelcnn_stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed,
+                            int64_t clip0, int64_t *codes, void *stream) {
+    return stream_step(st, aud, Hc, mode, uniforms, seed, clip0, codes, MixedOpts(), (hipStream_t)stream);
+}
+
+// ts_pixelcnn_stream_step under the per-clip sampling pieces of a mixed pass (talkshow_hip.h, "streaming sessions"); every optional
+// argument NULL / 0: that entry, launch for launch and on its graph keys
+int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed,
+                                int64_t clip0, int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob,
+                                const int64_t *given, const int32_t *given_rows_host, const float *style, const float *bias_dev,
+                                int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host;
+    o.style = style, o.style_rows = 1, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    return stream_step(st, aud, Hc, mode, uniforms, seed, clip0, codes, o, (hipStream_t)stream);
+}
+
+int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st) { return st ? st->w.captures : -1; }
+
+// Host only (tests): the device records rep_table makes of n_rep (1 or B) public records, four 32-bit words per clip slot into words_out
+int ts_debug_rep_table(const ts_repeat *rep_host, int n_rep, int B, int V, int32_t *words_out) {
+    if (!rep_host || !words_out || B < 1) return fail("ts_debug_rep_table: bad argument");
+    std::vector<SampleRep> tab;
+    TS_TRY(rep_table(rep_host, n_rep, B, V, "ts_debug_rep_table", tab));
+    std::memcpy(words_out, tab.data(), (size_t)B * sizeof(SampleRep));
     return 0;
 }
 

@@ -1317,8 +1317,8 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     if constexpr (BIAS && FAST) {
         if (bias) sample_load8(bias, v0, xb);   // beside the logits: both pairs of loads are in flight ahead of the row copy
     }
-    // REP: the clip's record (workgroup-uniform: one uniform load), its ring of this column, the launch's row r and the min(r, W) entries
-    // to count.  The window is clamped to the ring: s_rep holds SAMPLE_REP_RING entries whatever a record says
+    // REP: the clip's record (workgroup-uniform: one uniform load), its ring of this column, the launch's row r and the min(r - from_row, W)
+    // entries to count (from_row: 0 in a one-shot pass; a session's row at which the clip's penalty was switched on, never above r).  The window is clamped to the ring: s_rep holds SAMPLE_REP_RING entries whatever a record says
     [[maybe_unused]] int rep_n = 0, rep_slot = 0;
     [[maybe_unused]] float rep_pres = 0.f, rep_freq = 0.f;
     [[maybe_unused]] int32_t *ring = nullptr;
@@ -1332,7 +1332,7 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
             rep_pres = rr.presence;
             rep_freq = rr.frequency;
             if (!(GIVEN && !LP && forced)) {   // rows r - 1, r - 2, ...: wave 0 alone (rep_n <= 64), ahead of the first barrier
-                rep_n = (int)min(r, (uint32_t)min(rr.window, SAMPLE_REP_RING));
+                rep_n = (int)min(r - (uint32_t)rr.from_row, (uint32_t)min(rr.window, SAMPLE_REP_RING));
                 if (tid < rep_n) s_rep[tid] = ring[(r - 1u - (uint32_t)tid) & (uint32_t)(SAMPLE_REP_RING - 1)];
             }
         }

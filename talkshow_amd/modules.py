@@ -532,12 +532,14 @@ class GatedPixelCNN(NativeModule):
         """hipGraphs captured so far on the current stream (a serving loop checks that this stands still once it is warm)."""
         return int(_lib.load().ts_pixelcnn_graph_captures(self.handle(), _lib.stream_ptr())) if self.bh_model else 0
 
-    def open_stream(self, label, batch_size, max_chunk_rows):
+    def open_stream(self, label, batch_size, max_chunk_rows, *, sampling=None, style=None, code_bias=None, repeat=None):
         """A generation session with a persistent row cache (`ts_pixelcnn_stream_*`): `.step(aud_rows)` continues the
-        clip(s) where the previous step stopped, at a cost independent of the history length."""
+        clip(s) where the previous step stopped, at a cost independent of the history length.  sampling / style / code_bias / repeat:
+        session DEFAULTS in the forms `PixelCNNStream.step` takes; a step that passes no value for a keyword runs under the default, any
+        value it does pass takes its place for that step."""
         if not (self.audio and self.bh_model):
             raise NotImplementedError("streaming sessions exist for the shipped configuration (audio=True, bh_model=True)")
-        return PixelCNNStream(self, label, batch_size, max_chunk_rows)
+        return PixelCNNStream(self, label, batch_size, max_chunk_rows, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
 
     @staticmethod
     def _audio_rows(aud):
@@ -587,7 +589,7 @@ class GatedPixelCNN(NativeModule):
 class PixelCNNStream:
     """Host handle of `ts_pixelcnn_stream`: label (B,) or (1,) int64 fixed for the session."""
 
-    def __init__(self, net, label, batch_size, max_chunk_rows):
+    def __init__(self, net, label, batch_size, max_chunk_rows, sampling=None, style=None, code_bias=None, repeat=None):
         dev = net._dev()
         label = _index_tensor(label, net.n_classes, "class label", dev)
         if label.numel() == 1 and batch_size > 1:
@@ -595,6 +597,8 @@ class PixelCNNStream:
         if label.numel() != batch_size:
             raise ValueError(f"label must hold 1 or B={batch_size} class indices, got {label.numel()}")
         self.net, self.B, self.max_rows = net, int(batch_size), int(max_chunk_rows)
+        self.defaults = {"sampling": sampling, "style": style, "code_bias": code_bias, "repeat": repeat}
+        self._labels = label.detach().cpu().numpy()      # what `style=[None, ...]` stands for: the clip's own label
         h = C.c_void_p()
         with torch.cuda.device(dev):
             _lib.check(_lib.load().ts_pixelcnn_stream_open(net.handle(), _lib.dptr(label), self.B, self.max_rows, C.byref(h)))
@@ -604,22 +608,78 @@ class PixelCNNStream:
     def rows(self):
         return int(_lib.load().ts_pixelcnn_stream_rows(self._h))
 
-    def step(self, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=0, clip_index0=0):
-        """aud_rows (B,Hc,aud_dim) device -> codes (B,Hc,2) int64 of the next Hc code rows."""
-        dev = self.net._dev()
-        aud_rows = _dev_f32(aud_rows, dev)
-        B, Hc, _ = aud_rows.shape
+    def graph_captures(self):
+        """hipGraphs this session has captured so far (`ts_pixelcnn_stream_captures`): stands still once every (Hc, buffer phase, kind of
+        sampler) the host steps with has been met — the records, tables, given codes and style of a step are in no graph key."""
+        return int(_lib.load().ts_pixelcnn_stream_captures(self._h))
+
+    def _style_rows(self, style):
+        """`style=` of a step -> (B, n_classes) float32 numpy, one weight row per clip: the forms of `_lib.style_block` without tracks."""
+        if isinstance(style, (list, tuple)):
+            for i, e in enumerate(style):
+                if e is not None and np.ndim(e.detach().cpu().numpy() if hasattr(e, "detach") else e) >= 2:
+                    raise ValueError(f"step: style of clip {i} is a track of rows; a session takes ONE weight row per clip for a step "
+                                     f"(it holds until a later step brings another)")
+        return np.ascontiguousarray(_lib.style_block(style, [1] * self.B, self.net.n_classes, who="step", ids=self._labels)[:, 0])
+
+    def _pieces(self, Hc, mode, dev, sampling, logprobs, given, style, code_bias, repeat):
+        """The keywords of one step of Hc rows as the host-side pieces of the C call: the session's defaults stand in for a keyword left
+        at None, then every value is validated (ValueError naming the clip).  Pure host code: nothing is launched or uploaded."""
+        d = self.defaults
+        sampling = d["sampling"] if sampling is None else sampling
+        style = d["style"] if style is None else style
+        code_bias = d["code_bias"] if code_bias is None else code_bias
+        repeat = d["repeat"] if repeat is None else repeat
+        B, V = self.B, self.net.input_dim
+        lp = _lib.logprob_request(logprobs, (B, Hc, 2), dev)
+        ctl, n_ctl = (None, 0) if sampling is None else _lib.sampling_table(sampling, B, V, mode)
+        btab, bidx = _lib.code_bias_block(code_bias, B, V, who="step", mode=mode)
+        rtab, n_rep = _lib.repeat_table(repeat, B, V, who="step", mode=mode)
+        block = table = None
+        if given is not None:
+            block, table = _lib.given_block(given, [Hc] * B, V, who="step")
+        srows = None if style is None else self._style_rows(style)
+        return lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows
+
+    def step(self, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=0, clip_index0=0, *, sampling=None, logprobs=False, given=None,
+             style=None, code_bias=None, repeat=None):
+        """aud_rows (B,Hc,aud_dim) device -> codes (B,Hc,2) int64 of the next Hc code rows.
+        The keywords take the forms `GatedPixelCNN.run` takes and follow its rules FOR THIS STEP (`ts_pixelcnn_stream_step_ctl`;
+        talkshow_hip.h, "streaming sessions"); sampling / style / code_bias / repeat left at None run under the session's default
+        (`open_stream`).  sampling: one record or one per clip.  logprobs: True or a float32 (B,Hc,2) tensor -> returns (codes, logprobs).
+        given: a list with None or a (g_b,2) array per clip, or one (B,g,2) block: clip b's first g_b rows OF THIS STEP are taken from it.
+        style: one weight row per clip (no tracks); the rows stay in force until a later step brings others.  code_bias: tables for this
+        step.  repeat: records over the session's own history, which persists across steps; a clip whose penalty is switched on (after no
+        record, or window 0) starts from an empty history at this step's first row.  A bad value raises ValueError naming the clip before
+        any device work; the session's row counter does not move.  With every keyword at its default and no session default the call is
+        `ts_pixelcnn_stream_step`, exactly."""
+        B, Hc = int(aud_rows.shape[0]), int(aud_rows.shape[1])
         if B != self.B:
             raise ValueError(f"session was opened for B={self.B}, got {B}")
+        dev = self.net._dev()
+        lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows = self._pieces(Hc, mode, dev, sampling, logprobs, given, style, code_bias,
+                                                                                   repeat)
+        if uniforms is not None and tuple(uniforms.shape) != (B, Hc, 2):   # the library strides them by the chunk's Hc * 2: a wrong shape would misalign clips b > 0
+            raise ValueError(f"step(): uniforms must have shape (B={B}, Hc={Hc}, 2), got {tuple(uniforms.shape)}")
+        aud_rows = _dev_f32(aud_rows, dev)
         codes = torch.empty((B, Hc, 2), dtype=torch.int64, device=dev)
         if uniforms is not None:
             uniforms = _dev_f32(uniforms, dev)
-            if tuple(uniforms.shape) != (B, Hc, 2):       # the library strides them by the chunk's Hc * 2: a wrong shape would misalign clips b > 0
-                raise ValueError(f"step(): uniforms must have shape (B={B}, Hc={Hc}, 2), got {tuple(uniforms.shape)}")
-        _lib.check(_lib.load().ts_pixelcnn_stream_step(self._h, _lib.dptr(aud_rows), Hc, mode, _lib.dptr(uniforms),
-                                                       int(seed) & (2 ** 64 - 1), int(clip_index0), _lib.dptr(codes),
-                                                       _lib.stream_ptr()))
-        return codes
+        args = (self._h, _lib.dptr(aud_rows), Hc, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), int(clip_index0), _lib.dptr(codes))
+        if lp is None and ctl is None and btab is None and rtab is None and block is None and srows is None:
+            _lib.check(_lib.load().ts_pixelcnn_stream_step(*args, _lib.stream_ptr()))
+            return codes
+        if isinstance(lp, str):
+            lp = torch.empty((B, Hc, 2), dtype=torch.float32, device=dev)
+        i32p = C.POINTER(C.c_int32)
+        block_dev = upload(block, dev) if block is not None else None
+        style_dev = upload(srows, dev) if srows is not None else None
+        bias_dev = upload(btab, dev) if btab is not None else None
+        _lib.check(_lib.load().ts_pixelcnn_stream_step_ctl(
+            *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(block_dev), table.ctypes.data_as(i32p) if block is not None else None,
+            _lib.dptr(style_dev), _lib.dptr(bias_dev), int(btab.shape[0]) if btab is not None else 0,
+            bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep, _lib.stream_ptr()))
+        return codes if lp is None else (codes, lp)
 
     def close(self):
         if self._h is not None:
