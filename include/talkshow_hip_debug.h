@@ -339,6 +339,27 @@ int ts_debug_vq_argmin_pair_masked(ts_ctx *ctx, const float *z_body_dev, const f
                                    const float *codebook_body_dev, const float *codebook_hand_dev, int ncode_body, int ncode_hand,
                                    int dim_body, int dim_hand, int64_t *codes_dev, int form, int iters, void *stream);
 
+/* ---- the Winograd F(4,3) lowering of wide stride-1 k = 3 C -> C layers (csrc/conv_wino.hip; knob TS_CONV_WINO) ----
+ * Host-only (no GPU): is a conv layer of this geometry (padding k / 2) lowered under knob_list ("TS_CONV_WINO=1", null = the defaults), and
+ * into what?  Returns 1 / 0 (lowered / direct), -1 on a bad argument; lowered: out5 = {GEMMs per network (6), their rows M = B ceil(L / 4),
+ * columns N, depth K, rows of a tile (4)}.  The answer never depends on B or L (they only size M).  No reference counterpart. */
+int ts_debug_wino_lowering(int cin, int cout, int k, int stride, const char *knob_list, int B, int L, int *out5);
+/* Host-only: the six transformed matrices U_i = sum_k G[i][k] g_k of taps w (cout, cin, 3) (the reference's weight layout, BatchNorm
+ * already folded), computed in double and rounded once to fp32, as the library packs them: out (6, round_up(cout, 128), cin), rows at or
+ * beyond cout zero. */
+int ts_debug_wino_weights(const float *w, int cout, int cin, float *out);
+/* Test aid: ONE launch of a transform kernel on device buffers the caller owns.  which 0 wino_in: x (B, L, C) -> V (6, B J, C), J = ceil(L / 4);
+ * 1 wino_out: O (6, B J, C), bias (C,), res (B, L, C) or null -> y (B, L, C) = act(At O + bias (+ res)), every row written; 2 wino_out_in: O,
+ * bias -> V of the next layer, = 1 then 0 without storing y.  ptrs: 12 device pointers {x, V, O, bias, res, y} of network 0 then of network 1
+ * (nnet = 1: the second six are not read).  lens_dev (B,) int32 or null: clip b has min(L, (lens[b] >> shr) << shl) rows; rows beyond read as
+ * zeros and are stored as zeros.  act: 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 GELU.  Does not synchronize. */
+int ts_debug_wino_transform(ts_ctx *ctx, int which, int nnet, int B, int L, int C, int act, const int32_t *lens_dev, int shr, int shl,
+                            const void *const *ptrs, void *stream);
+/* Test aid: the six GEMMs per network of a lowered layer, O_i = V_i U_i^T, as the library launches them (one batched conv_gemm_f32 launch).
+ * V / O (6, M, C), U (6, round_up(C, 128), C) of ts_debug_wino_weights, device pointers; the *1 of nnet = 1 are not read.  Does not synchronize. */
+int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, const float *U0, const float *U1, float *O0, float *O1, int M,
+                       int C, void *stream);
+
 /* Tuning entry (not part of the drop-in surface): `iters` DEPENDENT skinny_gemm launches replayed from one hipGraph;
  * *us_out = microseconds per launch.  gate != 0: N = 2K with the tanh*sigmoid epilogue; debug: unused. */
 int ts_debug_skinny_chain(ts_ctx *ctx, int M, int K, int gate, int iters, int debug, float *us_out);

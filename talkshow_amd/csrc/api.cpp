@@ -33,6 +33,7 @@ static Knobs read_knobs(Get get) {
     v.conv_taps48 = num("TS_CONV_TAPS48", 1) != 0;
     v.face_pack = num("TS_FACE_PACK", 0) != 0;
     v.conv_sk = num("TS_CONV_SK", 1);
+    v.conv_wino = num("TS_CONV_WINO", -1);
     v.w2v_moments = num("TS_W2V_MOMENTS", 1) != 0;
     v.vq_lds = num("TS_VQ_LDS", 1) != 0;
     v.vq_pair = num("TS_VQ_PAIR", 1) != 0;
@@ -1288,6 +1289,49 @@ int ts_op_sample_philox(ts_ctx *ctx, const float *logits, int B, int V, uint64_t
     TS_HIP(launch_sample(sp, s));
     TS_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+// ---- Winograd lowering: host answers and single launches for tests/test_wino_host.py, tests/test_gpu_wino.py ----
+int ts_debug_wino_lowering(int cin, int cout, int k, int stride, const char *knob_list, int B, int L, int *out5) {
+    if (cin < 1 || cout < 1 || k < 1 || stride < 1 || B < 1 || L < 1 || !out5) return -1;
+    const ts::Knobs kn = ts::knobs_from_list(knob_list);
+    if (stride != 1 || !ts::wino_lowered(0, k, cin, cout, kn.conv_wino)) return 0;
+    const int o[5] = {6, B * ((L + 3) / 4), cout, cin, 4};
+    std::memcpy(out5, o, sizeof(o));
+    return 1;
+}
+
+int ts_debug_wino_weights(const float *w, int cout, int cin, float *out) {
+    if (!w || !out || cout < 1 || cin < 1) return fail("ts_debug_wino_weights: bad argument");
+    ts::wino_transform_weights(w, cout, cin, round_up(cout, 128), out);
+    return 0;
+}
+
+int ts_debug_wino_transform(ts_ctx *ctx, int which, int nnet, int B, int L, int C, int act, const int32_t *lens_dev, int shr, int shl,
+                            const void *const *ptrs, void *stream) {
+    if (!ctx || !ptrs || nnet < 1 || nnet > 2) return fail("ts_debug_wino_transform: bad argument");
+    ts::WinoParams w;
+    std::memset(&w, 0, sizeof(w));
+    w.nnet = nnet;
+    w.B = B, w.L = L, w.J = (L + 3) / 4, w.C = C, w.act = act;
+    w.lens = lens_dev, w.len_shr = shr, w.len_shl = shl;
+    for (int i = 0; i < nnet; ++i) {
+        const void *const *q = ptrs + 6 * i;
+        w.x[i] = (const float *)q[0], w.V[i] = (float *)q[1], w.O[i] = (const float *)q[2], w.bias[i] = (const float *)q[3];
+        w.res[i] = (const float *)q[4], w.y[i] = (float *)q[5];
+    }
+    MiscScope ms(ctx, (hipStream_t)stream);
+    TS_HIP(ts::launch_wino(which, w, (hipStream_t)stream));
+    return 0;
+}
+
+int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, const float *U0, const float *U1, float *O0, float *O1, int M,
+                       int C, void *stream) {
+    if (!ctx || nnet < 1 || nnet > 2 || !V0 || !U0 || !O0 || (nnet == 2 && (!V1 || !U1 || !O1)) || M < 1 || C < 32 || C % 32)
+        return fail("ts_debug_wino_gemm: bad argument");
+    const float *V[2] = {V0, V1}, *U[2] = {U0, U1};
+    float *O[2] = {O0, O1};
+    return ts::run_wino_gemm(ctx, nnet, V, U, O, M, C, round_up(C, 128), (hipStream_t)stream);
 }
 
 }  // extern "C"

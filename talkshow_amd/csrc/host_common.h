@@ -209,6 +209,7 @@ struct ConvLayer {
     ConvSeg segs[2][4];
     DevBuf w, bias;   // [ngroups][npad][ktot], [ngroups][npad]
     DevBuf wp;        // face generator, x3 plan only: w as bf16 plane images (launch_split_weight_planes)
+    DevBuf wino;      // lowered layers only (kernels.h::wino_lowered): the six Winograd matrices [6][npad][cin]; w stays packed for TS_CONV_WINO=0
     std::string name;
 };
 
@@ -226,6 +227,9 @@ int pack_conv_raw(const float *w, const float *bias, int cout, int cin, int K, c
 // For kind 2 the output buffer has 2*Lin rows of cout_pad (or ldo) floats.
 int conv_layer_params(const ConvLayer &layer, const float *x, int ldx, int B, int Lin, const float *res, int ldr,
                       float *out, int ldo, int out_col0, int n_store, ConvParams *p);
+
+// models.cpp: the six GEMMs per network of a Winograd-lowered layer (V, U, O of n = 1 or 2 networks; U rows npad apart) as one batched launch
+int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const *U, float *const *O, int M, int c, int npad, hipStream_t s);
 
 // accessors so that api.cpp needs no knowledge of the model structs
 int convnet_hidden(const ts_convnet *n);

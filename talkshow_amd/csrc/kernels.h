@@ -163,6 +163,35 @@ hipError_t launch_split_weight_planes(const float *w, float *planes, long rows, 
 double conv_gemm_flops(const ConvParams &p);
 
 // ------------------------------------------------------------------------------------------------
+// Winograd F(4,3) lowering of the wide stride-1 k = 3 C -> C layers (conv_wino.hip has the matrices, the tiling and the summation orders;
+// models.cpp::run_stack_n the sequence).  A lowering like the two output phases of a ConvTranspose: decided above plan_conv by the layer's
+// own geometry, never by B, T, the pass form or the stream, so a clip's bits do not depend on the batch it rides in.
+// ------------------------------------------------------------------------------------------------
+constexpr int WINO_MIN_C = 512;   // TS_CONV_WINO=-1: layers at least this wide are lowered (the audio encoder's widest stack, 256, stays direct)
+// knob: Knobs::conv_wino (-1 by width, 0 never, 1 every eligible geometry)
+inline bool wino_lowered(int kind, int k, int cin, int cout, int knob) {
+    const bool geom = kind == 0 && k == 3 && cin == cout && cin % 32 == 0;
+    return geom && knob != 0 && (knob == 1 || cout >= WINO_MIN_C);
+}
+struct WinoParams {
+    int nnet;              // 1 or 2 networks (grid y): body + hands in one launch
+    int B, L, J, C;        // clips, rows per clip, tiles per clip = ceil(L / 4), channels (% 4 == 0; rows are C floats apart, 16-byte aligned)
+    int act;               // ConvParams::act codes
+    const int *lens;       // mixed passes: L_b = min(L, (lens[b] >> len_shr) << len_shl); null: L_b = L
+    int len_shr, len_shl;
+    const float *x[2];     // wino_in: (B, L, C)
+    float *V[2];           // wino_in, wino_out_in: (6, B J, C)
+    const float *O[2];     // wino_out, wino_out_in: (6, B J, C)
+    const float *bias[2];  // [C]
+    const float *res[2];   // wino_out, optional: (B, L, C), added before the activation
+    float *y[2];           // wino_out: (B, L, C); every row is written, rows in [L_b, L) as zeros
+};
+// which: 0 wino_in (x -> V), 1 wino_out (O -> y), 2 wino_out_in (O of layer k -> V of layer k + 1)
+hipError_t launch_wino(int which, const WinoParams &p, hipStream_t stream);
+// host: the six transformed matrices of folded taps w (cout, cin, 3), computed in double and rounded once; out (6, npad, cin)
+void wino_transform_weights(const float *w, int cout, int cin, int npad, float *out);
+
+// ------------------------------------------------------------------------------------------------
 // skinny_gemm_f32: out[M x N] = A[M x K] * W[N x K]^T with M = a few tens of rows (the batch of clips at one
 // code position).  The A operand is a concatenation of up to 6 segments, each either a dense row-major
 // block or rows gathered from a table through an int32 index (token -> embedding row).  Each workgroup owns
@@ -397,6 +426,7 @@ struct Knobs {
     int skinny_trace = 0;       // TS_SKINNY_TRACE=1: in-kernel clock stamps (tools/skinny_trace.py, tools/wide_trace.py)
     bool wide_pair = true;      // TS_SKINNY_WIDE_PAIR=0: the wide kernel's tiles enumerated column-major instead of (clip-block pair, column tile, block of the pair) (A/B, tests)
     int wide_ablate = 0;        // TS_SKINNY_WIDE_ABLATE=2|4 (trace builds): no loads / no MFMAs in the wide kernel
+    int conv_wino = -1;         // TS_CONV_WINO: the Winograd F(4,3) lowering of stride-1 k = 3 C -> C layers: -1 from WINO_MIN_C channels on, 0 never (direct everywhere), 1 every eligible geometry (tests).  Read when a network is created
 };
 const Knobs &knobs();
 

@@ -6,8 +6,10 @@
 //   vqvae_1d.AudioEncoder / Encoder nets/spg/vqvae_1d.py:11-34,66-92
 //   vqvae_1d.Decoder                nets/spg/vqvae_1d.py:116-149
 //   VectorQuantizerEMA (eval)       nets/spg/vqvae_modules.py:274-286,311-323
+#include <algorithm>
 #include <cstdio>
 #include "host_common.h"
+#include "conv_tile.h"
 
 namespace ts {
 
@@ -234,6 +236,14 @@ int pack_conv_layer(const StateDict &sd, const std::string &conv_key, const std:
     }
     TS_TRY(L->w.upload(wp.data(), wp.size() * sizeof(float)));
     TS_TRY(L->bias.upload(bp.data(), bp.size() * sizeof(float)));
+    if (wino_lowered(kind, K, cin, cout, knobs().conv_wino)) {   // the folded taps in the reference's (cout, cin, 3) order -> six C x C matrices
+        std::vector<float> w3((size_t)cout * cin * 3), u((size_t)6 * L->npad * cin);
+        for (int o = 0; o < cout; ++o)
+            for (int i = 0; i < cin; ++i)
+                for (int kk = 0; kk < 3; ++kk) w3[((size_t)o * cin + i) * 3 + kk] = W(o, i, kk);
+        wino_transform_weights(w3.data(), cout, cin, L->npad, u.data());
+        TS_TRY(L->wino.upload(u.data(), u.size() * sizeof(float)));
+    }
     return 0;
 }
 
@@ -283,6 +293,40 @@ int pack_linear_layer(const float *w, long ldw, const float *bias, int N, int K,
     TS_TRY(L->w.upload(wp.data(), wp.size() * sizeof(float)));
     TS_TRY(L->bias.upload(bp.data(), bp.size() * sizeof(float)));
     return 0;
+}
+
+// One lowered layer's six GEMMs per network, V_i (M, C) x U_i^T -> O_i, as batched problems of ONE conv_gemm_f32 launch: blockIdx.z =
+// network * 6 + component (zdiv = 6; the second network's operands lie at constant distances from the first's).  Plain row-major A, one
+// segment, no bias, no activation, no length mask (wino_out / wino_out_in mask).  Layers that take 128 x 128 tiles go to the ring engine's
+// dealt grid (tile 35), which takes batched problems like any others; plan_conv itself keeps batched problems on conv_gemm.hip, where the
+// face generator's have always run.  Every plan here is a whole-tile plan: a row's bits do not depend on M.
+int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const *U, float *const *O, int M, int c, int npad, hipStream_t s) {
+    auto dist = [](const float *a, const float *b) { return (long)((reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b)) / (intptr_t)sizeof(float)); };
+    ConvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.M = p.Lout = p.Lin = M;
+    p.stride = 1;
+    p.ldx = p.ldo = c;
+    p.N = c;
+    p.Ktot = c;
+    p.ngroups = 6 * n;
+    p.zdiv = 6;
+    ConvGroup &g = p.g[0];
+    g.x = V[0];
+    g.w = U[0];
+    g.out = O[0];
+    g.nseg = 1;
+    g.seg[0] = ConvSeg{0, 0, c, 1};
+    p.x_zs1 = p.o_zs1 = (long)M * c;
+    p.w_zs1 = (long)npad * c;
+    if (n == 2) {
+        p.x_zs0 = dist(V[1], V[0]);
+        p.o_zs0 = dist(O[1], O[0]);
+        p.w_zs0 = dist(U[1], U[0]);
+    }
+    const ConvPlan pl = plan_conv(p, 0, knobs(), false);
+    const bool ring = pl.engine == ConvEngine::Reg && pl.bm == 128 && pl.bn == 128 && knobs().conv_ring > 0 && conv_gemm_ring_takes(p);
+    return run_conv(ctx, p, ring ? 35 : 0, s);
 }
 
 int conv_layer_params(const ConvLayer &L, const float *x, int ldx, int B, int Lin, const float *res, int ldr,
@@ -350,6 +394,13 @@ struct Pool {
         return slab.ensure(4 * each * sizeof(float));
     }
     float *buf(int i) const { return slab.f() + (size_t)i * each; }
+    // the Winograd lowering's two arenas (run_stack_wino): V and O, (6, B ceil(L / 4), C) each, grown where the slab grows
+    DevBuf wv, wo;
+    int ensure_wino(size_t floats) {
+        if (floats == 0) return 0;
+        TS_TRY(wv.ensure(floats * sizeof(float)));
+        return wo.ensure(floats * sizeof(float));
+    }
     int pick(int a, int b = -1, int c = -1) const {
         for (int i = 0; i < 4; ++i)
             if (i != a && i != b && i != c) return i;
@@ -438,9 +489,61 @@ int run_layer(ts_ctx *ctx, const ConvLayer &L, const float *x, int ldx, int B, i
     return run_layer_n(ctx, 1, Lp, xp, ldx, B, Lin, rp, ldr, op, ldo, &col0, &nstore, s, Lout, mk);
 }
 
+// floats of V (and of O) a stack of width c needs for B clips of L rows if it is lowered, else 0
+size_t stack_wino_floats(const Stack &st, int c, int B, int L) {
+    return st.tail.wino.p ? (size_t)6 * round_up(B * ((L + 3) / 4), 128) * c : 0;
+}
+
+// Res_CNR_Stack, every layer lowered (conv_wino.hip): wino_in on the stack's input (which stays in place for the tail's residual), then per
+// layer the GEMMs and wino_out_in into the next layer's V; the tail's GEMMs and wino_out with the residual and the ReLU.
+int run_stack_wino(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool, int cur, int c, int B, int L, hipStream_t s, int *out_idx,
+                   const LenMask *mk) {
+    WinoParams w;
+    std::memset(&w, 0, sizeof(w));
+    w.nnet = n;
+    w.B = B, w.L = L, w.J = (L + 3) / 4, w.C = c;
+    if (mk) w.lens = mk->lens, w.len_shr = mk->shr, w.len_shl = mk->shl;
+    const int o = pool[0]->pick(cur), M = B * w.J;
+    for (int i = 0; i < n; ++i) {
+        if (pool[i]->wv.bytes < (size_t)6 * M * c * sizeof(float) || pool[i]->wo.bytes < (size_t)6 * M * c * sizeof(float))
+            return fail("run_stack_wino: the Winograd arenas were not grown for this pass");
+        w.x[i] = pool[i]->buf(cur);
+        w.V[i] = pool[i]->wv.f();
+        w.O[i] = pool[i]->wo.f();
+        w.res[i] = pool[i]->buf(cur);
+        w.y[i] = pool[i]->buf(o);
+    }
+    const ConvLayer *Lp[2];
+    {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_wino(0, w, s));
+    }
+    const size_t nl = st[0]->layers.size();
+    for (size_t k = 0; k <= nl; ++k) {
+        for (int i = 0; i < n; ++i) {
+            Lp[i] = k < nl ? st[i]->layers[k].get() : &st[i]->tail;
+            w.bias[i] = Lp[i]->bias.f();
+        }
+        w.act = Lp[0]->act;
+        const float *Vp[2] = {w.V[0], w.V[1]}, *Up[2] = {Lp[0]->wino.f(), n == 2 ? Lp[1]->wino.f() : nullptr};
+        float *Op[2] = {pool[0]->wo.f(), n == 2 ? pool[1]->wo.f() : nullptr};
+        TS_TRY(run_wino_gemm(ctx, n, Vp, Up, Op, M, c, Lp[0]->npad, s));
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_wino(k < nl ? 2 : 1, w, s));
+    }
+    *out_idx = o;
+    return 0;
+}
+
 // Res_CNR_Stack on pool buffer `cur` of each network; returns the index of the output buffer (same for all)
 int run_stack_n(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool, int cur, int c, int B, int L, hipStream_t s,
                 int *out_idx, const LenMask *mk = nullptr) {
+    bool wino = true;   // a stack's layers share one geometry: all of them are lowered or none
+    for (int i = 0; i < n; ++i) {
+        wino = wino && st[i]->tail.wino.p;
+        for (const auto &l : st[i]->layers) wino = wino && l->wino.p;
+    }
+    if (wino) return run_stack_wino(ctx, n, st, pool, cur, c, B, L, s, out_idx, mk);
     int h = cur, tmp = 0;
     const int ns[2] = {c, c};
     const ConvLayer *Lp[2];
@@ -478,6 +581,8 @@ int run_trunk_n(int n, ts_convnet *const *net, const float *const *x, int x_ld, 
         ts_convnet::Work &wk = net[i]->work(s);
         pool[i] = &wk.pool;
         TS_TRY(pool[i]->ensure((size_t)B * T * (hid / 4)));
+        TS_TRY(pool[i]->ensure_wino(std::max({stack_wino_floats(net[i]->s1, hid / 4, B, T), stack_wino_floats(net[i]->s2, hid / 2, B, T / 2),
+                                              stack_wino_floats(net[i]->s3, hid, B, T / 4)})));
         xin[i] = x[i];
         ldx[i] = net[i]->in_dim;
         if (net[i]->in_dim % 32 != 0 || lens) {
@@ -612,6 +717,8 @@ int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const flo
         if (vq[i]->hid != hid) return fail("paired VQ-VAEs must have the same width");
         pool[i] = &vq[i]->work(s).pool;
         TS_TRY(pool[i]->ensure((size_t)B * H * hid));
+        TS_TRY(pool[i]->ensure_wino(std::max({stack_wino_floats(vq[i]->d1, hid, B, H), stack_wino_floats(vq[i]->d2, hid / 2, B, 2 * H),
+                                              stack_wino_floats(vq[i]->d3, hid / 4, B, 4 * H)})));
         if (z && z[i]) {
             int tmp = 0;
             TS_TRY(run_layer(ctx, vq[i]->aft, z[i], vq[i]->emb, B, H, nullptr, 0, pool[i]->buf(0), hid, 0, hid, s, &tmp));

@@ -1,0 +1,311 @@
+"""The Winograd F(4,3) lowering of the wide stride-1 k = 3 C -> C layers on the GPU (csrc/conv_wino.hip, csrc/models.cpp::run_stack_wino):
+the three transform kernels against the numpy restatement of tests/test_wino_host.py bit for bit, one lowered layer against float64 direct
+convolution, a fused stack against the unfused sequence, and the invariances the body path relies on (mixed versus alone, paired versus
+single network), through the product entries.
+
+Shapes: B = 3 clips, C = 512 (the narrowest width lowered by default) and C = 64, clip lengths L in {1, 2, 3, 4, 5, 6, 7, 19, 75}: L < 4,
+every L mod 4, B ceil(L / 4) never a multiple of the GEMM tile height.  Every V / O / y buffer sits between 4 KiB sentinel zones and starts
+out sentinel-filled: an overrun changes a zone, an element the kernels must write and do not keeps the sentinel.
+
+Bound of the op-level comparison: 2e-5 on layers of unit scale, the bound the project's conv op tests were measured under
+(profiles/r06_notes/measured_errors_s5.jsonl) — taken from there, not from this code; the direct engine's error on the same inputs is
+recorded beside it (assert_close_measured)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import assert_close_measured
+from test_wino_host import F32, F64, conv64, wino_in_np, wino_y_np
+
+pytestmark = pytest.mark.gpu
+
+LENGTHS = (1, 2, 3, 4, 5, 6, 7, 19, 75)
+RZ = 1024                                   # floats per red zone: 4 KiB
+SENTINEL = 0x7FE5A5A5                       # a quiet NaN with a payload no arithmetic produces
+BOUND = 2e-5
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from talkshow_amd import _lib
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    return _lib, _lib.load(), _lib.context(0)
+
+
+class Zoned:
+    """n floats between two sentinel zones, the body sentinel-filled too."""
+
+    def __init__(self, n):
+        self.n = n
+        self.t = torch.from_numpy(np.full(n + 2 * RZ, SENTINEL, np.uint32).view(F32)).cuda()
+
+    def ptr(self):
+        return self.t.data_ptr() + 4 * RZ
+
+    def check(self, name):
+        """zones intact, every body element written -> the body as numpy"""
+        bits = self.t.cpu().numpy().view(np.uint32)
+        assert np.all(bits[:RZ] == SENTINEL) and np.all(bits[RZ + self.n:] == SENTINEL), f"{name}: a red zone was written"
+        body = bits[RZ:RZ + self.n]
+        assert not np.any(body == SENTINEL), f"{name}: {int((body == SENTINEL).sum())} of {self.n} elements were not written"
+        return body.view(F32).copy()
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def transform(hip, which, B, L, Cc, act, nets, lens=None, shr=0, shl=0):
+    """nets: per network a dict of device addresses x / V / O / bias / res / y (missing = null)."""
+    _lib, lib, ctx = hip
+    ptrs = (C.c_void_p * 12)()
+    for i, n in enumerate(nets):
+        for j, k in enumerate(("x", "V", "O", "bias", "res", "y")):
+            ptrs[6 * i + j] = n.get(k)
+    _lib.check(lib.ts_debug_wino_transform(ctx, which, len(nets), B, L, Cc, act, _lib.dptr(lens), shr, shl, ptrs, _lib.stream_ptr()))
+
+
+def gemm(hip, V, U, O, M, Cc):
+    _lib, lib, ctx = hip
+    _lib.check(lib.ts_debug_wino_gemm(ctx, 1, V, None, U, None, O, None, M, Cc, _lib.stream_ptr()))
+
+
+def weights(hip, w):
+    """taps (cout, cin, 3) -> the packed Winograd matrices on the device"""
+    _lib, lib, ctx = hip
+    cout, cin, _ = w.shape
+    out = np.empty((6, (cout + 127) // 128 * 128, cin), F32)
+    _lib.check(lib.ts_debug_wino_weights(w.ctypes.data, cout, cin, out.ctypes.data))
+    return dev(out)
+
+
+def act64(v, act):
+    if act == 1:
+        return np.where(v >= 0, v, 0.2 * v)
+    if act == 2:
+        return np.maximum(v, 0.0)
+    if act == 3:
+        from scipy.special import erf
+        return 0.5 * v * (1.0 + erf(v / np.sqrt(2.0)))
+    return v
+
+
+# ----------------------------------------------------------------------------------------------- 1. the transform kernels, bit for bit
+MASKS = {None: None, "own": (0, 0), "shifted": (2, 1)}
+
+
+@pytest.mark.parametrize("Cc", [512, 64])
+def test_transforms_equal_the_restatement_bit_for_bit(hip, Cc):
+    rng = np.random.default_rng(Cc)
+    B = 3
+    for L in LENGTHS:
+        J = (L + 3) // 4
+        for mask, sh in MASKS.items():
+            if mask and L not in (6, 19):
+                continue
+            lens_h = shr = shl = None
+            if mask:
+                shr, shl = sh
+                lens_h = np.array([[L, 3, 0], [4 * L, 2 * L, 7]][mask == "shifted"], np.int32)      # own lengths: all of L, a part, none
+            lens = dev(lens_h) if mask else None
+            kw = dict(lens=lens, shr=shr or 0, shl=shl or 0)
+            nkw = dict(lens=lens_h, shr=shr or 0, shl=shl or 0)
+            x = rng.standard_normal((B, L, Cc)).astype(F32)
+            O = rng.standard_normal((6, B * J, Cc)).astype(F32)
+            bias, res = rng.standard_normal(Cc).astype(F32), rng.standard_normal((B, L, Cc)).astype(F32)
+            xd, Od, bd, rd = dev(x), dev(O), dev(bias), dev(res)
+            V = Zoned(6 * B * J * Cc)
+            transform(hip, 0, B, L, Cc, 0, [dict(x=xd.data_ptr(), V=V.ptr())], **kw)
+            assert np.array_equal(V.check("V").view(np.uint32), wino_in_np(x, **nkw).reshape(-1).view(np.uint32)), ("wino_in", L, mask)
+            for act in (0, 1, 2):
+                for r in (None, res):
+                    y = Zoned(B * L * Cc)
+                    transform(hip, 1, B, L, Cc, act, [dict(O=Od.data_ptr(), bias=bd.data_ptr(), res=rd.data_ptr() if r is not None else None, y=y.ptr())], **kw)
+                    want = wino_y_np(O, bias, B, L, act, res=r, **nkw)
+                    assert np.array_equal(y.check("y").view(np.uint32), want.reshape(-1).view(np.uint32)), ("wino_out", L, mask, act, r is not None)
+                V2 = Zoned(6 * B * J * Cc)
+                transform(hip, 2, B, L, Cc, act, [dict(O=Od.data_ptr(), bias=bd.data_ptr(), V=V2.ptr())], **kw)
+                want = wino_in_np(wino_y_np(O, bias, B, L, act, **nkw), **nkw)
+                assert np.array_equal(V2.check("V'").view(np.uint32), want.reshape(-1).view(np.uint32)), ("wino_out_in", L, mask, act)
+    # two networks in one launch = each alone
+    L, J = 7, 2
+    xs = [rng.standard_normal((B, L, Cc)).astype(F32) for _ in range(2)]
+    xd = [dev(x) for x in xs]
+    Vs = [Zoned(6 * B * J * Cc) for _ in range(2)]
+    transform(hip, 0, B, L, Cc, 0, [dict(x=xd[i].data_ptr(), V=Vs[i].ptr()) for i in range(2)])
+    for i in range(2):
+        assert np.array_equal(Vs[i].check("V pair").view(np.uint32), wino_in_np(xs[i]).reshape(-1).view(np.uint32))
+
+
+# ----------------------------------------------------------------------------------------------- 1 + 4. one lowered layer, red zones
+def lowered_layer(hip, x, Ud, bias, act, res=None):
+    """x (B, L, C) host -> y host through wino_in, the six GEMMs and wino_out, V / O / y in red-zoned buffers"""
+    B, L, Cc = x.shape
+    J = (L + 3) // 4
+    xd, bd = dev(x), dev(bias)
+    rd = dev(res) if res is not None else None
+    V, O, y = Zoned(6 * B * J * Cc), Zoned(6 * B * J * Cc), Zoned(B * L * Cc)
+    transform(hip, 0, B, L, Cc, 0, [dict(x=xd.data_ptr(), V=V.ptr())])
+    gemm(hip, V.ptr(), Ud.data_ptr(), O.ptr(), B * J, Cc)
+    transform(hip, 1, B, L, Cc, act, [dict(O=O.ptr(), bias=bd.data_ptr(), res=rd.data_ptr() if rd is not None else None, y=y.ptr())])
+    torch.cuda.synchronize()
+    V.check("V"), O.check("O")
+    return y.check("y").reshape(B, L, Cc)
+
+
+@pytest.mark.parametrize("Cc", [512, 64])
+def test_lowered_layer_against_float64(hip, Cc):
+    """x -> y of one lowered layer, each activation, with and without the residual, against float64 direct convolution of the same taps
+    on inputs of unit scale; the direct engine on the same inputs beside it."""
+    _lib, lib, ctx = hip
+    rng = np.random.default_rng(100 + Cc)
+    B = 3
+    w = (rng.standard_normal((Cc, Cc, 3)) / np.sqrt(3 * Cc)).astype(F32)          # outputs of unit scale
+    bias = rng.standard_normal(Cc).astype(F32)
+    Ud = weights(hip, w)
+    for L in LENGTHS:
+        x = rng.standard_normal((B, L, Cc)).astype(F32)
+        res = rng.standard_normal((B, L, Cc)).astype(F32)
+        pre = conv64(x, w, bias)
+        for act, r in ((0, None), (1, None), (2, res), (3, None), (1, res)) if L in (5, 75) else ((1, None), (2, res)):
+            ref = act64(pre + (r.astype(F64) if r is not None else 0.0), act)
+            got = lowered_layer(hip, x, Ud, bias, act, r)
+            assert_close_measured(f"wino layer C={Cc} L={L} act={act} res={r is not None}", got, ref, BOUND)
+        xd = dev(x)
+        out = torch.empty((B, L, Cc), dtype=torch.float32, device="cuda")
+        _lib.check(lib.ts_op_conv1d(ctx, _lib.dptr(xd), B, L, Cc, w.ctypes.data_as(C.POINTER(C.c_float)), bias.ctypes.data_as(C.POINTER(C.c_float)),
+                                    Cc, 3, 1, 1, 0, 1, _lib.dptr(out), _lib.stream_ptr()))
+        assert_close_measured(f"direct layer C={Cc} L={L} act=1", out.cpu().numpy(), act64(pre, 1), BOUND)
+
+
+# ----------------------------------------------------------------------------------------------- 2. a stack: fused = unfused
+@pytest.mark.parametrize("masked", [False, True])
+def test_fused_stack_equals_unfused(hip, masked):
+    """Res_CNR_Stack as production runs it (wino_in, then GEMMs + wino_out_in per layer, GEMMs + wino_out with the residual) against the same
+    layers run one by one (wino_in, GEMMs, wino_out each): bit for bit, the intermediate y never stored."""
+    rng = np.random.default_rng(9)
+    B, Cc = 3, 512
+    ws = [(rng.standard_normal((Cc, Cc, 3)) / np.sqrt(3 * Cc)).astype(F32) for _ in range(3)]
+    Us = [weights(hip, w) for w in ws]
+    bs = [dev(rng.standard_normal(Cc).astype(F32)) for _ in range(3)]
+    acts = (1, 1, 2)
+    for L in (3, 6, 19):
+        J = (L + 3) // 4
+        lens_h = np.array([L, L // 2, 1], np.int32) if masked else None
+        kw = dict(lens=dev(lens_h)) if masked else {}
+        x = rng.standard_normal((B, L, Cc)).astype(F32)
+        if masked:
+            for b in range(B):
+                x[b, lens_h[b]:] = 0
+        xd = dev(x)
+        V, O = Zoned(6 * B * J * Cc), Zoned(6 * B * J * Cc)
+        yf = Zoned(B * L * Cc)
+        transform(hip, 0, B, L, Cc, 0, [dict(x=xd.data_ptr(), V=V.ptr())], **kw)
+        for k in range(3):
+            gemm(hip, V.ptr(), Us[k].data_ptr(), O.ptr(), B * J, Cc)
+            if k < 2:
+                transform(hip, 2, B, L, Cc, acts[k], [dict(O=O.ptr(), bias=bs[k].data_ptr(), V=V.ptr())], **kw)
+            else:
+                transform(hip, 1, B, L, Cc, acts[k], [dict(O=O.ptr(), bias=bs[k].data_ptr(), res=xd.data_ptr(), y=yf.ptr())], **kw)
+        fused = yf.check("y fused")
+        h = xd
+        for k in range(3):
+            y = Zoned(B * L * Cc)
+            transform(hip, 0, B, L, Cc, 0, [dict(x=h.data_ptr(), V=V.ptr())], **kw)
+            gemm(hip, V.ptr(), Us[k].data_ptr(), O.ptr(), B * J, Cc)
+            transform(hip, 1, B, L, Cc, acts[k], [dict(O=O.ptr(), bias=bs[k].data_ptr(), res=xd.data_ptr() if k == 2 else None, y=y.ptr())], **kw)
+            h = dev(y.check(f"y layer {k}"))
+        assert np.array_equal(fused.view(np.uint32), h.cpu().numpy().reshape(-1).view(np.uint32)), (L, masked)
+        if masked:
+            f = fused.reshape(B, L, Cc)
+            assert all(np.all(f[b, lens_h[b]:] == 0) for b in range(B))
+
+
+# ----------------------------------------------------------------------------------------------- 3. invariances, product entries
+HID = int(os.environ.get("TS_WINO_TEST_HID", "512"))      # 512: the C = 512 stacks are lowered by default; 256 under TS_CONV_WINO=1 (child)
+
+
+def misc_launches(hip, fn):
+    _lib, lib, ctx = hip
+    n = (C.c_int64 * 4)()
+    _lib.check(lib.ts_prof_read_n(ctx, 4, None, n, None, 1))
+    _lib.check(lib.ts_prof_enable(ctx, 1))
+    fn()
+    torch.cuda.synchronize()
+    _lib.check(lib.ts_prof_read_n(ctx, 4, None, n, None, 1))
+    _lib.check(lib.ts_prof_enable(ctx, 0))
+    return int(n[2])
+
+
+def test_invariance_mixed_versus_alone_and_paired_versus_single(hip):
+    """Clips of every length alone (single network, unmasked) and the same clips at arbitrary slots of ONE masked pair pass
+    (ts_vqvae_encode_pair_masked / ts_vqvae_decode_pair_masked): valid rows bit-equal, rows beyond a clip's length exactly zero.
+    Body + hand in lockstep (ts_body_vq_infer, ts_vqvae_decode_pair) equal each network alone bit for bit."""
+    from talkshow_amd import synth
+    from talkshow_amd.modules import VQVAE, encode_pair_masked
+    _lib, lib, ctx = hip
+    vb, vh = VQVAE(39, 64, 256, HID, 2).cuda(), VQVAE(90, 64, 256, HID, 2).cuda()
+    vb.load_state_dict(synth.to_torch(synth.vqvae_state_dict(seed=3, in_dim=39, num_embeddings=256, num_hiddens=HID)))
+    vh.load_state_dict(synth.to_torch(synth.vqvae_state_dict(seed=3, in_dim=90, num_embeddings=256, num_hiddens=HID, salt=1)))
+    lowered_stacks = {512: 1, 256: 3}[HID]                 # per trunk / decoder: the widest by default, all three under TS_CONV_WINO=1
+    rng = np.random.default_rng(21)
+    Hs = [LENGTHS[i] for i in rng.permutation(len(LENGTHS))]     # code rows per clip = rows of the widest stack; arbitrary slots
+    B, H_max = len(Hs), max(Hs)
+    T_max = 4 * H_max
+    poses = synth.gt_poses(5, B, T_max)
+    block = np.zeros((B, T_max, 129), F32)
+    for b, h in enumerate(Hs):
+        block[b, :4 * h] = poses[b, :4 * h]
+    lens = dev(np.array([4 * h for h in Hs], np.int32))
+    # --- encode
+    codes, zb, zh = encode_pair_masked(vb, vh, dev(block), lens, want_z=True)
+    codes, zb, zh = codes.cpu().numpy(), zb.cpu().numpy(), zh.cpu().numpy()
+    for b, h in enumerate(Hs):
+        for net, z_mixed, col, sl in ((vb, zb, 0, slice(0, 39)), (vh, zh, 1, slice(39, 129))):
+            z, _, lat = net.encode_nlc(dev(block[b:b + 1, :4 * h, sl]), want_z=True)
+            assert np.array_equal(z.cpu().numpy()[0].view(np.uint32), z_mixed[b, :h].view(np.uint32)), ("z", b, h, col)
+            assert np.all(z_mixed[b, h:] == 0), ("z beyond", b, h, col)
+            assert np.array_equal(lat.cpu().numpy()[0], codes[b, :h, col]) and np.all(codes[b, h:, col] == -1)
+    # --- decode
+    lat = rng.integers(0, 256, (2, B, H_max)).astype(np.int64)
+    lb, lh = dev(lat[0]), dev(lat[1])
+    out = torch.full((B, 4 * H_max, 129), float("nan"), dtype=torch.float32, device="cuda")
+    n_misc = misc_launches(hip, lambda: _lib.check(lib.ts_vqvae_decode_pair_masked(vb.handle(), vh.handle(), _lib.dptr(lb), _lib.dptr(lh), _lib.dptr(lens),
+                                                                                   B, H_max, _lib.dptr(out), _lib.stream_ptr())))
+    assert n_misc == 2 + 4 * lowered_stacks, n_misc       # two gathers + wino_in, 2 x wino_out_in, wino_out per lowered stack (both networks in one launch)
+    out = out.cpu().numpy()
+    for b, h in enumerate(Hs):
+        for net, col0, w in ((vb, 0, 39), (vh, 39, 90)):
+            alone = net.decode_nlc(dev(lat[int(col0 > 0)][b:b + 1, :h])).cpu().numpy()[0]
+            assert np.array_equal(alone.view(np.uint32), out[b, :4 * h, col0:col0 + w].view(np.uint32)), ("decode", b, h, col0)
+        assert np.all(out[b, 4 * h:] == 0), ("decode beyond", b, h)
+    # --- paired = single, unmasked
+    pair = torch.empty((B, 4 * H_max, 129), dtype=torch.float32, device="cuda")
+    _lib.check(lib.ts_vqvae_decode_pair(vb.handle(), vh.handle(), _lib.dptr(lb), _lib.dptr(lh), B, H_max, _lib.dptr(pair), _lib.stream_ptr()))
+    pair = pair.cpu().numpy()
+    assert np.array_equal(vb.decode_nlc(lb).cpu().numpy().view(np.uint32), np.ascontiguousarray(pair[..., :39]).view(np.uint32))
+    assert np.array_equal(vh.decode_nlc(lh).cpu().numpy().view(np.uint32), np.ascontiguousarray(pair[..., 39:]).view(np.uint32))
+    pd = dev(poses)
+    vq = torch.empty((B, H_max, 2), dtype=torch.int64, device="cuda")
+    recon = torch.empty((B, T_max, 129), dtype=torch.float32, device="cuda")
+    _lib.check(lib.ts_body_vq_infer(vb.handle(), vh.handle(), _lib.dptr(pd), B, T_max, _lib.dptr(vq), _lib.dptr(recon), _lib.stream_ptr()))
+    vq, recon = vq.cpu().numpy(), recon.cpu().numpy()
+    for net, col, sl in ((vb, 0, slice(0, 39)), (vh, 1, slice(39, 129))):
+        _, _, l1 = net.encode_nlc(dev(poses[..., sl]))
+        assert np.array_equal(l1.cpu().numpy(), vq[..., col])
+        assert np.array_equal(net.decode_nlc(l1).cpu().numpy().view(np.uint32), np.ascontiguousarray(recon[..., sl]).view(np.uint32))
+
+
+def test_invariance_at_every_width_under_the_knob(hip):
+    """TS_CONV_WINO=1 lowers every eligible geometry (here the 64-, 128- and 256-wide stacks of a narrow VQ-VAE pair); the knob is read once
+    per process, so the invariance test above runs again in a child process, as test_alternate_kernel_paths does."""
+    env = dict(os.environ, TS_CONV_WINO="1", TS_WINO_TEST_HID="256")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-k", "mixed_versus_alone"],
+                       env=env, capture_output=True, text=True, timeout=600, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "1 passed" in r.stdout
