@@ -941,6 +941,58 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud_dev, in
 int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st);   /* hipGraphs this session has captured so far */
 void ts_pixelcnn_stream_close(ts_pixelcnn_stream *st);
 
+/* ---- seamless sessions ---------------------------------------------------------------------------------------------------
+ * A body session fed MFCC chunks of ANY length that returns, over its pushes and one flush, the codes and poses ts_body_pixel_infer
+ * returns for the concatenated audio, bit for bit (same mode, seed and clip_index0) — where a plain session (ts_audioenc_forward,
+ * ts_pixelcnn_stream_step and ts_vqvae_decode_pair per chunk, as the reference does) pads every chunk border like a clip edge.  No
+ * layer carries state: each call runs the audio encoder and both VQ decoders on a WINDOW through the existing entries and keeps the rows
+ * whose bits the window's borders cannot reach: 7 code rows either side for the encoder (its receptive field), 13 for the decoders
+ * (their receptive field of 6, and 7 more because the rounding of a Winograd-lowered layer reaches to the edge of its 4-row tile); every
+ * window is cut at a multiple of 4 code rows so that those tiles sit where the one-shot call has them.  The price is a lag: a code row
+ * is final 7 code rows (28 frames) after its audio arrived and its poses 13 rows after that — 20 code rows, 80 frames.  Where the audio
+ * encoder itself is lowered (TS_CONV_WINO=1, or an encoder of 512 channels or more) its reach is 14 rows for the same reason, the session
+ * takes that at open, and the lag is 27 code rows (ts_body_stream_lag_rows).
+ * The session owns a ts_pixelcnn_stream, the last <= 71 MFCC frames (127 with a lowered encoder; double-buffered) and a ring of its last code rows; all buffers are
+ * allocated at open and never grown, whatever the history.  max_chunk_frames bounds t of every push.  All clips of a session have one
+ * length.  ids_dev (B,) int64 is fixed for the session.  A session belongs to the thread that drives it. */
+typedef struct ts_body_stream ts_body_stream;
+int ts_body_stream_open(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *ids_dev, int B,
+                        int max_chunk_frames, ts_body_stream **out);
+/* Host only: what the next call — a push of t >= 1 frames (flush = 0) or the flush (flush != 0, t = 0) — will produce: *code_rows = n code
+ * rows, *pose_frames = m pose frames (either may be 0), so that the host can size uniforms, given, logprob and the outputs. */
+int ts_body_stream_plan(const ts_body_stream *st, int t, int flush, int64_t *code_rows, int64_t *pose_frames);
+/* mfcc_dev (B,t,64), 16-byte aligned -> codes_dev (B,n,2) int64 (16-byte aligned): the n code rows this call finalises, and poses_dev
+ * (B,m,body_dim+hand_dim): the next m pose frames, n and m as ts_body_stream_plan says; with n = 0 / m = 0 the pointer is not read.
+ * mode, uniforms_dev (B,n,2), seed, clip_index0 and the optional pieces are those of ts_pixelcnn_stream_step_ctl FOR THE n ROWS THIS
+ * CALL RUNS (logprob_dev, given_dev (B,n,2)); all NULL / 0: the plain step.  The session's own arguments are checked before the first
+ * launch; the pieces are checked by the chain before its first launch and before any counter moves; what is launched ahead of that writes
+ * scratch and the idle half of the double buffer only, so a REFUSED call leaves the session where it was.  A call that fails on the
+ * device leaves the session broken: every later call is refused.  Stream-ordered; no
+ * synchronisation, no host copy. */
+int ts_body_stream_push(ts_body_stream *st, const float *mfcc_dev, int t, int mode, const float *uniforms_dev, uint64_t seed,
+                        int64_t clip_index0, int64_t *codes_dev, float *poses_dev,
+                        const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                        const int64_t *given_dev, const int32_t *given_rows_host,
+                        const float *style_dev,
+                        const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                        const ts_repeat *rep_host, int n_rep, void *stream);
+/* The end of the clip: the rows and frames held back come out (the last window runs to the clip's true end, leftover frames_in % 4
+ * included, as the one-shot call's does).  Over a session the pose frames sum to 4 (frames_in / 4).  Every later call is refused. */
+int ts_body_stream_flush(ts_body_stream *st, int mode, const float *uniforms_dev, uint64_t seed, int64_t clip_index0, int64_t *codes_dev,
+                         float *poses_dev,
+                         const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                         const int64_t *given_dev, const int32_t *given_rows_host,
+                         const float *style_dev,
+                         const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                         const ts_repeat *rep_host, int n_rep, void *stream);
+int64_t ts_body_stream_frames_in(const ts_body_stream *st);     /* MFCC frames received */
+int64_t ts_body_stream_code_rows(const ts_body_stream *st);     /* code rows finalised */
+int64_t ts_body_stream_pose_frames(const ts_body_stream *st);   /* pose frames returned */
+int64_t ts_body_stream_state_bytes(const ts_body_stream *st);   /* device bytes of the session's own buffers: constant from open to close */
+int ts_body_stream_lag_rows(const ts_body_stream *st);          /* code rows between a row's audio and its poses: 20, or 27 with a lowered encoder */
+int64_t ts_body_stream_captures(const ts_body_stream *st);      /* ts_pixelcnn_stream_captures of the chain session it owns */
+void ts_body_stream_close(ts_body_stream *st);
+
 /* ---- batched SMPL-X joints / vertices ----------------------------------------------------------------
  * Replaces the per-frame float64 CPU calls of smplx.SMPLX.forward in scripts/demo.py:122-152 (get_vertices) and
  * data_utils/get_j.py:20-50 (get_joints).  Third-party arithmetic (smplx ~= 0.1.28, requirements.txt:5; package and

@@ -360,6 +360,15 @@ int ts_debug_wino_transform(ts_ctx *ctx, int which, int nnet, int B, int L, int 
 int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, const float *U0, const float *U1, float *O0, float *O1, int M,
                        int C, void *stream);
 
+/* ---- seamless sessions (csrc/body_stream.cpp; talkshow_hip.h, "seamless sessions") ----
+ * Host-only (no GPU): one call of the window plan on given counters.  state4 = {frames received F, code rows done A, code rows whose poses
+ * are out D, flushed}; a push of t >= 1 frames (flush = 0) or the flush (flush != 0, t = 0); enc_lowered != 0: the plan of a session whose
+ * audio encoder is Winograd-lowered (an encoder reach of 14 code rows in place of 7).  out14 = {F, A, D, flushed after the call;
+ * encoder window frames [f0, f1) (empty: no call); code rows [A0, A1) the call finalises; decoder window code rows [v0, v1) (empty: no
+ * call); code rows [D0, D1) whose poses come out; the first MFCC frame and the first code row a later call can still read}.  The
+ * arithmetic talkshow_amd/streaming.py::SeamlessPlan restates.  No reference counterpart. */
+int ts_debug_body_stream_plan(const int64_t *state4, int t, int flush, int enc_lowered, int64_t *out14);
+
 /* Tuning entry (not part of the drop-in surface): `iters` DEPENDENT skinny_gemm launches replayed from one hipGraph;
  * *us_out = microseconds per launch.  gate != 0: N = 2K with the tanh*sigmoid epilogue; debug: unused. */
 int ts_debug_skinny_chain(ts_ctx *ctx, int M, int K, int gate, int iters, int debug, float *us_out);

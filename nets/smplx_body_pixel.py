@@ -735,14 +735,71 @@ class TrainWrapper(TrainWrapperBaseClass):
         output = pred_poses
         return output
 
-    def open_stream(self, id, B, max_frames, *, sampling=None, style=None, code_bias=None, repeat=None):
+    def open_stream(self, id, B, max_frames, *, seamless=False, sampling=None, style=None, code_bias=None, repeat=None):
         """Long-audio / continuity generation: a session that is fed MFCC chunks and returns the poses of
         each chunk, every chunk continuing the PixelCNN row cache of the ones before it (`ts_pixelcnn_stream_*`) — the
         reference's `infer(..., pre_latents, pre_audio)` chain (`:291-304`) for any number of chunks, at a cost per chunk
-        that does not grow with the history.  As in the reference, each chunk goes through the audio encoder and the VQ
-        decoders on its own (their receptive fields are not carried across chunks).  sampling / style / code_bias / repeat: session
-        defaults for the keywords of `BodyStream.push` (`GatedPixelCNN.open_stream`)."""
+        that does not grow with the history.  sampling / style / code_bias / repeat: session defaults for the keywords of
+        `push` (`GatedPixelCNN.open_stream`).
+
+        seamless=False (the default): `BodyStream`.  As in the reference, each chunk goes through the audio encoder and the VQ
+        decoders on its own (their receptive fields are not carried across chunks), so every chunk border is padded like a clip
+        edge: audio rows within 7 code rows of a seam, the codes drawn from them, and pose frames within 6 code rows of it differ
+        from one call over the whole audio.  `push(mfcc (B,T,64)) -> poses (B, 4*(T//4), 129)`; a chunk's T % 4 frames are lost.
+
+        seamless=True: `talkshow_amd.streaming.SeamlessBodyStream` (`ts_body_stream_*`).  ANY chunking returns the
+        bits of `generate_batch` on the concatenated audio (same mode, seed, clip_index0 and keywords): the conv nets run on
+        windows cut so that every kept row has its whole receptive field, through the same entries a clip takes.
+          push(mfcc (B,t,64), ...)   any t in 1 .. max_frames; leftover frames are carried.  Returns poses (B, n, 129), n = 4 x the code
+                                     rows that became final — possibly 0 during the first ~80 frames: the poses of a code row follow its
+                                     audio by 20 code rows (80 frames, 2.67 s at 30 fps).
+          flush(...)                 the rest, ending the clip; a later push raises ValueError.  Over a session the returned frames sum to
+                                     4 * (frames_in // 4).
+          return_codes=True adds the call's codes (B,Hc,2), logprobs=True their log-probabilities.  The step keywords (sampling, style,
+          code_bias, repeat, given, uniforms) apply to the Hc code rows THAT call runs: `session.plan(t, flush=False)` ->
+          (code_rows, pose_frames) names the counts beforehand, and a wrong `uniforms` / `given` row count raises ValueError naming the
+          expected one before any device work.  Properties: frames_in, code_rows, frames, state_bytes (constant for any history).
+        Not taken by a seamless session: clips of different lengths, given poses, kept positions, style tracks inside a step."""
+        if seamless:
+            from talkshow_amd.streaming import SeamlessBodyStream
+            return SeamlessBodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
         return BodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
+
+    def generate_long(self, mfcc, ids, chunk_frames=240, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, sampling=None,
+                      style=None, code_bias=None, repeat=None):
+        """`generate_batch` for audio of ANY length at memory bounded by the chunk: mfcc (B,T,64), ids (B,) or one for all -> codes
+        (B,T//4,2), poses (B,4 (T//4),129), bit for bit what `generate_batch(mfcc, ids, mode=, uniforms=, seed=, clip_index0=, ...)` returns,
+        through one seamless session (`open_stream(..., seamless=True)`) pushed chunk_frames at a time.  Only the results are as long as the
+        audio (mfcc may live on the host: a chunk is uploaded when it is pushed).  uniforms: (B,T//4,2) for TS_SAMPLE_UNIFORMS.  sampling /
+        style (one weight row per clip) / code_bias / repeat: the keywords of `generate_batch` a session takes, for the whole clip."""
+        if len(mfcc.shape) != 3 or int(mfcc.shape[2]) != 64:
+            raise ValueError(f"generate_long: mfcc must be (B, T, 64), got {tuple(mfcc.shape)}")
+        B, T = int(mfcc.shape[0]), int(mfcc.shape[1])
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError(f"generate_long: chunk_frames is at least 1, got {chunk_frames}")
+        if uniforms is not None:
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
+            if tuple(uniforms.shape) != (B, T // 4, 2):
+                raise ValueError(f"generate_long: uniforms must have shape (B={B}, {T // 4}, 2), got {tuple(uniforms.shape)}")
+            mode = _lib.TS_SAMPLE_UNIFORMS
+        if seed is None:
+            seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
+        session = self.open_stream(ids, B, chunk_frames, seamless=True, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
+        codes, poses = [], []
+        try:
+            for f0 in list(range(0, T, chunk_frames)) + [None]:
+                t = 0 if f0 is None else min(chunk_frames, T - f0)
+                r0 = session.code_rows
+                n, _ = session.plan(t, flush=f0 is None)
+                kw = dict(mode=mode, seed=seed, clip_index0=clip_index0, uniforms=None if uniforms is None else uniforms[:, r0:r0 + n],
+                          return_codes=True)
+                p, c = session.flush(**kw) if f0 is None else session.push(mfcc[:, f0:f0 + t], **kw)
+                codes.append(c)
+                poses.append(p)
+        finally:
+            session.close()
+        return torch.cat(codes, 1), torch.cat(poses, 1)
 
     def infer(self, aud_feat, frame, id, B, pre_latents=None, pre_audio=None, pre_pose=None, mode=None, seed=None):
         """smplx_body_pixel.py:291-304 (continuity helper, reference call shape): returns latents, audio (B,256,H,2),

@@ -146,6 +146,21 @@ SIGNATURES = {
     "ts_debug_rep_table": (_i, [_rp, _i, _i, _i, C.POINTER(C.c_int32)]),
     "ts_pixelcnn_stream_rows": (_i64, [_vp]),
     "ts_pixelcnn_stream_close": (None, [_vp]),
+    # seamless sessions: the step's arguments around (mfcc, t) / the two outputs, then the pieces of ts_pixelcnn_stream_step_ctl
+    "ts_body_stream_open": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "ts_body_stream_plan": (_i, [_vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
+    "ts_body_stream_push": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                 C.POINTER(C.c_int32), _rp, _i, _vp]),
+    "ts_body_stream_flush": (_i, [_vp, _i, _vp, _u64, _i64, _vp, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                  C.POINTER(C.c_int32), _rp, _i, _vp]),
+    "ts_body_stream_frames_in": (_i64, [_vp]),
+    "ts_body_stream_code_rows": (_i64, [_vp]),
+    "ts_body_stream_pose_frames": (_i64, [_vp]),
+    "ts_body_stream_state_bytes": (_i64, [_vp]),
+    "ts_body_stream_captures": (_i64, [_vp]),
+    "ts_body_stream_close": (None, [_vp]),
+    "ts_body_stream_lag_rows": (_i, [_vp]),
+    "ts_debug_body_stream_plan": (_i, [C.POINTER(_i64), _i, _i, _i, C.POINTER(_i64)]),
     "ts_face_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, C.POINTER(_vp)]),
     "ts_face_destroy": (None, [_vp]),
     "ts_face_generate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

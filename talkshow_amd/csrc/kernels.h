@@ -684,4 +684,15 @@ struct PutWords {
 };
 hipError_t launch_put_words(int *dst, const int *host, long n, hipStream_t s);
 
+// ---- body_stream.hip: the staging around the window calls of a seamless body session (body_stream.cpp) ----
+// [tail (B, cap, 64) rows [0, n_tail) | chunk (B, t, 64)] per clip: frames [0, Tw) -> win (B, Tw, 64), frames [next0, next0 + n_next) ->
+// next (B, cap, 64) rows [0, n_next); tail != next.  Every pointer 16-byte aligned; a shape outside the buffers is hipErrorInvalidValue
+hipError_t launch_stream_stage_mfcc(const float *tail, const float *chunk, float *win, float *next, int B, int n_tail, int t, int cap, int Tw,
+                                    int next0, int n_next, hipStream_t s);
+// codes (B, n, 2) = code rows [A, A + n) -> ring (B, RC, 2) slots r % RC; rows [v0, v0 + Hw) of ring + codes -> lat_body, lat_hand (B, Hw)
+hipError_t launch_stream_emit(const int64_t *codes, int64_t *ring, int64_t *lat_body, int64_t *lat_hand, int B, int n, int A, int RC, int v0,
+                              int Hw, hipStream_t s);
+// dst (B, n, W) = rows [r0, r0 + n) of every clip of src (B, R, W)
+hipError_t launch_stream_keep_rows(const float *src, float *dst, int B, int R, int r0, int n, int W, hipStream_t s);
+
 }  // namespace ts

@@ -586,6 +586,37 @@ class GatedPixelCNN(NativeModule):
         return logits.permute(0, 3, 1, 2)
 
 
+def step_style_rows(net, B, labels, style):
+    """`style=` of a session step -> (B, n_classes) float32 numpy, one weight row per clip: the forms of `_lib.style_block` without tracks.
+    labels: the session's (B,) class labels, what `style=[None, ...]` stands for."""
+    if isinstance(style, (list, tuple)):
+        for i, e in enumerate(style):
+            if e is not None and np.ndim(e.detach().cpu().numpy() if hasattr(e, "detach") else e) >= 2:
+                raise ValueError(f"step: style of clip {i} is a track of rows; a session takes ONE weight row per clip for a step "
+                                 f"(it holds until a later step brings another)")
+    return np.ascontiguousarray(_lib.style_block(style, [1] * B, net.n_classes, who="step", ids=labels)[:, 0])
+
+
+def step_pieces(net, B, labels, defaults, Hc, mode, dev, sampling, logprobs, given, style, code_bias, repeat):
+    """The keywords of one session step of Hc rows as the host-side pieces of the C call (`PixelCNNStream.step`, and the seamless body
+    session's push): the session's `defaults` stand in for a keyword left at None, then every value is validated (ValueError naming the
+    clip).  Pure host code: nothing is launched or uploaded."""
+    sampling = defaults["sampling"] if sampling is None else sampling
+    style = defaults["style"] if style is None else style
+    code_bias = defaults["code_bias"] if code_bias is None else code_bias
+    repeat = defaults["repeat"] if repeat is None else repeat
+    V = net.input_dim
+    lp = _lib.logprob_request(logprobs, (B, Hc, 2), dev)
+    ctl, n_ctl = (None, 0) if sampling is None else _lib.sampling_table(sampling, B, V, mode)
+    btab, bidx = _lib.code_bias_block(code_bias, B, V, who="step", mode=mode)
+    rtab, n_rep = _lib.repeat_table(repeat, B, V, who="step", mode=mode)
+    block = table = None
+    if given is not None:
+        block, table = _lib.given_block(given, [Hc] * B, V, who="step")
+    srows = None if style is None else step_style_rows(net, B, labels, style)
+    return lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows
+
+
 class PixelCNNStream:
     """Host handle of `ts_pixelcnn_stream`: label (B,) or (1,) int64 fixed for the session."""
 
@@ -614,32 +645,12 @@ class PixelCNNStream:
         return int(_lib.load().ts_pixelcnn_stream_captures(self._h))
 
     def _style_rows(self, style):
-        """`style=` of a step -> (B, n_classes) float32 numpy, one weight row per clip: the forms of `_lib.style_block` without tracks."""
-        if isinstance(style, (list, tuple)):
-            for i, e in enumerate(style):
-                if e is not None and np.ndim(e.detach().cpu().numpy() if hasattr(e, "detach") else e) >= 2:
-                    raise ValueError(f"step: style of clip {i} is a track of rows; a session takes ONE weight row per clip for a step "
-                                     f"(it holds until a later step brings another)")
-        return np.ascontiguousarray(_lib.style_block(style, [1] * self.B, self.net.n_classes, who="step", ids=self._labels)[:, 0])
+        """`step_style_rows` on this session's network and labels."""
+        return step_style_rows(self.net, self.B, self._labels, style)
 
     def _pieces(self, Hc, mode, dev, sampling, logprobs, given, style, code_bias, repeat):
-        """The keywords of one step of Hc rows as the host-side pieces of the C call: the session's defaults stand in for a keyword left
-        at None, then every value is validated (ValueError naming the clip).  Pure host code: nothing is launched or uploaded."""
-        d = self.defaults
-        sampling = d["sampling"] if sampling is None else sampling
-        style = d["style"] if style is None else style
-        code_bias = d["code_bias"] if code_bias is None else code_bias
-        repeat = d["repeat"] if repeat is None else repeat
-        B, V = self.B, self.net.input_dim
-        lp = _lib.logprob_request(logprobs, (B, Hc, 2), dev)
-        ctl, n_ctl = (None, 0) if sampling is None else _lib.sampling_table(sampling, B, V, mode)
-        btab, bidx = _lib.code_bias_block(code_bias, B, V, who="step", mode=mode)
-        rtab, n_rep = _lib.repeat_table(repeat, B, V, who="step", mode=mode)
-        block = table = None
-        if given is not None:
-            block, table = _lib.given_block(given, [Hc] * B, V, who="step")
-        srows = None if style is None else self._style_rows(style)
-        return lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows
+        """`step_pieces` on this session's network, labels and defaults."""
+        return step_pieces(self.net, self.B, self._labels, self.defaults, Hc, mode, dev, sampling, logprobs, given, style, code_bias, repeat)
 
     def step(self, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=0, clip_index0=0, *, sampling=None, logprobs=False, given=None,
              style=None, code_bias=None, repeat=None):

@@ -1,0 +1,265 @@
+"""Seamless body streaming: where the windows of a chunked session are cut so that any chunking returns the one-shot call's bits.
+
+`SeamlessPlan` is host arithmetic only (no GPU, no torch): the four counters of a session and, per call, the encoder window, the code
+rows the chain runs, the decoder window and what is kept of each.  The native session (`csrc/body_stream.cpp`, `ts_body_stream_*`)
+restates the same arithmetic in C++; `tests/test_seamless_plan.py` holds the two against each other through a host-only debug entry.
+`SeamlessBodyStream` is the host handle of the native session (`TrainWrapper.open_stream(..., seamless=True)`).
+
+Why these windows ("seamless sessions"): output row i of the audio encoder reads MFCC frames 4i-25 .. 4i+28, 7 code rows to
+either side; pose frame t of a VQ decoder reads code rows t//4-6 .. t//4+6.  A row whose cone lies inside a window (or beyond the clip's own
+edge, where window and clip pad alike) comes out of the window as out of the whole clip.  Windows start at a multiple of 4 code rows so
+that the 4-row Winograd tiles of the lowered conv stacks, counted from a window's row 0, sit where the one-shot call has them.  Equal
+values are not yet equal bits there: an output row of an F(4,3) tile is summed from products that hold the tile's other input rows (y0 from
+d0..d4, y1 and y2 from d1..d4, y3 from d1..d5: csrc/conv_wino.hip), so a lowered layer's ROUNDING reaches to the edge of its tile.  Through
+the three lowered layers of each decoder stack that widens a pose frame's reach from 6 to at most 13 code rows: DEC_TILE_SLACK_ROWS."""
+from collections import namedtuple
+
+ENC_MARGIN_ROWS = 7      # code rows of audio an encoder output row needs on either side
+ENC_TILE_SLACK_ROWS = 7  # ... and how much further the rounding reaches where the audio encoder is Winograd-lowered (not by default)
+DEC_MARGIN_ROWS = 6      # code rows a pose frame needs on either side
+DEC_TILE_SLACK_ROWS = 7  # ... and how much further the rounding of the Winograd-lowered decoder stacks reaches (tile edges)
+ALIGN_ROWS = 4           # every window starts at a multiple of this many code rows
+TAIL_CAP_FRAMES = 72     # MFCC frames a session holds back between calls, at most 71 (see SeamlessPlan.retained; 8 m + 15 at m rows of reach)
+RING_KEEP_ROWS = 32      # code rows a session holds back between calls, at most 29
+
+# One call's work, in absolute frames / code rows of the clip.  enc = (f0, f1): the encoder window, frames [f0, f1), or None (no call);
+# rows = (A0, A1): the audio / code rows the call finalises (rows [A0 - f0 // 4, A1 - f0 // 4) of the window's output, one chain step);
+# dec = (v0, v1): the decoder window, code rows [v0, v1), or None; poses = (D0, D1): the code rows whose 4 pose frames each come out
+# (frames [4 (D0 - v0), 4 (D1 - v0)) of the window's output); keep_frame0 / keep_row0: the first MFCC frame / code row a later call reads.
+Call = namedtuple("Call", "enc rows dec poses keep_frame0 keep_row0")
+
+
+def _align_down(x):
+    return x // ALIGN_ROWS * ALIGN_ROWS
+
+
+class SeamlessPlan:
+    """F MFCC frames received, A audio / code rows done, D code rows whose poses are out, flushed.  `push(t)` / `flush()` move the counters
+    and return the `Call`.  enc_margin / enc_slack / dec_margin / dec_slack: the named constants; a test lowers one to show that a shorter
+    margin is caught (dec_slack=0: the plan for decoders without lowered stacks; enc_slack=ENC_TILE_SLACK_ROWS: the plan the native session
+    takes where the audio encoder is lowered too, TS_CONV_WINO=1 or an encoder of 512 channels or more)."""
+
+    def __init__(self, enc_margin=ENC_MARGIN_ROWS, dec_margin=DEC_MARGIN_ROWS, dec_slack=DEC_TILE_SLACK_ROWS, enc_slack=0):
+        self.F = self.A = self.D = 0
+        self.flushed = False
+        self.enc_margin, self.dec_margin = int(enc_margin) + int(enc_slack), int(dec_margin) + int(dec_slack)
+
+    def peek(self, t, flush=False):
+        """The `Call` a push of t frames (or the flush, t = 0) would make; the counters stay."""
+        if self.flushed:
+            raise ValueError("the session has been flushed (the clip has ended): open another")
+        t = int(t)
+        if flush and t != 0:
+            raise ValueError(f"a flush brings no frames, got t = {t}")
+        if not flush and t < 1:
+            raise ValueError(f"a push holds at least one MFCC frame, got t = {t}")
+        F, A, D, me, md = self.F + t, self.A, self.D, self.enc_margin, self.dec_margin
+        A1 = F // 4 if flush else max(A, F // 4 - me)
+        enc = None
+        if A1 > A:
+            w0 = _align_down(max(0, A - me))
+            enc = (4 * w0, F if flush else min(F, 4 * (A1 + me)))
+        D1 = A1 if flush else max(D, A1 - md)
+        dec = None
+        if D1 > D:
+            dec = (_align_down(max(0, D - md)), min(A1, D1 + md))
+        return Call(enc, (A, A1), dec, (D, D1), 4 * _align_down(max(0, A1 - me)), _align_down(max(0, D1 - md)))
+
+    def _commit(self, call, t, flush):
+        self.F, self.A, self.D, self.flushed = self.F + t, call.rows[1], call.poses[1], flush
+        return call
+
+    def push(self, t):
+        return self._commit(self.peek(t), int(t), False)
+
+    def flush(self):
+        return self._commit(self.peek(0, flush=True), 0, True)
+
+    def retained(self, call):
+        """(MFCC frames, code rows) the session holds after `call` (made last).  Frames: F - 4 w0_next with w0_next >= A - 7 - 3 and
+        A >= F // 4 - 7, so at most 71; rows: A - v0_next with v0_next >= D - 13 - 3 and D >= A - 13, so at most 29 — for any history."""
+        return self.F - call.keep_frame0, self.A - call.keep_row0
+
+    @property
+    def state(self):
+        return self.F, self.A, self.D, int(self.flushed)
+
+
+def chain_rows(max_chunk_frames, enc_reach=ENC_MARGIN_ROWS):
+    """The most code rows one call of a session opened for pushes of up to max_chunk_frames can run: a push of t frames finalises at most
+    t // 4 + 1 rows, the flush the enc_reach rows held back.  The native session opens its chain for this count, so no call is split."""
+    return max(int(enc_reach), int(max_chunk_frames) // 4 + 1)
+
+
+class SeamlessBodyStream:
+    """See `TrainWrapper.open_stream(..., seamless=True)`: the host handle of `ts_body_stream` (talkshow_hip.h, "seamless sessions")."""
+
+    def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None, seed=None):
+        import ctypes as C
+
+        import torch
+
+        from talkshow_amd import _lib
+        from talkshow_amd.modules import _index_tensor
+        gen = wrapper.generator
+        if not (gen.audio and gen.bh_model):
+            raise NotImplementedError("streaming sessions exist for the shipped configuration (audio=True, bh_model=True)")
+        self.w, self.B, self.max_frames = wrapper, int(B), int(max_frames)
+        if self.B < 1 or self.max_frames < 1:
+            raise ValueError(f"open_stream: B and max_frames are at least 1, got B={B}, max_frames={max_frames}")
+        dev = gen._dev()
+        if id is None:
+            id = torch.tensor([0])
+        label = _index_tensor(id, gen.n_classes, "speaker id", dev)
+        if label.numel() == 1 and self.B > 1:
+            label = label.repeat(self.B)
+        if label.numel() != self.B:
+            raise ValueError(f"ids must hold 1 or B={self.B} speaker indices, got {label.numel()}")
+        self.defaults = {"sampling": sampling, "style": style, "code_bias": code_bias, "repeat": repeat}
+        self._labels = label.detach().cpu().numpy()      # what `style=[None, ...]` stands for: the clip's own label
+        self.pose_dim = wrapper.each_dim[1] + wrapper.each_dim[2]
+        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)   # one random stream per session
+        h = C.c_void_p()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ts_body_stream_open(wrapper.audioencoder.handle(), gen.handle(), wrapper.g_body.handle(),
+                                                       wrapper.g_hand.handle(), _lib.dptr(label), self.B, self.max_frames, C.byref(h)))
+        self._h = h
+
+    # ---- counters (host reads; nothing synchronises) ----
+    def _get(self, name):
+        from talkshow_amd import _lib
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return int(getattr(_lib.load(), name)(self._h))
+
+    @property
+    def frames_in(self):
+        """MFCC frames received."""
+        return self._get("ts_body_stream_frames_in")
+
+    @property
+    def code_rows(self):
+        """Code rows finalised."""
+        return self._get("ts_body_stream_code_rows")
+
+    @property
+    def frames(self):
+        """Pose frames returned."""
+        return self._get("ts_body_stream_pose_frames")
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the session's own buffers: constant from open to close, whatever the history."""
+        return self._get("ts_body_stream_state_bytes")
+
+    @property
+    def lag_rows(self):
+        """Code rows between a row's audio and its poses: 20 (7 + 13), or 27 where the audio encoder is Winograd-lowered too."""
+        return self._get("ts_body_stream_lag_rows")
+
+    def graph_captures(self):
+        """`PixelCNNStream.graph_captures` of the chain session inside: stands still once the host's push sizes have been met."""
+        return self._get("ts_body_stream_captures")
+
+    def plan(self, t, flush=False):
+        """(code_rows, pose_frames) the next call — `push` of t frames, or `flush()` with flush=True (t is then not read) — will run and
+        return: the row count of that call's `uniforms` / `given`, and its output sizes.  ValueError after the flush, for t < 1 or for
+        t > max_frames."""
+        import ctypes as C
+
+        from talkshow_amd import _lib
+        if self._h is None:
+            raise ValueError("the session is closed")
+        n, m = C.c_int64(), C.c_int64()
+        try:
+            _lib.check(_lib.load().ts_body_stream_plan(self._h, 0 if flush else int(t), int(bool(flush)), C.byref(n), C.byref(m)))
+        except RuntimeError as e:          # host arithmetic only: a refusal is about the arguments
+            raise ValueError(str(e)) from None
+        return int(n.value), int(m.value)
+
+    def _call(self, mfcc, flush, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes):
+        import ctypes as C
+
+        import torch
+
+        from talkshow_amd import _lib
+        from talkshow_amd.modules import _dev_f32, step_pieces, upload
+        who = "flush" if flush else "push"
+        dev = self.w.generator._dev()
+        B, t = self.B, 0
+        if not flush:
+            if not hasattr(mfcc, "shape") or len(mfcc.shape) != 3 or int(mfcc.shape[0]) != B or int(mfcc.shape[2]) != 64:
+                raise ValueError(f"push: mfcc must have shape (B={B}, t, 64), got {tuple(getattr(mfcc, 'shape', ()))}")
+            t = int(mfcc.shape[1])
+        n, m = self.plan(t, flush)                     # ValueError: after the flush, t = 0, t > max_frames
+        if uniforms is not None:
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)          # lists and numpy arrays too
+            if tuple(uniforms.shape) != (B, n, 2):
+                raise ValueError(f"{who}: this call runs {n} code rows: uniforms must have shape (B={B}, {n}, 2), got {tuple(uniforms.shape)} "
+                                 f"(session.plan(t) names the count)")
+        if mode == _lib.TS_SAMPLE_UNIFORMS and uniforms is None and n > 0:
+            raise ValueError(f"{who}: TS_SAMPLE_UNIFORMS needs uniforms of shape (B={B}, {n}, 2) for the {n} code rows this call runs")
+        if given is not None and not isinstance(given, (list, tuple)) and len(getattr(given, "shape", ())) == 3 and int(given.shape[1]) > n:
+            raise ValueError(f"{who}: this call runs {n} code rows: a given block holds at most {n} rows per clip, got {tuple(given.shape)}")
+        lp = ctl = btab = bidx = rtab = block = table = srows = None
+        n_ctl = n_rep = 0
+        if n > 0:                                      # the keywords of the chain step this call makes, validated on the host
+            lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows = step_pieces(
+                self.w.generator, B, self._labels, self.defaults, n, mode, dev, sampling, logprobs, given, style, code_bias, repeat)
+        if isinstance(lp, str) or (lp is None and logprobs):
+            lp = torch.empty((B, n, 2), dtype=torch.float32, device=dev)
+        codes = torch.empty((B, n, 2), dtype=torch.int64, device=dev)
+        poses = torch.empty((B, m, self.pose_dim), dtype=torch.float32, device=dev)
+        if uniforms is not None:
+            uniforms = _dev_f32(uniforms, dev)
+        i32p = C.POINTER(C.c_int32)
+        block_dev = upload(block, dev) if block is not None else None
+        style_dev = upload(srows, dev) if srows is not None else None
+        bias_dev = upload(btab, dev) if btab is not None else None
+        mid = (mode, _lib.dptr(uniforms) if n > 0 else None, (self.seed if seed is None else int(seed)) & (2 ** 64 - 1), int(clip_index0),
+               _lib.dptr(codes) if n > 0 else None, _lib.dptr(poses) if m > 0 else None,
+               ctl, n_ctl, _lib.dptr(lp) if n > 0 else None, _lib.dptr(block_dev), table.ctypes.data_as(i32p) if block is not None else None,
+               _lib.dptr(style_dev), _lib.dptr(bias_dev), int(btab.shape[0]) if btab is not None else 0,
+               bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep, _lib.stream_ptr())
+        lib = _lib.load()
+        if flush:
+            _lib.check(lib.ts_body_stream_flush(self._h, *mid))
+        else:
+            mf = _dev_f32(mfcc, dev)
+            if mf.data_ptr() % 16:
+                mf = mf.clone()
+            _lib.check(lib.ts_body_stream_push(self._h, _lib.dptr(mf), t, *mid))
+        out = (poses,) + ((codes,) if return_codes else ()) + ((lp,) if lp is not None else ())
+        return out[0] if len(out) == 1 else out
+
+    def push(self, mfcc, mode=2, seed=None, clip_index0=0, uniforms=None, *, sampling=None, logprobs=False, given=None, style=None,
+             code_bias=None, repeat=None, return_codes=False):
+        """mfcc (B, t, 64), any t in 1 .. max_frames -> poses (B, m, 129), the next m = 4 x (code rows whose poses became final) frames of
+        the clip — possibly 0, as during a clip's first ~80 frames; leftover frames are carried.  The call runs n code rows (`plan(t)`
+        names n and m beforehand): `uniforms` (B, n, 2), `given` and the keywords `sampling`, `style`, `code_bias`, `repeat` — the forms and
+        rules of `PixelCNNStream.step`, the session's defaults standing in for None — apply to THOSE rows; with n = 0 they are not read.
+        return_codes=True: (poses, codes (B, n, 2)); logprobs=True adds their log-probabilities (B, n, 2) last.  mode 2 is
+        TS_SAMPLE_PHILOX.  A bad value raises ValueError before any device work, and no counter moves."""
+        return self._call(mfcc, False, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes)
+
+    def flush(self, mode=2, seed=None, clip_index0=0, uniforms=None, *, sampling=None, logprobs=False, given=None, style=None, code_bias=None,
+              repeat=None, return_codes=False):
+        """The end of the clip: the rows and frames held back (`plan(0, flush=True)`), in the form `push` returns them.  Over the session
+        the returned frames sum to 4 * (frames_in // 4), and equal `generate_batch` on the concatenated audio bit for bit.  A later push
+        raises ValueError."""
+        return self._call(None, True, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            import torch
+
+            from talkshow_amd import _lib
+            torch.cuda.synchronize()
+            _lib.load().ts_body_stream_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
