@@ -262,7 +262,7 @@ static int body_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *
     TS_TRY(mixed_style_rows_check("ts_body_pixel_infer_mixed", "T_max / 4", o, H));
     if (o.bias && body_bias_check("ts_body_pixel_infer_mixed_bias", a.mode, B, o.n_bias, o.bias_index_host) != 0) return 1;
     if (o.rep_host && body_repeat_check("ts_body_pixel_infer_mixed_repeat", a.mode, B, 1, o.rep_host, o.n_rep) != 0) return 1;
-    TS_TRY(mixed_given_check("ts_body_pixel_infer_mixed", o, a.lens_host, B));   // a bad row table is refused before the first launch of the pass, too
+    TS_TRY(mixed_given_check("ts_body_pixel_infer_mixed_keep", "ts_body_pixel_infer_mixed_given", o, a.lens_host, B));   // a bad row table is refused before the first launch of the pass, too
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * convnet_hidden(ae) * sizeof(float)));
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, a.lens_dev, B, a.rows, w.feat.f(), s));

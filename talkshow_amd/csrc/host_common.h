@@ -1,4 +1,4 @@
-// Host-side helpers shared by models.cpp / pixelcnn.cpp / api.cpp: error channel, device buffers, the
+// Host-side helpers shared by models.cpp / pixelcnn.cpp / sampler_host.cpp / api.cpp: error channel, device buffers, the
 // reference-state_dict view, the launch wrappers that feed the per-family profiler.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -288,11 +288,33 @@ inline int mixed_style_rows_check(const char *who, const char *rows_name, const 
     if (!o.style || o.style_rows == 1 || o.style_rows == H) return 0;
     return fail(std::string(who) + "_style: style_rows is 1 or " + rows_name + " = " + std::to_string(H) + ", got " + std::to_string(o.style_rows));
 }
-inline int mixed_given_check(const char *who, const MixedOpts &o, const int32_t *lens_host, int B) {
-    if (o.keep && !o.given) return fail(std::string(who) + "_keep: a mask of kept positions needs the given codes it selects from");
+// who_keep / who_given: the entries the two messages name
+inline int mixed_given_check(const char *who_keep, const char *who_given, const MixedOpts &o, const int32_t *lens_host, int B) {
+    if (o.keep && !o.given) return fail(std::string(who_keep) + ": a mask of kept positions needs the given codes it selects from");
     if (!o.given) return 0;
-    if (!o.given_rows_host) return fail(std::string(who) + "_given: given codes need their row table");
+    if (!o.given_rows_host) return fail(std::string(who_given) + ": given codes need their row table");
     return ts_given_rows_check(o.given_rows_host, lens_host, B);
 }
+
+// ---- a pass's sampler tables (sampler_host.cpp) -----------------------------------------------------------------------------
+// The host side of the per-clip sampling pieces of ONE pass (a mixed pass, a session step, a one-shot call with a table), in three steps:
+// build() checks what `o` brought, in one order for every caller, and leaves the device records here; the pass's owner then stages them
+// into its Work in stream order and binds its run configuration to the Work's buffers (pixelcnn.cpp: stage_sampler_tables,
+// bind_sampler_tables).  What differs between callers happens between the steps, on the vectors (a session makes from_row and the given
+// bounds absolute), never inside them.
+// The entries the messages of build() name: a table's faults, neutral records under a bias / under repetition records, a mask, given codes
+struct SamplerNames {
+    const char *ctl, *bias, *rep, *keep, *given;
+};
+inline SamplerNames sampler_names(const char *who) { return {who, who, who, who, who}; }   // an entry that names itself throughout
+struct SamplerTables {
+    int B = 0;
+    std::vector<SampleCtl> ctl;        // B records where a table, a bias or repetition records came (neutral ones without a table), else empty
+    std::vector<SampleRep> rep;        // B records where repetition records came
+    std::vector<int32_t> no_bias;      // B times -1 where repetition records came without bias tables: the index the samplers want
+    std::vector<int32_t> given_rows;   // a copy of o.given_rows_host where given codes came
+    // Launches nothing.  lens_host: the frames a clip's given rows must fit (>> 2), read only where given codes came
+    int build(const MixedOpts &o, int B, int V, int mode, const int32_t *lens_host, const SamplerNames &who);
+};
 
 }  // namespace ts

@@ -1214,50 +1214,52 @@ int ts_debug_code_table_stage(ts_pixelcnn *p, int which, const int32_t *tok, int
 }  // extern "C"
 
 namespace {
-
-// ---- sampling controls (talkshow_hip.h: ts_sampling) ------------------------------------------------------------------------------------
-// the rules of ts_sampling_check on one record; 0 or the message's tail
-const char *ctl_fault(const ts_sampling &r) {
-    if (!(r.temperature > 0.0f) || !std::isfinite(r.temperature)) return "temperature must be finite and > 0";
-    if (!std::isfinite(1.0f / r.temperature)) return "1 / temperature overflows fp32";
-    if (!(r.top_p > 0.0f) || !(r.top_p <= 1.0f)) return "top_p must be in (0, 1]";
-    if (r.top_k < 0) return "top_k must be >= 0 (0 or >= V: off)";
-    if (r.reserved != 0) return "reserved must be 0";
-    return nullptr;
-}
-int ctl_check(const ts_sampling *ctl, int n, int V, const char *who) {
-    if (!ctl || n < 1 || V < 1) return fail(std::string(who) + ": bad argument");
-    if (V > SAMPLE_CTL_MAX_V)
-        return fail(std::string(who) + ": sampling controls support vocabularies of at most " + std::to_string(SAMPLE_CTL_MAX_V) + " classes, got V = " + std::to_string(V));
-    for (int b = 0; b < n; ++b)
-        if (const char *m = ctl_fault(ctl[b])) return fail(std::string(who) + ": sampling record of clip " + std::to_string(b) + ": " + m);
-    return 0;
-}
-// validated host table -> the B device records of a pass (n_ctl = 1: one record for all clips); 1 / temperature is computed HERE, once, in fp32
-int ctl_table(const ts_sampling *ctl, int n_ctl, int B, int V, int mode, const char *who, std::vector<SampleCtl> &tab) {
-    if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
-        return fail(std::string(who) + ": sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1)");
-    if (n_ctl != 1 && n_ctl != B) return fail(std::string(who) + ": n_ctl must be 1 or B");
-    TS_TRY(ctl_check(ctl, n_ctl, V, who));
-    tab.resize(B);
-    for (int b = 0; b < B; ++b) {
-        const ts_sampling &r = ctl[n_ctl == 1 ? 0 : b];
-        tab[b] = SampleCtl{1.0f / r.temperature, r.top_p, r.top_k, 0};
-    }
-    return 0;
-}
-// The table reaches the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
-// synchronises, and any number of calls — each with its own table — may be queued behind each other.
+// ---- a pass's sampler tables (host_common.h: SamplerTables) behind their check: into the Work, then into the run configuration -------
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
 inline int sampler_bits(const RunCfg &c, const float *logprob) {
     const bool given = c.given_rows;
     return (c.ctl ? 1 : 0) | (logprob ? 2 : 0) | (given ? 4 : 0) | (given && c.keep_src ? 8 : 0) | (c.style ? 16 : 0) | (c.bias ? 32 : 0) | (c.rep ? 64 : 0);
 }
-int put_ctl_table(ts_ctx *ctx, ts_pixelcnn::Work *w, const std::vector<SampleCtl> &tab, hipStream_t s) {
-    static_assert(sizeof(SampleCtl) == 4 * sizeof(int), "SampleCtl is four words");
-    MiscScope ms(ctx, s);
-    TS_HIP(launch_put_words(w->ctl_tab.i(), reinterpret_cast<const int *>(tab.data()), (long)tab.size() * 4, s));
+// The tables reach the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
+// synchronises, and any number of calls — each with its own tables — may be queued behind each other.
+int stage_sampler_tables(ts_pixelcnn *p, ts_pixelcnn::Work *w, const SamplerTables &t, const MixedOpts &o, hipStream_t s) {
+    static_assert(sizeof(SampleCtl) == 4 * sizeof(int) && sizeof(SampleRep) == 4 * sizeof(int), "SampleCtl and SampleRep are four words");
+    ts_ctx *ctx = p->ctx;
+    const int B = t.B;
+    if (!t.ctl.empty()) {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w->ctl_tab.i(), reinterpret_cast<const int *>(t.ctl.data()), (long)B * 4, s));
+    }
+    if (o.bias) {   // n_bias <= B <= capB tables: the buffer follows capB alone (see Work::bias_tab), so it moves only when ensure_work has
+                    // dropped the graphs that read it (a session's capacity is fixed); the index travels as kernel arguments
+        TS_TRY(w->bias_tab.ensure((size_t)w->capB * 2 * p->V * sizeof(float)));
+        MiscScope ms(ctx, s);
+        TS_HIP(hipMemcpyAsync(w->bias_tab.p, o.bias, (size_t)o.n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
+        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), o.bias_index_host, B, s));
+    }
+    if (o.rep_host) {   // the records as kernel arguments, like the sampling table; a pass without tables brings the index the BIAS path wants
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(t.rep.data()), (long)B * 4, s));
+        if (!o.bias) TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), t.no_bias.data(), B, s));
+    }
+    if (o.given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w->given_tab.i(), t.given_rows.data(), B, s));
+    }
     return 0;
+}
+// Every table is indexed by the clip's slot in the pass (in a mixed pass the active clips are a prefix, so the slot is the same in every
+// chunk).  The given variants run in every chunk of a pass that brought given codes (one set of graph keys); which chunks stage codes, and
+// under which mask, is the caller's (given_stage, keep_src)
+void bind_sampler_tables(RunCfg &c, ts_pixelcnn::Work *w, const MixedOpts &o) {
+    if (o.ctl_host || o.bias || o.rep_host) c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
+    if (o.bias) c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+    if (o.rep_host) {   // records and rings; without tables the staged index is -1 everywhere and c.bias stays null
+        c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
+        c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
+        c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+    }
+    if (o.given) c.given_rows = w->given_tab.i(), c.given_src = o.given;
 }
 
 // audio conditioning of `rows` code rows per clip: AE = embedding_aud(aud); AEV / AEH = fusion_{v,h}[:, D:] . AE + bias;
@@ -1398,10 +1400,19 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
 // short last chunk serve every clip length.  The audio terms were computed for the whole call; a chunk's rows are copied into the
 // compact chunk buffers its graph reads.  Bit-identical to the whole-call graph (same launches, same order, same rings: only the
 // look-ahead partial sums of rows past the end are computed and never read).
-// rows [r0, r0 + Hc) of a call of out_H rows as one chunk: a 4-row token ring, the Work's compact chunk buffers for the audio terms
+
+// Rows [r0, r0 + Hc) behind a row cache, indexed absolutely: what a chunk of a one-shot call and a session step share.  The token ring
+// keeps 4 rows: layer 0 looks three code rows up; 4 also is the period of the Q ring.  The audio pointers are the caller's
+RunCfg ring_cfg(ts_pixelcnn::Work *w, int B, int r0, int Hc, int mode, uint64_t seed, int64_t clip0) {
+    return RunCfg{B, Hc, 0, r0 + Hc, mode, nullptr, seed, clip0, nullptr, nullptr, nullptr, w,
+                  /* ring */ 4, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
+}
+// a captured chunk is valid for every start row with the same buffer phases (parity of the per-layer row cache, slot in the 4-row
+// rings) and the same set of existing rows above (rows 0..2 have fewer): graphs are keyed on that, not on r0
+inline int ring_phase(int r0) { return r0 < 3 ? r0 : 3 + (r0 % 4); }
+// rows [r0, r0 + Hc) of a call of out_H rows as one chunk: the Work's compact chunk buffers for the audio terms
 RunCfg chunk_cfg(ts_pixelcnn::Work *w, int B, int r0, int Hc, int out_H, int mode, uint64_t seed, int64_t clip0) {
-    RunCfg c{B, Hc, 0, r0 + Hc, mode, nullptr, seed, clip0, nullptr, nullptr, nullptr, w,
-             /* ring */ 4, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
+    RunCfg c = ring_cfg(w, B, r0, Hc, mode, seed, clip0);
     c.aeh = w->cAEH.f(), c.aeh1 = w->cAEH1.f(), c.av1c = w->cAV1C.f(), c.av1p = w->cAV1P.f();
     c.out_H = out_H;
     c.out_row0 = r0;
@@ -1409,8 +1420,7 @@ RunCfg chunk_cfg(ts_pixelcnn::Work *w, int B, int r0, int Hc, int out_H, int mod
 }
 // the graph key of chunk `c` in a pass of Bs clip slots (0: a uniform call): its rows, the buffer phase of its first row, its samplers
 ts_pixelcnn::Work::Key chunk_key(const RunCfg &c, int Bs, const float *logprob) {
-    const int r0 = c.out_row0, phase = r0 < 3 ? r0 : 3 + (r0 % 4);
-    return std::make_tuple(c.B, c.H, -(1 + phase), c.mode, Bs, sampler_bits(c, logprob));
+    return std::make_tuple(c.B, c.H, -(1 + ring_phase(c.out_row0)), c.mode, Bs, sampler_bits(c, logprob));
 }
 // the chunk's rows of the whole call's audio terms (H rows per clip), for the first B clips, into the chunk buffers
 int stage_chunk_audio(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int r0, int Hc, int H, hipStream_t s) {
@@ -1484,18 +1494,9 @@ int run_mixed(ts_pixelcnn *p, ts_pixelcnn::Work *w, const MixedPass &a, const Mi
         RunCfg c = chunk_cfg(w, Ba, r0, Hc, H_max, a.mode, a.seed, 0);
         c.Bs = B;
         c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
-        // indexed by the clip's slot in the pass: the active clips are a prefix, so the slot is the same in every chunk
-        if (o.ctl_host || o.bias || o.rep_host) c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
-        if (o.bias) c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);   // by slot, too
-        if (o.rep_host) {   // records and rings by slot; without tables the index the caller staged is -1 everywhere and c.bias stays null
-            c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
-            c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
-            c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
-        }
-        if (o.given) {   // every chunk of the pass runs the given variants (one set of graph keys); only chunks with rows below max G stage codes
-            c.given_rows = w->given_tab.i();
-            c.given_src = o.given;
-            c.keep_src = o.keep;   // a masked pass runs the masked form in every chunk, too
+        bind_sampler_tables(c, w, o);
+        if (o.given) {   // only chunks with rows below max G stage codes; a masked pass runs the masked form in every chunk
+            c.keep_src = o.keep;
             c.given_stage = r0 < given_max;
         }
         if (tracked) {   // the chunk's conditioning rows, staged eagerly ahead of the replay like its uniforms and given codes: the only
@@ -1539,380 +1540,6 @@ int ts_debug_mixed_plan(const int32_t *hrows, int B, int max_counts, int32_t *ac
     return grid;
 }
 
-int ts_sampling_check(const ts_sampling *ctl_host, int n, int V) { return ctl_check(ctl_host, n, V, "ts_sampling_check"); }
-
-// the sampler with controls on given logits (ts_op_sample / ts_op_sample_philox with a table; kernel-level tests call it)
-int ts_op_sample_ctl(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
-                     uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, uint8_t *kept, void *stream) {
-    if (!ctl_host) return fail("ts_op_sample_ctl: a table is required (ts_op_sample / ts_op_sample_philox are the entries without one)");
-    return ts_op_sample_lp(ctx, logits, B, V, mode, uniforms, seed, clip_index0, position, ctl_host, n_ctl, idx, kept, nullptr, stream);
-}
-
-// one sampler launch on given logits, with the log-probability of every row's code (kernel-level tests call it).  Without a table: any of
-// the four modes through sample_lp_kernel (sample_kernel when logprob is NULL); teacher forced reads idx.  With one: ts_op_sample_ctl's launch.
-int ts_op_sample_lp(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
-                    uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, uint8_t *kept, float *logprob, void *stream) {
-    const char *who = logprob ? "ts_op_sample_lp" : "ts_op_sample_ctl";
-    if (!ctx || !logits || !idx) return fail(std::string(who) + ": null argument");
-    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
-    if (mode < 0 || mode > TS_TEACHER_FORCED) return fail(std::string(who) + ": bad mode");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
-    hipStream_t s = (hipStream_t)stream;
-    if (!ctl_host) {
-        if (kept) return fail(std::string(who) + ": kept_dev needs a table");
-        DevBuf tok;
-        TS_TRY(tok.ensure((size_t)B * sizeof(int)));
-        SampleLpParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.s.logits = logits;
-        q.s.B = B;
-        q.s.V = V;
-        q.s.mode = mode;
-        q.s.uniforms = uniforms;
-        q.s.u_stride = 1;
-        q.s.seed = seed;
-        q.s.clip_index0 = clip_index0;
-        q.s.position = position;
-        q.s.tok32 = tok.i();
-        q.s.tok_stride = 1;
-        q.s.codes = idx;
-        q.s.code_stride = 1;
-        q.logprob = logprob;
-        q.lp_stride = 1;
-        if (logprob) TS_HIP(launch_sample_lp(q, s));
-        else TS_HIP(launch_sample(q.s, s));
-        TS_HIP(hipStreamSynchronize(s));
-        return 0;
-    }
-    std::vector<SampleCtl> tab;
-    TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, who, tab));
-    DevBuf tok, dtab;
-    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
-    TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
-    TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
-    SampleCtlParams cp;
-    std::memset(&cp, 0, sizeof(cp));
-    cp.s.logits = logits;
-    cp.s.B = B;
-    cp.s.V = V;
-    cp.s.mode = mode;
-    cp.s.uniforms = uniforms;
-    cp.s.u_stride = 1;
-    cp.s.seed = seed;
-    cp.s.clip_index0 = clip_index0;
-    cp.s.position = position;
-    cp.s.tok32 = tok.i();
-    cp.s.tok_stride = 1;
-    cp.s.codes = idx;
-    cp.s.code_stride = 1;
-    cp.ctl = static_cast<const SampleCtl *>(dtab.p);
-    cp.kept = kept;
-    cp.logprob = logprob;
-    cp.lp_stride = 1;
-    TS_HIP(launch_sample_ctl(cp, s));
-    TS_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
-// one launch of the samplers' given variants on given logits (kernel-level tests call it): row b is forced iff forced_host[b] != 0
-int ts_op_sample_given(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
-                       uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *forced_host,
-                       const int64_t *given, void *stream) {
-    const char *who = "ts_op_sample_given";
-    if (!ctx || !logits || !idx || !forced_host || !given) return fail(std::string(who) + ": null argument");
-    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
-    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
-    if (position > 0x7ffffff0u) return fail(std::string(who) + ": position too large for a row table");
-    std::vector<SampleCtl> tab;
-    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, who, tab));
-    // the kernels force a workgroup whose position is below 2 G: G = position / 2 + 1 forces row b at this position, G = 0 never does
-    std::vector<int> rows(B);
-    for (int b = 0; b < B; ++b) rows[b] = forced_host[b] ? (int)(position / 2) + 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    DevBuf tok, dtab, drows;
-    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
-    TS_TRY(drows.ensure((size_t)B * sizeof(int)));
-    TS_HIP(launch_put_words(drows.i(), rows.data(), B, s));
-    if (ctl_host) {
-        TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
-        TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
-    }
-    SampleGivenParams gp;
-    std::memset(&gp, 0, sizeof(gp));
-    gp.c.s.logits = logits;
-    gp.c.s.B = B;
-    gp.c.s.V = V;
-    gp.c.s.mode = mode;
-    gp.c.s.uniforms = uniforms;
-    gp.c.s.u_stride = 1;
-    gp.c.s.seed = seed;
-    gp.c.s.clip_index0 = clip_index0;
-    gp.c.s.position = position;
-    gp.c.s.tok32 = tok.i();
-    gp.c.s.tok_stride = 1;
-    gp.c.s.codes = idx;
-    gp.c.s.code_stride = 1;
-    gp.c.ctl = ctl_host ? static_cast<const SampleCtl *>(dtab.p) : nullptr;
-    gp.c.logprob = logprob;
-    gp.c.lp_stride = 1;
-    gp.rows = drows.i();
-    gp.given = given;
-    gp.given_stride = 1;
-    TS_HIP(launch_sample_given(gp, s));
-    TS_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
-// Host only: what ts_op_sample_keep refuses before it touches the device
-static int op_sample_keep_check(const void *ctx, const void *logits, int B, int V, int mode, const void *uniforms, uint32_t position, const void *idx,
-                            const int32_t *given_rows_host, const void *given) {
-    const char *who = "ts_op_sample_keep";
-    if (!ctx || !logits || !idx || !given_rows_host || !given) return fail(std::string(who) + ": null argument");
-    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
-    if (mode != TS_SAMPLE_GREEDY && mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX) return fail(std::string(who) + ": bad mode");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
-    if (position > 0x7ffffff0u) return fail(std::string(who) + ": position too large for a row table");
-    for (int b = 0; b < B; ++b)
-        if (given_rows_host[b] < 0) return fail(std::string(who) + ": given rows of row " + std::to_string(b) + " are negative");
-    return 0;
-}
-
-// one launch of the samplers' given variants on given logits with the DEVICE-side decision exercised (kernel-level tests call it): row b is
-// forced iff position < 2 given_rows_host[b] and (keep == NULL or keep[b] != 0)
-int ts_op_sample_keep(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
-                      uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
-                      const uint8_t *keep, const int64_t *given, void *stream) {
-    const char *who = "ts_op_sample_keep";
-    TS_TRY(op_sample_keep_check(ctx, logits, B, V, mode, uniforms, position, idx, given_rows_host, given));
-    std::vector<SampleCtl> tab;
-    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, V, mode, who, tab));
-    hipStream_t s = (hipStream_t)stream;
-    DevBuf tok, dtab, drows;
-    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
-    TS_TRY(drows.ensure((size_t)B * sizeof(int)));
-    TS_HIP(launch_put_words(drows.i(), given_rows_host, B, s));
-    if (ctl_host) {
-        TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
-        TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
-    }
-    SampleGivenParams gp;
-    std::memset(&gp, 0, sizeof(gp));
-    gp.c.s.logits = logits;
-    gp.c.s.B = B;
-    gp.c.s.V = V;
-    gp.c.s.mode = mode;
-    gp.c.s.uniforms = uniforms;
-    gp.c.s.u_stride = 1;
-    gp.c.s.seed = seed;
-    gp.c.s.clip_index0 = clip_index0;
-    gp.c.s.position = position;
-    gp.c.s.tok32 = tok.i();
-    gp.c.s.tok_stride = 1;
-    gp.c.s.codes = idx;
-    gp.c.s.code_stride = 1;
-    gp.c.ctl = ctl_host ? static_cast<const SampleCtl *>(dtab.p) : nullptr;
-    gp.c.logprob = logprob;
-    gp.c.lp_stride = 1;
-    gp.rows = drows.i();
-    gp.given = given;
-    gp.given_stride = 1;
-    gp.keep = keep;
-    gp.keep_stride = 1;
-    TS_HIP(launch_sample_given(gp, s));
-    TS_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
-// Host only ("code bias"): tables (n_tables,2,V) — every entry -inf or finite with |b| <= 1e30 (no NaN, no +inf), every row with at least
-// one entry above -inf, V within the controls' limit; the message names the table, the column and the code
-int ts_code_bias_check(const float *tables_host, int n_tables, int V) {
-    if (!tables_host || n_tables < 1 || V < 1) return fail("ts_code_bias_check: bad argument");
-    if (V > SAMPLE_CTL_MAX_V)
-        return fail("ts_code_bias_check: a code bias supports vocabularies of at most " + std::to_string(SAMPLE_CTL_MAX_V) + " classes, got V = " +
-                    std::to_string(V));
-    static const char *const col[2] = {"body", "hand"};
-    for (int t = 0; t < n_tables; ++t)
-        for (int j = 0; j < 2; ++j) {
-            const float *row = tables_host + ((size_t)t * 2 + j) * V;
-            const std::string where = "ts_code_bias_check: table " + std::to_string(t) + ", " + col[j] + " column";
-            bool any = false;
-            for (int v = 0; v < V; ++v) {
-                const float x = row[v];
-                if (std::isnan(x)) return fail(where + ": the bias of code " + std::to_string(v) + " is NaN");
-                if (std::isinf(x)) {
-                    if (x > 0) return fail(where + ": the bias of code " + std::to_string(v) + " is +inf (only -inf, a ban, is allowed)");
-                    continue;
-                }
-                if (std::fabs(x) > 1e30f) return fail(where + ": the bias of code " + std::to_string(v) + " exceeds 1e30 in magnitude");
-                any = true;
-            }
-            if (!any) return fail(where + ": every code is banned (-inf); a column needs at least one code it may use");
-        }
-    return 0;
-}
-
-namespace {
-// n_rep (1 or B) checked records -> one device record per clip slot
-int rep_table(const ts_repeat *rep_host, int n_rep, int B, int V, const char *who, std::vector<SampleRep> &tab) {
-    if (n_rep != 1 && n_rep != B)
-        return fail(std::string(who) + ": a pass of " + std::to_string(B) + " clips brings 1 or " + std::to_string(B) + " repetition records, got " +
-                    std::to_string(n_rep));
-    TS_TRY(ts_repeat_check(rep_host, n_rep, V));
-    tab.resize(B);
-    for (int b = 0; b < B; ++b) {
-        const ts_repeat &r = rep_host[n_rep == 1 ? 0 : b];
-        tab[b] = SampleRep{r.window, r.presence, r.frequency, 0};
-    }
-    return 0;
-}
-}  // namespace
-
-// ts_op_sample_keep's launch under a "code bias" (kernel-level tests call it): bias (n_bias,2,V) device tables, bias_index_host (B,) the
-// table of every row or -1, column 0 / 1.  Without a sampling table the rows run on neutral records.  given_rows_host == NULL: no given
-// rows (sample_ctl_bias_kernel; given, keep unused); otherwise the given variant.  kept (optional, (B,V)): the kept bytes
-int ts_op_sample_bias(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
-                      uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
-                      const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
-                      const int32_t *bias_index_host, int column, void *stream) {
-    if (!bias || !bias_index_host) return fail("ts_op_sample_bias: null argument");
-    return ts_op_sample_repeat(ctx, logits, B, V, mode, uniforms, seed, clip_index0, position, ctl_host, n_ctl, idx, logprob, given_rows_host, keep,
-                               given, kept, logits_copy, bias, n_bias, bias_index_host, column, nullptr, 0, nullptr, nullptr, stream);
-}
-
-// The same launch under a "repetition penalty" (kernel-level tests call it): rep_host n_rep (1 or B) records; history (B,R) int32 on the
-// device, R = min(position >> 1, 64), the codes of rows (position >> 1) - R .. (position >> 1) - 1 of this column, oldest first; ring_out
-// (B,64) int32 or NULL.  The entry fills rings of -1, places the history where a pass would have left it (row r at r & 63), launches once
-// and copies every row's ring of this column out.  bias == NULL: no tables (an index of -1 everywhere).  rep_host == NULL: ts_op_sample_bias
-int ts_op_sample_repeat(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
-                        uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
-                        const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
-                        const int32_t *bias_index_host, int column, const ts_repeat *rep_host, int n_rep, const int32_t *history,
-                        int32_t *ring_out, void *stream) {
-    const char *who = rep_host ? "ts_op_sample_repeat" : "ts_op_sample_bias";
-    if (!ctx || !logits || !idx || (bias && !bias_index_host) || (!bias && !rep_host)) return fail(std::string(who) + ": null argument");
-    const int hist_rows = (int)std::min<uint32_t>(position >> 1, (uint32_t)SAMPLE_REP_RING);
-    if (rep_host && hist_rows > 0 && !history) return fail(std::string(who) + ": rows behind row 0 need their history");
-    if (!rep_host && (history || ring_out)) return fail(std::string(who) + ": a history and a ring output need records");
-    if (B < 1 || V < 1) return fail(std::string(who) + ": bad shape");
-    if (column != 0 && column != 1) return fail(std::string(who) + ": column is 0 (body) or 1 (hand)");
-    if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail(std::string(who) + ": uniforms required");
-    if (given_rows_host) {
-        if (!given) return fail(std::string(who) + ": given rows need their codes");
-        if (position > 0x7ffffff0u) return fail(std::string(who) + ": position too large for a row table");
-        for (int b = 0; b < B; ++b)
-            if (given_rows_host[b] < 0) return fail(std::string(who) + ": given rows of row " + std::to_string(b) + " are negative");
-    } else if (keep || given) {
-        return fail(std::string(who) + ": given codes and their mask need the row table");
-    }
-    std::vector<SampleCtl> tab;
-    const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
-    TS_TRY(ctl_table(ctl_host ? ctl_host : &neutral, ctl_host ? n_ctl : 1, B, V, mode, who, tab));   // refuses greedy and teacher forced
-    if (bias) TS_TRY(ts_code_bias_index_check(bias_index_host, B, n_bias));
-    std::vector<SampleRep> rtab;
-    if (rep_host) TS_TRY(rep_table(rep_host, n_rep, B, V, who, rtab));
-    hipStream_t s = (hipStream_t)stream;
-    DevBuf tok, dtab, drows, dbi, drep, dring;
-    TS_TRY(tok.ensure((size_t)B * sizeof(int)));
-    TS_TRY(dtab.ensure((size_t)B * sizeof(SampleCtl)));
-    TS_TRY(dbi.ensure((size_t)B * sizeof(int32_t)));
-    TS_HIP(launch_put_words(dtab.i(), reinterpret_cast<const int *>(tab.data()), (long)B * 4, s));
-    const std::vector<int32_t> none(B, -1);
-    TS_HIP(launch_put_words(dbi.i(), bias ? bias_index_host : none.data(), B, s));
-    const size_t ring_pitch = (size_t)2 * SAMPLE_REP_RING * sizeof(int32_t);   // one clip's two rings
-    if (rep_host) {
-        TS_TRY(drep.ensure((size_t)B * sizeof(SampleRep)));
-        TS_TRY(dring.ensure((size_t)B * ring_pitch));
-        TS_HIP(launch_put_words(drep.i(), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
-        TS_HIP(hipMemsetAsync(dring.p, 0xff, (size_t)B * ring_pitch, s));
-        // rows r - R .. r - 1 are consecutive ring slots modulo 64: one or two strided copies
-        const uint32_t first = (position >> 1) - (uint32_t)hist_rows;
-        for (int done = 0; done < hist_rows;) {
-            const int slot = (int)((first + (uint32_t)done) & (uint32_t)(SAMPLE_REP_RING - 1));
-            const int n = std::min(hist_rows - done, SAMPLE_REP_RING - slot);
-            TS_HIP(hipMemcpy2DAsync(dring.i() + (size_t)column * SAMPLE_REP_RING + slot, ring_pitch, history + done,
-                                    (size_t)hist_rows * sizeof(int32_t), (size_t)n * sizeof(int32_t), B, hipMemcpyDeviceToDevice, s));
-            done += n;
-        }
-    }
-    SampleGivenParams gp;
-    std::memset(&gp, 0, sizeof(gp));
-    gp.c.s.logits = logits;
-    gp.c.s.B = B;
-    gp.c.s.V = V;
-    gp.c.s.mode = mode;
-    gp.c.s.uniforms = uniforms;
-    gp.c.s.u_stride = 1;
-    gp.c.s.seed = seed;
-    gp.c.s.clip_index0 = clip_index0;
-    gp.c.s.position = position;
-    gp.c.s.tok32 = tok.i();
-    gp.c.s.tok_stride = 1;
-    gp.c.s.codes = idx;
-    gp.c.s.code_stride = 1;
-    gp.c.s.logits_copy = logits_copy;
-    gp.c.s.copy_stride = V;
-    gp.c.ctl = static_cast<const SampleCtl *>(dtab.p);
-    gp.c.kept = kept;
-    gp.c.logprob = logprob;
-    gp.c.lp_stride = 1;
-    gp.c.bias = bias;
-    gp.c.bias_index = static_cast<const int32_t *>(dbi.p);
-    gp.c.bias_col = column;
-    if (rep_host) {
-        gp.c.rep = static_cast<const SampleRep *>(drep.p);
-        gp.c.rep_ring = dring.i();
-    }
-    if (given_rows_host) {
-        TS_TRY(drows.ensure((size_t)B * sizeof(int)));
-        TS_HIP(launch_put_words(drows.i(), given_rows_host, B, s));
-        gp.rows = drows.i();
-        gp.given = given;
-        gp.given_stride = 1;
-        gp.keep = keep;
-        gp.keep_stride = 1;
-        TS_HIP(launch_sample_given(gp, s));
-    } else {
-        TS_HIP(launch_sample_ctl(gp.c, s));
-    }
-    if (rep_host && ring_out)
-        TS_HIP(hipMemcpy2DAsync(ring_out, (size_t)SAMPLE_REP_RING * sizeof(int32_t), dring.i() + (size_t)column * SAMPLE_REP_RING, ring_pitch,
-                                (size_t)SAMPLE_REP_RING * sizeof(int32_t), B, hipMemcpyDeviceToDevice, s));
-    TS_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
-// Host only ("speaker style"): every weight of a style block is finite; the first bad index is named
-int ts_style_check(const float *w_host, long n, int NC) {
-    if (!w_host || n < 0 || NC < 1) return fail("ts_style_check: bad argument");
-    for (long i = 0; i < n; ++i)
-        if (!std::isfinite(w_host[i]))
-            return fail("ts_style_check: weight " + std::to_string(i) + " (row " + std::to_string(i / NC) + ", speaker " + std::to_string(i % NC) +
-                        ") is not finite");
-    return 0;
-}
-
-// style_rows_kernel on its own (kernel-level tests call it): tables (NL,NC,W), weights (M,NC) -> out (NL,M,W), row m from weight row m.
-// Run as ONE clip slot with a track of M rows, so the kernel's row indexing is what is exercised
-int ts_op_style_rows(ts_ctx *ctx, const float *tables, int NL, int NC, int W, const float *weights, int M, float *out, void *stream) {
-    if (!ctx || !tables || !weights || !out) return fail("ts_op_style_rows: null argument");
-    if (NL < 1 || NC < 1 || M < 1 || W < 4 || W % 4) return fail("ts_op_style_rows: bad shape (W is a positive multiple of 4)");
-    hipStream_t s = (hipStream_t)stream;
-    StyleRowsParams q;
-    std::memset(&q, 0, sizeof(q));
-    q.tables = tables;
-    q.weights = weights;
-    q.w_ld = NC;
-    q.S = M, q.NC = NC, q.W = W, q.NL = NL;
-    q.r0 = 0, q.n = M, q.slots = 1;
-    q.out = out;
-    q.out_l_stride = (long)M * W;
-    q.out_r_stride = W;
-    TS_HIP(launch_style_rows(q, s));
-    TS_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
 int ts_pixelcnn_generate_mixed_ctl(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
                                    int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
                                    int64_t *codes, const ts_sampling *ctl_host, int n_ctl, void *stream) {
@@ -1929,17 +1556,6 @@ int ts_pixelcnn_generate_mixed_lp(ts_pixelcnn *p, const int64_t *label, const fl
     o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
     return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
-
-// Host only: the rule every _given entry applies to its row table before anything is launched
-int ts_given_rows_check(const int32_t *given_rows_host, const int32_t *lens_host, int B) {
-    if (!given_rows_host || !lens_host || B < 1) return fail("ts_given_rows_check: bad argument");
-    for (int b = 0; b < B; ++b)
-        if (given_rows_host[b] < 0 || given_rows_host[b] > (lens_host[b] >> 2))
-            return fail("given rows of clip " + std::to_string(b) + ": G = " + std::to_string(given_rows_host[b]) + " must be in [0, " +
-                        std::to_string(lens_host[b] >> 2) + "], the clip's own code rows");
-    return 0;
-}
-
 // the mixed pass in which clip b brings given_rows[b] code rows that are taken, not drawn (talkshow_hip.h, "given rows"); given == NULL: the
 // _lp entry, launch for launch
 int ts_pixelcnn_generate_mixed_given(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
@@ -1978,20 +1594,6 @@ int ts_pixelcnn_generate_mixed_style(ts_pixelcnn *p, const int64_t *label, const
     o.style = style, o.style_rows = style_rows;
     return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
-
-// Host only ("code bias"): what every entry that takes tables checks of their number and of the index table before anything is launched
-int ts_code_bias_index_check(const int32_t *bias_index_host, int B, int n_bias) {
-    if (!bias_index_host || B < 1) return fail("ts_code_bias_index_check: bad argument");
-    if (n_bias < 1 || n_bias > B)
-        return fail("code bias: a pass of " + std::to_string(B) + " clips brings 1 to " + std::to_string(B) + " tables (shared tables travel once), got " +
-                    std::to_string(n_bias));
-    for (int b = 0; b < B; ++b)
-        if (bias_index_host[b] < -1 || bias_index_host[b] >= n_bias)
-            return fail("code bias: the table index of clip " + std::to_string(b) + " is " + std::to_string(bias_index_host[b]) + ", not -1 (none) or in [0, " +
-                        std::to_string(n_bias) + ")");
-    return 0;
-}
-
 // the same pass under a "code bias" (talkshow_hip.h): bias_dev (n_bias,2,V) fp32 tables on the device, bias_index_host (B,) the table of every
 // clip in slot order or -1.  Tables and index are copied into the Work in stream order ahead of the pass; the samplers are the
 // sample_ctl_bias kernels on graph keys of their own (bit 5); a call without a sampling table runs on neutral records.  bias_dev == NULL:
@@ -2007,31 +1609,6 @@ int ts_pixelcnn_generate_mixed_bias(ts_pixelcnn *p, const int64_t *label, const 
     o.style = style, o.style_rows = style_rows, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
     return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
-
-// Host only ("repetition penalty"): n records — window in [0, 64], presence and frequency finite with |x| <= 1e30, reserved 0 — for a
-// vocabulary within the controls' limit; the message names the clip
-int ts_repeat_check(const ts_repeat *rep_host, int n, int V) {
-    if (!rep_host || n < 1 || V < 1) return fail("ts_repeat_check: bad argument");
-    if (V > SAMPLE_CTL_MAX_V)
-        return fail("ts_repeat_check: a repetition penalty supports vocabularies of at most " + std::to_string(SAMPLE_CTL_MAX_V) +
-                    " classes, got V = " + std::to_string(V));
-    for (int b = 0; b < n; ++b) {
-        const ts_repeat &r = rep_host[b];
-        const std::string where = "ts_repeat_check: clip " + std::to_string(b);
-        if (r.window < 0 || r.window > TS_REPEAT_MAX_WINDOW)
-            return fail(where + ": window " + std::to_string(r.window) + " is outside [0, " + std::to_string(TS_REPEAT_MAX_WINDOW) + "]");
-        const float v[2] = {r.presence, r.frequency};
-        static const char *const name[2] = {"presence", "frequency"};
-        for (int k = 0; k < 2; ++k) {
-            if (std::isnan(v[k])) return fail(where + ": " + name[k] + " is NaN");
-            if (std::isinf(v[k])) return fail(where + ": " + name[k] + " is infinite");
-            if (std::fabs(v[k]) > 1e30f) return fail(where + ": " + name[k] + " exceeds 1e30 in magnitude");
-        }
-        if (r.reserved != 0) return fail(where + ": the reserved word is " + std::to_string(r.reserved) + ", not 0");
-    }
-    return 0;
-}
-
 // the same pass under a "repetition penalty" (talkshow_hip.h): rep_host n_rep (1 or B) records in slot order.  The records are copied into the
 // Work in stream order ahead of the pass (kernel arguments, like the sampling table); the samplers are the sample_ctl_rep kernels on graph
 // keys of their own (bit 6), which keep every slot's history in Work::rep_ring; a call without a sampling table runs on neutral records, a
@@ -2070,41 +1647,14 @@ int ts::pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPas
         hrows[b] = a.lens_host[b] >> 2;
         if (hrows[b] > H_max) return fail("ts_pixelcnn_generate_mixed: clip " + std::to_string(b) + " has more code rows than H_max");
     }
-    std::vector<SampleCtl> tab;
-    if (o.ctl_host) TS_TRY(ctl_table(o.ctl_host, o.n_ctl, B, p->V, mode, "ts_pixelcnn_generate_mixed_ctl", tab));   // before anything is launched
-    if (o.bias || o.rep_host) {   // sampling controls with the table's scope; without a table the pass runs on neutral records (the plain sampler's bits)
-        if (!o.ctl_host) {
-            const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
-            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, o.rep_host ? "ts_pixelcnn_generate_mixed_repeat" : "ts_pixelcnn_generate_mixed_bias", tab));
-        }
-        if (o.bias) TS_TRY(ts_code_bias_index_check(o.bias_index_host, B, o.n_bias));
-    }
-    std::vector<SampleRep> rtab;
-    if (o.rep_host) TS_TRY(rep_table(o.rep_host, o.n_rep, B, p->V, "ts_pixelcnn_generate_mixed_repeat", rtab));
-    TS_TRY(mixed_given_check("ts_pixelcnn_generate_mixed", o, a.lens_host, B));
+    SamplerTables t;
+    TS_TRY(t.build(o, B, p->V, mode, a.lens_host,
+                   {"ts_pixelcnn_generate_mixed_ctl", "ts_pixelcnn_generate_mixed_bias", "ts_pixelcnn_generate_mixed_repeat",
+                    "ts_pixelcnn_generate_mixed_keep", "ts_pixelcnn_generate_mixed_given"}));
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));
-    if (o.ctl_host || o.bias || o.rep_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
-    if (o.bias) {   // n_bias <= B <= capB tables: the buffer follows capB alone (see Work::bias_tab); the index travels as kernel arguments
-        TS_TRY(w->bias_tab.ensure((size_t)w->capB * 2 * p->V * sizeof(float)));
-        MiscScope ms(ctx, s);
-        TS_HIP(hipMemcpyAsync(w->bias_tab.p, o.bias, (size_t)o.n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
-        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), o.bias_index_host, B, s));
-    }
-    if (o.rep_host) {   // the records as kernel arguments, like the sampling table; a pass without tables brings the index the BIAS path wants
-        static_assert(sizeof(SampleRep) == 4 * sizeof(int), "SampleRep is four words");
-        MiscScope ms(ctx, s);
-        TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
-        if (!o.bias) {
-            const std::vector<int32_t> none(B, -1);
-            TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), none.data(), B, s));
-        }
-    }
-    if (o.given) {   // stream-ordered, as kernel arguments: the host table is free when the call returns
-        MiscScope ms(ctx, s);
-        TS_HIP(launch_put_words(w->given_tab.i(), o.given_rows_host, B, s));
-    }
+    TS_TRY(stage_sampler_tables(p, w, t, o, s));
     TS_TRY(audio_terms(p, w, aud, B, H_max, s));
     if (tracked) {   // sized with the Work's clip capacity, so it moves only when ensure_work has dropped the graphs that read it
                      // (its size follows capB alone, and no graph reads it before its first allocation)
@@ -2151,21 +1701,23 @@ int ts_pixelcnn_generate_lp(ts_pixelcnn *p, const int64_t *label, const float *a
     if (mode < 0 || mode > TS_TEACHER_FORCED) return fail("ts_pixelcnn_generate: bad mode");
     if (mode == TS_SAMPLE_UNIFORMS && !uniforms) return fail("ts_pixelcnn_generate: uniforms required");
     if (H0 > 0 && (!pre_codes || !pre_aud)) return fail("ts_pixelcnn_generate: prefix pointers required");
-    std::vector<SampleCtl> tab;
-    if (ctl_host) TS_TRY(ctl_table(ctl_host, n_ctl, B, p->V, mode, "ts_pixelcnn_generate_ctl", tab));   // before anything is launched
+    const char *who = "ts_pixelcnn_generate_ctl";
+    MixedOpts o;   // a one-shot call takes the table alone
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl;
+    SamplerTables t;
+    TS_TRY(t.build(o, B, p->V, mode, nullptr, sampler_names(who)));
     hipStream_t s = (hipStream_t)stream;
     ts_ctx *ctx = p->ctx;
     const int Htot = H0 + H, AD = p->AD;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, Htot));
-    if (ctl_host) TS_TRY(put_ctl_table(ctx, w, tab, s));
-    const SampleCtl *ctl = ctl_host ? static_cast<const SampleCtl *>(w->ctl_tab.p) : nullptr;
+    TS_TRY(stage_sampler_tables(p, w, t, o, s));
 
     // eager launches remain for the instrumented / logits-returning / teacher-forced paths (teacher forced with log-probabilities too: it
     // runs the horizontal stack, see need_h in run_rows, as eager launches)
     const bool graph = p->use_graph && !ctx->prof.on && !logits && mode != TS_TEACHER_FORCED;
     RunCfg c = one_shot_cfg(B, H, H0, mode, uniforms, seed, clip0, codes, logits, w);
-    c.ctl = ctl;
+    bind_sampler_tables(c, w, o);
 
     const float *aud_all = aud;
     if (H0 > 0) {
@@ -2196,7 +1748,7 @@ int ts_pixelcnn_generate_lp(ts_pixelcnn *p, const int64_t *label, const float *a
     // hot (Work::hot: pinned by ts_pixelcnn_prepare, or its third sighting among the last 16 one-shot calls of this stream); then it gets
     // its own whole-call graph (one replay per call: the serving loops, bench.py).  The cache is bounded either way.
     if (graph && H0 == 0 && H > CHUNK_ROWS && !w->graphs.count(key) && !w->hot(key))
-        return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, ctl, logprob, s);
+        return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, c.ctl, logprob, s);
     return run_rows(p, c, 0, Htot, graph, key, uniforms, codes, logprob, s);
 }
 
@@ -2271,71 +1823,23 @@ int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, cons
     ts_pixelcnn::Work *w = &st->w;
     const int B = st->B, r0 = (int)st->rows;
     const char *who = "ts_pixelcnn_stream_step_ctl";
-    std::vector<SampleCtl> tab;
-    if (o.ctl_host) TS_TRY(ctl_table(o.ctl_host, o.n_ctl, B, p->V, mode, who, tab));
-    if (o.bias || o.rep_host) {   // the rules of the mixed entry: the table's scope, neutral records where the step brought none
-        if (!o.ctl_host) {
-            const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
-            TS_TRY(ctl_table(&neutral, 1, B, p->V, mode, who, tab));
-        }
-        if (o.bias) TS_TRY(ts_code_bias_index_check(o.bias_index_host, B, o.n_bias));
-    }
-    std::vector<SampleRep> rtab;
+    const std::vector<int32_t> lens(B, 4 * Hc);   // the rules of the mixed entry, on a pass of B clips of Hc rows
+    SamplerTables t;
+    TS_TRY(t.build(o, B, p->V, mode, lens.data(), sampler_names(who)));
     std::vector<int32_t> rep_from(B, -1);   // the session's table behind this step, kept only if the step is queued
-    if (o.rep_host) {
-        TS_TRY(rep_table(o.rep_host, o.n_rep, B, p->V, who, rtab));
-        for (int b = 0; b < B; ++b)
-            if (rtab[b].window > 0) rtab[b].from_row = rep_from[b] = st->rep_from[b] >= 0 ? st->rep_from[b] : r0;
-    }
-    std::vector<int32_t> gtab;
-    if (o.given) {   // the table the samplers read holds absolute bounds: clip b is forced at positions below 2 (r0 + g_b)
-        if (!o.given_rows_host) return fail(std::string(who) + ": given codes need their row table");
-        const std::vector<int32_t> lens(B, 4 * Hc);
-        TS_TRY(ts_given_rows_check(o.given_rows_host, lens.data(), B));
-        gtab.resize(B);
-        for (int b = 0; b < B; ++b) gtab[b] = r0 + o.given_rows_host[b];
-    }
-    constexpr int RING = 4;   // token rows kept: layer 0 looks three code rows up; 4 also is the period of the Q ring
+    for (size_t b = 0; b < t.rep.size(); ++b)
+        if (t.rep[b].window > 0) t.rep[b].from_row = rep_from[b] = st->rep_from[b] >= 0 ? st->rep_from[b] : r0;
+    for (int32_t &g : t.given_rows) g += r0;   // the table the samplers read holds absolute bounds: clip b is forced at positions below 2 (r0 + g_b)
     if (r0 == 0 && !o.style) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
     if (o.style) TS_TRY(class_rows_style(p, w, o.style, B, s));   // CR stays as written until a later step brings other rows
-    RunCfg c{B, Hc, 0, r0 + Hc, mode, nullptr, seed, clip0, nullptr, nullptr, nullptr, w,
-             RING, r0, Hc, r0, r0, 2l * r0, 0x7fffffff};
-    c.audio_from(w);
-    if (o.ctl_host || o.bias || o.rep_host) {
-        TS_TRY(put_ctl_table(ctx, w, tab, s));
-        c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
-    }
-    if (o.bias) {   // sized by the session's fixed clip capacity at the first biased step: it never moves, and no graph read it before
-        TS_TRY(w->bias_tab.ensure((size_t)w->capB * 2 * p->V * sizeof(float)));
-        MiscScope ms(ctx, s);
-        TS_HIP(hipMemcpyAsync(w->bias_tab.p, o.bias, (size_t)o.n_bias * 2 * p->V * sizeof(float), hipMemcpyDeviceToDevice, s));
-        TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), o.bias_index_host, B, s));
-        c.bias = w->bias_tab.f(), c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
-    }
-    if (o.rep_host) {
-        MiscScope ms(ctx, s);
-        TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(rtab.data()), (long)B * 4, s));
-        if (!o.bias) {
-            const std::vector<int32_t> none(B, -1);
-            TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), none.data(), B, s));
-        }
-        c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
-        c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
-        c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
-    }
-    if (o.given) {
-        MiscScope ms(ctx, s);
-        TS_HIP(launch_put_words(w->given_tab.i(), gtab.data(), B, s));
-        c.given_rows = w->given_tab.i();
-        c.given_src = o.given;
-        c.given_stage = true;
-    }
+    RunCfg c = ring_cfg(w, B, r0, Hc, mode, seed, clip0);
+    c.audio_from(w);   // a step's audio terms are the Work's whole buffers
+    TS_TRY(stage_sampler_tables(p, w, t, o, s));
+    bind_sampler_tables(c, w, o);
+    c.given_stage = true;   // a step's given block is staged whole
     TS_TRY(audio_terms(p, w, aud, B, Hc, s));
-    // a captured chunk is valid for every start row with the same buffer phases (parity of the per-layer row cache, slot
-    // in the 4-row rings) and the same set of existing rows above (rows 0..2 have fewer): key on that, not on r0
-    const int phase = r0 < 3 ? r0 : 3 + (r0 % 4);
     const bool graph = p->use_graph && !ctx->prof.on;
-    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + phase, mode, 0, sampler_bits(c, o.logprob)), uniforms, codes,
+    TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + ring_phase(r0), mode, 0, sampler_bits(c, o.logprob)), uniforms, codes,
                     o.logprob, s));
     st->rep_from.swap(rep_from);
     st->rows += Hc;
@@ -2365,14 +1869,4 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud, int Hc
 }
 
 int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st) { return st ? st->w.captures : -1; }
-
-// Host only (tests): the device records rep_table makes of n_rep (1 or B) public records, four 32-bit words per clip slot into words_out
-int ts_debug_rep_table(const ts_repeat *rep_host, int n_rep, int B, int V, int32_t *words_out) {
-    if (!rep_host || !words_out || B < 1) return fail("ts_debug_rep_table: bad argument");
-    std::vector<SampleRep> tab;
-    TS_TRY(rep_table(rep_host, n_rep, B, V, "ts_debug_rep_table", tab));
-    std::memcpy(words_out, tab.data(), (size_t)B * sizeof(SampleRep));
-    return 0;
-}
-
 }  // extern "C"
