@@ -23,10 +23,24 @@
  *     handles concurrently as long as each thread uses its own stream (the per-stream maps are mutex-guarded; a stream's arena and
  *     graphs are only touched by the thread driving that stream).  Two threads on the same stream at the same time is a data race.
  *   - create / destroy / ts_face_set_arith / ts_prof_enable of a handle must not run concurrently with calls on that handle.
- *   - ts_pixelcnn_stream sessions belong to the thread that steps them.
+ *     ts_ctx_create and the create of ANY handle also belong ahead of the threads' first calls (or between them): they read weights back and
+ *     probe the device with synchronous copies, which the HIP runtime refuses (hipErrorStreamCaptureImplicit) while any host thread
+ *     captures a graph, whatever its capture mode, invalidating that capture.  Everything else — every pass, a session's open / step /
+ *     push / flush / close, the first use of a resampling table — copies on a stream and waits for it, and may run beside captures.
+ *   - ts_pixelcnn_stream and ts_body_stream sessions belong to the thread that steps them.  A session owns its state (row cache, sampler
+ *     tables, graphs, tails and rings) and is bound to NO stream: every step / push / flush runs on the stream it is given, and independent
+ *     sessions on different streams overlap like independent passes.  A session MAY CHANGE STREAMS between two calls once the caller has
+ *     ordered them: everything the session queued on the earlier stream has completed (hipStreamSynchronize), or the later stream waits for
+ *     it (hipStreamWaitEvent), before the first call on the later one.  Two calls of one session in flight on streams that are not ordered
+ *     is a data race on the session's buffers; nothing detects it.  (The conv nets of a body session run on the per-stream arenas of the
+ *     stream of each call; they keep nothing between calls.)
  *   - ts_last_error() is thread-local.  ts_stream_destroy(stream) drops that stream's arenas in every live handle: no call on the
- *     stream may be in progress.
- *   Exercised by tests/test_gpu_threads.py (three host threads, one stream each, bit-equal to the serial run).
+ *     stream may be in progress.  A stream created afterwards may receive the same handle value; it starts from fresh arenas and graphs.
+ *   - ts_pixelcnn_graph_stats is exact under concurrent callers: a capture counts what its own call issues (a thread-local tally), never
+ *     the launches other threads make meanwhile.  The context-wide totals behind ts_prof_* count every thread's launches, as before.
+ *   Exercised by tests/test_gpu_threads.py (three host threads, one stream each, bit-equal to the serial run) and tests/test_gpu_streams.py
+ *   (every keyword of the mixed pass, sessions, growth beside replay, face / front end / SMPL-X / evaluation, one thread queueing on three
+ *   streams, stream teardown, graph statistics: bit-equal to the serial run on the default stream, with evidence that the streams overlapped).
  */
 #ifndef TALKSHOW_HIP_H
 #define TALKSHOW_HIP_H

@@ -35,6 +35,14 @@ inline int fail(const std::string &m) {
         if (r__ != 0) return r__; \
     } while (0)
 
+// The synchronous hipMemcpy is refused by the runtime (hipErrorStreamCaptureImplicit) while ANY host thread captures a graph, in every capture
+// mode, and the refusal invalidates that thread's capture.  The asynchronous copy on the same (legacy) stream and a wait for that stream are
+// not refused, and order and complete the same way: what every copy that can run beside another thread's call goes through.
+inline hipError_t copy_and_wait(void *dst, const void *src, size_t n, hipMemcpyKind kind) {
+    const hipError_t e = hipMemcpyAsync(dst, src, n, kind, nullptr);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -56,7 +64,7 @@ struct DevBuf {
     }
     int upload(const void *host, size_t n) {
         TS_TRY(ensure(n));
-        TS_HIP(hipMemcpy(p, host, n, hipMemcpyHostToDevice));
+        TS_HIP(copy_and_wait(p, host, n, hipMemcpyHostToDevice));
         return 0;
     }
     float *f() const { return static_cast<float *>(p); }
@@ -185,6 +193,16 @@ namespace ts {
 int run_conv(ts_ctx *ctx, const ConvParams &p, int tile, hipStream_t s);
 int run_skinny(ts_ctx *ctx, const SkinnyParams &p, hipStream_t s);
 int run_skinny_batch(ts_ctx *ctx, const SkinnyParams *const *ps, int n, hipStream_t s);
+// What run_skinny / run_skinny_batch issue on THIS host thread while a tally is installed: the capturing call of pixelcnn.cpp counts its
+// own graph with it (the context-wide counters above also move with every other thread inside the library).  Thread-local, never nested.
+struct SkinnyTally {
+    long launches = 0;
+    double flops = 0;
+    SkinnyTally();
+    ~SkinnyTally();
+    SkinnyTally(const SkinnyTally &) = delete;
+    SkinnyTally &operator=(const SkinnyTally &) = delete;
+};
 // misc launches are wrapped with this scope guard so they show up under FAM_MISC
 struct MiscScope {
     ts_ctx *ctx;

@@ -133,9 +133,19 @@ int run_conv(ts_ctx *ctx, const ConvParams &p, int tile, hipStream_t s) {
     return 0;
 }
 
+namespace {
+thread_local SkinnyTally *skinny_tally = nullptr;
+inline void tally_skinny(double fl) {
+    if (skinny_tally) ++skinny_tally->launches, skinny_tally->flops += fl;
+}
+}  // namespace
+SkinnyTally::SkinnyTally() { skinny_tally = this; }
+SkinnyTally::~SkinnyTally() { skinny_tally = nullptr; }
+
 int run_skinny(ts_ctx *ctx, const SkinnyParams &p, hipStream_t s) {
     ctx->n_launch[FAM_SKINNY].fetch_add(1, std::memory_order_relaxed);
     atomic_add(ctx->n_flops[FAM_SKINNY], 2.0 * p.M * (double)p.N * p.Ktot);
+    tally_skinny(2.0 * p.M * (double)p.N * p.Ktot);
     if (ctx->prof.on) {
         ctx->prof.begin(FAM_SKINNY, s);
         ctx->prof.flops[FAM_SKINNY] += 2.0 * p.M * (double)p.N * p.Ktot;
@@ -151,6 +161,7 @@ int run_skinny_batch(ts_ctx *ctx, const SkinnyParams *const *ps, int n, hipStrea
     for (int i = 0; i < n; ++i) fl += 2.0 * ps[i]->M * (double)ps[i]->N * ps[i]->Ktot;
     ctx->n_launch[FAM_SKINNY].fetch_add(1, std::memory_order_relaxed);
     atomic_add(ctx->n_flops[FAM_SKINNY], fl);
+    tally_skinny(fl);
     if (ctx->prof.on) {
         ctx->prof.begin(FAM_SKINNY, s);
         ctx->prof.flops[FAM_SKINNY] += fl;

@@ -1318,7 +1318,6 @@ int class_rows_style(ts_pixelcnn *p, ts_pixelcnn::Work *w, const float *style, i
 // the caller's arrays hold c.out_H rows per clip, of which this run covers rows c.out_row0 .. c.out_row0 + c.H - 1.
 int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const ts_pixelcnn::Work::Key &key,
              const float *uniforms, int64_t *codes, float *logprob, hipStream_t s, bool capture_only = false) {
-    ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = c.w;
     const int out_H = c.out_H > 0 ? c.out_H : c.H;
     auto row_loop = [&](hipStream_t st) -> int {
@@ -1363,11 +1362,13 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
         TS_TRY(w->make_room(s, key));
         if (!w->cap_stream) TS_HIP(hipStreamCreateWithFlags(&w->cap_stream, hipStreamNonBlocking));
         hipGraph_t g = nullptr;
-        const long l0 = ctx->n_launch[FAM_SKINNY];
-        const double f0 = ctx->n_flops[FAM_SKINNY];
         TS_HIP(hipStreamBeginCapture(w->cap_stream, hipStreamCaptureModeThreadLocal));
-        const int rc = row_loop(w->cap_stream);
-        w->graph_stats[key] = {ctx->n_launch[FAM_SKINNY] - l0, ctx->n_flops[FAM_SKINNY] - f0};
+        int rc;
+        {   // this thread's launches only: the context-wide counters move with every other thread inside the library
+            SkinnyTally tally;
+            rc = row_loop(w->cap_stream);
+            w->graph_stats[key] = {tally.launches, tally.flops};
+        }
         const hipError_t ec = hipStreamEndCapture(w->cap_stream, &g);
         if (rc != 0) {
             if (g) (void)hipGraphDestroy(g);
@@ -1794,7 +1795,8 @@ int ts_pixelcnn_stream_open(ts_pixelcnn *p, const int64_t *label, int B, int max
     TS_TRY(st->w.given_int.ensure((size_t)B * std::max(max_chunk_rows, CHUNK_ROWS) * 2 * sizeof(int64_t)));
     st->rep_from.assign(B, -1);
     TS_TRY(st->label.ensure((size_t)B * sizeof(int64_t)));
-    TS_HIP(hipMemcpy(st->label.p, label, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    // (not hipMemcpy: another thread may be capturing a graph while this one opens a session)
+    TS_HIP(copy_and_wait(st->label.p, label, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice));
     *out = st.release();
     return 0;
 }
