@@ -368,6 +368,46 @@ int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, 
  * call); code rows [D0, D1) whose poses come out; the first MFCC frame and the first code row a later call can still read}.  The
  * arithmetic talkshow_amd/streaming.py::SeamlessPlan restates.  No reference counterpart. */
 int ts_debug_body_stream_plan(const int64_t *state4, int t, int flush, int enc_lowered, int64_t *out14);
+/* Test aids: the three staging kernels of a session (csrc/body_stream.hip), ONE call of the launcher each on `stream`, device pointers the
+ * caller owns throughout; nothing is allocated or synchronized.  Every shape outside the buffers is refused by the launcher (nonzero, nothing
+ * launched); a call of zero elements returns 0 and launches nothing.
+ * ts_debug_stream_stage_mfcc: per clip the concatenation [tail (B, cap, 64) rows [0, n_tail) | chunk (B, t, 64)]: frames [0, Tw) -> win
+ * (B, Tw, 64), frames [next0, next0 + n_next) -> next (B, cap, 64) rows [0, n_next) (rows beyond are not written).  tail != next; n_tail,
+ * n_next <= cap; Tw, next0 + n_next <= n_tail + t; every pointer 16-byte aligned. */
+int ts_debug_stream_stage_mfcc(const float *tail, const float *chunk, float *win, float *next, int B, int n_tail, int t, int cap, int Tw,
+                               int next0, int n_next, void *stream);
+/* codes (B, n, 2) = code rows [A, A + n) -> ring (B, RC, 2), row r at slot r % RC (the other slots are left alone); rows [v0, v0 + Hw) -> column
+ * 0 / 1 into lat_body / lat_hand (B, Hw), a row at or beyond A from `codes`, an earlier one from the ring.  v0 <= A, A + n - v0 <= RC,
+ * v0 + Hw <= A + n; codes and ring 16-byte aligned. */
+int ts_debug_stream_emit(const int64_t *codes, int64_t *ring, int64_t *lat_body, int64_t *lat_hand, int B, int n, int A, int RC, int v0, int Hw,
+                         void *stream);
+/* dst (B, n, W) = rows [r0, r0 + n) of every clip of src (B, R, W); r0 + n <= R.  16-byte copies where W % 4 == 0 and both pointers are 16-byte
+ * aligned, word by word otherwise: the same bits either way. */
+int ts_debug_stream_keep_rows(const float *src, float *dst, int B, int R, int r0, int n, int W, void *stream);
+
+/* ---- the glue kernels of the VQ and PixelCNN passes (csrc/vq.hip) ----
+ * Test aids: ONE call of the production launcher each on `stream`, device pointers the caller owns throughout; nothing is allocated or
+ * synchronized.  A null pointer or a row count < 1 is refused here, everything else by the launcher (nonzero, nothing launched).
+ * ts_debug_gather_rows: out[m][0 .. width) = table[idx[m idx_stride]][0 .. width) for m < M; table rows ld_table floats apart, out rows ldo (the
+ * floats of a row at and beyond width are not written); an index outside [0, nrows) gives a row of NaN.  width, ld_table, ldo % 4 == 0.
+ * lens == NULL and L == 0: the plain kernel.  Otherwise the masked one (lens a DEVICE table (M / L,), M % L == 0, len_shr >= 0): row m = b L + t
+ * with t >= lens[b] >> len_shr is a row of +0.0 and its index is not read. */
+int ts_debug_gather_rows(const float *table, int ld_table, int nrows, const int64_t *idx, long idx_stride, int M, int width, float *out,
+                         int ldo, int L, const int32_t *lens, int len_shr, void *stream);
+/* dst[m][0 .. cpad) = src[m][0 .. c) then +0.0, for the M = B L rows m = b L + t; src rows lds floats apart, dst rows ldd (floats at and beyond
+ * cpad are not written); source columns >= c are not read.  lens (DEVICE (B,)) or NULL: rows t >= lens[b] are rows of +0.0, not read. */
+int ts_debug_pad_rows(const float *src, int lds, int c, float *dst, int ldd, int cpad, int B, int L, const int32_t *lens, void *stream);
+/* Rows r >= lens[b] >> 2 of codes (B, H, 2) int64 become -1 (launch_mask_codes), of logprob (B, H, 2) +0.0 (launch_mask_logprob); the rows
+ * below are left alone.  Either block may be NULL, not both. */
+int ts_debug_mask_rows(int64_t *codes, float *logprob, int B, int H, const int32_t *lens, void *stream);
+/* dst[i] = first + i, i < n. */
+int ts_debug_iota_i64(int64_t *dst, int n, int64_t first, void *stream);
+/* dst[i] = (int32) src[i], i < n. */
+int ts_debug_i64_to_i32(const int64_t *src, int32_t *dst, long n, void *stream);
+/* dst[0 .. 2] = a, b, c, carried by the launch's own arguments. */
+int ts_debug_set_words3(uint64_t *dst, uint64_t a, uint64_t b, uint64_t c, void *stream);
+/* out[j] = sum over c ascending of e[j][c]^2 in fp32, e (n, dim) dense. */
+int ts_debug_row_sqnorm(const float *e, int n, int dim, float *out, void *stream);
 
 /* Tuning entry (not part of the drop-in surface): `iters` DEPENDENT skinny_gemm launches replayed from one hipGraph;
  * *us_out = microseconds per launch.  gate != 0: N = 2K with the tanh*sigmoid epilogue; debug: unused. */

@@ -161,6 +161,17 @@ SIGNATURES = {
     "ts_body_stream_close": (None, [_vp]),
     "ts_body_stream_lag_rows": (_i, [_vp]),
     "ts_debug_body_stream_plan": (_i, [C.POINTER(_i64), _i, _i, _i, C.POINTER(_i64)]),
+    # the staging and glue kernels alone (tests/test_gpu_glue_ops.py)
+    "ts_debug_stream_stage_mfcc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ts_debug_stream_emit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ts_debug_stream_keep_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ts_debug_gather_rows": (_i, [_vp, _i, _i, _vp, C.c_long, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
+    "ts_debug_pad_rows": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ts_debug_mask_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ts_debug_iota_i64": (_i, [_vp, _i, _i64, _vp]),
+    "ts_debug_i64_to_i32": (_i, [_vp, _vp, C.c_long, _vp]),
+    "ts_debug_set_words3": (_i, [_vp, _u64, _u64, _u64, _vp]),
+    "ts_debug_row_sqnorm": (_i, [_vp, _i, _i, _vp, _vp]),
     "ts_face_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, C.POINTER(_vp)]),
     "ts_face_destroy": (None, [_vp]),
     "ts_face_generate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1334,4 +1334,45 @@ int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, 
     return ts::run_wino_gemm(ctx, nnet, V, U, O, M, C, round_up(C, 128), (hipStream_t)stream);
 }
 
+// ---- the glue kernels of vq.hip, one launch each on `stream` (talkshow_hip_debug.h): the launcher's own refusals come back through TS_HIP ----
+int ts_debug_gather_rows(const float *table, int ld_table, int nrows, const int64_t *idx, long idx_stride, int M, int width, float *out,
+                         int ldo, int L, const int32_t *lens, int len_shr, void *stream) {
+    if (!table || !idx || !out || M < 1 || width < 1) return fail("ts_debug_gather_rows: bad argument");
+    if (!lens && L == 0) TS_HIP(ts::launch_gather_rows(table, ld_table, nrows, idx, idx_stride, M, width, out, ldo, (hipStream_t)stream));
+    else TS_HIP(ts::launch_gather_rows_masked(table, ld_table, nrows, idx, idx_stride, M, width, out, ldo, L, lens, len_shr, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_pad_rows(const float *src, int lds, int c, float *dst, int ldd, int cpad, int B, int L, const int32_t *lens, void *stream) {
+    if (!src || !dst || B < 1 || L < 1 || cpad < 1) return fail("ts_debug_pad_rows: bad argument");
+    if (!lens) TS_HIP(ts::launch_pad_rows(src, lds, c, dst, ldd, cpad, (long)B * L, (hipStream_t)stream));
+    else TS_HIP(ts::launch_pad_rows_masked(src, lds, c, dst, ldd, cpad, B, L, lens, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_mask_rows(int64_t *codes, float *logprob, int B, int H, const int32_t *lens, void *stream) {
+    if ((!codes && !logprob) || !lens || B < 1 || H < 1) return fail("ts_debug_mask_rows: bad argument");
+    if (codes) TS_HIP(ts::launch_mask_codes(codes, B, H, lens, (hipStream_t)stream));
+    if (logprob) TS_HIP(ts::launch_mask_logprob(logprob, B, H, lens, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_iota_i64(int64_t *dst, int n, int64_t first, void *stream) {
+    if (!dst || n < 1) return fail("ts_debug_iota_i64: bad argument");
+    TS_HIP(ts::launch_iota_i64(dst, n, first, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_i64_to_i32(const int64_t *src, int32_t *dst, long n, void *stream) {
+    if (!src || !dst || n < 1) return fail("ts_debug_i64_to_i32: bad argument");
+    TS_HIP(ts::launch_i64_to_i32(src, dst, n, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_set_words3(uint64_t *dst, uint64_t a, uint64_t b, uint64_t c, void *stream) {
+    if (!dst) return fail("ts_debug_set_words3: bad argument");
+    TS_HIP(ts::launch_set_words3(dst, a, b, c, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_row_sqnorm(const float *e, int n, int dim, float *out, void *stream) {
+    if (!e || !out || n < 1 || dim < 1) return fail("ts_debug_row_sqnorm: bad argument");
+    TS_HIP(ts::launch_row_sqnorm(e, n, dim, out, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -276,4 +276,21 @@ int ts_debug_body_stream_plan(const int64_t *state4, int t, int flush, int enc_l
     return 0;
 }
 
+// Test aids (talkshow_hip_debug.h): the three staging kernels, one launcher call each on `stream`; the launchers own every shape check
+int ts_debug_stream_stage_mfcc(const float *tail, const float *chunk, float *win, float *next, int B, int n_tail, int t, int cap, int Tw,
+                               int next0, int n_next, void *stream) {
+    if ((n_tail > 0 && !tail) || (Tw > 0 && !win) || (n_next > 0 && !next)) return fail("ts_debug_stream_stage_mfcc: null argument");
+    TS_HIP(launch_stream_stage_mfcc(tail, chunk, win, next, B, n_tail, t, cap, Tw, next0, n_next, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_stream_emit(const int64_t *codes, int64_t *ring, int64_t *lat_body, int64_t *lat_hand, int B, int n, int A, int RC, int v0, int Hw,
+                         void *stream) {
+    TS_HIP(launch_stream_emit(codes, ring, lat_body, lat_hand, B, n, A, RC, v0, Hw, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_stream_keep_rows(const float *src, float *dst, int B, int R, int r0, int n, int W, void *stream) {
+    TS_HIP(launch_stream_keep_rows(src, dst, B, R, r0, n, W, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"
