@@ -955,6 +955,45 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud_dev, in
 int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st);   /* hipGraphs this session has captured so far */
 void ts_pixelcnn_stream_close(ts_pixelcnn_stream *st);
 
+/* ---- slot restart: the clips of a session come and go ("continuous batching") ---------------------------------------------
+ * A SLOT of a running session ends its clip and begins a new one at any step, while its neighbours carry on.  After a restart of slot b
+ * at session row R0 (the session's next row, ts_pixelcnn_stream_rows):
+ *   - slot b's code row R0 + k is row k of a NEW clip with the given label (or style row) and Philox clip index;
+ *   - its codes and log-probabilities from there on are those of ts_pixelcnn_generate* on that clip alone under the same mode, seed and
+ *     pieces, bit for bit (PHILOX: clip_index0 = the given index; the Philox position of its code is (row - R0, column));
+ *   - every other slot's bits are those of the session without the restart;
+ *   - a slot may restart any number of times, at any session row, rows 0 to 2 included; several slots may restart in one call.
+ * How: a step reads little of what earlier rows wrote — the token ring row above, the layer-0 look-ahead sums, one projected row per
+ * layer, the conditioning rows, the Philox position and the history rings (DESIGN.md §5 has the list) — and every kernel of the chain
+ * reads a negative code as the zero row.  The restart writes "nothing above this row" into the slot's rows of those buffers: -1 codes,
+ * +0.0 sums, the bare bias where a projection would be.  A one-shot call's row 0 leaves those terms out; the restarted slot adds exact
+ * zeros in their place, and x + (+0.0) is x.
+ *   slots_host (n,)        distinct slots in [0, B)
+ *   labels_host (n,)       class labels in [0, NC), or NULL                  } exactly one of the two; a one-hot style row is the label
+ *   style_dev (n,NC)       "speaker style" weight rows on the device, or NULL } bit for bit
+ *   clip_index_host (n,)   Philox clip index of each new clip, >= 0.  A restarted slot keeps its index whatever clip_index0 later steps
+ *                          pass; a slot that has never restarted keeps clip_index0 + b of each step.
+ * Session rows stay session rows everywhere else: given_rows_host of a step counts from the step's first row, the history rings are indexed
+ * by the session row, and a restarted slot's repetition penalty starts from an empty history at R0 (as a clip's does at its row 0).  A
+ * step's style_dev rewrites the conditioning rows of EVERY slot, a restarted one included.  A slot whose user has left needs no call: it
+ * keeps stepping on whatever audio rows it is given and its output is ignored.
+ * Everything is checked on the host, the failing slot named, before anything is launched or any table moves: a slot out of range or listed
+ * twice, a label outside [0, NC), both a label and a style row or neither, a negative clip index.  Stream-ordered, no synchronisation; the
+ * launches (one reset kernel; one more per style row) run ahead of the next step's replay and are in no graph.  A session that has
+ * restarted a slot runs its steps with its origin table bound, on graph keys of their own (bit 7 of the sixth key field): captured once
+ * per (Hc, buffer phase, kind of sampler), whichever slots restart later.  A session that never restarts launches, captures and returns
+ * exactly what it did before this entry existed.
+ * ts_body_stream_* (seamless sessions, below) has no such entry: its windows are cut on the session's row grid and all its clips have one
+ * length. */
+int ts_pixelcnn_stream_restart(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, const int64_t *labels_host,
+                               const float *style_dev, const int64_t *clip_index_host, void *stream);
+/* code rows of the slot's current clip (= ts_pixelcnn_stream_rows for a slot that has never restarted); -1 for a bad slot */
+int64_t ts_pixelcnn_stream_slot_rows(const ts_pixelcnn_stream *st, int slot);
+
+/* The session's cached graphs: their number, and the chain launches and flops recorded when they were captured, summed (any pointer may be
+ * NULL).  A session that never restarts a slot shows the figures of the same steps before the restart entry existed. */
+int ts_pixelcnn_stream_graph_stats(const ts_pixelcnn_stream *st, int64_t *graphs, int64_t *launches, double *flops);
+
 /* ---- seamless sessions ---------------------------------------------------------------------------------------------------
  * A body session fed MFCC chunks of ANY length that returns, over its pushes and one flush, the codes and poses ts_body_pixel_infer
  * returns for the concatenated audio, bit for bit (same mode, seed and clip_index0) — where a plain session (ts_audioenc_forward,

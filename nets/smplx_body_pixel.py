@@ -850,5 +850,18 @@ class BodyStream:
             return self.w._decode_pair(out[0]), out[1]
         return self.w._decode_pair(out)
 
+    @property
+    def slot_rows(self):
+        """`PixelCNNStream.slot_rows`: the code rows of every slot's current clip."""
+        return self.pix.slot_rows
+
+    def restart(self, slots, id=None, *, style=None, clip_indices=None):
+        """`PixelCNNStream.restart`: the listed slots begin new clips (speaker `id`, or a `style` row) with the next push.  A plain session
+        runs the audio encoder and the VQ decoders on each chunk per clip, so nothing else carries over: a restarted slot's poses equal
+        those of a fresh `open_stream(id, 1, ...)` pushed the same chunks (same seed, clip_index0 = its clip index).  A slot whose user
+        has left needs no call: push any audio rows for it and ignore its poses."""
+        self.pix.restart(slots, id, style=style, clip_indices=clip_indices)
+        return self
+
     def close(self):
         self.pix.close()

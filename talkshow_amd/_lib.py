@@ -146,6 +146,10 @@ SIGNATURES = {
     "ts_debug_rep_table": (_i, [_rp, _i, _i, _i, C.POINTER(C.c_int32)]),
     "ts_pixelcnn_stream_rows": (_i64, [_vp]),
     "ts_pixelcnn_stream_close": (None, [_vp]),
+    # slot restart: slots (n,) host, n, labels (n,) host or NULL, style (n,NC) device or NULL, clip indices (n,) host, stream
+    "ts_pixelcnn_stream_restart": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp]),
+    "ts_pixelcnn_stream_slot_rows": (_i64, [_vp, _i]),
+    "ts_pixelcnn_stream_graph_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_double)]),
     # seamless sessions: the step's arguments around (mfcc, t) / the two outputs, then the pieces of ts_pixelcnn_stream_step_ctl
     "ts_body_stream_open": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp)]),
     "ts_body_stream_plan": (_i, [_vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -543,8 +543,30 @@ struct SampleParams {
     float *logits_copy;    // optional: logits_copy[b * copy_stride + v] = logits[b][v]
     long copy_stride;
     const int64_t *clip_table;   // optional: clip b draws from Philox subsequence clip_table[b] instead of clip_index0 + b (mixed passes)
+    const int32_t *row_origin;   // optional ("slot restart", talkshow_hip.h): clip b's Philox counter word is the position minus 2 * row_origin[b],
+                                 // the position inside the slot's CURRENT clip; everything else (given bounds, history rings) stays in session rows
 };
 hipError_t launch_sample(const SampleParams &p, hipStream_t stream);
+
+// "slot restart" of a streaming session (talkshow_hip.h): for each of the n listed clip slots, write "nothing above row `row`" into the row
+// cache — the slots' entries of the token ring rows row-1 .. row-3 (those >= 0) become -1 (a negative gather index is the zero row), their
+// rows of Q1[row & 3], Q0[row & 3] and Q0[(row + 1) & 3] become +0.0, their row of P(l, row & 1) becomes bv[l] for l >= 1 — and, from labels,
+// their conditioning rows CR[l] = tables[l][label] (a copy: the label's bits); row_origin[slot] = row.  Those rows of those slots and nothing
+// else.  Every buffer is row-major with slabs of B clips; slots / labels are device tables the host wrote in stream order.
+struct SlotResetParams {
+    const int32_t *slots;    // (n,) in [0, B)
+    const int32_t *labels;   // (n,) in [0, NC), or null: CR is left to the caller (style rows)
+    int n, B, row;
+    int D, NL, NC, R;        // R: rows of the token ring tok32[B][R][2]
+    int *tok32;
+    float *Q1, *Q0;          // [4][B][4D]
+    float *P;                // [NL][2][B][4D]
+    float *CR;               // [NL][B][2D]
+    const float *bv;         // [NL][4D]
+    const float *tables;     // [NL][NC][2D]
+    int32_t *row_origin;     // (B,)
+};
+hipError_t launch_slot_reset(const SlotResetParams &p, hipStream_t stream);
 
 // Per-clip sampling controls (talkshow_hip.h: ts_sampling and the rule of steps 1-5).  The device record of a clip: 1 / temperature as the
 // HOST computed it in fp32, top_p, top_k (0 or >= V: off).  A sibling of SampleParams: the sampler without controls keeps its arguments (vq.hip: sample_ctl_body behind

@@ -70,6 +70,7 @@ struct ts_pixelcnn {
     DevBuf w1m, b1m;                                         // head1': [HID][D or 2D], [HID]
     ConvLayer aud_h1;                                        // Wh1_1 applied to AEH for every row (l = 1 has AEH in place of XH_0)
     DevBuf cls_all;                                          // the NL class tables again, contiguous [NL][NC][2D]: what style_rows_kernel reads
+    DevBuf bv_all;                                           // the NL vertical biases again, contiguous [NL][2*2D]: what slot_reset_kernel reads
     // Code tables (code_tables.hip).  Two launches of a code row multiply nothing but embeddings of codes that are already known: slot
     // V0 (W2 . E[r-1] and its riders W1 . E[r-1], W0 . E[r-1]) and hg_0 of column 1 (wh[0] . emb[code(r, 0)]).  The tables hold, per code,
     // the slice sums the chain kernels would form (same MFMA, same k order, same K split), so a lookup launch that adds them in the
@@ -128,7 +129,8 @@ struct ts_pixelcnn {
         // read keep_int; without the bit their mask pointer is null), bit 4 for a pass with per-row speaker style (the gate launches of every chunk
         // read their conditioning rows from style_int in place of CR), bit 5 for a pass with a code bias (its samplers are the sample_ctl_bias
         // kernels, which read bias_tab and bias_idx; neither the tables' content nor their number is part of the key), bit 6 for a pass with a repetition penalty (its samplers are the
-        // sample_ctl_rep kernels, which read rep_tab and bias_idx and read and write rep_ring; the records are not part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // sample_ctl_rep kernels, which read rep_tab and bias_idx and read and write rep_ring; the records are not part of the key), bit 7 for the steps of a
+        // session that has restarted a slot (their samplers read the session's row_origin and the clip table; which slots restarted, and where, is not part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -234,6 +236,12 @@ struct ts_pixelcnn_stream {
     // "repetition penalty" on a session: per clip, the first row of its current unbroken run of rows written under window > 0 (what
     // SampleRep::from_row carries to the samplers), -1 while the clip has no such run
     std::vector<int32_t> rep_from;
+    // "slot restart" (talkshow_hip.h): nothing below exists, on the host or the device, until the session's first restart
+    bool restarted = false;            // steps bind row_origin and the clip table (sampler bit 7: graph keys of their own)
+    bool cr_ready = false;             // CR was written from the labels ahead of a restart at row 0: the first step leaves it alone
+    std::vector<int32_t> origin;       // per slot: the session row at which its current clip began
+    std::vector<int64_t> clip_index;   // per slot: the Philox clip index given at its restart, -1 while it has never restarted
+    DevBuf row_origin, restart_tab;    // (B,) int32 the samplers read; {slots (B,), labels (B,)} of the restart being queued
 };
 
 namespace {
@@ -346,6 +354,9 @@ struct RunCfg {
     // records c.ctl and c.bias_index are set too (neutral records / an index of -1 when the call brought none)
     const SampleRep *rep = nullptr;
     int32_t *rep_ring = nullptr;
+    // "slot restart": the session's (slabB(),) table of the row at which every slot's current clip began, or null (a session that never
+    // restarted a slot, and every one-shot call).  With it c.clip_table is set too
+    const int32_t *row_origin = nullptr;
     // the class-conditioning rows of layer l for the gate launches of code row r (every such launch belongs to one row)
     const float *cls_rows(int l, int r, size_t D2) const {
         if (!style) return w->CR.f() + (size_t)l * slabB() * D2;
@@ -776,6 +787,7 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
     sp.seed = c.seed;
     sp.clip_index0 = c.clip0;
     sp.clip_table = c.clip_table;
+    sp.row_origin = c.row_origin;
     sp.dyn = c.dyn;
     sp.position = (uint32_t)((r - c.pos_r0) * 2 + j + (c.dyn ? 0 : c.pos_base));
     sp.tok32 = w->tok32.i() + (size_t)(r % c.R) * 2 + j;
@@ -879,7 +891,7 @@ int ts_pixelcnn_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int V, int D, i
     TS_TRY(p->emb.upload(emb, (size_t)V * D * sizeof(float)));
 
     p->wvt.resize(NL);
-    std::vector<float> cls_all;
+    std::vector<float> cls_all, bv_all;
     for (int l = 0; l < NL; ++l) {
         const std::string q = "layers." + std::to_string(l);
         const int kh = l == 0 ? 4 : 2;       // kernel // 2 + 1 rows, kernel = 7 / 3 (gated_pixelcnn_v2.py:34,112-113)
@@ -909,6 +921,7 @@ int ts_pixelcnn_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int V, int D, i
             TS_TRY(upload_vec(p->wvt[l], pv));
         }
         TS_TRY(upload_vec(p->bv, pb));
+        bv_all.insert(bv_all.end(), pb.begin(), pb.end());
         TS_TRY(upload_vec(p->wv2h, std::vector<float>(wvh, wvh + (size_t)D2 * D2)));
         TS_TRY(upload_vec(p->bv2h, std::vector<float>(bvh, bvh + D2)));
         // horizontal: row co, k = tap*D + ci ; tap 0 <-> column j-1, tap 1 <-> column j (kernel (1,2), padding (0,1))
@@ -926,6 +939,7 @@ int ts_pixelcnn_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int V, int D, i
         TS_TRY(upload_vec(p->br, std::vector<float>(br, br + D)));
     }
     TS_TRY(p->cls_all.upload(cls_all.data(), cls_all.size() * sizeof(float)));
+    TS_TRY(p->bv_all.upload(bv_all.data(), bv_all.size() * sizeof(float)));
     // audio conditioning
     const float *wa = sd.get("embedding_aud.weight", {D, AD, 1, 1}), *ba = sd.get("embedding_aud.bias", {D});
     const float *wfv = sd.get("fusion_v.weight", {D, D2, 1, 1}), *bfv = sd.get("fusion_v.bias", {D});
@@ -1218,7 +1232,8 @@ namespace {
 // the sixth field of a graph key: which sampler the run's launches are (Work::Key)
 inline int sampler_bits(const RunCfg &c, const float *logprob) {
     const bool given = c.given_rows;
-    return (c.ctl ? 1 : 0) | (logprob ? 2 : 0) | (given ? 4 : 0) | (given && c.keep_src ? 8 : 0) | (c.style ? 16 : 0) | (c.bias ? 32 : 0) | (c.rep ? 64 : 0);
+    return (c.ctl ? 1 : 0) | (logprob ? 2 : 0) | (given ? 4 : 0) | (given && c.keep_src ? 8 : 0) | (c.style ? 16 : 0) | (c.bias ? 32 : 0) | (c.rep ? 64 : 0) |
+           (c.row_origin ? 128 : 0);
 }
 // The tables reach the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own tables — may be queued behind each other.
@@ -1832,13 +1847,21 @@ int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, cons
     for (size_t b = 0; b < t.rep.size(); ++b)
         if (t.rep[b].window > 0) t.rep[b].from_row = rep_from[b] = st->rep_from[b] >= 0 ? st->rep_from[b] : r0;
     for (int32_t &g : t.given_rows) g += r0;   // the table the samplers read holds absolute bounds: clip b is forced at positions below 2 (r0 + g_b)
-    if (r0 == 0 && !o.style) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
+    if (r0 == 0 && !o.style && !st->cr_ready) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
     if (o.style) TS_TRY(class_rows_style(p, w, o.style, B, s));   // CR stays as written until a later step brings other rows
     RunCfg c = ring_cfg(w, B, r0, Hc, mode, seed, clip0);
     c.audio_from(w);   // a step's audio terms are the Work's whole buffers
     TS_TRY(stage_sampler_tables(p, w, t, o, s));
     bind_sampler_tables(c, w, o);
     c.given_stage = true;   // a step's given block is staged whole
+    if (st->restarted) {   // "slot restart": the origins, and every slot's Philox clip index as this step sees it (kernel arguments)
+        std::vector<int64_t> clips(B);
+        for (int b = 0; b < B; ++b) clips[b] = st->clip_index[b] >= 0 ? st->clip_index[b] : clip0 + b;
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(static_cast<int *>(w->clip_tab.p), reinterpret_cast<const int *>(clips.data()), 2l * B, s));
+        c.clip_table = static_cast<const int64_t *>(w->clip_tab.p);
+        c.row_origin = static_cast<const int32_t *>(st->row_origin.p);
+    }
     TS_TRY(audio_terms(p, w, aud, B, Hc, s));
     const bool graph = p->use_graph && !ctx->prof.on;
     TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + ring_phase(r0), mode, 0, sampler_bits(c, o.logprob)), uniforms, codes,
@@ -1871,4 +1894,94 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud, int Hc
 }
 
 int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st) { return st ? st->w.captures : -1; }
+
+// "slot restart" (talkshow_hip.h).  Everything is checked before anything is launched or any table moves.  The launches: the tables of
+// the call as kernel arguments, slot_reset_kernel, and one style_rows launch per slot that brings a weight row — all ahead of the next
+// step's replay and in no graph
+int ts_pixelcnn_stream_restart(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, const int64_t *labels_host, const float *style_dev,
+                               const int64_t *clip_index_host, void *stream) {
+    const std::string who = "ts_pixelcnn_stream_restart: ";
+    if (!st || !slots_host || !clip_index_host) return fail(who + "null argument");
+    const int B = st->B;
+    if (n < 1 || n > B) return fail(who + "n must be in [1, B = " + std::to_string(B) + "], got " + std::to_string(n));
+    for (int i = 0; i < n; ++i)
+        if (slots_host[i] < 0 || slots_host[i] >= B)
+            return fail(who + "entry " + std::to_string(i) + ": slot " + std::to_string(slots_host[i]) + " is outside [0, B = " + std::to_string(B) + ")");
+    if (!labels_host == !style_dev)
+        return fail(who + "slot " + std::to_string(slots_host[0]) + ": " + (labels_host ? "both a label and a style row" : "neither a label nor a style row") +
+                    " (a restarted clip takes exactly one of them)");
+    ts_pixelcnn *p = st->p;
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < n; ++i) {
+        const std::string slot = "slot " + std::to_string(slots_host[i]);
+        if (seen[slots_host[i]]++) return fail(who + slot + " is listed twice");
+        if (labels_host && (labels_host[i] < 0 || labels_host[i] >= p->NC))
+            return fail(who + slot + ": label " + std::to_string(labels_host[i]) + " is outside [0, NC = " + std::to_string(p->NC) + ")");
+        if (clip_index_host[i] < 0) return fail(who + slot + ": clip index " + std::to_string(clip_index_host[i]) + " is negative");
+    }
+    TS_HIP(hipSetDevice(p->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ts_pixelcnn::Work *w = &st->w;
+    if (st->rows == 0 && !st->cr_ready)   // the labels given at open, as the first step would write them: the restarted slots' rows then replace theirs
+        TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
+    MiscScope ms(p->ctx, s);
+    if (!st->restarted) {   // the session's first restart: the tables exist from here on, every origin 0 in stream order
+        TS_TRY(st->row_origin.ensure((size_t)B * sizeof(int32_t)));
+        TS_TRY(st->restart_tab.ensure((size_t)2 * B * sizeof(int32_t)));
+        const std::vector<int32_t> zeros(B, 0);
+        TS_HIP(launch_put_words(static_cast<int *>(st->row_origin.p), zeros.data(), B, s));
+    }
+    std::vector<int32_t> tab(2 * (size_t)n, 0);
+    for (int i = 0; i < n; ++i) tab[i] = slots_host[i], tab[n + i] = labels_host ? (int32_t)labels_host[i] : 0;
+    int32_t *tab_dev = static_cast<int32_t *>(st->restart_tab.p);
+    TS_HIP(launch_put_words(tab_dev, tab.data(), 2l * n, s));
+    SlotResetParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.slots = tab_dev, q.labels = labels_host ? tab_dev + n : nullptr;
+    q.n = n, q.B = B, q.row = (int)st->rows;
+    q.D = p->D, q.NL = p->NL, q.NC = p->NC, q.R = 4;   // the ring of ring_cfg
+    q.tok32 = w->tok32.i(), q.Q1 = w->Q1.f(), q.Q0 = w->Q0.f(), q.P = w->P.f(), q.CR = w->CR.f();
+    q.bv = p->bv_all.f(), q.tables = p->cls_all.f();
+    q.row_origin = static_cast<int32_t *>(st->row_origin.p);
+    TS_HIP(launch_slot_reset(q, s));
+    for (int i = 0; style_dev && i < n; ++i) {   // the "speaker style" rule in its order, on the slot's own rows of CR
+        StyleRowsParams y;
+        std::memset(&y, 0, sizeof(y));
+        y.tables = p->cls_all.f();
+        y.weights = style_dev + (size_t)i * p->NC;
+        y.w_ld = p->NC;
+        y.S = 1, y.NC = p->NC, y.W = 2 * p->D, y.NL = p->NL;
+        y.r0 = 0, y.n = 1, y.slots = 1;
+        y.out = w->CR.f() + (size_t)slots_host[i] * 2 * p->D;
+        y.out_l_stride = (long)B * 2 * p->D;
+        y.out_r_stride = 0;
+        TS_HIP(launch_style_rows(y, s));
+    }
+    if (!st->restarted) st->origin.assign(B, 0), st->clip_index.assign(B, -1);
+    st->restarted = st->cr_ready = true;
+    for (int i = 0; i < n; ++i) {
+        const int b = slots_host[i];
+        st->origin[b] = (int32_t)st->rows;
+        st->clip_index[b] = clip_index_host[i];
+        st->rep_from[b] = -1;   // a penalty starts from an empty history, as a one-shot clip's does
+    }
+    return 0;
+}
+
+// what the session's cached graphs hold: their number, and the skinny launches and flops recorded at their capture, summed
+int ts_pixelcnn_stream_graph_stats(const ts_pixelcnn_stream *st, int64_t *graphs, int64_t *launches, double *flops) {
+    if (!st) return fail("ts_pixelcnn_stream_graph_stats: null argument");
+    long n = 0;
+    double f = 0.0;
+    for (const auto &kv : st->w.graph_stats) n += kv.second.first, f += kv.second.second;
+    if (graphs) *graphs = (int64_t)st->w.graphs.size();
+    if (launches) *launches = n;
+    if (flops) *flops = f;
+    return 0;
+}
+
+int64_t ts_pixelcnn_stream_slot_rows(const ts_pixelcnn_stream *st, int slot) {
+    if (!st || slot < 0 || slot >= st->B) return -1;
+    return st->rows - (st->restarted ? st->origin[slot] : 0);
+}
 }  // extern "C"

@@ -752,6 +752,49 @@ hipError_t launch_set_words3(uint64_t *dst, uint64_t a, uint64_t b, uint64_t c, 
     return hipGetLastError();
 }
 
+// "slot restart" (kernels.h: SlotResetParams).  One workgroup per (listed slot, layer l) and one more per slot (blockIdx.y == NL) for what
+// has no layer: the token ring, the layer-0 look-ahead sums and the origin.  Every row is written as float4 (4D and 2D are multiples of 4:
+// D % 32 == 0).  A slot or label outside its range writes nothing (the host has refused such a call already).
+__global__ __launch_bounds__(256) void slot_reset_kernel(const SlotResetParams p) {
+    const int slot = p.slots[blockIdx.x], l = (int)blockIdx.y, tid = threadIdx.x;
+    if (slot < 0 || slot >= p.B) return;
+    const int D4 = 4 * p.D, D2 = 2 * p.D, r = p.row;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (l == p.NL) {
+        if (tid < 6) {   // rows r-1, r-2, r-3 of the ring, both columns
+            const int rr = r - 1 - (tid >> 1);
+            if (rr >= 0) p.tok32[((long)slot * p.R + rr % p.R) * 2 + (tid & 1)] = -1;
+        }
+        if (tid == 6) p.row_origin[slot] = r;
+        float4 *q1 = reinterpret_cast<float4 *>(p.Q1 + ((long)(r & 3) * p.B + slot) * D4);
+        float4 *q0a = reinterpret_cast<float4 *>(p.Q0 + ((long)(r & 3) * p.B + slot) * D4);
+        float4 *q0b = reinterpret_cast<float4 *>(p.Q0 + ((long)((r + 1) & 3) * p.B + slot) * D4);
+        for (int q = tid; q < D4 / 4; q += 256) q1[q] = q0a[q] = q0b[q] = zero;
+        return;
+    }
+    if (l >= 1) {
+        const float4 *bv = reinterpret_cast<const float4 *>(p.bv + (long)l * D4);
+        float4 *dst = reinterpret_cast<float4 *>(p.P + ((long)(l * 2 + (r & 1)) * p.B + slot) * D4);
+        for (int q = tid; q < D4 / 4; q += 256) dst[q] = bv[q];
+    }
+    if (p.labels) {
+        const int label = p.labels[blockIdx.x];
+        if (label < 0 || label >= p.NC) return;
+        const float4 *src = reinterpret_cast<const float4 *>(p.tables + ((long)l * p.NC + label) * D2);
+        float4 *dst = reinterpret_cast<float4 *>(p.CR + ((long)l * p.B + slot) * D2);
+        for (int q = tid; q < D2 / 4; q += 256) dst[q] = src[q];
+    }
+}
+hipError_t launch_slot_reset(const SlotResetParams &p, hipStream_t stream) {
+    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (!p.slots || !p.tok32 || !p.Q1 || !p.Q0 || !p.P || !p.CR || !p.bv || !p.tables || !p.row_origin || p.n < 1 || p.B < 1 || p.n > p.B ||
+        p.row < 0 || p.D < 4 || p.D % 4 || p.NL < 1 || p.NL > 65534 || p.NC < 1 || p.R < 4 || !al16(p.Q1) || !al16(p.Q0) || !al16(p.P) ||
+        !al16(p.CR) || !al16(p.bv) || !al16(p.tables))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slot_reset_kernel, dim3((unsigned)p.n, (unsigned)(p.NL + 1)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 // test aid: out[i] = gate_act(v[i], p[i]) — the chain kernels' gate on given operands (tests measure it against tanh * sigmoid in float64)
 __global__ void gate_act_kernel(const float *v, const float *p, float *out, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -867,9 +910,10 @@ __device__ __forceinline__ float sample_uniform(const SampleParams &p, int b) {
     // a mixed pass orders its clips by length: the subsequence then comes from a per-clip table, so that a clip's draws keep
     // depending on its GLOBAL index only
     const uint64_t clip = p.clip_table ? (uint64_t)p.clip_table[b] : (uint64_t)((p.dyn ? (int64_t)p.dyn[1] : p.clip_index0) + b);
+    // "slot restart": the counter word is the position inside the slot's current clip (null: the session's own, as ever)
+    const uint32_t pos = p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u) - (p.row_origin ? 2u * (uint32_t)p.row_origin[b] : 0u);
     uint32_t r;
-    philox4x32_10(p.position + (p.dyn ? (uint32_t)p.dyn[2] : 0u), (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
+    philox4x32_10(pos, (uint32_t)clip, (uint32_t)(clip >> 32), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
     return (float)(r >> 8) * (1.0f / 16777216.0f);
 }
 // thread 0, after every thread t stored its chunk sum in sf[t + 1]: the 256 sums left to right, sf[t] = sum of the chunks < t; returns the

@@ -692,6 +692,49 @@ class PixelCNNStream:
             bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep, _lib.stream_ptr()))
         return codes if lp is None else (codes, lp)
 
+    @property
+    def slot_rows(self):
+        """(B,) int64 numpy: the code rows of every slot's CURRENT clip (`rows` for a slot that has never restarted)."""
+        lib = _lib.load()
+        return np.array([lib.ts_pixelcnn_stream_slot_rows(self._h, b) for b in range(self.B)], np.int64)
+
+    def restart(self, slots, label=None, *, style=None, clip_indices=None):
+        """Slot restart (`ts_pixelcnn_stream_restart`; talkshow_hip.h, "slot restart"): each listed slot ends its clip and begins a NEW one at
+        the session's next row, while the other slots carry on — continuous batching.  From there on the slot's codes and
+        log-probabilities are those of `run` on the new clip alone (same mode, seed and keywords, clip_index0 = its clip index), bit for
+        bit, and every other slot's bits are those of the session without the call.
+        slots: one slot or a list of distinct slots.  label: the new clips' class labels (one for all listed slots, or one each), OR
+        style: one (n_classes,) weight row for all, or a list / (n, n_classes) array with one row each (`None` entries take `label`'s
+        entry).  clip_indices: the new clips' Philox clip indices (default: the slot numbers); a restarted slot keeps its index whatever
+        `clip_index0` later steps pass.  Any number of times, at any row.  The session's labels follow, so a later `style=[None, ...]`
+        means the NEW clip's own label; a weight row given here holds until a step brings style rows (a session default `style`
+        does, at every step).  Keywords of later steps keep counting in session rows: `given` from the step's first row, and a restarted
+        slot's `repeat` history is empty at its first row.  A slot whose user has left needs no call and no mask: it keeps stepping on
+        whatever audio rows it is given and its output is ignored.  A bad value raises ValueError naming the slot before any device
+        work; `rows` and `slot_rows` do not move."""
+        from talkshow_amd.streaming import SlotClock
+        NC = self.net.n_classes
+        slots, labels, styles, clips = SlotClock.check(self.B, NC, slots, label, style, clip_indices)
+        n = len(slots)
+        rows = None
+        if styles is not None:          # one entry of the C call's two tables is NULL: labels become their one-hot rows beside weight rows
+            rows = np.zeros((n, NC), np.float32)
+            for i in range(n):
+                if styles[i] is None:
+                    rows[i, int(labels[i])] = 1.0
+                else:
+                    e = styles[i]
+                    rows[i] = np.asarray(e.detach().cpu().numpy() if hasattr(e, "detach") else e, np.float32)
+        i32, i64 = C.c_int32 * n, C.c_int64 * n
+        style_dev = upload(rows, self.net._dev()) if rows is not None else None
+        _lib.check(_lib.load().ts_pixelcnn_stream_restart(
+            self._h, i32(*slots), n, None if rows is not None else i64(*[int(v) for v in labels]), _lib.dptr(style_dev), i64(*clips),
+            _lib.stream_ptr()))
+        for i, b in enumerate(slots):   # what `style=[None, ...]` stands for from here on; a blend keeps the slot's old label
+            if labels is not None and labels[i] is not None:
+                self._labels[b] = int(labels[i])
+        return self
+
     def close(self):
         if self._h is not None:
             torch.cuda.synchronize()

@@ -91,8 +91,124 @@ def chain_rows(max_chunk_frames, enc_reach=ENC_MARGIN_ROWS):
     return max(int(enc_reach), int(max_chunk_frames) // 4 + 1)
 
 
+class SlotClock:
+    """Slot restart (talkshow_hip.h, "slot restart"), restated on the host: the session row, per slot the row at which its
+    current clip began (its origin) and the Philox clip index it was given, and from those the rows of each slot's clip and the Philox
+    position of (slot, session row, column).  `rewrites(r)` names what a restart at row r writes on the device.  Pure Python: the wrapper
+    validates a restart through `check`, the tests hold the native session against the rest."""
+
+    RING_ROWS = 4     # rows of a session's token ring; also the period of the Q1 / Q0 rings
+
+    def __init__(self, B):
+        self.B = int(B)
+        if self.B < 1:
+            raise ValueError(f"a session has at least one slot, got B = {B}")
+        self.row = 0
+        self.origins = [[0] for _ in range(self.B)]      # per slot: the origin of every clip it has held, ascending
+        self.clip_index = [None] * self.B                # per slot: the index given at its last restart; None: clip_index0 + slot of a step
+
+    @staticmethod
+    def check(B, n_classes, slots, labels=None, styles=None, clip_indices=None):
+        """The argument rules of a restart -> (slots, labels or None, styles or None, clip indices) as lists of n entries.  ValueError naming
+        the slot: a slot outside [0, B) or listed twice, a label outside [0, n_classes), both a label and a style row or neither, a style
+        row of the wrong shape or with a non-finite weight, a negative clip index.  clip_indices None: every slot's own number."""
+        B, NC = int(B), int(n_classes)
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        n = len(slots)
+        if n < 1:
+            raise ValueError("restart: no slot given")
+
+        def seq(v):
+            try:
+                return not isinstance(v, str) and len(v) >= 0
+            except TypeError:
+                return False
+
+        def spread(x, what):   # one value for all listed slots, or one per slot (a style VALUE is itself a row of numbers)
+            if x is None:
+                return None
+            if hasattr(x, "detach"):
+                x = x.detach().cpu().numpy()
+            one = seq(x) and len(x) > 0 and all(e is not None and not seq(e) for e in x) if what == "style" else not seq(x)
+            x = [x] * n if one else list(x)
+            if len(x) != n:
+                raise ValueError(f"restart: {n} slots but {len(x)} {what} entries")
+            return x
+        labels, styles, clip_indices = spread(labels, "label"), spread(styles, "style"), spread(clip_indices, "clip index")
+        seen = set()
+        for i, b in enumerate(slots):
+            if int(b) != b or not 0 <= int(b) < B:
+                raise ValueError(f"restart: slot {b} is outside [0, B = {B})")
+            b = slots[i] = int(b)
+            if b in seen:
+                raise ValueError(f"restart: slot {b} is listed twice")
+            seen.add(b)
+            has_label = labels is not None and labels[i] is not None
+            has_style = styles is not None and styles[i] is not None
+            if has_label == has_style:
+                raise ValueError(f"restart: slot {b} brings {'both a label and a style row' if has_label else 'neither a label nor a style row'}: "
+                                 f"a new clip takes exactly one")
+            if has_label and (int(labels[i]) != labels[i] or not 0 <= int(labels[i]) < NC):
+                raise ValueError(f"restart: slot {b}: label {labels[i]} is outside [0, n_classes = {NC})")
+            if has_style:
+                row = styles[i].detach().cpu().numpy() if hasattr(styles[i], "detach") else styles[i]
+                row = list(row.tolist() if hasattr(row, "tolist") else row) if seq(row) else None
+                row = None if row is None or any(seq(v) for v in row) else [float(v) for v in row]
+                if row is None or len(row) != NC:
+                    raise ValueError(f"restart: slot {b}: a style row holds n_classes = {NC} weights (a session takes no tracks)")
+                if any(v != v or v in (float("inf"), float("-inf")) for v in row):
+                    raise ValueError(f"restart: slot {b}: a style weight is not finite")
+            if clip_indices is not None and (int(clip_indices[i]) != clip_indices[i] or int(clip_indices[i]) < 0):
+                raise ValueError(f"restart: slot {b}: clip index {clip_indices[i]} is negative")
+        return slots, labels, styles, [int(c) for c in clip_indices] if clip_indices is not None else list(slots)
+
+    def restart(self, slots, clip_indices=None):
+        """The listed slots begin new clips at the session's next row."""
+        slots, _, _, clips = self.check(self.B, 1, slots, labels=0, clip_indices=clip_indices)
+        for b, c in zip(slots, clips):
+            if self.origins[b][-1] != self.row:
+                self.origins[b].append(self.row)
+            self.clip_index[b] = c
+        return self
+
+    def advance(self, rows):
+        self.row += int(rows)
+        return self
+
+    def origin(self, slot, row=None):
+        """The origin of the clip that slot `slot` held at session row `row` (None: holds now)."""
+        if row is None:
+            return self.origins[slot][-1]
+        return max(o for o in self.origins[slot] if o <= row)
+
+    @property
+    def slot_rows(self):
+        """Rows of every slot's current clip."""
+        return [self.row - o[-1] for o in self.origins]
+
+    def position(self, slot, row, col):
+        """The Philox counter word of slot `slot`'s code at session row `row`, column `col`: its position inside the slot's clip."""
+        return 2 * (row - self.origin(slot, row)) + col
+
+    def clip(self, slot, clip_index0=0):
+        """The Philox clip index slot `slot` draws under in a step that passes clip_index0."""
+        return clip_index0 + slot if self.clip_index[slot] is None else self.clip_index[slot]
+
+    @classmethod
+    def rewrites(cls, r):
+        """What a restart at session row r writes in a slot's slabs: the token ring rows (ring index of rows r-1, r-2, r-3 that exist), the
+        Q1 ring row of row r, the Q0 ring rows of rows r and r + 1, the parity of P read by row r."""
+        R = cls.RING_ROWS
+        return {"tok": [(r - k) % R for k in (1, 2, 3) if r - k >= 0], "q1": [r % R], "q0": [r % R, (r + 1) % R], "p": r & 1}
+
+
 class SeamlessBodyStream:
     """See `TrainWrapper.open_stream(..., seamless=True)`: the host handle of `ts_body_stream` (talkshow_hip.h, "seamless sessions")."""
+
+    def restart(self, *a, **k):
+        """Not taken by a seamless session (talkshow_hip.h, "slot restart")."""
+        raise NotImplementedError("a seamless session restarts no slot: its encoder and decoder windows are cut on the SESSION's row grid and "
+                                  "all its clips have one length; use a plain session (open_stream(..., seamless=False)) or open another")
 
     def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None, seed=None):
         import ctypes as C
