@@ -359,6 +359,16 @@ int ts_debug_wino_transform(ts_ctx *ctx, int which, int nnet, int B, int L, int 
  * V / O (6, M, C), U (6, round_up(C, 128), C) of ts_debug_wino_weights, device pointers; the *1 of nnet = 1 are not read.  Does not synchronize. */
 int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, const float *U0, const float *U1, float *O0, float *O1, int M,
                        int C, void *stream);
+/* ---- the VQ decoders' first lowered layer from per-code tables (conv_wino.hip::wino_codes; knob TS_VQ_DEC_TABLES) ----
+ * Test aid: ONE launch of wino_codes on device buffers the caller owns.  codes (B, L) int64, T (6, ncode, C), O (6, B J, C), J = ceil(L / 4):
+ * O_i[b J + j] = sum_k Bt[i][k] T_i[codes[b][4j - 1 + k]] in wino_in's pinned order; a row outside [0, L_b) is the zero row and its code is
+ * not read, a code outside [0, ncode) is the zero row.  lens_dev, shr, shl as for ts_debug_wino_transform.  Does not synchronize. */
+int ts_debug_wino_codes(ts_ctx *ctx, int nnet, int B, int L, int C, const int32_t *lens_dev, int shr, int shl, const int64_t *codes0,
+                        const int64_t *codes1, const float *T0, const float *T1, int ncode0, int ncode1, float *O0, float *O1, void *stream);
+/* Test aid: 1 where the network decodes its first stack from tables, 0 where not (nothing is written), -1 on an error.  Copies to HOST
+ * buffers, each optional: tables (6, ncode, hid), aft_table (ncode, hid) and u (6, round_up(hid, 128), hid), the first layer's Winograd
+ * matrices the tables were multiplied by; *tables_dev = the tables' device address.  Synchronizes. */
+int ts_debug_vqvae_dec_tables(ts_vqvae *vq, float *tables, float *aft_table, float *u, const float **tables_dev);
 
 /* ---- seamless sessions (csrc/body_stream.cpp; talkshow_hip.h, "seamless sessions") ----
  * Host-only (no GPU): one call of the window plan on given counters.  state4 = {frames received F, code rows done A, code rows whose poses

@@ -226,6 +226,8 @@ SIGNATURES = {
     "ts_debug_wino_weights": (_i, [_vp, _i, _i, _vp]),
     "ts_debug_wino_transform": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, C.POINTER(_vp), _vp]),
     "ts_debug_wino_gemm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "ts_debug_wino_codes": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ts_debug_vqvae_dec_tables": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "ts_debug_conv_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_plan": (_i, [C.POINTER(_i), _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_run": (_i, [_vp, C.POINTER(SkinnyProblem), _i, C.c_char_p, C.POINTER(_i), _vp]),

@@ -34,6 +34,8 @@ static Knobs read_knobs(Get get) {
     v.face_pack = num("TS_FACE_PACK", 0) != 0;
     v.conv_sk = num("TS_CONV_SK", 1);
     v.conv_wino = num("TS_CONV_WINO", -1);
+    v.vq_dec_tables = num("TS_VQ_DEC_TABLES", -1);
+    v.wino_deal = num("TS_WINO_DEAL", 1) != 0;
     v.w2v_moments = num("TS_W2V_MOMENTS", 1) != 0;
     v.vq_lds = num("TS_VQ_LDS", 1) != 0;
     v.vq_pair = num("TS_VQ_PAIR", 1) != 0;
@@ -1332,6 +1334,20 @@ int ts_debug_wino_gemm(ts_ctx *ctx, int nnet, const float *V0, const float *V1, 
     const float *V[2] = {V0, V1}, *U[2] = {U0, U1};
     float *O[2] = {O0, O1};
     return ts::run_wino_gemm(ctx, nnet, V, U, O, M, C, round_up(C, 128), (hipStream_t)stream);
+}
+
+int ts_debug_wino_codes(ts_ctx *ctx, int nnet, int B, int L, int C, const int32_t *lens_dev, int shr, int shl, const int64_t *codes0,
+                        const int64_t *codes1, const float *T0, const float *T1, int ncode0, int ncode1, float *O0, float *O1, void *stream) {
+    if (!ctx || nnet < 1 || nnet > 2) return fail("ts_debug_wino_codes: bad argument");
+    ts::WinoParams w;
+    std::memset(&w, 0, sizeof(w));
+    w.nnet = nnet;
+    w.B = B, w.L = L, w.J = (L + 3) / 4, w.C = C;
+    w.lens = lens_dev, w.len_shr = shr, w.len_shl = shl;
+    w.codes[0] = codes0, w.codes[1] = codes1, w.T[0] = T0, w.T[1] = T1, w.ncode[0] = ncode0, w.ncode[1] = ncode1, w.Ow[0] = O0, w.Ow[1] = O1;
+    MiscScope ms(ctx, (hipStream_t)stream);
+    TS_HIP(ts::launch_wino(3, w, (hipStream_t)stream));
+    return 0;
 }
 
 // ---- the glue kernels of vq.hip, one launch each on `stream` (talkshow_hip_debug.h): the launcher's own refusals come back through TS_HIP ----

@@ -18,6 +18,9 @@
 //   then v = y + bias, v = v + res (if given), v = act(v).
 // wino_out_in evaluates exactly these expressions for the six rows a tile of the next layer reads, so it equals wino_out followed by
 // wino_in bit for bit; the intermediate y is never stored.
+// wino_codes (the decoder's first stack, whose input rows are rows of the aft_vq table) writes the first layer's O straight from the codes:
+//   O_i[b J + j] = sum_k Bt[i][k] T_i[code[b][4j - 1 + k]], T_i = table U_i^T, in V_i's expression with T_i[c_k] in place of d_k
+// (pinned by tests/test_gpu_vq_tables.py).  It rounds otherwise than wino_in followed by the GEMMs, within the same fp32 bound.
 #include "kernels.h"
 #include "conv_tile.h"
 
@@ -71,8 +74,15 @@ struct WinoItem {
 __device__ __forceinline__ WinoItem wino_item(const WinoParams &p) {
     WinoItem w;
     const int c4 = p.C >> 2;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned bx = blockIdx.x;
     w.net = blockIdx.y;
+    if (p.deal) {   // 1-D grid of nnet * deal workgroups; ids of equal residue mod 8 share an XCD: XCD x takes the x-th contiguous eighth
+        const unsigned total = gridDim.x, q = total >> 3, r = total & 7, x = bx & 7;
+        const unsigned g = x * q + (x < r ? x : r) + (bx >> 3);
+        w.net = g >= (unsigned)p.deal;
+        bx = g - (w.net ? p.deal : 0);
+    }
+    const long idx = (long)bx * blockDim.x + threadIdx.x;
     w.row = idx / c4;
     w.c = (int)(idx - w.row * c4) << 2;
     w.ok = w.row < (long)p.B * p.J;
@@ -157,6 +167,44 @@ __global__ __launch_bounds__(256) void wino_out_in_kernel(const WinoParams p) {
     for (int i = 0; i < 6; ++i) st4(V + i * cs, v[i]);
 }
 
+// wino_in and the six GEMMs of a layer whose input rows are rows of a table (the decoder's first stack: x[b][t] = aft_table[code[b][t]]).
+// The GEMMs are linear in x, so O_i = sum_k Bt[i][k] T_i[code(4j - 1 + k)] with T_i = table U_i^T made once per network; only the 22
+// non-zero entries of Bt are read.  wino_bt's expressions and order, T_i[c_k] in place of d[k].
+// A code outside [0, ncode) reads no table and counts as the zero row here, silently; the gather beside this launch still writes that row
+// of x as NaN (vq.hip::gather_rows_kernel, "memory-safe and loud"), which reaches the stack's output through the tail's residual: the bad
+// code shows as NaN in its own four pose rows, no longer in every row its tiles' GEMMs touched.
+__global__ __launch_bounds__(256) void wino_codes_kernel(const WinoParams p) {
+#pragma clang fp contract(off)
+    const WinoItem w = wino_item(p);
+    if (!w.ok) return;
+    const int ncode = p.ncode[w.net];
+    const int64_t *codes = p.codes[w.net] + (long)w.b * p.L;
+    long off[6];   // of code row k within one T_i, -1: the zero row
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int t = 4 * w.j - 1 + k;
+        off[k] = -1;
+        if (t >= 0 && t < w.Lb) {
+            const int64_t r = codes[t];
+            if (r >= 0 && r < ncode) off[k] = (long)r * p.C + w.c;
+        }
+    }
+    const float *T = p.T[w.net];
+    const long ts = (long)ncode * p.C;
+    auto row = [&](const int i, const int k) { return off[k] >= 0 ? ld4(T + i * ts + off[k]) : f32x4{0.f, 0.f, 0.f, 0.f}; };
+    f32x4 v[6];
+    v[0] = (4.f * row(0, 0) - 5.f * row(0, 2)) + row(0, 4);
+    v[1] = ((row(1, 3) - 4.f * row(1, 1)) - 4.f * row(1, 2)) + row(1, 4);
+    v[2] = ((4.f * row(2, 1) - 4.f * row(2, 2)) - row(2, 3)) + row(2, 4);
+    v[3] = ((2.f * row(3, 3) - 2.f * row(3, 1)) - row(3, 2)) + row(3, 4);
+    v[4] = ((2.f * row(4, 1) - row(4, 2)) - 2.f * row(4, 3)) + row(4, 4);
+    v[5] = (4.f * row(5, 1) - 5.f * row(5, 3)) + row(5, 5);
+    const long cs = (long)p.B * p.J * p.C;
+    float *O = p.Ow[w.net] + w.row * p.C + w.c;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) st4(O + i * cs, v[i]);
+}
+
 }  // namespace
 
 hipError_t launch_wino(int which, const WinoParams &p, hipStream_t stream) {
@@ -166,13 +214,22 @@ hipError_t launch_wino(int which, const WinoParams &p, hipStream_t stream) {
     const long items = (long)p.B * p.J * (p.C >> 2);
     if (items + 255 >= (1l << 31)) return hipErrorInvalidValue;
     for (int n = 0; n < p.nnet; ++n) {
-        const bool in = which == 0 ? p.x[n] && p.V[n] : which == 1 ? p.O[n] && p.bias[n] && p.y[n] : p.O[n] && p.bias[n] && p.V[n];
+        const bool in = which == 0   ? p.x[n] && p.V[n]
+                        : which == 1 ? p.O[n] && p.bias[n] && p.y[n]
+                        : which == 2 ? p.O[n] && p.bias[n] && p.V[n]
+                                     : p.codes[n] && p.T[n] && p.Ow[n] && p.ncode[n] > 0;
         if (!in) return hipErrorInvalidValue;
     }
-    const dim3 grid((unsigned)((items + 255) / 256), p.nnet);
-    if (which == 0) hipLaunchKernelGGL(wino_in_kernel, grid, dim3(256), 0, stream, p);
-    else if (which == 1) hipLaunchKernelGGL(wino_out_kernel, grid, dim3(256), 0, stream, p);
-    else if (which == 2) hipLaunchKernelGGL(wino_out_in_kernel, grid, dim3(256), 0, stream, p);
+    // wino_out_in reads its two neighbour tiles: consecutive workgroups on one XCD fetch an O row into one L2, not three.  Rests on what
+    // ts_ctx_create probed (conv_sk_supported); the plain grid otherwise.  The same bits either way
+    const unsigned nb = (unsigned)((items + 255) / 256);
+    WinoParams q = p;
+    q.deal = knobs().wino_deal && conv_sk_supported() ? (int)nb : 0;
+    const dim3 grid = q.deal ? dim3(nb * p.nnet) : dim3(nb, p.nnet);
+    if (which == 0) hipLaunchKernelGGL(wino_in_kernel, grid, dim3(256), 0, stream, q);
+    else if (which == 1) hipLaunchKernelGGL(wino_out_kernel, grid, dim3(256), 0, stream, q);
+    else if (which == 2) hipLaunchKernelGGL(wino_out_in_kernel, grid, dim3(256), 0, stream, q);
+    else if (which == 3) hipLaunchKernelGGL(wino_codes_kernel, grid, dim3(256), 0, stream, q);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

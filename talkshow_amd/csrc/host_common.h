@@ -247,7 +247,9 @@ int conv_layer_params(const ConvLayer &layer, const float *x, int ldx, int B, in
                       float *out, int ldo, int out_col0, int n_store, ConvParams *p);
 
 // models.cpp: the six GEMMs per network of a Winograd-lowered layer (V, U, O of n = 1 or 2 networks; U rows npad apart) as one batched launch
-int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const *U, float *const *O, int M, int c, int npad, hipStream_t s);
+// (one_v: all six multiply the one (M, C) matrix V[i] points to)
+int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const *U, float *const *O, int M, int c, int npad, hipStream_t s,
+                  bool one_v = false);
 
 // accessors so that api.cpp needs no knowledge of the model structs
 int convnet_hidden(const ts_convnet *n);

@@ -185,8 +185,14 @@ struct WinoParams {
     const float *bias[2];  // [C]
     const float *res[2];   // wino_out, optional: (B, L, C), added before the activation
     float *y[2];           // wino_out: (B, L, C); every row is written, rows in [L_b, L) as zeros
+    // wino_codes only: the layer's input rows are rows of a table, one code per row
+    const int64_t *codes[2];   // (B, L) code indices; a row outside [0, L_b) is never read, a code outside [0, ncode) is the zero row
+    const float *T[2];         // (6, ncode, C): T_i = table U_i^T (models.cpp::ts_vqvae_create)
+    int ncode[2];
+    float *Ow[2];              // (6, B J, C): what wino_in and the layer's six GEMMs would leave in O
+    int deal;                  // set by launch_wino: 0 = grid (blocks, nnet); else blocks per network of a 1-D grid dealt to the XCDs in contiguous runs
 };
-// which: 0 wino_in (x -> V), 1 wino_out (O -> y), 2 wino_out_in (O of layer k -> V of layer k + 1)
+// which: 0 wino_in (x -> V), 1 wino_out (O -> y), 2 wino_out_in (O of layer k -> V of layer k + 1), 3 wino_codes (codes -> O of the first layer)
 hipError_t launch_wino(int which, const WinoParams &p, hipStream_t stream);
 // host: the six transformed matrices of folded taps w (cout, cin, 3), computed in double and rounded once; out (6, npad, cin)
 void wino_transform_weights(const float *w, int cout, int cin, int npad, float *out);
@@ -427,6 +433,8 @@ struct Knobs {
     bool wide_pair = true;      // TS_SKINNY_WIDE_PAIR=0: the wide kernel's tiles enumerated column-major instead of (clip-block pair, column tile, block of the pair) (A/B, tests)
     int wide_ablate = 0;        // TS_SKINNY_WIDE_ABLATE=2|4 (trace builds): no loads / no MFMAs in the wide kernel
     int conv_wino = -1;         // TS_CONV_WINO: the Winograd F(4,3) lowering of stride-1 k = 3 C -> C layers: -1 from WINO_MIN_C channels on, 0 never (direct everywhere), 1 every eligible geometry (tests).  Read when a network is created
+    bool wino_deal = true;      // TS_WINO_DEAL=0: the Winograd transform kernels on a plain (blocks, networks) grid instead of dealt to the XCDs in contiguous runs (A/B, tests; the same bits)
+    int vq_dec_tables = -1;     // TS_VQ_DEC_TABLES: the VQ decoders' first Winograd-lowered layer from per-code tables (conv_wino.hip::wino_codes): -1 where that layer is lowered and the network has a codebook, 0 never.  Read when a network is created
 };
 const Knobs &knobs();
 

@@ -311,7 +311,9 @@ int pack_linear_layer(const float *w, long ldw, const float *bias, int N, int K,
 // segment, no bias, no activation, no length mask (wino_out / wino_out_in mask).  Layers that take 128 x 128 tiles go to the ring engine's
 // dealt grid (tile 35), which takes batched problems like any others; plan_conv itself keeps batched problems on conv_gemm.hip, where the
 // face generator's have always run.  Every plan here is a whole-tile plan: a row's bits do not depend on M.
-int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const *U, float *const *O, int M, int c, int npad, hipStream_t s) {
+// one_v: V is ONE (M, C) matrix per network that all six problems multiply (the decoder's code tables, ts_vqvae_create).
+int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const *U, float *const *O, int M, int c, int npad, hipStream_t s,
+                  bool one_v) {
     auto dist = [](const float *a, const float *b) { return (long)((reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b)) / (intptr_t)sizeof(float)); };
     ConvParams p;
     std::memset(&p, 0, sizeof(p));
@@ -328,7 +330,8 @@ int run_wino_gemm(ts_ctx *ctx, int n, const float *const *V, const float *const 
     g.out = O[0];
     g.nseg = 1;
     g.seg[0] = ConvSeg{0, 0, c, 1};
-    p.x_zs1 = p.o_zs1 = (long)M * c;
+    p.o_zs1 = (long)M * c;
+    p.x_zs1 = one_v ? 0 : p.o_zs1;
     p.w_zs1 = (long)npad * c;
     if (n == 2) {
         p.x_zs0 = dist(V[1], V[0]);
@@ -505,10 +508,19 @@ size_t stack_wino_floats(const Stack &st, int c, int B, int L) {
     return st.tail.wino.p ? (size_t)6 * round_up(B * ((L + 3) / 4), 128) * c : 0;
 }
 
+// a stack whose input rows are rows of a table, gathered by code (the decoder's first stack): the codes (B, L) and T_i = table U_i^T of the
+// stack's first layer, per network
+struct CodeSrc {
+    const int64_t *codes[2];
+    const float *T[2];
+    int ncode[2];
+};
+
 // Res_CNR_Stack, every layer lowered (conv_wino.hip): wino_in on the stack's input (which stays in place for the tail's residual), then per
 // layer the GEMMs and wino_out_in into the next layer's V; the tail's GEMMs and wino_out with the residual and the ReLU.
+// src: wino_codes writes the first layer's O from the codes, in place of wino_in and that layer's GEMMs.
 int run_stack_wino(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool, int cur, int c, int B, int L, hipStream_t s, int *out_idx,
-                   const LenMask *mk) {
+                   const LenMask *mk, const CodeSrc *src) {
     WinoParams w;
     std::memset(&w, 0, sizeof(w));
     w.nnet = n;
@@ -523,11 +535,12 @@ int run_stack_wino(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool
         w.O[i] = pool[i]->wo.f();
         w.res[i] = pool[i]->buf(cur);
         w.y[i] = pool[i]->buf(o);
+        if (src) w.codes[i] = src->codes[i], w.T[i] = src->T[i], w.ncode[i] = src->ncode[i], w.Ow[i] = pool[i]->wo.f();
     }
     const ConvLayer *Lp[2];
     {
         MiscScope ms(ctx, s);
-        TS_HIP(launch_wino(0, w, s));
+        TS_HIP(launch_wino(src ? 3 : 0, w, s));
     }
     const size_t nl = st[0]->layers.size();
     for (size_t k = 0; k <= nl; ++k) {
@@ -538,7 +551,7 @@ int run_stack_wino(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool
         w.act = Lp[0]->act;
         const float *Vp[2] = {w.V[0], w.V[1]}, *Up[2] = {Lp[0]->wino.f(), n == 2 ? Lp[1]->wino.f() : nullptr};
         float *Op[2] = {pool[0]->wo.f(), n == 2 ? pool[1]->wo.f() : nullptr};
-        TS_TRY(run_wino_gemm(ctx, n, Vp, Up, Op, M, c, Lp[0]->npad, s));
+        if (k > 0 || !src) TS_TRY(run_wino_gemm(ctx, n, Vp, Up, Op, M, c, Lp[0]->npad, s));
         MiscScope ms(ctx, s);
         TS_HIP(launch_wino(k < nl ? 2 : 1, w, s));
     }
@@ -548,13 +561,14 @@ int run_stack_wino(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool
 
 // Res_CNR_Stack on pool buffer `cur` of each network; returns the index of the output buffer (same for all)
 int run_stack_n(ts_ctx *ctx, int n, const Stack *const *st, Pool *const *pool, int cur, int c, int B, int L, hipStream_t s,
-                int *out_idx, const LenMask *mk = nullptr) {
+                int *out_idx, const LenMask *mk = nullptr, const CodeSrc *src = nullptr) {
     bool wino = true;   // a stack's layers share one geometry: all of them are lowered or none
     for (int i = 0; i < n; ++i) {
         wino = wino && st[i]->tail.wino.p;
         for (const auto &l : st[i]->layers) wino = wino && l->wino.p;
     }
-    if (wino) return run_stack_wino(ctx, n, st, pool, cur, c, B, L, s, out_idx, mk);
+    if (wino) return run_stack_wino(ctx, n, st, pool, cur, c, B, L, s, out_idx, mk, src);
+    if (src) return fail("run_stack_n: code tables given for a stack that is not lowered");
     int h = cur, tmp = 0;
     const int ns[2] = {c, c};
     const ConvLayer *Lp[2];
@@ -653,6 +667,9 @@ struct ts_vqvae {
     ts_convnet enc;
     DevBuf codebook, code_sq;
     DevBuf aft_table;   // [ncode][hid] = aft_vq_conv(embedding row): Decoder's first layer as a gather table
+    // [6][ncode][hid], T_i = aft_table U_i^T of _dec_1's first layer, where that layer is Winograd-lowered and TS_VQ_DEC_TABLES allows
+    // (ts_vqvae_create): a decode from codes reads these in place of wino_in and that layer's six GEMMs.  Empty otherwise
+    DevBuf dec_tables;
     ConvLayer aft;      // aft_vq_conv itself: the decoder's first layer on CONTINUOUS latents (vqvae_1d.AE, ncode == 0)
     Stack d1, d2, d3;
     ConvLayer up2, up3, project;
@@ -747,7 +764,16 @@ int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const flo
     float *op[2];
     int ns[2];
     for (int i = 0; i < n; ++i) Sp[i] = &vq[i]->d1;
-    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o, k0));
+    CodeSrc src;
+    std::memset(&src, 0, sizeof(src));
+    // every network decodes codes and has its tables (the gathers above stay: x is the tail's residual).  Tables exist only where _dec_1's
+    // first layer is lowered, and a stack is lowered whole or not at all, so run_stack_n never meets src on its direct path (it refuses)
+    bool tables = true;
+    for (int i = 0; i < n; ++i) {
+        tables = tables && lat && lat[i] && !(z && z[i]) && vq[i]->dec_tables.p;
+        src.codes[i] = lat ? lat[i] : nullptr, src.T[i] = vq[i]->dec_tables.f(), src.ncode[i] = vq[i]->ncode;
+    }
+    TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o, k0, tables ? &src : nullptr));
     cur = o;
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &vq[i]->up2; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 2; }
@@ -937,6 +963,18 @@ int ts_vqvae_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int in_dim, int em
         TS_HIP(hipStreamSynchronize(0));
     }
     TS_TRY(pack_stack(sd, "decoder._dec_1", hid, nres, &vq->d1));
+    {   // _dec_1's first layer multiplies nothing but rows of aft_table: its six products per code, once (the layer's own batched launch)
+        const ConvLayer &l0 = vq->d1.layers.empty() ? vq->d1.tail : *vq->d1.layers[0];
+        if (ncode > 0 && l0.wino.p && knobs().vq_dec_tables != 0) {
+            // the six tables lie ncode rows apart (run_wino_gemm's o_zs1 = M c; wino_codes and the debug copy index them so); the
+            // rounding is slack after the LAST table only, as the V / O arenas have it (stack_wino_floats), never rows between tables
+            TS_TRY(vq->dec_tables.ensure(((size_t)5 * ncode + round_up(ncode, 128)) * hid * sizeof(float)));
+            const float *Vp[1] = {vq->aft_table.f()}, *Up[1] = {l0.wino.f()};
+            float *Op[1] = {vq->dec_tables.f()};
+            TS_TRY(run_wino_gemm(ctx, 1, Vp, Up, Op, ncode, hid, l0.npad, 0, true));
+            TS_HIP(hipStreamSynchronize(0));
+        }
+    }
     TS_TRY(pack_conv_layer(sd, "decoder._up_2.conv", "decoder._up_2.norm", "decoder._up_2.residual_layer", 2, 4, hid,
                            hid / 2, 1, &vq->up2));
     TS_TRY(pack_stack(sd, "decoder._dec_2", hid / 2, nres, &vq->d2));
@@ -1072,6 +1110,19 @@ int ts_body_vq_infer_mixed(ts_vqvae *vb, ts_vqvae *vh, const float *poses, const
         TS_HIP(hipMemcpy2DAsync(lp[k], sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t), (size_t)B * H, hipMemcpyDeviceToDevice, s));
     }
     return ts_vqvae_decode_pair_masked(vb, vh, lp[0], lp[1], lens, B, H, recon, s);
+}
+
+// test aid (talkshow_hip_debug.h): the decoder's code tables and what they were made from, copied to the host
+int ts_debug_vqvae_dec_tables(ts_vqvae *vq, float *tables, float *aft_table, float *u, const float **tables_dev) {
+    if (!vq) return -1;
+    if (!vq->dec_tables.p) return 0;
+    const ConvLayer &l0 = vq->d1.layers.empty() ? vq->d1.tail : *vq->d1.layers[0];
+    const size_t t = (size_t)vq->ncode * vq->hid * sizeof(float);
+    if (tables && copy_and_wait(tables, vq->dec_tables.p, 6 * t, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (aft_table && copy_and_wait(aft_table, vq->aft_table.p, t, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (u && copy_and_wait(u, l0.wino.p, (size_t)6 * l0.npad * vq->hid * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (tables_dev) *tables_dev = vq->dec_tables.f();
+    return 1;
 }
 
 }  // extern "C"
