@@ -994,6 +994,61 @@ int64_t ts_pixelcnn_stream_slot_rows(const ts_pixelcnn_stream *st, int slot);
  * NULL).  A session that never restarts a slot shows the figures of the same steps before the restart entry existed. */
 int ts_pixelcnn_stream_graph_stats(const ts_pixelcnn_stream *st, int64_t *graphs, int64_t *launches, double *flops);
 
+/* ---- slot state: save a slot's state, load it into any slot (rewind, branch, hand a clip over, park a user) --------------------
+ * What a slot carries from row to row is small and closed (the list under "slot restart"): three rows of the token ring,
+ * Q1[r & 3], Q0[r & 3], Q0[(r + 1) & 3], P(l, r & 1) for l >= 1, CR[l], its row origin and Philox clip index, and its two 64-entry
+ * repetition histories.  A restart writes "nothing above this row" there; a save reads those entries out and a load writes them back at
+ * another slot, another session row and another buffer phase, one small launch each way.
+ * THE RULE.  ts_pixelcnn_stream_save of slot b at session row r (the session's next row) gives a state S; the slot's clip then has
+ * n = r - origin[b] rows.  Loading S into slot b' of a session T of a network with the same dimensions and weights, at T's next row r',
+ * under Philox clip index k' (default: the index the source drew under) gives:
+ *   - continuation: slot b' produces from row r' on the codes and log-probabilities slot b would have produced from row r on under the
+ *     same later inputs (audio rows, mode, seed, the pieces of the steps);
+ *   - one-shot equivalence: under index k' and any later inputs its rows equal rows n, n+1, ... of ts_pixelcnn_generate* over the clip's
+ *     whole audio with the clip's first n code rows given and clip_index0 = k', under the same label or style and pieces, bit for bit.  A
+ *     code's Philox position stays its (row, column) inside the clip;
+ *   - neighbours: every other slot of T has the bits of T without the call;
+ *   - save is read-only: the source session's later bits, launches and graph captures are those without the call; it runs in stream
+ *     order behind the previous step and needs no synchronisation;
+ *   - the state carries the slot's conditioning rows CR (a blend row in force stays in force until a step brings style rows), the label
+ *     the slot stands for, both repetition histories with their length (a window carries across the move), the clip index and the
+ *     clip's row count;
+ *   - it does not carry sampling records, bias tables, session defaults or given rows: those belong to a step or to the target session
+ *     and count in the TARGET session's rows, as after a restart;
+ *   - fan-out: one state may be loaded into several slots in one call (state_index_host), each under its own clip index; a slot may be
+ *     loaded any number of times;
+ *   - portability: a state moves between sessions of different B and between two network handles with EQUAL WEIGHTS, and as bytes
+ *     through the host and to another device.  ts_slot_info records D, NL, NC and V, which a load checks; that the weights are equal is
+ *     the caller's business and is not checked.
+ * The device state is one row of ts_pixelcnn_slot_state_words(pix) 32-bit words per slot (a function of D and NL alone; 16-byte aligned
+ * blocks); the host record beside it is ts_slot_info.  A save at r < 3 is canonical: an entry the session's launches of rows r and r + 1
+ * would not have read (they leave out terms in a session's first three rows) is saved as the value a restart writes there, so a state
+ * is complete and phase-neutral whatever row it came from.  For the same reason a load at r' < min(n, 3) is REFUSED: the target's launches
+ * of those rows would leave out terms the clip's state holds (n <= r' is always fine: the clip is younger than the session).  For
+ * r' < n the slot's origin r' - n is negative; ts_pixelcnn_stream_slot_rows still gives n.
+ * Everything is checked on the host, the slot named, before anything is launched or any table moves: a slot out of range, a slot listed
+ * twice (load), a dimension or version mismatch, a state index outside the given states, r' < min(n, 3), a negative clip index.  The
+ * first load of a session does what its first restart does (the origin table; steps on the restart graph keys from there on); a session
+ * already on those keys captures nothing new, and neither call is in any graph.  A session that never saves or loads allocates,
+ * launches, captures and returns exactly what it did before these entries existed.  ts_body_stream_* (seamless sessions) has no such
+ * entries: its MFCC tail and code ring sit on the session's row grid. */
+#define TS_SLOT_STATE_VERSION 1
+typedef struct ts_slot_info {
+    int32_t D, NL, NC, V;   /* the network the state is of */
+    int32_t version;        /* TS_SLOT_STATE_VERSION */
+    int32_t hist;           /* entries of the repetition histories that count (<= 64), or -1: no penalty was running */
+    int64_t rows;           /* n: code rows of the clip */
+    int64_t clip_index;     /* the Philox clip index the slot drew under, or -1 (a never-restarted slot of a session that has not stepped) */
+    int64_t label;          /* the label the slot stands for where the library was told it (a restart or a load), or -1: the open label */
+} ts_slot_info;
+int64_t ts_pixelcnn_slot_state_words(const ts_pixelcnn *pix);   /* 32-bit words of one slot's state row; -1 for NULL */
+/* slots_host (n,) in [0, B) -> state_dev (n, words) fp32-typed words (16-byte aligned), info_host (n,) */
+int ts_pixelcnn_stream_save(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, float *state_dev, ts_slot_info *info_host, void *stream);
+/* slot slots_host[i] takes state row state_index_host[i] of state_dev (n_states, words) / info_host (n_states,); state_index_host NULL: row i
+ * (n_states == n) or row 0 (n_states == 1).  clip_index_host (n,) or NULL: each state's own index. */
+int ts_pixelcnn_stream_load(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, const float *state_dev, int n_states,
+                            const int32_t *state_index_host, const ts_slot_info *info_host, const int64_t *clip_index_host, void *stream);
+
 /* ---- seamless sessions ---------------------------------------------------------------------------------------------------
  * A body session fed MFCC chunks of ANY length that returns, over its pushes and one flush, the codes and poses ts_body_pixel_infer
  * returns for the concatenated audio, bit for bit (same mode, seed and clip_index0) — where a plain session (ts_audioenc_forward,

@@ -416,6 +416,16 @@ int ts_debug_iota_i64(int64_t *dst, int n, int64_t first, void *stream);
 int ts_debug_i64_to_i32(const int64_t *src, int32_t *dst, long n, void *stream);
 /* dst[0 .. 2] = a, b, c, carried by the launch's own arguments. */
 int ts_debug_set_words3(uint64_t *dst, uint64_t a, uint64_t b, uint64_t c, void *stream);
+/* "slot state" (talkshow_hip.h): slot_save_kernel / slot_load_kernel alone on caller buffers in a session's shapes — tok32 (B, 4, 2) int32,
+ * Q1 / Q0 (4, B, 4D), P (NL, 2, B, 4D), CR (NL, B, 2D), bv (NL, 4D), rep_ring (B, 2, 64) int32, tables (NL, NC, 2D), state rows of
+ * 12 D + (NL - 1) 4 D + NL 2 D + 136 words.  slots / hist / index / origin are DEVICE tables (n,).  open_labels (B,) int64 with tables, or
+ * both NULL.  A slot outside [0, B) or an index outside [0, n_states) writes nothing. */
+int ts_debug_slot_save(const int32_t *slots, const int32_t *hist, int n, int B, int row, int D, int NL, int NC, const int32_t *tok32,
+                       const float *Q1, const float *Q0, const float *P, const float *CR, const float *bv, const int32_t *rep_ring,
+                       const int64_t *open_labels, const float *tables, float *state, void *stream);
+int ts_debug_slot_load(const int32_t *slots, const int32_t *index, const int32_t *origin, int n, int n_states, int B, int row, int D, int NL,
+                       int32_t *tok32, float *Q1, float *Q0, float *P, float *CR, int32_t *rep_ring, int32_t *row_origin, const float *state,
+                       void *stream);
 /* out[j] = sum over c ascending of e[j][c]^2 in fp32, e (n, dim) dense. */
 int ts_debug_row_sqnorm(const float *e, int n, int dim, float *out, void *stream);
 

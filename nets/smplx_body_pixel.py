@@ -863,5 +863,21 @@ class BodyStream:
         self.pix.restart(slots, id, style=style, clip_indices=clip_indices)
         return self
 
+    def save(self, slots):
+        """`PixelCNNStream.save`: the state of the listed slots' clips.  A plain session runs the audio encoder and the VQ decoders on each
+        chunk per clip, so the chain's slot state is all a clip carries between pushes."""
+        return self.pix.save(slots)
+
+    def load(self, slots, state, *, clip_indices=None):
+        """`PixelCNNStream.load`: the listed slots carry the saved clips on with the next push."""
+        self.pix.load(slots, state, clip_indices=clip_indices)
+        return self
+
+    def fork(self, src, dst_slots, *, clip_indices=None):
+        """`PixelCNNStream.fork`: the listed slots carry slot `src`'s clip on, each under its own clip index (default: the source's, which
+        makes them its twins: the same poses for the same audio)."""
+        self.pix.fork(src, dst_slots, clip_indices=clip_indices)
+        return self
+
     def close(self):
         self.pix.close()

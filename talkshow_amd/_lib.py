@@ -40,6 +40,13 @@ class TsRepeat(C.Structure):
 
 _rp = C.POINTER(TsRepeat)
 TS_REPEAT_MAX_WINDOW = 64
+TS_SLOT_STATE_VERSION = 1
+
+
+class TsSlotInfo(C.Structure):
+    """ts_slot_info (include/talkshow_hip.h, "slot state"): the host record beside one slot's state row."""
+    _fields_ = [("D", C.c_int32), ("NL", C.c_int32), ("NC", C.c_int32), ("V", C.c_int32), ("version", C.c_int32), ("hist", C.c_int32),
+                ("rows", C.c_int64), ("clip_index", C.c_int64), ("label", C.c_int64)]
 
 
 class SkinnySeg(C.Structure):
@@ -149,6 +156,11 @@ SIGNATURES = {
     # slot restart: slots (n,) host, n, labels (n,) host or NULL, style (n,NC) device or NULL, clip indices (n,) host, stream
     "ts_pixelcnn_stream_restart": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp]),
     "ts_pixelcnn_stream_slot_rows": (_i64, [_vp, _i]),
+    # slot state: slots (n,) host, n, state (n, words) device, info (n,) host, stream / ... states, n_states, index (n,) host or NULL, info
+    # (n_states,) host, clip indices (n,) host or NULL, stream
+    "ts_pixelcnn_slot_state_words": (_i64, [_vp]),
+    "ts_pixelcnn_stream_save": (_i, [_vp, C.POINTER(C.c_int32), _i, _vp, C.POINTER(TsSlotInfo), _vp]),
+    "ts_pixelcnn_stream_load": (_i, [_vp, C.POINTER(C.c_int32), _i, _vp, _i, C.POINTER(C.c_int32), C.POINTER(TsSlotInfo), C.POINTER(C.c_int64), _vp]),
     "ts_pixelcnn_stream_graph_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_double)]),
     # seamless sessions: the step's arguments around (mfcc, t) / the two outputs, then the pieces of ts_pixelcnn_stream_step_ctl
     "ts_body_stream_open": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp)]),
@@ -176,6 +188,8 @@ SIGNATURES = {
     "ts_debug_i64_to_i32": (_i, [_vp, _vp, C.c_long, _vp]),
     "ts_debug_set_words3": (_i, [_vp, _u64, _u64, _u64, _vp]),
     "ts_debug_row_sqnorm": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ts_debug_slot_save": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 11),
+    "ts_debug_slot_load": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 9),
     "ts_face_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, C.POINTER(_vp)]),
     "ts_face_destroy": (None, [_vp]),
     "ts_face_generate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1385,6 +1385,27 @@ int ts_debug_set_words3(uint64_t *dst, uint64_t a, uint64_t b, uint64_t c, void 
     TS_HIP(ts::launch_set_words3(dst, a, b, c, (hipStream_t)stream));
     return 0;
 }
+int ts_debug_slot_save(const int32_t *slots, const int32_t *hist, int n, int B, int row, int D, int NL, int NC, const int32_t *tok32,
+                       const float *Q1, const float *Q0, const float *P, const float *CR, const float *bv, const int32_t *rep_ring,
+                       const int64_t *open_labels, const float *tables, float *state, void *stream) {
+    ts::SlotSaveParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.slots = slots, q.hist = hist, q.n = n, q.B = B, q.row = row, q.D = D, q.NL = NL, q.NC = NC, q.R = 4;
+    q.tok32 = tok32, q.Q1 = Q1, q.Q0 = Q0, q.P = P, q.CR = CR, q.bv = bv, q.rep_ring = rep_ring;
+    q.open_labels = open_labels, q.tables = tables, q.state = state;
+    TS_HIP(ts::launch_slot_save(q, (hipStream_t)stream));
+    return 0;
+}
+int ts_debug_slot_load(const int32_t *slots, const int32_t *index, const int32_t *origin, int n, int n_states, int B, int row, int D, int NL,
+                       int32_t *tok32, float *Q1, float *Q0, float *P, float *CR, int32_t *rep_ring, int32_t *row_origin, const float *state,
+                       void *stream) {
+    ts::SlotLoadParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.slots = slots, q.index = index, q.origin = origin, q.n = n, q.n_states = n_states, q.B = B, q.row = row, q.D = D, q.NL = NL, q.R = 4;
+    q.tok32 = tok32, q.Q1 = Q1, q.Q0 = Q0, q.P = P, q.CR = CR, q.rep_ring = rep_ring, q.row_origin = row_origin, q.state = state;
+    TS_HIP(ts::launch_slot_load(q, (hipStream_t)stream));
+    return 0;
+}
 int ts_debug_row_sqnorm(const float *e, int n, int dim, float *out, void *stream) {
     if (!e || !out || n < 1 || dim < 1) return fail("ts_debug_row_sqnorm: bad argument");
     TS_HIP(ts::launch_row_sqnorm(e, n, dim, out, (hipStream_t)stream));

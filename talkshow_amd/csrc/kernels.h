@@ -576,6 +576,59 @@ struct SlotResetParams {
 };
 hipError_t launch_slot_reset(const SlotResetParams &p, hipStream_t stream);
 
+// "slot state" of a streaming session (talkshow_hip.h): what a restart writes, read out of one slot and written back at another slot, another
+// session row and another buffer phase.  A state is ONE ROW of 32-bit words per slot; the layout is a function of (D, NL) alone (offsets
+// in words; every float block starts at a multiple of 4 words, the integer tail is a multiple of 4 words long):
+//   q1   [4D]          Q1[r & 3]                      q0a [4D]  Q0[r & 3]             q0b [4D]  Q0[(r + 1) & 3]
+//   p    [NL-1][4D]    P(l, r & 1), l = 1 .. NL-1     cr  [NL][2D]  CR[l]
+//   tok  [8]  int32    the codes of rows r-1, r-2, r-3 (two columns each: word 2 k + c is row r-1-k, column c), then two words of 0
+//   rep  [2][64] int32 the repetition histories BY AGE: word 64 c + k is column c's code of row r-1-k for k < hist, -1 beyond
+struct SlotStateLayout {
+    int q1, q0a, q0b, p, cr, tok, rep, words;
+};
+constexpr int SLOT_STATE_TOK_WORDS = 8;
+__host__ __device__ inline SlotStateLayout slot_state_layout(int D, int NL) {
+    SlotStateLayout L;
+    L.q1 = 0, L.q0a = 4 * D, L.q0b = 8 * D, L.p = 12 * D;
+    L.cr = L.p + (NL - 1) * 4 * D;
+    L.tok = L.cr + NL * 2 * D;
+    L.rep = L.tok + SLOT_STATE_TOK_WORDS;
+    L.words = L.rep + 2 * 64;
+    return L;
+}
+// Save: state row i = the state of slot slots[i] at session row `row` (the session's NEXT row), canonical for row < 3: an entry the
+// session's launches of rows `row` and `row + 1` would not read is saved as the value a restart writes there (token rows below 0 as -1, Q1
+// and Q0[(row + 1) & 3] as +0.0 for row < 2, Q0[row & 3] as +0.0 for row < 3, P as bv[l] at row 0).  hist[i]: how many entries of the slot's
+// histories mean anything (<= 64; <= 0: none).  open_labels (with tables, NC) set: CR has not been written yet (a session at row 0) and
+// the rows are tables[l][open_labels[slot]], what the first step will write.  Reads the session's buffers, writes n rows of `state` only.
+struct SlotSaveParams {
+    const int32_t *slots;    // (n,) in [0, B); a slot outside writes nothing
+    const int32_t *hist;     // (n,)
+    int n, B, row;
+    int D, NL, NC, R;
+    const int *tok32;
+    const float *Q1, *Q0, *P, *CR, *bv;
+    const int32_t *rep_ring;       // [B][2][64]
+    const int64_t *open_labels;    // (B,) or null
+    const float *tables;           // [NL][NC][2D], read with open_labels only
+    float *state;                  // (n, words)
+};
+hipError_t launch_slot_save(const SlotSaveParams &p, hipStream_t stream);
+// Load: slot slots[i] takes state row index[i] (one row may serve many slots) at session row `row`: the ring rows row-1 .. row-3 that exist,
+// Q1[row & 3], Q0[row & 3], Q0[(row + 1) & 3], P(l, row & 1), CR[l], the histories at ring[(row - 1 - k) & 63], row_origin[slot] = origin[i].
+// A slot outside [0, B) or an index outside [0, n_states) writes nothing.
+struct SlotLoadParams {
+    const int32_t *slots, *index, *origin;   // (n,) each
+    int n, n_states, B, row;
+    int D, NL, R;
+    int *tok32;
+    float *Q1, *Q0, *P, *CR;
+    int32_t *rep_ring;
+    int32_t *row_origin;     // (B,)
+    const float *state;      // (n_states, words)
+};
+hipError_t launch_slot_load(const SlotLoadParams &p, hipStream_t stream);
+
 // Per-clip sampling controls (talkshow_hip.h: ts_sampling and the rule of steps 1-5).  The device record of a clip: 1 / temperature as the
 // HOST computed it in fp32, top_p, top_k (0 or >= V: off).  A sibling of SampleParams: the sampler without controls keeps its arguments (vq.hip: sample_ctl_body behind
 // sample_ctl_kernel<FAST, LP>; the samplers without controls share sample_plain_body).

@@ -234,14 +234,20 @@ struct ts_pixelcnn_stream {
     ts_pixelcnn::Work w;
     DevBuf label;
     // "repetition penalty" on a session: per clip, the first row of its current unbroken run of rows written under window > 0 (what
-    // SampleRep::from_row carries to the samplers), -1 while the clip has no such run
+    // SampleRep::from_row carries to the samplers), REP_NONE while the clip has no such run (a value no row takes: a loaded slot's run may
+    // have begun below the session's row 0, "slot state")
+    static constexpr int32_t REP_NONE = INT32_MIN;
     std::vector<int32_t> rep_from;
+    int64_t last_clip0 = -1;           // clip_index0 of the latest step (-1: none yet): what a never-restarted slot b drew under, less b
     // "slot restart" (talkshow_hip.h): nothing below exists, on the host or the device, until the session's first restart
     bool restarted = false;            // steps bind row_origin and the clip table (sampler bit 7: graph keys of their own)
     bool cr_ready = false;             // CR was written from the labels ahead of a restart at row 0: the first step leaves it alone
     std::vector<int32_t> origin;       // per slot: the session row at which its current clip began
     std::vector<int64_t> clip_index;   // per slot: the Philox clip index given at its restart, -1 while it has never restarted
     DevBuf row_origin, restart_tab;    // (B,) int32 the samplers read; {slots (B,), labels (B,)} of the restart being queued
+    // "slot state" (talkshow_hip.h): nothing below exists until the session's first save or load
+    DevBuf state_tab;                  // three (B,) int32 tables of the save / load being queued (kernel arguments, in stream order)
+    std::vector<int64_t> slot_label;   // per slot: the label a restart or a load brought, -1: the one given at open (the caller holds it)
 };
 
 namespace {
@@ -1808,7 +1814,7 @@ int ts_pixelcnn_stream_open(ts_pixelcnn *p, const int64_t *label, int B, int max
     TS_TRY(ensure_work(p, &st->w, B, std::max(max_chunk_rows, 4)));
     // a step's given block is staged whole ((B,Hc,2) with Hc up to max_chunk_rows), where a one-shot pass stages CHUNK_ROWS rows at a time
     TS_TRY(st->w.given_int.ensure((size_t)B * std::max(max_chunk_rows, CHUNK_ROWS) * 2 * sizeof(int64_t)));
-    st->rep_from.assign(B, -1);
+    st->rep_from.assign(B, ts_pixelcnn_stream::REP_NONE);
     TS_TRY(st->label.ensure((size_t)B * sizeof(int64_t)));
     // (not hipMemcpy: another thread may be capturing a graph while this one opens a session)
     TS_HIP(copy_and_wait(st->label.p, label, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice));
@@ -1843,9 +1849,10 @@ int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, cons
     const std::vector<int32_t> lens(B, 4 * Hc);   // the rules of the mixed entry, on a pass of B clips of Hc rows
     SamplerTables t;
     TS_TRY(t.build(o, B, p->V, mode, lens.data(), sampler_names(who)));
-    std::vector<int32_t> rep_from(B, -1);   // the session's table behind this step, kept only if the step is queued
+    constexpr int32_t REP_NONE = ts_pixelcnn_stream::REP_NONE;
+    std::vector<int32_t> rep_from(B, REP_NONE);   // the session's table behind this step, kept only if the step is queued
     for (size_t b = 0; b < t.rep.size(); ++b)
-        if (t.rep[b].window > 0) t.rep[b].from_row = rep_from[b] = st->rep_from[b] >= 0 ? st->rep_from[b] : r0;
+        if (t.rep[b].window > 0) t.rep[b].from_row = rep_from[b] = st->rep_from[b] != REP_NONE ? st->rep_from[b] : r0;
     for (int32_t &g : t.given_rows) g += r0;   // the table the samplers read holds absolute bounds: clip b is forced at positions below 2 (r0 + g_b)
     if (r0 == 0 && !o.style && !st->cr_ready) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
     if (o.style) TS_TRY(class_rows_style(p, w, o.style, B, s));   // CR stays as written until a later step brings other rows
@@ -1867,6 +1874,7 @@ int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, cons
     TS_TRY(run_rows(p, c, r0, r0 + Hc, graph, std::make_tuple(B, Hc, 1000 + ring_phase(r0), mode, 0, sampler_bits(c, o.logprob)), uniforms, codes,
                     o.logprob, s));
     st->rep_from.swap(rep_from);
+    st->last_clip0 = clip0;
     st->rows += Hc;
     return 0;
 }
@@ -1958,12 +1966,146 @@ int ts_pixelcnn_stream_restart(ts_pixelcnn_stream *st, const int32_t *slots_host
         TS_HIP(launch_style_rows(y, s));
     }
     if (!st->restarted) st->origin.assign(B, 0), st->clip_index.assign(B, -1);
+    if (st->slot_label.empty()) st->slot_label.assign(B, -1);
     st->restarted = st->cr_ready = true;
     for (int i = 0; i < n; ++i) {
         const int b = slots_host[i];
         st->origin[b] = (int32_t)st->rows;
         st->clip_index[b] = clip_index_host[i];
-        st->rep_from[b] = -1;   // a penalty starts from an empty history, as a one-shot clip's does
+        if (labels_host) st->slot_label[b] = labels_host[i];   // ("slot state": the label the slot stands for; a weight row keeps the old one)
+        st->rep_from[b] = ts_pixelcnn_stream::REP_NONE;   // a penalty starts from an empty history, as a one-shot clip's does
+    }
+    return 0;
+}
+
+// ---- "slot state" (talkshow_hip.h): save a slot's state, load it into any slot -------------------------------------------------------------
+int64_t ts_pixelcnn_slot_state_words(const ts_pixelcnn *p) { return p ? (int64_t)slot_state_layout(p->D, p->NL).words : -1; }
+
+// Read-only on the session: the tables of the call as kernel arguments and slot_save_kernel, in stream order behind the previous step and
+// in no graph.  Everything is checked before anything is launched.
+int ts_pixelcnn_stream_save(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, float *state_dev, ts_slot_info *info_host, void *stream) {
+    const std::string who = "ts_pixelcnn_stream_save: ";
+    if (!st || !slots_host || !state_dev || !info_host) return fail(who + "null argument");
+    const int B = st->B;
+    if (n < 1 || n > B) return fail(who + "n must be in [1, B = " + std::to_string(B) + "], got " + std::to_string(n));
+    for (int i = 0; i < n; ++i)
+        if (slots_host[i] < 0 || slots_host[i] >= B)
+            return fail(who + "entry " + std::to_string(i) + ": slot " + std::to_string(slots_host[i]) + " is outside [0, B = " + std::to_string(B) + ")");
+    if (reinterpret_cast<uintptr_t>(state_dev) & 15) return fail(who + "the state block must be 16-byte aligned");
+    ts_pixelcnn *p = st->p;
+    TS_HIP(hipSetDevice(p->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ts_pixelcnn::Work *w = &st->w;
+    TS_TRY(st->state_tab.ensure((size_t)3 * B * sizeof(int32_t)));
+    const int r = (int)st->rows;
+    std::vector<int32_t> tab(2 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int b = slots_host[i];
+        const int32_t from = st->rep_from[b];
+        const int hist = from == ts_pixelcnn_stream::REP_NONE ? -1 : std::min(r - from, SAMPLE_REP_RING);
+        tab[i] = b, tab[n + i] = hist;
+        ts_slot_info &o = info_host[i];
+        o.D = p->D, o.NL = p->NL, o.NC = p->NC, o.V = p->V, o.version = TS_SLOT_STATE_VERSION, o.hist = hist;
+        o.rows = st->rows - (st->restarted ? st->origin[b] : 0);
+        o.clip_index = st->restarted && st->clip_index[b] >= 0 ? st->clip_index[b] : (st->last_clip0 >= 0 ? st->last_clip0 + b : -1);
+        o.label = st->slot_label.empty() ? -1 : st->slot_label[b];
+    }
+    MiscScope ms(p->ctx, s);
+    int32_t *tab_dev = static_cast<int32_t *>(st->state_tab.p);
+    TS_HIP(launch_put_words(tab_dev, tab.data(), 2l * n, s));
+    SlotSaveParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.slots = tab_dev, q.hist = tab_dev + n;
+    q.n = n, q.B = B, q.row = r;
+    q.D = p->D, q.NL = p->NL, q.NC = p->NC, q.R = 4;
+    q.tok32 = w->tok32.i(), q.Q1 = w->Q1.f(), q.Q0 = w->Q0.f(), q.P = w->P.f(), q.CR = w->CR.f(), q.bv = p->bv_all.f();
+    q.rep_ring = static_cast<const int32_t *>(w->rep_ring.p);
+    if (st->rows == 0 && !st->cr_ready)   // CR is the first step's to write: the rows it will hold are the open labels'
+        q.open_labels = static_cast<const int64_t *>(st->label.p), q.tables = p->cls_all.f();
+    q.state = state_dev;
+    TS_HIP(launch_slot_save(q, s));
+    return 0;
+}
+
+// Everything is checked before anything is launched or any table moves.  The launches: what a session's first restart does (the origin
+// table), the tables of the call as kernel arguments, slot_load_kernel — ahead of the next step's replay and in no graph.
+int ts_pixelcnn_stream_load(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, const float *state_dev, int n_states,
+                            const int32_t *state_index_host, const ts_slot_info *info_host, const int64_t *clip_index_host, void *stream) {
+    const std::string who = "ts_pixelcnn_stream_load: ";
+    if (!st || !slots_host || !state_dev || !info_host) return fail(who + "null argument");
+    const int B = st->B;
+    if (n < 1 || n > B) return fail(who + "n must be in [1, B = " + std::to_string(B) + "], got " + std::to_string(n));
+    if (n_states < 1) return fail(who + "no state given");
+    if (!state_index_host && n_states != 1 && n_states != n)
+        return fail(who + std::to_string(n) + " slots but " + std::to_string(n_states) + " states (one for all listed slots, one each, or an index)");
+    if (reinterpret_cast<uintptr_t>(state_dev) & 15) return fail(who + "the state block must be 16-byte aligned");
+    for (int i = 0; i < n; ++i)
+        if (slots_host[i] < 0 || slots_host[i] >= B)
+            return fail(who + "entry " + std::to_string(i) + ": slot " + std::to_string(slots_host[i]) + " is outside [0, B = " + std::to_string(B) + ")");
+    ts_pixelcnn *p = st->p;
+    const long r = st->rows;
+    std::vector<char> seen(B, 0);
+    std::vector<int32_t> tab(3 * (size_t)n);
+    std::vector<int64_t> clips(n);
+    for (int i = 0; i < n; ++i) {
+        const int b = slots_host[i];
+        const std::string slot = "slot " + std::to_string(b);
+        if (seen[b]++) return fail(who + slot + " is listed twice");
+        const int k = state_index_host ? state_index_host[i] : (n_states == 1 ? 0 : i);
+        if (k < 0 || k >= n_states) return fail(who + slot + ": state index " + std::to_string(k) + " is outside the " + std::to_string(n_states) + " states given");
+        const ts_slot_info &o = info_host[k];
+        if (o.version != TS_SLOT_STATE_VERSION)
+            return fail(who + slot + ": the state has layout version " + std::to_string(o.version) + ", this library reads " + std::to_string(TS_SLOT_STATE_VERSION));
+        if (o.D != p->D || o.NL != p->NL || o.NC != p->NC || o.V != p->V)
+            return fail(who + slot + ": the state is of a network with (D, NL, NC, V) = (" + std::to_string(o.D) + ", " + std::to_string(o.NL) + ", " +
+                        std::to_string(o.NC) + ", " + std::to_string(o.V) + "), this session's has (" + std::to_string(p->D) + ", " + std::to_string(p->NL) +
+                        ", " + std::to_string(p->NC) + ", " + std::to_string(p->V) + ")");
+        if (o.rows < 0 || o.rows > (1l << 30) || o.hist < -1 || o.hist > SAMPLE_REP_RING || o.hist > o.rows || o.label < -1 || o.label >= p->NC)
+            return fail(who + slot + ": the state's record is damaged (rows " + std::to_string(o.rows) + ", history " + std::to_string(o.hist) + ", label " +
+                        std::to_string(o.label) + ")");
+        if (r < std::min<long>(o.rows, 3))
+            return fail(who + slot + ": a clip of " + std::to_string(o.rows) + " rows cannot be loaded at session row " + std::to_string(r) +
+                        " (the session's rows 0 to 2 leave out terms the clip's state holds: load at row min(rows, 3) or later)");
+        clips[i] = clip_index_host ? clip_index_host[i] : o.clip_index;
+        if (clips[i] < 0)
+            return fail(who + slot + ": clip index " + std::to_string(clips[i]) + " is negative" + (clip_index_host ? "" : " (the state records none: give one)"));
+        tab[i] = b, tab[n + i] = k, tab[2 * n + i] = (int32_t)(r - o.rows);
+    }
+    TS_HIP(hipSetDevice(p->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    ts_pixelcnn::Work *w = &st->w;
+    if (st->rows == 0 && !st->cr_ready)   // as a restart at row 0: the open labels' rows first, the loaded slots' rows then replace theirs
+        TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
+    MiscScope ms(p->ctx, s);
+    TS_TRY(st->state_tab.ensure((size_t)3 * B * sizeof(int32_t)));
+    if (!st->restarted) {   // what the session's first restart does: the tables exist from here on, every origin 0 in stream order
+        TS_TRY(st->row_origin.ensure((size_t)B * sizeof(int32_t)));
+        TS_TRY(st->restart_tab.ensure((size_t)2 * B * sizeof(int32_t)));
+        const std::vector<int32_t> zeros(B, 0);
+        TS_HIP(launch_put_words(static_cast<int *>(st->row_origin.p), zeros.data(), B, s));
+    }
+    int32_t *tab_dev = static_cast<int32_t *>(st->state_tab.p);
+    TS_HIP(launch_put_words(tab_dev, tab.data(), 3l * n, s));
+    SlotLoadParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.slots = tab_dev, q.index = tab_dev + n, q.origin = tab_dev + 2 * n;
+    q.n = n, q.n_states = n_states, q.B = B, q.row = (int)r;
+    q.D = p->D, q.NL = p->NL, q.R = 4;
+    q.tok32 = w->tok32.i(), q.Q1 = w->Q1.f(), q.Q0 = w->Q0.f(), q.P = w->P.f(), q.CR = w->CR.f();
+    q.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
+    q.row_origin = static_cast<int32_t *>(st->row_origin.p);
+    q.state = state_dev;
+    TS_HIP(launch_slot_load(q, s));
+    if (!st->restarted) st->origin.assign(B, 0), st->clip_index.assign(B, -1);
+    if (st->slot_label.empty()) st->slot_label.assign(B, -1);
+    st->restarted = st->cr_ready = true;
+    for (int i = 0; i < n; ++i) {
+        const int b = slots_host[i];
+        const ts_slot_info &o = info_host[tab[n + i]];
+        st->origin[b] = tab[2 * n + i];
+        st->clip_index[b] = clips[i];
+        st->rep_from[b] = o.hist < 0 ? ts_pixelcnn_stream::REP_NONE : (int32_t)(r - o.hist);
+        st->slot_label[b] = o.label;
     }
     return 0;
 }

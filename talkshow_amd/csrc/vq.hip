@@ -795,6 +795,109 @@ hipError_t launch_slot_reset(const SlotResetParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// "slot state" (kernels.h: SlotSaveParams, SlotLoadParams), in slot_reset_kernel's shape: one workgroup per (listed slot, layer l) for
+// P(l) and CR[l], and one more per slot (blockIdx.y == NL) for the token ring, the Q rows and the histories; float4 rows, plain vector
+// loads and stores.  Every index is bounded by the launcher's checks and the slot / state-index tests below.
+__global__ __launch_bounds__(256) void slot_save_kernel(const SlotSaveParams p) {
+    const int slot = p.slots[blockIdx.x], l = (int)blockIdx.y, tid = threadIdx.x;
+    if (slot < 0 || slot >= p.B) return;
+    const int D4 = 4 * p.D, D2 = 2 * p.D, r = p.row;
+    const SlotStateLayout L = slot_state_layout(p.D, p.NL);
+    float *out = p.state + (long)blockIdx.x * L.words;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (l == p.NL) {
+        int32_t *tok = reinterpret_cast<int32_t *>(out + L.tok), *rep = reinterpret_cast<int32_t *>(out + L.rep);
+        if (tid < SLOT_STATE_TOK_WORDS) {   // rows r-1, r-2, r-3 of the ring, both columns; a row below 0 is the restart's -1
+            int v = 0;
+            if (tid < 6) {
+                const int rr = r - 1 - (tid >> 1);
+                v = rr >= 0 ? p.tok32[((long)slot * p.R + rr % p.R) * 2 + (tid & 1)] : -1;
+            }
+            tok[tid] = v;
+        }
+        if (tid >= 128) {   // both histories by age: entry k is the code of row r-1-k
+            const int k = tid - 128, col = k >> 6, age = k & 63;
+            rep[k] = age < p.hist[blockIdx.x] ? p.rep_ring[((long)slot * 2 + col) * SAMPLE_REP_RING + ((r - 1 - age) & (SAMPLE_REP_RING - 1))] : -1;
+        }
+        const float4 *q1 = reinterpret_cast<const float4 *>(p.Q1 + ((long)(r & 3) * p.B + slot) * D4);
+        const float4 *q0a = reinterpret_cast<const float4 *>(p.Q0 + ((long)(r & 3) * p.B + slot) * D4);
+        const float4 *q0b = reinterpret_cast<const float4 *>(p.Q0 + ((long)((r + 1) & 3) * p.B + slot) * D4);
+        float4 *o1 = reinterpret_cast<float4 *>(out + L.q1), *oa = reinterpret_cast<float4 *>(out + L.q0a), *ob = reinterpret_cast<float4 *>(out + L.q0b);
+        for (int q = tid; q < D4 / 4; q += 256) {   // what rows r and r + 1 of the session do not read may never have been written
+            float4 a = q1[q], b = q0a[q], c = q0b[q];
+            if (r < 2) a = zero, c = zero;
+            if (r < 3) b = zero;
+            o1[q] = a, oa[q] = b, ob[q] = c;
+        }
+        return;
+    }
+    if (l >= 1) {
+        const float4 *src = reinterpret_cast<const float4 *>(r == 0 ? p.bv + (long)l * D4 : p.P + ((long)(l * 2 + (r & 1)) * p.B + slot) * D4);
+        float4 *dst = reinterpret_cast<float4 *>(out + L.p + (long)(l - 1) * D4);
+        for (int q = tid; q < D4 / 4; q += 256) dst[q] = src[q];
+    }
+    const float *cr = p.CR + ((long)l * p.B + slot) * D2;
+    if (p.open_labels) {   // a session at row 0: the first step has not written CR yet; its rows will be the open label's
+        const int64_t label = p.open_labels[slot];
+        if (label < 0 || label >= p.NC) return;
+        cr = p.tables + ((long)l * p.NC + label) * D2;
+    }
+    const float4 *src = reinterpret_cast<const float4 *>(cr);
+    float4 *dst = reinterpret_cast<float4 *>(out + L.cr + (long)l * D2);
+    for (int q = tid; q < D2 / 4; q += 256) dst[q] = src[q];
+}
+__global__ __launch_bounds__(256) void slot_load_kernel(const SlotLoadParams p) {
+    const int slot = p.slots[blockIdx.x], idx = p.index[blockIdx.x], l = (int)blockIdx.y, tid = threadIdx.x;
+    if (slot < 0 || slot >= p.B || idx < 0 || idx >= p.n_states) return;
+    const int D4 = 4 * p.D, D2 = 2 * p.D, r = p.row;
+    const SlotStateLayout L = slot_state_layout(p.D, p.NL);
+    const float *in = p.state + (long)idx * L.words;
+    if (l == p.NL) {
+        const int32_t *tok = reinterpret_cast<const int32_t *>(in + L.tok), *rep = reinterpret_cast<const int32_t *>(in + L.rep);
+        if (tid < 6) {
+            const int rr = r - 1 - (tid >> 1);
+            if (rr >= 0) p.tok32[((long)slot * p.R + rr % p.R) * 2 + (tid & 1)] = tok[tid];
+        }
+        if (tid == 6) p.row_origin[slot] = p.origin[blockIdx.x];
+        if (tid >= 128) {
+            const int k = tid - 128, col = k >> 6, age = k & 63;
+            p.rep_ring[((long)slot * 2 + col) * SAMPLE_REP_RING + ((r - 1 - age) & (SAMPLE_REP_RING - 1))] = rep[k];
+        }
+        float4 *q1 = reinterpret_cast<float4 *>(p.Q1 + ((long)(r & 3) * p.B + slot) * D4);
+        float4 *q0a = reinterpret_cast<float4 *>(p.Q0 + ((long)(r & 3) * p.B + slot) * D4);
+        float4 *q0b = reinterpret_cast<float4 *>(p.Q0 + ((long)((r + 1) & 3) * p.B + slot) * D4);
+        const float4 *i1 = reinterpret_cast<const float4 *>(in + L.q1), *ia = reinterpret_cast<const float4 *>(in + L.q0a),
+                     *ib = reinterpret_cast<const float4 *>(in + L.q0b);
+        for (int q = tid; q < D4 / 4; q += 256) q1[q] = i1[q], q0a[q] = ia[q], q0b[q] = ib[q];
+        return;
+    }
+    if (l >= 1) {
+        const float4 *src = reinterpret_cast<const float4 *>(in + L.p + (long)(l - 1) * D4);
+        float4 *dst = reinterpret_cast<float4 *>(p.P + ((long)(l * 2 + (r & 1)) * p.B + slot) * D4);
+        for (int q = tid; q < D4 / 4; q += 256) dst[q] = src[q];
+    }
+    const float4 *src = reinterpret_cast<const float4 *>(in + L.cr + (long)l * D2);
+    float4 *dst = reinterpret_cast<float4 *>(p.CR + ((long)l * p.B + slot) * D2);
+    for (int q = tid; q < D2 / 4; q += 256) dst[q] = src[q];
+}
+static bool slot_al16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+hipError_t launch_slot_save(const SlotSaveParams &p, hipStream_t stream) {
+    if (!p.slots || !p.hist || !p.tok32 || !p.Q1 || !p.Q0 || !p.P || !p.CR || !p.bv || !p.rep_ring || !p.state || p.n < 1 || p.B < 1 || p.n > p.B ||
+        p.row < 0 || p.D < 4 || p.D % 4 || p.NL < 1 || p.NL > 65534 || p.R < 4 || (p.open_labels && (!p.tables || p.NC < 1)) || !slot_al16(p.Q1) ||
+        !slot_al16(p.Q0) || !slot_al16(p.P) || !slot_al16(p.CR) || !slot_al16(p.bv) || !slot_al16(p.state) || (p.open_labels && !slot_al16(p.tables)))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slot_save_kernel, dim3((unsigned)p.n, (unsigned)(p.NL + 1)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+hipError_t launch_slot_load(const SlotLoadParams &p, hipStream_t stream) {
+    if (!p.slots || !p.index || !p.origin || !p.tok32 || !p.Q1 || !p.Q0 || !p.P || !p.CR || !p.rep_ring || !p.row_origin || !p.state || p.n < 1 ||
+        p.B < 1 || p.n > p.B || p.n_states < 1 || p.row < 0 || p.D < 4 || p.D % 4 || p.NL < 1 || p.NL > 65534 || p.R < 4 || !slot_al16(p.Q1) ||
+        !slot_al16(p.Q0) || !slot_al16(p.P) || !slot_al16(p.CR) || !slot_al16(p.state))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slot_load_kernel, dim3((unsigned)p.n, (unsigned)(p.NL + 1)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 // test aid: out[i] = gate_act(v[i], p[i]) — the chain kernels' gate on given operands (tests measure it against tanh * sigmoid in float64)
 __global__ void gate_act_kernel(const float *v, const float *p, float *out, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -735,6 +735,81 @@ class PixelCNNStream:
                 self._labels[b] = int(labels[i])
         return self
 
+    # ---- slot state (talkshow_hip.h, "slot state"; the rule is restated at `streaming.SlotClock`) ----
+    def _dims(self):
+        net = self.net
+        return (int(net.dim), int(net.n_layers), int(net.n_classes), int(net.input_dim))
+
+    def save(self, slots):
+        """Slot state (`ts_pixelcnn_stream_save`): the state of each listed slot at the session's next row -> `SlotState` on the session's
+        device.  Read-only: the session's later bits, launches and graph captures are those without the call; stream-ordered, no
+        synchronisation.  Loaded into any slot of any session of a network with the same dimensions and weights (`load`), the slot carries
+        the clip on: its rows equal rows n, n+1, ... of `run` over the clip's whole audio with `given=` its first n code rows, bit for bit.
+        The state carries the conditioning rows, the label the slot stands for, the repetition histories, the clip index and n — not the
+        sampling records, bias tables, defaults or given rows of a step.  A bad slot raises ValueError before any device work."""
+        from talkshow_amd.streaming import SlotClock, SlotState
+        slots = SlotClock.check_slots(self.B, slots, "save")
+        n, dev = len(slots), self.net._dev()
+        lib = _lib.load()
+        W = int(lib.ts_pixelcnn_slot_state_words(self.net.handle()))
+        assert W == SlotClock.state_words(*self._dims()[:2])
+        words = torch.empty((n, W), dtype=torch.int32, device=dev)
+        info = (_lib.TsSlotInfo * n)()
+        with torch.cuda.device(dev):
+            _lib.check(lib.ts_pixelcnn_stream_save(self._h, (C.c_int32 * n)(*slots), n, _lib.dptr(words), info, _lib.stream_ptr()))
+        infos = [{k: int(getattr(o, k)) for k, _ in _lib.TsSlotInfo._fields_} for o in info]
+        for o, b in zip(infos, slots):      # the label the slot stands for: this handle has followed it through every restart and load
+            o["label"] = int(self._labels[b])
+        return SlotState(words, infos)
+
+    def load(self, slots, state, *, clip_indices=None):
+        """Slot state (`ts_pixelcnn_stream_load`): each listed slot takes a saved state — `state` holds one for all listed slots (fan-out) or
+        one each — and carries that clip on from the session's next row under its clip index (clip_indices: one per slot; default: the
+        index the source drew under).  The other slots keep their bits.  The state may come from another session, another batch size,
+        another handle of a network with equal weights (not checked), another device, or `SlotState.frombytes`.  Refused with ValueError
+        naming the slot, before any device work and with `rows` / `slot_rows` where they were: a slot out of range or listed twice, a count
+        mismatch, a state of other (D, NL, NC, V) or version, session row < min(clip rows, 3), a negative clip index.  The session's first
+        load does what its first restart does (steps on the restart graph keys from there on)."""
+        from talkshow_amd.streaming import SlotClock, SlotState
+        if not isinstance(state, SlotState):
+            raise ValueError(f"load: state must be a SlotState, got {type(state).__name__}")
+        SlotClock.check_load(self.B, self._dims(), None, slots, state.infos, clip_indices)      # every rule the arguments alone decide,
+        slots, index, clips = SlotClock.check_load(self.B, self._dims(), self.rows, slots, state.infos, clip_indices)   # then the row's
+        n, m, dev = len(slots), len(state), self.net._dev()
+        W = SlotClock.state_words(*self._dims()[:2])
+        if tuple(state.words.shape) != (m, W):
+            raise ValueError(f"load: the state's words have shape {tuple(state.words.shape)}, this network's states are ({m}, {W})")
+        words = state.words.to(device=dev, dtype=torch.int32).contiguous()
+        if words.data_ptr() % 16:
+            words = words.clone()
+        info = (_lib.TsSlotInfo * m)()
+        for o, d in zip(info, state.infos):
+            for k, _ in _lib.TsSlotInfo._fields_:
+                setattr(o, k, int(d[k]))
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ts_pixelcnn_stream_load(self._h, (C.c_int32 * n)(*slots), n, _lib.dptr(words), m, (C.c_int32 * n)(*index), info,
+                                                          (C.c_int64 * n)(*clips), _lib.stream_ptr()))
+        for b, k in zip(slots, index):      # what `style=[None, ...]` stands for from here on
+            self._labels[b] = int(state.infos[k]["label"])
+        return self
+
+    def fork(self, src, dst_slots, *, clip_indices=None):
+        """`save(src)` and `load(dst_slots, ...)` inside this session: every listed slot carries slot `src`'s clip on (N candidate
+        continuations of a live clip: give each its own clip index).  Checked as a whole before anything is launched."""
+        from talkshow_amd.streaming import SlotClock
+        src = SlotClock.check_slots(self.B, src, "fork")
+        if len(src) != 1:
+            raise ValueError(f"fork: one source slot, got {len(src)}")
+        dst = SlotClock.check_slots(self.B, dst_slots, "fork", distinct=True)
+        if clip_indices is not None:
+            clip_indices = [clip_indices] * len(dst) if isinstance(clip_indices, int) else list(clip_indices)
+            if len(clip_indices) != len(dst):
+                raise ValueError(f"fork: {len(dst)} slots but {len(clip_indices)} clip index entries")
+            for b, c in zip(dst, clip_indices):
+                if int(c) != c or int(c) < 0:
+                    raise ValueError(f"fork: slot {b}: clip index {c} is negative")
+        return self.load(dst, self.save(src), clip_indices=clip_indices)
+
     def close(self):
         if self._h is not None:
             torch.cuda.synchronize()

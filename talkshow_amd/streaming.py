@@ -202,8 +202,184 @@ class SlotClock:
         return {"tok": [(r - k) % R for k in (1, 2, 3) if r - k >= 0], "q1": [r % R], "q0": [r % R, (r + 1) % R], "p": r & 1}
 
 
+    # ---- slot state (talkshow_hip.h, "slot state"): save a slot's state, load it into any slot ----------------------------------
+    # The rule.  `save` of slot b at session row r (the session's next row) gives a state S of the slot's clip of n = r - origin[b] rows.
+    # Loading S into slot b' of a session of a network with the same dimensions and weights at its next row r', under clip index k'
+    # (default: the one the source drew under): the slot produces from r' on what slot b would have produced from r on under the same
+    # later inputs, and its rows equal rows n, n+1, ... of the one-shot `run` over the clip's whole audio with `given=` the clip's first n
+    # code rows and clip_index0 = k'; every other slot has its bits; the save changes nothing in its session.  The state carries the
+    # conditioning rows, the label the slot stands for, both repetition histories with their length, the clip index and n; it does not
+    # carry what belongs to a step or to the target session (sampling records, bias tables, defaults, given rows).  One state may be
+    # loaded into several slots, each under its own index.  A save at r < 3 is canonical (`canonical`); a load at r' < min(n, 3) is refused.
+    STATE_VERSION = 1
+    TOK_WORDS = 8     # three ring rows of two codes, padded to a multiple of 4 words
+    REP_RING = 64     # entries of one repetition history
+
+    @classmethod
+    def state_layout(cls, D, NL):
+        """Word offsets of one slot's state row (32-bit words; a function of (D, NL) alone): q1, q0a, q0b (4D floats each: Q1[r & 3],
+        Q0[r & 3], Q0[(r + 1) & 3]), p (NL - 1 rows of 4D: P(l, r & 1), l >= 1), cr (NL rows of 2D), tok (int32: word 2 k + c = the code of
+        row r-1-k, column c, k < 3; two words of 0), rep (int32: word 64 c + k = column c's code of row r-1-k, -1 beyond the history), and
+        `words`, the row's length.  Every float block starts at a multiple of 4 words."""
+        D, NL = int(D), int(NL)
+        if D < 4 or D % 4 or NL < 1:
+            raise ValueError(f"state_layout: D is a positive multiple of 4 and NL at least 1, got D = {D}, NL = {NL}")
+        L = {"q1": 0, "q0a": 4 * D, "q0b": 8 * D, "p": 12 * D}
+        L["cr"] = L["p"] + (NL - 1) * 4 * D
+        L["tok"] = L["cr"] + NL * 2 * D
+        L["rep"] = L["tok"] + cls.TOK_WORDS
+        L["words"] = L["rep"] + 2 * cls.REP_RING
+        return L
+
+    @classmethod
+    def state_words(cls, D, NL):
+        return cls.state_layout(D, NL)["words"]
+
+    @staticmethod
+    def canonical(r):
+        """What a save at session row r writes as the value a RESTART writes there, because the session's launches of rows r and r + 1
+        would not have read the entry (it may never have been written): `tok`: the ages k (row r-1-k) saved as -1; `q1`, `q0a`, `q0b`:
+        saved as +0.0; `p`: saved as bv[l].  Nothing for r >= 3."""
+        r = int(r)
+        return {"tok": [k for k in range(3) if r - 1 - k < 0], "q1": r < 2, "q0a": r < 3, "q0b": r < 2, "p": r == 0}
+
+    @classmethod
+    def load_plan(cls, r_new, n, hist=-1):
+        """Where a load at session row r_new puts the state of a clip of n rows whose histories hold `hist` entries (-1: no penalty was
+        running): the slot's new origin (negative for r_new < n), its rep_from (None: no penalty running), the ring index of every
+        saved token row (None: the row lies below the session's row 0 and is not written), the Q ring rows and the parity of P (the
+        entries `rewrites(r_new)` names), and the history ring index of every age."""
+        r, n, hist = int(r_new), int(n), int(hist)
+        R = cls.RING_ROWS
+        return {"origin": r - n, "rep_from": None if hist < 0 else r - hist,
+                "tok": [(r - 1 - k) % R if r - 1 - k >= 0 else None for k in range(3)],
+                "q1": r % R, "q0": [r % R, (r + 1) % R], "p": r & 1,
+                "ring": [(r - 1 - k) % cls.REP_RING for k in range(cls.REP_RING)]}
+
+    @staticmethod
+    def check_slots(B, slots, who, distinct=False):
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        if len(slots) < 1:
+            raise ValueError(f"{who}: no slot given")
+        seen = set()
+        for i, b in enumerate(slots):
+            if int(b) != b or not 0 <= int(b) < int(B):
+                raise ValueError(f"{who}: slot {b} is outside [0, B = {int(B)})")
+            slots[i] = int(b)
+            if distinct and slots[i] in seen:
+                raise ValueError(f"{who}: slot {b} is listed twice")
+            seen.add(slots[i])
+        return slots
+
+    @classmethod
+    def check_load(cls, B, dims, row, slots, infos, clip_indices=None, who="load"):
+        """The argument rules of a load at session row `row` -> (slots, state index per slot, clip index per slot).  dims: the target
+        network's (D, NL, NC, V); infos: the records of the given states (dicts with D, NL, NC, V, version, rows, clip_index, hist, label),
+        one for all listed slots or one each; row None: every rule but the row's.  ValueError naming the slot: a slot outside [0, B) or listed twice, a count mismatch, a state
+        of other dimensions or version, row < min(rows, 3), a negative clip index (or none given and none recorded)."""
+        slots = cls.check_slots(B, slots, who, distinct=True)
+        n, infos = len(slots), list(infos)
+        if len(infos) not in (1, n):
+            raise ValueError(f"{who}: {n} slots but {len(infos)} states (one for all listed slots, or one each)")
+        index = [0] * n if len(infos) == 1 else list(range(n))
+        if clip_indices is not None:
+            clip_indices = [clip_indices] * n if isinstance(clip_indices, int) else list(clip_indices)
+            if len(clip_indices) != n:
+                raise ValueError(f"{who}: {n} slots but {len(clip_indices)} clip index entries")
+        clips = []
+        for i, b in enumerate(slots):
+            o = infos[index[i]]
+            if int(o["version"]) != cls.STATE_VERSION:
+                raise ValueError(f"{who}: slot {b}: the state has layout version {o['version']}, this package reads {cls.STATE_VERSION}")
+            got = tuple(int(o[k]) for k in ("D", "NL", "NC", "V"))
+            if got != tuple(int(v) for v in dims):
+                raise ValueError(f"{who}: slot {b}: the state is of a network with (D, NL, NC, V) = {got}, this session's has {tuple(dims)}")
+            rows = int(o["rows"])
+            if row is not None and int(row) < min(rows, 3):
+                raise ValueError(f"{who}: slot {b}: a clip of {rows} rows cannot be loaded at session row {int(row)} (the session's rows 0 to 2 "
+                                 f"leave out terms the clip's state holds: load at row min(rows, 3) or later)")
+            c = o["clip_index"] if clip_indices is None else clip_indices[i]
+            if c is None or int(c) != c or int(c) < 0:
+                raise ValueError(f"{who}: slot {b}: clip index {c} is negative" + ("" if clip_indices is not None else " (the state records none: give one)"))
+            clips.append(int(c))
+        return slots, index, clips
+
+    def load(self, slots, rows, clip_indices):
+        """The listed slots continue clips of rows[i] rows under clip_indices[i] from the session's next row.  The clock forgets the clips a
+        loaded slot held before: `origin(slot, row)` and `position` answer for rows from here on."""
+        for b, n, c in zip(slots, rows, clip_indices):
+            self.origins[b] = [self.row - int(n)]
+            self.clip_index[b] = int(c)
+        return self
+
+
+class SlotState:
+    """The saved state of one or more slots (`PixelCNNStream.save`; talkshow_hip.h, "slot state"): `words` (n, W) int32, one row per slot
+    in `SlotClock.state_layout`, on any device, and `infos`, one dict per row (D, NL, NC, V, version, rows, clip_index, label, hist).
+    Indexing gives the state of the chosen rows; `.to(device)` / `.cpu()` move the words; `tobytes()` / `frombytes()` make it portable."""
+    _FIELDS = ("D", "NL", "NC", "V", "version", "hist", "rows", "clip_index", "label")
+    _MAGIC = b"TSSLOT01"
+
+    def __init__(self, words, infos):
+        self.words, self.infos = words, [dict(o) for o in infos]
+        if len(self.infos) != int(words.shape[0]):
+            raise ValueError(f"SlotState: {int(words.shape[0])} rows of words but {len(self.infos)} records")
+
+    def __len__(self):
+        return len(self.infos)
+
+    def __getitem__(self, i):
+        idx = [i] if isinstance(i, int) else (list(range(len(self)))[i] if isinstance(i, slice) else [int(k) for k in i])
+        idx = [k + len(self) if k < 0 else k for k in idx]
+        return SlotState(self.words[idx].contiguous(), [self.infos[k] for k in idx])
+
+    @property
+    def device(self):
+        return self.words.device
+
+    @property
+    def rows(self):
+        return [int(o["rows"]) for o in self.infos]
+
+    def to(self, device):
+        return SlotState(self.words.to(device), self.infos)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def tobytes(self):
+        import struct
+        w = self.words.detach().cpu().contiguous().numpy()
+        head = self._MAGIC + struct.pack("<2q", w.shape[0], w.shape[1])
+        recs = b"".join(struct.pack("<6i3q", *[int(o[k]) for k in self._FIELDS]) for o in self.infos)
+        return head + recs + w.astype("<i4", copy=False).tobytes()
+
+    @classmethod
+    def frombytes(cls, data):
+        import struct
+
+        import numpy as np
+        import torch
+        data = bytes(data)
+        m = len(cls._MAGIC)
+        if len(data) < m + 16 or data[:m] != cls._MAGIC:
+            raise ValueError("SlotState.frombytes: not a slot state")
+        n, W = struct.unpack("<2q", data[m:m + 16])
+        if n < 1 or W < 1 or len(data) != m + 16 + n * 48 + n * W * 4:
+            raise ValueError(f"SlotState.frombytes: {len(data)} bytes do not hold {n} states of {W} words")
+        infos = [dict(zip(cls._FIELDS, struct.unpack("<6i3q", data[m + 16 + 48 * i:m + 16 + 48 * (i + 1)]))) for i in range(n)]
+        words = np.frombuffer(data, "<i4", n * W, m + 16 + 48 * n).reshape(n, W).astype(np.int32)
+        return cls(torch.from_numpy(words), infos)
+
+
 class SeamlessBodyStream:
     """See `TrainWrapper.open_stream(..., seamless=True)`: the host handle of `ts_body_stream` (talkshow_hip.h, "seamless sessions")."""
+
+    def _no_state(self, *a, **k):
+        """Not taken by a seamless session (talkshow_hip.h, "slot state")."""
+        raise NotImplementedError("a seamless session saves and loads no slot state: its MFCC tail and its code ring sit on the SESSION's row "
+                                  "grid; use a plain session (open_stream(..., seamless=False))")
+    save = load = fork = _no_state
 
     def restart(self, *a, **k):
         """Not taken by a seamless session (talkshow_hip.h, "slot restart")."""
