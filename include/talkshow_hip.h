@@ -902,6 +902,56 @@ int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav_dev, const int32_t *ns_ho
 /* stage 1 alone: out_dev (B, ts_mfcc_resampled_len(m, N_max)); samples at or beyond ts_mfcc_resampled_len(m, ns[b]) are written as 0. */
 int ts_mfcc_resample_mixed(ts_mfcc *m, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max,
                            float *out_dev, void *stream);
+/* The per-recording maximum ts_mfcc_forward_mixed clamps at (its floor is this value - 80 dB): the same launches up to the mel projection, then
+ * the maximum of 10 log10(max(x, 1e-10)) over the recording's own rows.  out_dev (B,) fp32.  Does not synchronise.  What a wav session
+ * in TS_WAV_DB_PEAK mode is opened with when the recording is known beforehand. */
+int ts_mfcc_peak_db_mixed(ts_mfcc *m, const float *wav_dev, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max,
+                          float *out_dev, void *stream);
+
+/* ---- wav sessions: the front end fed SAMPLES in chunks (no counterpart in the reference, which reads whole files) ------------------------
+ * A session of B slots that share one sample clock takes the recording's samples in pushes of any size 0 .. max_samples and returns, per
+ * push, the MFCC rows that have become final; ts_mfcc_stream_flush ends the recording and returns the rest.  THE CONTRACT: the rows of a session
+ * are the rows of ts_mfcc_forward on the whole recording, BIT FOR BIT, for any chunking — every stage is the one-shot kernel's arithmetic term
+ * for term (the same taps in the same fmaf order; the same window, FFT passes and twiddle tables; the mel and DCT GEMMs on whole-tile plans,
+ * where a row's bits do not depend on the rows it shares a launch with) — up to the one stage that looks across the recording, the clamp at
+ * (maximum - 80 dB), which a session cannot know before the end.  db_mode fixes what stands in for it:
+ *   TS_WAV_DB_PEAK     the floor of every row is peak_db_dev[b] - 80 (peak_db_dev: (B,) fp32 device table, copied at open).  With the
+ *                      recording's own maximum (ts_mfcc_peak_db_mixed) the rows ARE the one-shot rows, bit for bit.
+ *   TS_WAV_DB_RUNNING  the floor of row t is (the maximum over rows 0 .. t of the slot) - 80: a prefix maximum along time, carried across
+ *                      pushes, so the rows do not depend on the chunking.  They equal the one-shot rows from the recording's loudest row on,
+ *                      and before it wherever no value lies below the running floor.
+ * When a row is final.  With norig, nnew, width, kw the handle's resampler constants (ts_mfcc_constants) and n samples received: resampled sample
+ * j is final once its last tap (j / nnew) norig - width + kw - 1 < n; row t once t hop + 1023 < the count of final resampled samples (the left
+ * reflection i < 0 -> -i reads nothing beyond that, except in row 0, whose sample -1024 reflects to 1024: row 0 waits for 1025 samples; the right
+ * reflection and the rows up to T = N22 / hop + 1 come with the flush).
+ * LATENCY: a row follows its centre sample by 1024 resampled samples plus the resampler's right wing of kw - width - 1 = width + norig - 1
+ * input samples: 16 kHz -> 22 kHz (norig 8, width 7, kw 22): 46.5 ms + 14 samples = 47.4 ms; 44.1 kHz -> 22 kHz (norig 441, width 13, kw 467):
+ * 46.5 ms + 453 samples = 56.8 ms; equal rates: 46.5 ms.
+ * State, allocated at open and constant (ts_mfcc_stream_state_bytes): per slot fewer than kw input samples and at most 2048 resampled samples
+ * kept between calls (each ahead of room for one call's own), one running maximum, and the call's work rows; the counters live on the host.
+ * A session is bound to no stream (`stream` is per call) and takes ONE HOST THREAD AT A TIME.  ALL SLOTS SHARE THE SAMPLE CLOCK: there is no
+ * slot restart, save, load or fork of a wav session (the body sessions fed from one refuse them too).
+ * ts_mfcc_stream_push: wav_dev (B,n) contiguous, 0 <= n <= max_samples (n = 0: nothing is read) -> *frames rows in feat_dev (B,*frames,64)
+ *   (room for ts_mfcc_stream_max_frames rows per slot always suffices; ts_mfcc_stream_plan names the count beforehand).  A refusal (after the
+ *   flush, n out of range) moves no counter and launches nothing.
+ * ts_mfcc_stream_flush: the remaining rows.  A recording whose resampled length is <= half an FFT window is refused with ts_mfcc_forward's
+ *   message and no counter moves.  Afterwards only the counters and close are taken.
+ * ts_mfcc_stream_plan: host arithmetic from the rates alone — the rows out after samples_before samples, and after n more (flush != 0: after
+ *   the flush that follows them). */
+typedef struct ts_mfcc_stream ts_mfcc_stream;
+enum { TS_WAV_DB_RUNNING = 0, TS_WAV_DB_PEAK = 1 };
+int ts_mfcc_stream_open(ts_mfcc *m, int B, long max_samples, int db_mode, const float *peak_db_dev, ts_mfcc_stream **out);
+int ts_mfcc_stream_push(ts_mfcc_stream *h, const float *wav_dev, long n, float *feat_dev, int *frames, void *stream);
+int ts_mfcc_stream_flush(ts_mfcc_stream *h, float *feat_dev, int *frames, void *stream);
+long ts_mfcc_stream_samples_in(const ts_mfcc_stream *h);
+long ts_mfcc_stream_frames_out(const ts_mfcc_stream *h);
+long ts_mfcc_stream_state_bytes(const ts_mfcc_stream *h);
+long ts_mfcc_stream_max_frames(const ts_mfcc_stream *h);
+void ts_mfcc_stream_close(ts_mfcc_stream *h);
+int ts_mfcc_stream_plan(int sr_in, int sr_out, int fps, long samples_before, long n, int flush, long *frames_before, long *frames_after);
+/* out[5] = norig, nnew, width, kw, hop of the handle (equal rates: 1, 1, 0, 0, hop) */
+void ts_mfcc_constants(const ts_mfcc *m, int32_t out[5]);
+
 /* ts_resample_kaiser on recordings of different lengths: out_dev (B, ts_resample_kaiser_len(N_max, sr_in, sr_out)); row b holds the
  * ts_resample_kaiser_len(ns[b], ...) samples of the recording alone, zeros beyond.  A recording too short to give one output sample is an
  * error. */

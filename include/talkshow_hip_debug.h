@@ -267,6 +267,14 @@ int ts_debug_mfcc_mel(ts_mfcc *m, const float *power, const int32_t *frames_dev,
 int ts_debug_mfcc_db(ts_mfcc *m, float *mel, const int32_t *frames_dev, int B, int T, void *stream);
 /* mel (B T, 256) -> feat (B T, 64): the orthonormal DCT-II on conv_gemm_f32. */
 int ts_debug_mfcc_dct(ts_mfcc *m, const float *mel, const int32_t *frames_dev, int B, int T, float *feat, void *stream);
+/* Wav sessions (talkshow_hip.h, "wav sessions"), stage by stage.  ts_debug_mfcc_stream_tap: every later call of the session also leaves its new
+ * resampled samples in x22_dev (B rows of x22_ld, at their absolute index) and its new power rows in power_dev (B, power_rows, 1056) at their
+ * frame index; a null pointer switches that tap off; a call that would write past a tap is refused.  ts_debug_mfcc_stream_tails: out[2] = the
+ * input samples / resampled samples the session holds between calls.  ts_debug_mfcc_stream_db: the session's dB kernel on caller-owned
+ * buffers, mel (B, F, 256) in place; peak (B,) = the peak mode, null = the running mode on run_max (B,), read and written. */
+int ts_debug_mfcc_stream_tap(ts_mfcc_stream *h, float *x22_dev, long x22_ld, float *power_dev, long power_rows);
+void ts_debug_mfcc_stream_tails(const ts_mfcc_stream *h, long out[2]);
+int ts_debug_mfcc_stream_db(ts_mfcc *m, float *mel, int B, int F, const float *peak, float *run_max, void *stream);
 
 /* Test aids: the stages of the SMPL-X forward pass of talkshow_hip.h (csrc/smplx.cpp, csrc/smplx.hip), one production launch each on `stream` with the handle's OWN
  * tables (pose offsets and mean, the three packed GEMM operands, parents, sparse skinning weights, selector and landmark maps).  Device pointers

@@ -735,7 +735,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         output = pred_poses
         return output
 
-    def open_stream(self, id, B, max_frames, *, seamless=False, sampling=None, style=None, code_bias=None, repeat=None):
+    def open_stream(self, id, B, max_frames, *, seamless=False, sampling=None, style=None, code_bias=None, repeat=None, wav_sr=None,
+                    wav_db="running", max_samples=None, fps=30):
         """Long-audio / continuity generation: a session that is fed MFCC chunks and returns the poses of
         each chunk, every chunk continuing the PixelCNN row cache of the ones before it (`ts_pixelcnn_stream_*`) — the
         reference's `infer(..., pre_latents, pre_audio)` chain (`:291-304`) for any number of chunks, at a cost per chunk
@@ -759,7 +760,22 @@ class TrainWrapper(TrainWrapperBaseClass):
           code_bias, repeat, given, uniforms) apply to the Hc code rows THAT call runs: `session.plan(t, flush=False)` ->
           (code_rows, pose_frames) names the counts beforehand, and a wrong `uniforms` / `given` row count raises ValueError naming the
           expected one before any device work.  Properties: frames_in, code_rows, frames, state_bytes (constant for any history).
-        Not taken by a seamless session: clips of different lengths, given poses, kept positions, style tracks inside a step."""
+        Not taken by a seamless session: clips of different lengths, given poses, kept positions, style tracks inside a step.
+
+        wav_sr=None (the default): the sessions above, fed MFCC frames.  wav_sr = a sample rate: `talkshow_amd.streaming.WavBodyStream`, the
+        same session fed SAMPLES at that rate through a streaming front end (`MFCC.open_stream`; talkshow_hip.h, "wav sessions"):
+          push_wav(wav (B,n), ...)   any n in 0 .. max_samples (default: the samples of max_frames frames); the keywords of `push`.  A call
+                                     that yields no MFCC frame makes no body call and returns empty tensors.
+          flush(...)                 flushes the front end, pushes the last frames and flushes a seamless session.
+          plan_wav(n, flush=False)   -> (MFCC frames, code rows, pose frames) of that call.
+        wav_db="running" clamps each MFCC row at (the maximum so far - 80 dB); wav_db = the recordings' maxima (`MFCC.peak_db(wav)`, (B,))
+        makes the frames those of `MFCC(wav_sr)(wav)` bit for bit, and with seamless=True the poses those of `generate_batch` on them, for
+        any chunking of the samples.  The slots of a wav-fed session share ONE SAMPLE CLOCK: `restart`, `save`, `load` and `fork` raise
+        NotImplementedError."""
+        if wav_sr is not None:
+            from talkshow_amd.streaming import WavBodyStream
+            return WavBodyStream(self, id, B, max_frames, seamless, wav_sr, wav_db=wav_db, max_samples=max_samples, fps=fps, sampling=sampling,
+                                 style=style, code_bias=code_bias, repeat=repeat)
         if seamless:
             from talkshow_amd.streaming import SeamlessBodyStream
             return SeamlessBodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)

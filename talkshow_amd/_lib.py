@@ -207,6 +207,21 @@ SIGNATURES = {
     "ts_mfcc_forward_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
     "ts_mfcc_resample_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
     "ts_resample_kaiser_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _i, _i, _vp, _vp]),
+    "ts_mfcc_peak_db_mixed": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
+    # wav sessions (talkshow_hip.h, "wav sessions")
+    "ts_mfcc_stream_open": (_i, [_vp, _i, C.c_long, _i, _vp, C.POINTER(_vp)]),
+    "ts_mfcc_stream_push": (_i, [_vp, _vp, C.c_long, _vp, C.POINTER(_i), _vp]),
+    "ts_mfcc_stream_flush": (_i, [_vp, _vp, C.POINTER(_i), _vp]),
+    "ts_mfcc_stream_samples_in": (C.c_long, [_vp]),
+    "ts_mfcc_stream_frames_out": (C.c_long, [_vp]),
+    "ts_mfcc_stream_state_bytes": (C.c_long, [_vp]),
+    "ts_mfcc_stream_max_frames": (C.c_long, [_vp]),
+    "ts_mfcc_stream_close": (None, [_vp]),
+    "ts_mfcc_stream_plan": (_i, [_i, _i, _i, C.c_long, C.c_long, _i, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "ts_mfcc_constants": (None, [_vp, C.POINTER(C.c_int32)]),
+    "ts_debug_mfcc_stream_tap": (_i, [_vp, _vp, C.c_long, _vp, C.c_long]),
+    "ts_debug_mfcc_stream_tails": (None, [_vp, C.POINTER(C.c_long)]),
+    "ts_debug_mfcc_stream_db": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ts_debug_mfcc_stft": (_i, [_vp, _vp, _i, C.c_long, _vp, _vp]),
     "ts_debug_mfcc_stft_lens": (_i, [_vp, _vp, C.POINTER(C.c_int32), _vp, _i, C.c_long, _vp, _vp]),
     "ts_debug_mfcc_frames": (_i, [_vp, _vp, _i, C.c_long, _vp, _vp]),

@@ -31,6 +31,14 @@ hipError_t launch_mfcc_frames(const int *ns, int B, int N, int norig, int nnew, 
 hipError_t launch_stft_power_lens(const float *x, int B, int N, int T, const int *ns, int norig, int nnew, int hop, const float *win,
                                   const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
 hipError_t launch_db_topdb_lens(float *mel, int B, int T, int width, const int *frames, float top_db, hipStream_t s);
+hipError_t launch_db_peak_lens(const float *mel, int B, int T, int width, const int *frames, float *out, hipStream_t s);
+// wav sessions (mfcc.hip): rows indexed by absolute sample index
+hipError_t launch_stream_rows_copy(const float *src, long lds, long off, int len, float *dst, long ldd, int B, hipStream_t s);
+hipError_t launch_resample_polyphase_stream(const float *x, long ldx, long x0, long n, int B, const float *kern, int norig, int nnew, int width,
+                                            int kw, float *out, long ldo, long o0, long j_lo, long j_hi, hipStream_t s);
+hipError_t launch_stft_power_stream(const float *x, long ldx, long x0, long N, int B, int F, int t0, int hop, const float *win,
+                                    const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
+hipError_t launch_db_stream(float *mel, int B, int F, const float *peak, float *run_max, float top_db, hipStream_t s);
 }  // namespace ts
 
 struct ts_mfcc {
@@ -405,6 +413,259 @@ int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, 
         TS_TRY(db_stage(m, w.melb.f(), w.frames.i(), B, (int)T, s));
     }
     TS_TRY(gemm_stage(m, m->dct, w.melb.f(), m->nmels, w.frames.i(), B, (int)T, feat, m->nmfcc, s));
+    return 0;
+}
+
+// The maximum ts_mfcc_forward_mixed clamps each recording at: the same launches up to the mel projection, then the maximum of the dB
+// expression over the recording's own rows.  out_dev (B,) fp32; nothing synchronises.
+int ts_mfcc_peak_db_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, float *out,
+                          void *stream) {
+    if (!m || !wav || !out) return fail("ts_mfcc_peak_db_mixed: null argument");
+    TS_TRY(check_counts("ts_mfcc_peak_db_mixed", ns_host, ns_dev, B, N_max));
+    hipStream_t s = (hipStream_t)stream;
+    ts_ctx *ctx = m->ctx;
+    const long N22 = m->resampled_len(N_max);
+    const long T = N22 / m->hop + 1, M = (long)B * T;
+    if (N22 > 0x7fffffffl || M > 0x7fffffffl) return fail("ts_mfcc_peak_db_mixed: bad shape");
+    for (int b = 0; b < B; ++b)
+        if (m->resampled_len(ns_host[b]) <= m->nfft / 2)
+            return fail("ts_mfcc_peak_db_mixed: clip " + std::to_string(b) + " is shorter than half an FFT window (reflect padding undefined)");
+    ts_mfcc::Work &w = m->work(s);
+    const size_t F = sizeof(float);
+    const float *x22 = wav;
+    if (m->sr_in != m->sr_out) TS_TRY(w.x22.ensure((size_t)B * N22 * F));
+    TS_TRY(w.power.ensure((size_t)M * m->nbins_pad * F));
+    TS_TRY(w.melb.ensure((size_t)M * m->nmels * F));
+    TS_TRY(w.frames.ensure((size_t)B * sizeof(int)));
+    {
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_mfcc_frames(ns_dev, B, (int)N_max, m->norig, m->nnew, m->hop, w.frames.i(), s));
+        if (m->sr_in != m->sr_out) {
+            TS_HIP(launch_resample_polyphase_lens(wav, B, (int)N_max, ns_dev, m->rs_kern.f(), m->norig, m->nnew, m->width, m->kw, w.x22.f(),
+                                                  (int)N22, s));
+            x22 = w.x22.f();
+        }
+        TS_TRY(stft_stage(m, x22, ns_dev, B, (int)N22, (int)T, w.power.f(), s));
+    }
+    TS_TRY(gemm_stage(m, m->mel, w.power.f(), m->nbins_pad, w.frames.i(), B, (int)T, w.melb.f(), m->nmels, s));
+    MiscScope ms(ctx, s);
+    TS_HIP(launch_db_peak_lens(w.melb.f(), B, (int)T, m->nmels, w.frames.i(), out, s));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- wav sessions: the front end fed samples in chunks (talkshow_hip.h, "wav sessions") ---------------------------------------------------
+// Host arithmetic of a session, from the rates alone (ts_mfcc_stream_plan needs no handle): after n samples, resampled outputs below
+// final22(n) have every tap below n; frames below final_frames(n) have every sample — the reflected ones of the first rows included — below final22(n).
+namespace {
+struct WavClock {
+    int norig = 1, nnew = 1, width = 0, kw = 0, hop = 734;
+    long final22(long n) const { return n >= width ? (n - width) / norig * nnew : 0; }   // (j / nnew) norig - width + kw - 1 < n
+    long total22(long n) const { return (nnew * n + norig - 1) / norig; }
+    // row t reads resampled samples up to t hop + 1023, and row 0 — whose first sample, -1024, reflects to 1024 — one further
+    static long frames_of(long j22, int hop) { return j22 >= 1025 ? (j22 - 1024) / hop + 1 : 0; }
+    long final_frames(long n) const { return frames_of(final22(n), hop); }
+    long flush_frames(long n) const { return total22(n) / hop + 1; }
+    long in_keep0(long n) const { return std::max(0l, final22(n) / nnew * norig - width); }   // first input sample the next output reads
+    static long x22_keep0(long frames, int hop) { return std::max(0l, frames * hop - 1025); }  // first resampled sample a later frame reads
+};
+int wav_clock(int sr_in, int sr_out, int fps, WavClock *c) {
+    if (sr_in < 1 || sr_out < 1 || (fps != 30 && fps != 15)) return 1;
+    c->hop = fps == 30 ? 734 : 1467;
+    if (sr_in == sr_out) return 0;
+    const int g = gcd_i(sr_in, sr_out);
+    c->norig = sr_in / g;
+    c->nnew = sr_out / g;
+    c->width = (int)std::ceil(6.0 * c->norig / (std::min(c->norig, c->nnew) * 0.99));
+    c->kw = 2 * c->width + c->norig;
+    return 0;
+}
+}  // namespace
+
+struct ts_mfcc_stream {
+    ts_mfcc *m = nullptr;
+    WavClock c;
+    int B = 0, running = 1;
+    long max_samples = 0, cap_in = 0, cap22 = 0, max_frames = 0;
+    DevBuf in[2], x22[2], run_max, peak, power, melb;
+    int cur_in = 0, cur22 = 0;
+    long n_in = 0, in0 = 0;          // samples received; the sample at element 0 of in[cur_in]
+    long j22 = 0, r0 = 0;            // resampled samples final; the resampled sample at element 0 of x22[cur22]
+    long frames_out = 0;
+    bool flushed = false;
+    // test aid (ts_debug_mfcc_stream_tap): where every call also leaves its new resampled samples / power rows, by absolute index
+    float *tap22 = nullptr, *tap_pw = nullptr;
+    long tap22_ld = 0, tap_pw_rows = 0;
+    size_t bytes() const {
+        return in[0].bytes + in[1].bytes + x22[0].bytes + x22[1].bytes + run_max.bytes + peak.bytes + power.bytes + melb.bytes;
+    }
+};
+
+namespace {
+// one call of a session: the n new samples (flush: none, and the recording ends at the samples received)
+int stream_call(ts_mfcc_stream *h, const float *wav, long n, bool flush, float *feat, int *frames, hipStream_t s) {
+    ts_mfcc *m = h->m;
+    ts_ctx *ctx = m->ctx;
+    const WavClock &c = h->c;
+    const int B = h->B;
+    const long n1 = h->n_in + n;
+    const long j1 = flush ? c.total22(n1) : c.final22(n1);
+    const long t1 = flush ? c.flush_frames(n1) : c.final_frames(n1);
+    const long F = t1 - h->frames_out;
+    if (F < 0 || F > h->max_frames || j1 - h->r0 > h->cap22 || n1 - h->in0 > h->cap_in)
+        return fail("ts_mfcc_stream: internal: a call outgrew the session's buffers");
+    if (F > 0 && !feat) return fail("ts_mfcc_stream: null output");
+    if (h->tap22 && j1 > h->tap22_ld) return fail("ts_debug_mfcc_stream_tap: the resampled samples outgrew the tap");
+    if (h->tap_pw && t1 > h->tap_pw_rows) return fail("ts_debug_mfcc_stream_tap: the frames outgrew the tap");
+    const bool same_rate = m->sr_in == m->sr_out;
+    float *x22 = h->x22[h->cur22].f();
+    {
+        MiscScope ms(ctx, s);
+        if (same_rate) {   // the resampler is a copy: the new samples are the new resampled samples
+            TS_HIP(launch_stream_rows_copy(wav, n, 0, (int)n, x22 + (h->j22 - h->r0), h->cap22, B, s));
+        } else {
+            float *in = h->in[h->cur_in].f();
+            TS_HIP(launch_stream_rows_copy(wav, n, 0, (int)n, in + (h->n_in - h->in0), h->cap_in, B, s));
+            TS_HIP(launch_resample_polyphase_stream(in, h->cap_in, h->in0, n1, B, m->rs_kern.f(), c.norig, c.nnew, c.width, c.kw, x22, h->cap22,
+                                                    h->r0, h->j22, j1, s));
+        }
+        if (h->tap22 && j1 > h->j22) {
+            TS_HIP(launch_stream_rows_copy(x22, h->cap22, h->j22 - h->r0, (int)(j1 - h->j22), h->tap22 + h->j22, h->tap22_ld, B, s));
+        }
+        TS_HIP(launch_stft_power_stream(x22, h->cap22, h->r0, j1, B, (int)F, (int)h->frames_out, c.hop, m->window.f(), m->tw1024.f(),
+                                        m->tw2048.f(), h->power.f(), m->nbins_pad, s));
+        if (h->tap_pw && F > 0) {
+            for (int b = 0; b < B; ++b)   // row b F + f -> row b tap_rows + frames_out + f
+                TS_HIP(launch_stream_rows_copy(h->power.f() + (size_t)b * F * m->nbins_pad, 0, 0, (int)(F * m->nbins_pad),
+                                               h->tap_pw + ((size_t)b * h->tap_pw_rows + h->frames_out) * m->nbins_pad, 0, 1, s));
+        }
+    }
+    if (F > 0) {
+        TS_TRY(gemm_stage(m, m->mel, h->power.f(), m->nbins_pad, nullptr, B, (int)F, h->melb.f(), m->nmels, s));
+        {
+            MiscScope ms(ctx, s);
+            TS_HIP(launch_db_stream(h->melb.f(), B, (int)F, h->running ? nullptr : h->peak.f(), h->run_max.f(), 80.0f, s));
+        }
+        TS_TRY(gemm_stage(m, m->dct, h->melb.f(), m->nmels, nullptr, B, (int)F, feat, m->nmfcc, s));
+    }
+    if (!flush) {   // what later calls still read moves to the front of the twin buffers
+        MiscScope ms(ctx, s);
+        const long in0 = same_rate ? n1 : c.in_keep0(n1), r0 = WavClock::x22_keep0(t1, c.hop);
+        if (!same_rate && in0 != h->in0) {
+            TS_HIP(launch_stream_rows_copy(h->in[h->cur_in].f(), h->cap_in, in0 - h->in0, (int)(n1 - in0), h->in[h->cur_in ^ 1].f(), h->cap_in,
+                                           B, s));
+            h->cur_in ^= 1;
+        }
+        if (r0 != h->r0) {
+            TS_HIP(launch_stream_rows_copy(x22, h->cap22, r0 - h->r0, (int)(j1 - r0), h->x22[h->cur22 ^ 1].f(), h->cap22, B, s));
+            h->cur22 ^= 1;
+        }
+        h->in0 = in0;
+        h->r0 = r0;
+    }
+    h->n_in = n1;
+    h->j22 = j1;
+    h->frames_out = t1;
+    h->flushed = flush;
+    if (frames) *frames = (int)F;
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int ts_mfcc_stream_plan(int sr_in, int sr_out, int fps, long samples_before, long n, int flush, long *frames_before, long *frames_after) {
+    WavClock c;
+    if (wav_clock(sr_in, sr_out, fps, &c)) return fail("ts_mfcc_stream_plan: rates are positive and fps is 15 or 30");
+    if (samples_before < 0 || n < 0) return fail("ts_mfcc_stream_plan: negative sample count");
+    const long n1 = samples_before + n;
+    if (flush && c.total22(n1) <= 1024) return fail(std::string("ts_mfcc_stream_plan: ") + SHORT_CLIP);
+    if (frames_before) *frames_before = c.final_frames(samples_before);
+    if (frames_after) *frames_after = flush ? c.flush_frames(n1) : c.final_frames(n1);
+    return 0;
+}
+
+int ts_mfcc_stream_open(ts_mfcc *m, int B, long max_samples, int db_mode, const float *peak_db_dev, ts_mfcc_stream **out) {
+    if (!m || !out) return fail("ts_mfcc_stream_open: null argument");
+    if (B < 1 || max_samples < 1 || max_samples > (1l << 28)) return fail("ts_mfcc_stream_open: B and max_samples are at least 1 (max_samples at most 2^28)");
+    if (db_mode != TS_WAV_DB_RUNNING && db_mode != TS_WAV_DB_PEAK) return fail("ts_mfcc_stream_open: db_mode is TS_WAV_DB_RUNNING or TS_WAV_DB_PEAK");
+    if (db_mode == TS_WAV_DB_PEAK && !peak_db_dev) return fail("ts_mfcc_stream_open: TS_WAV_DB_PEAK needs the (B,) table of maxima");
+    if (m->nmels != 256) return fail("ts_mfcc_stream_open: the session's dB kernel is built for 256 mel bands");
+    TS_HIP(hipSetDevice(m->ctx->device));
+    std::unique_ptr<ts_mfcc_stream> h(new ts_mfcc_stream());
+    h->m = m;
+    h->B = B;
+    h->max_samples = max_samples;
+    h->running = db_mode == TS_WAV_DB_RUNNING;
+    WavClock &c = h->c;
+    c.norig = m->norig; c.nnew = m->nnew; c.width = m->width; c.kw = m->kw; c.hop = m->hop;
+    // new resampled samples of one call: a push finalises at most max_samples / norig + 1 more windows, the flush the width / norig + 2 held back
+    const long new22 = std::max((max_samples / c.norig + 1) * c.nnew, ((long)c.width / c.norig + 2) * c.nnew + 1);
+    h->cap_in = c.kw + max_samples;            // a tail of fewer than kw samples, then the call's own
+    h->cap22 = 2049 + new22;                   // a tail of at most 2048 resampled samples, then the call's own
+    h->max_frames = (2049 + new22) / c.hop + 2;
+    const size_t F = sizeof(float);
+    if (m->sr_in != m->sr_out)
+        for (int i = 0; i < 2; ++i) TS_TRY(h->in[i].ensure((size_t)B * h->cap_in * F));
+    for (int i = 0; i < 2; ++i) TS_TRY(h->x22[i].ensure((size_t)B * h->cap22 * F));
+    TS_TRY(h->power.ensure((size_t)B * h->max_frames * m->nbins_pad * F));
+    TS_TRY(h->melb.ensure((size_t)B * h->max_frames * m->nmels * F));
+    std::vector<float> ninf((size_t)B, -INFINITY);
+    TS_TRY(h->run_max.upload(ninf.data(), (size_t)B * F));
+    if (!h->running) {
+        TS_TRY(h->peak.ensure((size_t)B * F));
+        TS_HIP(copy_and_wait(h->peak.p, peak_db_dev, (size_t)B * F, hipMemcpyDeviceToDevice));
+    }
+    *out = h.release();
+    return 0;
+}
+
+int ts_mfcc_stream_push(ts_mfcc_stream *h, const float *wav, long n, float *feat, int *frames, void *stream) {
+    if (!h || !frames) return fail("ts_mfcc_stream_push: null argument");
+    if (h->flushed) return fail("ts_mfcc_stream_push: the session has been flushed (the recording has ended): open another");
+    if (n < 0 || n > h->max_samples)
+        return fail("ts_mfcc_stream_push: a push holds 0 to max_samples = " + std::to_string(h->max_samples) + " samples, got " + std::to_string(n));
+    if (n > 0 && !wav) return fail("ts_mfcc_stream_push: null samples");
+    if (h->n_in + n > (1l << 40)) return fail("ts_mfcc_stream_push: the session has run out of sample indices");
+    return stream_call(h, wav, n, false, feat, frames, (hipStream_t)stream);
+}
+
+int ts_mfcc_stream_flush(ts_mfcc_stream *h, float *feat, int *frames, void *stream) {
+    if (!h || !frames) return fail("ts_mfcc_stream_flush: null argument");
+    if (h->flushed) return fail("ts_mfcc_stream_flush: the session has been flushed already");
+    if (h->c.total22(h->n_in) <= h->m->nfft / 2) return fail(std::string("ts_mfcc_stream_flush: ") + SHORT_CLIP);
+    return stream_call(h, nullptr, 0, true, feat, frames, (hipStream_t)stream);
+}
+
+long ts_mfcc_stream_samples_in(const ts_mfcc_stream *h) { return h ? h->n_in : -1; }
+long ts_mfcc_stream_frames_out(const ts_mfcc_stream *h) { return h ? h->frames_out : -1; }
+long ts_mfcc_stream_state_bytes(const ts_mfcc_stream *h) { return h ? (long)h->bytes() : -1; }
+long ts_mfcc_stream_max_frames(const ts_mfcc_stream *h) { return h ? h->max_frames : -1; }
+void ts_mfcc_stream_close(ts_mfcc_stream *h) { delete h; }
+// the handle's resampler constants (norig, nnew, width, kw, hop): what the latency of a wav session is quoted from
+void ts_mfcc_constants(const ts_mfcc *m, int32_t out[5]) {
+    if (!m || !out) return;
+    out[0] = m->norig; out[1] = m->nnew; out[2] = m->width; out[3] = m->kw; out[4] = m->hop;
+}
+
+// test aids: every later call of the session also leaves its new resampled samples in x22_dev (B rows of x22_ld, by absolute index) and its
+// new power rows in power_dev (B, power_rows, nbins_pad), by frame index; null = off
+int ts_debug_mfcc_stream_tap(ts_mfcc_stream *h, float *x22_dev, long x22_ld, float *power_dev, long power_rows) {
+    if (!h) return fail("ts_debug_mfcc_stream_tap: null session");
+    h->tap22 = x22_dev; h->tap22_ld = x22_ld; h->tap_pw = power_dev; h->tap_pw_rows = power_rows;
+    return 0;
+}
+// the session's retained tails, in samples: input, resampled
+void ts_debug_mfcc_stream_tails(const ts_mfcc_stream *h, long out[2]) {
+    if (!h || !out) return;
+    out[0] = h->n_in - h->in0; out[1] = h->j22 - h->r0;
+}
+// the session's dB kernel on caller-owned buffers: mel (B, F, 256) in place; peak (B,) or null = the running mode on run_max (B,)
+int ts_debug_mfcc_stream_db(ts_mfcc *m, float *mel, int B, int F, const float *peak, float *run_max, void *stream) {
+    if (!m || !mel || B < 1 || F < 1 || (!peak && !run_max)) return fail("ts_debug_mfcc_stream_db: bad argument");
+    MiscScope ms(m->ctx, (hipStream_t)stream);
+    TS_HIP(launch_db_stream(mel, B, F, peak, run_max, 80.0f, (hipStream_t)stream));
     return 0;
 }
 

@@ -462,4 +462,213 @@ hipError_t launch_db_topdb_lens(float *mel, int B, int T, int width, const int *
     return hipGetLastError();
 }
 
+// the maximum db_topdb_len_kernel clamps at, and nothing else: out[b] = max over the recording's own rows of 10 log10(max(x, 1e-10)); mel is
+// only read (ts_mfcc_peak_db_mixed)
+__global__ __launch_bounds__(256) void db_peak_len_kernel(const float *__restrict__ mel, int T, int width, const int *__restrict__ frames,
+                                                          float *__restrict__ out) {
+    __shared__ float sm[4];
+    const float *p = mel + (long)blockIdx.x * T * width;
+    const long per_clip = (long)clamp_count(frames[blockIdx.x], T) * width;
+    float mx = -INFINITY;
+    for (long i = threadIdx.x; i < per_clip; i += 256) mx = fmaxf(mx, 10.0f * log10f(fmaxf(p[i], 1e-10f)));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+}
+hipError_t launch_db_peak_lens(const float *mel, int B, int T, int width, const int *frames, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(db_peak_len_kernel, dim3(B), dim3(256), 0, s, mel, T, width, frames, out);
+    return hipGetLastError();
+}
+
+// ---- wav sessions (ts_mfcc_stream_*, mfcc.cpp; talkshow_hip.h, "wav sessions"): the front end fed samples in chunks.  Kernels of their own:
+// the ones above keep their code.  A session keeps, per slot, the input samples its next output still reads and the resampled samples its
+// next frame still reads, each as the front of a row buffer that the call's new samples are appended to; the kernels index those rows by
+// ABSOLUTE sample index (the index the one-shot kernels use) minus the absolute index of the row's first element.  Every value is the
+// arithmetic of the one-shot kernel on the whole recording, term for term: the chunking moves WHEN a value is computed, never how. ----
+
+// dst[b][i] = src[b][off + i], i < len: appends a call's samples to a row buffer and carries a buffer's tail over to its twin
+__global__ void stream_rows_copy_kernel(const float *__restrict__ src, long lds, long off, int len, float *__restrict__ dst, long ldd) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < len) dst[b * ldd + i] = src[b * lds + off + i];
+}
+hipError_t launch_stream_rows_copy(const float *src, long lds, long off, int len, float *dst, long ldd, int B, hipStream_t s) {
+    if (len < 1) return hipSuccess;
+    hipLaunchKernelGGL(stream_rows_copy_kernel, dim3((len + 255) / 256, B), dim3(256), 0, s, src, lds, off, len, dst, ldd);
+    return hipGetLastError();
+}
+
+// outputs j in [j_lo, j_hi) of resample_polyphase_kernel over a recording of which samples [x0, n) sit in x (rows of ldx, element 0 = sample
+// x0); n = the samples received so far, or the recording's length at the flush: a tap at or beyond n reads as zero, as beyond the clip.
+// An output is asked for only once its taps below n are all at or beyond x0.  out: rows of ldo, element 0 = output o0
+__global__ void resample_polyphase_stream_kernel(const float *__restrict__ x, long ldx, long x0, long n, const float *__restrict__ kern,
+                                                 int norig, int nnew, int width, int kw, float *__restrict__ out, long ldo, long o0, long j_lo,
+                                                 long j_hi) {
+    const int b = blockIdx.y;
+    const long j = j_lo + (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= j_hi) return;
+    const long wdw = j / nnew;
+    const int ph = (int)(j - wdw * nnew);
+    const float *kr = kern + ph * kw;
+    const float *xb = x + b * ldx;
+    const long base = wdw * norig - width;
+    float acc = 0.f;
+    for (int k = 0; k < kw; ++k) {
+        const long i = base + k;
+        if (i >= x0 && i < n) acc = fmaf(kr[k], xb[i - x0], acc);   // i >= x0 covers i >= 0: x0 is never negative
+    }
+    out[b * ldo + (j - o0)] = acc;
+}
+// the LDS-staged form (resample_polyphase_lds_kernel): the same terms in the same order, a staged zero where the plain kernel skips a tap
+__global__ __launch_bounds__(256) void resample_polyphase_lds_stream_kernel(const float *__restrict__ x, long ldx, long x0, long n,
+                                                                            const float *__restrict__ kern, int norig, int nnew, int width,
+                                                                            int kw, float *__restrict__ out, long ldo, long o0, long j_lo,
+                                                                            long j_hi, int nwin) {
+    extern __shared__ float sm[];
+    float *sk = sm, *sw = sm + nnew * kw;
+    const int b = blockIdx.y;
+    const long j0 = j_lo + (long)blockIdx.x * 256;
+    const float *xb = x + b * ldx;
+    const long base = (j0 / nnew) * norig - width;           // first input sample any output of this block touches
+    for (int i = threadIdx.x; i < nnew * kw; i += 256) sk[i] = kern[i];
+    for (int i = threadIdx.x; i < nwin; i += 256) {
+        const long g = base + i;
+        sw[i] = (g >= x0 && g < n) ? xb[g - x0] : 0.f;
+    }
+    __syncthreads();
+    const long j = j0 + threadIdx.x;
+    if (j >= j_hi) return;
+    const long wdw = j / nnew;
+    const int ph = (int)(j - wdw * nnew);
+    const float *kr = sk + ph * kw, *xw = sw + (wdw * norig - width - base);
+    float acc = 0.f;
+    for (int k = 0; k < kw; ++k) acc = fmaf(kr[k], xw[k], acc);
+    out[b * ldo + (j - o0)] = acc;
+}
+hipError_t launch_resample_polyphase_stream(const float *x, long ldx, long x0, long n, int B, const float *kern, int norig, int nnew, int width,
+                                            int kw, float *out, long ldo, long o0, long j_lo, long j_hi, hipStream_t s) {
+    if (j_hi <= j_lo) return hipSuccess;
+    const unsigned blocks = (unsigned)((j_hi - j_lo + 255) / 256);
+    const int nwin = (255 / nnew + 1) * norig + kw;          // input window of 256 consecutive outputs, wherever they start
+    const size_t lds = ((size_t)nnew * kw + nwin) * sizeof(float);
+    if (lds <= 48 * 1024) {   // the same choice as launch_resample_polyphase: by the rate ratio alone
+        hipLaunchKernelGGL(resample_polyphase_lds_stream_kernel, dim3(blocks, B), dim3(256), lds, s, x, ldx, x0, n, kern, norig, nnew, width,
+                           kw, out, ldo, o0, j_lo, j_hi, nwin);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(resample_polyphase_stream_kernel, dim3(blocks, B), dim3(256), 0, s, x, ldx, x0, n, kern, norig, nnew, width, kw, out,
+                       ldo, o0, j_lo, j_hi);
+    return hipGetLastError();
+}
+
+// frames t0 .. t0 + F - 1 of stft_power_kernel over a recording of which resampled samples [x0, ..) sit in x (rows of ldx, element 0 = sample
+// x0).  N = the recording's resampled length at the flush; before it, the count of final resampled samples, which every frame asked for lies
+// below (so the right reflection is never taken).  Workgroup (b, f) of a (B, F) grid writes row b F + f of pw.
+__global__ __launch_bounds__(256) void stft_power_stream_kernel(const float *__restrict__ x, long ldx, long x0, long N, int F, int t0, int hop,
+                                                                const float *__restrict__ win, const f32x2 *__restrict__ tw1024,
+                                                                const f32x2 *__restrict__ tw2048, float *__restrict__ pw, int ldp) {
+    __shared__ f32x2 bufA[1024], bufB[1024];
+    const long row = blockIdx.x;   // b * F + f
+    const int b = (int)(row / F), t = t0 + (int)(row - (long)b * F);
+    const float *xb = x + b * ldx;
+    const int j = threadIdx.x;
+    auto sample = [&](int n) {
+        long i = (long)t * hop + n - 1024;
+        if (i < 0) i = -i;
+        if (i >= N) i = 2 * (N - 1) - i;
+        i = i < 0 ? 0 : (i >= N ? N - 1 : i);
+        i = i < x0 ? x0 : i;       // never taken by a frame the session asks for: keeps a wrong plan inside the row
+        return xb[i - x0] * win[n];
+    };
+    auto butterfly = [](f32x2 &v0, f32x2 &v1, f32x2 &v2, f32x2 &v3) {
+        const f32x2 a = v0 + v2, bb = v0 - v2, c = v1 + v3, d0 = v1 - v3;
+        const f32x2 d = {d0[1], -d0[0]};
+        v0 = a + c; v2 = a - c; v1 = bb + d; v3 = bb - d;
+    };
+    f32x2 v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n = j + 256 * r;
+        v[r] = f32x2{sample(2 * n), sample(2 * n + 1)};
+    }
+    butterfly(v[0], v[1], v[2], v[3]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bufA[j * 4 + r] = v[r];
+    __syncthreads();
+    f32x2 *src = bufA, *dst = bufB;
+#pragma unroll
+    for (int p = 1; p < 5; ++p) {
+        const int Ns = 1 << (2 * p), k = j & (Ns - 1), step = 256 >> (2 * p);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            v[r] = src[j + 256 * r];
+            if (r) v[r] = cmul(v[r], tw1024[r * k * step]);
+        }
+        butterfly(v[0], v[1], v[2], v[3]);
+        const int base = ((j - k) << 2) + k;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[base + r * Ns] = v[r];
+        __syncthreads();
+        f32x2 *tmp = src; src = dst; dst = tmp;
+    }
+    float *out = pw + row * ldp;
+    for (int k = j; k < ldp; k += 256) {
+        float val = 0.f;
+        if (k <= 1024) {
+            const f32x2 zk = src[k & 1023], zn0 = src[(1024 - k) & 1023];
+            const f32x2 zn = {zn0[0], -zn0[1]};
+            const f32x2 e = (zk + zn) * 0.5f, o = (zk - zn) * 0.5f;
+            const f32x2 tt = cmul(tw2048[k], o);
+            const float xr = e[0] + tt[1], xi = e[1] - tt[0];
+            val = xr * xr + xi * xi;
+        }
+        out[k] = val;
+    }
+}
+hipError_t launch_stft_power_stream(const float *x, long ldx, long x0, long N, int B, int F, int t0, int hop, const float *win,
+                                    const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s) {
+    if (F < 1) return hipSuccess;
+    hipLaunchKernelGGL(stft_power_stream_kernel, dim3((unsigned)((long)B * F)), dim3(256), 0, s, x, ldx, x0, N, F, t0, hop, win,
+                       reinterpret_cast<const f32x2 *>(tw1024), reinterpret_cast<const f32x2 *>(tw2048), pw, ldp);
+    return hipGetLastError();
+}
+
+// decibels and the clamp of db_topdb_kernel on the F new rows of every slot (mel: row b F + f, 256 values), in place; one thread per mel band.
+//   peak != null: the floor of every row is peak[b] - top_db (the recording's maximum, known beforehand); grid (B, any): rows f = blockIdx.y,
+//                 blockIdx.y + gridDim.y, ...; run_max is not touched
+//   peak == null: the floor of row f is (the maximum over the slot's rows so far, this one included) - top_db: a prefix maximum along time,
+//                 carried in run_max[b] from call to call; grid (B, 1)
+__global__ __launch_bounds__(256) void db_stream_kernel(float *__restrict__ mel, int F, const float *__restrict__ peak,
+                                                        float *__restrict__ run_max, float top_db) {
+    __shared__ float sm[2][4];
+    const int b = blockIdx.x;
+    float *p = mel + (long)b * F * 256 + threadIdx.x;
+    if (peak) {
+        const float lo = peak[b] - top_db;
+        for (int f = blockIdx.y; f < F; f += gridDim.y) p[(long)f * 256] = fmaxf(10.0f * log10f(fmaxf(p[(long)f * 256], 1e-10f)), lo);
+        return;
+    }
+    float run = run_max[b];
+    for (int f = 0; f < F; ++f) {
+        const float v = 10.0f * log10f(fmaxf(p[(long)f * 256], 1e-10f));
+        float mx = v;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+        float *red = sm[f & 1];                             // two buffers: one barrier per row
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        run = fmaxf(run, fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+        const float lo = run - top_db;
+        p[(long)f * 256] = fmaxf(v, lo);
+    }
+    if (threadIdx.x == 0) run_max[b] = run;
+}
+hipError_t launch_db_stream(float *mel, int B, int F, const float *peak, float *run_max, float top_db, hipStream_t s) {
+    if (F < 1) return hipSuccess;
+    hipLaunchKernelGGL(db_stream_kernel, dim3(B, peak ? (F < 64 ? F : 64) : 1), dim3(256), 0, s, mel, F, peak, run_max, top_db);
+    return hipGetLastError();
+}
+
 }  // namespace ts

@@ -209,6 +209,148 @@ def mfcc(wave, sample_rate, n_mfcc=64, n_fft=2048, hop_length=734, n_mels=256, t
     return mfcc_from_power(power_spectrogram(wave, n_fft, hop_length), sample_rate, n_mfcc, n_fft, n_mels, top_db)
 
 
+# ---- wav sessions (talkshow_hip.h, "wav sessions"): the front end fed samples in chunks ------------------------------------------------
+class WavStreamPlan:
+    """The host arithmetic of a wav session (`ts_mfcc_stream_*`), restated: pure Python, no device, no library.  n samples received ->
+    resampled samples below `final22(n)` have every tap below n (the last tap of output j is (j // nnew) norig - width + kw - 1), MFCC rows
+    below `final_frames(n)` have every sample below that count (row t reads resampled samples t hop - 1024 .. t hop + 1023, and row 0, whose
+    sample -1024 reflects to 1024, one more); the flush ends
+    the recording at N22 = ceil(n nnew / norig) resampled samples and N22 // hop + 1 rows.  `push(n)` / `flush()` move the counters and
+    return the rows that call emits; `retained` names the two tails the session holds between calls (fewer than kw input samples — none at
+    equal rates — and at most 2048 resampled samples)."""
+
+    def __init__(self, sr_in, sr_out=22000, fps=30):
+        self.sr_in, self.sr_out, self.hop = int(sr_in), int(sr_out), _hop(fps)
+        if self.sr_in < 1 or self.sr_out < 1:
+            raise ValueError(f"WavStreamPlan: rates are positive, got {sr_in}, {sr_out}")
+        self.norig, self.nnew, self.width, self.kw = 1, 1, 0, 0
+        if self.sr_in != self.sr_out:
+            g = math.gcd(self.sr_in, self.sr_out)
+            self.norig, self.nnew = self.sr_in // g, self.sr_out // g
+            self.width = int(math.ceil(6.0 * self.norig / (min(self.norig, self.nnew) * 0.99)))
+            self.kw = 2 * self.width + self.norig
+        self.samples_in = self.frames_out = 0
+        self.flushed = False
+
+    def final22(self, n):
+        return (n - self.width) // self.norig * self.nnew if n >= self.width else 0
+
+    def total22(self, n):
+        return (self.nnew * n + self.norig - 1) // self.norig
+
+    def final_frames(self, n):
+        j = self.final22(n)
+        return (j - 1024) // self.hop + 1 if j >= 1025 else 0
+
+    def peek(self, n, flush=False):
+        """Rows the next call emits: a push of n samples, or (flush=True) a flush after n more samples."""
+        if self.flushed:
+            raise ValueError("the session has been flushed (the recording has ended): open another")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"a push holds no fewer than 0 samples, got {n}")
+        n1 = self.samples_in + n
+        if flush:
+            if self.total22(n1) <= 1024:
+                raise ValueError("clip shorter than half an FFT window (reflect padding undefined)")
+            return self.total22(n1) // self.hop + 1 - self.frames_out
+        return self.final_frames(n1) - self.frames_out
+
+    def push(self, n):
+        f = self.peek(n)
+        self.samples_in, self.frames_out = self.samples_in + int(n), self.frames_out + f
+        return f
+
+    def flush(self):
+        f = self.peek(0, flush=True)
+        self.frames_out, self.flushed = self.frames_out + f, True
+        return f
+
+    @property
+    def retained(self):
+        """(input samples, resampled samples) held after the last push."""
+        n = self.samples_in
+        in0 = n if self.sr_in == self.sr_out else max(0, self.final22(n) // self.nnew * self.norig - self.width)
+        return n - in0, self.final22(n) - max(0, self.frames_out * self.hop - 1025)
+
+    @property
+    def latency_samples(self):
+        """(resampled samples, input samples) a row follows its centre sample by: half a window, and the resampler's right wing."""
+        return 1024, (self.width + self.norig - 1 if self.sr_in != self.sr_out else 0)
+
+
+def _rows_matmul(a, b):
+    """a @ b with the bits a row has in a product of 4 rows or more.  The BLAS behind numpy sums a product of fewer rows in another order
+    (measured with OpenBLAS 0.3.29: rows of products of 4 rows and more do not depend on the row count or the row's place; below 4 they
+    do), and a session's call may emit 1 row where the one-shot product has the whole recording's."""
+    if a.shape[0] >= 4:
+        return a @ b
+    return (np.concatenate([a, np.zeros((4 - a.shape[0], a.shape[1]), a.dtype)]) @ b)[:a.shape[0]]
+
+
+def mfcc_stream(chunks, sample_rate, n_mfcc=64, n_fft=2048, hop_length=734, n_mels=256, top_db=80.0, db="running"):
+    """The numpy twin of a wav session at equal rates: chunks = a list of 1-D sample blocks at `sample_rate` (any sizes, empty ones too) ->
+    a list of (rows, n_mfcc) blocks, one per chunk and one for the flush; concatenated they are `mfcc(wave, ...).T` up to the clamp.
+    db = a number: the floor of every row is db - top_db (with the recording's own maximum in dB — `peak_db` — the rows equal `mfcc`
+    exactly); db = "running": the floor of row t is the maximum over rows 0 .. t, minus top_db (row t of `mfcc_from_power` on the first t + 1
+    frames).  Samples are held back as the device session holds them: a row leaves once its 2048 samples are in.  Exact for recordings of 4
+    rows or more (`_rows_matmul`)."""
+    if n_fft != 2048:
+        raise ValueError("mfcc_stream: the session's frames are 2048 samples long")
+    plan = WavStreamPlan(sample_rate, sample_rate, 30)
+    plan.hop = int(hop_length)
+    fb = melscale_fbanks(n_fft // 2 + 1, 0.0, float(sample_rate // 2), n_mels, sample_rate)
+    dct = create_dct(n_mfcc, n_mels)
+    window = (0.5 - 0.5 * np.cos(2.0 * math.pi * np.arange(n_fft) / n_fft)).astype(F32)
+    from scipy import fft as sfft
+    tail, r0 = np.zeros(0, F32), 0                 # resampled samples [r0, r0 + len(tail))
+    running = isinstance(db, str)
+    if running and db != "running":
+        raise ValueError(f"mfcc_stream: db is \"running\" or the recording's maximum in dB, got {db!r}")
+    run = F32(-np.inf)
+    out, early = [], []
+    for k in range(len(chunks) + 1):
+        flush = k == len(chunks)
+        t0 = plan.frames_out
+        if flush:
+            f, N = plan.flush(), plan.samples_in
+        else:
+            c = np.asarray(chunks[k], dtype=F32).reshape(-1)
+            tail = np.concatenate([tail, c])
+            f, N = plan.push(c.shape[0]), None
+        rows = np.zeros((f, n_mfcc), F32)
+        if f:
+            idx = (t0 + np.arange(f))[:, None] * plan.hop + np.arange(n_fft)[None, :] - n_fft // 2
+            idx = np.abs(idx)
+            if flush:
+                idx = np.where(idx >= N, 2 * (N - 1) - idx, idx)
+            spec = sfft.rfft(tail[idx - r0] * window[None, :], axis=1)
+            power = (spec.real.astype(F32) ** 2 + spec.imag.astype(F32) ** 2).astype(F32)
+            v = (10.0 * np.log10(np.maximum(_rows_matmul(power, fb), F32(1e-10)))).astype(F32)
+            if running:
+                floor = np.maximum.accumulate(np.maximum(v.max(axis=1), run)).astype(F32)
+                run = floor[-1]
+                v = np.maximum(v, (floor - F32(top_db))[:, None])
+            else:
+                v = np.maximum(v, F32(db) - F32(top_db))
+            rows = np.ascontiguousarray(_rows_matmul(v, dct), dtype=F32)
+            for i in range(f):          # running mode, rows 0 .. 2: "the first t + 1 frames" are fewer than 4, and a product of fewer than
+                if running and t0 + i < 3:   # 4 rows rounds differently (_rows_matmul): these rows take the prefix's own small products
+                    early.append(power[i])
+                    e = (10.0 * np.log10(np.maximum(np.stack(early) @ fb, F32(1e-10)))).astype(F32)
+                    rows[i] = (np.maximum(e, e.max() - F32(top_db)) @ dct)[t0 + i]
+        out.append(rows)
+        keep0 = max(0, plan.frames_out * plan.hop - 1025)
+        tail, r0 = tail[keep0 - r0:], keep0
+    return out
+
+
+def peak_db(wave, sample_rate, n_fft=2048, hop_length=734, n_mels=256):
+    """The maximum `mfcc` clamps at: max of 10 log10(max(mel, 1e-10)) over the recording (`MFCC.peak_db` on the device)."""
+    mel = power_spectrogram(wave, n_fft, hop_length) @ melscale_fbanks(n_fft // 2 + 1, 0.0, float(sample_rate // 2), n_mels, sample_rate)
+    return F32((10.0 * np.log10(np.maximum(mel, F32(1e-10)))).astype(F32).max())
+
+
 def mfcc_float64(wave, sample_rate, n_mfcc=64, n_fft=2048, hop_length=734, n_mels=256, top_db=80.0):
     """`mfcc` above carried out in float64 from the (float32) samples on: the yardstick for what fp32 arithmetic costs in the
     device front-end (bench.py `frontend.stability`, tests/test_gpu_parity.py::test_wav_in_code_stability).  -> (n_mfcc, T) float64."""

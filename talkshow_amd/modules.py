@@ -1044,6 +1044,145 @@ class MFCC:
         return [out[b, :int(n_res[b])] for b in range(B)]
 
 
+    # --- samples in chunks (`ts_mfcc_stream_*`; talkshow_hip.h, "wav sessions") ---
+    @property
+    def constants(self):
+        """The handle's resampler constants: dict of norig, nnew, width, kw (1, 1, 0, 0 at equal rates) and hop."""
+        out = (C.c_int32 * 5)()
+        _lib.load().ts_mfcc_constants(self._h, out)
+        return dict(zip(("norig", "nnew", "width", "kw", "hop"), (int(v) for v in out)))
+
+    def peak_db(self, wavs):
+        """The maximum the one-shot call clamps each recording at (its floor is this - 80 dB): wavs (B,N) / (N,) samples at sr_in, or a list of
+        (N_b,) recordings of different lengths -> (B,) float32 device tensor (`ts_mfcc_peak_db_mixed`).  Does not synchronise."""
+        from .frontend import check_recordings
+        if not isinstance(wavs, (list, tuple)):
+            wavs = _dev_f32(wavs, self._dev)
+            wavs = list(wavs[None] if wavs.ndim == 1 else wavs)
+        ns = check_recordings(wavs, "MFCC.peak_db")
+        wav, ns_host, ns_dev = pad_recordings(wavs, ns, range(len(ns)), self._dev)
+        out = torch.empty((len(ns),), dtype=torch.float32, device=self._dev)
+        _lib.check(_lib.load().ts_mfcc_peak_db_mixed(self._h, _lib.dptr(wav), ns_host.ctypes.data_as(C.POINTER(C.c_int32)), _lib.dptr(ns_dev),
+                                                     len(ns), int(wav.shape[1]), _lib.dptr(out), _lib.stream_ptr()))
+        return out
+
+    def open_stream(self, B, max_samples, db="running"):
+        """A session that takes the recording's samples in chunks: `MFCCStream`.  db="running": the floor of row t is the maximum over rows
+        0 .. t, minus 80 dB; db = a (B,) tensor or array (or one number): the recordings' maxima in dB (`peak_db`), known beforehand — the
+        rows then equal `self(wav)` bit for bit, whatever the chunking."""
+        return MFCCStream(self, B, max_samples, db)
+
+
+class MFCCStream:
+    """`MFCC.open_stream`: B slots on one sample clock.  `push(wav (B,n))` -> the (B,f,64) rows that became final (f may be 0; a row follows its
+    centre sample by 1024 resampled samples and the resampler's right wing), `flush()` -> the rest, ending the recording; `plan(n, flush)`
+    names f beforehand.  Concatenated, the rows are those of `MFCC(...)(wav)` for any chunking, bit for bit up to the clamp (see
+    `MFCC.open_stream`).  A bad argument raises ValueError before any device work, and no counter moves.  Slots share the clock: there is no
+    restart, save, load or fork."""
+
+    def __init__(self, mfcc, B, max_samples, db="running"):
+        self.mfcc, self.B, self.max_samples = mfcc, int(B), int(max_samples)
+        if self.B < 1 or self.max_samples < 1:
+            raise ValueError(f"open_stream: B and max_samples are at least 1, got B={B}, max_samples={max_samples}")
+        peak = None
+        if isinstance(db, str):
+            if db != "running":
+                raise ValueError(f"open_stream: db is \"running\" or the (B,) maxima in dB, got {db!r}")
+        else:
+            peak = torch.as_tensor(db, dtype=torch.float32).reshape(-1)
+            if peak.numel() == 1 and self.B > 1:
+                peak = peak.repeat(self.B)
+            if peak.numel() != self.B:
+                raise ValueError(f"open_stream: the maxima must hold 1 or B={self.B} values, got {peak.numel()}")
+            if not bool(torch.isfinite(peak).all()):
+                raise ValueError("open_stream: a maximum is not finite")
+            peak = peak.to(mfcc._dev).contiguous()
+        self.db = "running" if peak is None else "peak"
+        h = C.c_void_p()
+        with torch.cuda.device(mfcc._dev):
+            torch.cuda.current_stream().synchronize()      # the table is copied at open
+            _lib.check(_lib.load().ts_mfcc_stream_open(mfcc._h, self.B, self.max_samples, 0 if peak is None else 1, _lib.dptr(peak), C.byref(h)))
+        self._h = h
+        self.max_frames = int(_lib.load().ts_mfcc_stream_max_frames(h))
+        self._flushed = False
+
+    def _get(self, name):
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return int(getattr(_lib.load(), name)(self._h))
+
+    @property
+    def samples_in(self):
+        return self._get("ts_mfcc_stream_samples_in")
+
+    @property
+    def frames_out(self):
+        return self._get("ts_mfcc_stream_frames_out")
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the session's buffers: constant from open to close."""
+        return self._get("ts_mfcc_stream_state_bytes")
+
+    def plan(self, n, flush=False):
+        """Rows the next call returns: `push` of n samples, or (flush=True; n is not read) `flush()`.  ValueError where that call would."""
+        if self._h is None:
+            raise ValueError("the session is closed")
+        if self._flushed:
+            raise ValueError("the session has been flushed (the recording has ended): open another")
+        n = 0 if flush else int(n)
+        if n < 0 or n > self.max_samples:
+            raise ValueError(f"a push holds 0 to max_samples = {self.max_samples} samples, got {n}")
+        m, before, after = self.mfcc, C.c_long(), C.c_long()
+        try:
+            _lib.check(_lib.load().ts_mfcc_stream_plan(m.sr_in, m.sr_out, m.fps, self.samples_in, n, int(bool(flush)), C.byref(before), C.byref(after)))
+        except RuntimeError as e:          # host arithmetic only: a refusal is about the arguments
+            raise ValueError(str(e)) from None
+        return int(after.value) - self.frames_out
+
+    def push(self, wav):
+        """wav (B,n) samples at sr_in, 0 <= n <= max_samples (a (n,) block where B = 1) -> (B,f,64) device tensor."""
+        if not hasattr(wav, "shape") or len(wav.shape) not in (1, 2):
+            raise ValueError(f"push: wav must have shape (B={self.B}, n), got {tuple(getattr(wav, 'shape', ()))}")
+        shape = tuple(int(v) for v in wav.shape)
+        if len(shape) == 1:
+            shape = (1,) + shape
+        if shape[0] != self.B:
+            raise ValueError(f"push: wav must have shape (B={self.B}, n), got {tuple(wav.shape)}")
+        n = shape[1]
+        f = self.plan(n)
+        dev = self.mfcc._dev
+        out = torch.empty((self.B, f, 64), dtype=torch.float32, device=dev)
+        w = _dev_f32(wav, dev).reshape(self.B, n) if n else None
+        got = C.c_int()
+        _lib.check(_lib.load().ts_mfcc_stream_push(self._h, _lib.dptr(w), n, _lib.dptr(out) if f else None, C.byref(got), _lib.stream_ptr()))
+        assert got.value == f
+        return out
+
+    def flush(self):
+        """The rows held back, ending the recording.  A recording of 1024 resampled samples or fewer is refused (ValueError), as by the one-shot
+        call."""
+        f = self.plan(0, flush=True)
+        out = torch.empty((self.B, f, 64), dtype=torch.float32, device=self.mfcc._dev)
+        got = C.c_int()
+        _lib.check(_lib.load().ts_mfcc_stream_flush(self._h, _lib.dptr(out) if f else None, C.byref(got), _lib.stream_ptr()))
+        assert got.value == f
+        self._flushed = True
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            torch.cuda.synchronize()
+            _lib.load().ts_mfcc_stream_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def upload(a, dev):
     """numpy array -> device tensor through pinned memory, without blocking the host (a pageable copy waits for the stream)."""
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)

@@ -469,6 +469,18 @@ class SeamlessBodyStream:
             raise ValueError(str(e)) from None
         return int(n.value), int(m.value)
 
+    def plan_calls(self, t, flush=False):
+        """[(code_rows, pose_frames)] of `push` of t frames (left out for t = 0) and, with flush=True, of the `flush()` after it.  The push is
+        `plan(t)`; the flush after it needs no margin: it finalises every code row and pose frame of the frames received that is not out
+        yet, (frames_in + t) // 4 rows in all."""
+        if not flush:
+            return [self.plan(t)] if t else []
+        if not t:
+            return [self.plan(0, flush=True)]
+        n, m = self.plan(t)
+        total = (self.frames_in + int(t)) // 4
+        return [(n, m), (total - self.code_rows - n, 4 * total - self.frames - m)]
+
     def _call(self, mfcc, flush, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes):
         import ctypes as C
 
@@ -549,6 +561,190 @@ class SeamlessBodyStream:
             torch.cuda.synchronize()
             _lib.load().ts_body_stream_close(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WavBodyStream:
+    """See `TrainWrapper.open_stream(..., wav_sr=...)`: a body session fed SAMPLES.  It owns an `MFCCStream` (talkshow_hip.h, "wav
+    sessions") and the body session the frames go into; nothing leaves the device and nothing synchronises between the two.
+      push_wav(wav (B,n), **push keywords)  -> poses [, codes][, log-probabilities] as `push` of the body session returns them; a call that
+                                            yields no MFCC frame (or, in a plain session, fewer than 4 with the carried ones) makes no body
+                                            call and returns empty tensors
+      flush(**keywords)                     flushes the front end, pushes the last frames and (seamless) flushes the body session
+      plan_wav(n, flush=False)              -> (MFCC frames, code rows, pose frames) of that call: the row count of its `uniforms` / `given`
+    seamless=True: the frames go straight into the seamless session; with db = the recordings' maxima (`MFCC.peak_db`) every chunking of the
+    samples returns the bits of `generate_batch(MFCC(...)(wav), ...)`.  seamless=False: the plain session drops T % 4 frames per chunk, so
+    the wrapper forwards frames in multiples of 4 and carries the remainder: what comes back equals `BodyStream.push` of the same frame
+    blocks.  ALL SLOTS SHARE ONE SAMPLE CLOCK: `restart`, `save`, `load` and `fork` raise NotImplementedError."""
+
+    def _no_slots(self, *a, **k):
+        """Not taken by a wav-fed session (talkshow_hip.h, "wav sessions")."""
+        raise NotImplementedError("a wav-fed session restarts, saves, loads and forks no slot: its slots share one sample clock; feed MFCC "
+                                  "frames to a plain session (open_stream(..., seamless=False)) for those")
+    restart = save = load = fork = _no_slots
+
+    def __init__(self, wrapper, id, B, max_frames, seamless, wav_sr, wav_db="running", max_samples=None, fps=30, **defaults):
+        from talkshow_amd.frontend import WavStreamPlan
+        from talkshow_amd.modules import MFCC
+        self.w, self.B, self.seamless = wrapper, int(B), bool(seamless)
+        clock = WavStreamPlan(wav_sr, 22000, fps)                # ValueError: rates, fps
+        if max_samples is None:                                   # the samples of max_frames rows
+            max_samples = max(1, int(max_frames) * clock.hop * clock.norig // clock.nnew)
+        self.mfcc = MFCC(wav_sr, 22000, fps, device=wrapper.generator._dev())
+        self.front = self.mfcc.open_stream(self.B, max_samples, db=wav_db)
+        try:
+            frames_cap = max(int(max_frames), self.front.max_frames + 3)       # one call's rows, and a plain session's carried ones
+            self.max_frames = frames_cap
+            if self.seamless:
+                self.body = SeamlessBodyStream(wrapper, id, B, frames_cap, **defaults)
+            else:
+                from nets.smplx_body_pixel import BodyStream
+                self.body = BodyStream(wrapper, id, B, frames_cap, **defaults)
+                self._carry = None
+        except Exception:
+            self.front.close()
+            raise
+        self.pose_dim = wrapper.each_dim[1] + wrapper.each_dim[2]
+
+    # ---- counters ----
+    @property
+    def samples_in(self):
+        return self.front.samples_in
+
+    @property
+    def frames_in(self):
+        """MFCC frames the front end has produced."""
+        return self.front.frames_out
+
+    @property
+    def frames(self):
+        """Pose frames returned."""
+        return self.body.frames
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the front end's buffers (and of the seamless session's): constant from open to close."""
+        return self.front.state_bytes + (self.body.state_bytes if self.seamless else 0)
+
+    def _body_plan(self, f, flush):
+        """[(code rows, pose frames)] of the body calls a wav call of f new frames makes, in order."""
+        if not self.seamless:
+            t = (f + (0 if self._carry is None else int(self._carry.shape[1]))) // 4 * 4
+            return [(t // 4, t)] if t else []
+        return self.body.plan_calls(f, flush)
+
+    def plan_wav(self, n, flush=False):
+        """(MFCC frames, code rows, pose frames) of the next call: `push_wav` of n samples, or `flush()` with flush=True (n is not read)."""
+        f = self.front.plan(n, flush)
+        calls = self._body_plan(f, flush)
+        return f, sum(c[0] for c in calls), sum(c[1] for c in calls)
+
+    def _empty(self, logprobs, return_codes):
+        import torch
+        dev = self.w.generator._dev()
+        out = (torch.empty((self.B, 0, self.pose_dim), dtype=torch.float32, device=dev),)
+        out += ((torch.empty((self.B, 0, 2), dtype=torch.int64, device=dev),) if return_codes else ())
+        out += ((torch.empty((self.B, 0, 2), dtype=torch.float32, device=dev),) if logprobs else ())
+        return out[0] if len(out) == 1 else out
+
+    _KEYWORDS = ("mode", "seed", "clip_index0", "uniforms", "sampling", "logprobs", "given", "style", "code_bias", "repeat", "return_codes")
+
+    def _check(self, wav, flush, kw):
+        """Everything a call can be refused for, on the host, before the front end is given a sample: the wav block's shape and size, the
+        keywords' names, and for every body call this call will make the checks that body call makes itself (`step_pieces` with its
+        planned row count).  -> (MFCC rows, the body calls' (code rows, pose frames), uniforms as a host tensor or None)"""
+        import torch
+
+        from talkshow_amd import _lib
+        from talkshow_amd.modules import step_pieces
+        who = "flush" if flush else "push_wav"
+        n_samples = 0
+        if not flush:
+            shape = tuple(int(v) for v in getattr(wav, "shape", ()))
+            if len(shape) == 1 and self.B == 1:
+                shape = (1,) + shape
+            if len(shape) != 2 or shape[0] != self.B:
+                raise ValueError(f"push_wav: wav must have shape (B={self.B}, n), got {tuple(getattr(wav, 'shape', ()))}")
+            n_samples = shape[1]
+        for name in kw:
+            if name not in self._KEYWORDS:
+                raise TypeError(f"{who}: unknown keyword {name!r}")
+        f = self.front.plan(n_samples, flush)                       # ValueError: after the flush, n out of range, a too-short recording
+        calls = self._body_plan(f, flush)
+        rows = sum(c[0] for c in calls)
+        mode, uniforms, given = kw.get("mode", _lib.TS_SAMPLE_PHILOX), kw.get("uniforms"), kw.get("given")
+        if not self.seamless and kw.get("return_codes"):
+            raise ValueError(f"{who}: a plain session returns no codes (open the session with seamless=True)")
+        if uniforms is not None:
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
+            if tuple(uniforms.shape) != (self.B, rows, 2):
+                raise ValueError(f"{who}: this call runs {rows} code rows: uniforms must have shape (B={self.B}, {rows}, 2), got "
+                                 f"{tuple(uniforms.shape)} (session.plan_wav(n) names the count)")
+        if mode == _lib.TS_SAMPLE_UNIFORMS and uniforms is None and rows > 0:
+            raise ValueError(f"{who}: TS_SAMPLE_UNIFORMS needs uniforms of shape (B={self.B}, {rows}, 2) for the {rows} code rows this call runs")
+        # `given` goes to the one body call that runs code rows (a flush makes two calls, and often one of them runs none)
+        if given is not None and len([c for c in calls if c[0]]) > 1:
+            raise ValueError("flush: the closing call makes two body calls that run code rows: give `given` rows to the pushes before it")
+        if given is not None and not isinstance(given, (list, tuple)) and len(getattr(given, "shape", ())) == 3 and int(given.shape[1]) > rows:
+            raise ValueError(f"{who}: this call runs {rows} code rows: a given block holds at most {rows} rows per clip, got {tuple(given.shape)}")
+        if not any(kw.get("logprobs") is v for v in (None, False, True)):
+            raise ValueError(f"{who}: logprobs is True or False (a wav call may make two body calls: it returns a tensor of its own)")
+        chain = self.body if self.seamless else self.body.pix          # whose labels and defaults the step keywords meet
+        gen = self.w.generator
+        for nrows, _ in calls:
+            if nrows > 0:                                              # ValueError naming the clip; nothing is launched or uploaded
+                step_pieces(gen, self.B, chain._labels, chain.defaults, nrows, mode, gen._dev(), kw.get("sampling"), kw.get("logprobs"),
+                            given, kw.get("style"), kw.get("code_bias"), kw.get("repeat"))
+        return f, calls, uniforms
+
+    def _call(self, wav, flush, kw):
+        import torch
+        f, calls, uniforms = self._check(wav, flush, kw)
+        feat = self.front.flush() if flush else self.front.push(wav)
+        if not self.seamless:
+            if self._carry is not None:
+                feat = torch.cat([self._carry, feat], dim=1)
+            t = int(feat.shape[1]) // 4 * 4
+            self._carry = feat[:, t:].contiguous() if feat.shape[1] > t else None
+            if t == 0:
+                return self._empty(kw.get("logprobs"), False)
+            return self.body.push(feat[:, :t].contiguous(), **{k: v for k, v in kw.items() if k != "return_codes"})
+        outs, r0 = [], 0
+        for i, (nrows, _) in enumerate(calls):
+            k = dict(kw)
+            if uniforms is not None:
+                k["uniforms"] = uniforms[:, r0:r0 + nrows].contiguous()
+            r0 += nrows
+            if nrows == 0:                      # `given` rows are the rows of the one body call that runs code rows (_check)
+                k.pop("given", None)
+            last = flush and i == len(calls) - 1
+            out = self.body.flush(**k) if last else self.body.push(feat, **k)
+            outs.append(out if isinstance(out, tuple) else (out,))
+        if not outs:
+            return self._empty(kw.get("logprobs"), kw.get("return_codes"))
+        out = tuple(torch.cat(parts, dim=1) for parts in zip(*outs)) if len(outs) > 1 else outs[0]
+        return out[0] if len(out) == 1 else out
+
+    def push_wav(self, wav, **kw):
+        """wav (B,n) samples at wav_sr, 0 <= n <= max_samples; the keywords of the body session's `push` apply to the code rows this call
+        runs (`plan_wav(n)` names them).  A bad value raises ValueError before any device work, and no counter moves."""
+        return self._call(wav, False, kw)
+
+    def flush(self, **kw):
+        """The end of the recording: the front end's last frames go through the body session, and a seamless session is flushed.  `uniforms`
+        holds the rows of both body calls, in order."""
+        return self._call(None, True, kw)
+
+    def close(self):
+        try:
+            self.front.close()
+        finally:
+            self.body.close()
 
     def __del__(self):
         try:
