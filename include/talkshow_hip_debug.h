@@ -117,16 +117,21 @@ typedef struct ts_debug_skinny_problem {
 int ts_debug_skinny_run(ts_ctx *ctx, const ts_debug_skinny_problem *problems, int n, const char *knob_list, int *out5, void *stream);
 /* Test aid: ONE launch of a conv_gemm_f32 problem given as plain structs (csrc/kernels.h, ConvSeg / ConvGroup / ConvParams: the fields below
  * mirror them one for one; every pointer is a device pointer the caller owns; what the launchers set themselves — zero, sk_ws, sk_flags,
- * xcd_tiles, w_planes — is left out) through production's planning and launch code: plan_conv(p, tile, knob_list, the device's stream-K
- * check) and launch_conv_plan.  tile: 0 = the production plan, else a tile id of ts_op_conv1d_timed; 22 / 23 / 24 (Split) are refused here.
+ * xcd_tiles — is left out) through production's planning and launch code: plan_conv(p, tile, knob_list, the device's stream-K
+ * check) and launch_conv_plan.  tile: 0 = the production plan, else a tile id of ts_op_conv1d_timed.  22 / 23 = Split with 2 / 3
+ * planes on the fp32 weights as given; 24 = 22 with w_planes set, on plane images this entry makes of every group's whole weight image
+ * (launch_split_weight_planes chunk by chunk, so ldw and the strides between batched problems carry over: multiples of 32 then).  48 = Taps48:
+ * Ktot is a multiple of 48 there (any tap count), a multiple of 32 for every other tile.
  * knob_list: "NAME=VALUE,..." as for ts_debug_conv_plan, null = the defaults.  Allocates and uploads nothing beyond what the launchers do (the
- * stream-K band's per-stream scratch); does not synchronize `stream`.
+ * stream-K band's per-stream scratch) and tile 24's plane images; does not synchronize `stream`, except for tile 24 (the images are freed on return).
  * dry != 0: host only, no HIP call (ctx and the pointers may be null; the device is taken to pass the stream-K check): stops after planning
  * and the launcher's layout checks, so the same return value and out8 say what a launch WOULD run.
  * Returns the engine that ran (numbering of ts_debug_conv_plan) with out8 = {engine, tile rows, tile columns, waves, K chunk, tiles of
- * the second band (the 64-row tiles of a banded plan, the tiles of the stream-K band; 0 if none), workgroups in all, masked (0 / 1: the length-masked kernels)},
+ * the second band (the 64-row tiles of a banded plan, the tiles of the stream-K band; 0 if none), workgroups in all, masked (0 / 1: the length-masked kernels)}
+ * (Split: engine 7 with the 128 x 128 or 64 x 64 tile its launcher takes by size, 4 waves),
  * or -1 with ts_last_error() set: a bad argument, an unknown tile id, a layout the plan's kernel does not implement (lens on a tile without a
- * masked kernel or with batched problems, more than 4 segments, Ktot over 60 000, a segment that is no multiple of the tile's K chunk, ...).
+ * masked kernel or with batched problems, more than 4 segments, Ktot over 60 000, a segment that is no multiple of the tile's K chunk; Split:
+ * x, w, ldx, ldw, c0 or a batched stride off its 16-byte loads, plane images with 3 planes or a pitch that is no multiple of 32, ...).
  * Nothing is launched then. */
 typedef struct ts_debug_conv_seg {
     int d, c0, len, ntap;
@@ -150,6 +155,7 @@ typedef struct ts_debug_conv_problem {
     int sk_ok;
     const int32_t *lens;
     int len_shr, len_shl;
+    int w_planes;   /* tiles 22 / 23 only: every w IS a plane image already (ConvParams::w_planes); tile 24 makes the images itself */
 } ts_debug_conv_problem;
 int ts_debug_conv_run(ts_ctx *ctx, const ts_debug_conv_problem *problem, int tile, const char *knob_list, int dry, int *out8, void *stream);
 /* Host-only helper (no GPU needed): the stream-K plan of the ring engine for `groups` problems of M rows x N columns x K (csrc/conv_gemm_ring.hip:

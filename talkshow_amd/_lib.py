@@ -80,7 +80,7 @@ class ConvProblem(C.Structure):
                 ("act", _i), ("ngroups", _i), ("g", ConvGroup * 4), ("res_after_act", _i), ("ldw", C.c_long), ("w_rows", _i), ("zdiv", _i),
                 ("x_zs0", C.c_long), ("x_zs1", C.c_long), ("w_zs0", C.c_long), ("w_zs1", C.c_long), ("o_zs0", C.c_long),
                 ("o_zs1", C.c_long), ("b_zs1", C.c_long), ("r_zs0", C.c_long), ("r_zs1", C.c_long), ("sk_ok", _i), ("lens", _vp),
-                ("len_shr", _i), ("len_shl", _i)]
+                ("len_shr", _i), ("len_shl", _i), ("w_planes", _i)]
 
 
 # name -> (restype, argtypes); every symbol include/*.h declares

@@ -789,8 +789,8 @@ int ts_debug_skinny_run(ts_ctx *ctx, const ts_debug_skinny_problem *pr, int n, c
 int ts_debug_conv_run(ts_ctx *ctx, const ts_debug_conv_problem *d, int tile, const char *knob_list, int dry, int *out8, void *stream) {
     auto bad = [](const std::string &m) { return fail("ts_debug_conv_run: " + m) ? -1 : -1; };
     if (!d || !out8 || (!dry && !ctx)) return bad("null argument");
-    if (tile >= 22 && tile <= 24) return bad("the Split plans are not run here (tests/test_gpu_face_ops.py::test_split_bf16_gemm)");
-    if (d->M < 1 || d->N < 1 || d->Lout < 1 || d->Lin < 1 || d->stride < 1 || d->M % d->Lout || d->ldx < 1 || d->ldo < 1 || d->Ktot < 32 || d->Ktot % 32 ||
+    const int kq = tile == 48 ? 48 : 32;   // conv_taps48's K is 48 per tap, any tap count (conv_taps48_takes is the judge); everyone else walks chunks of 32
+    if (d->M < 1 || d->N < 1 || d->Lout < 1 || d->Lin < 1 || d->stride < 1 || d->M % d->Lout || d->ldx < 1 || d->ldo < 1 || d->Ktot < kq || d->Ktot % kq ||
         d->act < 0 || d->act > 3 || d->ldw < 0 || d->w_rows < 0 || d->zdiv < 0)
         return bad("bad geometry");
     if (d->ngroups < 1 || (d->zdiv == 0 && d->ngroups > 4) || (d->zdiv > 0 && d->ngroups % d->zdiv)) return bad("1 to 4 groups, or a multiple of zdiv batched problems");
@@ -820,11 +820,36 @@ int ts_debug_conv_run(ts_ctx *ctx, const ts_debug_conv_problem *d, int tile, con
         }
         if (s.nseg <= 4 && k != d->Ktot) return bad("the segments do not add up to Ktot");
     }
-    const ts::ConvPlan pl = ts::plan_conv(p, tile, ts::knobs_from_list(knob_list), dry ? true : ts::conv_sk_supported());
+    // 24 = 22 on plane images of the weights (w_planes), as ts_op_conv1d_timed and the face's x3 plan run it
+    if (d->w_planes && tile != 22 && tile != 23) return bad("w_planes: weights given as plane images are for tiles 22 / 23 (24 makes the images itself)");
+    p.w_planes = d->w_planes != 0 || tile == 24;
+    const ts::ConvPlan pl = ts::plan_conv(p, tile == 24 ? 22 : tile, ts::knobs_from_list(knob_list), dry ? true : ts::conv_sk_supported());
     if (pl.engine == ts::ConvEngine::Invalid) return bad("unknown tile id");
     if (const char *why = ts::conv_plan_refusal(p, pl)) return bad(why);
+    if (tile == 24 && (p.w_zs0 < 0 || p.w_zs1 < 0)) return bad("plane images of weights with a negative stride between batched problems");
     if (!dry) {
-        const hipError_t e = ts::launch_conv_plan(p, pl, (hipStream_t)stream);
+        // the plane images of every group's whole weight image: a chunk of 32 floats becomes a chunk of 32 dwords at the same offset, so the
+        // row pitch (ldw) and the strides between batched problems carry over (conv_plan_refusal has made sure they are multiples of 32)
+        DevBuf planes[4];
+        for (int z = 0; tile == 24 && z < (p.zdiv > 0 ? 1 : p.ngroups); ++z) {
+            const long rows = p.w_rows > 0 ? p.w_rows : (p.N + 127) / 128 * 128, ldw = p.ldw > 0 ? p.ldw : p.Ktot;
+            const long extent = rows * ldw + (p.zdiv > 0 ? (p.ngroups / p.zdiv - 1) * p.w_zs0 + (p.zdiv - 1) * p.w_zs1 : 0);
+            if (planes[z].ensure((size_t)extent * sizeof(float)) != 0) {   // (ensure has set the message)
+                (void)hipStreamSynchronize((hipStream_t)stream);
+                return -1;
+            }
+            const hipError_t es = ts::launch_split_weight_planes(p.g[z].w, planes[z].f(), extent / 32, 32, (hipStream_t)stream);
+            if (es != hipSuccess) {
+                (void)hipStreamSynchronize((hipStream_t)stream);
+                return bad(hipGetErrorString(es));
+            }
+            p.g[z].w = planes[z].f();
+        }
+        hipError_t e = ts::launch_conv_plan(p, pl, (hipStream_t)stream);
+        if (tile == 24) {   // the plane images die with this frame
+            const hipError_t ew = hipStreamSynchronize((hipStream_t)stream);
+            if (e == hipSuccess) e = ew;
+        }
         if (e != hipSuccess) return bad(hipGetErrorString(e));
     }
     const int nt128 = (p.N + 127) / 128;
@@ -842,7 +867,12 @@ int ts_debug_conv_run(ts_ctx *ctx, const ts_debug_conv_problem *d, int tile, con
         case ts::ConvEngine::Taps48: wgs = 8 * (int)((((long)(p.M + 127) / 128) * p.ngroups + 7) / 8); break;
         default: break;
     }
-    const int o[8] = {(int)pl.engine, pl.bm, pl.bn, pl.wm > 0 ? (pl.bm / pl.wm) * (pl.bn / pl.wn) : 0, pl.bk, second, wgs, p.lens ? 1 : 0};
+    int o[8] = {(int)pl.engine, pl.bm, pl.bn, pl.wm > 0 ? (pl.bm / pl.wm) * (pl.bn / pl.wn) : 0, pl.bk, second, wgs, p.lens ? 1 : 0};
+    if (pl.engine == ts::ConvEngine::Split) {   // the variant its launcher takes by size: 128 x 128 or 64 x 64 tiles, 4 waves
+        long n = 0;
+        o[1] = o[2] = ts::conv_split_tile(p, &n);
+        o[3] = 4, o[6] = (int)n;
+    }
     std::memcpy(out8, o, sizeof(o));
     return (int)pl.engine;
 }

@@ -479,7 +479,7 @@ const char *conv_plan_refusal(const ConvParams &p, const ConvPlan &pl) {
             return !conv_gemm_ring_takes(p) || p.zdiv > 0 || pl.bands.mt_big < 1 || pl.bands.mt_small < 1 ? "no ring band plan for this layer" : nullptr;
         case ConvEngine::RingSK: return !conv_sk_valid(p, pl.sk) ? "no stream-K plan for this layer" : nullptr;
         case ConvEngine::Taps48: return !conv_taps48_takes(p) ? "conv_taps48 does not take this layer" : nullptr;
-        case ConvEngine::Split: return nullptr;   // conv_gemm_split.hip checks its own layouts
+        case ConvEngine::Split: return conv_split_refusal(p, pl.planes);
         default: return "unknown tile id";
     }
 }

@@ -399,10 +399,54 @@ __global__ __launch_bounds__(256) void conv_gemm_split_kernel(const ConvParams p
 }
 
 
-// planes: 2 (three products) or 3 (six products).  Same tile ids as launch_conv_gemm (1: 128 x 128, 2: 64 x 64); 0 = by size.
+// What the kernel above cannot compute, or would misread (host only, no HIP call; conv_plan_refusal asks, and the launcher below): it fetches
+// 16 bytes at x + row ldx + c0 + 4 j and at w + row ldw + 4 j, walks a tap in chunks of 32 k, follows the segments for Ktot / 32 chunks, has no
+// length-masked form, and copies plane images (w_planes) chunk by chunk: an image holds two planes and every weight row must start on a chunk.
+const char *conv_split_refusal(const ConvParams &p, int planes) {
+    auto al = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (planes != 2 && planes != 3) return "the split engine runs 2 or 3 planes";
+    if (p.w_planes && planes != 2) return "plane images of the weights hold 2 planes: the 3-plane kernel splits fp32 weights itself";
+    if (p.lens) return "this engine has no length-masked kernel";
+    if (p.Ktot < 32 || p.Ktot % 32) return "the split engine walks K in chunks of 32: Ktot is no multiple of 32";
+    if (p.ldx & 3) return "the split engine loads 16 bytes of a row at a time: ldx is no multiple of 4";
+    const long ldw = p.ldw > 0 ? p.ldw : p.Ktot;
+    const long wq = p.w_planes ? 31 : 3;   // plane images: a chunk of 32 k is one 128-byte record
+    if (ldw & wq) return p.w_planes ? "plane images need a weight row pitch that is a multiple of 32" : "the split engine loads 16 bytes of a weight row at a time: ldw is no multiple of 4";
+    if (p.zdiv > 0) {
+        if ((p.x_zs0 | p.x_zs1) & 3) return "the split engine loads 16 bytes of a row at a time: a batched problem's x stride is no multiple of 4";
+        if ((p.w_zs0 | p.w_zs1) & wq) return p.w_planes ? "plane images need batched weight strides that are multiples of 32" : "the split engine loads 16 bytes of a weight row at a time: a batched problem's w stride is no multiple of 4";
+    }
+    const int ng = p.zdiv > 0 ? 1 : (p.ngroups < 4 ? p.ngroups : 4);
+    for (int z = 0; z < ng; ++z) {
+        const ConvGroup &g = p.g[z];
+        if (g.nseg < 1 || g.nseg > 4) return "1 to 4 segments";
+        if (!al(g.x)) return "the split engine loads 16 bytes of a row at a time: x is not 16-byte aligned";
+        if (!al(g.w)) return "the split engine loads 16 bytes of a weight row at a time: w is not 16-byte aligned";
+        long k = 0;
+        for (int i = 0; i < g.nseg; ++i) {
+            if (g.seg[i].len < 32 || g.seg[i].len % 32) return "a segment length that is no multiple of the split engine's K chunk of 32";
+            if (g.seg[i].c0 & 3) return "the split engine loads 16 bytes of a row at a time: a segment's c0 is no multiple of 4";
+            k += (long)g.seg[i].len * (g.seg[i].ntap > 1 ? g.seg[i].ntap : 1);
+        }
+        if (k != p.Ktot) return "the segments do not add up to Ktot";
+    }
+    return nullptr;
+}
+
+// the variant the launcher below takes: 128 (x 128) tiles from 200 of them on, 64 (x 64) below; *workgroups = its grid
+int conv_split_tile(const ConvParams &p, long *workgroups) {
+    const long tiles128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.ngroups;
+    const int t = tiles128 >= 200 ? 128 : 64;
+    const long mt = (p.M + t - 1) / t, nt = (p.N + t - 1) / t;
+    const bool xcd = knobs().split_xcd > 0 && p.ngroups == 1 && p.zdiv == 0;
+    if (workgroups) *workgroups = xcd ? ((mt * nt + 7) / 8) * 8 : mt * nt * p.ngroups;
+    return t;
+}
+
+// planes: 2 (three products) or 3 (six products).  128 x 128 tiles or 64 x 64 by size (conv_split_tile).
 hipError_t launch_conv_gemm_split(const ConvParams &p_in, int planes, hipStream_t stream) {
     ConvParams p = p_in;
-    if (!p.zero || p.g[0].nseg > 4 || p.Ktot > 60000 || p.Ktot % 32 != 0 || (planes != 2 && planes != 3)) return hipErrorInvalidValue;
+    if (!p.zero || p.Ktot > 60000 || conv_split_refusal(p, planes)) return hipErrorInvalidValue;
     dim3 block(256);
     const bool xcd = knobs().split_xcd > 0 && p.ngroups == 1 && p.zdiv == 0;
     p.xcd_tiles = xcd ? knobs().split_xcd : 0;
@@ -410,8 +454,7 @@ hipError_t launch_conv_gemm_split(const ConvParams &p_in, int planes, hipStream_
         const int mt = (p.M + bm - 1) / bm, nt = (p.N + bn - 1) / bn;
         return xcd ? dim3(((mt * nt + 7) / 8) * 8) : dim3(mt, nt, p.ngroups);
     };
-    const long tiles128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.ngroups;
-    const bool big = tiles128 >= 200;
+    const bool big = conv_split_tile(p, nullptr) == 128;
     if (planes == 2 && p.w_planes) {
         if (big) hipLaunchKernelGGL((conv_gemm_split_kernel<128, 128, 64, 64, 2, true>), grid(128, 128), block, 0, stream, p);
         else hipLaunchKernelGGL((conv_gemm_split_kernel<64, 64, 32, 32, 2, true>), grid(64, 64), block, 0, stream, p);
@@ -419,7 +462,6 @@ hipError_t launch_conv_gemm_split(const ConvParams &p_in, int planes, hipStream_
         if (big) hipLaunchKernelGGL((conv_gemm_split_kernel<128, 128, 64, 64, 2, false>), grid(128, 128), block, 0, stream, p);
         else hipLaunchKernelGGL((conv_gemm_split_kernel<64, 64, 32, 32, 2, false>), grid(64, 64), block, 0, stream, p);
     } else {
-        if (p.w_planes) return hipErrorInvalidValue;
         if (big) hipLaunchKernelGGL((conv_gemm_split_kernel<128, 128, 64, 64, 3, false>), grid(128, 128), block, 0, stream, p);
         else hipLaunchKernelGGL((conv_gemm_split_kernel<64, 64, 32, 32, 3, false>), grid(64, 64), block, 0, stream, p);
     }

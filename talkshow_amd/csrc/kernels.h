@@ -160,6 +160,10 @@ __host__ __device__ inline bool split_tile_of(int bid, int MT, int NT, int GW, i
 // dwords of bf16(x - bf16(x)) pairs; the same size and pitch as the fp32 matrix (rows x K floats, K % 32 == 0).  Done once per layer when
 // the x3 plan is selected: weights are constants, only the activations need splitting per call.
 hipError_t launch_split_weight_planes(const float *w, float *planes, long rows, int K, hipStream_t stream);
+// Host only, no HIP call: why conv_gemm_split.hip cannot run p with `planes` planes as laid out (the 16-byte loads, the K chunk of 32, plane
+// images), or null; and the tile edge its launcher takes (128 or 64) with the workgroups of its grid.
+const char *conv_split_refusal(const ConvParams &p, int planes);
+int conv_split_tile(const ConvParams &p, long *workgroups);
 double conv_gemm_flops(const ConvParams &p);
 
 // ------------------------------------------------------------------------------------------------
