@@ -771,6 +771,35 @@ struct PutWords {
 };
 hipError_t launch_put_words(int *dst, const int *host, long n, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// audio front-end kernels (mfcc.hip; host side: mfcc.cpp)
+// ------------------------------------------------------------------------------------------------
+hipError_t launch_resample_polyphase(const float *x, int B, int N, const float *kern, int norig, int nnew, int width, int kw,
+                                     float *out, int Nout, hipStream_t s);
+hipError_t launch_stft_power(const float *x, int B, int N, int T, int hop, const float *win, const float *tw1024, const float *tw2048,
+                             float *pw, int ldp, hipStream_t s);
+hipError_t launch_resample_kaiser(const float *x, int B, int N, const float *win, const float *delta, int nwin, int num_table,
+                                  double ratio, float *out, int Nout, int ldo, hipStream_t s);
+hipError_t launch_db_topdb(float *mel, int B, long per_clip, float top_db, hipStream_t s);
+// length variants (mixed passes): ns = device table of the recordings' own sample counts at the input rate
+hipError_t launch_resample_polyphase_lens(const float *x, int B, int N, const int *ns, const float *kern, int norig, int nnew, int width,
+                                          int kw, float *out, int Nout, hipStream_t s);
+hipError_t launch_copy_samples_lens(const float *x, int B, int N, const int *ns, float *out, hipStream_t s);
+hipError_t launch_resample_kaiser_lens(const float *x, int B, int N, const int *ns, const float *win, const float *delta, int nwin,
+                                       int num_table, double ratio, float *out, int ldo, hipStream_t s);
+hipError_t launch_mfcc_frames(const int *ns, int B, int N, int norig, int nnew, int hop, int *frames, hipStream_t s);
+hipError_t launch_stft_power_lens(const float *x, int B, int N, int T, const int *ns, int norig, int nnew, int hop, const float *win,
+                                  const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
+hipError_t launch_db_topdb_lens(float *mel, int B, int T, int width, const int *frames, float top_db, hipStream_t s);
+hipError_t launch_db_peak_lens(const float *mel, int B, int T, int width, const int *frames, float *out, hipStream_t s);
+// wav sessions: rows indexed by absolute sample index
+hipError_t launch_stream_rows_copy(const float *src, long lds, long off, int len, float *dst, long ldd, int B, hipStream_t s);
+hipError_t launch_resample_polyphase_stream(const float *x, long ldx, long x0, long n, int B, const float *kern, int norig, int nnew, int width,
+                                            int kw, float *out, long ldo, long o0, long j_lo, long j_hi, hipStream_t s);
+hipError_t launch_stft_power_stream(const float *x, long ldx, long x0, long N, int B, int F, int t0, int hop, const float *win,
+                                    const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
+hipError_t launch_db_stream(float *mel, int B, int F, const float *peak, float *run_max, float top_db, hipStream_t s);
+
 // ---- body_stream.hip: the staging around the window calls of a seamless body session (body_stream.cpp) ----
 // [tail (B, cap, 64) rows [0, n_tail) | chunk (B, t, 64)] per clip: frames [0, Tw) -> win (B, Tw, 64), frames [next0, next0 + n_next) ->
 // next (B, cap, 64) rows [0, n_next); tail != next.  Every pointer 16-byte aligned; a shape outside the buffers is hipErrorInvalidValue

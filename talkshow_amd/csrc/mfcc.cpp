@@ -13,34 +13,6 @@
 
 using namespace ts;
 
-namespace ts {
-hipError_t launch_resample_polyphase(const float *x, int B, int N, const float *kern, int norig, int nnew, int width, int kw,
-                                     float *out, int Nout, hipStream_t s);
-hipError_t launch_stft_power(const float *x, int B, int N, int T, int hop, const float *win, const float *tw1024, const float *tw2048,
-                             float *pw, int ldp, hipStream_t s);
-hipError_t launch_resample_kaiser(const float *x, int B, int N, const float *win, const float *delta, int nwin, int num_table,
-                                  double ratio, float *out, int Nout, int ldo, hipStream_t s);
-hipError_t launch_db_topdb(float *mel, int B, long per_clip, float top_db, hipStream_t s);
-// length variants (mixed passes; mfcc.hip): ns = device table of the recordings' own sample counts at the input rate
-hipError_t launch_resample_polyphase_lens(const float *x, int B, int N, const int *ns, const float *kern, int norig, int nnew, int width,
-                                          int kw, float *out, int Nout, hipStream_t s);
-hipError_t launch_copy_samples_lens(const float *x, int B, int N, const int *ns, float *out, hipStream_t s);
-hipError_t launch_resample_kaiser_lens(const float *x, int B, int N, const int *ns, const float *win, const float *delta, int nwin,
-                                       int num_table, double ratio, float *out, int ldo, hipStream_t s);
-hipError_t launch_mfcc_frames(const int *ns, int B, int N, int norig, int nnew, int hop, int *frames, hipStream_t s);
-hipError_t launch_stft_power_lens(const float *x, int B, int N, int T, const int *ns, int norig, int nnew, int hop, const float *win,
-                                  const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
-hipError_t launch_db_topdb_lens(float *mel, int B, int T, int width, const int *frames, float top_db, hipStream_t s);
-hipError_t launch_db_peak_lens(const float *mel, int B, int T, int width, const int *frames, float *out, hipStream_t s);
-// wav sessions (mfcc.hip): rows indexed by absolute sample index
-hipError_t launch_stream_rows_copy(const float *src, long lds, long off, int len, float *dst, long ldd, int B, hipStream_t s);
-hipError_t launch_resample_polyphase_stream(const float *x, long ldx, long x0, long n, int B, const float *kern, int norig, int nnew, int width,
-                                            int kw, float *out, long ldo, long o0, long j_lo, long j_hi, hipStream_t s);
-hipError_t launch_stft_power_stream(const float *x, long ldx, long x0, long N, int B, int F, int t0, int hop, const float *win,
-                                    const float *tw1024, const float *tw2048, float *pw, int ldp, hipStream_t s);
-hipError_t launch_db_stream(float *mel, int B, int F, const float *peak, float *run_max, float top_db, hipStream_t s);
-}  // namespace ts
-
 struct ts_mfcc {
     ts_ctx *ctx = nullptr;
     int sr_in = 0, sr_out = 0, norig = 1, nnew = 1, width = 0, kw = 0;
@@ -378,18 +350,18 @@ int ts_resample_kaiser_mixed(ts_ctx *ctx, const float *wav, const int32_t *ns_ho
 // The launch plan of ts_mfcc_forward on the padded block: the length variants of the three kernels that look across a recording's samples or
 // rows, and the two GEMMs in the (B, T_max) row form with the length-masked epilogue (whole-tile plans only: sk_ok stays 0, so a row's bits do
 // not depend on the rows it shares a launch with)
-int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, float *feat,
-                          void *stream) {
-    if (!m || !wav || !feat) return fail("ts_mfcc_forward_mixed: null argument");
-    TS_TRY(check_counts("ts_mfcc_forward_mixed", ns_host, ns_dev, B, N_max));
-    hipStream_t s = (hipStream_t)stream;
-    ts_ctx *ctx = m->ctx;
+namespace {
+// the front of both entries below, up to the mel projection: the checks under the entry's name, the workspace, then frames, resample, STFT and
+// mel GEMM.  Returns the stream's workspace with melb (B, T, nmels: mel power, rows at or beyond a recording's own frames 0) and frames (B) filled
+int mixed_mel(const char *who, ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, hipStream_t s,
+              ts_mfcc::Work **w_out, int *T_out) {
+    TS_TRY(check_counts(who, ns_host, ns_dev, B, N_max));
     const long N22 = m->resampled_len(N_max);
     const long T = N22 / m->hop + 1, M = (long)B * T;
-    if (N22 > 0x7fffffffl || M > 0x7fffffffl) return fail("ts_mfcc_forward_mixed: bad shape");
+    if (N22 > 0x7fffffffl || M > 0x7fffffffl) return fail(std::string(who) + ": bad shape");
     for (int b = 0; b < B; ++b)
         if (m->resampled_len(ns_host[b]) <= m->nfft / 2)
-            return fail("ts_mfcc_forward_mixed: clip " + std::to_string(b) + " is shorter than half an FFT window (reflect padding undefined)");
+            return fail(std::string(who) + ": clip " + std::to_string(b) + " is shorter than half an FFT window (reflect padding undefined)");
     ts_mfcc::Work &w = m->work(s);
     const size_t F = sizeof(float);
     const float *x22 = wav;
@@ -398,7 +370,7 @@ int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, 
     TS_TRY(w.melb.ensure((size_t)M * m->nmels * F));
     TS_TRY(w.frames.ensure((size_t)B * sizeof(int)));
     {
-        MiscScope ms(ctx, s);
+        MiscScope ms(m->ctx, s);
         TS_HIP(launch_mfcc_frames(ns_dev, B, (int)N_max, m->norig, m->nnew, m->hop, w.frames.i(), s));
         if (m->sr_in != m->sr_out) {
             TS_HIP(launch_resample_polyphase_lens(wav, B, (int)N_max, ns_dev, m->rs_kern.f(), m->norig, m->nnew, m->width, m->kw, w.x22.f(),
@@ -407,12 +379,24 @@ int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, 
         }
         TS_TRY(stft_stage(m, x22, ns_dev, B, (int)N22, (int)T, w.power.f(), s));
     }
-    TS_TRY(gemm_stage(m, m->mel, w.power.f(), m->nbins_pad, w.frames.i(), B, (int)T, w.melb.f(), m->nmels, s));
+    *w_out = &w;
+    *T_out = (int)T;
+    return gemm_stage(m, m->mel, w.power.f(), m->nbins_pad, w.frames.i(), B, (int)T, w.melb.f(), m->nmels, s);
+}
+}  // namespace
+
+int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, float *feat,
+                          void *stream) {
+    if (!m || !wav || !feat) return fail("ts_mfcc_forward_mixed: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    ts_mfcc::Work *w = nullptr;
+    int T = 0;
+    TS_TRY(mixed_mel("ts_mfcc_forward_mixed", m, wav, ns_host, ns_dev, B, N_max, s, &w, &T));
     {
-        MiscScope ms(ctx, s);
-        TS_TRY(db_stage(m, w.melb.f(), w.frames.i(), B, (int)T, s));
+        MiscScope ms(m->ctx, s);
+        TS_TRY(db_stage(m, w->melb.f(), w->frames.i(), B, T, s));
     }
-    TS_TRY(gemm_stage(m, m->dct, w.melb.f(), m->nmels, w.frames.i(), B, (int)T, feat, m->nmfcc, s));
+    TS_TRY(gemm_stage(m, m->dct, w->melb.f(), m->nmels, w->frames.i(), B, T, feat, m->nmfcc, s));
     return 0;
 }
 
@@ -421,35 +405,12 @@ int ts_mfcc_forward_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, 
 int ts_mfcc_peak_db_mixed(ts_mfcc *m, const float *wav, const int32_t *ns_host, const int32_t *ns_dev, int B, long N_max, float *out,
                           void *stream) {
     if (!m || !wav || !out) return fail("ts_mfcc_peak_db_mixed: null argument");
-    TS_TRY(check_counts("ts_mfcc_peak_db_mixed", ns_host, ns_dev, B, N_max));
     hipStream_t s = (hipStream_t)stream;
-    ts_ctx *ctx = m->ctx;
-    const long N22 = m->resampled_len(N_max);
-    const long T = N22 / m->hop + 1, M = (long)B * T;
-    if (N22 > 0x7fffffffl || M > 0x7fffffffl) return fail("ts_mfcc_peak_db_mixed: bad shape");
-    for (int b = 0; b < B; ++b)
-        if (m->resampled_len(ns_host[b]) <= m->nfft / 2)
-            return fail("ts_mfcc_peak_db_mixed: clip " + std::to_string(b) + " is shorter than half an FFT window (reflect padding undefined)");
-    ts_mfcc::Work &w = m->work(s);
-    const size_t F = sizeof(float);
-    const float *x22 = wav;
-    if (m->sr_in != m->sr_out) TS_TRY(w.x22.ensure((size_t)B * N22 * F));
-    TS_TRY(w.power.ensure((size_t)M * m->nbins_pad * F));
-    TS_TRY(w.melb.ensure((size_t)M * m->nmels * F));
-    TS_TRY(w.frames.ensure((size_t)B * sizeof(int)));
-    {
-        MiscScope ms(ctx, s);
-        TS_HIP(launch_mfcc_frames(ns_dev, B, (int)N_max, m->norig, m->nnew, m->hop, w.frames.i(), s));
-        if (m->sr_in != m->sr_out) {
-            TS_HIP(launch_resample_polyphase_lens(wav, B, (int)N_max, ns_dev, m->rs_kern.f(), m->norig, m->nnew, m->width, m->kw, w.x22.f(),
-                                                  (int)N22, s));
-            x22 = w.x22.f();
-        }
-        TS_TRY(stft_stage(m, x22, ns_dev, B, (int)N22, (int)T, w.power.f(), s));
-    }
-    TS_TRY(gemm_stage(m, m->mel, w.power.f(), m->nbins_pad, w.frames.i(), B, (int)T, w.melb.f(), m->nmels, s));
-    MiscScope ms(ctx, s);
-    TS_HIP(launch_db_peak_lens(w.melb.f(), B, (int)T, m->nmels, w.frames.i(), out, s));
+    ts_mfcc::Work *w = nullptr;
+    int T = 0;
+    TS_TRY(mixed_mel("ts_mfcc_peak_db_mixed", m, wav, ns_host, ns_dev, B, N_max, s, &w, &T));
+    MiscScope ms(m->ctx, s);
+    TS_HIP(launch_db_peak_lens(w->melb.f(), B, T, m->nmels, w->frames.i(), out, s));
     return 0;
 }
 
