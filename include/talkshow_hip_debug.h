@@ -384,6 +384,28 @@ int ts_debug_wino_codes(ts_ctx *ctx, int nnet, int B, int L, int C, const int32_
  * matrices the tables were multiplied by; *tables_dev = the tables' device address.  Synchronizes. */
 int ts_debug_vqvae_dec_tables(ts_vqvae *vq, float *tables, float *aft_table, float *u, const float **tables_dev);
 
+/* ---- stage taps of the conv trunks (csrc/models.cpp: run_trunk_n, vq_decode_n; tests/test_gpu_vq_stages.py) ----
+ * Test aid: makes the PRODUCTION pass copy every stage's output to caller buffers; there is no second code path.  The table is thread-local
+ * and one-shot: it applies to the next pass entry this thread makes — ts_audioenc_forward [_masked], ts_vqvae_encode / _decode / _decode_z /
+ * _forward, ts_body_vq_infer [_mixed], ts_vqvae_decode_pair [_masked], ts_vqvae_encode_pair_masked, called directly or from inside another entry
+ * (ts_body_pixel_infer runs three of them: set the table right ahead of the call it is meant for) — and is dropped when that entry returns,
+ * whether it succeeded or not.  taps == null drops a table that still waits.  Always returns 0.
+ * enc[i][k] / dec[i][k]: DEVICE pointers, each may be null; i = the network's index in a paired pass (0 body, 1 hand; a single network is
+ * 0).  Stage k of the encoder trunk / of the decoder:
+ *   0  project                       | the decoder's first layer (the aft_vq table gather, or aft_vq_conv on continuous latents)
+ *   1  _enc_1    2  _down_1          | 1  _dec_1    2  _up_2
+ *   3  _enc_2    4  _down_2          | 3  _dec_2    4  _up_3
+ *   5  _enc_3                        | 5  _dec_3
+ * (z and the decoder's project are outputs already.)  Each tap is one hipMemcpyAsync, device to device on the pass's stream right after the
+ * stage's last launch, of the dense (B, L_stage, C_stage) block the stage left in the arena: encoder L = T, T, T/2, T/2, T/4, T/4 and
+ * C = hid/4, hid/4, hid/2, hid/2, hid, hid; decoder L = H, H, 2H, 2H, 4H, 4H and C = hid, hid, hid/2, hid/2, hid/4, hid/4; a masked pass
+ * copies the rows of T_max / H.  With no table a pass issues exactly what it issues without this entry. */
+typedef struct ts_debug_trunk_tap_table {
+    float *enc[2][6];
+    float *dec[2][6];
+} ts_debug_trunk_tap_table;
+int ts_debug_trunk_taps(const ts_debug_trunk_tap_table *taps);
+
 /* ---- seamless sessions (csrc/body_stream.cpp; talkshow_hip.h, "seamless sessions") ----
  * Host-only (no GPU): one call of the window plan on given counters.  state4 = {frames received F, code rows done A, code rows whose poses
  * are out D, flushed}; a push of t >= 1 frames (flush = 0) or the flush (flush != 0, t = 0); enc_lowered != 0: the plan of a session whose

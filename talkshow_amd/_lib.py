@@ -83,6 +83,11 @@ class ConvProblem(C.Structure):
                 ("len_shr", _i), ("len_shl", _i), ("w_planes", _i)]
 
 
+class TrunkTaps(C.Structure):
+    """ts_debug_trunk_tap_table (include/talkshow_hip_debug.h): device pointers enc[network][stage], dec[network][stage], null = no tap."""
+    _fields_ = [("enc", (_vp * 6) * 2), ("dec", (_vp * 6) * 2)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "ts_ctx_create": (_i, [_i, C.POINTER(_vp)]),
@@ -257,6 +262,7 @@ SIGNATURES = {
     "ts_debug_wino_gemm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ts_debug_wino_codes": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ts_debug_vqvae_dec_tables": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "ts_debug_trunk_taps": (_i, [C.POINTER(TrunkTaps)]),
     "ts_debug_conv_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_plan": (_i, [C.POINTER(_i), _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_run": (_i, [_vp, C.POINTER(SkinnyProblem), _i, C.c_char_p, C.POINTER(_i), _vp]),

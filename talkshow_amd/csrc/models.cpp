@@ -468,6 +468,33 @@ struct LenMask {
     int shr, shl;
 };
 
+// Stage taps (talkshow_hip_debug.h, ts_debug_trunk_taps): a table this thread set waits (`pending`) for the next pass entry of the C ABI
+// below; that entry's TapScope makes it `active` for its own duration, nested entries included, and drops it on the way out.  A pass
+// without a table pays one thread-local load per stage and issues nothing.
+struct TapState {
+    ts_debug_trunk_tap_table t;
+    bool pending = false, active = false;
+    int depth = 0;
+};
+thread_local TapState g_taps;
+struct TapScope {
+    TapScope() {
+        if (g_taps.depth++ == 0 && g_taps.pending) g_taps.active = true, g_taps.pending = false;
+    }
+    ~TapScope() {
+        if (--g_taps.depth == 0) g_taps.active = false;
+    }
+};
+// the dense (B, L, c) block a stage left in pool buffer `idx` of each network -> the caller's buffer of that stage, on the pass's stream
+int tap_stage(bool dec, int stage, int n, Pool *const *pool, int idx, size_t floats, hipStream_t s) {
+    if (!g_taps.active) return 0;
+    for (int i = 0; i < n; ++i) {
+        float *dst = dec ? g_taps.t.dec[i][stage] : g_taps.t.enc[i][stage];
+        if (dst) TS_HIP(hipMemcpyAsync(dst, pool[i]->buf(idx), floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+
 // Runs the same layer of n (1 or 2) structurally identical networks.  Body and hand VQ-VAEs differ only in their weights
 // (and in the width of their first / last layer), so wherever the two layers have the same geometry they go out as ONE
 // grouped conv_gemm launch (blockIdx.z selects the network): twice the tiles per launch, which is what the 256 CUs need
@@ -632,22 +659,28 @@ int run_trunk_n(int n, ts_convnet *const *net, const float *const *x, int x_ld, 
     // first layer: input widths differ between body and hand (39 / 90 channels) -> separate launches
     for (int i = 0; i < n; ++i)
         TS_TRY(run_layer(ctx, net[i]->project, xin[i], ldx[i], B, L, nullptr, 0, pool[i]->buf(0), hid / 4, 0, hid / 4, s, &tmp, k0));
+    TS_TRY(tap_stage(false, 0, n, pool, 0, (size_t)B * L * (hid / 4), s));
     for (int i = 0; i < n; ++i) Sp[i] = &net[i]->s1;
     TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 4, B, L, s, &o, k0));
     cur = o;
+    TS_TRY(tap_stage(false, 1, n, pool, cur, (size_t)B * L * (hid / 4), s));
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &net[i]->down1; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 2; }
     TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 4, B, L, nullptr, 0, op, hid / 2, nullptr, ns, s, &L, k1));
     cur = o;
+    TS_TRY(tap_stage(false, 2, n, pool, cur, (size_t)B * L * (hid / 2), s));
     for (int i = 0; i < n; ++i) Sp[i] = &net[i]->s2;
     TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 2, B, L, s, &o, k1));
     cur = o;
+    TS_TRY(tap_stage(false, 3, n, pool, cur, (size_t)B * L * (hid / 2), s));
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &net[i]->down2; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid; }
     TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 2, B, L, nullptr, 0, op, hid, nullptr, ns, s, &L, k2));
     cur = o;
+    TS_TRY(tap_stage(false, 4, n, pool, cur, (size_t)B * L * hid, s));
     for (int i = 0; i < n; ++i) Sp[i] = &net[i]->s3;
     TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o, k2));
+    TS_TRY(tap_stage(false, 5, n, pool, o, (size_t)B * L * hid, s));
     *out_idx = o;
     *H = L;
     return 0;
@@ -758,6 +791,7 @@ int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const flo
         }
     }
     int cur = 0, o = 0, L = H;
+    TS_TRY(tap_stage(true, 0, n, pool, 0, (size_t)B * L * hid, s));
     const ConvLayer *Lp[2];
     const Stack *Sp[2];
     const float *xp[2];
@@ -775,19 +809,24 @@ int vq_decode_n(int n, ts_vqvae *const *vq, const int64_t *const *lat, const flo
     }
     TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid, B, L, s, &o, k0, tables ? &src : nullptr));
     cur = o;
+    TS_TRY(tap_stage(true, 1, n, pool, cur, (size_t)B * L * hid, s));
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &vq[i]->up2; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 2; }
     TS_TRY(run_layer_n(ctx, n, Lp, xp, hid, B, L, nullptr, 0, op, hid / 2, nullptr, ns, s, &L, k0));   // (up-conv: masked at its input's length)
     cur = o;
+    TS_TRY(tap_stage(true, 2, n, pool, cur, (size_t)B * L * (hid / 2), s));
     for (int i = 0; i < n; ++i) Sp[i] = &vq[i]->d2;
     TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 2, B, L, s, &o, k1));
     cur = o;
+    TS_TRY(tap_stage(true, 3, n, pool, cur, (size_t)B * L * (hid / 2), s));
     o = pool[0]->pick(cur);
     for (int i = 0; i < n; ++i) { Lp[i] = &vq[i]->up3; xp[i] = pool[i]->buf(cur); op[i] = pool[i]->buf(o); ns[i] = hid / 4; }
     TS_TRY(run_layer_n(ctx, n, Lp, xp, hid / 2, B, L, nullptr, 0, op, hid / 4, nullptr, ns, s, &L, k1));
     cur = o;
+    TS_TRY(tap_stage(true, 4, n, pool, cur, (size_t)B * L * (hid / 4), s));
     for (int i = 0; i < n; ++i) Sp[i] = &vq[i]->d3;
     TS_TRY(run_stack_n(ctx, n, Sp, pool, cur, hid / 4, B, L, s, &o, k2));
+    TS_TRY(tap_stage(true, 5, n, pool, o, (size_t)B * L * (hid / 4), s));
     int tmp = 0;
     // last layer: output widths differ (39 / 90) -> separate launches into the two column ranges of `out`
     for (int i = 0; i < n; ++i)
@@ -914,6 +953,7 @@ int ts_audioenc_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int in_dim, int
 void ts_convnet_destroy(ts_convnet *net) { delete net; }
 
 int ts_audioenc_forward(ts_convnet *net, const float *mfcc, int B, int T, float *feat, void *stream) {
+    TapScope taps;
     if (!net || !mfcc || !feat) return fail("ts_audioenc_forward: null argument");
     hipStream_t s = (hipStream_t)stream;
     int idx = 0, H = 0;
@@ -923,6 +963,7 @@ int ts_audioenc_forward(ts_convnet *net, const float *mfcc, int B, int T, float 
 }
 
 int ts_audioenc_forward_masked(ts_convnet *net, const float *mfcc, const int32_t *lens, int B, int T, float *feat, void *stream) {
+    TapScope taps;
     if (!net || !mfcc || !lens || !feat) return fail("ts_audioenc_forward_masked: null argument");
     if (B < 1) return fail("ts_audioenc_forward_masked: bad shape");
     hipStream_t s = (hipStream_t)stream;
@@ -988,6 +1029,7 @@ int ts_vqvae_create(ts_ctx *ctx, const ts_tensor *sd_, int n, int in_dim, int em
 void ts_vqvae_destroy(ts_vqvae *vq) { delete vq; }
 
 int ts_vqvae_encode(ts_vqvae *vq, const float *poses, int B, int T, float *z, int64_t *lat, float *q, void *stream) {
+    TapScope taps;
     if (!vq || !poses) return fail("ts_vqvae_encode: null argument");
     if (vq->ncode > 0 && !lat) return fail("ts_vqvae_encode: latents_dev is required for a network with a codebook");
     if (vq->ncode == 0 && (!z || lat || q)) return fail("ts_vqvae_encode: an auto-encoder (num_embeddings = 0) produces z only");
@@ -996,12 +1038,14 @@ int ts_vqvae_encode(ts_vqvae *vq, const float *poses, int B, int T, float *z, in
 }
 
 int ts_vqvae_decode(ts_vqvae *vq, const int64_t *lat, int B, int H, float *out, int out_ld, int col0, void *stream) {
+    TapScope taps;
     if (!vq || !lat || !out) return fail("ts_vqvae_decode: null argument");
     if (out_ld < col0 + vq->in_dim) return fail("ts_vqvae_decode: out_ld too small");
     return vq_decode_impl(vq, lat, B, H, out, out_ld, col0, (hipStream_t)stream);
 }
 
 int ts_vqvae_decode_z(ts_vqvae *vq, const float *z, int B, int H, float *out, int out_ld, int col0, void *stream) {
+    TapScope taps;
     if (!vq || !z || !out) return fail("ts_vqvae_decode_z: null argument");
     if (out_ld < col0 + vq->in_dim) return fail("ts_vqvae_decode_z: out_ld too small");
     ts_vqvae *vp[1] = {vq};
@@ -1012,6 +1056,7 @@ int ts_vqvae_decode_z(ts_vqvae *vq, const float *z, int B, int H, float *out, in
 
 int ts_vqvae_forward(ts_vqvae *vq, const float *poses, int B, int T, int64_t *lat, float *out, int out_ld, int col0,
                      void *stream) {
+    TapScope taps;
     if (!vq || !poses || !out) return fail("ts_vqvae_forward: null argument");
     if (vq->ncode == 0) return fail("ts_vqvae_forward: auto-encoder handle; use ts_vqvae_encode + ts_vqvae_decode_z");
     hipStream_t s = (hipStream_t)stream;
@@ -1028,6 +1073,7 @@ int ts_vqvae_forward(ts_vqvae *vq, const float *poses, int B, int T, int64_t *la
 
 int ts_body_vq_infer(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int B, int T, int64_t *codes, float *recon,
                      void *stream) {
+    TapScope taps;
     if (!vb || !vh || !poses) return fail("ts_body_vq_infer: null argument");
     if (!codes && !recon) return fail("ts_body_vq_infer: nothing to produce");
     hipStream_t s = (hipStream_t)stream;
@@ -1059,6 +1105,7 @@ int ts_body_vq_infer(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int B, int 
 // VQVAE.decode of body and hand latents into the two column ranges of one (B,4H,body+hand) buffer, in lockstep
 int ts_vqvae_decode_pair(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_body, const int64_t *lat_hand, int B, int H,
                          float *out, void *stream) {
+    TapScope taps;
     if (!vb || !vh || !lat_body || !lat_hand || !out) return fail("ts_vqvae_decode_pair: null argument");
     ts_vqvae *vqs[2] = {vb, vh};
     const int64_t *lc[2] = {lat_body, lat_hand};
@@ -1068,6 +1115,7 @@ int ts_vqvae_decode_pair(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_body, co
 
 int ts_vqvae_decode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_body, const int64_t *lat_hand, const int32_t *lens,
                                 int B, int H, float *out, void *stream) {
+    TapScope taps;
     if (!vb || !vh || !lat_body || !lat_hand || !lens || !out) return fail("ts_vqvae_decode_pair_masked: null argument");
     if (B < 1 || H < 1) return fail("ts_vqvae_decode_pair_masked: bad shape");
     ts_vqvae *vqs[2] = {vb, vh};
@@ -1080,6 +1128,7 @@ int ts_vqvae_decode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const int64_t *lat_b
 // VQVAE.encode of both parts for clips of different lengths in one pass (talkshow_hip.h, "given poses")
 int ts_vqvae_encode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const float *poses, int poses_ld, const int32_t *lens, int B, int T_max,
                                 int64_t *codes, float *z_body, float *z_hand, void *stream) {
+    TapScope taps;
     if (!vb || !vh || !poses || !lens || !codes) return fail("ts_vqvae_encode_pair_masked: null argument");
     if (B < 1) return fail("ts_vqvae_encode_pair_masked: bad shape");
     if (poses_ld < vb->in_dim + vh->in_dim) return fail("ts_vqvae_encode_pair_masked: poses_ld is smaller than body_dim + hand_dim");
@@ -1089,6 +1138,7 @@ int ts_vqvae_encode_pair_masked(ts_vqvae *vb, ts_vqvae *vh, const float *poses, 
 // ts_body_vq_infer for clips of different lengths: the encode above, then ts_vqvae_decode_pair_masked
 int ts_body_vq_infer_mixed(ts_vqvae *vb, ts_vqvae *vh, const float *poses, const int32_t *lens, int B, int T_max, int64_t *codes, float *recon,
                            void *stream) {
+    TapScope taps;
     if (!vb || !vh || !poses || !lens) return fail("ts_body_vq_infer_mixed: null argument");
     if (!codes && !recon) return fail("ts_body_vq_infer_mixed: nothing to produce");
     if (B < 1) return fail("ts_body_vq_infer_mixed: bad shape");
@@ -1110,6 +1160,13 @@ int ts_body_vq_infer_mixed(ts_vqvae *vb, ts_vqvae *vh, const float *poses, const
         TS_HIP(hipMemcpy2DAsync(lp[k], sizeof(int64_t), codes + k, 2 * sizeof(int64_t), sizeof(int64_t), (size_t)B * H, hipMemcpyDeviceToDevice, s));
     }
     return ts_vqvae_decode_pair_masked(vb, vh, lp[0], lp[1], lens, B, H, recon, s);
+}
+
+// test aid (talkshow_hip_debug.h): the table the next pass entry of this thread copies its stages' outputs to
+int ts_debug_trunk_taps(const ts_debug_trunk_tap_table *taps) {
+    g_taps.pending = taps != nullptr;
+    if (taps) g_taps.t = *taps;
+    return 0;
 }
 
 // test aid (talkshow_hip_debug.h): the decoder's code tables and what they were made from, copied to the host

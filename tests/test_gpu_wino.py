@@ -9,7 +9,9 @@ out sentinel-filled: an overrun changes a zone, an element the kernels must writ
 
 Bound of the op-level comparison: 2e-5 on layers of unit scale, the bound the project's conv op tests were measured under
 (profiles/r06_notes/measured_errors_s5.jsonl) — taken from there, not from this code; the direct engine's error on the same inputs is
-recorded beside it (assert_close_measured)."""
+recorded beside it (assert_close_measured).  Beyond unit scale (test_lowered_layer_regimes): the error in units of the TILE's scale under
+the bound of tests/test_gpu_vq_stages.py (LOWERED_BOUND: 2x the first MI355X record, profiles/vq_stages_measured.jsonl), the direct engine
+under WHOLE_BOUND of tests/test_gpu_conv_ops.py in units of the element's own scale."""
 import ctypes as C
 import os
 import subprocess
@@ -181,6 +183,72 @@ def test_lowered_layer_against_float64(hip, Cc):
         _lib.check(lib.ts_op_conv1d(ctx, _lib.dptr(xd), B, L, Cc, w.ctypes.data_as(C.POINTER(C.c_float)), bias.ctypes.data_as(C.POINTER(C.c_float)),
                                     Cc, 3, 1, 1, 0, 1, _lib.dptr(out), _lib.stream_ptr()))
         assert_close_measured(f"direct layer C={Cc} L={L} act=1", out.cpu().numpy(), act64(pre, 1), BOUND)
+
+
+LAYER_REGIMES = ("unit", "onset", "spike", "offset", "post_relu")
+
+
+def layer_input(regime, rng, B, L, Cc):
+    """unit; onset inside a tile (rows < 10 scaled 1e-3: rows 8 and 9 are quiet rows of the tile that holds the loud rows 10 and 11); one row
+    times 100; a DC offset of 30; post-ReLU (half the elements zero, none negative)."""
+    x = rng.standard_normal((B, L, Cc)).astype(F32)
+    if regime == "onset":
+        x[:, :10] *= F32(1e-3)
+    elif regime == "spike":
+        x[:, L // 2] *= F32(100.0)
+    elif regime == "offset":
+        x += F32(30.0)
+    elif regime == "post_relu":
+        x = np.maximum(x, F32(0))
+    return x
+
+
+@pytest.mark.parametrize("Cc", [512, 64])
+def test_lowered_layer_regimes(hip, Cc):
+    """One lowered layer beyond unit scale (tests/test_vq_stages_host.py has the units): under every input regime its error in units of the
+    TILE scale |b| + sum_c max_tile |x_c| sum_k |w_k| is asserted under the bound of the lowered stacks (tests/test_gpu_vq_stages.py::
+    LOWERED_BOUND; recorded only while that is None) and within 4x the unit regime's; the direct engine on the same inputs (ts_op_conv1d) under
+    WHOLE_BOUND in units of the element's own scale.  Recorded beside them: the lowered error in own-scale units, and lowered / direct on the
+    quiet rows of the onset tile (the lowering's error is relative to its tile, not to the row)."""
+    import test_vq_stages_host as H
+    from test_gpu_conv_ops import WHOLE_BOUND
+    from test_gpu_vq_stages import LOWERED_BOUND, LOWERED_REGIME_RATIO, in_units, record
+    _lib, lib, ctx = hip
+    rng = np.random.default_rng(200 + Cc)
+    B = 3
+    w = (rng.standard_normal((Cc, Cc, 3)) / np.sqrt(3 * Cc)).astype(F32)
+    bias = rng.standard_normal(Cc).astype(F32)
+    Ud = weights(hip, w)
+    aw = np.abs(w.astype(F64))
+    worst = {}
+    for L in (5, 19, 24):
+        for regime in LAYER_REGIMES:
+            x = layer_input(regime, rng, B, L, Cc)
+            ref = act64(conv64(x, w, bias), 1)
+            ax = np.abs(x.astype(F64))
+            own = H.conv_same(ax, aw) + np.abs(bias.astype(F64))
+            tile = H.tile_max(ax) @ aw.sum(2).T + np.abs(bias.astype(F64))
+            got = lowered_layer(hip, x, Ud, bias, 1)
+            xd = dev(x)
+            out = torch.empty((B, L, Cc), dtype=torch.float32, device="cuda")
+            _lib.check(lib.ts_op_conv1d(ctx, _lib.dptr(xd), B, L, Cc, w.ctypes.data_as(C.POINTER(C.c_float)), bias.ctypes.data_as(C.POINTER(C.c_float)),
+                                        Cc, 3, 1, 1, 0, 1, _lib.dptr(out), _lib.stream_ptr()))
+            dl, dd = np.abs(got.astype(F64) - ref), np.abs(out.cpu().numpy().astype(F64) - ref)
+            e_tile, e_own, e_direct = in_units(dl, tile), in_units(dl, own), in_units(dd, own)
+            kv = dict(tile_units=e_tile, own_units=e_own, direct_own_units=e_direct, bound=LOWERED_BOUND)
+            if regime == "onset" and L > 10:                     # row 8: all three of its taps are quiet, its tile (rows 7 .. 12 in) is not
+                kv["quiet_row_lowered_abs"] = float(dl[:, 8].max())
+                kv["quiet_row_direct_abs"] = float(dd[:, 8].max())
+                kv["quiet_row_lowered_over_direct"] = kv["quiet_row_lowered_abs"] / max(kv["quiet_row_direct_abs"], 1e-300)
+                kv["all_quiet_tile_lowered_abs"] = float(dl[:, 4:7].max())      # rows of tile 1 (rows 3 .. 8 in): the lowering at its best
+                kv["all_quiet_tile_direct_abs"] = float(dd[:, 4:7].max())
+            record(f"wino.layer_regimes.C{Cc}.L{L}.{regime}", **kv)
+            worst[regime] = max(worst.get(regime, 0.0), e_tile)
+            assert e_direct <= WHOLE_BOUND, f"direct C={Cc} L={L} {regime}: {e_direct:.3e} of its scale > {WHOLE_BOUND:.1e}"
+            if LOWERED_BOUND is not None:
+                assert e_tile <= LOWERED_BOUND, f"lowered C={Cc} L={L} {regime}: {e_tile:.3e} of the tile scale > {LOWERED_BOUND:.1e}"
+    for regime, e in worst.items():
+        assert e <= LOWERED_REGIME_RATIO * worst["unit"], f"C={Cc} {regime}: {e:.3e} is {e / worst['unit']:.1f} x the unit regime's {worst['unit']:.3e}"
 
 
 # ----------------------------------------------------------------------------------------------- 2. a stack: fused = unfused
