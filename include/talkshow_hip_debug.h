@@ -320,8 +320,49 @@ int ts_debug_code_tables_plan(int V, int D, int B, int r, int j, int last_row, c
 /* TS_PIX_TABLES (-1 / 0 / 1) for one model object; builds the tables where wanted, drops the object's captured graphs.  mode -2 changes nothing.
  * Returns 1: tables exist, 0: not, -1: error. */
 int ts_debug_pixelcnn_tables(ts_pixelcnn *pix, int mode);
-/* A whole work buffer of `stream` (which = 0 HV, 1 OV0, 2 Q1, 3 Q0, 4 G) copied to buf_dev (put = 0) or filled from it (put = 1); returns floats. */
+/* A whole work buffer of `stream` (which = 0 HV, 1 OV0, 2 Q1, 3 Q0, 4 G; the per-pass audio terms 5 AE (B, H, D), 6 AEV (B, H, D), 7 AEH (B, H, D),
+ * 8 AEH1 (B, H, 2D), 9 AV1C (B, H, 4D), 10 AV1P (B, H, 4D) of the latest pass of B clips and H rows, prefix included; 11 the token ring tok32
+ * (B, R, 2) int32 words; 12 XV, 13 P, 14 V2H, 15 XH, 16 T0) copied to buf_dev (put = 0) or filled from it (put = 1); returns floats. */
 int64_t ts_debug_pixelcnn_work(ts_pixelcnn *pix, void *stream, int which, float *buf_dev, int64_t cap_floats, int put);
+
+/* ---- stage taps of the PixelCNN chain (csrc/pixelcnn.cpp: run_row / launch_row_slot; tests/test_gpu_pix_stages.py) ----
+ * Test aid in the form of ts_debug_trunk_taps: makes the PRODUCTION pass copy out what every launch of a code row wrote; there is no second
+ * code path.  The table is thread-local and one-shot: it applies to the next chain entry this thread makes — ts_pixelcnn_generate*,
+ * ts_pixelcnn_generate_mixed*, ts_pixelcnn_stream_step*, called directly or from inside ts_body_pixel_infer* — and is dropped when that entry
+ * returns, whether it succeeded or not.  taps == null drops a table that still waits.  Always returns 0.  With no table a pass issues
+ * exactly what it issues without this entry.
+ * GRAPHS: a tapped pass runs EAGERLY on the same run_row (the launches a TS_NO_GRAPH process issues).  It captures nothing, finds, adds
+ * and evicts no graph of Work::graphs, and is no sighting for the hot-shape rule.  A one-shot call of more than CHUNK_ROWS rows without
+ * a prefix runs in the whole call's configuration where its whole-call graph is cached, and as chunks otherwise.  That is NOT always the
+ * untapped call's form: a pinned or hot shape whose graph is not cached (never captured yet, or just dropped) runs as a whole call
+ * untapped, which captures, and as chunks tapped.  The bits of every stage are the same either way; the look-ahead sums differ: chunks
+ * write P / Q1 / Q0 for rows past the end, a whole call does not.
+ * Rows are ABSOLUTE code rows (a prefix counts, a session goes on counting).  row: the one row to tap, or -1: every row; only rows in
+ * [row0, row0 + rows) are tapped.  slab_clips >= the clips of the pass (of a mixed pass: all of them); a pass of more clips fails.
+ * stage[k]: DEVICE pointer or null.  Each holds `rows` records of units(k) slabs of S = round_up(slab_clips, 16) * width(k) floats:
+ * unit u of row r at ((r - row0) * units(k) + u) * S.  A slab is the RAW copy of the launch's output block for its M rows of `stride`
+ * floats: row-major M * stride floats, or, where the work buffer is tiled (tiled_width_of: networks with D % 128 == 0 unless
+ * TS_SKINNY_TILED=0; tests decode with tiled_index of tests/test_gpu_chain_ops.py), the whole 16-row blocks of its tiled view of width tw
+ * (element (m, n) = linear m * stride + n of that view).  Nothing else of a slab is written.  width = floats per clip of a slab.
+ *   k  stage  units  width  M   stride  tw   unit u holds
+ *   0  HV     NL     4D     B   4D      2D   layer u's pre-gate h_vert of row r, both columns [j][2D] (no class row), as vert_to_horiz reads it
+ *   1  OV     NL     2D     B   2D      2D   layer u's gate output [j][D]: OV0, the XV_{u+1} slab, OVlast (u = NL - 1 >= 1: row-major)
+ *   2  P      NL     4D     B   4D      0    u >= 1: Wprev_u . XV_u[r] + b, written FOR row r + 1 (none on a whole call's last row)
+ *   3  Q1     1      4D     B   4D      0    W1 . E[r-1], written for row r + 1 (rows r >= 1 with r + 1 < last row)
+ *   4  Q0     1      4D     B   4D      0    W0 . E[r-1], written for row r + 2 (rows r >= 1 with r + 2 < last row)
+ *   5  V2H    NL     4D     2B  2D      0    vert_to_horiz of layer u, rows (clip, column) of 2D
+ *   6  G      2 NL   D      B   D       D    u = 2 l + j: the horizontal gate output of layer l, column j
+ *   7  XH     2 NL   D      B   D       D    u = 2 l + j, l >= 1: the horizontal input of layer l, column j (XH_1 folds fusion_h)
+ *   8  T0     NL     2D     B   2D      0    u = l >= 1: Wh0_l . XH_l[0], column 0's launches only
+ *   9  Y      2      HID    B   HID     HID  u = j: relu(output_conv.0)
+ *  10  LG     2      V      B   V       0    u = j: the logits
+ * Rows that run the vertical stack only (a prefix, teacher forcing without logits) leave stages 6 .. 10 alone. */
+#define TS_DEBUG_PIX_TAP_STAGES 11
+typedef struct ts_debug_pix_tap_table {
+    int32_t row, row0, rows, slab_clips;
+    float *stage[TS_DEBUG_PIX_TAP_STAGES];
+} ts_debug_pix_tap_table;
+int ts_debug_pixelcnn_taps(const ts_debug_pix_tap_table *taps);
 /* One lookup launch on row-major caller buffers: which = 0 slot V0 (tok (B,2) int32; add1, add2 (B,4D) or null; cls (B,2D); pre (B,4D); out
  * (B,2D); q1, q0 (B,4D) or null), 1 hg_0 of column 1 (tok (B,2), column 0 read; add1 (B,2D) or null; cls (B,2D); out (B,D)). */
 int ts_debug_code_table_stage(ts_pixelcnn *pix, int which, const int32_t *tok_dev, int B, const float *add1, const float *add2, const float *cls,

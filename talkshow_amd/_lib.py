@@ -88,6 +88,15 @@ class TrunkTaps(C.Structure):
     _fields_ = [("enc", (_vp * 6) * 2), ("dec", (_vp * 6) * 2)]
 
 
+PIX_TAP_STAGES = ("HV", "OV", "P", "Q1", "Q0", "V2H", "G", "XH", "T0", "Y", "LG")
+
+
+class PixTaps(C.Structure):
+    """ts_debug_pix_tap_table (include/talkshow_hip_debug.h): the rows to tap and one device pointer per stage of PIX_TAP_STAGES."""
+    _fields_ = [("row", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32), ("slab_clips", C.c_int32),
+                ("stage", _vp * len(PIX_TAP_STAGES))]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 SIGNATURES = {
     "ts_ctx_create": (_i, [_i, C.POINTER(_vp)]),
@@ -263,6 +272,7 @@ SIGNATURES = {
     "ts_debug_wino_codes": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ts_debug_vqvae_dec_tables": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "ts_debug_trunk_taps": (_i, [C.POINTER(TrunkTaps)]),
+    "ts_debug_pixelcnn_taps": (_i, [C.POINTER(PixTaps)]),
     "ts_debug_conv_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_plan": (_i, [C.POINTER(_i), _i, C.c_char_p, C.POINTER(_i)]),
     "ts_debug_skinny_run": (_i, [_vp, C.POINTER(SkinnyProblem), _i, C.c_char_p, C.POINTER(_i), _vp]),

@@ -265,6 +265,10 @@ struct SkinnyBatch {
     SkinnyParams p[SKINNY_MAX_PROBLEMS];
 };
 
+// The K split of the 16-column chain kernels (wide, fast, generic 16-column): the waves a launch whose largest problem has depth K runs on.
+// The one statement of the rule: plan_skinny, the code tables and pixelcnn.cpp's launch_slot all take it from here.  (The generic
+// 32-column kernel, which odd shapes fall to, has its own rule in plan_skinny and is outside the bit contract.)
+inline int skinny_waves16(int K) { return K >= 256 ? 8 : 4; }
 // host-side: the tiled copy of a weight matrix W [N][ldw] (K columns used) for epilogue `epi` (column order of EPI_GATE tiles:
 // 8 "tanh" channels followed by their 8 "sigmoid" partners); out has ceil(N/16) * (K/16) * 256 floats
 void skinny_tile_weights(const float *W, int N, int K, long ldw, int epi, int gateD, float *out);
@@ -300,7 +304,7 @@ int skinny_trace_read(unsigned long long *out, int max_records);
 
 // ---- code tables of the chain (code_tables.hip): slot V0 and column 1's hg_0 as lookups of slice sums ----
 // The K split of a chain GEMM: W waves (plan_skinny's rule for the 16-column kernels), wave w owning q-steps [Q w / W, Q (w + 1) / W) of 16 k
-inline int code_table_waves(int K) { return K / 8 >= 32 ? 8 : 4; }
+inline int code_table_waves(int K) { return skinny_waves16(K); }
 constexpr int CODE_TABLE_MAX_SETS = 5;   // row sets of a table: one prefix (the first code's slices) + one per slice of a second code (W / 2 <= 4)
 // one row set: out[code][0..N) = sum in index order of slices [s0, s1) of W[n][k] . emb[code][k - kcol], K = the GEMM's whole K
 struct CodeTableBuild {

@@ -410,13 +410,39 @@ void add_gather(SkinnyParams &q, const float *table, long stride, const int *gid
     q.Ktot += len;
 }
 
+// Stage tags (talkshow_hip_debug.h, ts_debug_pixelcnn_taps): what a problem's `out` is, as (stage, unit of the stage).  A gate's `pre` is
+// HV of the same unit.  Only a tapped pass reads them.
+enum PixStage { PS_HV, PS_OV, PS_P, PS_Q1, PS_Q0, PS_V2H, PS_G, PS_XH, PS_T0, PS_Y, PS_LG, PS_N };
+static_assert(PS_N == TS_DEBUG_PIX_TAP_STAGES, "the stage list of talkshow_hip_debug.h");
+inline int ptag(int stage, int unit) { return ((stage + 1) << 8) | unit; }
+
 struct Slot {   // one launch: up to SKINNY_MAX_PROBLEMS independent problems
     SkinnyParams p[SKINNY_MAX_PROBLEMS];
+    int tag[SKINNY_MAX_PROBLEMS];   // ptag of every problem, 0: not a tapped stage
     int n = 0;
-    void add(const SkinnyParams &q) { p[n++] = q; }
+    void add(const SkinnyParams &q, int t = 0) { tag[n] = t, p[n++] = q; }
     bool table = false;   // the slot is a code-table lookup (ts_pixelcnn::CodeTables): `ts` is launched, there are no problems
     CodeTableStage ts;
+    int ttag = 0;         // ptag of the lookup's `out` (its `pre` is HV of the same unit, its riders are Q1 / Q0)
 };
+
+// Stage taps: a table this thread set waits (`pending`) for the next chain entry; that entry's PixTapScope makes it `active` for its own
+// duration and drops it on the way out.  A pass without a table pays one thread-local load per launch and issues nothing.
+struct PixTapState {
+    ts_debug_pix_tap_table t;
+    bool pending = false, active = false;
+    int depth = 0;
+};
+thread_local PixTapState g_ptaps;
+struct PixTapScope {
+    PixTapScope() {
+        if (g_ptaps.depth++ == 0 && g_ptaps.pending) g_ptaps.active = true, g_ptaps.pending = false;
+    }
+    ~PixTapScope() {
+        if (--g_ptaps.depth == 0) g_ptaps.active = false;
+    }
+};
+inline bool tapping() { return g_ptaps.active; }
 
 // ---- code tables (the host arithmetic is in kernels.h: code_table_plan and the rules beside it) ----
 bool use_tables(const ts_pixelcnn *p, int B) { return code_table_pass(p->tables.built, p->tables_mode, B); }
@@ -501,7 +527,74 @@ int launch_slot(ts_pixelcnn *p, ts_pixelcnn::Work *w, const Slot &a, const Slot 
         }
         ps[i] = &q[i];
     }
-    return run_skinny_batch(p->ctx, ps, n, s);
+    // A launch splits K over ONE wave count for all its problems, taken from its largest K (skinny_waves16, the 16-column plans' rule),
+    // and a problem's bits depend on that split.  Which problems share a launch depends on how the pass is run (a deferred P_l rides with
+    // column 1 or not, the last row has no P_l, a prefix row has no horizontal slot), so a problem must get the split of its OWN K
+    // whatever rides along — the split the code tables were built with, too.  Networks with D < 128 (every K < 256 but head2's) and
+    // D >= 256 (every K >= 256) never mix; in between (K = D < 256 <= 2D) a mixed launch goes out as two.  Zero-row segments multiply
+    // nothing: a problem made of them alone has the same bits under any split and stays where it is.  This holds for the 16-column plans
+    // (wide, fast, generic 16-column); a launch that falls to the generic 32-column kernel (shapes of odd models) splits by another rule
+    // (plan_skinny) and is outside the bit contract, as it always was.
+    auto waves_of = [](const SkinnyParams &x) {
+        int k = 0;
+        for (int i = 0; i < x.nseg; ++i)
+            if (x.seg[i].base || x.seg[i].gidx) k += x.seg[i].len;
+        return k == 0 ? 0 : skinny_waves16(k);
+    };
+    int n4 = 0, n8 = 0;
+    for (int i = 0; i < n; ++i) n4 += waves_of(q[i]) == 4, n8 += waves_of(q[i]) == 8;
+    if (n4 == 0 || n8 == 0) return run_skinny_batch(p->ctx, ps, n, s);
+    const SkinnyParams *part[SKINNY_MAX_PROBLEMS];
+    for (int pass = 0; pass < 2; ++pass) {
+        int m = 0;
+        for (int i = 0; i < n; ++i)
+            if ((waves_of(q[i]) == 4) == (pass == 1)) part[m++] = &q[i];
+        TS_TRY(run_skinny_batch(p->ctx, part, m, s));
+    }
+    return 0;
+}
+
+// one raw slab of a tapped stage -> its place in the caller's buffer (layout: talkshow_hip_debug.h)
+int tap_copy(ts_pixelcnn *p, ts_pixelcnn::Work *w, int r, int tag, const float *src, long M, long stride, hipStream_t s) {
+    const ts_debug_pix_tap_table &t = g_ptaps.t;
+    const int stage = (tag >> 8) - 1, unit = tag & 255;
+    if (tag <= 0 || stage >= PS_N || !src || !t.stage[stage]) return 0;
+    const int D = p->D, NL = p->NL;
+    const int units[PS_N] = {NL, NL, NL, 1, 1, NL, 2 * NL, 2 * NL, NL, 2, 2};
+    const int width[PS_N] = {4 * D, 2 * D, 4 * D, 4 * D, 4 * D, 4 * D, D, D, 2 * D, p->HID, p->V};
+    const size_t slab = (size_t)round_up(t.slab_clips, 16) * width[stage];
+    const int tw = tiled_width_of(p, w, src);
+    const size_t n = tw ? (size_t)round_up((int)((M * stride + tw - 1) / tw), 16) * tw : (size_t)(M * stride);
+    if (unit >= units[stage] || n > slab) return fail("pixelcnn taps: a stage does not fit the slab the table names");
+    float *dst = t.stage[stage] + ((size_t)(r - t.row0) * units[stage] + unit) * slab;
+    MiscScope ms(p->ctx, s);
+    TS_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+int tap_slot(ts_pixelcnn *p, ts_pixelcnn::Work *w, int r, const Slot &a, hipStream_t s) {
+    if (a.table) {
+        const int unit = a.ttag & 255;
+        TS_TRY(tap_copy(p, w, r, a.ttag, a.ts.out, a.ts.M, a.ts.out_stride, s));
+        TS_TRY(tap_copy(p, w, r, ptag(PS_HV, unit), a.ts.pre, a.ts.M, a.ts.pre_stride, s));
+        TS_TRY(tap_copy(p, w, r, ptag(PS_Q1, 0), a.ts.rider[0], a.ts.M, a.ts.rider_stride, s));
+        TS_TRY(tap_copy(p, w, r, ptag(PS_Q0, 0), a.ts.rider[1], a.ts.M, a.ts.rider_stride, s));
+    }
+    for (int i = 0; i < a.n; ++i) {
+        TS_TRY(tap_copy(p, w, r, a.tag[i], a.p[i].out, a.p[i].M, a.p[i].out_stride, s));
+        if (a.p[i].epi == EPI_GATE) TS_TRY(tap_copy(p, w, r, ptag(PS_HV, a.tag[i] & 255), a.p[i].pre, a.p[i].M, a.p[i].pre_stride, s));
+    }
+    return 0;
+}
+// launch_slot of code row r; a tapped pass copies out what the launch wrote, on the same stream right behind it
+int launch_row_slot(ts_pixelcnn *p, const RunCfg &c, int r, const Slot &a, const Slot *b, hipStream_t s) {
+    TS_TRY(launch_slot(p, c.w, a, b, s));
+    if (!tapping()) return 0;
+    const ts_debug_pix_tap_table &t = g_ptaps.t;
+    if ((t.row >= 0 && t.row != r) || r < t.row0 || r >= t.row0 + t.rows) return 0;
+    if (c.B > t.slab_clips) return fail("pixelcnn taps: the pass has more clips than the table's slab_clips");
+    TS_TRY(tap_slot(p, c.w, r, a, s));
+    if (b) TS_TRY(tap_slot(p, c.w, r, *b, s));
+    return 0;
 }
 
 // vertical stack + v->h projections of row r as NL+2 launch slots
@@ -542,6 +635,7 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
         v.out_stride = 2 * D;
         return v;
     };
+    auto add_v2h = [&](Slot &s, int l) { s.add(make_v2h(l), ptag(PS_V2H, l)); };
 
     out.clear();
     {   // V0: layer 0 (mask 'A', kernel rows 0..2 <-> code rows r-3..r-1): newest row here, older rows via Q1 / Q0.
@@ -581,8 +675,9 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
                 if (code_table_rider(r, t, c.last_row)) ts.rider[1 - t] = Q(t == 1 ? w->Q1 : w->Q0, r + (2 - t));
             ts.rider_stride = 4 * D;
             s.table = true;
+            s.ttag = ptag(PS_OV, 0);
         } else {
-            s.add(g);
+            s.add(g, ptag(PS_OV, 0));
         }
         for (int t = 1; t >= 0 && r >= 1 && !s.table; --t) {   // row r-1's codes as seen from row r+1 (kernel row 1) and r+2 (kernel row 0)
             const int target = r + (2 - t);
@@ -593,13 +688,13 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
             q.ldw = 2 * D;
             q.out = Q(t == 1 ? w->Q1 : w->Q0, target);
             q.out_stride = 4 * D;
-            s.add(q);
+            s.add(q, ptag(t == 1 ? PS_Q1 : PS_Q0, 0));
         }
         out.push_back(s);
     }
     if (NL == 1) {
         Slot s;
-        s.add(make_v2h(0));
+        add_v2h(s, 0);
         out.push_back(s);
         return;
     }
@@ -623,7 +718,7 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
             g.add2_stride = astride;
         }
         gate_common(g, l);
-        s.add(g);
+        s.add(g, ptag(PS_OV, l));
         if (r + 1 < c.last_row) {
             SkinnyParams q = base_params(B, 4 * D, EPI_LINEAR);
             add_dense(q, xin, 2 * D, 0, 2 * D);
@@ -636,15 +731,15 @@ void build_vertical(ts_pixelcnn *p, const RunCfg &c, int r, std::vector<Slot> &o
             }
             q.out = P(l, (r + 1) & 1);
             q.out_stride = 4 * D;
-            if (deferred) deferred->push_back(q);
-            else s.add(q);
+            if (deferred) deferred->push_back(q);   // (run_row tags them: entry i is P of layer i + 1)
+            else s.add(q, ptag(PS_P, l));
         }
-        s.add(make_v2h(l - 1));
+        add_v2h(s, l - 1);
         out.push_back(s);
     }
     {
         Slot s;
-        s.add(make_v2h(NL - 1));
+        add_v2h(s, NL - 1);
         out.push_back(s);
     }
 }
@@ -701,8 +796,9 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
             ts.cls = q.clsrow, ts.cls_ld = q.cls_ld;
             ts.out = q.out, ts.out_stride = q.out_stride, ts.out_tw = tiled_log2(tiled_width_of(p, w, q.out));
             s.table = true;
+            s.ttag = ptag(PS_G, j);
         } else {
-            s.add(q);
+            s.add(q, ptag(PS_G, j));
         }
         out.push_back(s);
     }
@@ -722,7 +818,7 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
         }
         a.out = XH(l, j);
         a.out_stride = D;
-        s.add(a);
+        s.add(a, ptag(PS_XH, 2 * l + j));
 
         SkinnyParams g = base_params(B, 2 * D, EPI_GATE);
         add_dense(g, G(l - 1), D, 0, D);
@@ -745,8 +841,8 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
         g.gateD = D;
         g.out = G(l);
         g.out_stride = D;
-        s.add(g);
-        if (j == 0 && l >= 2) s.add(make_t0(l - 1));
+        s.add(g, ptag(PS_G, 2 * l + j));
+        if (j == 0 && l >= 2) s.add(make_t0(l - 1), ptag(PS_T0, l - 1));
         out.push_back(s);
     }
     {   // head1' = relu(output_conv.0(XH_NL)) with XH_NL = horiz_resid_{NL-1}(G_{NL-1}) + XH_{NL-1} composed in
@@ -760,8 +856,8 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
         h1.relu = 1;
         h1.out = w->Y.f();
         h1.out_stride = p->HID;
-        s.add(h1);
-        if (j == 0 && NL >= 2) s.add(make_t0(NL - 1));
+        s.add(h1, ptag(PS_Y, j));
+        if (j == 0 && NL >= 2) s.add(make_t0(NL - 1), ptag(PS_T0, NL - 1));
         out.push_back(s);
     }
     {
@@ -773,7 +869,7 @@ void build_horizontal(ts_pixelcnn *p, const RunCfg &c, int r, int j, std::vector
         h2.bias = p->b2.f();
         h2.out = w->LG.f();
         h2.out_stride = p->V;
-        s.add(h2);
+        s.add(h2, ptag(PS_LG, j));
         out.push_back(s);
     }
 }
@@ -847,27 +943,30 @@ int run_row(ts_pixelcnn *p, const RunCfg &c, int r, bool need_h, hipStream_t s) 
     const bool defer = need_h && (p->defer_p < 0 ? c.B <= 128 : p->defer_p > 0);
     build_vertical(p, c, r, V, defer ? &Pd : nullptr);
     if (!need_h) {
-        for (auto &sl : V) TS_TRY(launch_slot(p, c.w, sl, nullptr, s));
+        for (auto &sl : V) TS_TRY(launch_row_slot(p, c, r, sl, nullptr, s));
         return 0;
     }
     build_horizontal(p, c, r, 0, H);
     size_t vi = 0;
     // hg_0 needs V2H_0 (V1); S_k needs V2H_k (V_{k+1}): V0, V1, H0 + V2, H1 + V3, ...
-    for (; vi < 2 && vi < V.size(); ++vi) TS_TRY(launch_slot(p, c.w, V[vi], nullptr, s));
+    for (; vi < 2 && vi < V.size(); ++vi) TS_TRY(launch_row_slot(p, c, r, V[vi], nullptr, s));
     for (size_t k = 0; k < H.size(); ++k) {
         const Slot *ride = nullptr;
         if (vi < V.size() && V[vi].n + H[k].n <= SKINNY_MAX_PROBLEMS) ride = &V[vi++];
-        TS_TRY(launch_slot(p, c.w, H[k], ride, s));
+        TS_TRY(launch_row_slot(p, c, r, H[k], ride, s));
     }
-    for (; vi < V.size(); ++vi) TS_TRY(launch_slot(p, c.w, V[vi], nullptr, s));   // only if the stack outlasts the chain
+    for (; vi < V.size(); ++vi) TS_TRY(launch_row_slot(p, c, r, V[vi], nullptr, s));   // only if the stack outlasts the chain
     TS_TRY(launch_sampler(p, c, r, 0, s));
     build_horizontal(p, c, r, 1, H);
     size_t pi = 0;
     for (size_t k = 0; k < H.size(); ++k) {
         Slot ride;
         // the last horizontal slots take what is left, so that every P_l has run before the row ends
-        while (!H[k].table && pi < Pd.size() && H[k].n + ride.n < SKINNY_MAX_PROBLEMS && (ride.n == 0 || Pd.size() - pi > H.size() - 1 - k)) ride.add(Pd[pi++]);
-        TS_TRY(launch_slot(p, c.w, H[k], ride.n ? &ride : nullptr, s));
+        while (!H[k].table && pi < Pd.size() && H[k].n + ride.n < SKINNY_MAX_PROBLEMS && (ride.n == 0 || Pd.size() - pi > H.size() - 1 - k)) {
+            ride.add(Pd[pi], ptag(PS_P, (int)pi + 1));
+            ++pi;
+        }
+        TS_TRY(launch_row_slot(p, c, r, H[k], ride.n ? &ride : nullptr, s));
     }
     if (pi < Pd.size()) return fail("pixelcnn: deferred projections left over");
     return launch_sampler(p, c, r, 1, s);
@@ -1159,6 +1258,13 @@ int ts_pixelcnn_graph_stats(ts_pixelcnn *p, void *stream, int B, int H, int mode
     return 0;
 }
 
+// Stage taps (talkshow_hip_debug.h): the table waits for the next chain entry of this thread
+int ts_debug_pixelcnn_taps(const ts_debug_pix_tap_table *taps) {
+    g_ptaps.pending = taps != nullptr;
+    if (taps) g_ptaps.t = *taps;
+    return 0;
+}
+
 // ---- code tables: test entries (talkshow_hip_debug.h) ----
 // TS_PIX_TABLES for one model object: mode -1 / 0 / 1 as the variable (-2: change nothing, only answer); builds the tables if they are
 // wanted and fit.  Every captured graph of the object's per-stream Works is dropped (their launches belong to the old setting); streaming
@@ -1177,13 +1283,15 @@ int ts_debug_pixelcnn_tables(ts_pixelcnn *p, int mode) {
     return p->tables.built ? 1 : 0;
 }
 
-// A work buffer of `stream`'s Work, whole: which = 0 HV, 1 OV0, 2 Q1, 3 Q0, 4 G.  put = 0: copied to buf_dev, put = 1: filled from buf_dev
+// A work buffer of `stream`'s Work, whole: which = 0 HV, 1 OV0, 2 Q1, 3 Q0, 4 G, 5 AE, 6 AEV, 7 AEH, 8 AEH1, 9 AV1C, 10 AV1P, 11 tok32 (int32 words),
+// 12 XV, 13 P, 14 V2H, 15 XH, 16 T0.  put = 0: copied to buf_dev, put = 1: filled from buf_dev
 // (tests poison the buffers ahead of a run).  Copies min(buffer, cap_floats) floats behind the stream's work and waits; returns the count, -1 on error
 int64_t ts_debug_pixelcnn_work(ts_pixelcnn *p, void *stream, int which, float *buf_dev, int64_t cap_floats, int put) {
-    if (!p || !buf_dev || cap_floats < 0 || which < 0 || which > 4) return fail("ts_debug_pixelcnn_work: bad argument") ? -1 : -1;
+    if (!p || !buf_dev || cap_floats < 0 || which < 0 || which > 16) return fail("ts_debug_pixelcnn_work: bad argument") ? -1 : -1;
     ts_pixelcnn::Work *w = p->works.find((hipStream_t)stream);
     if (!w) return fail("ts_debug_pixelcnn_work: nothing was run on this stream") ? -1 : -1;
-    DevBuf *bufs[5] = {&w->HV, &w->OV0, &w->Q1, &w->Q0, &w->G};
+    DevBuf *bufs[17] = {&w->HV,   &w->OV0,  &w->Q1,   &w->Q0,    &w->G, &w->AE,  &w->AEV, &w->AEH, &w->AEH1,
+                        &w->AV1C, &w->AV1P, &w->tok32, &w->XV,   &w->P, &w->V2H, &w->XH,  &w->T0};
     const size_t n = std::min((size_t)cap_floats, bufs[which]->bytes / sizeof(float));
     hipStream_t s = (hipStream_t)stream;
     if (hipMemcpyAsync(put ? bufs[which]->p : (void *)buf_dev, put ? (const void *)buf_dev : bufs[which]->p, n * sizeof(float), hipMemcpyDeviceToDevice, s) !=
@@ -1349,6 +1457,7 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
         }
         return 0;
     };
+    if (tapping() && !capture_only) graph = false;   // a tapped pass runs eagerly: no graph ever holds a tap copy, the cache is not touched
     if (!graph) {   // the samplers address the caller's arrays directly: rows out_row0 .. of out_H per clip
         if (out_H != c.H && c.logits) return fail("pixelcnn: eager rows with logits write the caller's arrays whole");
         c.codes = codes;
@@ -1654,6 +1763,7 @@ int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *p, const int64_t *label, cons
 // The body of every ts_pixelcnn_generate_mixed* entry: each fills `o` with its own arguments, so an absent keyword is null here and costs no
 // launch, no buffer and no bit of a graph key.  (given_rows_dev is not passed on: the table travels as kernel arguments from the host copy.)
 int ts::pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPass &a, const MixedOpts &o, hipStream_t s) {
+    PixTapScope taps;
     const int B = a.B, H_max = a.rows, mode = a.mode;
     if (!p || (!a.ids && !o.style) || !aud || !a.lens_host || !a.lens_dev || !a.codes) return fail("ts_pixelcnn_generate_mixed: null argument");
     if (B < 1 || H_max < 1) return fail("ts_pixelcnn_generate_mixed: bad shape");
@@ -1718,6 +1828,7 @@ int ts_pixelcnn_generate_lp(ts_pixelcnn *p, const int64_t *label, const float *a
                             const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *logits,
                             const int64_t *pre_codes, const float *pre_aud, int H0, const ts_sampling *ctl_host, int n_ctl, float *logprob,
                             void *stream) {
+    PixTapScope taps;
     if (!p || !label || !aud || !codes) return fail("ts_pixelcnn_generate: null argument");
     if (B < 1 || H < 1 || H0 < 0) return fail("ts_pixelcnn_generate: bad shape");
     if (mode < 0 || mode > TS_TEACHER_FORCED) return fail("ts_pixelcnn_generate: bad mode");
@@ -1769,7 +1880,7 @@ int ts_pixelcnn_generate_lp(ts_pixelcnn *p, const int64_t *label, const float *a
     // A shape without a whole-call graph runs as chunk graphs (two or three small captures that serve every clip length) until it is
     // hot (Work::hot: pinned by ts_pixelcnn_prepare, or its third sighting among the last 16 one-shot calls of this stream); then it gets
     // its own whole-call graph (one replay per call: the serving loops, bench.py).  The cache is bounded either way.
-    if (graph && H0 == 0 && H > CHUNK_ROWS && !w->graphs.count(key) && !w->hot(key))
+    if (graph && H0 == 0 && H > CHUNK_ROWS && !w->graphs.count(key) && (tapping() || !w->hot(key)))   // (a tapped pass is no sighting)
         return run_chunked(p, w, B, H, mode, uniforms, seed, clip0, codes, c.ctl, logprob, s);
     return run_rows(p, c, 0, Htot, graph, key, uniforms, codes, logprob, s);
 }
@@ -1834,6 +1945,7 @@ namespace {
 // graph key.  Everything is checked before anything is launched and before st->rows moves.
 int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
                 int64_t *codes, const MixedOpts &o, hipStream_t s) {
+    PixTapScope taps;
     if (!st || !aud || !codes) return fail("ts_pixelcnn_stream_step: null argument");
     if (Hc < 1) return fail("ts_pixelcnn_stream_step: empty chunk");
     if (Hc > st->max_rows) return fail("ts_pixelcnn_stream_step: chunk longer than max_chunk_rows given to ts_pixelcnn_stream_open");

@@ -856,7 +856,7 @@ SkinnyPlan plan_skinny(const SkinnyParams *const *ps, int n, const Knobs &k) {
         return pl;
     }
     pl.kernel = SkinnyKernel::Generic16;
-    pl.W = Q >= 32 ? 8 : 4;
+    pl.W = skinny_waves16(Q * 8);
     if (k.skinny_v != 0 && !plan_wide(b, n, k, pl)) plan_fast(b, n, k, pl);
     return pl;
 }
