@@ -761,6 +761,76 @@ int ts_body_pixel_infer_mixed_poses_repeat(ts_convnet *audioenc, ts_pixelcnn *pi
  * entry applies before its first launch. */
 int ts_repeat_check(const ts_repeat *rep_host, int n, int V);
 
+/* ---- guidance: a clip's logits pushed away from, or toward, those of a second conditioning ----------------------------------------------
+ * No counterpart in the reference.  Every control above reshapes the distribution the model computes for ONE conditioning; guidance
+ * compares two.  A pass has B clip slots.  A slot b may name one other slot g = guide[b] as its SHADOW, with a float scale[b]; guide[b] =
+ * -1: none.  The shadow is an ordinary slot of the pass, of the same length as b, with its own audio rows and its own label or style
+ * rows: the second conditioning q.  The shadow draws nothing.
+ * THE RULE, for the sampler launch of every position (r, j): the workgroup of b reads both logits rows and forms, element by element,
+ *     d = l_b - l_g;   t = scale * d;   l' = l_b + t
+ * — THREE IEEE fp32 operations, each rounded, never contracted into a fused multiply-add (the convention of "speaker style").  The rule
+ * runs AHEAD of step 0 (code bias), step 0b (repetition penalty) and steps 1-5: every later step, the log-probability included, runs on
+ * l' exactly as it runs on l without the feature.  The logits OUTPUT (the row copy) stays the network's l, for both slots.
+ *  Both slots, one history.  The workgroup of b writes what it chose or was given to BOTH slots: the token and the code of b and of g,
+ *     the kept bytes and the log-probability to both where those outputs exist.  The workgroup of g returns without reading or writing
+ *     anything.  l_g at the next position is therefore what q says about the codes b really produced.  A shadow's rows of every output
+ *     are its primary's: codes, log-probabilities, and in the body wrapper its poses.
+ *  scale > 0 pushes the draw away from q (classifier-free-guidance style: "more this audio than silence", "more speaker A, less speaker
+ *     B"); scale = -0.5 draws from the geometric mean of the two distributions — the distribution-space blend "speaker style" is not;
+ *     scale = -1 is q itself on b's history.
+ *  Bit identity.  scale = 0 returns the codes of the pass without the table (t = +-0; a logit of -0 may become +0, so log-probabilities
+ *     may differ in the sign of a zero).  A shadow with the primary's own conditioning gives d = 0 at every position: codes and
+ *     log-probability bits equal the plain pass's for any finite scale.
+ *  Random numbers.  A primary's uniform or Philox number is that of its own clip index and absolute position.  Shadows consume none and
+ *     shift no other clip's index (a mixed pass names every slot's index in its clip table).
+ *  Given, kept and forced positions are decided from the PRIMARY's row table and mask; a forced code is written to both slots.  The
+ *     primary's repetition history is the only one read or written; a shadow's records, tables and given rows are never read.
+ *  Independence.  A clip's result depends neither on which other clips of the pass are guided nor on where its shadow sits.
+ *  Finite by design.  |scale| <= 1e4 keeps scale * d finite for any logits a trained network produces (|d| < 3e34).  Beyond that a
+ *     non-finite l' — a NaN from inf - inf included — is the caller's affair: the samplers do not look for one.
+ *  Scope.  A sampling control like the bias: TS_SAMPLE_UNIFORMS and TS_SAMPLE_PHILOX; greedy is top_k = 1.  A pass without a sampling
+ *     table runs on neutral records.
+ * ts_guide_check refuses, naming the slot, before anything is launched: an index outside [-1, B); a slot that names itself; a shadow named
+ * twice; a shadow that is itself guided; unequal lengths in FRAMES (lens_host as the pass takes it, compared as it is — stricter than equal code rows; NULL: not checked); a NaN or an infinity; |scale| > 1e4.  In a pass it
+ * comes LAST among the sampler checks.  talkshow_amd/sampling.py restates rule and check (guided, sample_guide, guide_roles).
+ * Staging and graphs.  Roles (-1 plain, g >= 0 a primary, -2 a shadow) and scales are copied into the stream's work buffers in stream
+ * order ahead of the pass (kernel arguments).  The samplers are kernels of their own (sample_ctl_guide_kernel /
+ * sample_ctl_guide_given_kernel: the repetition kernels with the rule compiled in; a pass without records runs them on windows of 0, one
+ * without tables on an index of -1) on graph keys of their own: bit 8 (value 256) of the sixth key field (bit 7 is a session's slot
+ * restart).  Neither roles nor scales are in the key: a repeated guided pass captures nothing.  Passes without the table launch the
+ * kernels and find the graphs they always did.  Chunking is unchanged: the chunks of a mixed pass are prefixes of the non-increasing length
+ * table, so two slots of equal length are active together whatever lies between them.
+ * The entries: ts_pixelcnn_generate_guided, ts_body_pixel_infer_guided and ts_body_pixel_infer_guided_poses are ts_pixelcnn_generate_mixed_repeat,
+ * ts_body_pixel_infer_mixed_repeat and ts_body_pixel_infer_mixed_poses_repeat plus `const int32_t *guide_host, const float *guide_scale_host` ahead of the stream,
+ * (B,) each in slot order.  guide_host == NULL: the _repeat entry, launch for launch.
+ * Out of scope: the streaming sessions; ts_pixelcnn_v_*; the single-stack form; the scoring entries (a pass whose rows are all given, with
+ * a log-probability output, scores under guidance already); more than one shadow per clip. */
+int ts_pixelcnn_generate_guided(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                     const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                     const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                     float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                     const int32_t *given_rows_dev, const uint8_t *keep_dev, const float *style_dev, int style_rows,
+                                     const float *bias_dev, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
+                                     const int32_t *guide_host, const float *guide_scale_host, void *stream);
+int ts_body_pixel_infer_guided(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                    const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                    const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                    float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                    const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep_dev,
+                                    const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                    const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const int32_t *guide_host,
+                                    const float *guide_scale_host, void *stream);
+int ts_body_pixel_infer_guided_poses(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                          const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                          const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                          float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                          const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                          const uint8_t *keep_dev, const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                          const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const int32_t *guide_host,
+                                          const float *guide_scale_host, void *stream);
+/* Host only: the check above on a table of B slots; lens_host (B,) the slots' lengths in frames or NULL; 0, or an error that names the slot. */
+int ts_guide_check(const int32_t *guide_host, const float *guide_scale_host, const int32_t *lens_host, int B);
+
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.
  * Either output may be NULL: recon_dev == NULL is the encode-only form (VQVAE.encode of both parts, the latents
@@ -844,6 +914,16 @@ int ts_op_sample_repeat(ts_ctx *ctx, const float *logits_dev, int B, int V, int 
                         const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, uint8_t *kept_dev,
                         float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column,
                         const ts_repeat *rep_host, int n_rep, const int32_t *history_dev, int32_t *ring_out_dev, void *stream);
+/* One launch of the samplers under "guidance": ts_op_sample_repeat's arguments (rep_host may be NULL here: no records; history_dev and
+ * ring_out_dev are then optional), then guide_host (B) int32 — the shadow's ROW of every row or -1 — and guide_scale_host (B).  A primary
+ * reads its shadow's logits row and writes idx_dev, kept_dev and logprob_dev of both rows; logits_copy_dev receives both rows as they
+ * came; a shadow's ring stays as the entry filled it.  sample_ctl_guide_kernel, or sample_ctl_guide_given_kernel with given rows. */
+int ts_op_sample_guide(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                       int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
+                       const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, uint8_t *kept_dev,
+                       float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column,
+                       const ts_repeat *rep_host, int n_rep, const int32_t *history_dev, int32_t *ring_out_dev, const int32_t *guide_host,
+                       const float *guide_scale_host, void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).

@@ -97,7 +97,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
+                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -120,17 +120,20 @@ class TrainWrapper(TrainWrapperBaseClass):
         {"body", "hand"} dict (`generate_clips`, `ts_body_pixel_infer_mixed_bias`).  None: nothing changes.
         repeat: a per-clip repetition penalty over a window of earlier codes — one (window, presence, frequency) record or dict for all
         clips, or a list with one per clip (`generate_clips`, `ts_body_pixel_infer_mixed_repeat`).  None: nothing changes.
+        guide: per-clip guidance against a second conditioning — one dict for all clips or a list with, per clip, None or {"scale",
+        "mfcc" (T,64), "id", "style"} (`generate_clips`, `ts_body_pixel_infer_guided`).  None: nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
         if (sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None or style is not None
-                or code_bias is not None or repeat is not None):
+                or code_bias is not None or repeat is not None or guide is not None):
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
                                        _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
-                                       given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
+                                       given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat,
+                                       guide=guide)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -229,7 +232,7 @@ class TrainWrapper(TrainWrapperBaseClass):
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
                        _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None,
-                       style=None, code_bias=None, repeat=None):
+                       style=None, code_bias=None, repeat=None, guide=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -299,7 +302,21 @@ class TrainWrapper(TrainWrapperBaseClass):
         decode WITH THE SAME RECORD returns that decode.  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only; a clip's random numbers do not depend
         on its record.  Orthogonal to every other keyword.  A window outside [0, 64], a NaN, an infinity or a value beyond 1e30 raises
         ValueError naming the clip before anything is launched (`ts_body_pixel_infer_mixed_repeat` / `_poses_repeat`).  None: nothing
-        changes."""
+        changes.
+        guide: MORE OF THIS, LESS OF THAT (talkshow_hip.h, "guidance"; `_lib.guide_entries`) — one dict for all clips, or a list in submission
+        order with, per clip, None or a dict {"scale": s, "mfcc": (T_b, 64) array or None, "id": int or None, "style": row / track or
+        None}; an absent audio, id or style is the clip's own.  The clip is decoded under its own conditioning p; a SHADOW slot placed
+        directly behind it runs the same code history under the second conditioning q (other audio, another speaker), and at every
+        position the clip's logits become l' = l + scale * (l - l_q) — difference, product and sum rounded to fp32 separately
+        (`sampling.guided`) — AHEAD of code bias, repetition penalty, temperature, top-k and top-p; log-probabilities are those of the
+        guided distribution.  scale > 0: more driven by this audio than by q's (silence, say), "more speaker A, less speaker B";
+        scale = -0.5: the geometric mean of the two distributions — the MIXTURE OF DISTRIBUTIONS `style=` is not; scale = 0: the clip's
+        bits do not move; a shadow with the clip's own conditioning changes nothing for any scale.  The shadow draws nothing, consumes no
+        random number and shifts no clip's index; given, kept and forced positions are the clip's own and are written to both slots;
+        every other keyword's entry follows the clip, shadows bring none.  A guided clip costs a second slot of the pass; the caller
+        gets B results.  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only.  A wrong key, shape, length or scale (NaN, infinite, beyond 1e4)
+        raises ValueError naming the clip before anything is launched (`ts_body_pixel_infer_guided` / `ts_body_pixel_infer_guided_poses`).  None:
+        nothing changes."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
         dev = self.generator._dev()
@@ -343,6 +360,10 @@ class TrainWrapper(TrainWrapperBaseClass):
         sblock = _lib.style_block(style, [t // 4 for t in lens], self.num_classes, order, who="generate_clips", ids=ids)   # slot order, like the records
         btab, bidx = _lib.code_bias_block(code_bias, B, self.generator.input_dim, order, who="generate_clips", mode=mode)   # slot order, too
         rtab, n_rep = _lib.repeat_table(repeat, B, self.generator.input_dim, order, who="generate_clips", mode=mode)                # and the records
+        gent = _lib.guide_entries(guide, B, who="generate_clips", audio_key="mfcc", mode=mode, n_classes=self.num_classes, rows=[t // 4 for t in lens])
+        for b, e in enumerate(gent or ()):
+            if e is not None and e["audio"] is not None and tuple(np.shape(e["audio"])) != (lens[b], 64):
+                raise ValueError(f"generate_clips: guide of clip {b}: mfcc must have the clip's own shape ({lens[b]}, 64), got {tuple(np.shape(e['audio']))}")
         T_max = lens[order[0]]
         H_max = T_max // 4
         sorted_lens = [lens[i] for i in order]
@@ -371,14 +392,42 @@ class TrainWrapper(TrainWrapperBaseClass):
                 u[k, :lens[i] // 4] = ui
         if seed is None:
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
-        codes = torch.empty((B, H_max, 2), dtype=torch.int64, device=dev)
-        poses = torch.empty((B, 4 * H_max, self.each_dim[1] + self.each_dim[2]), dtype=torch.float32, device=dev)
+        Bp, gpair, prim = B, (None, None), None      # the slots of the pass: B, or B plus one shadow behind every guided clip
+        if gent is not None:
+            # every validated block is in slot order: slot s of the guided pass copies original slot src[s]; a shadow then takes its own
+            # audio, id and style and brings no given rows, no poses and no table
+            src, shadow, gtab, gscale = _lib.guide_layout(order, gent)
+            slot_ent = [gent[i] for i in order]
+            Bp, sidx, shadows = len(src), np.asarray(src, np.int64), np.asarray(shadow, bool)
+            sdev = torch.as_tensor(sidx, device=dev)
+            mf, ids_sorted, clip_index = mf.index_select(0, sdev).contiguous(), ids_sorted.index_select(0, sdev).contiguous(), clip_index.index_select(0, sdev).contiguous()
+            u = None if u is None else u.index_select(0, sdev).contiguous()
+            for s in np.flatnonzero(shadows):
+                e, t = slot_ent[src[s]], sorted_lens[src[s]]
+                if e["audio"] is not None:
+                    mf[s, :t] = torch.as_tensor(e["audio"], dtype=torch.float32, device=dev)
+                if e["id"] is not None:
+                    ids_sorted[s] = e["id"]
+            need_ids = sblock is None and any(e is not None and e["style"] is not None for e in gent)
+            sblock = _lib.guide_style_block(sblock, src, shadow, slot_ent, [t // 4 for t in sorted_lens], self.num_classes,
+                                            ids.index_select(0, order_dev).cpu().numpy() if need_ids else None, who="generate_clips", names=order)
+            lens_host = np.ascontiguousarray(lens_host[sidx])
+            lens_dev = torch.from_numpy(lens_host).to(dev)
+            (ctl, n_ctl), (gblock, gtable), (pblock, ptable), kblock, (btab, bidx), (rtab, n_rep) = _lib.guide_expand(
+                src, shadow, (ctl, n_ctl), (gblock, gtable), (pblock, ptable), kblock, (btab, bidx), (rtab, n_rep))
+            gpair = (gtab, gscale)
+            prim = torch.as_tensor(np.flatnonzero(~shadows).astype(np.int64), device=dev)
+        codes = torch.empty((Bp, H_max, 2), dtype=torch.int64, device=dev)
+        poses = torch.empty((Bp, 4 * H_max, self.each_dim[1] + self.each_dim[2]), dtype=torch.float32, device=dev)
         args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
-                _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), B, T_max,
+                _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), Bp, T_max,
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
-        lp = torch.empty((B, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
+        lp = torch.empty((Bp, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
         self._mixed_call(args, dev, ctl=(ctl, n_ctl), lp=lp, given=(gblock, gtable), poses=(pblock, ptable), keep=kblock, style=sblock,
-                         bias=(btab, bidx), repeat=(rtab, n_rep))      # the most general entry of the family; absent keywords travel as NULL
+                         bias=(btab, bidx), repeat=(rtab, n_rep), guide=gpair)      # the most general entry of the family; absent keywords travel as NULL
+        if prim is not None:      # the shadows' rows are their primaries': the caller sees B results
+            codes, poses = codes.index_select(0, prim), poses.index_select(0, prim)
+            lp = None if lp is None else lp.index_select(0, prim)
         inv_dev = torch.as_tensor(inverse, dtype=torch.int64, device=dev)
         codes, poses = codes.index_select(0, inv_dev), poses.index_select(0, inv_dev)     # back to submission order
         if lp is not None:
@@ -391,7 +440,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
     def _mixed_call(self, args, dev, ctl=(None, 0), lp=None, given=(None, None), poses=(None, None), keep=None, style=None, bias=(None, None),
-                    repeat=(None, 0)):
+                    repeat=(None, 0), guide=(None, None)):
         """Uploads the host blocks of a mixed pass, each once, and makes its one call (`_lib.body_mixed_call`): args the fixed arguments,
         the rest validated blocks (pairs: block and table) in slot order or None.  Given poses beside given codes are staged into one block."""
         from talkshow_amd.modules import upload
@@ -410,7 +459,7 @@ class TrainWrapper(TrainWrapperBaseClass):
             args, ctl=ctl[0], n_ctl=ctl[1], logprob=_lib.dptr(lp), given=_lib.dptr(gdev), given_rows=None if gdev is None else gtable.ctypes.data_as(i32p),
             poses=pose_piece, keep=_lib.dptr(kdev), style=_lib.dptr(sdev), style_rows=0 if style is None else int(style.shape[1]),
             bias=_lib.dptr(bdev), n_bias=0 if btab is None else int(btab.shape[0]), bias_index=None if btab is None else bidx.ctypes.data_as(i32p),
-            rep=repeat[0], n_rep=repeat[1])
+            rep=repeat[0], n_rep=repeat[1], guide=None if guide[0] is None else guide[0].ctypes.data_as(i32p), guide_scale=_lib.fptr(guide[1]))
 
     def _stage_given(self, gblock, gtable, pblock, ptable, dev):
         """One given block for a pass that holds code clips AND pose clips: gblock / gtable from `_lib.given_block`, pblock / ptable from
@@ -525,7 +574,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return S.allow_bias(codes.reshape(-1, 2), self.generator.input_dim)
 
     def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
-                         given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
+                         given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
@@ -536,7 +585,9 @@ class TrainWrapper(TrainWrapperBaseClass):
         given_keep: `_lib.given_keep_block(...)` in ROW order — the (B, H_max, 2) uint8 mask of kept positions — or None.
         style: `_lib.style_block(...)` in ROW order — the (B, 1 or H_max, NC) float32 speaker weights that take the place of `ids` — or None.
         code_bias: `_lib.code_bias_block(...)` in ROW order — (tables (NB, 2, V) float32, index (B,) int32), both numpy — or None.
-        repeat: `_lib.repeat_table(...)` in ROW order — (records, B) — or None."""
+        repeat: `_lib.repeat_table(...)` in ROW order — (records, B) — or None.
+        guide: (guide (B,) int32, scale (B,) float32) numpy tables in ROW order — the shadow's row of every row or -1, and the scales
+        (talkshow_hip.h, "guidance") — or None.  A shadow is a row of `wav` like any other."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
@@ -546,6 +597,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         lens_host = np.ascontiguousarray(rows, dtype=np.int32)
         if lens_dev is None:
             lens_dev = upload(lens_host, dev)
+        if guide is not None:
+            _lib.guide_check(guide[0], guide[1], lens_host)      # ValueError naming the row, before anything is launched
         mf = device_mfcc(sr, 22000, fps).forward_padded(wav, ns_host, ns_dev)
         B, T_max = mf.shape[0], mf.shape[1]
         H_max = T_max // 4
@@ -581,11 +634,46 @@ class TrainWrapper(TrainWrapperBaseClass):
         if pblock is not None and int(pblock.shape[1]) // 4 > H_max:
             raise ValueError(f"infer_padded_wav: the given poses hold {int(pblock.shape[1])} frames but the pass has {H_max} code rows")
         self._mixed_call(args, dev, ctl=sampling_table or (None, 0), given=(gblock, gtable), poses=(pblock, ptable), keep=given_keep, style=style,
-                         bias=(btab, bidx), repeat=(rtab, int(n_rep)))
+                         bias=(btab, bidx), repeat=(rtab, int(n_rep)), guide=guide or (None, None))
         return codes, poses, lens_host
 
+    def guide_wav_rows(self, gent, order, wav, ns_host, ids, clip_index, sr, fps, pieces, who):
+        """The rows of a GUIDED pass over recordings: gent = `_lib.guide_entries(..., audio_key="wav")` in submission order, order the sort
+        of the pass, wav / ns_host / ids / clip_index the padded block and its tables in ROW order, pieces = `infer_padded_wav`'s
+        keywords (validated blocks in row order) -> (wav, ns_host, ns_dev, ids, clip_index, pieces, prim): every shadow is a row directly
+        behind its primary, with its own samples, id and style and its primary's sample count; it brings no given rows, no poses and no
+        table; pieces gains `guide`; prim (numpy) are the rows of the clips themselves, in their old order."""
+        from talkshow_amd.frontend import mixed_tables
+        from talkshow_amd.modules import upload
+        dev = wav.device
+        src, shadow, gtab, gscale = _lib.guide_layout(order, gent)
+        slot_ent = [gent[i] for i in order]
+        sidx, shadows = np.asarray(src, np.int64), np.asarray(shadow, bool)
+        sdev = torch.as_tensor(sidx, device=dev)
+        rows_slot = [int(t) // 4 for t in mixed_tables(ns_host, sr, 22000, fps)["mfcc_rows"]]
+        style = pieces.get("style")
+        need_ids = style is None and any(e is not None and e["style"] is not None for e in gent)
+        style = _lib.guide_style_block(style, src, shadow, slot_ent, rows_slot, self.num_classes, ids.cpu().numpy() if need_ids else None,
+                                       who=who, names=order)
+        wav, ids, clip_index = wav.index_select(0, sdev).contiguous(), ids.index_select(0, sdev).contiguous(), clip_index.index_select(0, sdev).contiguous()
+        for s in np.flatnonzero(shadows):
+            e = slot_ent[src[s]]
+            if e["audio"] is not None:
+                wav[s, :int(ns_host[src[s]])] = torch.as_tensor(e["audio"], dtype=wav.dtype, device=dev)
+            if e["id"] is not None:
+                ids[s] = e["id"]
+        ns_host = np.ascontiguousarray(ns_host[sidx])
+        table, given, given_poses, keep, code_bias, repeat = _lib.guide_expand(
+            src, shadow, pieces.get("sampling_table") or (None, 0), pieces.get("given") or (None, None), pieces.get("given_poses") or (None, None),
+            pieces.get("given_keep"), pieces.get("code_bias") or (None, None), pieces.get("repeat") or (None, 0))
+        out = dict(sampling_table=table if table[0] is not None else None, given=given if given[0] is not None else None,
+                   given_poses=given_poses if given_poses[0] is not None else None, given_keep=keep, style=style,
+                   code_bias=code_bias if code_bias[0] is not None else None, repeat=repeat if repeat[0] is not None else None,
+                   guide=(gtab, gscale))
+        return wav, ns_host, upload(ns_host, dev), ids, clip_index, out, np.flatnonzero(~shadows)
+
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
+                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
@@ -597,7 +685,9 @@ class TrainWrapper(TrainWrapperBaseClass):
         "hand", a mask; one entry per recording, or one for all).  style: as for `generate_clips` — float speaker weights in place of the
         ids, per recording None, an (NC,) row or an (H_b,NC) track (H_b the recording's code rows), or one array for all.  code_bias: as for
         `generate_clips` — which codes a recording may use: one (2, V) table for all, or per recording None, a table or a dict.  repeat:
-        as for `generate_clips` — a repetition penalty over a window of earlier codes: one record for all, or a list with one per recording."""
+        as for `generate_clips` — a repetition penalty over a window of earlier codes: one record for all, or a list with one per recording.
+        guide: as for `generate_clips` — guidance against a second conditioning, whose audio is given as "wav": (N_b,) samples at `sr`,
+        the recording's own sample count (None: the recording's own audio); one dict for all, or a list with None or a dict per recording."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
@@ -631,6 +721,12 @@ class TrainWrapper(TrainWrapperBaseClass):
             code_bias = _lib.code_bias_block(code_bias, B, self.generator.input_dim, order, who="generate_clips_from_wav", mode=mode)
         if repeat is not None:
             repeat = _lib.repeat_table(repeat, B, self.generator.input_dim, order, who="generate_clips_from_wav", mode=mode)
+        gent = _lib.guide_entries(guide, B, who="generate_clips_from_wav", audio_key="wav", mode=mode, n_classes=self.num_classes,
+                                  rows=None if guide is None else [int(t) // 4 for t in mixed_tables(ns, sr, 22000, fps)["mfcc_rows"]])
+        for b, e in enumerate(gent or ()):
+            if e is not None and e["audio"] is not None and tuple(np.shape(e["audio"])) != (int(ns[b]),):
+                raise ValueError(f"generate_clips_from_wav: guide of clip {b}: wav must have the recording's own sample count ({int(ns[b])},), got "
+                                 f"{tuple(np.shape(e['audio']))}")
         ids = ids_in_row_order(ids, self.num_classes, order, dev)
         if clip_indices is None:
             clip_index = upload(np.asarray(order, np.int64) + int(clip_index0), dev)
@@ -639,8 +735,15 @@ class TrainWrapper(TrainWrapperBaseClass):
         if seed is None:
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
         wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
-        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, sampling_table=table, given=given,
-                                                    given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
+        pieces = dict(sampling_table=table, given=given, given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
+        prim = None
+        if gent is not None:
+            wav, ns_host, ns_dev, ids, clip_index, pieces, prim = self.guide_wav_rows(gent, order, wav, ns_host, ids, clip_index, sr, fps, pieces,
+                                                                                       "generate_clips_from_wav")
+        codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, **pieces)
+        if prim is not None:      # the shadows' rows are their primaries': the caller sees B results
+            pdev = torch.as_tensor(prim, dtype=torch.int64, device=dev)
+            codes, poses, lens = codes.index_select(0, pdev), poses.index_select(0, pdev), lens[prim]
         return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)]) for b in range(B)]
 
     def infer_on_audio(self, aud_fn, initial_pose=None, norm_stats=None, exp=None, var=None, w_pre=False, rand=None,

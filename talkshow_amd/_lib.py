@@ -155,6 +155,10 @@ SIGNATURES = {
     "ts_repeat_check": (_i, [_rp, _i, _i]),
     "ts_op_sample_repeat": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
                                  _i, C.POINTER(C.c_int32), _i, _rp, _i, _vp, _vp, _vp]),
+    # guidance: the host rule; one launch (ts_op_sample_repeat's arguments, then guide_host and guide_scale_host ahead of the stream)
+    "ts_guide_check": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32), _i]),
+    "ts_op_sample_guide": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
+                                _i, C.POINTER(C.c_int32), _i, _rp, _i, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -337,6 +341,7 @@ MIXED_PIECES = {
     "style": [_vp, _i],               # style_dev, style_rows
     "bias": [_vp, _i, _i32p],         # bias_dev, n_bias, bias_index_host
     "repeat": [_rp, _i],              # rep_host, n_rep
+    "guide": [_i32p, _fp],            # guide_host, guide_scale_host
 }
 
 
@@ -352,6 +357,14 @@ def _declare_ladder(stem, below, suffixes):
 _declare_ladder("ts_body_pixel_infer_mixed", (), ("ctl", "lp", "given", "keep", "style", "bias", "repeat"))
 _declare_ladder("ts_pixelcnn_generate_mixed", (), ("ctl", "lp", "given", "keep", "style", "bias", "repeat"))
 _declare_ladder("ts_body_pixel_infer_mixed", ("ctl", "lp"), ("poses", "poses_keep", "poses_style", "poses_bias", "poses_repeat"))
+# guidance: the most general entry of each family plus the guide piece ahead of the stream, under names of their own
+GUIDED_ENTRY = {
+    "ts_body_pixel_infer_mixed_repeat": "ts_body_pixel_infer_guided",
+    "ts_body_pixel_infer_mixed_poses_repeat": "ts_body_pixel_infer_guided_poses",
+    "ts_pixelcnn_generate_mixed_repeat": "ts_pixelcnn_generate_guided",
+}
+for _plain, _guided in GUIDED_ENTRY.items():
+    SIGNATURES[_guided] = (_i, SIGNATURES[_plain][1][:-1] + MIXED_PIECES["guide"] + [_vp])
 
 _lib = None
 
@@ -411,12 +424,19 @@ def face_generate_mixed(handle, wav, ns, ns_dev, frames, frames_dev, B, N_max, T
 
 
 def _mixed_tail(middle, ctl=None, n_ctl=0, logprob=None, keep=None, style=None, style_rows=0, bias=None, n_bias=0, bias_index=None,
-                rep=None, n_rep=0, stream=None):
+                rep=None, n_rep=0, guide=None, guide_scale=None, stream=None):
     """What follows the fixed arguments of a most general mixed entry (`..._repeat`), `middle` being its given or poses piece: every
-    keyword is an already-converted value (pointer, int, ctypes array), an absent one travels as None / 0."""
-    return (ctl, int(n_ctl) if ctl is not None else 0, logprob, *middle, keep, style, int(style_rows) if style is not None else 0,
+    keyword is an already-converted value (pointer, int, ctypes array), an absent one travels as None / 0.  guide / guide_scale (the
+    guided entries' piece, `GUIDED_ENTRY`) sit ahead of the stream only when a guide table came: without one the tail is the `_repeat`
+    entries'."""
+    tail = (ctl, int(n_ctl) if ctl is not None else 0, logprob, *middle, keep, style, int(style_rows) if style is not None else 0,
             bias, int(n_bias) if bias is not None else 0, bias_index if bias is not None else None,
-            rep, int(n_rep) if rep is not None else 0, stream)
+            rep, int(n_rep) if rep is not None else 0)
+    if guide is not None:
+        if guide_scale is None:
+            raise ValueError("_mixed_tail: a guide table needs its scales")
+        tail += (guide, guide_scale)
+    return (*tail, stream)
 
 
 def body_mixed_args(fixed, given=None, given_rows=None, poses=None, **pieces):
@@ -426,9 +446,12 @@ def body_mixed_args(fixed, given=None, given_rows=None, poses=None, **pieces):
     `ts_body_pixel_infer_mixed_repeat`: NULL is "the entry without that keyword, launch for launch" (talkshow_hip.h)."""
     if poses is not None and given is not None:
         raise ValueError("body_mixed_args: a pass brings given codes or given poses (stage the poses' codes into the given block)")
+    name = "ts_body_pixel_infer_mixed_poses_repeat" if poses is not None else "ts_body_pixel_infer_mixed_repeat"
+    if pieces.get("guide") is not None:      # the guided entries only for a pass that brings the table
+        name = GUIDED_ENTRY[name]
     if poses is not None:
-        return "ts_body_pixel_infer_mixed_poses_repeat", (*fixed, *_mixed_tail(tuple(poses), **pieces))
-    return "ts_body_pixel_infer_mixed_repeat", (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
+        return name, (*fixed, *_mixed_tail(tuple(poses), **pieces))
+    return name, (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
 
 
 def body_mixed_call(fixed, **pieces):
@@ -439,7 +462,10 @@ def body_mixed_call(fixed, **pieces):
 
 def pixelcnn_mixed_args(fixed, given=None, given_rows=None, **pieces):
     """`body_mixed_args` for the PixelCNN alone (`fixed`: its 12 arguments ahead of the stream): always `ts_pixelcnn_generate_mixed_repeat`."""
-    return "ts_pixelcnn_generate_mixed_repeat", (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
+    name = "ts_pixelcnn_generate_mixed_repeat"
+    if pieces.get("guide") is not None:
+        name = GUIDED_ENTRY[name]
+    return name, (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
 
 
 def pixelcnn_mixed_call(fixed, **pieces):
@@ -865,6 +891,189 @@ def repeat_table(repeat, B, V, order=None, who="repeat", mode=None):
         w, p, f = repeat_record(recs[i])
         arr[k].window, arr[k].presence, arr[k].frequency, arr[k].reserved = w, p, f, 0
     return arr, B
+
+
+GUIDE_MAX_SCALE = 1e4
+
+
+def guide_style(v, rows, NC, who, name):
+    """One guide entry's "style" as a validated float32 array: an (NC,) row or a (rows, NC) track of finite weights (`ts_style_check`).
+    ValueError naming clip `name`.  The one place these messages are made.  Pure host code; a device tensor is read back."""
+    v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    if v.dtype.kind not in "fiub" or v.ndim not in (1, 2) or (v.ndim == 2 and v.shape[0] != int(rows)) or v.shape[-1] != int(NC):
+        raise ValueError(f"{who}: guide of clip {name}: the style must have shape ({int(NC)},) or ({int(rows)}, {int(NC)}), got {v.dtype} {tuple(v.shape)}")
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    if load().ts_style_check(v.ctypes.data_as(C.POINTER(C.c_float)), int(v.size), int(NC)) != 0:
+        raise ValueError(f"{who}: guide of clip {name}: style: " + load().ts_last_error().decode())
+    return v
+
+
+def guide_entries(guide, B, who="guide", audio_key="mfcc", mode=None, n_classes=None, rows=None):
+    """The `guide=` keyword of the decode entries -> a list of B entries in SUBMISSION order, each None or a dict {"scale": float, "audio":
+    the entry's `audio_key` value or None, "id": int or None, "style": row / track or None}; None for `guide=None` or a list of None only
+    (talkshow_hip.h, "guidance": the clip is decoded under its own conditioning and at every position its logits are pushed away from, or
+    toward, those the same code history gets under a second conditioning — l' = l + scale * (l - l_q)).
+    guide: one dict for all clips, or a list with, per clip, None or a dict with the keys "scale" (required) and, each optional and None
+    meaning "the clip's own", `audio_key` ("mfcc", "wav" or "aud_rows": the second conditioning's audio, of the clip's own length), "id"
+    (in [0, n_classes) where n_classes is given) and "style" (validated here — shape and finite weights, `guide_style` — where rows, every
+    clip's own code rows in submission order, and n_classes are given; the entry then holds the float32 array).  mode: the call's draw mode, if the caller wants the scope checked here too.  Shapes of audio and style are the call
+    site's to check.  ValueError naming the SUBMITTED clip for a wrong key, a scale that is no number, a NaN, an infinity or |scale| > 1e4.
+    Pure host code."""
+    if guide is None:
+        return None
+    B = int(B)
+    if isinstance(guide, dict):
+        guide = [guide] * B
+    if not isinstance(guide, (list, tuple)) or len(guide) != B:
+        raise ValueError(f"{who}: guide takes one dict for all clips or a list with None or a dict per clip ({B}), got {type(guide).__name__}" +
+                         (f" of {len(guide)}" if isinstance(guide, (list, tuple)) else ""))
+    keys = ("scale", audio_key, "id", "style")
+    out = [None] * B
+    for i, e in enumerate(guide):
+        if e is None:
+            continue
+        if not isinstance(e, dict):
+            raise ValueError(f"{who}: guide of clip {i} must be None or a dict with the keys {keys}, got {type(e).__name__}")
+        unknown = [k for k in e if k not in keys]
+        if unknown:
+            raise ValueError(f"{who}: guide of clip {i}: unknown keys {sorted(map(str, unknown))} (the keys are {keys})")
+        if "scale" not in e:
+            raise ValueError(f"{who}: guide of clip {i} needs a scale")
+        try:
+            if isinstance(e["scale"], bool):
+                raise TypeError
+            with np.errstate(over="ignore"):
+                scale = float(np.float32(e["scale"]))
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: guide of clip {i}: the scale is a number, got {e['scale']!r}") from None
+        if np.isnan(scale):
+            raise ValueError(f"{who}: guide of clip {i}: the scale is NaN")
+        if np.isinf(scale):
+            raise ValueError(f"{who}: guide of clip {i}: the scale is infinite")
+        if abs(scale) > np.float32(GUIDE_MAX_SCALE):
+            raise ValueError(f"{who}: guide of clip {i}: the scale exceeds 1e4 in magnitude")
+        ident = e.get("id")
+        if ident is not None:
+            try:
+                if isinstance(ident, bool) or int(ident) != ident:
+                    raise TypeError
+                ident = int(ident)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: guide of clip {i}: the id is a whole number, got {e.get('id')!r}") from None
+            if n_classes is not None and not 0 <= ident < int(n_classes):
+                raise ValueError(f"{who}: guide of clip {i}: the id {ident} is outside [0, {int(n_classes)})")
+        style = e.get("style")
+        if style is not None and rows is not None and n_classes is not None:
+            style = guide_style(style, rows[i], n_classes, who, i)
+        out[i] = {"scale": scale, "audio": e.get(audio_key), "id": ident, "style": style}
+    if all(e is None for e in out):
+        return None
+    if mode is not None and mode not in (TS_SAMPLE_UNIFORMS, TS_SAMPLE_PHILOX):      # guidance shares the sampling table's scope
+        raise ValueError(f"{who}: guidance is a sampling control: sampling controls need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip "
+                         f"greedy is top_k = 1)")
+    return out
+
+
+def guide_layout(order, entries):
+    """The slots of a guided pass: order (sorted slot k holds submitted clip order[k]) and `guide_entries`' list -> (src, shadow, guide,
+    scale): the pass has len(src) slots; slot s copies every per-clip entry of ORIGINAL slot src[s]; shadow[s] says whether it is the
+    shadow of the slot before it; guide (int32) / scale (float32) are the guided entries' tables.  Every shadow sits directly behind
+    its primary, so the non-increasing length order holds and both are active in the same chunks.  Pure host code."""
+    src, shadow, guide, scale = [], [], [], []
+    for k, i in enumerate(order):
+        e = entries[int(i)]
+        src.append(k), shadow.append(False), guide.append(-1), scale.append(0.0)
+        if e is not None:
+            guide[-1], scale[-1] = len(src), e["scale"]
+            src.append(k), shadow.append(True), guide.append(-1), scale.append(0.0)
+    return src, shadow, np.asarray(guide, np.int32), np.asarray(scale, np.float32)
+
+
+def expand_records(arr, n, src):
+    """A ctypes array of n records (a sampling or repetition table in slot order) re-indexed for a guided pass: slot s takes record src[s].
+    A table of one record for all clips stays as it is."""
+    if arr is None or int(n) == 1:
+        return arr, n
+    out = (type(arr[0]) * len(src))()
+    for s, k in enumerate(src):
+        C.memmove(C.byref(out, s * C.sizeof(out[0])), C.byref(arr, int(k) * C.sizeof(arr[0])), C.sizeof(out[0]))
+    return out, len(src)
+
+
+def guide_style_block(sblock, src, shadow, entries, rows, NC, ids, who="guide", names=None):
+    """The style block of a guided pass: sblock = `style_block`'s (B, S, NC) block of the clips themselves in slot order, or None (the
+    pass runs on integer ids); src / shadow from `guide_layout`; entries[k] the guide entry of ORIGINAL slot k (or None); rows[k] its code
+    rows; ids (B,) the clips' integer ids in slot order (numpy; read only where a block has to be made of them); names[k] the submitted
+    index the messages name -> the (len(src), S', NC) block in which a shadow's rows are its "style" (an (NC,) row or a (rows[k], NC)
+    track), else the one-hot row of its "id", else its primary's rows; None if sblock is None and no shadow brings a style (the ids
+    carry every conditioning, the shadows' included).  ValueError naming the clip for a wrong shape or a non-finite weight."""
+    NC = int(NC)
+    names = list(range(len(rows))) if names is None else names
+    styles = {}
+    for s, k in enumerate(src):
+        e = entries[k] if shadow[s] else None
+        if e is None or e["style"] is None:
+            continue
+        styles[s] = guide_style(e["style"], rows[k], NC, who, names[k])      # (validated by `guide_entries` already where it had the rows)
+    if sblock is None and not styles:
+        return None
+    if sblock is None:
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        sblock = np.zeros((len(rows), 1, NC), np.float32)
+        sblock[np.arange(len(rows)), 0, ids] = 1.0
+    block = np.ascontiguousarray(sblock[np.asarray(src, np.int64)])
+    if block.shape[1] == 1 and any(v.ndim == 2 for v in styles.values()):
+        block = np.ascontiguousarray(np.repeat(block, max(int(h) for h in rows), axis=1))
+    for s, k in enumerate(src):
+        if not shadow[s]:
+            continue
+        if s in styles:
+            v = styles[s]
+            if v.ndim == 1:
+                block[s, :] = v
+            else:
+                block[s, :v.shape[0]] = v
+                block[s, v.shape[0]:] = v[-1]
+        elif entries[k]["id"] is not None:
+            block[s, :] = 0.0
+            block[s, :, entries[k]["id"]] = 1.0
+    return block
+
+
+def guide_expand(src, shadow, ctl=(None, 0), given=(None, None), poses=(None, None), keep=None, bias=(None, None), repeat=(None, 0)):
+    """The validated per-clip blocks of a pass (slot order) re-indexed to the slots of the guided pass (`guide_layout`): slot s takes the
+    entry of original slot src[s]; a shadow brings no given rows, no poses and no bias table (its sampling and repetition records are
+    its primary's and are never read).  Returns (ctl, given, poses, keep, bias, repeat) in the forms they came in.  Pure host code
+    (a pose block that is a device tensor is re-indexed on its device)."""
+    sidx, shadows = np.asarray(src, np.int64), np.asarray(shadow, bool)
+    ctl, repeat = expand_records(ctl[0], ctl[1], src), expand_records(repeat[0], repeat[1], src)
+    gblock, gtable = given
+    if gblock is not None:
+        given = (gblock[sidx], np.where(shadows, 0, gtable[sidx]).astype(np.int32))
+    pblock, ptable = poses
+    if pblock is not None:
+        if hasattr(pblock, "index_select"):
+            import torch
+            pblock = pblock.index_select(0, torch.as_tensor(sidx, device=pblock.device))
+        else:
+            pblock = pblock[sidx]
+        poses = (pblock, np.where(shadows, 0, ptable[sidx]).astype(np.int32))
+    keep = None if keep is None else np.ascontiguousarray(keep[sidx])
+    btab, bidx = bias
+    if btab is not None:
+        bias = (btab, np.where(shadows, -1, bidx[sidx]).astype(np.int32))
+    return ctl, given, poses, keep, bias, repeat
+
+
+def guide_check(guide, scale, lens=None):
+    """`ts_guide_check` on host tables: ValueError with the library's message (it names the slot).  Pure host code."""
+    guide = np.ascontiguousarray(guide, np.int32)
+    scale = np.ascontiguousarray(scale, np.float32)
+    i32p = C.POINTER(C.c_int32)
+    lens_p = None if lens is None else np.ascontiguousarray(lens, np.int32)
+    if load().ts_guide_check(guide.ctypes.data_as(i32p), scale.ctypes.data_as(_fp), None if lens_p is None else lens_p.ctypes.data_as(i32p),
+                             int(guide.size)) != 0:
+        raise ValueError(load().ts_last_error().decode())
 
 
 def given_pose_block(given_poses, rows, order=None, who="given_poses", width=129):

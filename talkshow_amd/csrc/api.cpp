@@ -256,6 +256,13 @@ static int body_repeat_check(const char *who, int mode, int B, int V, const ts_r
     return ts_repeat_check(rep_host, n_rep, V);
 }
 
+// What the body entries refuse of "guidance" before their first launch, the audio encoder's: the mode (a sampling control, like the bias) and
+// the tables, by the one rule the pass behind them applies again (ts_guide_check: one source for every message)
+static int body_guide_check(const char *who, int mode, int B, const MixedOpts &o, const int32_t *lens_host) {
+    TS_TRY(ctl_mode_check(who, mode));
+    return ts_guide_check(o.guide_host, o.guide_scale_host, lens_host, B);
+}
+
 // The body of every ts_body_pixel_infer_mixed* entry without given poses (a.rows = T_max): each entry fills `o` with its own arguments
 static int body_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const MixedPass &a, float *poses,
                       const MixedOpts &o, hipStream_t s) {
@@ -265,6 +272,7 @@ static int body_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *
     if (o.bias && body_bias_check("ts_body_pixel_infer_mixed_bias", a.mode, B, o.n_bias, o.bias_index_host) != 0) return 1;
     if (o.rep_host && body_repeat_check("ts_body_pixel_infer_mixed_repeat", a.mode, B, 1, o.rep_host, o.n_rep) != 0) return 1;
     TS_TRY(mixed_given_check("ts_body_pixel_infer_mixed_keep", "ts_body_pixel_infer_mixed_given", o, a.lens_host, B));   // a bad row table is refused before the first launch of the pass, too
+    if (o.guide_host && body_guide_check("ts_body_pixel_infer_guided", a.mode, B, o, a.lens_host) != 0) return 1;
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * convnet_hidden(ae) * sizeof(float)));
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, a.lens_dev, B, a.rows, w.feat.f(), s));
@@ -378,6 +386,24 @@ int ts_body_pixel_infer_mixed_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae 
     return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
+// the same pass under "guidance" (talkshow_hip.h): guide_host (B,) the shadow's slot of every clip slot or -1, guide_scale_host (B,).  A
+// shadow's rows of codes, log-probabilities and poses are its primary's.  guide_host == NULL: exactly the entry above
+int ts_body_pixel_infer_guided(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                    const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
+                                    const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
+                                    const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const int32_t *guide_host,
+                                    const float *guide_scale_host, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.guide_host = guide_host, o.guide_scale_host = guide_scale_host;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
+}
+
 // Host only: the rule every entry with given POSES applies to its frame table before anything is launched (talkshow_hip.h, "given poses")
 int ts_given_pose_rows_check(const int32_t *pose_lens_host, const int32_t *lens_host, int B) {
     if (!pose_lens_host || !lens_host || B < 1) return fail("ts_given_pose_rows_check: bad argument");
@@ -412,6 +438,7 @@ static int body_mixed_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_v
         if (o.bias && body_bias_check("ts_body_pixel_infer_mixed_poses_bias", a.mode, B, o.n_bias, o.bias_index_host) != 0) return 1;
         if (o.rep_host && body_repeat_check("ts_body_pixel_infer_mixed_poses_repeat", a.mode, B, 1, o.rep_host, o.n_rep) != 0) return 1;
         if (ts_given_pose_rows_check(o.pose_lens_host, a.lens_host, B) != 0) return 1;
+        if (o.guide_host && body_guide_check("ts_body_pixel_infer_guided_poses", a.mode, B, o, a.lens_host) != 0) return 1;
         int p_top = 0;
         G.resize(B);
         for (int b = 0; b < B; ++b) {
@@ -503,6 +530,24 @@ int ts_body_pixel_infer_mixed_poses_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_
     o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
     o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
     o.rep_host = rep_host, o.n_rep = n_rep;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
+}
+
+// the same under "guidance" (guide_host (B,), guide_scale_host (B,) in slot order; guide_host == NULL: exactly the entry above).  The encoders
+// never see the tables: a shadow brings no poses of its own, the codes of its primary's are written to both slots
+int ts_body_pixel_infer_guided_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                    const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                    uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                    float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                    const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
+                                    const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const int32_t *guide_host,
+                                    const float *guide_scale_host, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.guide_host = guide_host, o.guide_scale_host = guide_scale_host;
     return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 

@@ -296,6 +296,8 @@ struct MixedOpts {
     const int32_t *bias_index_host = nullptr;
     const ts_repeat *rep_host = nullptr;     // repetition penalty
     int n_rep = 0;
+    const int32_t *guide_host = nullptr;     // guidance: (B,) the shadow's slot of every clip slot or -1, and (B,) the scales
+    const float *guide_scale_host = nullptr;
     // the body wrapper only: given poses
     const float *given_poses = nullptr;
     int P_max = 0;
@@ -325,14 +327,19 @@ inline int mixed_given_check(const char *who_keep, const char *who_given, const 
 // The entries the messages of build() name: a table's faults, neutral records under a bias / under repetition records, a mask, given codes
 struct SamplerNames {
     const char *ctl, *bias, *rep, *keep, *given;
+    const char *guide = "ts_guide_check";   // neutral records under a guide table
 };
-inline SamplerNames sampler_names(const char *who) { return {who, who, who, who, who}; }   // an entry that names itself throughout
+inline SamplerNames sampler_names(const char *who) { return {who, who, who, who, who, who}; }   // an entry that names itself throughout
 struct SamplerTables {
     int B = 0;
     std::vector<SampleCtl> ctl;        // B records where a table, a bias or repetition records came (neutral ones without a table), else empty
     std::vector<SampleRep> rep;        // B records where repetition records came
     std::vector<int32_t> no_bias;      // B times -1 where repetition records came without bias tables: the index the samplers want
     std::vector<int32_t> given_rows;   // a copy of o.given_rows_host where given codes came
+    // guidance: B roles (-1 plain, g >= 0 the shadow's slot, -2 a shadow) and B scales where a guide table came, else empty.  A guided pass
+    // runs the BIAS and REP arithmetic: ctl, rep (window 0) and no_bias are then filled with neutral values where their pieces did not come
+    std::vector<int32_t> guide_role;
+    std::vector<float> guide_scale;
     // Launches nothing.  lens_host: the frames a clip's given rows must fit (>> 2), read only where given codes came
     int build(const MixedOpts &o, int B, int V, int mode, const int32_t *lens_host, const SamplerNames &who);
 };

@@ -672,6 +672,13 @@ struct SampleCtlParams {
     // bias null: a pass without tables); null for every other launch
     const SampleRep *rep;
     int32_t *rep_ring;
+    // "guidance" (talkshow_hip.h): guide_role[b] the role of clip slot b — -1 plain, g >= 0 a primary whose shadow is slot g, -2 a shadow,
+    // whose workgroup returns at once — and guide_scale[b] the scale of a primary.  A primary reads the logits row of slot g through the
+    // strides of its own and writes what it chose or was given to both slots' entries of tok32, codes, kept and logprob.  Read by the
+    // sample_ctl_guide kernels only, which also need rep, rep_ring and bias_index (records of window 0 / an index of -1: a pass without
+    // those pieces); null for every other launch
+    const int32_t *guide_role;
+    const float *guide_scale;
 };
 // a histogram bin of the kernel holds count << 44 | mass with mass <= V * 2^31: V * 2^31 < 2^44 bounds the vocabulary (the tie counters' 16 bits
 // and the count field hold more); launch_sample_ctl and the host checks refuse anything above

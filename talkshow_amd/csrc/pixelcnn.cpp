@@ -118,6 +118,8 @@ struct ts_pixelcnn {
                                            // history rings [slot][2][64] int32 (the code of row r, column j at index r & 63) the sample_ctl_rep kernels read and
                                            // write.  Both are sized by capB in ensure_work, so they never move under a graph; the rings need no clearing: a launch
                                            // reads min(r, W) entries, all written earlier in the same pass by the same slot
+        DevBuf guide_tab, guide_scl;       // passes with guidance: the role of every clip SLOT (int32: -1 plain, g >= 0 the shadow's slot, -2 a shadow) and
+                                           // the scale of every primary (fp32), written in stream order ahead of the pass; sized by capB in ensure_work
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step (in a session's own Work);
@@ -130,7 +132,8 @@ struct ts_pixelcnn {
         // read their conditioning rows from style_int in place of CR), bit 5 for a pass with a code bias (its samplers are the sample_ctl_bias
         // kernels, which read bias_tab and bias_idx; neither the tables' content nor their number is part of the key), bit 6 for a pass with a repetition penalty (its samplers are the
         // sample_ctl_rep kernels, which read rep_tab and bias_idx and read and write rep_ring; the records are not part of the key), bit 7 for the steps of a
-        // session that has restarted a slot (their samplers read the session's row_origin and the clip table; which slots restarted, and where, is not part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // session that has restarted a slot (their samplers read the session's row_origin and the clip table; which slots restarted, and where, is not part of the key), bit 8 for a pass
+        // with guidance (its samplers are the sample_ctl_guide kernels, which read guide_tab and guide_scl beside what the sample_ctl_rep kernels read; roles and scales are not part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -301,6 +304,8 @@ int ensure_work(ts_pixelcnn *p, ts_pixelcnn::Work *w, int B, int Htot) {
     TS_TRY(w->bias_idx.ensure((size_t)cb * sizeof(int32_t)));
     TS_TRY(w->rep_tab.ensure((size_t)cb * sizeof(SampleRep)));
     TS_TRY(w->rep_ring.ensure((size_t)cb * 2 * SAMPLE_REP_RING * sizeof(int32_t)));
+    TS_TRY(w->guide_tab.ensure((size_t)cb * sizeof(int32_t)));
+    TS_TRY(w->guide_scl.ensure((size_t)cb * sizeof(float)));
     TS_TRY(w->cAEH.ensure((size_t)cb * CHUNK_ROWS * D * f));
     TS_TRY(w->cAEH1.ensure((size_t)cb * CHUNK_ROWS * 2 * D * f));
     TS_TRY(w->cAV1C.ensure((size_t)cb * CHUNK_ROWS * 4 * D * f));
@@ -360,6 +365,10 @@ struct RunCfg {
     // records c.ctl and c.bias_index are set too (neutral records / an index of -1 when the call brought none)
     const SampleRep *rep = nullptr;
     int32_t *rep_ring = nullptr;
+    // "guidance": the Work's guide_tab and guide_scl (slabB(),), or null: the samplers without a role table.  With them c.ctl, c.bias_index,
+    // c.rep and c.rep_ring are set too (neutral records, an index of -1, records of window 0 when the call brought none)
+    const int32_t *guide_role = nullptr;
+    const float *guide_scale = nullptr;
     // "slot restart": the session's (slabB(),) table of the row at which every slot's current clip began, or null (a session that never
     // restarted a slot, and every one-shot call).  With it c.clip_table is set too
     const int32_t *row_origin = nullptr;
@@ -907,6 +916,7 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
     cp.logprob = lp, cp.lp_stride = (long)sH * 2;
     cp.bias = c.bias, cp.bias_index = c.bias_index, cp.bias_col = j;
     cp.rep = c.rep, cp.rep_ring = c.rep_ring;
+    cp.guide_role = c.guide_role, cp.guide_scale = c.guide_scale;
     if (c.given_rows) {
         SampleGivenParams gp;
         gp.c = cp;
@@ -1347,7 +1357,7 @@ namespace {
 inline int sampler_bits(const RunCfg &c, const float *logprob) {
     const bool given = c.given_rows;
     return (c.ctl ? 1 : 0) | (logprob ? 2 : 0) | (given ? 4 : 0) | (given && c.keep_src ? 8 : 0) | (c.style ? 16 : 0) | (c.bias ? 32 : 0) | (c.rep ? 64 : 0) |
-           (c.row_origin ? 128 : 0);
+           (c.row_origin ? 128 : 0) | (c.guide_role ? 256 : 0);
 }
 // The tables reach the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own tables — may be queued behind each other.
@@ -1375,6 +1385,15 @@ int stage_sampler_tables(ts_pixelcnn *p, ts_pixelcnn::Work *w, const SamplerTabl
         MiscScope ms(ctx, s);
         TS_HIP(launch_put_words(w->given_tab.i(), t.given_rows.data(), B, s));
     }
+    if (o.guide_host) {   // roles and scales as kernel arguments, and what the REP path reads where the pass brought no records / no tables
+        MiscScope ms(ctx, s);
+        TS_HIP(launch_put_words(w->guide_tab.i(), t.guide_role.data(), B, s));
+        TS_HIP(launch_put_words(w->guide_scl.i(), reinterpret_cast<const int *>(t.guide_scale.data()), B, s));
+        if (!o.rep_host) {
+            TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(t.rep.data()), (long)B * 4, s));
+            if (!o.bias) TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), t.no_bias.data(), B, s));
+        }
+    }
     return 0;
 }
 // Every table is indexed by the clip's slot in the pass (in a mixed pass the active clips are a prefix, so the slot is the same in every
@@ -1389,6 +1408,14 @@ void bind_sampler_tables(RunCfg &c, ts_pixelcnn::Work *w, const MixedOpts &o) {
         c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
     }
     if (o.given) c.given_rows = w->given_tab.i(), c.given_src = o.given;
+    if (o.guide_host) {   // the guided samplers read everything the sample_ctl_rep kernels read
+        c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
+        c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
+        c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
+        c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+        c.guide_role = w->guide_tab.i();
+        c.guide_scale = w->guide_scl.f();
+    }
 }
 
 // audio conditioning of `rows` code rows per clip: AE = embedding_aud(aud); AEV / AEH = fusion_{v,h}[:, D:] . AE + bias;
@@ -1758,6 +1785,26 @@ int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *p, const int64_t *label, cons
     return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
+// the same pass under "guidance" (talkshow_hip.h): guide_host (B,) the shadow's slot of every clip slot or -1, guide_scale_host (B,).  Roles
+// and scales are copied into the Work in stream order ahead of the pass (kernel arguments); the samplers are the sample_ctl_guide kernels
+// on graph keys of their own (bit 8); a call without a sampling table runs on neutral records.  guide_host == NULL: the _repeat entry,
+// launch for launch
+int ts_pixelcnn_generate_guided(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                     int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                     int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                     const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
+                                     int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                     const ts_repeat *rep_host, int n_rep, const int32_t *guide_host, const float *guide_scale_host,
+                                     void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.guide_host = guide_host, o.guide_scale_host = guide_scale_host;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // The body of every ts_pixelcnn_generate_mixed* entry: each fills `o` with its own arguments, so an absent keyword is null here and costs no
@@ -1782,7 +1829,7 @@ int ts::pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPas
     SamplerTables t;
     TS_TRY(t.build(o, B, p->V, mode, a.lens_host,
                    {"ts_pixelcnn_generate_mixed_ctl", "ts_pixelcnn_generate_mixed_bias", "ts_pixelcnn_generate_mixed_repeat",
-                    "ts_pixelcnn_generate_mixed_keep", "ts_pixelcnn_generate_mixed_given"}));
+                    "ts_pixelcnn_generate_mixed_keep", "ts_pixelcnn_generate_mixed_given", "ts_pixelcnn_generate_guided"}));
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));

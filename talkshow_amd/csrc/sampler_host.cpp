@@ -127,6 +127,38 @@ int ts_repeat_check(const ts_repeat *rep_host, int n, int V) {
     return 0;
 }
 
+// Host only ("guidance"): guide (B,) the shadow's slot of every clip slot or -1, scale (B,) floats (read where guide[b] >= 0), lens (B,)
+// the slots' lengths IN FRAMES as the pass entries take them, compared as they are (NULL: a launch whose rows have no lengths).  Refuses, naming the slot: an index outside [-1, B), a slot that names
+// itself, a shadow named twice, a shadow that is itself guided, unequal lengths, a NaN or an infinity, |scale| > 1e4
+int ts_guide_check(const int32_t *guide_host, const float *scale_host, const int32_t *lens_host, int B) {
+    if (!guide_host || !scale_host || B < 1) return fail("ts_guide_check: bad argument");
+    std::vector<int> named(B, -1);   // the primary that names a slot as its shadow
+    for (int b = 0; b < B; ++b) {
+        const int g = guide_host[b];
+        const std::string where = "ts_guide_check: clip " + std::to_string(b);
+        if (g < -1 || g >= B) return fail(where + ": the shadow index is " + std::to_string(g) + ", not -1 (none) or in [0, " + std::to_string(B) + ")");
+        if (g < 0) continue;
+        if (g == b) return fail(where + " names itself as its shadow");
+        if (named[g] >= 0) return fail(where + ": its shadow, slot " + std::to_string(g) + ", is already the shadow of clip " + std::to_string(named[g]));
+        named[g] = b;
+    }
+    for (int b = 0; b < B; ++b) {
+        const int g = guide_host[b];
+        if (g < 0) continue;
+        const std::string where = "ts_guide_check: clip " + std::to_string(b);
+        if (guide_host[g] >= 0) return fail(where + ": its shadow, slot " + std::to_string(g) + ", is itself guided (a shadow draws nothing)");
+        if (named[b] >= 0) return fail(where + " is guided and is the shadow of clip " + std::to_string(named[b]) + " (a shadow draws nothing)");
+        if (lens_host && lens_host[g] != lens_host[b])
+            return fail(where + ": its length of " + std::to_string(lens_host[b]) + " frames differs from the " + std::to_string(lens_host[g]) + " frames of its shadow, slot " +
+                        std::to_string(g));
+        const float sc = scale_host[b];
+        if (std::isnan(sc)) return fail(where + ": the scale is NaN");
+        if (std::isinf(sc)) return fail(where + ": the scale is infinite");
+        if (std::fabs(sc) > 1e4f) return fail(where + ": the scale exceeds 1e4 in magnitude");
+    }
+    return 0;
+}
+
 // Host only: the rule every _given entry applies to its row table before anything is launched
 int ts_given_rows_check(const int32_t *given_rows_host, const int32_t *lens_host, int B) {
     if (!given_rows_host || !lens_host || B < 1) return fail("ts_given_rows_check: bad argument");
@@ -164,6 +196,23 @@ int ts::SamplerTables::build(const MixedOpts &o, int B_, int V, int mode, const 
     }
     TS_TRY(mixed_given_check(who.keep, who.given, o, lens_host, B));
     if (o.given) given_rows.assign(o.given_rows_host, o.given_rows_host + B);
+    if (o.guide_host) {   // last: the refusals above keep their order and text
+        if (ctl.empty()) {   // a sampling control like the bias: neutral records, which refuse greedy and teacher forced
+            const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
+            TS_TRY(ctl_table(&neutral, 1, B, V, mode, who.guide, ctl));
+        }
+        TS_TRY(ts_guide_check(o.guide_host, o.guide_scale_host, lens_host, B));
+        guide_role.assign(o.guide_host, o.guide_host + B);
+        guide_scale.assign(B, 0.0f);
+        for (int b = 0; b < B; ++b)
+            if (o.guide_host[b] >= 0) {
+                guide_role[o.guide_host[b]] = -2;
+                guide_scale[b] = o.guide_scale_host[b];
+            }
+        // the guided samplers run the BIAS and REP paths: an index of -1 and records of window 0 are "same arithmetic" there
+        if (!o.bias && no_bias.empty()) no_bias.assign(B, -1);
+        if (rep.empty()) rep.assign(B, SampleRep{0, 0.0f, 0.0f, 0});
+    }
     return 0;
 }
 
@@ -191,7 +240,7 @@ struct OpSample {
     const uint8_t *keep = nullptr;
     const int64_t *given = nullptr;
     float *logits_copy = nullptr;
-    MixedOpts o;   // the sampling table, the bias and the repetition records, as a pass takes them
+    MixedOpts o;   // the sampling table, the bias, the repetition records and the guide table, as a pass takes them
     int column = 0;
     const int32_t *history = nullptr;
     int32_t *ring_out = nullptr;
@@ -205,12 +254,12 @@ int op_sample(const OpSample &a) {
     if (!a.ctx || !a.logits || !a.idx || a.missing) return fail(who + ": null argument");
     const int hist_rows = (int)std::min<uint32_t>(a.position >> 1, (uint32_t)SAMPLE_REP_RING);
     if (o.rep_host && hist_rows > 0 && !a.history) return fail(who + ": rows behind row 0 need their history");
-    if (!o.rep_host && (a.history || a.ring_out)) return fail(who + ": a history and a ring output need records");
+    if (!o.rep_host && !o.guide_host && (a.history || a.ring_out)) return fail(who + ": a history and a ring output need records");
     if (B < 1 || V < 1) return fail(who + ": bad shape");
     if (a.column != 0 && a.column != 1) return fail(who + ": column is 0 (body) or 1 (hand)");
     if (a.modes && (a.mode < 0 || a.mode >= a.modes)) return fail(who + ": bad mode");
     if (a.mode == TS_SAMPLE_UNIFORMS && !a.uniforms) return fail(who + ": uniforms required");
-    const bool pieces = o.bias || o.rep_host;   // they run on neutral records where no table came
+    const bool pieces = o.bias || o.rep_host || o.guide_host;   // they run on neutral records where no table came
     if (a.kept && !o.ctl_host && !pieces) return fail(who + ": kept_dev needs a table");
     const bool given_rows = a.forced_host || a.given_rows_host;
     if (given_rows) {
@@ -228,7 +277,7 @@ int op_sample(const OpSample &a) {
     for (size_t b = 0; b < rows.size(); ++b) rows[b] = a.forced_host[b] ? (int)(a.position / 2) + 1 : 0;
 
     hipStream_t s = (hipStream_t)a.stream;
-    DevBuf tok, dtab, drows, dbi, drep, dring;
+    DevBuf tok, dtab, drows, dbi, drep, dring, drole, dscale;
     TS_TRY(tok.ensure((size_t)B * sizeof(int)));
     SampleGivenParams gp;
     std::memset(&gp, 0, sizeof(gp));
@@ -264,14 +313,22 @@ int op_sample(const OpSample &a) {
         gp.c.bias_col = a.column;
     }
     const size_t ring_pitch = (size_t)2 * SAMPLE_REP_RING * sizeof(int32_t);   // one clip's two rings
-    if (o.rep_host) {
+    if (!t.guide_role.empty()) {
+        TS_TRY(drole.ensure((size_t)B * sizeof(int32_t)));
+        TS_TRY(dscale.ensure((size_t)B * sizeof(float)));
+        TS_HIP(launch_put_words(drole.i(), t.guide_role.data(), B, s));
+        TS_HIP(launch_put_words(dscale.i(), reinterpret_cast<const int *>(t.guide_scale.data()), B, s));
+        gp.c.guide_role = static_cast<const int32_t *>(drole.p);
+        gp.c.guide_scale = dscale.f();
+    }
+    if (!t.rep.empty()) {
         TS_TRY(drep.ensure((size_t)B * sizeof(SampleRep)));
         TS_TRY(dring.ensure((size_t)B * ring_pitch));
         TS_HIP(launch_put_words(drep.i(), reinterpret_cast<const int *>(t.rep.data()), (long)B * 4, s));
         TS_HIP(hipMemsetAsync(dring.p, 0xff, (size_t)B * ring_pitch, s));
         // rows r - R .. r - 1 are consecutive ring slots modulo 64: one or two strided copies
         const uint32_t first = (a.position >> 1) - (uint32_t)hist_rows;
-        for (int done = 0; done < hist_rows;) {
+        for (int done = 0; a.history && done < hist_rows;) {   // (a guided launch without records brings none: its windows are 0)
             const int slot = (int)((first + (uint32_t)done) & (uint32_t)(SAMPLE_REP_RING - 1));
             const int n = std::min(hist_rows - done, SAMPLE_REP_RING - slot);
             TS_HIP(hipMemcpy2DAsync(dring.i() + (size_t)a.column * SAMPLE_REP_RING + slot, ring_pitch, a.history + done,
@@ -297,7 +354,7 @@ int op_sample(const OpSample &a) {
     } else {
         TS_HIP(launch_sample(sp, s));
     }
-    if (o.rep_host && a.ring_out)
+    if (!t.rep.empty() && a.ring_out)
         TS_HIP(hipMemcpy2DAsync(a.ring_out, (size_t)SAMPLE_REP_RING * sizeof(int32_t), dring.i() + (size_t)a.column * SAMPLE_REP_RING, ring_pitch,
                                 (size_t)SAMPLE_REP_RING * sizeof(int32_t), B, hipMemcpyDeviceToDevice, s));
     TS_HIP(hipStreamSynchronize(s));
@@ -369,6 +426,24 @@ int ts_op_sample_repeat(ts_ctx *ctx, const float *logits, int B, int V, int mode
     a.o.ctl_host = ctl_host, a.o.n_ctl = n_ctl;
     a.kept = kept, a.logprob = logprob, a.given_rows_host = given_rows_host, a.keep = keep, a.given = given, a.logits_copy = logits_copy;
     a.o.bias = bias, a.o.n_bias = n_bias, a.o.bias_index_host = bias_index_host, a.o.rep_host = rep_host, a.o.n_rep = n_rep;
+    a.column = column, a.history = history, a.ring_out = ring_out;
+    return op_sample(a);
+}
+
+// The same launch under "guidance" (kernel-level tests call it): guide_host (B,) the shadow's row of every row or -1, scale_host (B,).  A
+// primary reads its shadow's logits row and writes idx, kept and logprob for both rows; a shadow's ring is not touched.  Every other
+// argument as for ts_op_sample_repeat (rep_host == NULL: no records; bias == NULL: no tables).  guide_host == NULL is refused
+int ts_op_sample_guide(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                       uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
+                       const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
+                       const int32_t *bias_index_host, int column, const ts_repeat *rep_host, int n_rep, const int32_t *history,
+                       int32_t *ring_out, const int32_t *guide_host, const float *scale_host, void *stream) {
+    OpSample a{"ts_op_sample_guide", !guide_host || !scale_host || (bias && !bias_index_host), 0, ctx, logits, B, V, mode, uniforms, seed,
+               clip_index0, position, idx, stream};
+    a.o.ctl_host = ctl_host, a.o.n_ctl = n_ctl;
+    a.kept = kept, a.logprob = logprob, a.given_rows_host = given_rows_host, a.keep = keep, a.given = given, a.logits_copy = logits_copy;
+    a.o.bias = bias, a.o.n_bias = n_bias, a.o.bias_index_host = bias_index_host, a.o.rep_host = rep_host, a.o.n_rep = n_rep;
+    a.o.guide_host = guide_host, a.o.guide_scale_host = scale_host;
     a.column = column, a.history = history, a.ring_out = ring_out;
     return op_sample(a);
 }

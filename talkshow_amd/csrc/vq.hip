@@ -1410,6 +1410,18 @@ __device__ __forceinline__ float rep_penalise(float l, int c, float presence, fl
     return l - g;
 }
 
+// the rule of "guidance" (talkshow_hip.h) for one token: difference, product and sum, each rounded on its own
+__device__ __forceinline__ float guide_mix(float l, float lq, float scale) {
+#pragma clang fp contract(off)
+    const float d = l - lq;
+    const float t = scale * d;
+    return l + t;
+}
+// the value sample_store_logprob stores, for a workgroup that stores it twice (GUIDE)
+__device__ __forceinline__ float sample_logprob_value(float d, float S, bool kept = true) {
+    return kept ? (float)((double)d - log((double)S)) : (float)log(0.0);
+}
+
 // The body of the eight samplers with controls.  Flags:
 //   FAST   V = 2048 on 16-byte aligned rows (the launchers decide): every thread owns 8 logits, held in registers from two 16-byte loads
 //   LP     also write the log-probability of the row's code under the distribution it was drawn from (cp.logprob; talkshow_hip.h,
@@ -1433,15 +1445,38 @@ __device__ __forceinline__ float rep_penalise(float l, int c, float presence, fl
 //          W = 64: slot r & 63 holds row r - 64, the OLDEST entry read, and is the entry written.  The reads are wave 0's, ahead of the
 //          barrier behind them; the store comes behind every barrier of the body, and a ring belongs to one workgroup of one launch.
 //          (A forced workgroup without LP returns ahead of the barriers: it reads no entry at all.)
-// Inlined into its __global__ entries (eight without BIAS, eight with, eight with BIAS and REP); DESIGN.md §5 ("One body per sampler
+//   GUIDE  "guidance" (talkshow_hip.h): the slot's role is one uniform load ahead of everything else.  -2, a shadow: the workgroup
+//          returns there, ahead of every load, store and barrier of the body; the condition depends on blockIdx alone, so the exit is
+//          uniform over the workgroup and no wave waits at a barrier for one that left.  g >= 0, a primary: the row of slot g is read
+//          through the strides of the slot's own row, l' = l + scale * (l - l_g) (guide_mix: three roundings) replaces l ahead of step
+//          0 — in the vector path in the 8 registers, behind the row copies, which stay the network's two rows — and every store of the
+//          slot's token, code, kept bytes and log-probability is made to slot g's entries as well; the ring read and written is the
+//          slot's own.  -1: the arithmetic of the kernel without GUIDE, operation for operation.  GUIDE = false compiles to what the
+//          body was before the flag existed.  Instantiated with BIAS = REP = true only.
+// Inlined into its __global__ entries (eight without BIAS, eight with, eight with BIAS and REP, eight with GUIDE); DESIGN.md §5 ("One body per sampler
 // family") records what was compared against the two separate kernel templates it replaces.
-template <bool FAST, bool LP, bool GIVEN, bool BIAS = false, bool REP = false>
+template <bool FAST, bool LP, bool GIVEN, bool BIAS = false, bool REP = false, bool GUIDE = false>
 __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride,
                                                 const unsigned char *keep, long keep_stride, float *sf, int *si, float &s_thr, int &s_last,
                                                 uint32_t *s_tie, ctl_u64 (*hist)[256], int *s_rep = nullptr) {
     const SampleParams &p = cp.s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    static_assert(!GUIDE || (BIAS && REP), "the guided samplers imply the bias and repetition arithmetic");
+    [[maybe_unused]] int gslot = -1;        // GUIDE: the shadow's slot of a primary, -1 for a plain slot
+    [[maybe_unused]] float gscale = 0.f;
+    if constexpr (GUIDE) {
+        const int role = cp.guide_role[b];
+        if (role == -2) return;             // a shadow draws nothing: out ahead of every barrier, the whole workgroup (blockIdx alone decides)
+        if (role >= 0) {
+            gslot = role;
+            gscale = cp.guide_scale[b];
+        }
+    }
     const float *lg = sample_row(p, b);
+    [[maybe_unused]] const float *lq = nullptr;   // GUIDE: the shadow's row, through the strides of the slot's own
+    if constexpr (GUIDE) {
+        if (gslot >= 0) lq = sample_row(p, gslot);
+    }
     bool forced = false;       // workgroup-uniform, ahead of every barrier
     long long gcode = -1;
     if constexpr (GIVEN) {
@@ -1454,6 +1489,10 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     const int n = FAST ? 8 : max(v1 - v0, 0);
     float x[8];
     if constexpr (FAST) sample_load8(lg, v0, x);
+    [[maybe_unused]] float xq[8];
+    if constexpr (GUIDE && FAST) {
+        if (lq) sample_load8(lq, v0, xq);
+    }
     // BIAS: the clip's row of this column, or null (workgroup-uniform: the index is one uniform load)
     const float *bias = nullptr;
     if constexpr (BIAS) {
@@ -1495,6 +1534,9 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         if constexpr (FAST) return x[k];
         else if constexpr (REP) {
             float l = lg[v0 + k];
+            if constexpr (GUIDE) {
+                if (lq) l = guide_mix(l, lq[v0 + k], gscale);
+            }
             if (bias) l = l + bias[v0 + k];
             return rep_any ? rep_penalise(l, rep_count(v0 + k), rep_pres, rep_freq) : l;
         }
@@ -1507,6 +1549,24 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         else return false;
     };
     sample_copy_row(p, b, FAST, lg, x, v0, v1);   // the network's l: step 0 comes behind the copy
+    if constexpr (GUIDE) {
+        if (lq) {   // the shadow's row copy is the network's, too; then l' takes l's place
+            sample_copy_row(p, gslot, FAST, lq, xq, v0, v1);
+            if constexpr (FAST) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) x[k] = guide_mix(x[k], xq[k], gscale);
+            }
+        }
+    }
+    // what a primary writes for itself it writes for its shadow (GUIDE; nothing otherwise)
+    auto store_shadow = [&](int tok, long long code) {
+        if constexpr (GUIDE) {
+            if (gslot >= 0) {
+                p.tok32[(long)gslot * p.tok_stride] = tok;
+                p.codes[(long)gslot * p.code_stride] = code;
+            }
+        }
+    };
     if constexpr (BIAS && FAST) {
         if (bias) {
 #pragma unroll
@@ -1518,6 +1578,7 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
             if (tid == 0) {
                 p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
                 p.codes[(long)b * p.code_stride] = gcode;
+                store_shadow(given_token(gcode, p.V), gcode);
                 if constexpr (REP) {
                     if (ring) ring[rep_slot] = given_token(gcode, p.V);   // a taken code enters the history
                 }
@@ -1663,12 +1724,19 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     {
         int jk = jk0, jp = jp0;
         unsigned char *kd = cp.kept ? cp.kept + (long)b * p.V : nullptr;
+        [[maybe_unused]] unsigned char *kq = nullptr;
+        if constexpr (GUIDE) {
+            if (cp.kept && gslot >= 0) kq = cp.kept + (long)gslot * p.V;
+        }
 #pragma unroll 8
         for (int k = 0; k < n; ++k) {
             bool kp = !sel || ctl_keep(S, key_of(k), jk, jp);
             if constexpr (BIAS) kp = kp && !banned(k);
             if (kp) { s += weight(k); hi = v0 + k; }
             if (kd) kd[v0 + k] = kp ? 1 : 0;
+            if constexpr (GUIDE) {
+                if (kq) kq[v0 + k] = kp ? 1 : 0;
+            }
             if constexpr (GIVEN && LP) {
                 if ((long long)(v0 + k) == gcode) { gkept = kp; glc = logit(k); }
             }
@@ -1684,11 +1752,22 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
     if constexpr (GIVEN && LP) {
         if (forced) {   // workgroup-uniform: S = sf[256] is there, nothing is drawn
             float *out = cp.logprob + (long)b * cp.lp_stride;
-            if (gcode >= (long long)v0 && gcode < (long long)v1) sample_store_logprob(out, ctl_arg(glc, best, inv_t), sf[256], gkept);
+            if constexpr (GUIDE) {
+                float *outq = gslot >= 0 ? cp.logprob + (long)gslot * cp.lp_stride : nullptr;
+                if (gcode >= (long long)v0 && gcode < (long long)v1) {
+                    const float val = sample_logprob_value(ctl_arg(glc, best, inv_t), sf[256], gkept);
+                    *out = val;
+                    if (outq) *outq = val;
+                }
+                if (tid == 0 && outq) sample_store_unowned(outq, gcode, p.V);
+            } else {
+                if (gcode >= (long long)v0 && gcode < (long long)v1) sample_store_logprob(out, ctl_arg(glc, best, inv_t), sf[256], gkept);
+            }
             if (tid == 0) {
                 sample_store_unowned(out, gcode, p.V);
                 p.tok32[(long)b * p.tok_stride] = given_token(gcode, p.V);
                 p.codes[(long)b * p.code_stride] = gcode;
+                store_shadow(given_token(gcode, p.V), gcode);
                 if constexpr (REP) {
                     if (ring) ring[rep_slot] = given_token(gcode, p.V);
                 }
@@ -1722,6 +1801,7 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         const int choice = si[0];
         p.tok32[(long)b * p.tok_stride] = choice;
         p.codes[(long)b * p.code_stride] = choice;
+        store_shadow(choice, choice);
         if constexpr (REP) {
             if (ring) ring[rep_slot] = choice;
         }
@@ -1733,7 +1813,13 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
 #pragma unroll 8
             for (int k = 0; k < n; ++k)
                 if (v0 + k == choice) lc = logit(k);
-            sample_store_logprob(cp.logprob + (long)b * cp.lp_stride, ctl_arg(lc, best, inv_t), sf[256]);
+            if constexpr (GUIDE) {
+                const float val = sample_logprob_value(ctl_arg(lc, best, inv_t), sf[256]);
+                cp.logprob[(long)b * cp.lp_stride] = val;
+                if (gslot >= 0) cp.logprob[(long)gslot * cp.lp_stride] = val;
+            } else {
+                sample_store_logprob(cp.logprob + (long)b * cp.lp_stride, ctl_arg(lc, best, inv_t), sf[256]);
+            }
         }
     }
 }
@@ -1805,17 +1891,57 @@ __global__ __launch_bounds__(256) void sample_ctl_rep_given_kernel(const SampleG
     sample_ctl_body<FAST, LP, true, true, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie, hist,
                                                 s_rep);
 }
+// "guidance": the two families once more with BIAS = REP = GUIDE = true, launched only for a run that brings a role table
+// (p.guide_role != null).  A run without records brings records of window 0, one without tables an index of -1 everywhere
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_guide_kernel(const SampleCtlParams cp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ int s_rep[SAMPLE_REP_RING];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, false, true, true, true>(cp, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist, s_rep);
+}
+template <bool FAST, bool LP>
+__global__ __launch_bounds__(256) void sample_ctl_guide_given_kernel(const SampleGivenParams gp) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ int s_rep[SAMPLE_REP_RING];
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, LP, true, true, true, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie,
+                                                      hist, s_rep);
+}
 // what a launch with tables needs beyond its sibling's checks; the vector path also needs 16-byte aligned table rows (V = 2048: every row
 // of an aligned block is)
 static bool sample_bias_ok(const SampleCtlParams &p) { return p.ctl && p.bias_index && (p.bias_col == 0 || p.bias_col == 1); }
 static bool sample_bias_fast(const SampleCtlParams &p) { return (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0; }
 // and a launch with records: its ring, and the index table the BIAS path reads (tables themselves are optional)
 static bool sample_rep_ok(const SampleCtlParams &p) { return p.ctl && p.rep_ring && p.bias_index && (p.bias_col == 0 || p.bias_col == 1); }
+// and a guided launch: the scale table, and what the REP path reads (records of window 0 where the run brought none)
+static bool sample_guide_ok(const SampleCtlParams &p) { return p.guide_scale && p.rep && sample_rep_ok(p); }
 
 hipError_t launch_sample_ctl(const SampleCtlParams &p, hipStream_t stream) {
     if (!p.ctl || p.s.V < 1 || p.s.V > SAMPLE_CTL_MAX_V || (p.s.mode != TS_SAMPLE_UNIFORMS && p.s.mode != TS_SAMPLE_PHILOX)) return hipErrorInvalidValue;
     const long ls = p.s.logit_stride ? p.s.logit_stride : (long)p.s.V;
     const bool fast = p.s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s.logits) & 15) == 0;
+    if (p.guide_role) {
+        if (!sample_guide_ok(p)) return hipErrorInvalidValue;
+        const bool bfast = fast && sample_bias_fast(p);
+        if (p.logprob) {
+            if (bfast) hipLaunchKernelGGL((sample_ctl_guide_kernel<true, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((sample_ctl_guide_kernel<false, true>), dim3(p.s.B), dim3(256), 0, stream, p);
+        } else if (bfast) {
+            hipLaunchKernelGGL((sample_ctl_guide_kernel<true, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((sample_ctl_guide_kernel<false, false>), dim3(p.s.B), dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.rep) {
         if (!sample_rep_ok(p)) return hipErrorInvalidValue;
         const bool bfast = fast && sample_bias_fast(p);
@@ -1858,7 +1984,7 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
     if (!p.rows || !p.given || s.V < 1) return hipErrorInvalidValue;
     if (s.mode != TS_SAMPLE_GREEDY && s.mode != TS_SAMPLE_UNIFORMS && s.mode != TS_SAMPLE_PHILOX) return hipErrorInvalidValue;
     if (!p.c.ctl) {
-        if (p.c.kept || p.c.bias || p.c.rep) return hipErrorInvalidValue;
+        if (p.c.kept || p.c.bias || p.c.rep || p.c.guide_role) return hipErrorInvalidValue;
         if (p.c.logprob) hipLaunchKernelGGL(sample_lp_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(sample_given_kernel, dim3(s.B), dim3(256), 0, stream, p);
         return hipGetLastError();
@@ -1866,6 +1992,19 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
     if (s.V > SAMPLE_CTL_MAX_V || s.mode == TS_SAMPLE_GREEDY) return hipErrorInvalidValue;
     const long ls = s.logit_stride ? s.logit_stride : (long)s.V;
     const bool fast = s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(s.logits) & 15) == 0;
+    if (p.c.guide_role) {
+        if (!sample_guide_ok(p.c)) return hipErrorInvalidValue;
+        const bool bfast = fast && sample_bias_fast(p.c);
+        if (p.c.logprob) {
+            if (bfast) hipLaunchKernelGGL((sample_ctl_guide_given_kernel<true, true>), dim3(s.B), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((sample_ctl_guide_given_kernel<false, true>), dim3(s.B), dim3(256), 0, stream, p);
+        } else if (bfast) {
+            hipLaunchKernelGGL((sample_ctl_guide_given_kernel<true, false>), dim3(s.B), dim3(256), 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((sample_ctl_guide_given_kernel<false, false>), dim3(s.B), dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.c.rep) {
         if (!sample_rep_ok(p.c)) return hipErrorInvalidValue;
         const bool bfast = fast && sample_bias_fast(p.c);

@@ -342,7 +342,7 @@ class GatedPixelCNN(NativeModule):
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
             want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None, given_keep=None,
-            style=None, code_bias=None, repeat=None):
+            style=None, code_bias=None, repeat=None, guide=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
@@ -381,7 +381,21 @@ class GatedPixelCNN(NativeModule):
         `window` rows of the same column loses presence + frequency * c ahead of the sampling rule (`sampling.penalised`).
         TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only.  Goes through the mixed entry with equal lengths (`ts_pixelcnn_generate_mixed_repeat`):
         not with want_logits or pre_codes.  ValueError naming the clip for a bad record, before any device work.  None (the default): no
-        return value and no launch changes."""
+        return value and no launch changes.
+        guide: GUIDANCE against a second conditioning (`_lib.guide_entries`; talkshow_hip.h, "guidance"): one dict for all clips or a list
+        with, per clip, None or {"scale": s, "aud_rows": (H, aud_dim) array or None, "id": int or None, "style": row / track or None}; an
+        absent audio, id or style is the clip's own.  The clip is decoded under its own conditioning p while a SHADOW slot behind it runs
+        the same code history under the second conditioning q; at every position the logits become l' = l + scale * (l - l_q)
+        (`sampling.guided`) ahead of every other control.  scale > 0 pushes away from q, -0.5 is the geometric mean of the two
+        distributions, 0 the call without the keyword.  The shadows are dropped from what is returned.  TS_SAMPLE_UNIFORMS /
+        TS_SAMPLE_PHILOX only.  Goes through the mixed entry with equal lengths (`ts_pixelcnn_generate_guided`): not with want_logits
+        or pre_codes.  ValueError naming the clip for a wrong key, shape or scale, before any device work.  None (the default): no return
+        value and no launch changes."""
+        if guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide)):      # a list of None only is no guidance
+            if not self.bh_model:
+                raise NotImplementedError("guidance exists for the bh_model=True chain (ts_pixelcnn_generate_guided), not for the single-stack form")
+            if want_logits or pre_codes is not None:
+                raise ValueError("run: guidance goes through the mixed entry, which takes no logits output and no pre_codes")
         if repeat is not None:
             if not self.bh_model:
                 raise NotImplementedError("a repetition penalty exists for the bh_model=True chain (ts_pixelcnn_generate_mixed_repeat), not for the single-stack form")
@@ -428,6 +442,11 @@ class GatedPixelCNN(NativeModule):
             ctl, n_ctl = _lib.sampling_table(sampling, B, self.input_dim, mode)
         btab, bidx = _lib.code_bias_block(code_bias, B, self.input_dim, who="run", mode=mode)   # ValueError before any device work
         rtab, n_rep = _lib.repeat_table(repeat, B, self.input_dim, who="run", mode=mode)       # too
+        gent = _lib.guide_entries(guide, B, who="run", audio_key="aud_rows", mode=mode, n_classes=self.n_classes, rows=[H] * B)   # and the guide entries
+        for b, e in enumerate(gent or ()):
+            if e is not None and e["audio"] is not None:
+                if aud_rows is None or tuple(np.shape(e["audio"])) != (H, aud_rows.shape[2]):
+                    raise ValueError(f"run: guide of clip {b}: aud_rows must have the clip's own shape ({H}, {self.aud_dim}), got {tuple(np.shape(e['audio']))}")
         kblock = None
         if given_keep is not None:   # ValueError before any device work, too (without given rows there is nothing to select from)
             kblock = _lib.given_keep_block(given_keep, _lib.given_counts(given, None, B), [H] * B, who="run")
@@ -441,6 +460,10 @@ class GatedPixelCNN(NativeModule):
         if label.numel() != B:
             raise ValueError(f"label must hold 1 or B={B} class indices, got {label.numel()}")
         sblock = _lib.style_block(style, [H] * B, self.n_classes, who="run", ids=label)   # ValueError before any device work
+        if gent is not None:      # the slots of the guided pass: every shadow directly behind its primary
+            src, shadow, gtab, gscale = _lib.guide_layout(range(B), gent)
+            need_ids = sblock is None and any(e is not None and e["style"] is not None for e in gent)
+            sblock = _lib.guide_style_block(sblock, src, shadow, gent, [H] * B, self.n_classes, label.cpu().numpy() if need_ids else None, who="run")
         if mode == _lib.TS_TEACHER_FORCED:
             codes = torch.as_tensor(codes, dtype=torch.int64, device=dev).contiguous()
             if lp is not None:
@@ -463,6 +486,10 @@ class GatedPixelCNN(NativeModule):
                 self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, W, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0, _lib.stream_ptr()))
             return codes, logits
+        if gent is not None:
+            return self._run_guided(label, aud_rows, mode, uniforms, seed, clip_index0, lp, ctl, n_ctl, block if given is not None else None,
+                                    table if given is not None else None, kblock if given is not None else None, sblock, btab, bidx, rtab,
+                                    n_rep, gent, src, shadow, gtab, gscale)
         if given is not None or sblock is not None or btab is not None or rtab is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
             i32p = C.POINTER(C.c_int32)
             lens = np.full(B, 4 * H, np.int32)
@@ -494,6 +521,59 @@ class GatedPixelCNN(NativeModule):
         else:
             _lib.check(_lib.load().ts_pixelcnn_generate_ctl(*args, ctl, n_ctl, _lib.stream_ptr()))
         return codes, logits
+
+    def _run_guided(self, label, aud_rows, mode, uniforms, seed, clip_index0, lp, ctl, n_ctl, block, table, kblock, sblock, btab, bidx, rtab,
+                    n_rep, gent, src, shadow, gtab, gscale):
+        """The guided branch of `run`: every validated per-clip block (slot order = submission order here) is re-indexed to the slots of
+        the guided pass (`_lib.guide_layout`: slot s copies original slot src[s]; a shadow then takes its own audio and id, brings no
+        given rows and no table), one call of `ts_pixelcnn_generate_guided`, and the primaries' rows are returned."""
+        dev = aud_rows.device
+        B, H, _ = aud_rows.shape
+        i32p = C.POINTER(C.c_int32)
+        Bx = len(src)
+        sidx = np.asarray(src, np.int64)
+        shadows = np.asarray(shadow, bool)
+        sdev = upload(sidx, dev)
+        aud_x = aud_rows.index_select(0, sdev).contiguous()
+        label_x = label.index_select(0, sdev).contiguous()
+        for s in np.flatnonzero(shadows):
+            e = gent[src[s]]
+            if e["audio"] is not None:
+                aud_x[s] = _dev_f32(e["audio"], dev)
+            if e["id"] is not None:
+                label_x[s] = e["id"]
+        lens = np.full(Bx, 4 * H, np.int32)
+        lens_dev = upload(lens, dev)
+        clip_index = upload(sidx + int(clip_index0), dev)      # a primary keeps Philox subsequence clip_index0 + b; shadows draw nothing
+        u_x = None if uniforms is None else uniforms.index_select(0, sdev).contiguous()
+        codes = torch.zeros((Bx, H, 2), dtype=torch.int64, device=dev)
+        lp_x = None if lp is None else torch.empty((Bx, H, 2), dtype=torch.float32, device=dev)
+        ctl, n_ctl = _lib.expand_records(ctl, n_ctl, src)
+        rtab, n_rep = _lib.expand_records(rtab, n_rep, src)
+        if block is not None:
+            block, table = block[sidx], np.where(shadows, 0, table[sidx]).astype(np.int32)
+            kblock = None if kblock is None else kblock[sidx]
+        if btab is not None:
+            bidx = np.where(shadows, -1, bidx[sidx]).astype(np.int32)
+        fixed = (self.handle(), _lib.dptr(label_x), _lib.dptr(aud_x), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), Bx, H, mode,
+                 _lib.dptr(u_x), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes))
+        block_dev = upload(block, dev) if block is not None else None
+        keep_dev = upload(kblock, dev) if kblock is not None else None
+        style_dev = upload(sblock, dev) if sblock is not None else None
+        bias_dev = upload(btab, dev) if btab is not None else None
+        _lib.pixelcnn_mixed_call(
+            fixed, ctl=ctl, n_ctl=n_ctl, logprob=_lib.dptr(lp_x), given=_lib.dptr(block_dev), given_rows=table.ctypes.data_as(i32p) if block is not None else None,
+            keep=_lib.dptr(keep_dev), style=_lib.dptr(style_dev), style_rows=int(sblock.shape[1]) if sblock is not None else 0,
+            bias=_lib.dptr(bias_dev), n_bias=int(btab.shape[0]) if btab is not None else 0, bias_index=bidx.ctypes.data_as(i32p) if btab is not None else None,
+            rep=rtab, n_rep=n_rep, guide=gtab.ctypes.data_as(i32p), guide_scale=_lib.fptr(gscale))
+        prim = upload(np.flatnonzero(~shadows).astype(np.int64), dev)
+        codes = codes.index_select(0, prim)
+        if lp is None:
+            return codes, None
+        if isinstance(lp, str):
+            return codes, None, lp_x.index_select(0, prim)
+        lp.copy_(lp_x.index_select(0, prim))
+        return codes, None, lp
 
     def score(self, label, aud_rows, codes, logprobs=True):
         """Teacher-forced scoring: the log-probability of every GIVEN code under the model, label / aud_rows (B,H,aud_dim) as for `run`,

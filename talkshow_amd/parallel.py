@@ -140,7 +140,7 @@ def whole_body_local(body, face, mfcc, ids, wav, face_ids, mode=None, seed=0, cl
 
 
 def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, clip_index0=0, stand=False, overlap=True, sampling=None,
-                     given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None):
+                     given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
     """Whole-body generation from RECORDINGS of different lengths, in one pass: wavs = list of (N_b,) sample arrays / tensors at ONE source
     rate `sr` (a host with several rates groups by rate), ids = one body speaker index per recording (or one for all), face_ids
     (B, 4) / (1, 4) one-hot or zero rows or None -> list of (frames_b, 265) device tensors in submission order, frames_b =
@@ -167,7 +167,10 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     code_bias: which codes the BODY half of a recording may use — one (2, V) table for all, or per recording None, a (2, V) table or a
     {"body", "hand"} dict; -inf bans a code (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_bias`).  The face half has no codes.
     repeat: a repetition penalty over a window of earlier codes for the BODY half — one (window, presence, frequency) record or dict for
-    all, or a list with one per recording (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_repeat`)."""
+    all, or a list with one per recording (`TrainWrapper.generate_clips`; `ts_body_pixel_infer_mixed_repeat`).
+    guide: guidance of the BODY half against a second conditioning — one dict for all or per recording None or {"scale", "wav" (N_b,)
+    samples at `sr`, "id", "style"} (`TrainWrapper.generate_clips_from_wav`; `ts_body_pixel_infer_guided`).  The shadows are rows of
+    the body pass only: the face half runs on the recordings themselves."""
     import ctypes as C
 
     import numpy as np
@@ -222,6 +225,16 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
         code_bias = _lib.code_bias_block(code_bias, B, body.generator.input_dim, order, who="whole_body_clips", mode=mode)
     if repeat is not None:         # and the records
         repeat = _lib.repeat_table(repeat, B, body.generator.input_dim, order, who="whole_body_clips", mode=mode)
+    grows = None
+    if guide is not None:      # rows of submitted recording i, for the entries' style tracks
+        grows = [0] * B
+        for k, i in enumerate(order):
+            grows[i] = int(tab["mfcc_rows"][k]) // 4
+    gent = _lib.guide_entries(guide, B, who="whole_body_clips", audio_key="wav", mode=mode, n_classes=body.num_classes, rows=grows)      # and the guide entries
+    for b, e in enumerate(gent or ()):
+        if e is not None and e["audio"] is not None and tuple(np.shape(e["audio"])) != (int(ns[b]),):
+            raise ValueError(f"whole_body_clips: guide of clip {b}: wav must have the recording's own sample count ({int(ns[b])},), got "
+                             f"{tuple(np.shape(e['audio']))}")
     dev = body.generator._dev()
     # every host table of the pass, before the first launch: sample counts and the padded block, 16 kHz counts, face and body frame counts
     wav, ns_host, ns_dev = pad_recordings(wavs, ns, order, dev)
@@ -237,8 +250,14 @@ def whole_body_clips(body, face, wavs, sr, ids, face_ids, mode=None, seed=0, cli
     if overlap:
         side.wait_stream(cur)
     with torch.cuda.stream(side):
-        _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, sampling_table=sampling,
-                                               given=given, given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
+        pieces = dict(sampling_table=sampling, given=given, given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat)
+        if gent is None:
+            _, poses, _ = body.infer_padded_wav(wav, ns_host, ns_dev, sr, ids_sorted, clip_index, mode, seed, lens_dev=rows_dev, **pieces)
+        else:      # the body half alone runs the shadows' rows; its poses come back as the recordings' own B rows
+            bwav, bns, bns_dev, bids, bclip, pieces, prim = body.guide_wav_rows(gent, order, wav, ns_host, ids_sorted, clip_index, sr, 30, pieces,
+                                                                                  "whole_body_clips")
+            _, poses, _ = body.infer_padded_wav(bwav, bns, bns_dev, sr, bids, bclip, mode, seed, **pieces)
+            poses = poses.index_select(0, upload(prim.astype(np.int64), dev))
     i32p = C.POINTER(C.c_int32)
     if int(sr) == 16000:
         wav16 = wav

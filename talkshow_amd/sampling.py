@@ -1,6 +1,7 @@
 """Numpy twin of the sampler with per-clip controls (`csrc/vq.hip::sample_ctl_kernel`; the rule: `include/talkshow_hip.h`, ts_sampling,
 steps 1-5, "code bias": step 0 and the kept-set sentence, `biased` / `keep_mask_bias` / `sample_bias` below, and "repetition penalty":
-step 0b, `repeat_counts` / `penalised` / `sample_repeat` / `decode_repeat` below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
+step 0b, `repeat_counts` / `penalised` / `sample_repeat` / `decode_repeat` below, and "guidance": the rule ahead of step 0 and the host check,
+`guided` / `guide_roles` / `sample_guide` below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
 bit for bit, so tests compare indices and kept sets for equality.  A record is (temperature, top_p, top_k), `_lib.sampling_record`'s form.
 
 The kept set is written here from its DEFINITION (sort the row, cumulative integer masses in rank order); the kernel finds the same set by
@@ -406,6 +407,99 @@ def decode_repeat(logits, u, record, repeat, bias=None, given=None, forced=None)
             i, _, l, _ = sample_repeat(logits[r, j][None], [u[r, j]], record, repeat, hist, 2 * r + j, tables, [0], j, g, f)
             codes[r, j], lps[r, j] = i[0], l[0]
     return codes, lps
+
+
+# ---- guidance (include/talkshow_hip.h, "guidance"; csrc/vq.hip: sample_ctl_body<., ., ., true, true, GUIDE = true>) ---------------------------
+
+GUIDE_MAX_SCALE = 1e4
+
+
+def guided(row_p, row_q, scale):
+    """The rule: d = l_p - l_q, t = scale * d, l' = l_p + t — three float32 operations, each rounded (numpy.float32 arithmetic: no fused
+    multiply-add).  scale = 0 and row_q equal to row_p return row_p's values (a -0 may become +0)."""
+    p = np.asarray(row_p, F32).reshape(-1)
+    q = np.asarray(row_q, F32).reshape(-1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = (p - q).astype(F32)
+        t = (F32(scale) * d).astype(F32)
+        return (p + t).astype(F32)
+
+
+def guide_roles(guide, B, scale=None, lens=None):
+    """`ts_guide_check` and the role table `SamplerTables::build` derives, restated: guide (B,) the shadow's slot of every slot or -1,
+    scale (B,) (None: not checked), lens (B,) the slots' lengths in frames (None: not checked) -> (B,) int32 roles: -1 plain, g >= 0 a primary
+    whose shadow is slot g, -2 a shadow.  ValueError with the library's text (without its "ts_guide_check: " prefix) for an index outside
+    [-1, B), a slot that names itself, a shadow named twice, a shadow that is itself guided, unequal lengths, a NaN, an infinity or
+    |scale| > 1e4 — found in the library's order."""
+    B = int(B)
+    guide = [int(g) for g in np.asarray(guide).reshape(-1)]
+    if len(guide) != B or B < 1:
+        raise ValueError("bad argument")
+    named = [-1] * B
+    for b, g in enumerate(guide):
+        if g < -1 or g >= B:
+            raise ValueError(f"clip {b}: the shadow index is {g}, not -1 (none) or in [0, {B})")
+        if g < 0:
+            continue
+        if g == b:
+            raise ValueError(f"clip {b} names itself as its shadow")
+        if named[g] >= 0:
+            raise ValueError(f"clip {b}: its shadow, slot {g}, is already the shadow of clip {named[g]}")
+        named[g] = b
+    roles = np.full(B, -1, np.int32)
+    for b, g in enumerate(guide):
+        if g < 0:
+            continue
+        if guide[g] >= 0:
+            raise ValueError(f"clip {b}: its shadow, slot {g}, is itself guided (a shadow draws nothing)")
+        if named[b] >= 0:
+            raise ValueError(f"clip {b} is guided and is the shadow of clip {named[b]} (a shadow draws nothing)")
+        if lens is not None and int(lens[g]) != int(lens[b]):
+            raise ValueError(f"clip {b}: its length of {int(lens[b])} frames differs from the {int(lens[g])} frames of its shadow, slot {g}")
+        if scale is not None:
+            with np.errstate(over="ignore"):
+                sc = F32(scale[b])
+            if np.isnan(sc):
+                raise ValueError(f"clip {b}: the scale is NaN")
+            if np.isinf(sc):
+                raise ValueError(f"clip {b}: the scale is infinite")
+            if abs(sc) > F32(GUIDE_MAX_SCALE):
+                raise ValueError(f"clip {b}: the scale exceeds 1e4 in magnitude")
+        roles[b] = g
+        roles[g] = -2
+    return roles
+
+
+def sample_guide(logits, u, records, guide, scale, repeat=None, history=None, position=0, bias=None, index=None, column=0, given=None,
+                 forced=None):
+    """One launch of the samplers under guidance, restated (`ts_op_sample_guide`): guide (B,) the shadow's row of every row or -1, scale
+    (B,); everything else as `sample_repeat` takes it (repeat None: no records, history unused) -> (idx (B,) int64, kept (B,V) bool, logprob
+    (B,) float32, ring (B,64) int32).  A primary runs `sample_repeat`'s row on l' = guided(l, l of its shadow, scale) under its own
+    record, table, history and forced flag; its shadow's idx, kept and logprob are copies of the primary's and its ring holds its history
+    and nothing else; a plain row is `sample_repeat`'s row."""
+    logits = np.asarray(logits, F32)
+    B, V = logits.shape
+    roles = guide_roles(guide, B, scale)
+    eff = logits.copy()
+    rep = _per_row((0, 0.0, 0.0) if repeat is None else repeat, B, 3)
+    rep = [tuple(r) for r in rep]
+    f = None if forced is None else [bool(x) for x in forced]
+    for b in range(B):
+        if roles[b] >= 0:
+            eff[b] = guided(logits[b], logits[roles[b]], scale[b])
+        elif roles[b] == -2:      # draws nothing, takes nothing, writes no ring
+            rep[b] = (0, 0.0, 0.0)
+            if f is not None:
+                f[b] = False
+    r = int(position) >> 1
+    if history is None:
+        history = np.full((B, min(r, REPEAT_MAX_WINDOW)), -1, np.int64)
+    idx, kept, lp, ring = sample_repeat(eff, u, records, rep, history, position, bias, index, column, given, f)
+    for b in range(B):
+        if roles[b] >= 0:
+            g = int(roles[b])
+            idx[g], kept[g], lp[g] = idx[b], kept[b], lp[b]
+    return idx, kept, lp, ring
 
 
 def keep_forced(G, keep, r, j):
