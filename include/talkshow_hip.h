@@ -803,7 +803,9 @@ int ts_repeat_check(const ts_repeat *rep_host, int n, int V);
  * The entries: ts_pixelcnn_generate_guided, ts_body_pixel_infer_guided and ts_body_pixel_infer_guided_poses are ts_pixelcnn_generate_mixed_repeat,
  * ts_body_pixel_infer_mixed_repeat and ts_body_pixel_infer_mixed_poses_repeat plus `const int32_t *guide_host, const float *guide_scale_host` ahead of the stream,
  * (B,) each in slot order.  guide_host == NULL: the _repeat entry, launch for launch.
- * Out of scope: the streaming sessions; ts_pixelcnn_v_*; the single-stack form; the scoring entries (a pass whose rows are all given, with
+ * The chain's streaming sessions take guidance at slot level ("session pairs" below), the seamless body sessions at clip level
+ * (ts_body_stream_open_guided, "seamless sessions" below).
+ * Out of scope: ts_pixelcnn_v_*; the single-stack form; the scoring entries (a pass whose rows are all given, with
  * a log-probability output, scores under guidance already); more than one shadow per clip. */
 int ts_pixelcnn_generate_guided(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
                                      const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
@@ -1179,6 +1181,52 @@ int ts_pixelcnn_stream_save(ts_pixelcnn_stream *st, const int32_t *slots_host, i
 int ts_pixelcnn_stream_load(ts_pixelcnn_stream *st, const int32_t *slots_host, int n, const float *state_dev, int n_states,
                             const int32_t *state_index_host, const ts_slot_info *info_host, const int64_t *clip_index_host, void *stream);
 
+/* ---- session pairs: "guidance" at slot level in a streaming session ----------------------------------------------------------------
+ * A session of S slots may hold PAIRS (b, g): slot g is the SHADOW of slot b under the rule of "guidance" above.  g has its own audio rows
+ * (aud_dev[g] of every step) and its own label or style row (from open, restart or load); it draws nothing and receives every token, code
+ * and log-probability b writes.  A paired clip's codes and log-probabilities equal those of ts_pixelcnn_generate_guided on the two slots
+ * alone, bit for bit, whatever the chunking, under every piece of ts_pixelcnn_stream_step_ctl; every other slot has the bits of the
+ * session without the pair.  A primary draws under its own clip index and row origin; the shadow's are never read.
+ * WHEN A PAIR MAY FORM.  The shadow's row cache must hold b's code history under q from the clip's row 0, so a pair is declared
+ *   - at session row 0,
+ *   - behind the call that restarts BOTH slots, or
+ *   - behind the call that loads BOTH slots from states of equal clip rows,
+ * and ahead of the next step.  Every other attempt is refused, naming the slots and the rows.  Restarting or loading one slot of a pair
+ * without the other is refused ("slot 3 is paired with slot 7: list both"); a restart or a load that lists both DISSOLVES the pair unless a
+ * ts_pixelcnn_stream_pair behind it declares it again.  There is no pairing and no un-pairing in the middle of a clip: scale 0 is the off
+ * switch (the codes of the session without the pair).  A save reads a paired slot like any other; pairs are not part of a state: a guided
+ * clip moves by saving both slots and loading both, then declaring the pair.
+ * Roles and scales are kernel arguments, never in a graph key.  Each pair has a stored scale; ts_pixelcnn_stream_step_guided may bring
+ * others for its step.  EVERY step entry of a session with pairs runs the guided sampler family (bit 8 of the sixth key field, with bit 7
+ * once the session has restarted or loaded) on neutral records where it brought none, ts_guide_check last among its checks; greedy mode
+ * is then refused as in a pass (top_k = 1 is the greedy guided decode).  One graph per (Hc, buffer phase, kind of sampler).  A shadow has
+ * no repetition history of its own: the primary's ring is the only one read or written.  So a saved SHADOW's state records no history
+ * (hist = -1): a load that swaps the roles — the old shadow's state into the new primary — starts that clip's penalty from an empty
+ * history at the load, which is NOT what the one-shot pass under the same records gives.  Load the primary's state into the primary
+ * where a repetition penalty runs.  A session without pairs issues exactly the
+ * launches it did and finds the graphs it had.
+ * ts_pixelcnn_stream_pair: n pairs (primary_host[i], shadow_host[i]) with stored scales scale_host[i]; host tables only, nothing is
+ * launched; all or none.  ts_pixelcnn_stream_pairs: the session's table into guide_out (S,) as ts_guide_check takes it (the shadow's slot
+ * of every primary, else -1); returns the number of pairs.  ts_pixelcnn_stream_step_guided: ts_pixelcnn_stream_step_ctl plus
+ * guide_scale_host (S,), read at primaries only; NULL: the stored scales.  A NaN, an infinity or |scale| > 1e4 is refused naming the slot.
+ * ts_pixelcnn_stream_pair_check, host only, holds the rule (the entries call it; talkshow_amd/streaming.py restates it as SlotPairs):
+ * S slots at session row `rows`; guide_host (S,) the pair table; clip_rows_host (S,) the rows of every slot's current clip; fresh_host (S,)
+ * per slot the serial (> 0) of the restart or load that listed it if no step was run since, else 0.  shadow_host != NULL: the declaration
+ * of n pairs — refused for a slot out of range, a slot that names itself, a slot listed twice, a slot already paired, rows > 0 without one
+ * call that listed both, unequal clip rows, a bad scale.  shadow_host == NULL: a restart or load listing the n slots of primary_host —
+ * refused where it lists one slot of a pair without the other. */
+int ts_pixelcnn_stream_pair(ts_pixelcnn_stream *st, const int32_t *primary_host, const int32_t *shadow_host, const float *scale_host, int n);
+int ts_pixelcnn_stream_pairs(const ts_pixelcnn_stream *st, int32_t *guide_out);
+int ts_pixelcnn_stream_step_guided(ts_pixelcnn_stream *st, const float *aud_dev, int Hc, int mode, const float *uniforms_dev,
+                                   uint64_t seed, int64_t clip_index0, int64_t *codes_dev,
+                                   const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                   const int64_t *given_dev, const int32_t *given_rows_host,
+                                   const float *style_dev,
+                                   const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                   const ts_repeat *rep_host, int n_rep, const float *guide_scale_host, void *stream);
+int ts_pixelcnn_stream_pair_check(int S, int64_t rows, const int32_t *guide_host, const int64_t *clip_rows_host, const int32_t *fresh_host,
+                                  const int32_t *primary_host, const int32_t *shadow_host, const float *scale_host, int n);
+
 /* ---- seamless sessions ---------------------------------------------------------------------------------------------------
  * A body session fed MFCC chunks of ANY length that returns, over its pushes and one flush, the codes and poses ts_body_pixel_infer
  * returns for the concatenated audio, bit for bit (same mode, seed and clip_index0) — where a plain session (ts_audioenc_forward,
@@ -1223,6 +1271,43 @@ int ts_body_stream_flush(ts_body_stream *st, int mode, const float *uniforms_dev
                          const float *style_dev,
                          const float *bias_dev, int n_bias, const int32_t *bias_index_host,
                          const ts_repeat *rep_host, int n_rep, void *stream);
+/* Guided sessions: "guidance" at clip level in a seamless session ("session pairs" above, "guidance").  The session's B clips may have
+ * n_shadow SHADOWS, at most one per clip.  The chain session behind it has S = B + n_shadow slots: the clips in slots 0 .. B-1 (their
+ * Philox clip indices stay clip_index0 + b), shadow k in slot B + k, paired with clip shadow_of[k] at row 0 under scale_host[k].  The audio
+ * encoder runs on E = B + n_a MFCC streams, n_a the shadows with audio of their own (enc_of[k] = its stream, numbered B, B + 1, ... in
+ * shadow order; -1: the shadow hears its clip's audio and gets the clip's ENCODED rows: nothing is encoded twice).  One small launch
+ * (stream_spread_rows_kernel) writes the kept audio rows of stream map[s] to chain slot s.  MFCC tails, the encoder window and its
+ * output are sized for E, the chain for S, the code ring, the latent columns and the decoders for B: ts_body_stream_state_bytes stays
+ * constant.  Over its pushes and one flush the session returns, for the B clips, the codes, poses and log-probabilities of
+ * ts_body_pixel_infer_guided on the whole audio, bit for bit.
+ *   ids_dev (S,)                 labels of the chain's slots: the clips', then the shadows'
+ *   shadow_of, enc_of (n_shadow,) host: strictly increasing clips; -1 or the next stream of its own
+ *   shadow_style_dev             (n_shadow, NC) weight rows of the shadows on the device, or NULL (the labels).  Given: EVERY shadow takes
+ *                                its row (a one-hot row is the label bit for bit), written as a restart at row 0 writes it, on `stream`
+ *   scale_host (n_shadow,)       the pairs' stored scales
+ * The session's calls are ts_body_stream_push_guided / _flush_guided: the existing entries with mfcc_dev (E, t, 64), with uniforms_dev,
+ * codes_dev, logprob_dev, given_dev and every per-clip table for the S slots (the clips first: the clips' rows of the (S, n, 2) code
+ * block are its first B * n entries, and only those reach the decoders), poses_dev (B, ., pose_dim), plus guide_scale_host (S,), read at
+ * primaries only; NULL: the stored scales.  The plain entries are refused on a guided session and the guided ones on a plain session; a
+ * refused call moves no counter; the broken-session rule is as above.  A session without shadows goes through the existing entries
+ * unchanged.  No restart, save or load, as for every seamless session. */
+int ts_body_stream_open_guided(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const int64_t *ids_dev, int B,
+                               int n_shadow, const int32_t *shadow_of, const int32_t *enc_of, const float *shadow_style_dev,
+                               const float *scale_host, int max_chunk_frames, void *stream, ts_body_stream **out);
+int ts_body_stream_push_guided(ts_body_stream *st, const float *mfcc_dev, int t, int mode, const float *uniforms_dev, uint64_t seed,
+                               int64_t clip_index0, int64_t *codes_dev, float *poses_dev,
+                               const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                               const int64_t *given_dev, const int32_t *given_rows_host,
+                               const float *style_dev,
+                               const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                               const ts_repeat *rep_host, int n_rep, const float *guide_scale_host, void *stream);
+int ts_body_stream_flush_guided(ts_body_stream *st, int mode, const float *uniforms_dev, uint64_t seed, int64_t clip_index0,
+                                int64_t *codes_dev, float *poses_dev,
+                                const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                const int64_t *given_dev, const int32_t *given_rows_host,
+                                const float *style_dev,
+                                const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                const ts_repeat *rep_host, int n_rep, const float *guide_scale_host, void *stream);
 int64_t ts_body_stream_frames_in(const ts_body_stream *st);     /* MFCC frames received */
 int64_t ts_body_stream_code_rows(const ts_body_stream *st);     /* code rows finalised */
 int64_t ts_body_stream_pose_frames(const ts_body_stream *st);   /* pose frames returned */

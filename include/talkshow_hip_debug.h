@@ -471,6 +471,9 @@ int ts_debug_stream_emit(const int64_t *codes, int64_t *ring, int64_t *lat_body,
 /* dst (B, n, W) = rows [r0, r0 + n) of every clip of src (B, R, W); r0 + n <= R.  16-byte copies where W % 4 == 0 and both pointers are 16-byte
  * aligned, word by word otherwise: the same bits either way. */
 int ts_debug_stream_keep_rows(const float *src, float *dst, int B, int R, int r0, int n, int W, void *stream);
+/* stream_spread_rows_kernel on its own: dst (S, n, W) = rows [r0, r0 + n) of stream map_host[s] of src (E, R, W); W a multiple of 4, both
+ * blocks 16-byte aligned; map_host (S,) with values in [0, E), checked here.  Waits for the launch. */
+int ts_debug_stream_spread_rows(const float *src, float *dst, const int32_t *map_host, int S, int E, int R, int r0, int n, int W, void *stream);
 
 /* ---- the glue kernels of the VQ and PixelCNN passes (csrc/vq.hip) ----
  * Test aids: ONE call of the production launcher each on `stream`, device pointers the caller owns throughout; nothing is allocated or

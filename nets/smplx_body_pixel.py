@@ -839,7 +839,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return output
 
     def open_stream(self, id, B, max_frames, *, seamless=False, sampling=None, style=None, code_bias=None, repeat=None, wav_sr=None,
-                    wav_db="running", max_samples=None, fps=30):
+                    wav_db="running", max_samples=None, fps=30, guide=None):
         """Long-audio / continuity generation: a session that is fed MFCC chunks and returns the poses of
         each chunk, every chunk continuing the PixelCNN row cache of the ones before it (`ts_pixelcnn_stream_*`) — the
         reference's `infer(..., pre_latents, pre_audio)` chain (`:291-304`) for any number of chunks, at a cost per chunk
@@ -874,23 +874,32 @@ class TrainWrapper(TrainWrapperBaseClass):
         wav_db="running" clamps each MFCC row at (the maximum so far - 80 dB); wav_db = the recordings' maxima (`MFCC.peak_db(wav)`, (B,))
         makes the frames those of `MFCC(wav_sr)(wav)` bit for bit, and with seamless=True the poses those of `generate_batch` on them, for
         any chunking of the samples.  The slots of a wav-fed session share ONE SAMPLE CLOCK: `restart`, `save`, `load` and `fork` raise
-        NotImplementedError."""
+        NotImplementedError.
+
+        guide: GUIDANCE at clip level in a plain session (`BodyStream`; `talkshow_amd.streaming.BodyGuide`): per clip None or {"scale": s,
+        "id": int or None, "style": row or None, "audio": bool}; one dict serves all clips.  An absent id or style is the clip's own;
+        "audio": False (the default) means the shadow hears the clip's own audio (id or style guidance), True that every push brings the
+        shadow's MFCC chunk (`push(..., guide=[{"scale": s, "mfcc": (t, 64)}, ...])`).  Plain and seamless sessions take both kinds
+        (`ts_body_stream_open_guided`); a wav-fed session takes shadows WITHOUT audio of their own (the MFCC rows come from the B-slot
+        front end; "audio": True raises NotImplementedError naming the reason)."""
         if wav_sr is not None:
             from talkshow_amd.streaming import WavBodyStream
             return WavBodyStream(self, id, B, max_frames, seamless, wav_sr, wav_db=wav_db, max_samples=max_samples, fps=fps, sampling=sampling,
-                                 style=style, code_bias=code_bias, repeat=repeat)
+                                 style=style, code_bias=code_bias, repeat=repeat, guide=guide)
         if seamless:
             from talkshow_amd.streaming import SeamlessBodyStream
-            return SeamlessBodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
-        return BodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
+            return SeamlessBodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat, guide=guide)
+        return BodyStream(self, id, B, max_frames, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat, guide=guide)
 
     def generate_long(self, mfcc, ids, chunk_frames=240, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, sampling=None,
-                      style=None, code_bias=None, repeat=None):
+                      style=None, code_bias=None, repeat=None, guide=None):
         """`generate_batch` for audio of ANY length at memory bounded by the chunk: mfcc (B,T,64), ids (B,) or one for all -> codes
         (B,T//4,2), poses (B,4 (T//4),129), bit for bit what `generate_batch(mfcc, ids, mode=, uniforms=, seed=, clip_index0=, ...)` returns,
         through one seamless session (`open_stream(..., seamless=True)`) pushed chunk_frames at a time.  Only the results are as long as the
         audio (mfcc may live on the host: a chunk is uploaded when it is pushed).  uniforms: (B,T//4,2) for TS_SAMPLE_UNIFORMS.  sampling /
-        style (one weight row per clip) / code_bias / repeat: the keywords of `generate_batch` a session takes, for the whole clip."""
+        style (one weight row per clip) / code_bias / repeat: the keywords of `generate_batch` a session takes, for the whole clip.
+        guide: the keyword of `generate_batch` — one dict for all clips or per clip None or {"scale": s, "mfcc": (T, 64) or None, "id": ..,
+        "style": one weight row} — passed through to the session: a shadow's "mfcc" is whole-length audio, cut per chunk."""
         if len(mfcc.shape) != 3 or int(mfcc.shape[2]) != 64:
             raise ValueError(f"generate_long: mfcc must be (B, T, 64), got {tuple(mfcc.shape)}")
         B, T = int(mfcc.shape[0]), int(mfcc.shape[1])
@@ -904,7 +913,20 @@ class TrainWrapper(TrainWrapperBaseClass):
             mode = _lib.TS_SAMPLE_UNIFORMS
         if seed is None:
             seed = _fresh_seed() if mode == _lib.TS_SAMPLE_PHILOX else 0
-        session = self.open_stream(ids, B, chunk_frames, seamless=True, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
+        opened = shadow_mfcc = None
+        if guide is not None:                      # the entries a session is opened with, and the whole-length audio of the shadows that bring one
+            per = [guide] * B if isinstance(guide, dict) else list(guide)
+            if len(per) != B:
+                raise ValueError(f"generate_long: guide is one dict for all clips or a list with one entry per clip (B = {B})")
+            opened, shadow_mfcc = [], {}
+            for b, e in enumerate(per):
+                if isinstance(e, dict) and e.get("mfcc") is not None:
+                    if tuple(e["mfcc"].shape) != (T, 64):
+                        raise ValueError(f"generate_long: guide of clip {b}: mfcc must have the clip's own shape ({T}, 64), got {tuple(e['mfcc'].shape)}")
+                    shadow_mfcc[b] = e["mfcc"]
+                opened.append(dict({k: v for k, v in e.items() if k != "mfcc"}, audio=b in shadow_mfcc) if isinstance(e, dict) else e)
+        session = self.open_stream(ids, B, chunk_frames, seamless=True, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat,
+                                   guide=opened)
         codes, poses = [], []
         try:
             for f0 in list(range(0, T, chunk_frames)) + [None]:
@@ -913,6 +935,8 @@ class TrainWrapper(TrainWrapperBaseClass):
                 n, _ = session.plan(t, flush=f0 is None)
                 kw = dict(mode=mode, seed=seed, clip_index0=clip_index0, uniforms=None if uniforms is None else uniforms[:, r0:r0 + n],
                           return_codes=True)
+                if shadow_mfcc and f0 is not None:
+                    kw["guide"] = [{"mfcc": shadow_mfcc[b][f0:f0 + t]} if b in shadow_mfcc else None for b in range(B)]
                 p, c = session.flush(**kw) if f0 is None else session.push(mfcc[:, f0:f0 + t], **kw)
                 codes.append(c)
                 poses.append(p)
@@ -944,57 +968,177 @@ class TrainWrapper(TrainWrapperBaseClass):
 
 
 class BodyStream:
-    """See `TrainWrapper.open_stream`.  `push(mfcc_chunk (B,T,64)) -> poses (B, 4*(T//4), 129)` device tensor."""
+    """See `TrainWrapper.open_stream`.  `push(mfcc_chunk (B,T,64)) -> poses (B, 4*(T//4), 129)` device tensor.
 
-    def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None):
+    guide (talkshow_amd.streaming.BodyGuide; DESIGN.md §5, "session pairs"): per clip None or {"scale": s, "id": int or None, "style": row or
+    None, "audio": bool} — guidance at clip level.  The chain session then has S = B + n_g slots, the clips first and their shadows behind
+    them, paired (`PixelCNNStream`, `pairs=`); the audio encoder runs on the clips' chunks and on the chunks of the shadows that hear audio
+    of their own, the encoded rows are spread to the S slots by index, ONE step runs under the pairs and only the clips' rows are decoded.
+    A clip opened without a shadow cannot take one later: open a shadow (scale 0 is the off switch) wherever guidance may be wanted."""
+
+    def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None, guide=None):
+        from talkshow_amd.streaming import BodyGuide
         self.w, self.B = wrapper, int(B)
         if id is None:
             id = torch.tensor([0])
-        self.pix = wrapper.generator.open_stream(id, self.B, max(1, int(max_frames) // 4), sampling=sampling, style=style,
-                                                 code_bias=code_bias, repeat=repeat)
+        gen = wrapper.generator
+        self.g = g = BodyGuide(guide, self.B, gen.n_classes)
+        rows = max(1, int(max_frames) // 4)
         self.seed = _fresh_seed()          # one stream of random numbers per session unless push() is given a seed
+        if not g.shadow_of:
+            self.pix = gen.open_stream(id, self.B, rows, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
+            return
+        ids = _index_tensor(id, gen.n_classes, "speaker id", gen._dev()).cpu().numpy().reshape(-1)
+        if ids.size == 1 and self.B > 1:
+            ids = np.repeat(ids, self.B)
+        if ids.size != self.B:
+            raise ValueError(f"open_stream: id must hold 1 or B={self.B} speaker ids, got {ids.size}")
+        self.shadow_style = {}             # clip -> its shadow's weight row, where the entry brought one
+        labels = list(ids) + [ids[b] if g.entries[b]["id"] is None else g.entries[b]["id"] for b in g.shadow_of]
+        defaults = {k: self._spread(k, v) for k, v in (("sampling", sampling), ("style", None), ("code_bias", code_bias), ("repeat", repeat))}
+        self._style_default = style        # spread at every push: a shadow keeps its own conditioning under a session default
+        styled = [b for b in g.shadow_of if g.entries[b]["style"] is not None]
+        self.pix = gen.open_stream(np.asarray(labels, np.int64), g.S, rows, sampling=defaults["sampling"], code_bias=defaults["code_bias"],
+                                   repeat=defaults["repeat"], pairs=None if styled else g.pairs())
+        if styled:                         # a shadow's weight row is written as a restart at row 0 writes it; the pairs form behind it
+            for b in styled:
+                self.shadow_style[b] = np.asarray(g.entries[b]["style"], np.float32)
+            self.pix.restart([g.slot_of[b] for b in styled], style=[self.shadow_style[b] for b in styled], pairs=g.pairs())
+
+    def _spread(self, name, v):
+        """`BodyGuide.spread_kw`: a per-clip keyword of B entries as the S entries of the chain session."""
+        return self.g.spread_kw(name, v, self.shadow_style)
 
     @property
     def frames(self):
         return 4 * self.pix.rows
 
     def push(self, mfcc, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, uniforms=None, *, sampling=None, logprobs=False, given=None,
-             style=None, code_bias=None, repeat=None):
+             style=None, code_bias=None, repeat=None, guide=None):
         """The keywords are `PixelCNNStream.step`'s, for this chunk's code rows; with `logprobs` the return value is (poses, logprobs
-        (B, T//4, 2))."""
-        rows = self.w.audioencoder.forward_nlc(mfcc)                      # (B, T//4, 256), this chunk alone
-        out = self.pix.step(rows, mode=mode, uniforms=uniforms, seed=self.seed if seed is None else seed, clip_index0=clip_index0,
-                            sampling=sampling, logprobs=logprobs, given=given, style=style, code_bias=code_bias, repeat=repeat)
-        if isinstance(out, tuple):
-            return self.w._decode_pair(out[0]), out[1]
-        return self.w._decode_pair(out)
+        (B, T//4, 2)).  guide: None, a float for all guided clips, or a list with, per clip, None, a float or {"scale": s, "mfcc": (t, 64)}
+        (`BodyGuide.push`): the step's scales, and the MFCC chunk of every shadow opened with "audio": True.  A wrong key or shape, or an
+        entry on a clip opened without a shadow, raises ValueError naming the clip before any device work."""
+        g = self.g
+        if not g.shadow_of:
+            if guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide)):
+                g.push(guide, int(mfcc.shape[1]))      # raises: names the clip that was opened without a shadow
+            rows = self.w.audioencoder.forward_nlc(mfcc)                      # (B, T//4, 256), this chunk alone
+            out = self.pix.step(rows, mode=mode, uniforms=uniforms, seed=self.seed if seed is None else seed, clip_index0=clip_index0,
+                                sampling=sampling, logprobs=logprobs, given=given, style=style, code_bias=code_bias, repeat=repeat)
+            if isinstance(out, tuple):
+                return self.w._decode_pair(out[0]), out[1]
+            return self.w._decode_pair(out)
+        if int(mfcc.shape[0]) != self.B:
+            raise ValueError(f"session was opened for B={self.B}, got {int(mfcc.shape[0])}")
+        scales, chunks = g.push(guide, int(mfcc.shape[1]))
+        if scales is not None:
+            self.pix._pairs.step_scales(scales, who="push")
+        style = self._style_default if style is None else style
+        kw = {k: self._spread(k, v) for k, v in (("sampling", sampling), ("given", given), ("style", style), ("code_bias", code_bias),
+                                                 ("repeat", repeat), ("uniforms", uniforms))}
+        dev = self.w.generator._dev()
+        mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
+        if chunks:                                                            # the E streams: the clips, then the shadows that hear their own
+            mfcc = torch.cat([mfcc, torch.stack([torch.as_tensor(m, dtype=torch.float32, device=dev) for m in chunks])])
+        rows = self.w.audioencoder.forward_nlc(mfcc)                          # (E, T//4, 256)
+        rows = rows.index_select(0, torch.as_tensor(g.spread(), dtype=torch.int64, device=rows.device))      # (S, T//4, 256): plumbing
+        want_lp = logprobs is not None and logprobs is not False
+        out = self.pix.step(rows, mode=mode, seed=self.seed if seed is None else seed, clip_index0=clip_index0, logprobs=bool(want_lp),
+                            guide=scales, **kw)
+        codes = out[0] if want_lp else out
+        poses = self.w._decode_pair(codes[:self.B].contiguous())              # the clips' rows are the block's first B
+        if not want_lp:
+            return poses
+        lp = out[1][:self.B]
+        if torch.is_tensor(logprobs):
+            logprobs.copy_(lp)
+            lp = logprobs
+        return poses, lp
 
     @property
     def slot_rows(self):
         """`PixelCNNStream.slot_rows`: the code rows of every slot's current clip."""
-        return self.pix.slot_rows
+        return self.pix.slot_rows[:self.B]
 
-    def restart(self, slots, id=None, *, style=None, clip_indices=None):
+    def _unguided(self, slots, what):
+        for b in ([slots] if isinstance(slots, int) else list(slots)):
+            if self.g.entries[b] is not None if 0 <= b < self.B else False:
+                raise ValueError(f"{what}: clip {b} is guided: its state is two slots of the chain session (`session.pix.save([b, g])`, "
+                                 f"`load([b2, g2], state, pairs={{b2: g2}})`)")
+
+    def restart(self, slots, id=None, *, style=None, clip_indices=None, guide=None):
         """`PixelCNNStream.restart`: the listed slots begin new clips (speaker `id`, or a `style` row) with the next push.  A plain session
         runs the audio encoder and the VQ decoders on each chunk per clip, so nothing else carries over: a restarted slot's poses equal
         those of a fresh `open_stream(id, 1, ...)` pushed the same chunks (same seed, clip_index0 = its clip index).  A slot whose user
-        has left needs no call: push any audio rows for it and ignore its poses."""
-        self.pix.restart(slots, id, style=style, clip_indices=clip_indices)
+        has left needs no call: push any audio rows for it and ignore its poses.
+        guide: one entry per listed slot (the forms of `open_stream`): a guided clip restarts together with its shadow under the new
+        entry's id or style, and the pair is declared again under its scale.  A clip opened without a shadow cannot take one; a clip with
+        a shadow that restarts without an entry gets scale 0; "audio" stays as the clip was opened."""
+        g = self.g
+        if not g.shadow_of:
+            if guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide)):
+                b = ([slots] if isinstance(slots, int) else list(slots) or [0])[0]
+                if isinstance(guide, (list, tuple)) and len(guide) == len([slots] if isinstance(slots, int) else list(slots)):
+                    b = [c for c, e in zip([slots] if isinstance(slots, int) else list(slots), guide) if e is not None][0]
+                raise ValueError(f"restart: guide of clip {b}: the clip was opened without a shadow (open one wherever guidance may be wanted)")
+            self.pix.restart(slots, id, style=style, clip_indices=clip_indices)
+            return self
+        from talkshow_amd.streaming import BodyGuide, SlotClock
+        NC = self.w.generator.n_classes
+        slots, labels, styles, clips = SlotClock.check(self.B, NC, slots, id, style, clip_indices)
+        n = len(slots)
+        entries = BodyGuide.parse(guide, n, NC, who="restart")
+        new, pairs = {}, {}
+        all_slots, all_labels, all_styles, all_clips = list(slots), list(labels or [None] * n), list(styles or [None] * n), list(clips)
+        for i, b in enumerate(slots):
+            opened, e = g.entries[b], entries[i]
+            if opened is None:
+                if e is not None:
+                    raise ValueError(f"restart: guide of clip {b}: the clip was opened without a shadow (open one wherever guidance may be wanted)")
+                continue
+            if e is None:                  # the shadow restarts as the clip's twin, switched off
+                e = {"scale": 0.0, "id": None, "style": None, "audio": opened["audio"]}
+            elif e["audio"] != opened["audio"]:
+                raise ValueError(f"restart: guide of clip {b}: \"audio\" stays as the clip was opened ({opened['audio']})")
+            new[b] = e
+            all_slots.append(g.slot_of[b]), all_clips.append(g.slot_of[b])
+            if e["style"] is not None:
+                all_labels.append(None), all_styles.append(np.asarray(e["style"], np.float32))
+            elif e["id"] is not None:
+                all_labels.append(e["id"]), all_styles.append(None)
+            else:                          # the clip's own conditioning
+                all_labels.append(all_labels[i]), all_styles.append(all_styles[i])
+            pairs[b] = (g.slot_of[b], e["scale"])
+        has_style = any(v is not None for v in all_styles)
+        self.pix.restart(all_slots, all_labels if any(v is not None for v in all_labels) else None, style=all_styles if has_style else None,
+                         clip_indices=all_clips, pairs=pairs or None)
+        for b, e in new.items():
+            g.entries[b] = e
+            self.shadow_style.pop(b, None)
+            if e["style"] is not None:
+                self.shadow_style[b] = np.asarray(e["style"], np.float32)
+            elif e["id"] is None and styles is not None and styles[slots.index(b)] is not None:
+                self.shadow_style[b] = np.asarray(torch.as_tensor(styles[slots.index(b)]).cpu().numpy(), np.float32)
         return self
 
     def save(self, slots):
         """`PixelCNNStream.save`: the state of the listed slots' clips.  A plain session runs the audio encoder and the VQ decoders on each
-        chunk per clip, so the chain's slot state is all a clip carries between pushes."""
+        chunk per clip, so the chain's slot state is all a clip carries between pushes.  A guided clip is refused, naming it."""
+        self._unguided(slots, "save")
         return self.pix.save(slots)
 
     def load(self, slots, state, *, clip_indices=None):
-        """`PixelCNNStream.load`: the listed slots carry the saved clips on with the next push."""
+        """`PixelCNNStream.load`: the listed slots carry the saved clips on with the next push.  A guided clip is refused, naming it."""
+        self._unguided(slots, "load")
         self.pix.load(slots, state, clip_indices=clip_indices)
         return self
 
     def fork(self, src, dst_slots, *, clip_indices=None):
         """`PixelCNNStream.fork`: the listed slots carry slot `src`'s clip on, each under its own clip index (default: the source's, which
-        makes them its twins: the same poses for the same audio)."""
+        makes them its twins: the same poses for the same audio).  A guided clip is refused, naming it."""
+        self._unguided(src, "fork")
+        self._unguided(dst_slots, "fork")
         self.pix.fork(src, dst_slots, clip_indices=clip_indices)
         return self
 

@@ -180,6 +180,14 @@ SIGNATURES = {
     "ts_pixelcnn_stream_save": (_i, [_vp, C.POINTER(C.c_int32), _i, _vp, C.POINTER(TsSlotInfo), _vp]),
     "ts_pixelcnn_stream_load": (_i, [_vp, C.POINTER(C.c_int32), _i, _vp, _i, C.POINTER(C.c_int32), C.POINTER(TsSlotInfo), C.POINTER(C.c_int64), _vp]),
     "ts_pixelcnn_stream_graph_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_double)]),
+    # session pairs: primary / shadow / scale (n,) host, n; the (S,) table out; step_ctl plus guide_scale (S,) host ahead of the stream;
+    # the host rule: S, rows, guide (S,), clip rows (S,), fresh (S,), primary (n,), shadow (n,) or NULL, scale (n,) or NULL, n
+    "ts_pixelcnn_stream_pair": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), _i]),
+    "ts_pixelcnn_stream_pairs": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "ts_pixelcnn_stream_step_guided": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                            C.POINTER(C.c_int32), _rp, _i, C.POINTER(C.c_float), _vp]),
+    "ts_pixelcnn_stream_pair_check": (_i, [_i, _i64, C.POINTER(C.c_int32), C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_float), _i]),
     # seamless sessions: the step's arguments around (mfcc, t) / the two outputs, then the pieces of ts_pixelcnn_stream_step_ctl
     "ts_body_stream_open": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp)]),
     "ts_body_stream_plan": (_i, [_vp, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -187,6 +195,14 @@ SIGNATURES = {
                                  C.POINTER(C.c_int32), _rp, _i, _vp]),
     "ts_body_stream_flush": (_i, [_vp, _i, _vp, _u64, _i64, _vp, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
                                   C.POINTER(C.c_int32), _rp, _i, _vp]),
+    # guided sessions: ids (S,) device, B, n_shadow, shadow_of / enc_of (n_shadow,) host, style (n_shadow,NC) device or NULL, scales
+    # (n_shadow,) host, max frames, stream, out; push / flush plus guide_scale (S,) host ahead of the stream
+    "ts_body_stream_open_guided": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_float),
+                                        _i, _vp, C.POINTER(_vp)]),
+    "ts_body_stream_push_guided": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                        C.POINTER(C.c_int32), _rp, _i, C.POINTER(C.c_float), _vp]),
+    "ts_body_stream_flush_guided": (_i, [_vp, _i, _vp, _u64, _i64, _vp, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                         C.POINTER(C.c_int32), _rp, _i, C.POINTER(C.c_float), _vp]),
     "ts_body_stream_frames_in": (_i64, [_vp]),
     "ts_body_stream_code_rows": (_i64, [_vp]),
     "ts_body_stream_pose_frames": (_i64, [_vp]),
@@ -199,6 +215,7 @@ SIGNATURES = {
     "ts_debug_stream_stage_mfcc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ts_debug_stream_emit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ts_debug_stream_keep_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ts_debug_stream_spread_rows": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, _vp]),
     "ts_debug_gather_rows": (_i, [_vp, _i, _i, _vp, C.c_long, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "ts_debug_pad_rows": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ts_debug_mask_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
@@ -390,6 +407,12 @@ def load():
 def check(rc):
     if rc != 0:
         raise RuntimeError("libtalkshow_hip: " + load().ts_last_error().decode())
+
+
+def check_value(rc):
+    """`check` for a host-only rule on the caller's values: ValueError with the library's message."""
+    if rc != 0:
+        raise ValueError("libtalkshow_hip: " + load().ts_last_error().decode())
 
 
 def fptr(a):

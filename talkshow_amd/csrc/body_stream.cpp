@@ -78,6 +78,12 @@ struct ts_body_stream {
     ts_vqvae *vb = nullptr, *vh = nullptr;
     ts_pixelcnn_stream *pix = nullptr;
     int B = 0, max_frames = 0, max_rows = 0, aud_dim = 0, pose_dim = 0;
+    // "guided sessions" (talkshow_hip.h): the chain runs S = B + n_shadow slots (the clips, then the shadows), the audio encoder E = B + n_a
+    // MFCC streams (n_a: the shadows with audio of their own); slot_map (S,) int32 on the device: the encoder stream slot s hears.
+    // A plain session has S = E = B and no map
+    int S = 0, E = 0;
+    bool guided = false;
+    DevBuf slot_map;
     int enc_reach = ENC_MARGIN_ROWS, tail_cap = 0;   // code rows either side a kept audio row needs inside its window; frames of a tail half
     int win_cap = 0, ring_cap = 0;   // frames of the largest encoder window; code rows of the ring = of the largest decoder window
     Counters c;
@@ -89,7 +95,8 @@ struct ts_body_stream {
         if (pix) ts_pixelcnn_stream_close(pix);
     }
     size_t bytes() const {
-        return tail[0].bytes + tail[1].bytes + ring.bytes + win.bytes + feat.bytes + aud.bytes + lat[0].bytes + lat[1].bytes + dec.bytes;
+        return tail[0].bytes + tail[1].bytes + ring.bytes + win.bytes + feat.bytes + aud.bytes + lat[0].bytes + lat[1].bytes + dec.bytes +
+               slot_map.bytes;
     }
 };
 
@@ -106,6 +113,8 @@ struct StepPieces {
     const int32_t *bias_index_host;
     const ts_repeat *rep_host;
     int n_rep;
+    bool guided = false;                  // the call came through a _guided entry: mfcc holds E streams, the pieces S slots
+    const float *guide_scale = nullptr;   // (S,) host, read at primaries; NULL: the stored scales
 };
 
 int stream_launches(ts_body_stream *st, const CallPlan &p, const float *mfcc, int t, bool flush, int mode, const float *uniforms, uint64_t seed,
@@ -118,6 +127,10 @@ int stream_call(ts_body_stream *st, const char *who, const float *mfcc, int t, b
     if (!st) return fail(w + ": null session");
     if (st->broken) return fail(w + ": an earlier call of this session failed on the device; close it");
     if (st->c.flushed) return fail(w + ": the session has been flushed (the clip has ended); open another");
+    if (o.guided != st->guided)
+        return fail(w + (st->guided ? ": the session was opened with shadows (ts_body_stream_open_guided): its calls are the _guided entries, which "
+                                      "bring the MFCC block of its E streams"
+                                    : ": the session was opened without shadows: its calls are ts_body_stream_push / _flush"));
     if (!flush) {
         if (!mfcc) return fail(w + ": null argument");
         if (t < 1) return fail(w + ": a push holds at least one MFCC frame, got " + std::to_string(t));
@@ -162,23 +175,31 @@ int stream_call(ts_body_stream *st, const char *who, const float *mfcc, int t, b
 // The device part of a call whose plan `p` has been checked against the session's buffers
 int stream_launches(ts_body_stream *st, const CallPlan &p, const float *mfcc, int t, bool flush, int mode, const float *uniforms, uint64_t seed,
                     int64_t clip0, int64_t *codes_out, float *poses_out, const StepPieces &o, hipStream_t s) {
-    const int B = st->B, n = (int)(p.A1 - p.A0), n_pose = (int)(4 * (p.D1 - p.D0));
+    const int B = st->B, E = st->E, n = (int)(p.A1 - p.A0), n_pose = (int)(4 * (p.D1 - p.D0));
     const int n_tail = (int)(st->c.F - st->tail0), Tw = (int)(p.enc_f1 - p.enc_f0), Hw = (int)(p.v1 - p.v0);
     const int next0 = (int)(p.keep_frame0 - st->tail0), n_next = flush ? 0 : (int)(p.after.F - p.keep_frame0);
     const int64_t ring0 = Hw > 0 ? p.v0 : p.A0;
     // 1. [tail | chunk] -> the encoder window, and the next tail into the other half (the live half is not written: a call that fails below
     //    leaves the session where it was)
-    TS_HIP(launch_stream_stage_mfcc(st->tail[st->half].f(), mfcc, st->win.f(), st->tail[st->half ^ 1].f(), B, n_tail, t, st->tail_cap, Tw,
+    TS_HIP(launch_stream_stage_mfcc(st->tail[st->half].f(), mfcc, st->win.f(), st->tail[st->half ^ 1].f(), E, n_tail, t, st->tail_cap, Tw,
                                     next0, n_next, s));
     // 2. the window through the audio encoder, its kept rows through the chain.  The chain checks the optional pieces before its own first
     //    launch and before its row counter moves
-    if (n > 0) {
+    if (n > 0 && st->guided) {   // E streams encoded once each, their kept rows spread to the S slots; the step runs under the session's pairs
+        TS_TRY(ts_audioenc_forward(st->ae, st->win.f(), E, Tw, st->feat.f(), s));
+        TS_HIP(launch_stream_spread_rows(st->feat.f(), st->aud.f(), static_cast<const int32_t *>(st->slot_map.p), st->S, E, Tw / 4,
+                                         (int)(p.A0 - p.w0), n, st->aud_dim, s));
+        TS_TRY(ts_pixelcnn_stream_step_guided(st->pix, st->aud.f(), n, mode, uniforms, seed, clip0, codes_out, o.ctl_host, o.n_ctl, o.logprob,
+                                              o.given, o.given_rows_host, o.style, o.bias, o.n_bias, o.bias_index_host, o.rep_host, o.n_rep,
+                                              o.guide_scale, s));
+    } else if (n > 0) {
         TS_TRY(ts_audioenc_forward(st->ae, st->win.f(), B, Tw, st->feat.f(), s));
         TS_HIP(launch_stream_keep_rows(st->feat.f(), st->aud.f(), B, Tw / 4, (int)(p.A0 - p.w0), n, st->aud_dim, s));
         TS_TRY(ts_pixelcnn_stream_step_ctl(st->pix, st->aud.f(), n, mode, uniforms, seed, clip0, codes_out, o.ctl_host, o.n_ctl, o.logprob, o.given,
                                            o.given_rows_host, o.style, o.bias, o.n_bias, o.bias_index_host, o.rep_host, o.n_rep, s));
     }
-    // 3. the codes into the ring; the decoder window out of ring + step, through both decoders; the kept frames to the caller
+    // 3. the codes into the ring; the decoder window out of ring + step, through both decoders; the kept frames to the caller.  A guided
+    //    call's code block is (S, n, 2), clip-major with stride n: its first B * n entries are the clips', and only those are emitted
     if (n > 0 || Hw > 0)
         TS_HIP(launch_stream_emit(codes_out, static_cast<int64_t *>(st->ring.p), static_cast<int64_t *>(st->lat[0].p),
                                   static_cast<int64_t *>(st->lat[1].p), B, n, (int)p.A0, st->ring_cap, (int)ring0, Hw, s));
@@ -194,13 +215,18 @@ int stream_launches(ts_body_stream *st, const CallPlan &p, const float *mfcc, in
 
 extern "C" {
 
-int ts_body_stream_open(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const int64_t *ids, int B, int max_chunk_frames,
-                        ts_body_stream **out) {
-    if (!ae || !pix || !vb || !vh || !ids || !out) return fail("ts_body_stream_open: null argument");
-    if (B < 1 || max_chunk_frames < 1 || max_chunk_frames > (1 << 20)) return fail("ts_body_stream_open: bad shape");
+}  // extern "C"
+
+namespace {
+// The body of both open entries: ids (S,) the labels of the chain's slots; MFCC tails, the encoder window and feat are sized for the E
+// encoder streams, the chain session and its audio rows for S, the code ring, the latent columns and the decoders for the B clips
+int stream_open(const char *who, ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const int64_t *ids, int B, int S, int E,
+                int max_chunk_frames, ts_body_stream **out) {
+    if (!ae || !pix || !vb || !vh || !ids || !out) return fail(std::string(who) + ": null argument");
+    if (B < 1 || max_chunk_frames < 1 || max_chunk_frames > (1 << 20)) return fail(std::string(who) + ": bad shape");
     std::unique_ptr<ts_body_stream> st(new ts_body_stream());
     st->ae = ae, st->vb = vb, st->vh = vh;
-    st->B = B, st->max_frames = max_chunk_frames;
+    st->B = B, st->S = S, st->E = E, st->max_frames = max_chunk_frames;
     st->aud_dim = convnet_hidden(ae), st->pose_dim = vqvae_in_dim(vb) + vqvae_in_dim(vh);
     // a lowered encoder's rounding reaches further (see the head of this file); the rule networks are created under
     if (wino_lowered(0, 3, st->aud_dim, st->aud_dim, knobs().conv_wino)) st->enc_reach += ENC_TILE_SLACK_ROWS;
@@ -210,17 +236,66 @@ int ts_body_stream_open(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae
     st->tail_cap = tail_cap_frames(st->enc_reach);
     st->win_cap = st->tail_cap + max_chunk_frames;
     st->ring_cap = RING_KEEP_ROWS + st->max_rows;
-    TS_TRY(ts_pixelcnn_stream_open(pix, ids, B, st->max_rows, &st->pix));   // selects the device
+    TS_TRY(ts_pixelcnn_stream_open(pix, ids, S, st->max_rows, &st->pix));   // selects the device
     // everything is allocated here, once: no call grows a buffer
-    const size_t b = (size_t)B;
-    for (auto &h : st->tail) TS_TRY(h.ensure(b * st->tail_cap * 64 * sizeof(float)));
+    const size_t b = (size_t)B, e = (size_t)E;
+    for (auto &h : st->tail) TS_TRY(h.ensure(e * st->tail_cap * 64 * sizeof(float)));
     TS_TRY(st->ring.ensure(b * st->ring_cap * 2 * sizeof(int64_t)));
-    TS_TRY(st->win.ensure(b * st->win_cap * 64 * sizeof(float)));
-    TS_TRY(st->feat.ensure(b * (st->win_cap / 4) * st->aud_dim * sizeof(float)));
-    TS_TRY(st->aud.ensure(b * st->max_rows * st->aud_dim * sizeof(float)));
+    TS_TRY(st->win.ensure(e * st->win_cap * 64 * sizeof(float)));
+    TS_TRY(st->feat.ensure(e * (st->win_cap / 4) * st->aud_dim * sizeof(float)));
+    TS_TRY(st->aud.ensure((size_t)S * st->max_rows * st->aud_dim * sizeof(float)));
     for (auto &l : st->lat) TS_TRY(l.ensure(b * st->ring_cap * sizeof(int64_t)));
     TS_TRY(st->dec.ensure(b * 4 * st->ring_cap * st->pose_dim * sizeof(float)));
     *out = st.release();
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int ts_body_stream_open(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const int64_t *ids, int B, int max_chunk_frames,
+                        ts_body_stream **out) {
+    return stream_open("ts_body_stream_open", ae, pix, vb, vh, ids, B, B, B, max_chunk_frames, out);
+}
+
+// "guided sessions" (talkshow_hip.h).  Everything is checked on the host before the session exists.  The launches: the slot map as kernel
+// arguments and, where the shadows bring weight rows, the chain's restart of the shadow slots at row 0 — on `stream`, in no graph
+int ts_body_stream_open_guided(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const int64_t *ids, int B, int n_shadow,
+                               const int32_t *shadow_of, const int32_t *enc_of, const float *shadow_style, const float *scale_host,
+                               int max_chunk_frames, void *stream, ts_body_stream **out) {
+    const std::string who = "ts_body_stream_open_guided: ";
+    if (!shadow_of || !enc_of || !scale_host) return fail(who + "null argument");
+    if (B < 1 || n_shadow < 1 || n_shadow > B)
+        return fail(who + "a session of " + std::to_string(B) + " clips holds 1 to " + std::to_string(B) + " shadows, got " + std::to_string(n_shadow));
+    const int S = B + n_shadow;
+    int E = B;
+    std::vector<int32_t> map(S), prim(n_shadow), shad(n_shadow);
+    for (int b = 0; b < B; ++b) map[b] = b;
+    for (int k = 0; k < n_shadow; ++k) {
+        const std::string sh = "shadow " + std::to_string(k);
+        if (shadow_of[k] < 0 || shadow_of[k] >= B) return fail(who + sh + ": clip " + std::to_string(shadow_of[k]) + " is outside [0, B = " + std::to_string(B) + ")");
+        if (k > 0 && shadow_of[k] <= shadow_of[k - 1])
+            return fail(who + sh + ": the shadows stand in clip order, one per clip (clip " + std::to_string(shadow_of[k]) + " behind clip " +
+                        std::to_string(shadow_of[k - 1]) + ")");
+        if (enc_of[k] != -1 && enc_of[k] != E)
+            return fail(who + sh + ": its encoder stream is -1 (the clip's) or the next stream of its own, " + std::to_string(E) + ", got " +
+                        std::to_string(enc_of[k]));
+        map[B + k] = enc_of[k] < 0 ? shadow_of[k] : E++;
+        prim[k] = shadow_of[k], shad[k] = B + k;
+    }
+    ts_body_stream *st = nullptr;
+    TS_TRY(stream_open("ts_body_stream_open_guided", ae, pix, vb, vh, ids, B, S, E, max_chunk_frames, &st));
+    std::unique_ptr<ts_body_stream> hold(st);
+    st->guided = true;
+    hipStream_t s = (hipStream_t)stream;
+    TS_TRY(st->slot_map.ensure((size_t)S * sizeof(int32_t)));
+    TS_HIP(launch_put_words(static_cast<int *>(st->slot_map.p), map.data(), S, s));
+    if (shadow_style) {   // a shadow's weight row, written as a restart at row 0 writes it (a one-hot row is the label bit for bit)
+        std::vector<int64_t> clips(shad.begin(), shad.end());
+        TS_TRY(ts_pixelcnn_stream_restart(st->pix, shad.data(), n_shadow, nullptr, shadow_style, clips.data(), stream));
+    }
+    TS_TRY(ts_pixelcnn_stream_pair(st->pix, prim.data(), shad.data(), scale_host, n_shadow));
+    *out = hold.release();
     return 0;
 }
 
@@ -252,6 +327,24 @@ int ts_body_stream_flush(ts_body_stream *st, int mode, const float *uniforms, ui
                          void *stream) {
     const StepPieces o{ctl_host, n_ctl, logprob, given, given_rows_host, style, bias, n_bias, bias_index_host, rep_host, n_rep};
     return stream_call(st, "ts_body_stream_flush", nullptr, 0, true, mode, uniforms, seed, clip0, codes, poses, o, (hipStream_t)stream);
+}
+
+// The existing entries on a session with shadows: mfcc (E, t, 64); uniforms, codes, logprob, given and every per-clip table for the S slots
+// of the chain (the clips first); poses (B, ., pose_dim); guide_scale_host (S,) read at primaries, NULL: the stored scales
+int ts_body_stream_push_guided(ts_body_stream *st, const float *mfcc, int t, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
+                               int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                               const int32_t *given_rows_host, const float *style, const float *bias, int n_bias,
+                               const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const float *guide_scale_host, void *stream) {
+    const StepPieces o{ctl_host, n_ctl, logprob, given, given_rows_host, style, bias, n_bias, bias_index_host, rep_host, n_rep, true, guide_scale_host};
+    return stream_call(st, "ts_body_stream_push_guided", mfcc, t, false, mode, uniforms, seed, clip0, codes, poses, o, (hipStream_t)stream);
+}
+
+int ts_body_stream_flush_guided(ts_body_stream *st, int mode, const float *uniforms, uint64_t seed, int64_t clip0, int64_t *codes, float *poses,
+                                const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given, const int32_t *given_rows_host,
+                                const float *style, const float *bias, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host,
+                                int n_rep, const float *guide_scale_host, void *stream) {
+    const StepPieces o{ctl_host, n_ctl, logprob, given, given_rows_host, style, bias, n_bias, bias_index_host, rep_host, n_rep, true, guide_scale_host};
+    return stream_call(st, "ts_body_stream_flush_guided", nullptr, 0, true, mode, uniforms, seed, clip0, codes, poses, o, (hipStream_t)stream);
 }
 
 int64_t ts_body_stream_frames_in(const ts_body_stream *st) { return st ? st->c.F : -1; }
@@ -286,6 +379,18 @@ int ts_debug_stream_stage_mfcc(const float *tail, const float *chunk, float *win
 int ts_debug_stream_emit(const int64_t *codes, int64_t *ring, int64_t *lat_body, int64_t *lat_hand, int B, int n, int A, int RC, int v0, int Hw,
                          void *stream) {
     TS_HIP(launch_stream_emit(codes, ring, lat_body, lat_hand, B, n, A, RC, v0, Hw, (hipStream_t)stream));
+    return 0;
+}
+// map_host (S,): the source stream of every slot, each in [0, E) (checked here: the kernel trusts its map); waits for the launch
+int ts_debug_stream_spread_rows(const float *src, float *dst, const int32_t *map_host, int S, int E, int R, int r0, int n, int W, void *stream) {
+    if (!map_host || S < 1) return fail("ts_debug_stream_spread_rows: bad argument");
+    for (int i = 0; i < S; ++i)
+        if (map_host[i] < 0 || map_host[i] >= E) return fail("ts_debug_stream_spread_rows: slot " + std::to_string(i) + " names stream " + std::to_string(map_host[i]));
+    DevBuf map;
+    TS_TRY(map.ensure((size_t)S * sizeof(int32_t)));
+    TS_HIP(launch_put_words(static_cast<int *>(map.p), map_host, S, (hipStream_t)stream));
+    TS_HIP(launch_stream_spread_rows(src, dst, static_cast<const int32_t *>(map.p), S, E, R, r0, n, W, (hipStream_t)stream));
+    TS_HIP(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }
 int ts_debug_stream_keep_rows(const float *src, float *dst, int B, int R, int r0, int n, int W, void *stream) {

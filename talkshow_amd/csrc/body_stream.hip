@@ -84,6 +84,19 @@ __global__ __launch_bounds__(STAGE_THREADS) void stream_keep_rows_kernel(const T
     }
 }
 
+// dst (S, n, W4) = rows [r0, r0 + n) of stream map[s] of src (E, R, W4), W4 counted in float4: the kept audio rows of every encoder
+// stream to the chain slots that hear it (a source may serve several slots: a shadow on its clip's audio).  map holds values in [0, E)
+// (the session checks them on the host at open).  No scratch, one float4 per thread and round
+__global__ __launch_bounds__(STAGE_THREADS) void stream_spread_rows_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst,
+                                                                           const int32_t *__restrict__ map, int S, int R, int r0, int n,
+                                                                           int W4) {
+    const long per = (long)n * W4, n_all = (long)S * per;
+    for (long u = (long)blockIdx.x * STAGE_THREADS + threadIdx.x; u < n_all; u += (long)gridDim.x * STAGE_THREADS) {
+        const long sl = u / per, e = u % per;
+        dst[u] = src[((long)map[sl] * R + r0) * W4 + e];
+    }
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace
 
@@ -124,6 +137,18 @@ hipError_t launch_stream_keep_rows(const float *src, float *dst, int B, int R, i
             reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst), B, R, r0, n, W / 4);
     else
         stream_keep_rows_kernel<float><<<stage_blocks(units), STAGE_THREADS, 0, s>>>(src, dst, B, R, r0, n, W);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_spread_rows(const float *src, float *dst, const int32_t *map, int S, int E, int R, int r0, int n, int W,
+                                     hipStream_t s) {
+    if (S < 1 || E < 1 || R < 1 || W < 4 || W % 4 || r0 < 0 || n < 0 || r0 + n > R || !src || !map || (n > 0 && !dst) || !aligned16(src) ||
+        !aligned16(dst))
+        return hipErrorInvalidValue;
+    const long units = (long)S * n * (W / 4);
+    if (units == 0) return hipSuccess;
+    stream_spread_rows_kernel<<<stage_blocks(units), STAGE_THREADS, 0, s>>>(reinterpret_cast<const float4 *>(src),
+                                                                             reinterpret_cast<float4 *>(dst), map, S, R, r0, n, W / 4);
     return hipGetLastError();
 }
 

@@ -821,5 +821,9 @@ hipError_t launch_stream_emit(const int64_t *codes, int64_t *ring, int64_t *lat_
                               int Hw, hipStream_t s);
 // dst (B, n, W) = rows [r0, r0 + n) of every clip of src (B, R, W)
 hipError_t launch_stream_keep_rows(const float *src, float *dst, int B, int R, int r0, int n, int W, hipStream_t s);
+// dst (S, n, W) = rows [r0, r0 + n) of stream map[s] of src (E, R, W): W a multiple of 4, both 16-byte aligned; map (S,) on the device,
+// values in [0, E) (the caller's to guarantee)
+hipError_t launch_stream_spread_rows(const float *src, float *dst, const int32_t *map, int S, int E, int R, int r0, int n, int W,
+                                     hipStream_t s);
 
 }  // namespace ts

@@ -251,6 +251,13 @@ struct ts_pixelcnn_stream {
     // "slot state" (talkshow_hip.h): nothing below exists until the session's first save or load
     DevBuf state_tab;                  // three (B,) int32 tables of the save / load being queued (kernel arguments, in stream order)
     std::vector<int64_t> slot_label;   // per slot: the label a restart or a load brought, -1: the one given at open (the caller holds it)
+    // "session pairs" (talkshow_hip.h): nothing below exists until the session's first pair, restart or load
+    std::vector<int32_t> pair_of;      // per slot: its shadow's slot where it is a primary, else -1 (the table ts_guide_check takes)
+    std::vector<float> pair_scale;     // per slot: the stored scale of a primary
+    int n_pairs = 0;
+    std::vector<int32_t> fresh;        // per slot: the serial of the restart or load that listed it at session row fresh_at, else 0
+    long fresh_at = -1;
+    int32_t serial = 0;
 };
 
 namespace {
@@ -1987,11 +1994,38 @@ int64_t ts_pixelcnn_stream_rows(const ts_pixelcnn_stream *st) { return st ? st->
 }  // extern "C"
 
 namespace {
-// The body of both step entries: `o` holds what ts_pixelcnn_stream_step_ctl brought (the fields of a mixed pass that a session takes: no
+// ---- "session pairs" (talkshow_hip.h): the session's side of ts_pixelcnn_stream_pair_check ---------------------------------------------
+int64_t stream_slot_rows(const ts_pixelcnn_stream *st, int b) { return st->rows - (st->restarted ? st->origin[b] : 0); }
+// the serials as the rule reads them: a step since the call that set them makes every slot stale
+std::vector<int32_t> stream_fresh(const ts_pixelcnn_stream *st) {
+    if (st->fresh.empty() || st->fresh_at != st->rows) return std::vector<int32_t>(st->B, 0);
+    return st->fresh;
+}
+// what a restart or a load of `slots` checks of the pairs before anything is launched: 0, or the one-sided refusal
+int stream_touch_check(const ts_pixelcnn_stream *st, const int32_t *slots, int n) {
+    if (st->n_pairs == 0) return 0;
+    std::vector<int64_t> rows(st->B);
+    for (int b = 0; b < st->B; ++b) rows[b] = stream_slot_rows(st, b);
+    return ts_pixelcnn_stream_pair_check(st->B, st->rows, st->pair_of.data(), rows.data(), stream_fresh(st).data(), slots, nullptr, nullptr, n);
+}
+// behind a restart or a load that was queued: the listed slots' pairs are dissolved (both slots were listed), their serial is the call's
+void stream_touched(ts_pixelcnn_stream *st, const int32_t *slots, int n) {
+    if (st->fresh.empty() || st->fresh_at != st->rows) st->fresh.assign(st->B, 0);
+    st->fresh_at = st->rows;
+    ++st->serial;
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i];
+        st->fresh[b] = st->serial;
+        if (st->n_pairs > 0 && st->pair_of[b] >= 0) st->pair_of[b] = -1, st->pair_scale[b] = 0.0f, --st->n_pairs;
+    }
+}
+
+// The body of the step entries: `o_in` holds what ts_pixelcnn_stream_step_ctl brought (the fields of a mixed pass that a session takes: no
 // mask of kept positions, no style track, no poses), so an absent piece is null here and costs no launch, no buffer and no bit of the
-// graph key.  Everything is checked before anything is launched and before st->rows moves.
+// graph key; a session with pairs adds its guide table and the step's scales (scale_host (B,), read at primaries; NULL: the stored ones).
+// Everything is checked before anything is launched and before st->rows moves.
 int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed, int64_t clip0,
-                int64_t *codes, const MixedOpts &o, hipStream_t s) {
+                int64_t *codes, const MixedOpts &o_in, hipStream_t s, const float *scale_host = nullptr) {
     PixTapScope taps;
     if (!st || !aud || !codes) return fail("ts_pixelcnn_stream_step: null argument");
     if (Hc < 1) return fail("ts_pixelcnn_stream_step: empty chunk");
@@ -2006,12 +2040,22 @@ int stream_step(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, cons
     const int B = st->B, r0 = (int)st->rows;
     const char *who = "ts_pixelcnn_stream_step_ctl";
     const std::vector<int32_t> lens(B, 4 * Hc);   // the rules of the mixed entry, on a pass of B clips of Hc rows
+    MixedOpts o = o_in;
+    std::vector<float> scales;
+    if (st->n_pairs > 0) {   // "session pairs": roles and scales are kernel arguments of the guided samplers, checked last as in a pass
+        scales = st->pair_scale;
+        for (int b = 0; scale_host && b < B; ++b)
+            if (st->pair_of[b] >= 0) scales[b] = scale_host[b];
+        o.guide_host = st->pair_of.data(), o.guide_scale_host = scales.data();
+    }
     SamplerTables t;
     TS_TRY(t.build(o, B, p->V, mode, lens.data(), sampler_names(who)));
     constexpr int32_t REP_NONE = ts_pixelcnn_stream::REP_NONE;
     std::vector<int32_t> rep_from(B, REP_NONE);   // the session's table behind this step, kept only if the step is queued
     for (size_t b = 0; b < t.rep.size(); ++b)
         if (t.rep[b].window > 0) t.rep[b].from_row = rep_from[b] = st->rep_from[b] != REP_NONE ? st->rep_from[b] : r0;
+    for (int b = 0; o.guide_host && b < B; ++b)   // a shadow's ring is never written: it has no run of penalised rows
+        if (o.guide_host[b] >= 0) rep_from[o.guide_host[b]] = REP_NONE;
     for (int32_t &g : t.given_rows) g += r0;   // the table the samplers read holds absolute bounds: clip b is forced at positions below 2 (r0 + g_b)
     if (r0 == 0 && !o.style && !st->cr_ready) TS_TRY(class_rows(p, w, static_cast<const int64_t *>(st->label.p), B, s));
     if (o.style) TS_TRY(class_rows_style(p, w, o.style, B, s));   // CR stays as written until a later step brings other rows
@@ -2060,6 +2104,100 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud, int Hc
     return stream_step(st, aud, Hc, mode, uniforms, seed, clip0, codes, o, (hipStream_t)stream);
 }
 
+// ts_pixelcnn_stream_step_ctl plus the step's scales (talkshow_hip.h, "session pairs"): guide_scale_host (B,), read at primaries only;
+// NULL: the stored scales — ts_pixelcnn_stream_step_ctl, exactly
+int ts_pixelcnn_stream_step_guided(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed,
+                                   int64_t clip0, int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob,
+                                   const int64_t *given, const int32_t *given_rows_host, const float *style, const float *bias_dev,
+                                   int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
+                                   const float *guide_scale_host, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host;
+    o.style = style, o.style_rows = 1, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    return stream_step(st, aud, Hc, mode, uniforms, seed, clip0, codes, o, (hipStream_t)stream, guide_scale_host);
+}
+
+// Host only ("session pairs"): the rule on host tables.  guide (S,) the session's pair table, clip_rows (S,) the rows of every slot's
+// current clip, fresh (S,) the serial of the restart or load that listed the slot with no step since, else 0.  shadow != NULL: the
+// declaration of n pairs (primary[i], shadow[i], scale[i]).  shadow == NULL: a restart or a load that lists the n slots of `primary`.
+int ts_pixelcnn_stream_pair_check(int S, int64_t rows, const int32_t *guide_host, const int64_t *clip_rows_host, const int32_t *fresh_host,
+                                  const int32_t *primary, const int32_t *shadow, const float *scale, int n) {
+    const std::string who = "session pairs: ";
+    if (S < 1 || rows < 0 || !guide_host || !clip_rows_host || !fresh_host || !primary || (shadow && !scale)) return fail(who + "bad argument");
+    if (n < 1) return fail(who + "no slot given");
+    std::vector<int> mate(S, -1);   // the other slot of every paired slot
+    for (int b = 0; b < S; ++b) {
+        const int g = guide_host[b];
+        if (g < -1 || g >= S || g == b) return fail(who + "bad argument");
+        if (g >= 0) mate[b] = g, mate[g] = b;
+    }
+    auto in_range = [&](int i, int x) -> int {
+        if (x >= 0 && x < S) return 0;
+        return fail(who + "entry " + std::to_string(i) + ": slot " + std::to_string(x) + " is outside [0, S = " + std::to_string(S) + ")");
+    };
+    std::vector<char> listed(S, 0);
+    if (!shadow) {   // a restart or a load: both slots of a pair, or neither
+        for (int i = 0; i < n; ++i) {
+            TS_TRY(in_range(i, primary[i]));
+            listed[primary[i]] = 1;
+        }
+        for (int i = 0; i < n; ++i) {
+            const int b = primary[i];
+            if (mate[b] >= 0 && !listed[mate[b]])
+                return fail(who + "slot " + std::to_string(b) + " is paired with slot " + std::to_string(mate[b]) + ": list both");
+        }
+        return 0;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int b = primary[i], g = shadow[i];
+        TS_TRY(in_range(i, b));
+        TS_TRY(in_range(i, g));
+        const std::string sb = "slot " + std::to_string(b), sg = "slot " + std::to_string(g);
+        if (b == g) return fail(who + sb + " names itself as its shadow");
+        for (int x : {b, g}) {
+            if (listed[x]) return fail(who + "slot " + std::to_string(x) + " is listed twice");
+            if (mate[x] >= 0)
+                return fail(who + "slot " + std::to_string(x) + " is paired with slot " + std::to_string(mate[x]) +
+                            ": restart or load both to dissolve the pair");
+        }
+        listed[b] = listed[g] = 1;
+        if (rows > 0 && (fresh_host[b] == 0 || fresh_host[b] != fresh_host[g]))
+            return fail(who + sb + " and " + sg + " cannot pair at session row " + std::to_string(rows) +
+                        ": a pair forms at session row 0 or behind the call that restarts or loads both slots, ahead of the next step");
+        if (clip_rows_host[b] != clip_rows_host[g])
+            return fail(who + sb + " holds a clip of " + std::to_string(clip_rows_host[b]) + " rows, " + sg + " one of " +
+                        std::to_string(clip_rows_host[g]) + ": a shadow carries its primary's history from the clip's row 0");
+        if (std::isnan(scale[i])) return fail(who + sb + ": the scale is NaN");
+        if (std::isinf(scale[i])) return fail(who + sb + ": the scale is infinite");
+        if (std::fabs(scale[i]) > 1e4f) return fail(who + sb + ": the scale exceeds 1e4 in magnitude");
+    }
+    return 0;
+}
+
+// "session pairs": n pairs declared behind an open, a restart or a load and ahead of the next step.  Host tables only: nothing is launched
+int ts_pixelcnn_stream_pair(ts_pixelcnn_stream *st, const int32_t *primary, const int32_t *shadow, const float *scale, int n) {
+    if (!st || !primary || !shadow || !scale) return fail("ts_pixelcnn_stream_pair: null argument");
+    const int B = st->B;
+    std::vector<int64_t> rows(B);
+    for (int b = 0; b < B; ++b) rows[b] = stream_slot_rows(st, b);
+    const std::vector<int32_t> none(B, -1);
+    TS_TRY(ts_pixelcnn_stream_pair_check(B, st->rows, st->pair_of.empty() ? none.data() : st->pair_of.data(), rows.data(),
+                                         stream_fresh(st).data(), primary, shadow, scale, n));
+    if (st->pair_of.empty()) st->pair_of.assign(B, -1), st->pair_scale.assign(B, 0.0f);
+    for (int i = 0; i < n; ++i) st->pair_of[primary[i]] = shadow[i], st->pair_scale[primary[i]] = scale[i];
+    st->n_pairs += n;
+    return 0;
+}
+
+// "session pairs": the session's table, (S,) as ts_guide_check takes it; returns the number of pairs, -1 on a null argument
+int ts_pixelcnn_stream_pairs(const ts_pixelcnn_stream *st, int32_t *guide_out) {
+    if (!st || !guide_out) return fail("ts_pixelcnn_stream_pairs: null argument") ? -1 : -1;
+    for (int b = 0; b < st->B; ++b) guide_out[b] = st->pair_of.empty() ? -1 : st->pair_of[b];
+    return st->n_pairs;
+}
+
 int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st) { return st ? st->w.captures : -1; }
 
 // "slot restart" (talkshow_hip.h).  Everything is checked before anything is launched or any table moves.  The launches: the tables of
@@ -2086,6 +2224,7 @@ int ts_pixelcnn_stream_restart(ts_pixelcnn_stream *st, const int32_t *slots_host
             return fail(who + slot + ": label " + std::to_string(labels_host[i]) + " is outside [0, NC = " + std::to_string(p->NC) + ")");
         if (clip_index_host[i] < 0) return fail(who + slot + ": clip index " + std::to_string(clip_index_host[i]) + " is negative");
     }
+    TS_TRY(stream_touch_check(st, slots_host, n));   // "session pairs": both slots of a pair, or neither
     TS_HIP(hipSetDevice(p->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     ts_pixelcnn::Work *w = &st->w;
@@ -2134,6 +2273,7 @@ int ts_pixelcnn_stream_restart(ts_pixelcnn_stream *st, const int32_t *slots_host
         if (labels_host) st->slot_label[b] = labels_host[i];   // ("slot state": the label the slot stands for; a weight row keeps the old one)
         st->rep_from[b] = ts_pixelcnn_stream::REP_NONE;   // a penalty starts from an empty history, as a one-shot clip's does
     }
+    stream_touched(st, slots_host, n);
     return 0;
 }
 
@@ -2230,6 +2370,7 @@ int ts_pixelcnn_stream_load(ts_pixelcnn_stream *st, const int32_t *slots_host, i
             return fail(who + slot + ": clip index " + std::to_string(clips[i]) + " is negative" + (clip_index_host ? "" : " (the state records none: give one)"));
         tab[i] = b, tab[n + i] = k, tab[2 * n + i] = (int32_t)(r - o.rows);
     }
+    TS_TRY(stream_touch_check(st, slots_host, n));   // "session pairs": both slots of a pair, or neither
     TS_HIP(hipSetDevice(p->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     ts_pixelcnn::Work *w = &st->w;
@@ -2266,6 +2407,7 @@ int ts_pixelcnn_stream_load(ts_pixelcnn_stream *st, const int32_t *slots_host, i
         st->rep_from[b] = o.hist < 0 ? ts_pixelcnn_stream::REP_NONE : (int32_t)(r - o.hist);
         st->slot_label[b] = o.label;
     }
+    stream_touched(st, slots_host, n);
     return 0;
 }
 

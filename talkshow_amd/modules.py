@@ -612,14 +612,17 @@ class GatedPixelCNN(NativeModule):
         """hipGraphs captured so far on the current stream (a serving loop checks that this stands still once it is warm)."""
         return int(_lib.load().ts_pixelcnn_graph_captures(self.handle(), _lib.stream_ptr())) if self.bh_model else 0
 
-    def open_stream(self, label, batch_size, max_chunk_rows, *, sampling=None, style=None, code_bias=None, repeat=None):
+    def open_stream(self, label, batch_size, max_chunk_rows, *, sampling=None, style=None, code_bias=None, repeat=None, pairs=None):
         """A generation session with a persistent row cache (`ts_pixelcnn_stream_*`): `.step(aud_rows)` continues the
         clip(s) where the previous step stopped, at a cost independent of the history length.  sampling / style / code_bias / repeat:
         session DEFAULTS in the forms `PixelCNNStream.step` takes; a step that passes no value for a keyword runs under the default, any
-        value it does pass takes its place for that step."""
+        value it does pass takes its place for that step.  pairs: GUIDANCE at slot level (talkshow_hip.h, "session pairs"):
+        {primary: shadow} (stored scale 1) or {primary: (shadow, scale)} — slot `shadow` runs the primary's code history under its own label
+        and audio rows and draws nothing; the primary is decoded as `run(..., guide=)` decodes it (`PixelCNNStream.step`)."""
         if not (self.audio and self.bh_model):
             raise NotImplementedError("streaming sessions exist for the shipped configuration (audio=True, bh_model=True)")
-        return PixelCNNStream(self, label, batch_size, max_chunk_rows, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat)
+        return PixelCNNStream(self, label, batch_size, max_chunk_rows, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat,
+                              pairs=pairs)
 
     @staticmethod
     def _audio_rows(aud):
@@ -700,7 +703,8 @@ def step_pieces(net, B, labels, defaults, Hc, mode, dev, sampling, logprobs, giv
 class PixelCNNStream:
     """Host handle of `ts_pixelcnn_stream`: label (B,) or (1,) int64 fixed for the session."""
 
-    def __init__(self, net, label, batch_size, max_chunk_rows, sampling=None, style=None, code_bias=None, repeat=None):
+    def __init__(self, net, label, batch_size, max_chunk_rows, sampling=None, style=None, code_bias=None, repeat=None, pairs=None):
+        from talkshow_amd.streaming import SlotPairs
         dev = net._dev()
         label = _index_tensor(label, net.n_classes, "class label", dev)
         if label.numel() == 1 and batch_size > 1:
@@ -710,10 +714,41 @@ class PixelCNNStream:
         self.net, self.B, self.max_rows = net, int(batch_size), int(max_chunk_rows)
         self.defaults = {"sampling": sampling, "style": style, "code_bias": code_bias, "repeat": repeat}
         self._labels = label.detach().cpu().numpy()      # what `style=[None, ...]` stands for: the clip's own label
+        self._pairs = SlotPairs(self.B)
+        declared = None
+        if pairs:                                          # validated before the session exists (ValueError naming the slot)
+            declared = SlotPairs.parse(pairs)
+            self._pairs.pair(0, [0] * self.B, *declared)
         h = C.c_void_p()
         with torch.cuda.device(dev):
             _lib.check(_lib.load().ts_pixelcnn_stream_open(net.handle(), _lib.dptr(label), self.B, self.max_rows, C.byref(h)))
         self._h = h
+        if declared:
+            self._declare(*declared)
+
+    def _pair_table(self, make=True):
+        """This handle's `SlotPairs`.  `__init__` makes it; a handle put together without `__init__` (the host tests build one around a
+        spy library) gets it on first use.  make=False: None while there is none."""
+        if self.__dict__.get("_pairs") is None and make:
+            from talkshow_amd.streaming import SlotPairs
+            self._pairs = SlotPairs(self.B)
+        return self.__dict__.get("_pairs")
+
+    def _declare(self, primary, shadow, scale):
+        """`ts_pixelcnn_stream_pair` on pairs the host rule (`streaming.SlotPairs`) has accepted: host tables, nothing is launched."""
+        n = len(primary)
+        _lib.check_value(_lib.load().ts_pixelcnn_stream_pair(self._h, (C.c_int32 * n)(*[int(b) for b in primary]),
+                                                             (C.c_int32 * n)(*[int(g) for g in shadow]),
+                                                             (C.c_float * n)(*[float(v) for v in scale]), n))
+
+    @property
+    def pairs(self):
+        """{primary: (shadow, stored scale)} as the library holds them (`ts_pixelcnn_stream_pairs`; the scales are this handle's copy)."""
+        tab = (C.c_int32 * self.B)()
+        _lib.load().ts_pixelcnn_stream_pairs(self._h, tab)
+        if list(tab) != self._pair_table().guide:
+            raise RuntimeError(f"session pairs: the library holds {list(tab)}, this handle {self._pair_table().guide}")
+        return self._pair_table().pairs
 
     @property
     def rows(self):
@@ -733,7 +768,7 @@ class PixelCNNStream:
         return step_pieces(self.net, self.B, self._labels, self.defaults, Hc, mode, dev, sampling, logprobs, given, style, code_bias, repeat)
 
     def step(self, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=0, clip_index0=0, *, sampling=None, logprobs=False, given=None,
-             style=None, code_bias=None, repeat=None):
+             style=None, code_bias=None, repeat=None, guide=None):
         """aud_rows (B,Hc,aud_dim) device -> codes (B,Hc,2) int64 of the next Hc code rows.
         The keywords take the forms `GatedPixelCNN.run` takes and follow its rules FOR THIS STEP (`ts_pixelcnn_stream_step_ctl`;
         talkshow_hip.h, "streaming sessions"); sampling / style / code_bias / repeat left at None run under the session's default
@@ -743,11 +778,18 @@ class PixelCNNStream:
         step.  repeat: records over the session's own history, which persists across steps; a clip whose penalty is switched on (after no
         record, or window 0) starts from an empty history at this step's first row.  A bad value raises ValueError naming the clip before
         any device work; the session's row counter does not move.  With every keyword at its default and no session default the call is
-        `ts_pixelcnn_stream_step`, exactly."""
+        `ts_pixelcnn_stream_step`, exactly.
+        guide: the scales of the session's PAIRS for this step (`ts_pixelcnn_stream_step_guided`; talkshow_hip.h, "session pairs"): None
+        (the stored scales), a float for all pairs, a {primary: scale} dict, or an (S,) list with None at non-primaries.  A scale for a
+        slot that is no primary, a NaN, an infinity or |scale| > 1e4 raises ValueError naming the slot.  A session with pairs runs every
+        step under them: a primary's codes and log-probabilities are those of `run(..., guide=)` on the pair alone, a shadow's rows of
+        what is returned are its primary's, and a shadow's entries of sampling / given / code_bias / repeat are never read.  Greedy mode
+        is refused with pairs (`top_k = 1` is the greedy guided decode).  A session without pairs takes no `guide` and runs as ever."""
         B, Hc = int(aud_rows.shape[0]), int(aud_rows.shape[1])
         if B != self.B:
             raise ValueError(f"session was opened for B={self.B}, got {B}")
         dev = self.net._dev()
+        scales = None if guide is None else self._pair_table().step_scales(guide)      # None: the library runs the stored scales
         lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows = self._pieces(Hc, mode, dev, sampling, logprobs, given, style, code_bias,
                                                                                    repeat)
         if uniforms is not None and tuple(uniforms.shape) != (B, Hc, 2):   # the library strides them by the chunk's Hc * 2: a wrong shape would misalign clips b > 0
@@ -757,7 +799,7 @@ class PixelCNNStream:
         if uniforms is not None:
             uniforms = _dev_f32(uniforms, dev)
         args = (self._h, _lib.dptr(aud_rows), Hc, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), int(clip_index0), _lib.dptr(codes))
-        if lp is None and ctl is None and btab is None and rtab is None and block is None and srows is None:
+        if lp is None and ctl is None and btab is None and rtab is None and block is None and srows is None and scales is None:
             _lib.check(_lib.load().ts_pixelcnn_stream_step(*args, _lib.stream_ptr()))
             return codes
         if isinstance(lp, str):
@@ -766,10 +808,13 @@ class PixelCNNStream:
         block_dev = upload(block, dev) if block is not None else None
         style_dev = upload(srows, dev) if srows is not None else None
         bias_dev = upload(btab, dev) if btab is not None else None
-        _lib.check(_lib.load().ts_pixelcnn_stream_step_ctl(
-            *args, ctl, n_ctl, _lib.dptr(lp), _lib.dptr(block_dev), table.ctypes.data_as(i32p) if block is not None else None,
-            _lib.dptr(style_dev), _lib.dptr(bias_dev), int(btab.shape[0]) if btab is not None else 0,
-            bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep, _lib.stream_ptr()))
+        pieces = (ctl, n_ctl, _lib.dptr(lp), _lib.dptr(block_dev), table.ctypes.data_as(i32p) if block is not None else None,
+                  _lib.dptr(style_dev), _lib.dptr(bias_dev), int(btab.shape[0]) if btab is not None else 0,
+                  bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep)
+        if scales is None:
+            _lib.check(_lib.load().ts_pixelcnn_stream_step_ctl(*args, *pieces, _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.load().ts_pixelcnn_stream_step_guided(*args, *pieces, (C.c_float * B)(*scales), _lib.stream_ptr()))
         return codes if lp is None else (codes, lp)
 
     @property
@@ -778,7 +823,27 @@ class PixelCNNStream:
         lib = _lib.load()
         return np.array([lib.ts_pixelcnn_stream_slot_rows(self._h, b) for b in range(self.B)], np.int64)
 
-    def restart(self, slots, label=None, *, style=None, clip_indices=None):
+    def _touch(self, slots, clip_rows, pairs):
+        """The pair table behind a restart or load of `slots` that (re-)declares `pairs`, validated as a whole before any device work:
+        -> (the new table, the parsed declaration or None).  clip_rows: the rows the listed slots' clips will hold."""
+        from talkshow_amd.streaming import SlotPairs
+        held = self._pair_table(make=False)
+        if not pairs and (held is None or not held.pairs):      # no pair is held and none is declared: nothing to check, nothing to keep
+            return held, None
+        rows = self.rows
+        sim = self._pair_table().copy()
+        sim.check_touch(rows, slots)
+        sim.touched(rows, slots)
+        declared = None
+        if pairs:
+            declared = SlotPairs.parse(pairs)
+            held = [int(v) for v in self.slot_rows]
+            for b, n in zip(slots, clip_rows):
+                held[b] = int(n)
+            sim.pair(rows, held, *declared)
+        return sim, declared
+
+    def restart(self, slots, label=None, *, style=None, clip_indices=None, pairs=None):
         """Slot restart (`ts_pixelcnn_stream_restart`; talkshow_hip.h, "slot restart"): each listed slot ends its clip and begins a NEW one at
         the session's next row, while the other slots carry on — continuous batching.  From there on the slot's codes and
         log-probabilities are those of `run` on the new clip alone (same mode, seed and keywords, clip_index0 = its clip index), bit for
@@ -791,11 +856,15 @@ class PixelCNNStream:
         does, at every step).  Keywords of later steps keep counting in session rows: `given` from the step's first row, and a restarted
         slot's `repeat` history is empty at its first row.  A slot whose user has left needs no call and no mask: it keeps stepping on
         whatever audio rows it is given and its output is ignored.  A bad value raises ValueError naming the slot before any device
-        work; `rows` and `slot_rows` do not move."""
+        work; `rows` and `slot_rows` do not move.
+        pairs: {primary: shadow} or {primary: (shadow, scale)} among the slots this call lists ("session pairs"): the two begin a guided
+        clip together.  A slot of a pair restarts only with its other slot ("slot 3 is paired with slot 7: list both"); listing both
+        dissolves the pair unless `pairs` declares it again."""
         from talkshow_amd.streaming import SlotClock
         NC = self.net.n_classes
         slots, labels, styles, clips = SlotClock.check(self.B, NC, slots, label, style, clip_indices)
         n = len(slots)
+        sim, declared = self._touch(slots, [0] * n, pairs)
         rows = None
         if styles is not None:          # one entry of the C call's two tables is NULL: labels become their one-hot rows beside weight rows
             rows = np.zeros((n, NC), np.float32)
@@ -810,6 +879,9 @@ class PixelCNNStream:
         _lib.check(_lib.load().ts_pixelcnn_stream_restart(
             self._h, i32(*slots), n, None if rows is not None else i64(*[int(v) for v in labels]), _lib.dptr(style_dev), i64(*clips),
             _lib.stream_ptr()))
+        self._pairs = sim
+        if declared:
+            self._declare(*declared)
         for i, b in enumerate(slots):   # what `style=[None, ...]` stands for from here on; a blend keeps the slot's old label
             if labels is not None and labels[i] is not None:
                 self._labels[b] = int(labels[i])
@@ -842,19 +914,22 @@ class PixelCNNStream:
             o["label"] = int(self._labels[b])
         return SlotState(words, infos)
 
-    def load(self, slots, state, *, clip_indices=None):
+    def load(self, slots, state, *, clip_indices=None, pairs=None):
         """Slot state (`ts_pixelcnn_stream_load`): each listed slot takes a saved state — `state` holds one for all listed slots (fan-out) or
         one each — and carries that clip on from the session's next row under its clip index (clip_indices: one per slot; default: the
         index the source drew under).  The other slots keep their bits.  The state may come from another session, another batch size,
         another handle of a network with equal weights (not checked), another device, or `SlotState.frombytes`.  Refused with ValueError
         naming the slot, before any device work and with `rows` / `slot_rows` where they were: a slot out of range or listed twice, a count
         mismatch, a state of other (D, NL, NC, V) or version, session row < min(clip rows, 3), a negative clip index.  The session's first
-        load does what its first restart does (steps on the restart graph keys from there on)."""
+        load does what its first restart does (steps on the restart graph keys from there on).
+        pairs: as for `restart`, among the slots this call lists, whose states must hold clips of equal rows: a guided clip is saved as
+        `save([b, g])` and carried on by `load([b2, g2], state, pairs={b2: g2})` (pairs are not part of a state)."""
         from talkshow_amd.streaming import SlotClock, SlotState
         if not isinstance(state, SlotState):
             raise ValueError(f"load: state must be a SlotState, got {type(state).__name__}")
         SlotClock.check_load(self.B, self._dims(), None, slots, state.infos, clip_indices)      # every rule the arguments alone decide,
         slots, index, clips = SlotClock.check_load(self.B, self._dims(), self.rows, slots, state.infos, clip_indices)   # then the row's
+        sim, declared = self._touch(slots, [state.infos[k]["rows"] for k in index], pairs)
         n, m, dev = len(slots), len(state), self.net._dev()
         W = SlotClock.state_words(*self._dims()[:2])
         if tuple(state.words.shape) != (m, W):
@@ -869,6 +944,9 @@ class PixelCNNStream:
         with torch.cuda.device(dev):
             _lib.check(_lib.load().ts_pixelcnn_stream_load(self._h, (C.c_int32 * n)(*slots), n, _lib.dptr(words), m, (C.c_int32 * n)(*index), info,
                                                           (C.c_int64 * n)(*clips), _lib.stream_ptr()))
+        self._pairs = sim
+        if declared:
+            self._declare(*declared)
         for b, k in zip(slots, index):      # what `style=[None, ...]` stands for from here on
             self._labels[b] = int(state.infos[k]["label"])
         return self

@@ -313,6 +313,340 @@ class SlotClock:
         return self
 
 
+def _f32(x):
+    """x as the fp32 value the library receives (a finite double beyond fp32's range arrives as an infinity)."""
+    import struct
+    try:
+        return struct.unpack("f", struct.pack("f", float(x)))[0]
+    except OverflowError:
+        return float("inf") if x > 0 else float("-inf")
+
+
+class SlotPairs:
+    """Session pairs (talkshow_hip.h, "session pairs"), restated on the host beside `SlotClock`: which slots of a session are
+    primary and shadow of a guided clip, each pair's stored scale, and WHEN a pair may form.  The shadow's row cache must hold its primary's
+    code history under the second conditioning from the clip's row 0, so a pair is declared at session row 0, or behind the call that
+    restarts both slots, or behind the call that loads both from states of equal clip rows — and ahead of the next step.  Restarting or
+    loading one slot of a pair without the other is refused; listing both dissolves the pair unless the call declares it again.  There is
+    no pairing and no un-pairing in the middle of a clip: scale 0 is the off switch.  `check` is `ts_pixelcnn_stream_pair_check` with the
+    C check's wording (tests/test_stream_pairs_host.py holds the two against each other); the instance is the table a session keeps.
+    Pure Python."""
+
+    WHO = "session pairs: "
+    MAX_SCALE = 1e4
+    DEFAULT_SCALE = 1.0     # `pairs={primary: shadow}` without a scale
+
+    def __init__(self, S):
+        self.S = int(S)
+        if self.S < 1:
+            raise ValueError(f"a session has at least one slot, got S = {S}")
+        self.guide = [-1] * self.S        # the table ts_guide_check takes: a primary's shadow, else -1
+        self.scale = [0.0] * self.S       # a primary's stored scale
+        self.fresh = [0] * self.S         # the serial of the restart or load that listed the slot at session row fresh_at, else 0
+        self.fresh_at = -1
+        self.serial = 0
+
+    @classmethod
+    def scale_fault(cls, s):
+        """The tail of the refusal of one scale, or None."""
+        try:
+            s = _f32(s)
+        except (TypeError, ValueError):
+            return "the scale is NaN"
+        if s != s:
+            return "the scale is NaN"
+        if s in (float("inf"), float("-inf")):
+            return "the scale is infinite"
+        if abs(s) > cls.MAX_SCALE:
+            return "the scale exceeds 1e4 in magnitude"
+        return None
+
+    @classmethod
+    def check(cls, S, rows, guide, clip_rows, fresh, primary, shadow=None, scale=None):
+        """`ts_pixelcnn_stream_pair_check`: S slots at session row `rows`; guide (S,) the pair table; clip_rows (S,) the rows of every slot's
+        current clip; fresh (S,) per slot the serial of the restart or load that listed it if no step was run since, else 0.  shadow given:
+        the declaration of the pairs (primary[i], shadow[i], scale[i]).  shadow None: a restart or load that lists the slots of `primary`.
+        ValueError with the library's text."""
+        who, S, rows = cls.WHO, int(S), int(rows)
+        primary = list(primary)
+        n = len(primary)
+        if n < 1:
+            raise ValueError(who + "no slot given")
+        mate = [-1] * S
+        for b, g in enumerate(guide):
+            if g >= 0:
+                mate[b], mate[g] = g, b
+
+        def in_range(i, x):
+            if int(x) != x or not 0 <= int(x) < S:
+                raise ValueError(who + f"entry {i}: slot {x} is outside [0, S = {S})")
+        listed = [False] * S
+        if shadow is None:
+            for i, b in enumerate(primary):
+                in_range(i, b)
+                listed[int(b)] = True
+            for b in primary:
+                if mate[int(b)] >= 0 and not listed[mate[int(b)]]:
+                    raise ValueError(who + f"slot {int(b)} is paired with slot {mate[int(b)]}: list both")
+            return
+        shadow, scale = list(shadow), list(scale)
+        for i in range(n):
+            in_range(i, primary[i])
+            in_range(i, shadow[i])
+            b, g = int(primary[i]), int(shadow[i])
+            if b == g:
+                raise ValueError(who + f"slot {b} names itself as its shadow")
+            for x in (b, g):
+                if listed[x]:
+                    raise ValueError(who + f"slot {x} is listed twice")
+                if mate[x] >= 0:
+                    raise ValueError(who + f"slot {x} is paired with slot {mate[x]}: restart or load both to dissolve the pair")
+            listed[b] = listed[g] = True
+            if rows > 0 and (fresh[b] == 0 or fresh[b] != fresh[g]):
+                raise ValueError(who + f"slot {b} and slot {g} cannot pair at session row {rows}: a pair forms at session row 0 or behind "
+                                       f"the call that restarts or loads both slots, ahead of the next step")
+            if int(clip_rows[b]) != int(clip_rows[g]):
+                raise ValueError(who + f"slot {b} holds a clip of {int(clip_rows[b])} rows, slot {g} one of {int(clip_rows[g])}: a shadow "
+                                       f"carries its primary's history from the clip's row 0")
+            fault = cls.scale_fault(scale[i])
+            if fault:
+                raise ValueError(who + f"slot {b}: {fault}")
+
+    @classmethod
+    def parse(cls, pairs):
+        """`pairs=` of open_stream / restart / load -> ([primary], [shadow], [scale]): {primary: shadow} or {primary: (shadow, scale)}."""
+        if not isinstance(pairs, dict):
+            raise ValueError(f"pairs: a dict {{primary: shadow}} or {{primary: (shadow, scale)}}, got {type(pairs).__name__}")
+        prim, shad, scal = [], [], []
+        for b, v in pairs.items():
+            g, s = (v[0], v[1]) if isinstance(v, (tuple, list)) and len(v) == 2 else (v, cls.DEFAULT_SCALE)
+            if isinstance(g, (tuple, list, dict)) or isinstance(b, (tuple, list)):
+                raise ValueError(f"pairs: the entry of slot {b} is a shadow slot or (shadow, scale), got {v!r}")
+            prim.append(b), shad.append(g), scal.append(s)
+        return prim, shad, scal
+
+    def fresh_now(self, rows):
+        """The serials as the rule reads them at session row `rows`: a step since the call that set them makes every slot stale."""
+        return list(self.fresh) if self.fresh_at == int(rows) else [0] * self.S
+
+    def check_touch(self, rows, slots):
+        """What a restart or a load of `slots` checks of the pairs."""
+        if any(g >= 0 for g in self.guide):
+            self.check(self.S, rows, self.guide, [0] * self.S, self.fresh_now(rows), slots)
+
+    def touched(self, rows, slots):
+        """Behind a restart or a load of `slots` at session row `rows`: their pairs are dissolved, their serial is the call's."""
+        self.fresh = self.fresh_now(rows)
+        self.fresh_at = int(rows)
+        self.serial += 1
+        for b in slots:
+            self.fresh[b] = self.serial
+            if self.guide[b] >= 0:
+                self.guide[b], self.scale[b] = -1, 0.0
+        return self
+
+    def copy(self):
+        c = SlotPairs(self.S)
+        c.guide, c.scale, c.fresh, c.fresh_at, c.serial = list(self.guide), list(self.scale), list(self.fresh), self.fresh_at, self.serial
+        return c
+
+    def pair(self, rows, clip_rows, primary, shadow, scale):
+        """Declare the pairs at session row `rows` (all or none)."""
+        self.check(self.S, rows, self.guide, clip_rows, self.fresh_now(rows), primary, shadow, scale)
+        for b, g, s in zip(primary, shadow, scale):
+            self.guide[int(b)], self.scale[int(b)] = int(g), _f32(s)
+        return self
+
+    @property
+    def pairs(self):
+        """{primary: (shadow, stored scale)}."""
+        return {b: (g, self.scale[b]) for b, g in enumerate(self.guide) if g >= 0}
+
+    def step_scales(self, guide, who="step"):
+        """`guide=` of a step -> None (the stored scales) or the (S,) list of floats the step runs under (0.0 where no primary sits).
+        A float applies to all pairs; a {primary: scale} dict or an (S,) list with None at non-primaries sets scales per pair (a primary
+        left out keeps its stored scale).  ValueError naming the slot: a scale for a slot that is no primary, a NaN, an infinity,
+        |scale| > 1e4."""
+        if guide is None:
+            return None
+        out = list(self.scale)
+        if isinstance(guide, dict):
+            items = list(guide.items())
+        elif isinstance(guide, (list, tuple)):
+            if len(guide) != self.S:
+                raise ValueError(f"{who}: guide holds one entry per slot (S = {self.S}), got {len(guide)}")
+            items = [(b, s) for b, s in enumerate(guide) if s is not None]
+        elif isinstance(guide, (int, float)) and not isinstance(guide, bool):
+            items = [(b, guide) for b, g in enumerate(self.guide) if g >= 0]
+            if not items:
+                raise ValueError(f"{who}: guide: the session holds no pair")
+        else:
+            raise ValueError(f"{who}: guide is None, a float, a {{primary: scale}} dict or an (S,) list, got {type(guide).__name__}")
+        for b, s in items:
+            if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.S:
+                raise ValueError(f"{who}: guide: slot {b} is outside [0, S = {self.S})")
+            if self.guide[b] < 0:
+                raise ValueError(f"{who}: guide: slot {b} is no primary of a pair")
+            fault = self.scale_fault(s) if isinstance(s, (int, float)) and not isinstance(s, bool) else "the scale is not a number"
+            if fault:
+                raise ValueError(f"{who}: guide: slot {b}: {fault}")
+            out[b] = _f32(s)
+        return out
+
+
+class BodyGuide:
+    """Guidance at CLIP level in a body session (`TrainWrapper.open_stream(..., guide=)`; DESIGN.md §5, "session pairs"), on the host: the
+    entries a session is opened with, the slot layout they give, and the `guide=` of a push.  The chain session behind a body session of
+    B clips has S = B + n_g slots: the clips in slots 0 .. B-1 (so Philox clip indices stay clip_index0 + b without a table, and the
+    clips' rows of a step's code block are its first B), the shadows behind them in clip order.  The audio encoder runs on E = B + n_a
+    MFCC streams, n_a the shadows with audio of their own; a shadow that shares its clip's audio gets the clip's ENCODED rows.  Pure
+    Python: nothing is launched."""
+
+    KEYS = ("scale", "id", "style", "audio")
+
+    def __init__(self, guide, B, n_classes, who="open_stream"):
+        self.B, self.NC = int(B), int(n_classes)
+        self.entries = self.parse(guide, self.B, self.NC, who)
+        self.shadow_of, self.enc_of, self.S, self.E = self.layout([e is not None for e in self.entries],
+                                                                  [bool(e and e["audio"]) for e in self.entries])
+        self.slot_of = {b: self.B + k for k, b in enumerate(self.shadow_of)}      # clip -> its shadow's slot
+
+    @classmethod
+    def entry(cls, e, b, NC, who):
+        """One entry -> None or {"scale", "id", "style", "audio"}; ValueError naming clip b."""
+        if e is None:
+            return None
+        if not isinstance(e, dict):
+            raise ValueError(f"{who}: guide of clip {b}: an entry is None or a dict with the keys {cls.KEYS}, got {type(e).__name__}")
+        unknown = sorted(set(e) - set(cls.KEYS))
+        if unknown:
+            raise ValueError(f"{who}: guide of clip {b}: unknown keys {unknown} {cls.KEYS}")
+        if "scale" not in e:
+            raise ValueError(f"{who}: guide of clip {b}: \"scale\" is required")
+        s = e["scale"]
+        fault = SlotPairs.scale_fault(s) if isinstance(s, (int, float)) and not isinstance(s, bool) else "the scale is not a number"
+        if fault:
+            raise ValueError(f"{who}: guide of clip {b}: {fault}")
+        i = e.get("id")
+        if i is not None and (isinstance(i, bool) or int(i) != i or not 0 <= int(i) < NC):
+            raise ValueError(f"{who}: guide of clip {b}: id {i} is outside [0, n_classes = {NC})")
+        row = e.get("style")
+        if row is not None:
+            row = row.detach().cpu().numpy() if hasattr(row, "detach") else row
+            row = list(row.tolist() if hasattr(row, "tolist") else row)
+            if len(row) != NC or any(isinstance(v, (list, tuple)) for v in row):
+                raise ValueError(f"{who}: guide of clip {b}: a style row holds n_classes = {NC} weights (a session takes no tracks)")
+            row = [float(v) for v in row]
+            if any(v != v or v in (float("inf"), float("-inf")) for v in row):
+                raise ValueError(f"{who}: guide of clip {b}: a style weight is not finite")
+        a = e.get("audio", False)
+        if not isinstance(a, bool):
+            raise ValueError(f"{who}: guide of clip {b}: \"audio\" is True (every push brings the shadow's MFCC chunk) or False")
+        return {"scale": _f32(s), "id": None if i is None else int(i), "style": row, "audio": a}
+
+    @classmethod
+    def parse(cls, guide, B, NC, who="open_stream"):
+        """`guide=` of open_stream -> B entries: None, one dict for all clips, or a list of B."""
+        if guide is None:
+            return [None] * B
+        if isinstance(guide, dict):
+            guide = [guide] * B
+        if not isinstance(guide, (list, tuple)) or len(guide) != B:
+            raise ValueError(f"{who}: guide is None, one dict for all clips or a list with one entry per clip (B = {B})")
+        return [cls.entry(e, b, NC, who) for b, e in enumerate(guide)]
+
+    @staticmethod
+    def layout(present, audio):
+        """present[b]: clip b has a shadow; audio[b]: the shadow hears audio of its own -> (shadow_of (n_g,) the clip of every shadow,
+        enc_of (n_g,) its encoder stream or -1 = the clip's, S, E)."""
+        B = len(present)
+        shadow_of = [b for b in range(B) if present[b]]
+        enc_of, E = [], B
+        for b in shadow_of:
+            if audio[b]:
+                enc_of.append(E)
+                E += 1
+            else:
+                enc_of.append(-1)
+        return shadow_of, enc_of, B + len(shadow_of), E
+
+    def spread(self):
+        """(S,) the encoder stream whose rows chain slot s hears."""
+        return list(range(self.B)) + [e if e >= 0 else b for b, e in zip(self.shadow_of, self.enc_of)]
+
+    def pairs(self):
+        """{clip: (shadow slot, stored scale)} for `PixelCNNStream`."""
+        return {b: (self.slot_of[b], self.entries[b]["scale"]) for b in self.shadow_of}
+
+    def spread_kw(self, name, v, shadow_style, who="push"):
+        """A per-clip keyword of B entries as the S entries of the chain session: a shadow's entry of sampling / code_bias / repeat / given
+        is never read (None), its `style` entry is its own conditioning (shadow_style[clip], else None: its id), its uniforms are zeros."""
+        import torch
+        B = self.B
+        if v is None or not self.shadow_of:
+            return v
+        if name == "style":
+            rows = torch.as_tensor(v).detach().cpu().numpy() if not isinstance(v, (list, tuple)) else None
+            if rows is not None:
+                v = [rows] * B if rows.ndim == 1 else list(rows)
+            if len(v) != B:
+                raise ValueError(f"{who}: style holds one row for all clips or one per clip (B = {B}), got {len(v)}")
+            return list(v) + [shadow_style.get(b) for b in self.shadow_of]
+        if name == "uniforms":
+            u = torch.as_tensor(v, dtype=torch.float32)
+            if u.dim() != 3 or int(u.shape[0]) != B:
+                raise ValueError(f"{who}: uniforms must have shape (B={B}, Hc, 2), got {tuple(u.shape)}")
+            return torch.cat([u, torch.zeros((self.S - B,) + tuple(u.shape[1:]), dtype=u.dtype, device=u.device)])
+        if name == "given" and not isinstance(v, (list, tuple)):
+            v = list(v)
+        if isinstance(v, list):
+            if len(v) != B:
+                raise ValueError(f"{who}: {name} holds one entry per clip (B = {B}), got {len(v)}")
+            return list(v) + [None] * (self.S - B)
+        return v
+
+    def push(self, guide, t, who="push", need_mfcc=True):
+        """`guide=` of a push of t frames -> ({clip: scale} or None, [the MFCC chunk of every shadow with audio of its own, in encoder
+        order]).  None, a float (all guided clips), or a list with, per clip, None, a float or {"scale": s, "mfcc": (t, 64)}.  A clip
+        opened with "audio": True must bring "mfcc" of the chunk's own t, a clip opened without must not (need_mfcc=False: a flush, which
+        brings no audio at all).  ValueError naming the clip."""
+        B = self.B
+        if guide is None or (isinstance(guide, (int, float)) and not isinstance(guide, bool)):
+            if guide is not None and not self.shadow_of:
+                raise ValueError(f"{who}: guide: the session was opened without a shadow")
+            per = [guide if self.entries[b] is not None else None for b in range(B)]
+        elif isinstance(guide, (list, tuple)) and len(guide) == B:
+            per = list(guide)
+        else:
+            raise ValueError(f"{who}: guide is None, a float or a list with one entry per clip (B = {B})")
+        scales, chunks = {}, []
+        for b, e in enumerate(per):
+            opened = self.entries[b]
+            if opened is None:
+                if e is not None:
+                    raise ValueError(f"{who}: guide of clip {b}: the clip was opened without a shadow")
+                continue
+            m = None
+            if isinstance(e, dict):
+                unknown = sorted(set(e) - {"scale", "mfcc"})
+                if unknown:
+                    raise ValueError(f"{who}: guide of clip {b}: unknown keys {unknown} ('scale', 'mfcc')")
+                m, e = e.get("mfcc"), e.get("scale")
+            if e is not None:
+                fault = SlotPairs.scale_fault(e) if isinstance(e, (int, float)) and not isinstance(e, bool) else "the scale is not a number"
+                if fault:
+                    raise ValueError(f"{who}: guide of clip {b}: {fault}")
+                scales[b] = _f32(e)
+            if opened["audio"] and need_mfcc:
+                if m is None or tuple(getattr(m, "shape", ())) != (int(t), 64):
+                    raise ValueError(f"{who}: guide of clip {b}: the shadow was opened with audio of its own: \"mfcc\" of shape ({int(t)}, 64) "
+                                     f"is required, got {None if m is None else tuple(getattr(m, 'shape', ()))}")
+                chunks.append(m)
+            elif m is not None:
+                raise ValueError(f"{who}: guide of clip {b}: the shadow was opened without audio of its own: it takes no \"mfcc\"")
+        return (scales or None), chunks
+
+
 class SlotState:
     """The saved state of one or more slots (`PixelCNNStream.save`; talkshow_hip.h, "slot state"): `words` (n, W) int32, one row per slot
     in `SlotClock.state_layout`, on any device, and `infos`, one dict per row (D, NL, NC, V, version, rows, clip_index, label, hist).
@@ -386,9 +720,10 @@ class SeamlessBodyStream:
         raise NotImplementedError("a seamless session restarts no slot: its encoder and decoder windows are cut on the SESSION's row grid and "
                                   "all its clips have one length; use a plain session (open_stream(..., seamless=False)) or open another")
 
-    def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None, seed=None):
+    def __init__(self, wrapper, id, B, max_frames, sampling=None, style=None, code_bias=None, repeat=None, seed=None, guide=None):
         import ctypes as C
 
+        import numpy as np
         import torch
 
         from talkshow_amd import _lib
@@ -411,10 +746,37 @@ class SeamlessBodyStream:
         self._labels = label.detach().cpu().numpy()      # what `style=[None, ...]` stands for: the clip's own label
         self.pose_dim = wrapper.each_dim[1] + wrapper.each_dim[2]
         self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)   # one random stream per session
+        # guidance at clip level (talkshow_hip.h, "seamless sessions": guided sessions): the chain runs S = B + n_g slots, the encoder E streams
+        self.g = g = BodyGuide(guide, self.B, gen.n_classes)
+        self.S, self.shadow_style = g.S, {}
         h = C.c_void_p()
+        if not g.shadow_of:
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().ts_body_stream_open(wrapper.audioencoder.handle(), gen.handle(), wrapper.g_body.handle(),
+                                                           wrapper.g_hand.handle(), _lib.dptr(label), self.B, self.max_frames, C.byref(h)))
+            self._h = h
+            return
+        ids = list(self._labels) + [self._labels[b] if g.entries[b]["id"] is None else g.entries[b]["id"] for b in g.shadow_of]
+        self._labels = np.asarray(ids, np.int64)
+        self.defaults = {k: g.spread_kw(k, v, self.shadow_style, who="open_stream") for k, v in self.defaults.items() if k != "style"}
+        self.defaults["style"], self._style_default = None, style      # spread at every call: a shadow keeps its own conditioning
+        rows = None
+        if any(g.entries[b]["style"] is not None for b in g.shadow_of):     # every shadow then brings a row: its weights, or its id's one-hot
+            rows = np.zeros((len(g.shadow_of), gen.n_classes), np.float32)
+            for k, b in enumerate(g.shadow_of):
+                if g.entries[b]["style"] is not None:
+                    rows[k] = self.shadow_style[b] = np.asarray(g.entries[b]["style"], np.float32)
+                else:
+                    rows[k, int(ids[self.B + k])] = 1.0
+        n_g = len(g.shadow_of)
+        i32, label_s = C.c_int32 * n_g, torch.as_tensor(self._labels, device=dev)
+        rows_dev = None if rows is None else torch.as_tensor(rows, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().ts_body_stream_open(wrapper.audioencoder.handle(), gen.handle(), wrapper.g_body.handle(),
-                                                       wrapper.g_hand.handle(), _lib.dptr(label), self.B, self.max_frames, C.byref(h)))
+            _lib.check(_lib.load().ts_body_stream_open_guided(
+                wrapper.audioencoder.handle(), gen.handle(), wrapper.g_body.handle(), wrapper.g_hand.handle(), _lib.dptr(label_s), self.B, n_g,
+                i32(*g.shadow_of), i32(*g.enc_of), _lib.dptr(rows_dev), (C.c_float * n_g)(*[g.entries[b]["scale"] for b in g.shadow_of]),
+                self.max_frames, _lib.stream_ptr(), C.byref(h)))
+            torch.cuda.current_stream().synchronize()                      # the weight rows were read from this call's own tensor
         self._h = h
 
     # ---- counters (host reads; nothing synchronises) ----
@@ -481,7 +843,8 @@ class SeamlessBodyStream:
         total = (self.frames_in + int(t)) // 4
         return [(n, m), (total - self.code_rows - n, 4 * total - self.frames - m)]
 
-    def _call(self, mfcc, flush, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes):
+    def _call(self, mfcc, flush, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes,
+              guide=None):
         import ctypes as C
 
         import torch
@@ -496,6 +859,10 @@ class SeamlessBodyStream:
                 raise ValueError(f"push: mfcc must have shape (B={B}, t, 64), got {tuple(getattr(mfcc, 'shape', ()))}")
             t = int(mfcc.shape[1])
         n, m = self.plan(t, flush)                     # ValueError: after the flush, t = 0, t > max_frames
+        g, S = self.g, self.S
+        scales = chunks = None
+        if g.shadow_of or guide is not None:           # ValueError naming the clip; nothing is launched and no counter moves
+            scales, chunks = g.push(guide, t, who=who, need_mfcc=not flush)
         if uniforms is not None:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float32)          # lists and numpy arrays too
             if tuple(uniforms.shape) != (B, n, 2):
@@ -507,12 +874,20 @@ class SeamlessBodyStream:
             raise ValueError(f"{who}: this call runs {n} code rows: a given block holds at most {n} rows per clip, got {tuple(given.shape)}")
         lp = ctl = btab = bidx = rtab = block = table = srows = None
         n_ctl = n_rep = 0
+        lp_out = None
+        if g.shadow_of:                                # the pieces for the S slots of the chain: the clips', then what a shadow needs
+            style = self._style_default if style is None else style
+            sampling, given, style, code_bias, repeat, uniforms = (g.spread_kw(k, v, self.shadow_style, who=who) for k, v in (
+                ("sampling", sampling), ("given", given), ("style", style), ("code_bias", code_bias), ("repeat", repeat), ("uniforms", uniforms)))
+            if torch.is_tensor(logprobs):
+                _lib.logprob_request(logprobs, (B, n, 2), dev)
+                lp_out, logprobs = logprobs, True
         if n > 0:                                      # the keywords of the chain step this call makes, validated on the host
             lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows = step_pieces(
-                self.w.generator, B, self._labels, self.defaults, n, mode, dev, sampling, logprobs, given, style, code_bias, repeat)
+                self.w.generator, S, self._labels, self.defaults, n, mode, dev, sampling, logprobs, given, style, code_bias, repeat)
         if isinstance(lp, str) or (lp is None and logprobs):
-            lp = torch.empty((B, n, 2), dtype=torch.float32, device=dev)
-        codes = torch.empty((B, n, 2), dtype=torch.int64, device=dev)
+            lp = torch.empty((S, n, 2), dtype=torch.float32, device=dev)
+        codes = torch.empty((S, n, 2), dtype=torch.int64, device=dev)
         poses = torch.empty((B, m, self.pose_dim), dtype=torch.float32, device=dev)
         if uniforms is not None:
             uniforms = _dev_f32(uniforms, dev)
@@ -526,7 +901,26 @@ class SeamlessBodyStream:
                _lib.dptr(style_dev), _lib.dptr(bias_dev), int(btab.shape[0]) if btab is not None else 0,
                bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep, _lib.stream_ptr())
         lib = _lib.load()
-        if flush:
+        if g.shadow_of:                                # the guided entries: the MFCC block of the E streams, the step's scales ahead of the stream
+            sc = None if scales is None else (C.c_float * S)(*self._scales(scales))
+            mid = mid[:-1] + (sc, mid[-1])
+            if flush:
+                _lib.check(lib.ts_body_stream_flush_guided(self._h, *mid))
+            else:
+                mf = _dev_f32(mfcc, dev)
+                if chunks:
+                    mf = torch.cat([mf, torch.stack([_dev_f32(c, dev) for c in chunks])])
+                mf = mf.contiguous()
+                if mf.data_ptr() % 16:
+                    mf = mf.clone()
+                _lib.check(lib.ts_body_stream_push_guided(self._h, _lib.dptr(mf), t, *mid))
+            codes = codes[:B]                          # the clips' rows are the block's first B
+            if lp is not None:
+                lp = lp[:B]
+                if lp_out is not None:
+                    lp_out.copy_(lp)
+                    lp = lp_out
+        elif flush:
             _lib.check(lib.ts_body_stream_flush(self._h, *mid))
         else:
             mf = _dev_f32(mfcc, dev)
@@ -536,22 +930,33 @@ class SeamlessBodyStream:
         out = (poses,) + ((codes,) if return_codes else ()) + ((lp,) if lp is not None else ())
         return out[0] if len(out) == 1 else out
 
+    def _scales(self, scales):
+        """{clip: scale} of a call -> the (S,) list the guided entries read at primaries: the stored scale where the call brings none."""
+        out = [0.0] * self.S
+        for b in self.g.shadow_of:
+            out[b] = scales.get(b, self.g.entries[b]["scale"])
+        return out
+
     def push(self, mfcc, mode=2, seed=None, clip_index0=0, uniforms=None, *, sampling=None, logprobs=False, given=None, style=None,
-             code_bias=None, repeat=None, return_codes=False):
+             code_bias=None, repeat=None, return_codes=False, guide=None):
         """mfcc (B, t, 64), any t in 1 .. max_frames -> poses (B, m, 129), the next m = 4 x (code rows whose poses became final) frames of
         the clip — possibly 0, as during a clip's first ~80 frames; leftover frames are carried.  The call runs n code rows (`plan(t)`
         names n and m beforehand): `uniforms` (B, n, 2), `given` and the keywords `sampling`, `style`, `code_bias`, `repeat` — the forms and
         rules of `PixelCNNStream.step`, the session's defaults standing in for None — apply to THOSE rows; with n = 0 they are not read.
         return_codes=True: (poses, codes (B, n, 2)); logprobs=True adds their log-probabilities (B, n, 2) last.  mode 2 is
-        TS_SAMPLE_PHILOX.  A bad value raises ValueError before any device work, and no counter moves."""
-        return self._call(mfcc, False, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes)
+        TS_SAMPLE_PHILOX.  A bad value raises ValueError before any device work, and no counter moves.
+        guide (a session opened with `guide=`): None, a float for all guided clips, or per clip None, a float or {"scale": s, "mfcc":
+        (t, 64)} (`BodyGuide.push`): the call's scales and the MFCC chunk of every shadow opened with "audio": True.  The caller gets the
+        B clips' results."""
+        return self._call(mfcc, False, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes,
+                          guide)
 
     def flush(self, mode=2, seed=None, clip_index0=0, uniforms=None, *, sampling=None, logprobs=False, given=None, style=None, code_bias=None,
-              repeat=None, return_codes=False):
+              repeat=None, return_codes=False, guide=None):
         """The end of the clip: the rows and frames held back (`plan(0, flush=True)`), in the form `push` returns them.  Over the session
         the returned frames sum to 4 * (frames_in // 4), and equal `generate_batch` on the concatenated audio bit for bit.  A later push
         raises ValueError."""
-        return self._call(None, True, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes)
+        return self._call(None, True, mode, seed, clip_index0, uniforms, sampling, logprobs, given, style, code_bias, repeat, return_codes, guide)
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -592,6 +997,11 @@ class WavBodyStream:
         from talkshow_amd.frontend import WavStreamPlan
         from talkshow_amd.modules import MFCC
         self.w, self.B, self.seamless = wrapper, int(B), bool(seamless)
+        for b, e in enumerate(BodyGuide.parse(defaults.get("guide"), self.B, wrapper.generator.n_classes)):
+            if e is not None and e["audio"]:       # id or style guidance only: the MFCC rows come from the B-slot front end
+                raise NotImplementedError(f"open_stream: guide of clip {b}: a wav-fed session takes shadows WITHOUT audio of their own (id or "
+                                          f"style guidance): the front end would need slots for the shadows' samples; feed MFCC frames "
+                                          f"(wav_sr=None) for \"audio\": True")
         clock = WavStreamPlan(wav_sr, 22000, fps)                # ValueError: rates, fps
         if max_samples is None:                                   # the samples of max_frames rows
             max_samples = max(1, int(max_frames) * clock.hop * clock.norig // clock.nnew)
@@ -652,7 +1062,8 @@ class WavBodyStream:
         out += ((torch.empty((self.B, 0, 2), dtype=torch.float32, device=dev),) if logprobs else ())
         return out[0] if len(out) == 1 else out
 
-    _KEYWORDS = ("mode", "seed", "clip_index0", "uniforms", "sampling", "logprobs", "given", "style", "code_bias", "repeat", "return_codes")
+    _KEYWORDS = ("mode", "seed", "clip_index0", "uniforms", "sampling", "logprobs", "given", "style", "code_bias", "repeat", "return_codes",
+                 "guide")
 
     def _check(self, wav, flush, kw):
         """Everything a call can be refused for, on the host, before the front end is given a sample: the wav block's shape and size, the
@@ -696,10 +1107,20 @@ class WavBodyStream:
             raise ValueError(f"{who}: logprobs is True or False (a wav call may make two body calls: it returns a tensor of its own)")
         chain = self.body if self.seamless else self.body.pix          # whose labels and defaults the step keywords meet
         gen = self.w.generator
+        g = self.body.g
+        if g.shadow_of or kw.get("guide") is not None:                 # the call's scales (no shadow of a wav session brings audio)
+            g.push(kw.get("guide"), 0, who=who, need_mfcc=False)
+        pieces = {k: kw.get(k) for k in ("sampling", "style", "code_bias", "repeat")}
+        pieces["given"] = given
+        if g.shadow_of:                                                # the S slots of the chain: the clips', then what a shadow needs
+            if pieces["style"] is None:
+                pieces["style"] = self.body._style_default
+            pieces = {k: g.spread_kw(k, v, self.body.shadow_style, who=who) for k, v in pieces.items()}
         for nrows, _ in calls:
             if nrows > 0:                                              # ValueError naming the clip; nothing is launched or uploaded
-                step_pieces(gen, self.B, chain._labels, chain.defaults, nrows, mode, gen._dev(), kw.get("sampling"), kw.get("logprobs"),
-                            given, kw.get("style"), kw.get("code_bias"), kw.get("repeat"))
+                step_pieces(gen, g.S, chain._labels, chain.defaults, nrows, mode, gen._dev(), pieces["sampling"],
+                            True if g.shadow_of and kw.get("logprobs") else kw.get("logprobs"), pieces["given"], pieces["style"],
+                            pieces["code_bias"], pieces["repeat"])
         return f, calls, uniforms
 
     def _call(self, wav, flush, kw):
