@@ -833,6 +833,79 @@ int ts_body_pixel_infer_guided_poses(ts_convnet *audioenc, ts_pixelcnn *pix, ts_
 /* Host only: the check above on a table of B slots; lens_host (B,) the slots' lengths in frames or NULL; 0, or an error that names the slot. */
 int ts_guide_check(const int32_t *guide_host, const float *guide_scale_host, const int32_t *lens_host, int B);
 
+/* ---- alternatives: entropy, rank and the n best codes of every position ------------------------------------------------------------------
+ * No counterpart in the reference.  "log-probabilities" returns one number about a position's distribution, that of the code chosen.  A
+ * pass that brings a ts_alt_out record also returns, from the same sampler launch, what else the model would have done and how sure it
+ * was.  For a position of a clip let l'' be the row every later step runs on: the network's logits behind step 0 (code bias) and step 0b
+ * (repetition penalty), and (T, k, p) the clip's record (neutral without a table).  The outputs describe the distribution THE FILTERS ARE
+ * APPLIED TO — steps 1 and 2 of ts_sampling, ahead of top-k and top-p — so a top_k = 1 decode (the per-clip greedy) still reports
+ * informative alternatives and entropy.
+ * THE RULE.
+ *  Quantities.  m = max l''; d_v = (l''_v - m) * inv_T, two fp32 operations, the argument of step 1; w_v = det_expf(d_v).  A token with
+ *     l''_v = -inf (banned) has w_v = 0 and takes no part in any sum.
+ *  S_all.  The fp32 total of w_v over all tokens with the samplers' summation structure: 256 contiguous chunks left to right, then the
+ *     chunk sums left to right.  Where the record has neither top-k nor top-p in force, S_all is the S of "log-probabilities" bit for bit.
+ *  Alternatives j = 0 .. n-1.  The tokens of rank j in step 2's ranking (l'' descending, -0 equal to +0, ties by index ascending), banned
+ *     tokens excluded.  alt_code[j] is the index; alt_logprob[j] = (float)((double)d_j - log((double)S_all)) — d_j is used, never
+ *     log w_j, as for "log-probabilities".  With fewer than n allowed tokens the remaining entries are code -1 and -inf.
+ *  Entropy.  t_v = w_v * d_v, one fp32 product formed only where w_v > 0; E the fp32 total of t_v with the same summation structure
+ *     (every addition rounded on its own: no fused multiply-add); entropy = (float)(log((double)S_all) - (double)E / (double)S_all).
+ *     Both terms are non-negative (S_all >= 1, E <= 0): nothing cancels.
+ *  Rank.  The number of tokens ahead of the position's code c — drawn, given or kept — in step 2's ranking over all V tokens: an exact
+ *     integer, independent of T; -1 for a given code outside [0, V).
+ *  Purity.  All four are pure functions of the clip's own row, record, bias row and history: bit-identical alone or inside a mixed pass of
+ *     any size, eager or replayed, drawn or forced.  Nothing here feeds the draw: codes and log-probabilities of a pass with the record
+ *     are those of the pass without it, bit for bit.
+ *  Forced positions (given / kept) get all four, as they get their log-probability.
+ *  Invalid rows of a mixed pass, at or beyond a clip's own H_b, hold -1, 0, 0, -1: codes, log-probabilities, entropy, rank.
+ * talkshow_amd/sampling.py restates the rule (alternatives, alternatives_error_bound).
+ * Kernels, staging and graphs.  The samplers are kernels of their own (sample_ctl_alt_kernel / sample_ctl_alt_given_kernel: the
+ * repetition kernels with the log-probability and the rule compiled in; a pass without records runs them on windows of 0, one without
+ * tables on an index of -1, one without a sampling table on neutral records — slots that execute the arithmetic of the smaller kernels
+ * operation for operation).  No launch is added to the chain.  Under graph replay the four outputs go to a staging block of the stream's
+ * work buffers and are copied out behind the replay, as logprob_dev is.  Graph keys of their own: bit 9 (value 512) of the sixth key
+ * field, with n in the bits above it, so a repeated pass with the same n captures nothing.  Passes without the record launch the kernels
+ * and find the graphs they always did.
+ * The entries are the _repeat entry of each family (the session: the _ctl step) plus `const ts_alt_out *alt` ahead of the stream; NULL:
+ * that entry, launch for launch.  They need logprob_dev (the kernels compute it either way) and a drawing mode; a guided pass and a session
+ * with pairs are refused.  The new checks run behind every existing one.
+ * Out of scope: guided passes and paired sessions; the seamless body sessions; the scoring entries; the single-stack form; the samplers
+ * without controls' modes (greedy, teacher forced); the face generator. */
+#define TS_ALT_MAX 8
+typedef struct ts_alt_out {
+    int32_t n;             /* 0 .. TS_ALT_MAX alternatives per position */
+    int32_t reserved;      /* 0 */
+    int32_t *codes_dev;    /* (B,H,2,n) int32; NULL for n = 0 */
+    float *logprob_dev;    /* (B,H,2,n) fp32;  NULL for n = 0 */
+    float *entropy_dev;    /* (B,H,2) fp32 */
+    int32_t *rank_dev;     /* (B,H,2) int32 */
+} ts_alt_out;
+/* Host only: n outside [0, TS_ALT_MAX], reserved != 0, a missing pointer, a mode that is not TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (the
+ * message says that per-clip greedy is top_k = 1 under a drawing mode); 0, or an error. */
+int ts_alt_check(const ts_alt_out *alt, int mode);
+int ts_pixelcnn_generate_alt(ts_pixelcnn *pix, const int64_t *label_dev, const float *aud_dev, const int32_t *lens_host,
+                                   const int32_t *lens_dev, int B, int H_max, int mode, const float *uniforms_dev, uint64_t seed,
+                                   const int64_t *clip_index_dev, int64_t *codes_dev, const ts_sampling *ctl_host, int n_ctl,
+                                   float *logprob_dev, const int64_t *given_dev, const int32_t *given_rows_host,
+                                   const int32_t *given_rows_dev, const uint8_t *keep_dev, const float *style_dev, int style_rows,
+                                   const float *bias_dev, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
+                                   const ts_alt_out *alt, void *stream);
+int ts_body_pixel_infer_alt(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                  const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                  const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                  float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev, const int64_t *given_dev,
+                                  const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep_dev,
+                                  const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                  const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const ts_alt_out *alt, void *stream);
+int ts_body_pixel_infer_alt_poses(ts_convnet *audioenc, ts_pixelcnn *pix, ts_vqvae *vq_body, ts_vqvae *vq_hand, const float *mfcc_dev,
+                                        const int64_t *ids_dev, const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode,
+                                        const float *uniforms_dev, uint64_t seed, const int64_t *clip_index_dev, int64_t *codes_dev,
+                                        float *poses_dev, const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                        const float *given_poses_dev, int P_max, const int32_t *pose_lens_host, const int32_t *pose_lens_dev,
+                                        const uint8_t *keep_dev, const float *style_dev, int style_rows, const float *bias_dev, int n_bias,
+                                        const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const ts_alt_out *alt,
+                                        void *stream);
+
 /* s2g_body_vq.TrainWrapper.infer_on_audio(initial_pose=gt) core (smplx_body_vq.py:254-281):
  * poses_dev (B,T,body_dim+hand_dim) in c_index order -> recon_dev same shape, codes_dev (B,H,2) int64.
  * Either output may be NULL: recon_dev == NULL is the encode-only form (VQVAE.encode of both parts, the latents
@@ -926,6 +999,15 @@ int ts_op_sample_guide(ts_ctx *ctx, const float *logits_dev, int B, int V, int m
                        float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column,
                        const ts_repeat *rep_host, int n_rep, const int32_t *history_dev, int32_t *ring_out_dev, const int32_t *guide_host,
                        const float *guide_scale_host, void *stream);
+/* One launch of the samplers with "alternatives": ts_op_sample_repeat's arguments (rep_host and bias_dev may both be NULL here), then the
+ * record, whose arrays hold one position per row: codes_dev and logprob_dev (B,n), entropy_dev and rank_dev (B).  logprob_dev of the
+ * launch is required.  sample_ctl_alt_kernel, or sample_ctl_alt_given_kernel with given rows; the vector path as for ts_op_sample_bias. */
+int ts_op_sample_alt(ts_ctx *ctx, const float *logits_dev, int B, int V, int mode, const float *uniforms_dev, uint64_t seed,
+                     int64_t clip_index0, uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx_dev, float *logprob_dev,
+                     const int32_t *given_rows_host, const uint8_t *keep_dev, const int64_t *given_dev, uint8_t *kept_dev,
+                     float *logits_copy_dev, const float *bias_dev, int n_bias, const int32_t *bias_index_host, int column,
+                     const ts_repeat *rep_host, int n_rep, const int32_t *history_dev, int32_t *ring_out_dev, const ts_alt_out *alt,
+                     void *stream);
 
 /* Output assembly the callers do after both generators (scripts/demo.py:207-229 + data_utils/lower_body.py:68-87
  * `part2full`): body_dev (B,Tb,129) body+hand poses, face_dev (B,Tf,103) jaw(3)+expression(100) -> out_dev (B,Tf,265).
@@ -1084,6 +1166,15 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud_dev, in
                                 const float *style_dev,
                                 const float *bias_dev, int n_bias, const int32_t *bias_index_host,
                                 const ts_repeat *rep_host, int n_rep, void *stream);
+/* The step plus "alternatives" for its Hc rows: the record's arrays are (B,Hc,2,n) and (B,Hc,2).  alt == NULL: the entry above, launch for
+ * launch.  A session with pairs is refused. */
+int ts_pixelcnn_stream_step_alt(ts_pixelcnn_stream *st, const float *aud_dev, int Hc, int mode, const float *uniforms_dev,
+                                uint64_t seed, int64_t clip_index0, int64_t *codes_dev,
+                                const ts_sampling *ctl_host, int n_ctl, float *logprob_dev,
+                                const int64_t *given_dev, const int32_t *given_rows_host,
+                                const float *style_dev,
+                                const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                const ts_repeat *rep_host, int n_rep, const ts_alt_out *alt, void *stream);
 int64_t ts_pixelcnn_stream_captures(const ts_pixelcnn_stream *st);   /* hipGraphs this session has captured so far */
 void ts_pixelcnn_stream_close(ts_pixelcnn_stream *st);
 

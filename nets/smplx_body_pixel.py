@@ -97,7 +97,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         return out
 
     def generate_batch(self, mfcc, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, _ids_checked=False, sampling=None,
-                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
+                       logprobs=False, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None,
+                       alternatives=None):
         """Batched device entry (one call into the C ABI): mfcc (B,T,64), ids (B,) -> codes (B,H,2), poses (B,4H,129).
 
         This is what `infer_on_audio` runs after the front-end, for B different clips; bench.py and the multi-GPU
@@ -122,18 +123,21 @@ class TrainWrapper(TrainWrapperBaseClass):
         clips, or a list with one per clip (`generate_clips`, `ts_body_pixel_infer_mixed_repeat`).  None: nothing changes.
         guide: per-clip guidance against a second conditioning — one dict for all clips or a list with, per clip, None or {"scale",
         "mfcc" (T,64), "id", "style"} (`generate_clips`, `ts_body_pixel_infer_guided`).  None: nothing changes.
+        alternatives: n in [0, 8] -> one more return value, a `sampling.Alternatives` over the (B,H,2) positions: the n likeliest codes with
+        their log-probabilities, the entropy and the rank of the position's code (`generate_clips`, `ts_body_pixel_infer_alt`).  None:
+        nothing changes.
         """
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_batch: logprobs is True or False (GatedPixelCNN.run takes an output tensor)")
         if (sampling is not None or logprobs or given is not None or given_poses is not None or given_keep is not None or style is not None
-                or code_bias is not None or repeat is not None or guide is not None):
+                or code_bias is not None or repeat is not None or guide is not None or alternatives is not None):
             dev = self.generator._dev()
             mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev)
             u = None if uniforms is None else list(torch.as_tensor(uniforms, dtype=torch.float32).unbind(0))
             return self.generate_clips(list(mfcc.unbind(0)), ids, mode=mode, uniforms=u, seed=seed, clip_index0=clip_index0,
                                        _ids_checked=_ids_checked, _stacked=True, sampling=sampling, logprobs=bool(logprobs), given=given,
                                        given_poses=given_poses, given_keep=given_keep, style=style, code_bias=code_bias, repeat=repeat,
-                                       guide=guide)
+                                       guide=guide, alternatives=alternatives)
         dev = self.generator._dev()
         mfcc = torch.as_tensor(mfcc, dtype=torch.float32, device=dev).contiguous()
         if _ids_checked:   # generate_batches range-checked every batch's ids before stacking them (no sync on the stacked tensor)
@@ -232,7 +236,7 @@ class TrainWrapper(TrainWrapperBaseClass):
 
     def generate_clips(self, mfcc_list, ids, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=None, clip_index0=0, clip_indices=None,
                        _ids_checked=False, _stacked=False, sampling=None, logprobs=False, given=None, given_poses=None, given_keep=None,
-                       style=None, code_bias=None, repeat=None, guide=None):
+                       style=None, code_bias=None, repeat=None, guide=None, alternatives=None):
         """One MIXED pass over clips of different lengths (`ts_body_pixel_infer_mixed`): mfcc_list = list of (T_b,64) clips, ids (B,) or
         one id for all -> list of (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order, H_b = T_b // 4.
 
@@ -316,9 +320,22 @@ class TrainWrapper(TrainWrapperBaseClass):
         every other keyword's entry follows the clip, shadows bring none.  A guided clip costs a second slot of the pass; the caller
         gets B results.  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only.  A wrong key, shape, length or scale (NaN, infinite, beyond 1e4)
         raises ValueError naming the clip before anything is launched (`ts_body_pixel_infer_guided` / `ts_body_pixel_infer_guided_poses`).  None:
+        nothing changes.
+        alternatives: WHAT ELSE, AND HOW SURE (talkshow_hip.h, "alternatives") — n in [0, 8]: every clip's tuple gains, behind the
+        log-probabilities where those are asked for, a `sampling.Alternatives` with codes int64 (H_b,2,n) and logprobs float32 (H_b,2,n) of
+        the n likeliest allowed codes of every position, entropy float32 (H_b,2) and rank int64 (H_b,2) of the position's own code (drawn,
+        given or kept; -1 for a given code outside the vocabulary) — all under the distribution the filters are applied to: code bias,
+        repetition penalty and temperature applied, top-k and top-p not, so a top_k = 1 decode still reports them.  Written by the sampler
+        launch itself; codes, poses and log-probabilities are those of the call without the keyword, bit for bit, and a clip's values are
+        bit-identical to the clip alone.  `sampling.uncertain_keep(alt.entropy, threshold)` is a `given_keep=` mask: hand the codes back
+        with it to keep what the model was sure of and redraw the rest.  TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only (ValueError: a greedy
+        decode with alternatives is sampling=(1, 1, 1) under Philox); not with guide (NotImplementedError); n outside [0, 8] raises
+        ValueError — all before anything is launched (`ts_body_pixel_infer_alt` / `ts_body_pixel_infer_alt_poses`).  None:
         nothing changes."""
         if not (logprobs is None or isinstance(logprobs, bool)):
             raise ValueError("generate_clips: logprobs is True or False")
+        guided = guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide))
+        an = _lib.alt_request(alternatives, mode, "generate_clips", guide=guided)
         dev = self.generator._dev()
         B = len(mfcc_list)
         if B < 1:
@@ -422,14 +439,25 @@ class TrainWrapper(TrainWrapperBaseClass):
         args = (self.audioencoder.handle(), self.generator.handle(), self.g_body.handle(), self.g_hand.handle(),
                 _lib.dptr(mf), _lib.dptr(ids_sorted), lens_host.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int32)), _lib.dptr(lens_dev), Bp, T_max,
                 mode, _lib.dptr(u), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes), _lib.dptr(poses))
-        lp = torch.empty((Bp, H_max, 2), dtype=torch.float32, device=dev) if logprobs else None
+        lp = torch.empty((Bp, H_max, 2), dtype=torch.float32, device=dev) if logprobs or an is not None else None   # the record needs one beside it
+        areq = None if an is None else _lib.AltRequest(an, (Bp, H_max, 2), dev)
         self._mixed_call(args, dev, ctl=(ctl, n_ctl), lp=lp, given=(gblock, gtable), poses=(pblock, ptable), keep=kblock, style=sblock,
-                         bias=(btab, bidx), repeat=(rtab, n_rep), guide=gpair)      # the most general entry of the family; absent keywords travel as NULL
+                         bias=(btab, bidx), repeat=(rtab, n_rep), guide=gpair, alt=areq)      # the most general entry of the family; absent keywords travel as NULL
+        if not logprobs:
+            lp = None
         if prim is not None:      # the shadows' rows are their primaries': the caller sees B results
             codes, poses = codes.index_select(0, prim), poses.index_select(0, prim)
             lp = None if lp is None else lp.index_select(0, prim)
         inv_dev = torch.as_tensor(inverse, dtype=torch.int64, device=dev)
         codes, poses = codes.index_select(0, inv_dev), poses.index_select(0, inv_dev)     # back to submission order
+        if areq is not None:      # the keyword's own return value, behind the log-probabilities; sliced per clip where the call returns per clip
+            from talkshow_amd import sampling as S
+            alt = areq.result(inv_dev)
+            lp = None if lp is None else lp.index_select(0, inv_dev)
+            if _stacked:
+                return (codes, poses) + (() if lp is None else (lp,)) + (alt,)
+            return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) + (() if lp is None else (lp[b, :lens[b] // 4],)) +
+                    (S.Alternatives(*(x[b, :lens[b] // 4] for x in alt)),) for b in range(B)]
         if lp is not None:
             lp = lp.index_select(0, inv_dev)
             if _stacked:
@@ -440,7 +468,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return [(codes[b, :lens[b] // 4], poses[b, :4 * (lens[b] // 4)]) for b in range(B)]
 
     def _mixed_call(self, args, dev, ctl=(None, 0), lp=None, given=(None, None), poses=(None, None), keep=None, style=None, bias=(None, None),
-                    repeat=(None, 0), guide=(None, None)):
+                    repeat=(None, 0), guide=(None, None), alt=None):
         """Uploads the host blocks of a mixed pass, each once, and makes its one call (`_lib.body_mixed_call`): args the fixed arguments,
         the rest validated blocks (pairs: block and table) in slot order or None.  Given poses beside given codes are staged into one block."""
         from talkshow_amd.modules import upload
@@ -459,7 +487,8 @@ class TrainWrapper(TrainWrapperBaseClass):
             args, ctl=ctl[0], n_ctl=ctl[1], logprob=_lib.dptr(lp), given=_lib.dptr(gdev), given_rows=None if gdev is None else gtable.ctypes.data_as(i32p),
             poses=pose_piece, keep=_lib.dptr(kdev), style=_lib.dptr(sdev), style_rows=0 if style is None else int(style.shape[1]),
             bias=_lib.dptr(bdev), n_bias=0 if btab is None else int(btab.shape[0]), bias_index=None if btab is None else bidx.ctypes.data_as(i32p),
-            rep=repeat[0], n_rep=repeat[1], guide=None if guide[0] is None else guide[0].ctypes.data_as(i32p), guide_scale=_lib.fptr(guide[1]))
+            rep=repeat[0], n_rep=repeat[1], guide=None if guide[0] is None else guide[0].ctypes.data_as(i32p), guide_scale=_lib.fptr(guide[1]),
+            alt=None if alt is None else alt.ptr())
 
     def _stage_given(self, gblock, gtable, pblock, ptable, dev):
         """One given block for a pass that holds code clips AND pose clips: gblock / gtable from `_lib.given_block`, pblock / ptable from
@@ -574,7 +603,7 @@ class TrainWrapper(TrainWrapperBaseClass):
         return S.allow_bias(codes.reshape(-1, 2), self.generator.input_dim)
 
     def infer_padded_wav(self, wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps=30, lens_dev=None, sampling_table=None, given=None,
-                         given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
+                         given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None, alternatives=None):
         """The device part of a pass over recordings: wav (B,N_max) padded device block whose rows are ordered longest first, ns_host / ns_dev
         their sample counts (int32, host and device), ids / clip_index (B,) int64 device tensors in row order -> codes (B,H_max,2) with -1
         and poses (B,4 H_max,129) with 0 beyond a clip's own rows.  The mixed MFCC front-end feeds the mixed body pass on the device; the body
@@ -587,8 +616,11 @@ class TrainWrapper(TrainWrapperBaseClass):
         code_bias: `_lib.code_bias_block(...)` in ROW order — (tables (NB, 2, V) float32, index (B,) int32), both numpy — or None.
         repeat: `_lib.repeat_table(...)` in ROW order — (records, B) — or None.
         guide: (guide (B,) int32, scale (B,) float32) numpy tables in ROW order — the shadow's row of every row or -1, and the scales
-        (talkshow_hip.h, "guidance") — or None.  A shadow is a row of `wav` like any other."""
+        (talkshow_hip.h, "guidance") — or None.  A shadow is a row of `wav` like any other.
+        alternatives: n in [0, 8] (talkshow_hip.h, "alternatives") -> a fourth return value, a `sampling.Alternatives` over the (B,H_max,2)
+        positions in ROW order; a drawing mode only, not with guide.  None: three return values and the launches there always were."""
         from talkshow_amd.frontend import device_mfcc, mixed_tables
+        an = _lib.alt_request(alternatives, mode, "infer_padded_wav", guide=guide is not None)      # before anything is launched
         from talkshow_amd.modules import upload
         dev = self.generator._dev()
         rows = mixed_tables(ns_host, sr, 22000, fps)["mfcc_rows"]
@@ -633,8 +665,12 @@ class TrainWrapper(TrainWrapperBaseClass):
         pblock, ptable = given_poses if given_poses is not None else (None, None)
         if pblock is not None and int(pblock.shape[1]) // 4 > H_max:
             raise ValueError(f"infer_padded_wav: the given poses hold {int(pblock.shape[1])} frames but the pass has {H_max} code rows")
-        self._mixed_call(args, dev, ctl=sampling_table or (None, 0), given=(gblock, gtable), poses=(pblock, ptable), keep=given_keep, style=style,
-                         bias=(btab, bidx), repeat=(rtab, int(n_rep)), guide=guide or (None, None))
+        areq = None if an is None else _lib.AltRequest(an, (B, H_max, 2), dev)
+        lp = None if areq is None else torch.empty((B, H_max, 2), dtype=torch.float32, device=dev)      # the record needs one beside it
+        self._mixed_call(args, dev, ctl=sampling_table or (None, 0), lp=lp, given=(gblock, gtable), poses=(pblock, ptable), keep=given_keep, style=style,
+                         bias=(btab, bidx), repeat=(rtab, int(n_rep)), guide=guide or (None, None), alt=areq)
+        if areq is not None:
+            return codes, poses, lens_host, areq.result()
         return codes, poses, lens_host
 
     def guide_wav_rows(self, gent, order, wav, ns_host, ids, clip_index, sr, fps, pieces, who):
@@ -673,7 +709,8 @@ class TrainWrapper(TrainWrapperBaseClass):
         return wav, ns_host, upload(ns_host, dev), ids, clip_index, out, np.flatnonzero(~shadows)
 
     def generate_clips_from_wav(self, wavs, sr, ids, mode=_lib.TS_SAMPLE_PHILOX, seed=None, clip_index0=0, clip_indices=None, fps=30,
-                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None):
+                                sampling=None, given=None, given_poses=None, given_keep=None, style=None, code_bias=None, repeat=None, guide=None,
+                                alternatives=None):
         """`generate_clips` from RECORDINGS: wavs = list of (N_b,) sample arrays / tensors at `sr`, ids (B,) or one id for all -> list of
         (codes_b (H_b,2), poses_b (4 H_b,129)) in submission order.  The mixed MFCC front-end and the mixed body pass run back to back on the
         device: the MFCC rows never leave it and nothing synchronises.  A clip's result is bit-identical to
@@ -687,8 +724,12 @@ class TrainWrapper(TrainWrapperBaseClass):
         `generate_clips` — which codes a recording may use: one (2, V) table for all, or per recording None, a table or a dict.  repeat:
         as for `generate_clips` — a repetition penalty over a window of earlier codes: one record for all, or a list with one per recording.
         guide: as for `generate_clips` — guidance against a second conditioning, whose audio is given as "wav": (N_b,) samples at `sr`,
-        the recording's own sample count (None: the recording's own audio); one dict for all, or a list with None or a dict per recording."""
+        the recording's own sample count (None: the recording's own audio); one dict for all, or a list with None or a dict per recording.
+        alternatives: as for `generate_clips` — n in [0, 8]: every recording's tuple gains a `sampling.Alternatives` over its (H_b,2)
+        positions; a drawing mode only, not with guide."""
         from talkshow_amd.frontend import check_recordings, mixed_tables
+        guided = guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide))
+        an = _lib.alt_request(alternatives, mode, "generate_clips_from_wav", guide=guided)      # before anything is launched
         from talkshow_amd.modules import ids_in_row_order, pad_recordings, upload
         ns = check_recordings(wavs, "generate_clips_from_wav")
         B = len(ns)
@@ -740,6 +781,11 @@ class TrainWrapper(TrainWrapperBaseClass):
         if gent is not None:
             wav, ns_host, ns_dev, ids, clip_index, pieces, prim = self.guide_wav_rows(gent, order, wav, ns_host, ids, clip_index, sr, fps, pieces,
                                                                                        "generate_clips_from_wav")
+        if an is not None:      # no guidance here (refused above): the rows are the recordings
+            from talkshow_amd import sampling as S
+            codes, poses, lens, alt = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, alternatives=an, **pieces)
+            return [(codes[inverse[b], :int(lens[inverse[b]]) // 4], poses[inverse[b], :4 * (int(lens[inverse[b]]) // 4)],
+                     S.Alternatives(*(x[inverse[b], :int(lens[inverse[b]]) // 4] for x in alt))) for b in range(B)]
         codes, poses, lens = self.infer_padded_wav(wav, ns_host, ns_dev, sr, ids, clip_index, mode, seed, fps, **pieces)
         if prim is not None:      # the shadows' rows are their primaries': the caller sees B results
             pdev = torch.as_tensor(prim, dtype=torch.int64, device=dev)

@@ -39,6 +39,16 @@ class TsRepeat(C.Structure):
 
 
 _rp = C.POINTER(TsRepeat)
+
+
+class TsAltOut(C.Structure):
+    """ts_alt_out (include/talkshow_hip.h, "alternatives"): n and the four device arrays a pass fills."""
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("codes_dev", C.c_void_p), ("logprob_dev", C.c_void_p), ("entropy_dev", C.c_void_p),
+                ("rank_dev", C.c_void_p)]
+
+
+_ap = C.POINTER(TsAltOut)
+TS_ALT_MAX = 8
 TS_REPEAT_MAX_WINDOW = 64
 TS_SLOT_STATE_VERSION = 1
 
@@ -159,6 +169,10 @@ SIGNATURES = {
     "ts_guide_check": (_i, [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32), _i]),
     "ts_op_sample_guide": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
                                 _i, C.POINTER(C.c_int32), _i, _rp, _i, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), _vp]),
+    # alternatives: the host rule; one launch (ts_op_sample_repeat's arguments, then the record ahead of the stream)
+    "ts_alt_check": (_i, [_ap, _i]),
+    "ts_op_sample_alt": (_i, [_vp, _vp, _i, _i, _i, _vp, _u64, _i64, C.c_uint32, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
+                              _i, C.POINTER(C.c_int32), _i, _rp, _i, _vp, _vp, _ap, _vp]),
     "ts_pixelcnn_v_create": (_i, [_vp, C.POINTER(TsTensor), _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ts_pixelcnn_v_destroy": (None, [_vp]),
     "ts_pixelcnn_v_generate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -167,6 +181,9 @@ SIGNATURES = {
     # the step plus ctl / n_ctl, logprob, given / given_rows, style, bias / n_bias / bias_index, rep / n_rep ahead of the stream
     "ts_pixelcnn_stream_step_ctl": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
                                          C.POINTER(C.c_int32), _rp, _i, _vp]),
+    # the step plus the alternatives record ahead of the stream
+    "ts_pixelcnn_stream_step_alt": (_i, [_vp, _vp, _i, _i, _vp, _u64, _i64, _vp, _sp, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _i,
+                                         C.POINTER(C.c_int32), _rp, _i, _ap, _vp]),
     "ts_pixelcnn_stream_captures": (_i64, [_vp]),
     "ts_debug_rep_table": (_i, [_rp, _i, _i, _i, C.POINTER(C.c_int32)]),
     "ts_pixelcnn_stream_rows": (_i64, [_vp]),
@@ -359,6 +376,7 @@ MIXED_PIECES = {
     "bias": [_vp, _i, _i32p],         # bias_dev, n_bias, bias_index_host
     "repeat": [_rp, _i],              # rep_host, n_rep
     "guide": [_i32p, _fp],            # guide_host, guide_scale_host
+    "alt": [_ap],                     # alt (the ts_alt_out record)
 }
 
 
@@ -374,6 +392,13 @@ def _declare_ladder(stem, below, suffixes):
 _declare_ladder("ts_body_pixel_infer_mixed", (), ("ctl", "lp", "given", "keep", "style", "bias", "repeat"))
 _declare_ladder("ts_pixelcnn_generate_mixed", (), ("ctl", "lp", "given", "keep", "style", "bias", "repeat"))
 _declare_ladder("ts_body_pixel_infer_mixed", ("ctl", "lp"), ("poses", "poses_keep", "poses_style", "poses_bias", "poses_repeat"))
+# alternatives: the rung above the most general unguided entry of each family, under names of their own like the guided entries, named only
+# by a pass that brings the record
+ALT_ENTRY = {
+    "ts_body_pixel_infer_mixed_repeat": "ts_body_pixel_infer_alt",
+    "ts_body_pixel_infer_mixed_poses_repeat": "ts_body_pixel_infer_alt_poses",
+    "ts_pixelcnn_generate_mixed_repeat": "ts_pixelcnn_generate_alt",
+}
 # guidance: the most general entry of each family plus the guide piece ahead of the stream, under names of their own
 GUIDED_ENTRY = {
     "ts_body_pixel_infer_mixed_repeat": "ts_body_pixel_infer_guided",
@@ -382,6 +407,8 @@ GUIDED_ENTRY = {
 }
 for _plain, _guided in GUIDED_ENTRY.items():
     SIGNATURES[_guided] = (_i, SIGNATURES[_plain][1][:-1] + MIXED_PIECES["guide"] + [_vp])
+for _plain, _alt in ALT_ENTRY.items():
+    SIGNATURES[_alt] = (_i, SIGNATURES[_plain][1][:-1] + MIXED_PIECES["alt"] + [_vp])
 
 _lib = None
 
@@ -447,7 +474,7 @@ def face_generate_mixed(handle, wav, ns, ns_dev, frames, frames_dev, B, N_max, T
 
 
 def _mixed_tail(middle, ctl=None, n_ctl=0, logprob=None, keep=None, style=None, style_rows=0, bias=None, n_bias=0, bias_index=None,
-                rep=None, n_rep=0, guide=None, guide_scale=None, stream=None):
+                rep=None, n_rep=0, guide=None, guide_scale=None, alt=None, stream=None):
     """What follows the fixed arguments of a most general mixed entry (`..._repeat`), `middle` being its given or poses piece: every
     keyword is an already-converted value (pointer, int, ctypes array), an absent one travels as None / 0.  guide / guide_scale (the
     guided entries' piece, `GUIDED_ENTRY`) sit ahead of the stream only when a guide table came: without one the tail is the `_repeat`
@@ -459,6 +486,10 @@ def _mixed_tail(middle, ctl=None, n_ctl=0, logprob=None, keep=None, style=None, 
         if guide_scale is None:
             raise ValueError("_mixed_tail: a guide table needs its scales")
         tail += (guide, guide_scale)
+    if alt is not None:      # the `_alt` entries' piece (`ALT_ENTRY`), likewise only when the record came
+        if guide is not None:
+            raise NotImplementedError("alternatives are not offered on a guided pass")
+        tail += (alt,)
     return (*tail, stream)
 
 
@@ -472,6 +503,8 @@ def body_mixed_args(fixed, given=None, given_rows=None, poses=None, **pieces):
     name = "ts_body_pixel_infer_mixed_poses_repeat" if poses is not None else "ts_body_pixel_infer_mixed_repeat"
     if pieces.get("guide") is not None:      # the guided entries only for a pass that brings the table
         name = GUIDED_ENTRY[name]
+    elif pieces.get("alt") is not None:        # and the alternatives entries only for a pass that brings the record
+        name = ALT_ENTRY[name]
     if poses is not None:
         return name, (*fixed, *_mixed_tail(tuple(poses), **pieces))
     return name, (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
@@ -488,6 +521,8 @@ def pixelcnn_mixed_args(fixed, given=None, given_rows=None, **pieces):
     name = "ts_pixelcnn_generate_mixed_repeat"
     if pieces.get("guide") is not None:
         name = GUIDED_ENTRY[name]
+    elif pieces.get("alt") is not None:
+        name = ALT_ENTRY[name]
     return name, (*fixed, *_mixed_tail((given, given_rows if given is not None else None, None), **pieces))
 
 
@@ -568,6 +603,45 @@ def logprob_request(logprobs, shape, device=None):
     if device is not None and str(logprobs.device).split(":")[0] != str(device).split(":")[0]:
         raise ValueError(f"logprobs output must live on {device}, got {logprobs.device}")
     return logprobs
+
+
+class AltRequest:
+    """The `alternatives=n` keyword of one call: the four device tensors over `shape` (the codes' positions, (..., 2)) and the ts_alt_out
+    record that names them.  `result()` is what the call appends to its return value."""
+
+    def __init__(self, n, shape, device):
+        self.n = int(n)
+        shape = tuple(int(x) for x in shape)
+        self.codes = torch.empty(shape + (self.n,), dtype=torch.int32, device=device)
+        self.logprobs = torch.empty(shape + (self.n,), dtype=torch.float32, device=device)
+        self.entropy = torch.empty(shape, dtype=torch.float32, device=device)
+        self.rank = torch.empty(shape, dtype=torch.int32, device=device)
+        self.record = TsAltOut(self.n, 0, self.codes.data_ptr() if self.n else None, self.logprobs.data_ptr() if self.n else None,
+                               self.entropy.data_ptr(), self.rank.data_ptr())
+
+    def ptr(self):
+        return C.pointer(self.record)
+
+    def result(self, index=None):
+        """sampling.Alternatives of the whole block, or of rows `index` (an int64 device tensor) of its first axis."""
+        from . import sampling
+        pick = (lambda t: t) if index is None else (lambda t: t.index_select(0, index))
+        return sampling.Alternatives(pick(self.codes).long(), pick(self.logprobs), pick(self.entropy), pick(self.rank).long())
+
+
+def alt_request(alternatives, mode, who, guide=False):
+    """The `alternatives=` keyword, checked before any device work: None -> None (the entries without the record); otherwise n in [0, 8]
+    (ValueError), a drawing mode (ValueError: greedy is sampling=(1, 1, 1) under Philox) and no guidance (NotImplementedError)."""
+    if alternatives is None:
+        return None
+    from . import sampling
+    n = sampling.alt_count(alternatives)
+    if mode not in (TS_SAMPLE_UNIFORMS, TS_SAMPLE_PHILOX):
+        raise ValueError(f"{who}: alternatives need a drawing mode (TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX); a greedy decode with "
+                         "alternatives is sampling=(1, 1, 1) under TS_SAMPLE_PHILOX")
+    if guide:
+        raise NotImplementedError(f"{who}: alternatives are not offered on a guided pass or a session with pairs")
+    return n
 
 
 def given_block(given, rows, V, order=None, who="given", keep=None):

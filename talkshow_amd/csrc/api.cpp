@@ -273,6 +273,10 @@ static int body_mixed(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *
     if (o.rep_host && body_repeat_check("ts_body_pixel_infer_mixed_repeat", a.mode, B, 1, o.rep_host, o.n_rep) != 0) return 1;
     TS_TRY(mixed_given_check("ts_body_pixel_infer_mixed_keep", "ts_body_pixel_infer_mixed_given", o, a.lens_host, B));   // a bad row table is refused before the first launch of the pass, too
     if (o.guide_host && body_guide_check("ts_body_pixel_infer_guided", a.mode, B, o, a.lens_host) != 0) return 1;
+    if (o.alt) {   // last, and ahead of the audio encoder's launches
+        if (ts_alt_check(o.alt, a.mode) != 0) return 1;
+        if (!o.logprob) return fail("ts_body_pixel_infer_alt: the record needs logprob_dev beside it");
+    }
     BodyWork &w = body_work(s);
     TS_TRY(w.feat.ensure((size_t)B * H * convnet_hidden(ae) * sizeof(float)));
     TS_TRY(ts_audioenc_forward_masked(ae, mfcc, a.lens_dev, B, a.rows, w.feat.f(), s));
@@ -383,6 +387,23 @@ int ts_body_pixel_infer_mixed_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae 
     o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
     o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
     o.rep_host = rep_host, o.n_rep = n_rep;
+    return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
+}
+
+// the same pass with "alternatives" (talkshow_hip.h): the record of the four outputs over the pass's T_max / 4 code rows.  alt == NULL:
+// exactly the entry above
+int ts_body_pixel_infer_alt(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                  const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                  uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host, int n_ctl,
+                                  float *logprob, const int64_t *given, const int32_t *given_rows_host, const int32_t *given_rows_dev,
+                                  const uint8_t *keep, const float *style, int style_rows, const float *bias, int n_bias,
+                                  const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const ts_alt_out *alt, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.alt = alt;
     return body_mixed(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 
@@ -530,6 +551,24 @@ int ts_body_pixel_infer_mixed_poses_repeat(ts_convnet *ae, ts_pixelcnn *pix, ts_
     o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
     o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
     o.rep_host = rep_host, o.n_rep = n_rep;
+    return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
+}
+
+// the same with "alternatives" (alt == NULL: exactly the entry above).  The encoders never see the record: the codes they find are ranked
+// and scored as given codes are
+int ts_body_pixel_infer_alt_poses(ts_convnet *ae, ts_pixelcnn *pix, ts_vqvae *vb, ts_vqvae *vh, const float *mfcc, const int64_t *ids,
+                                        const int32_t *lens_host, const int32_t *lens_dev, int B, int T_max, int mode, const float *uniforms,
+                                        uint64_t seed, const int64_t *clip_index, int64_t *codes, float *poses, const ts_sampling *ctl_host,
+                                        int n_ctl, float *logprob, const float *given_poses, int P_max, const int32_t *pose_lens_host,
+                                        const int32_t *pose_lens_dev, const uint8_t *keep, const float *style, int style_rows,
+                                        const float *bias, int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep,
+                                        const ts_alt_out *alt, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given_poses = given_poses, o.P_max = P_max, o.pose_lens_host = pose_lens_host, o.pose_lens_dev = pose_lens_dev, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.alt = alt;
     return body_mixed_poses(ae, pix, vb, vh, mfcc, {ids, lens_host, lens_dev, B, T_max, mode, uniforms, seed, clip_index, codes}, poses, o, (hipStream_t)stream);
 }
 

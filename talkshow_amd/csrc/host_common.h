@@ -298,6 +298,7 @@ struct MixedOpts {
     int n_rep = 0;
     const int32_t *guide_host = nullptr;     // guidance: (B,) the shadow's slot of every clip slot or -1, and (B,) the scales
     const float *guide_scale_host = nullptr;
+    const ts_alt_out *alt = nullptr;         // alternatives: the record of the four outputs
     // the body wrapper only: given poses
     const float *given_poses = nullptr;
     int P_max = 0;
@@ -328,8 +329,9 @@ inline int mixed_given_check(const char *who_keep, const char *who_given, const 
 struct SamplerNames {
     const char *ctl, *bias, *rep, *keep, *given;
     const char *guide = "ts_guide_check";   // neutral records under a guide table
+    const char *alt = "alternatives";       // the refusals of a pass that brings a ts_alt_out record
 };
-inline SamplerNames sampler_names(const char *who) { return {who, who, who, who, who, who}; }   // an entry that names itself throughout
+inline SamplerNames sampler_names(const char *who) { return {who, who, who, who, who, who, who}; }   // an entry that names itself throughout
 struct SamplerTables {
     int B = 0;
     std::vector<SampleCtl> ctl;        // B records where a table, a bias or repetition records came (neutral ones without a table), else empty
@@ -340,6 +342,9 @@ struct SamplerTables {
     // runs the BIAS and REP arithmetic: ctl, rep (window 0) and no_bias are then filled with neutral values where their pieces did not come
     std::vector<int32_t> guide_role;
     std::vector<float> guide_scale;
+    // alternatives: the record came (checked).  ctl, rep (window 0) and no_bias are then filled with neutral values where their pieces did
+    // not come, as under guidance: the pass runs on the most general unguided samplers
+    bool alt = false;
     // Launches nothing.  lens_host: the frames a clip's given rows must fit (>> 2), read only where given codes came
     int build(const MixedOpts &o, int B, int V, int mode, const int32_t *lens_host, const SamplerNames &who);
 };

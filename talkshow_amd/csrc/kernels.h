@@ -711,6 +711,24 @@ struct SampleGivenParams {
     long keep_stride;
 };
 hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream);
+// "alternatives" (talkshow_hip.h; vq.hip: sample_ctl_alt_kernel, sample_ctl_alt_given_kernel): the launch of the most general unguided
+// family — g.c.ctl, g.c.logprob, g.c.bias_index, g.c.rep and g.c.rep_ring are all required (neutral records, an index of -1, records of
+// window 0 where the caller brought none); g.rows == nullptr: no given rows — which also writes, for the row of clip b at element e =
+// b * stride: codes[e * n + j] / logprob[e * n + j] (j < n; null for n = 0), entropy[e], rank[e].  A sibling of the structs above again:
+// they keep their arguments.
+constexpr int SAMPLE_ALT_MAX = 8;
+struct SampleAltParams {
+    SampleGivenParams g;
+    int n;                     // 0 .. SAMPLE_ALT_MAX
+    int32_t *codes;
+    float *logprob;
+    float *entropy;
+    int32_t *rank;
+    long stride;
+};
+hipError_t launch_sample_alt(const SampleAltParams &p, hipStream_t stream);
+// alternatives of a mixed pass: rows at or beyond a clip's own H_b = lens[b] >> 2 hold -1, 0, 0, -1 (codes, log-probabilities, entropy, rank)
+hipError_t launch_mask_alt(int32_t *codes, float *logprob, float *entropy, int32_t *rank, int n, int B, int H, const int *lens, hipStream_t stream);
 // logprob (B,H,2) rows at or beyond a clip's own H_b = lens[b] >> 2 become 0 (mixed passes; beside launch_mask_codes)
 hipError_t launch_mask_logprob(float *logprob, int B, int H, const int *lens, hipStream_t stream);
 // Per-clip fixed-order fp64 sums of logprob (B,H,2): out[b] = {body column, hand column, body + hand} over rows r < H_b (lens == nullptr:

@@ -120,6 +120,10 @@ struct ts_pixelcnn {
                                            // reads min(r, W) entries, all written earlier in the same pass by the same slot
         DevBuf guide_tab, guide_scl;       // passes with guidance: the role of every clip SLOT (int32: -1 plain, g >= 0 the shadow's slot, -2 a shadow) and
                                            // the scale of every primary (fp32), written in stream order ahead of the pass; sized by capB in ensure_work
+        DevBuf alt_int;                    // passes with alternatives: what the captured samplers write, four blocks of capB * capH * 2 positions each —
+                                           // codes [.][8] int32, log-probabilities [.][8] fp32, entropy fp32, rank int32 — laid out (B,rows,2,n) / (B,rows,2)
+                                           // from the block's start; allocated by the first such pass, sized by the Work's capacity alone, so it moves only
+                                           // when ensure_work has dropped the graphs that write it
         hipStream_t cap_stream = nullptr;
         // Captured graphs, least recently used out first: at most GRAPH_CAP per Work.  Keys: (B, H, H0, mode, 0) = a whole one-shot call;
         // (B, Hc, -(1 + phase), mode, 0) = Hc rows of a chunked one-shot call; (B, Hc, 1000 + phase, mode, 0) = a streaming step (in a session's own Work);
@@ -133,7 +137,7 @@ struct ts_pixelcnn {
         // kernels, which read bias_tab and bias_idx; neither the tables' content nor their number is part of the key), bit 6 for a pass with a repetition penalty (its samplers are the
         // sample_ctl_rep kernels, which read rep_tab and bias_idx and read and write rep_ring; the records are not part of the key), bit 7 for the steps of a
         // session that has restarted a slot (their samplers read the session's row_origin and the clip table; which slots restarted, and where, is not part of the key), bit 8 for a pass
-        // with guidance (its samplers are the sample_ctl_guide kernels, which read guide_tab and guide_scl beside what the sample_ctl_rep kernels read; roles and scales are not part of the key); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
+        // with guidance (its samplers are the sample_ctl_guide kernels, which read guide_tab and guide_scl beside what the sample_ctl_rep kernels read; roles and scales are not part of the key), bit 9 for a pass with alternatives (its samplers are the sample_ctl_alt kernels, which write alt_int; n sits in the bits above, value n << 10); 0 otherwise: runs with none find exactly the graphs they found before the field existed; the
         // tables' CONTENT is not part of the key (a replay reads what the call wrote).
         // At most GRAPH_CAP unpinned graphs + PIN_CAP pinned ones per Work.
         typedef std::tuple<int, int, int, int, int, int> Key;
@@ -376,6 +380,11 @@ struct RunCfg {
     // c.rep and c.rep_ring are set too (neutral records, an index of -1, records of window 0 when the call brought none)
     const int32_t *guide_role = nullptr;
     const float *guide_scale = nullptr;
+    // "alternatives": the caller's record, or null: the samplers without them.  With it c.ctl, c.bias_index, c.rep and c.rep_ring are set too
+    // (neutral records, an index of -1, records of window 0 when the call brought none).  alt: set by run_rows, the arrays the samplers
+    // address, laid out like `codes` (staging or the caller's)
+    const ts_alt_out *alt_src = nullptr;
+    ts_alt_out alt = {};
     // "slot restart": the session's (slabB(),) table of the row at which every slot's current clip began, or null (a session that never
     // restarted a slot, and every one-shot call).  With it c.clip_table is set too
     const int32_t *row_origin = nullptr;
@@ -924,7 +933,26 @@ int launch_sampler(ts_pixelcnn *p, const RunCfg &c, int r, int j, hipStream_t s)
     cp.bias = c.bias, cp.bias_index = c.bias_index, cp.bias_col = j;
     cp.rep = c.rep, cp.rep_ring = c.rep_ring;
     cp.guide_role = c.guide_role, cp.guide_scale = c.guide_scale;
-    if (c.given_rows) {
+    if (c.alt_src) {   // the given variants where the pass brought given rows
+        SampleAltParams ap;
+        std::memset(&ap, 0, sizeof(ap));
+        ap.g.c = cp;
+        if (c.given_rows) {
+            ap.g.rows = c.given_rows;
+            ap.g.given = c.given + (size_t)ro * 2 + j;
+            ap.g.given_stride = (long)sH * 2;
+            ap.g.keep = c.keep ? c.keep + (size_t)ro * 2 + j : nullptr;
+            ap.g.keep_stride = (long)sH * 2;
+        }
+        const size_t pos = (size_t)ro * 2 + j;
+        ap.n = c.alt.n;
+        ap.codes = c.alt.n ? c.alt.codes_dev + pos * c.alt.n : nullptr;
+        ap.logprob = c.alt.n ? c.alt.logprob_dev + pos * c.alt.n : nullptr;
+        ap.entropy = c.alt.entropy_dev + pos;
+        ap.rank = c.alt.rank_dev + pos;
+        ap.stride = (long)sH * 2;
+        TS_HIP(launch_sample_alt(ap, s));
+    } else if (c.given_rows) {
         SampleGivenParams gp;
         gp.c = cp;
         gp.rows = c.given_rows;
@@ -1364,7 +1392,7 @@ namespace {
 inline int sampler_bits(const RunCfg &c, const float *logprob) {
     const bool given = c.given_rows;
     return (c.ctl ? 1 : 0) | (logprob ? 2 : 0) | (given ? 4 : 0) | (given && c.keep_src ? 8 : 0) | (c.style ? 16 : 0) | (c.bias ? 32 : 0) | (c.rep ? 64 : 0) |
-           (c.row_origin ? 128 : 0) | (c.guide_role ? 256 : 0);
+           (c.row_origin ? 128 : 0) | (c.guide_role ? 256 : 0) | (c.alt_src ? 512 | (c.alt_src->n << 10) : 0);
 }
 // The tables reach the Work in stream order as kernel ARGUMENTS (launch_put_words): nothing on the host has to outlive the call, nothing
 // synchronises, and any number of calls — each with its own tables — may be queued behind each other.
@@ -1401,6 +1429,14 @@ int stage_sampler_tables(ts_pixelcnn *p, ts_pixelcnn::Work *w, const SamplerTabl
             if (!o.bias) TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), t.no_bias.data(), B, s));
         }
     }
+    if (t.alt) {   // what the REP path reads where the pass brought no records / no tables, and the staging block of the four outputs
+        MiscScope ms(ctx, s);
+        if (!o.rep_host) {
+            TS_HIP(launch_put_words(static_cast<int *>(w->rep_tab.p), reinterpret_cast<const int *>(t.rep.data()), (long)B * 4, s));
+            if (!o.bias) TS_HIP(launch_put_words(static_cast<int *>(w->bias_idx.p), t.no_bias.data(), B, s));
+        }
+        TS_TRY(w->alt_int.ensure((size_t)w->capB * w->capH * 2 * (2 * SAMPLE_ALT_MAX + 2) * sizeof(float)));
+    }
     return 0;
 }
 // Every table is indexed by the clip's slot in the pass (in a mixed pass the active clips are a prefix, so the slot is the same in every
@@ -1422,6 +1458,13 @@ void bind_sampler_tables(RunCfg &c, ts_pixelcnn::Work *w, const MixedOpts &o) {
         c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
         c.guide_role = w->guide_tab.i();
         c.guide_scale = w->guide_scl.f();
+    }
+    if (o.alt) {   // the alternatives samplers read everything the sample_ctl_rep kernels read
+        c.ctl = static_cast<const SampleCtl *>(w->ctl_tab.p);
+        c.rep = static_cast<const SampleRep *>(w->rep_tab.p);
+        c.rep_ring = static_cast<int32_t *>(w->rep_ring.p);
+        c.bias_index = static_cast<const int32_t *>(w->bias_idx.p);
+        c.alt_src = o.alt;
     }
 }
 
@@ -1496,6 +1539,7 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
         if (out_H != c.H && c.logits) return fail("pixelcnn: eager rows with logits write the caller's arrays whole");
         c.codes = codes;
         c.logprob = logprob;
+        if (c.alt_src) c.alt = *c.alt_src;
         c.uniforms = uniforms;
         c.given = c.given_src;
         c.keep = c.keep_src;
@@ -1513,6 +1557,14 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
                                 hipMemcpyDeviceToDevice, s));
     c.codes = static_cast<int64_t *>(w->codes_int.p);
     c.logprob = logprob ? w->lp_int.f() : nullptr;
+    if (c.alt_src) {   // the four blocks of alt_int
+        const size_t cap = (size_t)w->capB * w->capH * 2;
+        c.alt = *c.alt_src;
+        c.alt.codes_dev = static_cast<int32_t *>(w->alt_int.p);
+        c.alt.logprob_dev = w->alt_int.f() + cap * SAMPLE_ALT_MAX;
+        c.alt.entropy_dev = w->alt_int.f() + cap * 2 * SAMPLE_ALT_MAX;
+        c.alt.rank_dev = static_cast<int32_t *>(w->alt_int.p) + cap * (2 * SAMPLE_ALT_MAX + 1);
+    }
     c.uniforms = c.mode == TS_SAMPLE_UNIFORMS ? w->unif_int.f() : nullptr;
     c.dyn = static_cast<const uint64_t *>(w->dyn.p);
     if (c.mode == TS_SAMPLE_UNIFORMS && !capture_only)
@@ -1554,6 +1606,16 @@ int run_rows(ts_pixelcnn *p, RunCfg c, int r_begin, int r_end, bool graph, const
     if (logprob)   // the same rows of the caller's log-probability array, the way the codes travel
         TS_HIP(hipMemcpy2DAsync(logprob + (size_t)c.out_row0 * 2, (size_t)out_H * 2 * sizeof(float), w->lp_int.p,
                                 (size_t)c.H * 2 * sizeof(float), (size_t)c.H * 2 * sizeof(float), c.B, hipMemcpyDeviceToDevice, s));
+    if (c.alt_src) {   // and of the four alternatives arrays: n words per position, then one
+        const ts_alt_out &d = *c.alt_src;
+        const size_t e = sizeof(float), n = (size_t)d.n;
+        struct { void *dst; const void *src; size_t words; } blocks[4] = {{d.codes_dev, c.alt.codes_dev, n}, {d.logprob_dev, c.alt.logprob_dev, n},
+                                                                          {d.entropy_dev, c.alt.entropy_dev, 1}, {d.rank_dev, c.alt.rank_dev, 1}};
+        for (auto &m : blocks)
+            if (m.words)
+                TS_HIP(hipMemcpy2DAsync(static_cast<char *>(m.dst) + (size_t)c.out_row0 * 2 * m.words * e, (size_t)out_H * 2 * m.words * e, m.src,
+                                        (size_t)c.H * 2 * m.words * e, (size_t)c.H * 2 * m.words * e, c.B, hipMemcpyDeviceToDevice, s));
+    }
     return 0;
 }
 
@@ -1792,6 +1854,24 @@ int ts_pixelcnn_generate_mixed_repeat(ts_pixelcnn *p, const int64_t *label, cons
     return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
 }
 
+// the same pass with "alternatives" (talkshow_hip.h): the record of the four outputs, (B,H_max,2,n) and (B,H_max,2).  The samplers are the
+// sample_ctl_alt kernels on graph keys of their own (bit 9, n above it); a call without a table runs on neutral records, one without records
+// on windows of 0, one without tables on an index of -1.  alt == NULL: the _repeat entry, launch for launch
+int ts_pixelcnn_generate_alt(ts_pixelcnn *p, const int64_t *label, const float *aud, const int32_t *lens_host, const int32_t *lens_dev,
+                                   int B, int H_max, int mode, const float *uniforms, uint64_t seed, const int64_t *clip_index,
+                                   int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob, const int64_t *given,
+                                   const int32_t *given_rows_host, const int32_t *given_rows_dev, const uint8_t *keep, const float *style,
+                                   int style_rows, const float *bias_dev, int n_bias, const int32_t *bias_index_host,
+                                   const ts_repeat *rep_host, int n_rep, const ts_alt_out *alt, void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host, o.keep = keep;
+    o.style = style, o.style_rows = style_rows, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.alt = alt;
+    return pixelcnn_generate_mixed(p, aud, {label, lens_host, lens_dev, B, H_max, mode, uniforms, seed, clip_index, codes}, o, (hipStream_t)stream);
+}
+
 // the same pass under "guidance" (talkshow_hip.h): guide_host (B,) the shadow's slot of every clip slot or -1, guide_scale_host (B,).  Roles
 // and scales are copied into the Work in stream order ahead of the pass (kernel arguments); the samplers are the sample_ctl_guide kernels
 // on graph keys of their own (bit 8); a call without a sampling table runs on neutral records.  guide_host == NULL: the _repeat entry,
@@ -1836,7 +1916,8 @@ int ts::pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPas
     SamplerTables t;
     TS_TRY(t.build(o, B, p->V, mode, a.lens_host,
                    {"ts_pixelcnn_generate_mixed_ctl", "ts_pixelcnn_generate_mixed_bias", "ts_pixelcnn_generate_mixed_repeat",
-                    "ts_pixelcnn_generate_mixed_keep", "ts_pixelcnn_generate_mixed_given", "ts_pixelcnn_generate_guided"}));
+                    "ts_pixelcnn_generate_mixed_keep", "ts_pixelcnn_generate_mixed_given", "ts_pixelcnn_generate_guided",
+                    "ts_pixelcnn_generate_alt"}));
     ts_ctx *ctx = p->ctx;
     ts_pixelcnn::Work *w = &p->work(s);
     TS_TRY(ensure_work(p, w, B, H_max));
@@ -1859,6 +1940,8 @@ int ts::pixelcnn_generate_mixed(ts_pixelcnn *p, const float *aud, const MixedPas
     MiscScope ms(ctx, s);
     TS_HIP(launch_mask_codes(a.codes, B, H_max, a.lens_dev, s));   // rows at or beyond a clip's own H_b (surplus rows, rows never run): -1
     if (o.logprob) TS_HIP(launch_mask_logprob(o.logprob, B, H_max, a.lens_dev, s));   // and their log-probabilities: 0
+    if (o.alt)   // and their alternatives: -1, 0, 0, -1
+        TS_HIP(launch_mask_alt(o.alt->codes_dev, o.alt->logprob_dev, o.alt->entropy_dev, o.alt->rank_dev, o.alt->n, B, H_max, a.lens_dev, s));
     return 0;
 }
 
@@ -2101,6 +2184,21 @@ int ts_pixelcnn_stream_step_ctl(ts_pixelcnn_stream *st, const float *aud, int Hc
     o.given = given, o.given_rows_host = given_rows_host;
     o.style = style, o.style_rows = 1, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
     o.rep_host = rep_host, o.n_rep = n_rep;
+    return stream_step(st, aud, Hc, mode, uniforms, seed, clip0, codes, o, (hipStream_t)stream);
+}
+
+// ts_pixelcnn_stream_step_ctl plus "alternatives" for the step's rows (talkshow_hip.h); alt == NULL: that entry, exactly
+int ts_pixelcnn_stream_step_alt(ts_pixelcnn_stream *st, const float *aud, int Hc, int mode, const float *uniforms, uint64_t seed,
+                                int64_t clip0, int64_t *codes, const ts_sampling *ctl_host, int n_ctl, float *logprob,
+                                const int64_t *given, const int32_t *given_rows_host, const float *style, const float *bias_dev,
+                                int n_bias, const int32_t *bias_index_host, const ts_repeat *rep_host, int n_rep, const ts_alt_out *alt,
+                                void *stream) {
+    MixedOpts o;
+    o.ctl_host = ctl_host, o.n_ctl = n_ctl, o.logprob = logprob;
+    o.given = given, o.given_rows_host = given_rows_host;
+    o.style = style, o.style_rows = 1, o.bias = bias_dev, o.n_bias = n_bias, o.bias_index_host = bias_index_host;
+    o.rep_host = rep_host, o.n_rep = n_rep;
+    o.alt = alt;
     return stream_step(st, aud, Hc, mode, uniforms, seed, clip0, codes, o, (hipStream_t)stream);
 }
 

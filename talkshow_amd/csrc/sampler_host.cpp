@@ -159,6 +159,19 @@ int ts_guide_check(const int32_t *guide_host, const float *scale_host, const int
     return 0;
 }
 
+// Host only ("alternatives"): the record of a pass and the mode it runs in
+int ts_alt_check(const ts_alt_out *alt, int mode) {
+    if (!alt) return fail("ts_alt_check: bad argument");
+    if (alt->n < 0 || alt->n > TS_ALT_MAX)
+        return fail("ts_alt_check: n = " + std::to_string(alt->n) + " is outside [0, " + std::to_string(TS_ALT_MAX) + "]");
+    if (alt->reserved != 0) return fail("ts_alt_check: the reserved word is " + std::to_string(alt->reserved) + ", not 0");
+    if (!alt->entropy_dev || !alt->rank_dev) return fail("ts_alt_check: entropy_dev and rank_dev are required");
+    if (alt->n > 0 && (!alt->codes_dev || !alt->logprob_dev)) return fail("ts_alt_check: n > 0 needs codes_dev and logprob_dev");
+    if (mode != TS_SAMPLE_UNIFORMS && mode != TS_SAMPLE_PHILOX)
+        return fail("ts_alt_check: alternatives need TS_SAMPLE_UNIFORMS or TS_SAMPLE_PHILOX (per-clip greedy is top_k = 1 under a drawing mode)");
+    return 0;
+}
+
 // Host only: the rule every _given entry applies to its row table before anything is launched
 int ts_given_rows_check(const int32_t *given_rows_host, const int32_t *lens_host, int B) {
     if (!given_rows_host || !lens_host || B < 1) return fail("ts_given_rows_check: bad argument");
@@ -213,6 +226,19 @@ int ts::SamplerTables::build(const MixedOpts &o, int B_, int V, int mode, const 
         if (!o.bias && no_bias.empty()) no_bias.assign(B, -1);
         if (rep.empty()) rep.assign(B, SampleRep{0, 0.0f, 0.0f, 0});
     }
+    if (o.alt) {   // behind every check there was: the refusals above keep their order and text
+        TS_TRY(ts_alt_check(o.alt, mode));
+        if (o.guide_host) return fail(std::string(who.alt) + ": a guided pass (a session with pairs) returns no alternatives");
+        if (!o.logprob) return fail(std::string(who.alt) + ": the record needs logprob_dev beside it");
+        if (ctl.empty()) {
+            const ts_sampling neutral = {1.0f, 1.0f, 0, 0};
+            TS_TRY(ctl_table(&neutral, 1, B, V, mode, who.alt, ctl));
+        }
+        // the samplers run the BIAS and REP paths: an index of -1 and records of window 0 are "same arithmetic" there
+        if (!o.bias && no_bias.empty()) no_bias.assign(B, -1);
+        if (rep.empty()) rep.assign(B, SampleRep{0, 0.0f, 0.0f, 0});
+        alt = true;
+    }
     return 0;
 }
 
@@ -259,7 +285,7 @@ int op_sample(const OpSample &a) {
     if (a.column != 0 && a.column != 1) return fail(who + ": column is 0 (body) or 1 (hand)");
     if (a.modes && (a.mode < 0 || a.mode >= a.modes)) return fail(who + ": bad mode");
     if (a.mode == TS_SAMPLE_UNIFORMS && !a.uniforms) return fail(who + ": uniforms required");
-    const bool pieces = o.bias || o.rep_host || o.guide_host;   // they run on neutral records where no table came
+    const bool pieces = o.bias || o.rep_host || o.guide_host || o.alt;   // they run on neutral records where no table came
     if (a.kept && !o.ctl_host && !pieces) return fail(who + ": kept_dev needs a table");
     const bool given_rows = a.forced_host || a.given_rows_host;
     if (given_rows) {
@@ -346,6 +372,10 @@ int op_sample(const OpSample &a) {
         gp.given_stride = 1;
         gp.keep = a.keep;
         gp.keep_stride = 1;
+    }
+    if (t.alt) {   // one position per row
+        TS_HIP(launch_sample_alt(SampleAltParams{gp, o.alt->n, o.alt->codes_dev, o.alt->logprob_dev, o.alt->entropy_dev, o.alt->rank_dev, 1}, s));
+    } else if (given_rows) {
         TS_HIP(launch_sample_given(gp, s));
     } else if (gp.c.ctl) {
         TS_HIP(launch_sample_ctl(gp.c, s));
@@ -444,6 +474,22 @@ int ts_op_sample_guide(ts_ctx *ctx, const float *logits, int B, int V, int mode,
     a.kept = kept, a.logprob = logprob, a.given_rows_host = given_rows_host, a.keep = keep, a.given = given, a.logits_copy = logits_copy;
     a.o.bias = bias, a.o.n_bias = n_bias, a.o.bias_index_host = bias_index_host, a.o.rep_host = rep_host, a.o.n_rep = n_rep;
     a.o.guide_host = guide_host, a.o.guide_scale_host = scale_host;
+    a.column = column, a.history = history, a.ring_out = ring_out;
+    return op_sample(a);
+}
+
+// The same launch with "alternatives" (kernel-level tests call it): ts_op_sample_repeat's arguments, where rep_host and bias may both be NULL
+// (records of window 0, an index of -1), then the record: codes / logprob (B,n), entropy / rank (B).  alt == NULL is refused
+int ts_op_sample_alt(ts_ctx *ctx, const float *logits, int B, int V, int mode, const float *uniforms, uint64_t seed, int64_t clip_index0,
+                     uint32_t position, const ts_sampling *ctl_host, int n_ctl, int64_t *idx, float *logprob, const int32_t *given_rows_host,
+                     const uint8_t *keep, const int64_t *given, uint8_t *kept, float *logits_copy, const float *bias, int n_bias,
+                     const int32_t *bias_index_host, int column, const ts_repeat *rep_host, int n_rep, const int32_t *history,
+                     int32_t *ring_out, const ts_alt_out *alt, void *stream) {
+    OpSample a{"ts_op_sample_alt", !alt || (bias && !bias_index_host), 0, ctx, logits, B, V, mode, uniforms, seed, clip_index0, position, idx, stream};
+    a.o.ctl_host = ctl_host, a.o.n_ctl = n_ctl;
+    a.kept = kept, a.logprob = logprob, a.given_rows_host = given_rows_host, a.keep = keep, a.given = given, a.logits_copy = logits_copy;
+    a.o.bias = bias, a.o.n_bias = n_bias, a.o.bias_index_host = bias_index_host, a.o.rep_host = rep_host, a.o.n_rep = n_rep;
+    a.o.alt = alt, a.o.logprob = logprob;
     a.column = column, a.history = history, a.ring_out = ring_out;
     return op_sample(a);
 }

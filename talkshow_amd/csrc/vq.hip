@@ -1422,6 +1422,61 @@ __device__ __forceinline__ float sample_logprob_value(float d, float S, bool kep
     return kept ? (float)((double)d - log((double)S)) : (float)log(0.0);
 }
 
+// ---- "alternatives" (talkshow_hip.h): what the ALT flag of the body below adds ----
+// a token's place in step 2's ranking as one integer: a higher key first, a lower index first among equal keys.  Never 0 for a token
+__device__ __forceinline__ ctl_u64 alt_pack(uint32_t key, int v) { return ((ctl_u64)key << 32) | (ctl_u64)(0xffffffffu - (uint32_t)v); }
+__device__ __forceinline__ int alt_index(ctl_u64 pk) { return (int)(0xffffffffu - (uint32_t)pk); }
+// E += w * d: one fp32 product, one fp32 addition
+__device__ __forceinline__ float alt_acc(float e, float w, float d) {
+#pragma clang fp contract(off)
+    const float t = w * d;
+    return e + t;
+}
+struct AltLds {
+    ctl_u64 top[2][4];             // a round's wave maxima, double buffered: one barrier per round
+    ctl_u64 ck;                    // the packed place of the row's code (0: a code outside [0, V))
+    float d[SAMPLE_ALT_MAX];       // d_j of the alternatives, stored by their owners
+    int code[SAMPLE_ALT_MAX];      // their indices, -1 beyond the allowed tokens
+    float sa[256], se[256];        // chunk sums of w and of w * d over all tokens
+    float tot[2];                  // S_all, E
+    int rank;
+};
+
+// ALT: the rank of the row's code and the four stores; two barriers, reached by a forced workgroup and an unforced one alike.  logit: the
+// body's own accessor of l''
+template <class L>
+__device__ __forceinline__ void alt_finish(const SampleAltParams *ap, AltLds *al, long long code, int b, int v0, int v1, int n, const L &logit) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (code >= (long long)v0 && code < (long long)v1) {   // the owner of the code's index (a code outside [0, V) has none)
+#pragma unroll 8
+        for (int k = 0; k < n; ++k)
+            if ((long long)(v0 + k) == code) al->ck = alt_pack(ctl_key(logit(k)), v0 + k);
+    }
+    __syncthreads();
+    const ctl_u64 ck = al->ck;
+    if (ck) {   // workgroup-uniform
+        int cnt = 0;
+#pragma unroll 8
+        for (int k = 0; k < n; ++k) cnt += alt_pack(ctl_key(logit(k)), v0 + k) > ck ? 1 : 0;   // all V tokens, banned ones included
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+        if (lane == 0) atomicAdd(&al->rank, cnt);
+    }
+    __syncthreads();
+    const long e = (long)b * ap->stride;
+    const float S_all = al->tot[0];
+    if (tid < ap->n) {
+        const int c = al->code[tid];
+        ap->codes[e * ap->n + tid] = c;
+        ap->logprob[e * ap->n + tid] = c >= 0 ? (float)((double)al->d[tid] - log((double)S_all)) : (float)log(0.0);
+    }
+    if (tid == 64) ap->entropy[e] = (float)(log((double)S_all) - (double)al->tot[1] / (double)S_all);
+    if (tid == 65) ap->rank[e] = ck ? al->rank : -1;
+}
+// the chunk's sums of w and of w * d over all tokens: no member, no register without ALT
+template <bool ON> struct AltSums { float s = 0.f, e = 0.f; };
+template <> struct AltSums<false> {};
+
 // The body of the eight samplers with controls.  Flags:
 //   FAST   V = 2048 on 16-byte aligned rows (the launchers decide): every thread owns 8 logits, held in registers from two 16-byte loads
 //   LP     also write the log-probability of the row's code under the distribution it was drawn from (cp.logprob; talkshow_hip.h,
@@ -1453,15 +1508,25 @@ __device__ __forceinline__ float sample_logprob_value(float d, float S, bool kep
 //          slot's token, code, kept bytes and log-probability is made to slot g's entries as well; the ring read and written is the
 //          slot's own.  -1: the arithmetic of the kernel without GUIDE, operation for operation.  GUIDE = false compiles to what the
 //          body was before the flag existed.  Instantiated with BIAS = REP = true only.
-// Inlined into its __global__ entries (eight without BIAS, eight with, eight with BIAS and REP, eight with GUIDE); DESIGN.md §5 ("One body per sampler
+//   ALT    "alternatives" (talkshow_hip.h): the row's n best allowed tokens with their log-probabilities, its entropy and the rank of its
+//          code, all under the distribution of steps 1 and 2 (ahead of top-k and top-p), in the same launch.  The n best: n rounds of a
+//          workgroup maximum over the tokens' packed places (alt_pack), each round over the tokens behind the round before it, so nothing
+//          is marked as taken; a round's owner stores its d_j.  S_all and E: a second and a third chunk sum beside step 5's, added left to
+//          right by one thread of wave 1 and one of wave 2 while thread 0 forms step 5's prefix sums.  The rank: the code's owner
+//          publishes its packed place, every thread counts its tokens ahead of it, one integer LDS atomic per wave.  A forced workgroup
+//          writes all four too.  Nothing here feeds the draw: idx and logprob are the bits of the kernel without ALT.  ALT = false
+//          compiles to what the body was before the flag existed.  Instantiated with BIAS = REP = LP = true, GUIDE = false only.
+// Inlined into its __global__ entries (eight without BIAS, eight with, eight with BIAS and REP, eight with GUIDE, four with ALT); DESIGN.md §5 ("One body per sampler
 // family") records what was compared against the two separate kernel templates it replaces.
-template <bool FAST, bool LP, bool GIVEN, bool BIAS = false, bool REP = false, bool GUIDE = false>
+template <bool FAST, bool LP, bool GIVEN, bool BIAS = false, bool REP = false, bool GUIDE = false, bool ALT = false>
 __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const int *rows, const int64_t *given, long given_stride,
                                                 const unsigned char *keep, long keep_stride, float *sf, int *si, float &s_thr, int &s_last,
-                                                uint32_t *s_tie, ctl_u64 (*hist)[256], int *s_rep = nullptr) {
+                                                uint32_t *s_tie, ctl_u64 (*hist)[256], int *s_rep = nullptr,
+                                                const SampleAltParams *ap = nullptr, AltLds *al = nullptr) {
     const SampleParams &p = cp.s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     static_assert(!GUIDE || (BIAS && REP), "the guided samplers imply the bias and repetition arithmetic");
+    static_assert(!ALT || (BIAS && REP && LP && !GUIDE), "alternatives run on the most general unguided family");
     [[maybe_unused]] int gslot = -1;        // GUIDE: the shadow's slot of a primary, -1 for a plain slot
     [[maybe_unused]] float gscale = 0.f;
     if constexpr (GUIDE) {
@@ -1715,10 +1780,40 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
         jp0 = (int)(ex >> 16);
     }
 
+    // ---- ALT: the n best allowed tokens of step 2's ranking, one workgroup maximum per round ----
+    if constexpr (ALT) {
+        if (tid == 0) { al->ck = 0; al->rank = 0; }   // read behind later barriers only
+        ctl_u64 prev = ~0ull;                         // the place taken by the round before: this round looks behind it
+        for (int j = 0; j < ap->n; ++j) {             // workgroup-uniform
+            ctl_u64 mb = 0;
+            float ml = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < n; ++k) {
+                const float l = logit(k);
+                const ctl_u64 pk = alt_pack(ctl_key(l), v0 + k);
+                if (l != -INFINITY && pk < prev && pk > mb) { mb = pk; ml = l; }
+            }
+            ctl_u64 wb = mb;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const ctl_u64 o = __shfl_xor(wb, off);
+                wb = o > wb ? o : wb;
+            }
+            if (lane == 0) al->top[j & 1][wave] = wb;
+            __syncthreads();
+            ctl_u64 win = al->top[j & 1][0];
+            for (int w = 1; w < 4; ++w) win = al->top[j & 1][w] > win ? al->top[j & 1][w] : win;
+            if (tid == 0) al->code[j] = win ? alt_index(win) : -1;   // 0: fewer allowed tokens than n
+            if (win && mb == win) al->d[j] = ctl_arg(ml, best, inv_t);   // the owner: a place holds its index, so there is one
+            prev = win;
+        }
+    }
+
     // ---- step 5: the plain body's inverse CDF over w' = kept ? w : 0 (adding a zero changes no bit, so dropped tokens are skipped);
     //      the owner of a given code notes its logit and whether it was kept ----
     float s = 0.f;
     int hi = -1;   // highest kept index of the chunk
+    [[maybe_unused]] AltSums<ALT> asum;
     bool gkept = false;
     float glc = 0.f;
     {
@@ -1740,13 +1835,31 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
             if constexpr (GIVEN && LP) {
                 if ((long long)(v0 + k) == gcode) { gkept = kp; glc = logit(k); }
             }
+            if constexpr (ALT) {   // every token with l'' above -inf, whatever the filters keep
+                const float l = logit(k);
+                if (l != -INFINITY) {
+                    const float d = ctl_arg(l, best, inv_t);
+                    const float w = det_expf(d);
+                    asum.s += w;
+                    if (w > 0.f) asum.e = alt_acc(asum.e, w, d);
+                }
+            }
         }
     }
     sf[tid + 1] = s;
     si[tid] = hi;
+    if constexpr (ALT) { al->sa[tid] = asum.s; al->se[tid] = asum.e; }
     __syncthreads();
     if (tid == 0) {
         s_thr = u * sample_prefix_sum<true>(sf, si, &s_last);   // s_last: the highest kept index of the row (rank 0 is always kept)
+    }
+    if constexpr (ALT) {   // the chunk sums left to right, beside thread 0's
+        if (tid == 64 || tid == 128) {
+            const float *src = tid == 64 ? al->sa : al->se;
+            float c = 0.f;
+            for (int t = 0; t < 256; ++t) c += src[t];
+            al->tot[tid == 64 ? 0 : 1] = c;
+        }
     }
     __syncthreads();
     if constexpr (GIVEN && LP) {
@@ -1772,6 +1885,7 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
                     if (ring) ring[rep_slot] = given_token(gcode, p.V);
                 }
             }
+            if constexpr (ALT) alt_finish(ap, al, gcode, b, v0, v1, n, logit);
             return;
         }
     }
@@ -1822,6 +1936,7 @@ __device__ __forceinline__ void sample_ctl_body(const SampleCtlParams &cp, const
             }
         }
     }
+    if constexpr (ALT) alt_finish(ap, al, (long long)si[0], b, v0, v1, n, logit);
 }
 
 template <bool FAST, bool LP>
@@ -1916,6 +2031,51 @@ __global__ __launch_bounds__(256) void sample_ctl_guide_given_kernel(const Sampl
     sample_ctl_body<FAST, LP, true, true, true, true>(gp.c, gp.rows, gp.given, gp.given_stride, gp.keep, gp.keep_stride, sf, si, s_thr, s_last, s_tie,
                                                       hist, s_rep);
 }
+// "alternatives": the family with BIAS = REP = LP = true once more with ALT = true, launched only for a run that asks for alternatives.
+// A run without records brings records of window 0, one without tables an index of -1 everywhere, one without a table neutral records
+template <bool FAST>
+__global__ __launch_bounds__(256) void sample_ctl_alt_kernel(const SampleAltParams ap) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ int s_rep[SAMPLE_REP_RING];
+    __shared__ AltLds al;
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, true, false, true, true, false, true>(ap.g.c, nullptr, nullptr, 0, nullptr, 0, sf, si, s_thr, s_last, s_tie, hist, s_rep, &ap,
+                                                                &al);
+}
+template <bool FAST>
+__global__ __launch_bounds__(256) void sample_ctl_alt_given_kernel(const SampleAltParams ap) {
+    __shared__ float sf[256 + 1];
+    __shared__ int si[256];
+    __shared__ float s_thr;
+    __shared__ int s_last;
+    __shared__ uint32_t s_tie[4];
+    __shared__ int s_rep[SAMPLE_REP_RING];
+    __shared__ AltLds al;
+    __shared__ __attribute__((aligned(16))) ctl_u64 hist[7][256];
+    sample_ctl_body<FAST, true, true, true, true, false, true>(ap.g.c, ap.g.rows, ap.g.given, ap.g.given_stride, ap.g.keep, ap.g.keep_stride, sf, si,
+                                                               s_thr, s_last, s_tie, hist, s_rep, &ap, &al);
+}
+// rows at or beyond a clip's own H_b: -1, 0, 0, -1 (one thread per position; beside mask_logprob_kernel)
+__global__ void mask_alt_kernel(int32_t *codes, float *logprob, float *entropy, int32_t *rank, int n, int B, int H, const int *__restrict__ lens) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * H * 2) return;
+    const int b = (int)(i / ((long)H * 2)), r = (int)((i / 2) % H);
+    if (r < (lens[b] >> 2)) return;
+    for (int j = 0; j < n; ++j) { codes[i * n + j] = -1; logprob[i * n + j] = 0.f; }
+    entropy[i] = 0.f;
+    rank[i] = -1;
+}
+hipError_t launch_mask_alt(int32_t *codes, float *logprob, float *entropy, int32_t *rank, int n, int B, int H, const int *lens, hipStream_t stream) {
+    if (!entropy || !rank || !lens || B < 1 || H < 1 || n < 0 || n > SAMPLE_ALT_MAX || (n > 0 && (!codes || !logprob))) return hipErrorInvalidValue;
+    const long total = (long)B * H * 2;
+    hipLaunchKernelGGL(mask_alt_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, codes, logprob, entropy, rank, n, B, H, lens);
+    return hipGetLastError();
+}
+
 // what a launch with tables needs beyond its sibling's checks; the vector path also needs 16-byte aligned table rows (V = 2048: every row
 // of an aligned block is)
 static bool sample_bias_ok(const SampleCtlParams &p) { return p.ctl && p.bias_index && (p.bias_col == 0 || p.bias_col == 1); }
@@ -2038,6 +2198,25 @@ hipError_t launch_sample_given(const SampleGivenParams &p, hipStream_t stream) {
         hipLaunchKernelGGL((sample_ctl_given_kernel<true, false>), dim3(s.B), dim3(256), 0, stream, p);
     } else {
         hipLaunchKernelGGL((sample_ctl_given_kernel<false, false>), dim3(s.B), dim3(256), 0, stream, p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_alt(const SampleAltParams &p, hipStream_t stream) {
+    const SampleCtlParams &c = p.g.c;
+    const SampleParams &s = c.s;
+    if (s.V < 1 || s.V > SAMPLE_CTL_MAX_V || (s.mode != TS_SAMPLE_UNIFORMS && s.mode != TS_SAMPLE_PHILOX)) return hipErrorInvalidValue;
+    if (!c.logprob || !c.rep || c.guide_role || !sample_rep_ok(c)) return hipErrorInvalidValue;
+    if (p.n < 0 || p.n > SAMPLE_ALT_MAX || !p.entropy || !p.rank || (p.n > 0 && (!p.codes || !p.logprob))) return hipErrorInvalidValue;
+    if (p.g.rows && !p.g.given) return hipErrorInvalidValue;
+    const long ls = s.logit_stride ? s.logit_stride : (long)s.V;
+    const bool fast = s.V == 2048 && (ls & 3) == 0 && (reinterpret_cast<uintptr_t>(s.logits) & 15) == 0 && sample_bias_fast(c);
+    if (p.g.rows) {
+        if (fast) hipLaunchKernelGGL((sample_ctl_alt_given_kernel<true>), dim3(s.B), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((sample_ctl_alt_given_kernel<false>), dim3(s.B), dim3(256), 0, stream, p);
+    } else {
+        if (fast) hipLaunchKernelGGL((sample_ctl_alt_kernel<true>), dim3(s.B), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((sample_ctl_alt_kernel<false>), dim3(s.B), dim3(256), 0, stream, p);
     }
     return hipGetLastError();
 }

@@ -342,7 +342,7 @@ class GatedPixelCNN(NativeModule):
 
     def run(self, label, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, codes=None, uniforms=None, seed=0, clip_index0=0,
             want_logits=False, pre_codes=None, pre_aud=None, shape=None, sampling=None, logprobs=False, given=None, given_keep=None,
-            style=None, code_bias=None, repeat=None, guide=None):
+            style=None, code_bias=None, repeat=None, guide=None, alternatives=None):
         """aud_rows (B,H,aud_dim) device (None for audio=False: pass shape=(B,H)); returns (codes (B,H,W) int64, logits
         (B,H,W,V) or None); W = 2 unless bh_model=False and shape=(B,H,W) says otherwise.  sampling: one sampling record
         (`_lib.sampling_record`: temperature, top_p, top_k) for all clips or one per clip (`ts_pixelcnn_generate_ctl`); the logits returned
@@ -390,7 +390,22 @@ class GatedPixelCNN(NativeModule):
         distributions, 0 the call without the keyword.  The shadows are dropped from what is returned.  TS_SAMPLE_UNIFORMS /
         TS_SAMPLE_PHILOX only.  Goes through the mixed entry with equal lengths (`ts_pixelcnn_generate_guided`): not with want_logits
         or pre_codes.  ValueError naming the clip for a wrong key, shape or scale, before any device work.  None (the default): no return
-        value and no launch changes."""
+        value and no launch changes.
+        alternatives: n in [0, 8] -> one more return value behind the log-probabilities (where those are asked for), a
+        `sampling.Alternatives` (talkshow_hip.h, "alternatives"): codes int64 (B,H,2,n) and logprobs float32 (B,H,2,n) of the n likeliest
+        allowed codes of every position, entropy float32 (B,H,2) and rank int64 (B,H,2) of the position's own code — drawn, given or kept —
+        all under the distribution the filters are applied to (code bias, repetition penalty and temperature applied; top-k and top-p
+        not), written by the sampler launch itself.  Codes and log-probabilities are those of the call without the keyword, bit for bit.
+        TS_SAMPLE_UNIFORMS / TS_SAMPLE_PHILOX only (ValueError: a greedy decode with alternatives is sampling=(1, 1, 1) under Philox); not
+        with guide (NotImplementedError).  Goes through the mixed entry with equal lengths (`ts_pixelcnn_generate_alt`): not with
+        want_logits or pre_codes.  None (the default): no return value and no launch changes."""
+        guided = guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide))
+        an = _lib.alt_request(alternatives, mode, "run", guide=guided)      # ValueError / NotImplementedError before any device work
+        if an is not None:
+            if not self.bh_model:
+                raise NotImplementedError("alternatives exist for the bh_model=True chain (ts_pixelcnn_generate_alt), not for the single-stack form")
+            if want_logits or pre_codes is not None:
+                raise ValueError("run: alternatives go through the mixed entry, which takes no logits output and no pre_codes")
         if guide is not None and not (isinstance(guide, (list, tuple)) and all(e is None for e in guide)):      # a list of None only is no guidance
             if not self.bh_model:
                 raise NotImplementedError("guidance exists for the bh_model=True chain (ts_pixelcnn_generate_guided), not for the single-stack form")
@@ -490,13 +505,15 @@ class GatedPixelCNN(NativeModule):
             return self._run_guided(label, aud_rows, mode, uniforms, seed, clip_index0, lp, ctl, n_ctl, block if given is not None else None,
                                     table if given is not None else None, kblock if given is not None else None, sblock, btab, bidx, rtab,
                                     n_rep, gent, src, shadow, gtab, gscale)
-        if given is not None or sblock is not None or btab is not None or rtab is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
+        if given is not None or sblock is not None or btab is not None or rtab is not None or an is not None:   # the mixed entry with equal lengths; clip b keeps Philox subsequence clip_index0 + b
             i32p = C.POINTER(C.c_int32)
             lens = np.full(B, 4 * H, np.int32)
             lens_dev = upload(lens, dev)
             clip_index = upload(np.arange(B, dtype=np.int64) + int(clip_index0), dev)
             if isinstance(lp, str):
                 lp = torch.empty((B, H, 2), dtype=torch.float32, device=dev)
+            areq = None if an is None else _lib.AltRequest(an, (B, H, 2), dev)
+            lp_dev = lp if lp is not None or areq is None else torch.empty((B, H, 2), dtype=torch.float32, device=dev)   # the record needs one beside it
             fixed = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), lens.ctypes.data_as(i32p), _lib.dptr(lens_dev), B, H, mode,
                      _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), _lib.dptr(clip_index), _lib.dptr(codes))
             block_dev = upload(block, dev) if given is not None else None
@@ -504,11 +521,12 @@ class GatedPixelCNN(NativeModule):
             style_dev = upload(sblock, dev) if sblock is not None else None
             bias_dev = upload(btab, dev) if btab is not None else None
             _lib.pixelcnn_mixed_call(
-                fixed, ctl=ctl, n_ctl=n_ctl, logprob=_lib.dptr(lp), given=_lib.dptr(block_dev), given_rows=table.ctypes.data_as(i32p) if given is not None else None,
+                fixed, ctl=ctl, n_ctl=n_ctl, logprob=_lib.dptr(lp_dev), given=_lib.dptr(block_dev), given_rows=table.ctypes.data_as(i32p) if given is not None else None,
                 keep=_lib.dptr(keep_dev), style=_lib.dptr(style_dev), style_rows=int(sblock.shape[1]) if sblock is not None else 0,
                 bias=_lib.dptr(bias_dev), n_bias=int(btab.shape[0]) if btab is not None else 0, bias_index=bidx.ctypes.data_as(i32p) if btab is not None else None,
-                rep=rtab, n_rep=n_rep)
-            return (codes, None) if lp is None else (codes, None, lp)
+                rep=rtab, n_rep=n_rep, alt=None if areq is None else areq.ptr())
+            out = (codes, None) if lp is None else (codes, None, lp)
+            return out if areq is None else out + (areq.result(),)
         args = (self.handle(), _lib.dptr(label), _lib.dptr(aud_rows), B, H, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1),
                 int(clip_index0), _lib.dptr(codes), _lib.dptr(logits), _lib.dptr(pre_codes), _lib.dptr(pre_aud), H0)
         if lp is not None:
@@ -612,17 +630,19 @@ class GatedPixelCNN(NativeModule):
         """hipGraphs captured so far on the current stream (a serving loop checks that this stands still once it is warm)."""
         return int(_lib.load().ts_pixelcnn_graph_captures(self.handle(), _lib.stream_ptr())) if self.bh_model else 0
 
-    def open_stream(self, label, batch_size, max_chunk_rows, *, sampling=None, style=None, code_bias=None, repeat=None, pairs=None):
+    def open_stream(self, label, batch_size, max_chunk_rows, *, sampling=None, style=None, code_bias=None, repeat=None, pairs=None,
+                    alternatives=None):
         """A generation session with a persistent row cache (`ts_pixelcnn_stream_*`): `.step(aud_rows)` continues the
         clip(s) where the previous step stopped, at a cost independent of the history length.  sampling / style / code_bias / repeat:
         session DEFAULTS in the forms `PixelCNNStream.step` takes; a step that passes no value for a keyword runs under the default, any
         value it does pass takes its place for that step.  pairs: GUIDANCE at slot level (talkshow_hip.h, "session pairs"):
         {primary: shadow} (stored scale 1) or {primary: (shadow, scale)} — slot `shadow` runs the primary's code history under its own label
-        and audio rows and draws nothing; the primary is decoded as `run(..., guide=)` decodes it (`PixelCNNStream.step`)."""
+        and audio rows and draws nothing; the primary is decoded as `run(..., guide=)` decodes it (`PixelCNNStream.step`).  alternatives: the
+        session default of `step(alternatives=)`; not with pairs."""
         if not (self.audio and self.bh_model):
             raise NotImplementedError("streaming sessions exist for the shipped configuration (audio=True, bh_model=True)")
         return PixelCNNStream(self, label, batch_size, max_chunk_rows, sampling=sampling, style=style, code_bias=code_bias, repeat=repeat,
-                              pairs=pairs)
+                              pairs=pairs, alternatives=alternatives)
 
     @staticmethod
     def _audio_rows(aud):
@@ -645,12 +665,13 @@ class GatedPixelCNN(NativeModule):
 
     # --- reference call shapes ---
     def generate(self, label, shape=(8, 8), batch_size=64, aud_feat=None, pre_latents=None, pre_audio=None,
-                 mode=None, seed=None, uniforms=None, sampling=None, logprobs=False):
+                 mode=None, seed=None, uniforms=None, sampling=None, logprobs=False, alternatives=None):
         """`GatedPixelCNN.generate` (`gated_pixelcnn_v2.py:152-177`): aud_feat (B,aud_dim,H,2) -> codes (B,H,2).
 
         Default is stochastic like the reference (softmax + one multinomial draw per position), with Philox uniforms
         seeded from torch's default generator; `mode=TS_SAMPLE_GREEDY` gives the argmax harness.  `sampling`: as for `run`.
         `logprobs=True` (or an output tensor): returns (codes, logprobs (B,H,2) float32) instead of codes.
+        `alternatives=n`: as for `run`; a `sampling.Alternatives` is appended to what is returned.
         """
         rows = self._audio_rows(aud_feat)
         pre_rows = self._audio_rows(pre_audio)
@@ -659,7 +680,9 @@ class GatedPixelCNN(NativeModule):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if mode == _lib.TS_SAMPLE_PHILOX else 0
         out = self.run(label, rows, mode=mode, uniforms=uniforms, seed=seed, pre_codes=pre_latents, pre_aud=pre_rows,
-                       shape=(batch_size, shape[0], shape[1]), sampling=sampling, logprobs=logprobs)
+                       shape=(batch_size, shape[0], shape[1]), sampling=sampling, logprobs=logprobs, alternatives=alternatives)
+        if alternatives is not None:
+            return (out[0],) + tuple(out[2:])
         return out[0] if len(out) == 2 else (out[0], out[2])
 
     def __call__(self, x, label, aud=None):
@@ -703,8 +726,14 @@ def step_pieces(net, B, labels, defaults, Hc, mode, dev, sampling, logprobs, giv
 class PixelCNNStream:
     """Host handle of `ts_pixelcnn_stream`: label (B,) or (1,) int64 fixed for the session."""
 
-    def __init__(self, net, label, batch_size, max_chunk_rows, sampling=None, style=None, code_bias=None, repeat=None, pairs=None):
+    def __init__(self, net, label, batch_size, max_chunk_rows, sampling=None, style=None, code_bias=None, repeat=None, pairs=None,
+                 alternatives=None):
         from talkshow_amd.streaming import SlotPairs
+        from talkshow_amd import sampling as _sampling
+        if alternatives is not None:
+            _sampling.alt_count(alternatives)      # ValueError before the session exists
+            if pairs:
+                raise NotImplementedError("open_stream: alternatives are not offered on a session with pairs")
         dev = net._dev()
         label = _index_tensor(label, net.n_classes, "class label", dev)
         if label.numel() == 1 and batch_size > 1:
@@ -712,7 +741,7 @@ class PixelCNNStream:
         if label.numel() != batch_size:
             raise ValueError(f"label must hold 1 or B={batch_size} class indices, got {label.numel()}")
         self.net, self.B, self.max_rows = net, int(batch_size), int(max_chunk_rows)
-        self.defaults = {"sampling": sampling, "style": style, "code_bias": code_bias, "repeat": repeat}
+        self.defaults = {"sampling": sampling, "style": style, "code_bias": code_bias, "repeat": repeat, "alternatives": alternatives}
         self._labels = label.detach().cpu().numpy()      # what `style=[None, ...]` stands for: the clip's own label
         self._pairs = SlotPairs(self.B)
         declared = None
@@ -768,7 +797,7 @@ class PixelCNNStream:
         return step_pieces(self.net, self.B, self._labels, self.defaults, Hc, mode, dev, sampling, logprobs, given, style, code_bias, repeat)
 
     def step(self, aud_rows, mode=_lib.TS_SAMPLE_PHILOX, uniforms=None, seed=0, clip_index0=0, *, sampling=None, logprobs=False, given=None,
-             style=None, code_bias=None, repeat=None, guide=None):
+             style=None, code_bias=None, repeat=None, guide=None, alternatives=None):
         """aud_rows (B,Hc,aud_dim) device -> codes (B,Hc,2) int64 of the next Hc code rows.
         The keywords take the forms `GatedPixelCNN.run` takes and follow its rules FOR THIS STEP (`ts_pixelcnn_stream_step_ctl`;
         talkshow_hip.h, "streaming sessions"); sampling / style / code_bias / repeat left at None run under the session's default
@@ -784,11 +813,18 @@ class PixelCNNStream:
         slot that is no primary, a NaN, an infinity or |scale| > 1e4 raises ValueError naming the slot.  A session with pairs runs every
         step under them: a primary's codes and log-probabilities are those of `run(..., guide=)` on the pair alone, a shadow's rows of
         what is returned are its primary's, and a shadow's entries of sampling / given / code_bias / repeat are never read.  Greedy mode
-        is refused with pairs (`top_k = 1` is the greedy guided decode).  A session without pairs takes no `guide` and runs as ever."""
+        is refused with pairs (`top_k = 1` is the greedy guided decode).  A session without pairs takes no `guide` and runs as ever.
+        alternatives: n in [0, 8] (None: the session's default, `open_stream(alternatives=)`) -> a `sampling.Alternatives` over this step's
+        (B,Hc,2) positions is appended to what is returned, as for `run` (`ts_pixelcnn_stream_step_alt`; talkshow_hip.h, "alternatives").
+        Drawing modes only (ValueError); not on a session with pairs (NotImplementedError)."""
         B, Hc = int(aud_rows.shape[0]), int(aud_rows.shape[1])
         if B != self.B:
             raise ValueError(f"session was opened for B={self.B}, got {B}")
         dev = self.net._dev()
+        if alternatives is None:
+            alternatives = self.defaults.get("alternatives")
+        ptab = self._pair_table(make=False)
+        an = _lib.alt_request(alternatives, mode, "step", guide=guide is not None or (ptab is not None and any(g >= 0 for g in ptab.guide)))
         scales = None if guide is None else self._pair_table().step_scales(guide)      # None: the library runs the stored scales
         lp, ctl, n_ctl, btab, bidx, rtab, n_rep, block, table, srows = self._pieces(Hc, mode, dev, sampling, logprobs, given, style, code_bias,
                                                                                    repeat)
@@ -799,7 +835,7 @@ class PixelCNNStream:
         if uniforms is not None:
             uniforms = _dev_f32(uniforms, dev)
         args = (self._h, _lib.dptr(aud_rows), Hc, mode, _lib.dptr(uniforms), int(seed) & (2 ** 64 - 1), int(clip_index0), _lib.dptr(codes))
-        if lp is None and ctl is None and btab is None and rtab is None and block is None and srows is None and scales is None:
+        if lp is None and ctl is None and btab is None and rtab is None and block is None and srows is None and scales is None and an is None:
             _lib.check(_lib.load().ts_pixelcnn_stream_step(*args, _lib.stream_ptr()))
             return codes
         if isinstance(lp, str):
@@ -808,9 +844,14 @@ class PixelCNNStream:
         block_dev = upload(block, dev) if block is not None else None
         style_dev = upload(srows, dev) if srows is not None else None
         bias_dev = upload(btab, dev) if btab is not None else None
-        pieces = (ctl, n_ctl, _lib.dptr(lp), _lib.dptr(block_dev), table.ctypes.data_as(i32p) if block is not None else None,
+        areq = None if an is None else _lib.AltRequest(an, (B, Hc, 2), dev)
+        lp_dev = lp if lp is not None or areq is None else torch.empty((B, Hc, 2), dtype=torch.float32, device=dev)   # the record needs one beside it
+        pieces = (ctl, n_ctl, _lib.dptr(lp_dev), _lib.dptr(block_dev), table.ctypes.data_as(i32p) if block is not None else None,
                   _lib.dptr(style_dev), _lib.dptr(bias_dev), int(btab.shape[0]) if btab is not None else 0,
                   bidx.ctypes.data_as(i32p) if btab is not None else None, rtab, n_rep)
+        if areq is not None:      # the entry with the record is named only when the keyword is given
+            _lib.check(_lib.load().ts_pixelcnn_stream_step_alt(*args, *pieces, areq.ptr(), _lib.stream_ptr()))
+            return (codes, areq.result()) if lp is None else (codes, lp, areq.result())
         if scales is None:
             _lib.check(_lib.load().ts_pixelcnn_stream_step_ctl(*args, *pieces, _lib.stream_ptr()))
         else:

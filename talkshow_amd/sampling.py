@@ -1,12 +1,15 @@
 """Numpy twin of the sampler with per-clip controls (`csrc/vq.hip::sample_ctl_kernel`; the rule: `include/talkshow_hip.h`, ts_sampling,
 steps 1-5, "code bias": step 0 and the kept-set sentence, `biased` / `keep_mask_bias` / `sample_bias` below, and "repetition penalty":
 step 0b, `repeat_counts` / `penalised` / `sample_repeat` / `decode_repeat` below, and "guidance": the rule ahead of step 0 and the host check,
-`guided` / `guide_roles` / `sample_guide` below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
+`guided` / `guide_roles` / `sample_guide` below, and "alternatives": `alternatives` / `alternatives_error_bound` / `uncertain_keep`
+below).  Pure host code, the device's arithmetic operation for operation: `keep_mask` and `sample_ctl` return what the device returns,
 bit for bit, so tests compare indices and kept sets for equality.  A record is (temperature, top_p, top_k), `_lib.sampling_record`'s form.
 
 The kept set is written here from its DEFINITION (sort the row, cumulative integer masses in rank order); the kernel finds the same set by
 radix select.  Both use the same integers, and integer sums do not depend on the order they are taken in.
 """
+import collections
+
 import numpy as np
 
 F32 = np.float32
@@ -177,6 +180,101 @@ def given_logprob(row, code, record=None):
         with np.errstate(divide="ignore"):
             return F32(np.log(np.float64(0.0)))
     return logprob(row, code, record)
+
+
+# ---- alternatives (include/talkshow_hip.h, "alternatives"; csrc/vq.hip: sample_ctl_body<..., ALT = true>) -----------------------------------
+
+ALT_MAX = 8
+
+Alternatives = collections.namedtuple("Alternatives", "codes logprobs entropy rank")
+Alternatives.__doc__ = """What `alternatives=n` appends to a decode's return value: codes int64 (..., n) the n best allowed codes of every
+position (-1 beyond the allowed ones), logprobs float32 (..., n) their log-probabilities (-inf there), entropy float32 (...) of the
+position's distribution, rank int64 (...) of the position's own code (-1 for a given code outside the vocabulary) — all under the
+distribution the filters are applied to (temperature applied, top-k and top-p not)."""
+
+
+def alt_count(n):
+    """The `alternatives=` keyword as an integer in [0, 8]; ValueError otherwise (a bool is no count)."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise ValueError(f"alternatives must be None or an integer in [0, {ALT_MAX}], got {n!r}")
+    if not 0 <= int(n) <= ALT_MAX:
+        raise ValueError(f"alternatives must be in [0, {ALT_MAX}], got {int(n)}")
+    return int(n)
+
+
+def alternatives(row, record, n, bias=None, counts=None, rep=None, code=None):
+    """The rule of "alternatives" for ONE position, the device's arithmetic operation for operation: row (V,) the network's logits, record
+    (temperature, top_p, top_k) or None (neutral; top_p and top_k are not used: the outputs describe the distribution ahead of the
+    filters), n in [0, 8], bias the clip's (V,) row of this column or None (step 0), counts (V,) and rep = (window, presence, frequency)
+    the history counts and record of step 0b (`repeat_counts`; None or window 0: no penalty), code the position's own code or None ->
+    Alternatives(codes (n,) int64, logprobs (n,) float32, entropy float32, rank int: -1 for a code outside [0, V) and for code None).
+    S_all, E and every d_j equal the device's bit for bit; the two fp64 logs may differ from the device's in their last place, so a
+    log-probability and the entropy are the device's value or an adjacent float32."""
+    n = alt_count(n)
+    temperature = 1.0 if record is None else record[0]
+    l = biased(row, bias)
+    if counts is not None and rep is not None and int(rep[0]) > 0:
+        l = penalised(l, counts, rep)
+    V = l.size
+    m = l[int(np.argmax(l))]                                              # the first maximum, as the workgroup arg-max returns it
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = (l - m).astype(F32)
+        d = (d * inv_temperature(temperature)).astype(F32)
+        allowed = l != F32(-np.inf)
+        w = np.where(allowed, det_expf(d), F32(0.0)).astype(F32)
+        t = np.where(w > 0, (w * np.where(w > 0, d, F32(0.0))).astype(F32), F32(0.0)).astype(F32)    # one fp32 product where w > 0
+    S_all = chunk_total(w)
+    E = chunk_total(t)
+    log_s = np.log(np.float64(S_all))
+    order = ranking(l)
+    best = order[allowed[order]][:n]
+    codes = np.full(n, -1, np.int64)
+    lps = np.full(n, -np.inf, F32)
+    codes[:best.size] = best
+    lps[:best.size] = (d[best].astype(np.float64) - log_s).astype(F32)
+    entropy = F32(log_s - np.float64(E) / np.float64(S_all))
+    rank = -1
+    if code is not None and 0 <= int(code) < V:
+        rank = int(np.flatnonzero(order == int(code))[0])
+    return Alternatives(codes, lps, entropy, rank)
+
+
+def alternatives_error_bound(V, d, lp, entropy):
+    """Bounds on |alternatives(...) - exact| -> (bound for a log-probability with fp32 argument d and value lp, bound for the entropy),
+    exact = the float64 log-softmax / entropy of z_v = (l''_v - m) / T over the allowed tokens, DERIVED from the rule in the manner of
+    `logprob_error_bound`:
+      d_v            a subtraction, 1 / T and a product, each one fp32 rounding: d_v = z_v (1 + e), |e| <= 3 * 2^-24 (1 + small)
+      w_v            det_expf's relative error + that of its argument, |d_v| <= 86 for a non-zero weight: eps_w = DET_EXPF_REL_ERR + 86 * 3u;
+                     weights below e^-86 are dropped: at most V * e^-86 of S_all >= 1
+      S_all          at most chunk - 1 + 255 fp32 additions of non-negative terms, each relative 2^-24 of a partial sum <= S_all
+      log-prob       |d| * 3u + eps_S / (1 - eps_S) + the fp64 log and subtraction 2^-50 (1 + |lp|) + the rounding to fp32 |lp| * 2^-24
+      t_v            w_v * d_v: eps_w + 3u + one rounding; all terms are <= 0, so E carries eps_E = eps_w + 4u + (chunk - 1 + 255) u relative
+                     to |E|; a dropped term is at most 87 e^-86 in magnitude (|z| e^z falls beyond 86)
+      entropy        H = log S + A with A = -E / S >= 0, so A <= H: |dH| <= eps_S / (1 - eps_S) + H (eps_E + eps_S) + V * 87 e^-86 +
+                     the fp64 operations 4 * 2^-50 (1 + H) + the rounding to fp32 H * 2^-24."""
+    u = 2.0 ** -24
+    chunk = (int(V) + NTHREADS - 1) // NTHREADS
+    nadd = chunk - 1 + 255
+    eps_w = DET_EXPF_REL_ERR + 86 * 3 * u
+    eps_s = (nadd * u + eps_w) * 1.001 + V * np.exp(-86.0)
+    eps_e = (eps_w + 4 * u + nadd * u) * 1.001
+    lp_bound = abs(float(d)) * 3 * u * 1.001 + eps_s / (1 - eps_s) + 2.0 ** -50 * (1 + abs(float(lp))) + abs(float(lp)) * u
+    H = abs(float(entropy))
+    h_bound = eps_s / (1 - eps_s) + H * (eps_e + eps_s) * 1.001 + V * 87 * np.exp(-86.0) + 4 * 2.0 ** -50 * (1 + H) + H * u
+    return lp_bound, h_bound
+
+
+def uncertain_keep(entropy, threshold):
+    """A mask for `given_keep=`: entropy (G, 2) of a decode's positions (`Alternatives.entropy` of one clip; a tensor is read back) ->
+    (G, 2) bool, True where entropy <= threshold.  Handing the decode back through `given=` with this mask keeps what the model was sure
+    of and redraws the rest."""
+    e = np.asarray(entropy.detach().cpu().numpy() if hasattr(entropy, "detach") else entropy, np.float64)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError(f"uncertain_keep: entropy must be (G, 2), got {tuple(e.shape)}")
+    thr = float(threshold)
+    if np.isnan(thr):
+        raise ValueError("uncertain_keep: the threshold is NaN")
+    return e <= thr
 
 
 def style_rows(weights, table):
